@@ -11,9 +11,11 @@ torch.distributed.run (one process per GPU); under a launcher, WORLD_SIZE must e
 output is the size of the process group that actually ran, never the flag.
 
 Prints ONE JSON line (rank 0).  `value` = simulated seconds per wall second summed over every seed of
-every rank; seeds/s and executor-steps/s ride along in `extra`.  After the timed region (never inside it) the
-line gains `verified_seeds` (sampled seeds of the last batch on every stream compared bit-for-bit with the CPU
-oracle), a first-failing-seed measurement on the packet-loss variant, and the CPU baseline.
+every rank; seeds/s and executor-steps/s ride along in `extra`.  A plain run sets up, warms up, times exactly
+--steps steps (one region), writes the last step's outputs under --dump-outputs DIR when given, and prints the line.
+With --full, after the timed regions (never inside them) the line gains `verified_seeds` (sampled seeds of the last
+batch on every stream compared bit-for-bit with the CPU oracle), the first-failing-seed and campaign legs, the other
+workloads, the roofline with its live counter passes, and the CPU baseline.
 """
 import argparse
 import json
@@ -39,10 +41,16 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=1000)      # ~1.5 s timed at 1.46 ms per batch (65.5 M seeds)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--seeds", type=int, default=0, help="seeds per GPU per step (default 65 536)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: repeated timed regions, the oracle checks, the first-fail / campaign / "
+                         "run_batch legs, extra.workloads, the roofline (live rocprofv3 and tools/ubench_issue passes) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (per-seed results and the step's report) "
+                         "as float64 .npy files under DIR")
     ap.add_argument("--repeats", type=int, default=0,
                     help="timed regions of exactly --steps steps each, back to back, every one bracketed by barrier + synchronize; the "
                          "line's ms_per_step / value are those of the MEDIAN region, all of them are listed in extra.regions "
-                         "(default: 21 for short regions, fewer for long ones — about 2 000 steps in total, at least 3)")
+                         "(default: one; with --full 21 for short regions, fewer for long ones — about 2 000 steps in total, at least 3)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-verify", action="store_true", help="skip the oracle check of sampled seeds after the timed region")
     ap.add_argument("--no-first-fail", action="store_true", help="skip the first-failing-seed measurements (loss variants)")
@@ -54,7 +62,7 @@ def parse_args(argv=None):
                     help="packet_loss_rate of the very-rare-failure search: ~5e-6 of the seeds deadlock, i.e. one per ~3 batches")
     ap.add_argument("--measure-traffic", action="store_true", default=None,
                     help="collect FETCH_SIZE / WRITE_SIZE of this same command with two short rocprofv3 --pmc passes after the "
-                         "timed region (default at one GPU when rocprofv3 is on PATH; a few seconds)")
+                         "timed region (default with --full at one GPU when rocprofv3 is on PATH; a few seconds)")
     ap.add_argument("--no-measure-traffic", dest="measure_traffic", action="store_false")
     ap.add_argument("--loss", type=float, default=0.0, help="packet_loss_rate of the timed batches (0 = Config::default())")
     ap.add_argument("--first-fail-loss", type=float, default=0.01, help="packet_loss_rate of the first-fail leg (SURVEY 8d)")
@@ -91,8 +99,8 @@ def measure_counters(argv, passes=("TRACE", "FETCH_SIZE", "WRITE_SIZE", None), e
     exe = shutil.which("rocprofv3")
     if not exe:
         return None, "rocprofv3 not on PATH"
-    base = [a for a in argv if a != "--measure-traffic"] + ["--no-measure-traffic"]
-    for flag in ("--steps", "--warmup", "--workload"):
+    base = [a for a in argv if a != "--measure-traffic" and not a.startswith("--dump-outputs=")] + ["--no-measure-traffic"]
+    for flag in ("--steps", "--warmup", "--workload", "--dump-outputs"):
         if flag in base:
             k = base.index(flag)
             del base[k:k + 2]
@@ -165,6 +173,35 @@ def issue_ceiling():
         j["source"] = "profiles/r3_issue_ceiling.json (tools/ubench_issue on an MI355X, not this run)"
         return j
     return None
+
+
+DUMP_MAX_SEEDS = 1 << 19      # 13 float64 per seed: at most 52 MiB of per-seed results over all ranks, a fixed sample beyond
+
+
+def dump_outputs(out_dir, results, report, suffix="", max_seeds=DUMP_MAX_SEEDS):
+    """--dump-outputs: one batch as its caller receives it — the per-seed madsim_result_t array and the batch's summary
+    (first_failing_seed, n_failed, total_steps, total_clock_ns) — as float64 .npy files, exact: every 64-bit field is split into its
+    low and high 32-bit halves (<name>_lo / <name>_hi).  seed_offset.npy holds each row's seed relative to the batch's first seed
+    (all of them, or a fixed sample of max_seeds)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    idx = np.arange(len(results))
+    if len(idx) > max_seeds:
+        idx = np.sort(np.random.default_rng(0).choice(len(results), max_seeds, replace=False))
+    arrays = {"seed_offset": idx.astype(np.float64)}
+    sample = results[idx]
+    for name in results.dtype.names:
+        col = sample[name]
+        if col.dtype.itemsize == 8:
+            arrays[name + "_lo"] = (col & np.uint64(0xFFFFFFFF)).astype(np.float64)
+            arrays[name + "_hi"] = (col >> np.uint64(32)).astype(np.float64)
+        else:
+            arrays[name] = col.astype(np.float64)
+    rep = np.asarray(report, dtype=np.uint64)
+    arrays["report_lo"] = (rep & np.uint64(0xFFFFFFFF)).astype(np.float64)
+    arrays["report_hi"] = (rep >> np.uint64(32)).astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
 
 
 def main():
@@ -262,7 +299,7 @@ def main():
     # Fully asynchronous steps: the simulation kernel, the summary reduction and (N > 1) the RCCL all-gather of the
     # report are all queued on streams; the host never waits inside the timed region.
     use_device_report = world == 1 or backend == "nccl"
-    repeats = args.repeats if args.repeats > 0 else max(3, min(21, 2000 // max(1, args.steps)))
+    repeats = args.repeats if args.repeats > 0 else max(3, min(21, 2000 // max(1, args.steps))) if args.full else 1
     n_rows = args.steps * repeats + args.warmup
     ring = torch.zeros((n_rows, REPORT_WORDS), dtype=torch.int64, device=dev)   # one report per step
     ring[:, 4] = rank                      # identity words: the gathered report must hold one row per rank
@@ -289,11 +326,13 @@ def main():
         else:   # functional-test hook (gloo on a 1-GPU box): host-side report
             sm = runtime.run_batch_device(w, seed0 + k * total, count, d_outs[0].data_ptr(), streams[0].cuda_stream, cfg, lim)
             last_on_stream[0] = k
+            last_host_summary[0] = sm
             rep = mdist.reduce_report(sm.first_failing_seed, sm.n_failed, sm.total_steps, sm.total_clock_ns, cdev)
             if timed:
                 host_tot[0] += rep[1]; host_tot[1] += rep[2]; host_tot[2] += rep[3]; host_tot[3] += sm.kernel_ms
 
     host_tot = [0, 0, 0, 0.0]
+    last_host_summary = [None]
 
     def sync():
         if world > 1:
@@ -353,9 +392,20 @@ def main():
     dt = med["dt"]
     row0 = med["first_row"]
     # ---------------- everything below is outside the timed region ----------------
+    if args.dump_outputs:        # the last timed step, as its caller receives it: per-seed results and the step's summary
+        k_last = n_rows - 1
+        si_last = next(si for si, k in last_on_stream.items() if k == k_last)
+        got = np.frombuffer(d_outs[si_last].cpu().numpy().tobytes(), dtype=A.RESULT_DTYPE)
+        if use_device_report:
+            ff, nf, ns_, nc = (int(x) for x in ring[k_last, :4].tolist())
+            summ_last = [mdist.decode_first_fail(ff), nf, ns_, nc]
+        else:
+            hs = last_host_summary[0]
+            summ_last = [hs.first_failing_seed, hs.n_failed, hs.total_steps, hs.total_clock_ns]
+        dump_outputs(args.dump_outputs, got, summ_last, f"_rank{rank}" if world > 1 else "", DUMP_MAX_SEEDS // n_ranks)
     # for reference beside the overlapped figure: the same step with nothing else in flight (one stream)
     single_ms = None
-    if use_device_report and n_streams > 1 and world == 1:
+    if args.full and use_device_report and n_streams > 1 and world == 1:
         ns = min(10, n_rows)
         scratch = torch.empty_like(d_outs[0])
         t1 = time.perf_counter()
@@ -387,8 +437,9 @@ def main():
                             "kernel_ms_per_step are the median region's"}
 
     # oracle check of the batches that were just timed: the last batch on every stream, sampled k*257 mod count
-    verified = 0
-    if not args.no_verify:
+    verified = None                       # null in the line when the oracle check did not run
+    if args.full and not args.no_verify:
+        verified = 0
         import oracle
         n_samp = min(256, count)
         for si, k in sorted(last_on_stream.items()):
@@ -410,7 +461,7 @@ def main():
 
     # first-failing-seed leg (SURVEY 8d fault variant): wall time from launch to the failing seed being known on the host
     first_fail = None
-    if not args.no_first_fail and world == 1 and args.workload == "pingpong":
+    if args.full and not args.no_first_fail and world == 1 and args.workload == "pingpong":
         import oracle
         fcfg = A.Config.default(packet_loss_rate=args.first_fail_loss)
         fbuf = d_outs[0]
@@ -519,7 +570,7 @@ def main():
     # the same overlap without torch: ONE library call keeps the batches in flight on the library's own streams — the rate a Rust / C
     # host gets from madsim_hip_run_campaign (no per-seed results: report only)
     campaign = None
-    if not args.no_first_fail and world == 1 and headline and not args.loss:
+    if args.full and not args.no_first_fail and world == 1 and headline and not args.loss:
         nb = 60
         runtime.run_campaign(w, 1 << 47, 6 * count, count, n_streams, False, cfg, lim)               # warm
         rep = runtime.run_campaign(w, (1 << 47) + 6 * count, nb * count, count, n_streams, False, cfg, lim)
@@ -532,7 +583,7 @@ def main():
     # round (RCCL over xGMI under "nccl").  The half of BASELINE's metric that `--gpus N` measures at N > 1: seeds searched per hour when
     # nothing fails (the steady rate of the search), and the wall time to a very rare first failure.  At N = 1 the same path, no collective.
     ranks_search = None
-    if not args.no_first_fail and headline and not args.loss:
+    if args.full and not args.no_first_fail and headline and not args.loss:
         rb = 4 * n_streams
         per_round = rb * count * n_ranks
         runtime.run_campaign_over_ranks(w, 1 << 52, per_round, count, False, cfg, lim, device_tensors=cdev, round_batches=rb)       # warm (streams, buffers, tables, the communicator)
@@ -560,7 +611,7 @@ def main():
     # it keeps in flight and overlaps their device-to-host copies (run_pipelined); the figure includes the copy of all 12.6 MB of
     # per-seed results into pageable host memory.  Sampled seeds are compared with the oracle, the whole array with the summary.
     run_batch_big = None
-    if not args.no_first_fail and world == 1 and headline and not args.loss:
+    if args.full and not args.no_first_fail and world == 1 and headline and not args.loss:
         import oracle
         nbig = 4 * count
         runtime.run_batch(w, 1 << 48, nbig, cfg, lim)                                   # warm (flights, staging buffers)
@@ -601,7 +652,7 @@ def main():
     # run needs; the headline keeps the fingerprint (all 48 result bytes oracle-checked).  Same streams, same batch size, its own
     # timed region and its own oracle check (the oracle honours the same flag).
     plain = None
-    if not args.no_extras and world == 1 and headline and not args.loss and use_device_report:
+    if args.full and not args.no_extras and world == 1 and headline and not args.loss and use_device_report:
         import copy
         plim = copy.copy(lim); plim.no_trace_hash = 1
         psteps, pwu = max(args.steps, 12), 4
@@ -645,7 +696,7 @@ def main():
                  "kernel": runtime.variant_name(pg)}
 
     first_fail_rare = first_fail_very_rare = None
-    if not args.no_first_fail and world == 1 and args.workload == "pingpong":
+    if args.full and not args.no_first_fail and world == 1 and args.workload == "pingpong":
         first_fail_rare = rare_search(args.rare_loss, 1 << 43)
         first_fail_very_rare = rare_search(args.very_rare_loss, 1 << 44)
         for ff in (first_fail_rare, first_fail_very_rare):
@@ -656,8 +707,8 @@ def main():
     # extra.workloads: the configs[2] / [3] / [4]-shaped workloads and the timer storm, two timed steps per stream each on the same streams,
     # every line with sampled seeds of its timed batches checked against the oracle
     extras = None
-    ceil_all = issue_ceiling() if world == 1 and rank == 0 else None      # (tools/ubench_issue --quick: issue ceilings + the attainable HBM copy rate)
-    if not args.no_extras and world == 1 and headline and not args.loss:
+    ceil_all = issue_ceiling() if args.full and world == 1 and rank == 0 else None      # (tools/ubench_issue --quick: issue ceilings + the attainable HBM copy rate)
+    if args.full and not args.no_extras and world == 1 and headline and not args.loss:
         import oracle
         extras = {}
         # a step of these = the per-GPU batch BASELINE.json quotes the config on (configs[2]: 262 144 seeds on one GPU; configs[3]:
@@ -738,19 +789,21 @@ def main():
                                          "per launch / launch_ms (SURVEY 8d iii: the HBM-bound figure), measured_chip_gbps over wall time, against "
                                          "copy_peak_gbps (the float4 copy rate tools/ubench_issue measures on this GPU)"}
 
+    roof = None
     if rank == 0:
         seeds_total = total * args.steps
         sim_s = clock_total / 1e9
+        k_avg_ms = kernel_ms / args.steps
+        ms_step = dt / args.steps * 1e3
+        g = runtime.geometry(w, lim)
+    if rank == 0 and args.full:
         # Roofline of the dominant kernel (sim_kernel).  The executor state lives in registers and LDS, so the kernel's binding
         # bound is VALU instruction issue, not HBM: `roofline` prices the VALU wave-instructions the launches executed (PMC,
         # live) against the chip's sustained issue rate for the same instruction mix (tools/ubench_issue, live); the nominal
         # SURVEY 8d HBM yardstick (120 algorithmic bytes per executor step) rides along in roofline.hbm_nominal.
-        k_avg_ms = kernel_ms / args.steps
-        ms_step = dt / args.steps * 1e3
         steps_per_launch = steps_total / args.steps / n_ranks
         algo_bytes = steps_per_launch * ALGO_BYTES_PER_STEP + count * IO_BYTES_PER_SEED
         achieved = algo_bytes / (k_avg_ms * 1e-3) / 1e9
-        g = runtime.geometry(w, lim)
         kname = runtime.variant_name(g)
         pmc, pmc_note = None, None
         if world == 1 and args.measure_traffic is not False:
@@ -841,6 +894,7 @@ def main():
         roof["note"] = ("frac = algorithmic_bytes_per_launch / launch_ms / 8 TB/s (SURVEY 8d).  One division reproduces it from profiles/r6_pingpong_profile.txt: "
                         "12.229 GB / the sim_kernel AverageNs of the stats table / 8e12.  Those bytes stay in LDS and registers: `traffic` is what "
                         "reaches HBM per launch, and hbm_chip_frac (all overlapping launches / wall time) exceeds 1 for exactly that reason.")
+    if rank == 0:
         line = {
             "metric": "sim_seconds_per_sec", "value": sim_s / dt, "unit": "sim-s/s",
             "n_gpus": n_ranks, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_step,
@@ -868,7 +922,7 @@ def main():
                                                    or (first_fail_rare or {}).get("seeds_per_hour") or (first_fail["seeds_per_hour"] if first_fail else None)},
             "roofline": roof,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             import oracle
             sample = 4 * workload.BENCH_SEEDS_PER_GPU if args.workload == "pingpong" else 16384
             t1 = time.perf_counter()

@@ -721,7 +721,7 @@ def test_global_and_lds_state_agree_at_batch_size(hip, name):
     assert (a[idx] == want).all()
 
 
-def test_bench_two_ranks_share_the_gpu_over_gloo(hip):
+def test_bench_two_ranks_share_the_gpu_over_gloo(hip, tmp_path):
     """The N > 1 path of bench.py end to end on a 1-GPU box: `--gpus 2` re-executes itself as two ranks
     (torch.distributed.run), both on this GPU, reports reduced over gloo (the functional-test hook; a real node runs one
     rank per GPU over RCCL).  The line must say n_gpus 2, cover both ranks' seed blocks and carry oracle-verified seeds."""
@@ -734,8 +734,9 @@ def test_bench_two_ranks_share_the_gpu_over_gloo(hip):
     env = dict(os.environ, MADSIM_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-                        "--no-cpu-baseline", "--no-measure-traffic"], env=env, capture_output=True, text=True, timeout=600)
+    dump = os.path.join(str(tmp_path), "dump")
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--full",
+                        "--no-cpu-baseline", "--no-measure-traffic", "--dump-outputs", dump], env=env, capture_output=True, text=True, timeout=600)
     hip.init(0)
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
@@ -746,6 +747,12 @@ def test_bench_two_ranks_share_the_gpu_over_gloo(hip):
     ff = line["extra"]["first_fail_over_ranks"]
     assert ff["world"] == 2 and ff["failed"] == 0 and ff["rounds"] == 3 and ff["seeds_searched"] == 3 * 2 * ff["round_batches_per_rank"] * 65536
     assert line["extra"]["first_fail_seeds_per_hour"] == ff["seeds_per_hour"] > 0
+    # --dump-outputs through the host-report path: each rank's block of the last timed step, in files of its own
+    from tests import test_bench as TB
+    k_last = 2 + line["extra"]["regions"]["n"] * 4 - 1
+    w, lim, _ = W.bench_case("pingpong")
+    for r in range(2):
+        TB.check_dump(TB._load(dump, f"_rank{r}"), w, lim, k_last * 2 * 65536 + r * 65536, 65536)
 
 
 def test_campaign_keeps_batches_in_flight_and_reports_like_the_oracle(hip):

@@ -7,8 +7,6 @@ parsed out of the Rust source and compared with the header as tests/cheader.py p
 import os
 import re
 
-import pytest
-
 from tests import cheader as H
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -122,19 +120,18 @@ def test_dsl_pingpong_is_the_c_and_python_table():
     assert ops[9:18] == [O["BIND"], O["SLEEP"], O["SET"], O["SEND"], O["RECV"], O["ASSERT_VAL"], O["DJNZ"], O["DONE"], O["BIND"]]
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/madsim"), reason="the reference checkout is not on this box")
 def test_patch_context_lines_exist_in_the_reference():
-    """bindings/rust/patches/0001-*.patch: every context / removed line of every hunk is a line of the reference file it patches."""
-    patch = open(os.path.join(RS, "patches", "0001-builder-run_workload.patch")).read()
-    cur, checked = None, 0
-    for line in patch.splitlines():
-        if line.startswith("+++ b/"):
-            cur = open(os.path.join("/root/reference", line[6:])).read().splitlines()
-            cur = {l.strip() for l in cur}
-        elif cur is not None and (line.startswith(" ") or (line.startswith("-") and not line.startswith("---"))):
-            if line[1:].strip():
-                assert line[1:].strip() in cur, line
-                checked += 1
-        elif line.startswith("diff --git"):
-            cur = None
+    """bindings/rust/patches/0001-*.patch: every context / removed line of every hunk is a line of the reference file it patches —
+    against tests/golden/patch_context.json, the digests of those lines as tests/golden/make_patch_context.py recorded them
+    from a madsim checkout."""
+    import importlib.util
+    import json
+    spec = importlib.util.spec_from_file_location("make_patch_context", os.path.join(ROOT, "tests", "golden", "make_patch_context.py"))
+    mk = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mk)
+    golden = json.load(open(mk.OUT))["files"]
+    checked = 0
+    for path, text in mk.context_lines(open(mk.PATCH).read()):
+        assert mk.digest(text) in golden[path]["line_sha256"], (path, text)
+        checked += 1
     assert checked >= 15

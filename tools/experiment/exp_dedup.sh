@@ -6,7 +6,7 @@
 cd "$GRAFT_REPO_ROOT" || exit 1
 O=gpurun_out/$1; mkdir -p "$O"; WL=${2:-raft}; ST=${3:-12}
 run() {   # tag, lib, flags
-  MADSIM_HIP_LIB=$2 MADSIM_BENCH_STATE_FLAGS=$3 timeout 300 python bench.py --workload $WL --steps $ST --warmup 4 --no-cpu-baseline --no-measure-traffic --no-first-fail --no-extras > "$O/l.json" 2> "$O/l.err"
+  MADSIM_HIP_LIB=$2 MADSIM_BENCH_STATE_FLAGS=$3 timeout 300 python bench.py --full --workload $WL --steps $ST --warmup 4 --no-cpu-baseline --no-measure-traffic --no-first-fail --no-extras > "$O/l.json" 2> "$O/l.err"
   python - "$O/l.json" "$1" <<'PY'
 import json, sys
 try:

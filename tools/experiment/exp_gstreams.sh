@@ -5,7 +5,7 @@
 cd "$GRAFT_REPO_ROOT" || exit 1
 O=gpurun_out/$1; mkdir -p "$O"
 for r in 1 2; do for wl in raft topo kv; do for s in 3 4; do
-  timeout 300 python bench.py --workload $wl --steps 12 --warmup 4 --streams $s --no-cpu-baseline --no-measure-traffic --no-first-fail --no-extras > "$O/l.json" 2> "$O/l.err"
+  timeout 300 python bench.py --full --workload $wl --steps 12 --warmup 4 --streams $s --no-cpu-baseline --no-measure-traffic --no-first-fail --no-extras > "$O/l.json" 2> "$O/l.err"
   python - "$O/l.json" "$wl streams $s r$r" <<'PY'
 import json, sys
 try:

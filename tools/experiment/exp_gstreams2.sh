@@ -5,7 +5,7 @@
 cd "$GRAFT_REPO_ROOT" || exit 1
 O=gpurun_out/$1; mkdir -p "$O"
 for wl in $3; do for s in $4; do for lib in $2; do
-  MADSIM_HIP_LIB=$PWD/madsim_amd/$lib timeout 300 python bench.py --workload $wl --steps ${5:-24} --warmup 4 --repeats ${6:-5} --streams $s --no-cpu-baseline --no-measure-traffic --no-first-fail --no-extras > "$O/l.json" 2> "$O/l.err"
+  MADSIM_HIP_LIB=$PWD/madsim_amd/$lib timeout 300 python bench.py --full --workload $wl --steps ${5:-24} --warmup 4 --repeats ${6:-5} --streams $s --no-cpu-baseline --no-measure-traffic --no-first-fail --no-extras > "$O/l.json" 2> "$O/l.err"
   python - "$O/l.json" "$wl streams $s $lib" <<'PY'
 import json, sys
 try:

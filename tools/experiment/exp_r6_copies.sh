@@ -14,7 +14,7 @@ except Exception as ex:
 PY
 }
 run() { label=$1; wl=$2; steps=$3; shift 3
-  env "$@" timeout 400 python bench.py --workload "$wl" --steps "$steps" --warmup 4 --no-cpu-baseline --no-measure-traffic --no-first-fail --no-extras \
+  env "$@" timeout 400 python bench.py --full --workload "$wl" --steps "$steps" --warmup 4 --no-cpu-baseline --no-measure-traffic --no-first-fail --no-extras \
     > "$O/x.json" 2> "$O/x.err"; line "$O/x.json" "$label"; }
 N=MADSIM_BENCH_STATE_FLAGS=0x200
 NC=MADSIM_HIP_LIB=$PWD/madsim_amd/libmadsim_hip_nocopies.so
@@ -26,6 +26,6 @@ for round in 1 2 3; do
   run "raft l64 narrow no-dedup batched    r$round" raft 16 MADSIM_BENCH_STATE_FLAGS=0x200 MADSIM_BENCH_LPW=64 MADSIM_BENCH_CLEAR_FLAGS=0x100
   run "raft l64 narrow no-dedup one-by-one r$round" raft 16 MADSIM_BENCH_STATE_FLAGS=0x200 MADSIM_BENCH_LPW=64 MADSIM_BENCH_CLEAR_FLAGS=0x100 $NC
   run "raft l64 narrow dedup               r$round" raft 16 MADSIM_BENCH_STATE_FLAGS=0x200 MADSIM_BENCH_LPW=64
-  timeout 300 python bench.py --steps 20 --warmup 50 --no-cpu-baseline --no-measure-traffic --no-first-fail --no-extras > "$O/x.json" 2> "$O/x.err"; line "$O/x.json" "pingpong r6 (this tree)  r$round"
+  timeout 300 python bench.py --full --steps 20 --warmup 50 --no-cpu-baseline --no-measure-traffic --no-first-fail --no-extras > "$O/x.json" 2> "$O/x.err"; line "$O/x.json" "pingpong r6 (this tree)  r$round"
   ( cd _r5tree && timeout 300 python bench.py --steps 20 --warmup 50 --no-cpu-baseline --no-measure-traffic --no-first-fail --no-extras > "../$O/y.json" 2> "../$O/y.err" ); line "$O/y.json" "pingpong r5 (8add2ed)    r$round"
 done | tee "$O/ab.txt"

@@ -14,7 +14,7 @@ except Exception as ex:
 PY
 }
 for round in 1 2 3 4; do
-  timeout 300 python bench.py --steps 20 --warmup 50 --no-cpu-baseline --no-measure-traffic --no-first-fail --no-extras > "$O/x.json" 2> "$O/x.err"; line "$O/x.json" "pingpong r6 (this tree)  r$round"
+  timeout 300 python bench.py --full --steps 20 --warmup 50 --no-cpu-baseline --no-measure-traffic --no-first-fail --no-extras > "$O/x.json" 2> "$O/x.err"; line "$O/x.json" "pingpong r6 (this tree)  r$round"
   ( cd _r5tree && timeout 300 python bench.py --steps 20 --warmup 50 --no-cpu-baseline --no-measure-traffic --no-first-fail --no-extras > "../$O/y.json" 2> "../$O/y.err" ); line "$O/y.json" "pingpong r5 (8add2ed)    r$round"
 done | tee "$O/ab.txt"
 ( time timeout 2400 python -m pytest tests -m gpu -x -q > "$O/pytest.txt" 2>&1 ) 2> "$O/pytest.time"; tail -5 "$O/pytest.txt"; grep real "$O/pytest.time"

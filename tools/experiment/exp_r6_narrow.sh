@@ -16,7 +16,7 @@ PY
 }
 run() {   # run <label> <workload> <steps> <env...>
   label=$1; wl=$2; steps=$3; shift 3
-  env "$@" timeout 400 python bench.py --workload "$wl" --steps "$steps" --warmup 4 --no-cpu-baseline --no-measure-traffic --no-first-fail --no-extras \
+  env "$@" timeout 400 python bench.py --full --workload "$wl" --steps "$steps" --warmup 4 --no-cpu-baseline --no-measure-traffic --no-first-fail --no-extras \
     > "$O/x.json" 2> "$O/x.err"; line "$O/x.json" "$label"
 }
 timeout 900 python -m pytest tests/test_gpu_parity.py -m gpu -x -q -k "narrow" > "$O/pytest_narrow.txt" 2>&1; tail -3 "$O/pytest_narrow.txt"

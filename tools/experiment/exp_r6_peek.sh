@@ -18,10 +18,10 @@ timeout 1200 python -m pytest tests -m gpu -x -q > "$O/pytest.txt" 2>&1; tail -2
 for round in 1 2 3 4; do
   for v in "peek 2 (product)|X=1" "peek 1           |MADSIM_HIP_LIB=$PWD/madsim_amd/libmadsim_hip_peek1.so" "no peek          |MADSIM_HIP_LIB=$PWD/madsim_amd/libmadsim_hip_nopeek.so"; do
     IFS='|' read -r name envv <<< "$v"
-    env $envv timeout 300 python bench.py --steps 20 --warmup 50 --no-cpu-baseline --no-measure-traffic --no-first-fail --no-extras > "$O/x.json" 2> "$O/x.err"; line "$O/x.json" "pingpong $name r$round"
+    env $envv timeout 300 python bench.py --full --steps 20 --warmup 50 --no-cpu-baseline --no-measure-traffic --no-first-fail --no-extras > "$O/x.json" 2> "$O/x.err"; line "$O/x.json" "pingpong $name r$round"
   done
   for v in "peek 2 (product)|X=1" "no peek          |MADSIM_HIP_LIB=$PWD/madsim_amd/libmadsim_hip_nopeek.so"; do
     IFS='|' read -r name envv <<< "$v"
-    env $envv timeout 300 python bench.py --workload timers --steps 48 --warmup 4 --no-cpu-baseline --no-measure-traffic --no-first-fail --no-extras > "$O/x.json" 2> "$O/x.err"; line "$O/x.json" "timers   $name r$round"
+    env $envv timeout 300 python bench.py --full --workload timers --steps 48 --warmup 4 --no-cpu-baseline --no-measure-traffic --no-first-fail --no-extras > "$O/x.json" 2> "$O/x.err"; line "$O/x.json" "timers   $name r$round"
   done
 done | tee "$O/ab.txt"

@@ -14,7 +14,7 @@ except Exception as ex:
 PY
 }
 run() { label=$1; shift
-  timeout 600 python bench.py "$@" --warmup 2 --no-cpu-baseline --no-measure-traffic --no-first-fail --no-extras > "$O/x.json" 2> "$O/x.err"; line "$O/x.json" "$label"; }
+  timeout 600 python bench.py --full "$@" --warmup 2 --no-cpu-baseline --no-measure-traffic --no-first-fail --no-extras > "$O/x.json" 2> "$O/x.err"; line "$O/x.json" "$label"; }
 for round in 1 2; do
   for wl in raft topo; do
     run "$wl 65536/launch x4 in flight (bench)      r$round" --workload $wl --steps 16

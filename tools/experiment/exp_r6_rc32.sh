@@ -16,10 +16,10 @@ PY
 PV=MADSIM_HIP_LIB=$PWD/madsim_amd/libmadsim_hip_prev.so
 timeout 1200 python -m pytest tests -m gpu -x -q > "$O/pytest.txt" 2>&1; tail -2 "$O/pytest.txt"
 for round in 1 2 3 4; do
-  timeout 300 python bench.py --steps 20 --warmup 50 --no-cpu-baseline --no-measure-traffic --no-first-fail --no-extras > "$O/x.json" 2> "$O/x.err"; line "$O/x.json" "pingpong 32-bit count r$round"
-  env $PV timeout 300 python bench.py --steps 20 --warmup 50 --no-cpu-baseline --no-measure-traffic --no-first-fail --no-extras > "$O/x.json" 2> "$O/x.err"; line "$O/x.json" "pingpong previous     r$round"
+  timeout 300 python bench.py --full --steps 20 --warmup 50 --no-cpu-baseline --no-measure-traffic --no-first-fail --no-extras > "$O/x.json" 2> "$O/x.err"; line "$O/x.json" "pingpong 32-bit count r$round"
+  env $PV timeout 300 python bench.py --full --steps 20 --warmup 50 --no-cpu-baseline --no-measure-traffic --no-first-fail --no-extras > "$O/x.json" 2> "$O/x.err"; line "$O/x.json" "pingpong previous     r$round"
   for wl in timers kv topo; do
-    timeout 300 python bench.py --workload $wl --steps 24 --warmup 4 --no-cpu-baseline --no-measure-traffic --no-first-fail --no-extras > "$O/x.json" 2> "$O/x.err"; line "$O/x.json" "$wl 32-bit count r$round"
-    env $PV timeout 300 python bench.py --workload $wl --steps 24 --warmup 4 --no-cpu-baseline --no-measure-traffic --no-first-fail --no-extras > "$O/x.json" 2> "$O/x.err"; line "$O/x.json" "$wl previous     r$round"
+    timeout 300 python bench.py --full --workload $wl --steps 24 --warmup 4 --no-cpu-baseline --no-measure-traffic --no-first-fail --no-extras > "$O/x.json" 2> "$O/x.err"; line "$O/x.json" "$wl 32-bit count r$round"
+    env $PV timeout 300 python bench.py --full --workload $wl --steps 24 --warmup 4 --no-cpu-baseline --no-measure-traffic --no-first-fail --no-extras > "$O/x.json" 2> "$O/x.err"; line "$O/x.json" "$wl previous     r$round"
   done
 done | tee "$O/ab.txt"

@@ -13,7 +13,7 @@ except Exception as ex:
 PY
 }
 run() { label=$1; shift
-  timeout 600 python bench.py "$@" --warmup 4 --no-cpu-baseline --no-measure-traffic --no-first-fail --no-extras > "$O/x.json" 2> "$O/x.err"; line "$O/x.json" "$label"; }
+  timeout 600 python bench.py --full "$@" --warmup 4 --no-cpu-baseline --no-measure-traffic --no-first-fail --no-extras > "$O/x.json" 2> "$O/x.err"; line "$O/x.json" "$label"; }
 for round in 1 2; do
   for wl in topo raft; do
     run "$wl 65536 x4 (bench)  r$round" --workload $wl --steps 16

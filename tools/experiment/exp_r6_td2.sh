@@ -13,7 +13,7 @@ except Exception as ex:
 PY
 }
 run() { label=$1; wl=$2; steps=$3; shift 3
-  env "$@" timeout 400 python bench.py --workload "$wl" --steps "$steps" --warmup 4 --no-cpu-baseline --no-measure-traffic --no-first-fail --no-extras \
+  env "$@" timeout 400 python bench.py --full --workload "$wl" --steps "$steps" --warmup 4 --no-cpu-baseline --no-measure-traffic --no-first-fail --no-extras \
     > "$O/x.json" 2> "$O/x.err"; line "$O/x.json" "$label"; }
 TD=MADSIM_HIP_LIB=$PWD/madsim_amd/libmadsim_hip_td2.so
 MADSIM_HIP_LIB=$PWD/madsim_amd/libmadsim_hip_td2.so timeout 900 python -m pytest tests/test_gpu_parity.py -m gpu -x -q > "$O/pytest_td2.txt" 2>&1; tail -2 "$O/pytest_td2.txt"

@@ -13,7 +13,7 @@ except Exception as ex:
 PY
 }
 run() { label=$1; wl=$2; steps=$3; shift 3
-  env "$@" timeout 400 python bench.py --workload "$wl" --steps "$steps" --warmup 4 --no-cpu-baseline --no-measure-traffic --no-first-fail --no-extras \
+  env "$@" timeout 400 python bench.py --full --workload "$wl" --steps "$steps" --warmup 4 --no-cpu-baseline --no-measure-traffic --no-first-fail --no-extras \
     > "$O/x.json" 2> "$O/x.err"; line "$O/x.json" "$label"; }
 N=MADSIM_BENCH_STATE_FLAGS=0x200
 for round in 1 2; do
@@ -22,7 +22,7 @@ for round in 1 2; do
   run "topo wide     3w (w3)   r$round" topo 16 X=1 MADSIM_HIP_LIB=$PWD/madsim_amd/libmadsim_hip_w3.so
 done | tee "$O/ab.txt"
 timeout 900 python -m pytest tests/test_gpu_parity.py -m gpu -x -q -s -k "campaign_over_ranks or latency or hard_model or port0 or lifecycle_reference_tests_gpu" > "$O/pytest.txt" 2>&1; tail -5 "$O/pytest.txt"
-( time timeout 900 python bench.py --steps 20 > "$O/bench_default20.json" 2> "$O/bench_default20.err" ) 2> "$O/bench.time"; tail -c 600 "$O/bench_default20.err"; cat "$O/bench.time" | grep real
+( time timeout 900 python bench.py --full --steps 20 > "$O/bench_default20.json" 2> "$O/bench_default20.err" ) 2> "$O/bench.time"; tail -c 600 "$O/bench_default20.err"; cat "$O/bench.time" | grep real
 python - "$O/bench_default20.json" <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); r=d["roofline"]

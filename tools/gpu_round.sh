@@ -6,8 +6,8 @@
 #   vmem              tools/ubench_vmem (cost of divergent global-memory instructions, round-trip latency)
 #   tests             python -m pytest tests -m gpu -x -q
 #   smoke             __graft_entry__.smoke()
-#   bench             python bench.py (the default line: headline + extra.workloads + first-fail legs)
-#   bench:<args>      python bench.py <args with ',' for spaces>, e.g. bench:--workload,raft,--steps,12
+#   bench             python bench.py --full (the full line: headline + extra.workloads + first-fail legs)
+#   bench:<args>      python bench.py --full <args with ',' for spaces>, e.g. bench:--workload,raft,--steps,12
 #   line:<wl>[:<steps>]  one bench line of workload <wl> without the extra legs (fast A/B)
 #   prof:<wl>[:full]  tools/prof_workload.sh on workload <wl> (kernel-trace --stats + PMC passes; full adds FETCH/WRITE)
 #   phase:<wl>[:<n>[:<tag>]]  tools/phase_prof.py on workload <wl> (in-kernel s_memtime probes of an EXP_PROF build), n batches in flight, libmadsim_hip_<tag>.so
@@ -44,9 +44,9 @@ for st in "$@"; do
     bench)
       if [ -n "$a1" ]; then args=${a1//,/ }; else args=""; fi
       n=$(ls "$O" | grep -c '^bench[0-9]*\.json$')
-      ( time timeout 900 python bench.py $args > "$O/bench$n.json" 2> "$O/bench$n.err" ) 2> "$O/bench$n.time"; line "$O/bench$n.json" "bench[$args]"; grep real "$O/bench$n.time";;
+      ( time timeout 900 python bench.py --full $args > "$O/bench$n.json" 2> "$O/bench$n.err" ) 2> "$O/bench$n.time"; line "$O/bench$n.json" "bench[$args]"; grep real "$O/bench$n.time";;
     line)
-      timeout 400 python bench.py --workload "$a1" --steps "${a2:-20}" --warmup 4 --no-cpu-baseline --no-measure-traffic --no-first-fail --no-extras \
+      timeout 400 python bench.py --full --workload "$a1" --steps "${a2:-20}" --warmup 4 --no-cpu-baseline --no-measure-traffic --no-first-fail --no-extras \
         > "$O/line_$a1.json" 2> "$O/line_$a1.err"; line "$O/line_$a1.json" "$a1";;
     prof)
       args=""; [ "$a1" != pingpong ] && args="--workload $a1"
@@ -58,7 +58,7 @@ for st in "$@"; do
       timeout $(( ${a1:-90} + 120 )) python tools/fuzz_campaign.py "${a1:-90}" "$(( $(date +%s) * 1000 ))" $a2 > "$O/fuzz.txt" 2>&1; tail -2 "$O/fuzz.txt";;
     ab)
       for round in 1 2 3; do for lib in madsim_amd/libmadsim_hip*.so; do
-        MADSIM_HIP_LIB=$PWD/$lib timeout 300 python bench.py --workload "$a1" --steps "${a2:-20}" --warmup 4 --no-cpu-baseline --no-measure-traffic --no-first-fail --no-extras \
+        MADSIM_HIP_LIB=$PWD/$lib timeout 300 python bench.py --full --workload "$a1" --steps "${a2:-20}" --warmup 4 --no-cpu-baseline --no-measure-traffic --no-first-fail --no-extras \
           > "$O/ab.json" 2> "$O/ab.err"; line "$O/ab.json" "$lib r$round"
       done; done | tee -a "$O/ab.txt";;
     *) echo "unknown stage $st";;
