@@ -214,6 +214,8 @@ pub const MS_OP_HOOK_REQ: u8 = 56;
 pub const MS_OP_HOOK_RSP: u8 = 57;
 pub const MS_OP_IPVS: u8 = 58;
 pub const MS_OP_SET_LATENCY: u8 = 59;
+pub const MS_OP_TIMEOUT_BEGIN: u8 = 60;
+pub const MS_OP_TIMEOUT_END: u8 = 61;
 pub const MADSIM_PASS: u32 = 0;
 pub const MADSIM_PANIC: u32 = 1;
 pub const MADSIM_DEADLOCK: u32 = 2;
@@ -224,7 +226,7 @@ pub const MADSIM_UNSUPPORTED: u32 = 6;
 pub const MADSIM_INTERNAL: u32 = 7;
 
 // ---- #define constants -------------------------------------------------------------------------------------------
-pub const MADSIM_HIP_ABI_VERSION: u32 = 4;
+pub const MADSIM_HIP_ABI_VERSION: u32 = 5;
 pub const MADSIM_IPVS_ADD_SERVICE: u32 = 0;
 pub const MADSIM_IPVS_DEL_SERVICE: u32 = 1;
 pub const MADSIM_IPVS_ADD_SERVER: u32 = 2;

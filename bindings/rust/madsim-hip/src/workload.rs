@@ -24,6 +24,9 @@ pub struct TaskBuilder {
     code: Vec<Ins>,
 }
 
+/// A jump to the END of a timeout scope that is still open (patched by `timeout_end`).
+const SCOPE_END: u16 = 0xffff;
+
 fn dur_parts(d: Duration) -> (u16, u32) {
     assert!(d.as_secs() <= u16::MAX as u64, "durations are encoded as u16 seconds + u32 nanoseconds");
     (d.as_secs() as u16, d.subsec_nanos())
@@ -91,6 +94,21 @@ impl TaskBuilder {
     pub fn recv_from_timeout(&mut self, ep: Addr, tag: u8, d: Duration) -> &mut Self {
         assert!(d.as_secs() <= 255);
         self.emit(sys::MS_OP_RECV_TIMEOUT, ep.0, ((tag as u16) << 8) | d.as_secs() as u16, d.subsec_nanos(), false)
+    }
+    /// `timeout(d, async { .. })` over the ops up to `timeout_end(scope)`: returns the scope; `jeq_scope_end` jumps to its END before it
+    /// exists (connect1's `?`).  On expiry `val = MADSIM_VAL_TIMEOUT` and the body goes on behind the END.
+    pub fn timeout_begin(&mut self, d: Duration) -> u16 {
+        assert!(d.as_secs() <= 255);
+        self.emit(sys::MS_OP_TIMEOUT_BEGIN, d.as_secs() as u8, SCOPE_END, d.subsec_nanos(), true);
+        self.label() - 1
+    }
+    pub fn jeq_scope_end(&mut self, v: u32, _scope: u16) -> &mut Self { self.emit(sys::MS_OP_JEQ, 0, SCOPE_END, v, true) }
+    pub fn timeout_end(&mut self, scope: u16) -> &mut Self {
+        let end = self.label();
+        for i in self.code[scope as usize..].iter_mut() {
+            if i.reloc && i.insn.b == SCOPE_END { i.insn.b = end; }
+        }
+        self.emit(sys::MS_OP_TIMEOUT_END, 0, 0, 0, false)
     }
     // ---- supervisor ----------------------------------------------------------------------------------------------------------
     pub fn kill(&mut self, node: u8) -> &mut Self { self.emit(sys::MS_OP_KILL, node, 0, 0, false) }

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define MADSIM_HIP_ABI_VERSION 4u
+#define MADSIM_HIP_ABI_VERSION 5u
 
 /* ------------------------------------------------------------------------------------------------
  * Workload: the actor program (read-only, caller-owned POD).
@@ -151,6 +151,18 @@ enum madsim_op {
                               (net/mod.rs:138-141 -> Network::update_config, net/network.rs:129): every later link test samples
                               the new range (network.rs:267) — datagram sends, connect1, channel sends and their retries alike;
                               messages already in flight keep the latency they drew.  No draw, no await.                    */
+    /* -- ABI v5: timeout scopes, time::timeout(d, async { .. several awaits .. }) (time/mod.rs:128-140) -- */
+    MS_OP_TIMEOUT_BEGIN = 60,/* a=secs, imm=ns (< 10^9), b=pc of the matching MS_OP_TIMEOUT_END: the timeout's Sleep is created now
+                              (deadline max(now + d, now + 1 ms), no draw, no timer); the ops up to END are the inner future.  Each
+                              poll that leaves the inner future Pending polls the Sleep (ANOTHER timer while not elapsed,
+                              time/sleep.rs:47-54); once elapsed the inner future is dropped at whatever await it is parked on
+                              and val := MADSIM_VAL_TIMEOUT, execution goes on at END + 1 in the same poll.  Rules (validate(),
+                              MADSIM_E_WORKLOAD otherwise): scopes do not nest, a pair lies in one program, no jump enters a scope
+                              and none leaves it except to its END; inside only sleep / sleep_until / sleep_rand / yield, send /
+                              reply / recv / untimed rpc_call, connect / csend / crecv, the light ops, trace_time, the flag ops,
+                              panic, random, rand_bool; csend / crecv need a connect at a lower pc of the same scope.          */
+    MS_OP_TIMEOUT_END = 61,/* closes the scope (completion: val is what the block left).  A connection a MS_OP_CONNECT of the scope
+                              made is a local of the async block: dropped here, and on expiry (tx, then rx)                   */
     MS_OP__COUNT
 };
 #define MADSIM_IPVS_ADD_SERVICE 0u
@@ -600,7 +612,7 @@ typedef struct madsim_geometry {
                                     * (1 timeouts, 2 channel, 4 RPC, 8 node lifecycle, 16 general address resolution), bit 13 = built without the determinism-log
                                     * fold (madsim_limits_t.no_trace_hash on a base-op workload), bit 14 = the compact base-op layout (MADSIM_STATE_COMPACT), bit 15 = 8-byte
                                     * timer-heap entries (MADSIM_STATE_NARROW_HEAP); bits 16-19 = compile-time log2 lane
-                                    * stride (15 = runtime) */
+                                    * stride (15 = runtime); bit 20 = timeout scopes compiled in (MS_OP_TIMEOUT_BEGIN / END) */
     uint32_t global_bytes_per_seed; /* size of a lane's state block in global memory (global-state builds), else 0 */
 } madsim_geometry_t;
 int madsim_hip_geometry(const madsim_workload_t* w, const madsim_limits_t* lim, madsim_geometry_t* g);

@@ -173,6 +173,19 @@ class Task {
     Task& trace(uint32_t v) { return emit(MS_OP_TRACE, 0, 0, v); }
     Task& sleep(std::chrono::nanoseconds d) { return dur(MS_OP_SLEEP, 0, d); }
     Task& mark() { return emit(MS_OP_MARK); }
+    // time::timeout(d, async { .. }) over the ops up to timeout_end(scope) (MS_OP_TIMEOUT_BEGIN / END): returns the scope handle;
+    // jmp_scope_end / jeq_scope_end jump to its END before it exists (an early return, connect1's `?`).  Expired: val = MADSIM_VAL_TIMEOUT.
+    int timeout_begin(std::chrono::nanoseconds d) {
+        if (d.count() < 0 || d.count() / 1000000000 > 255) throw std::invalid_argument("timeout_begin: 0 .. 255 s");
+        emit(MS_OP_TIMEOUT_BEGIN, (uint8_t)(d.count() / 1000000000), SCOPE_END, (uint32_t)(d.count() % 1000000000), true);
+        return label() - 1;
+    }
+    Task& jeq_scope_end(uint32_t v, int scope) { (void)scope; return emit(MS_OP_JEQ, 0, SCOPE_END, v, true); }
+    Task& jmp_scope_end(int scope) { (void)scope; return emit(MS_OP_JMP, 0, SCOPE_END, 0, true); }
+    Task& timeout_end(int scope) {
+        for (size_t i = (size_t)scope; i < code_.size(); i++) if (code_[i].reloc && code_[i].in.b == SCOPE_END) code_[i].in.b = (uint16_t)label();
+        return emit(MS_OP_TIMEOUT_END);
+    }
     Task& sleep_until(std::chrono::nanoseconds after_mark) { return dur(MS_OP_SLEEP_UNTIL, 0, after_mark); }
     Task& assert_elapsed_eq(std::chrono::nanoseconds d) { return dur(MS_OP_ASSERT_ELAPSED, 0, d); }
     Task& assert_elapsed_ge(std::chrono::nanoseconds d) { return dur(MS_OP_ASSERT_ELAPSED, 1, d); }
@@ -246,6 +259,7 @@ class Task {
     friend class WorkloadBuilder;
     struct Ins { madsim_insn_t in; bool reloc; std::string text; };     // text: the literal message of a panic("..")
     Task(int index, int node, uint8_t flags) : index_(index), node_(node), flags_(flags) {}
+    static constexpr uint16_t SCOPE_END = 0xffff;      // (a jump to the END of the scope still open: patched by timeout_end)
     Task& emit(uint8_t op, uint8_t a = 0, uint16_t b = 0, uint32_t imm = 0, bool reloc = false) {
         code_.push_back({madsim_insn_t{op, a, b, imm}, reloc, std::string()});
         return *this;

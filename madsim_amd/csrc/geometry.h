@@ -173,6 +173,52 @@ inline int validate(const madsim_workload_t* w, const madsim_config_t* cfg, std:
                 return fail(err, MADSIM_E_WORKLOAD, "sleep_until / assert_elapsed before the program's first mark: t0 is not assigned yet");
         }
     }
+    {   // timeout scopes (MS_OP_TIMEOUT_BEGIN .. MS_OP_TIMEOUT_END): time::timeout(d, async { .. }) with the block's awaits inside.  A scope covers
+        // the pcs BEGIN + 1 .. END; the device keeps ONE scope per task (no nesting), and the ops a scope may drop at any await are the ones whose
+        // pending state it knows how to drop (include/madsim_hip.h).
+        std::vector<int32_t> scope(w->n_insns, -1);         // pc -> BEGIN pc of the scope that covers it
+        std::vector<uint8_t> is_entry(w->n_insns, 0);
+        for (uint32_t p = 0; p < w->n_progs; p++) is_entry[w->progs[p].entry] = 1;
+        for (uint32_t i = 0; i < w->n_insns; i++) {
+            const madsim_insn_t& in = w->insns[i];
+            if (in.op == MS_OP_TIMEOUT_END && scope[i] < 0) return fail(err, MADSIM_E_WORKLOAD, "timeout_end without its timeout_begin");
+            if (in.op != MS_OP_TIMEOUT_BEGIN) continue;
+            if (scope[i] >= 0) return fail(err, MADSIM_E_WORKLOAD, "timeout scopes do not nest");
+            if (in.imm >= 1000000000u) return fail(err, MADSIM_E_WORKLOAD, "timeout_begin: imm is the nanoseconds below one second");
+            const uint32_t end = in.b;
+            if (end <= i || end >= w->n_insns || w->insns[end].op != MS_OP_TIMEOUT_END) return fail(err, MADSIM_E_WORKLOAD, "timeout_begin: b must name its timeout_end at a higher pc");
+            bool conn = false;
+            for (uint32_t k = i + 1; k <= end; k++) {
+                const uint8_t op = w->insns[k].op;
+                if (is_entry[k]) return fail(err, MADSIM_E_WORKLOAD, "a timeout scope must lie inside one program");
+                if (op == MS_OP_TIMEOUT_BEGIN) return fail(err, MADSIM_E_WORKLOAD, "timeout scopes do not nest");
+                if (k < end) {
+                    bool ok = false;
+                    switch (op) {
+                    case MS_OP_SLEEP: case MS_OP_SLEEP_UNTIL: case MS_OP_SLEEP_RAND: case MS_OP_YIELD:
+                    case MS_OP_SEND: case MS_OP_REPLY: case MS_OP_RECV: case MS_OP_CONNECT:
+                    case MS_OP_SET: case MS_OP_DJNZ: case MS_OP_JMP: case MS_OP_JEQ: case MS_OP_ASSERT_VAL: case MS_OP_TRACE: case MS_OP_TRACE_TIME:
+                    case MS_OP_GSET: case MS_OP_GADD: case MS_OP_ASSERT_G: case MS_OP_PANIC_IF_G_LT: case MS_OP_PANIC: case MS_OP_RANDOM: case MS_OP_RAND_BOOL:
+                        ok = true; break;
+                    case MS_OP_RPC_CALL: ok = (w->insns[k].imm >> 8) == 0; break;          // an untimed call only
+                    case MS_OP_CSEND: case MS_OP_CRECV: ok = conn; break;                   // on the block's own connection
+                    default: break;
+                    }
+                    if (!ok) return fail(err, MADSIM_E_WORKLOAD, (op == MS_OP_CSEND || op == MS_OP_CRECV)
+                        ? "csend / crecv inside a timeout scope need a connect at a lower pc of the same scope"
+                        : "op not allowed inside a timeout scope (nested timeouts, spawn / join / abort / done, bind / close / accept / cclose, node ops, hooks, ipvs, set_latency, advance)");
+                    if (op == MS_OP_CONNECT) conn = true;
+                }
+                scope[k] = (int32_t)i;
+            }
+        }
+        for (uint32_t i = 0; i < w->n_insns; i++) {     // no jump enters a scope; none leaves one except to its END
+            const madsim_insn_t& in = w->insns[i];
+            if (in.op != MS_OP_DJNZ && in.op != MS_OP_JMP && in.op != MS_OP_JEQ) continue;
+            const int32_t from = scope[i], to = scope[in.b];
+            if (from != to) return fail(err, MADSIM_E_WORKLOAD, from < 0 ? "a jump into a timeout scope" : "a jump out of a timeout scope (only its timeout_end may be the target)");
+        }
+    }
     for (uint32_t p = 0; p < w->n_progs; p++) {
         if (!(w->progs[p].flags & MADSIM_PROG_DROP_SPAWN)) continue;
         if (p + 1 >= w->n_progs || w->progs[p + 1].node != w->progs[p].node)
@@ -275,6 +321,9 @@ inline int make_geometry(const Device& g, const madsim_workload_t* w, const mads
     // them (unit 2's other half is the timeout deadline RPC calls use anyway), else a unit of their own
     const bool mark = uses_op(w, MS_OP_MARK) || uses_op(w, MS_OP_SLEEP_UNTIL) || uses_op(w, MS_OP_ASSERT_ELAPSED);
     if (P.uses_rpc) { if (!mark) P.rpc_unit = 2; else { P.rpc_unit = P.task_units; P.task_units++; } }
+    // timeout scopes: {END pc | active << 16 | connection made in the scope << 17, -, the scope's deadline} (k_poll.h)
+    P.scope_unit = 0;
+    if (uses_op(w, MS_OP_TIMEOUT_BEGIN)) { P.scope_unit = P.task_units; P.task_units++; }
     // per socket: header, owner, registrations, queued messages (+ accept queue, parked acceptor); set once the layout
     // (base or extended) is known, below
     P.max_conns = L.max_conns ? L.max_conns : 4;
@@ -323,7 +372,9 @@ inline int make_geometry(const Device& g, const madsim_workload_t* w, const mads
     if (!P.uniq_addr) P.features |= MADSIM_FEAT_ADDR;
     for (uint32_t i = 0; i < w->n_progs; i++)          // guards that spawn in Drop: compiled into the full builds only
         if (w->progs[i].flags & MADSIM_PROG_DROP_SPAWN) P.features |= MADSIM_FEAT_NODE | MADSIM_FEAT_ADDR;
+    const bool scopes = uses_op(w, MS_OP_TIMEOUT_BEGIN);
     if (trace) P.features = MADSIM_FEAT_ALL;          // the trace build carries every class
+    if (scopes) P.features |= MADSIM_FEAT_SCOPE;      // (outside MADSIM_FEAT_ALL: only these workloads select the scope builds)
     P.lifecycle = P.features != 0;
     const uint32_t cus = g.num_cus > 0 ? (uint32_t)g.num_cus : 256u;
     uint32_t lw = 64;
@@ -336,7 +387,7 @@ inline int make_geometry(const Device& g, const madsim_workload_t* w, const mads
         return fail(err, MADSIM_E_LIMITS, "state_mem must be 0 (auto), 1 (LDS), 2 (global) or 3 (compact), optionally | MADSIM_STATE_DEDUP_TIMERS | MADSIM_STATE_NARROW_HEAP");
     // MADSIM_STATE_NARROW_HEAP: 8-byte heap entries hold the low deadline word — admitted when nothing the workload can ask for lies 2^31 ns
     // ahead of the clock (the device checks every push all the same: a channel back-off can grow past it at run time)
-    bool narrow_ok = (L.state_mem & MADSIM_STATE_NARROW_HEAP) && !trace && !cfg->buggify && !P.has_restart_on_panic;
+    bool narrow_ok = (L.state_mem & MADSIM_STATE_NARROW_HEAP) && !trace && !cfg->buggify && !P.has_restart_on_panic && !scopes;   // (no narrow scope build)
     {
         uint64_t horizon = std::max<uint64_t>(cfg->lat_hi_ns, 1000000ull);
         for (uint32_t i = 0; i < cfg->n_lat_table && i < 4; i++) horizon = std::max<uint64_t>(horizon, cfg->lat_table_hi_ns[i]);

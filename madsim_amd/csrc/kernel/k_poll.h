@@ -111,6 +111,13 @@ __device__ __forceinline__ bool poll_task(const Ctx& c, Lane& L, const uint32_t 
 #define RQ_SET(k_, v_) do { const uint32_t rq_v_ = (v_); if (HoistRpc<K>::ON) { if (k_) pp.rq1 = rq_v_; else pp.rq0 = rq_v_; } TWORD(c, slot, P.rpc_unit, (k_)) = rq_v_; } while (0)
     // stage [A]'s requests for the ops that send in this round (HdrPrefetch): destination table entry, its header, the caller's own header (rpc call)
     uint32_t a_dst = ~0u, a_hdr = 0, a_own = 0;
+    // A receive dropped with the future that awaited it — an expired timeout(recv_from), call_timeout, or a timeout scope: its oneshot::Receiver
+    // is gone, and the registration it may have left in the mailbox is dead from now on (the next receive takes the next sequence number).
+#define RX_DROP() do { u1.x = (u1.x & ~0xffu) | (((u1.x & 0xff) + 1) & 0xff); u1_dirty = true; if ((u1.x & 0xff) == 0) u0.x |= TF_RXWRAP; u0.x &= ~TF_INBOX; } while (0)
+    // Timeout scopes: the end of the async block (its END, or the expiry of its Sleep) drops the (tx, rx) a connect1 of the block made — a local of
+    // the block.  (A macro, like RQ_GET: the builds without scopes never see it.)
+#define SCOPE_DROP_CONN(sx_) do { if ((sx_) & SCOPE_MADE) { const uint32_t cx_ = cu0_get(); \
+        if ((cx_ & 0xff) != 0xff) { conn_drop_handles<K>(c, L, cx_ & 0xff, (cx_ >> 8) & 1, (u0.x & TF_KILLED) != 0); cu0_set(cx_ | 0xff); } } } while (0)
     auto recv_timeout_poll = [&]() -> bool {
         bool fut_ready = false;
         bool d1_new = false;
@@ -133,9 +140,7 @@ __device__ __forceinline__ bool poll_task(const Ctx& c, Lane& L, const uint32_t 
         if (K::G) d2 = u64of(pp.d2lo, pp.d2hi);              // (came with unit 0: k_state.h PollPrefetch)
         else { uint4 u2 = TU(c, slot, 2); d2 = u64of(u2.z, u2.w); }
         if (L.clock >= d2) {                                 // Err(Elapsed): the recv future is dropped
-            u1.x = (u1.x & ~0xffu) | (((u1.x & 0xff) + 1) & 0xff); u1_dirty = true;   // its oneshot::Receiver is gone
-            if ((u1.x & 0xff) == 0) u0.x |= TF_RXWRAP;
-            u0.x &= ~TF_INBOX;
+            RX_DROP();
             u0.w = MADSIM_VAL_TIMEOUT;
             return true;
         }
@@ -223,6 +228,7 @@ __device__ __forceinline__ bool poll_task(const Ctx& c, Lane& L, const uint32_t 
             if (K::G) d2 = u64of(pp.d2lo, pp.d2hi);
             else { uint4 u2 = TU(c, slot, 2); d2 = u64of(u2.z, u2.w); }
             if (L.clock >= d2) {                             // Err(Elapsed) -> TimedOut: the call future is dropped
+                // (RX_DROP's statements, in the order this build's code has always had them)
                 if (sub >= 2) { u1.x = (u1.x & ~0xffu) | (((u1.x & 0xff) + 1) & 0xff); u1_dirty = true; u0.x &= ~TF_INBOX; if ((u1.x & 0xff) == 0) u0.x |= TF_RXWRAP; }
                 u0.w = MADSIM_VAL_TIMEOUT;
                 return true;
@@ -272,6 +278,29 @@ __device__ __forceinline__ bool poll_task(const Ctx& c, Lane& L, const uint32_t 
 
     HeapPre heap_pre = {~0u, make_uint2(0, 0)};          // (k_timer.h timer_push_prefetch: requested when a round begins, used by the flush that ends it)
     for (;;) {
+        // Timeout scopes (time::timeout over an async block = select_biased! { block, sleep }, time/mod.rs:128-140): a round that leaves the block
+        // Pending — from stage [A] (a parked await) or [C] (an await that began) — polls the scope's Sleep here, after the block's own timers.  Not
+        // elapsed: ANOTHER timer at its deadline (time/sleep.rs:47-54).  Elapsed: the block is dropped at the await it is parked on (a receive's
+        // registration goes dead, a pending rand_delay / sleep just stops, the block's connection drops), val := TIMEOUT, and the body goes on
+        // behind END in this same poll.
+        if constexpr (K::FS) if (st == ST_PENDING) {
+            const uint4 su = TU(c, slot, P.scope_unit);
+            if (su.x & SCOPE_ACTIVE) {
+                const uint64_t sd = u64of(su.z, su.w);
+                if (L.clock < sd) timer_schedule<K>(c, L, sd, (EV_WAKE << EV_SHIFT) | (gen << 8) | slot, 0, true, true);
+                else {
+                    const uint32_t sop = INSN(c, pc).x & 0xff;
+                    if (sop == MS_OP_RECV || (sop == MS_OP_RPC_CALL && sub >= 2)) RX_DROP();   // recv_from_raw's future (the call's send: nothing)
+                    u0.x &= ~TF_INBOX;
+                    SCOPE_DROP_CONN(su.x);
+                    TWORD(c, slot, P.scope_unit, 0) = 0;
+                    u0.w = MADSIM_VAL_TIMEOUT;
+                    pc = (su.x & 0xffff) + 1;
+                    sub = 0;
+                    st = ST_RUN;
+                }
+            }
+        }
         // global-state builds: the Timer::add calls of the previous round happen here, at one site for the whole wave
         timer_flush<K>(c, L, (EV_WAKE << EV_SHIFT) | (gen << 8) | slot, heap_pre);
         PROBE_FLUSH();          // (EXP_PROF builds: the pushes apart from the wait for the other lanes' further rounds behind the loop)
@@ -344,6 +373,10 @@ __device__ __forceinline__ bool poll_task(const Ctx& c, Lane& L, const uint32_t 
                     }
                     else u0.w = u3.y;                      // sub 3: sleep_until(arrive_time) done -> yield value
                 } else if (K::FC && op == MS_OP_CONNECT) {   // NetSim::connect1 (net/mod.rs:345-363)
+                    if constexpr (K::FS) {                 // inside a timeout scope the pair is the async block's: note it for the block's end
+                        const uint32_t sx = TWORD(c, slot, P.scope_unit, 0);
+                        if (sx & SCOPE_ACTIVE) TWORD(c, slot, P.scope_unit, 0) = sx | SCOPE_MADE;
+                    }
                     uint32_t cx = cu0_get();
                     if ((cx & 0xff) != 0xff) { conn_drop_handles<K>(c, L, cx & 0xff, (cx >> 8) & 1, (u0.x & TF_KILLED) != 0); cu0_set(cx | 0xff); }
                     uint64_t lat; int ds; uint32_t lb;
@@ -514,9 +547,18 @@ __device__ __forceinline__ bool poll_task(const Ctx& c, Lane& L, const uint32_t 
         if constexpr (HdrPrefetch<K>::ON) a_dst = ~0u;     // (stage [A]'s requests are spent)
         PROBE(6);
         // ================= [B] cheap ops that never await ========================================
-        while (is_light(op)) {
+        while (is_light(op) || (K::FS && (op == MS_OP_TIMEOUT_BEGIN || op == MS_OP_TIMEOUT_END))) {
             REG(13);
-            if (op == MS_OP_ASSERT_VAL) {
+            if (K::FS && op == MS_OP_TIMEOUT_BEGIN) {     // timeout(d, ..): its Sleep exists from here on (sleep(d): 1 ms floor, no timer yet)
+                const uint64_t sd = sleep_deadline(L, L.clock + (uint64_t)a * NS_PER_S + imm);
+                TU(c, slot, P.scope_unit) = make_uint4(b | SCOPE_ACTIVE, 0, (uint32_t)sd, (uint32_t)(sd >> 32));
+                pc++;
+            } else if (K::FS && op == MS_OP_TIMEOUT_END) { // the block completed: its locals drop, the Sleep with it
+                const uint32_t sx = TWORD(c, slot, P.scope_unit, 0);
+                SCOPE_DROP_CONN(sx);
+                TWORD(c, slot, P.scope_unit, 0) = 0;
+                pc++;
+            } else if (op == MS_OP_ASSERT_VAL) {
                 if (u0.w != imm) { st = ST_PANIC; break; }
                 pc++;
             } else if (op == MS_OP_DJNZ) {
@@ -541,7 +583,8 @@ __device__ __forceinline__ bool poll_task(const Ctx& c, Lane& L, const uint32_t 
             in = insn_fetch<K>(c, L, pc);
             op = in.x & 0xff; a = (in.x >> 8) & 0xff; b = in.x >> 16; imm = in.y;
         }
-        if (st != ST_RUN) { if (K::G) continue; else break; }      // (global-state builds leave through the flush at the head)
+        if (st != ST_RUN) { if (K::G || K::FS) continue; else break; }      // (global-state builds leave through the flush at the head; scope builds
+                                                                               //  through the scope's test there)
 
         PROBE(7);
         REG(9);
@@ -603,7 +646,7 @@ __device__ __forceinline__ bool poll_task(const Ctx& c, Lane& L, const uint32_t 
                         const uint32_t reg = tag | (slot << 8) | (rxseq << 16) | ((gen & 0xff) << 24);
                         // dead registrations (timed-out / dropped receives, extended ops only) stay in the Vec like the
                         // reference's; an 8-bit rxseq that wraps onto one of them would make it look live: overflow, never a different answer
-                        if ((K::FT || K::FN) && may_have_twin(u0.x, gen)) for (uint32_t i = 0; i < nreg; i++) if (SW(c, a, 2 + i) == reg) OVF_SET(L, OVF_MODEL);
+                        if ((K::FT || K::FN || K::FS) && may_have_twin(u0.x, gen)) for (uint32_t i = 0; i < nreg; i++) if (SW(c, a, 2 + i) == reg) OVF_SET(L, OVF_MODEL);
                         SW(c, a, 2 + nreg) = reg;
                         SW(c, a, 0) = (h & ~(0xffu << 9)) | ((nreg + 1) << 9);
                         sub = 1;
@@ -1056,6 +1099,8 @@ __device__ __forceinline__ bool poll_task(const Ctx& c, Lane& L, const uint32_t 
     }
     return st == ST_PANIC;
 }
+#undef RX_DROP
+#undef SCOPE_DROP_CONN
 
 }  // namespace madsim_k
 

@@ -37,6 +37,8 @@ namespace madsim_k {
 enum : uint32_t { TF_ALIVE = 1, TF_SCHED = 2, TF_RUN = 4, TF_KILLED = 8, TF_CANCEL = 16, TF_INBOX = 32,
                   TF_RXWRAP = 64 /* this task's 8-bit receive sequence number has wrapped at least once */,
                   TF_OWNER = 128 /* this task has bound an Endpoint: its finish must look for sockets to close */ };
+// scope unit word 0 (timeout scopes, KParams.scope_unit): END pc | SCOPE_ACTIVE | SCOPE_MADE (a connect1 of the scope has made the task's pair)
+enum : uint32_t { SCOPE_ACTIVE = 1u << 16, SCOPE_MADE = 1u << 17 };
 // `sub` values of a task parked in MS_OP_JOIN (bit 7 set: stage [A] of poll_task ignores them, stage [C] owns them)
 enum : uint32_t { SUB_JOIN_WAIT = 0x80, SUB_JOIN_COMPLETED = 0x81, SUB_JOIN_CANCELLED = 0x82 };
 enum : uint32_t { EV_WAKE = 1, EV_DELIVER = 2, EV_RESTART = 3,
@@ -76,6 +78,8 @@ template <bool TRACE_, bool SPILL_, int LWS_, int FEAT_, bool RQ_ = false, bool 
     static constexpr bool FT = (FEAT_ & MADSIM_FEAT_TIME) != 0, FC = (FEAT_ & MADSIM_FEAT_CHAN) != 0,
                           FR = (FEAT_ & MADSIM_FEAT_RPC) != 0, FN = (FEAT_ & MADSIM_FEAT_NODE) != 0,
                           FA = (FEAT_ & MADSIM_FEAT_ADDR) != 0;
+    // timeout scopes (MS_OP_TIMEOUT_BEGIN / END): outside MADSIM_FEAT_ALL, so FEAT above does not see the bit
+    static constexpr bool FS = (FEAT_ & MADSIM_FEAT_SCOPE) != 0;
 };
 
 // REG(id): divergence-model markers, compiled in only by tools/divergence_model.py's host emulation build

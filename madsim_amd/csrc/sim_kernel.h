@@ -33,6 +33,10 @@
    the heap levels per LDS byte, half the bytes per spilled level.  Exact while every live deadline lies within 2^31 ns of the clock:
    checked per push on the device (a violation is a capacity verdict: the re-run uses the wide entries). */
 #define MADSIM_FEAT_NARROW 128
+/* Timeout scopes (MS_OP_TIMEOUT_BEGIN / END, KParams.features when a workload uses them).  Kept OUT of MADSIM_FEAT_ALL: every other
+   workload selects the build it selected before, and those builds carry none of the scope code.  Scope workloads run on builds of
+   their own (MADSIM_FOR_EACH_SCOPE_VARIANT), every class compiled in. */
+#define MADSIM_FEAT_SCOPE 256
 /* Global-state builds: identical wake-ups are fired as a batch (k_net.h timer_expire).  Sleep::poll registers ANOTHER timer with the same
    deadline and waker on every not-elapsed poll (time/sleep.rs:51-53), so more than half of the topology's heap entries are copies of an
    earlier one; copies leave the heap back to back, and every one after the first finds its task SCHEDULED already (or gone): a step
@@ -145,6 +149,7 @@ struct KParams {
     uint64_t* prof;            // profiling builds (tools/experiment): per-phase cycle accumulators
     uint32_t* iter_est;        // one word per workload: the passes a wave of it runs, as the last finished wave counted them (0 = nothing
                                // finished yet); null = no progress-based priority (k_main.h wave_progress_priority)
+    uint32_t scope_unit;       // (last: the other fields keep their kernel-argument offsets) timeout scopes (MADSIM_FEAT_SCOPE): index of the task unit {END pc | active << 16 | made << 17, -, deadline lo, hi}
 };
 
 // Kernel variants (Variant<TRACE, SPILL, LWS, FEAT, RQ>): the trace build; for base-op workloads on full 64-lane waves one
@@ -180,7 +185,17 @@ struct KParams {
     X(false, true, 6, MADSIM_FEAT_ALL, false, true)    \
     X(false, true, 6, MADSIM_FEAT_TIME | MADSIM_FEAT_NARROW, false, true) \
     X(false, true, 5, MADSIM_FEAT_TIME | MADSIM_FEAT_NARROW, false, true) \
-    X(false, true, 6, (MADSIM_FEAT_ALL & ~MADSIM_FEAT_ADDR) | MADSIM_FEAT_NARROW, false, true)
+    X(false, true, 6, (MADSIM_FEAT_ALL & ~MADSIM_FEAT_ADDR) | MADSIM_FEAT_NARROW, false, true) \
+    MADSIM_FOR_EACH_SCOPE_VARIANT(X)
+#endif
+// The builds of timeout-scope workloads (MADSIM_FEAT_SCOPE): the trace build, the LDS-resident every-class build (runtime lane stride), the
+// global-state every-class builds (wide heap entries; plain addresses and general resolution).
+#ifndef MADSIM_FOR_EACH_SCOPE_VARIANT
+#define MADSIM_FOR_EACH_SCOPE_VARIANT(X)                                      \
+    X(true, true, -1, MADSIM_FEAT_ALL | MADSIM_FEAT_SCOPE, false, false)      \
+    X(false, true, -1, MADSIM_FEAT_ALL | MADSIM_FEAT_SCOPE, false, false)     \
+    X(false, true, 6, (MADSIM_FEAT_ALL & ~MADSIM_FEAT_ADDR) | MADSIM_FEAT_SCOPE, false, true) \
+    X(false, true, 6, MADSIM_FEAT_ALL | MADSIM_FEAT_SCOPE, false, true)
 #endif
 
 // Which compiled specialisation of sim_kernel a parameter block runs on (one rule for the launcher and for
@@ -188,6 +203,11 @@ struct KParams {
 struct VariantSel { int trace, spill, lws, feat, rq, g; };
 inline VariantSel select_variant(const KParams& P, bool trace) {
     const int spill = P.heap_spill > 0, lw = (int)P.lw_shift, feat = (int)P.features;
+    if (feat & MADSIM_FEAT_SCOPE) {                                     // timeout scopes: builds of their own, every class
+        if (trace) return {1, 1, -1, MADSIM_FEAT_ALL | MADSIM_FEAT_SCOPE, 0, 0};
+        if (P.gstate_mode) return {0, 1, 6, ((feat & MADSIM_FEAT_ADDR) ? MADSIM_FEAT_ALL : MADSIM_FEAT_ALL & ~MADSIM_FEAT_ADDR) | MADSIM_FEAT_SCOPE, 0, 1};
+        return {0, 1, -1, MADSIM_FEAT_ALL | MADSIM_FEAT_SCOPE, 0, 0};
+    }
     if (trace) return {1, 1, -1, MADSIM_FEAT_ALL, 0, 0};
     if (feat == 0) {                                                    // base ops only
         if (lw == 6 && P.compact) return {0, 0, 6, MADSIM_FEAT_COMPACT | (P.no_log ? MADSIM_FEAT_NOLOG : 0), 1, 0};
@@ -237,7 +257,9 @@ inline const char* variant_mismatch(const KParams& P, const VariantSel& v, bool 
     if (v.rq && (P.max_tasks > 8 || P.lw_shift != 6 || P.lifecycle)) return "register ready queue needs <= 8 tasks, full waves, base ops";
     if (!v.spill && P.heap_spill) return "a build without the spill path on a geometry with spilled heap levels";
     const int classes = v.feat & MADSIM_FEAT_ALL;
-    if (((int)P.features & ~classes) != 0) return "the build lacks an op class the workload uses";
+    if (((int)P.features & ~(classes | (v.feat & MADSIM_FEAT_SCOPE))) != 0) return "the build lacks an op class the workload uses";
+    if ((v.feat & MADSIM_FEAT_SCOPE) && (!((int)P.features & MADSIM_FEAT_SCOPE) || !P.scope_unit || P.narrow || P.dedup_n))
+        return "a timeout-scope build on a layout without the scope unit (or with narrow entries / re-registration counts)";
     if ((classes != 0) != (P.lifecycle != 0)) return "extended-op build on the base-op LDS layout (or the reverse)";
     if (((v.feat & MADSIM_FEAT_COMPACT) != 0) != (P.compact != 0)) return "compact build on a plain layout (or the reverse)";
     if (P.compact && (P.heap_spill || P.lifecycle || P.lw_shift != 6 || !P.rq_in_reg || P.max_tasks > 8)) return "compact layout outside its conditions";

@@ -34,6 +34,9 @@ class TaskBuilder:
         self.code = []  # (op, a, b, imm, reloc)
 
     def _emit(self, op, a=0, b=0, imm=0, reloc=False):
+        if isinstance(b, _ScopeEnd):                 # a jump to the END of a scope still open: patched by timeout_end
+            b.refs.append(len(self.code))
+            b = 0
         self.code.append([A.OP[op], a, b, imm & 0xFFFFFFFF, reloc])
         return self
 
@@ -86,6 +89,32 @@ class TaskBuilder:
 
     def build_node(self, node):
         return self._emit("BUILD", a=node)
+
+    # -- timeout scopes: madsim::time::timeout(d, async { .. }).await (time/mod.rs:128-140) ---------------------------------
+    def timeout_begin(self, **kw):
+        """Open `timeout(d, async { ... })` around the ops that follow, up to timeout_end(handle).  On completion val is what the
+        block left in it; on expiry val = VAL_TIMEOUT and execution goes on behind timeout_end.  The handle's `.end` is a jump
+        target (an early return out of the block, e.g. `jeq(VAL_REFUSED, h.end)` for connect1's `?`)."""
+        b, imm = _dur(**kw)
+        if b > 0xFF:
+            raise ValueError("timeout too long (at most 255 s)")
+        h = _ScopeEnd(len(self.code))
+        self.code.append([A.OP["TIMEOUT_BEGIN"], b, 0, imm, True])
+        return h
+
+    def timeout_end(self, handle):
+        if handle.closed:
+            raise ValueError("timeout scope already closed")
+        end = len(self.code)
+        self.code.append([A.OP["TIMEOUT_END"], 0, 0, 0, False])
+        for i in [handle.begin] + handle.refs:
+            self.code[i][2] = end
+        handle.closed = True
+        return self
+
+    def timeout(self, **kw):
+        """`with t.timeout(ms=..) as s:` — timeout_begin / timeout_end around the block; `s.end` is its END as a jump target."""
+        return _ScopeCtx(self, self.timeout_begin(**kw))
 
     # -- time ------------------------------------------------------------------------------------
     def sleep(self, **kw):
@@ -275,6 +304,30 @@ class TaskBuilder:
 
     def jeq(self, value, target):
         return self._emit("JEQ", b=target, imm=value, reloc=True)
+
+
+class _ScopeEnd:
+    """Handle of an open timeout scope: `.end` names its MS_OP_TIMEOUT_END before it exists (the jumps are patched when it closes)."""
+
+    def __init__(self, begin):
+        self.begin, self.refs, self.closed = begin, [], False
+
+    @property
+    def end(self):
+        return self
+
+
+class _ScopeCtx:
+    def __init__(self, task, handle):
+        self.task, self.handle = task, handle
+
+    def __enter__(self):
+        return self.handle
+
+    def __exit__(self, *exc):
+        if exc[0] is None:
+            self.task.timeout_end(self.handle)
+        return False
 
 
 class BuiltWorkload:
@@ -621,6 +674,75 @@ def kv_rpc(n_clients=4, n_ops=8):
         m.join(c)
     m.assert_flag(0, n_clients * n_ops)
     return wl.build()
+
+
+def tonic_unary(n_clients=4, n_calls=6, timeout_ms=40, svc_ms=50, clog=True, kill=True, min_ok=0):
+    """BASELINE configs[4]'s tonic half: madsim-tonic unary calls under a request timeout (madsim-tonic/src/client.rs:52-78,208-219;
+    tonic-example/tests/test.rs `request_timeout`).  The server node's init task binds and accepts in a loop, spawning one handler
+    per connection (receive the request, `sleep_rand` as service time, send the response).  Every client makes `n_calls` calls,
+    each one `timeout(d, async { connect1; ?; send; recv })` — the block's (tx, rx) drop when it completes or expires — and
+    traces what it got (the response, VAL_TIMEOUT, VAL_REFUSED or VAL_RESET).  The supervisor clogs a client's link (the
+    receiver's backoff), kills the server node and restarts it.  min_ok > 0: the test asserts at least that many responses
+    (a configuration some seeds fail)."""
+    REQ, RSP = 0x11, 0x22
+    wl = WorkloadBuilder()
+    ns = wl.create_node()
+    asv = wl.addr(ns, 50051)
+    handler = wl.task(ns)
+    handler.chan_recv()
+    fin = handler.label() + 4
+    handler.jeq(A.VAL_RESET, fin)
+    handler.sleep_rand(lo_ms=0, ms=svc_ms)
+    handler.chan_send(RSP)
+    handler.flag_add(1, 1)
+    assert handler.label() == fin
+    handler.done()
+    srv = wl.task(ns, init=True, pre=True)
+    srv.bind(asv)
+    top = srv.label()
+    srv.accept1(asv); srv.spawn(handler, move_conn=True); srv.jmp(top)
+    clients = []
+    for i in range(n_clients):
+        nc = wl.create_node()
+        acl = wl.addr(nc, 1)
+        c = wl.task(nc)
+        c.bind(acl); c.sleep(ms=1 + i); c.set(0, n_calls)
+        top = c.label()
+        with c.timeout(ms=timeout_ms) as s:
+            c.connect1(acl, asv)
+            c.jeq(A.VAL_REFUSED, s.end)          # connect1(..).await?
+            c.chan_send(REQ)
+            c.chan_recv()
+        c.trace_val()
+        nxt = c.label() + 2
+        c.jeq(RSP, nxt + 0)
+        c.jmp(nxt + 1)
+        assert c.label() == nxt
+        c.flag_add(0, 1)
+        c.djnz(0, top)
+        c.done()
+        clients.append((nc, c))
+    m = wl.main()
+    for _, c in clients:
+        m.spawn(c)
+    if clog:
+        m.sleep(ms=30); m.clog_link(ns, clients[0][0]); m.sleep(ms=60); m.unclog_link(ns, clients[0][0])
+    if kill:
+        m.sleep(ms=40); m.kill(ns); m.sleep(ms=20); m.restart(ns)
+    for _, c in clients:
+        m.join(c)
+    if min_ok:
+        m.panic_if_flag_lt(0, min_ok)
+    m.done()
+    return wl.build()
+
+
+def tonic_unary_limits():
+    """Capacities for tonic_unary: a connection per client plus the ones a killed server leaves behind, a handler per connection."""
+    lim = A.Limits()
+    lim.max_conns, lim.max_tasks = 16, 32
+    lim.mbox_regs, lim.mbox_msgs = 4, 4
+    return lim
 
 
 def streaming_topology(n_compute=12, n_brokers=3, rounds=4):
