@@ -5,7 +5,7 @@
 //! run of the very same table must reproduce.
 //!
 //! Covers the base ops (datagram Endpoint API, sleeps, spawn / join / abort / yield, loop and assert glue, shared flags,
-//! clogs, kill / restart / pause / resume, observations).  Ops outside that set panic with "interp: unsupported op": they have
+//! clogs, kill / restart / pause / resume, observations, interval tickers).  Ops outside that set panic with "interp: unsupported op": they have
 //! hand-written twins in tools/ref_twin/src/main.rs instead.  Only built with `--features madsim` and `--cfg madsim`.
 use crate::workload::Workload;
 use madsim::net::{Endpoint, NetSim};
@@ -88,6 +88,8 @@ fn run_task(sh: Arc<Shared>, prog: usize) -> Task {
         let mut from: Option<SocketAddr> = None;
         let mut eps: HashMap<u8, Endpoint> = HashMap::new();
         let mut buf = vec![0u8; 4096];
+        let mut mark: Option<Instant> = None;                  // `let t0 = Instant::now()` of MS_OP_MARK (interval_at's start)
+        let mut ticker: Option<time::Interval> = None;         // `let mut i = time::interval(..)`: a local of this task body
         loop {
             let i = sh.insns[pc];
             let (a, b, imm) = (i.a, i.b, i.imm);
@@ -136,6 +138,24 @@ fn run_task(sh: Arc<Shared>, prog: usize) -> Task {
                 },
                 sys::MS_OP_RANDOM if a == 0 => val = madsim::rand::random::<u32>(),
                 sys::MS_OP_SLEEP => time::sleep(dur(b, imm)).await,
+                sys::MS_OP_MARK => mark = Some(Instant::now()),
+                sys::MS_OP_INTERVAL => {
+                    let mut t = if a & 4 != 0 { time::interval_at(mark.expect("interval_at before mark"), dur(b, imm)) } else { time::interval(dur(b, imm)) };
+                    t.set_missed_tick_behavior(match a & 3 {
+                        0 => time::MissedTickBehavior::Burst,
+                        1 => time::MissedTickBehavior::Delay,
+                        _ => time::MissedTickBehavior::Skip,
+                    });
+                    ticker = Some(t);
+                }
+                sys::MS_OP_TICK => {
+                    let at = ticker.as_mut().expect("tick before interval").tick().await;
+                    if a & 1 == 1 {
+                        let t0: Option<Instant> = *sh.t0.lock().unwrap();
+                        sh.observe(at.duration_since(t0.expect("t0")).as_nanos() as u64);
+                    }
+                }
+                sys::MS_OP_INTERVAL_RESET => ticker.as_mut().expect("reset before interval").reset(),
                 sys::MS_OP_BIND => {
                     let ep = Endpoint::bind(sh.addr(a)).await.unwrap();
                     eps.insert(a, ep);

@@ -110,6 +110,14 @@ impl TaskBuilder {
         }
         self.emit(sys::MS_OP_TIMEOUT_END, 0, 0, 0, false)
     }
+    /// `time::interval(p)` (or `interval_at(t0, p)` with `at_mark`, t0 = this program's `mark()`) with `set_missed_tick_behavior`:
+    /// 0 Burst, 1 Delay, 2 Skip.  `tick(true)` folds the instant the tick was scheduled for; `interval_reset()` is `Interval::reset`.
+    pub fn interval(&mut self, p: Duration, behavior: u8, at_mark: bool) -> &mut Self {
+        assert!(!p.is_zero() && p.as_secs() <= 0xffff && behavior <= 2);
+        self.emit(sys::MS_OP_INTERVAL, behavior | if at_mark { 4 } else { 0 }, p.as_secs() as u16, p.subsec_nanos(), false)
+    }
+    pub fn tick(&mut self, trace: bool) -> &mut Self { self.emit(sys::MS_OP_TICK, trace as u8, 0, 0, false) }
+    pub fn interval_reset(&mut self) -> &mut Self { self.emit(sys::MS_OP_INTERVAL_RESET, 0, 0, 0, false) }
     // ---- supervisor ----------------------------------------------------------------------------------------------------------
     pub fn kill(&mut self, node: u8) -> &mut Self { self.emit(sys::MS_OP_KILL, node, 0, 0, false) }
     pub fn restart(&mut self, node: u8) -> &mut Self { self.emit(sys::MS_OP_RESTART, node, 0, 0, false) }

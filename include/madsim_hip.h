@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define MADSIM_HIP_ABI_VERSION 5u
+#define MADSIM_HIP_ABI_VERSION 6u
 
 /* ------------------------------------------------------------------------------------------------
  * Workload: the actor program (read-only, caller-owned POD).
@@ -160,9 +160,24 @@ enum madsim_op {
                               MADSIM_E_WORKLOAD otherwise): scopes do not nest, a pair lies in one program, no jump enters a scope
                               and none leaves it except to its END; inside only sleep / sleep_until / sleep_rand / yield, send /
                               reply / recv / untimed rpc_call, connect / csend / crecv, the light ops, trace_time, the flag ops,
-                              panic, random, rand_bool; csend / crecv need a connect at a lower pc of the same scope.          */
+                              panic, random, rand_bool, tick / interval_reset (v6); csend / crecv need a connect at a lower pc of the same scope.          */
     MS_OP_TIMEOUT_END = 61,/* closes the scope (completion: val is what the block left).  A connection a MS_OP_CONNECT of the scope
                               made is a local of the async block: dropped here, and on expiry (tx, then rx)                   */
+    /* -- ABI v6: interval tickers, `let mut i = time::interval(p); loop { i.tick().await; .. }` (time/interval.rs) -------------- */
+    MS_OP_INTERVAL = 62,   /* a bits 0-1 = MissedTickBehavior (0 Burst, 1 Delay, 2 Skip), a bit 2 = interval_at(t0, p) (t0 = the
+                              program's MARK, which must stand at a lower pc) instead of interval(p) = interval_at(now, p); b = whole
+                              seconds of the period, imm = the nanoseconds below one second (< 10^9); period > 0.  Makes the task's
+                              ticker: its Sleep is sleep_until(start), deadline max(start, now + 1 ms) (time/mod.rs:118-124).  Again:
+                              the ticker is replaced (Rust reassignment).  Never awaits.  Not inside a timeout scope.          */
+    MS_OP_TICK = 63,       /* ticker.tick().await.  Deadline passed (now >= deadline): Ready at once, NO timer and no yield; else a
+                              timer at the deadline on every poll that leaves it Pending (time/sleep.rs:47-54).  On completion the
+                              next deadline is deadline + period, unless the tick is late (now > deadline + 5 ms): then Burst
+                              deadline + period, Delay now + period, Skip now + period - (now - deadline) % period.  a & 1: obs_hash
+                              <- fold(the tick's scheduled instant, ns since the runtime's start, as MS_OP_TRACE_TIME a=1); val is
+                              unchanged.  Every path from the program's entry must pass an MS_OP_INTERVAL first.  Allowed inside a
+                              timeout scope: its expiry drops the tick future only, the ticker keeps its deadline.            */
+    MS_OP_INTERVAL_RESET = 64,/* ticker.reset(): next deadline := now + period (no floor, no behaviour).  Never awaits.  Needs a ticker,
+                              as MS_OP_TICK does.                                                                             */
     MS_OP__COUNT
 };
 #define MADSIM_IPVS_ADD_SERVICE 0u
@@ -612,7 +627,8 @@ typedef struct madsim_geometry {
                                     * (1 timeouts, 2 channel, 4 RPC, 8 node lifecycle, 16 general address resolution), bit 13 = built without the determinism-log
                                     * fold (madsim_limits_t.no_trace_hash on a base-op workload), bit 14 = the compact base-op layout (MADSIM_STATE_COMPACT), bit 15 = 8-byte
                                     * timer-heap entries (MADSIM_STATE_NARROW_HEAP); bits 16-19 = compile-time log2 lane
-                                    * stride (15 = runtime); bit 20 = timeout scopes compiled in (MS_OP_TIMEOUT_BEGIN / END) */
+                                    * stride (15 = runtime); bit 20 = timeout scopes compiled in (MS_OP_TIMEOUT_BEGIN / END); bit 21 = interval
+                                    * tickers compiled in (MS_OP_INTERVAL / TICK / INTERVAL_RESET) */
     uint32_t global_bytes_per_seed; /* size of a lane's state block in global memory (global-state builds), else 0 */
 } madsim_geometry_t;
 int madsim_hip_geometry(const madsim_workload_t* w, const madsim_limits_t* lim, madsim_geometry_t* g);

@@ -173,6 +173,14 @@ class Task {
     Task& trace(uint32_t v) { return emit(MS_OP_TRACE, 0, 0, v); }
     Task& sleep(std::chrono::nanoseconds d) { return dur(MS_OP_SLEEP, 0, d); }
     Task& mark() { return emit(MS_OP_MARK); }
+    // time::interval(p) / interval_at(t0, p) with set_missed_tick_behavior (0 Burst, 1 Delay, 2 Skip), ticker.tick().await, ticker.reset()
+    // (MS_OP_INTERVAL / MS_OP_TICK / MS_OP_INTERVAL_RESET).  tick(true) folds the instant the tick was scheduled for.
+    Task& interval(std::chrono::nanoseconds p, uint8_t behavior = 0, bool at_mark = false) {
+        if (p.count() <= 0 || p.count() / 1000000000 > 0xffff || behavior > 2) throw std::invalid_argument("interval: 0 < period < 65536 s, behavior 0..2");
+        return emit(MS_OP_INTERVAL, (uint8_t)(behavior | (at_mark ? 4 : 0)), (uint16_t)(p.count() / 1000000000), (uint32_t)(p.count() % 1000000000));
+    }
+    Task& tick(bool trace = false) { return emit(MS_OP_TICK, trace ? 1 : 0); }
+    Task& interval_reset() { return emit(MS_OP_INTERVAL_RESET); }
     // time::timeout(d, async { .. }) over the ops up to timeout_end(scope) (MS_OP_TIMEOUT_BEGIN / END): returns the scope handle;
     // jmp_scope_end / jeq_scope_end jump to its END before it exists (an early return, connect1's `?`).  Expired: val = MADSIM_VAL_TIMEOUT.
     int timeout_begin(std::chrono::nanoseconds d) {

@@ -199,7 +199,10 @@ inline int validate(const madsim_workload_t* w, const madsim_config_t* cfg, std:
                     case MS_OP_SEND: case MS_OP_REPLY: case MS_OP_RECV: case MS_OP_CONNECT:
                     case MS_OP_SET: case MS_OP_DJNZ: case MS_OP_JMP: case MS_OP_JEQ: case MS_OP_ASSERT_VAL: case MS_OP_TRACE: case MS_OP_TRACE_TIME:
                     case MS_OP_GSET: case MS_OP_GADD: case MS_OP_ASSERT_G: case MS_OP_PANIC_IF_G_LT: case MS_OP_PANIC: case MS_OP_RANDOM: case MS_OP_RAND_BOOL:
+                    case MS_OP_TICK: case MS_OP_INTERVAL_RESET:     // timeout(d, ticker.tick()): expiry drops the tick future, not the ticker
                         ok = true; break;
+                    case MS_OP_INTERVAL:
+                        return fail(err, MADSIM_E_WORKLOAD, "interval inside a timeout scope: the ticker would be a local of the async block");
                     case MS_OP_RPC_CALL: ok = (w->insns[k].imm >> 8) == 0; break;          // an untimed call only
                     case MS_OP_CSEND: case MS_OP_CRECV: ok = conn; break;                   // on the block's own connection
                     default: break;
@@ -217,6 +220,41 @@ inline int validate(const madsim_workload_t* w, const madsim_config_t* cfg, std:
             if (in.op != MS_OP_DJNZ && in.op != MS_OP_JMP && in.op != MS_OP_JEQ) continue;
             const int32_t from = scope[i], to = scope[in.b];
             if (from != to) return fail(err, MADSIM_E_WORKLOAD, from < 0 ? "a jump into a timeout scope" : "a jump out of a timeout scope (only its timeout_end may be the target)");
+        }
+    }
+    {   // interval tickers (MS_OP_INTERVAL / TICK / INTERVAL_RESET): `let mut i = interval(p)` is a local of the task body.  Rust refuses a use
+        // before the assignment, and so does this: forward data-flow from every program entry over fall-through, jump and scope-expiry edges
+        // (BEGIN -> END + 1); an INTERVAL ends a path that has no ticker.  A spawned program starts without one (it has its own entry).
+        std::vector<uint8_t> is_entry(w->n_insns, 0);
+        for (uint32_t p = 0; p < w->n_progs; p++) is_entry[w->progs[p].entry] = 1;
+        bool marked = false, ticks = false;
+        for (uint32_t i = 0; i < w->n_insns; i++) {
+            if (is_entry[i]) marked = false;
+            const madsim_insn_t& in = w->insns[i];
+            if (in.op == MS_OP_MARK) marked = true;
+            if (in.op == MS_OP_TICK || in.op == MS_OP_INTERVAL_RESET) ticks = true;
+            if (in.op != MS_OP_INTERVAL) continue;
+            if (in.b == 0 && in.imm == 0) return fail(err, MADSIM_E_WORKLOAD, "interval: the period must be non-zero");
+            if ((in.a & 3) == 3 || in.a > 7) return fail(err, MADSIM_E_WORKLOAD, "interval: a bits 0-1 are the missed-tick behaviour (0 burst, 1 delay, 2 skip), bit 2 interval_at");
+            if (in.imm >= 1000000000u) return fail(err, MADSIM_E_WORKLOAD, "interval: imm is the nanoseconds below one second");
+            if ((in.a & 4) && !marked) return fail(err, MADSIM_E_WORKLOAD, "interval_at before the program's first mark: t0 is not assigned yet");
+        }
+        if (ticks) {
+            std::vector<uint8_t> bare(w->n_insns, 0);         // pc reachable from an entry on a path without an INTERVAL
+            std::vector<uint32_t> work;
+            for (uint32_t p = 0; p < w->n_progs; p++) if (!bare[w->progs[p].entry]) { bare[w->progs[p].entry] = 1; work.push_back(w->progs[p].entry); }
+            auto edge = [&](uint32_t to) { if (to < w->n_insns && !bare[to]) { bare[to] = 1; work.push_back(to); } };
+            while (!work.empty()) {
+                const uint32_t i = work.back(); work.pop_back();
+                const madsim_insn_t& in = w->insns[i];
+                if (in.op == MS_OP_TICK || in.op == MS_OP_INTERVAL_RESET)
+                    return fail(err, MADSIM_E_WORKLOAD, "tick / interval_reset on a path from the program's entry that passes no interval: the ticker does not exist yet");
+                if (in.op == MS_OP_INTERVAL || in.op == MS_OP_DONE || in.op == MS_OP_PANIC) continue;
+                if (in.op == MS_OP_JMP) { edge(in.b); continue; }
+                if (in.op == MS_OP_DJNZ || in.op == MS_OP_JEQ) edge(in.b);
+                if (in.op == MS_OP_TIMEOUT_BEGIN) edge((uint32_t)in.b + 1);
+                edge(i + 1);
+            }
         }
     }
     for (uint32_t p = 0; p < w->n_progs; p++) {
@@ -324,6 +362,9 @@ inline int make_geometry(const Device& g, const madsim_workload_t* w, const mads
     // timeout scopes: {END pc | active << 16 | connection made in the scope << 17, -, the scope's deadline} (k_poll.h)
     P.scope_unit = 0;
     if (uses_op(w, MS_OP_TIMEOUT_BEGIN)) { P.scope_unit = P.task_units; P.task_units++; }
+    // interval tickers: {TICK_ACTIVE | behaviour << 1 | period s << 16, period ns, next deadline} (k_poll.h)
+    P.tick_unit = 0;
+    if (uses_op(w, MS_OP_INTERVAL)) { P.tick_unit = P.task_units; P.task_units++; }
     // per socket: header, owner, registrations, queued messages (+ accept queue, parked acceptor); set once the layout
     // (base or extended) is known, below
     P.max_conns = L.max_conns ? L.max_conns : 4;
@@ -375,6 +416,8 @@ inline int make_geometry(const Device& g, const madsim_workload_t* w, const mads
     const bool scopes = uses_op(w, MS_OP_TIMEOUT_BEGIN);
     if (trace) P.features = MADSIM_FEAT_ALL;          // the trace build carries every class
     if (scopes) P.features |= MADSIM_FEAT_SCOPE;      // (outside MADSIM_FEAT_ALL: only these workloads select the scope builds)
+    const bool ticks = uses_op(w, MS_OP_INTERVAL);
+    if (ticks) P.features |= MADSIM_FEAT_TICK;        // (likewise: only these workloads select the ticker builds)
     P.lifecycle = P.features != 0;
     const uint32_t cus = g.num_cus > 0 ? (uint32_t)g.num_cus : 256u;
     uint32_t lw = 64;
@@ -387,7 +430,7 @@ inline int make_geometry(const Device& g, const madsim_workload_t* w, const mads
         return fail(err, MADSIM_E_LIMITS, "state_mem must be 0 (auto), 1 (LDS), 2 (global) or 3 (compact), optionally | MADSIM_STATE_DEDUP_TIMERS | MADSIM_STATE_NARROW_HEAP");
     // MADSIM_STATE_NARROW_HEAP: 8-byte heap entries hold the low deadline word — admitted when nothing the workload can ask for lies 2^31 ns
     // ahead of the clock (the device checks every push all the same: a channel back-off can grow past it at run time)
-    bool narrow_ok = (L.state_mem & MADSIM_STATE_NARROW_HEAP) && !trace && !cfg->buggify && !P.has_restart_on_panic && !scopes;   // (no narrow scope build)
+    bool narrow_ok = (L.state_mem & MADSIM_STATE_NARROW_HEAP) && !trace && !cfg->buggify && !P.has_restart_on_panic && !scopes && !ticks;   // (no narrow scope / ticker build)
     {
         uint64_t horizon = std::max<uint64_t>(cfg->lat_hi_ns, 1000000ull);
         for (uint32_t i = 0; i < cfg->n_lat_table && i < 4; i++) horizon = std::max<uint64_t>(horizon, cfg->lat_table_hi_ns[i]);

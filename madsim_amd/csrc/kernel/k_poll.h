@@ -63,6 +63,28 @@ __device__ __forceinline__ uint4 insn_fetch(const Ctx& c, Lane& L, uint32_t pc) 
     return in;
 }
 
+// Interval tickers (time/interval.rs).  A late tick (now > deadline + 5 ms, :158) of a Delay / Skip ticker picks its next deadline by
+// MissedTickBehavior::next_timeout (:76-101): Delay now + period, Skip now + period - (now - deadline) % period.  Kept out of line: Skip's
+// 64-bit remainder is a software division on gfx950, and this branch is rare — none of it belongs in the poll loop's live range.
+__device__ __attribute__((noinline)) uint64_t tick_late_next(uint64_t deadline, uint64_t now, uint64_t period, uint32_t behaviour) {
+    if (behaviour == TICK_DELAY) return now + period;
+    return now + (period - (now - deadline) % period);
+}
+
+// A tick whose deadline has passed (Interval::poll_tick, time/interval.rs:142-169): the Sleep is reset to the next deadline — deadline + period
+// for a tick on time and for every Burst tick — and the tick returns the deadline it was scheduled for (not `now`), folded into obs_hash on
+// request (`a & 1`, the form of MS_OP_TRACE_TIME a=1).  `tu` is the tick unit as read by the caller.
+template <class K>
+__device__ __forceinline__ void tick_complete(const Ctx& c, Lane& L, uint32_t slot, const uint4 tu, uint32_t a) {
+    const uint64_t dl = u64of(tu.z, tu.w), period = (uint64_t)(tu.x >> 16) * NS_PER_S + tu.y;
+    const uint32_t behaviour = (tu.x >> 1) & 3;
+    uint64_t next = dl + period;
+    if (behaviour != TICK_BURST && L.clock > dl + 5 * NS_PER_MS) next = tick_late_next(dl, L.clock, period, behaviour);
+    TWORD(c, slot, c.P.tick_unit, 2) = (uint32_t)next;
+    TWORD(c, slot, c.P.tick_unit, 3) = (uint32_t)(next >> 32);
+    if (a & 1) L.obs_hash = (L.obs_hash ^ dl) * FNV_PRIME;
+}
+
 __device__ __forceinline__ bool is_light(uint32_t op) {
     return op == MS_OP_ASSERT_VAL || op == MS_OP_DJNZ || op == MS_OP_SET || op == MS_OP_JMP || op == MS_OP_TRACE || op == MS_OP_JEQ;
 }
@@ -283,7 +305,7 @@ __device__ __forceinline__ bool poll_task(const Ctx& c, Lane& L, const uint32_t 
         // elapsed: ANOTHER timer at its deadline (time/sleep.rs:47-54).  Elapsed: the block is dropped at the await it is parked on (a receive's
         // registration goes dead, a pending rand_delay / sleep just stops, the block's connection drops), val := TIMEOUT, and the body goes on
         // behind END in this same poll.
-        if constexpr (K::FS) if (st == ST_PENDING) {
+        if constexpr (K::FS) if (st == ST_PENDING && (!K::FK || P.scope_unit)) {     // (ticker builds run workloads without scopes too)
             const uint4 su = TU(c, slot, P.scope_unit);
             if (su.x & SCOPE_ACTIVE) {
                 const uint64_t sd = u64of(su.z, su.w);
@@ -355,6 +377,9 @@ __device__ __forceinline__ bool poll_task(const Ctx& c, Lane& L, const uint32_t 
                     timer_schedule<K>(c, L, deadline, (EV_WAKE << EV_SHIFT) | (gen << 8) | slot, 0, true, true);
                     st = ST_PENDING;
                 }
+                // a parked tick (its Sleep's deadline is the tick unit's, copied to u1 when it began): elapsed -> Ready.  A wake before it (the stale
+                // timer of a tick a timeout scope dropped, the scope's own Sleep) took the branch above: ANOTHER timer, as for any Sleep.
+                else if (K::FK && op == MS_OP_TICK) tick_complete<K>(c, L, slot, TU(c, slot, P.tick_unit), a);
                 else if (K::FC && op == MS_OP_ACCEPT) {    // rand_delay done -> conn_rx.recv()
                     sub = 2;
                     accept_check(a);                       // (false: st is Pending)
@@ -373,7 +398,7 @@ __device__ __forceinline__ bool poll_task(const Ctx& c, Lane& L, const uint32_t 
                     }
                     else u0.w = u3.y;                      // sub 3: sleep_until(arrive_time) done -> yield value
                 } else if (K::FC && op == MS_OP_CONNECT) {   // NetSim::connect1 (net/mod.rs:345-363)
-                    if constexpr (K::FS) {                 // inside a timeout scope the pair is the async block's: note it for the block's end
+                    if constexpr (K::FS) if (!K::FK || P.scope_unit) {   // inside a timeout scope the pair is the async block's: note it for the block's end
                         const uint32_t sx = TWORD(c, slot, P.scope_unit, 0);
                         if (sx & SCOPE_ACTIVE) TWORD(c, slot, P.scope_unit, 0) = sx | SCOPE_MADE;
                     }
@@ -547,9 +572,21 @@ __device__ __forceinline__ bool poll_task(const Ctx& c, Lane& L, const uint32_t 
         if constexpr (HdrPrefetch<K>::ON) a_dst = ~0u;     // (stage [A]'s requests are spent)
         PROBE(6);
         // ================= [B] cheap ops that never await ========================================
-        while (is_light(op) || (K::FS && (op == MS_OP_TIMEOUT_BEGIN || op == MS_OP_TIMEOUT_END))) {
+        while (is_light(op) || (K::FS && (op == MS_OP_TIMEOUT_BEGIN || op == MS_OP_TIMEOUT_END)) || (K::FK && (op == MS_OP_INTERVAL || op == MS_OP_INTERVAL_RESET))) {
             REG(13);
-            if (K::FS && op == MS_OP_TIMEOUT_BEGIN) {     // timeout(d, ..): its Sleep exists from here on (sleep(d): 1 ms floor, no timer yet)
+            if (K::FK && op == MS_OP_INTERVAL) {          // interval(p) / interval_at(t0, p): its Sleep is sleep_until(start) (1 ms floor, no timer yet)
+                uint64_t start = L.clock;
+                if (a & 4) { const uint4 u2 = TU(c, slot, 2); start = u64of(u2.x, u2.y); }
+                const uint64_t dl = sleep_deadline(L, start);
+                TU(c, slot, P.tick_unit) = make_uint4(TICK_ACTIVE | ((a & 3u) << 1) | (b << 16), imm, (uint32_t)dl, (uint32_t)(dl >> 32));
+                pc++;
+            } else if (K::FK && op == MS_OP_INTERVAL_RESET) {   // Interval::reset: Sleep::reset(now + period) — no floor, no behaviour
+                const uint4 tu = TU(c, slot, P.tick_unit);
+                const uint64_t dl = L.clock + (uint64_t)(tu.x >> 16) * NS_PER_S + tu.y;
+                TWORD(c, slot, P.tick_unit, 2) = (uint32_t)dl;
+                TWORD(c, slot, P.tick_unit, 3) = (uint32_t)(dl >> 32);
+                pc++;
+            } else if (K::FS && op == MS_OP_TIMEOUT_BEGIN) {     // timeout(d, ..): its Sleep exists from here on (sleep(d): 1 ms floor, no timer yet)
                 const uint64_t sd = sleep_deadline(L, L.clock + (uint64_t)a * NS_PER_S + imm);
                 TU(c, slot, P.scope_unit) = make_uint4(b | SCOPE_ACTIVE, 0, (uint32_t)sd, (uint32_t)(sd >> 32));
                 pc++;
@@ -1074,6 +1111,12 @@ __device__ __forceinline__ bool poll_task(const Ctx& c, Lane& L, const uint32_t 
                 // every workload with the op to one.  (Under `default`, not a case of its own: the base-op builds' switch — the headline
                 // kernel's — keeps round 5's code byte for byte; a case label here cost it 1.4 % on the GPU, profiles/r6_experiments.md.)
                 if (K::LIFE && op == MS_OP_SET_LATENCY) { L.loss_always = (L.loss_always & ~0x70u) | (((a & 3u) + 1u) << 4); pc++; }
+                else if (K::FK && op == MS_OP_TICK) {     // ticker.tick(): a deadline that has passed is Ready at this first poll — no timer, no
+                    const uint4 tu = TU(c, slot, P.tick_unit);     // yield, the body goes on in this poll; else a Sleep begins at the deadline
+                    const uint64_t dl = u64of(tu.z, tu.w);
+                    if (L.clock >= dl) { tick_complete<K>(c, L, slot, tu, a); pc++; }
+                    else { deadline = dl; want_sleep = true; }
+                }
                 else st = ST_PANIC;
                 break;
             }

@@ -39,6 +39,8 @@ enum : uint32_t { TF_ALIVE = 1, TF_SCHED = 2, TF_RUN = 4, TF_KILLED = 8, TF_CANC
                   TF_OWNER = 128 /* this task has bound an Endpoint: its finish must look for sockets to close */ };
 // scope unit word 0 (timeout scopes, KParams.scope_unit): END pc | SCOPE_ACTIVE | SCOPE_MADE (a connect1 of the scope has made the task's pair)
 enum : uint32_t { SCOPE_ACTIVE = 1u << 16, SCOPE_MADE = 1u << 17 };
+// tick unit word 0 (interval tickers, KParams.tick_unit): TICK_ACTIVE | MissedTickBehavior << 1 (TICK_BURST / DELAY / SKIP) | period seconds << 16
+enum : uint32_t { TICK_ACTIVE = 1u, TICK_BURST = 0, TICK_DELAY = 1, TICK_SKIP = 2 };
 // `sub` values of a task parked in MS_OP_JOIN (bit 7 set: stage [A] of poll_task ignores them, stage [C] owns them)
 enum : uint32_t { SUB_JOIN_WAIT = 0x80, SUB_JOIN_COMPLETED = 0x81, SUB_JOIN_CANCELLED = 0x82 };
 enum : uint32_t { EV_WAKE = 1, EV_DELIVER = 2, EV_RESTART = 3,
@@ -80,6 +82,8 @@ template <bool TRACE_, bool SPILL_, int LWS_, int FEAT_, bool RQ_ = false, bool 
                           FA = (FEAT_ & MADSIM_FEAT_ADDR) != 0;
     // timeout scopes (MS_OP_TIMEOUT_BEGIN / END): outside MADSIM_FEAT_ALL, so FEAT above does not see the bit
     static constexpr bool FS = (FEAT_ & MADSIM_FEAT_SCOPE) != 0;
+    // interval tickers (MS_OP_INTERVAL / TICK / INTERVAL_RESET): outside MADSIM_FEAT_ALL as well; these builds carry FS too
+    static constexpr bool FK = (FEAT_ & MADSIM_FEAT_TICK) != 0;
 };
 
 // REG(id): divergence-model markers, compiled in only by tools/divergence_model.py's host emulation build

@@ -116,6 +116,27 @@ class TaskBuilder:
         """`with t.timeout(ms=..) as s:` — timeout_begin / timeout_end around the block; `s.end` is its END as a jump target."""
         return _ScopeCtx(self, self.timeout_begin(**kw))
 
+    # -- interval tickers: madsim::time::interval / interval_at, Interval::tick / reset (time/interval.rs) ----------------------------
+    TICK_BEHAVIOR = {"burst": 0, "delay": 1, "skip": 2}
+
+    def interval(self, behavior="burst", at_mark=False, **kw):
+        """`let mut i = interval(period)` (or `interval_at(t0, period)` with at_mark, t0 = this program's mark()), with
+        `i.set_missed_tick_behavior(..)`.  The first tick comes at max(start, now + 1 ms); executed again, it replaces the ticker."""
+        b, imm = _dur(**kw)
+        if b == 0 and imm == 0:
+            raise ValueError("interval: the period must be non-zero")
+        if behavior not in self.TICK_BEHAVIOR:
+            raise ValueError("interval: behavior is 'burst', 'delay' or 'skip'")
+        return self._emit("INTERVAL", a=self.TICK_BEHAVIOR[behavior] | (4 if at_mark else 0), b=b, imm=imm)
+
+    def tick(self, trace=False):
+        """`i.tick().await`: Ready at once when its deadline has passed (no yield); trace=True folds the instant it was scheduled for."""
+        return self._emit("TICK", a=1 if trace else 0)
+
+    def interval_reset(self):
+        """`i.reset()`: the next tick one period from now."""
+        return self._emit("INTERVAL_RESET")
+
     # -- time ------------------------------------------------------------------------------------
     def sleep(self, **kw):
         b, imm = _dur(**kw)
@@ -627,6 +648,149 @@ def raft_election(n_nodes=5, heartbeats=20, partitions=4):
     m.panic_if_flag_lt(0, 1)
     m.done()
     return wl.build()
+
+
+def raft_ticker(n_nodes=5, heartbeats=20, pauses=3, behavior="burst", min_ticks=0):
+    """raft_election with the leader's heartbeats on a ticker: `let mut hb = interval(50 ms); loop { hb.tick().await; send
+    heartbeats; .. }` (time/interval.rs), the shape of a Raft leader, lease keeper or gossip round.  Followers keep their election
+    timeout as `timeout(recv_from)`, the timer that restarts on every message.  After each tick the leader drains its mailbox for
+    up to 5 ms (late grants; a rival's heartbeat makes it step down), so the cadence is the ticker's, not the drain's.
+
+    The supervisor pauses a node for ~4-5 periods and resumes it (`Handle::pause` / `resume`): when it is the leader, its
+    overdue ticks come due together — Burst sends them back to back, Delay and Skip pick a later deadline — and it clogs one
+    link at a time.  Every tick is traced with its scheduled instant and counted in flag 1.  The run panics if no leader was ever
+    elected, and with min_ticks > 0 also if the leaders ticked fewer than min_ticks times in all (a configuration some seeds fail)."""
+    MAIN, VREQ = 1, 2
+    GRANT = 1
+    wl = WorkloadBuilder()
+    nodes = [wl.create_node() for _ in range(n_nodes)]
+    addrs = [wl.addr(n, 1) for n in nodes]
+    need = n_nodes // 2
+    mains = []
+    for i, n in enumerate(nodes):
+        peers = [j for j in range(n_nodes) if j != i]
+        t = wl.task(n)
+        v = wl.task(n)
+        t.bind(addrs[i])
+        t.spawn(v)
+        follower = t.label()
+        t.recv_from_timeout(addrs[i], MAIN, ms=150 + 40 * i)
+        cand_jump = len(t.code); t.jeq(A.VAL_TIMEOUT, 0)
+        t.jmp(follower)
+        candidate = t.label()
+        t.code[cand_jump][2] = candidate
+        t.sleep_rand(lo_ms=0, ms=50)
+        for j in peers:
+            t.send_to(addrs[i], addrs[j], VREQ, i)
+        t.set(1, need)
+        collect = t.label()
+        t.recv_from_timeout(addrs[i], MAIN, ms=100)
+        t.jeq(A.VAL_TIMEOUT, follower)
+        got_grant = len(t.code); t.jeq(GRANT, 0)
+        t.jmp(follower)
+        t.code[got_grant][2] = t.label()
+        t.djnz(1, collect)
+        t.flag_add(0, 1)                                   # elected
+        t.trace(0x200 + i)
+        t.interval(ms=50, behavior=behavior)               # the leader's heartbeat ticker (first tick 1 ms from now)
+        t.set(0, heartbeats)
+        hb = t.label()
+        t.tick(trace=True)
+        t.flag_add(1, 1)
+        for j in peers:
+            t.send_to(addrs[i], addrs[j], MAIN, 100 + i)
+        t.recv_from_timeout(addrs[i], MAIN, ms=5)          # drain: late grants stay, a rival leader's heartbeat steps down
+        stay = len(t.code); t.jeq(A.VAL_TIMEOUT, 0)
+        keep = len(t.code); t.jeq(GRANT, 0)
+        t.jmp(follower)
+        t.code[stay][2] = t.label(); t.code[keep][2] = t.label()
+        t.djnz(0, hb)
+        t.jmp(follower)
+        mains.append(t)
+        top = v.label()
+        v.recv_from(addrs[i], VREQ); v.reply(addrs[i], MAIN, GRANT); v.jmp(top)
+    m = wl.main()
+    for t in mains:
+        m.spawn(t)
+    for k in range(pauses):
+        victim = nodes[k % n_nodes]
+        m.sleep_rand(lo_ms=0, ms=600)
+        m.pause(victim)
+        m.sleep_rand(lo_ms=200, ms=260)                    # 4 - 5 periods
+        m.resume(victim)
+        m.clog_link(victim, nodes[(k + 1) % n_nodes])
+        m.sleep(ms=120)
+        m.unclog_link(victim, nodes[(k + 1) % n_nodes])
+    m.sleep(secs=1)
+    m.panic_if_flag_lt(0, 1)
+    if min_ticks:
+        m.panic_if_flag_lt(1, min_ticks)
+    m.done()
+    return wl.build()
+
+
+def raft_ticker_limits():
+    """Capacities for raft_ticker: raft_election's, with wide (16-byte) heap entries and no re-registration counts (the ticker
+    builds have neither)."""
+    lim = raft_election_limits()
+    lim.state_mem = A.STATE_GLOBAL
+    return lim
+
+
+def lease_keeper(n_keepers=3, period_ms=20, svc_ms=30, behavior="skip", rounds=12):
+    """A lease holder renewing by RPC on a ticker: `let mut t = interval(period); t.set_missed_tick_behavior(Skip); loop {
+    t.tick().await; match lease.renew().await { Ok(_) => .., Err(_) => t.reset() } }`.  The lease server answers after a
+    random service time that sometimes exceeds the period, so renewals overrun their tick and the next one is late (Skip picks
+    the next multiple of the period from the start).  A renewal is a `timeout(2 * period, call)` scope; a failed one resets the
+    ticker.  The supervisor kills and restarts the server once.  Each keeper traces its ticks' instants and the renewal results."""
+    OK = 0x42
+    wl = WorkloadBuilder()
+    ns = wl.create_node()
+    asv = wl.addr(ns, 2379)
+    h = wl.task(ns)
+    h.sleep_rand(lo_ms=0, ms=svc_ms); h.rpc_reply(asv, OK); h.done()
+    srv = wl.task(ns, init=True, pre=True)
+    srv.bind(asv)
+    top = srv.label()
+    srv.rpc_recv(asv, 1); srv.spawn(h, move_request=True); srv.jmp(top)
+    keepers = []
+    for i in range(n_keepers):
+        nc = wl.create_node()
+        acl = wl.addr(nc, 1)
+        k = wl.task(nc)
+        k.bind(acl); k.sleep(ms=1 + 3 * i)
+        k.interval(ms=period_ms, behavior=behavior)
+        k.set(0, rounds)
+        loop = k.label()
+        k.tick(trace=True)
+        with k.timeout(ms=2 * period_ms):
+            k.rpc_call(acl, asv, 1, i)
+        k.trace_val()
+        ok = k.label() + 3
+        k.jeq(OK, ok)
+        k.interval_reset()                                 # renewal failed: start the period over from now
+        k.jmp(ok + 1)
+        assert k.label() == ok
+        k.flag_add(0, 1)
+        k.djnz(0, loop)
+        k.done()
+        keepers.append(k)
+    m = wl.main()
+    for k in keepers:
+        m.spawn(k)
+    m.sleep(ms=5 * period_ms); m.kill(ns); m.sleep(ms=2 * period_ms); m.restart(ns)
+    for k in keepers:
+        m.join(k)
+    m.done()
+    return wl.build()
+
+
+def lease_keeper_limits():
+    lim = A.Limits()
+    lim.max_tasks = 32
+    lim.mbox_regs, lim.mbox_msgs = 8, 8
+    lim.heap_lds_slots, lim.heap_spill_slots = 16, 112
+    return lim
 
 
 def kv_rpc(n_clients=4, n_ops=8):
