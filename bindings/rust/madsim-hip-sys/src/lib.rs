@@ -219,6 +219,8 @@ pub const MS_OP_TIMEOUT_END: u8 = 61;
 pub const MS_OP_INTERVAL: u8 = 62;
 pub const MS_OP_TICK: u8 = 63;
 pub const MS_OP_INTERVAL_RESET: u8 = 64;
+pub const MS_OP_RECV_OR_TICK: u8 = 65;
+pub const MS_OP_RECV_TIMEOUT_AT: u8 = 66;
 pub const MADSIM_PASS: u32 = 0;
 pub const MADSIM_PANIC: u32 = 1;
 pub const MADSIM_DEADLOCK: u32 = 2;
@@ -229,7 +231,7 @@ pub const MADSIM_UNSUPPORTED: u32 = 6;
 pub const MADSIM_INTERNAL: u32 = 7;
 
 // ---- #define constants -------------------------------------------------------------------------------------------
-pub const MADSIM_HIP_ABI_VERSION: u32 = 6;
+pub const MADSIM_HIP_ABI_VERSION: u32 = 7;
 pub const MADSIM_IPVS_ADD_SERVICE: u32 = 0;
 pub const MADSIM_IPVS_DEL_SERVICE: u32 = 1;
 pub const MADSIM_IPVS_ADD_SERVER: u32 = 2;

@@ -5,7 +5,7 @@
 //! run of the very same table must reproduce.
 //!
 //! Covers the base ops (datagram Endpoint API, sleeps, spawn / join / abort / yield, loop and assert glue, shared flags,
-//! clogs, kill / restart / pause / resume, observations, interval tickers).  Ops outside that set panic with "interp: unsupported op": they have
+//! clogs, kill / restart / pause / resume, observations, interval tickers, select_biased! over a receive and a tick, timeout_at).  Ops outside that set panic with "interp: unsupported op": they have
 //! hand-written twins in tools/ref_twin/src/main.rs instead.  Only built with `--features madsim` and `--cfg madsim`.
 use crate::workload::Workload;
 use madsim::net::{Endpoint, NetSim};
@@ -171,6 +171,50 @@ fn run_task(sh: Arc<Shared>, prog: usize) -> Task {
                     let (len, f) = eps[&a].recv_from((b >> 8) as u64, &mut buf).await.unwrap();
                     val = sh.value_of(&buf[..len]);
                     from = Some(f);
+                }
+                sys::MS_OP_RECV_TIMEOUT_AT => {
+                    let deadline = mark.expect("timeout_at before mark") + dur(b & 0xff, imm);
+                    match time::timeout_at(deadline, eps[&a].recv_from((b >> 8) as u64, &mut buf)).await {
+                        Ok(r) => {
+                            let (len, f) = r.unwrap();
+                            val = sh.value_of(&buf[..len]);
+                            from = Some(f);
+                        }
+                        Err(_) => val = sys::MADSIM_VAL_TIMEOUT,
+                    }
+                }
+                sys::MS_OP_RECV_OR_TICK => {
+                    // select! { biased; .. }: each poll polls the two arms in the program's order, the first Ready wins, the other is dropped
+                    let won = {
+                        let mut rx = std::pin::pin!(eps[&a].recv_from((b >> 8) as u64, &mut buf));
+                        let mut tk = std::pin::pin!(ticker.as_mut().expect("recv_or_tick before interval").tick());
+                        std::future::poll_fn(|cx| {
+                            use std::task::Poll;
+                            if b & 1 == 1 {
+                                if let Poll::Ready(at) = tk.as_mut().poll(cx) { return Poll::Ready(Err(at)); }
+                            }
+                            if let Poll::Ready(r) = rx.as_mut().poll(cx) { return Poll::Ready(Ok(r)); }
+                            if b & 1 == 0 {
+                                if let Poll::Ready(at) = tk.as_mut().poll(cx) { return Poll::Ready(Err(at)); }
+                            }
+                            Poll::Pending
+                        })
+                        .await
+                    };
+                    match won {
+                        Ok(r) => {
+                            let (len, f) = r.unwrap();
+                            val = sh.value_of(&buf[..len]);
+                            from = Some(f);
+                        }
+                        Err(at) => {
+                            val = sys::MADSIM_VAL_TIMEOUT;
+                            if b & 2 == 2 {
+                                let t0: Option<Instant> = *sh.t0.lock().unwrap();
+                                sh.observe(at.duration_since(t0.expect("t0")).as_nanos() as u64);
+                            }
+                        }
+                    }
                 }
                 sys::MS_OP_ASSERT_VAL => assert_eq!(val, imm),
                 sys::MS_OP_CLOSE => { eps.remove(&a); }

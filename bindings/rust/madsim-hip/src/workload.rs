@@ -118,6 +118,16 @@ impl TaskBuilder {
     }
     pub fn tick(&mut self, trace: bool) -> &mut Self { self.emit(sys::MS_OP_TICK, trace as u8, 0, 0, false) }
     pub fn interval_reset(&mut self) -> &mut Self { self.emit(sys::MS_OP_INTERVAL_RESET, 0, 0, 0, false) }
+    /// `select! { biased; (msg, from) = ep.recv_from(tag) => .., _ = i.tick() => .. }` on this program's ticker (`tick_first`: the tick
+    /// arm first).  A won tick sets `val = MADSIM_VAL_TIMEOUT`; `trace` folds the instant it was scheduled for.
+    pub fn recv_or_tick(&mut self, ep: Addr, tag: u8, tick_first: bool, trace: bool) -> &mut Self {
+        self.emit(sys::MS_OP_RECV_OR_TICK, ep.0, ((tag as u16) << 8) | tick_first as u16 | ((trace as u16) << 1), 0, false)
+    }
+    /// `timeout_at(t0 + d, ep.recv_from(tag)).await`, t0 = this program's `mark()`: `val = MADSIM_VAL_TIMEOUT` on `Err(Elapsed)`
+    pub fn recv_from_timeout_at(&mut self, ep: Addr, tag: u8, d: Duration) -> &mut Self {
+        assert!(d.as_secs() <= 255);
+        self.emit(sys::MS_OP_RECV_TIMEOUT_AT, ep.0, ((tag as u16) << 8) | d.as_secs() as u16, d.subsec_nanos(), false)
+    }
     // ---- supervisor ----------------------------------------------------------------------------------------------------------
     pub fn kill(&mut self, node: u8) -> &mut Self { self.emit(sys::MS_OP_KILL, node, 0, 0, false) }
     pub fn restart(&mut self, node: u8) -> &mut Self { self.emit(sys::MS_OP_RESTART, node, 0, 0, false) }

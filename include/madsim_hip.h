@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define MADSIM_HIP_ABI_VERSION 6u
+#define MADSIM_HIP_ABI_VERSION 7u
 
 /* ------------------------------------------------------------------------------------------------
  * Workload: the actor program (read-only, caller-owned POD).
@@ -178,6 +178,25 @@ enum madsim_op {
                               timeout scope: its expiry drops the tick future only, the ticker keeps its deadline.            */
     MS_OP_INTERVAL_RESET = 64,/* ticker.reset(): next deadline := now + period (no floor, no behaviour).  Never awaits.  Needs a ticker,
                               as MS_OP_TICK does.                                                                             */
+    /* -- ABI v7: select_biased! over a receive and a time arm (time/mod.rs:128-156, futures' select_biased!) --------------------- */
+    MS_OP_RECV_OR_TICK = 65,/* a=sock, b=(tag<<8)|flags: select! { biased; (msg, from) = ep.recv_from(tag) => .., _ = ticker.tick() => .. },
+                              the two arms in the order flags bit 0 gives (0 recv first, 1 tick first); every poll polls both in
+                              that order, the first Ready wins and the other is dropped.  The recv arm is MS_OP_RECV_TIMEOUT's:
+                              nothing before its first poll, then Mailbox::recv (take a queued message or register), then
+                              rand_delay (one draw, 1 ms floor: Pending at first).  Dropped after it took its message, the
+                              message is lost (its draw and its timer stay); dropped while registered, the registration is
+                              dead.  The tick arm is MS_OP_TICK's: deadline passed -> Ready in that poll, no timer; else a
+                              timer at the deadline on every poll that leaves it Pending; dropped, the ticker keeps its
+                              deadline and its timers stay.  Tick first with the deadline passed: the tick wins at the first
+                              poll, no registration, no draw, no yield.  Recv wins: val / from as MS_OP_RECV_TIMEOUT sets them.
+                              Tick wins: val := MADSIM_VAL_TIMEOUT, the ticker advances as MS_OP_TICK's does, flags bit 1 folds
+                              the tick's scheduled instant (MS_OP_TICK a=1).  Every path from the program's entry must pass an
+                              MS_OP_INTERVAL first.  Not inside a timeout scope.  (tokio's unbiased select! starts at a branch
+                              its thread-local FastRand picks: not restated)                                               */
+    MS_OP_RECV_TIMEOUT_AT = 66,/* a=sock, b=(tag<<8)|secs, imm=ns (< 10^9): timeout_at(t0 + d, ep.recv_from(tag)).await, t0 = the
+                              program's MARK (which must stand at a lower pc); the deadline max(t0 + d, now + 1 ms) is fixed when
+                              the op starts (time/mod.rs:144-156, the sleep_until floor).  Otherwise MS_OP_RECV_TIMEOUT: a message
+                              does not move the deadline.  Not inside a timeout scope.                                      */
     MS_OP__COUNT
 };
 #define MADSIM_IPVS_ADD_SERVICE 0u
@@ -628,7 +647,8 @@ typedef struct madsim_geometry {
                                     * fold (madsim_limits_t.no_trace_hash on a base-op workload), bit 14 = the compact base-op layout (MADSIM_STATE_COMPACT), bit 15 = 8-byte
                                     * timer-heap entries (MADSIM_STATE_NARROW_HEAP); bits 16-19 = compile-time log2 lane
                                     * stride (15 = runtime); bit 20 = timeout scopes compiled in (MS_OP_TIMEOUT_BEGIN / END); bit 21 = interval
-                                    * tickers compiled in (MS_OP_INTERVAL / TICK / INTERVAL_RESET) */
+                                    * tickers compiled in (MS_OP_INTERVAL / TICK / INTERVAL_RESET); bit 22 = selects compiled in (MS_OP_RECV_OR_TICK /
+                                    * RECV_TIMEOUT_AT, v7) */
     uint32_t global_bytes_per_seed; /* size of a lane's state block in global memory (global-state builds), else 0 */
 } madsim_geometry_t;
 int madsim_hip_geometry(const madsim_workload_t* w, const madsim_limits_t* lim, madsim_geometry_t* g);

@@ -181,6 +181,16 @@ class Task {
     }
     Task& tick(bool trace = false) { return emit(MS_OP_TICK, trace ? 1 : 0); }
     Task& interval_reset() { return emit(MS_OP_INTERVAL_RESET); }
+    // select! { biased; recv_from(tag), ticker.tick() } (tick_first: the tick arm first) and timeout_at(t0 + d, recv_from(tag)), t0 = this
+    // program's mark() (MS_OP_RECV_OR_TICK / MS_OP_RECV_TIMEOUT_AT, ABI v7).  A won tick or an expired deadline: val = MADSIM_VAL_TIMEOUT.
+    Task& recv_or_tick(int ep, uint8_t tag, bool tick_first = false, bool trace = false) {
+        return emit(MS_OP_RECV_OR_TICK, (uint8_t)ep, (uint16_t)((tag << 8) | (tick_first ? 1 : 0) | (trace ? 2 : 0)));
+    }
+    Task& recv_from_timeout_at(int ep, uint8_t tag, std::chrono::nanoseconds d) {
+        uint64_t ns = (uint64_t)d.count();
+        if (ns / 1000000000ull > 0xff) throw std::invalid_argument("recv_from_timeout_at: at most 255 s");
+        return emit(MS_OP_RECV_TIMEOUT_AT, (uint8_t)ep, (uint16_t)((tag << 8) | (ns / 1000000000ull)), (uint32_t)(ns % 1000000000ull));
+    }
     // time::timeout(d, async { .. }) over the ops up to timeout_end(scope) (MS_OP_TIMEOUT_BEGIN / END): returns the scope handle;
     // jmp_scope_end / jeq_scope_end jump to its END before it exists (an early return, connect1's `?`).  Expired: val = MADSIM_VAL_TIMEOUT.
     int timeout_begin(std::chrono::nanoseconds d) {

@@ -6,7 +6,7 @@ same structs, so a parity test hands identical bytes to both sides.
 """
 import ctypes as C
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 U64_MAX = (1 << 64) - 1
 LIMIT_NONE = 0xFFFFFFFF
 SCHED_STATIC, SCHED_QUEUE = 0, 1
@@ -135,6 +135,7 @@ class Geometry(C.Structure):
 
 VARIANT_SCOPE = 1 << 20     # madsim_geometry_t.variant: timeout scopes (MS_OP_TIMEOUT_BEGIN / END) compiled in
 VARIANT_TICK = 1 << 21      # madsim_geometry_t.variant: interval tickers (MS_OP_INTERVAL / TICK / INTERVAL_RESET) compiled in
+VARIANT_SELECT = 1 << 22    # madsim_geometry_t.variant: selects over a receive and a tick, timeout_at (MS_OP_RECV_OR_TICK / RECV_TIMEOUT_AT) compiled in
 
 
 HEADER_STRUCTS["madsim_campaign_t"] = Campaign
@@ -160,7 +161,7 @@ OP = dict(
     BIND=20, SEND=21, REPLY=22, RECV=23, ASSERT_VAL=24, RECV_TIMEOUT=25, CLOSE=26,
     KILL=30, RESTART=31, PAUSE=32, RESUME=33, CLOG_NODE=34, UNCLOG_NODE=35, CLOG_LINK=36,
     UNCLOG_LINK=37, ASSERT_EXIT=38, SET_LOSS=39, SLEEP_RAND=40, GSET=41, GADD=42, ASSERT_G=43, PANIC_IF_G_LT=44, JEQ=45, CONNECT=46, ACCEPT=47, CSEND=48, CRECV=49, CCLOSE=50, RPC_CALL=51, RPC_REPLY=52, RAND_BOOL=53, RANDOM=54, TRACE_TIME=55, HOOK_REQ=56, HOOK_RSP=57, IPVS=58, SET_LATENCY=59,
-    TIMEOUT_BEGIN=60, TIMEOUT_END=61, INTERVAL=62, TICK=63, INTERVAL_RESET=64,
+    TIMEOUT_BEGIN=60, TIMEOUT_END=61, INTERVAL=62, TICK=63, INTERVAL_RESET=64, RECV_OR_TICK=65, RECV_TIMEOUT_AT=66,
 )
 PROG_INIT, PROG_PRE, PROG_DROP_SPAWN = 1, 2, 4
 NODE_RESTART_ON_PANIC = 1

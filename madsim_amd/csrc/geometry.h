@@ -124,11 +124,15 @@ inline int validate(const madsim_workload_t* w, const madsim_config_t* cfg, std:
         case MS_OP_DJNZ: case MS_OP_JMP: case MS_OP_JEQ:
             if (in.b >= w->n_insns) return fail(err, MADSIM_E_WORKLOAD, "jump target out of range"); break;
         case MS_OP_BIND: case MS_OP_REPLY: case MS_OP_RECV: case MS_OP_CLOSE: case MS_OP_RECV_TIMEOUT: case MS_OP_ACCEPT:
+        case MS_OP_RECV_OR_TICK: case MS_OP_RECV_TIMEOUT_AT:
             if (in.a >= w->n_socks) return fail(err, MADSIM_E_WORKLOAD, "socket operand out of range");
             // (the reference would let an IP-less node bind it and answer AddrNotAvailable to every other: not modelled, refused)
             if (w->socks[in.a].kind == MADSIM_ADDR_VIRTUAL) return fail(err, MADSIM_E_WORKLOAD, "a virtual address is a destination only: it cannot be bound or used as an Endpoint");
-            if ((in.op == MS_OP_REPLY || in.op == MS_OP_RECV || in.op == MS_OP_RECV_TIMEOUT) && (in.b >> 8) > MADSIM_TAG_RPC_LAST)
+            if ((in.op == MS_OP_REPLY || in.op == MS_OP_RECV || in.op == MS_OP_RECV_TIMEOUT || in.op == MS_OP_RECV_OR_TICK || in.op == MS_OP_RECV_TIMEOUT_AT)
+                && (in.b >> 8) > MADSIM_TAG_RPC_LAST)
                 return fail(err, MADSIM_E_WORKLOAD, "tags 0xFE and 0xFF are reserved");
+            if (in.op == MS_OP_RECV_OR_TICK && (in.b & 0xfc)) return fail(err, MADSIM_E_WORKLOAD, "recv_or_tick: b bits 0-1 are the flags (1 tick arm first, 2 fold the tick's instant)");
+            if (in.op == MS_OP_RECV_TIMEOUT_AT && in.imm >= 1000000000u) return fail(err, MADSIM_E_WORKLOAD, "recv_from_timeout_at: imm is the nanoseconds below one second");
             break;
         case MS_OP_SEND: case MS_OP_CONNECT:
             if (in.a >= w->n_socks || (uint32_t)(in.b & 0xff) >= w->n_socks) return fail(err, MADSIM_E_WORKLOAD, "socket operand out of range");
@@ -171,6 +175,8 @@ inline int validate(const madsim_workload_t* w, const madsim_config_t* cfg, std:
             if (op == MS_OP_MARK) marked = true;
             else if ((op == MS_OP_SLEEP_UNTIL || op == MS_OP_ASSERT_ELAPSED) && !marked)
                 return fail(err, MADSIM_E_WORKLOAD, "sleep_until / assert_elapsed before the program's first mark: t0 is not assigned yet");
+            else if (op == MS_OP_RECV_TIMEOUT_AT && !marked)
+                return fail(err, MADSIM_E_WORKLOAD, "recv_from_timeout_at before the program's first mark: t0 is not assigned yet");
         }
     }
     {   // timeout scopes (MS_OP_TIMEOUT_BEGIN .. MS_OP_TIMEOUT_END): time::timeout(d, async { .. }) with the block's awaits inside.  A scope covers
@@ -232,7 +238,7 @@ inline int validate(const madsim_workload_t* w, const madsim_config_t* cfg, std:
             if (is_entry[i]) marked = false;
             const madsim_insn_t& in = w->insns[i];
             if (in.op == MS_OP_MARK) marked = true;
-            if (in.op == MS_OP_TICK || in.op == MS_OP_INTERVAL_RESET) ticks = true;
+            if (in.op == MS_OP_TICK || in.op == MS_OP_INTERVAL_RESET || in.op == MS_OP_RECV_OR_TICK) ticks = true;
             if (in.op != MS_OP_INTERVAL) continue;
             if (in.b == 0 && in.imm == 0) return fail(err, MADSIM_E_WORKLOAD, "interval: the period must be non-zero");
             if ((in.a & 3) == 3 || in.a > 7) return fail(err, MADSIM_E_WORKLOAD, "interval: a bits 0-1 are the missed-tick behaviour (0 burst, 1 delay, 2 skip), bit 2 interval_at");
@@ -247,8 +253,8 @@ inline int validate(const madsim_workload_t* w, const madsim_config_t* cfg, std:
             while (!work.empty()) {
                 const uint32_t i = work.back(); work.pop_back();
                 const madsim_insn_t& in = w->insns[i];
-                if (in.op == MS_OP_TICK || in.op == MS_OP_INTERVAL_RESET)
-                    return fail(err, MADSIM_E_WORKLOAD, "tick / interval_reset on a path from the program's entry that passes no interval: the ticker does not exist yet");
+                if (in.op == MS_OP_TICK || in.op == MS_OP_INTERVAL_RESET || in.op == MS_OP_RECV_OR_TICK)
+                    return fail(err, MADSIM_E_WORKLOAD, "tick / interval_reset / recv_or_tick on a path from the program's entry that passes no interval: the ticker does not exist yet");
                 if (in.op == MS_OP_INTERVAL || in.op == MS_OP_DONE || in.op == MS_OP_PANIC) continue;
                 if (in.op == MS_OP_JMP) { edge(in.b); continue; }
                 if (in.op == MS_OP_DJNZ || in.op == MS_OP_JEQ) edge(in.b);
@@ -350,6 +356,7 @@ inline int make_geometry(const Device& g, const madsim_workload_t* w, const mads
     P.heap_lds = L.heap_lds_slots ? L.heap_lds_slots : 8;
     P.heap_spill = (L.heap_lds_slots || L.heap_spill_slots) ? L.heap_spill_slots : 56;
     bool t0 = uses_op(w, MS_OP_MARK) || uses_op(w, MS_OP_SLEEP_UNTIL) || uses_op(w, MS_OP_ASSERT_ELAPSED) || uses_op(w, MS_OP_RECV_TIMEOUT) || P.uses_rpc;
+    t0 |= uses_op(w, MS_OP_RECV_OR_TICK) || uses_op(w, MS_OP_RECV_TIMEOUT_AT);      // (the receive of either rides RECV_TIMEOUT's path)
     // (MS_OP_CCLOSE alone counts too: without the connection unit a stray `drop((tx, rx))` read the task's flag word as a connection id)
     P.uses_chan = uses_op(w, MS_OP_CONNECT) || uses_op(w, MS_OP_ACCEPT) || uses_op(w, MS_OP_CSEND) || uses_op(w, MS_OP_CRECV) || uses_op(w, MS_OP_CCLOSE);
     // task units: 0-1 always; 2 = {t0, timeout()'s deadline} when used; then the connection unit, then the RPC unit
@@ -405,6 +412,7 @@ inline int make_geometry(const Device& g, const madsim_workload_t* w, const mads
     P.features = 0;
     if (uses_op(w, MS_OP_RECV_TIMEOUT) || uses_op(w, MS_OP_MARK) || uses_op(w, MS_OP_SLEEP_UNTIL) || uses_op(w, MS_OP_ASSERT_ELAPSED) ||
         uses_op(w, MS_OP_ADVANCE) || uses_op(w, MS_OP_TRACE_TIME) || P.uses_set_lat) P.features |= MADSIM_FEAT_TIME;   // (set_latency: any extended build; this is the leanest)
+    if (uses_op(w, MS_OP_RECV_OR_TICK) || uses_op(w, MS_OP_RECV_TIMEOUT_AT)) P.features |= MADSIM_FEAT_TIME;
     if (P.uses_chan) P.features |= MADSIM_FEAT_CHAN;
     if (P.uses_rpc) P.features |= MADSIM_FEAT_RPC | MADSIM_FEAT_TIME;            // call_timeout rides the timeout unit
     if (P.has_restart_on_panic || uses_op(w, MS_OP_KILL) || uses_op(w, MS_OP_RESTART) || uses_op(w, MS_OP_PAUSE) || uses_op(w, MS_OP_RESUME) ||
@@ -416,8 +424,12 @@ inline int make_geometry(const Device& g, const madsim_workload_t* w, const mads
     const bool scopes = uses_op(w, MS_OP_TIMEOUT_BEGIN);
     if (trace) P.features = MADSIM_FEAT_ALL;          // the trace build carries every class
     if (scopes) P.features |= MADSIM_FEAT_SCOPE;      // (outside MADSIM_FEAT_ALL: only these workloads select the scope builds)
-    const bool ticks = uses_op(w, MS_OP_INTERVAL);
-    if (ticks) P.features |= MADSIM_FEAT_TICK;        // (likewise: only these workloads select the ticker builds)
+    // (likewise: only these workloads select the ticker builds; those with the selects of ABI v7, the select builds — a workload with
+    //  timeout_at and no ticker runs there without the tick unit, only INTERVAL allocates it)
+    const bool selects = uses_op(w, MS_OP_RECV_OR_TICK) || uses_op(w, MS_OP_RECV_TIMEOUT_AT);
+    const bool ticks = uses_op(w, MS_OP_INTERVAL) || selects;
+    if (ticks) P.features |= MADSIM_FEAT_TICK;
+    if (selects) P.features |= MADSIM_FEAT_SELECT;
     P.lifecycle = P.features != 0;
     const uint32_t cus = g.num_cus > 0 ? (uint32_t)g.num_cus : 256u;
     uint32_t lw = 64;
@@ -438,7 +450,7 @@ inline int make_geometry(const Device& g, const madsim_workload_t* w, const mads
             const madsim_insn_t& in = w->insns[i];
             if (in.op == MS_OP_SLEEP || in.op == MS_OP_SLEEP_RAND || in.op == MS_OP_SLEEP_UNTIL || in.op == MS_OP_ADVANCE)
                 horizon = std::max<uint64_t>(horizon, (uint64_t)in.b * 1000000000ull + in.imm);
-            if (in.op == MS_OP_RECV_TIMEOUT) horizon = std::max<uint64_t>(horizon, (uint64_t)(in.b & 0xff) * 1000000000ull + in.imm);
+            if (in.op == MS_OP_RECV_TIMEOUT || in.op == MS_OP_RECV_TIMEOUT_AT) horizon = std::max<uint64_t>(horizon, (uint64_t)(in.b & 0xff) * 1000000000ull + in.imm);
             if (in.op == MS_OP_RPC_CALL) horizon = std::max<uint64_t>(horizon, (uint64_t)(in.imm >> 8) * 1000000ull);
         }
         if (horizon >= (1ull << 31) - (1ull << 24)) narrow_ok = false;

@@ -105,7 +105,7 @@ __device__ __forceinline__ uint32_t spawn_task(const Ctx& c, Lane& L, uint32_t p
     tu1_store<K>(c, slot, make_uint4(0xffu << 8, (seq & 0xffffff) | (info_gen << 24), 0, 0));   // rxseq 0, no awaiter; spawn order
     if (K::FC && c.P.uses_chan) TU(c, slot, c.P.chan_unit) = make_uint4(0xff, 0, 0, 0);                // no connection held
     if constexpr (K::FS) if (!K::FK || c.P.scope_unit) TWORD(c, slot, c.P.scope_unit, 0) = 0;              // no timeout scope open
-    if constexpr (K::FK) TWORD(c, slot, c.P.tick_unit, 0) = 0;                                           // no ticker (a child does not inherit one)
+    if constexpr (K::FK) if (!K::FSEL || c.P.tick_unit) TWORD(c, slot, c.P.tick_unit, 0) = 0;            // no ticker (a child does not inherit one)
     if (K::FR && c.P.uses_rpc) { TWORD(c, slot, c.P.rpc_unit, 0) = init.move_req ? init.req : 0u; TWORD(c, slot, c.P.rpc_unit, 1) = 0; }   // no request in hand
     ready_push<K>(c, L, slot);
     if (record) HW(prog) = H_RUNNING | (slot << 8) | (gen << 16);

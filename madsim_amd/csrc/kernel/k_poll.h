@@ -52,7 +52,8 @@ __device__ __forceinline__ uint4 insn_fetch(const Ctx& c, Lane& L, uint32_t pc) 
     if (!PLAIN_ADDR && c.P.uses_eph) {
         const uint32_t op = in.x & 0xff;
         const bool own = op == MS_OP_SEND || op == MS_OP_CONNECT || op == MS_OP_RPC_CALL || op == MS_OP_REPLY || op == MS_OP_RECV ||
-                         op == MS_OP_RECV_TIMEOUT || op == MS_OP_CLOSE || op == MS_OP_ACCEPT || op == MS_OP_RPC_REPLY;   // a names an Endpoint
+                         op == MS_OP_RECV_TIMEOUT || op == MS_OP_CLOSE || op == MS_OP_ACCEPT || op == MS_OP_RPC_REPLY ||   // a names an Endpoint
+                         (K::FSEL && (op == MS_OP_RECV_OR_TICK || op == MS_OP_RECV_TIMEOUT_AT));
         const uint32_t s = (in.x >> 8) & 0xff;
         if (own && (SOCKW(c, s) & 0x8000u)) {
             if (handle_names_its_socket<K>(c, s)) in.x = (in.x & ~0xff00u) | (sock_resolve<K>(c, s) << 8);
@@ -83,6 +84,27 @@ __device__ __forceinline__ void tick_complete(const Ctx& c, Lane& L, uint32_t sl
     TWORD(c, slot, c.P.tick_unit, 2) = (uint32_t)next;
     TWORD(c, slot, c.P.tick_unit, 3) = (uint32_t)(next >> 32);
     if (a & 1) L.obs_hash = (L.obs_hash ^ dl) * FNV_PRIME;
+}
+
+// The tick arm of MS_OP_RECV_OR_TICK's select! (Interval::poll_tick, time/interval.rs:142-169), polled after the task's Mailbox::recv.  Its
+// deadline has passed: Ready — the recv arm is dropped (its registration goes dead, and a message it took is lost in its rand_delay, whose draw
+// and timer stay: the statements of k_poll's RX_DROP), val := TIMEOUT, the ticker advances (tick_complete, `fold & 1` folds the instant).  Else
+// ANOTHER timer at the deadline (time/sleep.rs:47-54; `again`: not the select's first poll) and the select stays Pending.
+template <class K>
+__device__ __forceinline__ bool select_tick_arm(const Ctx& c, Lane& L, uint32_t slot, uint32_t gen, uint4& u0, uint4& u1, bool& u1_dirty,
+                                                bool again, uint32_t fold) {
+    const uint4 tu = TU(c, slot, c.P.tick_unit);
+    const uint64_t dl = u64of(tu.z, tu.w);
+    if (L.clock >= dl) {
+        u1.x = (u1.x & ~0xffu) | (((u1.x & 0xff) + 1) & 0xff); u1_dirty = true;
+        if ((u1.x & 0xff) == 0) u0.x |= TF_RXWRAP;
+        u0.x &= ~TF_INBOX;
+        tick_complete<K>(c, L, slot, tu, fold);
+        u0.w = MADSIM_VAL_TIMEOUT;
+        return true;
+    }
+    timer_schedule<K>(c, L, dl, (EV_WAKE << EV_SHIFT) | (gen << 8) | slot, 0, true, again);
+    return false;
 }
 
 __device__ __forceinline__ bool is_light(uint32_t op) {
@@ -140,7 +162,13 @@ __device__ __forceinline__ bool poll_task(const Ctx& c, Lane& L, const uint32_t 
     // the block.  (A macro, like RQ_GET: the builds without scopes never see it.)
 #define SCOPE_DROP_CONN(sx_) do { if ((sx_) & SCOPE_MADE) { const uint32_t cx_ = cu0_get(); \
         if ((cx_ & 0xff) != 0xff) { conn_drop_handles<K>(c, L, cx_ & 0xff, (cx_ >> 8) & 1, (u0.x & TF_KILLED) != 0); cu0_set(cx_ | 0xff); } } } while (0)
-    auto recv_timeout_poll = [&]() -> bool {
+    // (select! { biased; .. } over recv_from and a ticker, MS_OP_RECV_OR_TICK (select builds, MADSIM_FEAT_SELECT): the same poll with the tick
+    //  arm in the Sleep's place, polled first when its flags say so — select_tick_arm.  The caller passes `sel` = SEL_ON | the op's flags (b & 3)
+    //  for a select, 0 otherwise.  timeout_at, MS_OP_RECV_TIMEOUT_AT, is this poll as it stands: only its deadline was computed differently.
+    //  Everything of the select sits under `if constexpr`: the other builds compile to what they were.)
+    auto recv_timeout_poll = [&](uint32_t sel = 0) -> bool {
+        if constexpr (K::FSEL) if ((sel & (SEL_ON | SEL_TICK_FIRST)) == (SEL_ON | SEL_TICK_FIRST) &&
+                                    select_tick_arm<K>(c, L, slot, gen, u0, u1, u1_dirty, !first_poll, sel >> 1)) return true;
         bool fut_ready = false;
         bool d1_new = false;
         if (sub == 1 && (u0.x & TF_INBOX)) {                 // oneshot ready -> rand_delay (endpoint.rs:145)
@@ -158,6 +186,11 @@ __device__ __forceinline__ bool poll_task(const Ctx& c, Lane& L, const uint32_t 
             else timer_schedule<K>(c, L, d1, (EV_WAKE << EV_SHIFT) | (gen << 8) | slot, 0, true, !d1_new);
         }
         if (fut_ready) return true;                          // Ok((len, from))
+        if constexpr (K::FSEL) if (sel & SEL_ON) {
+            if (!(sel & SEL_TICK_FIRST) && select_tick_arm<K>(c, L, slot, gen, u0, u1, u1_dirty, !first_poll, sel >> 1)) return true;
+            st = ST_PENDING;
+            return false;
+        }
         uint64_t d2;
         if (K::G) d2 = u64of(pp.d2lo, pp.d2hi);              // (came with unit 0: k_state.h PollPrefetch)
         else { uint4 u2 = TU(c, slot, 2); d2 = u64of(u2.z, u2.w); }
@@ -362,8 +395,9 @@ __device__ __forceinline__ bool poll_task(const Ctx& c, Lane& L, const uint32_t 
                 }
             } else if (op == MS_OP_YIELD) {
                 completed = true;
-            } else if (K::FT && op == MS_OP_RECV_TIMEOUT) {
-                completed = recv_timeout_poll();            // (false: st is Pending — the round leaves behind [B], no `break` here)
+            } else if (K::FT && (op == MS_OP_RECV_TIMEOUT || (K::FSEL && (op == MS_OP_RECV_TIMEOUT_AT || op == MS_OP_RECV_OR_TICK)))) {
+                if constexpr (K::FSEL) completed = recv_timeout_poll(op == MS_OP_RECV_OR_TICK ? SEL_ON | (b & 3u) : 0u);
+                else completed = recv_timeout_poll();       // (false: st is Pending — the round leaves behind [B], no `break` here)
             } else if (K::FR && op == MS_OP_RPC_CALL) {
                 completed = rpc_call_poll() && st == ST_RUN;
             } else if (K::FC && op == MS_OP_ACCEPT && sub == 2) {
@@ -632,7 +666,8 @@ __device__ __forceinline__ bool poll_task(const Ctx& c, Lane& L, const uint32_t 
         // Both kinds request them HERE, in one instruction stream for the lanes of either, so the wave waits once for the two handlers, not once in
         // each (a wave runs every handler some lane is in; each handler's wait holds all 64 lanes).  Nothing is stored between here and the handlers.
         uint32_t c_hdr = 0, c_q0 = 0, c_q1 = 0;
-        if (RecvPrefetch<K>::ON && ((op == MS_OP_RECV && sub == 0) || (K::FT && op == MS_OP_RECV_TIMEOUT))) {
+        if (RecvPrefetch<K>::ON && ((op == MS_OP_RECV && sub == 0) || (K::FT && op == MS_OP_RECV_TIMEOUT) ||
+                                    (K::FSEL && (op == MS_OP_RECV_TIMEOUT_AT || op == MS_OP_RECV_OR_TICK)))) {
             c_hdr = SW(c, a, 0); c_q0 = SW(c, a, 2 + P.mbox_regs); c_q1 = SW(c, a, 3 + P.mbox_regs);
         }
         // (... and the first reads of `spawn` and of a task that ends — the two rare-op handlers every pass of the topology runs: with the receives'
@@ -694,11 +729,21 @@ __device__ __forceinline__ bool poll_task(const Ctx& c, Lane& L, const uint32_t 
             want_delay = (sub == 2);                       // endpoint.rs:145 rand_delay
         } else if (op == MS_OP_SEND || op == MS_OP_REPLY || op == MS_OP_BIND || (K::FC && (op == MS_OP_CONNECT || op == MS_OP_ACCEPT)) || (K::FR && op == MS_OP_RPC_REPLY)) {
             want_delay = true;                             // net/mod.rs:306,344,457, endpoint.rs:198: rand_delay first
-        } else if (K::FT && op == MS_OP_RECV_TIMEOUT) {
+        } else if (K::FSEL && op == MS_OP_RECV_OR_TICK && (b & SEL_TICK_FIRST) && L.clock >= u64of((uint32_t)TWORD(c, slot, P.tick_unit, 2), (uint32_t)TWORD(c, slot, P.tick_unit, 3))) {
+            // select! { biased; tick, recv } whose tick is due at this first poll: it wins without yielding, the recv future is never polled —
+            // no registration, no draw — and the body goes on in this poll
+            tick_complete<K>(c, L, slot, TU(c, slot, P.tick_unit), b >> 1);
+            u0.w = MADSIM_VAL_TIMEOUT;
+            pc++;
+        } else if (K::FT && (op == MS_OP_RECV_TIMEOUT || (K::FSEL && (op == MS_OP_RECV_TIMEOUT_AT || op == MS_OP_RECV_OR_TICK)))) {
             uint32_t tag = b >> 8;
-            uint64_t d2 = sleep_deadline(L, L.clock + (uint64_t)(b & 0xff) * NS_PER_S + imm);   // timeout()'s Sleep
-            if (K::G) { buf_store64(c.gs, gs_addr_task(c, slot, 2 * 16u + 8u), make_uint2((uint32_t)d2, (uint32_t)(d2 >> 32))); pp.d2lo = (uint32_t)d2; pp.d2hi = (uint32_t)(d2 >> 32); }
-            else { uint4 u2 = TU(c, slot, 2); u2.z = (uint32_t)d2; u2.w = (uint32_t)(d2 >> 32); TU(c, slot, 2) = u2; }
+            if (!(K::FSEL && op == MS_OP_RECV_OR_TICK)) {      // (a select's time arm is the ticker: no Sleep of its own)
+                // timeout()'s Sleep; timeout_at(t0 + d)'s is sleep_until's, from the program's MARK
+                uint64_t d2 = sleep_deadline(L, (K::FSEL && op == MS_OP_RECV_TIMEOUT_AT ? u64of((uint32_t)TWORD(c, slot, 2, 0), (uint32_t)TWORD(c, slot, 2, 1)) : L.clock)
+                                                + (uint64_t)(b & 0xff) * NS_PER_S + imm);
+                if (K::G) { buf_store64(c.gs, gs_addr_task(c, slot, 2 * 16u + 8u), make_uint2((uint32_t)d2, (uint32_t)(d2 >> 32))); pp.d2lo = (uint32_t)d2; pp.d2hi = (uint32_t)(d2 >> 32); }
+                else { uint4 u2 = TU(c, slot, 2); u2.z = (uint32_t)d2; u2.w = (uint32_t)(d2 >> 32); TU(c, slot, 2) = u2; }
+            }
             uint32_t rxseq = ((u1.x & 0xff) + 1) & 0xff;       // Mailbox::recv (endpoint.rs:353-362)
             u1.x = (u1.x & ~0xffu) | rxseq; u1_dirty = true;
             if (rxseq == 0) u0.x |= TF_RXWRAP;
@@ -737,7 +782,8 @@ __device__ __forceinline__ bool poll_task(const Ctx& c, Lane& L, const uint32_t 
             }
             sub = 1;
             first_poll = true;
-            if (recv_timeout_poll()) { sub = 0; pc++; }
+            if constexpr (K::FSEL) { if (recv_timeout_poll(op == MS_OP_RECV_OR_TICK ? SEL_ON | (b & 3u) : 0u)) { sub = 0; pc++; } }
+            else if (recv_timeout_poll()) { sub = 0; pc++; }
             first_poll = false;
         } else if (K::FR && op == MS_OP_RPC_CALL) {          // first poll of timeout(d, ep.call(dst, req)) / ep.call(dst, req)
             if (imm >> 8) {                                    // timeout()'s Sleep exists before the call is polled

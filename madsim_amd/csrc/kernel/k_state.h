@@ -41,6 +41,9 @@ enum : uint32_t { TF_ALIVE = 1, TF_SCHED = 2, TF_RUN = 4, TF_KILLED = 8, TF_CANC
 enum : uint32_t { SCOPE_ACTIVE = 1u << 16, SCOPE_MADE = 1u << 17 };
 // tick unit word 0 (interval tickers, KParams.tick_unit): TICK_ACTIVE | MissedTickBehavior << 1 (TICK_BURST / DELAY / SKIP) | period seconds << 16
 enum : uint32_t { TICK_ACTIVE = 1u, TICK_BURST = 0, TICK_DELAY = 1, TICK_SKIP = 2 };
+// MS_OP_RECV_OR_TICK's b flags (k_poll.h): bit 0 = the tick arm is polled first, bit 1 = fold the tick's instant; SEL_ON marks a select
+// in recv_timeout_poll's argument
+enum : uint32_t { SEL_TICK_FIRST = 1u, SEL_ON = 4u };
 // `sub` values of a task parked in MS_OP_JOIN (bit 7 set: stage [A] of poll_task ignores them, stage [C] owns them)
 enum : uint32_t { SUB_JOIN_WAIT = 0x80, SUB_JOIN_COMPLETED = 0x81, SUB_JOIN_CANCELLED = 0x82 };
 enum : uint32_t { EV_WAKE = 1, EV_DELIVER = 2, EV_RESTART = 3,
@@ -84,6 +87,8 @@ template <bool TRACE_, bool SPILL_, int LWS_, int FEAT_, bool RQ_ = false, bool 
     static constexpr bool FS = (FEAT_ & MADSIM_FEAT_SCOPE) != 0;
     // interval tickers (MS_OP_INTERVAL / TICK / INTERVAL_RESET): outside MADSIM_FEAT_ALL as well; these builds carry FS too
     static constexpr bool FK = (FEAT_ & MADSIM_FEAT_TICK) != 0;
+    // selects over a receive and a tick, timeout_at (MS_OP_RECV_OR_TICK / RECV_TIMEOUT_AT): builds of their own, which carry FK and FS too
+    static constexpr bool FSEL = (FEAT_ & MADSIM_FEAT_SELECT) != 0;
 };
 
 // REG(id): divergence-model markers, compiled in only by tools/divergence_model.py's host emulation build

@@ -40,6 +40,10 @@
 /* Interval tickers (MS_OP_INTERVAL / TICK / INTERVAL_RESET, KParams.features when a workload uses them).  Outside MADSIM_FEAT_ALL like
    MADSIM_FEAT_SCOPE; ticker workloads run on builds of their own (MADSIM_FOR_EACH_TICK_VARIANT) that carry every class and the scope code. */
 #define MADSIM_FEAT_TICK 512
+/* Selects over a receive and a tick, timeout_at (MS_OP_RECV_OR_TICK / RECV_TIMEOUT_AT, ABI v7; with MADSIM_FEAT_TICK in KParams.features).
+   Builds of their own again (MADSIM_FOR_EACH_SELECT_VARIANT: the ticker builds' four shapes with the select code): the ticker builds
+   compile to what they were, so the ticker workloads pay nothing for it. */
+#define MADSIM_FEAT_SELECT 1024
 /* Global-state builds: identical wake-ups are fired as a batch (k_net.h timer_expire).  Sleep::poll registers ANOTHER timer with the same
    deadline and waker on every not-elapsed poll (time/sleep.rs:51-53), so more than half of the topology's heap entries are copies of an
    earlier one; copies leave the heap back to back, and every one after the first finds its task SCHEDULED already (or gone): a step
@@ -153,7 +157,8 @@ struct KParams {
     uint32_t* iter_est;        // one word per workload: the passes a wave of it runs, as the last finished wave counted them (0 = nothing
                                // finished yet); null = no progress-based priority (k_main.h wave_progress_priority)
     uint32_t scope_unit;       // (last: the other fields keep their kernel-argument offsets) timeout scopes (MADSIM_FEAT_SCOPE): index of the task unit {END pc | active << 16 | made << 17, -, deadline lo, hi}
-    uint32_t tick_unit;        // (after scope_unit, same reason) interval tickers (MADSIM_FEAT_TICK): index of the task unit {TICK_ACTIVE | behaviour << 1 | period s << 16, period ns, next deadline lo, hi}
+    uint32_t tick_unit;        // (after scope_unit, same reason) interval tickers (MADSIM_FEAT_TICK): index of the task unit {TICK_ACTIVE | behaviour << 1 | period s << 16, period ns, next deadline lo, hi};
+                               // 0 = none (a select build's workload without MS_OP_INTERVAL)
 };
 
 // Kernel variants (Variant<TRACE, SPILL, LWS, FEAT, RQ>): the trace build; for base-op workloads on full 64-lane waves one
@@ -208,7 +213,16 @@ struct KParams {
     X(true, true, -1, MADSIM_FEAT_ALL | MADSIM_FEAT_SCOPE | MADSIM_FEAT_TICK, false, false)      \
     X(false, true, -1, MADSIM_FEAT_ALL | MADSIM_FEAT_SCOPE | MADSIM_FEAT_TICK, false, false)     \
     X(false, true, 6, (MADSIM_FEAT_ALL & ~MADSIM_FEAT_ADDR) | MADSIM_FEAT_SCOPE | MADSIM_FEAT_TICK, false, true) \
-    X(false, true, 6, MADSIM_FEAT_ALL | MADSIM_FEAT_SCOPE | MADSIM_FEAT_TICK, false, true)
+    X(false, true, 6, MADSIM_FEAT_ALL | MADSIM_FEAT_SCOPE | MADSIM_FEAT_TICK, false, true)          \
+    MADSIM_FOR_EACH_SELECT_VARIANT(X)
+#endif
+// The builds of select workloads (MADSIM_FEAT_SELECT, with tickers, scopes or neither): the ticker builds' four shapes with the select code.
+#ifndef MADSIM_FOR_EACH_SELECT_VARIANT
+#define MADSIM_FOR_EACH_SELECT_VARIANT(X)                                                                             \
+    X(true, true, -1, MADSIM_FEAT_ALL | MADSIM_FEAT_SCOPE | MADSIM_FEAT_TICK | MADSIM_FEAT_SELECT, false, false)      \
+    X(false, true, -1, MADSIM_FEAT_ALL | MADSIM_FEAT_SCOPE | MADSIM_FEAT_TICK | MADSIM_FEAT_SELECT, false, false)     \
+    X(false, true, 6, (MADSIM_FEAT_ALL & ~MADSIM_FEAT_ADDR) | MADSIM_FEAT_SCOPE | MADSIM_FEAT_TICK | MADSIM_FEAT_SELECT, false, true) \
+    X(false, true, 6, MADSIM_FEAT_ALL | MADSIM_FEAT_SCOPE | MADSIM_FEAT_TICK | MADSIM_FEAT_SELECT, false, true)
 #endif
 
 // Which compiled specialisation of sim_kernel a parameter block runs on (one rule for the launcher and for
@@ -216,8 +230,8 @@ struct KParams {
 struct VariantSel { int trace, spill, lws, feat, rq, g; };
 inline VariantSel select_variant(const KParams& P, bool trace) {
     const int spill = P.heap_spill > 0, lw = (int)P.lw_shift, feat = (int)P.features;
-    if (feat & MADSIM_FEAT_TICK) {                                      // interval tickers (scopes or not): builds of their own, every class
-        const int tk = MADSIM_FEAT_SCOPE | MADSIM_FEAT_TICK;
+    if (feat & MADSIM_FEAT_TICK) {                                      // interval tickers (scopes or not): builds of their own, every class;
+        const int tk = MADSIM_FEAT_SCOPE | MADSIM_FEAT_TICK | (feat & MADSIM_FEAT_SELECT);   // selects: the select builds of these shapes
         if (trace) return {1, 1, -1, MADSIM_FEAT_ALL | tk, 0, 0};
         if (P.gstate_mode) return {0, 1, 6, ((feat & MADSIM_FEAT_ADDR) ? MADSIM_FEAT_ALL : MADSIM_FEAT_ALL & ~MADSIM_FEAT_ADDR) | tk, 0, 1};
         return {0, 1, -1, MADSIM_FEAT_ALL | tk, 0, 0};
@@ -276,9 +290,11 @@ inline const char* variant_mismatch(const KParams& P, const VariantSel& v, bool 
     if (v.rq && (P.max_tasks > 8 || P.lw_shift != 6 || P.lifecycle)) return "register ready queue needs <= 8 tasks, full waves, base ops";
     if (!v.spill && P.heap_spill) return "a build without the spill path on a geometry with spilled heap levels";
     const int classes = v.feat & MADSIM_FEAT_ALL;
-    if (((int)P.features & ~(classes | (v.feat & (MADSIM_FEAT_SCOPE | MADSIM_FEAT_TICK)))) != 0) return "the build lacks an op class the workload uses";
-    if ((v.feat & MADSIM_FEAT_TICK) && (!((int)P.features & MADSIM_FEAT_TICK) || !P.tick_unit || P.narrow || P.dedup_n))
+    if (((int)P.features & ~(classes | (v.feat & (MADSIM_FEAT_SCOPE | MADSIM_FEAT_TICK | MADSIM_FEAT_SELECT)))) != 0) return "the build lacks an op class the workload uses";
+    // (a select build's workload may have no tick unit: its only v7 op is recv_from_timeout_at)
+    if ((v.feat & MADSIM_FEAT_TICK) && (!((int)P.features & MADSIM_FEAT_TICK) || (!P.tick_unit && !(v.feat & MADSIM_FEAT_SELECT)) || P.narrow || P.dedup_n))
         return "an interval-ticker build on a layout without the tick unit (or with narrow entries / re-registration counts)";
+    if (((v.feat & MADSIM_FEAT_SELECT) != 0) != (((int)P.features & MADSIM_FEAT_SELECT) != 0)) return "a select build for a workload without selects (or the reverse)";
     if ((v.feat & MADSIM_FEAT_SCOPE) && !(v.feat & MADSIM_FEAT_TICK) && (!((int)P.features & MADSIM_FEAT_SCOPE) || !P.scope_unit || P.narrow || P.dedup_n))
         return "a timeout-scope build on a layout without the scope unit (or with narrow entries / re-registration counts)";
     if ((v.feat & MADSIM_FEAT_TICK) && (((int)P.features & MADSIM_FEAT_SCOPE) != 0) != (P.scope_unit != 0))

@@ -137,6 +137,22 @@ class TaskBuilder:
         """`i.reset()`: the next tick one period from now."""
         return self._emit("INTERVAL_RESET")
 
+    # -- select_biased! over a receive and a time arm (ABI v7) --------------------------------------------------------------------
+    def recv_or_tick(self, ep, tag, tick_first=False, trace=False):
+        """`select! { biased; (msg, from) = ep.recv_from(tag) => .., _ = i.tick() => .. }` on this program's ticker (tick_first: the
+        tick arm is polled first).  The recv arm wins: val / from as recv_from sets them; the tick wins: val = VAL_TIMEOUT, and
+        trace=True folds the instant the tick was scheduled for.  A message the recv arm took is lost when the tick wins while its
+        rand_delay is pending.  Only the biased form: tokio's unbiased select! starts at a branch its thread-local FastRand picks."""
+        return self._emit("RECV_OR_TICK", a=ep, b=(tag << 8) | (1 if tick_first else 0) | (2 if trace else 0))
+
+    def recv_from_timeout_at(self, ep, tag, **kw):
+        """`timeout_at(t0 + d, ep.recv_from(tag))`, t0 = this program's mark(): the deadline max(t0 + d, now + 1 ms) is fixed when
+        the receive starts, so a message does not move it.  Expired: val = VAL_TIMEOUT."""
+        b, imm = _dur(**kw)
+        if b > 0xFF:
+            raise ValueError("timeout too long")
+        return self._emit("RECV_TIMEOUT_AT", a=ep, b=(tag << 8) | b, imm=imm)
+
     # -- time ------------------------------------------------------------------------------------
     def sleep(self, **kw):
         b, imm = _dur(**kw)
@@ -790,6 +806,122 @@ def lease_keeper_limits():
     lim.max_tasks = 32
     lim.mbox_regs, lim.mbox_msgs = 8, 8
     lim.heap_lds_slots, lim.heap_spill_slots = 16, 112
+    return lim
+
+
+def raft_select(n_nodes=5, heartbeats=20, pauses=3, behavior="burst", min_ticks=0):
+    """raft_ticker with the leader's loop as madsim tests write it: `loop { select! { biased; _ = hb.tick() => send_heartbeats(),
+    (msg, from) = ep.recv_from(MAIN) => handle(msg, from) } }` (MS_OP_RECV_OR_TICK, tick arm first), so a rival leader's heartbeat
+    is seen whenever it arrives, not only inside a drain window; it makes the leader step down, a late grant is ignored.  Followers
+    keep a fixed election deadline: `let t0 = Instant::now(); timeout_at(t0 + d, ep.recv_from(MAIN))` (MS_OP_RECV_TIMEOUT_AT), re-marked
+    only on a leader heartbeat — a late grant does not move it.  Candidates, pauses and clogs are raft_ticker's.  Every tick is traced
+    with its scheduled instant and counted in flag 1; the run panics if no leader was ever elected, and with min_ticks > 0 also if the
+    leaders ticked fewer than min_ticks times in all."""
+    MAIN, VREQ = 1, 2
+    GRANT = 1
+    wl = WorkloadBuilder()
+    nodes = [wl.create_node() for _ in range(n_nodes)]
+    addrs = [wl.addr(n, 1) for n in nodes]
+    need = n_nodes // 2
+    mains = []
+    for i, n in enumerate(nodes):
+        peers = [j for j in range(n_nodes) if j != i]
+        t = wl.task(n)
+        v = wl.task(n)
+        t.bind(addrs[i])
+        t.spawn(v)
+        follower = t.label()
+        t.mark()                                           # the election deadline starts now
+        wait = t.label()
+        t.recv_from_timeout_at(addrs[i], MAIN, ms=150 + 40 * i)
+        cand_jump = len(t.code); t.jeq(A.VAL_TIMEOUT, 0)
+        t.jeq(GRANT, wait)                                 # a late grant: the deadline stays
+        t.jmp(follower)                                    # a leader's heartbeat: a new deadline
+        candidate = t.label()
+        t.code[cand_jump][2] = candidate
+        t.sleep_rand(lo_ms=0, ms=50)
+        for j in peers:
+            t.send_to(addrs[i], addrs[j], VREQ, i)
+        t.set(1, need)
+        collect = t.label()
+        t.recv_from_timeout(addrs[i], MAIN, ms=100)
+        t.jeq(A.VAL_TIMEOUT, follower)
+        got_grant = len(t.code); t.jeq(GRANT, 0)
+        t.jmp(follower)
+        t.code[got_grant][2] = t.label()
+        t.djnz(1, collect)
+        t.flag_add(0, 1)                                   # elected
+        t.trace(0x200 + i)
+        t.interval(ms=50, behavior=behavior)               # the leader's heartbeat ticker (first tick 1 ms from now)
+        t.set(0, heartbeats)
+        hb = t.label()
+        t.recv_or_tick(addrs[i], MAIN, tick_first=True, trace=True)
+        tick_jump = len(t.code); t.jeq(A.VAL_TIMEOUT, 0)
+        t.jeq(GRANT, hb)                                   # a late grant: ignored
+        t.jmp(follower)                                    # a rival leader's heartbeat: step down
+        t.code[tick_jump][2] = t.label()
+        t.flag_add(1, 1)
+        for j in peers:
+            t.send_to(addrs[i], addrs[j], MAIN, 100 + i)
+        t.djnz(0, hb)
+        t.jmp(follower)
+        mains.append(t)
+        top = v.label()
+        v.recv_from(addrs[i], VREQ); v.reply(addrs[i], MAIN, GRANT); v.jmp(top)
+    m = wl.main()
+    for t in mains:
+        m.spawn(t)
+    for k in range(pauses):
+        victim = nodes[k % n_nodes]
+        m.sleep_rand(lo_ms=0, ms=600)
+        m.pause(victim)
+        m.sleep_rand(lo_ms=200, ms=260)                    # 4 - 5 periods
+        m.resume(victim)
+        m.clog_link(victim, nodes[(k + 1) % n_nodes])
+        m.sleep(ms=120)
+        m.unclog_link(victim, nodes[(k + 1) % n_nodes])
+    m.sleep(secs=1)
+    m.panic_if_flag_lt(0, 1)
+    if min_ticks:
+        m.panic_if_flag_lt(1, min_ticks)
+    m.done()
+    return wl.build()
+
+
+def raft_select_limits():
+    """Capacities for raft_select: raft_ticker's (wide heap entries, no re-registration counts: the ticker builds have neither)."""
+    return raft_ticker_limits()
+
+
+def lossy_select(rounds=16, sends=12, period_us=2000, body_ms=3, tick_first=False):
+    """A recv-first select that loses messages: `loop { select! { biased; m = ep.recv_from(T) => .., _ = i.tick() => .. }; sleep(body) }`
+    on a ticker whose period is shorter than the body, so every select finds its tick due.  A queued message is taken by the recv
+    arm, whose rand_delay is Pending — then the tick wins and the message is gone (madsim's cancel-unsafety); with none queued the
+    recv arm registers and the tick wins, leaving a dead registration.  A sender on another node sends `sends` datagrams at random
+    intervals.  The receiver traces every result and every tick's scheduled instant.  With tick_first the due tick wins before the recv
+    arm is polled: the same sends, nothing taken."""
+    T = 7
+    wl = WorkloadBuilder()
+    ns, nr = wl.create_node(), wl.create_node()
+    a_s, a_r = wl.addr(ns, 1), wl.addr(nr, 1)
+    s = wl.task(ns)
+    s.bind(a_s); s.set(0, sends)
+    top = s.label()
+    s.sleep_rand(lo_ms=0, ms=6); s.send_to(a_s, a_r, T, 0x51); s.djnz(0, top); s.done()
+    r = wl.task(nr)
+    r.bind(a_r); r.interval(us=period_us); r.set(0, rounds)
+    top = r.label()
+    r.recv_or_tick(a_r, T, tick_first=tick_first, trace=True); r.trace_val(); r.sleep(ms=body_ms); r.djnz(0, top); r.done()
+    m = wl.main()
+    m.spawn(r); m.spawn(s); m.join(s); m.join(r); m.done()
+    return wl.build()
+
+
+def lossy_select_limits():
+    lim = A.Limits()
+    lim.max_tasks = 8
+    lim.mbox_regs, lim.mbox_msgs = 24, 16
+    lim.heap_lds_slots, lim.heap_spill_slots = 16, 48
     return lim
 
 
