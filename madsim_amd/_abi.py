@@ -136,6 +136,7 @@ class Geometry(C.Structure):
 VARIANT_SCOPE = 1 << 20     # madsim_geometry_t.variant: timeout scopes (MS_OP_TIMEOUT_BEGIN / END) compiled in
 VARIANT_TICK = 1 << 21      # madsim_geometry_t.variant: interval tickers (MS_OP_INTERVAL / TICK / INTERVAL_RESET) compiled in
 VARIANT_SELECT = 1 << 22    # madsim_geometry_t.variant: selects over a receive and a tick, timeout_at (MS_OP_RECV_OR_TICK / RECV_TIMEOUT_AT) compiled in
+VARIANT_TIER_FEAT = ((VARIANT_SCOPE, 256), (VARIANT_TICK, 512), (VARIANT_SELECT, 1024))   # report bit -> MADSIM_FEAT_SCOPE / TICK / SELECT
 
 
 HEADER_STRUCTS["madsim_campaign_t"] = Campaign

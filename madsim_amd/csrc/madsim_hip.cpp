@@ -690,10 +690,9 @@ int madsim_hip_prefer_hw_queues(int n) {
 
 #define MADSIM_STR2(x) #x
 #define MADSIM_STR(x) MADSIM_STR2(x)
-#define MADSIM_COUNT_VARIANT(...) +1
 const char* madsim_hip_build_info(void) {
     static const std::string info = std::string("madsim_hip abi=") + MADSIM_STR(MADSIM_HIP_ABI_VERSION) + " arch=gfx950 kernels="
-        + std::to_string(0 MADSIM_FOR_EACH_VARIANT(MADSIM_COUNT_VARIANT)) + " backend=hip-rocm"
+        + std::to_string(madsim_k::n_variants) + " backend=hip-rocm"
 #ifdef MADSIM_EXPERIMENT_BUILD
         + " experiment-build"
 #endif
@@ -1084,8 +1083,7 @@ int madsim_hip_geometry(const madsim_workload_t* w, const madsim_limits_t* lim, 
     out->heap_spill_slots = G.P.heap_spill; out->max_tasks = G.P.max_tasks; out->lanes_per_wave = G.lanes_per_wave;
     const madsim_k::VariantSel v = madsim_k::select_variant(G.P, false);
     out->variant = (v.spill ? 1u : 0u) | ((v.feat & MADSIM_FEAT_ALL) ? 2u : 0u) | (v.rq ? 4u : 0u) | (v.lws < 0 ? 8u : 0u) | (v.g ? 16u : 0u) | ((uint32_t)(v.feat & 0xff) << 8) | ((uint32_t)(v.lws & 0xf) << 16)
-                 | ((v.feat & MADSIM_FEAT_SCOPE) ? 1u << 20 : 0u) | ((v.feat & MADSIM_FEAT_TICK) ? 1u << 21 : 0u)
-                 | ((v.feat & MADSIM_FEAT_SELECT) ? 1u << 22 : 0u);
+                 | (uint32_t)(v.feat & MADSIM_FEAT_TIERS) >> 8 << 20;     // bits 20-22: the timer-op tier, MADSIM_FEAT_SCOPE / TICK / SELECT in order
     out->global_bytes_per_seed = G.P.gstate_mode ? G.P.gs_stride : 0;
     return 0;
 }

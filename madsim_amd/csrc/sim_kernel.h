@@ -33,17 +33,15 @@
    the heap levels per LDS byte, half the bytes per spilled level.  Exact while every live deadline lies within 2^31 ns of the clock:
    checked per push on the device (a violation is a capacity verdict: the re-run uses the wide entries). */
 #define MADSIM_FEAT_NARROW 128
-/* Timeout scopes (MS_OP_TIMEOUT_BEGIN / END, KParams.features when a workload uses them).  Kept OUT of MADSIM_FEAT_ALL: every other
-   workload selects the build it selected before, and those builds carry none of the scope code.  Scope workloads run on builds of
-   their own (MADSIM_FOR_EACH_SCOPE_VARIANT), every class compiled in. */
+/* The timer-op tiers, kept OUT of MADSIM_FEAT_ALL so that every other workload selects the build it selected before.  Each tier is
+   the one before it plus one op family, and its workloads run on four builds of their own (MADSIM_TIER_VARIANTS), every class
+   compiled in: timeout scopes (MS_OP_TIMEOUT_BEGIN / END), interval tickers (MS_OP_INTERVAL / TICK / INTERVAL_RESET), selects over a
+   receive and a tick and timeout_at (MS_OP_RECV_OR_TICK / RECV_TIMEOUT_AT).  KParams.features carries the bits a workload's ops need;
+   feature_tier() rounds them up to the tier. */
 #define MADSIM_FEAT_SCOPE 256
-/* Interval tickers (MS_OP_INTERVAL / TICK / INTERVAL_RESET, KParams.features when a workload uses them).  Outside MADSIM_FEAT_ALL like
-   MADSIM_FEAT_SCOPE; ticker workloads run on builds of their own (MADSIM_FOR_EACH_TICK_VARIANT) that carry every class and the scope code. */
 #define MADSIM_FEAT_TICK 512
-/* Selects over a receive and a tick, timeout_at (MS_OP_RECV_OR_TICK / RECV_TIMEOUT_AT, ABI v7; with MADSIM_FEAT_TICK in KParams.features).
-   Builds of their own again (MADSIM_FOR_EACH_SELECT_VARIANT: the ticker builds' four shapes with the select code): the ticker builds
-   compile to what they were, so the ticker workloads pay nothing for it. */
 #define MADSIM_FEAT_SELECT 1024
+#define MADSIM_FEAT_TIERS (MADSIM_FEAT_SCOPE | MADSIM_FEAT_TICK | MADSIM_FEAT_SELECT)
 /* Global-state builds: identical wake-ups are fired as a batch (k_net.h timer_expire).  Sleep::poll registers ANOTHER timer with the same
    deadline and waker on every not-elapsed poll (time/sleep.rs:51-53), so more than half of the topology's heap entries are copies of an
    earlier one; copies leave the heap back to back, and every one after the first finds its task SCHEDULED already (or gone): a step
@@ -161,12 +159,19 @@ struct KParams {
                                // 0 = none (a select build's workload without MS_OP_INTERVAL)
 };
 
-// Kernel variants (Variant<TRACE, SPILL, LWS, FEAT, RQ>): the trace build; for base-op workloads on full 64-lane waves one
-// build per (heap spill, register ready queue) combination plus a runtime-lane-stride build; single-class builds for
-// workloads that only use timeouts (FEAT_TIME) or only the reliable channel (FEAT_CHAN) — a third of the code and
+// The compiled builds, X(TRACE, SPILL, LWS, FEAT, RQ, G) = sim_kernel<Variant<...>>: the trace build; for base-op workloads on
+// full 64-lane waves one build per (heap spill, register ready queue) combination plus a runtime-lane-stride build; single-class
+// builds for workloads that only use timeouts (FEAT_TIME) or only the reliable channel (FEAT_CHAN) — a third of the code and
 // fewer registers than the full build; the full build for every lane stride (64/32/16/8 seed lanes per wave, runtime);
-// and the global-state builds (G: task table + planes in global memory) of the three extended classes.
+// the global-state builds (G: task table + planes in global memory) of the three extended classes; then the timer-op tiers,
+// each with the four shapes of MADSIM_TIER_VARIANTS: the trace build, the LDS-resident build (runtime lane stride) and the
+// global-state builds (plain addresses, general resolution), every class compiled in.
 #ifndef MADSIM_FOR_EACH_VARIANT      // (tools/ may compile a subset: -D'MADSIM_FOR_EACH_VARIANT(X)=X(false,false,6,0,true,false)')
+#define MADSIM_TIER_VARIANTS(X, M)                                              \
+    X(true, true, -1, MADSIM_FEAT_ALL | (M), false, false)                      \
+    X(false, true, -1, MADSIM_FEAT_ALL | (M), false, false)                     \
+    X(false, true, 6, (MADSIM_FEAT_ALL & ~MADSIM_FEAT_ADDR) | (M), false, true) \
+    X(false, true, 6, MADSIM_FEAT_ALL | (M), false, true)
 #define MADSIM_FOR_EACH_VARIANT(X)                     \
     X(true, true, -1, MADSIM_FEAT_ALL, false, false)   \
     X(false, false, 6, 0, false, false)                \
@@ -195,51 +200,40 @@ struct KParams {
     X(false, true, 6, MADSIM_FEAT_TIME | MADSIM_FEAT_NARROW, false, true) \
     X(false, true, 5, MADSIM_FEAT_TIME | MADSIM_FEAT_NARROW, false, true) \
     X(false, true, 6, (MADSIM_FEAT_ALL & ~MADSIM_FEAT_ADDR) | MADSIM_FEAT_NARROW, false, true) \
-    MADSIM_FOR_EACH_SCOPE_VARIANT(X)
-#endif
-// The builds of timeout-scope workloads (MADSIM_FEAT_SCOPE): the trace build, the LDS-resident every-class build (runtime lane stride), the
-// global-state every-class builds (wide heap entries; plain addresses and general resolution).
-#ifndef MADSIM_FOR_EACH_SCOPE_VARIANT
-#define MADSIM_FOR_EACH_SCOPE_VARIANT(X)                                      \
-    X(true, true, -1, MADSIM_FEAT_ALL | MADSIM_FEAT_SCOPE, false, false)      \
-    X(false, true, -1, MADSIM_FEAT_ALL | MADSIM_FEAT_SCOPE, false, false)     \
-    X(false, true, 6, (MADSIM_FEAT_ALL & ~MADSIM_FEAT_ADDR) | MADSIM_FEAT_SCOPE, false, true) \
-    X(false, true, 6, MADSIM_FEAT_ALL | MADSIM_FEAT_SCOPE, false, true)   \
-    MADSIM_FOR_EACH_TICK_VARIANT(X)
-#endif
-// The builds of interval-ticker workloads (MADSIM_FEAT_TICK, with or without scopes): the same four shapes, the scope code compiled in too.
-#ifndef MADSIM_FOR_EACH_TICK_VARIANT
-#define MADSIM_FOR_EACH_TICK_VARIANT(X)                                                          \
-    X(true, true, -1, MADSIM_FEAT_ALL | MADSIM_FEAT_SCOPE | MADSIM_FEAT_TICK, false, false)      \
-    X(false, true, -1, MADSIM_FEAT_ALL | MADSIM_FEAT_SCOPE | MADSIM_FEAT_TICK, false, false)     \
-    X(false, true, 6, (MADSIM_FEAT_ALL & ~MADSIM_FEAT_ADDR) | MADSIM_FEAT_SCOPE | MADSIM_FEAT_TICK, false, true) \
-    X(false, true, 6, MADSIM_FEAT_ALL | MADSIM_FEAT_SCOPE | MADSIM_FEAT_TICK, false, true)          \
-    MADSIM_FOR_EACH_SELECT_VARIANT(X)
-#endif
-// The builds of select workloads (MADSIM_FEAT_SELECT, with tickers, scopes or neither): the ticker builds' four shapes with the select code.
-#ifndef MADSIM_FOR_EACH_SELECT_VARIANT
-#define MADSIM_FOR_EACH_SELECT_VARIANT(X)                                                                             \
-    X(true, true, -1, MADSIM_FEAT_ALL | MADSIM_FEAT_SCOPE | MADSIM_FEAT_TICK | MADSIM_FEAT_SELECT, false, false)      \
-    X(false, true, -1, MADSIM_FEAT_ALL | MADSIM_FEAT_SCOPE | MADSIM_FEAT_TICK | MADSIM_FEAT_SELECT, false, false)     \
-    X(false, true, 6, (MADSIM_FEAT_ALL & ~MADSIM_FEAT_ADDR) | MADSIM_FEAT_SCOPE | MADSIM_FEAT_TICK | MADSIM_FEAT_SELECT, false, true) \
-    X(false, true, 6, MADSIM_FEAT_ALL | MADSIM_FEAT_SCOPE | MADSIM_FEAT_TICK | MADSIM_FEAT_SELECT, false, true)
+    MADSIM_TIER_VARIANTS(X, MADSIM_FEAT_SCOPE)         \
+    MADSIM_TIER_VARIANTS(X, MADSIM_FEAT_SCOPE | MADSIM_FEAT_TICK) \
+    MADSIM_TIER_VARIANTS(X, MADSIM_FEAT_SCOPE | MADSIM_FEAT_TICK | MADSIM_FEAT_SELECT)
 #endif
 
-// Which compiled specialisation of sim_kernel a parameter block runs on (one rule for the launcher and for
-// madsim_hip_geometry's report).  Compiled set = MADSIM_FOR_EACH_VARIANT in sim_kernel.hip.
+// A compiled specialisation of sim_kernel, and the compiled set as a table in MADSIM_FOR_EACH_VARIANT's order (sim_kernel.hip
+// builds its kernel table, the host emulation its function table, from the same macro): variant_index() is the one lookup.
 struct VariantSel { int trace, spill, lws, feat, rq, g; };
+#define MADSIM_VARIANT_ROW(T_, S_, L_, F_, R_, G_) VariantSel{(int)(T_), (int)(S_), (L_), (F_), (int)(R_), (int)(G_)},
+inline constexpr VariantSel variant_table[] = {MADSIM_FOR_EACH_VARIANT(MADSIM_VARIANT_ROW)};
+#undef MADSIM_VARIANT_ROW
+inline constexpr int n_variants = (int)(sizeof variant_table / sizeof *variant_table);
+inline int variant_index(const VariantSel& v) {
+    for (int i = 0; i < n_variants; i++) {
+        const VariantSel& r = variant_table[i];
+        if (r.trace == v.trace && r.spill == v.spill && r.lws == v.lws && r.feat == v.feat && r.rq == v.rq && r.g == v.g) return i;
+    }
+    return -1;
+}
+inline bool variant_compiled(const VariantSel& v) { return variant_index(v) >= 0; }
+
+// The timer-op tier of a features word: 0, SCOPE, SCOPE|TICK or SCOPE|TICK|SELECT.
+inline int feature_tier(int feat) {
+    return (feat & MADSIM_FEAT_SELECT) ? MADSIM_FEAT_TIERS : (feat & MADSIM_FEAT_TICK) ? MADSIM_FEAT_SCOPE | MADSIM_FEAT_TICK : feat & MADSIM_FEAT_SCOPE;
+}
+
+// Which compiled specialisation of sim_kernel a parameter block runs on (one rule for the launcher and for
+// madsim_hip_geometry's report).
 inline VariantSel select_variant(const KParams& P, bool trace) {
     const int spill = P.heap_spill > 0, lw = (int)P.lw_shift, feat = (int)P.features;
-    if (feat & MADSIM_FEAT_TICK) {                                      // interval tickers (scopes or not): builds of their own, every class;
-        const int tk = MADSIM_FEAT_SCOPE | MADSIM_FEAT_TICK | (feat & MADSIM_FEAT_SELECT);   // selects: the select builds of these shapes
-        if (trace) return {1, 1, -1, MADSIM_FEAT_ALL | tk, 0, 0};
-        if (P.gstate_mode) return {0, 1, 6, ((feat & MADSIM_FEAT_ADDR) ? MADSIM_FEAT_ALL : MADSIM_FEAT_ALL & ~MADSIM_FEAT_ADDR) | tk, 0, 1};
-        return {0, 1, -1, MADSIM_FEAT_ALL | tk, 0, 0};
-    }
-    if (feat & MADSIM_FEAT_SCOPE) {                                     // timeout scopes: builds of their own, every class
-        if (trace) return {1, 1, -1, MADSIM_FEAT_ALL | MADSIM_FEAT_SCOPE, 0, 0};
-        if (P.gstate_mode) return {0, 1, 6, ((feat & MADSIM_FEAT_ADDR) ? MADSIM_FEAT_ALL : MADSIM_FEAT_ALL & ~MADSIM_FEAT_ADDR) | MADSIM_FEAT_SCOPE, 0, 1};
-        return {0, 1, -1, MADSIM_FEAT_ALL | MADSIM_FEAT_SCOPE, 0, 0};
+    if (const int tier = feature_tier(feat)) {                          // timer-op tiers: builds of their own, every class
+        if (trace) return {1, 1, -1, MADSIM_FEAT_ALL | tier, 0, 0};
+        if (P.gstate_mode) return {0, 1, 6, ((feat & MADSIM_FEAT_ADDR) ? MADSIM_FEAT_ALL : MADSIM_FEAT_ALL & ~MADSIM_FEAT_ADDR) | tier, 0, 1};
+        return {0, 1, -1, MADSIM_FEAT_ALL | tier, 0, 0};
     }
     if (trace) return {1, 1, -1, MADSIM_FEAT_ALL, 0, 0};
     if (feat == 0) {                                                    // base ops only
@@ -267,16 +261,6 @@ inline VariantSel select_variant(const KParams& P, bool trace) {
     return {0, 1, -1, MADSIM_FEAT_ALL, 0, 0};
 }
 
-// Is the build `v` names one of the compiled set?  (Host-side twin of the dispatch chain in sim_kernel.hip: same macro, no kernels.)
-inline bool variant_compiled(const VariantSel& v) {
-    bool hit = false;
-#define MADSIM_VARIANT_HIT(T_, S_, L_, F_, R_, G_) \
-    hit = hit || (v.trace == (int)(T_) && v.spill == (int)(S_) && v.lws == (L_) && v.feat == (F_) && v.rq == (int)(R_) && v.g == (int)(G_));
-    MADSIM_FOR_EACH_VARIANT(MADSIM_VARIANT_HIT)
-#undef MADSIM_VARIANT_HIT
-    return hit;
-}
-
 // The contract between a parameter block and the build that will run it — checked by make_geometry before anything can be launched
 // (round 4 ran the 64-lane build of the every-class kernel on a 32-lane geometry once: a selection-order slip that hung a GPU box;
 // with this check such a pair is MADSIM_E_LIMITS, never a launch) and walked by tests/test_geometry_consistency.py over every
@@ -289,16 +273,14 @@ inline const char* variant_mismatch(const KParams& P, const VariantSel& v, bool 
     if ((v.rq != 0) != (P.rq_in_reg != 0)) return "register ready queue build on a layout with an LDS ready queue (or the reverse)";
     if (v.rq && (P.max_tasks > 8 || P.lw_shift != 6 || P.lifecycle)) return "register ready queue needs <= 8 tasks, full waves, base ops";
     if (!v.spill && P.heap_spill) return "a build without the spill path on a geometry with spilled heap levels";
-    const int classes = v.feat & MADSIM_FEAT_ALL;
-    if (((int)P.features & ~(classes | (v.feat & (MADSIM_FEAT_SCOPE | MADSIM_FEAT_TICK | MADSIM_FEAT_SELECT)))) != 0) return "the build lacks an op class the workload uses";
-    // (a select build's workload may have no tick unit: its only v7 op is recv_from_timeout_at)
-    if ((v.feat & MADSIM_FEAT_TICK) && (!((int)P.features & MADSIM_FEAT_TICK) || (!P.tick_unit && !(v.feat & MADSIM_FEAT_SELECT)) || P.narrow || P.dedup_n))
-        return "an interval-ticker build on a layout without the tick unit (or with narrow entries / re-registration counts)";
-    if (((v.feat & MADSIM_FEAT_SELECT) != 0) != (((int)P.features & MADSIM_FEAT_SELECT) != 0)) return "a select build for a workload without selects (or the reverse)";
-    if ((v.feat & MADSIM_FEAT_SCOPE) && !(v.feat & MADSIM_FEAT_TICK) && (!((int)P.features & MADSIM_FEAT_SCOPE) || !P.scope_unit || P.narrow || P.dedup_n))
-        return "a timeout-scope build on a layout without the scope unit (or with narrow entries / re-registration counts)";
-    if ((v.feat & MADSIM_FEAT_TICK) && (((int)P.features & MADSIM_FEAT_SCOPE) != 0) != (P.scope_unit != 0))
-        return "an interval-ticker build: the scope unit and the scope class disagree";
+    const int classes = v.feat & MADSIM_FEAT_ALL, tier = feature_tier(v.feat);
+    if (((int)P.features & ~(classes | MADSIM_FEAT_TIERS)) != 0) return "the build lacks an op class the workload uses";
+    if (tier != feature_tier((int)P.features)) return "the build's timer-op tier differs from the workload's";
+    if (tier && (P.narrow || P.dedup_n)) return "a timer-op tier build on a layout with narrow entries or re-registration counts";
+    if ((P.scope_unit != 0) != (((int)P.features & MADSIM_FEAT_SCOPE) != 0)) return "the scope unit and the scope class disagree";
+    // (a select-tier workload may have no tick unit: its only select-tier op is recv_from_timeout_at)
+    if (tier == (MADSIM_FEAT_SCOPE | MADSIM_FEAT_TICK) ? !P.tick_unit : (P.tick_unit && !(tier & MADSIM_FEAT_TICK)))
+        return "a tick unit on a build without the ticker tier (or a ticker-tier build without one)";
     if ((classes != 0) != (P.lifecycle != 0)) return "extended-op build on the base-op LDS layout (or the reverse)";
     if (((v.feat & MADSIM_FEAT_COMPACT) != 0) != (P.compact != 0)) return "compact build on a plain layout (or the reverse)";
     if (P.compact && (P.heap_spill || P.lifecycle || P.lw_shift != 6 || !P.rq_in_reg || P.max_tasks > 8)) return "compact layout outside its conditions";

@@ -91,21 +91,21 @@ __global__ __launch_bounds__(256) void summary6_kernel(const madsim_result_t* __
 
 __global__ void keyflip_kernel(unsigned long long* acc) { acc[0] ^= 0x8000000000000000ull; }
 
+// one kernel per row of variant_table (sim_kernel.h), same macro, same order
+#define MADSIM_VARIANT_KERNEL(T_, S_, L_, F_, R_, G_) (const void*)sim_kernel<Variant<T_, S_, L_, F_, R_, G_>>,
+static const void* const variant_kernels[] = {MADSIM_FOR_EACH_VARIANT(MADSIM_VARIANT_KERNEL)};
+#undef MADSIM_VARIANT_KERNEL
+static_assert(sizeof variant_kernels / sizeof *variant_kernels == n_variants, "one kernel per build");
+
 }  // namespace madsim_k
 
 extern "C" int madsim_k_launch_sim(const madsim_k::KParams* P, uint32_t grid, uint32_t lds_bytes, void* stream, int trace) {
     using namespace madsim_k;
-    const VariantSel v = select_variant(*P, trace != 0);
-    hipStream_t st = (hipStream_t)stream;
-    bool launched = false;
-#define TRY_LAUNCH(T_, S_, L_, F_, R_, G_)                                                                               \
-    if (!launched && v.trace == (int)(T_) && v.spill == (int)(S_) && v.lws == (L_) && v.feat == (F_) && v.rq == (int)(R_) && v.g == (int)(G_)) { \
-        hipLaunchKernelGGL((sim_kernel<Variant<T_, S_, L_, F_, R_, G_>>), dim3(grid), dim3(64 * P->waves_per_block), lds_bytes, st, *P); \
-        launched = true;                                                                                                 \
-    }
-    MADSIM_FOR_EACH_VARIANT(TRY_LAUNCH)
-#undef TRY_LAUNCH
-    return launched ? 0 : -1;      // select_variant named a build that is not compiled: a bug, never a silent substitute
+    const int i = variant_index(select_variant(*P, trace != 0));
+    if (i < 0) return -1;          // select_variant named a build that is not compiled: a bug, never a silent substitute
+    void* args[] = {const_cast<KParams*>(P)};      // the by-value KParams, as the <<<>>> stub passes it
+    (void)hipLaunchKernel(variant_kernels[i], dim3(grid), dim3(64 * P->waves_per_block), args, lds_bytes, (hipStream_t)stream);
+    return 0;
 }
 
 extern "C" void madsim_k_launch_summary(const madsim_result_t* out, uint64_t count, uint64_t seed0, unsigned long long* acc, void* stream) {
@@ -129,23 +129,14 @@ extern "C" void madsim_k_launch_keyflip(unsigned long long* acc, void* stream) {
 // VGPRs per lane of the build select_variant names (0 = not compiled / error): the host sizes waves per CU with it.
 extern "C" int madsim_k_variant_vgprs(const madsim_k::VariantSel* v) {
     using namespace madsim_k;
-    int regs = 0;
-#define TRY_ATTR(T_, S_, L_, F_, R_, G_)                                                                                 \
-    if (!regs && v->trace == (int)(T_) && v->spill == (int)(S_) && v->lws == (L_) && v->feat == (F_) && v->rq == (int)(R_) && v->g == (int)(G_)) { \
-        hipFuncAttributes a;                                                                                             \
-        if (hipFuncGetAttributes(&a, (const void*)sim_kernel<Variant<T_, S_, L_, F_, R_, G_>>) == hipSuccess) regs = a.numRegs; \
-    }
-    MADSIM_FOR_EACH_VARIANT(TRY_ATTR)
-#undef TRY_ATTR
-    return regs;
+    const int i = variant_index(*v);
+    hipFuncAttributes a;
+    return i >= 0 && hipFuncGetAttributes(&a, variant_kernels[i]) == hipSuccess ? a.numRegs : 0;
 }
 
 extern "C" int madsim_k_set_max_lds(uint32_t lds_bytes) {
-    using namespace madsim_k;
     hipError_t e = hipSuccess;
-#define SETATTR(...)                                                                                                     \
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)sim_kernel<Variant<__VA_ARGS__>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    MADSIM_FOR_EACH_VARIANT(SETATTR)
-#undef SETATTR
+    for (const void* k : madsim_k::variant_kernels)
+        if (e == hipSuccess) e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     return (int)e;
 }

@@ -359,7 +359,8 @@ def variant_name(g):
     """The sim_kernel specialisation a madsim_geometry_t selects (madsim_k_launch_sim's dispatch), as rocprofv3 names it."""
     b = lambda x: "true" if x else "false"
     lws = (g.variant >> 16) & 0xf
-    return (f"sim_kernel<Variant<false, {b(g.variant & 1)}, {-1 if lws == 15 else lws}, {((g.variant >> 8) & 0xff) | (256 if g.variant & (1 << 20) else 0) | (512 if g.variant & (1 << 21) else 0) | (1024 if g.variant & (1 << 22) else 0)}, "
+    feat = ((g.variant >> 8) & 0xff) | sum(f for bit, f in A.VARIANT_TIER_FEAT if g.variant & bit)
+    return (f"sim_kernel<Variant<false, {b(g.variant & 1)}, {-1 if lws == 15 else lws}, {feat}, "
             f"{b(g.variant & 4)}, {b(g.variant & 16)}>>")
 
 

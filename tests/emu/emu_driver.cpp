@@ -121,6 +121,22 @@ void madsim_emu_ovf_note(const char* file, int line, uint32_t bits) {
 
 extern "C" const char* madsim_emu_last_error(void) { return emu_err.c_str(); }
 
+// the host functions of the compiled builds, one per row of madsim_k::variant_table (sim_kernel.h), same macro, same order
+#define EMU_KERNEL(T_, S_, L_, F_, R_, G_) &madsim_k::sim_kernel<madsim_k::Variant<T_, S_, L_, F_, R_, G_>>,
+static void (*const emu_kernels[])(madsim_k::KParams) = {MADSIM_FOR_EACH_VARIANT(EMU_KERNEL)};
+#undef EMU_KERNEL
+static_assert(sizeof emu_kernels / sizeof *emu_kernels == madsim_k::n_variants, "one function per build");
+
+// the compiled set: n_variants rows of {trace, spill, lws, feat, rq, g} into out6 (up to cap rows); returns n_variants
+extern "C" int madsim_emu_variants(int32_t* out6, int cap) {
+    for (int i = 0; i < madsim_k::n_variants && i < cap; i++) {
+        const madsim_k::VariantSel& v = madsim_k::variant_table[i];
+        const int32_t row[6] = {v.trace, v.spill, v.lws, v.feat, v.rq, v.g};
+        memcpy(out6 + 6 * i, row, sizeof row);
+    }
+    return madsim_k::n_variants;
+}
+
 extern "C" int madsim_emu_run_batch(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t count,
                                     const madsim_limits_t* lim, madsim_result_t* out, int num_cus, uint8_t* tlog,
                                     uint64_t tcap, uint64_t* tlen) {
@@ -166,13 +182,9 @@ extern "C" int madsim_emu_run_batch(const madsim_workload_t* w, const madsim_con
 #endif
             blockIdx.x = b / G.waves_per_block; threadIdx.x = (b % G.waves_per_block) * 64 + t; emu_smem = base;
             using namespace madsim_k;
-            const VariantSel v = select_variant(P, tlog != nullptr);      // the same build the GPU launcher would pick
-            bool ran = false;
-#define EMU_TRY(T_, S_, L_, F_, R_, G_) \
-            if (!ran && v.trace == (int)(T_) && v.spill == (int)(S_) && v.lws == (L_) && v.feat == (F_) && v.rq == (int)(R_) && v.g == (int)(G_)) { sim_kernel<Variant<T_, S_, L_, F_, R_, G_>>(P); ran = true; }
-            MADSIM_FOR_EACH_VARIANT(EMU_TRY)
-#undef EMU_TRY
-            if (!ran) { emu_err = "select_variant named a build that is not compiled"; return MADSIM_E_LIMITS; }
+            const int vi = variant_index(select_variant(P, tlog != nullptr));      // the same build the GPU launcher would pick
+            if (vi < 0) { emu_err = "select_variant named a build that is not compiled"; return MADSIM_E_LIMITS; }
+            emu_kernels[vi](P);
         }
 #ifdef MADSIM_EMU_SITES
         emu_site_log = nullptr;

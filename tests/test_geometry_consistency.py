@@ -1,65 +1,69 @@
 """Geometry <-> kernel-build consistency, on the CPU.
 
 `madsim_hip_geometry` runs the same `make_geometry` + `select_variant` a launch runs (madsim_amd/csrc/geometry.h, sim_kernel.h) and
-needs no GPU.  This walks every bench case, every lifecycle workload and a block of every fuzz generator through it for
-state_mem in {AUTO, LDS, GLOBAL, COMPACT} x {plain, | DEDUP_TIMERS} x lanes_per_wave in {0, 8, 16, 32, 64} and checks, from the OUTSIDE
-(the reported madsim_geometry_t only), the contract `variant_mismatch()` enforces from the inside:
+needs no GPU.  This walks every bench case, every lifecycle workload, a block of every fuzz generator (the timer-op tiers' included)
+and the directed workloads of the timer-op tiers through it for state_mem in {AUTO, LDS, GLOBAL, COMPACT} x {plain, | DEDUP_TIMERS}
+x lanes_per_wave in {0, 8, 16, 32, 64} and checks, from the OUTSIDE (the reported madsim_geometry_t only), the contract
+`variant_mismatch()` enforces from the inside:
 
 * a combination is either a geometry or MADSIM_E_LIMITS / MADSIM_E_WORKLOAD — never anything else, so never a launch of a build that
   does not fit (round 4 once ran the 64-lane every-class build on a 32-lane geometry: a hung GPU box);
 * the build's compile-time lane stride is the geometry's, or the build takes it at run time;
 * global-state build <=> a global block per seed; register ready queue => <= 8 tasks, full waves, base ops;
-* the build carries every op class the workload uses (recomputed here from the instruction table);
+* the build carries every op class the workload uses, and its timer-op tier is the workload's (recomputed here from the instruction table);
 * the workgroups the geometry puts on a CU fit its 160 KiB of LDS (1 280-byte allocation granules), the workgroup is 1/2/4 waves;
-* the named build exists (the set of MADSIM_FOR_EACH_VARIANT, restated below and cross-checked against sim_kernel.h's text).
+* the named build exists (the compiled set as the build itself lists it: the host emulation's table, made from the same
+  MADSIM_FOR_EACH_VARIANT, cross-checked against the kernel count of madsim_hip_build_info()).
 """
-import os
+import ctypes as C
 import random
-import re
 
 import pytest
 
 from madsim_amd import _abi as A
 from madsim_amd import runtime
 from madsim_amd import workload as W
-from tests import fuzz, lifecycle_workloads as LW
+from tests import emu, fuzz, fuzz_interval, fuzz_scope, fuzz_select, lifecycle_workloads as LW
+from tests import test_interval, test_select, test_timeout_scope
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LDS_PER_CU = 160 * 1024
 E_WORKLOAD, E_LIMITS = -4, -5          # include/madsim_hip.h
-FEAT = dict(TIME=1, CHAN=2, RPC=4, NODE=8, ADDR=16, ALL=31, NOLOG=32, COMPACT=64, NARROW=128)
+FEAT = dict(TIME=1, CHAN=2, RPC=4, NODE=8, ADDR=16, ALL=31, NOLOG=32, COMPACT=64, NARROW=128, SCOPE=256, TICK=512, SELECT=1024)
+TIERS = FEAT["SCOPE"] | FEAT["TICK"] | FEAT["SELECT"]
 
 
 def compiled_variants():
-    """(spill, lws, feat, rq, g) of every non-trace build: parsed from sim_kernel.h's MADSIM_FOR_EACH_VARIANT."""
-    text = open(os.path.join(ROOT, "madsim_amd", "csrc", "sim_kernel.h")).read()
-    body = text[text.index("#define MADSIM_FOR_EACH_VARIANT(X)"):text.index("#endif", text.index("#define MADSIM_FOR_EACH_VARIANT(X)"))]
-    out = set()
-    for m in re.finditer(r"X\((true|false), (true|false), (-?\d+), ([^,]+(?:\|[^,]+)*), (true|false), (true|false)\)", body):
-        trace, spill, lws, feat, rq, g = m.groups()
-        f = eval(feat.replace("MADSIM_FEAT_", ""), {}, dict(FEAT))
-        if trace == "false":
-            out.add((spill == "true", int(lws), f, rq == "true", g == "true"))
-    return out
+    """(trace, spill, lws, feat, rq, g) of every build, in the build's own order (tests/emu madsim_emu_variants)."""
+    L = emu.lib()
+    L.madsim_emu_variants.argtypes = [C.POINTER(C.c_int32), C.c_int]
+    n = L.madsim_emu_variants(None, 0)
+    rows = (C.c_int32 * (6 * n))()
+    assert L.madsim_emu_variants(rows, n) == n
+    return [(bool(r[0]), bool(r[1]), r[2], r[3], bool(r[4]), bool(r[5])) for r in (rows[6 * i:6 * i + 6] for i in range(n))]
 
 
-COMPILED = compiled_variants()
+VARIANTS = compiled_variants()
+COMPILED = {v[1:] for v in VARIANTS if not v[0]}       # (spill, lws, feat, rq, g) of every non-trace build
 
 
 def decode(v):
     """madsim_geometry_t.variant -> (spill, lws, feat, rq, g)  (include/madsim_hip.h)."""
     lws = (v >> 16) & 0xf
-    return (bool(v & 1), -1 if (v & 8) else lws, (v >> 8) & 0xff, bool(v & 4), bool(v & 16))
+    feat = ((v >> 8) & 0xff) | (FEAT["SCOPE"] if v & A.VARIANT_SCOPE else 0) | (FEAT["TICK"] if v & A.VARIANT_TICK else 0) \
+        | (FEAT["SELECT"] if v & A.VARIANT_SELECT else 0)
+    return (bool(v & 1), -1 if (v & 8) else lws, feat, bool(v & 4), bool(v & 16))
 
 
 def classes_needed(w):
     """The op classes a workload's instruction table asks for, as geometry.h derives them (a superset check: ADDR and the
-    spawn-in-Drop rule are left to the library — the build may carry MORE classes than this, never fewer)."""
+    spawn-in-Drop rule are left to the library — the build may carry MORE classes than this, never fewer), and its timer-op tier
+    (exact: SCOPE, SCOPE|TICK or SCOPE|TICK|SELECT)."""
     s = w.struct
     ops = {w.insns[i].op for i in range(s.n_insns)}
     O = A.OP
     f = 0
-    if ops & {O["RECV_TIMEOUT"], O["MARK"], O["SLEEP_UNTIL"], O["ASSERT_ELAPSED"], O["ADVANCE"], O["TRACE_TIME"]}:
+    if ops & {O["RECV_TIMEOUT"], O["MARK"], O["SLEEP_UNTIL"], O["ASSERT_ELAPSED"], O["ADVANCE"], O["TRACE_TIME"], O["RECV_OR_TICK"],
+              O["RECV_TIMEOUT_AT"]}:
         f |= FEAT["TIME"]
     if ops & {O["CONNECT"], O["ACCEPT"], O["CSEND"], O["CRECV"], O["CCLOSE"]}:
         f |= FEAT["CHAN"]
@@ -67,6 +71,12 @@ def classes_needed(w):
         f |= FEAT["RPC"] | FEAT["TIME"]
     if ops & {O["KILL"], O["RESTART"], O["PAUSE"], O["RESUME"], O["ABORT"], O["ASSERT_EXIT"], O["BUILD"]}:
         f |= FEAT["NODE"]
+    if ops & {O["RECV_OR_TICK"], O["RECV_TIMEOUT_AT"]}:
+        f |= TIERS
+    elif ops & {O["INTERVAL"], O["TICK"], O["INTERVAL_RESET"]}:
+        f |= FEAT["SCOPE"] | FEAT["TICK"]
+    elif O["TIMEOUT_BEGIN"] in ops:
+        f |= FEAT["SCOPE"]
     return f
 
 
@@ -91,7 +101,10 @@ def check(w, lim, what):
     if not spill:
         assert g.heap_spill_slots == 0, (what, "a build without the spill path on a geometry with spilled levels")
     need = classes_needed(w)
-    assert need & ~(feat & FEAT["ALL"]) == 0, (what, f"build classes {feat & 31:#x} lack {need & ~feat:#x}")
+    assert need & FEAT["ALL"] & ~feat == 0, (what, f"build classes {feat & 31:#x} lack {need & FEAT['ALL'] & ~feat:#x}")
+    assert feat & TIERS == need & TIERS, (what, f"build tier {feat & TIERS:#x}, workload tier {need & TIERS:#x}")
+    if feat & TIERS:
+        assert (feat | FEAT["ADDR"]) & FEAT["ALL"] == FEAT["ALL"] and not feat & FEAT["NARROW"], (what, "timer-op tier builds: every class, wide entries")
     if feat & FEAT["NARROW"]:
         assert glob and (lim.state_mem & A.STATE_NARROW_HEAP), (what, "8-byte heap entries: global-state builds, on request only")
     if feat & FEAT["COMPACT"]:
@@ -141,7 +154,12 @@ def walk(w, base, name):
 
 
 def test_compiled_set_is_parsed():
+    """The emulation's table is the library's build list: as many rows as madsim_hip_build_info() counts kernels, no row twice."""
+    kernels = int(dict(kv.split("=", 1) for kv in runtime.lib().madsim_hip_build_info().decode().split() if "=" in kv)["kernels"])
+    assert len(VARIANTS) == kernels and len(set(VARIANTS)) == kernels
     assert len(COMPILED) >= 20 and (False, 6, FEAT["COMPACT"], True, False) in COMPILED and (True, 5, FEAT["TIME"], False, True) in COMPILED
+    for tier in (FEAT["SCOPE"], FEAT["SCOPE"] | FEAT["TICK"], TIERS):       # each tier: the trace build and three others
+        assert sum(v[3] & TIERS == tier for v in VARIANTS) == 4 and (True, True, -1, FEAT["ALL"] | tier, False, False) in VARIANTS
 
 
 @pytest.mark.parametrize("name", ["pingpong", "raft", "kv", "timers", "topo"])
@@ -191,13 +209,32 @@ GENS = [("random_workload", fuzz.generous_limits), ("random_lifecycle_workload",
         ("random_latency_workload", fuzz.mailbox_limits)]
 
 
+GENS += [("random_scope_workload", fuzz_scope.scope_limits), ("random_interval_workload", fuzz_interval.interval_limits),
+         ("random_select_workload", fuzz_select.select_limits)]
+GEN_MODULES = (fuzz, fuzz_scope, fuzz_interval, fuzz_select)
+
+
 @pytest.mark.parametrize("gen,limits", GENS, ids=[g[0] for g in GENS])
 def test_fuzz_block_every_layout_and_lane_count(gen, limits):
     """24 programs of every generator, default capacities and the generator's own, through every combination."""
+    make = next(getattr(m, gen) for m in GEN_MODULES if hasattr(m, gen))
     ok = 0
     for k in range(24):
-        w = getattr(fuzz, gen)(random.Random(660_000 + k))[0]
+        w = make(random.Random(660_000 + k))[0]
         for base in (None, limits()):
             a, _ = walk(w, base, (gen, k))
             ok += a
+    assert ok > 0
+
+
+DIRECTED = [(test_timeout_scope, name, test_timeout_scope.scope_limits) for name in sorted(test_timeout_scope.DIRECTED)] \
+    + [(test_interval, name, fuzz_interval.interval_limits) for name in sorted(test_interval.DIRECTED)] \
+    + [(test_select, name, lambda n=name: test_select.limits_for(n, 0)) for name in sorted(test_select.DIRECTED)]
+
+
+@pytest.mark.parametrize("mod,name,limits", DIRECTED, ids=[f"{m.__name__.split('.')[-1]}-{n}" for m, n, _ in DIRECTED])
+def test_directed_tier_workloads_every_layout_and_lane_count(mod, name, limits):
+    """The directed workloads of the timer-op tiers, default capacities and their tests' own, through every combination."""
+    w = mod.DIRECTED[name][0]
+    ok = sum(walk(w, base, (name, "base" if base else "default"))[0] for base in (None, limits()))
     assert ok > 0
