@@ -221,6 +221,9 @@ pub const MS_OP_TICK: u8 = 63;
 pub const MS_OP_INTERVAL_RESET: u8 = 64;
 pub const MS_OP_RECV_OR_TICK: u8 = 65;
 pub const MS_OP_RECV_TIMEOUT_AT: u8 = 66;
+pub const MS_OP_CTRL_C: u8 = 67;
+pub const MS_OP_SEND_CTRL_C: u8 = 68;
+pub const MS_OP_RECV_OR_CTRL_C: u8 = 69;
 pub const MADSIM_PASS: u32 = 0;
 pub const MADSIM_PANIC: u32 = 1;
 pub const MADSIM_DEADLOCK: u32 = 2;

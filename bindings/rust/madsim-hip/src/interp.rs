@@ -5,7 +5,7 @@
 //! run of the very same table must reproduce.
 //!
 //! Covers the base ops (datagram Endpoint API, sleeps, spawn / join / abort / yield, loop and assert glue, shared flags,
-//! clogs, kill / restart / pause / resume, observations, interval tickers, select_biased! over a receive and a tick, timeout_at).  Ops outside that set panic with "interp: unsupported op": they have
+//! clogs, kill / restart / pause / resume, observations, interval tickers, select_biased! over a receive and a tick, timeout_at, ctrl-c signals).  Ops outside that set panic with "interp: unsupported op": they have
 //! hand-written twins in tools/ref_twin/src/main.rs instead.  Only built with `--features madsim` and `--cfg madsim`.
 use crate::workload::Workload;
 use madsim::net::{Endpoint, NetSim};
@@ -214,6 +214,34 @@ fn run_task(sh: Arc<Shared>, prog: usize) -> Task {
                                 sh.observe(at.duration_since(t0.expect("t0")).as_nanos() as u64);
                             }
                         }
+                    }
+                }
+                sys::MS_OP_CTRL_C => madsim::signal::ctrl_c().await.unwrap(),
+                sys::MS_OP_SEND_CTRL_C => Handle::current().send_ctrl_c(sh.node_handles.lock().unwrap()[a as usize].as_ref().expect("node").id()),
+                sys::MS_OP_RECV_OR_CTRL_C => {
+                    let won = {
+                        let mut rx = std::pin::pin!(eps[&a].recv_from((b >> 8) as u64, &mut buf));
+                        let mut sig = std::pin::pin!(madsim::signal::ctrl_c());
+                        std::future::poll_fn(|cx| {
+                            use std::task::Poll;
+                            if b & 1 == 0 {
+                                if sig.as_mut().poll(cx).is_ready() { return Poll::Ready(None); }
+                            }
+                            if let Poll::Ready(r) = rx.as_mut().poll(cx) { return Poll::Ready(Some(r)); }
+                            if b & 1 == 1 {
+                                if sig.as_mut().poll(cx).is_ready() { return Poll::Ready(None); }
+                            }
+                            Poll::Pending
+                        })
+                        .await
+                    };
+                    match won {
+                        Some(r) => {
+                            let (len, f) = r.unwrap();
+                            val = sh.value_of(&buf[..len]);
+                            from = Some(f);
+                        }
+                        None => val = sys::MADSIM_VAL_TIMEOUT,
                     }
                 }
                 sys::MS_OP_ASSERT_VAL => assert_eq!(val, imm),

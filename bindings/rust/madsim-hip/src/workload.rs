@@ -128,6 +128,16 @@ impl TaskBuilder {
         assert!(d.as_secs() <= 255);
         self.emit(sys::MS_OP_RECV_TIMEOUT_AT, ep.0, ((tag as u16) << 8) | d.as_secs() as u16, d.subsec_nanos(), false)
     }
+    // ---- ctrl-c signals (signal.rs, task/mod.rs:426-441) ---------------------------------------------------------------------------
+    /// `signal::ctrl_c().await.unwrap()`: installs the node's handler at its first poll, completes on the next signal sent after it.
+    pub fn ctrl_c(&mut self) -> &mut Self { self.emit(sys::MS_OP_CTRL_C, 0, 0, 0, false) }
+    /// `Handle::current().send_ctrl_c(node)`: kills a node without a handler, else wakes its waiting tasks (nobody waiting: lost).
+    pub fn send_ctrl_c(&mut self, node: u8) -> &mut Self { self.emit(sys::MS_OP_SEND_CTRL_C, node, 0, 0, false) }
+    /// `select! { biased; _ = ctrl_c() => .., (msg, from) = ep.recv_from(tag) => .. }` (`recv_first`: the recv arm first).  A won
+    /// ctrl-c arm sets `val = MADSIM_VAL_TIMEOUT`.
+    pub fn recv_or_ctrl_c(&mut self, ep: Addr, tag: u8, recv_first: bool) -> &mut Self {
+        self.emit(sys::MS_OP_RECV_OR_CTRL_C, ep.0, ((tag as u16) << 8) | recv_first as u16, 0, false)
+    }
     // ---- supervisor ----------------------------------------------------------------------------------------------------------
     pub fn kill(&mut self, node: u8) -> &mut Self { self.emit(sys::MS_OP_KILL, node, 0, 0, false) }
     pub fn restart(&mut self, node: u8) -> &mut Self { self.emit(sys::MS_OP_RESTART, node, 0, 0, false) }

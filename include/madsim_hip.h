@@ -197,6 +197,26 @@ enum madsim_op {
                               program's MARK (which must stand at a lower pc); the deadline max(t0 + d, now + 1 ms) is fixed when
                               the op starts (time/mod.rs:144-156, the sleep_until floor).  Otherwise MS_OP_RECV_TIMEOUT: a message
                               does not move the deadline.  Not inside a timeout scope.                                      */
+    /* -- ctrl-c signals (signal.rs:4-8, task/mod.rs:166-175,426-441; additive: new opcode values only, the ABI stays v7) -------------- */
+    MS_OP_CTRL_C = 67,     /* signal::ctrl_c().await.unwrap().  Its first poll marks the task's NodeInfo "handler installed" (for the rest
+                              of that incarnation: a restart makes a NodeInfo without it, a kill alone leaves it) and subscribes: it
+                              sees only signals sent after that poll, so it is always Pending there.  No timer, no draw; it is woken
+                              by another task's MS_OP_SEND_CTRL_C and completes on that poll.  val is unchanged.                  */
+    MS_OP_SEND_CTRL_C = 68,/* a=node: Handle::current().send_ctrl_c(node).  No handler installed on the node's current NodeInfo: exactly
+                              MS_OP_KILL (kill_id).  Installed: every task of that NodeInfo parked in a ctrl_c(), or in a select whose
+                              ctrl-c arm is pending, is woken (a task that is scheduled already is not queued again; on a paused node the
+                              runnable is parked); nothing else happens — a signal nobody waits for is lost.  Never awaits.  A send
+                              that would schedule two or more tasks is MADSIM_UNSUPPORTED for that seed: the order in which tokio's
+                              watch::Sender wakes several waiters is picked by a thread-local generator the seed does not control.  */
+    MS_OP_RECV_OR_CTRL_C = 69,/* a=sock, b=(tag<<8)|flags: select! { biased; _ = ctrl_c() => .., (msg, from) = ep.recv_from(tag) => .. },
+                              flags bit 0: the recv arm is polled first.  Every poll polls both arms in that order.  The ctrl-c arm is
+                              MS_OP_CTRL_C's (installs and subscribes at the select's first poll, never Ready there); the recv arm is
+                              MS_OP_RECV_TIMEOUT's, dropped under MS_OP_RECV_OR_TICK's rules.  Ctrl-c wins: val := MADSIM_VAL_TIMEOUT, a
+                              message the recv arm took is lost (its draw and its timer stay), a registration goes dead.  Recv wins: val /
+                              from as MS_OP_RECV_TIMEOUT sets them and the subscription is dropped — the next select subscribes afresh, so
+                              a signal sent between two selects, or to a recv-first select whose message is ready, is lost.
+                              None of the three ops may share a workload with a timer-tier op (MS_OP_TIMEOUT_BEGIN / END, INTERVAL, TICK,
+                              INTERVAL_RESET, RECV_OR_TICK, RECV_TIMEOUT_AT): no kernel build carries both (MADSIM_E_WORKLOAD).            */
     MS_OP__COUNT
 };
 #define MADSIM_IPVS_ADD_SERVICE 0u
@@ -648,7 +668,7 @@ typedef struct madsim_geometry {
                                     * timer-heap entries (MADSIM_STATE_NARROW_HEAP); bits 16-19 = compile-time log2 lane
                                     * stride (15 = runtime); bit 20 = timeout scopes compiled in (MS_OP_TIMEOUT_BEGIN / END); bit 21 = interval
                                     * tickers compiled in (MS_OP_INTERVAL / TICK / INTERVAL_RESET); bit 22 = selects compiled in (MS_OP_RECV_OR_TICK /
-                                    * RECV_TIMEOUT_AT, v7) */
+                                    * RECV_TIMEOUT_AT, v7); bit 23 = ctrl-c signals compiled in (MS_OP_CTRL_C / SEND_CTRL_C / RECV_OR_CTRL_C) */
     uint32_t global_bytes_per_seed; /* size of a lane's state block in global memory (global-state builds), else 0 */
 } madsim_geometry_t;
 int madsim_hip_geometry(const madsim_workload_t* w, const madsim_limits_t* lim, madsim_geometry_t* g);

@@ -191,6 +191,14 @@ class Task {
         if (ns / 1000000000ull > 0xff) throw std::invalid_argument("recv_from_timeout_at: at most 255 s");
         return emit(MS_OP_RECV_TIMEOUT_AT, (uint8_t)ep, (uint16_t)((tag << 8) | (ns / 1000000000ull)), (uint32_t)(ns % 1000000000ull));
     }
+    // signal::ctrl_c().await, Handle::current().send_ctrl_c(node) and select! { biased; ctrl_c(), recv_from(tag) } (recv_first: the recv arm
+    // first) — MS_OP_CTRL_C / MS_OP_SEND_CTRL_C / MS_OP_RECV_OR_CTRL_C.  A won ctrl-c arm: val = MADSIM_VAL_TIMEOUT.  Not in a workload with
+    // timeout scopes, tickers, recv_or_tick or recv_from_timeout_at.
+    Task& ctrl_c() { return emit(MS_OP_CTRL_C); }
+    Task& send_ctrl_c(int node) { return emit(MS_OP_SEND_CTRL_C, (uint8_t)node); }
+    Task& recv_or_ctrl_c(int ep, uint8_t tag, bool recv_first = false) {
+        return emit(MS_OP_RECV_OR_CTRL_C, (uint8_t)ep, (uint16_t)((tag << 8) | (recv_first ? 1 : 0)));
+    }
     // time::timeout(d, async { .. }) over the ops up to timeout_end(scope) (MS_OP_TIMEOUT_BEGIN / END): returns the scope handle;
     // jmp_scope_end / jeq_scope_end jump to its END before it exists (an early return, connect1's `?`).  Expired: val = MADSIM_VAL_TIMEOUT.
     int timeout_begin(std::chrono::nanoseconds d) {

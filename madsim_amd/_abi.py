@@ -136,7 +136,8 @@ class Geometry(C.Structure):
 VARIANT_SCOPE = 1 << 20     # madsim_geometry_t.variant: timeout scopes (MS_OP_TIMEOUT_BEGIN / END) compiled in
 VARIANT_TICK = 1 << 21      # madsim_geometry_t.variant: interval tickers (MS_OP_INTERVAL / TICK / INTERVAL_RESET) compiled in
 VARIANT_SELECT = 1 << 22    # madsim_geometry_t.variant: selects over a receive and a tick, timeout_at (MS_OP_RECV_OR_TICK / RECV_TIMEOUT_AT) compiled in
-VARIANT_TIER_FEAT = ((VARIANT_SCOPE, 256), (VARIANT_TICK, 512), (VARIANT_SELECT, 1024))   # report bit -> MADSIM_FEAT_SCOPE / TICK / SELECT
+VARIANT_SIGNAL = 1 << 23    # madsim_geometry_t.variant: ctrl-c signals (MS_OP_CTRL_C / SEND_CTRL_C / RECV_OR_CTRL_C) compiled in
+VARIANT_TIER_FEAT = ((VARIANT_SCOPE, 256), (VARIANT_TICK, 512), (VARIANT_SELECT, 1024), (VARIANT_SIGNAL, 2048))   # report bit -> MADSIM_FEAT_SCOPE / TICK / SELECT / SIGNAL
 
 
 HEADER_STRUCTS["madsim_campaign_t"] = Campaign
@@ -163,6 +164,7 @@ OP = dict(
     KILL=30, RESTART=31, PAUSE=32, RESUME=33, CLOG_NODE=34, UNCLOG_NODE=35, CLOG_LINK=36,
     UNCLOG_LINK=37, ASSERT_EXIT=38, SET_LOSS=39, SLEEP_RAND=40, GSET=41, GADD=42, ASSERT_G=43, PANIC_IF_G_LT=44, JEQ=45, CONNECT=46, ACCEPT=47, CSEND=48, CRECV=49, CCLOSE=50, RPC_CALL=51, RPC_REPLY=52, RAND_BOOL=53, RANDOM=54, TRACE_TIME=55, HOOK_REQ=56, HOOK_RSP=57, IPVS=58, SET_LATENCY=59,
     TIMEOUT_BEGIN=60, TIMEOUT_END=61, INTERVAL=62, TICK=63, INTERVAL_RESET=64, RECV_OR_TICK=65, RECV_TIMEOUT_AT=66,
+    CTRL_C=67, SEND_CTRL_C=68, RECV_OR_CTRL_C=69,
 )
 PROG_INIT, PROG_PRE, PROG_DROP_SPAWN = 1, 2, 4
 NODE_RESTART_ON_PANIC = 1

@@ -124,14 +124,15 @@ inline int validate(const madsim_workload_t* w, const madsim_config_t* cfg, std:
         case MS_OP_DJNZ: case MS_OP_JMP: case MS_OP_JEQ:
             if (in.b >= w->n_insns) return fail(err, MADSIM_E_WORKLOAD, "jump target out of range"); break;
         case MS_OP_BIND: case MS_OP_REPLY: case MS_OP_RECV: case MS_OP_CLOSE: case MS_OP_RECV_TIMEOUT: case MS_OP_ACCEPT:
-        case MS_OP_RECV_OR_TICK: case MS_OP_RECV_TIMEOUT_AT:
+        case MS_OP_RECV_OR_TICK: case MS_OP_RECV_TIMEOUT_AT: case MS_OP_RECV_OR_CTRL_C:
             if (in.a >= w->n_socks) return fail(err, MADSIM_E_WORKLOAD, "socket operand out of range");
             // (the reference would let an IP-less node bind it and answer AddrNotAvailable to every other: not modelled, refused)
             if (w->socks[in.a].kind == MADSIM_ADDR_VIRTUAL) return fail(err, MADSIM_E_WORKLOAD, "a virtual address is a destination only: it cannot be bound or used as an Endpoint");
-            if ((in.op == MS_OP_REPLY || in.op == MS_OP_RECV || in.op == MS_OP_RECV_TIMEOUT || in.op == MS_OP_RECV_OR_TICK || in.op == MS_OP_RECV_TIMEOUT_AT)
-                && (in.b >> 8) > MADSIM_TAG_RPC_LAST)
+            if ((in.op == MS_OP_REPLY || in.op == MS_OP_RECV || in.op == MS_OP_RECV_TIMEOUT || in.op == MS_OP_RECV_OR_TICK || in.op == MS_OP_RECV_TIMEOUT_AT ||
+                 in.op == MS_OP_RECV_OR_CTRL_C) && (in.b >> 8) > MADSIM_TAG_RPC_LAST)
                 return fail(err, MADSIM_E_WORKLOAD, "tags 0xFE and 0xFF are reserved");
             if (in.op == MS_OP_RECV_OR_TICK && (in.b & 0xfc)) return fail(err, MADSIM_E_WORKLOAD, "recv_or_tick: b bits 0-1 are the flags (1 tick arm first, 2 fold the tick's instant)");
+            if (in.op == MS_OP_RECV_OR_CTRL_C && (in.b & 0xfe)) return fail(err, MADSIM_E_WORKLOAD, "recv_or_ctrl_c: b bit 0 is the only flag (1 recv arm first)");
             if (in.op == MS_OP_RECV_TIMEOUT_AT && in.imm >= 1000000000u) return fail(err, MADSIM_E_WORKLOAD, "recv_from_timeout_at: imm is the nanoseconds below one second");
             break;
         case MS_OP_SEND: case MS_OP_CONNECT:
@@ -155,7 +156,7 @@ inline int validate(const madsim_workload_t* w, const madsim_config_t* cfg, std:
             if ((uint32_t)(in.b >> 8) < MADSIM_TAG_RPC_FIRST || (uint32_t)(in.b >> 8) > MADSIM_TAG_RPC_LAST) return fail(err, MADSIM_E_WORKLOAD, "hook_rpc_req needs a typed request tag (0x80..0xFD)");
             /* fall through */
         case MS_OP_HOOK_RSP:
-        case MS_OP_BUILD: case MS_OP_KILL: case MS_OP_RESTART: case MS_OP_PAUSE: case MS_OP_RESUME:
+        case MS_OP_BUILD: case MS_OP_KILL: case MS_OP_RESTART: case MS_OP_PAUSE: case MS_OP_RESUME: case MS_OP_SEND_CTRL_C:
         case MS_OP_CLOG_NODE: case MS_OP_UNCLOG_NODE: case MS_OP_ASSERT_EXIT:
             if (in.a > w->n_nodes) return fail(err, MADSIM_E_WORKLOAD, "node operand out of range"); break;
         case MS_OP_CLOG_LINK: case MS_OP_UNCLOG_LINK:
@@ -263,6 +264,14 @@ inline int validate(const madsim_workload_t* w, const madsim_config_t* cfg, std:
             }
         }
     }
+    {   // ctrl-c signals (MS_OP_CTRL_C / SEND_CTRL_C / RECV_OR_CTRL_C) run on builds of their own, which carry no timer-op tier: a workload that
+        // uses both has no build (a limit of the compiled set, not of madsim)
+        const bool signals = uses_op(w, MS_OP_CTRL_C) || uses_op(w, MS_OP_SEND_CTRL_C) || uses_op(w, MS_OP_RECV_OR_CTRL_C);
+        const bool tiers = uses_op(w, MS_OP_TIMEOUT_BEGIN) || uses_op(w, MS_OP_TIMEOUT_END) || uses_op(w, MS_OP_INTERVAL) || uses_op(w, MS_OP_TICK) ||
+                           uses_op(w, MS_OP_INTERVAL_RESET) || uses_op(w, MS_OP_RECV_OR_TICK) || uses_op(w, MS_OP_RECV_TIMEOUT_AT);
+        if (signals && tiers)
+            return fail(err, MADSIM_E_WORKLOAD, "ctrl-c signal ops cannot be combined with timeout scopes, interval tickers, recv_or_tick or recv_from_timeout_at: no kernel build carries both");
+    }
     for (uint32_t p = 0; p < w->n_progs; p++) {
         if (!(w->progs[p].flags & MADSIM_PROG_DROP_SPAWN)) continue;
         if (p + 1 >= w->n_progs || w->progs[p + 1].node != w->progs[p].node)
@@ -278,7 +287,7 @@ inline int validate(const madsim_workload_t* w, const madsim_config_t* cfg, std:
         uint32_t resettable = 0;
         for (uint32_t i = 0; i < w->n_insns; i++) {
             const madsim_insn_t& in = w->insns[i];
-            if (in.op == MS_OP_KILL || in.op == MS_OP_RESTART) resettable |= 1u << in.a;
+            if (in.op == MS_OP_KILL || in.op == MS_OP_RESTART || in.op == MS_OP_SEND_CTRL_C) resettable |= 1u << in.a;   // (a ctrl-c without a handler is kill_id)
         }
         for (uint32_t n = 0; n <= w->n_nodes && w->nodes; n++) if (w->nodes[n].flags & (MADSIM_NODE_RESTART_ON_PANIC | MADSIM_NODE_RESTART_MATCHING)) resettable |= 1u << n;
         for (uint32_t p = 0; p < w->n_progs; p++) if (w->progs[p].flags & MADSIM_PROG_INIT) resettable |= 1u << w->progs[p].node;
@@ -357,6 +366,7 @@ inline int make_geometry(const Device& g, const madsim_workload_t* w, const mads
     P.heap_spill = (L.heap_lds_slots || L.heap_spill_slots) ? L.heap_spill_slots : 56;
     bool t0 = uses_op(w, MS_OP_MARK) || uses_op(w, MS_OP_SLEEP_UNTIL) || uses_op(w, MS_OP_ASSERT_ELAPSED) || uses_op(w, MS_OP_RECV_TIMEOUT) || P.uses_rpc;
     t0 |= uses_op(w, MS_OP_RECV_OR_TICK) || uses_op(w, MS_OP_RECV_TIMEOUT_AT);      // (the receive of either rides RECV_TIMEOUT's path)
+    t0 |= uses_op(w, MS_OP_RECV_OR_CTRL_C);                                          // (likewise)
     // (MS_OP_CCLOSE alone counts too: without the connection unit a stray `drop((tx, rx))` read the task's flag word as a connection id)
     P.uses_chan = uses_op(w, MS_OP_CONNECT) || uses_op(w, MS_OP_ACCEPT) || uses_op(w, MS_OP_CSEND) || uses_op(w, MS_OP_CRECV) || uses_op(w, MS_OP_CCLOSE);
     // task units: 0-1 always; 2 = {t0, timeout()'s deadline} when used; then the connection unit, then the RPC unit
@@ -413,6 +423,10 @@ inline int make_geometry(const Device& g, const madsim_workload_t* w, const mads
     if (uses_op(w, MS_OP_RECV_TIMEOUT) || uses_op(w, MS_OP_MARK) || uses_op(w, MS_OP_SLEEP_UNTIL) || uses_op(w, MS_OP_ASSERT_ELAPSED) ||
         uses_op(w, MS_OP_ADVANCE) || uses_op(w, MS_OP_TRACE_TIME) || P.uses_set_lat) P.features |= MADSIM_FEAT_TIME;   // (set_latency: any extended build; this is the leanest)
     if (uses_op(w, MS_OP_RECV_OR_TICK) || uses_op(w, MS_OP_RECV_TIMEOUT_AT)) P.features |= MADSIM_FEAT_TIME;
+    // ctrl-c signals: a send without a handler is kill_id (the node class); the select's receive rides RECV_TIMEOUT's path (the time class)
+    const bool signals = uses_op(w, MS_OP_CTRL_C) || uses_op(w, MS_OP_SEND_CTRL_C) || uses_op(w, MS_OP_RECV_OR_CTRL_C);
+    if (signals) P.features |= MADSIM_FEAT_NODE;
+    if (uses_op(w, MS_OP_RECV_OR_CTRL_C)) P.features |= MADSIM_FEAT_TIME;
     if (P.uses_chan) P.features |= MADSIM_FEAT_CHAN;
     if (P.uses_rpc) P.features |= MADSIM_FEAT_RPC | MADSIM_FEAT_TIME;            // call_timeout rides the timeout unit
     if (P.has_restart_on_panic || uses_op(w, MS_OP_KILL) || uses_op(w, MS_OP_RESTART) || uses_op(w, MS_OP_PAUSE) || uses_op(w, MS_OP_RESUME) ||
@@ -430,6 +444,7 @@ inline int make_geometry(const Device& g, const madsim_workload_t* w, const mads
     const bool ticks = uses_op(w, MS_OP_INTERVAL) || selects;
     if (ticks) P.features |= MADSIM_FEAT_TICK;
     if (selects) P.features |= MADSIM_FEAT_SELECT;
+    if (signals) P.features |= MADSIM_FEAT_SIGNAL;    // (outside MADSIM_FEAT_ALL too: only these workloads select the signal builds)
     P.lifecycle = P.features != 0;
     const uint32_t cus = g.num_cus > 0 ? (uint32_t)g.num_cus : 256u;
     uint32_t lw = 64;
@@ -442,7 +457,7 @@ inline int make_geometry(const Device& g, const madsim_workload_t* w, const mads
         return fail(err, MADSIM_E_LIMITS, "state_mem must be 0 (auto), 1 (LDS), 2 (global) or 3 (compact), optionally | MADSIM_STATE_DEDUP_TIMERS | MADSIM_STATE_NARROW_HEAP");
     // MADSIM_STATE_NARROW_HEAP: 8-byte heap entries hold the low deadline word — admitted when nothing the workload can ask for lies 2^31 ns
     // ahead of the clock (the device checks every push all the same: a channel back-off can grow past it at run time)
-    bool narrow_ok = (L.state_mem & MADSIM_STATE_NARROW_HEAP) && !trace && !cfg->buggify && !P.has_restart_on_panic && !scopes && !ticks;   // (no narrow scope / ticker build)
+    bool narrow_ok = (L.state_mem & MADSIM_STATE_NARROW_HEAP) && !trace && !cfg->buggify && !P.has_restart_on_panic && !scopes && !ticks && !signals;   // (no narrow scope / ticker / signal build)
     {
         uint64_t horizon = std::max<uint64_t>(cfg->lat_hi_ns, 1000000ull);
         for (uint32_t i = 0; i < cfg->n_lat_table && i < 4; i++) horizon = std::max<uint64_t>(horizon, cfg->lat_table_hi_ns[i]);
@@ -477,7 +492,8 @@ inline int make_geometry(const Device& g, const madsim_workload_t* w, const mads
         // JoinHandle words: a plane with the extended ops, else unit1.y of task slot p (sim_kernel.hip HW)
         P.off_nodes = P.off_handles + (P.lifecycle ? P.n_progs : 0);
         // node region (extended ops only): killed / paused / gen0_killed masks, spawn counter, one info_gen byte per node
-        P.off_clog = P.off_nodes + (P.lifecycle ? 4 + (P.n_nodes + 4) / 4 + 1 : 0);   // + the base-time word
+        // (signal builds' workloads only: one more mask behind the base-time word, "a ctrl-c handler is installed" — k_state.h NODE_SIGW)
+        P.off_clog = P.off_nodes + (P.lifecycle ? 4 + (P.n_nodes + 4) / 4 + 1 + (signals ? 1 : 0) : 0);   // + the base-time word
         P.off_pause = P.off_clog + (P.has_clog ? 2 + (P.has_clog_link ? P.n_nodes + 1 : 0) : 0);
         P.uses_pause = uses_op(w, MS_OP_PAUSE);
         P.off_greg = P.off_pause + (P.uses_pause ? 1 + P.max_tasks : 0);

@@ -298,12 +298,54 @@ __device__ __forceinline__ void node_restart(const Ctx& c, Lane& L, uint32_t nod
     NODEW(4 + (node >> 2)) = (w & ~(0xffu << sh)) | (((g + 1) & 0xff) << sh);      // new_info
     NODEW(0) &= ~(1u << node);
     NODEW(1) &= ~(1u << node);
+    if constexpr (K::FSIG) NODE_SIGW &= ~(1u << node);       // ctrl_c: Mutex::new(None)
     paused_clear<K>(c, L, node);
     info_kill<K>(c, L, node, g);                             // old_info.kill()
     for (uint32_t p = 1; p < c.P.n_progs; p++) {             // init(&Spawner { new info })
         uint32_t pw = PROGW(c, p);
         if ((pw & 0xff) == node && ((pw >> 8) & MADSIM_PROG_INIT)) spawn_task<K>(c, L, p, false);
     }
+}
+
+// TaskHandle::send_ctrl_c (task/mod.rs:426-441).  No task of the node's current NodeInfo has called signal::ctrl_c(): kill_id.  Else
+// watch::Sender::send: every task of that NodeInfo subscribed to the channel — parked in MS_OP_CTRL_C, or in MS_OP_RECV_OR_CTRL_C (both arms of that
+// select are polled at its first poll, so a parked select is subscribed) — finds a new version at its next poll (SUB_SIGNALLED) and gets
+// waker.wake(): the ordinary wake path, a task that is SCHEDULED already is not queued again.  The order in which tokio wakes several
+// waiters is not the seed's, so the tasks the send would schedule are counted before any is woken: two or more leave the workload model.
+// One scan of the node's live tasks, in the style of info_kill; global-state builds: the alive mask from LDS, four tasks per round trip.
+template <class K>
+__device__ __forceinline__ void node_send_ctrl_c(const Ctx& c, Lane& L, uint32_t node) {
+    if (!(((uint32_t)NODE_SIGW >> node) & 1)) { node_kill<K>(c, L, node); return; }     // "ctrl-c" has never been called: kill node
+    const uint32_t g = NODE_INFO_GEN(node);
+    uint32_t n = 0, w_slot = 0, w_f = 0;
+    auto visit = [&](uint32_t t, uint32_t f, uint32_t y, uint32_t sw) {
+        if (!(f & TF_ALIVE) || (PROGW(c, f >> 24) & 0xff) != node || (sw >> 24) != g) return;
+        const uint32_t sub = (y >> 16) & 0xff, op = INSN(c, y & 0xffff).x & 0xff;
+        if ((op != MS_OP_CTRL_C && op != MS_OP_RECV_OR_CTRL_C) || sub == 0 || sub >= SUB_JOIN_WAIT) return;
+        TWORD(c, t, 0, 1) = y | (SUB_SIGNALLED << 16);
+        if (!(f & TF_SCHED)) { n++; w_slot = t; w_f = f; }
+    };
+    if constexpr (K::G) {
+        for (uint32_t wi = 0; wi < (c.P.max_tasks + 31) / 32; wi++) {
+            uint32_t m = AMASK(wi);
+            while (m) {
+                uint32_t ix[4], fw[4], yw[4], sw[4], k4 = 0;
+                for (uint32_t k = 0; k < 4; k++) { ix[k] = wi * 32 + (uint32_t)__builtin_ctz(m | 0x80000000u); if (m) { k4++; m &= m - 1; } }
+                for (uint32_t k = 0; k < 4; k++) {
+                    const uint32_t t = k < k4 ? ix[k] : ix[0];
+                    fw[k] = TWORD(c, t, 0, 0); yw[k] = TWORD(c, t, 0, 1); sw[k] = TWORD(c, t, 1, 1);
+                }
+                for (uint32_t k = 0; k < k4; k++) visit(ix[k], fw[k], yw[k], sw[k]);
+            }
+        }
+    } else {
+        for (uint32_t t = 0; t < c.P.max_tasks; t++) {
+            const uint32_t f = TWORD(c, t, 0, 0);
+            if (f & TF_ALIVE) visit(t, f, TWORD(c, t, 0, 1), TWORD(c, t, 1, 1));
+        }
+    }
+    if (n >= 2) OVF_SET(L, OVF_MODEL);
+    else if (n == 1) wake_with<K>(c, L, w_slot, (w_f >> 8) & 0xffff, w_f);
 }
 
 }  // namespace madsim_k

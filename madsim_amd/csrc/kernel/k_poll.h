@@ -51,9 +51,10 @@ __device__ __forceinline__ uint4 insn_fetch(const Ctx& c, Lane& L, uint32_t pc) 
     uint4 in = INSN(c, pc);
     if (!PLAIN_ADDR && c.P.uses_eph) {
         const uint32_t op = in.x & 0xff;
-        const bool own = op == MS_OP_SEND || op == MS_OP_CONNECT || op == MS_OP_RPC_CALL || op == MS_OP_REPLY || op == MS_OP_RECV ||
-                         op == MS_OP_RECV_TIMEOUT || op == MS_OP_CLOSE || op == MS_OP_ACCEPT || op == MS_OP_RPC_REPLY ||   // a names an Endpoint
-                         (K::FSEL && (op == MS_OP_RECV_OR_TICK || op == MS_OP_RECV_TIMEOUT_AT));
+        bool own = op == MS_OP_SEND || op == MS_OP_CONNECT || op == MS_OP_RPC_CALL || op == MS_OP_REPLY || op == MS_OP_RECV ||
+                   op == MS_OP_RECV_TIMEOUT || op == MS_OP_CLOSE || op == MS_OP_ACCEPT || op == MS_OP_RPC_REPLY ||   // a names an Endpoint
+                   (K::FSEL && (op == MS_OP_RECV_OR_TICK || op == MS_OP_RECV_TIMEOUT_AT));
+        if constexpr (K::FSIG) own = own || op == MS_OP_RECV_OR_CTRL_C;      // (a statement of its own: the other builds' expression is the one they had)
         const uint32_t s = (in.x >> 8) & 0xff;
         if (own && (SOCKW(c, s) & 0x8000u)) {
             if (handle_names_its_socket<K>(c, s)) in.x = (in.x & ~0xff00u) | (sock_resolve<K>(c, s) << 8);
@@ -131,6 +132,10 @@ __device__ __forceinline__ bool poll_task(const Ctx& c, Lane& L, const uint32_t 
     const uint32_t gen = (u0.x >> 8) & 0xffff;
     const uint32_t node = PROGW(c, u0.x >> 24) & 0xff;
     uint32_t st = ST_RUN;
+    // signal builds: a MS_OP_SEND_CTRL_C reached this task while it was subscribed (k_state.h SUB_SIGNALLED).  The op it is parked on consumes it
+    // in this poll — ctrl_c() completes, the select's ctrl-c arm is Ready — or loses it (a recv-first select whose message is ready).
+    bool sig = false;
+    if constexpr (K::FSIG) { sig = (sub & SUB_SIGNALLED) != 0; sub &= ~SUB_SIGNALLED; }
 
     // timeout(d, ep.recv_from(tag)) = select_biased! { fut, sleep } (time/mod.rs:128-140): poll the recv future,
     // then the timeout's Sleep — which registers ANOTHER timer on every not-elapsed poll (time/sleep.rs:51-53).
@@ -166,9 +171,14 @@ __device__ __forceinline__ bool poll_task(const Ctx& c, Lane& L, const uint32_t 
     //  arm in the Sleep's place, polled first when its flags say so — select_tick_arm.  The caller passes `sel` = SEL_ON | the op's flags (b & 3)
     //  for a select, 0 otherwise.  timeout_at, MS_OP_RECV_TIMEOUT_AT, is this poll as it stands: only its deadline was computed differently.
     //  Everything of the select sits under `if constexpr`: the other builds compile to what they were.)
+    // (select! { biased; .. } over ctrl_c() and recv_from, MS_OP_RECV_OR_CTRL_C (signal builds, MADSIM_FEAT_SIGNAL): the same poll again with the
+    //  ctrl-c arm in the Sleep's place, `sel` = SEL_SIG | SEL_TICK_FIRST when that arm is polled first.  The arm is Ready when a signal came since
+    //  it subscribed (`sig`): the recv arm is dropped as a won tick drops it — RX_DROP, a message it took is lost with its draw and its
+    //  timer — and val := TIMEOUT.  It registers nothing while Pending: no timer.)
     auto recv_timeout_poll = [&](uint32_t sel = 0) -> bool {
         if constexpr (K::FSEL) if ((sel & (SEL_ON | SEL_TICK_FIRST)) == (SEL_ON | SEL_TICK_FIRST) &&
                                     select_tick_arm<K>(c, L, slot, gen, u0, u1, u1_dirty, !first_poll, sel >> 1)) return true;
+        if constexpr (K::FSIG) if ((sel & (SEL_SIG | SEL_TICK_FIRST)) == (SEL_SIG | SEL_TICK_FIRST) && sig) { RX_DROP(); u0.w = MADSIM_VAL_TIMEOUT; return true; }
         bool fut_ready = false;
         bool d1_new = false;
         if (sub == 1 && (u0.x & TF_INBOX)) {                 // oneshot ready -> rand_delay (endpoint.rs:145)
@@ -188,6 +198,11 @@ __device__ __forceinline__ bool poll_task(const Ctx& c, Lane& L, const uint32_t 
         if (fut_ready) return true;                          // Ok((len, from))
         if constexpr (K::FSEL) if (sel & SEL_ON) {
             if (!(sel & SEL_TICK_FIRST) && select_tick_arm<K>(c, L, slot, gen, u0, u1, u1_dirty, !first_poll, sel >> 1)) return true;
+            st = ST_PENDING;
+            return false;
+        }
+        if constexpr (K::FSIG) if (sel & SEL_SIG) {
+            if (!(sel & SEL_TICK_FIRST) && sig) { RX_DROP(); u0.w = MADSIM_VAL_TIMEOUT; return true; }
             st = ST_PENDING;
             return false;
         }
@@ -398,6 +413,10 @@ __device__ __forceinline__ bool poll_task(const Ctx& c, Lane& L, const uint32_t 
             } else if (K::FT && (op == MS_OP_RECV_TIMEOUT || (K::FSEL && (op == MS_OP_RECV_TIMEOUT_AT || op == MS_OP_RECV_OR_TICK)))) {
                 if constexpr (K::FSEL) completed = recv_timeout_poll(op == MS_OP_RECV_OR_TICK ? SEL_ON | (b & 3u) : 0u);
                 else completed = recv_timeout_poll();       // (false: st is Pending — the round leaves behind [B], no `break` here)
+            } else if (K::FSIG && op == MS_OP_RECV_OR_CTRL_C) {   // (a branch of its own: the one above stays what the other builds compiled)
+                completed = recv_timeout_poll(SEL_SIG | ((b & 1u) ? 0u : (uint32_t)SEL_TICK_FIRST));
+            } else if (K::FSIG && op == MS_OP_CTRL_C) {     // rx.changed(): a new version since the subscription, or Pending again (a stale timer's wake)
+                if (sig) completed = true; else st = ST_PENDING;
             } else if (K::FR && op == MS_OP_RPC_CALL) {
                 completed = rpc_call_poll() && st == ST_RUN;
             } else if (K::FC && op == MS_OP_ACCEPT && sub == 2) {
@@ -670,6 +689,9 @@ __device__ __forceinline__ bool poll_task(const Ctx& c, Lane& L, const uint32_t 
                                     (K::FSEL && (op == MS_OP_RECV_TIMEOUT_AT || op == MS_OP_RECV_OR_TICK)))) {
             c_hdr = SW(c, a, 0); c_q0 = SW(c, a, 2 + P.mbox_regs); c_q1 = SW(c, a, 3 + P.mbox_regs);
         }
+        if constexpr (K::FSIG) if (RecvPrefetch<K>::ON && op == MS_OP_RECV_OR_CTRL_C) {
+            c_hdr = SW(c, a, 0); c_q0 = SW(c, a, 2 + P.mbox_regs); c_q1 = SW(c, a, 3 + P.mbox_regs);
+        }
         // (... and the first reads of `spawn` and of a task that ends — the two rare-op handlers every pass of the topology runs: with the receives'
         //  requests above the whole stage waits once.  The free slot is the one spawn_task would find: the alive mask changes in spawn / finish only.)
         uint32_t g_slot = ~0u, g_old = 0, g_gen = 0, g_seq = 0, g_killed = 0, g_hw = 0;
@@ -735,9 +757,13 @@ __device__ __forceinline__ bool poll_task(const Ctx& c, Lane& L, const uint32_t 
             tick_complete<K>(c, L, slot, TU(c, slot, P.tick_unit), b >> 1);
             u0.w = MADSIM_VAL_TIMEOUT;
             pc++;
-        } else if (K::FT && (op == MS_OP_RECV_TIMEOUT || (K::FSEL && (op == MS_OP_RECV_TIMEOUT_AT || op == MS_OP_RECV_OR_TICK)))) {
+        } else if (K::FT && (op == MS_OP_RECV_TIMEOUT || (K::FSEL && (op == MS_OP_RECV_TIMEOUT_AT || op == MS_OP_RECV_OR_TICK)) || (K::FSIG && op == MS_OP_RECV_OR_CTRL_C))) {
             uint32_t tag = b >> 8;
-            if (!(K::FSEL && op == MS_OP_RECV_OR_TICK)) {      // (a select's time arm is the ticker: no Sleep of its own)
+            if constexpr (K::FSIG) if (op == MS_OP_RECV_OR_CTRL_C) {      // the ctrl-c arm's first poll: node.ctrl_c() installs the handler and subscribes —
+                NODE_SIGW |= 1u << node;                                   // it sees only signals sent from now on
+                sig = false;
+            }
+            if (!(K::FSEL && op == MS_OP_RECV_OR_TICK) && !(K::FSIG && op == MS_OP_RECV_OR_CTRL_C)) {      // (a select's other arm is the ticker / the ctrl-c channel: no Sleep of its own)
                 // timeout()'s Sleep; timeout_at(t0 + d)'s is sleep_until's, from the program's MARK
                 uint64_t d2 = sleep_deadline(L, (K::FSEL && op == MS_OP_RECV_TIMEOUT_AT ? u64of((uint32_t)TWORD(c, slot, 2, 0), (uint32_t)TWORD(c, slot, 2, 1)) : L.clock)
                                                 + (uint64_t)(b & 0xff) * NS_PER_S + imm);
@@ -783,6 +809,7 @@ __device__ __forceinline__ bool poll_task(const Ctx& c, Lane& L, const uint32_t 
             sub = 1;
             first_poll = true;
             if constexpr (K::FSEL) { if (recv_timeout_poll(op == MS_OP_RECV_OR_TICK ? SEL_ON | (b & 3u) : 0u)) { sub = 0; pc++; } }
+            else if constexpr (K::FSIG) { if (recv_timeout_poll(op == MS_OP_RECV_OR_CTRL_C ? SEL_SIG | ((b & 1u) ? 0u : (uint32_t)SEL_TICK_FIRST) : 0u)) { sub = 0; pc++; } }
             else if (recv_timeout_poll()) { sub = 0; pc++; }
             first_poll = false;
         } else if (K::FR && op == MS_OP_RPC_CALL) {          // first poll of timeout(d, ep.call(dst, req)) / ep.call(dst, req)
@@ -1162,6 +1189,20 @@ __device__ __forceinline__ bool poll_task(const Ctx& c, Lane& L, const uint32_t 
                     const uint64_t dl = u64of(tu.z, tu.w);
                     if (L.clock >= dl) { tick_complete<K>(c, L, slot, tu, a); pc++; }
                     else { deadline = dl; want_sleep = true; }
+                }
+                else if constexpr (K::FSIG) {
+                    if (op == MS_OP_CTRL_C) {              // signal::ctrl_c(): node.ctrl_c() (get_or_insert_with + subscribe), then rx.changed() — Pending, no timer
+                        NODE_SIGW |= 1u << node;
+                        sig = false;
+                        sub = 1;
+                        st = ST_PENDING;
+                    } else if (op == MS_OP_SEND_CTRL_C) {  // (as MS_OP_KILL: the call may kill this task's node)
+                        u0.y = pc | (sub << 16) | (from << 24);
+                        TU(c, slot, 0) = u0;
+                        node_send_ctrl_c<K>(c, L, a);
+                        u0.x = TWORD(c, slot, 0, 0);
+                        pc++;
+                    } else st = ST_PANIC;
                 }
                 else st = ST_PANIC;
                 break;

@@ -44,6 +44,11 @@ enum : uint32_t { TICK_ACTIVE = 1u, TICK_BURST = 0, TICK_DELAY = 1, TICK_SKIP = 
 // MS_OP_RECV_OR_TICK's b flags (k_poll.h): bit 0 = the tick arm is polled first, bit 1 = fold the tick's instant; SEL_ON marks a select
 // in recv_timeout_poll's argument
 enum : uint32_t { SEL_TICK_FIRST = 1u, SEL_ON = 4u };
+// MS_OP_RECV_OR_CTRL_C (signal builds): SEL_SIG marks the select over ctrl_c() and a receive in recv_timeout_poll's argument, with SEL_TICK_FIRST
+// for "the ctrl-c arm is polled first" (the op's b bit 0 says the reverse: recv first).  SUB_SIGNALLED: bit of a parked task's `sub` that
+// MS_OP_SEND_CTRL_C sets in a task subscribed to its node's ctrl-c channel (parked in MS_OP_CTRL_C, or in the select with the arm pending):
+// watch::Receiver::changed() will find a new version.  The task's next poll takes the bit out of `sub` before anything looks at it.
+enum : uint32_t { SEL_SIG = 8u, SUB_SIGNALLED = 0x40 };
 // `sub` values of a task parked in MS_OP_JOIN (bit 7 set: stage [A] of poll_task ignores them, stage [C] owns them)
 enum : uint32_t { SUB_JOIN_WAIT = 0x80, SUB_JOIN_COMPLETED = 0x81, SUB_JOIN_CANCELLED = 0x82 };
 enum : uint32_t { EV_WAKE = 1, EV_DELIVER = 2, EV_RESTART = 3,
@@ -89,6 +94,8 @@ template <bool TRACE_, bool SPILL_, int LWS_, int FEAT_, bool RQ_ = false, bool 
     static constexpr bool FK = (FEAT_ & MADSIM_FEAT_TICK) != 0;
     // selects over a receive and a tick, timeout_at (MS_OP_RECV_OR_TICK / RECV_TIMEOUT_AT): builds of their own, which carry FK and FS too
     static constexpr bool FSEL = (FEAT_ & MADSIM_FEAT_SELECT) != 0;
+    // ctrl-c signals (MS_OP_CTRL_C / SEND_CTRL_C / RECV_OR_CTRL_C): builds of their own with every class, none of the timer-op tiers
+    static constexpr bool FSIG = (FEAT_ & MADSIM_FEAT_SIGNAL) != 0;
 };
 
 // REG(id): divergence-model markers, compiled in only by tools/divergence_model.py's host emulation build
@@ -301,6 +308,9 @@ template <class K> __device__ __forceinline__ WRef<K::G> plane_ref(const Ctx& c,
 #define CONNW(id_, f_) plane_ref<K>(c, c.conn0, (id_) * c.P.conn_words + (f_))
 // node region: [0] killed mask, [1] paused mask, [2] gen0_killed mask, [3] spawn counter, [4 + n/4] info_gen bytes,
 //              then one word: the seed's base time in seconds into 2022 (time/mod.rs:26-33)
+// (signal builds' workloads: one more word behind the base time, bit n = a task of node n's current NodeInfo has called signal::ctrl_c() —
+//  NodeInfo.ctrl_c is Some, task/mod.rs:166-175)
+#define NODE_SIGW NODEW(5 + ((c.P.n_nodes + 4) >> 2))
 #define NODE_INFO_GEN(n_) (((uint32_t)NODEW(4 + ((n_) >> 2)) >> (((n_) & 3) * 8)) & 0xff)
 // Socket s, field f: [0] header, [1] owner (slot | gen << 16), [2 ..] registrations, then queued messages (2 words each),
 // then (channel users) accept queue + parked acceptor.  Header = bound:1 | gen:8 <<1 | nreg:8 <<9 | nmsg <<17.

@@ -1083,7 +1083,7 @@ int madsim_hip_geometry(const madsim_workload_t* w, const madsim_limits_t* lim, 
     out->heap_spill_slots = G.P.heap_spill; out->max_tasks = G.P.max_tasks; out->lanes_per_wave = G.lanes_per_wave;
     const madsim_k::VariantSel v = madsim_k::select_variant(G.P, false);
     out->variant = (v.spill ? 1u : 0u) | ((v.feat & MADSIM_FEAT_ALL) ? 2u : 0u) | (v.rq ? 4u : 0u) | (v.lws < 0 ? 8u : 0u) | (v.g ? 16u : 0u) | ((uint32_t)(v.feat & 0xff) << 8) | ((uint32_t)(v.lws & 0xf) << 16)
-                 | (uint32_t)(v.feat & MADSIM_FEAT_TIERS) >> 8 << 20;     // bits 20-22: the timer-op tier, MADSIM_FEAT_SCOPE / TICK / SELECT in order
+                 | (uint32_t)(v.feat & (MADSIM_FEAT_TIERS | MADSIM_FEAT_SIGNAL)) >> 8 << 20;     // bits 20-22: the timer-op tier, MADSIM_FEAT_SCOPE / TICK / SELECT in order; bit 23: MADSIM_FEAT_SIGNAL
     out->global_bytes_per_seed = G.P.gstate_mode ? G.P.gs_stride : 0;
     return 0;
 }

@@ -42,6 +42,10 @@
 #define MADSIM_FEAT_TICK 512
 #define MADSIM_FEAT_SELECT 1024
 #define MADSIM_FEAT_TIERS (MADSIM_FEAT_SCOPE | MADSIM_FEAT_TICK | MADSIM_FEAT_SELECT)
+/* Ctrl-c signals (MS_OP_CTRL_C / SEND_CTRL_C / RECV_OR_CTRL_C).  Outside MADSIM_FEAT_ALL and outside MADSIM_FEAT_TIERS: a class of its own, not a
+   timer-op tier.  Its workloads run on four builds of their own — MADSIM_TIER_VARIANTS' shapes with this mask alone, every class compiled
+   in — so every other build compiles to what it was; validate() refuses a workload that mixes it with a timer-tier op (no combined build). */
+#define MADSIM_FEAT_SIGNAL 2048
 /* Global-state builds: identical wake-ups are fired as a batch (k_net.h timer_expire).  Sleep::poll registers ANOTHER timer with the same
    deadline and waker on every not-elapsed poll (time/sleep.rs:51-53), so more than half of the topology's heap entries are copies of an
    earlier one; copies leave the heap back to back, and every one after the first finds its task SCHEDULED already (or gone): a step
@@ -165,7 +169,7 @@ struct KParams {
 // fewer registers than the full build; the full build for every lane stride (64/32/16/8 seed lanes per wave, runtime);
 // the global-state builds (G: task table + planes in global memory) of the three extended classes; then the timer-op tiers,
 // each with the four shapes of MADSIM_TIER_VARIANTS: the trace build, the LDS-resident build (runtime lane stride) and the
-// global-state builds (plain addresses, general resolution), every class compiled in.
+// global-state builds (plain addresses, general resolution), every class compiled in; then the ctrl-c signal builds, the same four shapes.
 #ifndef MADSIM_FOR_EACH_VARIANT      // (tools/ may compile a subset: -D'MADSIM_FOR_EACH_VARIANT(X)=X(false,false,6,0,true,false)')
 #define MADSIM_TIER_VARIANTS(X, M)                                              \
     X(true, true, -1, MADSIM_FEAT_ALL | (M), false, false)                      \
@@ -202,7 +206,8 @@ struct KParams {
     X(false, true, 6, (MADSIM_FEAT_ALL & ~MADSIM_FEAT_ADDR) | MADSIM_FEAT_NARROW, false, true) \
     MADSIM_TIER_VARIANTS(X, MADSIM_FEAT_SCOPE)         \
     MADSIM_TIER_VARIANTS(X, MADSIM_FEAT_SCOPE | MADSIM_FEAT_TICK) \
-    MADSIM_TIER_VARIANTS(X, MADSIM_FEAT_SCOPE | MADSIM_FEAT_TICK | MADSIM_FEAT_SELECT)
+    MADSIM_TIER_VARIANTS(X, MADSIM_FEAT_SCOPE | MADSIM_FEAT_TICK | MADSIM_FEAT_SELECT) \
+    MADSIM_TIER_VARIANTS(X, MADSIM_FEAT_SIGNAL)
 #endif
 
 // A compiled specialisation of sim_kernel, and the compiled set as a table in MADSIM_FOR_EACH_VARIANT's order (sim_kernel.hip
@@ -221,8 +226,10 @@ inline int variant_index(const VariantSel& v) {
 }
 inline bool variant_compiled(const VariantSel& v) { return variant_index(v) >= 0; }
 
-// The timer-op tier of a features word: 0, SCOPE, SCOPE|TICK or SCOPE|TICK|SELECT.
+// The timer-op tier of a features word: 0, SCOPE, SCOPE|TICK or SCOPE|TICK|SELECT — or SIGNAL, the ctrl-c class, which shares the tiers'
+// build shapes and none of their ops (validate() keeps the two apart).
 inline int feature_tier(int feat) {
+    if (feat & MADSIM_FEAT_SIGNAL) return MADSIM_FEAT_SIGNAL;
     return (feat & MADSIM_FEAT_SELECT) ? MADSIM_FEAT_TIERS : (feat & MADSIM_FEAT_TICK) ? MADSIM_FEAT_SCOPE | MADSIM_FEAT_TICK : feat & MADSIM_FEAT_SCOPE;
 }
 
@@ -274,7 +281,8 @@ inline const char* variant_mismatch(const KParams& P, const VariantSel& v, bool 
     if (v.rq && (P.max_tasks > 8 || P.lw_shift != 6 || P.lifecycle)) return "register ready queue needs <= 8 tasks, full waves, base ops";
     if (!v.spill && P.heap_spill) return "a build without the spill path on a geometry with spilled heap levels";
     const int classes = v.feat & MADSIM_FEAT_ALL, tier = feature_tier(v.feat);
-    if (((int)P.features & ~(classes | MADSIM_FEAT_TIERS)) != 0) return "the build lacks an op class the workload uses";
+    if (((int)P.features & ~(classes | MADSIM_FEAT_TIERS | MADSIM_FEAT_SIGNAL)) != 0) return "the build lacks an op class the workload uses";
+    if (((int)P.features & MADSIM_FEAT_SIGNAL) && ((int)P.features & MADSIM_FEAT_TIERS)) return "ctrl-c signals and a timer-op tier in one workload: no such build";
     if (tier != feature_tier((int)P.features)) return "the build's timer-op tier differs from the workload's";
     if (tier && (P.narrow || P.dedup_n)) return "a timer-op tier build on a layout with narrow entries or re-registration counts";
     if ((P.scope_unit != 0) != (((int)P.features & MADSIM_FEAT_SCOPE) != 0)) return "the scope unit and the scope class disagree";

@@ -153,6 +153,24 @@ class TaskBuilder:
             raise ValueError("timeout too long")
         return self._emit("RECV_TIMEOUT_AT", a=ep, b=(tag << 8) | b, imm=imm)
 
+    # -- ctrl-c signals: madsim::signal::ctrl_c, Handle::send_ctrl_c (signal.rs:4-8, task/mod.rs:166-175,426-441) --------------------
+    def ctrl_c(self):
+        """`signal::ctrl_c().await.unwrap()`: installs the node's handler at its first poll (from then on a ctrl-c no longer kills the
+        node, until a restart) and completes on the first signal sent after that poll.  No timer, no draw."""
+        return self._emit("CTRL_C")
+
+    def send_ctrl_c(self, node):
+        """`Handle::current().send_ctrl_c(node)`: kills the node when none of its tasks has called ctrl_c() since its last restart;
+        otherwise wakes the tasks waiting in ctrl_c() / recv_or_ctrl_c() and nothing else (nobody waiting: the signal is lost).
+        A send that would schedule two or more tasks ends the seed with the verdict UNSUPPORTED."""
+        return self._emit("SEND_CTRL_C", a=node)
+
+    def recv_or_ctrl_c(self, ep, tag, recv_first=False):
+        """`select! { biased; _ = ctrl_c() => .., (msg, from) = ep.recv_from(tag) => .. }` (recv_first: the recv arm is polled first).
+        Ctrl-c wins: val = VAL_TIMEOUT, and a message the recv arm took is lost.  The recv arm wins: val / from as recv_from sets
+        them; the subscription ends with the select, so a signal sent before the next one starts is lost."""
+        return self._emit("RECV_OR_CTRL_C", a=ep, b=(tag << 8) | (1 if recv_first else 0))
+
     # -- time ------------------------------------------------------------------------------------
     def sleep(self, **kw):
         b, imm = _dur(**kw)
@@ -918,6 +936,111 @@ def lossy_select(rounds=16, sends=12, period_us=2000, body_ms=3, tick_first=Fals
 
 
 def lossy_select_limits():
+    lim = A.Limits()
+    lim.max_tasks = 8
+    lim.mbox_regs, lim.mbox_msgs = 24, 16
+    lim.heap_lds_slots, lim.heap_spill_slots = 16, 48
+    return lim
+
+
+def graceful_shutdown(n_servers=4, n_clients=2, requests=6, recv_first=False):
+    """Graceful shutdown against a crash.  `n_servers` echo servers, one node each, loop on
+    `select! { biased; _ = ctrl_c() => break, (m, from) = ep.recv_from(T) => ep.send_to(from, T, ..) }`; on ctrl-c a server sends a
+    farewell datagram to the supervisor and returns.  One more server node runs a plain `recv_from` loop and installs no handler.
+    Clients send requests round-robin over all servers and wait for each answer with a timeout (a server that has gone answers
+    nothing).  The supervisor lets the clients run, then sends ctrl-c to each node in turn, again every 15 ms until the node's farewell
+    arrives (a signal sent while the server answers a request finds no subscriber and is lost); the node without a handler is killed by
+    the same call (`is_exit`).  One waiter per node: exact."""
+    T, TF = 7, 8
+    wl = WorkloadBuilder()
+    m = wl.main()
+    nodes = [wl.create_node() for _ in range(n_servers + 1)]
+    addrs = [wl.addr(n, 1) for n in nodes]
+    n_sup = wl.create_node()
+    a_sup = wl.addr(n_sup, 1)
+    servers = []
+    for i, (n, a) in enumerate(zip(nodes[:-1], addrs[:-1])):
+        t = wl.task(n)
+        t.bind(a)
+        top = t.label()
+        t.recv_or_ctrl_c(a, T, recv_first=recv_first)
+        out = t.label() + 3
+        t.jeq(A.VAL_TIMEOUT, out); t.reply(a, T, 0x70 + i); t.jmp(top)
+        t.send_to(a, a_sup, TF, 0xB0 + i); t.done()
+        servers.append(t)
+    crash = wl.task(nodes[-1])
+    crash.bind(addrs[-1])
+    top = crash.label()
+    crash.recv_from(addrs[-1], T); crash.reply(addrs[-1], T, 0x7F); crash.jmp(top)
+    clients = []
+    for k in range(n_clients):
+        nc = wl.create_node()
+        ac = wl.addr(nc, 1)
+        c = wl.task(nc)
+        c.bind(ac); c.set(0, requests)
+        top = c.label()
+        for a in addrs:
+            c.send_to(ac, a, T, 0x10 + k); c.recv_from_timeout(ac, T, ms=20); c.trace_val()
+        c.sleep_rand(lo_ms=0, ms=4); c.djnz(0, top); c.done()
+        clients.append(c)
+    sup = wl.task(n_sup)
+    sup.bind(a_sup); sup.sleep(ms=30)
+    for i, n in enumerate(nodes[:-1]):
+        again = sup.label()                        # a server that is answering a request is not subscribed: the signal is lost, send it again
+        sup.send_ctrl_c(n); sup.recv_from_timeout(a_sup, TF, ms=15); sup.jeq(A.VAL_TIMEOUT, again); sup.assert_val(0xB0 + i)
+    sup.send_ctrl_c(nodes[-1]); sup.assert_exit(nodes[-1], True)
+    for n in nodes[:-1]:
+        sup.assert_exit(n, False)
+    sup.done()
+    for t in servers + [crash] + clients + [sup]:
+        m.spawn(t)
+    for t in servers + clients + [sup]:
+        m.join(t)
+    m.done()
+    return wl.build()
+
+
+def graceful_shutdown_limits():
+    lim = A.Limits()
+    lim.max_tasks = 16
+    lim.mbox_regs, lim.mbox_msgs = 48, 8          # (a client's timed-out receives leave dead registrations)
+    lim.heap_lds_slots, lim.heap_spill_slots = 16, 48
+    return lim
+
+
+def shutdown_race(signals=2, sends=4, gap_ms=7, min_caught=None):
+    """The lost-signal bug of a select loop: `loop { select! { biased; _ = ctrl_c() => caught += 1, (m, from) = ep.recv_from(T) =>
+    ep.send_to(from, T, ..) } }`.  Each iteration subscribes afresh, and while the server answers a message (the send's rand_delay) it
+    is not subscribed at all: a ctrl-c sent then wakes nobody.  The supervisor sends `signals` ctrl-cs `gap_ms` apart while a client
+    sends `sends` datagrams at random intervals, then asserts that every signal was caught — some seeds fail it (the first-fail
+    search case)."""
+    T = 7
+    wl = WorkloadBuilder()
+    m = wl.main()
+    ns, nc = wl.create_node(), wl.create_node()
+    a_s, a_c = wl.addr(ns, 1), wl.addr(nc, 1)
+    srv = wl.task(ns)
+    srv.bind(a_s)
+    top = srv.label()
+    srv.recv_or_ctrl_c(a_s, T)
+    caught = srv.label() + 3
+    srv.jeq(A.VAL_TIMEOUT, caught); srv.reply(a_s, T, 0x61); srv.jmp(top)
+    srv.flag_add(0, 1); srv.jmp(top)
+    cl = wl.task(nc)
+    cl.bind(a_c); cl.set(0, sends)
+    top = cl.label()
+    cl.sleep_rand(lo_ms=0, ms=5); cl.send_to(a_c, a_s, T, 0x51); cl.djnz(0, top); cl.done()
+    m.spawn(srv); m.spawn(cl)
+    m.sleep(ms=3)
+    for _ in range(signals):
+        m.send_ctrl_c(ns); m.sleep(ms=gap_ms)
+    m.join(cl)
+    m.panic_if_flag_lt(0, signals if min_caught is None else min_caught)
+    m.done()
+    return wl.build()
+
+
+def shutdown_race_limits():
     lim = A.Limits()
     lim.max_tasks = 8
     lim.mbox_regs, lim.mbox_msgs = 24, 16
