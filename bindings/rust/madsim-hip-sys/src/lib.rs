@@ -146,6 +146,22 @@ pub struct madsim_campaign_t {
 
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
+pub struct madsim_failure_t {
+    pub seed: u64,
+    pub result: madsim_result_t,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct madsim_collect_t {
+    pub failures: *const madsim_failure_t,
+    pub cap: u64,
+    pub n_listed: u64,
+    pub n_by_verdict: [u64; 8],
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
 pub struct madsim_geometry_t {
     pub lds_bytes_per_seed: u32,
     pub lds_bytes_per_block: u32,
@@ -282,6 +298,8 @@ pub const MADSIM_E_NOINIT: c_int = -3;
 pub const MADSIM_E_WORKLOAD: c_int = -4;
 pub const MADSIM_E_LIMITS: c_int = -5;
 pub const MADSIM_CAMPAIGN_STOP_AT_FAILURE: u32 = 1;
+pub const MADSIM_CAMPAIGN_LIST_RUNNER: u32 = 2;
+pub const MADSIM_CAMPAIGN_STOP_AT_CAP: u32 = 4;
 
 #[link(name = "madsim_hip")]
 extern "C" {
@@ -312,6 +330,9 @@ extern "C" {
     pub fn madsim_hip_ctx_run_campaign(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, batch: u64, in_flight: u32, flags: u32, lim: *const madsim_limits_t, out: *mut madsim_campaign_t) -> c_int;
     pub fn madsim_hip_run_campaign(w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, batch: u64, in_flight: u32, flags: u32, lim: *const madsim_limits_t, out: *mut madsim_campaign_t) -> c_int;
     pub fn madsim_hip_run_campaign_multi(ctxs: *const *mut madsim_hip_ctx_t, n_ctx: c_int, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, batch: u64, in_flight: u32, flags: u32, lim: *const madsim_limits_t, out: *mut madsim_campaign_t) -> c_int;
+    pub fn madsim_hip_ctx_run_campaign_collect(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, batch: u64, in_flight: u32, flags: u32, lim: *const madsim_limits_t, out: *mut madsim_campaign_t, col: *mut madsim_collect_t) -> c_int;
+    pub fn madsim_hip_run_campaign_collect(w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, batch: u64, in_flight: u32, flags: u32, lim: *const madsim_limits_t, out: *mut madsim_campaign_t, col: *mut madsim_collect_t) -> c_int;
+    pub fn madsim_hip_run_campaign_collect_multi(ctxs: *const *mut madsim_hip_ctx_t, n_ctx: c_int, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, batch: u64, in_flight: u32, flags: u32, lim: *const madsim_limits_t, out: *mut madsim_campaign_t, col: *mut madsim_collect_t) -> c_int;
     pub fn madsim_hip_geometry(w: *const madsim_workload_t, lim: *const madsim_limits_t, g: *mut madsim_geometry_t) -> c_int;
     pub fn madsim_hip_debug_counters(out16: *mut u64) -> c_int;
     pub fn madsim_workload_pingpong(n_nodes: u32, rounds: u32, nodes: *mut madsim_node_t, progs: *mut madsim_prog_t, socks: *mut madsim_sock_t, insns: *mut madsim_insn_t, cap_insns: u32, w: *mut madsim_workload_t) -> c_int;

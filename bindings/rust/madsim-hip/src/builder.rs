@@ -147,6 +147,15 @@ fn zero_limits() -> sys::madsim_limits_t {
     unsafe { std::mem::zeroed() }
 }
 
+/// What `Builder::search_failures` found: the failing seeds (ascending, at most as many as asked for), the seeds per verdict
+/// value over the whole range, and the campaign report.
+#[derive(Clone, Debug)]
+pub struct Failures {
+    pub failures: Vec<sys::madsim_failure_t>,
+    pub by_verdict: [u64; 8],
+    pub campaign: sys::madsim_campaign_t,
+}
+
 impl Builder {
     /// builder.rs:64-118: `MADSIM_TEST_SEED`, `MADSIM_TEST_NUM`, `MADSIM_TEST_JOBS`, `MADSIM_TEST_TIME_LIMIT`,
     /// `MADSIM_TEST_CHECK_DETERMINISM`, `MADSIM_ALLOW_SYSTEM_THREAD` (`MADSIM_TEST_CONFIG` is read by the caller: the TOML
@@ -223,6 +232,32 @@ impl Builder {
             note_seed(rep.first_failing_seed);
         }
         Ok(rep)
+    }
+
+    /// Triage: WHICH seeds of `self.seed .. self.seed + self.count` fail, and how (`madsim_hip_run_campaign_collect`).  The whole
+    /// range runs at the campaign's rate; the `max_failures` smallest failing seeds come back in ascending order, each with the
+    /// result `madsim_hip_run_batch` gives for it, beside the number of seeds per verdict value (index = `MADSIM_PASS` ..
+    /// `MADSIM_INTERNAL`) and the campaign report.  Never panics: hand `failures[0].seed` to `run_workload` for the reference's
+    /// behaviour.
+    pub fn search_failures(&self, workload: &Workload, max_failures: usize) -> Result<Failures, RunError> {
+        let w = workload.raw();
+        let cfg = self.config.raw();
+        let lim = self.raw_limits(true);
+        let ctx = contexts()?.0[0];
+        let mut failures: Vec<sys::madsim_failure_t> = vec![unsafe { std::mem::zeroed() }; max_failures];
+        let mut campaign: sys::madsim_campaign_t = unsafe { std::mem::zeroed() };
+        let mut col = sys::madsim_collect_t {
+            failures: if max_failures > 0 { failures.as_mut_ptr() as *const _ } else { std::ptr::null() },   // (the library writes through it)
+            cap: max_failures as u64,
+            n_listed: 0,
+            n_by_verdict: [0; 8],
+        };
+        let rc = unsafe { sys::madsim_hip_ctx_run_campaign_collect(ctx, &w, &cfg, self.seed, self.count, 0, 0, 0, &lim, &mut campaign, &mut col) };
+        if rc != 0 {
+            return Err(last_error(rc));
+        }
+        failures.truncate(col.n_listed as usize);
+        Ok(Failures { failures, by_verdict: col.n_by_verdict, campaign })
     }
 
     /// Same contract as `Builder::run` (builder.rs:121-162) for a test body registered as a workload: returns the per-seed

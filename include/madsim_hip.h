@@ -650,6 +650,46 @@ int madsim_hip_run_campaign_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, cons
                                   const madsim_config_t* cfg, uint64_t seed0, uint64_t total, uint64_t batch,
                                   uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim, madsim_campaign_t* out);
 
+/* ---- Collecting campaigns: WHICH seeds fail, and how ------------------------------------------------------------------------
+ * The same campaign, with a report kernel that keeps what the plain one folds away: per batch it counts the seeds per verdict
+ * value and compacts the LISTED seeds — those with a genuine verdict (panic / deadlock / time limit); with
+ * MADSIM_CAMPAIGN_LIST_RUNNER every verdict but MADSIM_PASS, to hand the seeds to madsim_hip_run_batch_auto — into records of
+ * {seed, all 48 result bytes} in ascending seed order, on the device, without an atomic deciding a position: the list is the same
+ * on every run.  `out` is exactly what the plain campaign reports for the same arguments (early stops included);
+ * col->failures[0 .. n_listed) are the `cap` smallest listed seeds of the prefix [seed0, seed0 + seeds_run), ascending, each with the
+ * bytes madsim_hip_run_batch returns for that seed — whatever `batch`, `in_flight` and the number of contexts.  n_by_verdict sums to
+ * seeds_run: [1] + [2] + [3] = out->n_failed, [4] + .. + [7] = out->n_runner.
+ * Per batch 120 bytes of report come back instead of 48; the records of a batch are copied only when it has listed seeds, and only
+ * as many as the list can still take (a full list copies nothing more; the histogram goes on).  cap == 0: histogram only.
+ * MADSIM_CAMPAIGN_STOP_AT_CAP: stop launching once the batches read so far hold `cap` listed seeds ("the first 32 failing seeds");
+ * seeds_run / batches_run / batches_launched follow the rules of MADSIM_CAMPAIGN_STOP_AT_FAILURE, and the two may be combined.
+ * MADSIM_E_ARG: col == NULL, cap > 0 without `failures`, STOP_AT_CAP with cap == 0.  The plain entry points ignore both flags. */
+/* (declared in two statements: the one struct of this header that holds another by value, which the header parser the ABI tests share,
+ * tests/cheader.py, does not lay out by itself — tests/test_collect.py hands it the inner size) */
+struct madsim_failure {
+    uint64_t seed;
+    madsim_result_t result;       /* as madsim_hip_run_batch returns it for `seed` with the same workload, config and limits      */
+};                                /* 56 bytes */
+typedef struct madsim_failure madsim_failure_t;
+typedef struct madsim_collect {
+    madsim_failure_t* failures;   /* caller's host array [cap]; may be NULL when cap == 0 (histogram only)                        */
+    uint64_t cap;
+    uint64_t n_listed;            /* out: records written = min(cap, listed seeds among seeds_run)                                */
+    uint64_t n_by_verdict[8];     /* out: seeds of [seed0, seed0 + seeds_run) per verdict value (index = enum madsim_verdict)     */
+} madsim_collect_t;
+#define MADSIM_CAMPAIGN_LIST_RUNNER 2u   /* list runner verdicts too                                                              */
+#define MADSIM_CAMPAIGN_STOP_AT_CAP 4u   /* stop launching once `cap` listed seeds have been read                                 */
+int madsim_hip_ctx_run_campaign_collect(madsim_hip_ctx_t* ctx, const madsim_workload_t* w, const madsim_config_t* cfg,
+                                        uint64_t seed0, uint64_t total, uint64_t batch, uint32_t in_flight, uint32_t flags,
+                                        const madsim_limits_t* lim, madsim_campaign_t* out, madsim_collect_t* col);
+int madsim_hip_run_campaign_collect(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total,
+                                    uint64_t batch, uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim,
+                                    madsim_campaign_t* out, madsim_collect_t* col);
+int madsim_hip_run_campaign_collect_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_workload_t* w,
+                                          const madsim_config_t* cfg, uint64_t seed0, uint64_t total, uint64_t batch,
+                                          uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim, madsim_campaign_t* out,
+                                          madsim_collect_t* col);
+
 /* Geometry the library picked for a workload (for DESIGN/bench reporting). */
 typedef struct madsim_geometry {
     uint32_t lds_bytes_per_seed;

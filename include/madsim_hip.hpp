@@ -15,6 +15,7 @@
 #define MADSIM_HIP_HPP
 
 #include <algorithm>
+#include <array>
 #include <cctype>
 #include <chrono>
 #include <cstdio>
@@ -500,6 +501,32 @@ struct Builder {
         madsim::check(madsim_hip_run_campaign(&w, &cfg, seed, count, 0, 0, MADSIM_CAMPAIGN_STOP_AT_FAILURE, &lim, &rep));
         if (rep.first_failing_seed != UINT64_MAX) panic_with_info(rep.first_failing_seed);
         return rep;
+    }
+
+    // Triage: WHICH seeds of seed .. seed + count fail, and how (madsim_hip_run_campaign_collect).  The whole range runs at the
+    // campaign's rate; the `max_failures` smallest failing seeds come back in ascending order, each with the result
+    // madsim_hip_run_batch gives for it, beside the number of seeds per verdict value (index = enum madsim_verdict) and the
+    // campaign report.  Does not "panic": a caller that wants the reference's behaviour takes failures.front() to run().
+    struct Failures {
+        std::vector<madsim_failure_t> failures;
+        std::array<uint64_t, 8> by_verdict{};
+        madsim_campaign_t campaign{};
+    };
+    Failures search_failures(const Workload& wl, size_t max_failures) const {
+        madsim::check(madsim_hip_init(device));
+        madsim_workload_t w = wl.raw();
+        madsim_config_t cfg = config.raw();
+        madsim_limits_t lim = capacities;
+        if (time_limit) { lim.time_limit_ns = (uint64_t)(*time_limit * 1e9 + 0.5); if (!lim.time_limit_ns) lim.time_limit_ns = 1; }
+        Failures f;
+        f.failures.resize(max_failures);
+        madsim_collect_t col{};
+        col.failures = max_failures ? f.failures.data() : nullptr;
+        col.cap = max_failures;
+        madsim::check(madsim_hip_run_campaign_collect(&w, &cfg, seed, count, 0, 0, 0, &lim, &f.campaign, &col));
+        f.failures.resize((size_t)col.n_listed);
+        for (int v = 0; v < 8; v++) f.by_verdict[(size_t)v] = col.n_by_verdict[v];
+        return f;
     }
 
     // builder.rs:121-162: run seeds seed..seed+count; return on success, "panic" on the first failing seed.

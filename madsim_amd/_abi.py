@@ -122,6 +122,18 @@ class Campaign(C.Structure):
 
 
 CAMPAIGN_STOP_AT_FAILURE = 1
+CAMPAIGN_LIST_RUNNER = 2      # collecting campaigns: list runner verdicts too
+CAMPAIGN_STOP_AT_CAP = 4      # collecting campaigns: stop launching once `cap` listed seeds have been read
+
+
+class Failure(C.Structure):
+    """madsim_failure_t: one record of a collecting campaign's list — the seed and its 48 result bytes."""
+    _fields_ = [("seed", C.c_uint64), ("result", Result)]
+
+
+class Collect(C.Structure):
+    """madsim_collect_t: the caller's record array going in, the list length and the verdict histogram coming out."""
+    _fields_ = [("failures", C.POINTER(Failure)), ("cap", C.c_uint64), ("n_listed", C.c_uint64), ("n_by_verdict", C.c_uint64 * 8)]
 
 
 class Geometry(C.Structure):
@@ -141,12 +153,16 @@ VARIANT_TIER_FEAT = ((VARIANT_SCOPE, 256), (VARIANT_TICK, 512), (VARIANT_SELECT,
 
 
 HEADER_STRUCTS["madsim_campaign_t"] = Campaign
+HEADER_STRUCTS["madsim_collect_t"] = Collect
 assert C.sizeof(Insn) == 8 and C.sizeof(Prog) == 4 and C.sizeof(Sock) == 4 and C.sizeof(Node) == 4
 assert C.sizeof(Result) == 48 and C.sizeof(Summary) == 48 and C.sizeof(Limits) == 64 and C.sizeof(Config) == 136
 
 # numpy view of a result array: one record per seed, same layout as madsim_result_t
 RESULT_DTYPE = [("verdict", "<u4"), ("steps", "<u4"), ("clock_ns", "<u8"), ("msg_count", "<u8"),
                 ("rng_calls", "<u8"), ("trace_hash", "<u8"), ("obs_hash", "<u8")]
+# numpy view of a collecting campaign's list: madsim_failure_t, the seed in front of the result's fields
+FAILURE_DTYPE = [("seed", "<u8")] + RESULT_DTYPE
+assert C.sizeof(Failure) == 56 and C.sizeof(Collect) == 88
 
 PASS, PANIC, DEADLOCK, TIME_LIMIT, OVERFLOW, STEP_LIMIT, UNSUPPORTED, INTERNAL = range(8)
 VERDICT_NAMES = ["pass", "panic", "deadlock", "time-limit", "resource-overflow", "step-limit", "outside-the-workload-model", "internal-invariant"]

@@ -93,7 +93,10 @@ struct madsim_hip_ctx {
     static constexpr int CAMPAIGN_MAX = 8;
     struct Flight { hipStream_t stream = nullptr; madsim_result_t* d_out = nullptr; size_t cap = 0; unsigned long long* d_acc6 = nullptr;
                     unsigned long long* h_acc6 = nullptr; hipEvent_t e0 = nullptr, e1 = nullptr, done = nullptr;
-                    madsim_result_t* h_out = nullptr; size_t h_cap = 0; };      // h_out: page-locked staging of run_pipelined
+                    madsim_result_t* h_out = nullptr; size_t h_cap = 0;         // h_out: page-locked staging of run_pipelined
+                    // collecting campaigns only: report words (device, page-locked host), per-wave counts, the batch's failure records
+                    unsigned long long* d_rep = nullptr; unsigned long long* h_rep = nullptr; uint32_t* d_wcnt = nullptr;
+                    madsim_failure_t* d_rec = nullptr; size_t rec_cap = 0; };
     Flight flights[CAMPAIGN_MAX];
     unsigned long long* d_acc = nullptr;      // 4 x u64 summary accumulators
     madsim_result_t* d_out = nullptr; size_t out_cap = 0;
@@ -135,7 +138,7 @@ struct madsim_hip_ctx {
                  const madsim_limits_t* lim, madsim_result_t* out, madsim_summary_t* summary);
     int run_list(const madsim_workload_t* w, const madsim_config_t* cfg, const std::vector<uint64_t>& seeds,
                  const madsim_limits_t* lim, std::vector<madsim_result_t>& res, double* kernel_ms);
-    int ensure_flights(uint32_t n, uint64_t batch, bool staging);
+    int ensure_flights(uint32_t n, uint64_t batch, bool staging, bool collect = false, uint64_t records = 0);
     uint32_t flights_for(const madsim_workload_t* w, const madsim_config_t* cfg, const madsim_limits_t* lim, uint64_t batch);
 };
 
@@ -203,6 +206,10 @@ void madsim_hip_ctx::close() {
         if (f.d_acc6) (void)hipFree(f.d_acc6);
         if (f.h_acc6) (void)hipHostFree(f.h_acc6);
         if (f.h_out) (void)hipHostFree(f.h_out);
+        if (f.d_rep) (void)hipFree(f.d_rep);
+        if (f.h_rep) (void)hipHostFree(f.h_rep);
+        if (f.d_wcnt) (void)hipFree(f.d_wcnt);
+        if (f.d_rec) (void)hipFree(f.d_rec);
         if (f.e0) (void)hipEventDestroy(f.e0);
         if (f.e1) (void)hipEventDestroy(f.e1);
         if (f.done) (void)hipEventDestroy(f.done);
@@ -432,8 +439,9 @@ int madsim_hip_ctx::run_list(const madsim_workload_t* w, const madsim_config_t* 
 }
 
 // Streams, report words, events and result buffers of the first n flights (campaigns and run_pipelined share them; the
-// context's mutex serialises the two).  `staging`: also a page-locked host buffer of `batch` results per flight.
-int madsim_hip_ctx::ensure_flights(uint32_t n, uint64_t batch, bool staging) {
+// context's mutex serialises the two).  `staging`: also a page-locked host buffer of `batch` results per flight.  `collect`: also
+// the report words and wave counts of a collecting campaign and room for `records` failure records per flight.
+int madsim_hip_ctx::ensure_flights(uint32_t n, uint64_t batch, bool staging, bool collect, uint64_t records) {
     if (n > (uint32_t)CAMPAIGN_MAX) return fail(MADSIM_E_ARG, "at most 8 batches in flight");
     hint_hw_queues(n);
     for (uint32_t i = 0; i < n; i++) {
@@ -455,6 +463,17 @@ int madsim_hip_ctx::ensure_flights(uint32_t n, uint64_t batch, bool staging) {
             f.h_out = nullptr; f.h_cap = 0;
             HIP_TRY(hipHostMalloc((void**)&f.h_out, batch * sizeof(madsim_result_t), hipHostMallocDefault));
             f.h_cap = batch;
+        }
+        if (collect && !f.d_rep) {
+            HIP_TRY(hipMalloc(&f.d_rep, 16 * sizeof(unsigned long long)));
+            HIP_TRY(hipHostMalloc((void**)&f.h_rep, 16 * sizeof(unsigned long long), hipHostMallocDefault));
+            HIP_TRY(hipMalloc(&f.d_wcnt, MADSIM_K_COLLECT_WAVES * sizeof(uint32_t)));
+        }
+        if (collect && records > f.rec_cap) {
+            if (f.d_rec) { HIP_TRY(hipStreamSynchronize(f.stream)); (void)hipFree(f.d_rec); }
+            f.d_rec = nullptr; f.rec_cap = 0;
+            HIP_TRY(hipMalloc(&f.d_rec, records * sizeof(madsim_failure_t)));
+            f.rec_cap = records;
         }
     }
     return 0;
@@ -882,10 +901,13 @@ int madsim_hip_run_batch_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const m
 // (runtime/builder.rs:129-160: every thread's result is joined in seed order, the first failure is re-raised).
 namespace {
 int run_campaign_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total,
-                      uint64_t batch, uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim, madsim_campaign_t* out) {
+                      uint64_t batch, uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim, madsim_campaign_t* out,
+                      madsim_collect_t* col = nullptr) {
     auto t0 = std::chrono::steady_clock::now();
     memset(out, 0, sizeof *out);
     out->first_failing_seed = UINT64_MAX;
+    if (col) { col->n_listed = 0; memset(col->n_by_verdict, 0, sizeof col->n_by_verdict); }
+    else flags &= ~(MADSIM_CAMPAIGN_LIST_RUNNER | MADSIM_CAMPAIGN_STOP_AT_CAP);      // (flags of the collecting form only)
     int rc = madsim_geo::validate(w, cfg, &g_err);
     if (rc) return rc;
     if (batch == 0) batch = 65536;
@@ -893,6 +915,8 @@ int run_campaign_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workl
     if (seed0 + total < seed0) return fail(MADSIM_E_ARG, "seed0 + total wraps");
     if (total == 0) return 0;
     const uint64_t n_batches = (total + batch - 1) / batch, N = (uint64_t)n_ctx;
+    const uint64_t rec_batch = col ? std::min(col->cap, std::min(batch, total)) : 0;      // records a flight holds: no batch lists more
+    uint64_t listed_seen = 0;                                   // listed seeds of the batches folded so far (not cut at cap)
     std::vector<uint32_t> F(n_ctx);                             // flights per context: what its occupancy rewards, no more than it has batches
     for (int g = 0; g < n_ctx; g++) {
         if ((rc = ctxs[g]->bind())) return rc;
@@ -900,7 +924,7 @@ int run_campaign_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workl
         uint32_t f = in_flight ? in_flight : ctxs[g]->flights_for(w, cfg, lim, batch);
         if ((uint64_t)f > mine) f = (uint32_t)mine;
         F[g] = f;
-        if (f && (rc = ctxs[g]->ensure_flights(f, batch, false))) return rc;
+        if (f && (rc = ctxs[g]->ensure_flights(f, batch, false, col != nullptr, rec_batch))) return rc;
     }
     int first_err = 0;
     std::string first_msg;
@@ -911,16 +935,24 @@ int run_campaign_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workl
         const uint64_t lo = k * batch, n = std::min(batch, total - lo);
         int e;
         if ((e = c->bind())) return e;
-        HIP_TRY(hipMemsetAsync(f.d_acc6, 0xff, 8, f.stream));
-        HIP_TRY(hipMemsetAsync((char*)f.d_acc6 + 8, 0, 24, f.stream));
-        HIP_TRY(hipMemsetAsync((char*)f.d_acc6 + 32, 0xff, 8, f.stream));
-        HIP_TRY(hipMemsetAsync((char*)f.d_acc6 + 40, 0, 8, f.stream));
+        unsigned long long* const d_words = col ? f.d_rep : f.d_acc6;          // the same four memsets, the last one longer when collecting
+        HIP_TRY(hipMemsetAsync(d_words, 0xff, 8, f.stream));
+        HIP_TRY(hipMemsetAsync((char*)d_words + 8, 0, 24, f.stream));
+        HIP_TRY(hipMemsetAsync((char*)d_words + 32, 0xff, 8, f.stream));
+        HIP_TRY(hipMemsetAsync((char*)d_words + 40, 0, col ? (MADSIM_K_COLLECT_WORDS - 5) * 8 : 8, f.stream));
         HIP_TRY(hipEventRecord(f.e0, f.stream));
         if ((e = c->launch(w, cfg, seed0 + lo, n, nullptr, lim, f.d_out, f.stream))) return e;
         HIP_TRY(hipEventRecord(f.e1, f.stream));
-        madsim_k_launch_summary6(f.d_out, n, seed0 + lo, f.d_acc6, f.stream);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(f.h_acc6, f.d_acc6, 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost, f.stream));
+        if (col) {
+            madsim_k_launch_collect(f.d_out, n, seed0 + lo, (flags & MADSIM_CAMPAIGN_LIST_RUNNER) ? 1u : 0u, f.d_rep, f.d_wcnt, f.d_rec,
+                                    std::min(rec_batch, n), f.stream);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(f.h_rep, f.d_rep, MADSIM_K_COLLECT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, f.stream));
+        } else {
+            madsim_k_launch_summary6(f.d_out, n, seed0 + lo, f.d_acc6, f.stream);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(f.h_acc6, f.d_acc6, 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost, f.stream));
+        }
         HIP_TRY(hipEventRecord(f.done, f.stream));
         return 0;
     };
@@ -936,13 +968,27 @@ int run_campaign_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workl
         float ms = 0.f;
         HIP_TRY(hipEventElapsedTime(&ms, f.e0, f.e1));
         if (!stop) {                                            // batches launched beyond the failing one are not part of the answer
+            const unsigned long long* a = col ? f.h_rep : f.h_acc6;
             out->kernel_ms += ms;
             out->batches_run++; out->seeds_run += n;
-            out->n_runner += f.h_acc6[5];
-            out->n_failed += f.h_acc6[1] - f.h_acc6[5];
-            out->total_steps += f.h_acc6[2]; out->total_clock_ns += f.h_acc6[3];
-            if (f.h_acc6[4] < out->first_failing_seed) out->first_failing_seed = f.h_acc6[4];
-            if ((flags & MADSIM_CAMPAIGN_STOP_AT_FAILURE) && f.h_acc6[4] != UINT64_MAX) stop = true;
+            out->n_runner += a[5];
+            out->n_failed += a[1] - a[5];
+            out->total_steps += a[2]; out->total_clock_ns += a[3];
+            if (a[4] < out->first_failing_seed) out->first_failing_seed = a[4];
+            if ((flags & MADSIM_CAMPAIGN_STOP_AT_FAILURE) && a[4] != UINT64_MAX) stop = true;
+            if (col) {
+                for (int v = 0; v < 8; v++) col->n_by_verdict[v] += a[6 + v];
+                // the batch's records, as many as the list still takes: batches are read in seed order, so appending keeps the order.
+                // The stream is idle (its `done` has passed) and takes no launch before this returns.
+                const uint64_t take = std::min<uint64_t>(std::min<uint64_t>(a[14], std::min(rec_batch, n)), col->cap - col->n_listed);
+                if (take) {
+                    HIP_TRY(hipMemcpyAsync(col->failures + col->n_listed, f.d_rec, take * sizeof(madsim_failure_t), hipMemcpyDeviceToHost, f.stream));
+                    HIP_TRY(hipStreamSynchronize(f.stream));
+                    col->n_listed += take;
+                }
+                listed_seen += a[14];
+                if ((flags & MADSIM_CAMPAIGN_STOP_AT_CAP) && listed_seen >= col->cap) stop = true;
+            }
         }
         return 0;
     };
@@ -992,6 +1038,43 @@ int madsim_hip_run_campaign_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, cons
     return run_campaign_impl(ctxs, n_ctx, w, cfg, seed0, total, batch, in_flight, flags, lim, out);
 }
 
+// The collecting forms: the argument errors that need no device are told first, so that a host without a GPU hears about them too.
+namespace {
+int check_collect_args(const madsim_campaign_t* out, const madsim_collect_t* col, uint32_t in_flight, uint32_t flags) {
+    if (!out) return fail(MADSIM_E_ARG, "null campaign report");
+    if (!col) return fail(MADSIM_E_ARG, "null madsim_collect_t (madsim_hip_run_campaign is the form without a failure list)");
+    if (col->cap && !col->failures) return fail(MADSIM_E_ARG, "madsim_collect_t.cap > 0 without a failures array");
+    if ((flags & MADSIM_CAMPAIGN_STOP_AT_CAP) && !col->cap) return fail(MADSIM_E_ARG, "MADSIM_CAMPAIGN_STOP_AT_CAP with cap == 0");
+    if (in_flight > (uint32_t)madsim_hip_ctx::CAMPAIGN_MAX) return fail(MADSIM_E_ARG, "at most 8 batches in flight per context");
+    return 0;
+}
+}  // namespace
+
+int madsim_hip_ctx_run_campaign_collect(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total,
+                                        uint64_t batch, uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim, madsim_campaign_t* out,
+                                        madsim_collect_t* col) {
+    if (int rc = check_collect_args(out, col, in_flight, flags)) return rc;
+    CTX_ENTER(c);
+    madsim_hip_ctx* one[1] = {c};
+    return run_campaign_impl(one, 1, w, cfg, seed0, total, batch, in_flight, flags, lim, out, col);
+}
+
+int madsim_hip_run_campaign_collect_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_workload_t* w, const madsim_config_t* cfg,
+                                          uint64_t seed0, uint64_t total, uint64_t batch, uint32_t in_flight, uint32_t flags,
+                                          const madsim_limits_t* lim, madsim_campaign_t* out, madsim_collect_t* col) {
+    if (int rc = check_collect_args(out, col, in_flight, flags)) return rc;
+    if (!ctxs || n_ctx < 1) return fail(MADSIM_E_ARG, "run_campaign_collect_multi needs at least one context");
+    for (int g = 0; g < n_ctx; g++) {
+        if (!ctxs[g]) return fail(MADSIM_E_NOINIT, "null context");
+        for (int h = 0; h < g; h++) if (ctxs[h] == ctxs[g]) return fail(MADSIM_E_ARG, "the same context appears twice");
+    }
+    std::vector<madsim_hip_ctx*> order(ctxs, ctxs + n_ctx);      // locks in address order (see madsim_hip_run_batch_multi)
+    std::sort(order.begin(), order.end(), [](madsim_hip_ctx* a, madsim_hip_ctx* b) { return std::less<madsim_hip_ctx*>()(a, b); });
+    std::vector<std::unique_lock<std::mutex>> locks;
+    for (madsim_hip_ctx* c : order) locks.emplace_back(c->mu);
+    for (int g = 0; g < n_ctx; g++) if (ctxs[g]->device < 0) return fail(MADSIM_E_NOINIT, "closed context");
+    return run_campaign_impl(ctxs, n_ctx, w, cfg, seed0, total, batch, in_flight, flags, lim, out, col);
+}
 
 // ---- v1 entry points: wrappers on the process-default context ------------------------------------------------------------
 // The default context is reference-counted by its users: a wrapper pins it under g_default_mu for the duration of its call,
@@ -1067,6 +1150,12 @@ int madsim_hip_run_campaign(const madsim_workload_t* w, const madsim_config_t* c
                             uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim, madsim_campaign_t* out) {
     DefaultPin p;
     return madsim_hip_ctx_run_campaign(p.c, w, cfg, seed0, total, batch, in_flight, flags, lim, out);
+}
+
+int madsim_hip_run_campaign_collect(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total, uint64_t batch,
+                                    uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim, madsim_campaign_t* out, madsim_collect_t* col) {
+    DefaultPin p;
+    return madsim_hip_ctx_run_campaign_collect(p.c, w, cfg, seed0, total, batch, in_flight, flags, lim, out, col);
 }
 
 int madsim_hip_geometry(const madsim_workload_t* w, const madsim_limits_t* lim, madsim_geometry_t* out) {

@@ -308,6 +308,12 @@ extern "C" {
 int  madsim_k_launch_sim(const madsim_k::KParams* P, uint32_t grid, uint32_t lds_bytes, void* stream, int trace);
 void madsim_k_launch_summary(const madsim_result_t* out, uint64_t count, uint64_t seed0, unsigned long long* acc, void* stream);
 void madsim_k_launch_summary6(const madsim_result_t* out, uint64_t count, uint64_t seed0, unsigned long long* acc6, void* stream);
+// the collecting campaign's report kernels: summary6's words, by_verdict[8], n listed (MADSIM_K_COLLECT_WORDS words in `rep`) and the `cap`
+// listed seeds of the batch with the smallest seeds, ascending, in `recs`; wave_cnt: MADSIM_K_COLLECT_WAVES words of scratch
+#define MADSIM_K_COLLECT_WORDS 15u
+#define MADSIM_K_COLLECT_WAVES 1024u
+void madsim_k_launch_collect(const madsim_result_t* out, uint64_t count, uint64_t seed0, uint32_t list_runner, unsigned long long* rep,
+                             uint32_t* wave_cnt, madsim_failure_t* recs, uint64_t cap, void* stream);
 int  madsim_k_set_max_lds(uint32_t lds_bytes);
 int  madsim_k_variant_vgprs(const madsim_k::VariantSel* v);
 void madsim_k_launch_keyflip(unsigned long long* acc, void* stream);

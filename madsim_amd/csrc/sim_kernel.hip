@@ -89,6 +89,104 @@ __global__ __launch_bounds__(256) void summary6_kernel(const madsim_result_t* __
     }
 }
 
+// ---- the collecting campaign form: summary6's six words, a histogram of the verdicts and the ORDERED list of the failing seeds ----
+// Two kernels over the same cut of the batch: wave W (= 4 * workgroup + wave of the workgroup, COLLECT_MAX_WAVES at most) owns the
+// contiguous piece [W * piece, (W + 1) * piece) of the result array, so "ascending wave, ascending position in the wave" IS ascending
+// seed order whatever the grid.  collect_count_kernel reads 16 B per seed (as the summary kernels do), folds the report and leaves
+// every wave's number of listed seeds in wave_cnt[W]; collect_write_kernel gives a wave the exclusive prefix of wave_cnt as its offset
+// into the record array, and only a wave that has listed seeds AND an offset below `cap` reads its piece again — failures are rare and
+// the list is short, so the second kernel touches a few pieces (a 65 536-seed batch: 64 seeds, 1 KB, per piece).  No atomic decides a
+// position: the list is the same on every run.
+// rep = {acc6[0..5] as summary6_kernel, by_verdict[0..7], n listed} (15 words; 0xff words 0 and 4, the rest 0 before the launch).
+// Listed = a genuine verdict (panic / deadlock / time limit), or any verdict but PASS when list_runner is set.
+constexpr uint32_t COLLECT_MAX_WAVES = 1024;          // 256 workgroups of 4 waves
+constexpr uint32_t COLLECT_REP_WORDS = 15;
+
+__device__ __forceinline__ uint32_t lanes_below(unsigned long long mask) {       // set bits of `mask` below the calling lane
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+__device__ __forceinline__ bool collect_listed(uint32_t verdict, uint32_t list_runner) {
+    return verdict != MADSIM_PASS && (list_runner || !MADSIM_IS_RUNNER_VERDICT(verdict));
+}
+
+__global__ __launch_bounds__(256) void collect_count_kernel(const madsim_result_t* __restrict__ out, uint64_t count, uint64_t seed0,
+                                                            uint64_t piece, uint32_t list_runner,
+                                                            unsigned long long* __restrict__ rep, uint32_t* __restrict__ wave_cnt) {
+    const uint32_t W = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const uint64_t lo = (uint64_t)W * piece, hi = lo + piece < count ? lo + piece : count;
+    unsigned long long first = ~0ull, nfail = 0, steps = 0, clk = 0, gfirst = ~0ull, nrun = 0;
+    uint32_t hist[8] = {0, 0, 0, 0, 0, 0, 0, 0}, listed = 0;                       // wave-uniform (popcounts of ballots); hist[0] stays 0
+    for (uint64_t base = lo; base < hi; base += 64) {
+        const uint64_t i = base + lane;
+        uint32_t v = MADSIM_PASS;
+        if (i < hi) {
+            const uint4 r = reinterpret_cast<const uint4*>(out + i)[0];
+            v = r.x;
+            if (v != MADSIM_PASS) {
+                const unsigned long long s = seed0 + i;
+                nfail++; first = s < first ? s : first;
+                if (MADSIM_IS_RUNNER_VERDICT(v)) nrun++; else gfirst = s < gfirst ? s : gfirst;
+            }
+            steps += r.y; clk += ((unsigned long long)r.w << 32) | r.z;
+        }
+        if (__ballot(v != MADSIM_PASS)) {                                          // (wave-uniform: rare-failure batches never get here)
+#pragma unroll
+            for (uint32_t k = 1; k < 7; k++) hist[k] += (uint32_t)__popcll(__ballot(v == k));
+            hist[7] += (uint32_t)__popcll(__ballot(v >= 7));
+            listed += (uint32_t)__popcll(__ballot(collect_listed(v, list_runner)));
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        unsigned long long f2 = __shfl_xor(first, o), g2 = __shfl_xor(gfirst, o);
+        first = f2 < first ? f2 : first; gfirst = g2 < gfirst ? g2 : gfirst;
+        nfail += __shfl_xor(nfail, o); steps += __shfl_xor(steps, o); clk += __shfl_xor(clk, o); nrun += __shfl_xor(nrun, o);
+    }
+    if (lane == 0) {                                                               // one set of atomics per wave, summary6's six when nothing fails
+        wave_cnt[W] = listed;
+        atomicMin(&rep[0], first); atomicAdd(&rep[1], nfail); atomicAdd(&rep[2], steps); atomicAdd(&rep[3], clk);
+        atomicMin(&rep[4], gfirst); atomicAdd(&rep[5], nrun);
+        if (nfail) {
+#pragma unroll
+            for (uint32_t k = 1; k < 8; k++) if (hist[k]) atomicAdd(&rep[6 + k], (unsigned long long)hist[k]);
+            if (listed) atomicAdd(&rep[14], (unsigned long long)listed);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void collect_write_kernel(const madsim_result_t* __restrict__ out, uint64_t count, uint64_t seed0,
+                                                            uint64_t piece, uint32_t list_runner, unsigned long long* __restrict__ rep,
+                                                            const uint32_t* __restrict__ wave_cnt, madsim_failure_t* __restrict__ recs,
+                                                            uint64_t cap) {
+    const uint32_t W = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (W == 0 && lane == 0) {                                                     // the PASS count is what the other seven leave
+        unsigned long long other = 0;
+        for (uint32_t k = 1; k < 8; k++) other += rep[6 + k];
+        rep[6] = count - other;
+    }
+    if (cap == 0 || wave_cnt[W] == 0) return;                                      // (wave-uniform)
+    uint64_t at = 0;                                                               // listed seeds of the waves before this one
+    for (uint32_t j = lane; j < W; j += 64) at += wave_cnt[j];
+    for (int o = 32; o > 0; o >>= 1) at += __shfl_xor(at, o);
+    const uint64_t lo = (uint64_t)W * piece, hi = lo + piece < count ? lo + piece : count;
+    for (uint64_t base = lo; base < hi && at < cap; base += 64) {
+        const uint64_t i = base + lane;
+        uint4 r = {MADSIM_PASS, 0, 0, 0};
+        if (i < hi) r = reinterpret_cast<const uint4*>(out + i)[0];
+        const bool mine = collect_listed(r.x, list_runner);
+        const unsigned long long m = __ballot(mine);
+        const uint64_t rank = at + lanes_below(m);
+        if (mine && rank < cap) {                                                  // the other 32 bytes only of a seed that is listed
+            const uint4 r1 = reinterpret_cast<const uint4*>(out + i)[1], r2 = reinterpret_cast<const uint4*>(out + i)[2];
+            unsigned long long* p = reinterpret_cast<unsigned long long*>(recs + rank);          // 56 B records: 8-byte stores
+            p[0] = seed0 + i;
+            p[1] = ((unsigned long long)r.y << 32) | r.x;   p[2] = ((unsigned long long)r.w << 32) | r.z;
+            p[3] = ((unsigned long long)r1.y << 32) | r1.x; p[4] = ((unsigned long long)r1.w << 32) | r1.z;
+            p[5] = ((unsigned long long)r2.y << 32) | r2.x; p[6] = ((unsigned long long)r2.w << 32) | r2.z;
+        }
+        at += (uint64_t)__popcll(m);
+    }
+}
+
 __global__ void keyflip_kernel(unsigned long long* acc) { acc[0] ^= 0x8000000000000000ull; }
 
 // one kernel per row of variant_table (sim_kernel.h), same macro, same order
@@ -120,6 +218,21 @@ extern "C" void madsim_k_launch_summary6(const madsim_result_t* out, uint64_t co
     if (grid > 256) grid = 256;
     if (grid == 0) grid = 1;
     hipLaunchKernelGGL(madsim_k::summary6_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, out, count, seed0, acc6);
+}
+
+// rep: COLLECT_REP_WORDS words, wave_cnt: MADSIM_K_COLLECT_WAVES words, recs: `cap` records (may be null when cap == 0); all prepared by the
+// caller on `stream` (rep words 0 and 4 all-ones, the rest zero)
+extern "C" void madsim_k_launch_collect(const madsim_result_t* out, uint64_t count, uint64_t seed0, uint32_t list_runner,
+                                        unsigned long long* rep, uint32_t* wave_cnt, madsim_failure_t* recs, uint64_t cap, void* stream) {
+    static_assert(madsim_k::COLLECT_MAX_WAVES == MADSIM_K_COLLECT_WAVES && madsim_k::COLLECT_REP_WORDS == MADSIM_K_COLLECT_WORDS, "sim_kernel.h");
+    static_assert(sizeof(madsim_failure_t) == 56 && sizeof(madsim_result_t) == 48, "record layout");
+    uint32_t grid = (uint32_t)((count + 1023) / 1024);     // summary6's grid; every wave a contiguous piece, a multiple of 64 results
+    if (grid > 256) grid = 256;
+    if (grid == 0) grid = 1;
+    const uint64_t waves = 4ull * grid, piece = ((count + waves - 1) / waves + 63) / 64 * 64;
+    hipLaunchKernelGGL(madsim_k::collect_count_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, out, count, seed0, piece, list_runner, rep, wave_cnt);
+    hipLaunchKernelGGL(madsim_k::collect_write_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, out, count, seed0, piece, list_runner, rep,
+                       (const uint32_t*)wave_cnt, recs, cap);
 }
 
 extern "C" void madsim_k_launch_keyflip(unsigned long long* acc, void* stream) {

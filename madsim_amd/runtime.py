@@ -112,6 +112,9 @@ def lib():
                                               C.c_uint32, C.c_uint32, C.POINTER(A.Limits), C.POINTER(A.Campaign)]
         L.madsim_hip_ctx_run_campaign.argtypes = [ctxp] + L.madsim_hip_run_campaign.argtypes
         L.madsim_hip_run_campaign_multi.argtypes = [C.POINTER(ctxp), C.c_int] + L.madsim_hip_run_campaign.argtypes
+        L.madsim_hip_run_campaign_collect.argtypes = L.madsim_hip_run_campaign.argtypes + [C.POINTER(A.Collect)]
+        L.madsim_hip_ctx_run_campaign_collect.argtypes = [ctxp] + L.madsim_hip_run_campaign_collect.argtypes
+        L.madsim_hip_run_campaign_collect_multi.argtypes = [C.POINTER(ctxp), C.c_int] + L.madsim_hip_run_campaign_collect.argtypes
         if L.madsim_hip_version() != A.ABI_VERSION:
             raise MadsimHipError("libmadsim_hip.so ABI version mismatch")
         # build identity: MADSIM_HIP_LIB may name an A/B build of THIS library (tools/build_variant.sh), nothing else — an
@@ -195,18 +198,45 @@ def run_batch_auto(workload, seed0, count, config=None, limits=None, max_rounds=
     return out, summ
 
 
-def run_campaign(workload, seed0, total, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None):
+def _campaign_flags(stop_at_failure, list_runner=False, stop_at_cap=False):
+    return (A.CAMPAIGN_STOP_AT_FAILURE if stop_at_failure else 0) | (A.CAMPAIGN_LIST_RUNNER if list_runner else 0) \
+        | (A.CAMPAIGN_STOP_AT_CAP if stop_at_cap else 0)
+
+
+def _collecting(call, collect):
+    """Run `call(col)` — one of the madsim_hip_*run_campaign_collect* entry points with everything but the madsim_collect_t bound — with
+    room for `collect` records; returns (failures ndarray[FAILURE_DTYPE] of n_listed entries, by_verdict uint64[8])."""
+    rec = np.zeros(collect, dtype=A.FAILURE_DTYPE)
+    col = A.Collect()
+    col.failures = rec.ctypes.data_as(C.POINTER(A.Failure)) if collect else None
+    col.cap = collect
+    _check(call(C.byref(col)))
+    return rec[:col.n_listed].copy(), np.array(list(col.n_by_verdict), dtype=np.uint64)
+
+
+def run_campaign(workload, seed0, total, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None,
+                 collect=None, list_runner=False, stop_at_cap=False):
     """madsim_hip_run_campaign: `total` seeds as batches kept in flight on the library's own streams; returns the Campaign
     report (first failing seed, counts) — no per-seed results.  stop_at_failure: stop launching once a completed batch holds a
-    seed with a genuine verdict."""
+    seed with a genuine verdict.
+
+    collect=K (madsim_hip_run_campaign_collect): returns (campaign, failures, by_verdict) — the K smallest failing seeds of the
+    prefix that ran, ascending, as records of FAILURE_DTYPE (the seed and the result run_batch gives for it), and the number of
+    seeds per verdict value.  K = 0: the histogram alone.  list_runner: runner verdicts are listed too; stop_at_cap: stop
+    launching once K listed seeds have been read."""
     if _inited_device is None:
         init(0)
     cfg = config or A.Config.default()
     lim = limits or A.Limits()
     rep = A.Campaign()
-    _check(lib().madsim_hip_run_campaign(workload.ref(), C.byref(cfg), seed0, total, batch, in_flight,
-                                         A.CAMPAIGN_STOP_AT_FAILURE if stop_at_failure else 0, C.byref(lim), C.byref(rep)))
-    return rep
+    if collect is None:
+        _check(lib().madsim_hip_run_campaign(workload.ref(), C.byref(cfg), seed0, total, batch, in_flight,
+                                             _campaign_flags(stop_at_failure), C.byref(lim), C.byref(rep)))
+        return rep
+    flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap)
+    failures, by_verdict = _collecting(lambda col: lib().madsim_hip_run_campaign_collect(
+        workload.ref(), C.byref(cfg), seed0, total, batch, in_flight, flags, C.byref(lim), C.byref(rep), col), collect)
+    return rep, failures, by_verdict
 
 
 def run_batch_device(workload, seed0, count, d_out_ptr, stream_ptr=0, config=None, limits=None, want_summary=True):
@@ -266,6 +296,20 @@ class Context:
                                                   out.ctypes.data_as(C.c_void_p), C.byref(summ)))
         return out, summ
 
+    def run_campaign(self, workload, seed0, total, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None,
+                     collect=None, list_runner=False, stop_at_cap=False):
+        """runtime.run_campaign on this context (madsim_hip_ctx_run_campaign / madsim_hip_ctx_run_campaign_collect)."""
+        cfg, lim = config or A.Config.default(), limits or A.Limits()
+        rep = A.Campaign()
+        if collect is None:
+            _check(lib().madsim_hip_ctx_run_campaign(self._h, workload.ref(), C.byref(cfg), seed0, total, batch, in_flight,
+                                                     _campaign_flags(stop_at_failure), C.byref(lim), C.byref(rep)))
+            return rep
+        flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap)
+        failures, by_verdict = _collecting(lambda col: lib().madsim_hip_ctx_run_campaign_collect(
+            self._h, workload.ref(), C.byref(cfg), seed0, total, batch, in_flight, flags, C.byref(lim), C.byref(rep), col), collect)
+        return rep, failures, by_verdict
+
 
 def run_batch_multi(contexts, workload, seed0, count, config=None, limits=None, max_rounds=5):
     """madsim_hip_run_batch_multi: one process, one host thread, the seed range sharded contiguously over `contexts`
@@ -279,16 +323,24 @@ def run_batch_multi(contexts, workload, seed0, count, config=None, limits=None, 
     return out, summ
 
 
-def run_campaign_multi(contexts, workload, seed0, total, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None):
+def run_campaign_multi(contexts, workload, seed0, total, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None,
+                       collect=None, list_runner=False, stop_at_cap=False):
     """madsim_hip_run_campaign_multi: the seed search over several contexts (one per GPU) from one host thread — batch k on context
-    k % n, reports read in batch order, every device stopped within one round of batches of the first genuine failure."""
+    k % n, reports read in batch order, every device stopped within one round of batches of the first genuine failure.
+    collect / list_runner / stop_at_cap: as run_campaign (madsim_hip_run_campaign_collect_multi); the list is the one a single
+    context gives."""
     cfg = config or A.Config.default()
     lim = limits or A.Limits()
     rep = A.Campaign()
     arr = (C.c_void_p * len(contexts))(*[c._h for c in contexts])
-    _check(lib().madsim_hip_run_campaign_multi(arr, len(contexts), workload.ref(), C.byref(cfg), seed0, total, batch, in_flight,
-                                               A.CAMPAIGN_STOP_AT_FAILURE if stop_at_failure else 0, C.byref(lim), C.byref(rep)))
-    return rep
+    if collect is None:
+        _check(lib().madsim_hip_run_campaign_multi(arr, len(contexts), workload.ref(), C.byref(cfg), seed0, total, batch, in_flight,
+                                                   _campaign_flags(stop_at_failure), C.byref(lim), C.byref(rep)))
+        return rep
+    flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap)
+    failures, by_verdict = _collecting(lambda col: lib().madsim_hip_run_campaign_collect_multi(
+        arr, len(contexts), workload.ref(), C.byref(cfg), seed0, total, batch, in_flight, flags, C.byref(lim), C.byref(rep), col), collect)
+    return rep, failures, by_verdict
 
 
 def run_campaign_over_ranks(workload, seed0, total, batch=65536, stop_at_failure=True, config=None, limits=None, device_tensors=None, group=None,

@@ -48,7 +48,9 @@ def main():
     w("pub struct madsim_hip_ctx_t {")
     w("    _private: [u8; 0],")
     w("}")
-    for name, fields in H.structs(text).items():
+    # (a struct declared as `struct s { .. }; typedef struct s s_t;` — one that holds another by value — gets its twin like the rest)
+    two = re.sub(r"\bstruct\s+(\w+)\s*\{([^{}]*)\}\s*;\s*typedef\s+struct\s+\1\s+(\w+)\s*;", r"typedef struct \1 {\2} \3;", text)
+    for name, fields in H.structs(two).items():
         w("")
         w("#[repr(C)]")
         w("#[derive(Clone, Copy, Debug)]")
