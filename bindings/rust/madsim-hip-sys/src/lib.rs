@@ -162,6 +162,34 @@ pub struct madsim_collect_t {
 
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
+pub struct madsim_extreme_t {
+    pub value: u64,
+    pub seed: u64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct madsim_metric_t {
+    pub min: u64,
+    pub max: u64,
+    pub sum_lo: u64,
+    pub sum_hi: u64,
+    pub hist: [u64; 256],
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct madsim_stats_t {
+    pub include: u32,
+    pub top_k: u32,
+    pub top: *const madsim_extreme_t,
+    pub n: u64,
+    pub n_top: u64,
+    pub metric: [madsim_metric_t; 4],
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
 pub struct madsim_geometry_t {
     pub lds_bytes_per_seed: u32,
     pub lds_bytes_per_block: u32,
@@ -300,6 +328,13 @@ pub const MADSIM_E_LIMITS: c_int = -5;
 pub const MADSIM_CAMPAIGN_STOP_AT_FAILURE: u32 = 1;
 pub const MADSIM_CAMPAIGN_LIST_RUNNER: u32 = 2;
 pub const MADSIM_CAMPAIGN_STOP_AT_CAP: u32 = 4;
+pub const MADSIM_STAT_CLOCK: u32 = 0;
+pub const MADSIM_STAT_STEPS: u32 = 1;
+pub const MADSIM_STAT_MSGS: u32 = 2;
+pub const MADSIM_STAT_RNG: u32 = 3;
+pub const MADSIM_STAT_METRICS: u32 = 4;
+pub const MADSIM_STAT_BUCKETS: u32 = 256;
+pub const MADSIM_STAT_MAX_TOP: u32 = 16;
 
 #[link(name = "madsim_hip")]
 extern "C" {
@@ -333,6 +368,11 @@ extern "C" {
     pub fn madsim_hip_ctx_run_campaign_collect(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, batch: u64, in_flight: u32, flags: u32, lim: *const madsim_limits_t, out: *mut madsim_campaign_t, col: *mut madsim_collect_t) -> c_int;
     pub fn madsim_hip_run_campaign_collect(w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, batch: u64, in_flight: u32, flags: u32, lim: *const madsim_limits_t, out: *mut madsim_campaign_t, col: *mut madsim_collect_t) -> c_int;
     pub fn madsim_hip_run_campaign_collect_multi(ctxs: *const *mut madsim_hip_ctx_t, n_ctx: c_int, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, batch: u64, in_flight: u32, flags: u32, lim: *const madsim_limits_t, out: *mut madsim_campaign_t, col: *mut madsim_collect_t) -> c_int;
+    pub fn madsim_hip_stat_bucket(v: u64) -> u32;
+    pub fn madsim_hip_stat_bucket_floor(b: u32) -> u64;
+    pub fn madsim_hip_ctx_run_campaign_stats(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, batch: u64, in_flight: u32, flags: u32, lim: *const madsim_limits_t, out: *mut madsim_campaign_t, col: *mut madsim_collect_t, st: *mut madsim_stats_t) -> c_int;
+    pub fn madsim_hip_run_campaign_stats(w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, batch: u64, in_flight: u32, flags: u32, lim: *const madsim_limits_t, out: *mut madsim_campaign_t, col: *mut madsim_collect_t, st: *mut madsim_stats_t) -> c_int;
+    pub fn madsim_hip_run_campaign_stats_multi(ctxs: *const *mut madsim_hip_ctx_t, n_ctx: c_int, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, batch: u64, in_flight: u32, flags: u32, lim: *const madsim_limits_t, out: *mut madsim_campaign_t, col: *mut madsim_collect_t, st: *mut madsim_stats_t) -> c_int;
     pub fn madsim_hip_geometry(w: *const madsim_workload_t, lim: *const madsim_limits_t, g: *mut madsim_geometry_t) -> c_int;
     pub fn madsim_hip_debug_counters(out16: *mut u64) -> c_int;
     pub fn madsim_workload_pingpong(n_nodes: u32, rounds: u32, nodes: *mut madsim_node_t, progs: *mut madsim_prog_t, socks: *mut madsim_sock_t, insns: *mut madsim_insn_t, cap_insns: u32, w: *mut madsim_workload_t) -> c_int;

@@ -156,6 +156,15 @@ pub struct Failures {
     pub campaign: sys::madsim_campaign_t,
 }
 
+/// What `Builder::campaign_stats` found over the counted seeds: `stats.n`, per metric (`MADSIM_STAT_CLOCK` ..) min, max, the
+/// 128-bit sum and the bucket counts, and `top[m]`: the extreme seeds of metric `m`, value descending, then seed ascending.
+#[derive(Clone, Debug)]
+pub struct Stats {
+    pub stats: sys::madsim_stats_t,
+    pub top: [Vec<sys::madsim_extreme_t>; 4],
+    pub campaign: sys::madsim_campaign_t,
+}
+
 impl Builder {
     /// builder.rs:64-118: `MADSIM_TEST_SEED`, `MADSIM_TEST_NUM`, `MADSIM_TEST_JOBS`, `MADSIM_TEST_TIME_LIMIT`,
     /// `MADSIM_TEST_CHECK_DETERMINISM`, `MADSIM_ALLOW_SYSTEM_THREAD` (`MADSIM_TEST_CONFIG` is read by the caller: the TOML
@@ -258,6 +267,33 @@ impl Builder {
         }
         failures.truncate(col.n_listed as usize);
         Ok(Failures { failures, by_verdict: col.n_by_verdict, campaign })
+    }
+
+    /// Statistics: HOW the runs of `self.seed .. self.seed + self.count` are distributed, and which seeds are the outliers
+    /// (`madsim_hip_run_campaign_stats`).  `include`: bit `v` set = count the seeds whose verdict is `v` (bits 0-3: `MADSIM_PASS` ..
+    /// `MADSIM_TIME_LIMIT`); `top_k` <= `MADSIM_STAT_MAX_TOP` extreme seeds per metric.
+    pub fn campaign_stats(&self, workload: &Workload, include: u32, top_k: u32) -> Result<Stats, RunError> {
+        let w = workload.raw();
+        let cfg = self.config.raw();
+        let lim = self.raw_limits(true);
+        let ctx = contexts()?.0[0];
+        let k = top_k as usize;
+        let mut top: Vec<sys::madsim_extreme_t> = vec![unsafe { std::mem::zeroed() }; 4 * k];
+        let mut campaign: sys::madsim_campaign_t = unsafe { std::mem::zeroed() };
+        let mut stats: sys::madsim_stats_t = unsafe { std::mem::zeroed() };
+        stats.include = include;
+        stats.top_k = top_k;
+        stats.top = if k > 0 { top.as_mut_ptr() as *const _ } else { std::ptr::null() };   // (the library writes through it)
+        let rc = unsafe {
+            sys::madsim_hip_ctx_run_campaign_stats(ctx, &w, &cfg, self.seed, self.count, 0, 0, 0, &lim, &mut campaign, std::ptr::null_mut(), &mut stats)
+        };
+        if rc != 0 {
+            return Err(last_error(rc));
+        }
+        stats.top = std::ptr::null();
+        let n_top = stats.n_top as usize;
+        let rows: [Vec<sys::madsim_extreme_t>; 4] = std::array::from_fn(|m| top[m * k..m * k + n_top].to_vec());
+        Ok(Stats { stats, top: rows, campaign })
     }
 
     /// Same contract as `Builder::run` (builder.rs:121-162) for a test body registered as a workload: returns the per-seed

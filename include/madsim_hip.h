@@ -690,6 +690,63 @@ int madsim_hip_run_campaign_collect_multi(madsim_hip_ctx_t* const* ctxs, int n_c
                                           uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim, madsim_campaign_t* out,
                                           madsim_collect_t* col);
 
+/* ---- Campaign statistics: HOW the runs are distributed, and which seeds are the outliers -----------------------------------
+ * The same campaign, with report kernels that reduce the four per-seed numbers of madsim_result_t — clock_ns, steps, msg_count,
+ * rng_calls — over the COUNTED seeds of every batch: count, minimum, maximum, the exact 128-bit sum, a histogram of 252 logarithmic
+ * buckets (four per octave: a bucket is at most 25 % wide) and the `top_k` extreme seeds per metric.  All integer, all exact.
+ * A seed is counted when bit `verdict` is set in `include`; only bits 0-3 (PASS, PANIC, DEADLOCK, TIME_LIMIT) exist — a seed with a
+ * runner verdict carries no usable numbers and is never counted.
+ * bucket(v) = v for v < 4; otherwise, with e the index of v's top set bit, 4 * (e - 1) + ((v >> (e - 2)) & 3): values 0 .. 2^64 - 1
+ * map to buckets 0 .. 251.  madsim_hip_stat_bucket / madsim_hip_stat_bucket_floor are host helpers (no device needed):
+ * floor(b) = b for b < 4, else (4 + b % 4) << (b / 4 - 1), the smallest value of bucket b; b >= 252 gives UINT64_MAX.
+ * top[m * top_k + r], r < n_top: the counted seeds that come first when ordered by metric m descending, then seed ascending (among
+ * tied values the smaller seeds win).  No atomic and no arrival order decides a position.
+ * Everything is a function of the per-seed results of the prefix [seed0, seed0 + seeds_run): the same bytes whatever `batch`,
+ * `in_flight` and the number of contexts, on every run; batches launched beyond a stopping one contribute nothing.  The per-batch
+ * statistics (about 5 KB) ride back with the batch's report and are folded on the host in batch order.
+ * `out` is exactly the plain campaign's report.  `col` may be NULL (no failure list, no verdict histogram); otherwise it is filled
+ * exactly as madsim_hip_run_campaign_collect fills it, and the flags of that form apply.  A batch must hold fewer than 2^32 seeds.
+ * MADSIM_E_ARG: st == NULL, include == 0 or a bit at or above 4, top_k > MADSIM_STAT_MAX_TOP, top_k > 0 without `top`, and the
+ * collecting form's own argument errors when `col` is given. */
+#define MADSIM_STAT_CLOCK 0u      /* madsim_result_t.clock_ns  */
+#define MADSIM_STAT_STEPS 1u      /* madsim_result_t.steps     */
+#define MADSIM_STAT_MSGS  2u      /* madsim_result_t.msg_count */
+#define MADSIM_STAT_RNG   3u      /* madsim_result_t.rng_calls */
+#define MADSIM_STAT_METRICS 4u
+#define MADSIM_STAT_BUCKETS 256u  /* 252 used */
+#define MADSIM_STAT_MAX_TOP 16u
+typedef struct madsim_extreme {
+    uint64_t value, seed;
+} madsim_extreme_t;               /* 16 bytes */
+typedef struct madsim_metric {
+    uint64_t min, max;            /* over the counted seeds; UINT64_MAX and 0 when there is none                                  */
+    uint64_t sum_lo, sum_hi;      /* the 128-bit sum                                                                              */
+    uint64_t hist[256];           /* [MADSIM_STAT_BUCKETS]: counted seeds per bucket                                              */
+} madsim_metric_t;                /* 2080 bytes */
+/* (two statements, as madsim_failure above: it holds madsim_metric_t by value) */
+struct madsim_stats {
+    uint32_t include;             /* in: bit v set = count the seeds whose verdict is v (bits 0-3 only)                           */
+    uint32_t top_k;               /* in: 0 .. MADSIM_STAT_MAX_TOP                                                                 */
+    madsim_extreme_t* top;        /* in: caller's host array [MADSIM_STAT_METRICS][top_k]; may be NULL when top_k == 0            */
+    uint64_t n;                   /* out: counted seeds of [seed0, seed0 + seeds_run)                                             */
+    uint64_t n_top;               /* out: min(top_k, n): entries valid per metric row                                             */
+    madsim_metric_t metric[4];    /* [MADSIM_STAT_METRICS]                                                                        */
+};
+typedef struct madsim_stats madsim_stats_t;
+uint32_t madsim_hip_stat_bucket(uint64_t v);
+uint64_t madsim_hip_stat_bucket_floor(uint32_t b);
+int madsim_hip_ctx_run_campaign_stats(madsim_hip_ctx_t* ctx, const madsim_workload_t* w, const madsim_config_t* cfg,
+                                      uint64_t seed0, uint64_t total, uint64_t batch, uint32_t in_flight, uint32_t flags,
+                                      const madsim_limits_t* lim, madsim_campaign_t* out, madsim_collect_t* col,
+                                      madsim_stats_t* st);
+int madsim_hip_run_campaign_stats(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total,
+                                  uint64_t batch, uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim,
+                                  madsim_campaign_t* out, madsim_collect_t* col, madsim_stats_t* st);
+int madsim_hip_run_campaign_stats_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_workload_t* w,
+                                        const madsim_config_t* cfg, uint64_t seed0, uint64_t total, uint64_t batch,
+                                        uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim, madsim_campaign_t* out,
+                                        madsim_collect_t* col, madsim_stats_t* st);
+
 /* Geometry the library picked for a workload (for DESIGN/bench reporting). */
 typedef struct madsim_geometry {
     uint32_t lds_bytes_per_seed;

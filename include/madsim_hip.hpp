@@ -529,6 +529,31 @@ struct Builder {
         return f;
     }
 
+    // Statistics: HOW the runs of seed .. seed + count are distributed, and which seeds are the outliers (madsim_hip_run_campaign_stats).
+    // The whole range runs at the campaign's rate; over the seeds whose verdict bit is set in `include` (bit v = verdict v, bits 0-3) come
+    // back the count, and per metric (index MADSIM_STAT_CLOCK / _STEPS / _MSGS / _RNG) min, max, the 128-bit sum, the bucket counts and the
+    // `top_k` (<= MADSIM_STAT_MAX_TOP) seeds that come first by value descending, then seed ascending.
+    struct Stats {
+        madsim_stats_t stats{};                                           // (stats.top points into `top` while this object is not moved from)
+        std::vector<madsim_extreme_t> top;                                // [MADSIM_STAT_METRICS][top_k], stats.n_top valid per row
+        madsim_campaign_t campaign{};
+        const madsim_extreme_t* top_of(uint32_t metric) const { return top.data() + (size_t)metric * stats.top_k; }
+    };
+    Stats campaign_stats(const Workload& wl, uint32_t include = 1u << MADSIM_PASS, uint32_t top_k = 0) const {
+        madsim::check(madsim_hip_init(device));
+        madsim_workload_t w = wl.raw();
+        madsim_config_t cfg = config.raw();
+        madsim_limits_t lim = capacities;
+        if (time_limit) { lim.time_limit_ns = (uint64_t)(*time_limit * 1e9 + 0.5); if (!lim.time_limit_ns) lim.time_limit_ns = 1; }
+        Stats s;
+        s.top.resize((size_t)MADSIM_STAT_METRICS * top_k);
+        s.stats.include = include;
+        s.stats.top_k = top_k;
+        s.stats.top = top_k ? s.top.data() : nullptr;
+        madsim::check(madsim_hip_run_campaign_stats(&w, &cfg, seed, count, 0, 0, 0, &lim, &s.campaign, nullptr, &s.stats));
+        return s;
+    }
+
     // builder.rs:121-162: run seeds seed..seed+count; return on success, "panic" on the first failing seed.
     // Reports the numerically smallest failing seed (the reference reports the first to complete).
     std::vector<madsim_result_t> run(const Workload& wl) const {

@@ -136,6 +136,42 @@ class Collect(C.Structure):
     _fields_ = [("failures", C.POINTER(Failure)), ("cap", C.c_uint64), ("n_listed", C.c_uint64), ("n_by_verdict", C.c_uint64 * 8)]
 
 
+STAT_CLOCK, STAT_STEPS, STAT_MSGS, STAT_RNG = range(4)      # the metrics of a statistics campaign, in madsim_stats_t.metric order
+STAT_METRICS, STAT_BUCKETS, STAT_MAX_TOP = 4, 256, 16
+STAT_NAMES = ("clock_ns", "steps", "msg_count", "rng_calls")
+
+
+class Extreme(C.Structure):
+    """madsim_extreme_t: one of a metric's extreme seeds."""
+    _fields_ = [("value", C.c_uint64), ("seed", C.c_uint64)]
+
+
+class Metric(C.Structure):
+    """madsim_metric_t: one metric over the counted seeds — min, max, the 128-bit sum, the bucket counts."""
+    _fields_ = [("min", C.c_uint64), ("max", C.c_uint64), ("sum_lo", C.c_uint64), ("sum_hi", C.c_uint64), ("hist", C.c_uint64 * STAT_BUCKETS)]
+
+
+class Stats(C.Structure):
+    """madsim_stats_t: which verdicts to count and the caller's top array going in, the statistics coming out."""
+    _fields_ = [("include", C.c_uint32), ("top_k", C.c_uint32), ("top", C.POINTER(Extreme)), ("n", C.c_uint64), ("n_top", C.c_uint64),
+                ("metric", Metric * STAT_METRICS)]
+
+
+def stat_bucket(v):
+    """madsim_hip_stat_bucket: v itself below 4, else four buckets per octave — the top set bit and the two bits after it."""
+    if v < 4:
+        return v
+    e = v.bit_length() - 1
+    return 4 * (e - 1) + ((v >> (e - 2)) & 3)
+
+
+def stat_bucket_floor(b):
+    """madsim_hip_stat_bucket_floor: the smallest value of bucket b (2^64 - 1 from 252 on: no such bucket)."""
+    if b < 4:
+        return b
+    return U64_MAX if b >= 252 else (4 + b % 4) << (b // 4 - 1)
+
+
 class Geometry(C.Structure):
     _fields_ = [
         ("lds_bytes_per_seed", C.c_uint32), ("lds_bytes_per_block", C.c_uint32), ("block_threads", C.c_uint32),
@@ -154,6 +190,8 @@ VARIANT_TIER_FEAT = ((VARIANT_SCOPE, 256), (VARIANT_TICK, 512), (VARIANT_SELECT,
 
 HEADER_STRUCTS["madsim_campaign_t"] = Campaign
 HEADER_STRUCTS["madsim_collect_t"] = Collect
+HEADER_STRUCTS["madsim_extreme_t"] = Extreme
+HEADER_STRUCTS["madsim_metric_t"] = Metric
 assert C.sizeof(Insn) == 8 and C.sizeof(Prog) == 4 and C.sizeof(Sock) == 4 and C.sizeof(Node) == 4
 assert C.sizeof(Result) == 48 and C.sizeof(Summary) == 48 and C.sizeof(Limits) == 64 and C.sizeof(Config) == 136
 
@@ -163,6 +201,9 @@ RESULT_DTYPE = [("verdict", "<u4"), ("steps", "<u4"), ("clock_ns", "<u8"), ("msg
 # numpy view of a collecting campaign's list: madsim_failure_t, the seed in front of the result's fields
 FAILURE_DTYPE = [("seed", "<u8")] + RESULT_DTYPE
 assert C.sizeof(Failure) == 56 and C.sizeof(Collect) == 88
+# numpy view of a statistics campaign's extreme seeds: madsim_extreme_t
+EXTREME_DTYPE = [("value", "<u8"), ("seed", "<u8")]
+assert C.sizeof(Extreme) == 16 and C.sizeof(Metric) == 2080 and C.sizeof(Stats) == 32 + 4 * 2080
 
 PASS, PANIC, DEADLOCK, TIME_LIMIT, OVERFLOW, STEP_LIMIT, UNSUPPORTED, INTERNAL = range(8)
 VERDICT_NAMES = ["pass", "panic", "deadlock", "time-limit", "resource-overflow", "step-limit", "outside-the-workload-model", "internal-invariant"]

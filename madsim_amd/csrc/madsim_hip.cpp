@@ -91,12 +91,15 @@ struct madsim_hip_ctx {
     std::unordered_map<hipStream_t, Scratch> scratch;
     // madsim_hip_ctx_run_campaign: batches in flight on the context's own streams
     static constexpr int CAMPAIGN_MAX = 8;
+    static constexpr size_t STATS_REP_WORDS = 16 + MADSIM_K_STATS_WORDS;      // a statistics campaign's report: the plain / collecting report's words in front
     struct Flight { hipStream_t stream = nullptr; madsim_result_t* d_out = nullptr; size_t cap = 0; unsigned long long* d_acc6 = nullptr;
                     unsigned long long* h_acc6 = nullptr; hipEvent_t e0 = nullptr, e1 = nullptr, done = nullptr;
                     madsim_result_t* h_out = nullptr; size_t h_cap = 0;         // h_out: page-locked staging of run_pipelined
                     // collecting campaigns only: report words (device, page-locked host), per-wave counts, the batch's failure records
                     unsigned long long* d_rep = nullptr; unsigned long long* h_rep = nullptr; uint32_t* d_wcnt = nullptr;
-                    madsim_failure_t* d_rec = nullptr; size_t rec_cap = 0; };
+                    madsim_failure_t* d_rec = nullptr; size_t rec_cap = 0;
+                    // statistics campaigns only: 16 report words (summary6's or collect's) + MADSIM_K_STATS_WORDS (device, page-locked host), candidates
+                    unsigned long long* d_srep = nullptr; unsigned long long* h_srep = nullptr; unsigned long long* d_cand = nullptr; };
     Flight flights[CAMPAIGN_MAX];
     unsigned long long* d_acc = nullptr;      // 4 x u64 summary accumulators
     madsim_result_t* d_out = nullptr; size_t out_cap = 0;
@@ -138,7 +141,7 @@ struct madsim_hip_ctx {
                  const madsim_limits_t* lim, madsim_result_t* out, madsim_summary_t* summary);
     int run_list(const madsim_workload_t* w, const madsim_config_t* cfg, const std::vector<uint64_t>& seeds,
                  const madsim_limits_t* lim, std::vector<madsim_result_t>& res, double* kernel_ms);
-    int ensure_flights(uint32_t n, uint64_t batch, bool staging, bool collect = false, uint64_t records = 0);
+    int ensure_flights(uint32_t n, uint64_t batch, bool staging, bool collect = false, uint64_t records = 0, bool stats = false);
     uint32_t flights_for(const madsim_workload_t* w, const madsim_config_t* cfg, const madsim_limits_t* lim, uint64_t batch);
 };
 
@@ -210,6 +213,9 @@ void madsim_hip_ctx::close() {
         if (f.h_rep) (void)hipHostFree(f.h_rep);
         if (f.d_wcnt) (void)hipFree(f.d_wcnt);
         if (f.d_rec) (void)hipFree(f.d_rec);
+        if (f.d_srep) (void)hipFree(f.d_srep);
+        if (f.h_srep) (void)hipHostFree(f.h_srep);
+        if (f.d_cand) (void)hipFree(f.d_cand);
         if (f.e0) (void)hipEventDestroy(f.e0);
         if (f.e1) (void)hipEventDestroy(f.e1);
         if (f.done) (void)hipEventDestroy(f.done);
@@ -440,8 +446,9 @@ int madsim_hip_ctx::run_list(const madsim_workload_t* w, const madsim_config_t* 
 
 // Streams, report words, events and result buffers of the first n flights (campaigns and run_pipelined share them; the
 // context's mutex serialises the two).  `staging`: also a page-locked host buffer of `batch` results per flight.  `collect`: also
-// the report words and wave counts of a collecting campaign and room for `records` failure records per flight.
-int madsim_hip_ctx::ensure_flights(uint32_t n, uint64_t batch, bool staging, bool collect, uint64_t records) {
+// the report words and wave counts of a collecting campaign and room for `records` failure records per flight.  `stats`: also the
+// report and candidate words of a statistics campaign.
+int madsim_hip_ctx::ensure_flights(uint32_t n, uint64_t batch, bool staging, bool collect, uint64_t records, bool stats) {
     if (n > (uint32_t)CAMPAIGN_MAX) return fail(MADSIM_E_ARG, "at most 8 batches in flight");
     hint_hw_queues(n);
     for (uint32_t i = 0; i < n; i++) {
@@ -474,6 +481,11 @@ int madsim_hip_ctx::ensure_flights(uint32_t n, uint64_t batch, bool staging, boo
             f.d_rec = nullptr; f.rec_cap = 0;
             HIP_TRY(hipMalloc(&f.d_rec, records * sizeof(madsim_failure_t)));
             f.rec_cap = records;
+        }
+        if (stats && !f.d_srep) {
+            HIP_TRY(hipMalloc(&f.d_srep, STATS_REP_WORDS * sizeof(unsigned long long)));
+            HIP_TRY(hipHostMalloc((void**)&f.h_srep, STATS_REP_WORDS * sizeof(unsigned long long), hipHostMallocDefault));
+            HIP_TRY(hipMalloc(&f.d_cand, MADSIM_K_STATS_CAND_WORDS * sizeof(unsigned long long)));
         }
     }
     return 0;
@@ -891,6 +903,49 @@ int madsim_hip_run_batch_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const m
     return 0;
 }
 
+// ---- campaign statistics: the bucket rule and the host fold of a batch's report --------------------------------------------
+uint32_t madsim_hip_stat_bucket(uint64_t v) {
+    if (v < 4) return (uint32_t)v;
+    const uint32_t e = 63u - (uint32_t)__builtin_clzll(v);
+    return 4u * (e - 1u) + ((uint32_t)(v >> (e - 2u)) & 3u);
+}
+
+uint64_t madsim_hip_stat_bucket_floor(uint32_t b) {
+    if (b < 4) return b;
+    return b >= 252 ? UINT64_MAX : (uint64_t)(4 + b % 4) << (b / 4 - 1);
+}
+
+namespace {
+// s = a batch's MADSIM_K_STATS_WORDS (sim_kernel.hip): batches are folded in seed order, but nothing here relies on it — count, min, max and
+// the sums commute, and the extreme seeds are merged under the total order (value descending, seed ascending).
+void fold_stats(madsim_stats_t* st, const unsigned long long* s) {
+    const uint64_t n = s[0];
+    if (!n) return;
+    const uint32_t* hist = reinterpret_cast<const uint32_t*>(s + 17);
+    const madsim_extreme_t* top = reinterpret_cast<const madsim_extreme_t*>(s + 17 + MADSIM_STAT_METRICS * MADSIM_STAT_BUCKETS / 2);
+    const uint64_t K = st->top_k, have = st->n_top, got = std::min(K, n), keep = std::min(K, have + got);
+    for (uint32_t m = 0; m < MADSIM_STAT_METRICS; m++) {
+        madsim_metric_t& M = st->metric[m];
+        M.min = std::min<uint64_t>(M.min, ~s[1 + m]);
+        M.max = std::max<uint64_t>(M.max, s[5 + m]);
+        const unsigned __int128 sum = ((unsigned __int128)M.sum_hi << 64 | M.sum_lo) + s[9 + m] + ((unsigned __int128)s[13 + m] << 32);
+        M.sum_lo = (uint64_t)sum; M.sum_hi = (uint64_t)(sum >> 64);
+        for (uint32_t b = 0; b < MADSIM_STAT_BUCKETS; b++) M.hist[b] += hist[m * MADSIM_STAT_BUCKETS + b];
+        if (!K) continue;
+        madsim_extreme_t* row = st->top + m * K;
+        const madsim_extreme_t* add = top + m * MADSIM_STAT_MAX_TOP;
+        madsim_extreme_t merged[MADSIM_STAT_MAX_TOP];
+        for (uint64_t i = 0, a = 0, b = 0; i < keep; i++) {
+            const bool from_row = b >= got || (a < have && (row[a].value > add[b].value || (row[a].value == add[b].value && row[a].seed < add[b].seed)));
+            merged[i] = from_row ? row[a++] : add[b++];
+        }
+        memcpy(row, merged, keep * sizeof *row);
+    }
+    st->n += n;
+    st->n_top = keep;
+}
+}  // namespace
+
 // ---- campaigns -------------------------------------------------------------------------------------------------------------
 // One implementation for one context and for several (madsim_hip_run_campaign_multi): batch k of the range runs on context k % n,
 // on that context's flight (k / n) % in_flight — the devices advance through the seed space TOGETHER, so with
@@ -902,10 +957,15 @@ int madsim_hip_run_batch_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const m
 namespace {
 int run_campaign_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total,
                       uint64_t batch, uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim, madsim_campaign_t* out,
-                      madsim_collect_t* col = nullptr) {
+                      madsim_collect_t* col = nullptr, madsim_stats_t* st = nullptr) {
     auto t0 = std::chrono::steady_clock::now();
     memset(out, 0, sizeof *out);
     out->first_failing_seed = UINT64_MAX;
+    if (st) {
+        st->n = st->n_top = 0;
+        memset(st->metric, 0, sizeof st->metric);
+        for (madsim_metric_t& m : st->metric) m.min = UINT64_MAX;
+    }
     if (col) { col->n_listed = 0; memset(col->n_by_verdict, 0, sizeof col->n_by_verdict); }
     else flags &= ~(MADSIM_CAMPAIGN_LIST_RUNNER | MADSIM_CAMPAIGN_STOP_AT_CAP);      // (flags of the collecting form only)
     int rc = madsim_geo::validate(w, cfg, &g_err);
@@ -914,6 +974,7 @@ int run_campaign_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workl
     if (in_flight > (uint32_t)madsim_hip_ctx::CAMPAIGN_MAX) return fail(MADSIM_E_ARG, "at most 8 batches in flight per context");
     if (seed0 + total < seed0) return fail(MADSIM_E_ARG, "seed0 + total wraps");
     if (total == 0) return 0;
+    if (st && std::min(batch, total) >= 0xffffffffull) return fail(MADSIM_E_ARG, "a statistics campaign's batch holds fewer than 2^32 - 1 seeds");
     const uint64_t n_batches = (total + batch - 1) / batch, N = (uint64_t)n_ctx;
     const uint64_t rec_batch = col ? std::min(col->cap, std::min(batch, total)) : 0;      // records a flight holds: no batch lists more
     uint64_t listed_seen = 0;                                   // listed seeds of the batches folded so far (not cut at cap)
@@ -924,7 +985,7 @@ int run_campaign_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workl
         uint32_t f = in_flight ? in_flight : ctxs[g]->flights_for(w, cfg, lim, batch);
         if ((uint64_t)f > mine) f = (uint32_t)mine;
         F[g] = f;
-        if (f && (rc = ctxs[g]->ensure_flights(f, batch, false, col != nullptr, rec_batch))) return rc;
+        if (f && (rc = ctxs[g]->ensure_flights(f, batch, false, col != nullptr, rec_batch, st != nullptr))) return rc;
     }
     int first_err = 0;
     std::string first_msg;
@@ -935,24 +996,26 @@ int run_campaign_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workl
         const uint64_t lo = k * batch, n = std::min(batch, total - lo);
         int e;
         if ((e = c->bind())) return e;
-        unsigned long long* const d_words = col ? f.d_rep : f.d_acc6;          // the same four memsets, the last one longer when collecting
+        // the same four memsets, the last one longer when collecting, and longer still with statistics (whose words all start as zero)
+        unsigned long long* const d_words = st ? f.d_srep : col ? f.d_rep : f.d_acc6;
+        const size_t n_words = st ? madsim_hip_ctx::STATS_REP_WORDS - (st->top_k ? 0 : 2 * MADSIM_STAT_METRICS * MADSIM_STAT_MAX_TOP)
+                                  : col ? MADSIM_K_COLLECT_WORDS : 6;
         HIP_TRY(hipMemsetAsync(d_words, 0xff, 8, f.stream));
         HIP_TRY(hipMemsetAsync((char*)d_words + 8, 0, 24, f.stream));
         HIP_TRY(hipMemsetAsync((char*)d_words + 32, 0xff, 8, f.stream));
-        HIP_TRY(hipMemsetAsync((char*)d_words + 40, 0, col ? (MADSIM_K_COLLECT_WORDS - 5) * 8 : 8, f.stream));
+        HIP_TRY(hipMemsetAsync((char*)d_words + 40, 0, (n_words - 5) * 8, f.stream));
         HIP_TRY(hipEventRecord(f.e0, f.stream));
         if ((e = c->launch(w, cfg, seed0 + lo, n, nullptr, lim, f.d_out, f.stream))) return e;
         HIP_TRY(hipEventRecord(f.e1, f.stream));
-        if (col) {
-            madsim_k_launch_collect(f.d_out, n, seed0 + lo, (flags & MADSIM_CAMPAIGN_LIST_RUNNER) ? 1u : 0u, f.d_rep, f.d_wcnt, f.d_rec,
-                                    std::min(rec_batch, n), f.stream);
+        if (col) madsim_k_launch_collect(f.d_out, n, seed0 + lo, (flags & MADSIM_CAMPAIGN_LIST_RUNNER) ? 1u : 0u, d_words, f.d_wcnt, f.d_rec,
+                                         std::min(rec_batch, n), f.stream);
+        else madsim_k_launch_summary6(f.d_out, n, seed0 + lo, d_words, f.stream);
+        HIP_TRY(hipGetLastError());
+        if (st) {                                                // behind the report kernel, into the words after its sixteen
+            madsim_k_launch_stats(f.d_out, n, seed0 + lo, st->include, st->top_k, f.d_srep + 16, f.d_cand, f.stream);
             HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(f.h_rep, f.d_rep, MADSIM_K_COLLECT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, f.stream));
-        } else {
-            madsim_k_launch_summary6(f.d_out, n, seed0 + lo, f.d_acc6, f.stream);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(f.h_acc6, f.d_acc6, 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost, f.stream));
         }
+        HIP_TRY(hipMemcpyAsync(st ? f.h_srep : col ? f.h_rep : f.h_acc6, d_words, n_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, f.stream));
         HIP_TRY(hipEventRecord(f.done, f.stream));
         return 0;
     };
@@ -968,7 +1031,7 @@ int run_campaign_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workl
         float ms = 0.f;
         HIP_TRY(hipEventElapsedTime(&ms, f.e0, f.e1));
         if (!stop) {                                            // batches launched beyond the failing one are not part of the answer
-            const unsigned long long* a = col ? f.h_rep : f.h_acc6;
+            const unsigned long long* a = st ? f.h_srep : col ? f.h_rep : f.h_acc6;
             out->kernel_ms += ms;
             out->batches_run++; out->seeds_run += n;
             out->n_runner += a[5];
@@ -989,6 +1052,7 @@ int run_campaign_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workl
                 listed_seen += a[14];
                 if ((flags & MADSIM_CAMPAIGN_STOP_AT_CAP) && listed_seen >= col->cap) stop = true;
             }
+            if (st) fold_stats(st, a + 16);
         }
         return 0;
     };
@@ -1076,6 +1140,46 @@ int madsim_hip_run_campaign_collect_multi(madsim_hip_ctx_t* const* ctxs, int n_c
     return run_campaign_impl(ctxs, n_ctx, w, cfg, seed0, total, batch, in_flight, flags, lim, out, col);
 }
 
+// The statistics forms: argument errors first, as the collecting forms.
+namespace {
+int check_stats_args(const madsim_campaign_t* out, const madsim_collect_t* col, const madsim_stats_t* st, uint32_t in_flight, uint32_t flags) {
+    if (!out) return fail(MADSIM_E_ARG, "null campaign report");
+    if (!st) return fail(MADSIM_E_ARG, "null madsim_stats_t");
+    if (st->include == 0 || (st->include & ~0xfu)) return fail(MADSIM_E_ARG, "madsim_stats_t.include: at least one of bits 0-3 (PASS, PANIC, DEADLOCK, TIME_LIMIT), no other");
+    if (st->top_k > MADSIM_STAT_MAX_TOP) return fail(MADSIM_E_ARG, "madsim_stats_t.top_k > MADSIM_STAT_MAX_TOP");
+    if (st->top_k && !st->top) return fail(MADSIM_E_ARG, "madsim_stats_t.top_k > 0 without a top array");
+    if (col) return check_collect_args(out, col, in_flight, flags);
+    if (in_flight > (uint32_t)madsim_hip_ctx::CAMPAIGN_MAX) return fail(MADSIM_E_ARG, "at most 8 batches in flight per context");
+    return 0;
+}
+}  // namespace
+
+int madsim_hip_ctx_run_campaign_stats(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total,
+                                      uint64_t batch, uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim, madsim_campaign_t* out,
+                                      madsim_collect_t* col, madsim_stats_t* st) {
+    if (int rc = check_stats_args(out, col, st, in_flight, flags)) return rc;
+    CTX_ENTER(c);
+    madsim_hip_ctx* one[1] = {c};
+    return run_campaign_impl(one, 1, w, cfg, seed0, total, batch, in_flight, flags, lim, out, col, st);
+}
+
+int madsim_hip_run_campaign_stats_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_workload_t* w, const madsim_config_t* cfg,
+                                        uint64_t seed0, uint64_t total, uint64_t batch, uint32_t in_flight, uint32_t flags,
+                                        const madsim_limits_t* lim, madsim_campaign_t* out, madsim_collect_t* col, madsim_stats_t* st) {
+    if (int rc = check_stats_args(out, col, st, in_flight, flags)) return rc;
+    if (!ctxs || n_ctx < 1) return fail(MADSIM_E_ARG, "run_campaign_stats_multi needs at least one context");
+    for (int g = 0; g < n_ctx; g++) {
+        if (!ctxs[g]) return fail(MADSIM_E_NOINIT, "null context");
+        for (int h = 0; h < g; h++) if (ctxs[h] == ctxs[g]) return fail(MADSIM_E_ARG, "the same context appears twice");
+    }
+    std::vector<madsim_hip_ctx*> order(ctxs, ctxs + n_ctx);      // locks in address order (see madsim_hip_run_batch_multi)
+    std::sort(order.begin(), order.end(), [](madsim_hip_ctx* a, madsim_hip_ctx* b) { return std::less<madsim_hip_ctx*>()(a, b); });
+    std::vector<std::unique_lock<std::mutex>> locks;
+    for (madsim_hip_ctx* c : order) locks.emplace_back(c->mu);
+    for (int g = 0; g < n_ctx; g++) if (ctxs[g]->device < 0) return fail(MADSIM_E_NOINIT, "closed context");
+    return run_campaign_impl(ctxs, n_ctx, w, cfg, seed0, total, batch, in_flight, flags, lim, out, col, st);
+}
+
 // ---- v1 entry points: wrappers on the process-default context ------------------------------------------------------------
 // The default context is reference-counted by its users: a wrapper pins it under g_default_mu for the duration of its call,
 // and madsim_hip_shutdown waits until no call is inside before destroying it — a concurrent run_batch and shutdown is a
@@ -1156,6 +1260,13 @@ int madsim_hip_run_campaign_collect(const madsim_workload_t* w, const madsim_con
                                     uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim, madsim_campaign_t* out, madsim_collect_t* col) {
     DefaultPin p;
     return madsim_hip_ctx_run_campaign_collect(p.c, w, cfg, seed0, total, batch, in_flight, flags, lim, out, col);
+}
+
+int madsim_hip_run_campaign_stats(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total, uint64_t batch,
+                                  uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim, madsim_campaign_t* out, madsim_collect_t* col,
+                                  madsim_stats_t* st) {
+    DefaultPin p;
+    return madsim_hip_ctx_run_campaign_stats(p.c, w, cfg, seed0, total, batch, in_flight, flags, lim, out, col, st);
 }
 
 int madsim_hip_geometry(const madsim_workload_t* w, const madsim_limits_t* lim, madsim_geometry_t* out) {

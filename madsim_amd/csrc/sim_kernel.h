@@ -314,6 +314,12 @@ void madsim_k_launch_summary6(const madsim_result_t* out, uint64_t count, uint64
 #define MADSIM_K_COLLECT_WAVES 1024u
 void madsim_k_launch_collect(const madsim_result_t* out, uint64_t count, uint64_t seed0, uint32_t list_runner, unsigned long long* rep,
                              uint32_t* wave_cnt, madsim_failure_t* recs, uint64_t cap, void* stream);
+// the statistics campaign's report kernels, behind summary6 / collect on the same stream: `srep` = {n, ~min[4], max[4], low half-sums[4], high
+// half-sums[4]} (17 words), hist[4][256] as 32-bit counters (512 words), top[4][16] {value, seed} (128 words); cand: per-workgroup candidate lists
+#define MADSIM_K_STATS_WORDS 657u
+#define MADSIM_K_STATS_CAND_WORDS 32768u
+void madsim_k_launch_stats(const madsim_result_t* out, uint64_t count, uint64_t seed0, uint32_t include, uint32_t top_k, unsigned long long* srep,
+                           unsigned long long* cand, void* stream);
 int  madsim_k_set_max_lds(uint32_t lds_bytes);
 int  madsim_k_variant_vgprs(const madsim_k::VariantSel* v);
 void madsim_k_launch_keyflip(unsigned long long* acc, void* stream);

@@ -187,6 +187,184 @@ __global__ __launch_bounds__(256) void collect_write_kernel(const madsim_result_
     }
 }
 
+// ---- the statistics campaign form: count, min, max, 128-bit sum, a 252-bucket histogram and the K extreme seeds of four metrics ----
+// Two kernels behind the batch's summary6 / collect kernels, over collect's cut of the batch (wave W owns a contiguous piece).
+// stats_fold_kernel reads the first 32 of a seed's 48 bytes (verdict, steps, clock_ns, msg_count, rng_calls: two 16-byte loads) once.
+// A seed is COUNTED when bit `verdict` of `include` is set (bits 0-3 only, so never a runner verdict).  Min, max and the two half-sums
+// (sum of v & 0xffffffff, sum of v >> 32: exact below 2^32 seeds) fold in registers, per wave, then per workgroup through LDS: one set
+// of atomics per workgroup.  The four histograms are LDS counters, flushed with one atomic per non-zero bucket.  Integer adds, min and
+// max commute: the words do not depend on any order.
+// The K extreme seeds of a metric are the K first counted seeds under the TOTAL order "value descending, seed ascending" — the key
+// {value, ~index in the batch}, unique per seed — so they are a function of the batch alone, and no atomic decides a position: a wave
+// keeps its K first in lanes 0 .. K-1 (topk_merge: K rounds of a wave-wide maximum over the list and the 64 new elements; a round of 64
+// elements none of which beats the K-th is skipped, which is also what happens to every later element of a tie), wave m of a workgroup
+// merges the four waves' lists of metric m into cand[m][workgroup][0..16), and stats_top_kernel (one workgroup per metric) merges the
+// workgroups' lists the same way and writes {value, seed} in order.  Tied values cost what distinct ones cost.
+// srep = {n, ~min[4], max[4], sum of low halves[4], sum of high halves[4]} (17 words, all zero before the launch: the minimum is kept
+// inverted so that one memset prepares everything), then hist[4][256] as 32-bit counters, then top[4][16] {value, seed}.
+constexpr uint32_t STAT_TOP = MADSIM_STAT_MAX_TOP, STAT_WGS = COLLECT_MAX_WAVES / 4;
+
+struct TopKey { unsigned long long v; uint32_t k; };              // k = ~(index in the batch), 0 = no element (then v = 0: below every element)
+__device__ __forceinline__ bool key_gt(const TopKey& a, const TopKey& b) { return a.v > b.v || (a.v == b.v && a.k > b.k); }
+
+__device__ __forceinline__ uint32_t stat_bucket(unsigned long long v) {          // madsim_hip_stat_bucket
+    if (v < 4) return (uint32_t)v;
+    const uint32_t e = 63u - (uint32_t)__clzll((long long)v);
+    return 4u * (e - 1u) + ((uint32_t)(v >> (e - 2u)) & 3u);
+}
+
+// list[m] (entry r in lane r, r < K <= 16, sorted; {0, 0} elsewhere) := the K first of list[m] and the wave's 64 nw[m].  Wave-uniform flow.
+template <int M>
+__device__ __forceinline__ void topk_merge(TopKey (&list)[M], TopKey (&nw)[M], uint32_t K, uint32_t lane) {
+    TopKey res[M];
+#pragma unroll
+    for (int m = 0; m < M; m++) res[m] = TopKey{0, 0};
+    for (uint32_t r = 0; r < K; r++) {
+        TopKey mine[M], best[M];
+        bool from_list[M];
+#pragma unroll
+        for (int m = 0; m < M; m++) { from_list[m] = key_gt(list[m], nw[m]); best[m] = mine[m] = from_list[m] ? list[m] : nw[m]; }
+        for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+            for (int m = 0; m < M; m++) {
+                const TopKey t = {__shfl_xor(best[m].v, o), __shfl_xor(best[m].k, o)};
+                if (key_gt(t, best[m])) best[m] = t;
+            }
+        }
+        uint32_t left = 0;
+#pragma unroll
+        for (int m = 0; m < M; m++) {                                             // keys are unique: exactly one lane holds the winner
+            if (best[m].k != 0 && mine[m].k == best[m].k && mine[m].v == best[m].v) { if (from_list[m]) list[m] = TopKey{0, 0}; else nw[m] = TopKey{0, 0}; }
+            if (lane == r) res[m] = best[m];
+            left |= best[m].k;
+        }
+        if (!left) break;                                                          // (wave-uniform) nothing left in any metric
+    }
+#pragma unroll
+    for (int m = 0; m < M; m++) list[m] = res[m];
+}
+
+// true (wave-uniform) when one of the wave's nw[m] comes before the K-th entry of list[m]: only then the list changes
+template <int M>
+__device__ __forceinline__ bool topk_enters(const TopKey (&list)[M], const TopKey (&nw)[M], uint32_t K) {
+    bool any = false;
+#pragma unroll
+    for (int m = 0; m < M; m++) {
+        const TopKey kth = {__shfl(list[m].v, (int)K - 1), __shfl(list[m].k, (int)K - 1)};
+        any |= key_gt(nw[m], kth);
+    }
+    return __ballot(any) != 0;
+}
+
+__global__ __launch_bounds__(256) void stats_fold_kernel(const madsim_result_t* __restrict__ out, uint64_t count, uint64_t piece, uint32_t include,
+                                                         uint32_t K, unsigned long long* __restrict__ srep, uint32_t* __restrict__ ghist,
+                                                         unsigned long long* __restrict__ cand) {
+    __shared__ uint32_t hist[MADSIM_STAT_METRICS][MADSIM_STAT_BUCKETS];
+    __shared__ unsigned long long part[4][17];
+    __shared__ unsigned long long lv[MADSIM_STAT_METRICS][4 * STAT_TOP];
+    __shared__ uint32_t lk[MADSIM_STAT_METRICS][4 * STAT_TOP];
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63, W = blockIdx.x * 4 + wave;
+    for (uint32_t i = threadIdx.x; i < MADSIM_STAT_METRICS * MADSIM_STAT_BUCKETS; i += 256) (&hist[0][0])[i] = 0;
+    __syncthreads();
+    const uint64_t lo = (uint64_t)W * piece, hi = lo + piece < count ? lo + piece : count;
+    unsigned long long acc[17];                                                    // n, ~min[4], max[4], low halves[4], high halves[4]
+#pragma unroll
+    for (int j = 0; j < 17; j++) acc[j] = 0;
+    TopKey list[MADSIM_STAT_METRICS];
+#pragma unroll
+    for (int m = 0; m < 4; m++) list[m] = TopKey{0, 0};
+    for (uint64_t base = lo; base < hi; base += 64) {
+        const uint64_t i = base + lane;
+        TopKey nw[MADSIM_STAT_METRICS];
+#pragma unroll
+        for (int m = 0; m < 4; m++) nw[m] = TopKey{0, 0};
+        if (i < hi) {
+            const uint4 r0 = reinterpret_cast<const uint4*>(out + i)[0], r1 = reinterpret_cast<const uint4*>(out + i)[1];
+            if (r0.x < 4u && ((include >> r0.x) & 1u)) {
+                const unsigned long long v[4] = {((unsigned long long)r0.w << 32) | r0.z, r0.y, ((unsigned long long)r1.y << 32) | r1.x,
+                                                 ((unsigned long long)r1.w << 32) | r1.z};
+                acc[0]++;
+#pragma unroll
+                for (int m = 0; m < 4; m++) {
+                    acc[1 + m] = ~v[m] > acc[1 + m] ? ~v[m] : acc[1 + m];
+                    acc[5 + m] = v[m] > acc[5 + m] ? v[m] : acc[5 + m];
+                    acc[9 + m] += v[m] & 0xffffffffull; acc[13 + m] += v[m] >> 32;
+                    atomicAdd(&hist[m][stat_bucket(v[m])], 1u);
+                    nw[m] = TopKey{v[m], ~(uint32_t)i};                            // (a batch holds fewer than 2^32 - 1 seeds: never 0)
+                }
+            }
+        }
+        if (K && topk_enters<4>(list, nw, K)) topk_merge<4>(list, nw, K, lane);
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+        for (int j = 0; j < 17; j++) {
+            const unsigned long long t = __shfl_xor(acc[j], o);
+            if (j >= 1 && j < 9) acc[j] = t > acc[j] ? t : acc[j]; else acc[j] += t;
+        }
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int j = 0; j < 17; j++) part[wave][j] = acc[j];
+    }
+    if (K && lane < STAT_TOP) {
+#pragma unroll
+        for (int m = 0; m < 4; m++) { lv[m][wave * STAT_TOP + lane] = list[m].v; lk[m][wave * STAT_TOP + lane] = list[m].k; }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int m = 0; m < 4; m++) {                                                  // thread t: bucket t of every metric
+        const uint32_t c = hist[m][threadIdx.x];
+        if (c) atomicAdd(&ghist[m * MADSIM_STAT_BUCKETS + threadIdx.x], c);
+    }
+    if (threadIdx.x < 17 && part[0][0] + part[1][0] + part[2][0] + part[3][0] != 0) {        // one set of atomics per workgroup that counted a seed
+        const uint32_t j = threadIdx.x;
+        unsigned long long a = part[0][j];
+        for (int w = 1; w < 4; w++) { const unsigned long long t = part[w][j]; if (j >= 1 && j < 9) a = t > a ? t : a; else a += t; }
+        if (j >= 1 && j < 9) atomicMax(&srep[j], a); else atomicAdd(&srep[j], a);
+    }
+    if (K) {                                                                       // wave m: the workgroup's list of metric m
+        TopKey l1[1] = {TopKey{0, 0}}, n1[1] = {TopKey{lv[wave][lane], lk[wave][lane]}};
+        topk_merge<1>(l1, n1, K, lane);
+        if (lane < STAT_TOP) {
+            unsigned long long* p = cand + ((uint64_t)(wave * STAT_WGS + blockIdx.x) * STAT_TOP + lane) * 2;
+            p[0] = l1[0].v; p[1] = l1[0].k ? (unsigned long long)(uint32_t)~l1[0].k : ~0ull;
+        }
+    }
+}
+
+// grid = MADSIM_STAT_METRICS workgroups: workgroup m merges cand[m][0 .. n_wg)[0 .. 16) ({value, index in the batch or ~0}), a quarter per
+// wave, then wave 0 the four lists; top[m][r] = {value, seed}, r < min(K, counted seeds of the batch).
+__global__ __launch_bounds__(256) void stats_top_kernel(const unsigned long long* __restrict__ cand, uint32_t n_wg, uint32_t K, uint64_t seed0,
+                                                        unsigned long long* __restrict__ top) {
+    __shared__ unsigned long long lv[4 * STAT_TOP];
+    __shared__ uint32_t lk[4 * STAT_TOP];
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63, m = blockIdx.x;
+    const uint32_t total = n_wg * STAT_TOP, quarter = (total / 4 + 63) / 64 * 64;      // (total is a multiple of 16, at most 4 096)
+    const uint32_t lo = wave * quarter, hi = lo + quarter < total ? lo + quarter : total;
+    const unsigned long long* src = cand + (uint64_t)m * STAT_WGS * STAT_TOP * 2;
+    TopKey list[1] = {TopKey{0, 0}};
+    for (uint32_t base = lo; base < hi; base += 64) {
+        const uint32_t j = base + lane;
+        TopKey nw[1] = {TopKey{0, 0}};
+        if (j < hi) {
+            const unsigned long long v = src[2 * j], x = src[2 * j + 1];
+            if (x != ~0ull) nw[0] = TopKey{v, ~(uint32_t)x};
+        }
+        if (topk_enters<1>(list, nw, K)) topk_merge<1>(list, nw, K, lane);
+    }
+    if (lane < STAT_TOP) { lv[wave * STAT_TOP + lane] = list[0].v; lk[wave * STAT_TOP + lane] = list[0].k; }
+    __syncthreads();
+    if (wave == 0) {
+        TopKey l1[1] = {TopKey{0, 0}}, n1[1] = {TopKey{lv[lane], lk[lane]}};
+        topk_merge<1>(l1, n1, K, lane);
+        if (lane < K && l1[0].k) {
+            unsigned long long* p = top + (uint64_t)(m * STAT_TOP + lane) * 2;
+            p[0] = l1[0].v; p[1] = seed0 + (uint32_t)~l1[0].k;
+        }
+    }
+}
+
 __global__ void keyflip_kernel(unsigned long long* acc) { acc[0] ^= 0x8000000000000000ull; }
 
 // one kernel per row of variant_table (sim_kernel.h), same macro, same order
@@ -233,6 +411,24 @@ extern "C" void madsim_k_launch_collect(const madsim_result_t* out, uint64_t cou
     hipLaunchKernelGGL(madsim_k::collect_count_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, out, count, seed0, piece, list_runner, rep, wave_cnt);
     hipLaunchKernelGGL(madsim_k::collect_write_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, out, count, seed0, piece, list_runner, rep,
                        (const uint32_t*)wave_cnt, recs, cap);
+}
+
+// srep: MADSIM_K_STATS_WORDS words, all zero (prepared by the caller on `stream`); cand: MADSIM_K_STATS_CAND_WORDS words of scratch, untouched
+// when top_k == 0; count < 2^32 - 1
+extern "C" void madsim_k_launch_stats(const madsim_result_t* out, uint64_t count, uint64_t seed0, uint32_t include, uint32_t top_k,
+                                      unsigned long long* srep, unsigned long long* cand, void* stream) {
+    static_assert(MADSIM_K_STATS_WORDS == 17 + MADSIM_STAT_METRICS * MADSIM_STAT_BUCKETS / 2 + MADSIM_STAT_METRICS * MADSIM_STAT_MAX_TOP * 2, "sim_kernel.h");
+    static_assert(MADSIM_K_STATS_CAND_WORDS == MADSIM_STAT_METRICS * madsim_k::STAT_WGS * madsim_k::STAT_TOP * 2, "sim_kernel.h");
+    static_assert(MADSIM_STAT_BUCKETS == 256 && MADSIM_STAT_METRICS == 4 && MADSIM_STAT_MAX_TOP == 16, "one bucket per thread, one metric per wave");
+    uint32_t grid = (uint32_t)((count + 1023) / 1024);     // collect's cut
+    if (grid > madsim_k::STAT_WGS) grid = madsim_k::STAT_WGS;
+    if (grid == 0) grid = 1;
+    const uint64_t waves = 4ull * grid, piece = ((count + waves - 1) / waves + 63) / 64 * 64;
+    uint32_t* const ghist = reinterpret_cast<uint32_t*>(srep + 17);
+    hipLaunchKernelGGL(madsim_k::stats_fold_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, out, count, piece, include, top_k, srep, ghist, cand);
+    if (top_k)
+        hipLaunchKernelGGL(madsim_k::stats_top_kernel, dim3(MADSIM_STAT_METRICS), dim3(256), 0, (hipStream_t)stream, (const unsigned long long*)cand, grid,
+                           top_k, seed0, srep + 17 + MADSIM_STAT_METRICS * MADSIM_STAT_BUCKETS / 2);
 }
 
 extern "C" void madsim_k_launch_keyflip(unsigned long long* acc, void* stream) {

@@ -12,6 +12,7 @@ There is no CPU fallback: if the library is missing or no GPU is visible this
 module raises, loudly.
 """
 import ctypes as C
+import math
 import os
 import sys
 import time
@@ -115,6 +116,13 @@ def lib():
         L.madsim_hip_run_campaign_collect.argtypes = L.madsim_hip_run_campaign.argtypes + [C.POINTER(A.Collect)]
         L.madsim_hip_ctx_run_campaign_collect.argtypes = [ctxp] + L.madsim_hip_run_campaign_collect.argtypes
         L.madsim_hip_run_campaign_collect_multi.argtypes = [C.POINTER(ctxp), C.c_int] + L.madsim_hip_run_campaign_collect.argtypes
+        L.madsim_hip_stat_bucket.restype = C.c_uint32
+        L.madsim_hip_stat_bucket.argtypes = [C.c_uint64]
+        L.madsim_hip_stat_bucket_floor.restype = C.c_uint64
+        L.madsim_hip_stat_bucket_floor.argtypes = [C.c_uint32]
+        L.madsim_hip_run_campaign_stats.argtypes = L.madsim_hip_run_campaign_collect.argtypes + [C.POINTER(A.Stats)]
+        L.madsim_hip_ctx_run_campaign_stats.argtypes = [ctxp] + L.madsim_hip_run_campaign_stats.argtypes
+        L.madsim_hip_run_campaign_stats_multi.argtypes = [C.POINTER(ctxp), C.c_int] + L.madsim_hip_run_campaign_stats.argtypes
         if L.madsim_hip_version() != A.ABI_VERSION:
             raise MadsimHipError("libmadsim_hip.so ABI version mismatch")
         # build identity: MADSIM_HIP_LIB may name an A/B build of THIS library (tools/build_variant.sh), nothing else — an
@@ -239,6 +247,79 @@ def run_campaign(workload, seed0, total, batch=0, in_flight=0, stop_at_failure=F
     return rep, failures, by_verdict
 
 
+class CampaignStats:
+    """What a statistics campaign (madsim_hip_run_campaign_stats) says about the counted seeds of the prefix that ran: `n`, and per metric
+    name of A.STAT_NAMES — "clock_ns", "steps", "msg_count", "rng_calls" — `min`, `max`, `sum` (a Python int: the exact 128-bit sum),
+    `mean` and `hist` (uint64[256] bucket counts) as dicts, `top(metric)` and `quantile(metric, q)`.  All exact integers but `mean`."""
+
+    def __init__(self, st, top):
+        self.include, self.top_k, self.n, self.n_top = int(st.include), int(st.top_k), int(st.n), int(st.n_top)
+        self.min, self.max, self.sum, self.mean, self.hist = {}, {}, {}, {}, {}
+        self._top = {}
+        for m, name in enumerate(A.STAT_NAMES):
+            M = st.metric[m]
+            self.min[name], self.max[name] = int(M.min), int(M.max)
+            self.sum[name] = (int(M.sum_hi) << 64) | int(M.sum_lo)
+            self.mean[name] = self.sum[name] / self.n if self.n else float("nan")
+            self.hist[name] = np.ctypeslib.as_array(M.hist).astype(np.uint64)
+            self._top[name] = top[m, :self.n_top].copy()
+
+    def top(self, metric):
+        """The n_top = min(top_k, n) counted seeds that come first by `metric` descending, then seed ascending: ndarray[EXTREME_DTYPE]."""
+        return self._top[metric]
+
+    def quantile(self, metric, q):
+        """(lo, hi): inclusive bounds of the value of rank ceil(q * n) (1-based, ascending, q in (0, 1]) — those of its bucket, clipped to
+        [min, max]."""
+        if not 0 < q <= 1:
+            raise ValueError("quantile: q in (0, 1]")
+        if not self.n:
+            raise ValueError("quantile of no seeds")
+        rank = min(max(math.ceil(q * self.n), 1), self.n)
+        b = int(np.searchsorted(np.cumsum(self.hist[metric]), rank))
+        return max(A.stat_bucket_floor(b), self.min[metric]), min(A.stat_bucket_floor(b + 1) - (1 if b < 251 else 0), self.max[metric])
+
+
+def _include_mask(include):
+    if isinstance(include, int):
+        include = (include,)
+    mask = 0
+    for v in include:
+        if not 0 <= int(v) < 4:
+            raise MadsimHipError(f"include: verdicts 0-3 (PASS, PANIC, DEADLOCK, TIME_LIMIT), got {v}")
+        mask |= 1 << int(v)
+    return mask
+
+
+def _campaign_stats(call, include, top_k, collect, rep):
+    """Run `call(col, st)` — one of the madsim_hip_*run_campaign_stats* entry points with everything but its last two arguments bound."""
+    mask = _include_mask(include)
+    if not mask or not 0 <= top_k <= A.STAT_MAX_TOP:
+        raise MadsimHipError(f"run_campaign_stats: include must name a verdict and top_k be 0..{A.STAT_MAX_TOP}")
+    st = A.Stats()
+    st.include, st.top_k = mask, top_k
+    top = np.zeros((A.STAT_METRICS, top_k), dtype=A.EXTREME_DTYPE)
+    st.top = top.ctypes.data_as(C.POINTER(A.Extreme)) if top_k else None
+    if collect is None:
+        _check(call(None, C.byref(st)))
+        return rep, CampaignStats(st, top)
+    failures, by_verdict = _collecting(lambda col: call(col, C.byref(st)), collect)
+    return rep, failures, by_verdict, CampaignStats(st, top)
+
+
+def run_campaign_stats(workload, seed0, total, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None, include=(A.PASS,),
+                       top_k=0, collect=None, list_runner=False, stop_at_cap=False):
+    """madsim_hip_run_campaign_stats: run_campaign, plus the statistics of clock_ns, steps, msg_count and rng_calls over the seeds whose
+    verdict is in `include` (PASS / PANIC / DEADLOCK / TIME_LIMIT) and the `top_k` (<= 16) extreme seeds of each.  Returns
+    (campaign, CampaignStats); with collect=K (as run_campaign) (campaign, failures, by_verdict, CampaignStats)."""
+    if _inited_device is None:
+        init(0)
+    cfg, lim, rep = config or A.Config.default(), limits or A.Limits(), A.Campaign()
+    flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap)
+    return _campaign_stats(lambda col, st: lib().madsim_hip_run_campaign_stats(
+        workload.ref(), C.byref(cfg), seed0, total, batch, in_flight, flags, C.byref(lim), C.byref(rep), col, st), include, top_k, collect, rep)
+
+
 def run_batch_device(workload, seed0, count, d_out_ptr, stream_ptr=0, config=None, limits=None, want_summary=True):
     """Device-resident entry point: results stay in HBM at `d_out_ptr` (48 B/seed)."""
     if _inited_device is None:
@@ -310,6 +391,15 @@ class Context:
             self._h, workload.ref(), C.byref(cfg), seed0, total, batch, in_flight, flags, C.byref(lim), C.byref(rep), col), collect)
         return rep, failures, by_verdict
 
+    def run_campaign_stats(self, workload, seed0, total, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None,
+                           include=(A.PASS,), top_k=0, collect=None, list_runner=False, stop_at_cap=False):
+        """runtime.run_campaign_stats on this context (madsim_hip_ctx_run_campaign_stats)."""
+        cfg, lim, rep = config or A.Config.default(), limits or A.Limits(), A.Campaign()
+        flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap)
+        return _campaign_stats(lambda col, st: lib().madsim_hip_ctx_run_campaign_stats(
+            self._h, workload.ref(), C.byref(cfg), seed0, total, batch, in_flight, flags, C.byref(lim), C.byref(rep), col, st),
+            include, top_k, collect, rep)
+
 
 def run_batch_multi(contexts, workload, seed0, count, config=None, limits=None, max_rounds=5):
     """madsim_hip_run_batch_multi: one process, one host thread, the seed range sharded contiguously over `contexts`
@@ -341,6 +431,17 @@ def run_campaign_multi(contexts, workload, seed0, total, batch=0, in_flight=0, s
     failures, by_verdict = _collecting(lambda col: lib().madsim_hip_run_campaign_collect_multi(
         arr, len(contexts), workload.ref(), C.byref(cfg), seed0, total, batch, in_flight, flags, C.byref(lim), C.byref(rep), col), collect)
     return rep, failures, by_verdict
+
+
+def run_campaign_stats_multi(contexts, workload, seed0, total, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None,
+                             include=(A.PASS,), top_k=0, collect=None, list_runner=False, stop_at_cap=False):
+    """madsim_hip_run_campaign_stats_multi: run_campaign_stats over several contexts; the statistics are the ones a single context gives."""
+    cfg, lim, rep = config or A.Config.default(), limits or A.Limits(), A.Campaign()
+    arr = (C.c_void_p * len(contexts))(*[c._h for c in contexts])
+    flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap)
+    return _campaign_stats(lambda col, st: lib().madsim_hip_run_campaign_stats_multi(
+        arr, len(contexts), workload.ref(), C.byref(cfg), seed0, total, batch, in_flight, flags, C.byref(lim), C.byref(rep), col, st),
+        include, top_k, collect, rep)
 
 
 def run_campaign_over_ranks(workload, seed0, total, batch=65536, stop_at_failure=True, config=None, limits=None, device_tensors=None, group=None,
