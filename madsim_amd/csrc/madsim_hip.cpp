@@ -915,10 +915,10 @@ uint64_t madsim_hip_stat_bucket_floor(uint32_t b) {
     return b >= 252 ? UINT64_MAX : (uint64_t)(4 + b % 4) << (b / 4 - 1);
 }
 
-namespace {
 // s = a batch's MADSIM_K_STATS_WORDS (sim_kernel.hip): batches are folded in seed order, but nothing here relies on it — count, min, max and
-// the sums commute, and the extreme seeds are merged under the total order (value descending, seed ascending).
-void fold_stats(madsim_stats_t* st, const unsigned long long* s) {
+// the sums commute, and the extreme seeds are merged under the total order (value descending, seed ascending).  Declared in sim_kernel.h
+// beside the launchers (not part of the public ABI): the tests feed it synthetic words without a device.
+extern "C" void madsim_k_fold_stats(madsim_stats_t* st, const unsigned long long* s) {
     const uint64_t n = s[0];
     if (!n) return;
     const uint32_t* hist = reinterpret_cast<const uint32_t*>(s + 17);
@@ -944,7 +944,6 @@ void fold_stats(madsim_stats_t* st, const unsigned long long* s) {
     st->n += n;
     st->n_top = keep;
 }
-}  // namespace
 
 // ---- campaigns -------------------------------------------------------------------------------------------------------------
 // One implementation for one context and for several (madsim_hip_run_campaign_multi): batch k of the range runs on context k % n,
@@ -1052,7 +1051,7 @@ int run_campaign_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workl
                 listed_seen += a[14];
                 if ((flags & MADSIM_CAMPAIGN_STOP_AT_CAP) && listed_seen >= col->cap) stop = true;
             }
-            if (st) fold_stats(st, a + 16);
+            if (st) madsim_k_fold_stats(st, a + 16);
         }
         return 0;
     };

@@ -320,6 +320,8 @@ void madsim_k_launch_collect(const madsim_result_t* out, uint64_t count, uint64_
 #define MADSIM_K_STATS_CAND_WORDS 32768u
 void madsim_k_launch_stats(const madsim_result_t* out, uint64_t count, uint64_t seed0, uint32_t include, uint32_t top_k, unsigned long long* srep,
                            unsigned long long* cand, void* stream);
+// the host fold of one batch's MADSIM_K_STATS_WORDS into the caller's statistics (madsim_hip.cpp; no device involved)
+void madsim_k_fold_stats(madsim_stats_t* st, const unsigned long long* s);
 int  madsim_k_set_max_lds(uint32_t lds_bytes);
 int  madsim_k_variant_vgprs(const madsim_k::VariantSel* v);
 void madsim_k_launch_keyflip(unsigned long long* acc, void* stream);

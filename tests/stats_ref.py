@@ -62,9 +62,11 @@ def stats_truth(results, seed0, include, top_k):
     for name in METRICS:
         v = results[name][idx].astype(np.uint64)
         order = np.lexsort((seeds, ~v))[:top_k]           # value descending, then seed ascending
+        # the sum as two half-sums in uint64 (exact below 2^32 seeds; tests/test_report_kernels.py holds it against plain Python ints)
+        halves = (int((v & np.uint64(0xffffffff)).sum(dtype=np.uint64)), int((v >> np.uint64(32)).sum(dtype=np.uint64)))
         out[name] = {
             "min": int(v.min()) if n else U64_MAX, "max": int(v.max()) if n else 0,
-            "sum": sum(int(x) for x in v.tolist()),
+            "sum": halves[0] + (halves[1] << 32), "halves": halves,
             "hist": np.bincount(buckets(v), minlength=N_BUCKETS).astype(np.uint64),
             "top": [(int(v[i]), int(seeds[i])) for i in order],
         }
