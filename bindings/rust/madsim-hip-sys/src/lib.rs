@@ -190,6 +190,28 @@ pub struct madsim_stats_t {
 
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
+pub struct madsim_group_t {
+    pub key: u64,
+    pub verdict: u32,
+    pub reserved: u32,
+    pub count: u64,
+    pub first_seed: u64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct madsim_groups_t {
+    pub include: u32,
+    pub key_field: u32,
+    pub groups: *const madsim_group_t,
+    pub cap: u64,
+    pub n_groups: u64,
+    pub n_grouped: u64,
+    pub n_ungrouped: u64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
 pub struct madsim_geometry_t {
     pub lds_bytes_per_seed: u32,
     pub lds_bytes_per_block: u32,
@@ -335,6 +357,15 @@ pub const MADSIM_STAT_RNG: u32 = 3;
 pub const MADSIM_STAT_METRICS: u32 = 4;
 pub const MADSIM_STAT_BUCKETS: u32 = 256;
 pub const MADSIM_STAT_MAX_TOP: u32 = 16;
+pub const MADSIM_GROUP_KEY_OBS: u32 = 0;
+pub const MADSIM_GROUP_KEY_TRACE: u32 = 1;
+pub const MADSIM_GROUP_KEY_MSGS: u32 = 2;
+pub const MADSIM_GROUP_KEY_CLOCK: u32 = 3;
+pub const MADSIM_GROUP_KEY_RNG: u32 = 4;
+pub const MADSIM_GROUP_KEY_STEPS: u32 = 5;
+pub const MADSIM_GROUP_KEYS: u32 = 6;
+pub const MADSIM_GROUP_MAX_BATCH: u32 = 1048576;
+pub const MADSIM_CAMPAIGN_STOP_AT_GROUPS: u32 = 8;
 
 #[link(name = "madsim_hip")]
 extern "C" {
@@ -373,6 +404,9 @@ extern "C" {
     pub fn madsim_hip_ctx_run_campaign_stats(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, batch: u64, in_flight: u32, flags: u32, lim: *const madsim_limits_t, out: *mut madsim_campaign_t, col: *mut madsim_collect_t, st: *mut madsim_stats_t) -> c_int;
     pub fn madsim_hip_run_campaign_stats(w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, batch: u64, in_flight: u32, flags: u32, lim: *const madsim_limits_t, out: *mut madsim_campaign_t, col: *mut madsim_collect_t, st: *mut madsim_stats_t) -> c_int;
     pub fn madsim_hip_run_campaign_stats_multi(ctxs: *const *mut madsim_hip_ctx_t, n_ctx: c_int, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, batch: u64, in_flight: u32, flags: u32, lim: *const madsim_limits_t, out: *mut madsim_campaign_t, col: *mut madsim_collect_t, st: *mut madsim_stats_t) -> c_int;
+    pub fn madsim_hip_ctx_run_campaign_groups(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, batch: u64, in_flight: u32, flags: u32, lim: *const madsim_limits_t, out: *mut madsim_campaign_t, col: *mut madsim_collect_t, st: *mut madsim_stats_t, grp: *mut madsim_groups_t) -> c_int;
+    pub fn madsim_hip_run_campaign_groups(w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, batch: u64, in_flight: u32, flags: u32, lim: *const madsim_limits_t, out: *mut madsim_campaign_t, col: *mut madsim_collect_t, st: *mut madsim_stats_t, grp: *mut madsim_groups_t) -> c_int;
+    pub fn madsim_hip_run_campaign_groups_multi(ctxs: *const *mut madsim_hip_ctx_t, n_ctx: c_int, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, batch: u64, in_flight: u32, flags: u32, lim: *const madsim_limits_t, out: *mut madsim_campaign_t, col: *mut madsim_collect_t, st: *mut madsim_stats_t, grp: *mut madsim_groups_t) -> c_int;
     pub fn madsim_hip_geometry(w: *const madsim_workload_t, lim: *const madsim_limits_t, g: *mut madsim_geometry_t) -> c_int;
     pub fn madsim_hip_debug_counters(out16: *mut u64) -> c_int;
     pub fn madsim_workload_pingpong(n_nodes: u32, rounds: u32, nodes: *mut madsim_node_t, progs: *mut madsim_prog_t, socks: *mut madsim_sock_t, insns: *mut madsim_insn_t, cap_insns: u32, w: *mut madsim_workload_t) -> c_int;

@@ -165,6 +165,16 @@ pub struct Stats {
     pub campaign: sys::madsim_campaign_t,
 }
 
+/// What `Builder::failure_groups` found: the failure modes in order of first appearance (ascending `first_seed`), the counted seeds
+/// they hold, the counted seeds of the modes that did not make the list, and the campaign report.
+#[derive(Clone, Debug)]
+pub struct Groups {
+    pub groups: Vec<sys::madsim_group_t>,
+    pub n_grouped: u64,
+    pub n_ungrouped: u64,
+    pub campaign: sys::madsim_campaign_t,
+}
+
 impl Builder {
     /// builder.rs:64-118: `MADSIM_TEST_SEED`, `MADSIM_TEST_NUM`, `MADSIM_TEST_JOBS`, `MADSIM_TEST_TIME_LIMIT`,
     /// `MADSIM_TEST_CHECK_DETERMINISM`, `MADSIM_ALLOW_SYSTEM_THREAD` (`MADSIM_TEST_CONFIG` is read by the caller: the TOML
@@ -294,6 +304,37 @@ impl Builder {
         let n_top = stats.n_top as usize;
         let rows: [Vec<sys::madsim_extreme_t>; 4] = std::array::from_fn(|m| top[m * k..m * k + n_top].to_vec());
         Ok(Stats { stats, top: rows, campaign })
+    }
+
+    /// Failure modes: HOW MANY DIFFERENT failures `self.seed .. self.seed + self.count` holds (`madsim_hip_run_campaign_groups`).
+    /// The seeds whose verdict bit is set in `include` (bits 0-3) are grouped by (verdict, key), `key_field` one of
+    /// `MADSIM_GROUP_KEY_*` (`MADSIM_GROUP_KEY_OBS`: `obs_hash`, what the test body traced); the first `max_groups` groups in order
+    /// of first appearance come back, each with its exact count over the range and its smallest seed — the one to replay.
+    pub fn failure_groups(&self, workload: &Workload, max_groups: usize, include: u32, key_field: u32) -> Result<Groups, RunError> {
+        let w = workload.raw();
+        let cfg = self.config.raw();
+        let lim = self.raw_limits(true);
+        let ctx = contexts()?.0[0];
+        let mut groups: Vec<sys::madsim_group_t> = vec![unsafe { std::mem::zeroed() }; max_groups];
+        let mut campaign: sys::madsim_campaign_t = unsafe { std::mem::zeroed() };
+        let mut grp = sys::madsim_groups_t {
+            include,
+            key_field,
+            groups: if max_groups > 0 { groups.as_mut_ptr() as *const _ } else { std::ptr::null() },   // (the library writes through it)
+            cap: max_groups as u64,
+            n_groups: 0,
+            n_grouped: 0,
+            n_ungrouped: 0,
+        };
+        let rc = unsafe {
+            sys::madsim_hip_ctx_run_campaign_groups(ctx, &w, &cfg, self.seed, self.count, 0, 0, 0, &lim, &mut campaign, std::ptr::null_mut(),
+                                                    std::ptr::null_mut(), &mut grp)
+        };
+        if rc != 0 {
+            return Err(last_error(rc));
+        }
+        groups.truncate(grp.n_groups as usize);
+        Ok(Groups { groups, n_grouped: grp.n_grouped, n_ungrouped: grp.n_ungrouped, campaign })
     }
 
     /// Same contract as `Builder::run` (builder.rs:121-162) for a test body registered as a workload: returns the per-seed

@@ -747,6 +747,64 @@ int madsim_hip_run_campaign_stats_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx
                                         uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim, madsim_campaign_t* out,
                                         madsim_collect_t* col, madsim_stats_t* st);
 
+/* ---- Failure-mode grouping: HOW MANY DIFFERENT failures there are, each with its size and a seed to replay -----------------
+ * The same campaign, with report kernels that group the COUNTED seeds of every batch by their SIGNATURE (verdict, key): `key` is one
+ * 64-bit field of madsim_result_t, obs_hash by default — FNV-1a over the MS_OP_TRACE values in execution order, so a test body that
+ * traces "which role / which phase" before it asserts or blocks names its failure modes.  A seed is counted when bit `verdict` is set
+ * in `include`; only bits 0-3 (PASS, PANIC, DEADLOCK, TIME_LIMIT) exist, as in madsim_stats_t.include: runner verdicts are never
+ * grouped.  Every 64-bit value is a key (0, 2^64 - 1 and the FNV offset basis — the obs_hash of a seed that traced nothing —
+ * included), and equal keys under different verdicts are different groups.
+ * groups[0 .. n_groups) are the first `cap` groups in order of first appearance: of all the groups of the prefix
+ * [seed0, seed0 + seeds_run), those with the smallest `first_seed`, ascending by `first_seed` (unique per group).  Each carries its
+ * exact `count` over the WHOLE prefix and its smallest seed.  n_grouped is the sum of the written counts, n_ungrouped the counted
+ * seeds that belong to none of the written groups: n_grouped + n_ungrouped is the number of counted seeds of the prefix.
+ * Everything is a function of the per-seed results of the prefix: the same bytes whatever `batch`, `in_flight` and the number of
+ * contexts, on every run; batches launched beyond a stopping one contribute nothing.  Per batch the number of its groups rides back
+ * with the report, and its entries (32 bytes per group of the batch) are copied only when there are some, and only that many.
+ * `out` is exactly the plain campaign's report.  `col` and `st` may be NULL; when given they are filled exactly as
+ * madsim_hip_run_campaign_collect / madsim_hip_run_campaign_stats fill them (their flags apply): one call, the whole triage report.
+ * MADSIM_CAMPAIGN_STOP_AT_GROUPS ("find me `cap` different failures"): stop launching once the batches read so far hold `cap` groups;
+ * seeds_run / batches_run / batches_launched follow the rules of MADSIM_CAMPAIGN_STOP_AT_FAILURE, and it may be combined with the
+ * other stop flags.  The other entry points ignore it.
+ * MADSIM_E_ARG: grp == NULL, include == 0 or a bit at or above 4, an unknown key_field, cap > 0 without `groups`, STOP_AT_GROUPS with
+ * cap == 0, min(batch, total) above MADSIM_GROUP_MAX_BATCH seeds (the device table is sized to the batch), and the collecting and
+ * statistics forms' own argument errors when `col` / `st` are given. */
+#define MADSIM_GROUP_KEY_OBS   0u /* madsim_result_t.obs_hash                  */
+#define MADSIM_GROUP_KEY_TRACE 1u /* madsim_result_t.trace_hash                */
+#define MADSIM_GROUP_KEY_MSGS  2u /* madsim_result_t.msg_count                 */
+#define MADSIM_GROUP_KEY_CLOCK 3u /* madsim_result_t.clock_ns                  */
+#define MADSIM_GROUP_KEY_RNG   4u /* madsim_result_t.rng_calls                 */
+#define MADSIM_GROUP_KEY_STEPS 5u /* madsim_result_t.steps, zero-extended      */
+#define MADSIM_GROUP_KEYS 6u
+#define MADSIM_GROUP_MAX_BATCH 1048576u /* 2^20 seeds per batch */
+typedef struct madsim_group {          /* 32 bytes */
+    uint64_t key;                      /* the grouped field's value (obs_hash by default)                                         */
+    uint32_t verdict, reserved;        /* reserved = 0                                                                            */
+    uint64_t count;                    /* counted seeds of [seed0, seed0 + seeds_run) in this group                               */
+    uint64_t first_seed;               /* the smallest of them                                                                    */
+} madsim_group_t;
+typedef struct madsim_groups {
+    uint32_t include;                  /* in: bit v set = group the seeds whose verdict is v (bits 0-3 only, as madsim_stats_t.include) */
+    uint32_t key_field;                /* in: MADSIM_GROUP_KEY_*                                                                  */
+    madsim_group_t* groups;            /* in: caller's host array [cap]; may be NULL when cap == 0                                */
+    uint64_t cap;
+    uint64_t n_groups;                 /* out: entries written                                                                    */
+    uint64_t n_grouped;                /* out: sum of the written entries' counts                                                 */
+    uint64_t n_ungrouped;              /* out: counted seeds that belong to none of the written groups                            */
+} madsim_groups_t;
+#define MADSIM_CAMPAIGN_STOP_AT_GROUPS 8u /* stop launching once `cap` groups have been read                                      */
+int madsim_hip_ctx_run_campaign_groups(madsim_hip_ctx_t* ctx, const madsim_workload_t* w, const madsim_config_t* cfg,
+                                       uint64_t seed0, uint64_t total, uint64_t batch, uint32_t in_flight, uint32_t flags,
+                                       const madsim_limits_t* lim, madsim_campaign_t* out, madsim_collect_t* col,
+                                       madsim_stats_t* st, madsim_groups_t* grp);
+int madsim_hip_run_campaign_groups(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total,
+                                   uint64_t batch, uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim,
+                                   madsim_campaign_t* out, madsim_collect_t* col, madsim_stats_t* st, madsim_groups_t* grp);
+int madsim_hip_run_campaign_groups_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_workload_t* w,
+                                         const madsim_config_t* cfg, uint64_t seed0, uint64_t total, uint64_t batch,
+                                         uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim, madsim_campaign_t* out,
+                                         madsim_collect_t* col, madsim_stats_t* st, madsim_groups_t* grp);
+
 /* Geometry the library picked for a workload (for DESIGN/bench reporting). */
 typedef struct madsim_geometry {
     uint32_t lds_bytes_per_seed;

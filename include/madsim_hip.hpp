@@ -554,6 +554,37 @@ struct Builder {
         return s;
     }
 
+    // Failure modes: HOW MANY DIFFERENT failures seed .. seed + count holds (madsim_hip_run_campaign_groups).  The whole range runs at the
+    // campaign's rate; the seeds whose verdict bit is set in `include` are grouped by (verdict, key), `key_field` one of MADSIM_GROUP_KEY_*
+    // (obs_hash by default: what the test body traced), and the first `max_groups` groups in order of first appearance come back, each with
+    // its exact count over the range and its smallest seed — the one to replay.
+    struct Groups {
+        std::vector<madsim_group_t> groups;                               // ascending by first_seed
+        uint64_t n_grouped = 0, n_ungrouped = 0;                          // counted seeds in `groups` / in the groups that did not make the list
+        madsim_campaign_t campaign{};
+    };
+    Groups failure_groups(const Workload& wl, size_t max_groups,
+                          uint32_t include = (1u << MADSIM_PANIC) | (1u << MADSIM_DEADLOCK) | (1u << MADSIM_TIME_LIMIT),
+                          uint32_t key_field = MADSIM_GROUP_KEY_OBS) const {
+        madsim::check(madsim_hip_init(device));
+        madsim_workload_t w = wl.raw();
+        madsim_config_t cfg = config.raw();
+        madsim_limits_t lim = capacities;
+        if (time_limit) { lim.time_limit_ns = (uint64_t)(*time_limit * 1e9 + 0.5); if (!lim.time_limit_ns) lim.time_limit_ns = 1; }
+        Groups g;
+        g.groups.resize(max_groups);
+        madsim_groups_t grp{};
+        grp.include = include;
+        grp.key_field = key_field;
+        grp.groups = max_groups ? g.groups.data() : nullptr;
+        grp.cap = max_groups;
+        madsim::check(madsim_hip_run_campaign_groups(&w, &cfg, seed, count, 0, 0, 0, &lim, &g.campaign, nullptr, nullptr, &grp));
+        g.groups.resize((size_t)grp.n_groups);
+        g.n_grouped = grp.n_grouped;
+        g.n_ungrouped = grp.n_ungrouped;
+        return g;
+    }
+
     // builder.rs:121-162: run seeds seed..seed+count; return on success, "panic" on the first failing seed.
     // Reports the numerically smallest failing seed (the reference reports the first to complete).
     std::vector<madsim_result_t> run(const Workload& wl) const {

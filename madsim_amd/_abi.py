@@ -172,6 +172,32 @@ def stat_bucket_floor(b):
     return U64_MAX if b >= 252 else (4 + b % 4) << (b // 4 - 1)
 
 
+CAMPAIGN_STOP_AT_GROUPS = 8   # grouping campaigns: stop launching once `cap` groups have been read
+GROUP_KEY_OBS, GROUP_KEY_TRACE, GROUP_KEY_MSGS, GROUP_KEY_CLOCK, GROUP_KEY_RNG, GROUP_KEY_STEPS = range(6)      # madsim_groups_t.key_field
+GROUP_KEYS = 6
+GROUP_KEY_NAMES = ("obs", "trace", "msgs", "clock", "rng", "steps")      # the `key=` names of runtime.run_campaign_groups, by key_field
+GROUP_KEY_FIELDS = ("obs_hash", "trace_hash", "msg_count", "clock_ns", "rng_calls", "steps")      # ... and the result field each one groups by
+GROUP_MAX_BATCH = 1 << 20
+
+
+class Group(C.Structure):
+    """madsim_group_t: one failure mode — the signature (verdict, key), how many counted seeds carry it, the smallest of them."""
+    _fields_ = [("key", C.c_uint64), ("verdict", C.c_uint32), ("reserved", C.c_uint32), ("count", C.c_uint64), ("first_seed", C.c_uint64)]
+
+
+class Groups(C.Structure):
+    """madsim_groups_t: which verdicts to group by which field and the caller's array going in, the groups and the two totals coming out."""
+    _fields_ = [("include", C.c_uint32), ("key_field", C.c_uint32), ("groups", C.POINTER(Group)), ("cap", C.c_uint64), ("n_groups", C.c_uint64),
+                ("n_grouped", C.c_uint64), ("n_ungrouped", C.c_uint64)]
+
+
+# numpy view of a grouping campaign's list: madsim_group_t
+GROUP_DTYPE = [("key", "<u8"), ("verdict", "<u4"), ("reserved", "<u4"), ("count", "<u8"), ("first_seed", "<u8")]
+assert C.sizeof(Group) == 32 and C.sizeof(Groups) == 48
+HEADER_STRUCTS["madsim_group_t"] = Group
+HEADER_STRUCTS["madsim_groups_t"] = Groups
+
+
 class Geometry(C.Structure):
     _fields_ = [
         ("lds_bytes_per_seed", C.c_uint32), ("lds_bytes_per_block", C.c_uint32), ("block_threads", C.c_uint32),

@@ -99,7 +99,13 @@ struct madsim_hip_ctx {
                     unsigned long long* d_rep = nullptr; unsigned long long* h_rep = nullptr; uint32_t* d_wcnt = nullptr;
                     madsim_failure_t* d_rec = nullptr; size_t rec_cap = 0;
                     // statistics campaigns only: 16 report words (summary6's or collect's) + MADSIM_K_STATS_WORDS (device, page-locked host), candidates
-                    unsigned long long* d_srep = nullptr; unsigned long long* h_srep = nullptr; unsigned long long* d_cand = nullptr; };
+                    unsigned long long* d_srep = nullptr; unsigned long long* h_srep = nullptr; unsigned long long* d_cand = nullptr;
+                    // grouping campaigns only: the 16 report words + the statistics words (used when asked for) + MADSIM_K_GROUP_WORDS (device,
+                    // page-locked host); the keyed table (zero between batches: grp_dirty = a batch was queued and never harvested), the list
+                    // of claimed slots and the batch's entries, sized for batches of grp_cap seeds
+                    unsigned long long* d_grep = nullptr; unsigned long long* h_grep = nullptr; uint32_t* d_gtab = nullptr; uint32_t* d_glist = nullptr;
+                    madsim_group_t* d_gent = nullptr; size_t grp_cap = 0; bool grp_dirty = false; };
+    static constexpr size_t GROUP_REP_WORDS = STATS_REP_WORDS + MADSIM_K_GROUP_WORDS;
     Flight flights[CAMPAIGN_MAX];
     unsigned long long* d_acc = nullptr;      // 4 x u64 summary accumulators
     madsim_result_t* d_out = nullptr; size_t out_cap = 0;
@@ -141,7 +147,7 @@ struct madsim_hip_ctx {
                  const madsim_limits_t* lim, madsim_result_t* out, madsim_summary_t* summary);
     int run_list(const madsim_workload_t* w, const madsim_config_t* cfg, const std::vector<uint64_t>& seeds,
                  const madsim_limits_t* lim, std::vector<madsim_result_t>& res, double* kernel_ms);
-    int ensure_flights(uint32_t n, uint64_t batch, bool staging, bool collect = false, uint64_t records = 0, bool stats = false);
+    int ensure_flights(uint32_t n, uint64_t batch, bool staging, bool collect = false, uint64_t records = 0, bool stats = false, uint64_t groups = 0);
     uint32_t flights_for(const madsim_workload_t* w, const madsim_config_t* cfg, const madsim_limits_t* lim, uint64_t batch);
 };
 
@@ -216,6 +222,11 @@ void madsim_hip_ctx::close() {
         if (f.d_srep) (void)hipFree(f.d_srep);
         if (f.h_srep) (void)hipHostFree(f.h_srep);
         if (f.d_cand) (void)hipFree(f.d_cand);
+        if (f.d_grep) (void)hipFree(f.d_grep);
+        if (f.h_grep) (void)hipHostFree(f.h_grep);
+        if (f.d_gtab) (void)hipFree(f.d_gtab);
+        if (f.d_glist) (void)hipFree(f.d_glist);
+        if (f.d_gent) (void)hipFree(f.d_gent);
         if (f.e0) (void)hipEventDestroy(f.e0);
         if (f.e1) (void)hipEventDestroy(f.e1);
         if (f.done) (void)hipEventDestroy(f.done);
@@ -447,8 +458,9 @@ int madsim_hip_ctx::run_list(const madsim_workload_t* w, const madsim_config_t* 
 // Streams, report words, events and result buffers of the first n flights (campaigns and run_pipelined share them; the
 // context's mutex serialises the two).  `staging`: also a page-locked host buffer of `batch` results per flight.  `collect`: also
 // the report words and wave counts of a collecting campaign and room for `records` failure records per flight.  `stats`: also the
-// report and candidate words of a statistics campaign.
-int madsim_hip_ctx::ensure_flights(uint32_t n, uint64_t batch, bool staging, bool collect, uint64_t records, bool stats) {
+// report and candidate words of a statistics campaign.  `groups` (seeds per batch, 0 = none): also the report words, the keyed table, the
+// slot list and the entry buffer of a grouping campaign — nothing of it exists for the other campaigns.
+int madsim_hip_ctx::ensure_flights(uint32_t n, uint64_t batch, bool staging, bool collect, uint64_t records, bool stats, uint64_t groups) {
     if (n > (uint32_t)CAMPAIGN_MAX) return fail(MADSIM_E_ARG, "at most 8 batches in flight");
     hint_hw_queues(n);
     for (uint32_t i = 0; i < n; i++) {
@@ -486,6 +498,23 @@ int madsim_hip_ctx::ensure_flights(uint32_t n, uint64_t batch, bool staging, boo
             HIP_TRY(hipMalloc(&f.d_srep, STATS_REP_WORDS * sizeof(unsigned long long)));
             HIP_TRY(hipHostMalloc((void**)&f.h_srep, STATS_REP_WORDS * sizeof(unsigned long long), hipHostMallocDefault));
             HIP_TRY(hipMalloc(&f.d_cand, MADSIM_K_STATS_CAND_WORDS * sizeof(unsigned long long)));
+        }
+        if (groups && !f.d_grep) {
+            HIP_TRY(hipMalloc(&f.d_grep, GROUP_REP_WORDS * sizeof(unsigned long long)));
+            HIP_TRY(hipHostMalloc((void**)&f.h_grep, GROUP_REP_WORDS * sizeof(unsigned long long), hipHostMallocDefault));
+        }
+        if (groups > f.grp_cap) {
+            if (f.d_gtab) { HIP_TRY(hipStreamSynchronize(f.stream)); (void)hipFree(f.d_gtab); (void)hipFree(f.d_glist); (void)hipFree(f.d_gent); }
+            f.d_gtab = nullptr; f.d_glist = nullptr; f.d_gent = nullptr; f.grp_cap = 0;
+            HIP_TRY(hipMalloc(&f.d_gtab, madsim_k_group_slots(groups) * MADSIM_K_GROUP_SLOT_BYTES));
+            HIP_TRY(hipMalloc(&f.d_glist, groups * sizeof(uint32_t)));
+            HIP_TRY(hipMalloc(&f.d_gent, groups * sizeof(madsim_group_t)));
+            f.grp_cap = groups; f.grp_dirty = true;
+        }
+        if (groups && f.grp_dirty) {             // a new table, or one that an error left between a batch's two passes: the only time it is cleared whole
+            HIP_TRY(hipMemsetAsync(f.d_gtab, 0, madsim_k_group_slots(f.grp_cap) * MADSIM_K_GROUP_SLOT_BYTES, f.stream));
+            HIP_TRY(hipStreamSynchronize(f.stream));
+            f.grp_dirty = false;
         }
     }
     return 0;
@@ -945,6 +974,49 @@ extern "C" void madsim_k_fold_stats(madsim_stats_t* st, const unsigned long long
     st->n_top = keep;
 }
 
+// ---- failure-mode grouping: table size, probe start and the host fold of a batch's entries ---------------------------------------
+extern "C" uint64_t madsim_k_group_slots(uint64_t count) {
+    uint64_t slots = MADSIM_K_GROUP_MIN_SLOTS;
+    while (slots < 2 * count) slots <<= 1;
+    return slots;
+}
+
+extern "C" uint64_t madsim_k_group_slot(uint64_t key, uint32_t verdict, uint64_t slots) { return madsim_k::group_slot(key, verdict, slots); }
+
+// Which signature sits at which index of the caller's list: only WRITTEN signatures are remembered, so the memory is bounded by `cap`.
+// Batches are folded in seed order and a batch's entries by first_seed: once the list is full, every signature not in it first appears
+// behind all the written ones, so "append while there is room, else count as ungrouped" yields exactly the `cap` groups of smallest
+// first_seed, each with the count of the whole prefix.
+namespace {
+struct GroupSig {
+    uint64_t key; uint32_t verdict;
+    bool operator==(const GroupSig& o) const { return key == o.key && verdict == o.verdict; }
+};
+struct GroupSigHash { size_t operator()(const GroupSig& s) const { return (size_t)madsim_k::group_slot(s.key, s.verdict, 0); } };   // (slots = 0: no mask)
+struct GroupState { std::unordered_map<GroupSig, uint64_t, GroupSigHash> at; std::vector<madsim_group_t> sorted; };
+}  // namespace
+
+extern "C" void* madsim_k_group_state_new(void) { return new GroupState; }
+extern "C" void madsim_k_group_state_free(void* state) { delete static_cast<GroupState*>(state); }
+
+extern "C" void madsim_k_fold_groups(madsim_groups_t* grp, void* state, const madsim_group_t* batch_entries, uint64_t n, uint64_t seed0_of_batch) {
+    GroupState& S = *static_cast<GroupState*>(state);
+    S.sorted.assign(batch_entries, batch_entries + n);
+    std::sort(S.sorted.begin(), S.sorted.end(), [seed0_of_batch](const madsim_group_t& a, const madsim_group_t& b) {
+        return a.first_seed - seed0_of_batch < b.first_seed - seed0_of_batch;      // the index in the batch: unique per group
+    });
+    for (const madsim_group_t& e : S.sorted) {
+        const GroupSig sig{e.key, e.verdict};
+        auto it = S.at.find(sig);
+        if (it != S.at.end()) { grp->groups[it->second].count += e.count; grp->n_grouped += e.count; continue; }
+        if (grp->n_groups < grp->cap) {
+            S.at.emplace(sig, grp->n_groups);
+            grp->groups[grp->n_groups++] = madsim_group_t{e.key, e.verdict, 0, e.count, e.first_seed};
+            grp->n_grouped += e.count;
+        } else grp->n_ungrouped += e.count;
+    }
+}
+
 // ---- campaigns -------------------------------------------------------------------------------------------------------------
 // One implementation for one context and for several (madsim_hip_run_campaign_multi): batch k of the range runs on context k % n,
 // on that context's flight (k / n) % in_flight — the devices advance through the seed space TOGETHER, so with
@@ -956,7 +1028,7 @@ extern "C" void madsim_k_fold_stats(madsim_stats_t* st, const unsigned long long
 namespace {
 int run_campaign_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total,
                       uint64_t batch, uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim, madsim_campaign_t* out,
-                      madsim_collect_t* col = nullptr, madsim_stats_t* st = nullptr) {
+                      madsim_collect_t* col = nullptr, madsim_stats_t* st = nullptr, madsim_groups_t* grp = nullptr) {
     auto t0 = std::chrono::steady_clock::now();
     memset(out, 0, sizeof *out);
     out->first_failing_seed = UINT64_MAX;
@@ -967,6 +1039,10 @@ int run_campaign_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workl
     }
     if (col) { col->n_listed = 0; memset(col->n_by_verdict, 0, sizeof col->n_by_verdict); }
     else flags &= ~(MADSIM_CAMPAIGN_LIST_RUNNER | MADSIM_CAMPAIGN_STOP_AT_CAP);      // (flags of the collecting form only)
+    if (grp) grp->n_groups = grp->n_grouped = grp->n_ungrouped = 0;
+    else flags &= ~MADSIM_CAMPAIGN_STOP_AT_GROUPS;                                   // (a flag of the grouping form only)
+    struct GroupStateOwner { void* p; ~GroupStateOwner() { if (p) madsim_k_group_state_free(p); } } gstate{grp ? madsim_k_group_state_new() : nullptr};
+    std::vector<madsim_group_t> gbatch;                          // a batch's entries, as the device left them
     int rc = madsim_geo::validate(w, cfg, &g_err);
     if (rc) return rc;
     if (batch == 0) batch = 65536;
@@ -976,6 +1052,9 @@ int run_campaign_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workl
     if (st && std::min(batch, total) >= 0xffffffffull) return fail(MADSIM_E_ARG, "a statistics campaign's batch holds fewer than 2^32 - 1 seeds");
     const uint64_t n_batches = (total + batch - 1) / batch, N = (uint64_t)n_ctx;
     const uint64_t rec_batch = col ? std::min(col->cap, std::min(batch, total)) : 0;      // records a flight holds: no batch lists more
+    // a grouping campaign's report: the sixteen words, the statistics words when asked for, then the grouping words; its table is sized to the batch
+    const size_t goff = 16 + (st ? MADSIM_K_STATS_WORDS : 0);
+    const uint64_t gslots = grp ? madsim_k_group_slots(std::min(batch, total)) : 0;
     uint64_t listed_seen = 0;                                   // listed seeds of the batches folded so far (not cut at cap)
     std::vector<uint32_t> F(n_ctx);                             // flights per context: what its occupancy rewards, no more than it has batches
     for (int g = 0; g < n_ctx; g++) {
@@ -984,7 +1063,7 @@ int run_campaign_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workl
         uint32_t f = in_flight ? in_flight : ctxs[g]->flights_for(w, cfg, lim, batch);
         if ((uint64_t)f > mine) f = (uint32_t)mine;
         F[g] = f;
-        if (f && (rc = ctxs[g]->ensure_flights(f, batch, false, col != nullptr, rec_batch, st != nullptr))) return rc;
+        if (f && (rc = ctxs[g]->ensure_flights(f, batch, false, col != nullptr, rec_batch, st != nullptr, grp ? std::min(batch, total) : 0))) return rc;
     }
     int first_err = 0;
     std::string first_msg;
@@ -996,9 +1075,10 @@ int run_campaign_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workl
         int e;
         if ((e = c->bind())) return e;
         // the same four memsets, the last one longer when collecting, and longer still with statistics (whose words all start as zero)
-        unsigned long long* const d_words = st ? f.d_srep : col ? f.d_rep : f.d_acc6;
-        const size_t n_words = st ? madsim_hip_ctx::STATS_REP_WORDS - (st->top_k ? 0 : 2 * MADSIM_STAT_METRICS * MADSIM_STAT_MAX_TOP)
-                                  : col ? MADSIM_K_COLLECT_WORDS : 6;
+        unsigned long long* const d_words = grp ? f.d_grep : st ? f.d_srep : col ? f.d_rep : f.d_acc6;
+        const size_t n_words = grp ? goff + MADSIM_K_GROUP_WORDS
+                                   : st ? madsim_hip_ctx::STATS_REP_WORDS - (st->top_k ? 0 : 2 * MADSIM_STAT_METRICS * MADSIM_STAT_MAX_TOP)
+                                   : col ? MADSIM_K_COLLECT_WORDS : 6;
         HIP_TRY(hipMemsetAsync(d_words, 0xff, 8, f.stream));
         HIP_TRY(hipMemsetAsync((char*)d_words + 8, 0, 24, f.stream));
         HIP_TRY(hipMemsetAsync((char*)d_words + 32, 0xff, 8, f.stream));
@@ -1011,10 +1091,16 @@ int run_campaign_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workl
         else madsim_k_launch_summary6(f.d_out, n, seed0 + lo, d_words, f.stream);
         HIP_TRY(hipGetLastError());
         if (st) {                                                // behind the report kernel, into the words after its sixteen
-            madsim_k_launch_stats(f.d_out, n, seed0 + lo, st->include, st->top_k, f.d_srep + 16, f.d_cand, f.stream);
+            madsim_k_launch_stats(f.d_out, n, seed0 + lo, st->include, st->top_k, d_words + 16, f.d_cand, f.stream);
             HIP_TRY(hipGetLastError());
         }
-        HIP_TRY(hipMemcpyAsync(st ? f.h_srep : col ? f.h_rep : f.h_acc6, d_words, n_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, f.stream));
+        if (grp) {                                               // behind them: the batch's groups; their number rides with the report words
+            f.grp_dirty = true;                                  // (until the batch is harvested: its extraction pass has then left the table zero)
+            if (madsim_k_launch_groups(f.d_out, n, seed0 + lo, grp->include, grp->key_field, f.d_gtab, gslots, f.d_glist, d_words + goff, f.d_gent, f.stream))
+                return fail(MADSIM_E_ARG, "madsim_k_launch_groups refused the batch's sizes");
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipMemcpyAsync(grp ? f.h_grep : st ? f.h_srep : col ? f.h_rep : f.h_acc6, d_words, n_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, f.stream));
         HIP_TRY(hipEventRecord(f.done, f.stream));
         return 0;
     };
@@ -1025,12 +1111,13 @@ int run_campaign_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workl
         int e;
         if ((e = c->bind())) return e;
         HIP_TRY(hipEventSynchronize(f.done));
+        f.grp_dirty = false;                                    // (both grouping passes of the batch, if any, have run)
         if (first_err) return 0;                                // (draining after an error: nothing is folded any more)
         const uint64_t lo = k * batch, n = std::min(batch, total - lo);
         float ms = 0.f;
         HIP_TRY(hipEventElapsedTime(&ms, f.e0, f.e1));
         if (!stop) {                                            // batches launched beyond the failing one are not part of the answer
-            const unsigned long long* a = st ? f.h_srep : col ? f.h_rep : f.h_acc6;
+            const unsigned long long* a = grp ? f.h_grep : st ? f.h_srep : col ? f.h_rep : f.h_acc6;
             out->kernel_ms += ms;
             out->batches_run++; out->seeds_run += n;
             out->n_runner += a[5];
@@ -1052,6 +1139,19 @@ int run_campaign_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workl
                 if ((flags & MADSIM_CAMPAIGN_STOP_AT_CAP) && listed_seen >= col->cap) stop = true;
             }
             if (st) madsim_k_fold_stats(st, a + 16);
+            if (grp) {
+                const uint64_t ng = a[goff];
+                if (a[goff + 1] || ng > n)
+                    return fail(MADSIM_E_HIP, "grouping: a probe of the batch's group table ran out, or the table was not clean (error word " +
+                                                  std::to_string(a[goff + 1]) + ", " + std::to_string(ng) + " groups)");
+                if (ng) {                                       // the batch's entries, only when there are some and only that many (the stream is idle)
+                    gbatch.resize(ng);
+                    HIP_TRY(hipMemcpyAsync(gbatch.data(), f.d_gent, ng * sizeof(madsim_group_t), hipMemcpyDeviceToHost, f.stream));
+                    HIP_TRY(hipStreamSynchronize(f.stream));
+                    madsim_k_fold_groups(grp, gstate.p, gbatch.data(), ng, seed0 + lo);
+                }
+                if ((flags & MADSIM_CAMPAIGN_STOP_AT_GROUPS) && grp->n_groups >= grp->cap) stop = true;
+            }
         }
         return 0;
     };
@@ -1179,6 +1279,52 @@ int madsim_hip_run_campaign_stats_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx
     return run_campaign_impl(ctxs, n_ctx, w, cfg, seed0, total, batch, in_flight, flags, lim, out, col, st);
 }
 
+// The grouping forms: argument errors first, as the collecting and statistics forms.
+namespace {
+int check_groups_args(const madsim_campaign_t* out, const madsim_collect_t* col, const madsim_stats_t* st, const madsim_groups_t* grp, uint64_t total,
+                      uint64_t batch, uint32_t in_flight, uint32_t flags) {
+    if (!out) return fail(MADSIM_E_ARG, "null campaign report");
+    if (!grp) return fail(MADSIM_E_ARG, "null madsim_groups_t");
+    if (grp->include == 0 || (grp->include & ~0xfu)) return fail(MADSIM_E_ARG, "madsim_groups_t.include: at least one of bits 0-3 (PASS, PANIC, DEADLOCK, TIME_LIMIT), no other");
+    if (grp->key_field >= MADSIM_GROUP_KEYS) return fail(MADSIM_E_ARG, "madsim_groups_t.key_field: one of MADSIM_GROUP_KEY_*");
+    if (grp->cap && !grp->groups) return fail(MADSIM_E_ARG, "madsim_groups_t.cap > 0 without a groups array");
+    if ((flags & MADSIM_CAMPAIGN_STOP_AT_GROUPS) && !grp->cap) return fail(MADSIM_E_ARG, "MADSIM_CAMPAIGN_STOP_AT_GROUPS with cap == 0");
+    if (std::min(batch ? batch : 65536, total) > MADSIM_GROUP_MAX_BATCH)
+        return fail(MADSIM_E_ARG, "a grouping campaign's batch holds at most MADSIM_GROUP_MAX_BATCH (2^20) seeds: the device table is sized to the batch");
+    if (st) return check_stats_args(out, col, st, in_flight, flags);
+    if (col) return check_collect_args(out, col, in_flight, flags);
+    if (in_flight > (uint32_t)madsim_hip_ctx::CAMPAIGN_MAX) return fail(MADSIM_E_ARG, "at most 8 batches in flight per context");
+    return 0;
+}
+}  // namespace
+
+int madsim_hip_ctx_run_campaign_groups(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total,
+                                       uint64_t batch, uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim, madsim_campaign_t* out,
+                                       madsim_collect_t* col, madsim_stats_t* st, madsim_groups_t* grp) {
+    if (int rc = check_groups_args(out, col, st, grp, total, batch, in_flight, flags)) return rc;
+    CTX_ENTER(c);
+    madsim_hip_ctx* one[1] = {c};
+    return run_campaign_impl(one, 1, w, cfg, seed0, total, batch, in_flight, flags, lim, out, col, st, grp);
+}
+
+int madsim_hip_run_campaign_groups_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_workload_t* w, const madsim_config_t* cfg,
+                                         uint64_t seed0, uint64_t total, uint64_t batch, uint32_t in_flight, uint32_t flags,
+                                         const madsim_limits_t* lim, madsim_campaign_t* out, madsim_collect_t* col, madsim_stats_t* st,
+                                         madsim_groups_t* grp) {
+    if (int rc = check_groups_args(out, col, st, grp, total, batch, in_flight, flags)) return rc;
+    if (!ctxs || n_ctx < 1) return fail(MADSIM_E_ARG, "run_campaign_groups_multi needs at least one context");
+    for (int g = 0; g < n_ctx; g++) {
+        if (!ctxs[g]) return fail(MADSIM_E_NOINIT, "null context");
+        for (int h = 0; h < g; h++) if (ctxs[h] == ctxs[g]) return fail(MADSIM_E_ARG, "the same context appears twice");
+    }
+    std::vector<madsim_hip_ctx*> order(ctxs, ctxs + n_ctx);      // locks in address order (see madsim_hip_run_batch_multi)
+    std::sort(order.begin(), order.end(), [](madsim_hip_ctx* a, madsim_hip_ctx* b) { return std::less<madsim_hip_ctx*>()(a, b); });
+    std::vector<std::unique_lock<std::mutex>> locks;
+    for (madsim_hip_ctx* c : order) locks.emplace_back(c->mu);
+    for (int g = 0; g < n_ctx; g++) if (ctxs[g]->device < 0) return fail(MADSIM_E_NOINIT, "closed context");
+    return run_campaign_impl(ctxs, n_ctx, w, cfg, seed0, total, batch, in_flight, flags, lim, out, col, st, grp);
+}
+
 // ---- v1 entry points: wrappers on the process-default context ------------------------------------------------------------
 // The default context is reference-counted by its users: a wrapper pins it under g_default_mu for the duration of its call,
 // and madsim_hip_shutdown waits until no call is inside before destroying it — a concurrent run_batch and shutdown is a
@@ -1266,6 +1412,13 @@ int madsim_hip_run_campaign_stats(const madsim_workload_t* w, const madsim_confi
                                   madsim_stats_t* st) {
     DefaultPin p;
     return madsim_hip_ctx_run_campaign_stats(p.c, w, cfg, seed0, total, batch, in_flight, flags, lim, out, col, st);
+}
+
+int madsim_hip_run_campaign_groups(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total, uint64_t batch,
+                                   uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim, madsim_campaign_t* out, madsim_collect_t* col,
+                                   madsim_stats_t* st, madsim_groups_t* grp) {
+    DefaultPin p;
+    return madsim_hip_ctx_run_campaign_groups(p.c, w, cfg, seed0, total, batch, in_flight, flags, lim, out, col, st, grp);
 }
 
 int madsim_hip_geometry(const madsim_workload_t* w, const madsim_limits_t* lim, madsim_geometry_t* out) {

@@ -302,6 +302,16 @@ inline const char* variant_mismatch(const KParams& P, const VariantSel& v, bool 
     return nullptr;
 }
 
+// Grouping campaigns: where the signature (key, verdict) starts probing in a table of `slots` (a power of two) slots — splitmix64's finalizer
+// over the key offset by the verdict, so equal keys under different verdicts start apart.  constexpr: one definition for the device
+// (group_fold_kernel) and the host (madsim_k_group_slot, with which the tests construct colliding keys).
+inline constexpr uint64_t group_slot(uint64_t key, uint32_t verdict, uint64_t slots) {
+    uint64_t h = key + ((uint64_t)verdict + 1u) * 0x9E3779B97F4A7C15ull;
+    h = (h ^ (h >> 30)) * 0xBF58476D1CE4E5B9ull;
+    h = (h ^ (h >> 27)) * 0x94D049BB133111EBull;
+    return (h ^ (h >> 31)) & (slots - 1);
+}
+
 }  // namespace madsim_k
 
 extern "C" {
@@ -322,6 +332,28 @@ void madsim_k_launch_stats(const madsim_result_t* out, uint64_t count, uint64_t 
                            unsigned long long* cand, void* stream);
 // the host fold of one batch's MADSIM_K_STATS_WORDS into the caller's statistics (madsim_hip.cpp; no device involved)
 void madsim_k_fold_stats(madsim_stats_t* st, const unsigned long long* s);
+// the grouping campaign's report kernels, behind summary6 / collect / stats on the same stream: the distinct (verdict, key) among the batch's
+// counted seeds, each with its count and its smallest seed.  `table`: `slots` (a power of two, >= 2 * count and >= MADSIM_K_GROUP_MIN_SLOTS)
+// slots of MADSIM_K_GROUP_SLOT_BYTES, ALL ZERO before the launch and all zero again after it (the extraction pass resets the slots it
+// reads); `list`: count 32-bit words of scratch (the claimed slots, in arrival order); `grep`: MADSIM_K_GROUP_WORDS words, zero before the
+// launch: {groups of the batch, error word: non-zero = a probe ran out or met a slot that no seed of the batch can have claimed};
+// `entries`: room for `count` madsim_group_t, the first grep[0] written, in arrival order — the host sorts them.  count <= 2^20.
+#define MADSIM_K_GROUP_WORDS 2u         /* 64-bit words of a batch's grouping report      */
+#define MADSIM_K_GROUP_SLOT_BYTES 16u   /* {tag, count, ~smallest index, 0}               */
+#define MADSIM_K_GROUP_MIN_SLOTS 128u   /* a table is never smaller                       */
+#define MADSIM_K_GROUP_MAX_COUNT 1048576u /* = MADSIM_GROUP_MAX_BATCH                      */
+// Returns 0, or -1 without launching anything when a size is outside what the kernels are written for.
+int  madsim_k_launch_groups(const madsim_result_t* out, uint64_t count, uint64_t seed0, uint32_t include, uint32_t key_field, uint32_t* table,
+                            uint64_t slots, uint32_t* list, unsigned long long* grep, madsim_group_t* entries, void* stream);
+// the smallest table madsim_k_launch_groups accepts for `count` seeds (madsim_hip.cpp; no device involved)
+uint64_t madsim_k_group_slots(uint64_t count);
+// the slot at which a (key, verdict) starts probing in a table of `slots` slots (a power of two); probing goes on at slot + 1, wrapping
+uint64_t madsim_k_group_slot(uint64_t key, uint32_t verdict, uint64_t slots);
+// the host fold of one batch's entries into the caller's groups (madsim_hip.cpp; no device involved): batches in seed order, the entries of a
+// batch in any order (sorted here by first_seed - seed0_of_batch, their index in the batch).  `state` remembers which signature sits where.
+void* madsim_k_group_state_new(void);
+void  madsim_k_group_state_free(void* state);
+void  madsim_k_fold_groups(madsim_groups_t* grp, void* state, const madsim_group_t* batch_entries, uint64_t n, uint64_t seed0_of_batch);
 int  madsim_k_set_max_lds(uint32_t lds_bytes);
 int  madsim_k_variant_vgprs(const madsim_k::VariantSel* v);
 void madsim_k_launch_keyflip(unsigned long long* acc, void* stream);

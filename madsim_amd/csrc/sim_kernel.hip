@@ -365,6 +365,106 @@ __global__ __launch_bounds__(256) void stats_top_kernel(const unsigned long long
     }
 }
 
+// ---- the grouping campaign form: the distinct signatures (verdict, key) of the batch's counted seeds, each with its count and its smallest seed ----
+// Two kernels behind the batch's other report kernels, over collect's cut of the batch.  A seed is COUNTED as in stats_fold_kernel (bit
+// `verdict` of `include`, bits 0-3 only); its key is one 8-byte word of its result (key_word 1 .. 5; 0 = steps, which the verdict word holds
+// already): 16 + 8 bytes are read per counted seed, 16 per other seed.
+// The table in global memory has `mask + 1` slots (a power of two, >= 2 x the batch: load <= 0.5) of {tag, count, ~smallest index, 0}, all
+// zero between launches.  A slot's TAG is 1 + the batch index of the seed that claimed it, and the slot's signature is THAT SEED's, read from
+// the result array — which nobody writes while these kernels run.  So a slot is complete the moment its tag is set: every 64-bit value is a
+// legal key, one 32-bit compare-and-swap claims, and nobody ever waits for a "ready" word.  count and the smallest index (kept inverted, so
+// that zero is neutral) follow by atomicAdd / atomicMax.  Linear probing from group_slot(), wrapping, bounded by the slot count; a probe
+// that runs out, or a tag no seed of the batch can have written, sets the error word (grep[1]) instead of reading out of bounds.
+// Equal signatures are combined inside the wave first: a wave-uniform loop takes the first remaining counted lane, ballots the lanes
+// that share its signature and leaves that lane the popcount; then the leaders — one per distinct signature of the round, all at once —
+// insert.  Lanes hold ascending seeds, so a leader's index is its signature's smallest of the round.  "600 deadlocks, all one signature" is
+// one add and one max per wave that holds any; a round without a counted seed (wave-uniform) touches nothing.
+// Every successful claim appends its slot to `list` (position: one atomicAdd on grep[0], the batch's number of groups).
+// group_extract_kernel walks the list: entry j = {key, verdict, count, seed0 + smallest index} of slot list[j], and the slot is zeroed
+// again — work proportional to the groups, never to the table.  Arrival order places the entries; the host sorts them (madsim_k_fold_groups).
+constexpr uint32_t GROUP_ERR_PROBE = 1, GROUP_ERR_TAG = 2, GROUP_ERR_LIST = 4;
+
+__device__ __forceinline__ unsigned long long group_key(const madsim_result_t* __restrict__ r, uint32_t key_word) {
+    return key_word ? reinterpret_cast<const unsigned long long*>(r)[key_word] : (unsigned long long)reinterpret_cast<const uint32_t*>(r)[1];
+}
+
+// the calling lane's `cnt` seeds of signature (v, key), the smallest of them batch index i
+__device__ __forceinline__ void group_insert(const madsim_result_t* __restrict__ out, uint32_t count, uint32_t key_word, uint4* __restrict__ table,
+                                             uint32_t mask, uint32_t* __restrict__ list, unsigned long long* __restrict__ grep,
+                                             unsigned long long key, uint32_t v, uint32_t cnt, uint32_t i) {
+    uint32_t s = (uint32_t)group_slot(key, v, (uint64_t)mask + 1u);
+    for (uint32_t probe = 0; probe <= mask; probe++, s = (s + 1u) & mask) {
+        uint32_t* const slot = reinterpret_cast<uint32_t*>(table + s);
+        uint32_t tag = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // (a tag only ever goes from 0 to its value)
+        if (tag == 0) {
+            tag = atomicCAS(slot, 0u, i + 1u);
+            if (tag == 0) {                                                        // claimed: the slot's signature is this seed's
+                const unsigned long long pos = atomicAdd(&grep[0], 1ull);
+                if (pos < count) list[pos] = s; else atomicOr(&grep[1], (unsigned long long)GROUP_ERR_LIST);
+                tag = i + 1u;
+            }
+        }
+        bool match = tag == i + 1u;
+        if (!match) {
+            const uint32_t rep = tag - 1u;
+            if (rep >= count) { atomicOr(&grep[1], (unsigned long long)GROUP_ERR_TAG); return; }       // (a table that was not clean)
+            match = reinterpret_cast<const uint32_t*>(out + rep)[0] == v && group_key(out + rep, key_word) == key;
+        }
+        if (match) { atomicAdd(slot + 1, cnt); atomicMax(slot + 2, ~i); return; }
+    }
+    atomicOr(&grep[1], (unsigned long long)GROUP_ERR_PROBE);                       // (cannot happen at load <= 0.5)
+}
+
+__global__ __launch_bounds__(256) void group_fold_kernel(const madsim_result_t* __restrict__ out, uint32_t count, uint32_t piece, uint32_t include,
+                                                         uint32_t key_word, uint4* __restrict__ table, uint32_t mask, uint32_t* __restrict__ list,
+                                                         unsigned long long* __restrict__ grep) {
+    const uint32_t W = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const uint64_t lo = (uint64_t)W * piece, hi = lo + piece < count ? lo + piece : count;
+    for (uint64_t base = lo; base < hi; base += 64) {
+        const uint64_t i = base + lane;
+        uint32_t v = ~0u, steps = 0;
+        if (i < hi) { const uint4 r = reinterpret_cast<const uint4*>(out + i)[0]; v = r.x; steps = r.y; }
+        const bool counted = v < 4u && ((include >> v) & 1u);
+        unsigned long long m = __ballot(counted);
+        if (!m) continue;                                                          // (wave-uniform: a batch with nothing counted ends here)
+        unsigned long long key = 0;
+        if (counted) key = key_word ? reinterpret_cast<const unsigned long long*>(out + i)[key_word] : (unsigned long long)steps;
+        uint32_t cnt = 0;                                                          // non-zero in the leaders
+        while (m) {                                                                // (wave-uniform) one trip per distinct signature of the round
+            const int l = __ffsll((long long)m) - 1;
+            const unsigned long long lk = __shfl(key, l);
+            const uint32_t lv = __shfl(v, l);
+            const unsigned long long sm = __ballot(counted && key == lk && v == lv);      // a subset of m: lane l's signature is none of the earlier leaders'
+            if ((int)lane == l) cnt = (uint32_t)__popcll(sm);
+            m &= ~sm;
+        }
+        if (cnt) group_insert(out, count, key_word, table, mask, list, grep, key, v, cnt, (uint32_t)i);
+    }
+}
+
+__global__ __launch_bounds__(256) void group_extract_kernel(const madsim_result_t* __restrict__ out, uint32_t count, uint64_t seed0, uint32_t key_word,
+                                                            uint4* __restrict__ table, uint32_t mask, const uint32_t* __restrict__ list,
+                                                            unsigned long long* __restrict__ grep, madsim_group_t* __restrict__ entries) {
+    const unsigned long long claimed = grep[0];                                    // (nobody adds to it in this kernel)
+    const uint32_t n = claimed < count ? (uint32_t)claimed : count;
+    for (uint32_t j = blockIdx.x * 256u + threadIdx.x; j < n; j += gridDim.x * 256u) {
+        const uint32_t s = list[j] & mask;
+        const uint4 e = table[s];
+        table[s] = uint4{0, 0, 0, 0};
+        const uint32_t rep = e.x - 1u, first = ~e.z;
+        unsigned long long* const p = reinterpret_cast<unsigned long long*>(entries + j);
+        if (e.x == 0 || rep >= count || first >= count) {                          // (a table that was not clean)
+            atomicOr(&grep[1], (unsigned long long)GROUP_ERR_TAG);
+            p[0] = p[1] = p[2] = p[3] = 0;
+            continue;
+        }
+        p[0] = group_key(out + rep, key_word);
+        p[1] = reinterpret_cast<const uint32_t*>(out + rep)[0];                    // verdict, reserved = 0
+        p[2] = e.y;
+        p[3] = seed0 + first;
+    }
+}
+
 __global__ void keyflip_kernel(unsigned long long* acc) { acc[0] ^= 0x8000000000000000ull; }
 
 // one kernel per row of variant_table (sim_kernel.h), same macro, same order
@@ -429,6 +529,27 @@ extern "C" void madsim_k_launch_stats(const madsim_result_t* out, uint64_t count
     if (top_k)
         hipLaunchKernelGGL(madsim_k::stats_top_kernel, dim3(MADSIM_STAT_METRICS), dim3(256), 0, (hipStream_t)stream, (const unsigned long long*)cand, grid,
                            top_k, seed0, srep + 17 + MADSIM_STAT_METRICS * MADSIM_STAT_BUCKETS / 2);
+}
+
+// table: `slots` zeroed slots; list: `count` words of scratch; grep: MADSIM_K_GROUP_WORDS zeroed words; entries: room for `count` (sim_kernel.h).
+// Returns 0, or -1 (nothing launched) for sizes the kernels are not written for.
+extern "C" int madsim_k_launch_groups(const madsim_result_t* out, uint64_t count, uint64_t seed0, uint32_t include, uint32_t key_field, uint32_t* table,
+                                      uint64_t slots, uint32_t* list, unsigned long long* grep, madsim_group_t* entries, void* stream) {
+    static_assert(sizeof(madsim_group_t) == 32 && sizeof(uint4) == MADSIM_K_GROUP_SLOT_BYTES && sizeof(madsim_result_t) == 48, "record layout");
+    static_assert(MADSIM_K_GROUP_MAX_COUNT == MADSIM_GROUP_MAX_BATCH && MADSIM_GROUP_KEYS == 6, "sim_kernel.h");
+    static const uint32_t key_words[MADSIM_GROUP_KEYS] = {5, 4, 2, 1, 3, 0};      // obs_hash, trace_hash, msg_count, clock_ns, rng_calls; steps
+    if (count == 0 || count > MADSIM_K_GROUP_MAX_COUNT || key_field >= MADSIM_GROUP_KEYS || include == 0 || (include & ~0xfu)) return -1;
+    if ((slots & (slots - 1)) || slots < 2 * count || slots < MADSIM_K_GROUP_MIN_SLOTS || slots > (1ull << 31)) return -1;
+    uint32_t grid = (uint32_t)((count + 1023) / 1024);     // collect's cut
+    if (grid > 256) grid = 256;
+    const uint64_t waves = 4ull * grid, piece = ((count + waves - 1) / waves + 63) / 64 * 64;
+    hipLaunchKernelGGL(madsim_k::group_fold_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, out, (uint32_t)count, (uint32_t)piece, include,
+                       key_words[key_field], reinterpret_cast<uint4*>(table), (uint32_t)(slots - 1), list, grep);
+    uint32_t xgrid = (uint32_t)((count + 255) / 256);      // the extraction pass: as many threads as there can be groups, 64 workgroups at most
+    if (xgrid > 64) xgrid = 64;
+    hipLaunchKernelGGL(madsim_k::group_extract_kernel, dim3(xgrid), dim3(256), 0, (hipStream_t)stream, out, (uint32_t)count, seed0, key_words[key_field],
+                       reinterpret_cast<uint4*>(table), (uint32_t)(slots - 1), (const uint32_t*)list, grep, entries);
+    return 0;
 }
 
 extern "C" void madsim_k_launch_keyflip(unsigned long long* acc, void* stream) {

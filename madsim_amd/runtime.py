@@ -123,6 +123,9 @@ def lib():
         L.madsim_hip_run_campaign_stats.argtypes = L.madsim_hip_run_campaign_collect.argtypes + [C.POINTER(A.Stats)]
         L.madsim_hip_ctx_run_campaign_stats.argtypes = [ctxp] + L.madsim_hip_run_campaign_stats.argtypes
         L.madsim_hip_run_campaign_stats_multi.argtypes = [C.POINTER(ctxp), C.c_int] + L.madsim_hip_run_campaign_stats.argtypes
+        L.madsim_hip_run_campaign_groups.argtypes = L.madsim_hip_run_campaign_stats.argtypes + [C.POINTER(A.Groups)]
+        L.madsim_hip_ctx_run_campaign_groups.argtypes = [ctxp] + L.madsim_hip_run_campaign_groups.argtypes
+        L.madsim_hip_run_campaign_groups_multi.argtypes = [C.POINTER(ctxp), C.c_int] + L.madsim_hip_run_campaign_groups.argtypes
         if L.madsim_hip_version() != A.ABI_VERSION:
             raise MadsimHipError("libmadsim_hip.so ABI version mismatch")
         # build identity: MADSIM_HIP_LIB may name an A/B build of THIS library (tools/build_variant.sh), nothing else — an
@@ -206,9 +209,9 @@ def run_batch_auto(workload, seed0, count, config=None, limits=None, max_rounds=
     return out, summ
 
 
-def _campaign_flags(stop_at_failure, list_runner=False, stop_at_cap=False):
+def _campaign_flags(stop_at_failure, list_runner=False, stop_at_cap=False, stop_at_groups=False):
     return (A.CAMPAIGN_STOP_AT_FAILURE if stop_at_failure else 0) | (A.CAMPAIGN_LIST_RUNNER if list_runner else 0) \
-        | (A.CAMPAIGN_STOP_AT_CAP if stop_at_cap else 0)
+        | (A.CAMPAIGN_STOP_AT_CAP if stop_at_cap else 0) | (A.CAMPAIGN_STOP_AT_GROUPS if stop_at_groups else 0)
 
 
 def _collecting(call, collect):
@@ -320,6 +323,63 @@ def run_campaign_stats(workload, seed0, total, batch=0, in_flight=0, stop_at_fai
         workload.ref(), C.byref(cfg), seed0, total, batch, in_flight, flags, C.byref(lim), C.byref(rep), col, st), include, top_k, collect, rep)
 
 
+class CampaignGroups:
+    """What a grouping campaign (madsim_hip_run_campaign_groups) says about the counted seeds of the prefix that ran: `groups`, an
+    ndarray[GROUP_DTYPE] of the first max_groups failure modes in order of first appearance — key, verdict, count over the whole prefix,
+    first_seed —, `n_grouped` (the sum of their counts) and `n_ungrouped` (counted seeds of modes that did not make the list)."""
+
+    def __init__(self, grp, groups):
+        self.include, self.key_field, self.max_groups = int(grp.include), int(grp.key_field), int(grp.cap)
+        self.key = A.GROUP_KEY_NAMES[self.key_field]
+        self.groups = groups[:grp.n_groups].copy()
+        self.n_grouped, self.n_ungrouped = int(grp.n_grouped), int(grp.n_ungrouped)
+
+    def __len__(self):
+        return len(self.groups)
+
+    def __iter__(self):
+        """(verdict, key, count, first_seed) per group, as Python ints."""
+        return iter([(int(g["verdict"]), int(g["key"]), int(g["count"]), int(g["first_seed"])) for g in self.groups])
+
+
+def _campaign_groups(call, include, key, max_groups, collect, stats, rep):
+    """Run `call(col, st, grp)` — one of the madsim_hip_*run_campaign_groups* entry points with everything but its last three arguments bound.
+    `stats`: None, or (include, top_k) of the statistics to take in the same call."""
+    mask = _include_mask(include)
+    if key not in A.GROUP_KEY_NAMES or not mask or max_groups < 0:
+        raise MadsimHipError(f"run_campaign_groups: include must name a verdict, key be one of {A.GROUP_KEY_NAMES}, max_groups >= 0")
+    arr = np.zeros(max_groups, dtype=A.GROUP_DTYPE)
+    grp = A.Groups()
+    grp.include, grp.key_field, grp.cap = mask, A.GROUP_KEY_NAMES.index(key), max_groups
+    grp.groups = arr.ctypes.data_as(C.POINTER(A.Group)) if max_groups else None
+    done = lambda: CampaignGroups(grp, arr)                                         # noqa: E731
+    if stats is None:
+        if collect is None:
+            _check(call(None, None, C.byref(grp)))
+            return rep, done()
+        failures, by_verdict = _collecting(lambda col: call(col, None, C.byref(grp)), collect)
+        return rep, failures, by_verdict, done()
+    out = _campaign_stats(lambda col, st: call(col, st, C.byref(grp)), stats[0], stats[1], collect, rep)
+    return out + (done(),)
+
+
+def run_campaign_groups(workload, seed0, total, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None,
+                        include=(A.PANIC, A.DEADLOCK, A.TIME_LIMIT), key="obs", max_groups=32, stop_at_groups=False, collect=None, stats=None,
+                        list_runner=False, stop_at_cap=False):
+    """madsim_hip_run_campaign_groups: run_campaign, plus the failure modes of the range — the seeds whose verdict is in `include` grouped by
+    (verdict, key), `key` one of "obs" (obs_hash: what the workload traced), "trace", "msgs", "clock", "rng", "steps"; the first `max_groups`
+    groups in order of first appearance, each with its exact count and its smallest seed.  stop_at_groups: stop launching once max_groups
+    different modes have been read.  Returns (campaign, CampaignGroups); with collect=K (as run_campaign) and / or stats=(include, top_k) (as
+    run_campaign_stats) their outputs come in between: (campaign[, failures, by_verdict][, CampaignStats], CampaignGroups)."""
+    if _inited_device is None:
+        init(0)
+    cfg, lim, rep = config or A.Config.default(), limits or A.Limits(), A.Campaign()
+    flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap, stop_at_groups)
+    return _campaign_groups(lambda col, st, grp: lib().madsim_hip_run_campaign_groups(
+        workload.ref(), C.byref(cfg), seed0, total, batch, in_flight, flags, C.byref(lim), C.byref(rep), col, st, grp),
+        include, key, max_groups, collect, stats, rep)
+
+
 def run_batch_device(workload, seed0, count, d_out_ptr, stream_ptr=0, config=None, limits=None, want_summary=True):
     """Device-resident entry point: results stay in HBM at `d_out_ptr` (48 B/seed)."""
     if _inited_device is None:
@@ -401,6 +461,17 @@ class Context:
             include, top_k, collect, rep)
 
 
+    def run_campaign_groups(self, workload, seed0, total, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None,
+                            include=(A.PANIC, A.DEADLOCK, A.TIME_LIMIT), key="obs", max_groups=32, stop_at_groups=False, collect=None, stats=None,
+                            list_runner=False, stop_at_cap=False):
+        """runtime.run_campaign_groups on this context (madsim_hip_ctx_run_campaign_groups)."""
+        cfg, lim, rep = config or A.Config.default(), limits or A.Limits(), A.Campaign()
+        flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap, stop_at_groups)
+        return _campaign_groups(lambda col, st, grp: lib().madsim_hip_ctx_run_campaign_groups(
+            self._h, workload.ref(), C.byref(cfg), seed0, total, batch, in_flight, flags, C.byref(lim), C.byref(rep), col, st, grp),
+            include, key, max_groups, collect, stats, rep)
+
+
 def run_batch_multi(contexts, workload, seed0, count, config=None, limits=None, max_rounds=5):
     """madsim_hip_run_batch_multi: one process, one host thread, the seed range sharded contiguously over `contexts`
     (all devices' kernels in flight together), runner verdicts re-run compacted, reports folded on the host."""
@@ -442,6 +513,18 @@ def run_campaign_stats_multi(contexts, workload, seed0, total, batch=0, in_fligh
     return _campaign_stats(lambda col, st: lib().madsim_hip_run_campaign_stats_multi(
         arr, len(contexts), workload.ref(), C.byref(cfg), seed0, total, batch, in_flight, flags, C.byref(lim), C.byref(rep), col, st),
         include, top_k, collect, rep)
+
+
+def run_campaign_groups_multi(contexts, workload, seed0, total, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None,
+                              include=(A.PANIC, A.DEADLOCK, A.TIME_LIMIT), key="obs", max_groups=32, stop_at_groups=False, collect=None, stats=None,
+                              list_runner=False, stop_at_cap=False):
+    """madsim_hip_run_campaign_groups_multi: run_campaign_groups over several contexts; the groups are the ones a single context gives."""
+    cfg, lim, rep = config or A.Config.default(), limits or A.Limits(), A.Campaign()
+    arr = (C.c_void_p * len(contexts))(*[c._h for c in contexts])
+    flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap, stop_at_groups)
+    return _campaign_groups(lambda col, st, grp: lib().madsim_hip_run_campaign_groups_multi(
+        arr, len(contexts), workload.ref(), C.byref(cfg), seed0, total, batch, in_flight, flags, C.byref(lim), C.byref(rep), col, st, grp),
+        include, key, max_groups, collect, stats, rep)
 
 
 def run_campaign_over_ranks(workload, seed0, total, batch=65536, stop_at_failure=True, config=None, limits=None, device_tensors=None, group=None,
