@@ -212,6 +212,29 @@ pub struct madsim_groups_t {
 
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
+pub struct madsim_diff_record_t {
+    pub seed: u64,
+    pub a: madsim_result_t,
+    pub b: madsim_result_t,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct madsim_diff_t {
+    pub fields: u32,
+    pub reserved: u32,
+    pub records: *const madsim_diff_record_t,
+    pub cap: u64,
+    pub n_listed: u64,
+    pub n_compared: u64,
+    pub n_incomparable: u64,
+    pub n_differ: u64,
+    pub n_by_field: [u64; 8],
+    pub transitions: [[u64; 8]; 8],
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
 pub struct madsim_geometry_t {
     pub lds_bytes_per_seed: u32,
     pub lds_bytes_per_block: u32,
@@ -366,6 +389,16 @@ pub const MADSIM_GROUP_KEY_STEPS: u32 = 5;
 pub const MADSIM_GROUP_KEYS: u32 = 6;
 pub const MADSIM_GROUP_MAX_BATCH: u32 = 1048576;
 pub const MADSIM_CAMPAIGN_STOP_AT_GROUPS: u32 = 8;
+pub const MADSIM_DIFF_VERDICT: u32 = 1;
+pub const MADSIM_DIFF_STEPS: u32 = 2;
+pub const MADSIM_DIFF_CLOCK: u32 = 4;
+pub const MADSIM_DIFF_MSGS: u32 = 8;
+pub const MADSIM_DIFF_RNG: u32 = 16;
+pub const MADSIM_DIFF_TRACE: u32 = 32;
+pub const MADSIM_DIFF_OBS: u32 = 64;
+pub const MADSIM_DIFF_ALL: u32 = 127;
+pub const MADSIM_DIFF_FIELDS: u32 = 7;
+pub const MADSIM_CAMPAIGN_STOP_AT_DIFFS: u32 = 16;
 
 #[link(name = "madsim_hip")]
 extern "C" {
@@ -407,6 +440,9 @@ extern "C" {
     pub fn madsim_hip_ctx_run_campaign_groups(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, batch: u64, in_flight: u32, flags: u32, lim: *const madsim_limits_t, out: *mut madsim_campaign_t, col: *mut madsim_collect_t, st: *mut madsim_stats_t, grp: *mut madsim_groups_t) -> c_int;
     pub fn madsim_hip_run_campaign_groups(w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, batch: u64, in_flight: u32, flags: u32, lim: *const madsim_limits_t, out: *mut madsim_campaign_t, col: *mut madsim_collect_t, st: *mut madsim_stats_t, grp: *mut madsim_groups_t) -> c_int;
     pub fn madsim_hip_run_campaign_groups_multi(ctxs: *const *mut madsim_hip_ctx_t, n_ctx: c_int, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, batch: u64, in_flight: u32, flags: u32, lim: *const madsim_limits_t, out: *mut madsim_campaign_t, col: *mut madsim_collect_t, st: *mut madsim_stats_t, grp: *mut madsim_groups_t) -> c_int;
+    pub fn madsim_hip_ctx_run_campaign_diff(ctx: *mut madsim_hip_ctx_t, wA: *const madsim_workload_t, cfgA: *const madsim_config_t, limA: *const madsim_limits_t, wB: *const madsim_workload_t, cfgB: *const madsim_config_t, limB: *const madsim_limits_t, seed0: u64, total: u64, batch: u64, in_flight: u32, flags: u32, outA: *mut madsim_campaign_t, outB: *mut madsim_campaign_t, diff: *mut madsim_diff_t) -> c_int;
+    pub fn madsim_hip_run_campaign_diff(wA: *const madsim_workload_t, cfgA: *const madsim_config_t, limA: *const madsim_limits_t, wB: *const madsim_workload_t, cfgB: *const madsim_config_t, limB: *const madsim_limits_t, seed0: u64, total: u64, batch: u64, in_flight: u32, flags: u32, outA: *mut madsim_campaign_t, outB: *mut madsim_campaign_t, diff: *mut madsim_diff_t) -> c_int;
+    pub fn madsim_hip_run_campaign_diff_multi(ctxs: *const *mut madsim_hip_ctx_t, n_ctx: c_int, wA: *const madsim_workload_t, cfgA: *const madsim_config_t, limA: *const madsim_limits_t, wB: *const madsim_workload_t, cfgB: *const madsim_config_t, limB: *const madsim_limits_t, seed0: u64, total: u64, batch: u64, in_flight: u32, flags: u32, outA: *mut madsim_campaign_t, outB: *mut madsim_campaign_t, diff: *mut madsim_diff_t) -> c_int;
     pub fn madsim_hip_geometry(w: *const madsim_workload_t, lim: *const madsim_limits_t, g: *mut madsim_geometry_t) -> c_int;
     pub fn madsim_hip_debug_counters(out16: *mut u64) -> c_int;
     pub fn madsim_workload_pingpong(n_nodes: u32, rounds: u32, nodes: *mut madsim_node_t, progs: *mut madsim_prog_t, socks: *mut madsim_sock_t, insns: *mut madsim_insn_t, cap_insns: u32, w: *mut madsim_workload_t) -> c_int;

@@ -175,6 +175,23 @@ pub struct Groups {
     pub campaign: sys::madsim_campaign_t,
 }
 
+/// What `Builder::diff_campaign` found: the smallest differing seeds with both sides' results (ascending), the report — counts and
+/// the 8 x 8 matrix `transitions[verdict A][verdict B]` — and each side's plain campaign report.
+#[derive(Clone, Debug)]
+pub struct Diff {
+    pub records: Vec<sys::madsim_diff_record_t>,
+    pub report: sys::madsim_diff_t,
+    pub a: sys::madsim_campaign_t,
+    pub b: sys::madsim_campaign_t,
+}
+
+impl Diff {
+    /// Seeds that passed on side A and carry any other verdict on side B.
+    pub fn regressions(&self) -> u64 {
+        self.report.transitions[sys::MADSIM_PASS as usize][1..].iter().sum()
+    }
+}
+
 impl Builder {
     /// builder.rs:64-118: `MADSIM_TEST_SEED`, `MADSIM_TEST_NUM`, `MADSIM_TEST_JOBS`, `MADSIM_TEST_TIME_LIMIT`,
     /// `MADSIM_TEST_CHECK_DETERMINISM`, `MADSIM_ALLOW_SYSTEM_THREAD` (`MADSIM_TEST_CONFIG` is read by the caller: the TOML
@@ -335,6 +352,33 @@ impl Builder {
         }
         groups.truncate(grp.n_groups as usize);
         Ok(Groups { groups, n_grouped: grp.n_grouped, n_ungrouped: grp.n_ungrouped, campaign })
+    }
+
+    /// Fix check: `self` running `workload` (side A) against `other` running `other_workload` (side B) over `self.seed .. self.seed +
+    /// self.count` (`madsim_hip_run_campaign_diff`).  Both sides run at the campaign's rate and are compared on the device on the result
+    /// fields named in `fields` (`MADSIM_DIFF_*`); config and limits are each side's own.  The `max_listed` smallest differing seeds come
+    /// back with both results, with the counts and the verdict-transition matrix.
+    pub fn diff_campaign(&self, workload: &Workload, other: &Builder, other_workload: &Workload, fields: u32, max_listed: usize) -> Result<Diff, RunError> {
+        let (wa, wb) = (workload.raw(), other_workload.raw());
+        let (ca, cb) = (self.config.raw(), other.config.raw());
+        let (la, lb) = (self.raw_limits(true), other.raw_limits(true));
+        let ctx = contexts()?.0[0];
+        let mut records: Vec<sys::madsim_diff_record_t> = vec![unsafe { std::mem::zeroed() }; max_listed];
+        let mut a: sys::madsim_campaign_t = unsafe { std::mem::zeroed() };
+        let mut b: sys::madsim_campaign_t = unsafe { std::mem::zeroed() };
+        let mut report: sys::madsim_diff_t = unsafe { std::mem::zeroed() };
+        report.fields = fields;
+        report.records = if max_listed > 0 { records.as_mut_ptr() as *const _ } else { std::ptr::null() };   // (the library writes through it)
+        report.cap = max_listed as u64;
+        let rc = unsafe {
+            sys::madsim_hip_ctx_run_campaign_diff(ctx, &wa, &ca, &la, &wb, &cb, &lb, self.seed, self.count, 0, 0, 0, &mut a, &mut b, &mut report)
+        };
+        if rc != 0 {
+            return Err(last_error(rc));
+        }
+        records.truncate(report.n_listed as usize);
+        report.records = std::ptr::null();
+        Ok(Diff { records, report, a, b })
     }
 
     /// Same contract as `Builder::run` (builder.rs:121-162) for a test body registered as a workload: returns the per-seed

@@ -805,6 +805,73 @@ int madsim_hip_run_campaign_groups_multi(madsim_hip_ctx_t* const* ctxs, int n_ct
                                          uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim, madsim_campaign_t* out,
                                          madsim_collect_t* col, madsim_stats_t* st, madsim_groups_t* grp);
 
+/* ---- Differential campaigns: TWO variants over one seed range, compared on the device --------------------------------------
+ * "I changed something: which seeds changed outcome, did the change break a seed that used to pass, and is every other seed still
+ * the same run?"  Side A runs (wA, cfgA, limA) and side B runs (wB, cfgB, limB) over the same seeds — any of the three may be the same
+ * pointer on both sides: two test bodies, two loss rates, or one workload under two state layouts / limits, which must give the same
+ * 48 bytes for every seed.  Per batch both simulations run on the flight's one stream, each followed by the plain campaign's report
+ * kernel, then two diff kernels read both result arrays; nothing is copied back but the report words and the disagreements.
+ * A seed is COMPARED when neither side's verdict is a runner verdict (MADSIM_IS_RUNNER_VERDICT: such a seed carries no usable
+ * numbers); otherwise it is INCOMPARABLE: it still counts in `transitions`, it never differs and is never listed.
+ * n_compared + n_incomparable = seeds_run.  A compared seed DIFFERS when any field named in `fields` (MADSIM_DIFF_*) differs;
+ * n_by_field[i] counts the compared seeds whose field bit i is masked and differs, so one seed may count in several.
+ * records[0 .. n_listed) are the `cap` smallest differing seeds of the prefix [seed0, seed0 + seeds_run), ascending, each with the 48
+ * bytes madsim_hip_run_batch returns for that seed on each side; no atomic decides a position.  transitions[a][b] counts the seeds
+ * with min(verdict A, 7) = a and min(verdict B, 7) = b: the entries sum to seeds_run, the row sums are what
+ * madsim_hip_run_campaign_collect reports as n_by_verdict for side A alone, the column sums the same for side B — "deadlock -> pass:
+ * N" is transitions[MADSIM_DEADLOCK][MADSIM_PASS].  outA / outB are exactly the plain campaign's report for that side over the same
+ * prefix (kernel_ms from an event pair of the side's own; wall_s is the call's).
+ * Everything is a function of the per-seed results of the prefix: the same bytes whatever `batch`, `in_flight` and the number of
+ * contexts, on every run; batches launched beyond a stopping one contribute nothing.  Both sides of batch k run on context
+ * k % n_ctx; automatic `in_flight` is the smaller of the two sides'.  The records of a batch are copied only when it has differing
+ * seeds, and only as many as the list still takes.
+ * MADSIM_CAMPAIGN_STOP_AT_DIFFS: stop launching once the batches read so far hold `cap` differing seeds; seeds_run / batches_run /
+ * batches_launched follow the rules of MADSIM_CAMPAIGN_STOP_AT_FAILURE.  The other stop flags are ignored by this form, and the other
+ * entry points ignore this flag.
+ * MADSIM_E_ARG: a NULL diff, outA or outB, fields == 0 or a bit above MADSIM_DIFF_ALL, reserved != 0, cap > 0 without `records`,
+ * STOP_AT_DIFFS with cap == 0, and the usual in_flight, seed0 + total and validate errors of either side (the message says which). */
+#define MADSIM_DIFF_VERDICT 1u    /* madsim_result_t.verdict    */
+#define MADSIM_DIFF_STEPS   2u    /* madsim_result_t.steps      */
+#define MADSIM_DIFF_CLOCK   4u    /* madsim_result_t.clock_ns   */
+#define MADSIM_DIFF_MSGS    8u    /* madsim_result_t.msg_count  */
+#define MADSIM_DIFF_RNG     16u   /* madsim_result_t.rng_calls  */
+#define MADSIM_DIFF_TRACE   32u   /* madsim_result_t.trace_hash */
+#define MADSIM_DIFF_OBS     64u   /* madsim_result_t.obs_hash   */
+#define MADSIM_DIFF_ALL     127u
+#define MADSIM_DIFF_FIELDS  7u
+#define MADSIM_CAMPAIGN_STOP_AT_DIFFS 16u /* stop launching once `cap` differing seeds have been read                             */
+/* (two statements each, as madsim_failure above: the record holds madsim_result_t by value, and the report a two-dimensional array,
+ * neither of which tests/cheader.py lays out by itself) */
+struct madsim_diff_record {
+    uint64_t seed;
+    madsim_result_t a, b;              /* as madsim_hip_run_batch returns them for `seed` on side A and on side B                 */
+};                                     /* 104 bytes */
+typedef struct madsim_diff_record madsim_diff_record_t;
+struct madsim_diff {
+    uint32_t fields, reserved;         /* in: MADSIM_DIFF_* mask of the fields compared; reserved = 0                             */
+    madsim_diff_record_t* records;     /* in: caller's host array [cap]; may be NULL when cap == 0                                */
+    uint64_t cap;
+    uint64_t n_listed;                 /* out: min(cap, n_differ)                                                                 */
+    uint64_t n_compared, n_incomparable, n_differ;
+    uint64_t n_by_field[8];            /* out: [i] = compared seeds whose field bit i is masked and differs; [7] = 0              */
+    uint64_t transitions[8][8];        /* out: seeds with min(verdict A, 7) = row and min(verdict B, 7) = column                  */
+};                                     /* 632 bytes */
+typedef struct madsim_diff madsim_diff_t;
+int madsim_hip_ctx_run_campaign_diff(madsim_hip_ctx_t* ctx, const madsim_workload_t* wA, const madsim_config_t* cfgA,
+                                     const madsim_limits_t* limA, const madsim_workload_t* wB, const madsim_config_t* cfgB,
+                                     const madsim_limits_t* limB, uint64_t seed0, uint64_t total, uint64_t batch,
+                                     uint32_t in_flight, uint32_t flags, madsim_campaign_t* outA, madsim_campaign_t* outB,
+                                     madsim_diff_t* diff);
+int madsim_hip_run_campaign_diff(const madsim_workload_t* wA, const madsim_config_t* cfgA, const madsim_limits_t* limA,
+                                 const madsim_workload_t* wB, const madsim_config_t* cfgB, const madsim_limits_t* limB,
+                                 uint64_t seed0, uint64_t total, uint64_t batch, uint32_t in_flight, uint32_t flags,
+                                 madsim_campaign_t* outA, madsim_campaign_t* outB, madsim_diff_t* diff);
+int madsim_hip_run_campaign_diff_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_workload_t* wA,
+                                       const madsim_config_t* cfgA, const madsim_limits_t* limA, const madsim_workload_t* wB,
+                                       const madsim_config_t* cfgB, const madsim_limits_t* limB, uint64_t seed0, uint64_t total,
+                                       uint64_t batch, uint32_t in_flight, uint32_t flags, madsim_campaign_t* outA,
+                                       madsim_campaign_t* outB, madsim_diff_t* diff);
+
 /* Geometry the library picked for a workload (for DESIGN/bench reporting). */
 typedef struct madsim_geometry {
     uint32_t lds_bytes_per_seed;

@@ -585,6 +585,43 @@ struct Builder {
         return g;
     }
 
+    // Fix check: this builder's run of `wl` (side A) against `other`'s run of `other_wl` (side B) over THIS builder's seed .. seed + count
+    // (madsim_hip_run_campaign_diff): both sides run at the campaign's rate and are compared on the device on the result fields named in
+    // `fields` (MADSIM_DIFF_*).  Config, capacities and time limit are each side's own; seed range and device are this builder's.  The
+    // `max_listed` smallest differing seeds come back with both results, with the counts and the 8 x 8 verdict-transition matrix:
+    // transitions[MADSIM_DEADLOCK][MADSIM_PASS] seeds were fixed, transitions[MADSIM_PASS][v != PASS] seeds were broken.
+    struct Diff {
+        std::vector<madsim_diff_record_t> records;                        // ascending by seed
+        madsim_diff_t report{};                                           // (records / cap: of the call; read `records` above)
+        madsim_campaign_t a{}, b{};                                       // each side's plain campaign report
+        uint64_t regressions() const {                                    // passed on side A, any other verdict on side B
+            uint64_t n = 0;
+            for (int v = 1; v < 8; v++) n += report.transitions[MADSIM_PASS][v];
+            return n;
+        }
+    };
+    Diff diff_against(const Builder& other, const Workload& wl, const Workload& other_wl,
+                      uint32_t fields = MADSIM_DIFF_ALL, size_t max_listed = 0) const {
+        madsim::check(madsim_hip_init(device));
+        madsim_workload_t wa = wl.raw(), wb = other_wl.raw();
+        madsim_config_t ca = config.raw(), cb = other.config.raw();
+        madsim_limits_t la = capacities, lb = other.capacities;
+        if (time_limit) { la.time_limit_ns = (uint64_t)(*time_limit * 1e9 + 0.5); if (!la.time_limit_ns) la.time_limit_ns = 1; }
+        if (other.time_limit) { lb.time_limit_ns = (uint64_t)(*other.time_limit * 1e9 + 0.5); if (!lb.time_limit_ns) lb.time_limit_ns = 1; }
+        Diff d;
+        d.records.resize(max_listed);
+        d.report.fields = fields;
+        d.report.records = max_listed ? d.records.data() : nullptr;
+        d.report.cap = max_listed;
+        madsim::check(madsim_hip_run_campaign_diff(&wa, &ca, &la, &wb, &cb, &lb, seed, count, 0, 0, 0, &d.a, &d.b, &d.report));
+        d.records.resize((size_t)d.report.n_listed);
+        d.report.records = nullptr;                                       // (the vector may move with the struct)
+        return d;
+    }
+    Diff diff_against(const Builder& other, const Workload& wl, uint32_t fields = MADSIM_DIFF_ALL, size_t max_listed = 0) const {
+        return diff_against(other, wl, wl, fields, max_listed);           // one test body under two configurations
+    }
+
     // builder.rs:121-162: run seeds seed..seed+count; return on success, "panic" on the first failing seed.
     // Reports the numerically smallest failing seed (the reference reports the first to complete).
     std::vector<madsim_result_t> run(const Workload& wl) const {

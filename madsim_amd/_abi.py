@@ -198,6 +198,30 @@ HEADER_STRUCTS["madsim_group_t"] = Group
 HEADER_STRUCTS["madsim_groups_t"] = Groups
 
 
+CAMPAIGN_STOP_AT_DIFFS = 16   # differential campaigns: stop launching once `cap` differing seeds have been read
+DIFF_VERDICT, DIFF_STEPS, DIFF_CLOCK, DIFF_MSGS, DIFF_RNG, DIFF_TRACE, DIFF_OBS = (1 << i for i in range(7))      # madsim_diff_t.fields
+DIFF_ALL = 127
+DIFF_FIELDS = 7
+DIFF_FIELD_NAMES = ("verdict", "steps", "clock_ns", "msg_count", "rng_calls", "trace_hash", "obs_hash")      # the result field behind bit i
+
+
+class DiffRecord(C.Structure):
+    """madsim_diff_record_t: one differing seed of a differential campaign — the seed and its 48 result bytes on each side."""
+    _fields_ = [("seed", C.c_uint64), ("a", Result), ("b", Result)]
+
+
+class Diff(C.Structure):
+    """madsim_diff_t: the compared fields and the caller's record array going in; the list length, the counts and the 8 x 8 matrix of
+    verdict transitions coming out.  (Like madsim_failure_t and madsim_stats_t it is declared in two statements in the header, so it is
+    not in HEADER_STRUCTS: tests/test_campaign_diff.py holds it against the header.)"""
+    _fields_ = [("fields", C.c_uint32), ("reserved", C.c_uint32), ("records", C.POINTER(DiffRecord)), ("cap", C.c_uint64), ("n_listed", C.c_uint64),
+                ("n_compared", C.c_uint64), ("n_incomparable", C.c_uint64), ("n_differ", C.c_uint64), ("n_by_field", C.c_uint64 * 8),
+                ("transitions", C.c_uint64 * 8 * 8)]
+
+
+assert C.sizeof(DiffRecord) == 104 and C.sizeof(Diff) == 632
+
+
 class Geometry(C.Structure):
     _fields_ = [
         ("lds_bytes_per_seed", C.c_uint32), ("lds_bytes_per_block", C.c_uint32), ("block_threads", C.c_uint32),
@@ -227,6 +251,8 @@ RESULT_DTYPE = [("verdict", "<u4"), ("steps", "<u4"), ("clock_ns", "<u8"), ("msg
 # numpy view of a collecting campaign's list: madsim_failure_t, the seed in front of the result's fields
 FAILURE_DTYPE = [("seed", "<u8")] + RESULT_DTYPE
 assert C.sizeof(Failure) == 56 and C.sizeof(Collect) == 88
+# numpy view of a differential campaign's list: madsim_diff_record_t, the seed, then side A's result and side B's
+DIFF_RECORD_DTYPE = [("seed", "<u8"), ("a", RESULT_DTYPE), ("b", RESULT_DTYPE)]
 # numpy view of a statistics campaign's extreme seeds: madsim_extreme_t
 EXTREME_DTYPE = [("value", "<u8"), ("seed", "<u8")]
 assert C.sizeof(Extreme) == 16 and C.sizeof(Metric) == 2080 and C.sizeof(Stats) == 32 + 4 * 2080

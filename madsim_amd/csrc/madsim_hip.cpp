@@ -104,8 +104,15 @@ struct madsim_hip_ctx {
                     // page-locked host); the keyed table (zero between batches: grp_dirty = a batch was queued and never harvested), the list
                     // of claimed slots and the batch's entries, sized for batches of grp_cap seeds
                     unsigned long long* d_grep = nullptr; unsigned long long* h_grep = nullptr; uint32_t* d_gtab = nullptr; uint32_t* d_glist = nullptr;
-                    madsim_group_t* d_gent = nullptr; size_t grp_cap = 0; bool grp_dirty = false; };
+                    madsim_group_t* d_gent = nullptr; size_t grp_cap = 0; bool grp_dirty = false;
+                    // differential campaigns only: side B's results, its event pair, the report words — DIFF_REP_WORDS live ones (device, page-locked
+                    // host) and behind the device's a copy of their state before a batch, from which one device copy prepares them —, per-wave
+                    // counts and the batch's records
+                    madsim_result_t* d_out_b = nullptr; size_t cap_b = 0; hipEvent_t b0 = nullptr, b1 = nullptr;
+                    unsigned long long* d_drep = nullptr; unsigned long long* h_drep = nullptr; uint32_t* d_dwcnt = nullptr;
+                    madsim_diff_record_t* d_drec = nullptr; size_t drec_cap = 0; };
     static constexpr size_t GROUP_REP_WORDS = STATS_REP_WORDS + MADSIM_K_GROUP_WORDS;
+    static constexpr size_t DIFF_REP_WORDS = 16 + MADSIM_K_DIFF_WORDS;      // summary6's six words of side A at 0, of side B at 8, the diff words at 16
     Flight flights[CAMPAIGN_MAX];
     unsigned long long* d_acc = nullptr;      // 4 x u64 summary accumulators
     madsim_result_t* d_out = nullptr; size_t out_cap = 0;
@@ -147,7 +154,8 @@ struct madsim_hip_ctx {
                  const madsim_limits_t* lim, madsim_result_t* out, madsim_summary_t* summary);
     int run_list(const madsim_workload_t* w, const madsim_config_t* cfg, const std::vector<uint64_t>& seeds,
                  const madsim_limits_t* lim, std::vector<madsim_result_t>& res, double* kernel_ms);
-    int ensure_flights(uint32_t n, uint64_t batch, bool staging, bool collect = false, uint64_t records = 0, bool stats = false, uint64_t groups = 0);
+    int ensure_flights(uint32_t n, uint64_t batch, bool staging, bool collect = false, uint64_t records = 0, bool stats = false, uint64_t groups = 0,
+                       bool diff = false, uint64_t diff_records = 0);
     uint32_t flights_for(const madsim_workload_t* w, const madsim_config_t* cfg, const madsim_limits_t* lim, uint64_t batch);
 };
 
@@ -227,6 +235,13 @@ void madsim_hip_ctx::close() {
         if (f.d_gtab) (void)hipFree(f.d_gtab);
         if (f.d_glist) (void)hipFree(f.d_glist);
         if (f.d_gent) (void)hipFree(f.d_gent);
+        if (f.d_out_b) (void)hipFree(f.d_out_b);
+        if (f.d_drep) (void)hipFree(f.d_drep);
+        if (f.h_drep) (void)hipHostFree(f.h_drep);
+        if (f.d_dwcnt) (void)hipFree(f.d_dwcnt);
+        if (f.d_drec) (void)hipFree(f.d_drec);
+        if (f.b0) (void)hipEventDestroy(f.b0);
+        if (f.b1) (void)hipEventDestroy(f.b1);
         if (f.e0) (void)hipEventDestroy(f.e0);
         if (f.e1) (void)hipEventDestroy(f.e1);
         if (f.done) (void)hipEventDestroy(f.done);
@@ -459,8 +474,10 @@ int madsim_hip_ctx::run_list(const madsim_workload_t* w, const madsim_config_t* 
 // context's mutex serialises the two).  `staging`: also a page-locked host buffer of `batch` results per flight.  `collect`: also
 // the report words and wave counts of a collecting campaign and room for `records` failure records per flight.  `stats`: also the
 // report and candidate words of a statistics campaign.  `groups` (seeds per batch, 0 = none): also the report words, the keyed table, the
-// slot list and the entry buffer of a grouping campaign — nothing of it exists for the other campaigns.
-int madsim_hip_ctx::ensure_flights(uint32_t n, uint64_t batch, bool staging, bool collect, uint64_t records, bool stats, uint64_t groups) {
+// slot list and the entry buffer of a grouping campaign — nothing of it exists for the other campaigns.  `diff`: also side B's result buffer and
+// event pair, the report words, the wave counts and room for `diff_records` records of a differential campaign — for that form only.
+int madsim_hip_ctx::ensure_flights(uint32_t n, uint64_t batch, bool staging, bool collect, uint64_t records, bool stats, uint64_t groups, bool diff,
+                                   uint64_t diff_records) {
     if (n > (uint32_t)CAMPAIGN_MAX) return fail(MADSIM_E_ARG, "at most 8 batches in flight");
     hint_hw_queues(n);
     for (uint32_t i = 0; i < n; i++) {
@@ -515,6 +532,27 @@ int madsim_hip_ctx::ensure_flights(uint32_t n, uint64_t batch, bool staging, boo
             HIP_TRY(hipMemsetAsync(f.d_gtab, 0, madsim_k_group_slots(f.grp_cap) * MADSIM_K_GROUP_SLOT_BYTES, f.stream));
             HIP_TRY(hipStreamSynchronize(f.stream));
             f.grp_dirty = false;
+        }
+        if (diff && !f.d_drep) {
+            unsigned long long init[DIFF_REP_WORDS] = {};                          // the words before a batch: summary6's two minima all-ones, the rest zero
+            init[0] = init[4] = init[8] = init[12] = ~0ull;
+            HIP_TRY(hipMalloc(&f.d_drep, 2 * DIFF_REP_WORDS * sizeof(unsigned long long)));
+            HIP_TRY(hipMemcpy(f.d_drep + DIFF_REP_WORDS, init, sizeof init, hipMemcpyHostToDevice));
+            HIP_TRY(hipHostMalloc((void**)&f.h_drep, DIFF_REP_WORDS * sizeof(unsigned long long), hipHostMallocDefault));
+            HIP_TRY(hipMalloc(&f.d_dwcnt, MADSIM_K_COLLECT_WAVES * sizeof(uint32_t)));
+            HIP_TRY(hipEventCreate(&f.b0)); HIP_TRY(hipEventCreate(&f.b1));
+        }
+        if (diff && batch > f.cap_b) {
+            if (f.d_out_b) { HIP_TRY(hipStreamSynchronize(f.stream)); (void)hipFree(f.d_out_b); }
+            f.d_out_b = nullptr; f.cap_b = 0;
+            HIP_TRY(hipMalloc(&f.d_out_b, batch * sizeof(madsim_result_t)));
+            f.cap_b = batch;
+        }
+        if (diff && diff_records > f.drec_cap) {
+            if (f.d_drec) { HIP_TRY(hipStreamSynchronize(f.stream)); (void)hipFree(f.d_drec); }
+            f.d_drec = nullptr; f.drec_cap = 0;
+            HIP_TRY(hipMalloc(&f.d_drec, diff_records * sizeof(madsim_diff_record_t)));
+            f.drec_cap = diff_records;
         }
     }
     return 0;
@@ -1017,6 +1055,21 @@ extern "C" void madsim_k_fold_groups(madsim_groups_t* grp, void* state, const ma
     }
 }
 
+// ---- differential campaigns: the host fold of a batch's words --------------------------------------------------------------------
+// w = a batch's MADSIM_K_DIFF_WORDS (sim_kernel.hip): {n_differ, n_incomparable, n_by_field[8], transitions[8][8]}.  The counts commute; the list
+// is appended in batch order, which is seed order, and never beyond `cap`.
+extern "C" uint64_t madsim_k_fold_diff(madsim_diff_t* diff, const unsigned long long* w, uint64_t count, const madsim_diff_record_t* batch_recs) {
+    diff->n_differ += w[0];
+    diff->n_incomparable += w[1];
+    diff->n_compared += count - w[1];
+    for (int k = 0; k < 8; k++) diff->n_by_field[k] += w[2 + k];
+    for (int k = 0; k < 64; k++) (&diff->transitions[0][0])[k] += w[10 + k];
+    const uint64_t take = std::min<uint64_t>(w[0], diff->cap - diff->n_listed);
+    if (take && batch_recs) memcpy(diff->records + diff->n_listed, batch_recs, take * sizeof(madsim_diff_record_t));
+    diff->n_listed += take;
+    return take;
+}
+
 // ---- campaigns -------------------------------------------------------------------------------------------------------------
 // One implementation for one context and for several (madsim_hip_run_campaign_multi): batch k of the range runs on context k % n,
 // on that context's flight (k / n) % in_flight — the devices advance through the seed space TOGETHER, so with
@@ -1026,6 +1079,31 @@ extern "C" void madsim_k_fold_groups(madsim_groups_t* grp, void* state, const ma
 // whatever the number of devices: the report of n contexts equals the report of one.  Builder::run's fan-out with an early exit
 // (runtime/builder.rs:129-160: every thread's result is joined in seed order, the first failure is re-raised).
 namespace {
+// The queue-and-harvest loop every campaign form shares: batch k may be queued once batch k - n * F[k % n] (the previous user of its flight)
+// has been harvested; batches are harvested in order.  Returns the number of batches launched; after an error (first_err, first_msg) every
+// stream of the flights has been drained.
+extern "C++" {                                                   // (a template, inside this file's extern "C" block)
+template <class Queue, class Harvest>
+uint64_t pump_batches(madsim_hip_ctx* const* ctxs, int n_ctx, uint64_t n_batches, const std::vector<uint32_t>& F, const bool& stop, int& first_err,
+                      std::string& first_msg, Queue queue, Harvest harvest) {
+    const uint64_t N = (uint64_t)n_ctx;
+    auto note = [&](int e) { if (e && !first_err) { first_err = e; first_msg = g_err; } };
+    uint64_t launched = 0, harvested = 0;
+    while (harvested < launched || (launched < n_batches && !stop && !first_err)) {
+        const bool room = launched < n_batches && launched < harvested + N * (uint64_t)F[launched % N];
+        if (room && !stop && !first_err) { note(queue(launched)); launched++; continue; }
+        note(harvest(harvested)); harvested++;                  // the oldest batch in flight: its stream takes the next launch
+    }
+    if (first_err) {                                             // (as in run_pipelined: a stale `done` must not let a kernel outlive the call)
+        for (int g = 0; g < n_ctx; g++) {
+            if (ctxs[g]->bind()) continue;
+            for (uint32_t i = 0; i < F[g]; i++) (void)hipStreamSynchronize(ctxs[g]->flights[i].stream);
+        }
+    }
+    return launched;
+}
+}  // extern "C++"
+
 int run_campaign_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total,
                       uint64_t batch, uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim, madsim_campaign_t* out,
                       madsim_collect_t* col = nullptr, madsim_stats_t* st = nullptr, madsim_groups_t* grp = nullptr) {
@@ -1155,24 +1233,106 @@ int run_campaign_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workl
         }
         return 0;
     };
-    auto note = [&](int e) { if (e && !first_err) { first_err = e; first_msg = g_err; } };
-    // batch k may be queued once batch k - n * F[k % n] (the previous user of its flight) has been harvested
-    uint64_t launched = 0, harvested = 0;
-    while (harvested < launched || (launched < n_batches && !stop && !first_err)) {
-        const bool room = launched < n_batches && launched < harvested + N * (uint64_t)F[launched % N];
-        if (room && !stop && !first_err) { note(queue(launched)); launched++; continue; }
-        note(harvest(harvested)); harvested++;                  // the oldest batch in flight: its stream takes the next launch
-    }
-    out->batches_launched = launched;
+    out->batches_launched = pump_batches(ctxs, n_ctx, n_batches, F, stop, first_err, first_msg, queue, harvest);
     out->wall_s = since(t0);
-    if (first_err) {                                             // (as in run_pipelined: a stale `done` must not let a kernel outlive the call)
-        for (int g = 0; g < n_ctx; g++) {
-            if (ctxs[g]->bind()) continue;
-            for (uint32_t i = 0; i < F[g]; i++) (void)hipStreamSynchronize(ctxs[g]->flights[i].stream);
-        }
-        return fail(first_err, first_msg);
+    return first_err ? fail(first_err, first_msg) : 0;
+}
+
+// The differential form: the same flights, the same loop; per batch both sides' simulation and summary6 launches, then the two diff kernels,
+// all on the flight's one stream, and one copy of the words.  Both sides of batch k run on context k % n.
+struct DiffSide { const madsim_workload_t* w; const madsim_config_t* cfg; const madsim_limits_t* lim; madsim_campaign_t* out; };
+
+int run_campaign_diff_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const DiffSide (&side)[2], uint64_t seed0, uint64_t total, uint64_t batch,
+                           uint32_t in_flight, uint32_t flags, madsim_diff_t* d) {
+    auto t0 = std::chrono::steady_clock::now();
+    for (const DiffSide& s : side) { memset(s.out, 0, sizeof *s.out); s.out->first_failing_seed = UINT64_MAX; }
+    d->n_listed = d->n_compared = d->n_incomparable = d->n_differ = 0;
+    memset(d->n_by_field, 0, sizeof d->n_by_field);
+    memset(d->transitions, 0, sizeof d->transitions);
+    flags &= MADSIM_CAMPAIGN_STOP_AT_DIFFS;                      // (the other stop flags belong to the other forms)
+    for (int s = 0; s < 2; s++)
+        if (int rc = madsim_geo::validate(side[s].w, side[s].cfg, &g_err)) return fail(rc, std::string(s ? "side B: " : "side A: ") + g_err);
+    if (batch == 0) batch = 65536;
+    if (in_flight > (uint32_t)madsim_hip_ctx::CAMPAIGN_MAX) return fail(MADSIM_E_ARG, "at most 8 batches in flight per context");
+    if (seed0 + total < seed0) return fail(MADSIM_E_ARG, "seed0 + total wraps");
+    if (total == 0) return 0;
+    if (std::min(batch, total) >= (1ull << 32)) return fail(MADSIM_E_ARG, "a differential campaign's batch holds fewer than 2^32 seeds");
+    const uint64_t n_batches = (total + batch - 1) / batch, N = (uint64_t)n_ctx;
+    const uint64_t rec_batch = std::min(d->cap, std::min(batch, total));      // records a flight holds: no batch lists more
+    int rc;
+    std::vector<uint32_t> F(n_ctx);
+    for (int g = 0; g < n_ctx; g++) {
+        if ((rc = ctxs[g]->bind())) return rc;
+        const uint64_t mine = (n_batches + N - 1 - (uint64_t)g) / N;
+        uint32_t f = in_flight ? in_flight
+                               : std::min(ctxs[g]->flights_for(side[0].w, side[0].cfg, side[0].lim, batch), ctxs[g]->flights_for(side[1].w, side[1].cfg, side[1].lim, batch));
+        if ((uint64_t)f > mine) f = (uint32_t)mine;
+        F[g] = f;
+        if (f && (rc = ctxs[g]->ensure_flights(f, batch, false, false, 0, false, 0, true, rec_batch))) return rc;
     }
-    return 0;
+    constexpr size_t n_words = madsim_hip_ctx::DIFF_REP_WORDS;
+    int first_err = 0;
+    std::string first_msg;
+    bool stop = false;
+    auto flight_of = [&](uint64_t k) -> madsim_hip_ctx::Flight& { const int g = (int)(k % N); return ctxs[g]->flights[(k / N) % F[g]]; };
+    auto queue = [&](uint64_t k) -> int {
+        madsim_hip_ctx* c = ctxs[k % N];
+        madsim_hip_ctx::Flight& f = flight_of(k);
+        const uint64_t lo = k * batch, n = std::min(batch, total - lo);
+        int e;
+        if ((e = c->bind())) return e;
+        HIP_TRY(hipMemcpyAsync(f.d_drep, f.d_drep + n_words, n_words * sizeof(unsigned long long), hipMemcpyDeviceToDevice, f.stream));
+        HIP_TRY(hipEventRecord(f.e0, f.stream));
+        if ((e = c->launch(side[0].w, side[0].cfg, seed0 + lo, n, nullptr, side[0].lim, f.d_out, f.stream))) return fail(e, "side A: " + g_err);
+        HIP_TRY(hipEventRecord(f.e1, f.stream));
+        madsim_k_launch_summary6(f.d_out, n, seed0 + lo, f.d_drep, f.stream);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(f.b0, f.stream));
+        if ((e = c->launch(side[1].w, side[1].cfg, seed0 + lo, n, nullptr, side[1].lim, f.d_out_b, f.stream))) return fail(e, "side B: " + g_err);
+        HIP_TRY(hipEventRecord(f.b1, f.stream));
+        madsim_k_launch_summary6(f.d_out_b, n, seed0 + lo, f.d_drep + 8, f.stream);
+        HIP_TRY(hipGetLastError());
+        if (madsim_k_launch_diff(f.d_out, f.d_out_b, n, seed0 + lo, d->fields, f.d_drep + 16, f.d_dwcnt, f.d_drec, std::min(rec_batch, n), f.stream))
+            return fail(MADSIM_E_ARG, "madsim_k_launch_diff refused the batch's arguments");
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(f.h_drep, f.d_drep, n_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, f.stream));
+        HIP_TRY(hipEventRecord(f.done, f.stream));
+        return 0;
+    };
+    auto harvest = [&](uint64_t k) -> int {
+        madsim_hip_ctx* c = ctxs[k % N];
+        madsim_hip_ctx::Flight& f = flight_of(k);
+        int e;
+        if ((e = c->bind())) return e;
+        HIP_TRY(hipEventSynchronize(f.done));
+        if (first_err || stop) return 0;                        // (draining after an error, or a batch launched beyond the stopping one)
+        const uint64_t lo = k * batch, n = std::min(batch, total - lo);
+        float ms[2] = {0.f, 0.f};
+        HIP_TRY(hipEventElapsedTime(&ms[0], f.e0, f.e1));
+        HIP_TRY(hipEventElapsedTime(&ms[1], f.b0, f.b1));
+        for (int s = 0; s < 2; s++) {
+            const unsigned long long* a = f.h_drep + 8 * s;
+            madsim_campaign_t* out = side[s].out;
+            out->kernel_ms += ms[s];
+            out->batches_run++; out->seeds_run += n;
+            out->n_runner += a[5];
+            out->n_failed += a[1] - a[5];
+            out->total_steps += a[2]; out->total_clock_ns += a[3];
+            if (a[4] < out->first_failing_seed) out->first_failing_seed = a[4];
+        }
+        if (f.h_drep[16] > n) return fail(MADSIM_E_HIP, "differential campaign: a batch reports more differing seeds than it holds");
+        // the batch's records, as many as the list still takes (the stream is idle: its `done` has passed, and it takes no launch before this returns)
+        const uint64_t at = d->n_listed, take = madsim_k_fold_diff(d, f.h_drep + 16, n, nullptr);
+        if (take) {
+            HIP_TRY(hipMemcpyAsync(d->records + at, f.d_drec, take * sizeof(madsim_diff_record_t), hipMemcpyDeviceToHost, f.stream));
+            HIP_TRY(hipStreamSynchronize(f.stream));
+        }
+        if ((flags & MADSIM_CAMPAIGN_STOP_AT_DIFFS) && d->n_differ >= d->cap) stop = true;
+        return 0;
+    };
+    const uint64_t launched = pump_batches(ctxs, n_ctx, n_batches, F, stop, first_err, first_msg, queue, harvest);
+    for (const DiffSide& s : side) { s.out->batches_launched = launched; s.out->wall_s = since(t0); }
+    return first_err ? fail(first_err, first_msg) : 0;
 }
 }  // namespace
 
@@ -1325,6 +1485,50 @@ int madsim_hip_run_campaign_groups_multi(madsim_hip_ctx_t* const* ctxs, int n_ct
     return run_campaign_impl(ctxs, n_ctx, w, cfg, seed0, total, batch, in_flight, flags, lim, out, col, st, grp);
 }
 
+// The differential forms: argument errors first, as the other forms.
+namespace {
+int check_diff_args(const madsim_campaign_t* outA, const madsim_campaign_t* outB, const madsim_diff_t* d, uint32_t in_flight, uint32_t flags) {
+    if (!outA || !outB) return fail(MADSIM_E_ARG, "null campaign report (a differential campaign fills one per side)");
+    if (!d) return fail(MADSIM_E_ARG, "null madsim_diff_t");
+    if (d->fields == 0 || (d->fields & ~MADSIM_DIFF_ALL)) return fail(MADSIM_E_ARG, "madsim_diff_t.fields: at least one MADSIM_DIFF_* bit, none above MADSIM_DIFF_ALL");
+    if (d->reserved) return fail(MADSIM_E_ARG, "madsim_diff_t.reserved must be 0");
+    if (d->cap && !d->records) return fail(MADSIM_E_ARG, "madsim_diff_t.cap > 0 without a records array");
+    if ((flags & MADSIM_CAMPAIGN_STOP_AT_DIFFS) && !d->cap) return fail(MADSIM_E_ARG, "MADSIM_CAMPAIGN_STOP_AT_DIFFS with cap == 0");
+    if (in_flight > (uint32_t)madsim_hip_ctx::CAMPAIGN_MAX) return fail(MADSIM_E_ARG, "at most 8 batches in flight per context");
+    return 0;
+}
+}  // namespace
+
+int madsim_hip_ctx_run_campaign_diff(madsim_hip_ctx_t* c, const madsim_workload_t* wA, const madsim_config_t* cfgA, const madsim_limits_t* limA,
+                                     const madsim_workload_t* wB, const madsim_config_t* cfgB, const madsim_limits_t* limB, uint64_t seed0,
+                                     uint64_t total, uint64_t batch, uint32_t in_flight, uint32_t flags, madsim_campaign_t* outA,
+                                     madsim_campaign_t* outB, madsim_diff_t* diff) {
+    if (int rc = check_diff_args(outA, outB, diff, in_flight, flags)) return rc;
+    CTX_ENTER(c);
+    madsim_hip_ctx* one[1] = {c};
+    const DiffSide side[2] = {{wA, cfgA, limA, outA}, {wB, cfgB, limB, outB}};
+    return run_campaign_diff_impl(one, 1, side, seed0, total, batch, in_flight, flags, diff);
+}
+
+int madsim_hip_run_campaign_diff_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_workload_t* wA, const madsim_config_t* cfgA,
+                                       const madsim_limits_t* limA, const madsim_workload_t* wB, const madsim_config_t* cfgB,
+                                       const madsim_limits_t* limB, uint64_t seed0, uint64_t total, uint64_t batch, uint32_t in_flight,
+                                       uint32_t flags, madsim_campaign_t* outA, madsim_campaign_t* outB, madsim_diff_t* diff) {
+    if (int rc = check_diff_args(outA, outB, diff, in_flight, flags)) return rc;
+    if (!ctxs || n_ctx < 1) return fail(MADSIM_E_ARG, "run_campaign_diff_multi needs at least one context");
+    for (int g = 0; g < n_ctx; g++) {
+        if (!ctxs[g]) return fail(MADSIM_E_NOINIT, "null context");
+        for (int h = 0; h < g; h++) if (ctxs[h] == ctxs[g]) return fail(MADSIM_E_ARG, "the same context appears twice");
+    }
+    std::vector<madsim_hip_ctx*> order(ctxs, ctxs + n_ctx);      // locks in address order (see madsim_hip_run_batch_multi)
+    std::sort(order.begin(), order.end(), [](madsim_hip_ctx* a, madsim_hip_ctx* b) { return std::less<madsim_hip_ctx*>()(a, b); });
+    std::vector<std::unique_lock<std::mutex>> locks;
+    for (madsim_hip_ctx* c : order) locks.emplace_back(c->mu);
+    for (int g = 0; g < n_ctx; g++) if (ctxs[g]->device < 0) return fail(MADSIM_E_NOINIT, "closed context");
+    const DiffSide side[2] = {{wA, cfgA, limA, outA}, {wB, cfgB, limB, outB}};
+    return run_campaign_diff_impl(ctxs, n_ctx, side, seed0, total, batch, in_flight, flags, diff);
+}
+
 // ---- v1 entry points: wrappers on the process-default context ------------------------------------------------------------
 // The default context is reference-counted by its users: a wrapper pins it under g_default_mu for the duration of its call,
 // and madsim_hip_shutdown waits until no call is inside before destroying it — a concurrent run_batch and shutdown is a
@@ -1419,6 +1623,13 @@ int madsim_hip_run_campaign_groups(const madsim_workload_t* w, const madsim_conf
                                    madsim_stats_t* st, madsim_groups_t* grp) {
     DefaultPin p;
     return madsim_hip_ctx_run_campaign_groups(p.c, w, cfg, seed0, total, batch, in_flight, flags, lim, out, col, st, grp);
+}
+
+int madsim_hip_run_campaign_diff(const madsim_workload_t* wA, const madsim_config_t* cfgA, const madsim_limits_t* limA, const madsim_workload_t* wB,
+                                 const madsim_config_t* cfgB, const madsim_limits_t* limB, uint64_t seed0, uint64_t total, uint64_t batch,
+                                 uint32_t in_flight, uint32_t flags, madsim_campaign_t* outA, madsim_campaign_t* outB, madsim_diff_t* diff) {
+    DefaultPin p;
+    return madsim_hip_ctx_run_campaign_diff(p.c, wA, cfgA, limA, wB, cfgB, limB, seed0, total, batch, in_flight, flags, outA, outB, diff);
 }
 
 int madsim_hip_geometry(const madsim_workload_t* w, const madsim_limits_t* lim, madsim_geometry_t* out) {

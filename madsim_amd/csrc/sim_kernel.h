@@ -354,6 +354,19 @@ uint64_t madsim_k_group_slot(uint64_t key, uint32_t verdict, uint64_t slots);
 void* madsim_k_group_state_new(void);
 void  madsim_k_group_state_free(void* state);
 void  madsim_k_fold_groups(madsim_groups_t* grp, void* state, const madsim_group_t* batch_entries, uint64_t n, uint64_t seed0_of_batch);
+// the differential campaign's report kernels, behind the two sides' simulation and summary6 launches on the same stream: `a` and `b` are the
+// two sides' results of the same `count` seeds.  `words`: MADSIM_K_DIFF_WORDS words, ALL ZERO before the launch: {n_differ, n_incomparable,
+// n_by_field[8], transitions[8][8]} of the batch; `wave_cnt`: MADSIM_K_COLLECT_WAVES words of scratch (every wave's number of differing seeds);
+// `recs`: the `cap` differing seeds of the batch with the smallest seeds, ascending (may be null when cap == 0; nothing behind
+// min(cap, n_differ) is written).  `fields`: a MADSIM_DIFF_* mask.  Returns 0, or -1 without launching anything for fields == 0, a bit above
+// MADSIM_DIFF_ALL, count == 0 or count >= 2^32 (the counters of a workgroup are 32-bit).
+#define MADSIM_K_DIFF_WORDS 74u         /* 64-bit words of a batch's diff report: 2 + 8 + 64 */
+int  madsim_k_launch_diff(const madsim_result_t* a, const madsim_result_t* b, uint64_t count, uint64_t seed0, uint32_t fields,
+                          unsigned long long* words, uint32_t* wave_cnt, madsim_diff_record_t* recs, uint64_t cap, void* stream);
+// the host fold of one batch's MADSIM_K_DIFF_WORDS into the caller's report (madsim_hip.cpp; no device involved): batches in seed order.
+// Returns how many of the batch's records the list still takes — min(the batch's n_differ, cap - n_listed) — and advances n_listed by it;
+// when `batch_recs` (host memory, at least that many) is given they are appended to diff->records, otherwise the caller copies them there.
+uint64_t madsim_k_fold_diff(madsim_diff_t* diff, const unsigned long long* words, uint64_t count, const madsim_diff_record_t* batch_recs);
 int  madsim_k_set_max_lds(uint32_t lds_bytes);
 int  madsim_k_variant_vgprs(const madsim_k::VariantSel* v);
 void madsim_k_launch_keyflip(unsigned long long* acc, void* stream);

@@ -465,6 +465,112 @@ __global__ __launch_bounds__(256) void group_extract_kernel(const madsim_result_
     }
 }
 
+// ---- the differential campaign form: two result arrays of the same seeds, compared field by field ----
+// Two kernels behind the two sides' simulation and summary6 launches, over collect's cut of the batch (wave W owns a contiguous piece, so
+// "ascending wave, ascending lane" is ascending seed order).  A seed is COMPARED when neither verdict is a runner verdict; its difference
+// mask has bit k set when field k (verdict, steps, clock_ns, msg_count, rng_calls, trace_hash, obs_hash) is named in `fields` and differs.
+// An incomparable seed has mask 0 whatever its bytes.  The first 16 bytes of each side are always read (the verdict is there); the second
+// 16 (msg_count, rng_calls) and the third (the two hashes) only when `fields` names one of theirs — a kernel argument, so wave-uniform.
+// words = {n_differ, n_incomparable, n_by_field[8], transitions[8][8]}, all zero before the launch.  The PASS -> PASS cell is not counted:
+// diff_write_kernel sets it to what the other 63 leave, so a round of 64 seeds that all passed on both sides with no masked difference
+// ends at one ballot.  Any other round adds its cells to 64 LDS counters of the workgroup (one global atomic per non-zero cell per
+// workgroup) and its ballots' popcounts to the wave's registers (one set of global atomics per wave).
+// diff_write_kernel is collect_write_kernel with two sources: the exclusive prefix of wave_cnt is a wave's offset, only a wave with
+// differing seeds and an offset below `cap` reads its piece again, rank = offset + lanes_below(ballot): integer adds only, no atomic
+// decides a position.  A record is {seed, a, b}: 104 bytes, thirteen 8-byte stores.
+struct DiffLoads { bool b1, b2; };                                                 // which of the later 16-byte parts `fields` touches
+__device__ __forceinline__ DiffLoads diff_loads(uint32_t fields) {
+    return DiffLoads{(fields & (MADSIM_DIFF_MSGS | MADSIM_DIFF_RNG)) != 0, (fields & (MADSIM_DIFF_TRACE | MADSIM_DIFF_OBS)) != 0};
+}
+__device__ __forceinline__ uint32_t diff_cell(uint32_t va, uint32_t vb) { return (va < 7u ? va : 7u) * 8u + (vb < 7u ? vb : 7u); }
+
+// the difference mask of seed i (0 for an incomparable seed); va / vb: the two verdicts
+__device__ __forceinline__ uint32_t diff_mask(const madsim_result_t* __restrict__ a, const madsim_result_t* __restrict__ b, uint64_t i, uint32_t fields,
+                                              DiffLoads L, uint32_t& va, uint32_t& vb) {
+    const uint4 a0 = reinterpret_cast<const uint4*>(a + i)[0], b0 = reinterpret_cast<const uint4*>(b + i)[0];
+    va = a0.x; vb = b0.x;
+    uint32_t d = (a0.x != b0.x ? MADSIM_DIFF_VERDICT : 0u) | (a0.y != b0.y ? MADSIM_DIFF_STEPS : 0u) | ((a0.z != b0.z || a0.w != b0.w) ? MADSIM_DIFF_CLOCK : 0u);
+    if (L.b1) {
+        const uint4 a1 = reinterpret_cast<const uint4*>(a + i)[1], b1 = reinterpret_cast<const uint4*>(b + i)[1];
+        d |= ((a1.x != b1.x || a1.y != b1.y) ? MADSIM_DIFF_MSGS : 0u) | ((a1.z != b1.z || a1.w != b1.w) ? MADSIM_DIFF_RNG : 0u);
+    }
+    if (L.b2) {
+        const uint4 a2 = reinterpret_cast<const uint4*>(a + i)[2], b2 = reinterpret_cast<const uint4*>(b + i)[2];
+        d |= ((a2.x != b2.x || a2.y != b2.y) ? MADSIM_DIFF_TRACE : 0u) | ((a2.z != b2.z || a2.w != b2.w) ? MADSIM_DIFF_OBS : 0u);
+    }
+    return (MADSIM_IS_RUNNER_VERDICT(va) || MADSIM_IS_RUNNER_VERDICT(vb)) ? 0u : d & fields;
+}
+
+__global__ __launch_bounds__(256) void diff_count_kernel(const madsim_result_t* __restrict__ a, const madsim_result_t* __restrict__ b, uint64_t count,
+                                                         uint64_t piece, uint32_t fields, unsigned long long* __restrict__ words,
+                                                         uint32_t* __restrict__ wave_cnt) {
+    __shared__ uint32_t cells[64];
+    const uint32_t W = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (threadIdx.x < 64) cells[threadIdx.x] = 0;
+    __syncthreads();
+    const uint64_t lo = (uint64_t)W * piece, hi = lo + piece < count ? lo + piece : count;
+    const DiffLoads L = diff_loads(fields);
+    uint32_t n_differ = 0, n_inc = 0, by_field[MADSIM_DIFF_FIELDS] = {0, 0, 0, 0, 0, 0, 0};      // wave-uniform (popcounts of ballots)
+    for (uint64_t base = lo; base < hi; base += 64) {
+        const uint64_t i = base + lane;
+        uint32_t va = MADSIM_PASS, vb = MADSIM_PASS, d = 0;
+        if (i < hi) d = diff_mask(a, b, i, fields, L, va, vb);
+        if (!__ballot((va | vb | d) != 0)) continue;                               // (wave-uniform) all PASS -> PASS, nothing differs
+        const uint32_t cell = diff_cell(va, vb);
+        if (cell) atomicAdd(&cells[cell], 1u);
+        n_differ += (uint32_t)__popcll(__ballot(d != 0));
+        n_inc += (uint32_t)__popcll(__ballot(MADSIM_IS_RUNNER_VERDICT(va) || MADSIM_IS_RUNNER_VERDICT(vb)));
+#pragma unroll
+        for (uint32_t k = 0; k < MADSIM_DIFF_FIELDS; k++) by_field[k] += (uint32_t)__popcll(__ballot((d >> k) & 1u));
+    }
+    if (lane == 0) {                                                               // one set of atomics per wave: none when nothing differs
+        wave_cnt[W] = n_differ;
+        if (n_differ) atomicAdd(&words[0], (unsigned long long)n_differ);
+        if (n_inc) atomicAdd(&words[1], (unsigned long long)n_inc);
+#pragma unroll
+        for (uint32_t k = 0; k < MADSIM_DIFF_FIELDS; k++) if (by_field[k]) atomicAdd(&words[2 + k], (unsigned long long)by_field[k]);
+    }
+    __syncthreads();
+    if (threadIdx.x > 0 && threadIdx.x < 64 && cells[threadIdx.x]) atomicAdd(&words[10 + threadIdx.x], (unsigned long long)cells[threadIdx.x]);
+}
+
+__global__ __launch_bounds__(256) void diff_write_kernel(const madsim_result_t* __restrict__ a, const madsim_result_t* __restrict__ b, uint64_t count,
+                                                         uint64_t seed0, uint64_t piece, uint32_t fields, unsigned long long* __restrict__ words,
+                                                         const uint32_t* __restrict__ wave_cnt, madsim_diff_record_t* __restrict__ recs, uint64_t cap) {
+    const uint32_t W = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (W == 0 && lane == 0) {                                                     // PASS -> PASS is what the other 63 cells leave
+        unsigned long long other = 0;
+        for (uint32_t k = 1; k < 64; k++) other += words[10 + k];
+        words[10] = count - other;
+    }
+    if (cap == 0 || wave_cnt[W] == 0) return;                                      // (wave-uniform)
+    uint64_t at = 0;                                                               // differing seeds of the waves before this one
+    for (uint32_t j = lane; j < W; j += 64) at += wave_cnt[j];
+    for (int o = 32; o > 0; o >>= 1) at += __shfl_xor(at, o);
+    const uint64_t lo = (uint64_t)W * piece, hi = lo + piece < count ? lo + piece : count;
+    const DiffLoads L = diff_loads(fields);
+    for (uint64_t base = lo; base < hi && at < cap; base += 64) {
+        const uint64_t i = base + lane;
+        uint32_t va = MADSIM_PASS, vb = MADSIM_PASS, d = 0;
+        if (i < hi) d = diff_mask(a, b, i, fields, L, va, vb);
+        const unsigned long long m = __ballot(d != 0);
+        const uint64_t rank = at + lanes_below(m);
+        if (d != 0 && rank < cap) {                                                // all 96 bytes only of a seed that is listed
+            const uint4* qa = reinterpret_cast<const uint4*>(a + i);
+            const uint4* qb = reinterpret_cast<const uint4*>(b + i);
+            unsigned long long* p = reinterpret_cast<unsigned long long*>(recs) + rank * 13u;      // 104 B records: 8-byte stores
+            p[0] = seed0 + i;
+#pragma unroll
+            for (int j = 0; j < 3; j++) {
+                const uint4 x = qa[j], y = qb[j];
+                p[1 + 2 * j] = ((unsigned long long)x.y << 32) | x.x; p[2 + 2 * j] = ((unsigned long long)x.w << 32) | x.z;
+                p[7 + 2 * j] = ((unsigned long long)y.y << 32) | y.x; p[8 + 2 * j] = ((unsigned long long)y.w << 32) | y.z;
+            }
+        }
+        at += (uint64_t)__popcll(m);
+    }
+}
+
 __global__ void keyflip_kernel(unsigned long long* acc) { acc[0] ^= 0x8000000000000000ull; }
 
 // one kernel per row of variant_table (sim_kernel.h), same macro, same order
@@ -549,6 +655,22 @@ extern "C" int madsim_k_launch_groups(const madsim_result_t* out, uint64_t count
     if (xgrid > 64) xgrid = 64;
     hipLaunchKernelGGL(madsim_k::group_extract_kernel, dim3(xgrid), dim3(256), 0, (hipStream_t)stream, out, (uint32_t)count, seed0, key_words[key_field],
                        reinterpret_cast<uint4*>(table), (uint32_t)(slots - 1), (const uint32_t*)list, grep, entries);
+    return 0;
+}
+
+// words: MADSIM_K_DIFF_WORDS zeroed words; wave_cnt: MADSIM_K_COLLECT_WAVES words; recs: `cap` records (may be null when cap == 0); all prepared by
+// the caller on `stream` (sim_kernel.h).  Returns 0, or -1 (nothing launched) for arguments the kernels are not written for.
+extern "C" int madsim_k_launch_diff(const madsim_result_t* a, const madsim_result_t* b, uint64_t count, uint64_t seed0, uint32_t fields,
+                                    unsigned long long* words, uint32_t* wave_cnt, madsim_diff_record_t* recs, uint64_t cap, void* stream) {
+    static_assert(sizeof(madsim_diff_record_t) == 104 && sizeof(madsim_result_t) == 48, "record layout");
+    static_assert(MADSIM_K_DIFF_WORDS == 2 + 8 + 64 && MADSIM_DIFF_FIELDS == 7 && MADSIM_DIFF_ALL == (1u << MADSIM_DIFF_FIELDS) - 1, "sim_kernel.h");
+    if (count == 0 || count >= (1ull << 32) || fields == 0 || (fields & ~MADSIM_DIFF_ALL) || (cap && !recs)) return -1;
+    uint32_t grid = (uint32_t)((count + 1023) / 1024);     // collect's cut
+    if (grid > 256) grid = 256;
+    const uint64_t waves = 4ull * grid, piece = ((count + waves - 1) / waves + 63) / 64 * 64;
+    hipLaunchKernelGGL(madsim_k::diff_count_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, a, b, count, piece, fields, words, wave_cnt);
+    hipLaunchKernelGGL(madsim_k::diff_write_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, a, b, count, seed0, piece, fields, words,
+                       (const uint32_t*)wave_cnt, recs, cap);
     return 0;
 }
 

@@ -126,6 +126,11 @@ def lib():
         L.madsim_hip_run_campaign_groups.argtypes = L.madsim_hip_run_campaign_stats.argtypes + [C.POINTER(A.Groups)]
         L.madsim_hip_ctx_run_campaign_groups.argtypes = [ctxp] + L.madsim_hip_run_campaign_groups.argtypes
         L.madsim_hip_run_campaign_groups_multi.argtypes = [C.POINTER(ctxp), C.c_int] + L.madsim_hip_run_campaign_groups.argtypes
+        side = [C.POINTER(A.Workload), C.POINTER(A.Config), C.POINTER(A.Limits)]
+        L.madsim_hip_run_campaign_diff.argtypes = side + side + [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(A.Campaign),
+                                                                 C.POINTER(A.Campaign), C.POINTER(A.Diff)]
+        L.madsim_hip_ctx_run_campaign_diff.argtypes = [ctxp] + L.madsim_hip_run_campaign_diff.argtypes
+        L.madsim_hip_run_campaign_diff_multi.argtypes = [C.POINTER(ctxp), C.c_int] + L.madsim_hip_run_campaign_diff.argtypes
         if L.madsim_hip_version() != A.ABI_VERSION:
             raise MadsimHipError("libmadsim_hip.so ABI version mismatch")
         # build identity: MADSIM_HIP_LIB may name an A/B build of THIS library (tools/build_variant.sh), nothing else — an
@@ -380,6 +385,57 @@ def run_campaign_groups(workload, seed0, total, batch=0, in_flight=0, stop_at_fa
         include, key, max_groups, collect, stats, rep)
 
 
+class CampaignDiff:
+    """What a differential campaign (madsim_hip_run_campaign_diff) says about the prefix that ran: `records`, an ndarray[DIFF_RECORD_DTYPE] of the
+    max_listed smallest differing seeds, ascending — seed, and the result on side `a` and on side `b` —; `n_compared`, `n_incomparable` (a runner
+    verdict on either side), `n_differ`; `n_by_field`, 8 counts by field bit (A.DIFF_FIELD_NAMES; one seed may count in several); and
+    `transitions`, the 8 x 8 matrix of seeds by min(verdict A, 7) (row) and min(verdict B, 7) (column)."""
+
+    def __init__(self, d, records):
+        self.fields, self.max_listed = int(d.fields), int(d.cap)
+        self.records = records[:d.n_listed].copy()
+        self.n_compared, self.n_incomparable, self.n_differ = int(d.n_compared), int(d.n_incomparable), int(d.n_differ)
+        self.n_by_field = np.array(d.n_by_field[:], dtype=np.uint64)
+        self.transitions = np.array([row[:] for row in d.transitions], dtype=np.uint64)
+
+    def __len__(self):
+        return len(self.records)
+
+    def regressions(self):
+        """Seeds that passed on side A and carry any other verdict on side B."""
+        return int(self.transitions[A.PASS, 1:].sum())
+
+
+def _campaign_diff(call, workload, other, config, other_config, limits, other_limits, fields, max_listed, stop_at_diffs):
+    """Run `call(wA, cfgA, limA, wB, cfgB, limB, flags, repA, repB, diff)` — one of the madsim_hip_*run_campaign_diff* entry points with its
+    contexts and its range bound.  A None on the B side means "the same as A's"."""
+    if not isinstance(fields, int) or fields <= 0 or fields & ~A.DIFF_ALL or max_listed < 0 or (stop_at_diffs and not max_listed):
+        raise MadsimHipError("run_campaign_diff: fields is a non-empty mask of A.DIFF_* bits, max_listed >= 0, and stop_at_diffs needs max_listed > 0")
+    cfg_a, lim_a = config or A.Config.default(), limits or A.Limits()
+    w_b, cfg_b, lim_b = other or workload, other_config or cfg_a, other_limits or lim_a
+    arr = np.zeros(max_listed, dtype=A.DIFF_RECORD_DTYPE)
+    d = A.Diff()
+    d.fields, d.cap = fields, max_listed
+    d.records = arr.ctypes.data_as(C.POINTER(A.DiffRecord)) if max_listed else None
+    rep_a, rep_b = A.Campaign(), A.Campaign()
+    _check(call(workload.ref(), C.byref(cfg_a), C.byref(lim_a), w_b.ref(), C.byref(cfg_b), C.byref(lim_b),
+                A.CAMPAIGN_STOP_AT_DIFFS if stop_at_diffs else 0, C.byref(rep_a), C.byref(rep_b), C.byref(d)))
+    return rep_a, rep_b, CampaignDiff(d, arr)
+
+
+def run_campaign_diff(workload, seed0, total, other=None, config=None, other_config=None, limits=None, other_limits=None, fields=A.DIFF_ALL,
+                      max_listed=0, stop_at_diffs=False, batch=0, in_flight=0):
+    """madsim_hip_run_campaign_diff: side A = (workload, config, limits) and side B = (other, other_config, other_limits) over the same seeds —
+    a None on the B side means "the same as A's" —, compared on the device on the result fields named in `fields` (A.DIFF_* bits).  Returns
+    (campaign A, campaign B, CampaignDiff): each side's plain campaign report, the max_listed smallest differing seeds with both results, the
+    counts, and the verdict-transition matrix.  stop_at_diffs: stop launching once max_listed differing seeds have been read."""
+    if _inited_device is None:
+        init(0)
+    return _campaign_diff(lambda wa, ca, la, wb, cb, lb, flags, ra, rb, d: lib().madsim_hip_run_campaign_diff(
+        wa, ca, la, wb, cb, lb, seed0, total, batch, in_flight, flags, ra, rb, d),
+        workload, other, config, other_config, limits, other_limits, fields, max_listed, stop_at_diffs)
+
+
 def run_batch_device(workload, seed0, count, d_out_ptr, stream_ptr=0, config=None, limits=None, want_summary=True):
     """Device-resident entry point: results stay in HBM at `d_out_ptr` (48 B/seed)."""
     if _inited_device is None:
@@ -472,6 +528,14 @@ class Context:
             include, key, max_groups, collect, stats, rep)
 
 
+    def run_campaign_diff(self, workload, seed0, total, other=None, config=None, other_config=None, limits=None, other_limits=None,
+                          fields=A.DIFF_ALL, max_listed=0, stop_at_diffs=False, batch=0, in_flight=0):
+        """runtime.run_campaign_diff on this context (madsim_hip_ctx_run_campaign_diff)."""
+        return _campaign_diff(lambda wa, ca, la, wb, cb, lb, flags, ra, rb, d: lib().madsim_hip_ctx_run_campaign_diff(
+            self._h, wa, ca, la, wb, cb, lb, seed0, total, batch, in_flight, flags, ra, rb, d),
+            workload, other, config, other_config, limits, other_limits, fields, max_listed, stop_at_diffs)
+
+
 def run_batch_multi(contexts, workload, seed0, count, config=None, limits=None, max_rounds=5):
     """madsim_hip_run_batch_multi: one process, one host thread, the seed range sharded contiguously over `contexts`
     (all devices' kernels in flight together), runner verdicts re-run compacted, reports folded on the host."""
@@ -525,6 +589,16 @@ def run_campaign_groups_multi(contexts, workload, seed0, total, batch=0, in_flig
     return _campaign_groups(lambda col, st, grp: lib().madsim_hip_run_campaign_groups_multi(
         arr, len(contexts), workload.ref(), C.byref(cfg), seed0, total, batch, in_flight, flags, C.byref(lim), C.byref(rep), col, st, grp),
         include, key, max_groups, collect, stats, rep)
+
+
+def run_campaign_diff_multi(contexts, workload, seed0, total, other=None, config=None, other_config=None, limits=None, other_limits=None,
+                            fields=A.DIFF_ALL, max_listed=0, stop_at_diffs=False, batch=0, in_flight=0):
+    """madsim_hip_run_campaign_diff_multi: run_campaign_diff over several contexts (both sides of batch k on context k % n); the report is the
+    one a single context gives."""
+    arr = (C.c_void_p * len(contexts))(*[c._h for c in contexts])
+    return _campaign_diff(lambda wa, ca, la, wb, cb, lb, flags, ra, rb, d: lib().madsim_hip_run_campaign_diff_multi(
+        arr, len(contexts), wa, ca, la, wb, cb, lb, seed0, total, batch, in_flight, flags, ra, rb, d),
+        workload, other, config, other_config, limits, other_limits, fields, max_listed, stop_at_diffs)
 
 
 def run_campaign_over_ranks(workload, seed0, total, batch=65536, stop_at_failure=True, config=None, limits=None, device_tensors=None, group=None,

@@ -50,6 +50,9 @@ def main():
     w("}")
     # (a struct declared as `struct s { .. }; typedef struct s s_t;` — one that holds another by value — gets its twin like the rest)
     two = re.sub(r"\bstruct\s+(\w+)\s*\{([^{}]*)\}\s*;\s*typedef\s+struct\s+\1\s+(\w+)\s*;", r"typedef struct \1 {\2} \3;", text)
+    # (a two-dimensional array `t name[a][b]`, which tests/cheader.py does not parse, is handed over as `name[a * b]` and written as [[t; b]; a])
+    dims = {m.group(1): (int(m.group(2)), int(m.group(3))) for m in re.finditer(r"(\w+)\[(\d+)\]\[(\d+)\]", two)}
+    two = re.sub(r"(\w+)\[(\d+)\]\[(\d+)\]", lambda m: f"{m.group(1)}[{int(m.group(2)) * int(m.group(3))}]", two)
     for name, fields in H.structs(two).items():
         w("")
         w("#[repr(C)]")
@@ -59,7 +62,9 @@ def main():
             t = PRIM.get(ctype, ctype)
             if ptr:
                 t = "*const " + t
-            if arr:
+            if arr and fname in dims and dims[fname][0] * dims[fname][1] == arr:
+                t = f"[[{t}; {dims[fname][1]}]; {dims[fname][0]}]"
+            elif arr:
                 t = f"[{t}; {arr}]"
             rname = "r#match" if fname == "match" else fname
             w(f"    pub {rname}: {t},")
