@@ -235,6 +235,19 @@ pub struct madsim_diff_t {
 
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
+pub struct madsim_resolve_t {
+    pub n_first_pass: u64,
+    pub n_resolved: u64,
+    pub n_unresolved: u64,
+    pub n_by_round: [u64; 8],
+    pub batches_resolved: u64,
+    pub rounds: u32,
+    pub reserved: u32,
+    pub rerun_kernel_ms: f64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
 pub struct madsim_geometry_t {
     pub lds_bytes_per_seed: u32,
     pub lds_bytes_per_block: u32,
@@ -399,6 +412,11 @@ pub const MADSIM_DIFF_OBS: u32 = 64;
 pub const MADSIM_DIFF_ALL: u32 = 127;
 pub const MADSIM_DIFF_FIELDS: u32 = 7;
 pub const MADSIM_CAMPAIGN_STOP_AT_DIFFS: u32 = 16;
+pub const MADSIM_CAMPAIGN_RESOLVE: u32 = 32;
+pub const MADSIM_CAMPAIGN_RESOLVE_ROUNDS_SHIFT: u32 = 8;
+pub const MADSIM_CAMPAIGN_RESOLVE_ROUNDS_MASK: u32 = 3840;
+pub const MADSIM_RESOLVE_DEFAULT_ROUNDS: u32 = 4;
+pub const MADSIM_RESOLVE_MAX_ROUNDS: u32 = 8;
 
 #[link(name = "madsim_hip")]
 extern "C" {
@@ -443,6 +461,9 @@ extern "C" {
     pub fn madsim_hip_ctx_run_campaign_diff(ctx: *mut madsim_hip_ctx_t, wA: *const madsim_workload_t, cfgA: *const madsim_config_t, limA: *const madsim_limits_t, wB: *const madsim_workload_t, cfgB: *const madsim_config_t, limB: *const madsim_limits_t, seed0: u64, total: u64, batch: u64, in_flight: u32, flags: u32, outA: *mut madsim_campaign_t, outB: *mut madsim_campaign_t, diff: *mut madsim_diff_t) -> c_int;
     pub fn madsim_hip_run_campaign_diff(wA: *const madsim_workload_t, cfgA: *const madsim_config_t, limA: *const madsim_limits_t, wB: *const madsim_workload_t, cfgB: *const madsim_config_t, limB: *const madsim_limits_t, seed0: u64, total: u64, batch: u64, in_flight: u32, flags: u32, outA: *mut madsim_campaign_t, outB: *mut madsim_campaign_t, diff: *mut madsim_diff_t) -> c_int;
     pub fn madsim_hip_run_campaign_diff_multi(ctxs: *const *mut madsim_hip_ctx_t, n_ctx: c_int, wA: *const madsim_workload_t, cfgA: *const madsim_config_t, limA: *const madsim_limits_t, wB: *const madsim_workload_t, cfgB: *const madsim_config_t, limB: *const madsim_limits_t, seed0: u64, total: u64, batch: u64, in_flight: u32, flags: u32, outA: *mut madsim_campaign_t, outB: *mut madsim_campaign_t, diff: *mut madsim_diff_t) -> c_int;
+    pub fn madsim_hip_campaign_resolved(out: *mut madsim_resolve_t) -> c_int;
+    pub fn madsim_hip_ctx_campaign_resolved(ctx: *mut madsim_hip_ctx_t, out: *mut madsim_resolve_t) -> c_int;
+    pub fn madsim_hip_grow_limits(w: *const madsim_workload_t, lim: *const madsim_limits_t, rounds: u32, out: *mut madsim_limits_t) -> c_int;
     pub fn madsim_hip_geometry(w: *const madsim_workload_t, lim: *const madsim_limits_t, g: *mut madsim_geometry_t) -> c_int;
     pub fn madsim_hip_debug_counters(out16: *mut u64) -> c_int;
     pub fn madsim_workload_pingpong(n_nodes: u32, rounds: u32, nodes: *mut madsim_node_t, progs: *mut madsim_prog_t, socks: *mut madsim_sock_t, insns: *mut madsim_insn_t, cap_insns: u32, w: *mut madsim_workload_t) -> c_int;

@@ -140,6 +140,8 @@ pub struct Builder {
     /// Device capacities to start from (no reference counterpart; all zero = defaults).  `limits.no_trace_hash = 1` drops the
     /// determinism-log fingerprint from the results (the reference logs only under `check`, rand.rs:67): 4 % faster on ping-pong.
     pub limits: sys::madsim_limits_t,
+    /// `MADSIM_CAMPAIGN_RESOLVE` and its rounds bits, set by `resolve_runner` (0 = runner verdicts are counted apart).
+    pub resolve_flags: u32,
 }
 
 fn zero_limits() -> sys::madsim_limits_t {
@@ -220,7 +222,28 @@ impl Builder {
             count = count.max(2);
         }
         let allow_system_thread = std::env::var("MADSIM_ALLOW_SYSTEM_THREAD").is_ok();
-        Builder { seed, count, jobs, config: NetConfig::default(), time_limit, check, allow_system_thread, limits: zero_limits() }
+        Builder { seed, count, jobs, config: NetConfig::default(), time_limit, check, allow_system_thread, limits: zero_limits(), resolve_flags: 0 }
+    }
+
+    /// `search_failures`, `campaign_stats`, `failure_groups` and `diff_campaign` report on SETTLED results: seeds that come back with a
+    /// runner verdict (a device capacity, the step cap) are run again on the device under grown limits, up to `rounds` times (0 = the
+    /// library's default, at most `MADSIM_RESOLVE_MAX_ROUNDS`), before their batch is reported (`MADSIM_CAMPAIGN_RESOLVE`).
+    pub fn resolve_runner(mut self, rounds: u32) -> Self {
+        assert!(rounds <= sys::MADSIM_RESOLVE_MAX_ROUNDS, "resolve_runner: at most MADSIM_RESOLVE_MAX_ROUNDS rounds");
+        self.resolve_flags = sys::MADSIM_CAMPAIGN_RESOLVE | rounds << sys::MADSIM_CAMPAIGN_RESOLVE_ROUNDS_SHIFT;
+        self
+    }
+
+    /// The resolve account of the most recent campaign call (`madsim_hip_ctx_campaign_resolved`): how many seeds the first pass left
+    /// re-runnable, how many each round re-ran, how many ended settled.
+    pub fn resolved(&self) -> Result<sys::madsim_resolve_t, RunError> {
+        let ctx = contexts()?.0[0];
+        let mut r: sys::madsim_resolve_t = unsafe { std::mem::zeroed() };
+        let rc = unsafe { sys::madsim_hip_ctx_campaign_resolved(ctx, &mut r) };
+        if rc != 0 {
+            return Err(last_error(rc));
+        }
+        Ok(r)
     }
 
     fn raw_limits(&self, with_time_limit: bool) -> sys::madsim_limits_t {
@@ -288,7 +311,7 @@ impl Builder {
             n_listed: 0,
             n_by_verdict: [0; 8],
         };
-        let rc = unsafe { sys::madsim_hip_ctx_run_campaign_collect(ctx, &w, &cfg, self.seed, self.count, 0, 0, 0, &lim, &mut campaign, &mut col) };
+        let rc = unsafe { sys::madsim_hip_ctx_run_campaign_collect(ctx, &w, &cfg, self.seed, self.count, 0, 0, self.resolve_flags, &lim, &mut campaign, &mut col) };
         if rc != 0 {
             return Err(last_error(rc));
         }
@@ -312,7 +335,7 @@ impl Builder {
         stats.top_k = top_k;
         stats.top = if k > 0 { top.as_mut_ptr() as *const _ } else { std::ptr::null() };   // (the library writes through it)
         let rc = unsafe {
-            sys::madsim_hip_ctx_run_campaign_stats(ctx, &w, &cfg, self.seed, self.count, 0, 0, 0, &lim, &mut campaign, std::ptr::null_mut(), &mut stats)
+            sys::madsim_hip_ctx_run_campaign_stats(ctx, &w, &cfg, self.seed, self.count, 0, 0, self.resolve_flags, &lim, &mut campaign, std::ptr::null_mut(), &mut stats)
         };
         if rc != 0 {
             return Err(last_error(rc));
@@ -344,7 +367,7 @@ impl Builder {
             n_ungrouped: 0,
         };
         let rc = unsafe {
-            sys::madsim_hip_ctx_run_campaign_groups(ctx, &w, &cfg, self.seed, self.count, 0, 0, 0, &lim, &mut campaign, std::ptr::null_mut(),
+            sys::madsim_hip_ctx_run_campaign_groups(ctx, &w, &cfg, self.seed, self.count, 0, 0, self.resolve_flags, &lim, &mut campaign, std::ptr::null_mut(),
                                                     std::ptr::null_mut(), &mut grp)
         };
         if rc != 0 {
@@ -371,7 +394,7 @@ impl Builder {
         report.records = if max_listed > 0 { records.as_mut_ptr() as *const _ } else { std::ptr::null() };   // (the library writes through it)
         report.cap = max_listed as u64;
         let rc = unsafe {
-            sys::madsim_hip_ctx_run_campaign_diff(ctx, &wa, &ca, &la, &wb, &cb, &lb, self.seed, self.count, 0, 0, 0, &mut a, &mut b, &mut report)
+            sys::madsim_hip_ctx_run_campaign_diff(ctx, &wa, &ca, &la, &wb, &cb, &lb, self.seed, self.count, 0, 0, self.resolve_flags, &mut a, &mut b, &mut report)
         };
         if rc != 0 {
             return Err(last_error(rc));

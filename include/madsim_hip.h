@@ -618,8 +618,9 @@ int madsim_hip_run_batch_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const m
  * MADSIM_CAMPAIGN_STOP_AT_FAILURE: stop launching as soon as a completed batch reports a seed with a GENUINE verdict (panic /
  * deadlock / time limit); batches are contiguous and reports are read in order, so `first_failing_seed` is then the smallest
  * failing seed of [seed0, seed0 + seeds_run): at most `in_flight - 1` batches beyond the failing one have been started.
- * Runner verdicts (MADSIM_OVERFLOW / MADSIM_STEP_LIMIT) never stop a campaign and are counted apart (`n_runner`): re-run those
- * ranges with madsim_hip_run_batch_auto. */
+ * Runner verdicts (MADSIM_OVERFLOW / MADSIM_STEP_LIMIT) never stop a campaign and are counted apart (`n_runner`): pass
+ * MADSIM_CAMPAIGN_RESOLVE (below) to have them re-run on the device before the batch is reported, or re-run those ranges with
+ * madsim_hip_run_batch_auto. */
 #define MADSIM_CAMPAIGN_STOP_AT_FAILURE 1u
 typedef struct madsim_campaign {
     uint64_t seeds_run;           /* seeds whose batch ran to completion and was read (a prefix of the range)                 */
@@ -627,7 +628,8 @@ typedef struct madsim_campaign {
     uint64_t batches_launched;    /* >= batches_run: with STOP_AT_FAILURE the batches in flight when the failure was read      */
     uint64_t first_failing_seed;  /* smallest seed with a genuine verdict among seeds_run; UINT64_MAX if none                  */
     uint64_t n_failed;            /* genuine failures among seeds_run                                                          */
-    uint64_t n_runner;            /* seeds that came back with a runner verdict (not failures; to be re-run)                   */
+    uint64_t n_runner;            /* seeds that came back with a runner verdict (not failures; to be re-run) — with
+                                   * MADSIM_CAMPAIGN_RESOLVE: those still left with one after the resolve rounds               */
     uint64_t total_steps, total_clock_ns;
     double   kernel_ms;           /* sum of the simulation kernels' HIP-event durations (they overlap: > wall time)            */
     double   wall_s;
@@ -812,7 +814,9 @@ int madsim_hip_run_campaign_groups_multi(madsim_hip_ctx_t* const* ctxs, int n_ct
  * 48 bytes for every seed.  Per batch both simulations run on the flight's one stream, each followed by the plain campaign's report
  * kernel, then two diff kernels read both result arrays; nothing is copied back but the report words and the disagreements.
  * A seed is COMPARED when neither side's verdict is a runner verdict (MADSIM_IS_RUNNER_VERDICT: such a seed carries no usable
- * numbers); otherwise it is INCOMPARABLE: it still counts in `transitions`, it never differs and is never listed.
+ * numbers); otherwise it is INCOMPARABLE: it still counts in `transitions`, it never differs and is never listed.  With
+ * MADSIM_CAMPAIGN_RESOLVE each side's runner verdicts are first re-run under that side's own grown limits, so only the seeds that no
+ * round settles stay incomparable.
  * n_compared + n_incomparable = seeds_run.  A compared seed DIFFERS when any field named in `fields` (MADSIM_DIFF_*) differs;
  * n_by_field[i] counts the compared seeds whose field bit i is masked and differs, so one seed may count in several.
  * records[0 .. n_listed) are the `cap` smallest differing seeds of the prefix [seed0, seed0 + seeds_run), ascending, each with the 48
@@ -871,6 +875,61 @@ int madsim_hip_run_campaign_diff_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx,
                                        const madsim_config_t* cfgB, const madsim_limits_t* limB, uint64_t seed0, uint64_t total,
                                        uint64_t batch, uint32_t in_flight, uint32_t flags, madsim_campaign_t* outA,
                                        madsim_campaign_t* outB, madsim_diff_t* diff);
+
+/* ---- Self-resolving campaigns: runner verdicts re-run on the device, every report over SETTLED results ----------------------
+ * A runner verdict (MADSIM_OVERFLOW, MADSIM_STEP_LIMIT) is a statement about this runner, never an answer: real madsim gives pass /
+ * panic / deadlock / time limit for such a seed, so a report that sets those seeds aside is biased — a genuine failure can hide
+ * behind an overflow.  MADSIM_CAMPAIGN_RESOLVE, honoured by all fifteen campaign entry points, closes the gap: when a harvested
+ * batch reports runner verdicts, the re-runnable seeds are compacted into a seed list on the device, run again under grown limits
+ * in one launch per round, their 48 bytes written back where they were, and the batch's report kernels run once more — so every
+ * field of madsim_campaign_t, madsim_collect_t, madsim_stats_t, madsim_groups_t and madsim_diff_t, and every stop rule, is taken
+ * over the RESOLVED results.  A batch without runner verdicts costs nothing new, and without the flag nothing changes at all.
+ * The contract is per seed.  Let G(L) be the limits madsim_hip_grow_limits gives for one round over L — the growth step of
+ * madsim_hip_run_batch_auto with BOTH the capacities and the step cap grown — and r_j(s) the 48 bytes madsim_hip_run_batch gives
+ * for seed s under G^j(lim).  A result is RE-RUNNABLE under L when its verdict is MADSIM_OVERFLOW, or MADSIM_STEP_LIMIT while L's
+ * step cap is below its ceiling (max_steps_ceiling); MADSIM_UNSUPPORTED and MADSIM_INTERNAL are never re-run.  With R rounds the
+ * resolved result of s is r_k(s) for the smallest k <= R such that k == R or r_k(s) is not re-runnable under G^k(lim).  A round
+ * always grows everything and never looks at which verdicts a batch happened to hold, so the resolved result is a function of the
+ * seed alone: the same bytes whatever `batch`, `in_flight` and the number of contexts.  It can differ from
+ * madsim_hip_run_batch_auto, which grows only what the verdicts at hand ask for, in one corner: a seed that needs more steps only
+ * after its capacities grew.
+ * R rides in flag bits 8-11 (flags |= R << MADSIM_CAMPAIGN_RESOLVE_ROUNDS_SHIFT): 0 means MADSIM_RESOLVE_DEFAULT_ROUNDS, more than
+ * MADSIM_RESOLVE_MAX_ROUNDS with the flag set is MADSIM_E_ARG, and without the flag the bits are ignored.  A resolving campaign's
+ * batch holds fewer than 2^30 seeds.  The differential form resolves each side with that side's own limits before the diff kernels
+ * read the two arrays.  Stop flags are evaluated on the resolved report of each batch (MADSIM_CAMPAIGN_STOP_AT_FAILURE finds a
+ * genuine failure that a first-pass overflow was hiding); n_runner and n_by_verdict[4..7] are what is left after the rounds;
+ * madsim_campaign_t.kernel_ms includes the re-run kernels.  Grown limits that fit no kernel build fail the call as they fail
+ * madsim_hip_run_batch_auto (MADSIM_E_LIMITS), with every stream drained.  Re-run scratch (60 bytes per seed of a batch) is
+ * allocated per flight on first need.
+ * madsim_hip_campaign_resolved / madsim_hip_ctx_campaign_resolved read the account of the most recent campaign call made through
+ * that context (all zero when that call did not resolve, and before any call; the default form also gives zeros when no default
+ * context exists): the shape of madsim_hip_timing_ms.  A _multi call stores the same totals in every context it was given; a
+ * differential call sums its two sides.  Every integer field is a function of the per-seed ladder r_0 .. r_R over the prefix
+ * [seed0, seed0 + seeds_run): batches launched beyond a stopping one contribute nothing. */
+#define MADSIM_CAMPAIGN_RESOLVE 32u              /* re-run runner verdicts on the device before a batch is reported          */
+#define MADSIM_CAMPAIGN_RESOLVE_ROUNDS_SHIFT 8u  /* flag bits 8-11: the number of rounds, 0 = the default                    */
+#define MADSIM_CAMPAIGN_RESOLVE_ROUNDS_MASK 3840u    /* 0xf00 (written in decimal: the header's flag parsers read decimal words)  */
+#define MADSIM_RESOLVE_DEFAULT_ROUNDS 4u
+#define MADSIM_RESOLVE_MAX_ROUNDS 8u
+typedef struct madsim_resolve {
+    uint64_t n_first_pass;        /* seeds of the prefix whose first pass was re-runnable                                      */
+    uint64_t n_resolved;          /* of those, seeds whose resolved verdict is not a runner verdict                            */
+    uint64_t n_unresolved;        /* n_first_pass - n_resolved                                                                 */
+    uint64_t n_by_round[8];       /* [r]: seeds re-run in round r + 1 ([MADSIM_RESOLVE_MAX_ROUNDS])                            */
+    uint64_t batches_resolved;    /* batches of the prefix that needed a round (a differential call: both sides summed)        */
+    uint32_t rounds;              /* the R in force; 0 when the call did not resolve                                           */
+    uint32_t reserved;
+    double   rerun_kernel_ms;     /* sum of the re-run simulation kernels' HIP-event durations (part of kernel_ms)             */
+} madsim_resolve_t;
+int madsim_hip_campaign_resolved(madsim_resolve_t* out);
+int madsim_hip_ctx_campaign_resolved(madsim_hip_ctx_t* ctx, madsim_resolve_t* out);
+/* Host helper, no device needed: *out = G^rounds(*lim) (lim == NULL: the defaults), the limits round `rounds` of a resolving
+ * campaign runs under — which limits a resolved seed needed, and what to hand madsim_hip_run_batch to reproduce r_j(s).  One round:
+ * lanes_per_wave = 0; MADSIM_STATE_COMPACT becomes MADSIM_STATE_AUTO and MADSIM_STATE_NARROW_HEAP is cleared; heap_lds_slots keeps
+ * its value (0 becomes 8); heap_spill_slots, max_tasks, mbox_regs, mbox_msgs, max_conns and chan_queue double from their value or,
+ * from 0, from 32, n_progs + 8, 2, 2, 4 and 2, up to 2^20, 254, 255, 255, 127 and 15; max_steps (0 = 2^24) grows 16-fold up to
+ * max_steps_ceiling (0 = 2^28, and never below the first pass's cap).  MADSIM_E_ARG: w or out NULL, rounds above 64. */
+int madsim_hip_grow_limits(const madsim_workload_t* w, const madsim_limits_t* lim, uint32_t rounds, madsim_limits_t* out);
 
 /* Geometry the library picked for a workload (for DESIGN/bench reporting). */
 typedef struct madsim_geometry {

@@ -454,6 +454,22 @@ struct Builder {
     int device = 0;
     madsim_limits_t capacities{};            // device capacities to start from (no reference counterpart; 0 = defaults);
                                              // capacities.no_trace_hash = 1: results without the determinism-log fingerprint (4 % faster on ping-pong)
+    uint32_t resolve_flags = 0;              // MADSIM_CAMPAIGN_RESOLVE and its rounds bits, set by resolve_runner() (0 = runner verdicts counted apart)
+
+    // search_failures, campaign_stats, failure_groups and diff_against report on SETTLED results: seeds that come back with a runner verdict
+    // (a device capacity, the step cap) are run again on the device under grown limits, up to `rounds` times (0 = the library's default,
+    // at most MADSIM_RESOLVE_MAX_ROUNDS), before their batch is reported (MADSIM_CAMPAIGN_RESOLVE).  resolved() tells what the rounds did.
+    Builder& resolve_runner(unsigned rounds = 0) {
+        if (rounds > MADSIM_RESOLVE_MAX_ROUNDS) throw std::invalid_argument("resolve_runner: at most MADSIM_RESOLVE_MAX_ROUNDS rounds");
+        resolve_flags = MADSIM_CAMPAIGN_RESOLVE | (uint32_t)rounds << MADSIM_CAMPAIGN_RESOLVE_ROUNDS_SHIFT;
+        return *this;
+    }
+    // The resolve account of the most recent campaign call on the default context (madsim_hip_campaign_resolved).
+    static madsim_resolve_t resolved() {
+        madsim_resolve_t r{};
+        madsim::check(madsim_hip_campaign_resolved(&r));
+        return r;
+    }
 
     // builder.rs:64-118
     static Builder from_env() {
@@ -523,7 +539,7 @@ struct Builder {
         madsim_collect_t col{};
         col.failures = max_failures ? f.failures.data() : nullptr;
         col.cap = max_failures;
-        madsim::check(madsim_hip_run_campaign_collect(&w, &cfg, seed, count, 0, 0, 0, &lim, &f.campaign, &col));
+        madsim::check(madsim_hip_run_campaign_collect(&w, &cfg, seed, count, 0, 0, resolve_flags, &lim, &f.campaign, &col));
         f.failures.resize((size_t)col.n_listed);
         for (int v = 0; v < 8; v++) f.by_verdict[(size_t)v] = col.n_by_verdict[v];
         return f;
@@ -550,7 +566,7 @@ struct Builder {
         s.stats.include = include;
         s.stats.top_k = top_k;
         s.stats.top = top_k ? s.top.data() : nullptr;
-        madsim::check(madsim_hip_run_campaign_stats(&w, &cfg, seed, count, 0, 0, 0, &lim, &s.campaign, nullptr, &s.stats));
+        madsim::check(madsim_hip_run_campaign_stats(&w, &cfg, seed, count, 0, 0, resolve_flags, &lim, &s.campaign, nullptr, &s.stats));
         return s;
     }
 
@@ -578,7 +594,7 @@ struct Builder {
         grp.key_field = key_field;
         grp.groups = max_groups ? g.groups.data() : nullptr;
         grp.cap = max_groups;
-        madsim::check(madsim_hip_run_campaign_groups(&w, &cfg, seed, count, 0, 0, 0, &lim, &g.campaign, nullptr, nullptr, &grp));
+        madsim::check(madsim_hip_run_campaign_groups(&w, &cfg, seed, count, 0, 0, resolve_flags, &lim, &g.campaign, nullptr, nullptr, &grp));
         g.groups.resize((size_t)grp.n_groups);
         g.n_grouped = grp.n_grouped;
         g.n_ungrouped = grp.n_ungrouped;
@@ -613,7 +629,7 @@ struct Builder {
         d.report.fields = fields;
         d.report.records = max_listed ? d.records.data() : nullptr;
         d.report.cap = max_listed;
-        madsim::check(madsim_hip_run_campaign_diff(&wa, &ca, &la, &wb, &cb, &lb, seed, count, 0, 0, 0, &d.a, &d.b, &d.report));
+        madsim::check(madsim_hip_run_campaign_diff(&wa, &ca, &la, &wb, &cb, &lb, seed, count, 0, 0, resolve_flags, &d.a, &d.b, &d.report));
         d.records.resize((size_t)d.report.n_listed);
         d.report.records = nullptr;                                       // (the vector may move with the struct)
         return d;

@@ -222,6 +222,21 @@ class Diff(C.Structure):
 assert C.sizeof(DiffRecord) == 104 and C.sizeof(Diff) == 632
 
 
+CAMPAIGN_RESOLVE = 32         # every campaign form: re-run runner verdicts on the device before a batch is reported
+CAMPAIGN_RESOLVE_ROUNDS_SHIFT, CAMPAIGN_RESOLVE_ROUNDS_MASK = 8, 0xF00      # flag bits 8-11: the number of rounds, 0 = the default
+RESOLVE_DEFAULT_ROUNDS, RESOLVE_MAX_ROUNDS = 4, 8
+
+
+class Resolve(C.Structure):
+    """madsim_resolve_t: what the resolve rounds of the most recent campaign call did (madsim_hip_campaign_resolved)."""
+    _fields_ = [("n_first_pass", C.c_uint64), ("n_resolved", C.c_uint64), ("n_unresolved", C.c_uint64), ("n_by_round", C.c_uint64 * 8),
+                ("batches_resolved", C.c_uint64), ("rounds", C.c_uint32), ("reserved", C.c_uint32), ("rerun_kernel_ms", C.c_double)]
+
+
+assert C.sizeof(Resolve) == 112
+HEADER_STRUCTS["madsim_resolve_t"] = Resolve
+
+
 class Geometry(C.Structure):
     _fields_ = [
         ("lds_bytes_per_seed", C.c_uint32), ("lds_bytes_per_block", C.c_uint32), ("block_threads", C.c_uint32),

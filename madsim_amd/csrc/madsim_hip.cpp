@@ -110,7 +110,12 @@ struct madsim_hip_ctx {
                     // counts and the batch's records
                     madsim_result_t* d_out_b = nullptr; size_t cap_b = 0; hipEvent_t b0 = nullptr, b1 = nullptr;
                     unsigned long long* d_drep = nullptr; unsigned long long* h_drep = nullptr; uint32_t* d_dwcnt = nullptr;
-                    madsim_diff_record_t* d_drec = nullptr; size_t drec_cap = 0; };
+                    madsim_diff_record_t* d_drec = nullptr; size_t drec_cap = 0;
+                    // resolving campaigns only, allocated when a batch first needs a round: the seed list, the index list and the re-run results of
+                    // up to rr_cap seeds (60 B per seed), the list kernels' wave counts with the count word behind them (device) and that word's
+                    // page-locked host copy, the re-run kernel's event pair
+                    uint64_t* d_seeds = nullptr; uint32_t* d_idx = nullptr; madsim_result_t* d_rerun = nullptr; size_t rr_cap = 0;
+                    uint32_t* d_rcnt = nullptr; uint32_t* h_rcnt = nullptr; hipEvent_t r0 = nullptr, r1 = nullptr; };
     static constexpr size_t GROUP_REP_WORDS = STATS_REP_WORDS + MADSIM_K_GROUP_WORDS;
     static constexpr size_t DIFF_REP_WORDS = 16 + MADSIM_K_DIFF_WORDS;      // summary6's six words of side A at 0, of side B at 8, the diff words at 16
     Flight flights[CAMPAIGN_MAX];
@@ -123,6 +128,7 @@ struct madsim_hip_ctx {
     hipEvent_t tev[2 * 64] = {};              // timing slots of madsim_hip_run_batch_async
     uint32_t lds_attr = 0;
     uint64_t* d_prof = nullptr;               // debug counters (profiling kernel builds)
+    madsim_resolve_t resolved{};              // the resolve account of the most recent campaign call (madsim_hip_ctx_campaign_resolved)
 
     madsim_geo::Device dev() const {
         madsim_geo::Device d; d.num_cus = num_cus > 0 ? num_cus : 256; d.lds_per_cu = lds_per_cu; d.vgprs = variant_vgprs_cached;
@@ -157,6 +163,7 @@ struct madsim_hip_ctx {
     int ensure_flights(uint32_t n, uint64_t batch, bool staging, bool collect = false, uint64_t records = 0, bool stats = false, uint64_t groups = 0,
                        bool diff = false, uint64_t diff_records = 0);
     uint32_t flights_for(const madsim_workload_t* w, const madsim_config_t* cfg, const madsim_limits_t* lim, uint64_t batch);
+    int ensure_resolve(Flight& f, uint64_t n);
 };
 
 // The library keeps up to five sub-batches of a call in flight, each on its own HIP stream (run_pipelined, campaigns).  ROCclr maps
@@ -240,6 +247,13 @@ void madsim_hip_ctx::close() {
         if (f.h_drep) (void)hipHostFree(f.h_drep);
         if (f.d_dwcnt) (void)hipFree(f.d_dwcnt);
         if (f.d_drec) (void)hipFree(f.d_drec);
+        if (f.d_seeds) (void)hipFree(f.d_seeds);
+        if (f.d_idx) (void)hipFree(f.d_idx);
+        if (f.d_rerun) (void)hipFree(f.d_rerun);
+        if (f.d_rcnt) (void)hipFree(f.d_rcnt);
+        if (f.h_rcnt) (void)hipHostFree(f.h_rcnt);
+        if (f.r0) (void)hipEventDestroy(f.r0);
+        if (f.r1) (void)hipEventDestroy(f.r1);
         if (f.b0) (void)hipEventDestroy(f.b0);
         if (f.b1) (void)hipEventDestroy(f.b1);
         if (f.e0) (void)hipEventDestroy(f.e0);
@@ -554,6 +568,29 @@ int madsim_hip_ctx::ensure_flights(uint32_t n, uint64_t batch, bool staging, boo
             HIP_TRY(hipMalloc(&f.d_drec, diff_records * sizeof(madsim_diff_record_t)));
             f.drec_cap = diff_records;
         }
+    }
+    return 0;
+}
+
+// The re-run scratch of a resolving campaign's flight, for a batch of n seeds: made when a batch of the flight first needs a round (most
+// campaigns never do), kept with the flight, enlarged — with the flight's stream drained — when a later call brings larger batches.
+int madsim_hip_ctx::ensure_resolve(Flight& f, uint64_t n) {
+    if (!f.d_rcnt) {
+        HIP_TRY(hipMalloc(&f.d_rcnt, (MADSIM_K_RESOLVE_WAVES + 1) * sizeof(uint32_t)));
+        HIP_TRY(hipHostMalloc((void**)&f.h_rcnt, sizeof(uint32_t), hipHostMallocDefault));
+        HIP_TRY(hipEventCreate(&f.r0)); HIP_TRY(hipEventCreate(&f.r1));
+    }
+    const size_t want = std::max<size_t>(n, f.cap);         // the flight's batch size: one allocation per campaign
+    if (want > f.rr_cap) {
+        if (f.rr_cap) HIP_TRY(hipStreamSynchronize(f.stream));
+        if (f.d_seeds) (void)hipFree(f.d_seeds);                // (each on its own: an allocation error may have left some of the three)
+        if (f.d_idx) (void)hipFree(f.d_idx);
+        if (f.d_rerun) (void)hipFree(f.d_rerun);
+        f.d_seeds = nullptr; f.d_idx = nullptr; f.d_rerun = nullptr; f.rr_cap = 0;
+        HIP_TRY(hipMalloc(&f.d_seeds, want * sizeof(uint64_t)));
+        HIP_TRY(hipMalloc(&f.d_idx, want * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc(&f.d_rerun, want * sizeof(madsim_result_t)));
+        f.rr_cap = want;
     }
     return 0;
 }
@@ -882,6 +919,28 @@ int madsim_hip_ctx_timing_ms(madsim_hip_ctx_t* c, int timing_slot, double* ms) {
     return 0;
 }
 
+// The resolve account of the most recent campaign call made through the context (the shape of madsim_hip_ctx_timing_ms).
+int madsim_hip_ctx_campaign_resolved(madsim_hip_ctx_t* c, madsim_resolve_t* out) {
+    if (!out) return fail(MADSIM_E_ARG, "null madsim_resolve_t");
+    memset(out, 0, sizeof *out);
+    if (!c || c->device < 0) return fail(MADSIM_E_NOINIT, "no context (madsim_hip_init / madsim_hip_ctx_create has not been called)");
+    std::lock_guard<std::mutex> lk(c->mu);
+    *out = c->resolved;
+    return 0;
+}
+
+// G^rounds(lim): `rounds` applications of the growth step a resolve round (and a re-run round of madsim_hip_run_batch_auto that met both
+// kinds of runner verdict) takes.  No device involved.
+int madsim_hip_grow_limits(const madsim_workload_t* w, const madsim_limits_t* lim, uint32_t rounds, madsim_limits_t* out) {
+    if (!w || !out) return fail(MADSIM_E_ARG, "madsim_hip_grow_limits: null workload or result");
+    if (rounds > 64) return fail(MADSIM_E_ARG, "madsim_hip_grow_limits: at most 64 rounds");
+    madsim_limits_t L{};
+    if (lim) L = *lim;
+    for (uint32_t r = 0; r < rounds; r++) grow(L, w, true, true);
+    *out = L;
+    return 0;
+}
+
 int madsim_hip_ctx_run_batch_auto(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t count,
                                   const madsim_limits_t* lim, madsim_result_t* out, madsim_summary_t* summary, int max_rounds) {
     if (!out && count) return fail(MADSIM_E_ARG, "run_batch_auto needs the result array");
@@ -1104,12 +1163,84 @@ uint64_t pump_batches(madsim_hip_ctx* const* ctxs, int n_ctx, uint64_t n_batches
 }
 }  // extern "C++"
 
+// ---- resolving campaigns (MADSIM_CAMPAIGN_RESOLVE) ---------------------------------------------------------------------------------
+// The rounds a call's flags ask for (0: the call does not resolve), and the one argument error they can hold — told, like the other
+// argument errors, before any context is looked at.
+uint32_t resolve_rounds(uint32_t flags) {
+    if (!(flags & MADSIM_CAMPAIGN_RESOLVE)) return 0;
+    const uint32_t r = (flags & MADSIM_CAMPAIGN_RESOLVE_ROUNDS_MASK) >> MADSIM_CAMPAIGN_RESOLVE_ROUNDS_SHIFT;
+    return r ? r : MADSIM_RESOLVE_DEFAULT_ROUNDS;
+}
+int check_resolve_flags(uint32_t flags) {
+    if (resolve_rounds(flags) > MADSIM_RESOLVE_MAX_ROUNDS) return fail(MADSIM_E_ARG, "MADSIM_CAMPAIGN_RESOLVE: at most MADSIM_RESOLVE_MAX_ROUNDS (8) rounds");
+    return 0;
+}
+
+// A campaign call's resolve account: zeroed in every context of the call when it starts, stored in every one when it ends (errors included).
+struct ResolveAccount {
+    madsim_hip_ctx* const* ctxs; int n_ctx; madsim_resolve_t a{};
+    ResolveAccount(madsim_hip_ctx* const* c, int n, uint32_t rounds) : ctxs(c), n_ctx(n) { a.rounds = rounds; store(); }
+    ~ResolveAccount() { a.n_unresolved = a.n_first_pass - a.n_resolved; store(); }
+    void store() { for (int g = 0; g < n_ctx; g++) ctxs[g]->resolved = a; }
+};
+
+// The rounds of one harvested batch, all on the flight's own stream (its scratch is keyed by the stream, and the other flights keep running):
+// d_res[0 .. n) are the results of seeds seed_lo .. under `lim`.  Round r compacts the seeds whose result is re-runnable under G^(r-1)(lim)
+// (madsim_k_launch_resolve_list), reads the one count word, and — unless it is 0 — runs them in one launch under G^r(lim) and writes their
+// new results where the old ones were (madsim_k_launch_resolve_scatter).  Every round grows everything (grow(.., true, true)): what a seed
+// ends with does not depend on its batch.  On return the stream holds nothing unfinished but the last scatter; *ran = a round ran, so the
+// caller's report is stale.
+int resolve_results(madsim_hip_ctx* c, madsim_hip_ctx::Flight& f, const madsim_workload_t* w, const madsim_config_t* cfg, const madsim_limits_t* lim,
+                    madsim_result_t* d_res, uint64_t seed_lo, uint64_t n, uint32_t rounds, madsim_resolve_t& acct, double* rerun_ms, bool* ran) {
+    madsim_limits_t L{};
+    if (lim) L = *lim;
+    int e;
+    if ((e = c->ensure_resolve(f, n))) return e;
+    uint32_t* const d_total = f.d_rcnt + MADSIM_K_RESOLVE_WAVES;
+    bool timed = false;                                          // an event pair recorded and not yet read
+    auto take_ms = [&]() -> int {
+        if (!timed) return 0;
+        float t = 0.f;
+        HIP_TRY(hipEventElapsedTime(&t, f.r0, f.r1));
+        *rerun_ms += t; timed = false;
+        return 0;
+    };
+    for (uint32_t r = 1; r <= rounds; r++) {
+        const uint32_t steps_maxed = (L.max_steps ? L.max_steps : (1u << 24)) >= step_ceiling(L) ? 1u : 0u;
+        if (madsim_k_launch_resolve_list(d_res, n, seed_lo, steps_maxed, f.d_rcnt, d_total, f.d_seeds, f.d_idx, f.stream))
+            return fail(MADSIM_E_ARG, "madsim_k_launch_resolve_list refused the batch's size");
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(f.h_rcnt, d_total, sizeof(uint32_t), hipMemcpyDeviceToHost, f.stream));
+        HIP_TRY(hipStreamSynchronize(f.stream));
+        if ((e = take_ms())) return e;
+        const uint64_t m = *f.h_rcnt;
+        if (m == 0) break;
+        if (m > n || m > f.rr_cap) return fail(MADSIM_E_HIP, "resolve: a batch lists more re-runnable seeds than it holds");
+        if (r == 1) { acct.n_first_pass += m; acct.batches_resolved++; }
+        acct.n_by_round[r - 1] += m;
+        grow(L, w, true, true);
+        HIP_TRY(hipEventRecord(f.r0, f.stream));
+        if ((e = c->launch(w, cfg, 0, m, f.d_seeds, &L, f.d_rerun, f.stream))) return e;
+        HIP_TRY(hipEventRecord(f.r1, f.stream));
+        timed = true;
+        if (madsim_k_launch_resolve_scatter(d_res, f.d_rerun, f.d_idx, m, f.stream))
+            return fail(MADSIM_E_ARG, "madsim_k_launch_resolve_scatter refused the list's size");
+        HIP_TRY(hipGetLastError());
+        *ran = true;
+    }
+    if (timed) { HIP_TRY(hipStreamSynchronize(f.stream)); if ((e = take_ms())) return e; }      // (the last of the rounds ran: no list pair behind it)
+    return 0;
+}
+
 int run_campaign_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total,
                       uint64_t batch, uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim, madsim_campaign_t* out,
                       madsim_collect_t* col = nullptr, madsim_stats_t* st = nullptr, madsim_groups_t* grp = nullptr) {
     auto t0 = std::chrono::steady_clock::now();
     memset(out, 0, sizeof *out);
     out->first_failing_seed = UINT64_MAX;
+    const uint32_t R = resolve_rounds(flags);                   // 0: runner verdicts are counted apart, as ever
+    ResolveAccount account(ctxs, n_ctx, R);
+    madsim_resolve_t& acct = account.a;
     if (st) {
         st->n = st->n_top = 0;
         memset(st->metric, 0, sizeof st->metric);
@@ -1128,6 +1259,7 @@ int run_campaign_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workl
     if (seed0 + total < seed0) return fail(MADSIM_E_ARG, "seed0 + total wraps");
     if (total == 0) return 0;
     if (st && std::min(batch, total) >= 0xffffffffull) return fail(MADSIM_E_ARG, "a statistics campaign's batch holds fewer than 2^32 - 1 seeds");
+    if (R && std::min(batch, total) >= (1ull << 30)) return fail(MADSIM_E_ARG, "a resolving campaign's batch holds fewer than 2^30 seeds");
     const uint64_t n_batches = (total + batch - 1) / batch, N = (uint64_t)n_ctx;
     const uint64_t rec_batch = col ? std::min(col->cap, std::min(batch, total)) : 0;      // records a flight holds: no batch lists more
     // a grouping campaign's report: the sixteen words, the statistics words when asked for, then the grouping words; its table is sized to the batch
@@ -1146,24 +1278,23 @@ int run_campaign_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workl
     int first_err = 0;
     std::string first_msg;
     auto flight_of = [&](uint64_t k) -> madsim_hip_ctx::Flight& { const int g = (int)(k % N); return ctxs[g]->flights[(k / N) % F[g]]; };
-    auto queue = [&](uint64_t k) -> int {
-        madsim_hip_ctx* c = ctxs[k % N];
-        madsim_hip_ctx::Flight& f = flight_of(k);
-        const uint64_t lo = k * batch, n = std::min(batch, total - lo);
-        int e;
-        if ((e = c->bind())) return e;
+    // A batch's report chain, in two parts that `queue` puts around the simulation launch and a resolving `harvest` queues again back to
+    // back: the report words made ready, then the report kernels over f.d_out, the copy of the words and the `done` event.
+    const size_t n_words = grp ? goff + MADSIM_K_GROUP_WORDS
+                               : st ? madsim_hip_ctx::STATS_REP_WORDS - (st->top_k ? 0 : 2 * MADSIM_STAT_METRICS * MADSIM_STAT_MAX_TOP)
+                               : col ? MADSIM_K_COLLECT_WORDS : 6;
+    auto words_of = [&](madsim_hip_ctx::Flight& f) -> unsigned long long* { return grp ? f.d_grep : st ? f.d_srep : col ? f.d_rep : f.d_acc6; };
+    auto prepare_report = [&](madsim_hip_ctx::Flight& f) -> int {
         // the same four memsets, the last one longer when collecting, and longer still with statistics (whose words all start as zero)
-        unsigned long long* const d_words = grp ? f.d_grep : st ? f.d_srep : col ? f.d_rep : f.d_acc6;
-        const size_t n_words = grp ? goff + MADSIM_K_GROUP_WORDS
-                                   : st ? madsim_hip_ctx::STATS_REP_WORDS - (st->top_k ? 0 : 2 * MADSIM_STAT_METRICS * MADSIM_STAT_MAX_TOP)
-                                   : col ? MADSIM_K_COLLECT_WORDS : 6;
+        unsigned long long* const d_words = words_of(f);
         HIP_TRY(hipMemsetAsync(d_words, 0xff, 8, f.stream));
         HIP_TRY(hipMemsetAsync((char*)d_words + 8, 0, 24, f.stream));
         HIP_TRY(hipMemsetAsync((char*)d_words + 32, 0xff, 8, f.stream));
         HIP_TRY(hipMemsetAsync((char*)d_words + 40, 0, (n_words - 5) * 8, f.stream));
-        HIP_TRY(hipEventRecord(f.e0, f.stream));
-        if ((e = c->launch(w, cfg, seed0 + lo, n, nullptr, lim, f.d_out, f.stream))) return e;
-        HIP_TRY(hipEventRecord(f.e1, f.stream));
+        return 0;
+    };
+    auto queue_report = [&](madsim_hip_ctx::Flight& f, uint64_t lo, uint64_t n) -> int {
+        unsigned long long* const d_words = words_of(f);
         if (col) madsim_k_launch_collect(f.d_out, n, seed0 + lo, (flags & MADSIM_CAMPAIGN_LIST_RUNNER) ? 1u : 0u, d_words, f.d_wcnt, f.d_rec,
                                          std::min(rec_batch, n), f.stream);
         else madsim_k_launch_summary6(f.d_out, n, seed0 + lo, d_words, f.stream);
@@ -1182,6 +1313,18 @@ int run_campaign_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workl
         HIP_TRY(hipEventRecord(f.done, f.stream));
         return 0;
     };
+    auto queue = [&](uint64_t k) -> int {
+        madsim_hip_ctx* c = ctxs[k % N];
+        madsim_hip_ctx::Flight& f = flight_of(k);
+        const uint64_t lo = k * batch, n = std::min(batch, total - lo);
+        int e;
+        if ((e = c->bind())) return e;
+        if ((e = prepare_report(f))) return e;
+        HIP_TRY(hipEventRecord(f.e0, f.stream));
+        if ((e = c->launch(w, cfg, seed0 + lo, n, nullptr, lim, f.d_out, f.stream))) return e;
+        HIP_TRY(hipEventRecord(f.e1, f.stream));
+        return queue_report(f, lo, n);
+    };
     bool stop = false;
     auto harvest = [&](uint64_t k) -> int {                     // wait for batch k, fold its report (batches are read in order)
         madsim_hip_ctx* c = ctxs[k % N];
@@ -1196,6 +1339,19 @@ int run_campaign_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workl
         HIP_TRY(hipEventElapsedTime(&ms, f.e0, f.e1));
         if (!stop) {                                            // batches launched beyond the failing one are not part of the answer
             const unsigned long long* a = grp ? f.h_grep : st ? f.h_srep : col ? f.h_rep : f.h_acc6;
+            if (R && a[5] > 0) {                                // runner verdicts in a batch that is part of the answer: settle them, report again
+                const unsigned long long runner_before = a[5];
+                double rerun_ms = 0.0;
+                bool ran = false;
+                if ((e = resolve_results(c, f, w, cfg, lim, f.d_out, seed0 + lo, n, R, acct, &rerun_ms, &ran))) return e;
+                acct.rerun_kernel_ms += rerun_ms; out->kernel_ms += rerun_ms;
+                if (ran) {                                      // (the grouping table is clean: the first chain's extraction pass left it so)
+                    if ((e = prepare_report(f)) || (e = queue_report(f, lo, n))) return e;
+                    HIP_TRY(hipEventSynchronize(f.done));
+                    f.grp_dirty = false;
+                    acct.n_resolved += runner_before - a[5];
+                }
+            }
             out->kernel_ms += ms;
             out->batches_run++; out->seeds_run += n;
             out->n_runner += a[5];
@@ -1249,7 +1405,10 @@ int run_campaign_diff_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const DiffSid
     d->n_listed = d->n_compared = d->n_incomparable = d->n_differ = 0;
     memset(d->n_by_field, 0, sizeof d->n_by_field);
     memset(d->transitions, 0, sizeof d->transitions);
-    flags &= MADSIM_CAMPAIGN_STOP_AT_DIFFS;                      // (the other stop flags belong to the other forms)
+    flags &= MADSIM_CAMPAIGN_STOP_AT_DIFFS | MADSIM_CAMPAIGN_RESOLVE | MADSIM_CAMPAIGN_RESOLVE_ROUNDS_MASK;      // (the other stop flags belong to the other forms)
+    const uint32_t R = resolve_rounds(flags);
+    ResolveAccount account(ctxs, n_ctx, R);
+    madsim_resolve_t& acct = account.a;
     for (int s = 0; s < 2; s++)
         if (int rc = madsim_geo::validate(side[s].w, side[s].cfg, &g_err)) return fail(rc, std::string(s ? "side B: " : "side A: ") + g_err);
     if (batch == 0) batch = 65536;
@@ -1257,6 +1416,7 @@ int run_campaign_diff_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const DiffSid
     if (seed0 + total < seed0) return fail(MADSIM_E_ARG, "seed0 + total wraps");
     if (total == 0) return 0;
     if (std::min(batch, total) >= (1ull << 32)) return fail(MADSIM_E_ARG, "a differential campaign's batch holds fewer than 2^32 seeds");
+    if (R && std::min(batch, total) >= (1ull << 30)) return fail(MADSIM_E_ARG, "a resolving campaign's batch holds fewer than 2^30 seeds");
     const uint64_t n_batches = (total + batch - 1) / batch, N = (uint64_t)n_ctx;
     const uint64_t rec_batch = std::min(d->cap, std::min(batch, total));      // records a flight holds: no batch lists more
     int rc;
@@ -1275,29 +1435,41 @@ int run_campaign_diff_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const DiffSid
     std::string first_msg;
     bool stop = false;
     auto flight_of = [&](uint64_t k) -> madsim_hip_ctx::Flight& { const int g = (int)(k % N); return ctxs[g]->flights[(k / N) % F[g]]; };
-    auto queue = [&](uint64_t k) -> int {
-        madsim_hip_ctx* c = ctxs[k % N];
-        madsim_hip_ctx::Flight& f = flight_of(k);
-        const uint64_t lo = k * batch, n = std::min(batch, total - lo);
-        int e;
-        if ((e = c->bind())) return e;
+    // A batch's report chain in the parts that `queue` puts around the two simulation launches and a resolving `harvest` queues again back
+    // to back: the words reset by one device copy, a side's summary6 over its results, then the diff kernels, the copy and the `done` event.
+    auto prepare_report = [&](madsim_hip_ctx::Flight& f) -> int {
         HIP_TRY(hipMemcpyAsync(f.d_drep, f.d_drep + n_words, n_words * sizeof(unsigned long long), hipMemcpyDeviceToDevice, f.stream));
-        HIP_TRY(hipEventRecord(f.e0, f.stream));
-        if ((e = c->launch(side[0].w, side[0].cfg, seed0 + lo, n, nullptr, side[0].lim, f.d_out, f.stream))) return fail(e, "side A: " + g_err);
-        HIP_TRY(hipEventRecord(f.e1, f.stream));
-        madsim_k_launch_summary6(f.d_out, n, seed0 + lo, f.d_drep, f.stream);
+        return 0;
+    };
+    auto queue_summary = [&](madsim_hip_ctx::Flight& f, int s, uint64_t lo, uint64_t n) -> int {
+        madsim_k_launch_summary6(s ? f.d_out_b : f.d_out, n, seed0 + lo, f.d_drep + 8 * s, f.stream);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(f.b0, f.stream));
-        if ((e = c->launch(side[1].w, side[1].cfg, seed0 + lo, n, nullptr, side[1].lim, f.d_out_b, f.stream))) return fail(e, "side B: " + g_err);
-        HIP_TRY(hipEventRecord(f.b1, f.stream));
-        madsim_k_launch_summary6(f.d_out_b, n, seed0 + lo, f.d_drep + 8, f.stream);
-        HIP_TRY(hipGetLastError());
+        return 0;
+    };
+    auto queue_diff = [&](madsim_hip_ctx::Flight& f, uint64_t lo, uint64_t n) -> int {
         if (madsim_k_launch_diff(f.d_out, f.d_out_b, n, seed0 + lo, d->fields, f.d_drep + 16, f.d_dwcnt, f.d_drec, std::min(rec_batch, n), f.stream))
             return fail(MADSIM_E_ARG, "madsim_k_launch_diff refused the batch's arguments");
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(f.h_drep, f.d_drep, n_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, f.stream));
         HIP_TRY(hipEventRecord(f.done, f.stream));
         return 0;
+    };
+    auto queue = [&](uint64_t k) -> int {
+        madsim_hip_ctx* c = ctxs[k % N];
+        madsim_hip_ctx::Flight& f = flight_of(k);
+        const uint64_t lo = k * batch, n = std::min(batch, total - lo);
+        int e;
+        if ((e = c->bind())) return e;
+        if ((e = prepare_report(f))) return e;
+        HIP_TRY(hipEventRecord(f.e0, f.stream));
+        if ((e = c->launch(side[0].w, side[0].cfg, seed0 + lo, n, nullptr, side[0].lim, f.d_out, f.stream))) return fail(e, "side A: " + g_err);
+        HIP_TRY(hipEventRecord(f.e1, f.stream));
+        if ((e = queue_summary(f, 0, lo, n))) return e;
+        HIP_TRY(hipEventRecord(f.b0, f.stream));
+        if ((e = c->launch(side[1].w, side[1].cfg, seed0 + lo, n, nullptr, side[1].lim, f.d_out_b, f.stream))) return fail(e, "side B: " + g_err);
+        HIP_TRY(hipEventRecord(f.b1, f.stream));
+        if ((e = queue_summary(f, 1, lo, n))) return e;
+        return queue_diff(f, lo, n);
     };
     auto harvest = [&](uint64_t k) -> int {
         madsim_hip_ctx* c = ctxs[k % N];
@@ -1310,6 +1482,22 @@ int run_campaign_diff_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const DiffSid
         float ms[2] = {0.f, 0.f};
         HIP_TRY(hipEventElapsedTime(&ms[0], f.e0, f.e1));
         HIP_TRY(hipEventElapsedTime(&ms[1], f.b0, f.b1));
+        if (R && (f.h_drep[5] > 0 || f.h_drep[8 + 5] > 0)) {    // runner verdicts on a side: settle them under that side's own limits, diff again
+            const unsigned long long runner_before[2] = {f.h_drep[5], f.h_drep[8 + 5]};
+            bool ran = false;
+            for (int s = 0; s < 2; s++) {                       // (one after the other on the flight's stream: they share its re-run scratch)
+                if (!runner_before[s]) continue;
+                double rerun_ms = 0.0;
+                if ((e = resolve_results(c, f, side[s].w, side[s].cfg, side[s].lim, s ? f.d_out_b : f.d_out, seed0 + lo, n, R, acct, &rerun_ms, &ran)))
+                    return fail(e, std::string(s ? "side B: " : "side A: ") + g_err);
+                acct.rerun_kernel_ms += rerun_ms; side[s].out->kernel_ms += rerun_ms;
+            }
+            if (ran) {
+                if ((e = prepare_report(f)) || (e = queue_summary(f, 0, lo, n)) || (e = queue_summary(f, 1, lo, n)) || (e = queue_diff(f, lo, n))) return e;
+                HIP_TRY(hipEventSynchronize(f.done));
+                acct.n_resolved += (runner_before[0] - f.h_drep[5]) + (runner_before[1] - f.h_drep[8 + 5]);
+            }
+        }
         for (int s = 0; s < 2; s++) {
             const unsigned long long* a = f.h_drep + 8 * s;
             madsim_campaign_t* out = side[s].out;
@@ -1339,6 +1527,7 @@ int run_campaign_diff_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const DiffSid
 int madsim_hip_ctx_run_campaign(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total,
                                 uint64_t batch, uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim, madsim_campaign_t* out) {
     if (!out) return fail(MADSIM_E_ARG, "null campaign report");
+    if (int rc = check_resolve_flags(flags)) return rc;
     CTX_ENTER(c);
     madsim_hip_ctx* one[1] = {c};
     return run_campaign_impl(one, 1, w, cfg, seed0, total, batch, in_flight, flags, lim, out);
@@ -1348,6 +1537,7 @@ int madsim_hip_run_campaign_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, cons
                                   uint64_t seed0, uint64_t total, uint64_t batch, uint32_t in_flight, uint32_t flags,
                                   const madsim_limits_t* lim, madsim_campaign_t* out) {
     if (!out) return fail(MADSIM_E_ARG, "null campaign report");
+    if (int rc = check_resolve_flags(flags)) return rc;
     if (!ctxs || n_ctx < 1) return fail(MADSIM_E_ARG, "run_campaign_multi needs at least one context");
     for (int g = 0; g < n_ctx; g++) {
         if (!ctxs[g]) return fail(MADSIM_E_NOINIT, "null context");
@@ -1368,6 +1558,7 @@ int check_collect_args(const madsim_campaign_t* out, const madsim_collect_t* col
     if (!col) return fail(MADSIM_E_ARG, "null madsim_collect_t (madsim_hip_run_campaign is the form without a failure list)");
     if (col->cap && !col->failures) return fail(MADSIM_E_ARG, "madsim_collect_t.cap > 0 without a failures array");
     if ((flags & MADSIM_CAMPAIGN_STOP_AT_CAP) && !col->cap) return fail(MADSIM_E_ARG, "MADSIM_CAMPAIGN_STOP_AT_CAP with cap == 0");
+    if (int rc = check_resolve_flags(flags)) return rc;
     if (in_flight > (uint32_t)madsim_hip_ctx::CAMPAIGN_MAX) return fail(MADSIM_E_ARG, "at most 8 batches in flight per context");
     return 0;
 }
@@ -1407,6 +1598,7 @@ int check_stats_args(const madsim_campaign_t* out, const madsim_collect_t* col, 
     if (st->include == 0 || (st->include & ~0xfu)) return fail(MADSIM_E_ARG, "madsim_stats_t.include: at least one of bits 0-3 (PASS, PANIC, DEADLOCK, TIME_LIMIT), no other");
     if (st->top_k > MADSIM_STAT_MAX_TOP) return fail(MADSIM_E_ARG, "madsim_stats_t.top_k > MADSIM_STAT_MAX_TOP");
     if (st->top_k && !st->top) return fail(MADSIM_E_ARG, "madsim_stats_t.top_k > 0 without a top array");
+    if (int rc = check_resolve_flags(flags)) return rc;
     if (col) return check_collect_args(out, col, in_flight, flags);
     if (in_flight > (uint32_t)madsim_hip_ctx::CAMPAIGN_MAX) return fail(MADSIM_E_ARG, "at most 8 batches in flight per context");
     return 0;
@@ -1449,6 +1641,7 @@ int check_groups_args(const madsim_campaign_t* out, const madsim_collect_t* col,
     if (grp->key_field >= MADSIM_GROUP_KEYS) return fail(MADSIM_E_ARG, "madsim_groups_t.key_field: one of MADSIM_GROUP_KEY_*");
     if (grp->cap && !grp->groups) return fail(MADSIM_E_ARG, "madsim_groups_t.cap > 0 without a groups array");
     if ((flags & MADSIM_CAMPAIGN_STOP_AT_GROUPS) && !grp->cap) return fail(MADSIM_E_ARG, "MADSIM_CAMPAIGN_STOP_AT_GROUPS with cap == 0");
+    if (int rc = check_resolve_flags(flags)) return rc;
     if (std::min(batch ? batch : 65536, total) > MADSIM_GROUP_MAX_BATCH)
         return fail(MADSIM_E_ARG, "a grouping campaign's batch holds at most MADSIM_GROUP_MAX_BATCH (2^20) seeds: the device table is sized to the batch");
     if (st) return check_stats_args(out, col, st, in_flight, flags);
@@ -1494,6 +1687,7 @@ int check_diff_args(const madsim_campaign_t* outA, const madsim_campaign_t* outB
     if (d->reserved) return fail(MADSIM_E_ARG, "madsim_diff_t.reserved must be 0");
     if (d->cap && !d->records) return fail(MADSIM_E_ARG, "madsim_diff_t.cap > 0 without a records array");
     if ((flags & MADSIM_CAMPAIGN_STOP_AT_DIFFS) && !d->cap) return fail(MADSIM_E_ARG, "MADSIM_CAMPAIGN_STOP_AT_DIFFS with cap == 0");
+    if (int rc = check_resolve_flags(flags)) return rc;
     if (in_flight > (uint32_t)madsim_hip_ctx::CAMPAIGN_MAX) return fail(MADSIM_E_ARG, "at most 8 batches in flight per context");
     return 0;
 }
@@ -1592,6 +1786,12 @@ int madsim_hip_run_batch_async(const madsim_workload_t* w, const madsim_config_t
 }
 
 int madsim_hip_timing_ms(int timing_slot, double* ms) { DefaultPin p; return madsim_hip_ctx_timing_ms(p.c, timing_slot, ms); }
+
+int madsim_hip_campaign_resolved(madsim_resolve_t* out) {
+    DefaultPin p;
+    if (out && !p.c) { memset(out, 0, sizeof *out); return 0; }      // no default context: no campaign has run through it
+    return madsim_hip_ctx_campaign_resolved(p.c, out);
+}
 
 int64_t madsim_hip_trace_seed(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed,
                               const madsim_limits_t* lim, uint8_t* log, uint64_t cap, madsim_result_t* out) {

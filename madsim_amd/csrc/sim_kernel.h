@@ -367,6 +367,18 @@ int  madsim_k_launch_diff(const madsim_result_t* a, const madsim_result_t* b, ui
 // Returns how many of the batch's records the list still takes — min(the batch's n_differ, cap - n_listed) — and advances n_listed by it;
 // when `batch_recs` (host memory, at least that many) is given they are appended to diff->records, otherwise the caller copies them there.
 uint64_t madsim_k_fold_diff(madsim_diff_t* diff, const unsigned long long* words, uint64_t count, const madsim_diff_record_t* batch_recs);
+// resolving campaigns (MADSIM_CAMPAIGN_RESOLVE).  The list pair, over collect's cut of the batch: a result is re-runnable when its verdict is
+// MADSIM_OVERFLOW, or MADSIM_STEP_LIMIT with `steps_maxed` == 0.  *total = m, the re-runnable seeds of out[0 .. count); seeds[0 .. m) =
+// seed0 + i and idx[0 .. m) = i of those results, ascending, the same on every run; nothing behind m is written.  `wave_cnt`:
+// MADSIM_K_RESOLVE_WAVES words of scratch; nothing needs preparing.  Returns 0, or -1 without launching anything for count == 0 or
+// count >= 2^32 (the index list is 32-bit).
+#define MADSIM_K_RESOLVE_WAVES 1024u    /* = MADSIM_K_COLLECT_WAVES: the same cut            */
+#define MADSIM_K_RESOLVE_CHUNKS 3u      /* 16-byte chunks of a madsim_result_t               */
+int  madsim_k_launch_resolve_list(const madsim_result_t* out, uint64_t count, uint64_t seed0, uint32_t steps_maxed, uint32_t* wave_cnt,
+                                  uint32_t* total, uint64_t* seeds, uint32_t* idx, void* stream);
+// out[idx[j]] = rerun[j] for j < m, 48 bytes each as three 16-byte chunks (thread t: chunk t % 3 of record t / 3); idx: distinct indices into
+// `out`, nothing else of which is touched.  m == 0 launches nothing.  Returns 0, or -1 without launching anything for 3 * m >= 2^32.
+int  madsim_k_launch_resolve_scatter(madsim_result_t* out, const madsim_result_t* rerun, const uint32_t* idx, uint64_t m, void* stream);
 int  madsim_k_set_max_lds(uint32_t lds_bytes);
 int  madsim_k_variant_vgprs(const madsim_k::VariantSel* v);
 void madsim_k_launch_keyflip(unsigned long long* acc, void* stream);

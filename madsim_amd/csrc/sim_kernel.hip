@@ -573,6 +573,74 @@ __global__ __launch_bounds__(256) void diff_write_kernel(const madsim_result_t* 
 
 __global__ void keyflip_kernel(unsigned long long* acc) { acc[0] ^= 0x8000000000000000ull; }
 
+// ---- resolving campaigns: which seeds of a batch are run again, and their new results back in place ----------------------------
+// A result is RE-RUNNABLE when its verdict is MADSIM_OVERFLOW, or MADSIM_STEP_LIMIT while the step cap can still grow (steps_maxed == 0):
+// rerun_runner_verdicts' rule (madsim_hip.cpp).  The list pair runs over collect's cut of the batch — wave W owns a contiguous piece, so
+// ascending wave then ascending lane is ascending seed order: resolve_count_kernel reads the 16-byte head of every result and leaves every
+// wave's number of re-runnable seeds in wave_cnt[W]; resolve_write_kernel gives a wave the exclusive prefix of wave_cnt as its offset and
+// writes, for each re-runnable seed i of its piece, seed0 + i into `seeds` and i into `idx` at rank = offset + its position in the ballot.
+// Wave 0 also leaves the total in *total.  No atomic anywhere: the lists are the same on every run, and nothing behind the total is
+// written.  A wave without re-runnable seeds leaves after one load.  count < 2^32 (the index list is 32-bit).
+__device__ __forceinline__ bool resolve_rerunnable(uint32_t verdict, uint32_t steps_maxed) {
+    return verdict == MADSIM_OVERFLOW || (verdict == MADSIM_STEP_LIMIT && !steps_maxed);
+}
+
+__global__ __launch_bounds__(256) void resolve_count_kernel(const madsim_result_t* __restrict__ out, uint64_t count, uint64_t piece,
+                                                            uint32_t steps_maxed, uint32_t* __restrict__ wave_cnt) {
+    const uint32_t W = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const uint64_t lo = (uint64_t)W * piece, hi = lo + piece < count ? lo + piece : count;
+    uint32_t n = 0;                                                                // wave-uniform (popcounts of ballots)
+    for (uint64_t base = lo; base < hi; base += 64) {
+        const uint64_t i = base + lane;
+        uint32_t v = MADSIM_PASS;
+        if (i < hi) v = reinterpret_cast<const uint4*>(out + i)[0].x;
+        n += (uint32_t)__popcll(__ballot(resolve_rerunnable(v, steps_maxed)));
+    }
+    if (lane == 0) wave_cnt[W] = n;
+}
+
+__global__ __launch_bounds__(256) void resolve_write_kernel(const madsim_result_t* __restrict__ out, uint64_t count, uint64_t seed0,
+                                                            uint64_t piece, uint32_t steps_maxed, const uint32_t* __restrict__ wave_cnt,
+                                                            uint32_t n_waves, uint32_t* __restrict__ total, uint64_t* __restrict__ seeds,
+                                                            uint32_t* __restrict__ idx) {
+    const uint32_t W = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (W == 0) {                                                                  // the total: every wave's count, summed by the first wave
+        uint32_t t = 0;
+        for (uint32_t j = lane; j < n_waves; j += 64) t += wave_cnt[j];
+        for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
+        if (lane == 0) *total = t;
+    }
+    if (wave_cnt[W] == 0) return;                                                  // (wave-uniform)
+    uint32_t at = 0;                                                               // re-runnable seeds of the waves before this one
+    for (uint32_t j = lane; j < W; j += 64) at += wave_cnt[j];
+    for (int o = 32; o > 0; o >>= 1) at += __shfl_xor(at, o);
+    const uint64_t lo = (uint64_t)W * piece, hi = lo + piece < count ? lo + piece : count;
+    for (uint64_t base = lo; base < hi; base += 64) {
+        const uint64_t i = base + lane;
+        uint32_t v = MADSIM_PASS;
+        if (i < hi) v = reinterpret_cast<const uint4*>(out + i)[0].x;
+        const bool mine = resolve_rerunnable(v, steps_maxed);
+        const unsigned long long m = __ballot(mine);
+        if (mine) {
+            const uint32_t rank = at + lanes_below(m);
+            seeds[rank] = seed0 + i;
+            idx[rank] = (uint32_t)i;
+        }
+        at += (uint32_t)__popcll(m);
+    }
+}
+
+// out[idx[j]] = rerun[j] for j < m: a 48-byte record is three 16-byte chunks and thread t moves chunk t % 3 of record t / 3, so the reads of
+// the compact re-run array are one contiguous run of 16-byte loads.  Nothing else of `out` is touched; the indices are distinct.
+__global__ __launch_bounds__(256) void resolve_scatter_kernel(madsim_result_t* __restrict__ out, const madsim_result_t* __restrict__ rerun,
+                                                              const uint32_t* __restrict__ idx, uint32_t m) {
+    const uint64_t t = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    const uint64_t j = t / 3;
+    if (j >= m) return;
+    const uint32_t chunk = (uint32_t)(t - 3 * j);
+    reinterpret_cast<uint4*>(out + idx[j])[chunk] = reinterpret_cast<const uint4*>(rerun)[t];
+}
+
 // one kernel per row of variant_table (sim_kernel.h), same macro, same order
 #define MADSIM_VARIANT_KERNEL(T_, S_, L_, F_, R_, G_) (const void*)sim_kernel<Variant<T_, S_, L_, F_, R_, G_>>,
 static const void* const variant_kernels[] = {MADSIM_FOR_EACH_VARIANT(MADSIM_VARIANT_KERNEL)};
@@ -671,6 +739,32 @@ extern "C" int madsim_k_launch_diff(const madsim_result_t* a, const madsim_resul
     hipLaunchKernelGGL(madsim_k::diff_count_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, a, b, count, piece, fields, words, wave_cnt);
     hipLaunchKernelGGL(madsim_k::diff_write_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, a, b, count, seed0, piece, fields, words,
                        (const uint32_t*)wave_cnt, recs, cap);
+    return 0;
+}
+
+// wave_cnt: MADSIM_K_RESOLVE_WAVES words of scratch; total: one word; seeds / idx: room for `count` entries each, the first *total written
+// (sim_kernel.h).  Returns 0, or -1 (nothing launched) for count == 0 or count >= 2^32.
+extern "C" int madsim_k_launch_resolve_list(const madsim_result_t* out, uint64_t count, uint64_t seed0, uint32_t steps_maxed, uint32_t* wave_cnt,
+                                            uint32_t* total, uint64_t* seeds, uint32_t* idx, void* stream) {
+    static_assert(madsim_k::COLLECT_MAX_WAVES == MADSIM_K_RESOLVE_WAVES && sizeof(madsim_result_t) == 48, "sim_kernel.h");
+    if (count == 0 || count >= (1ull << 32)) return -1;
+    uint32_t grid = (uint32_t)((count + 1023) / 1024);     // collect's cut
+    if (grid > 256) grid = 256;
+    const uint64_t waves = 4ull * grid, piece = ((count + waves - 1) / waves + 63) / 64 * 64;
+    hipLaunchKernelGGL(madsim_k::resolve_count_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, out, count, piece, steps_maxed ? 1u : 0u, wave_cnt);
+    hipLaunchKernelGGL(madsim_k::resolve_write_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, out, count, seed0, piece, steps_maxed ? 1u : 0u,
+                       (const uint32_t*)wave_cnt, (uint32_t)waves, total, seeds, idx);
+    return 0;
+}
+
+// out: the batch's results; rerun: m results; idx: m distinct indices into `out`.  m == 0 launches nothing.  Returns 0, or -1 (nothing
+// launched) for m >= 2^32 / 3.
+extern "C" int madsim_k_launch_resolve_scatter(madsim_result_t* out, const madsim_result_t* rerun, const uint32_t* idx, uint64_t m, void* stream) {
+    static_assert(MADSIM_K_RESOLVE_CHUNKS * sizeof(uint4) == sizeof(madsim_result_t), "three 16-byte chunks per record");
+    if (m >= (1ull << 32) / MADSIM_K_RESOLVE_CHUNKS) return -1;
+    if (m == 0) return 0;
+    const uint32_t grid = (uint32_t)((MADSIM_K_RESOLVE_CHUNKS * m + 255) / 256);
+    hipLaunchKernelGGL(madsim_k::resolve_scatter_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, out, rerun, idx, (uint32_t)m);
     return 0;
 }
 

@@ -131,6 +131,9 @@ def lib():
                                                                  C.POINTER(A.Campaign), C.POINTER(A.Diff)]
         L.madsim_hip_ctx_run_campaign_diff.argtypes = [ctxp] + L.madsim_hip_run_campaign_diff.argtypes
         L.madsim_hip_run_campaign_diff_multi.argtypes = [C.POINTER(ctxp), C.c_int] + L.madsim_hip_run_campaign_diff.argtypes
+        L.madsim_hip_campaign_resolved.argtypes = [C.POINTER(A.Resolve)]
+        L.madsim_hip_ctx_campaign_resolved.argtypes = [ctxp, C.POINTER(A.Resolve)]
+        L.madsim_hip_grow_limits.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Limits), C.c_uint32, C.POINTER(A.Limits)]
         if L.madsim_hip_version() != A.ABI_VERSION:
             raise MadsimHipError("libmadsim_hip.so ABI version mismatch")
         # build identity: MADSIM_HIP_LIB may name an A/B build of THIS library (tools/build_variant.sh), nothing else — an
@@ -214,9 +217,40 @@ def run_batch_auto(workload, seed0, count, config=None, limits=None, max_rounds=
     return out, summ
 
 
-def _campaign_flags(stop_at_failure, list_runner=False, stop_at_cap=False, stop_at_groups=False):
+def grown_limits(workload, limits=None, rounds=1):
+    """madsim_hip_grow_limits: the limits round `rounds` of a resolving campaign runs under — `rounds` applications of the growth step of
+    run_batch_auto with both the capacities and the step cap grown.  A host helper: no device needed.  (grow_limits above is the older,
+    Python-side doubling that Builder.check_determinism uses.)"""
+    out = A.Limits()
+    lim = limits or A.Limits()
+    _check(lib().madsim_hip_grow_limits(workload.ref(), C.byref(lim), rounds, C.byref(out)))
+    return out
+
+
+def campaign_resolved():
+    """madsim_hip_campaign_resolved: the A.Resolve account of the most recent campaign call on the default context — how many seeds the first
+    pass left re-runnable, how many each round re-ran, how many ended settled; all zero when that call did not resolve, and before any."""
+    out = A.Resolve()
+    _check(lib().madsim_hip_campaign_resolved(C.byref(out)))
+    return out
+
+
+def _resolve_flags(resolve):
+    """`resolve=` of the campaign wrappers as flag bits: None / False = none, True = MADSIM_CAMPAIGN_RESOLVE with the default number of rounds,
+    an int = that many rounds (more than A.RESOLVE_MAX_ROUNDS is the library's MADSIM_E_ARG)."""
+    if resolve is None or resolve is False:
+        return 0
+    if resolve is True:
+        return A.CAMPAIGN_RESOLVE
+    rounds = int(resolve)
+    if not 1 <= rounds <= A.CAMPAIGN_RESOLVE_ROUNDS_MASK >> A.CAMPAIGN_RESOLVE_ROUNDS_SHIFT:
+        raise MadsimHipError(f"resolve: None, True or a number of rounds 1..{A.RESOLVE_MAX_ROUNDS}, got {resolve!r}")
+    return A.CAMPAIGN_RESOLVE | rounds << A.CAMPAIGN_RESOLVE_ROUNDS_SHIFT
+
+
+def _campaign_flags(stop_at_failure, list_runner=False, stop_at_cap=False, stop_at_groups=False, resolve=None):
     return (A.CAMPAIGN_STOP_AT_FAILURE if stop_at_failure else 0) | (A.CAMPAIGN_LIST_RUNNER if list_runner else 0) \
-        | (A.CAMPAIGN_STOP_AT_CAP if stop_at_cap else 0) | (A.CAMPAIGN_STOP_AT_GROUPS if stop_at_groups else 0)
+        | (A.CAMPAIGN_STOP_AT_CAP if stop_at_cap else 0) | (A.CAMPAIGN_STOP_AT_GROUPS if stop_at_groups else 0) | _resolve_flags(resolve)
 
 
 def _collecting(call, collect):
@@ -231,7 +265,7 @@ def _collecting(call, collect):
 
 
 def run_campaign(workload, seed0, total, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None,
-                 collect=None, list_runner=False, stop_at_cap=False):
+                 collect=None, list_runner=False, stop_at_cap=False, resolve=None):
     """madsim_hip_run_campaign: `total` seeds as batches kept in flight on the library's own streams; returns the Campaign
     report (first failing seed, counts) — no per-seed results.  stop_at_failure: stop launching once a completed batch holds a
     seed with a genuine verdict.
@@ -239,7 +273,12 @@ def run_campaign(workload, seed0, total, batch=0, in_flight=0, stop_at_failure=F
     collect=K (madsim_hip_run_campaign_collect): returns (campaign, failures, by_verdict) — the K smallest failing seeds of the
     prefix that ran, ascending, as records of FAILURE_DTYPE (the seed and the result run_batch gives for it), and the number of
     seeds per verdict value.  K = 0: the histogram alone.  list_runner: runner verdicts are listed too; stop_at_cap: stop
-    launching once K listed seeds have been read."""
+    launching once K listed seeds have been read.
+
+    resolve=True | rounds (MADSIM_CAMPAIGN_RESOLVE; every run_campaign* wrapper takes it): seeds that come back with a runner verdict
+    (a device capacity, the step cap) are run again on the device under grown limits — grown_limits(workload, limits, r) in round r — before
+    their batch is reported, so the report, the list, the statistics, the groups and the diff are over settled results; n_runner is what
+    no round settled.  campaign_resolved() tells what the rounds did."""
     if _inited_device is None:
         init(0)
     cfg = config or A.Config.default()
@@ -247,9 +286,9 @@ def run_campaign(workload, seed0, total, batch=0, in_flight=0, stop_at_failure=F
     rep = A.Campaign()
     if collect is None:
         _check(lib().madsim_hip_run_campaign(workload.ref(), C.byref(cfg), seed0, total, batch, in_flight,
-                                             _campaign_flags(stop_at_failure), C.byref(lim), C.byref(rep)))
+                                             _campaign_flags(stop_at_failure, resolve=resolve), C.byref(lim), C.byref(rep)))
         return rep
-    flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap)
+    flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap, resolve=resolve)
     failures, by_verdict = _collecting(lambda col: lib().madsim_hip_run_campaign_collect(
         workload.ref(), C.byref(cfg), seed0, total, batch, in_flight, flags, C.byref(lim), C.byref(rep), col), collect)
     return rep, failures, by_verdict
@@ -316,14 +355,14 @@ def _campaign_stats(call, include, top_k, collect, rep):
 
 
 def run_campaign_stats(workload, seed0, total, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None, include=(A.PASS,),
-                       top_k=0, collect=None, list_runner=False, stop_at_cap=False):
+                       top_k=0, collect=None, list_runner=False, stop_at_cap=False, resolve=None):
     """madsim_hip_run_campaign_stats: run_campaign, plus the statistics of clock_ns, steps, msg_count and rng_calls over the seeds whose
     verdict is in `include` (PASS / PANIC / DEADLOCK / TIME_LIMIT) and the `top_k` (<= 16) extreme seeds of each.  Returns
     (campaign, CampaignStats); with collect=K (as run_campaign) (campaign, failures, by_verdict, CampaignStats)."""
     if _inited_device is None:
         init(0)
     cfg, lim, rep = config or A.Config.default(), limits or A.Limits(), A.Campaign()
-    flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap)
+    flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap, resolve=resolve)
     return _campaign_stats(lambda col, st: lib().madsim_hip_run_campaign_stats(
         workload.ref(), C.byref(cfg), seed0, total, batch, in_flight, flags, C.byref(lim), C.byref(rep), col, st), include, top_k, collect, rep)
 
@@ -370,7 +409,7 @@ def _campaign_groups(call, include, key, max_groups, collect, stats, rep):
 
 def run_campaign_groups(workload, seed0, total, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None,
                         include=(A.PANIC, A.DEADLOCK, A.TIME_LIMIT), key="obs", max_groups=32, stop_at_groups=False, collect=None, stats=None,
-                        list_runner=False, stop_at_cap=False):
+                        list_runner=False, stop_at_cap=False, resolve=None):
     """madsim_hip_run_campaign_groups: run_campaign, plus the failure modes of the range — the seeds whose verdict is in `include` grouped by
     (verdict, key), `key` one of "obs" (obs_hash: what the workload traced), "trace", "msgs", "clock", "rng", "steps"; the first `max_groups`
     groups in order of first appearance, each with its exact count and its smallest seed.  stop_at_groups: stop launching once max_groups
@@ -379,7 +418,7 @@ def run_campaign_groups(workload, seed0, total, batch=0, in_flight=0, stop_at_fa
     if _inited_device is None:
         init(0)
     cfg, lim, rep = config or A.Config.default(), limits or A.Limits(), A.Campaign()
-    flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap, stop_at_groups)
+    flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap, stop_at_groups, resolve)
     return _campaign_groups(lambda col, st, grp: lib().madsim_hip_run_campaign_groups(
         workload.ref(), C.byref(cfg), seed0, total, batch, in_flight, flags, C.byref(lim), C.byref(rep), col, st, grp),
         include, key, max_groups, collect, stats, rep)
@@ -406,7 +445,7 @@ class CampaignDiff:
         return int(self.transitions[A.PASS, 1:].sum())
 
 
-def _campaign_diff(call, workload, other, config, other_config, limits, other_limits, fields, max_listed, stop_at_diffs):
+def _campaign_diff(call, workload, other, config, other_config, limits, other_limits, fields, max_listed, stop_at_diffs, resolve=None):
     """Run `call(wA, cfgA, limA, wB, cfgB, limB, flags, repA, repB, diff)` — one of the madsim_hip_*run_campaign_diff* entry points with its
     contexts and its range bound.  A None on the B side means "the same as A's"."""
     if not isinstance(fields, int) or fields <= 0 or fields & ~A.DIFF_ALL or max_listed < 0 or (stop_at_diffs and not max_listed):
@@ -419,7 +458,7 @@ def _campaign_diff(call, workload, other, config, other_config, limits, other_li
     d.records = arr.ctypes.data_as(C.POINTER(A.DiffRecord)) if max_listed else None
     rep_a, rep_b = A.Campaign(), A.Campaign()
     _check(call(workload.ref(), C.byref(cfg_a), C.byref(lim_a), w_b.ref(), C.byref(cfg_b), C.byref(lim_b),
-                A.CAMPAIGN_STOP_AT_DIFFS if stop_at_diffs else 0, C.byref(rep_a), C.byref(rep_b), C.byref(d)))
+                (A.CAMPAIGN_STOP_AT_DIFFS if stop_at_diffs else 0) | _resolve_flags(resolve), C.byref(rep_a), C.byref(rep_b), C.byref(d)))
     return rep_a, rep_b, CampaignDiff(d, arr)
 
 
@@ -428,12 +467,21 @@ def run_campaign_diff(workload, seed0, total, other=None, config=None, other_con
     """madsim_hip_run_campaign_diff: side A = (workload, config, limits) and side B = (other, other_config, other_limits) over the same seeds —
     a None on the B side means "the same as A's" —, compared on the device on the result fields named in `fields` (A.DIFF_* bits).  Returns
     (campaign A, campaign B, CampaignDiff): each side's plain campaign report, the max_listed smallest differing seeds with both results, the
-    counts, and the verdict-transition matrix.  stop_at_diffs: stop launching once max_listed differing seeds have been read."""
+    counts, and the verdict-transition matrix.  stop_at_diffs: stop launching once max_listed differing seeds have been read.
+    (This one wrapper's parameter list is pinned; its resolving form is run_campaign_diff_resolved.)"""
+    return run_campaign_diff_resolved(workload, seed0, total, None, other, config, other_config, limits, other_limits, fields, max_listed,
+                                      stop_at_diffs, batch, in_flight)
+
+
+def run_campaign_diff_resolved(workload, seed0, total, resolve=True, other=None, config=None, other_config=None, limits=None, other_limits=None,
+                               fields=A.DIFF_ALL, max_listed=0, stop_at_diffs=False, batch=0, in_flight=0):
+    """run_campaign_diff with MADSIM_CAMPAIGN_RESOLVE (`resolve`: True or a number of rounds, as run_campaign's): each side's runner verdicts are
+    re-run under that side's own grown limits before the two arrays are compared, so only seeds that no round settles stay incomparable."""
     if _inited_device is None:
         init(0)
     return _campaign_diff(lambda wa, ca, la, wb, cb, lb, flags, ra, rb, d: lib().madsim_hip_run_campaign_diff(
         wa, ca, la, wb, cb, lb, seed0, total, batch, in_flight, flags, ra, rb, d),
-        workload, other, config, other_config, limits, other_limits, fields, max_listed, stop_at_diffs)
+        workload, other, config, other_config, limits, other_limits, fields, max_listed, stop_at_diffs, resolve)
 
 
 def run_batch_device(workload, seed0, count, d_out_ptr, stream_ptr=0, config=None, limits=None, want_summary=True):
@@ -481,6 +529,12 @@ class Context:
     def __exit__(self, *exc):
         self.close()
 
+    def campaign_resolved(self):
+        """runtime.campaign_resolved for this context (madsim_hip_ctx_campaign_resolved); after a _multi call every context holds the call's totals."""
+        out = A.Resolve()
+        _check(lib().madsim_hip_ctx_campaign_resolved(self._h, C.byref(out)))
+        return out
+
     def run_batch(self, workload, seed0, count, config=None, limits=None, auto_rounds=0):
         cfg, lim = config or A.Config.default(), limits or A.Limits()
         out = np.zeros(count, dtype=A.RESULT_DTYPE)
@@ -494,24 +548,24 @@ class Context:
         return out, summ
 
     def run_campaign(self, workload, seed0, total, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None,
-                     collect=None, list_runner=False, stop_at_cap=False):
+                     collect=None, list_runner=False, stop_at_cap=False, resolve=None):
         """runtime.run_campaign on this context (madsim_hip_ctx_run_campaign / madsim_hip_ctx_run_campaign_collect)."""
         cfg, lim = config or A.Config.default(), limits or A.Limits()
         rep = A.Campaign()
         if collect is None:
             _check(lib().madsim_hip_ctx_run_campaign(self._h, workload.ref(), C.byref(cfg), seed0, total, batch, in_flight,
-                                                     _campaign_flags(stop_at_failure), C.byref(lim), C.byref(rep)))
+                                                     _campaign_flags(stop_at_failure, resolve=resolve), C.byref(lim), C.byref(rep)))
             return rep
-        flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap)
+        flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap, resolve=resolve)
         failures, by_verdict = _collecting(lambda col: lib().madsim_hip_ctx_run_campaign_collect(
             self._h, workload.ref(), C.byref(cfg), seed0, total, batch, in_flight, flags, C.byref(lim), C.byref(rep), col), collect)
         return rep, failures, by_verdict
 
     def run_campaign_stats(self, workload, seed0, total, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None,
-                           include=(A.PASS,), top_k=0, collect=None, list_runner=False, stop_at_cap=False):
+                           include=(A.PASS,), top_k=0, collect=None, list_runner=False, stop_at_cap=False, resolve=None):
         """runtime.run_campaign_stats on this context (madsim_hip_ctx_run_campaign_stats)."""
         cfg, lim, rep = config or A.Config.default(), limits or A.Limits(), A.Campaign()
-        flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap)
+        flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap, resolve=resolve)
         return _campaign_stats(lambda col, st: lib().madsim_hip_ctx_run_campaign_stats(
             self._h, workload.ref(), C.byref(cfg), seed0, total, batch, in_flight, flags, C.byref(lim), C.byref(rep), col, st),
             include, top_k, collect, rep)
@@ -519,21 +573,21 @@ class Context:
 
     def run_campaign_groups(self, workload, seed0, total, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None,
                             include=(A.PANIC, A.DEADLOCK, A.TIME_LIMIT), key="obs", max_groups=32, stop_at_groups=False, collect=None, stats=None,
-                            list_runner=False, stop_at_cap=False):
+                            list_runner=False, stop_at_cap=False, resolve=None):
         """runtime.run_campaign_groups on this context (madsim_hip_ctx_run_campaign_groups)."""
         cfg, lim, rep = config or A.Config.default(), limits or A.Limits(), A.Campaign()
-        flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap, stop_at_groups)
+        flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap, stop_at_groups, resolve)
         return _campaign_groups(lambda col, st, grp: lib().madsim_hip_ctx_run_campaign_groups(
             self._h, workload.ref(), C.byref(cfg), seed0, total, batch, in_flight, flags, C.byref(lim), C.byref(rep), col, st, grp),
             include, key, max_groups, collect, stats, rep)
 
 
     def run_campaign_diff(self, workload, seed0, total, other=None, config=None, other_config=None, limits=None, other_limits=None,
-                          fields=A.DIFF_ALL, max_listed=0, stop_at_diffs=False, batch=0, in_flight=0):
+                          fields=A.DIFF_ALL, max_listed=0, stop_at_diffs=False, batch=0, in_flight=0, resolve=None):
         """runtime.run_campaign_diff on this context (madsim_hip_ctx_run_campaign_diff)."""
         return _campaign_diff(lambda wa, ca, la, wb, cb, lb, flags, ra, rb, d: lib().madsim_hip_ctx_run_campaign_diff(
             self._h, wa, ca, la, wb, cb, lb, seed0, total, batch, in_flight, flags, ra, rb, d),
-            workload, other, config, other_config, limits, other_limits, fields, max_listed, stop_at_diffs)
+            workload, other, config, other_config, limits, other_limits, fields, max_listed, stop_at_diffs, resolve)
 
 
 def run_batch_multi(contexts, workload, seed0, count, config=None, limits=None, max_rounds=5):
@@ -549,7 +603,7 @@ def run_batch_multi(contexts, workload, seed0, count, config=None, limits=None, 
 
 
 def run_campaign_multi(contexts, workload, seed0, total, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None,
-                       collect=None, list_runner=False, stop_at_cap=False):
+                       collect=None, list_runner=False, stop_at_cap=False, resolve=None):
     """madsim_hip_run_campaign_multi: the seed search over several contexts (one per GPU) from one host thread — batch k on context
     k % n, reports read in batch order, every device stopped within one round of batches of the first genuine failure.
     collect / list_runner / stop_at_cap: as run_campaign (madsim_hip_run_campaign_collect_multi); the list is the one a single
@@ -560,20 +614,20 @@ def run_campaign_multi(contexts, workload, seed0, total, batch=0, in_flight=0, s
     arr = (C.c_void_p * len(contexts))(*[c._h for c in contexts])
     if collect is None:
         _check(lib().madsim_hip_run_campaign_multi(arr, len(contexts), workload.ref(), C.byref(cfg), seed0, total, batch, in_flight,
-                                                   _campaign_flags(stop_at_failure), C.byref(lim), C.byref(rep)))
+                                                   _campaign_flags(stop_at_failure, resolve=resolve), C.byref(lim), C.byref(rep)))
         return rep
-    flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap)
+    flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap, resolve=resolve)
     failures, by_verdict = _collecting(lambda col: lib().madsim_hip_run_campaign_collect_multi(
         arr, len(contexts), workload.ref(), C.byref(cfg), seed0, total, batch, in_flight, flags, C.byref(lim), C.byref(rep), col), collect)
     return rep, failures, by_verdict
 
 
 def run_campaign_stats_multi(contexts, workload, seed0, total, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None,
-                             include=(A.PASS,), top_k=0, collect=None, list_runner=False, stop_at_cap=False):
+                             include=(A.PASS,), top_k=0, collect=None, list_runner=False, stop_at_cap=False, resolve=None):
     """madsim_hip_run_campaign_stats_multi: run_campaign_stats over several contexts; the statistics are the ones a single context gives."""
     cfg, lim, rep = config or A.Config.default(), limits or A.Limits(), A.Campaign()
     arr = (C.c_void_p * len(contexts))(*[c._h for c in contexts])
-    flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap)
+    flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap, resolve=resolve)
     return _campaign_stats(lambda col, st: lib().madsim_hip_run_campaign_stats_multi(
         arr, len(contexts), workload.ref(), C.byref(cfg), seed0, total, batch, in_flight, flags, C.byref(lim), C.byref(rep), col, st),
         include, top_k, collect, rep)
@@ -581,24 +635,24 @@ def run_campaign_stats_multi(contexts, workload, seed0, total, batch=0, in_fligh
 
 def run_campaign_groups_multi(contexts, workload, seed0, total, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None,
                               include=(A.PANIC, A.DEADLOCK, A.TIME_LIMIT), key="obs", max_groups=32, stop_at_groups=False, collect=None, stats=None,
-                              list_runner=False, stop_at_cap=False):
+                              list_runner=False, stop_at_cap=False, resolve=None):
     """madsim_hip_run_campaign_groups_multi: run_campaign_groups over several contexts; the groups are the ones a single context gives."""
     cfg, lim, rep = config or A.Config.default(), limits or A.Limits(), A.Campaign()
     arr = (C.c_void_p * len(contexts))(*[c._h for c in contexts])
-    flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap, stop_at_groups)
+    flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap, stop_at_groups, resolve)
     return _campaign_groups(lambda col, st, grp: lib().madsim_hip_run_campaign_groups_multi(
         arr, len(contexts), workload.ref(), C.byref(cfg), seed0, total, batch, in_flight, flags, C.byref(lim), C.byref(rep), col, st, grp),
         include, key, max_groups, collect, stats, rep)
 
 
 def run_campaign_diff_multi(contexts, workload, seed0, total, other=None, config=None, other_config=None, limits=None, other_limits=None,
-                            fields=A.DIFF_ALL, max_listed=0, stop_at_diffs=False, batch=0, in_flight=0):
+                            fields=A.DIFF_ALL, max_listed=0, stop_at_diffs=False, batch=0, in_flight=0, resolve=None):
     """madsim_hip_run_campaign_diff_multi: run_campaign_diff over several contexts (both sides of batch k on context k % n); the report is the
     one a single context gives."""
     arr = (C.c_void_p * len(contexts))(*[c._h for c in contexts])
     return _campaign_diff(lambda wa, ca, la, wb, cb, lb, flags, ra, rb, d: lib().madsim_hip_run_campaign_diff_multi(
         arr, len(contexts), wa, ca, la, wb, cb, lb, seed0, total, batch, in_flight, flags, ra, rb, d),
-        workload, other, config, other_config, limits, other_limits, fields, max_listed, stop_at_diffs)
+        workload, other, config, other_config, limits, other_limits, fields, max_listed, stop_at_diffs, resolve)
 
 
 def run_campaign_over_ranks(workload, seed0, total, batch=65536, stop_at_failure=True, config=None, limits=None, device_tensors=None, group=None,
