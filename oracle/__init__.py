@@ -21,7 +21,23 @@ _LIB = os.path.join(_HERE, "libmadsim_oracle.so")
 
 class OracleStats(C.Structure):
     _fields_ = [("max_heap", C.c_uint32), ("max_ready", C.c_uint32), ("max_tasks", C.c_uint32),
-                ("max_msgs", C.c_uint32), ("max_regs", C.c_uint32), ("max_conns", C.c_uint32), ("max_cq", C.c_uint32)]
+                ("max_msgs", C.c_uint32), ("max_regs", C.c_uint32), ("max_conns", C.c_uint32), ("max_cq", C.c_uint32),
+                # test-only event counters of the timer-tier and signal ops, summed over the run (madsim_oracle.h)
+                ("scopes_expired", C.c_uint32), ("scopes_completed", C.c_uint32), ("ticks_first_poll", C.c_uint32),
+                ("ticks_parked", C.c_uint32), ("sel_won_recv", C.c_uint32), ("sel_won_time", C.c_uint32),
+                ("sel_won_ctrl_c", C.c_uint32), ("msgs_lost", C.c_uint32), ("sig_lost", C.c_uint32),
+                ("sig_caught", C.c_uint32), ("sig_killed", C.c_uint32)]
+
+
+class OracleError(RuntimeError):
+    """The oracle refused the call: `code` is its return value (E_OPCODE: an opcode it has no case for — never a verdict)."""
+
+    def __init__(self, code):
+        super().__init__(f"oracle error {code}" + (": an opcode the oracle does not implement" if code == E_OPCODE else ""))
+        self.code = code
+
+
+E_OPCODE = -100
 
 
 def build(force=False):
@@ -76,7 +92,7 @@ def run_batch(workload, seed0, count, config=None, limits=None, want_stats=False
     rc = lib().madsim_oracle_run_batch(workload.ref(), C.byref(cfg), seed0, count, C.byref(lim),
                                        out.ctypes.data_as(C.c_void_p), C.byref(summ), C.byref(st))
     if rc != 0:
-        raise RuntimeError(f"oracle error {rc}")
+        raise OracleError(rc)
     return (out, summ, st) if want_stats else (out, summ)
 
 
@@ -84,7 +100,7 @@ ME_NAMES = {1: "live tasks > 254", 2: "registrations per socket > 255", 4: "regi
             16: "connections waiting for accept1 > 8", 32: "servers per IPVS service > 6", 64: "formatted panic value > panic_dyn_max",
             128: "port-0 entry bound beside its live Endpoint", 256: "op through a port-0 entry that lost its socket",
             512: "connection ends per Endpoint guard > 127", 1024: "ephemeral port beyond the table's candidates", 2048: "live connections > 127",
-            4096: "queued messages per mailbox > 255"}
+            4096: "queued messages per mailbox > 255", 8192: "ctrl-c signal that would schedule two or more waiters"}
 
 
 def run_batch_pure(workload, seed0, count, config=None, limits=None):
@@ -97,7 +113,7 @@ def run_batch_pure(workload, seed0, count, config=None, limits=None):
     rc = lib().madsim_oracle_run_batch_pure(workload.ref(), C.byref(cfg), seed0, count, C.byref(lim),
                                             out.ctypes.data_as(C.c_void_p), ev.ctypes.data_as(C.c_void_p))
     if rc != 0:
-        raise RuntimeError(f"oracle error {rc}")
+        raise OracleError(rc)
     return out, ev
 
 
@@ -119,7 +135,7 @@ def trace_seed(workload, seed, config=None, limits=None, cap=1 << 20):
     res = A.Result()
     n = lib().madsim_oracle_trace_seed(workload.ref(), C.byref(cfg), seed, C.byref(lim), buf, cap, C.byref(res))
     if n < 0:
-        raise RuntimeError(f"oracle error {n}")
+        raise OracleError(n)
     return bytes(buf[:min(n, cap)]), res
 
 
@@ -131,5 +147,5 @@ def observe_seed(workload, seed, config=None, limits=None, cap=1 << 16):
     res = A.Result()
     n = lib().madsim_oracle_observe_seed(workload.ref(), C.byref(cfg), seed, C.byref(lim), buf, cap, C.byref(res))
     if n < 0:
-        raise RuntimeError(f"oracle error {n}")
+        raise OracleError(n)
     return [int(v) for v in buf[:min(n, cap)]], res

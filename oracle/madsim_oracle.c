@@ -154,6 +154,17 @@ typedef struct {
     uint8_t  join_state;                  /* parked in MS_OP_JOIN: 1 awaiting, 2 / 3 the awaited task completed / was cancelled */
     int8_t   conn; uint8_t side;          /* the (Sender, Receiver) pair this task holds, and which end */
     uint32_t cval; uint8_t chas; uint64_t carrive; uint32_t backoff_ms;   /* receiver stream state (net/mod.rs:386-400) */
+    /* time::timeout over an async block (time/mod.rs:128-140): the Timeout future's Sleep, where the block ends, and whether the
+     * block has made a (tx, rx) of its own — a local of the block, dropped with it */
+    uint8_t  scope_on, scope_made; uint16_t scope_end; uint64_t scope_deadline;
+    /* `let mut i = time::interval(p)`: a local of the task body (time/interval.rs:111-120): Interval { delay, period, missed_tick_behavior } */
+    uint8_t  tk_on, tk_behavior; uint64_t tk_period, tk_deadline;
+    uint8_t  sel;          /* a select / timeout_at has been polled at least once: its Sleep exists                     */
+    /* the watch::Receiver of a pending ctrl_c() (signal.rs:5): held, and the version it has seen (tokio watch)          */
+    uint8_t  sig_sub; uint32_t sig_seen;
+    /* what the task's `from` / rsp_tag bindings held when a receive that may be DROPPED began: a recv future writes them only when it
+     * completes (`let (val, from) = ..await`), this restatement's oneshot writes them on delivery */
+    uint32_t sv_from; uint64_t sv_aux;
 } task_t;
 
 enum { H_NONE = 0, H_RUNNING = 1, H_COMPLETED = 2, H_CANCELLED = 3 };
@@ -166,6 +177,8 @@ typedef struct {
     uint8_t gen0_killed;                  /* the NodeInfo captured by NodeHandles at build() is dead  */
     /* NetSim.hooks_req / hooks_rsp entries of this node (net/mod.rs:250-284): valid, mode (1 = drop all), tag, code */
     uint8_t hreq_valid, hreq_all, hreq_tag, hreq_code, hrsp_valid, hrsp_all, hrsp_code;
+    uint8_t sig_installed;                /* the CURRENT NodeInfo's ctrl_c is Some(watch::Sender) (task/mod.rs:108-111,166-175) */
+    uint32_t sig_version;                 /* ... and that watch channel's version: one step per successful send          */
     VEC(uint16_t) paused_list;            /* Node.paused: Vec<Runnable> (task/mod.rs:345-350)        */
     VEC(tref_t) tasks;                    /* NodeInfo.tasks: Vec<Weak<TaskInfo>> in spawn order (:105) */
 } node_t;
@@ -206,6 +219,7 @@ typedef struct {
     int model_limits;                                    /* 1: the workload MODEL's ceilings decide verdicts (what the device runner reports);
                                                             0: the reference's unbounded containers all the way, ceilings only recorded */
     uint32_t model_events;                               /* MADSIM_ORACLE_ME_* of this seed, recorded either way */
+    int err;                                             /* the run met something this oracle cannot answer (an opcode without a case): the CALL fails */
     madsim_oracle_stats_t st;
 } sim_t;
 
@@ -601,6 +615,7 @@ static void node_restart(sim_t* S, unsigned node) {       /* TaskHandle::restart
     n->tasks.p = NULL; n->tasks.n = n->tasks.cap = 0;
     if (n->info_gen == 0) n->gen0_killed = 1;
     n->info_gen++; n->killed = 0; n->paused = 0;          /* new_info */
+    n->sig_installed = 0; n->sig_version = 0;             /* ctrl_c: Mutex::new(None) (task/mod.rs:389); kill_id keeps the NodeInfo and with it the handler */
     paused_clear(S, node);
     for (size_t i = 0; i < cnt; i++) {                    /* old_info.kill() */
         task_t* t = old[i].slot < S->tasks.n ? &S->tasks.p[old[i].slot] : NULL;
@@ -703,7 +718,103 @@ static uint64_t rand_delay_start(sim_t* S) {
 
 static void timer_expire(sim_t* S, uint64_t now);
 
-static int poll_task(sim_t* S, uint16_t slot) {
+/* ---- interval tickers (time/interval.rs) ---- */
+/* Interval::poll_tick after its Sleep is Ready (time/interval.rs:146-168): the next deadline — deadline + period, or by the
+ * MissedTickBehavior when now > deadline + 5 ms (next_timeout, :76-99) — through Sleep::reset, which has no floor (time/sleep.rs:39-41);
+ * returns the instant the tick was scheduled for. */
+static uint64_t tick_complete(sim_t* S, task_t* t, int fold) {
+    const uint64_t timeout = t->tk_deadline, now = S->clock, period = t->tk_period;
+    uint64_t next = timeout + period;
+    if (now > timeout + 5 * NS_PER_MS) {
+        if (t->tk_behavior == 1) next = now + period;                                      /* Delay */
+        else if (t->tk_behavior == 2) next = now + (period - (now - timeout) % period);    /* Skip  */
+    }
+    t->tk_deadline = next;
+    if (fold) { obs_record(timeout); S->obs_hash = (S->obs_hash ^ timeout) * FNV_PRIME; }
+    return timeout;
+}
+
+/* ---- the recv arm of a select: Endpoint::recv_from_raw (net/endpoint.rs:140-149) polled as one of two futures ---- */
+/* Nothing before its first poll; then Mailbox::recv (endpoint.rs:353-362: take a queued message of the tag, or register a oneshot);
+ * once the oneshot holds the message, rand_delay (net/mod.rs:287-292), whose Sleep has the 1 ms floor: Pending at first.
+ * t->sub: 0 not polled yet, 1 the oneshot is awaited, 2 in rand_delay.  Returns 1 when Ready. */
+static int recv_arm_poll(sim_t* S, uint16_t slot, const madsim_insn_t* in) {
+    task_t* t = &S->tasks.p[slot];
+    sock_t* k = &S->socks[in->a];
+    const uint8_t tag = (uint8_t)(in->b >> 8);
+    if (t->sub == 0) {
+        t->sv_from = t->from; t->sv_aux = t->aux;
+        t->rxseq++; t->inbox_full = 0;
+        size_t idx = 0;
+        while (idx < k->msgs.n && k->msgs.p[idx].tag != tag) idx++;
+        if (idx < k->msgs.n) {
+            msg_t m = k->msgs.p[idx];
+            k->msgs.p[idx] = k->msgs.p[--k->msgs.n];                    /* swap_remove */
+            t->inbox_full = 1; t->val = m.val; t->from = m.from; t->inbox_aux = m.aux;
+        } else {
+            reg_t r = { tag, slot, t->gen, t->rxseq, (uint8_t)tag };
+            reg_model_limits(S, k, &r);
+            vec_push(k->registered, r);
+            if (k->registered.n > S->st.max_regs) S->st.max_regs = (uint32_t)k->registered.n;
+        }
+        t->sub = 1;
+    }
+    if (t->sub == 1 && t->inbox_full) {
+        t->inbox_full = 0;
+        if (tag >= MADSIM_TAG_RPC_FIRST) t->aux = t->inbox_aux;
+        t->deadline = rand_delay_start(S); t->sub = 2;
+    }
+    return t->sub == 2 ? sleep_poll(S, slot, t->deadline) : 0;
+}
+/* drop(recv future): its oneshot::Receiver goes — a registration left in the mailbox is dead, a message the future had taken is
+ * gone with it (the draw of its rand_delay was made, the timer stays in the heap) — and the task's bindings were never assigned. */
+static void recv_future_drop(sim_t* S, task_t* t, int in_rand_delay) {
+    if (in_rand_delay) S->st.msgs_lost++;
+    t->rxseq++; t->inbox_full = 0;
+    t->from = t->sv_from; t->aux = t->sv_aux;
+}
+static void recv_arm_drop(sim_t* S, task_t* t) {
+    if (t->sub) recv_future_drop(S, t, t->sub == 2);       /* (an arm that was never polled has done nothing) */
+    t->sub = 0;
+}
+
+/* ---- ctrl-c signals (signal.rs:4-8; NodeInfo::ctrl_c task/mod.rs:166-175; TaskHandle::send_ctrl_c :426-441) ---- */
+/* One poll of `ctrl_c()`: the first calls node.ctrl_c() on the TASK's own NodeInfo — get_or_insert_with(watch::channel): the handler
+ * is installed for the rest of that NodeInfo's life — and subscribes: a fresh Receiver has seen the current version, so changed() is
+ * Pending there.  No timer, no draw.  (A task of a replaced NodeInfo installs on that dead one: no send looks at it again.) */
+static int ctrl_c_poll(sim_t* S, task_t* t) {
+    node_t* n = &S->nodes[t->node];
+    const int current = t->info_gen == n->info_gen;
+    if (!t->sig_sub) {
+        if (current) n->sig_installed = 1;
+        t->sig_sub = 1; t->sig_seen = current ? n->sig_version : 0;
+        return 0;
+    }
+    return current && t->sig_seen != n->sig_version;
+}
+/* TaskHandle::send_ctrl_c.  Returns 1 when the seed has left the workload model and the run must stop. */
+static int node_send_ctrl_c(sim_t* S, unsigned node) {
+    node_t* n = &S->nodes[node];
+    if (!n->sig_installed) { S->st.sig_killed++; node_kill(S, node); return 0; }   /* "ctrl-c" has never been called: kill node (:437-440) */
+    uint32_t receivers = 0, would = 0;
+    for (size_t i = 0; i < S->tasks.n; i++) {
+        const task_t* r = &S->tasks.p[i];
+        if (!r->alive || !r->sig_sub || r->node != node || r->info_gen != n->info_gen) continue;
+        receivers++; would += !r->scheduled;
+    }
+    if (!receivers) { S->st.sig_lost++; return 0; }        /* `_ = tx.send(())`: "may return error if no receiver" (:433-434) */
+    /* watch::Sender::send wakes every waiter, in an order tokio's thread-local generator picks: the workload model covers the sends
+     * that schedule at most one task.  With the limits off they are woken in ascending slot order (a result nobody compares). */
+    if (would >= 2 && model_event(S, MADSIM_ORACLE_ME_SIG_WAITERS)) return 1;
+    n->sig_version++;
+    for (size_t i = 0; i < S->tasks.n; i++) {
+        const task_t* r = &S->tasks.p[i];
+        if (r->alive && r->sig_sub && r->node == node && r->info_gen == n->info_gen) wake(S, (uint16_t)i, r->gen);
+    }
+    return 0;
+}
+
+static int poll_body(sim_t* S, uint16_t slot) {
     const madsim_workload_t* w = S->w;
     for (;;) {
         task_t* t = &S->tasks.p[slot];
@@ -971,6 +1082,7 @@ static int poll_task(sim_t* S, uint16_t slot) {
             sock_t* k = &S->socks[in->a];
             uint8_t tag = (uint8_t)(in->b >> 8);
             if (t->sub == 0) {
+                t->sv_from = t->from; t->sv_aux = t->aux;  /* (a timeout scope may drop this future: scope_drop_block) */
                 t->rxseq++; t->inbox_full = 0;
                 size_t idx = 0;
                 while (idx < k->msgs.n && k->msgs.p[idx].tag != tag) idx++;
@@ -1036,6 +1148,7 @@ static int poll_task(sim_t* S, uint16_t slot) {
                 }
             }
             t = &S->tasks.p[slot]; t->sub = 0; t->pc++;
+            if (t->scope_on) t->scope_made = 1;            /* `let (tx, rx) = ep.connect1(..).await?` inside the async block: its local */
             break;
         case MS_OP_ACCEPT: {                               /* Endpoint::accept1 (endpoint.rs:197-211) */
             if (t->sub == 0) { t->deadline = rand_delay_start(S); t->sub = 1; }
@@ -1195,6 +1308,7 @@ static int poll_task(sim_t* S, uint16_t slot) {
                     t = &S->tasks.p[slot];
                 }
                 /* recv_from_raw(rsp_tag): Mailbox::recv (endpoint.rs:353-362) */
+                t->sv_from = t->from; t->sv_aux = t->aux;  /* (a timeout scope may drop this future: scope_drop_block) */
                 t->rxseq++; t->inbox_full = 0;
                 size_t idx = 0;
                 while (idx < k->msgs.n && k->msgs.p[idx].tag != t->rsp_tag) idx++;
@@ -1288,9 +1402,150 @@ static int poll_task(sim_t* S, uint16_t slot) {
             t->pc++;
             break;
         }
-        default:
-            return 1;                                      /* unsupported op in this oracle build */
+        case MS_OP_TIMEOUT_BEGIN:                          /* time::timeout(d, async { .. }) (time/mod.rs:128-133): the Sleep is made now, by
+                                                              TimeHandle::sleep (:111-116: the 1 ms floor); no timer, no draw */
+            t->scope_on = 1; t->scope_made = 0; t->scope_end = in->b;
+            t->scope_deadline = sleep_deadline(S, S->clock + (uint64_t)in->a * NS_PER_S + in->imm);
+            t->pc++;
+            break;
+        case MS_OP_TIMEOUT_END:                            /* the block completed: Ok(..); its locals drop — the (tx, rx) of a connect1 made
+                                                              inside, tx then rx (net/endpoint.rs:178-193) */
+            if (t->scope_on) {
+                t->scope_on = 0; S->st.scopes_completed++;
+                if (t->scope_made && t->conn >= 0) { int id = t->conn; t->conn = -1; conn_drop_handles(S, id, t->side, t->killed); t = &S->tasks.p[slot]; }
+            }
+            t->pc++;
+            break;
+        case MS_OP_INTERVAL: {                             /* interval / interval_at (time/interval.rs:38-58): delay = sleep_until(start),
+                                                              with TimeHandle::sleep_until's floor (time/mod.rs:118-124); an Interval assigned
+                                                              again replaces the old one (its timers stay in the heap) */
+            const uint64_t start = (in->a & 4) ? t->t0 : S->clock;
+            t->tk_on = 1; t->tk_behavior = in->a & 3; t->tk_period = insn_dur(in);
+            t->tk_deadline = sleep_deadline(S, start);
+            t->pc++;
+            break;
         }
+        case MS_OP_TICK:                                   /* Interval::tick -> poll_tick (time/interval.rs:124-169): ready!(delay.poll(cx)) —
+                                                              Sleep::poll (time/sleep.rs:47-54): Ready once elapsed, with no timer; else ANOTHER
+                                                              timer on every poll */
+            if (!t->tk_on) { S->err = MADSIM_E_ARG; return 1; }
+            if (!sleep_poll(S, slot, t->tk_deadline)) {
+                if (!t->sub) { t->sub = 1; S->st.ticks_parked++; }
+                return 0;
+            }
+            if (!t->sub) S->st.ticks_first_poll++;
+            t->sub = 0;
+            tick_complete(S, t, in->a & 1);
+            t->pc++;
+            break;
+        case MS_OP_INTERVAL_RESET:                         /* Interval::reset (time/interval.rs:174-176): now + period, no floor */
+            if (!t->tk_on) { S->err = MADSIM_E_ARG; return 1; }
+            t->tk_deadline = S->clock + t->tk_period;
+            t->pc++;
+            break;
+        case MS_OP_RECV_OR_TICK: {                         /* select! { biased; recv_from(tag), ticker.tick() } in the order the flags give:
+                                                              every poll polls both arms in that order, the first Ready wins, the other is dropped */
+            if (!t->tk_on) { S->err = MADSIM_E_ARG; return 1; }
+            const int tick_first = in->b & 1;
+            int won = -1;                                  /* 0 the recv arm, 1 the tick arm */
+            for (int i = 0; i < 2 && won < 0; i++) {
+                if ((i == 0) == tick_first) { if (sleep_poll(S, slot, t->tk_deadline)) won = 1; }    /* poll_tick: pending -> another timer */
+                else if (recv_arm_poll(S, slot, in)) won = 0;
+                t = &S->tasks.p[slot];
+            }
+            if (won < 0) return 0;
+            if (won == 0) { S->st.sel_won_recv++; t->sub = 0; }        /* Ok((val, from)): the bindings delivery wrote stand; a pending tick
+                                                                          arm is dropped — the Interval keeps its deadline, its timers stay */
+            else {                                         /* the tick arm: the recv future is dropped wherever it is */
+                S->st.sel_won_time++;
+                recv_arm_drop(S, t);
+                tick_complete(S, t, in->b & 2);
+                t->val = MADSIM_VAL_TIMEOUT;
+            }
+            t->pc++;
+            break;
+        }
+        case MS_OP_RECV_TIMEOUT_AT: {                      /* timeout_at(t0 + d, recv_from(tag)) (time/mod.rs:144-156): sleep_until(deadline)
+                                                              made when the call is (the 1 ms floor, :118-124), then select_biased! { fut, sleep } */
+            if (!t->sel) {
+                t->deadline2 = sleep_deadline(S, t->t0 + (uint64_t)(in->b & 0xff) * NS_PER_S + in->imm);
+                t->sel = 1;
+            }
+            if (recv_arm_poll(S, slot, in)) { S->st.sel_won_recv++; t->sub = 0; }
+            else if (sleep_poll(S, slot, t->deadline2)) {  /* Err(Elapsed) */
+                S->st.sel_won_time++;
+                recv_arm_drop(S, t);
+                t->val = MADSIM_VAL_TIMEOUT;
+            } else return 0;
+            t->sel = 0; t->pc++;
+            break;
+        }
+        case MS_OP_CTRL_C:                                 /* signal::ctrl_c().await (signal.rs:4-8) */
+            if (!ctrl_c_poll(S, t)) return 0;
+            t->sig_sub = 0;                                /* rx drops with the future */
+            S->st.sig_caught++;
+            t->pc++;
+            break;
+        case MS_OP_SEND_CTRL_C:
+            if (node_send_ctrl_c(S, in->a)) return 1;
+            t = &S->tasks.p[slot]; t->pc++;
+            break;
+        case MS_OP_RECV_OR_CTRL_C: {                       /* select! { biased; ctrl_c(), recv_from(tag) }, flags bit 0: the recv arm first */
+            const int recv_first = in->b & 1;
+            int won = -1;                                  /* 0 the recv arm, 1 the ctrl-c arm */
+            for (int i = 0; i < 2 && won < 0; i++) {
+                if ((i == 0) == recv_first) { if (recv_arm_poll(S, slot, in)) won = 0; }
+                else if (ctrl_c_poll(S, t)) won = 1;
+                t = &S->tasks.p[slot];
+            }
+            if (won < 0) return 0;
+            if (won == 0) {                                /* the ctrl-c future drops, its Receiver with it: a version it had not looked at is a signal lost */
+                S->st.sel_won_recv++; t->sub = 0;
+                if (t->sig_sub && t->info_gen == S->nodes[t->node].info_gen && t->sig_seen != S->nodes[t->node].sig_version) S->st.sig_lost++;
+            } else {
+                S->st.sel_won_ctrl_c++; S->st.sig_caught++;
+                recv_arm_drop(S, t);
+                t->val = MADSIM_VAL_TIMEOUT;
+            }
+            t->sig_sub = 0;
+            t->pc++;
+            break;
+        }
+        default:
+            S->err = MADSIM_ORACLE_E_OPCODE;               /* no case for this opcode: the CALL fails (run_one), it is never a verdict */
+            return 1;
+        }
+    }
+}
+
+/* Err(Elapsed) of time::timeout (time/mod.rs:134-139): the async block is dropped at the await it is parked on.  What each
+ * droppable await (the ops validate() admits inside a scope) leaves behind:
+ *   sleep / sleep_until / sleep_rand / a tick / the rand_delay of send, reply, connect1: their timers, which fire for nothing;
+ *   yield_now: the wake it made;  recv_from / the response receive of call(): a dead registration, or the message it had taken;
+ *   Receiver::recv: the message it had taken, and its waker in the channel (tokio's rx_waker: a later send wakes the task for nothing).
+ * Then the block's locals: the (tx, rx) of a connect1 inside it, tx then rx. */
+static void scope_drop_block(sim_t* S, uint16_t slot) {
+    task_t* t = &S->tasks.p[slot];
+    const madsim_insn_t* in = &S->w->insns[t->pc];
+    if (in->op == MS_OP_RECV && t->sub) recv_future_drop(S, t, t->sub == 2);
+    if (in->op == MS_OP_RPC_CALL && t->sub >= 2) recv_future_drop(S, t, t->sub == 3);
+    t->sub = 0;
+    if (t->scope_made && t->conn >= 0) { int id = t->conn; t->conn = -1; conn_drop_handles(S, id, t->side, t->killed); }
+}
+
+/* One poll of the task's future.  Inside a timeout scope that is Timeout::poll (time/mod.rs:128-140, select_biased! { fut, sleep }):
+ * the block first; if it is Pending, the Sleep — Ready once elapsed (Err(Elapsed): val, and the body goes on behind END in this same
+ * poll), else ANOTHER timer (time/sleep.rs:47-54). */
+static int poll_task(sim_t* S, uint16_t slot) {
+    for (;;) {
+        if (poll_body(S, slot)) return 1;
+        task_t* t = &S->tasks.p[slot];
+        if (!t->alive || !t->scope_on) return 0;
+        if (!sleep_poll(S, slot, t->scope_deadline)) return 0;
+        S->st.scopes_expired++;
+        scope_drop_block(S, slot);
+        t = &S->tasks.p[slot];
+        t->scope_on = 0; t->val = MADSIM_VAL_TIMEOUT; t->pc = (uint16_t)(t->scope_end + 1);
     }
 }
 
@@ -1344,7 +1599,7 @@ static void run_all_ready(sim_t* S, uint32_t max_steps) {
                         restart |= (S->w->panic_match[node * 8 + (S->panic_code >> 5)] >> (S->panic_code & 31)) & 1;
                     else for (unsigned k = 0; k < nb->n_match && k < 2; k++) restart |= nb->match[k] == S->panic_code;
                 }
-                if (!restart || S->unsupported) {
+                if (!restart || S->unsupported || S->err) {
                     S->panic = 1;
                     return;                                /* resume_unwind: block_on unwinds */
                 }
@@ -1395,6 +1650,65 @@ static int validate(const madsim_workload_t* w, const madsim_config_t* cfg) {
             (uint32_t)(in->b & 0xff) < w->n_socks && w->socks[in->b & 0xff].port == 0) return -1;
     }
     if (w->n_insns == 0) return -1;
+    for (uint32_t i = 0; i < w->n_insns; i++) if (w->insns[i].op >= MS_OP__COUNT) return MADSIM_ORACLE_E_OPCODE;   /* beyond the table: no case */
+    {   /* timeout scopes: one Timeout per task at a time (no nesting), a BEGIN names its END at a higher pc of the same program, inside
+         * only the awaits scope_drop_block knows how to drop (include/madsim_hip.h MS_OP_TIMEOUT_BEGIN), no jump across the boundary */
+        int32_t* scope = malloc(w->n_insns * sizeof *scope);
+        int bad = 0;
+        for (uint32_t i = 0; i < w->n_insns; i++) scope[i] = -1;
+        for (uint32_t i = 0; i < w->n_insns && !bad; i++) {
+            const madsim_insn_t* in = &w->insns[i];
+            if (in->op == MS_OP_TIMEOUT_END && scope[i] < 0) bad = 1;
+            if (in->op != MS_OP_TIMEOUT_BEGIN) continue;
+            const uint32_t end = in->b;
+            if (scope[i] >= 0 || in->imm >= NS_PER_S || end <= i || end >= w->n_insns || w->insns[end].op != MS_OP_TIMEOUT_END) { bad = 1; break; }
+            int conn = 0;
+            for (uint32_t k = i + 1; k <= end && !bad; k++) {
+                const uint8_t op = w->insns[k].op;
+                for (uint32_t p = 0; p < w->n_progs; p++) bad |= w->progs[p].entry == k;
+                if (k < end) switch (op) {
+                case MS_OP_SLEEP: case MS_OP_SLEEP_UNTIL: case MS_OP_SLEEP_RAND: case MS_OP_YIELD: case MS_OP_SEND: case MS_OP_REPLY: case MS_OP_RECV:
+                case MS_OP_SET: case MS_OP_DJNZ: case MS_OP_JMP: case MS_OP_JEQ: case MS_OP_ASSERT_VAL: case MS_OP_TRACE: case MS_OP_TRACE_TIME:
+                case MS_OP_GSET: case MS_OP_GADD: case MS_OP_ASSERT_G: case MS_OP_PANIC_IF_G_LT: case MS_OP_PANIC: case MS_OP_RANDOM: case MS_OP_RAND_BOOL:
+                case MS_OP_TICK: case MS_OP_INTERVAL_RESET: break;
+                case MS_OP_CONNECT: conn = 1; break;
+                case MS_OP_RPC_CALL: bad |= (w->insns[k].imm >> 8) != 0; break;       /* call_timeout would nest a timeout */
+                case MS_OP_CSEND: case MS_OP_CRECV: bad |= !conn; break;              /* on the block's own connection */
+                default: bad = 1; break;
+                }
+                scope[k] = (int32_t)i;
+            }
+        }
+        for (uint32_t i = 0; i < w->n_insns && !bad; i++) {
+            const madsim_insn_t* in = &w->insns[i];
+            if ((in->op == MS_OP_DJNZ || in->op == MS_OP_JMP || in->op == MS_OP_JEQ) && in->b < w->n_insns && scope[i] != scope[in->b]) bad = 1;
+        }
+        free(scope);
+        if (bad) return -1;
+    }
+    {   /* tickers, selects, signals: operand ranges (an op that runs without its ticker fails the call when it is met: poll_body);
+         * a select or timeout_at inside a scope would nest timeouts (refused above: not in the list); signals do not share a workload
+         * with the timer-tier ops (no kernel build carries both) */
+        int tiers = 0, signals = 0;
+        for (uint32_t i = 0; i < w->n_insns; i++) {
+            const madsim_insn_t* in = &w->insns[i];
+            switch (in->op) {
+            case MS_OP_INTERVAL: if ((in->b == 0 && in->imm == 0) || (in->a & 3) == 3 || in->a > 7 || in->imm >= NS_PER_S) return -1;   /* "`period` must be non-zero." */
+                /* fall through */
+            case MS_OP_TIMEOUT_BEGIN: case MS_OP_TIMEOUT_END: case MS_OP_TICK: case MS_OP_INTERVAL_RESET: tiers = 1; break;
+            case MS_OP_RECV_OR_TICK: case MS_OP_RECV_TIMEOUT_AT:
+                tiers = 1;
+                if (in->a >= w->n_socks || (in->op == MS_OP_RECV_OR_TICK ? (in->b & 0xfc) != 0 : in->imm >= NS_PER_S)) return -1;
+                break;
+            case MS_OP_RECV_OR_CTRL_C: if (in->a >= w->n_socks || (in->b & 0xfe)) return -1;
+                /* fall through */
+            case MS_OP_CTRL_C: signals = 1; break;
+            case MS_OP_SEND_CTRL_C: signals = 1; if (in->a > w->n_nodes) return -1; break;
+            default: break;
+            }
+        }
+        if (tiers && signals) return -1;
+    }
     {                                                     /* no body may run off the end of the table (the kernel does not check) */
         const uint8_t last = w->insns[w->n_insns - 1].op;
         if (last != MS_OP_DONE && last != MS_OP_JMP && last != MS_OP_PANIC) return -1;
@@ -1410,7 +1724,7 @@ static int validate(const madsim_workload_t* w, const madsim_config_t* cfg) {
     {   /* reset_node's socket drop order (network.rs:142-147: a HashMap under the seed's SipHash keys) is not restated: workloads
          * where it could be observed — a resettable node with two listening Endpoints — are refused, here as in the library */
         uint64_t resettable = 0;
-        for (uint32_t i = 0; i < w->n_insns; i++) if (w->insns[i].op == MS_OP_KILL || w->insns[i].op == MS_OP_RESTART) resettable |= 1ull << (w->insns[i].a & 63);
+        for (uint32_t i = 0; i < w->n_insns; i++) if (w->insns[i].op == MS_OP_KILL || w->insns[i].op == MS_OP_RESTART || w->insns[i].op == MS_OP_SEND_CTRL_C) resettable |= 1ull << (w->insns[i].a & 63);
         for (uint32_t n = 0; n <= w->n_nodes && w->nodes; n++) if (w->nodes[n].flags & (MADSIM_NODE_RESTART_ON_PANIC | MADSIM_NODE_RESTART_MATCHING)) resettable |= 1ull << n;
         for (uint32_t p = 0; p < w->n_progs; p++) if (w->progs[p].flags & MADSIM_PROG_INIT) resettable |= 1ull << (w->progs[p].node & 63);
         for (uint32_t n = 1; n <= w->n_nodes && n < 64; n++) {
@@ -1432,7 +1746,7 @@ static int validate(const madsim_workload_t* w, const madsim_config_t* cfg) {
     return 0;
 }
 
-static void run_one(const madsim_workload_t* w, const madsim_config_t* cfg, const madsim_limits_t* lim,
+static int run_one(const madsim_workload_t* w, const madsim_config_t* cfg, const madsim_limits_t* lim,
                     uint64_t seed, madsim_result_t* out, uint8_t* log, uint64_t log_cap,
                     uint64_t* log_len, madsim_oracle_stats_t* stats, int model_limits, uint32_t* events) {
     sim_t S; memset(&S, 0, sizeof S);
@@ -1497,6 +1811,11 @@ static void run_one(const madsim_workload_t* w, const madsim_config_t* cfg, cons
     if (log_len) *log_len = S.log_len;
     if (events) *events = S.model_events;
     if (stats) {
+        stats->scopes_expired += S.st.scopes_expired; stats->scopes_completed += S.st.scopes_completed;
+        stats->ticks_first_poll += S.st.ticks_first_poll; stats->ticks_parked += S.st.ticks_parked;
+        stats->sel_won_recv += S.st.sel_won_recv; stats->sel_won_time += S.st.sel_won_time; stats->sel_won_ctrl_c += S.st.sel_won_ctrl_c;
+        stats->msgs_lost += S.st.msgs_lost; stats->sig_lost += S.st.sig_lost; stats->sig_caught += S.st.sig_caught;
+        stats->sig_killed += S.st.sig_killed;
         if (S.st.max_heap > stats->max_heap) stats->max_heap = S.st.max_heap;
         if (S.st.max_ready > stats->max_ready) stats->max_ready = S.st.max_ready;
         if (S.st.max_tasks > stats->max_tasks) stats->max_tasks = S.st.max_tasks;
@@ -1511,6 +1830,7 @@ static void run_one(const madsim_workload_t* w, const madsim_config_t* cfg, cons
     for (uint32_t i = 0; i <= w->n_nodes; i++) { vec_free(S.nodes[i].paused_list); vec_free(S.nodes[i].tasks); }
     vec_free(S.heap); vec_free(S.ready); vec_free(S.tasks);
     free(S.handles); free(S.nodes); free(S.socks); free(S.clog_link);
+    return S.err;
 }
 
 /* ------------------------------------------------------------------------------------------------
@@ -1521,12 +1841,13 @@ static double now_s(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &
 int madsim_oracle_run_batch(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0,
                             uint64_t count, const madsim_limits_t* lim, madsim_result_t* out,
                             madsim_summary_t* summary, madsim_oracle_stats_t* stats) {
-    if (!cfg || validate(w, cfg)) return MADSIM_E_ARG;
+    { const int bad = cfg ? validate(w, cfg) : MADSIM_E_ARG; if (bad) return bad; }
     double t0 = now_s();
     uint64_t first = UINT64_MAX, nfail = 0, tsteps = 0, tclock = 0;
     for (uint64_t i = 0; i < count; i++) {
         madsim_result_t r;
-        run_one(w, cfg, lim, seed0 + i, &r, NULL, 0, NULL, stats, 1, NULL);
+        const int err = run_one(w, cfg, lim, seed0 + i, &r, NULL, 0, NULL, stats, 1, NULL);
+        if (err) return err;
         if (out) out[i] = r;
         if (r.verdict != MADSIM_PASS) { nfail++; if (seed0 + i < first) first = seed0 + i; }
         tsteps += r.steps; tclock += r.clock_ns;
@@ -1541,9 +1862,10 @@ int madsim_oracle_run_batch(const madsim_workload_t* w, const madsim_config_t* c
 int64_t madsim_oracle_trace_seed(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed,
                                  const madsim_limits_t* lim, uint8_t* log, uint64_t cap,
                                  madsim_result_t* out) {
-    if (!cfg || validate(w, cfg)) return MADSIM_E_ARG;
+    { const int bad = cfg ? validate(w, cfg) : MADSIM_E_ARG; if (bad) return bad; }
     madsim_result_t r; uint64_t n = 0;
-    run_one(w, cfg, lim, seed, &r, log, cap, &n, NULL, 1, NULL);
+    const int err = run_one(w, cfg, lim, seed, &r, log, cap, &n, NULL, 1, NULL);
+    if (err) return err;
     if (out) *out = r;
     return (int64_t)n;
 }
@@ -1553,10 +1875,11 @@ int64_t madsim_oracle_trace_seed(const madsim_workload_t* w, const madsim_config
  * madsim_oracle_run_batch reports; for any other seed the device runner's answer is the verdict MADSIM_UNSUPPORTED. */
 int madsim_oracle_run_batch_pure(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t count,
                                  const madsim_limits_t* lim, madsim_result_t* out, uint32_t* events) {
-    if (!cfg || validate(w, cfg)) return MADSIM_E_ARG;
+    { const int bad = cfg ? validate(w, cfg) : MADSIM_E_ARG; if (bad) return bad; }
     for (uint64_t i = 0; i < count; i++) {
         madsim_result_t r; uint32_t ev = 0;
-        run_one(w, cfg, lim, seed0 + i, &r, NULL, 0, NULL, NULL, 0, &ev);
+        const int err = run_one(w, cfg, lim, seed0 + i, &r, NULL, 0, NULL, NULL, 0, &ev);
+        if (err) return err;
         if (out) out[i] = r;
         if (events) events[i] = ev;
     }
@@ -1585,11 +1908,12 @@ int madsim_cpu_run_batch(const madsim_workload_t* w, const madsim_config_t* cfg,
 /* One seed with its observed-value list (see obs_record).  Returns the number of observations (may exceed cap). */
 int64_t madsim_oracle_observe_seed(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed,
                                    const madsim_limits_t* lim, uint64_t* obs, uint64_t cap, madsim_result_t* out) {
-    if (!cfg || validate(w, cfg)) return MADSIM_E_ARG;
+    { const int bad = cfg ? validate(w, cfg) : MADSIM_E_ARG; if (bad) return bad; }
     madsim_result_t r;
     g_obs_buf = obs; g_obs_cap = cap; g_obs_len = 0;
-    run_one(w, cfg, lim, seed, &r, NULL, 0, NULL, NULL, 1, NULL);
+    const int err = run_one(w, cfg, lim, seed, &r, NULL, 0, NULL, NULL, 1, NULL);
     g_obs_buf = NULL;
+    if (err) return err;
     if (out) *out = r;
     return (int64_t)g_obs_len;
 }

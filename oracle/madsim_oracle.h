@@ -20,6 +20,19 @@ typedef struct madsim_oracle_stats {
     uint32_t max_regs;   /* Mailbox.registered per socket */
     uint32_t max_conns;  /* live connections */
     uint32_t max_cq;     /* queued payloads per channel direction */
+    /* TEST-ONLY event counters of the timer-tier and signal ops, SUMMED over the seeds of the run (the fields above are maxima): what
+     * tests/test_oracle_tiers.py checks a fuzz block against, so that a block which never expires a scope cannot pass for one that does */
+    uint32_t scopes_expired;    /* timeout scopes whose Sleep elapsed: the block was dropped                           */
+    uint32_t scopes_completed;  /* timeout scopes whose block reached its MS_OP_TIMEOUT_END                            */
+    uint32_t ticks_first_poll;  /* MS_OP_TICKs Ready at their first poll (no timer, no yield)                          */
+    uint32_t ticks_parked;      /* MS_OP_TICKs that were Pending at their first poll                                   */
+    uint32_t sel_won_recv;      /* selects (RECV_OR_TICK, RECV_TIMEOUT_AT, RECV_OR_CTRL_C) the recv arm won            */
+    uint32_t sel_won_time;      /* ... the tick arm or timeout_at's Sleep won                                          */
+    uint32_t sel_won_ctrl_c;    /* ... the ctrl-c arm won                                                              */
+    uint32_t msgs_lost;         /* messages a dropped recv arm had taken into its rand_delay                           */
+    uint32_t sig_lost;          /* ctrl-c signals nobody waited for, or dropped with a select's subscription           */
+    uint32_t sig_caught;        /* ctrl_c() calls and ctrl-c arms that completed                                       */
+    uint32_t sig_killed;        /* ctrl-c signals to a node without a handler: kill_id                                 */
 } madsim_oracle_stats_t;
 
 /* Events in which a seed leaves the device runner's workload MODEL (not reference concepts; madsim_oracle.c model_event). */
@@ -36,6 +49,11 @@ typedef struct madsim_oracle_stats {
 #define MADSIM_ORACLE_ME_EPH_PORTS  1024u /* an ephemeral bind whose port lies beyond the table's candidate ports of that (node, IP) */
 #define MADSIM_ORACLE_ME_CONNS      2048u /* a 128th live connection                                                        */
 #define MADSIM_ORACLE_ME_MSGS       4096u /* a 256th message queued in one mailbox                                          */
+#define MADSIM_ORACLE_ME_SIG_WAITERS 8192u /* a ctrl-c signal that would schedule two or more waiters of one node           */
+
+/* An opcode this oracle has no case for (one beyond the table, or of an op family it does not restate): the call fails, it never
+ * becomes a verdict.  Returned by every entry point below (the trace / observe ones return it as their negative length). */
+#define MADSIM_ORACLE_E_OPCODE (-100)
 
 int madsim_oracle_run_batch(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0,
                             uint64_t count, const madsim_limits_t* lim, madsim_result_t* out,

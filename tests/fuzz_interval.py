@@ -11,6 +11,7 @@ import random
 
 from madsim_amd import _abi as A
 from madsim_amd import workload as W
+from tests.fuzz_scope import hazard
 
 REQ, RSP, TAG_REQ, TAG_RSP = 0x11, 0x22, 1, 2
 PERIODS_US = [300, 999, 1000, 1500, 4000, 10000, 25000, 50000]
@@ -48,11 +49,20 @@ def _body(rng, c, acl, a_dg, a_rpc, period_us):
     c.trace_val()
 
 
-def random_interval_workload(rng: random.Random):
+def general_servers(wl, ns, ports):
+    """The server's Endpoints bound on 0.0.0.0:port while the clients name them by the node's IP (Network::try_send's
+    `.or_else(0.0.0.0:port)` lookup, network.rs:296-313), as tests/fuzz.py random_addr_workload does: entries to bind."""
+    return [wl.addr(ns, p, ip="unspecified") for p in ports]
+
+
+def random_interval_workload(rng: random.Random, general_addr=False, hazards=False):
+    """-> (workload, config, description).  `general_addr`: see general_servers — the workload then needs the builds with general
+    address resolution.  `hazards`: fuzz_scope.hazard at the end of every ticker task.  Both off, the programs are the ones this
+    generator always made."""
     wl = W.WorkloadBuilder()
     ns = wl.create_node()
     a_dg, a_rpc = wl.addr(ns, 100), wl.addr(ns, 300)
-    _servers(wl, ns, a_dg, a_rpc, rng.choice([1, 3, 12]))
+    _servers(wl, ns, *(general_servers(wl, ns, (100, 300)) if general_addr else (a_dg, a_rpc)), rng.choice([1, 3, 12]))
     tickers = []
     for i in range(rng.randint(1, 3)):
         nc = wl.create_node()
@@ -80,6 +90,8 @@ def random_interval_workload(rng: random.Random):
         if rng.random() < 0.1:
             c.interval(behavior=rng.choice(["burst", "delay", "skip"]), us=rng.choice(PERIODS_US))   # replaced ticker
         c.djnz(0, top)
+        if hazards:
+            hazard(rng, c, acl)
         c.done()
         tickers.append((nc, c))
     m = wl.main()
@@ -102,7 +114,7 @@ def random_interval_workload(rng: random.Random):
     m.done()
     w = wl.build()
     cfg = A.Config.default(packet_loss_rate=rng.choice([0.0, 0.0, 0.1]))
-    return w, cfg
+    return w, cfg, f"{len(tickers)}t/{w.struct.n_insns}i" + ("/any" if general_addr else "")
 
 
 def interval_limits(state_mem=0):

@@ -64,11 +64,33 @@ def _scope(rng, c, acl, a_dg, a_ch, a_rpc):
         assert c.label() == j
 
 
-def random_scope_workload(rng: random.Random):
+HAZARD_TAG = 0x3D
+
+
+def hazard(rng, c, ep):
+    """What a client sometimes does last (the generators' `hazards` option): panic unless its last call timed out, or wait for a
+    datagram nobody sends — the run is a DEADLOCK once every timer has fired.  The blocks of tests/tier_blocks.py need both verdicts."""
+    r = rng.random()
+    if r < 0.08:
+        skip = c.label() + 2
+        c.jeq(A.VAL_TIMEOUT, skip); c.panic(5)
+        assert c.label() == skip
+    elif r < 0.16:
+        c.recv_from(ep, HAZARD_TAG)
+
+
+def random_scope_workload(rng: random.Random, general_addr=False, hazards=False):
+    """-> (workload, config, description).  `general_addr`: the server's Endpoints bind 0.0.0.0:port and the clients name them by the
+    node's IP (Network::try_send's `.or_else(0.0.0.0:port)` lookup, network.rs:296-313), as tests/fuzz.py random_addr_workload does: the
+    workload then needs the builds with general address resolution.  `hazards`: see hazard().  Both off, the programs are the ones
+    this generator always made."""
     wl = W.WorkloadBuilder()
     ns = wl.create_node()
     a_dg, a_ch, a_rpc = wl.addr(ns, 100), wl.addr(ns, 200), wl.addr(ns, 300)
-    _servers(wl, ns, a_dg, a_ch, a_rpc, rng.choice([1, 2, 5, 20]))
+    if general_addr:                                    # (no draw: the programs of one Random differ in their addresses only)
+        _servers(wl, ns, *(wl.addr(ns, p, ip="unspecified") for p in (100, 200, 300)), rng.choice([1, 2, 5, 20]))
+    else:
+        _servers(wl, ns, a_dg, a_ch, a_rpc, rng.choice([1, 2, 5, 20]))
     clients = []
     for i in range(rng.randint(1, 3)):
         nc = wl.create_node()
@@ -83,6 +105,8 @@ def random_scope_workload(rng: random.Random):
             _scope(rng, c, acl, a_dg, a_ch, a_rpc)
         if loop:
             c.djnz(0, top)
+        if hazards:
+            hazard(rng, c, acl)
         c.done()
         clients.append((nc, c))
     m = wl.main()
@@ -102,7 +126,7 @@ def random_scope_workload(rng: random.Random):
     cfg = A.Config.default(packet_loss_rate=rng.choice([0.0, 0.0, 0.1]))
     if rng.random() < 0.2:
         cfg.buggify = 1
-    return w, cfg
+    return w, cfg, f"{len(clients)}c/{w.struct.n_insns}i" + ("/any" if general_addr else "") + ("/buggify" if cfg.buggify else "")
 
 
 def scope_limits():

@@ -16,11 +16,14 @@ from tests import fuzz_interval as FI
 T = 9
 
 
-def random_select_workload(rng: random.Random):
+def random_select_workload(rng: random.Random, general_addr=False, hazards=False):
+    """-> (workload, config, description).  `general_addr`: the echo and RPC servers bind 0.0.0.0:port and their callers name
+    them by the node's IP (fuzz_interval.general_servers): the workload then needs the builds with general address resolution.  `hazards`:
+    fuzz_scope.hazard at the end of every selecting task.  Both off, the programs are the ones this generator always made."""
     wl = W.WorkloadBuilder()
     ns = wl.create_node()
     a_dg, a_rpc = wl.addr(ns, 100), wl.addr(ns, 300)
-    FI._servers(wl, ns, a_dg, a_rpc, rng.choice([1, 3, 12]))
+    FI._servers(wl, ns, *(FI.general_servers(wl, ns, (100, 300)) if general_addr else (a_dg, a_rpc)), rng.choice([1, 3, 12]))
     tickers = []
     for i in range(rng.randint(1, 3)):
         nc = wl.create_node()
@@ -46,6 +49,8 @@ def random_select_workload(rng: random.Random):
         if rng.random() < 0.1:
             c.tick(trace=True)
         c.djnz(0, top)
+        if hazards:
+            FI.hazard(rng, c, acl)
         c.done()
         tickers.append((nc, acl, c))
     peers = []
@@ -85,7 +90,7 @@ def random_select_workload(rng: random.Random):
     m.done()
     w = wl.build()
     cfg = A.Config.default(packet_loss_rate=rng.choice([0.0, 0.0, 0.1]))
-    return w, cfg
+    return w, cfg, f"{len(tickers)}t/{len(peers)}p/{w.struct.n_insns}i" + ("/any" if general_addr else "")
 
 
 def select_limits(state_mem=0):

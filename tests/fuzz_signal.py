@@ -12,18 +12,24 @@ import random
 
 from madsim_amd import _abi as A
 from madsim_amd import workload as W
+from tests.fuzz_scope import hazard
 
 T = 9
 SECOND_WAITER_P = 0.12
 
 
-def random_signal_workload(rng: random.Random):
+def random_signal_workload(rng: random.Random, general_addr=False, hazards=False):
+    """-> (workload, config, description).  `general_addr`: the nodes that are signalled bind 0.0.0.0:port and the peers name them by
+    the node's IP (Network::try_send's `.or_else(0.0.0.0:port)` lookup, network.rs:296-313), as tests/fuzz.py random_addr_workload
+    does: the workload then needs the build with general address resolution.  `hazards`: fuzz_scope.hazard at the end of every peer.  Both off, the
+    programs are the ones this generator always made."""
     wl = W.WorkloadBuilder()
     m = wl.main()
     servers, extra = [], []
     for i in range(rng.randint(1, 3)):
         n = wl.create_node()
-        a = wl.addr(n, 1 + i)
+        dst = wl.addr(n, 1 + i)                                # what the peers name
+        a = wl.addr(n, 1 + i, ip="unspecified") if general_addr else dst      # what the node binds
         s = wl.task(n, init=True, pre=True)
         s.bind(a)
         top = s.label()
@@ -39,7 +45,7 @@ def random_signal_workload(rng: random.Random):
         if rng.random() < 0.25:
             s.ctrl_c(); s.trace_instant()                      # a plain await in the same task
         s.jmp(top)
-        servers.append((n, a))
+        servers.append((n, dst))
         if rng.random() < SECOND_WAITER_P:
             x = wl.task(n)
             x.sleep_rand(lo_ms=0, ms=rng.choice([10, 40, 90]))
@@ -48,12 +54,13 @@ def random_signal_workload(rng: random.Random):
     bare = None
     if rng.random() < 0.5:                                     # a node whose tasks never call ctrl_c(): the signal kills it
         nb = wl.create_node()
-        ab = wl.addr(nb, 7)
+        db = wl.addr(nb, 7)
+        ab = wl.addr(nb, 7, ip="unspecified") if general_addr else db
         b = wl.task(nb, init=True, pre=True)
         b.bind(ab)
         top = b.label()
         b.recv_from(ab, T); b.reply(ab, T, 0x7E); b.jmp(top)
-        bare = (nb, ab)
+        bare = (nb, db)
     peers = []
     targets = servers + ([bare] if bare else [])
     for i in range(rng.randint(1, 2)):
@@ -68,6 +75,8 @@ def random_signal_workload(rng: random.Random):
         if rng.random() < 0.5:
             p.recv_from_timeout(ap, T, ms=rng.choice([2, 8])); p.trace_val()
         p.djnz(0, top)
+        if hazards:
+            hazard(rng, p, ap)
         p.done()
         peers.append(p)
     for x in extra:
@@ -100,7 +109,7 @@ def random_signal_workload(rng: random.Random):
     m.done()
     w = wl.build()
     cfg = A.Config.default(packet_loss_rate=rng.choice([0.0, 0.0, 0.1]))
-    return w, cfg
+    return w, cfg, f"{len(servers)}s/{len(extra)}x/{len(peers)}p/{w.struct.n_insns}i" + ("/any" if general_addr else "")
 
 
 def signal_limits(state_mem=0):

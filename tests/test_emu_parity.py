@@ -821,3 +821,25 @@ def test_global_state_32_lanes_is_refused_for_other_op_classes():
     lim.lanes_per_wave, lim.state_mem = 32, A.STATE_GLOBAL
     with pytest.raises(RuntimeError):
         emu.run_batch(LW.ALL["kv_rpc"](), 0, 8, None, lim)
+
+
+# ---- the op families with builds of their own: timeout scopes, interval tickers, selects, ctrl-c signals ------------------------------
+@pytest.mark.parametrize("family", ["scope", "interval", "select", "signal"])
+def test_fuzz_tier_families(family):
+    """The generators of tests/fuzz_scope.py, fuzz_interval.py, fuzz_select.py and fuzz_signal.py against the oracle: 40 programs x 24
+    seeds each, LDS and global state on alternating programs, general addresses on every third (the options and limits of the GPU blocks,
+    tests/tier_blocks.py) — a bug in the kernel text of the sixteen tier builds shows here without a GPU."""
+    from madsim_amd import runtime
+    from tests import tier_blocks as TB
+    fam = TB.FAMILIES[family]
+    verdicts = set()
+    for k in range(40):
+        w, cfg, desc = fam.program(6_000_000 + 1000 * sorted(TB.FAMILIES).index(family), k)
+        lim = TB.limits_of(fam, k)
+        g = runtime.geometry(w, lim)                      # (the host library's: what the device run of this program selects)
+        assert g.variant & TB.TIER_BITS == fam.tier and bool(g.variant & 16) == bool(k % 2), (family, k)
+        o, _ = oracle.run_batch(w, k * 7, 24, cfg, lim)
+        e = emu.run_batch(w, k * 7, 24, cfg, lim)
+        _strict(w, k * 7, o, e, cfg, lim, (family, k, desc))
+        verdicts |= set(o["verdict"].tolist())
+    assert {A.PASS, A.DEADLOCK} <= verdicts, (family, sorted(verdicts))

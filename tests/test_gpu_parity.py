@@ -39,14 +39,14 @@ FUZZ_SEED = _fuzz_seed()
 TALLY = parity.Tally()      # per generator: seeds compared, re-run with grown capacities, proven beyond the layout's ceilings
 
 
-def _fuzz_block(hip, gen, base, n, count, seed_mul, limits, alt_global=False, gen_kw=None, tally=None):
+def _fuzz_block(hip, gen, base, n, count, seed_mul, limits, alt_global=False, gen_kw=None, tally=None, gen_kw_of=None):
     """Programs gen(Random(base + k)), k < n, `count` seeds each, GPU vs oracle on all 48 result bytes.  EVERY seed is compared:
     a first-pass device capacity verdict (MADSIM_OVERFLOW) is re-run through madsim_hip_run_batch_auto and what comes back is held
     against the oracle like any other seed (tests/parity.py); a seed still OVERFLOW at the largest capacities fails unless the oracle's
     own high-water marks prove it needs more than the layout can hold."""
     import random
     for k in range(n):
-        w, cfg, desc = gen(random.Random(base + k), **(gen_kw or {}))
+        w, cfg, desc = gen(random.Random(base + k), **(gen_kw_of(k) if gen_kw_of else gen_kw or {}))      # (gen_kw_of: options by program index)
         lim = limits()
         if alt_global and k % 2:
             lim.lanes_per_wave, lim.state_mem = 0, A.STATE_GLOBAL

@@ -327,7 +327,7 @@ def test_emu_interval_fuzz_equals_interval_sim(block):
     import time
     base = 300 if block == "fixed" else int(time.time()) % 1_000_000 * 100
     for k in range(16):
-        w, cfg = fuzz_interval.random_interval_workload(random.Random(base + k))
+        w, cfg, _ = fuzz_interval.random_interval_workload(random.Random(base + k))
         got = resolved_emu(w, 0, 4, cfg, fuzz_interval.interval_limits(A.STATE_GLOBAL if k % 2 else A.STATE_LDS))
         assert_equals_interval_sim(got, w, cfg, 0, f"random_interval_workload(Random({base + k}))")
 

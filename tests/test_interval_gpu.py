@@ -26,7 +26,7 @@ def test_gpu_directed_interval_workloads_equal_interval_sim(hip):
 def test_gpu_interval_fuzz_equals_interval_sim(hip, block):
     base = 8000 if block == "fixed" else int(time.time()) % 1_000_000 * 100
     for k in range(12):
-        w, cfg = fuzz_interval.random_interval_workload(random.Random(base + k))
+        w, cfg, _ = fuzz_interval.random_interval_workload(random.Random(base + k))
         seed0 = 1000 * k
         got, _ = hip.run_batch_auto(w, seed0, 12, cfg, fuzz_interval.interval_limits(A.STATE_GLOBAL if k % 2 else A.STATE_LDS))
         assert_equals_interval_sim(got, w, cfg, seed0, f"random_interval_workload(Random({base + k})) seeds {seed0}..")

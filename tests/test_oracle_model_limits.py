@@ -16,9 +16,29 @@ import oracle
 from madsim_amd import _abi as A
 from tests import fuzz
 from tests import lifecycle_workloads as LW
+from tests import tier_blocks as TB
 
 
-@pytest.mark.parametrize("case", LW.model_ceiling_workloads(), ids=lambda c: c[0])
+def two_ctrl_c_waiters():
+    """The ceiling the ctrl-c ops added: two tasks of one node parked in ctrl_c() when the signal comes — the send would schedule both, in
+    an order tokio picks (MADSIM_UNSUPPORTED on the device, k_lifecycle.h node_send_ctrl_c).  On every seed: nothing else can happen first."""
+    wl = fuzz.W.WorkloadBuilder()
+    n = wl.create_node()
+    waiters = []
+    for i in range(2):
+        t = wl.task(n); t.ctrl_c(); t.flag_add(i, 1); t.done()
+        waiters.append(t)
+    m = wl.main()
+    for t in waiters:
+        m.spawn(t)
+    m.sleep(ms=5); m.send_ctrl_c(n)
+    for t in waiters:
+        m.join(t)
+    m.assert_flag(0, 1); m.assert_flag(1, 1); m.done()
+    return ("two ctrl_c() waiters of one node", wl.build(), A.Limits(), 8192)
+
+
+@pytest.mark.parametrize("case", LW.model_ceiling_workloads() + [two_ctrl_c_waiters()], ids=lambda c: c[0])
 def test_each_ceiling_is_an_event_of_the_pure_run_and_a_verdict_of_the_model_run(case):
     name, w, lim, bit = case
     on, _ = oracle.run_batch(w, 0, 16, None, lim)
@@ -52,18 +72,21 @@ GENS = [("random_workload", fuzz.generous_limits, {}), ("random_lifecycle_worklo
         ("random_ipvs_runtime_workload", fuzz.generous_limits, {}), ("random_timeout_workload", fuzz.mailbox_limits, {}),
         ("random_latency_workload", fuzz.mailbox_limits, {}), ("random_reply_without_receive_workload", fuzz.mailbox_limits, {}),
         ("random_unstructured_workload", fuzz.generous_limits, {}), ("random_unstructured_wide_workload", lambda: fuzz.wide_limits(0), {})]
+# the generators of the op families with builds of their own (the functions themselves: they live in modules of their own), with the
+# options of the GPU blocks (tests/tier_blocks.py), plain and general addresses
+GENS += [(fam.gen, fam.limits, dict(hazards=True, general_addr=ga)) for fam in TB.FAMILIES.values() for ga in (False, True)]
 
 EVENTS_SEEN = {}
 
 
-@pytest.mark.parametrize("gen,limits,kw", GENS, ids=[g[0] + ("+hooks" if g[2] else "") for g in GENS])
+@pytest.mark.parametrize("gen,limits,kw", GENS, ids=[(g[0] if isinstance(g[0], str) else g[0].__name__) + ("+hooks" if g[2].get("hooks") else "+general_addr" if g[2].get("general_addr") else "") for g in GENS])
 def test_every_generator_both_ways(gen, limits, kw):
     """600 programs x 8 seeds per generator, model limits on and off: byte-identical wherever the seed met no ceiling, MADSIM_UNSUPPORTED
     (every other field 0) in the model run wherever it met one."""
     n_ev = n = 0
     for k in range(600):
         try:
-            r = getattr(fuzz, gen)(random.Random(770_000 + k), **kw)
+            r = (getattr(fuzz, gen) if isinstance(gen, str) else gen)(random.Random(770_000 + k), **kw)
             w, cfg = r[0], r[1]
             on, _ = oracle.run_batch(w, k * 5, 8, cfg, limits())
         except RuntimeError:
@@ -78,4 +101,4 @@ def test_every_generator_both_ways(gen, limits, kw):
         for b in np.unique(ev[~inside]):
             EVENTS_SEEN[int(b)] = EVENTS_SEEN.get(int(b), 0) + 1
     assert n >= 3000, n
-    print(f"{gen}: {n} seeds both ways, {n_ev} met a ceiling of the workload model")
+    print(f"{gen if isinstance(gen, str) else gen.__name__}: {n} seeds both ways, {n_ev} met a ceiling of the workload model")

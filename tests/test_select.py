@@ -314,7 +314,7 @@ def test_emu_select_fuzz_equals_select_sim(block):
     import time
     base = 500 if block == "fixed" else int(time.time()) % 1_000_000 * 100
     for k in range(16):
-        w, cfg = fuzz_select.random_select_workload(random.Random(base + k))
+        w, cfg, _ = fuzz_select.random_select_workload(random.Random(base + k))
         got = resolved_emu(w, 0, 4, cfg, fuzz_select.select_limits(A.STATE_GLOBAL if k % 2 else A.STATE_LDS))
         assert_equals_select_sim(got, w, cfg, 0, f"random_select_workload(Random({base + k}))")
 
@@ -322,7 +322,7 @@ def test_emu_select_fuzz_equals_select_sim(block):
 def test_select_fuzz_reaches_every_rule():
     tot = dict(recv=0, tick=0, deadline=0, lost=0, immediate=0, stale=0)
     for k in range(24):
-        w, cfg = fuzz_select.random_select_workload(random.Random(500 + k))
+        w, cfg, _ = fuzz_select.random_select_workload(random.Random(500 + k))
         s = _sim(w, cfg)
         tot["recv"] += s.won["recv"]; tot["tick"] += s.won["tick"]; tot["deadline"] += s.won["deadline"]
         tot["lost"] += s.lost; tot["immediate"] += s.tick_immediate; tot["stale"] += s.stale_wakes

@@ -29,7 +29,7 @@ def test_gpu_directed_select_workloads_equal_select_sim(hip):
 def test_gpu_select_fuzz_equals_select_sim(hip, block):
     base = 9000 if block == "fixed" else int(time.time()) % 1_000_000 * 100
     for k in range(12):
-        w, cfg = fuzz_select.random_select_workload(random.Random(base + k))
+        w, cfg, _ = fuzz_select.random_select_workload(random.Random(base + k))
         seed0 = 1000 * k
         got, _ = hip.run_batch_auto(w, seed0, 12, cfg, fuzz_select.select_limits(A.STATE_GLOBAL if k % 2 else A.STATE_LDS))
         assert_equals_select_sim(got, w, cfg, seed0, f"random_select_workload(Random({base + k})) seeds {seed0}..")

@@ -360,7 +360,7 @@ def test_signal_fuzz_reaches_every_rule_and_keeps_the_unsupported_share_low():
     tot = dict(killed_by_signal=0, caught=0, lost_signals=0, lost_messages=0, unsupported=0)
     n = 0
     for k in range(48):
-        w, cfg = fuzz_signal.random_signal_workload(random.Random(500 + k))
+        w, cfg, _ = fuzz_signal.random_signal_workload(random.Random(500 + k))
         for seed in range(4):
             s = _sim(w, cfg, seed)
             n += 1
@@ -443,7 +443,7 @@ def test_emu_signal_fuzz_equals_signal_sim(block):
     import time
     base = 500 if block == "fixed" else int(time.time()) % 1_000_000 * 100
     for k in range(24):
-        w, cfg = fuzz_signal.random_signal_workload(random.Random(base + k))
+        w, cfg, _ = fuzz_signal.random_signal_workload(random.Random(base + k))
         got = resolved_emu(w, 0, 4, cfg, fuzz_signal.signal_limits(A.STATE_GLOBAL if k % 2 else A.STATE_LDS))
         assert_equals_signal_sim(got, w, cfg, 0, f"random_signal_workload(Random({base + k}))")
 

@@ -30,7 +30,7 @@ def test_gpu_signal_fuzz_equals_signal_sim(hip, block):
     base = 9000 if block == "fixed" else int(time.time()) % 1_000_000 * 100
     print("signal fuzz base", base)
     for k in range(12):
-        w, cfg = fuzz_signal.random_signal_workload(random.Random(base + k))
+        w, cfg, _ = fuzz_signal.random_signal_workload(random.Random(base + k))
         seed0 = 1000 * k
         got, _ = hip.run_batch_auto(w, seed0, 12, cfg, fuzz_signal.signal_limits(A.STATE_GLOBAL if k % 2 else A.STATE_LDS))
         assert_equals_signal_sim(got, w, cfg, seed0, f"random_signal_workload(Random({base + k})) seeds {seed0}..")

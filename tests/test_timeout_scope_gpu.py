@@ -33,7 +33,7 @@ def test_gpu_directed_scope_workloads_equal_scope_sim(hip):
 def test_gpu_scope_fuzz_equals_scope_sim(hip, block):
     base = 7000 if block == "fixed" else int(time.time()) % 1_000_000 * 100
     for k in range(12):
-        w, cfg = fuzz_scope.random_scope_workload(random.Random(base + k))
+        w, cfg, _ = fuzz_scope.random_scope_workload(random.Random(base + k))
         seed0 = 1000 * k
         got, _ = hip.run_batch_auto(w, seed0, 12, cfg, scope_limits(A.STATE_GLOBAL if k % 2 else A.STATE_LDS))
         assert_equals_scope_sim(got, w, cfg, seed0, f"random_scope_workload(Random({base + k})) seeds {seed0}..")

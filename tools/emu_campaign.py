@@ -2,7 +2,7 @@
 """CPU campaign: the kernel sources compiled for the host (tests/emu — a debugging aid, never the product path) against the oracle on fresh
 random programs of every generator in tests/fuzz.py, odd programs with the per-seed state in the global-memory block.  What it is for:
 kernel *logic* (the workload VM, the executor loop) checked at scale without GPU time; what it cannot see: anything the hardware or the
-device compiler adds.  Usage: emu_campaign.py [programs per generator] [base seed] [tight]
+device compiler adds.  Usage: emu_campaign.py [programs per generator] [base seed] [tight|-] [generators]
 `tight`: random stingy capacities (tasks, registrations, queued messages, heap slots, connections) instead of generous ones — the kernel
 must then give the capacity verdict and, re-run with grown capacities, the oracle's answer."""
 import os, sys, random, time
@@ -10,19 +10,25 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, oracle
 from tests import fuzz, emu, parity
 from madsim_amd import _abi as A
+from tests import tier_blocks as TB
 gens = [("random_workload", None, None), ("random_lifecycle_workload", 24, None), ("random_rpc_workload", 24, None), ("random_rpc_workload", 24, "hooks"),
         ("random_addr_workload", None, None), ("random_ephemeral_workload", None, None), ("random_channel_workload", 24, None),
         ("random_guard_workload", 24, None), ("random_supervisor_workload", 48, None), ("random_mixed_workload", 60, None), ("random_ipvs_workload", 24, None), ("random_ipvs_runtime_workload", 24, None),
         ("random_timeout_workload", None, None), ("random_reply_without_receive_workload", None, None),
         ("random_unstructured_workload", 16, None), ("random_latency_workload", None, None)]
+# the op families with builds of their own (tests/tier_blocks.py): "tier" entries, the family's name in the options' place
+gens += [(f.gen.__name__, "tier", f.name) for f in TB.FAMILIES.values()]
+if len(sys.argv) > 4:                              # optional: only the generators whose name contains one of these (comma-separated)
+    gens = [g for g in gens if any(x in g[0] for x in sys.argv[4].split(","))]
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 200; base = int(sys.argv[2]) if len(sys.argv) > 2 else 3_000_000; TIGHT = len(sys.argv) > 3 and sys.argv[3] == 'tight'; t0=time.time(); total=0; bad=0; tally=parity.Tally()
 for gi,(g,mt,opt) in enumerate(gens):
     for k in range(N):
         rng = random.Random(base + 100000*gi + k)
-        r = fuzz.random_rpc_workload(rng, hooks=True) if opt else getattr(fuzz, g)(rng)
+        fam = TB.FAMILIES[opt] if mt == "tier" else None
+        r = fam.gen(rng, **fam.gen_kw_of(k)) if fam else fuzz.random_rpc_workload(rng, hooks=True) if opt else getattr(fuzz, g)(rng)
         w, cfg, desc = r[0], r[1], r[2]
-        lim = fuzz.mixed_limits() if mt == 60 else fuzz.mailbox_limits() if g in ('random_timeout_workload', 'random_reply_without_receive_workload', 'random_latency_workload') else fuzz.generous_limits()
-        if mt and mt != 60: lim.max_tasks = mt
+        lim = fam.limits() if fam else fuzz.mixed_limits() if mt == 60 else fuzz.mailbox_limits() if g in ('random_timeout_workload', 'random_reply_without_receive_workload', 'random_latency_workload') else fuzz.generous_limits()
+        if mt and mt not in (60, "tier"): lim.max_tasks = mt
         if TIGHT:
             lr = random.Random(k)
             lim = A.Limits(); lim.max_steps = 200000
@@ -45,7 +51,7 @@ for gi,(g,mt,opt) in enumerate(gens):
         o, _ = oracle.run_batch(w, k * 5, 8, cfg, lim)
         total += 8
         try:                                      # every seed is compared: first-pass capacity verdicts are re-run with grown capacities (tests/parity.py)
-            parity.compare(e, o, lambda: parity.resolve_seed_by_seed(emu.run_batch, w, k * 5, e, cfg, lim), g + ("+hooks" if opt else ""), tally,
+            parity.compare(e, o, lambda: parity.resolve_seed_by_seed(emu.run_batch, w, k * 5, e, cfg, lim), g + ("+hooks" if opt == "hooks" else ""), tally,
                            (g, base + 100000*gi + k, desc[:120]), lambda i: parity.beyond_ceiling(w, k * 5 + i, cfg, lim))
         except AssertionError as ex:
             bad += 1; print("MISMATCH", ex)

@@ -8,6 +8,7 @@ import numpy as np
 import oracle
 from madsim_amd import runtime, _abi as A
 from tests import fuzz, parity
+from tests import tier_blocks as TB
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
 base = int(sys.argv[2]) if len(sys.argv) > 2 else 1_000_000
@@ -19,13 +20,17 @@ gens = [("plain", fuzz.random_workload, None), ("lifecycle", fuzz.random_lifecyc
         ("mixed", fuzz.random_mixed_workload, 60), ("ipvs", fuzz.random_ipvs_workload, 24), ("ipvs_rt", fuzz.random_ipvs_runtime_workload, 24),
         ("timeouts", fuzz.random_timeout_workload, None), ("stale_from", fuzz.random_reply_without_receive_workload, None),
         ("op_soup", fuzz.random_unstructured_workload, 16), ("latency", fuzz.random_latency_workload, None)]
+# the op families with builds of their own (timeout scopes, interval tickers, selects, ctrl-c signals): "tier_<family>", with the
+# hazards of the test blocks, general addresses on a third of the programs, under the family's limits (LDS; global on alternate rounds)
+tiers = {"tier_" + f.name: f for f in TB.FAMILIES.values()}
+gens += [(name, (lambda r, f=f: f.gen(r, general_addr=r.random() < 1 / 3, hazards=True)), None) for name, f in tiers.items()]
 if len(sys.argv) > 3:                              # optional: only the generators whose name contains one of these (comma-separated)
     gens = [g for g in gens if any(x in g[0] for x in sys.argv[3].split(","))]
 t0 = time.time(); k = 0; tally = parity.Tally(); n_narrow = 0
 while time.time() - t0 < budget:
     name, gen, max_tasks = gens[k % len(gens)]
     w, cfg, desc = gen(random.Random(base + k))
-    lim = fuzz.mailbox_limits() if name in ("timeouts", "stale_from", "latency") else fuzz.generous_limits()
+    lim = tiers[name].limits() if name in tiers else fuzz.mailbox_limits() if name in ("timeouts", "stale_from", "latency") else fuzz.generous_limits()
     if max_tasks: lim.max_tasks = max_tasks
     if (k // len(gens)) % 2:          # every other round: per-seed state in the global-memory block instead of LDS (Variant::G)
         lim.lanes_per_wave, lim.state_mem = 0, A.STATE_GLOBAL
