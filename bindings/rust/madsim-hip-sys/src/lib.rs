@@ -383,6 +383,7 @@ pub const MADSIM_E_HIP: c_int = -2;
 pub const MADSIM_E_NOINIT: c_int = -3;
 pub const MADSIM_E_WORKLOAD: c_int = -4;
 pub const MADSIM_E_LIMITS: c_int = -5;
+pub const MADSIM_TRACE_MAX_BYTES: u32 = 1073741824;
 pub const MADSIM_CAMPAIGN_STOP_AT_FAILURE: u32 = 1;
 pub const MADSIM_CAMPAIGN_LIST_RUNNER: u32 = 2;
 pub const MADSIM_CAMPAIGN_STOP_AT_CAP: u32 = 4;
@@ -437,12 +438,16 @@ extern "C" {
     pub fn madsim_hip_run_batch_async(w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, count: u64, lim: *const madsim_limits_t, d_out: *mut c_void, d_summary4: *mut c_void, stream: *mut c_void, timing_slot: c_int) -> c_int;
     pub fn madsim_hip_timing_ms(timing_slot: c_int, ms: *mut f64) -> c_int;
     pub fn madsim_hip_trace_seed(w: *const madsim_workload_t, cfg: *const madsim_config_t, seed: u64, lim: *const madsim_limits_t, log: *mut u8, cap: u64, out: *mut madsim_result_t) -> i64;
+    pub fn madsim_hip_trace_seeds(w: *const madsim_workload_t, cfg: *const madsim_config_t, seeds: *const u64, n: u64, lim: *const madsim_limits_t, logs: *mut u8, log_cap: u64, obs: *mut u64, obs_cap: u64, log_len: *mut u64, obs_len: *mut u64, out: *mut madsim_result_t) -> c_int;
+    pub fn madsim_hip_observe_seed(w: *const madsim_workload_t, cfg: *const madsim_config_t, seed: u64, lim: *const madsim_limits_t, obs: *mut u64, cap: u64, out: *mut madsim_result_t) -> i64;
     pub fn madsim_hip_ctx_run_batch(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, count: u64, lim: *const madsim_limits_t, out: *mut madsim_result_t, summary: *mut madsim_summary_t) -> c_int;
     pub fn madsim_hip_ctx_run_batch_auto(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, count: u64, lim: *const madsim_limits_t, out: *mut madsim_result_t, summary: *mut madsim_summary_t, max_rounds: c_int) -> c_int;
     pub fn madsim_hip_ctx_run_batch_device(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, count: u64, lim: *const madsim_limits_t, d_out: *mut c_void, stream: *mut c_void, summary: *mut madsim_summary_t) -> c_int;
     pub fn madsim_hip_ctx_run_batch_async(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, count: u64, lim: *const madsim_limits_t, d_out: *mut c_void, d_summary4: *mut c_void, stream: *mut c_void, timing_slot: c_int) -> c_int;
     pub fn madsim_hip_ctx_timing_ms(ctx: *mut madsim_hip_ctx_t, timing_slot: c_int, ms: *mut f64) -> c_int;
     pub fn madsim_hip_ctx_trace_seed(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed: u64, lim: *const madsim_limits_t, log: *mut u8, cap: u64, out: *mut madsim_result_t) -> i64;
+    pub fn madsim_hip_ctx_trace_seeds(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seeds: *const u64, n: u64, lim: *const madsim_limits_t, logs: *mut u8, log_cap: u64, obs: *mut u64, obs_cap: u64, log_len: *mut u64, obs_len: *mut u64, out: *mut madsim_result_t) -> c_int;
+    pub fn madsim_hip_ctx_observe_seed(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed: u64, lim: *const madsim_limits_t, obs: *mut u64, cap: u64, out: *mut madsim_result_t) -> i64;
     pub fn madsim_hip_run_batch_multi(ctxs: *const *mut madsim_hip_ctx_t, n_ctx: c_int, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, count: u64, lim: *const madsim_limits_t, out: *mut madsim_result_t, summary: *mut madsim_summary_t, max_rounds: c_int) -> c_int;
     pub fn madsim_hip_ctx_run_campaign(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, batch: u64, in_flight: u32, flags: u32, lim: *const madsim_limits_t, out: *mut madsim_campaign_t) -> c_int;
     pub fn madsim_hip_run_campaign(w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, batch: u64, in_flight: u32, flags: u32, lim: *const madsim_limits_t, out: *mut madsim_campaign_t) -> c_int;

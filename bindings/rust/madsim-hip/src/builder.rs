@@ -187,6 +187,25 @@ pub struct Diff {
     pub b: sys::madsim_campaign_t,
 }
 
+/// What one seed traced (`Builder::trace_seeds`): its result; `observations`, the first `obs_cap` values its test body handed to
+/// `trace` / `trace_time` / a traced tick, in execution order — what `obs_hash` folds — and `n_observations`, how many there were;
+/// `log`, the first `log_cap` bytes of its determinism log, and `log_len`, that log's length.  Under a runner verdict the lists are
+/// what was recorded until the verdict: not meaningful.
+#[derive(Clone, Debug)]
+pub struct SeedTrace {
+    pub seed: u64,
+    pub result: sys::madsim_result_t,
+    pub observations: Vec<u64>,
+    pub n_observations: u64,
+    pub log: Vec<u8>,
+    pub log_len: u64,
+}
+
+/// The `obs_hash` of a run that traced `values`, in that order: 64-bit FNV-1a over whole values (the offset basis for none).
+pub fn fold_observations(values: &[u64]) -> u64 {
+    values.iter().fold(0xCBF2_9CE4_8422_2325u64, |h, v| (h ^ v).wrapping_mul(0x100_0000_01B3))
+}
+
 impl Diff {
     /// Seeds that passed on side A and carry any other verdict on side B.
     pub fn regressions(&self) -> u64 {
@@ -268,6 +287,78 @@ impl Builder {
         }
         log.truncate((n as usize).min(log.len()));
         Ok((log, res))
+    }
+
+    /// What `seeds` traced (`madsim_hip_ctx_trace_seeds`): any order, duplicates allowed, the whole list in ONE launch of the trace build,
+    /// one `SeedTrace` per seed in the order given — the output a failing `#[madsim::test]` prints, for the seeds `search_failures`,
+    /// `failure_groups` and `diff_campaign` list.  With `resolve_runner` set, seeds that come back with a re-runnable runner verdict
+    /// are replayed as one further call per round under `madsim_hip_grow_limits(.., r)`, r = 1, 2, .. — a resolving campaign's rounds.
+    pub fn trace_seeds(&self, workload: &Workload, seeds: &[u64], obs_cap: usize, log_cap: usize) -> Result<Vec<SeedTrace>, RunError> {
+        let w = workload.raw();
+        let cfg = self.config.raw();
+        let lim0 = self.raw_limits(true);
+        let ctx = contexts()?.0[0];
+        let zero: sys::madsim_result_t = unsafe { std::mem::zeroed() };
+        let mut traces: Vec<SeedTrace> =
+            seeds.iter().map(|&seed| SeedTrace { seed, result: zero, observations: Vec::new(), n_observations: 0, log: Vec::new(), log_len: 0 }).collect();
+        let mut idx: Vec<usize> = (0..seeds.len()).collect();
+        let rounds = if self.resolve_flags & sys::MADSIM_CAMPAIGN_RESOLVE == 0 {
+            0
+        } else {
+            match (self.resolve_flags & sys::MADSIM_CAMPAIGN_RESOLVE_ROUNDS_MASK) >> sys::MADSIM_CAMPAIGN_RESOLVE_ROUNDS_SHIFT {
+                0 => sys::MADSIM_RESOLVE_DEFAULT_ROUNDS,
+                r => r,
+            }
+        };
+        for r in 0..=rounds {
+            if idx.is_empty() {
+                break;
+            }
+            let mut lim = lim0;
+            if r > 0 {
+                let rc = unsafe { sys::madsim_hip_grow_limits(&w, &lim0, r, &mut lim) };
+                if rc != 0 {
+                    return Err(last_error(rc));
+                }
+            }
+            let m = idx.len();
+            let s: Vec<u64> = idx.iter().map(|&i| seeds[i]).collect();
+            let (mut obs, mut logs) = (vec![0u64; m * obs_cap], vec![0u8; m * log_cap]);
+            let (mut olen, mut llen) = (vec![0u64; m], vec![0u64; m]);
+            let mut res = vec![zero; m];
+            let rc = unsafe {
+                sys::madsim_hip_ctx_trace_seeds(ctx, &w, &cfg, s.as_ptr(), m as u64, &lim,
+                                                if log_cap > 0 { logs.as_mut_ptr() } else { std::ptr::null_mut() }, log_cap as u64,
+                                                if obs_cap > 0 { obs.as_mut_ptr() } else { std::ptr::null_mut() }, obs_cap as u64,
+                                                llen.as_mut_ptr(), olen.as_mut_ptr(), res.as_mut_ptr())
+            };
+            if rc != 0 {
+                return Err(last_error(rc));
+            }
+            let cap = if lim.max_steps != 0 { lim.max_steps } else { 1 << 24 };
+            let ceiling = if lim.max_steps_ceiling != 0 { lim.max_steps_ceiling } else { 1 << 28 };
+            let mut again = Vec::new();
+            for (j, &i) in idx.iter().enumerate() {
+                let t = &mut traces[i];
+                t.result = res[j];
+                t.n_observations = olen[j];
+                t.log_len = llen[j];
+                t.observations = obs[j * obs_cap..j * obs_cap + (olen[j] as usize).min(obs_cap)].to_vec();
+                t.log = logs[j * log_cap..j * log_cap + (llen[j] as usize).min(log_cap)].to_vec();
+                if res[j].verdict == sys::MADSIM_OVERFLOW || (res[j].verdict == sys::MADSIM_STEP_LIMIT && cap < ceiling) {
+                    again.push(i);
+                }
+            }
+            idx = again;
+        }
+        Ok(traces)
+    }
+
+    /// What one seed traced, and its result: the values in execution order (at most 65 536 of them).  A failing `run_workload` names
+    /// its seed in the reproduction note; `Builder { seed, ..b }.observe_seed(&w, seed)` prints what that seed's test body traced.
+    pub fn observe_seed(&self, workload: &Workload, seed: u64) -> Result<(Vec<u64>, sys::madsim_result_t), RunError> {
+        let t = self.trace_seeds(workload, &[seed], 1 << 16, 0)?.remove(0);
+        Ok((t.observations, t.result))
     }
 
     /// Seed search: seeds `self.seed .. self.seed + self.count` as batches the LIBRARY keeps in flight on its own streams

@@ -575,6 +575,35 @@ int64_t madsim_hip_trace_seed(const madsim_workload_t* w, const madsim_config_t*
                               const madsim_limits_t* lim, uint8_t* log, uint64_t cap,
                               madsim_result_t* out);
 
+/* Observation logs: what the listed seeds traced.  madsim_result_t.obs_hash is an FNV-1a fold of the values the test body handed to
+ * MS_OP_TRACE, MS_OP_TRACE_TIME and a traced tick (64-bit offset basis 0xcbf29ce484222325, then h = (h ^ value) * 0x100000001b3 per value,
+ * the value folded whole); these calls return the values themselves, in execution order — the output a failing #[madsim::test] prints,
+ * for the seeds a campaign listed (madsim_failure_t.seed, madsim_group_t.first_seed, madsim_diff_record_t.seed).
+ *
+ * madsim_hip_trace_seeds replays `n` seeds (any order, duplicates allowed) on the trace build in ONE launch, with one synchronisation of the
+ * stream it runs on at the end of the call.  Row i of each output belongs to seeds[i].
+ *   logs:  n rows of log_cap bytes (NULL with log_cap 0: none kept): the determinism log, as madsim_hip_trace_seed writes it
+ *   obs:   n rows of obs_cap 64-bit words (NULL with obs_cap 0: none kept): the observed values in execution order, what obs_hash folds
+ *   log_len / obs_len (either may be NULL): n TRUE lengths, which may exceed the caps; a row holds the first min(len, cap) entries and
+ *          zeros behind them
+ *   out:   n results (may be NULL), the 48 bytes madsim_hip_run_batch gives for the seed under the same limits (with
+ *          madsim_limits_t.no_trace_hash: trace_hash = 0, though the log rows are written all the same)
+ * The call runs under the limits it is given and does not re-run: a seed may come back with a runner verdict (MADSIM_IS_RUNNER_VERDICT),
+ * and then its lists are what was recorded until that verdict — not meaningful, never to be compared; for a verdict >= MADSIM_UNSUPPORTED
+ * every other result field is 0, as everywhere.  Replay such seeds under madsim_hip_grow_limits(w, lim, r), r = 1, 2, ...
+ * n == 0 returns 0 and touches nothing.  MADSIM_E_ARG: seeds == NULL with n > 0; a buffer without a cap or a cap without a buffer.
+ * MADSIM_E_LIMITS: the call would ask the device for more than MADSIM_TRACE_MAX_BYTES — n * (log_cap + 8 * obs_cap + 72) bytes: the rows,
+ * two length words, the seed and the result of every seed.  The library never splits a list behind the caller's back: pass fewer seeds
+ * per call, or smaller caps. */
+#define MADSIM_TRACE_MAX_BYTES 1073741824u /* 1 GiB of device memory per madsim_hip_trace_seeds call */
+int madsim_hip_trace_seeds(const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n,
+                           const madsim_limits_t* lim, uint8_t* logs, uint64_t log_cap, uint64_t* obs, uint64_t obs_cap,
+                           uint64_t* log_len, uint64_t* obs_len, madsim_result_t* out);
+/* One seed's observations (the oracle's madsim_oracle_observe_seed, on the device): returns how many values the seed traced (may exceed
+ * cap; only the first cap are written, zeros behind a shorter list), <0 on error.  obs may be NULL with cap 0: the count alone. */
+int64_t madsim_hip_observe_seed(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed,
+                                const madsim_limits_t* lim, uint64_t* obs, uint64_t cap, madsim_result_t* out);
+
 /* The same entry points on an explicit context (see "Per-device contexts" above). */
 int madsim_hip_ctx_run_batch(madsim_hip_ctx_t* ctx, const madsim_workload_t* w, const madsim_config_t* cfg,
                              uint64_t seed0, uint64_t count, const madsim_limits_t* lim,
@@ -592,6 +621,12 @@ int madsim_hip_ctx_timing_ms(madsim_hip_ctx_t* ctx, int timing_slot, double* ms)
 int64_t madsim_hip_ctx_trace_seed(madsim_hip_ctx_t* ctx, const madsim_workload_t* w, const madsim_config_t* cfg,
                                   uint64_t seed, const madsim_limits_t* lim, uint8_t* log, uint64_t cap,
                                   madsim_result_t* out);
+int madsim_hip_ctx_trace_seeds(madsim_hip_ctx_t* ctx, const madsim_workload_t* w, const madsim_config_t* cfg,
+                               const uint64_t* seeds, uint64_t n, const madsim_limits_t* lim, uint8_t* logs, uint64_t log_cap,
+                               uint64_t* obs, uint64_t obs_cap, uint64_t* log_len, uint64_t* obs_len, madsim_result_t* out);
+int64_t madsim_hip_ctx_observe_seed(madsim_hip_ctx_t* ctx, const madsim_workload_t* w, const madsim_config_t* cfg,
+                                    uint64_t seed, const madsim_limits_t* lim, uint64_t* obs, uint64_t cap,
+                                    madsim_result_t* out);
 
 /* One process, several GPUs: the whole seed loop of Builder::run (builder.rs:129-150, every seed driven from one
  * process) over `n_ctx` contexts, each on its own GPU (or, for tests on a 1-GPU box, several on the same one).

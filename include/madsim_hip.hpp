@@ -504,6 +504,93 @@ struct Builder {
         return b;
     }
 
+    // What seeds traced (madsim_hip_trace_seeds): the values their test bodies handed to trace / trace_system_time / trace_instant / trace_val /
+    // a traced tick, in execution order — the output of a failing #[madsim::test] — for a whole list of seeds in ONE launch of the trace
+    // build.  `observations` holds the first obs_cap values (n_observations says how many there were), `log` the first log_cap bytes of the
+    // determinism log.  The builder's resolve_runner() rounds apply: seeds that come back with a re-runnable runner verdict are replayed as
+    // one further call under madsim_hip_grow_limits(.., r), r = 1, 2, ..  Under a runner verdict that stays the lists mean nothing.
+    struct SeedTrace {
+        uint64_t seed = 0;
+        madsim_result_t result{};
+        std::vector<uint64_t> observations;
+        uint64_t n_observations = 0;
+        std::vector<uint8_t> log;
+        uint64_t log_len = 0;
+    };
+    static uint64_t fold_observations(const std::vector<uint64_t>& values) {     // the obs_hash of a run that traced `values`: 64-bit FNV-1a
+        uint64_t h = 0xCBF29CE484222325ull;
+        for (uint64_t v : values) h = (h ^ v) * 0x100000001B3ull;
+        return h;
+    }
+    std::vector<SeedTrace> trace_seeds(const Workload& wl, const std::vector<uint64_t>& seeds, size_t obs_cap = 256, size_t log_cap = 0) const {
+        madsim::check(madsim_hip_init(device));
+        madsim_workload_t w = wl.raw();
+        madsim_config_t cfg = config.raw();
+        madsim_limits_t lim0 = capacities;
+        if (time_limit) { lim0.time_limit_ns = (uint64_t)(*time_limit * 1e9 + 0.5); if (!lim0.time_limit_ns) lim0.time_limit_ns = 1; }
+        return trace_seeds_under(w, cfg, lim0, seeds, obs_cap, log_cap);
+    }
+    // One seed's observation list (the shape of the oracle's observe_seed); `out`: its result.
+    std::vector<uint64_t> observe_seed(const Workload& wl, uint64_t s, madsim_result_t* out = nullptr, size_t obs_cap = 65536) const {
+        SeedTrace t = trace_seeds(wl, {s}, obs_cap, 0).front();
+        if (out) *out = t.result;
+        return t.observations;
+    }
+
+  private:
+    std::vector<SeedTrace> trace_seeds_under(const madsim_workload_t& w, const madsim_config_t& cfg, const madsim_limits_t& lim0,
+                                             const std::vector<uint64_t>& seeds, size_t obs_cap, size_t log_cap) const {
+        std::vector<SeedTrace> traces(seeds.size());
+        std::vector<size_t> idx(seeds.size());
+        for (size_t i = 0; i < idx.size(); i++) idx[i] = i;
+        uint32_t rounds = 0;
+        if (resolve_flags & MADSIM_CAMPAIGN_RESOLVE) {
+            rounds = (resolve_flags & MADSIM_CAMPAIGN_RESOLVE_ROUNDS_MASK) >> MADSIM_CAMPAIGN_RESOLVE_ROUNDS_SHIFT;
+            if (!rounds) rounds = MADSIM_RESOLVE_DEFAULT_ROUNDS;
+        }
+        for (uint32_t r = 0; r <= rounds && !idx.empty(); r++) {
+            madsim_limits_t lim = lim0;
+            if (r) madsim::check(madsim_hip_grow_limits(&w, &lim0, r, &lim));
+            const size_t m = idx.size();
+            std::vector<uint64_t> s(m), obs(m * obs_cap), olen(m), llen(m);
+            std::vector<uint8_t> logs(m * log_cap);
+            std::vector<madsim_result_t> res(m);
+            for (size_t j = 0; j < m; j++) s[j] = seeds[idx[j]];
+            madsim::check(madsim_hip_trace_seeds(&w, &cfg, s.data(), m, &lim, log_cap ? logs.data() : nullptr, log_cap, obs_cap ? obs.data() : nullptr,
+                                                 obs_cap, llen.data(), olen.data(), res.data()));
+            std::vector<size_t> again;
+            const uint32_t cap = lim.max_steps ? lim.max_steps : 1u << 24, ceiling = lim.max_steps_ceiling ? lim.max_steps_ceiling : 1u << 28;
+            for (size_t j = 0; j < m; j++) {
+                SeedTrace& t = traces[idx[j]];
+                t.seed = s[j]; t.result = res[j]; t.n_observations = olen[j]; t.log_len = llen[j];
+                t.observations.assign(obs.begin() + j * obs_cap, obs.begin() + j * obs_cap + (size_t)std::min<uint64_t>(olen[j], obs_cap));
+                t.log.assign(logs.begin() + j * log_cap, logs.begin() + j * log_cap + (size_t)std::min<uint64_t>(llen[j], log_cap));
+                if (res[j].verdict == MADSIM_OVERFLOW || (res[j].verdict == MADSIM_STEP_LIMIT && cap < ceiling)) again.push_back(idx[j]);
+            }
+            idx.swap(again);
+        }
+        return traces;
+    }
+    static bool same_result(const madsim_result_t& a, const madsim_result_t& b) {
+        return a.verdict == b.verdict && a.steps == b.steps && a.clock_ns == b.clock_ns && a.msg_count == b.msg_count && a.rng_calls == b.rng_calls &&
+               a.trace_hash == b.trace_hash && a.obs_hash == b.obs_hash;
+    }
+    // the `observe` option of search_failures / failure_groups / diff_against: the listed seeds replayed in one trace_seeds call; the trace build
+    // must give the bytes the campaign listed (a listed runner verdict says nothing a replay must repeat)
+    std::vector<std::vector<uint64_t>> observe_listed(const madsim_workload_t& w, const madsim_config_t& cfg, const madsim_limits_t& lim,
+                                                      const std::vector<uint64_t>& seeds, const std::vector<madsim_result_t>& listed, size_t cap) const {
+        std::vector<std::vector<uint64_t>> lists;
+        if (seeds.empty()) return lists;
+        std::vector<SeedTrace> traces = trace_seeds_under(w, cfg, lim, seeds, cap, 0);
+        for (size_t i = 0; i < traces.size(); i++) {
+            if (!MADSIM_IS_RUNNER_VERDICT(listed[i].verdict) && !same_result(traces[i].result, listed[i]))
+                throw Error(MADSIM_E_HIP, "seed " + std::to_string(seeds[i]) + ": the trace build's replay differs from the result the campaign listed");
+            lists.push_back(std::move(traces[i].observations));
+        }
+        return lists;
+    }
+
+  public:
     // Seed search: seed .. seed + count as batches the LIBRARY keeps in flight on its own streams (madsim_hip_run_campaign),
     // stopping at the first batch that holds a failing seed; prints the reproduction note for the seed it found.  No per-seed
     // results: re-run the reported seed for details.
@@ -527,8 +614,9 @@ struct Builder {
         std::vector<madsim_failure_t> failures;
         std::array<uint64_t, 8> by_verdict{};
         madsim_campaign_t campaign{};
+        std::vector<std::vector<uint64_t>> observations;                  // observe > 0: what failures[i].seed traced, at most `observe` values
     };
-    Failures search_failures(const Workload& wl, size_t max_failures) const {
+    Failures search_failures(const Workload& wl, size_t max_failures, size_t observe = 0) const {
         madsim::check(madsim_hip_init(device));
         madsim_workload_t w = wl.raw();
         madsim_config_t cfg = config.raw();
@@ -542,6 +630,12 @@ struct Builder {
         madsim::check(madsim_hip_run_campaign_collect(&w, &cfg, seed, count, 0, 0, resolve_flags, &lim, &f.campaign, &col));
         f.failures.resize((size_t)col.n_listed);
         for (int v = 0; v < 8; v++) f.by_verdict[(size_t)v] = col.n_by_verdict[v];
+        if (observe) {
+            std::vector<uint64_t> seeds;
+            std::vector<madsim_result_t> listed;
+            for (const madsim_failure_t& x : f.failures) { seeds.push_back(x.seed); listed.push_back(x.result); }
+            f.observations = observe_listed(w, cfg, lim, seeds, listed, observe);
+        }
         return f;
     }
 
@@ -578,10 +672,16 @@ struct Builder {
         std::vector<madsim_group_t> groups;                               // ascending by first_seed
         uint64_t n_grouped = 0, n_ungrouped = 0;                          // counted seeds in `groups` / in the groups that did not make the list
         madsim_campaign_t campaign{};
+        std::vector<std::vector<uint64_t>> observations;                  // observe > 0: what groups[i].first_seed traced, at most `observe` values
     };
     Groups failure_groups(const Workload& wl, size_t max_groups,
                           uint32_t include = (1u << MADSIM_PANIC) | (1u << MADSIM_DEADLOCK) | (1u << MADSIM_TIME_LIMIT),
                           uint32_t key_field = MADSIM_GROUP_KEY_OBS) const {
+        return failure_groups(wl, max_groups, include, key_field, 0);
+    }
+    // ... with `observe` > 0: each group's smallest seed replayed on the trace build (one trace_seeds call), Groups::observations[i] = the values it
+    // traced — the failure mode spelled out.  The replay must carry the verdict and the key the seed was grouped under.
+    Groups failure_groups(const Workload& wl, size_t max_groups, uint32_t include, uint32_t key_field, size_t observe) const {
         madsim::check(madsim_hip_init(device));
         madsim_workload_t w = wl.raw();
         madsim_config_t cfg = config.raw();
@@ -598,6 +698,20 @@ struct Builder {
         g.groups.resize((size_t)grp.n_groups);
         g.n_grouped = grp.n_grouped;
         g.n_ungrouped = grp.n_ungrouped;
+        if (observe && !g.groups.empty()) {
+            std::vector<uint64_t> seeds;
+            for (const madsim_group_t& x : g.groups) seeds.push_back(x.first_seed);
+            std::vector<SeedTrace> traces = trace_seeds_under(w, cfg, lim, seeds, observe, 0);
+            for (size_t i = 0; i < traces.size(); i++) {
+                const madsim_result_t& r = traces[i].result;
+                const uint64_t key = key_field == MADSIM_GROUP_KEY_OBS ? r.obs_hash : key_field == MADSIM_GROUP_KEY_TRACE ? r.trace_hash :
+                                     key_field == MADSIM_GROUP_KEY_MSGS ? r.msg_count : key_field == MADSIM_GROUP_KEY_CLOCK ? r.clock_ns :
+                                     key_field == MADSIM_GROUP_KEY_RNG ? r.rng_calls : r.steps;
+                if (r.verdict != g.groups[i].verdict || key != g.groups[i].key)
+                    throw Error(MADSIM_E_HIP, "seed " + std::to_string(seeds[i]) + ": the trace build's replay is not of the group the campaign put it in");
+                g.observations.push_back(std::move(traces[i].observations));
+            }
+        }
         return g;
     }
 
@@ -610,6 +724,7 @@ struct Builder {
         std::vector<madsim_diff_record_t> records;                        // ascending by seed
         madsim_diff_t report{};                                           // (records / cap: of the call; read `records` above)
         madsim_campaign_t a{}, b{};                                       // each side's plain campaign report
+        std::vector<std::vector<uint64_t>> observations_a, observations_b; // observe > 0: what records[i].seed traced on each side
         uint64_t regressions() const {                                    // passed on side A, any other verdict on side B
             uint64_t n = 0;
             for (int v = 1; v < 8; v++) n += report.transitions[MADSIM_PASS][v];
@@ -618,6 +733,11 @@ struct Builder {
     };
     Diff diff_against(const Builder& other, const Workload& wl, const Workload& other_wl,
                       uint32_t fields = MADSIM_DIFF_ALL, size_t max_listed = 0) const {
+        return diff_against(other, wl, other_wl, fields, max_listed, 0);
+    }
+    // ... with `observe` > 0: the listed seeds replayed on the trace build, one trace_seeds call per side under that side's configuration and
+    // capacities (this builder's resolve rounds), Diff::observations_a[i] / _b[i] = what records[i].seed traced on each side.
+    Diff diff_against(const Builder& other, const Workload& wl, const Workload& other_wl, uint32_t fields, size_t max_listed, size_t observe) const {
         madsim::check(madsim_hip_init(device));
         madsim_workload_t wa = wl.raw(), wb = other_wl.raw();
         madsim_config_t ca = config.raw(), cb = other.config.raw();
@@ -632,6 +752,13 @@ struct Builder {
         madsim::check(madsim_hip_run_campaign_diff(&wa, &ca, &la, &wb, &cb, &lb, seed, count, 0, 0, resolve_flags, &d.a, &d.b, &d.report));
         d.records.resize((size_t)d.report.n_listed);
         d.report.records = nullptr;                                       // (the vector may move with the struct)
+        if (observe) {
+            std::vector<uint64_t> seeds;
+            std::vector<madsim_result_t> ra, rb;
+            for (const madsim_diff_record_t& x : d.records) { seeds.push_back(x.seed); ra.push_back(x.a); rb.push_back(x.b); }
+            d.observations_a = observe_listed(wa, ca, la, seeds, ra, observe);
+            d.observations_b = observe_listed(wb, cb, lb, seeds, rb, observe);
+        }
         return d;
     }
     Diff diff_against(const Builder& other, const Workload& wl, uint32_t fields = MADSIM_DIFF_ALL, size_t max_listed = 0) const {

@@ -236,6 +236,9 @@ class Resolve(C.Structure):
 assert C.sizeof(Resolve) == 112
 HEADER_STRUCTS["madsim_resolve_t"] = Resolve
 
+TRACE_MAX_BYTES = 1 << 30     # madsim_hip_trace_seeds: device memory one call may ask for, n * (log_cap + 8 * obs_cap + 72)
+FNV_OFFSET, FNV_PRIME = 0xCBF29CE484222325, 0x100000001B3      # obs_hash / trace_hash: 64-bit FNV-1a over whole values
+
 
 class Geometry(C.Structure):
     _fields_ = [

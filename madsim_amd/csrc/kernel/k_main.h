@@ -37,6 +37,7 @@ __device__ __forceinline__ void seed_init(const Ctx& c, Lane& L, uint64_t seed) 
     { uint64_t h = L.trace_hash, n = L.log_len; uint32_t bt = gen_range_small<Variant<false, false, K::LWS, 0, K::RQ>, 31536000u>(c, L); L.trace_hash = h; L.log_len = n;
       if (K::LIFE) NODEW(4 + ((P.n_nodes + 4) >> 2)) = bt; }      // seconds into 2022: SystemTime::now() of MS_OP_TRACE_TIME
     L.trace_hash = FNV_OFFSET; L.obs_hash = FNV_OFFSET; L.log_len = 0;
+    if (K::TRACE) L.obs_len = 0;
     // tasks spawned before block_on, then the main task (task/mod.rs:222-235)
     for (uint32_t p = 1; p < P.n_progs; p++) {
         uint32_t fl = (PROGW(c, p) >> 8) & 0xff;
@@ -155,6 +156,10 @@ __global__ __launch_bounds__(256, K::CMP ? 4 : !K::G ? 1 : (K::FEAT & (MADSIM_FE
         pass++;
         if (!have) {
             if (next >= P.count) break;
+            if (K::TRACE) {                               // this unit's rows of the two logs (next < count: inside what the host sized)
+                c.tlog = P.trace_log + next * P.trace_cap;
+                c.olog = (P.obs_log && P.obs_cap) ? P.obs_log + next * P.obs_cap : nullptr;
+            }
             seed_init<K>(c, L, P.seed_list ? P.seed_list[next] : P.seed0 + next);
             have = true;
         }
@@ -276,7 +281,7 @@ __global__ __launch_bounds__(256, K::CMP ? 4 : !K::G ? 1 : (K::FEAT & (MADSIM_FE
             r.rng_calls = L.rng_calls; r.trace_hash = (K::NOLOG || (K::LOGSW && P.no_log)) ? 0 : L.trace_hash; r.obs_hash = L.obs_hash;
             if (r.verdict >= MADSIM_UNSUPPORTED) { r.steps = 0; r.clock_ns = 0; r.msg_count = 0; r.rng_calls = 0; r.trace_hash = 0; r.obs_hash = 0; }   // the verdict is the whole answer
             P.out[next] = r;
-            if (K::TRACE) *P.trace_len = L.log_len;
+            if (K::TRACE) { P.trace_len[next] = L.log_len; if (P.obs_len) P.obs_len[next] = L.obs_len; }
             have = false;
             if (K::DEDUP) L.exact = 0;
             // next unit: static striding, or the per-launch work queue (a lane whose seeds end early — deadlocks under

@@ -84,7 +84,7 @@ __device__ __forceinline__ void tick_complete(const Ctx& c, Lane& L, uint32_t sl
     if (behaviour != TICK_BURST && L.clock > dl + 5 * NS_PER_MS) next = tick_late_next(dl, L.clock, period, behaviour);
     TWORD(c, slot, c.P.tick_unit, 2) = (uint32_t)next;
     TWORD(c, slot, c.P.tick_unit, 3) = (uint32_t)(next >> 32);
-    if (a & 1) L.obs_hash = (L.obs_hash ^ dl) * FNV_PRIME;
+    if (a & 1) obs_fold<K>(c, L, dl);
 }
 
 // The tick arm of MS_OP_RECV_OR_TICK's select! (Interval::poll_tick, time/interval.rs:142-169), polled after the task's Mailbox::recv.  Its
@@ -666,7 +666,7 @@ __device__ __forceinline__ bool poll_task(const Ctx& c, Lane& L, const uint32_t 
             } else {                                       // MS_OP_TRACE
                 uint64_t v = imm;
                 if (b & 1) v += (u0.z >> ((a & 1) * 16)) & 0xffff;
-                L.obs_hash = (L.obs_hash ^ v) * FNV_PRIME;
+                obs_fold<K>(c, L, v);
                 pc++;
             }
 
@@ -1166,7 +1166,7 @@ __device__ __forceinline__ bool poll_task(const Ctx& c, Lane& L, const uint32_t 
                 if (!K::LIFE) { st = ST_PANIC; break; }
                 uint64_t v = a == 2 ? (uint64_t)u0.w : L.clock;
                 if (a == 0) v += (1639872000ull + NODEW(4 + ((P.n_nodes + 4) >> 2))) * NS_PER_S;   // 52 x 365 days + the draw
-                L.obs_hash = (L.obs_hash ^ v) * FNV_PRIME;
+                obs_fold<K>(c, L, v);
                 pc++;
                 break;
             }

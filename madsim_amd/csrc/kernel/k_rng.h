@@ -75,6 +75,17 @@ __device__ __forceinline__ void rng_log(const Ctx& c, Lane& L, bool have = false
     L.log_len++;
 }
 
+// One observed value (MS_OP_TRACE, MS_OP_TRACE_TIME, a traced tick): folded into obs_hash; the trace builds also keep the value itself,
+// the first obs_cap of a seed (rng_log's rule: the length counts on past the cap).
+template <class K>
+__device__ __forceinline__ void obs_fold(const Ctx& c, Lane& L, uint64_t v) {
+    L.obs_hash = (L.obs_hash ^ v) * FNV_PRIME;
+    if (K::TRACE) {
+        if (c.olog && L.obs_len < c.P.obs_cap) c.olog[L.obs_len] = v;
+        L.obs_len++;
+    }
+}
+
 // gen_range(lo..hi) on u64 [DEP rand 0.8 UniformInt::sample_single_inclusive]; one with() per call.
 template <class K>
 __device__ __forceinline__ uint64_t gen_range_u64(const Ctx& c, Lane& L, uint64_t lo, uint64_t range) {

@@ -159,6 +159,7 @@ struct Lane {
     // every timer a heap entry, as everywhere else
     uint32_t exact, hazard;
     uint64_t dd_occ;         // which buckets of the re-registration table hold a count (k_timer.h dedup_note)
+    uint64_t obs_len;        // trace builds: values folded into obs_hash so far (k_rng.h obs_fold)
 };
 
 #define LDS128(i) (reinterpret_cast<uint4*>(SMEM)[(i)])
@@ -188,7 +189,8 @@ struct Ctx {
     // has not finished yet (task_finish's "which endpoints did this task own" search)
     uint32_t amask0, omask0;
     uint32_t pmask0;     // Variant::NH: word index of the delivery-record pool's used mask (bit r of word r / 32 = record r holds a message in flight)
-    uint8_t* tlog;       // trace mode only
+    uint8_t* tlog;       // trace mode only: the current unit's row of the determinism log
+    uint64_t* olog;      // trace mode only: the current unit's row of the observation log (null: none kept)
     __device__ Ctx(const KParams& p) : P(p) {}
 };
 

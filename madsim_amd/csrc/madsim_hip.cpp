@@ -122,7 +122,8 @@ struct madsim_hip_ctx {
     unsigned long long* d_acc = nullptr;      // 4 x u64 summary accumulators
     madsim_result_t* d_out = nullptr; size_t out_cap = 0;
     uint64_t* d_seeds = nullptr; size_t seeds_cap = 0;        // seed list of a compacted re-run
-    uint8_t* d_tlog = nullptr; size_t tlog_cap = 0; uint64_t* d_tlen = nullptr;
+    // trace launches: the rows of the determinism log (bytes) and of the observation log (words), the length words (tlen_cap of them)
+    uint8_t* d_tlog = nullptr; size_t tlog_cap = 0; uint64_t* d_olog = nullptr; size_t olog_cap = 0; uint64_t* d_tlen = nullptr; size_t tlen_cap = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipEvent_t pipe_begin = nullptr;          // run_pipelined: before the first sub-batch of a call
     hipEvent_t tev[2 * 64] = {};              // timing slots of madsim_hip_run_batch_async
@@ -198,7 +199,6 @@ int madsim_hip_ctx::open(int dev_index) {
     lds_per_cu = prop.maxSharedMemoryPerMultiProcessor ? prop.maxSharedMemoryPerMultiProcessor : 160 * 1024;
     if (lds_per_cu > 160 * 1024) lds_per_cu = 160 * 1024;
     HIP_TRY(hipMalloc(&d_acc, 4 * sizeof(unsigned long long)));
-    HIP_TRY(hipMalloc(&d_tlen, sizeof(uint64_t)));
     HIP_TRY(hipMalloc(&d_prof, 16 * sizeof(uint64_t)));
     HIP_TRY(hipMemset(d_prof, 0, 16 * sizeof(uint64_t)));
     HIP_TRY(hipEventCreate(&ev0));
@@ -219,6 +219,7 @@ void madsim_hip_ctx::close() {
     if (d_out) (void)hipFree(d_out);
     if (d_seeds) (void)hipFree(d_seeds);
     if (d_tlog) (void)hipFree(d_tlog);
+    if (d_olog) (void)hipFree(d_olog);
     if (d_tlen) (void)hipFree(d_tlen);
     if (d_prof) (void)hipFree(d_prof);
     if (ev0) (void)hipEventDestroy(ev0);
@@ -262,8 +263,8 @@ void madsim_hip_ctx::close() {
         f = Flight();
     }
     for (auto& e : tev) if (e) (void)hipEventDestroy(e);
-    d_acc = nullptr; d_out = nullptr; d_seeds = nullptr; d_tlog = nullptr; d_tlen = nullptr; d_prof = nullptr;
-    ev0 = ev1 = nullptr; pipe_begin = nullptr; out_cap = seeds_cap = tlog_cap = 0;
+    d_acc = nullptr; d_out = nullptr; d_seeds = nullptr; d_tlog = nullptr; d_olog = nullptr; d_tlen = nullptr; d_prof = nullptr;
+    ev0 = ev1 = nullptr; pipe_begin = nullptr; out_cap = seeds_cap = tlog_cap = olog_cap = tlen_cap = 0;
     for (auto& e : tev) e = nullptr;
     device = -1;
 }
@@ -956,36 +957,114 @@ int madsim_hip_ctx_run_batch_auto(madsim_hip_ctx_t* c, const madsim_workload_t* 
     return 0;
 }
 
-int64_t madsim_hip_ctx_trace_seed(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed,
-                                  const madsim_limits_t* lim, uint8_t* log, uint64_t cap, madsim_result_t* out) {
+// Replay a list of seeds on the trace build: one launch, unit i = seeds[i], each unit with its own row of the determinism log and of the
+// observation log and its own pair of length words (k_main.h).  The device buffers are zero before the launch, so a row comes back as its
+// first min(len, cap) entries and zeros; every output is one copy, and the call ends with one synchronisation of the stream it ran on.
+// Once anything is queued that reads or writes the caller's memory no error returns before that synchronisation: the first error is kept
+// and nothing more is queued behind it.
+// `single` is madsim_hip_trace_seed, as it always was: one seed, the log copied straight into the caller's buffer — its first min(len, cap)
+// bytes and nothing behind them, so the device row needs no zeroes —, no bound on `log_cap` but the device's memory, and results that
+// carry the fingerprint whatever the limits say.  The list form answers with the bytes madsim_hip_run_batch gives: the trace builds always
+// fold the determinism log, so under madsim_limits_t.no_trace_hash its results' trace_hash is zeroed here.
+static int trace_list(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n,
+                      const madsim_limits_t* lim, uint8_t* logs, uint64_t log_cap, uint64_t* obs, uint64_t obs_cap,
+                      uint64_t* log_len, uint64_t* obs_len, madsim_result_t* out, bool single) {
+    if (n == 0) return 0;
+    if (!seeds) return fail(MADSIM_E_ARG, "trace_seeds: null seed list");
+    if ((logs != nullptr) != (log_cap != 0)) return fail(MADSIM_E_ARG, "trace_seeds: `logs` and log_cap are given together or not at all");
+    if ((obs != nullptr) != (obs_cap != 0)) return fail(MADSIM_E_ARG, "trace_seeds: `obs` and obs_cap are given together or not at all");
+    if (!single) {
+        // what the call asks of the device, per seed: the two rows, the two lengths, the seed and the result
+        const uint64_t M = MADSIM_TRACE_MAX_BYTES;
+        if (log_cap > M || obs_cap > M / 8 || n > M) return fail(MADSIM_E_LIMITS, "trace_seeds: more than MADSIM_TRACE_MAX_BYTES of device memory");
+        const uint64_t per_seed = log_cap + 8 * obs_cap + 3 * sizeof(uint64_t) + sizeof(madsim_result_t);
+        if (per_seed > M / n) return fail(MADSIM_E_LIMITS, "trace_seeds: n x (log_cap + 8 obs_cap + 72) exceeds MADSIM_TRACE_MAX_BYTES: fewer seeds per call, or smaller caps");
+    }
     CTX_ENTER(c);
     int rc = madsim_geo::validate(w, cfg, &g_err);
     if (rc) return rc;
     Geo G;
-    if ((rc = madsim_geo::make_geometry(c->dev(), w, cfg, lim, 1, &G, &g_err, true))) return rc;
+    if ((rc = madsim_geo::make_geometry(c->dev(), w, cfg, lim, n, &G, &g_err, true))) return rc;
+    G.P.count = n;
     if ((rc = c->upload_workload(w, G.P))) return rc;
-    if ((rc = c->ensure_scratch(G.P, nullptr, false))) return rc;
-    if (cap > c->tlog_cap) {
-        if (c->d_tlog) (void)hipFree(c->d_tlog);
-        c->d_tlog = nullptr; c->tlog_cap = 0;
-        HIP_TRY(hipMalloc(&c->d_tlog, cap));
-        c->tlog_cap = cap;
-    }
-    if ((rc = c->ensure_out(64))) return rc;
-    G.P.seed0 = seed; G.P.count = 1; G.P.out = c->d_out;
-    G.P.trace_log = cap ? c->d_tlog : nullptr; G.P.trace_cap = cap; G.P.trace_len = c->d_tlen;
+    hipStream_t st = nullptr;
+    if ((rc = c->ensure_scratch(G.P, st, false))) return rc;
+    auto room = [](auto*& d, size_t& have, size_t want) -> hipError_t {       // (`want` in elements of *d)
+        if (want <= have) return hipSuccess;
+        if (d) (void)hipFree(d);
+        d = nullptr; have = 0;
+        hipError_t e = hipMalloc((void**)&d, want * sizeof *d);
+        if (e == hipSuccess) have = want;
+        return e;
+    };
+    HIP_TRY(room(c->d_tlog, c->tlog_cap, (size_t)(n * log_cap)));
+    HIP_TRY(room(c->d_olog, c->olog_cap, (size_t)(n * obs_cap)));
+    HIP_TRY(room(c->d_tlen, c->tlen_cap, (size_t)(2 * n)));                  // [n] log lengths, then [n] observation counts
+    HIP_TRY(room(c->d_seeds, c->seeds_cap, (size_t)n));
+    if ((rc = c->ensure_out((size_t)n))) return rc;
     if (G.lds_bytes > c->lds_attr) {
         if (madsim_k_set_max_lds((uint32_t)c->lds_per_cu)) return fail(MADSIM_E_HIP, "hipFuncSetAttribute failed");
         c->lds_attr = (uint32_t)c->lds_per_cu;
     }
-    if (madsim_k_launch_sim(&G.P, 1, G.lds_bytes, nullptr, 1)) return fail(MADSIM_E_LIMITS, "no trace kernel build");
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    uint64_t n = 0;
-    HIP_TRY(hipMemcpy(&n, c->d_tlen, sizeof n, hipMemcpyDeviceToHost));
-    if (log && cap) HIP_TRY(hipMemcpy(log, c->d_tlog, n < cap ? n : cap, hipMemcpyDeviceToHost));
-    if (out) HIP_TRY(hipMemcpy(out, c->d_out, sizeof *out, hipMemcpyDeviceToHost));
-    return (int64_t)n;
+    uint64_t* d_olen = c->d_tlen + n;
+    G.P.seed0 = 0; G.P.count = n; G.P.seed_list = c->d_seeds; G.P.out = c->d_out;
+    G.P.trace_log = log_cap ? c->d_tlog : nullptr; G.P.trace_cap = log_cap; G.P.trace_len = c->d_tlen;
+    G.P.obs_log = obs_cap ? c->d_olog : nullptr; G.P.obs_cap = obs_cap; G.P.obs_len = d_olen;
+    // from here on the stream may hold work on the caller's memory: every step is tried only while all before it succeeded, and the
+    // synchronisation is reached whatever happened
+    hipError_t err = hipSuccess;
+    const char* at = nullptr;
+    bool no_build = false;
+    auto step = [&](hipError_t e, const char* what) { if (e != hipSuccess && err == hipSuccess) { err = e; at = what; } return err == hipSuccess && !no_build; };
+    uint64_t one_len = 0;                                                     // (`single`: the length is needed here, before the log is copied)
+    bool ok = step(hipMemcpyAsync(c->d_seeds, seeds, n * sizeof(uint64_t), hipMemcpyHostToDevice, st), "hipMemcpyAsync(seeds)");
+    if (ok && log_cap && !single) ok = step(hipMemsetAsync(c->d_tlog, 0, n * log_cap, st), "hipMemsetAsync(log rows)");
+    if (ok && obs_cap) ok = step(hipMemsetAsync(c->d_olog, 0, n * obs_cap * sizeof(uint64_t), st), "hipMemsetAsync(observation rows)");
+    if (ok) ok = step(hipMemsetAsync(c->d_tlen, 0, 2 * n * sizeof(uint64_t), st), "hipMemsetAsync(lengths)");
+    if (ok) ok = step(hipMemsetAsync(c->d_out, 0, n * sizeof(madsim_result_t), st), "hipMemsetAsync(results)");
+    if (ok) {
+        no_build = madsim_k_launch_sim(&G.P, G.grid, G.lds_bytes, st, 1) != 0;
+        ok = step(no_build ? hipSuccess : hipGetLastError(), "trace kernel launch");
+    }
+    if (ok && logs && !single) ok = step(hipMemcpyAsync(logs, c->d_tlog, n * log_cap, hipMemcpyDeviceToHost, st), "hipMemcpyAsync(log rows)");
+    if (ok && obs) ok = step(hipMemcpyAsync(obs, c->d_olog, n * obs_cap * sizeof(uint64_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync(observation rows)");
+    if (ok && single) ok = step(hipMemcpyAsync(&one_len, c->d_tlen, sizeof one_len, hipMemcpyDeviceToHost, st), "hipMemcpyAsync(length)");
+    if (ok && log_len && !single) ok = step(hipMemcpyAsync(log_len, c->d_tlen, n * sizeof(uint64_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync(log lengths)");
+    if (ok && obs_len) ok = step(hipMemcpyAsync(obs_len, d_olen, n * sizeof(uint64_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync(observation counts)");
+    if (ok && out) ok = step(hipMemcpyAsync(out, c->d_out, n * sizeof(madsim_result_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync(results)");
+    ok = step(hipStreamSynchronize(st), "hipStreamSynchronize");
+    if (err != hipSuccess) return fail(MADSIM_E_HIP, std::string(at) + ": " + hipGetErrorString(err));
+    if (no_build) return fail(MADSIM_E_LIMITS, "no trace kernel build");
+    if (single) {
+        if (log_len) *log_len = one_len;
+        if (logs && one_len) HIP_TRY(hipMemcpy(logs, c->d_tlog, (size_t)std::min(one_len, log_cap), hipMemcpyDeviceToHost));      // (synchronous)
+    } else if (out && lim && lim->no_trace_hash) {
+        for (uint64_t i = 0; i < n; i++) out[i].trace_hash = 0;
+    }
+    return 0;
+}
+
+int madsim_hip_ctx_trace_seeds(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n,
+                               const madsim_limits_t* lim, uint8_t* logs, uint64_t log_cap, uint64_t* obs, uint64_t obs_cap,
+                               uint64_t* log_len, uint64_t* obs_len, madsim_result_t* out) {
+    return trace_list(c, w, cfg, seeds, n, lim, logs, log_cap, obs, obs_cap, log_len, obs_len, out, false);
+}
+
+// One seed of the list form.  (What it always did: at most min(length, cap) bytes of `log` are written, and a null `log` or a zero cap asks
+// for the length alone.)
+int64_t madsim_hip_ctx_trace_seed(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed,
+                                  const madsim_limits_t* lim, uint8_t* log, uint64_t cap, madsim_result_t* out) {
+    if (!log || !cap) { log = nullptr; cap = 0; }
+    uint64_t len = 0;
+    int rc = trace_list(c, w, cfg, &seed, 1, lim, log, cap, nullptr, 0, &len, nullptr, out, true);
+    return rc ? rc : (int64_t)len;
+}
+
+int64_t madsim_hip_ctx_observe_seed(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed,
+                                    const madsim_limits_t* lim, uint64_t* obs, uint64_t cap, madsim_result_t* out) {
+    uint64_t len = 0;
+    int rc = madsim_hip_ctx_trace_seeds(c, w, cfg, &seed, 1, lim, nullptr, 0, obs, cap, nullptr, &len, out);
+    return rc ? rc : (int64_t)len;
 }
 
 // ---- one process, several GPUs -----------------------------------------------------------------------------------------
@@ -1797,6 +1876,19 @@ int64_t madsim_hip_trace_seed(const madsim_workload_t* w, const madsim_config_t*
                               const madsim_limits_t* lim, uint8_t* log, uint64_t cap, madsim_result_t* out) {
     DefaultPin p;
     return madsim_hip_ctx_trace_seed(p.c, w, cfg, seed, lim, log, cap, out);
+}
+
+int madsim_hip_trace_seeds(const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n, const madsim_limits_t* lim,
+                           uint8_t* logs, uint64_t log_cap, uint64_t* obs, uint64_t obs_cap, uint64_t* log_len, uint64_t* obs_len,
+                           madsim_result_t* out) {
+    DefaultPin p;
+    return madsim_hip_ctx_trace_seeds(p.c, w, cfg, seeds, n, lim, logs, log_cap, obs, obs_cap, log_len, obs_len, out);
+}
+
+int64_t madsim_hip_observe_seed(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed, const madsim_limits_t* lim,
+                                uint64_t* obs, uint64_t cap, madsim_result_t* out) {
+    DefaultPin p;
+    return madsim_hip_ctx_observe_seed(p.c, w, cfg, seed, lim, obs, cap, out);
 }
 
 int madsim_hip_run_campaign(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total, uint64_t batch,

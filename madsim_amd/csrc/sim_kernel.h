@@ -144,7 +144,7 @@ struct KParams {
     unsigned long long* work_ctr; // non-null: a lane that finishes unit i pulls unit total_lanes + atomicAdd(work_ctr, 1) next
     uint4* spill;
     uint32_t total_lanes;
-    // trace mode (single seed)
+    // trace mode: one row of trace_cap bytes and one length word per unit (obs_log below)
     uint8_t* trace_log; uint64_t trace_cap; uint64_t* trace_len;
     uint32_t compact;          // base-op builds: the compact LDS layout (MADSIM_FEAT_COMPACT); gstate then holds the main tasks' records
     uint32_t no_log;           // madsim_limits_t.no_trace_hash: skip rng_log, report trace_hash = 0 (trace launches ignore it)
@@ -161,6 +161,10 @@ struct KParams {
     uint32_t scope_unit;       // (last: the other fields keep their kernel-argument offsets) timeout scopes (MADSIM_FEAT_SCOPE): index of the task unit {END pc | active << 16 | made << 17, -, deadline lo, hi}
     uint32_t tick_unit;        // (after scope_unit, same reason) interval tickers (MADSIM_FEAT_TICK): index of the task unit {TICK_ACTIVE | behaviour << 1 | period s << 16, period ns, next deadline lo, hi};
                                // 0 = none (a select build's workload without MS_OP_INTERVAL)
+    // trace builds (after tick_unit, same reason): the observation log — the values obs_hash folds, in execution order.  Unit i of a trace
+    // launch writes its determinism log to trace_log + i * trace_cap, its observations to obs_log + i * obs_cap (64-bit words) and its
+    // true lengths to trace_len[i] / obs_len[i]; a null obs_log or obs_cap == 0 stores no observation, a null obs_len no length
+    uint64_t* obs_log; uint64_t obs_cap; uint64_t* obs_len;
 };
 
 // The compiled builds, X(TRACE, SPILL, LWS, FEAT, RQ, G) = sim_kernel<Variant<...>>: the trace build; for base-op workloads on

@@ -134,6 +134,15 @@ def lib():
         L.madsim_hip_campaign_resolved.argtypes = [C.POINTER(A.Resolve)]
         L.madsim_hip_ctx_campaign_resolved.argtypes = [ctxp, C.POINTER(A.Resolve)]
         L.madsim_hip_grow_limits.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Limits), C.c_uint32, C.POINTER(A.Limits)]
+        u64p = C.POINTER(C.c_uint64)
+        L.madsim_hip_trace_seeds.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), u64p, C.c_uint64, C.POINTER(A.Limits), C.c_void_p,
+                                             C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.madsim_hip_ctx_trace_seeds.argtypes = [ctxp] + L.madsim_hip_trace_seeds.argtypes
+        L.madsim_hip_observe_seed.restype = C.c_int64
+        L.madsim_hip_observe_seed.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), C.c_uint64, C.POINTER(A.Limits), C.c_void_p, C.c_uint64,
+                                              C.POINTER(A.Result)]
+        L.madsim_hip_ctx_observe_seed.restype = C.c_int64
+        L.madsim_hip_ctx_observe_seed.argtypes = [ctxp] + L.madsim_hip_observe_seed.argtypes
         if L.madsim_hip_version() != A.ABI_VERSION:
             raise MadsimHipError("libmadsim_hip.so ABI version mismatch")
         # build identity: MADSIM_HIP_LIB may name an A/B build of THIS library (tools/build_variant.sh), nothing else — an
@@ -253,6 +262,138 @@ def _campaign_flags(stop_at_failure, list_runner=False, stop_at_cap=False, stop_
         | (A.CAMPAIGN_STOP_AT_CAP if stop_at_cap else 0) | (A.CAMPAIGN_STOP_AT_GROUPS if stop_at_groups else 0) | _resolve_flags(resolve)
 
 
+def fold_observations(values):
+    """The obs_hash of a run that traced `values`, in that order: 64-bit FNV-1a over whole values (offset basis for the empty list).  Pure
+    Python: what turns an observation list back into the key a grouping campaign reports."""
+    h = A.FNV_OFFSET
+    for v in values:
+        h = ((h ^ (int(v) & A.U64_MAX)) * A.FNV_PRIME) & A.U64_MAX
+    return h
+
+
+class SeedTrace:
+    """What one seed traced (runtime.trace_seeds): `seed`; `result`, its A.Result; `observations`, the first obs_cap values it handed to
+    trace / trace_time / a traced tick, in execution order, as Python ints, and `n_observations`, how many there were; `log`, the first
+    log_cap bytes of its determinism log, and `log_len`, that log's length.  Under a runner verdict the lists are what was recorded until
+    the verdict: not meaningful."""
+    __slots__ = ("seed", "result", "observations", "n_observations", "log", "log_len")
+
+    def __init__(self, seed, result, observations, n_observations, log, log_len):
+        self.seed, self.result, self.observations, self.n_observations = seed, result, observations, n_observations
+        self.log, self.log_len = log, log_len
+
+    def __repr__(self):
+        return (f"SeedTrace(seed={self.seed}, verdict={A.VERDICT_NAMES[self.result.verdict] if self.result.verdict < 8 else self.result.verdict}, "
+                f"observations={self.observations}, n_observations={self.n_observations}, log_len={self.log_len})")
+
+
+def _rerunnable(res, lim):
+    """Which of `res` (ndarray[RESULT_DTYPE]) a resolve round re-runs under `lim`: MADSIM_OVERFLOW, or MADSIM_STEP_LIMIT while the step cap
+    is below its ceiling (include/madsim_hip.h, "Self-resolving campaigns")."""
+    cap, ceiling = lim.max_steps or 1 << 24, lim.max_steps_ceiling or 1 << 28
+    return (res["verdict"] == A.OVERFLOW) | ((res["verdict"] == A.STEP_LIMIT) & (cap < ceiling))
+
+
+def _trace_seeds(call, workload, seeds, config, limits, obs_cap, log_cap, resolve):
+    """Run `call(cfg, seeds*, n, lim, logs, log_cap, obs, obs_cap, log_len, obs_len, out)` — a madsim_hip_*trace_seeds entry point with its context
+    and workload bound — over `seeds`, then over the seeds a round leaves re-runnable, each round one further call."""
+    seeds = [int(s) for s in seeds]
+    if any(not 0 <= s <= A.U64_MAX for s in seeds) or obs_cap < 0 or log_cap < 0:
+        raise MadsimHipError("trace_seeds: seeds must fit u64, caps be >= 0")
+    cfg, lim0 = config or A.Config.default(), limits or A.Limits()
+    n = len(seeds)
+    res = np.zeros(n, dtype=A.RESULT_DTYPE)
+    obs, logs = np.zeros((n, obs_cap), dtype=np.uint64), np.zeros((n, log_cap), dtype=np.uint8)
+    obs_len, log_len = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
+    rounds = 0 if resolve is None or resolve is False else A.RESOLVE_DEFAULT_ROUNDS if resolve is True else int(resolve)
+    if not 0 <= rounds <= A.RESOLVE_MAX_ROUNDS:
+        raise MadsimHipError(f"resolve: None, True or a number of rounds 1..{A.RESOLVE_MAX_ROUNDS}, got {resolve!r}")
+    idx = np.arange(n)
+    for r in range(rounds + 1):
+        if not len(idx):
+            break
+        lim = lim0 if r == 0 else grown_limits(workload, lim0, r)
+        m = len(idx)
+        s = np.array([seeds[i] for i in idx], dtype=np.uint64)
+        o, lg = np.zeros((m, obs_cap), dtype=np.uint64), np.zeros((m, log_cap), dtype=np.uint8)
+        ol, ll, out = np.zeros(m, dtype=np.uint64), np.zeros(m, dtype=np.uint64), np.zeros(m, dtype=A.RESULT_DTYPE)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)                                 # noqa: E731
+        _check(call(C.byref(cfg), s.ctypes.data_as(C.POINTER(C.c_uint64)), m, C.byref(lim), ptr(lg) if log_cap else None, log_cap,
+                    ptr(o) if obs_cap else None, obs_cap, ptr(ll), ptr(ol), ptr(out)))
+        res[idx], obs[idx], logs[idx], obs_len[idx], log_len[idx] = out, o, lg, ol, ll
+        idx = idx[_rerunnable(out, lim)]
+    traces = []
+    for i in range(n):
+        traces.append(SeedTrace(seeds[i], A.Result(*[int(x) for x in res[i]]), [int(v) for v in obs[i, :min(int(obs_len[i]), obs_cap)]],
+                                int(obs_len[i]), logs[i, :min(int(log_len[i]), log_cap)].tobytes(), int(log_len[i])))
+    return traces
+
+
+def trace_seeds(workload, seeds, config=None, limits=None, obs_cap=256, log_cap=0, resolve=True):
+    """madsim_hip_trace_seeds: replay `seeds` (any order, duplicates allowed) on the trace build, the whole list in one launch; returns one
+    SeedTrace per seed, in the order given.  resolve=True | rounds: the seeds a call leaves with a re-runnable runner verdict are replayed as
+    one further call under grown_limits(workload, limits, r), r = 1, 2, ... — the rounds of a resolving campaign; resolve=None / False: the
+    one call under `limits`, runner verdicts as they come."""
+    if _inited_device is None:
+        init(0)
+    return _trace_seeds(lambda *a: lib().madsim_hip_trace_seeds(workload.ref(), *a), workload, seeds, config, limits, obs_cap, log_cap, resolve)
+
+
+def observe_seed(workload, seed, config=None, limits=None, cap=1 << 16, resolve=True):
+    """What one seed traced, as oracle.observe_seed gives it: (list of values, A.Result)."""
+    t = trace_seeds(workload, [seed], config, limits, obs_cap=cap, log_cap=0, resolve=resolve)[0]
+    return t.observations, t.result
+
+
+def _observe_listed(tracer, workload, records, config, limits, cap, resolve, what):
+    """The observation lists of a campaign's listed seeds: one trace_seeds call, and the check that the trace build's 48 bytes are the
+    bytes the campaign listed (`records`: (seed, result record) pairs).  A listed runner verdict says nothing a replay must repeat."""
+    if not len(records):
+        return []
+    traces = tracer(workload, [int(s) for s, _ in records], config, limits, cap, 0, resolve)
+    for t, (seed, rec) in zip(traces, records):
+        want = tuple(int(x) for x in rec)
+        if not A.is_runner_verdict(want[0]) and t.result.astuple() != want:
+            raise MadsimHipError(f"{what}: seed {seed} replayed on the trace build gives {t.result.astuple()}, the campaign listed {want}")
+    return [t.observations for t in traces]
+
+
+def _default_tracer(workload, seeds, config, limits, obs_cap, log_cap, resolve):
+    return trace_seeds(workload, seeds, config, limits, obs_cap, log_cap, resolve)
+
+
+def _result_fields(rec):
+    return [rec[name] for name, _ in A.RESULT_DTYPE]
+
+
+def _observe_failures(tracer, workload, failures, cfg, lim, cap, resolve):
+    return _observe_listed(tracer, workload, [(f["seed"], _result_fields(f)) for f in failures], cfg, lim, cap, resolve, "run_campaign(observe)")
+
+
+def _observe_groups(tracer, workload, out, cfg, lim, cap, resolve):
+    """Fill CampaignGroups.observations (the last element of a grouping campaign's return value) from each group's smallest seed.  A group
+    carries its key and verdict, not 48 bytes: the replay must give that verdict, and with key="obs" its list must fold to that key."""
+    cg = out[-1]
+    traces = tracer(workload, [int(g["first_seed"]) for g in cg.groups], cfg, lim, cap, 0, resolve) if len(cg.groups) else []
+    for t, g in zip(traces, cg.groups):
+        if t.result.verdict != int(g["verdict"]) or getattr(t.result, A.GROUP_KEY_FIELDS[cg.key_field]) != int(g["key"]):
+            raise MadsimHipError(f"run_campaign_groups(observe): seed {t.seed} replayed on the trace build gives {t.result.astuple()}, "
+                                 f"the campaign grouped it under verdict {int(g['verdict'])}, {cg.key} key {int(g['key']):#x}")
+    cg.observations = [t.observations for t in traces]
+    cg.n_observations = [t.n_observations for t in traces]
+    return out
+
+
+def _observe_diff(tracer, workload, other, out, cfg_a, lim_a, cfg_b, lim_b, cap, resolve):
+    """Fill CampaignDiff.observations_a / _b (the last element of a differential campaign's return value): one trace_seeds call per side."""
+    d = out[-1]
+    d.observations_a = _observe_listed(tracer, workload, [(x["seed"], _result_fields(x["a"])) for x in d.records], cfg_a, lim_a, cap, resolve,
+                                       "run_campaign_diff(observe), side A")
+    d.observations_b = _observe_listed(tracer, other, [(x["seed"], _result_fields(x["b"])) for x in d.records], cfg_b, lim_b, cap, resolve,
+                                       "run_campaign_diff(observe), side B")
+    return out
+
+
 def _collecting(call, collect):
     """Run `call(col)` — one of the madsim_hip_*run_campaign_collect* entry points with everything but the madsim_collect_t bound — with
     room for `collect` records; returns (failures ndarray[FAILURE_DTYPE] of n_listed entries, by_verdict uint64[8])."""
@@ -265,7 +406,7 @@ def _collecting(call, collect):
 
 
 def run_campaign(workload, seed0, total, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None,
-                 collect=None, list_runner=False, stop_at_cap=False, resolve=None):
+                 collect=None, list_runner=False, stop_at_cap=False, resolve=None, observe=0):
     """madsim_hip_run_campaign: `total` seeds as batches kept in flight on the library's own streams; returns the Campaign
     report (first failing seed, counts) — no per-seed results.  stop_at_failure: stop launching once a completed batch holds a
     seed with a genuine verdict.
@@ -278,7 +419,15 @@ def run_campaign(workload, seed0, total, batch=0, in_flight=0, stop_at_failure=F
     resolve=True | rounds (MADSIM_CAMPAIGN_RESOLVE; every run_campaign* wrapper takes it): seeds that come back with a runner verdict
     (a device capacity, the step cap) are run again on the device under grown limits — grown_limits(workload, limits, r) in round r — before
     their batch is reported, so the report, the list, the statistics, the groups and the diff are over settled results; n_runner is what
-    no round settled.  campaign_resolved() tells what the rounds did."""
+    no round settled.  campaign_resolved() tells what the rounds did.
+
+    observe=cap (0, the default: nothing new) CHANGES THE RETURN SHAPE: with collect=K the call returns FOUR values, (campaign, failures,
+    by_verdict, observations) — observations[i] = what failures[i]["seed"] traced, a list of at most `cap` values (the records are a numpy
+    array and cannot carry lists) — from ONE trace_seeds call after the campaign under the campaign's limits (and its resolve rounds).  The
+    replay's 48 bytes must be the bytes the campaign listed: MadsimHipError if the trace build and the production build ever disagree.
+    observe without collect is MadsimHipError: there is no list to explain."""
+    if observe and collect is None:
+        raise MadsimHipError("run_campaign: observe= explains the listed seeds: it needs collect=K")
     if _inited_device is None:
         init(0)
     cfg = config or A.Config.default()
@@ -291,6 +440,8 @@ def run_campaign(workload, seed0, total, batch=0, in_flight=0, stop_at_failure=F
     flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap, resolve=resolve)
     failures, by_verdict = _collecting(lambda col: lib().madsim_hip_run_campaign_collect(
         workload.ref(), C.byref(cfg), seed0, total, batch, in_flight, flags, C.byref(lim), C.byref(rep), col), collect)
+    if observe:
+        return rep, failures, by_verdict, _observe_failures(_default_tracer, workload, failures, cfg, lim, observe, resolve)
     return rep, failures, by_verdict
 
 
@@ -377,6 +528,8 @@ class CampaignGroups:
         self.key = A.GROUP_KEY_NAMES[self.key_field]
         self.groups = groups[:grp.n_groups].copy()
         self.n_grouped, self.n_ungrouped = int(grp.n_grouped), int(grp.n_ungrouped)
+        self.observations = None      # observe=cap: observations[i] = what groups[i]["first_seed"] traced (at most cap values), n_observations[i] how many
+        self.n_observations = None
 
     def __len__(self):
         return len(self.groups)
@@ -409,19 +562,24 @@ def _campaign_groups(call, include, key, max_groups, collect, stats, rep):
 
 def run_campaign_groups(workload, seed0, total, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None,
                         include=(A.PANIC, A.DEADLOCK, A.TIME_LIMIT), key="obs", max_groups=32, stop_at_groups=False, collect=None, stats=None,
-                        list_runner=False, stop_at_cap=False, resolve=None):
+                        list_runner=False, stop_at_cap=False, resolve=None, observe=0):
     """madsim_hip_run_campaign_groups: run_campaign, plus the failure modes of the range — the seeds whose verdict is in `include` grouped by
     (verdict, key), `key` one of "obs" (obs_hash: what the workload traced), "trace", "msgs", "clock", "rng", "steps"; the first `max_groups`
     groups in order of first appearance, each with its exact count and its smallest seed.  stop_at_groups: stop launching once max_groups
     different modes have been read.  Returns (campaign, CampaignGroups); with collect=K (as run_campaign) and / or stats=(include, top_k) (as
-    run_campaign_stats) their outputs come in between: (campaign[, failures, by_verdict][, CampaignStats], CampaignGroups)."""
+    run_campaign_stats) their outputs come in between: (campaign[, failures, by_verdict][, CampaignStats], CampaignGroups).
+
+    observe=cap (0 = nothing new): CampaignGroups.observations[i] is what the smallest seed of groups[i] traced, at most `cap` values — the
+    failure mode spelled out, not only its key.  One trace_seeds call after the campaign, under the campaign's limits and resolve rounds;
+    MadsimHipError if a replayed seed does not carry the verdict and key it was grouped under."""
     if _inited_device is None:
         init(0)
     cfg, lim, rep = config or A.Config.default(), limits or A.Limits(), A.Campaign()
     flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap, stop_at_groups, resolve)
-    return _campaign_groups(lambda col, st, grp: lib().madsim_hip_run_campaign_groups(
+    out = _campaign_groups(lambda col, st, grp: lib().madsim_hip_run_campaign_groups(
         workload.ref(), C.byref(cfg), seed0, total, batch, in_flight, flags, C.byref(lim), C.byref(rep), col, st, grp),
         include, key, max_groups, collect, stats, rep)
+    return _observe_groups(_default_tracer, workload, out, cfg, lim, observe, resolve) if observe else out
 
 
 class CampaignDiff:
@@ -436,6 +594,7 @@ class CampaignDiff:
         self.n_compared, self.n_incomparable, self.n_differ = int(d.n_compared), int(d.n_incomparable), int(d.n_differ)
         self.n_by_field = np.array(d.n_by_field[:], dtype=np.uint64)
         self.transitions = np.array([row[:] for row in d.transitions], dtype=np.uint64)
+        self.observations_a = self.observations_b = None      # observe=cap: what records[i]["seed"] traced on each side (at most cap values)
 
     def __len__(self):
         return len(self.records)
@@ -445,7 +604,8 @@ class CampaignDiff:
         return int(self.transitions[A.PASS, 1:].sum())
 
 
-def _campaign_diff(call, workload, other, config, other_config, limits, other_limits, fields, max_listed, stop_at_diffs, resolve=None):
+def _campaign_diff(call, workload, other, config, other_config, limits, other_limits, fields, max_listed, stop_at_diffs, resolve=None, observe=0,
+                   tracer=None):
     """Run `call(wA, cfgA, limA, wB, cfgB, limB, flags, repA, repB, diff)` — one of the madsim_hip_*run_campaign_diff* entry points with its
     contexts and its range bound.  A None on the B side means "the same as A's"."""
     if not isinstance(fields, int) or fields <= 0 or fields & ~A.DIFF_ALL or max_listed < 0 or (stop_at_diffs and not max_listed):
@@ -459,7 +619,8 @@ def _campaign_diff(call, workload, other, config, other_config, limits, other_li
     rep_a, rep_b = A.Campaign(), A.Campaign()
     _check(call(workload.ref(), C.byref(cfg_a), C.byref(lim_a), w_b.ref(), C.byref(cfg_b), C.byref(lim_b),
                 (A.CAMPAIGN_STOP_AT_DIFFS if stop_at_diffs else 0) | _resolve_flags(resolve), C.byref(rep_a), C.byref(rep_b), C.byref(d)))
-    return rep_a, rep_b, CampaignDiff(d, arr)
+    out = rep_a, rep_b, CampaignDiff(d, arr)
+    return _observe_diff(tracer or _default_tracer, workload, w_b, out, cfg_a, lim_a, cfg_b, lim_b, observe, resolve) if observe else out
 
 
 def run_campaign_diff(workload, seed0, total, other=None, config=None, other_config=None, limits=None, other_limits=None, fields=A.DIFF_ALL,
@@ -468,20 +629,23 @@ def run_campaign_diff(workload, seed0, total, other=None, config=None, other_con
     a None on the B side means "the same as A's" —, compared on the device on the result fields named in `fields` (A.DIFF_* bits).  Returns
     (campaign A, campaign B, CampaignDiff): each side's plain campaign report, the max_listed smallest differing seeds with both results, the
     counts, and the verdict-transition matrix.  stop_at_diffs: stop launching once max_listed differing seeds have been read.
-    (This one wrapper's parameter list is pinned; its resolving form is run_campaign_diff_resolved.)"""
+    (This one wrapper's parameter list is pinned; its resolving and observing form is run_campaign_diff_resolved.)"""
     return run_campaign_diff_resolved(workload, seed0, total, None, other, config, other_config, limits, other_limits, fields, max_listed,
                                       stop_at_diffs, batch, in_flight)
 
 
 def run_campaign_diff_resolved(workload, seed0, total, resolve=True, other=None, config=None, other_config=None, limits=None, other_limits=None,
-                               fields=A.DIFF_ALL, max_listed=0, stop_at_diffs=False, batch=0, in_flight=0):
-    """run_campaign_diff with MADSIM_CAMPAIGN_RESOLVE (`resolve`: True or a number of rounds, as run_campaign's): each side's runner verdicts are
-    re-run under that side's own grown limits before the two arrays are compared, so only seeds that no round settles stay incomparable."""
+                               fields=A.DIFF_ALL, max_listed=0, stop_at_diffs=False, batch=0, in_flight=0, observe=0):
+    """run_campaign_diff with MADSIM_CAMPAIGN_RESOLVE (`resolve`: True or a number of rounds, as run_campaign's; None: plain): each side's runner
+    verdicts are re-run under that side's own grown limits before the two arrays are compared, so only seeds that no round settles stay
+    incomparable.  observe=cap (0 = nothing new): CampaignDiff.observations_a[i] / observations_b[i] are what records[i]["seed"] traced on
+    each side, at most `cap` values — one trace_seeds call per side after the campaign, under that side's limits, with run_campaign's check
+    of the replayed 48 bytes against the listed ones."""
     if _inited_device is None:
         init(0)
     return _campaign_diff(lambda wa, ca, la, wb, cb, lb, flags, ra, rb, d: lib().madsim_hip_run_campaign_diff(
         wa, ca, la, wb, cb, lb, seed0, total, batch, in_flight, flags, ra, rb, d),
-        workload, other, config, other_config, limits, other_limits, fields, max_listed, stop_at_diffs, resolve)
+        workload, other, config, other_config, limits, other_limits, fields, max_listed, stop_at_diffs, resolve, observe)
 
 
 def run_batch_device(workload, seed0, count, d_out_ptr, stream_ptr=0, config=None, limits=None, want_summary=True):
@@ -547,9 +711,22 @@ class Context:
                                                   out.ctypes.data_as(C.c_void_p), C.byref(summ)))
         return out, summ
 
+    def trace_seeds(self, workload, seeds, config=None, limits=None, obs_cap=256, log_cap=0, resolve=True):
+        """runtime.trace_seeds on this context (madsim_hip_ctx_trace_seeds)."""
+        return _trace_seeds(lambda *a: lib().madsim_hip_ctx_trace_seeds(self._h, workload.ref(), *a), workload, seeds, config, limits, obs_cap,
+                            log_cap, resolve)
+
+    def observe_seed(self, workload, seed, config=None, limits=None, cap=1 << 16, resolve=True):
+        """runtime.observe_seed on this context."""
+        t = self.trace_seeds(workload, [seed], config, limits, obs_cap=cap, log_cap=0, resolve=resolve)[0]
+        return t.observations, t.result
+
     def run_campaign(self, workload, seed0, total, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None,
-                     collect=None, list_runner=False, stop_at_cap=False, resolve=None):
-        """runtime.run_campaign on this context (madsim_hip_ctx_run_campaign / madsim_hip_ctx_run_campaign_collect)."""
+                     collect=None, list_runner=False, stop_at_cap=False, resolve=None, observe=0):
+        """runtime.run_campaign on this context (madsim_hip_ctx_run_campaign / madsim_hip_ctx_run_campaign_collect); observe=cap needs
+        collect=K and makes the return value (campaign, failures, by_verdict, observations), as there."""
+        if observe and collect is None:
+            raise MadsimHipError("run_campaign: observe= explains the listed seeds: it needs collect=K")
         cfg, lim = config or A.Config.default(), limits or A.Limits()
         rep = A.Campaign()
         if collect is None:
@@ -559,6 +736,8 @@ class Context:
         flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap, resolve=resolve)
         failures, by_verdict = _collecting(lambda col: lib().madsim_hip_ctx_run_campaign_collect(
             self._h, workload.ref(), C.byref(cfg), seed0, total, batch, in_flight, flags, C.byref(lim), C.byref(rep), col), collect)
+        if observe:
+            return rep, failures, by_verdict, _observe_failures(self.trace_seeds, workload, failures, cfg, lim, observe, resolve)
         return rep, failures, by_verdict
 
     def run_campaign_stats(self, workload, seed0, total, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None,
@@ -573,21 +752,22 @@ class Context:
 
     def run_campaign_groups(self, workload, seed0, total, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None,
                             include=(A.PANIC, A.DEADLOCK, A.TIME_LIMIT), key="obs", max_groups=32, stop_at_groups=False, collect=None, stats=None,
-                            list_runner=False, stop_at_cap=False, resolve=None):
+                            list_runner=False, stop_at_cap=False, resolve=None, observe=0):
         """runtime.run_campaign_groups on this context (madsim_hip_ctx_run_campaign_groups)."""
         cfg, lim, rep = config or A.Config.default(), limits or A.Limits(), A.Campaign()
         flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap, stop_at_groups, resolve)
-        return _campaign_groups(lambda col, st, grp: lib().madsim_hip_ctx_run_campaign_groups(
+        out = _campaign_groups(lambda col, st, grp: lib().madsim_hip_ctx_run_campaign_groups(
             self._h, workload.ref(), C.byref(cfg), seed0, total, batch, in_flight, flags, C.byref(lim), C.byref(rep), col, st, grp),
             include, key, max_groups, collect, stats, rep)
+        return _observe_groups(self.trace_seeds, workload, out, cfg, lim, observe, resolve) if observe else out
 
 
     def run_campaign_diff(self, workload, seed0, total, other=None, config=None, other_config=None, limits=None, other_limits=None,
-                          fields=A.DIFF_ALL, max_listed=0, stop_at_diffs=False, batch=0, in_flight=0, resolve=None):
-        """runtime.run_campaign_diff on this context (madsim_hip_ctx_run_campaign_diff)."""
+                          fields=A.DIFF_ALL, max_listed=0, stop_at_diffs=False, batch=0, in_flight=0, resolve=None, observe=0):
+        """runtime.run_campaign_diff on this context (madsim_hip_ctx_run_campaign_diff); observe: as run_campaign_diff_resolved's."""
         return _campaign_diff(lambda wa, ca, la, wb, cb, lb, flags, ra, rb, d: lib().madsim_hip_ctx_run_campaign_diff(
             self._h, wa, ca, la, wb, cb, lb, seed0, total, batch, in_flight, flags, ra, rb, d),
-            workload, other, config, other_config, limits, other_limits, fields, max_listed, stop_at_diffs, resolve)
+            workload, other, config, other_config, limits, other_limits, fields, max_listed, stop_at_diffs, resolve, observe, self.trace_seeds)
 
 
 def run_batch_multi(contexts, workload, seed0, count, config=None, limits=None, max_rounds=5):

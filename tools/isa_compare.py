@@ -2,7 +2,10 @@
 """Compare the gfx950 code of two sim_kernel.o builds kernel by kernel (no GPU needed).
 
 Each object's device code is unbundled and disassembled with llvm-objdump; per function symbol, the instruction text is kept with
-addresses, encodings and branch-target labels stripped (so code that moved as a whole still compares equal).  Prints one line per
+addresses, encodings, branch-target labels and pc-relative displacements (the literal added to an s_getpc_b64 result: a call of an
+out-of-line function, a long branch) stripped, so code that moved as a whole still compares equal — the callee is a symbol of its own
+and is compared like every other.  (What that leaves unseen: a call retargeted to ANOTHER callee, everything else equal, reads `same`.  The
+displacement is not resolved to its target's name here.)  Prints one line per
 symbol: `same`, `DIFFERENT` (with the count of differing lines) or `only in old / new`.  Exit status 1 if a symbol of the old object
 is missing or different in the new one.
 
@@ -24,7 +27,7 @@ def functions(obj, tmp):
     t = next(x for x in targets if "gfx950" in x)
     subprocess.check_call([f"{B}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={fat}", f"--targets={t}", f"--output={co}"])
     dis = subprocess.check_output([f"{B}/llvm-objdump", "-d", "--no-show-raw-insn", "--no-leading-addr", co], text=True)
-    out, cur = {}, None
+    out, cur, pc = {}, None, None                            # pc: the register that holds the low half of the last s_getpc_b64
     for ln in dis.splitlines():
         m = re.match(r"^(?:[0-9a-f]+ )?<(.+)>:$", ln)
         if m:
@@ -35,6 +38,10 @@ def functions(obj, tmp):
         s = re.sub(r"<[^>]*>", "<L>", s)                     # branch targets: symbolic
         s = re.sub(r"\b0x[0-9a-f]+\b(?=\s*<L>)", "", s)
         if s:
+            m = re.match(r"s_getpc_b64 s\[(\d+):\d+\]$", s)
+            if pc is not None and re.match(r"s_add_u32 s%s, s%s, 0x[0-9a-f]+$" % (pc, pc), s):
+                s = "s_add_u32 s%s, s%s, <pcrel>" % (pc, pc)
+            pc = m.group(1) if m else None
             out[cur].append(s)
     for f in out.values():                                   # alignment padding behind a function (s_nop, the `...` of a zero run)
         while f and f[-1] in ("s_nop 0", "..."):
