@@ -469,6 +469,12 @@ extern "C" {
     pub fn madsim_hip_campaign_resolved(out: *mut madsim_resolve_t) -> c_int;
     pub fn madsim_hip_ctx_campaign_resolved(ctx: *mut madsim_hip_ctx_t, out: *mut madsim_resolve_t) -> c_int;
     pub fn madsim_hip_grow_limits(w: *const madsim_workload_t, lim: *const madsim_limits_t, rounds: u32, out: *mut madsim_limits_t) -> c_int;
+    pub fn madsim_hip_ctx_run_seeds_campaign(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seeds: *const u64, n: u64, batch: u64, in_flight: u32, flags: u32, lim: *const madsim_limits_t, out: *mut madsim_campaign_t, col: *mut madsim_collect_t, st: *mut madsim_stats_t, grp: *mut madsim_groups_t) -> c_int;
+    pub fn madsim_hip_run_seeds_campaign(w: *const madsim_workload_t, cfg: *const madsim_config_t, seeds: *const u64, n: u64, batch: u64, in_flight: u32, flags: u32, lim: *const madsim_limits_t, out: *mut madsim_campaign_t, col: *mut madsim_collect_t, st: *mut madsim_stats_t, grp: *mut madsim_groups_t) -> c_int;
+    pub fn madsim_hip_run_seeds_campaign_multi(ctxs: *const *mut madsim_hip_ctx_t, n_ctx: c_int, w: *const madsim_workload_t, cfg: *const madsim_config_t, seeds: *const u64, n: u64, batch: u64, in_flight: u32, flags: u32, lim: *const madsim_limits_t, out: *mut madsim_campaign_t, col: *mut madsim_collect_t, st: *mut madsim_stats_t, grp: *mut madsim_groups_t) -> c_int;
+    pub fn madsim_hip_ctx_run_seeds_campaign_diff(ctx: *mut madsim_hip_ctx_t, wA: *const madsim_workload_t, cfgA: *const madsim_config_t, limA: *const madsim_limits_t, wB: *const madsim_workload_t, cfgB: *const madsim_config_t, limB: *const madsim_limits_t, seeds: *const u64, n: u64, batch: u64, in_flight: u32, flags: u32, outA: *mut madsim_campaign_t, outB: *mut madsim_campaign_t, diff: *mut madsim_diff_t) -> c_int;
+    pub fn madsim_hip_run_seeds_campaign_diff(wA: *const madsim_workload_t, cfgA: *const madsim_config_t, limA: *const madsim_limits_t, wB: *const madsim_workload_t, cfgB: *const madsim_config_t, limB: *const madsim_limits_t, seeds: *const u64, n: u64, batch: u64, in_flight: u32, flags: u32, outA: *mut madsim_campaign_t, outB: *mut madsim_campaign_t, diff: *mut madsim_diff_t) -> c_int;
+    pub fn madsim_hip_run_seeds_campaign_diff_multi(ctxs: *const *mut madsim_hip_ctx_t, n_ctx: c_int, wA: *const madsim_workload_t, cfgA: *const madsim_config_t, limA: *const madsim_limits_t, wB: *const madsim_workload_t, cfgB: *const madsim_config_t, limB: *const madsim_limits_t, seeds: *const u64, n: u64, batch: u64, in_flight: u32, flags: u32, outA: *mut madsim_campaign_t, outB: *mut madsim_campaign_t, diff: *mut madsim_diff_t) -> c_int;
     pub fn madsim_hip_geometry(w: *const madsim_workload_t, lim: *const madsim_limits_t, g: *mut madsim_geometry_t) -> c_int;
     pub fn madsim_hip_debug_counters(out16: *mut u64) -> c_int;
     pub fn madsim_workload_pingpong(n_nodes: u32, rounds: u32, nodes: *mut madsim_node_t, progs: *mut madsim_prog_t, socks: *mut madsim_sock_t, insns: *mut madsim_insn_t, cap_insns: u32, w: *mut madsim_workload_t) -> c_int;

@@ -187,6 +187,15 @@ pub struct Diff {
     pub b: sys::madsim_campaign_t,
 }
 
+/// What `Builder::campaign_over_seeds` found over the listed seeds: the campaign report, and each part that was asked for.
+#[derive(Clone, Debug)]
+pub struct ListCampaign {
+    pub campaign: sys::madsim_campaign_t,
+    pub failures: Option<Failures>,
+    pub stats: Option<Stats>,
+    pub groups: Option<Groups>,
+}
+
 /// What one seed traced (`Builder::trace_seeds`): its result; `observations`, the first `obs_cap` values its test body handed to
 /// `trace` / `trace_time` / a traced tick, in execution order — what `obs_hash` folds — and `n_observations`, how many there were;
 /// `log`, the first `log_cap` bytes of its determinism log, and `log_len`, that log's length.  Under a runner verdict the lists are
@@ -486,6 +495,96 @@ impl Builder {
         report.cap = max_listed as u64;
         let rc = unsafe {
             sys::madsim_hip_ctx_run_campaign_diff(ctx, &wa, &ca, &la, &wb, &cb, &lb, self.seed, self.count, 0, 0, self.resolve_flags, &mut a, &mut b, &mut report)
+        };
+        if rc != 0 {
+            return Err(last_error(rc));
+        }
+        records.truncate(report.n_listed as usize);
+        report.records = std::ptr::null();
+        Ok(Diff { records, report, a, b })
+    }
+
+    /// The list campaign: `search_failures`, `campaign_stats` and `failure_groups` in one call over the seeds you NAME instead of
+    /// `self.seed .. self.seed + self.count` (`madsim_hip_run_seeds_campaign`) — the failing seeds an earlier campaign listed, a
+    /// regression corpus, the members of one failure mode.  `seeds` must ascend strictly (sorted, no duplicates: `sort_unstable` +
+    /// `dedup`), so that "smallest seed" and "first position" stay one thing; the library refuses any other list, it never sorts
+    /// silently.  Position `i` of the list takes the role of `seed + i`: `campaign.seeds_run` counts positions.
+    /// `max_failures`: `Some(k)` = list the `k` smallest failing seeds (and count the verdicts); `stats`: `Some((include, top_k))`;
+    /// `groups`: `Some((include, key_field, max_groups))`.  A part that is not asked for comes back `None`.
+    /// (Like the rest of this crate: written against the header, never compiled — there is no Rust toolchain where it is developed.)
+    pub fn campaign_over_seeds(&self, workload: &Workload, seeds: &[u64], max_failures: Option<usize>, stats: Option<(u32, u32)>,
+                               groups: Option<(u32, u32, usize)>) -> Result<ListCampaign, RunError> {
+        let w = workload.raw();
+        let cfg = self.config.raw();
+        let lim = self.raw_limits(true);
+        let ctx = contexts()?.0[0];
+        let mut campaign: sys::madsim_campaign_t = unsafe { std::mem::zeroed() };
+        let cap = max_failures.unwrap_or(0);
+        let mut failures: Vec<sys::madsim_failure_t> = vec![unsafe { std::mem::zeroed() }; cap];
+        let mut col = sys::madsim_collect_t {
+            failures: if cap > 0 { failures.as_mut_ptr() as *const _ } else { std::ptr::null() },   // (the library writes through it)
+            cap: cap as u64,
+            n_listed: 0,
+            n_by_verdict: [0; 8],
+        };
+        let (include, top_k) = stats.unwrap_or((0, 0));
+        let k = top_k as usize;
+        let mut top: Vec<sys::madsim_extreme_t> = vec![unsafe { std::mem::zeroed() }; 4 * k];
+        let mut st: sys::madsim_stats_t = unsafe { std::mem::zeroed() };
+        st.include = include;
+        st.top_k = top_k;
+        st.top = if k > 0 { top.as_mut_ptr() as *const _ } else { std::ptr::null() };
+        let (g_include, key_field, max_groups) = groups.unwrap_or((0, 0, 0));
+        let mut entries: Vec<sys::madsim_group_t> = vec![unsafe { std::mem::zeroed() }; max_groups];
+        let mut grp = sys::madsim_groups_t {
+            include: g_include,
+            key_field,
+            groups: if max_groups > 0 { entries.as_mut_ptr() as *const _ } else { std::ptr::null() },
+            cap: max_groups as u64,
+            n_groups: 0,
+            n_grouped: 0,
+            n_ungrouped: 0,
+        };
+        let rc = unsafe {
+            sys::madsim_hip_ctx_run_seeds_campaign(ctx, &w, &cfg, seeds.as_ptr(), seeds.len() as u64, 0, 0, self.resolve_flags, &lim, &mut campaign,
+                                                   if max_failures.is_some() { &mut col } else { std::ptr::null_mut() },
+                                                   if stats.is_some() { &mut st } else { std::ptr::null_mut() },
+                                                   if groups.is_some() { &mut grp } else { std::ptr::null_mut() })
+        };
+        if rc != 0 {
+            return Err(last_error(rc));
+        }
+        failures.truncate(col.n_listed as usize);
+        st.top = std::ptr::null();
+        let n_top = st.n_top as usize;
+        let rows: [Vec<sys::madsim_extreme_t>; 4] = std::array::from_fn(|m| top[m * k..m * k + n_top].to_vec());
+        entries.truncate(grp.n_groups as usize);
+        Ok(ListCampaign {
+            failures: max_failures.map(|_| Failures { failures, by_verdict: col.n_by_verdict, campaign }),
+            stats: stats.map(|_| Stats { stats: st, top: rows, campaign }),
+            groups: groups.map(|_| Groups { groups: entries, n_grouped: grp.n_grouped, n_ungrouped: grp.n_ungrouped, campaign }),
+            campaign,
+        })
+    }
+
+    /// `diff_campaign` over the seeds you name (`madsim_hip_run_seeds_campaign_diff`): "did the fix fix all of them?" over exactly the
+    /// seeds that failed.  `seeds` as `campaign_over_seeds`': strictly ascending.
+    pub fn diff_campaign_seeds(&self, workload: &Workload, other: &Builder, other_workload: &Workload, seeds: &[u64], fields: u32,
+                               max_listed: usize) -> Result<Diff, RunError> {
+        let (wa, wb) = (workload.raw(), other_workload.raw());
+        let (ca, cb) = (self.config.raw(), other.config.raw());
+        let (la, lb) = (self.raw_limits(true), other.raw_limits(true));
+        let ctx = contexts()?.0[0];
+        let mut records: Vec<sys::madsim_diff_record_t> = vec![unsafe { std::mem::zeroed() }; max_listed];
+        let mut a: sys::madsim_campaign_t = unsafe { std::mem::zeroed() };
+        let mut b: sys::madsim_campaign_t = unsafe { std::mem::zeroed() };
+        let mut report: sys::madsim_diff_t = unsafe { std::mem::zeroed() };
+        report.fields = fields;
+        report.records = if max_listed > 0 { records.as_mut_ptr() as *const _ } else { std::ptr::null() };   // (the library writes through it)
+        report.cap = max_listed as u64;
+        let rc = unsafe {
+            sys::madsim_hip_ctx_run_seeds_campaign_diff(ctx, &wa, &ca, &la, &wb, &cb, &lb, seeds.as_ptr(), seeds.len() as u64, 0, 0, self.resolve_flags,
+                                                        &mut a, &mut b, &mut report)
         };
         if rc != 0 {
             return Err(last_error(rc));

@@ -914,7 +914,7 @@ int madsim_hip_run_campaign_diff_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx,
 /* ---- Self-resolving campaigns: runner verdicts re-run on the device, every report over SETTLED results ----------------------
  * A runner verdict (MADSIM_OVERFLOW, MADSIM_STEP_LIMIT) is a statement about this runner, never an answer: real madsim gives pass /
  * panic / deadlock / time limit for such a seed, so a report that sets those seeds aside is biased — a genuine failure can hide
- * behind an overflow.  MADSIM_CAMPAIGN_RESOLVE, honoured by all fifteen campaign entry points, closes the gap: when a harvested
+ * behind an overflow.  MADSIM_CAMPAIGN_RESOLVE, honoured by every campaign entry point (the list forms too), closes the gap: when a harvested
  * batch reports runner verdicts, the re-runnable seeds are compacted into a seed list on the device, run again under grown limits
  * in one launch per round, their 48 bytes written back where they were, and the batch's report kernels run once more — so every
  * field of madsim_campaign_t, madsim_collect_t, madsim_stats_t, madsim_groups_t and madsim_diff_t, and every stop rule, is taken
@@ -965,6 +965,66 @@ int madsim_hip_ctx_campaign_resolved(madsim_hip_ctx_t* ctx, madsim_resolve_t* ou
  * from 0, from 32, n_progs + 8, 2, 2, 4 and 2, up to 2^20, 254, 255, 255, 127 and 15; max_steps (0 = 2^24) grows 16-fold up to
  * max_steps_ceiling (0 = 2^28, and never below the first pass's cap).  MADSIM_E_ARG: w or out NULL, rounds above 64. */
 int madsim_hip_grow_limits(const madsim_workload_t* w, const madsim_limits_t* lim, uint32_t rounds, madsim_limits_t* out);
+
+/* ---- List campaigns: every campaign form over the seeds you NAME -----------------------------------------------------------------
+ * The forms above run one contiguous range.  The step behind each of them is not a range: the failing seeds a collecting campaign
+ * returned, diffed against a fixed test body; a regression corpus of every seed that ever failed; the members of one failure mode.
+ * These entry points take an explicit list instead of (seed0, total): seeds[0 .. n), host memory, read only during the call.
+ * THE LIST MUST ASCEND STRICTLY (seeds[i] < seeds[i + 1]) — so that nothing about ordering changes: with an ascending list "smallest
+ * seed" and "first position" are the same thing, and every ordering rule of the range forms keeps its wording.  A list that is
+ * unsorted or holds a duplicate is MADSIM_E_ARG, never sorted silently.
+ * Position i of the list takes the role seed0 + i has in a range campaign:
+ *  - batch k is positions [k * batch, min((k + 1) * batch, n)) and runs on context k % n_ctx; reports are read in batch order;
+ *  - seeds_run counts POSITIONS of the prefix that was read: where the sections above say "of the prefix [seed0, seed0 + seeds_run)",
+ *    read "of seeds[0 .. seeds_run)";
+ *  - unchanged in wording: the collect records and the diff records ascend by seed; the statistics' top-K tie-break is "seed
+ *    ascending"; a group's first_seed is its smallest seed and the groups come in order of first appearance; first_failing_seed is
+ *    the smallest genuinely failing seed of the prefix;
+ *  - every flag keeps its meaning (MADSIM_CAMPAIGN_STOP_AT_FAILURE, LIST_RUNNER, STOP_AT_CAP, STOP_AT_GROUPS, STOP_AT_DIFFS, RESOLVE
+ *    and its rounds), and madsim_hip_campaign_resolved accounts for a list call as for a range call.
+ * Identity: when seeds is seed0, seed0 + 1, .., seed0 + n - 1, every byte of every report (madsim_campaign_t, madsim_collect_t and its
+ * records, madsim_stats_t, madsim_groups_t and its entries, madsim_diff_t and its records, madsim_resolve_t) equals the range entry
+ * point's, the timing fields kernel_ms, wall_s and rerun_kernel_ms apart.  Restriction: every report is a function of the per-seed
+ * results madsim_hip_run_batch returns for each listed seed (after the resolve rounds, if asked for) — the same bytes whatever
+ * `batch`, `in_flight` and the number of contexts.
+ * madsim_hip_run_seeds_campaign is all four non-differential forms in one: `col`, `st` and `grp` work as in
+ * madsim_hip_run_campaign_groups, and each of the three may be NULL (all three NULL: the plain campaign).  Flags that belong to an
+ * absent part are ignored; each present part's own argument checks apply.  The differential form is madsim_hip_run_campaign_diff
+ * with the list in place of the range; both sides of a batch run the same seeds.
+ * Errors are told before any context is looked at, like the other argument errors: MADSIM_E_ARG for seeds == NULL with n > 0, and for
+ * a pair that does not ascend (the message names the first offending position i: seeds[i] >= seeds[i + 1]).  The batch-size limits
+ * of the statistics, resolving, grouping and differential forms apply to min(batch, n).  n == 0 returns 0 with the reports
+ * initialised as for total == 0 (the ctx and default forms: with or without a device).  A list may contain UINT64_MAX: as the
+ * remark at first_failing_seed says, test n_failed, not the sentinel.
+ * Device memory for the list is 8 bytes per seed of a batch and flight, never proportional to n: a batch's slice is staged through
+ * page-locked memory onto the flight's stream ahead of its simulation launch.  The report kernels read a list entry only for a
+ * result whose seed they report. */
+int madsim_hip_ctx_run_seeds_campaign(madsim_hip_ctx_t* ctx, const madsim_workload_t* w, const madsim_config_t* cfg,
+                                      const uint64_t* seeds, uint64_t n, uint64_t batch, uint32_t in_flight, uint32_t flags,
+                                      const madsim_limits_t* lim, madsim_campaign_t* out, madsim_collect_t* col,
+                                      madsim_stats_t* st, madsim_groups_t* grp);
+int madsim_hip_run_seeds_campaign(const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n,
+                                  uint64_t batch, uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim,
+                                  madsim_campaign_t* out, madsim_collect_t* col, madsim_stats_t* st, madsim_groups_t* grp);
+int madsim_hip_run_seeds_campaign_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_workload_t* w,
+                                        const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n, uint64_t batch,
+                                        uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim, madsim_campaign_t* out,
+                                        madsim_collect_t* col, madsim_stats_t* st, madsim_groups_t* grp);
+int madsim_hip_ctx_run_seeds_campaign_diff(madsim_hip_ctx_t* ctx, const madsim_workload_t* wA, const madsim_config_t* cfgA,
+                                           const madsim_limits_t* limA, const madsim_workload_t* wB, const madsim_config_t* cfgB,
+                                           const madsim_limits_t* limB, const uint64_t* seeds, uint64_t n, uint64_t batch,
+                                           uint32_t in_flight, uint32_t flags, madsim_campaign_t* outA, madsim_campaign_t* outB,
+                                           madsim_diff_t* diff);
+int madsim_hip_run_seeds_campaign_diff(const madsim_workload_t* wA, const madsim_config_t* cfgA, const madsim_limits_t* limA,
+                                       const madsim_workload_t* wB, const madsim_config_t* cfgB, const madsim_limits_t* limB,
+                                       const uint64_t* seeds, uint64_t n, uint64_t batch, uint32_t in_flight, uint32_t flags,
+                                       madsim_campaign_t* outA, madsim_campaign_t* outB, madsim_diff_t* diff);
+int madsim_hip_run_seeds_campaign_diff_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_workload_t* wA,
+                                             const madsim_config_t* cfgA, const madsim_limits_t* limA,
+                                             const madsim_workload_t* wB, const madsim_config_t* cfgB,
+                                             const madsim_limits_t* limB, const uint64_t* seeds, uint64_t n, uint64_t batch,
+                                             uint32_t in_flight, uint32_t flags, madsim_campaign_t* outA,
+                                             madsim_campaign_t* outB, madsim_diff_t* diff);
 
 /* Geometry the library picked for a workload (for DESIGN/bench reporting). */
 typedef struct madsim_geometry {

@@ -456,6 +456,16 @@ struct Builder {
                                              // capacities.no_trace_hash = 1: results without the determinism-log fingerprint (4 % faster on ping-pong)
     uint32_t resolve_flags = 0;              // MADSIM_CAMPAIGN_RESOLVE and its rounds bits, set by resolve_runner() (0 = runner verdicts counted apart)
 
+    // The seeds the four campaign forms below run, when they are not the range seed .. seed + count: search_failures, campaign_stats,
+    // failure_groups and diff_against all honour over_seeds() (ONE setter rather than four overloads: the list is a property of the run, like
+    // the seed range it replaces).  The list must ascend strictly — sorted, no duplicates: std::sort + std::unique — so that "smallest seed"
+    // and "first position" stay one thing; the library refuses any other list (MADSIM_E_ARG), it never sorts silently.  seeds_run then counts
+    // positions of the list.  over_range() goes back to seed .. seed + count.  search_first_failure, run and check_determinism ignore it.
+    std::vector<uint64_t> seed_list;
+    bool listed_seeds = false;
+    Builder& over_seeds(std::vector<uint64_t> seeds) { seed_list = std::move(seeds); listed_seeds = true; return *this; }
+    Builder& over_range() { seed_list.clear(); listed_seeds = false; return *this; }
+
     // search_failures, campaign_stats, failure_groups and diff_against report on SETTLED results: seeds that come back with a runner verdict
     // (a device capacity, the step cap) are run again on the device under grown limits, up to `rounds` times (0 = the library's default,
     // at most MADSIM_RESOLVE_MAX_ROUNDS), before their batch is reported (MADSIM_CAMPAIGN_RESOLVE).  resolved() tells what the rounds did.
@@ -627,7 +637,8 @@ struct Builder {
         madsim_collect_t col{};
         col.failures = max_failures ? f.failures.data() : nullptr;
         col.cap = max_failures;
-        madsim::check(madsim_hip_run_campaign_collect(&w, &cfg, seed, count, 0, 0, resolve_flags, &lim, &f.campaign, &col));
+        madsim::check(listed_seeds ? madsim_hip_run_seeds_campaign(&w, &cfg, seed_list.data(), seed_list.size(), 0, 0, resolve_flags, &lim, &f.campaign, &col, nullptr, nullptr)
+                                   : madsim_hip_run_campaign_collect(&w, &cfg, seed, count, 0, 0, resolve_flags, &lim, &f.campaign, &col));
         f.failures.resize((size_t)col.n_listed);
         for (int v = 0; v < 8; v++) f.by_verdict[(size_t)v] = col.n_by_verdict[v];
         if (observe) {
@@ -660,7 +671,8 @@ struct Builder {
         s.stats.include = include;
         s.stats.top_k = top_k;
         s.stats.top = top_k ? s.top.data() : nullptr;
-        madsim::check(madsim_hip_run_campaign_stats(&w, &cfg, seed, count, 0, 0, resolve_flags, &lim, &s.campaign, nullptr, &s.stats));
+        madsim::check(listed_seeds ? madsim_hip_run_seeds_campaign(&w, &cfg, seed_list.data(), seed_list.size(), 0, 0, resolve_flags, &lim, &s.campaign, nullptr, &s.stats, nullptr)
+                                   : madsim_hip_run_campaign_stats(&w, &cfg, seed, count, 0, 0, resolve_flags, &lim, &s.campaign, nullptr, &s.stats));
         return s;
     }
 
@@ -694,7 +706,8 @@ struct Builder {
         grp.key_field = key_field;
         grp.groups = max_groups ? g.groups.data() : nullptr;
         grp.cap = max_groups;
-        madsim::check(madsim_hip_run_campaign_groups(&w, &cfg, seed, count, 0, 0, resolve_flags, &lim, &g.campaign, nullptr, nullptr, &grp));
+        madsim::check(listed_seeds ? madsim_hip_run_seeds_campaign(&w, &cfg, seed_list.data(), seed_list.size(), 0, 0, resolve_flags, &lim, &g.campaign, nullptr, nullptr, &grp)
+                                   : madsim_hip_run_campaign_groups(&w, &cfg, seed, count, 0, 0, resolve_flags, &lim, &g.campaign, nullptr, nullptr, &grp));
         g.groups.resize((size_t)grp.n_groups);
         g.n_grouped = grp.n_grouped;
         g.n_ungrouped = grp.n_ungrouped;
@@ -716,6 +729,7 @@ struct Builder {
     }
 
     // Fix check: this builder's run of `wl` (side A) against `other`'s run of `other_wl` (side B) over THIS builder's seed .. seed + count
+    // — or THIS builder's over_seeds() list: "did the fix fix all of them?" over exactly the seeds that failed (examples/corpus_test.cpp) —
     // (madsim_hip_run_campaign_diff): both sides run at the campaign's rate and are compared on the device on the result fields named in
     // `fields` (MADSIM_DIFF_*).  Config, capacities and time limit are each side's own; seed range and device are this builder's.  The
     // `max_listed` smallest differing seeds come back with both results, with the counts and the 8 x 8 verdict-transition matrix:
@@ -749,7 +763,8 @@ struct Builder {
         d.report.fields = fields;
         d.report.records = max_listed ? d.records.data() : nullptr;
         d.report.cap = max_listed;
-        madsim::check(madsim_hip_run_campaign_diff(&wa, &ca, &la, &wb, &cb, &lb, seed, count, 0, 0, resolve_flags, &d.a, &d.b, &d.report));
+        madsim::check(listed_seeds ? madsim_hip_run_seeds_campaign_diff(&wa, &ca, &la, &wb, &cb, &lb, seed_list.data(), seed_list.size(), 0, 0, resolve_flags, &d.a, &d.b, &d.report)
+                                   : madsim_hip_run_campaign_diff(&wa, &ca, &la, &wb, &cb, &lb, seed, count, 0, 0, resolve_flags, &d.a, &d.b, &d.report));
         d.records.resize((size_t)d.report.n_listed);
         d.report.records = nullptr;                                       // (the vector may move with the struct)
         if (observe) {

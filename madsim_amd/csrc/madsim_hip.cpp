@@ -115,7 +115,10 @@ struct madsim_hip_ctx {
                     // up to rr_cap seeds (60 B per seed), the list kernels' wave counts with the count word behind them (device) and that word's
                     // page-locked host copy, the re-run kernel's event pair
                     uint64_t* d_seeds = nullptr; uint32_t* d_idx = nullptr; madsim_result_t* d_rerun = nullptr; size_t rr_cap = 0;
-                    uint32_t* d_rcnt = nullptr; uint32_t* h_rcnt = nullptr; hipEvent_t r0 = nullptr, r1 = nullptr; };
+                    uint32_t* d_rcnt = nullptr; uint32_t* h_rcnt = nullptr; hipEvent_t r0 = nullptr, r1 = nullptr;
+                    // list campaigns only: the batch's slice of the caller's seed list (device) and its page-locked staging copy, list_cap words
+                    // each.  Not d_seeds: a resolving list campaign reads this one while it writes that one.
+                    uint64_t* d_list = nullptr; uint64_t* h_list = nullptr; size_t list_cap = 0; };
     static constexpr size_t GROUP_REP_WORDS = STATS_REP_WORDS + MADSIM_K_GROUP_WORDS;
     static constexpr size_t DIFF_REP_WORDS = 16 + MADSIM_K_DIFF_WORDS;      // summary6's six words of side A at 0, of side B at 8, the diff words at 16
     Flight flights[CAMPAIGN_MAX];
@@ -165,6 +168,7 @@ struct madsim_hip_ctx {
                        bool diff = false, uint64_t diff_records = 0);
     uint32_t flights_for(const madsim_workload_t* w, const madsim_config_t* cfg, const madsim_limits_t* lim, uint64_t batch);
     int ensure_resolve(Flight& f, uint64_t n);
+    int ensure_list(uint32_t n, uint64_t batch);
 };
 
 // The library keeps up to five sub-batches of a call in flight, each on its own HIP stream (run_pipelined, campaigns).  ROCclr maps
@@ -253,6 +257,8 @@ void madsim_hip_ctx::close() {
         if (f.d_rerun) (void)hipFree(f.d_rerun);
         if (f.d_rcnt) (void)hipFree(f.d_rcnt);
         if (f.h_rcnt) (void)hipHostFree(f.h_rcnt);
+        if (f.d_list) (void)hipFree(f.d_list);
+        if (f.h_list) (void)hipHostFree(f.h_list);
         if (f.r0) (void)hipEventDestroy(f.r0);
         if (f.r1) (void)hipEventDestroy(f.r1);
         if (f.b0) (void)hipEventDestroy(f.b0);
@@ -592,6 +598,23 @@ int madsim_hip_ctx::ensure_resolve(Flight& f, uint64_t n) {
         HIP_TRY(hipMalloc(&f.d_idx, want * sizeof(uint32_t)));
         HIP_TRY(hipMalloc(&f.d_rerun, want * sizeof(madsim_result_t)));
         f.rr_cap = want;
+    }
+    return 0;
+}
+
+// The list buffers of the first n flights (after ensure_flights), for list campaigns with batches of `batch` seeds: 8 bytes per seed of a
+// batch on the device and as many page-locked on the host, per flight — proportional to batch x flights, never to the length of the list.
+int madsim_hip_ctx::ensure_list(uint32_t n, uint64_t batch) {
+    for (uint32_t i = 0; i < n; i++) {
+        Flight& f = flights[i];
+        if (batch <= f.list_cap) continue;
+        if (f.list_cap) HIP_TRY(hipStreamSynchronize(f.stream));
+        if (f.d_list) (void)hipFree(f.d_list);
+        if (f.h_list) (void)hipHostFree(f.h_list);
+        f.d_list = nullptr; f.h_list = nullptr; f.list_cap = 0;
+        HIP_TRY(hipMalloc(&f.d_list, batch * sizeof(uint64_t)));
+        HIP_TRY(hipHostMalloc((void**)&f.h_list, batch * sizeof(uint64_t), hipHostMallocDefault));
+        f.list_cap = batch;
     }
     return 0;
 }
@@ -1178,6 +1201,8 @@ extern "C" void madsim_k_group_state_free(void* state) { delete static_cast<Grou
 extern "C" void madsim_k_fold_groups(madsim_groups_t* grp, void* state, const madsim_group_t* batch_entries, uint64_t n, uint64_t seed0_of_batch) {
     GroupState& S = *static_cast<GroupState*>(state);
     S.sorted.assign(batch_entries, batch_entries + n);
+    // (A list campaign passes the batch's FIRST LISTED seed: its entries' seeds ascend with their position in the batch, and none is
+    // below the first, so the differences order the entries exactly as their positions would.)
     std::sort(S.sorted.begin(), S.sorted.end(), [seed0_of_batch](const madsim_group_t& a, const madsim_group_t& b) {
         return a.first_seed - seed0_of_batch < b.first_seed - seed0_of_batch;      // the index in the batch: unique per group
     });
@@ -1264,13 +1289,14 @@ struct ResolveAccount {
 };
 
 // The rounds of one harvested batch, all on the flight's own stream (its scratch is keyed by the stream, and the other flights keep running):
-// d_res[0 .. n) are the results of seeds seed_lo .. under `lim`.  Round r compacts the seeds whose result is re-runnable under G^(r-1)(lim)
+// d_res[0 .. n) are the results of seeds seed_lo .. — or, in a list campaign, of d_list[0 .. n), the flight's slice of the list — under `lim`.  Round r compacts the seeds whose result is re-runnable under G^(r-1)(lim)
 // (madsim_k_launch_resolve_list), reads the one count word, and — unless it is 0 — runs them in one launch under G^r(lim) and writes their
 // new results where the old ones were (madsim_k_launch_resolve_scatter).  Every round grows everything (grow(.., true, true)): what a seed
 // ends with does not depend on its batch.  On return the stream holds nothing unfinished but the last scatter; *ran = a round ran, so the
 // caller's report is stale.
 int resolve_results(madsim_hip_ctx* c, madsim_hip_ctx::Flight& f, const madsim_workload_t* w, const madsim_config_t* cfg, const madsim_limits_t* lim,
-                    madsim_result_t* d_res, uint64_t seed_lo, uint64_t n, uint32_t rounds, madsim_resolve_t& acct, double* rerun_ms, bool* ran) {
+                    madsim_result_t* d_res, uint64_t seed_lo, const uint64_t* d_list, uint64_t n, uint32_t rounds, madsim_resolve_t& acct, double* rerun_ms,
+                    bool* ran) {
     madsim_limits_t L{};
     if (lim) L = *lim;
     int e;
@@ -1286,7 +1312,8 @@ int resolve_results(madsim_hip_ctx* c, madsim_hip_ctx::Flight& f, const madsim_w
     };
     for (uint32_t r = 1; r <= rounds; r++) {
         const uint32_t steps_maxed = (L.max_steps ? L.max_steps : (1u << 24)) >= step_ceiling(L) ? 1u : 0u;
-        if (madsim_k_launch_resolve_list(d_res, n, seed_lo, steps_maxed, f.d_rcnt, d_total, f.d_seeds, f.d_idx, f.stream))
+        if (d_list ? madsim_k_launch_resolve_list_list(d_res, n, d_list, steps_maxed, f.d_rcnt, d_total, f.d_seeds, f.d_idx, f.stream)
+                   : madsim_k_launch_resolve_list(d_res, n, seed_lo, steps_maxed, f.d_rcnt, d_total, f.d_seeds, f.d_idx, f.stream))
             return fail(MADSIM_E_ARG, "madsim_k_launch_resolve_list refused the batch's size");
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(f.h_rcnt, d_total, sizeof(uint32_t), hipMemcpyDeviceToHost, f.stream));
@@ -1313,7 +1340,9 @@ int resolve_results(madsim_hip_ctx* c, madsim_hip_ctx::Flight& f, const madsim_w
 
 int run_campaign_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total,
                       uint64_t batch, uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim, madsim_campaign_t* out,
-                      madsim_collect_t* col = nullptr, madsim_stats_t* st = nullptr, madsim_groups_t* grp = nullptr) {
+                      madsim_collect_t* col = nullptr, madsim_stats_t* st = nullptr, madsim_groups_t* grp = nullptr, const uint64_t* list = nullptr) {
+    // `list` (the list campaigns): position i of list[0 .. total) takes the role of seed0 + i, and seed0 is 0.  The loop, the flights, the fold
+    // and the stop rules are the range form's; a flight also carries the batch's slice of the list, copied in ahead of its simulation launch.
     auto t0 = std::chrono::steady_clock::now();
     memset(out, 0, sizeof *out);
     out->first_failing_seed = UINT64_MAX;
@@ -1335,7 +1364,7 @@ int run_campaign_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workl
     if (rc) return rc;
     if (batch == 0) batch = 65536;
     if (in_flight > (uint32_t)madsim_hip_ctx::CAMPAIGN_MAX) return fail(MADSIM_E_ARG, "at most 8 batches in flight per context");
-    if (seed0 + total < seed0) return fail(MADSIM_E_ARG, "seed0 + total wraps");
+    if (!list && seed0 + total < seed0) return fail(MADSIM_E_ARG, "seed0 + total wraps");
     if (total == 0) return 0;
     if (st && std::min(batch, total) >= 0xffffffffull) return fail(MADSIM_E_ARG, "a statistics campaign's batch holds fewer than 2^32 - 1 seeds");
     if (R && std::min(batch, total) >= (1ull << 30)) return fail(MADSIM_E_ARG, "a resolving campaign's batch holds fewer than 2^30 seeds");
@@ -1353,6 +1382,7 @@ int run_campaign_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workl
         if ((uint64_t)f > mine) f = (uint32_t)mine;
         F[g] = f;
         if (f && (rc = ctxs[g]->ensure_flights(f, batch, false, col != nullptr, rec_batch, st != nullptr, grp ? std::min(batch, total) : 0))) return rc;
+        if (f && list && (rc = ctxs[g]->ensure_list(f, std::min(batch, total)))) return rc;
     }
     int first_err = 0;
     std::string first_msg;
@@ -1374,17 +1404,21 @@ int run_campaign_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workl
     };
     auto queue_report = [&](madsim_hip_ctx::Flight& f, uint64_t lo, uint64_t n) -> int {
         unsigned long long* const d_words = words_of(f);
-        if (col) madsim_k_launch_collect(f.d_out, n, seed0 + lo, (flags & MADSIM_CAMPAIGN_LIST_RUNNER) ? 1u : 0u, d_words, f.d_wcnt, f.d_rec,
-                                         std::min(rec_batch, n), f.stream);
+        const uint32_t list_runner = (flags & MADSIM_CAMPAIGN_LIST_RUNNER) ? 1u : 0u;
+        if (col && list) madsim_k_launch_collect_list(f.d_out, n, f.d_list, list_runner, d_words, f.d_wcnt, f.d_rec, std::min(rec_batch, n), f.stream);
+        else if (col) madsim_k_launch_collect(f.d_out, n, seed0 + lo, list_runner, d_words, f.d_wcnt, f.d_rec, std::min(rec_batch, n), f.stream);
+        else if (list) madsim_k_launch_summary6_list(f.d_out, n, f.d_list, d_words, f.stream);
         else madsim_k_launch_summary6(f.d_out, n, seed0 + lo, d_words, f.stream);
         HIP_TRY(hipGetLastError());
         if (st) {                                                // behind the report kernel, into the words after its sixteen
-            madsim_k_launch_stats(f.d_out, n, seed0 + lo, st->include, st->top_k, d_words + 16, f.d_cand, f.stream);
+            if (list) madsim_k_launch_stats_list(f.d_out, n, f.d_list, st->include, st->top_k, d_words + 16, f.d_cand, f.stream);
+            else madsim_k_launch_stats(f.d_out, n, seed0 + lo, st->include, st->top_k, d_words + 16, f.d_cand, f.stream);
             HIP_TRY(hipGetLastError());
         }
         if (grp) {                                               // behind them: the batch's groups; their number rides with the report words
             f.grp_dirty = true;                                  // (until the batch is harvested: its extraction pass has then left the table zero)
-            if (madsim_k_launch_groups(f.d_out, n, seed0 + lo, grp->include, grp->key_field, f.d_gtab, gslots, f.d_glist, d_words + goff, f.d_gent, f.stream))
+            if (list ? madsim_k_launch_groups_list(f.d_out, n, f.d_list, grp->include, grp->key_field, f.d_gtab, gslots, f.d_glist, d_words + goff, f.d_gent, f.stream)
+                     : madsim_k_launch_groups(f.d_out, n, seed0 + lo, grp->include, grp->key_field, f.d_gtab, gslots, f.d_glist, d_words + goff, f.d_gent, f.stream))
                 return fail(MADSIM_E_ARG, "madsim_k_launch_groups refused the batch's sizes");
             HIP_TRY(hipGetLastError());
         }
@@ -1399,8 +1433,12 @@ int run_campaign_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workl
         int e;
         if ((e = c->bind())) return e;
         if ((e = prepare_report(f))) return e;
+        if (list) {                                              // the batch's slice, ahead of the launch that reads it (the flight's previous batch
+            memcpy(f.h_list, list + lo, n * sizeof(uint64_t));   // has been harvested: both buffers are free)
+            HIP_TRY(hipMemcpyAsync(f.d_list, f.h_list, n * sizeof(uint64_t), hipMemcpyHostToDevice, f.stream));
+        }
         HIP_TRY(hipEventRecord(f.e0, f.stream));
-        if ((e = c->launch(w, cfg, seed0 + lo, n, nullptr, lim, f.d_out, f.stream))) return e;
+        if ((e = c->launch(w, cfg, seed0 + lo, n, list ? f.d_list : nullptr, lim, f.d_out, f.stream))) return e;
         HIP_TRY(hipEventRecord(f.e1, f.stream));
         return queue_report(f, lo, n);
     };
@@ -1422,7 +1460,7 @@ int run_campaign_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workl
                 const unsigned long long runner_before = a[5];
                 double rerun_ms = 0.0;
                 bool ran = false;
-                if ((e = resolve_results(c, f, w, cfg, lim, f.d_out, seed0 + lo, n, R, acct, &rerun_ms, &ran))) return e;
+                if ((e = resolve_results(c, f, w, cfg, lim, f.d_out, seed0 + lo, list ? f.d_list : nullptr, n, R, acct, &rerun_ms, &ran))) return e;
                 acct.rerun_kernel_ms += rerun_ms; out->kernel_ms += rerun_ms;
                 if (ran) {                                      // (the grouping table is clean: the first chain's extraction pass left it so)
                     if ((e = prepare_report(f)) || (e = queue_report(f, lo, n))) return e;
@@ -1461,7 +1499,7 @@ int run_campaign_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workl
                     gbatch.resize(ng);
                     HIP_TRY(hipMemcpyAsync(gbatch.data(), f.d_gent, ng * sizeof(madsim_group_t), hipMemcpyDeviceToHost, f.stream));
                     HIP_TRY(hipStreamSynchronize(f.stream));
-                    madsim_k_fold_groups(grp, gstate.p, gbatch.data(), ng, seed0 + lo);
+                    madsim_k_fold_groups(grp, gstate.p, gbatch.data(), ng, list ? list[lo] : seed0 + lo);
                 }
                 if ((flags & MADSIM_CAMPAIGN_STOP_AT_GROUPS) && grp->n_groups >= grp->cap) stop = true;
             }
@@ -1478,7 +1516,8 @@ int run_campaign_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workl
 struct DiffSide { const madsim_workload_t* w; const madsim_config_t* cfg; const madsim_limits_t* lim; madsim_campaign_t* out; };
 
 int run_campaign_diff_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const DiffSide (&side)[2], uint64_t seed0, uint64_t total, uint64_t batch,
-                           uint32_t in_flight, uint32_t flags, madsim_diff_t* d) {
+                           uint32_t in_flight, uint32_t flags, madsim_diff_t* d, const uint64_t* list = nullptr) {
+    // `list`: as in run_campaign_impl — position i of list[0 .. total) for seed0 + i, seed0 = 0; both sides of a batch read the same slice.
     auto t0 = std::chrono::steady_clock::now();
     for (const DiffSide& s : side) { memset(s.out, 0, sizeof *s.out); s.out->first_failing_seed = UINT64_MAX; }
     d->n_listed = d->n_compared = d->n_incomparable = d->n_differ = 0;
@@ -1492,7 +1531,7 @@ int run_campaign_diff_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const DiffSid
         if (int rc = madsim_geo::validate(side[s].w, side[s].cfg, &g_err)) return fail(rc, std::string(s ? "side B: " : "side A: ") + g_err);
     if (batch == 0) batch = 65536;
     if (in_flight > (uint32_t)madsim_hip_ctx::CAMPAIGN_MAX) return fail(MADSIM_E_ARG, "at most 8 batches in flight per context");
-    if (seed0 + total < seed0) return fail(MADSIM_E_ARG, "seed0 + total wraps");
+    if (!list && seed0 + total < seed0) return fail(MADSIM_E_ARG, "seed0 + total wraps");
     if (total == 0) return 0;
     if (std::min(batch, total) >= (1ull << 32)) return fail(MADSIM_E_ARG, "a differential campaign's batch holds fewer than 2^32 seeds");
     if (R && std::min(batch, total) >= (1ull << 30)) return fail(MADSIM_E_ARG, "a resolving campaign's batch holds fewer than 2^30 seeds");
@@ -1508,6 +1547,7 @@ int run_campaign_diff_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const DiffSid
         if ((uint64_t)f > mine) f = (uint32_t)mine;
         F[g] = f;
         if (f && (rc = ctxs[g]->ensure_flights(f, batch, false, false, 0, false, 0, true, rec_batch))) return rc;
+        if (f && list && (rc = ctxs[g]->ensure_list(f, std::min(batch, total)))) return rc;
     }
     constexpr size_t n_words = madsim_hip_ctx::DIFF_REP_WORDS;
     int first_err = 0;
@@ -1521,12 +1561,14 @@ int run_campaign_diff_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const DiffSid
         return 0;
     };
     auto queue_summary = [&](madsim_hip_ctx::Flight& f, int s, uint64_t lo, uint64_t n) -> int {
-        madsim_k_launch_summary6(s ? f.d_out_b : f.d_out, n, seed0 + lo, f.d_drep + 8 * s, f.stream);
+        if (list) madsim_k_launch_summary6_list(s ? f.d_out_b : f.d_out, n, f.d_list, f.d_drep + 8 * s, f.stream);
+        else madsim_k_launch_summary6(s ? f.d_out_b : f.d_out, n, seed0 + lo, f.d_drep + 8 * s, f.stream);
         HIP_TRY(hipGetLastError());
         return 0;
     };
     auto queue_diff = [&](madsim_hip_ctx::Flight& f, uint64_t lo, uint64_t n) -> int {
-        if (madsim_k_launch_diff(f.d_out, f.d_out_b, n, seed0 + lo, d->fields, f.d_drep + 16, f.d_dwcnt, f.d_drec, std::min(rec_batch, n), f.stream))
+        if (list ? madsim_k_launch_diff_list(f.d_out, f.d_out_b, n, f.d_list, d->fields, f.d_drep + 16, f.d_dwcnt, f.d_drec, std::min(rec_batch, n), f.stream)
+                 : madsim_k_launch_diff(f.d_out, f.d_out_b, n, seed0 + lo, d->fields, f.d_drep + 16, f.d_dwcnt, f.d_drec, std::min(rec_batch, n), f.stream))
             return fail(MADSIM_E_ARG, "madsim_k_launch_diff refused the batch's arguments");
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(f.h_drep, f.d_drep, n_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, f.stream));
@@ -1540,12 +1582,17 @@ int run_campaign_diff_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const DiffSid
         int e;
         if ((e = c->bind())) return e;
         if ((e = prepare_report(f))) return e;
+        if (list) {                                              // one slice for both sides (the flight's previous batch has been harvested)
+            memcpy(f.h_list, list + lo, n * sizeof(uint64_t));
+            HIP_TRY(hipMemcpyAsync(f.d_list, f.h_list, n * sizeof(uint64_t), hipMemcpyHostToDevice, f.stream));
+        }
+        const uint64_t* const d_list = list ? f.d_list : nullptr;
         HIP_TRY(hipEventRecord(f.e0, f.stream));
-        if ((e = c->launch(side[0].w, side[0].cfg, seed0 + lo, n, nullptr, side[0].lim, f.d_out, f.stream))) return fail(e, "side A: " + g_err);
+        if ((e = c->launch(side[0].w, side[0].cfg, seed0 + lo, n, d_list, side[0].lim, f.d_out, f.stream))) return fail(e, "side A: " + g_err);
         HIP_TRY(hipEventRecord(f.e1, f.stream));
         if ((e = queue_summary(f, 0, lo, n))) return e;
         HIP_TRY(hipEventRecord(f.b0, f.stream));
-        if ((e = c->launch(side[1].w, side[1].cfg, seed0 + lo, n, nullptr, side[1].lim, f.d_out_b, f.stream))) return fail(e, "side B: " + g_err);
+        if ((e = c->launch(side[1].w, side[1].cfg, seed0 + lo, n, d_list, side[1].lim, f.d_out_b, f.stream))) return fail(e, "side B: " + g_err);
         HIP_TRY(hipEventRecord(f.b1, f.stream));
         if ((e = queue_summary(f, 1, lo, n))) return e;
         return queue_diff(f, lo, n);
@@ -1567,7 +1614,8 @@ int run_campaign_diff_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const DiffSid
             for (int s = 0; s < 2; s++) {                       // (one after the other on the flight's stream: they share its re-run scratch)
                 if (!runner_before[s]) continue;
                 double rerun_ms = 0.0;
-                if ((e = resolve_results(c, f, side[s].w, side[s].cfg, side[s].lim, s ? f.d_out_b : f.d_out, seed0 + lo, n, R, acct, &rerun_ms, &ran)))
+                if ((e = resolve_results(c, f, side[s].w, side[s].cfg, side[s].lim, s ? f.d_out_b : f.d_out, seed0 + lo, list ? f.d_list : nullptr, n, R, acct,
+                                         &rerun_ms, &ran)))
                     return fail(e, std::string(s ? "side B: " : "side A: ") + g_err);
                 acct.rerun_kernel_ms += rerun_ms; side[s].out->kernel_ms += rerun_ms;
             }
@@ -1802,6 +1850,92 @@ int madsim_hip_run_campaign_diff_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx,
     return run_campaign_diff_impl(ctxs, n_ctx, side, seed0, total, batch, in_flight, flags, diff);
 }
 
+// ---- list campaigns: every campaign form over an explicit seed list ----------------------------------------------------------------
+// Argument errors first, as the other forms: the list itself (NULL with n > 0; a pair that does not ascend strictly, named by the position
+// of its first seed), then each present part's own checks.  All told before any context is looked at.
+namespace {
+int check_seed_list(const uint64_t* seeds, uint64_t n) {
+    if (!seeds && n) return fail(MADSIM_E_ARG, "null seed list with n > 0");
+    for (uint64_t i = 0; i + 1 < n; i++)
+        if (seeds[i] >= seeds[i + 1])
+            return fail(MADSIM_E_ARG, "the seed list must ascend strictly: seeds[" + std::to_string(i) + "] = " + std::to_string(seeds[i]) + " is not below seeds[" +
+                                          std::to_string(i + 1) + "] = " + std::to_string(seeds[i + 1]) + " (sort it and drop duplicates)");
+    return 0;
+}
+int check_seeds_args(const uint64_t* seeds, uint64_t n, uint64_t batch, uint32_t in_flight, uint32_t flags, const madsim_campaign_t* out,
+                     const madsim_collect_t* col, const madsim_stats_t* st, const madsim_groups_t* grp) {
+    if (int rc = check_seed_list(seeds, n)) return rc;
+    if (!col) flags &= ~(MADSIM_CAMPAIGN_LIST_RUNNER | MADSIM_CAMPAIGN_STOP_AT_CAP);      // (flags of an absent part are ignored)
+    if (!grp) flags &= ~MADSIM_CAMPAIGN_STOP_AT_GROUPS;
+    if (grp) return check_groups_args(out, col, st, grp, n, batch, in_flight, flags);
+    if (st) return check_stats_args(out, col, st, in_flight, flags);
+    if (col) return check_collect_args(out, col, in_flight, flags);
+    if (!out) return fail(MADSIM_E_ARG, "null campaign report");
+    if (int rc = check_resolve_flags(flags)) return rc;
+    if (in_flight > (uint32_t)madsim_hip_ctx::CAMPAIGN_MAX) return fail(MADSIM_E_ARG, "at most 8 batches in flight per context");
+    return 0;
+}
+// the contexts of a _multi call, checked and locked in address order (see madsim_hip_run_batch_multi)
+int lock_contexts(madsim_hip_ctx_t* const* ctxs, int n_ctx, const char* who, std::vector<std::unique_lock<std::mutex>>& locks) {
+    if (!ctxs || n_ctx < 1) return fail(MADSIM_E_ARG, std::string(who) + " needs at least one context");
+    for (int g = 0; g < n_ctx; g++) {
+        if (!ctxs[g]) return fail(MADSIM_E_NOINIT, "null context");
+        for (int h = 0; h < g; h++) if (ctxs[h] == ctxs[g]) return fail(MADSIM_E_ARG, "the same context appears twice");
+    }
+    std::vector<madsim_hip_ctx*> order(ctxs, ctxs + n_ctx);
+    std::sort(order.begin(), order.end(), [](madsim_hip_ctx* a, madsim_hip_ctx* b) { return std::less<madsim_hip_ctx*>()(a, b); });
+    for (madsim_hip_ctx* c : order) locks.emplace_back(c->mu);
+    for (int g = 0; g < n_ctx; g++) if (ctxs[g]->device < 0) return fail(MADSIM_E_NOINIT, "closed context");
+    return 0;
+}
+}  // namespace
+
+int madsim_hip_ctx_run_seeds_campaign(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n,
+                                      uint64_t batch, uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim, madsim_campaign_t* out,
+                                      madsim_collect_t* col, madsim_stats_t* st, madsim_groups_t* grp) {
+    if (int rc = check_seeds_args(seeds, n, batch, in_flight, flags, out, col, st, grp)) return rc;
+    if (n == 0 && (!c || c->device < 0))                         // an empty list needs no device: the reports of an empty range, and 0
+        return run_campaign_impl(nullptr, 0, w, cfg, 0, 0, batch, in_flight, flags, lim, out, col, st, grp);
+    CTX_ENTER(c);
+    madsim_hip_ctx* one[1] = {c};
+    return run_campaign_impl(one, 1, w, cfg, 0, n, batch, in_flight, flags, lim, out, col, st, grp, n ? seeds : nullptr);
+}
+
+int madsim_hip_run_seeds_campaign_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_workload_t* w, const madsim_config_t* cfg,
+                                        const uint64_t* seeds, uint64_t n, uint64_t batch, uint32_t in_flight, uint32_t flags,
+                                        const madsim_limits_t* lim, madsim_campaign_t* out, madsim_collect_t* col, madsim_stats_t* st,
+                                        madsim_groups_t* grp) {
+    if (int rc = check_seeds_args(seeds, n, batch, in_flight, flags, out, col, st, grp)) return rc;
+    std::vector<std::unique_lock<std::mutex>> locks;
+    if (int rc = lock_contexts(ctxs, n_ctx, "run_seeds_campaign_multi", locks)) return rc;
+    return run_campaign_impl(ctxs, n_ctx, w, cfg, 0, n, batch, in_flight, flags, lim, out, col, st, grp, n ? seeds : nullptr);
+}
+
+int madsim_hip_ctx_run_seeds_campaign_diff(madsim_hip_ctx_t* c, const madsim_workload_t* wA, const madsim_config_t* cfgA, const madsim_limits_t* limA,
+                                           const madsim_workload_t* wB, const madsim_config_t* cfgB, const madsim_limits_t* limB,
+                                           const uint64_t* seeds, uint64_t n, uint64_t batch, uint32_t in_flight, uint32_t flags,
+                                           madsim_campaign_t* outA, madsim_campaign_t* outB, madsim_diff_t* diff) {
+    if (int rc = check_seed_list(seeds, n)) return rc;
+    if (int rc = check_diff_args(outA, outB, diff, in_flight, flags)) return rc;
+    const DiffSide side[2] = {{wA, cfgA, limA, outA}, {wB, cfgB, limB, outB}};
+    if (n == 0 && (!c || c->device < 0)) return run_campaign_diff_impl(nullptr, 0, side, 0, 0, batch, in_flight, flags, diff);      // (no device needed)
+    CTX_ENTER(c);
+    madsim_hip_ctx* one[1] = {c};
+    return run_campaign_diff_impl(one, 1, side, 0, n, batch, in_flight, flags, diff, n ? seeds : nullptr);
+}
+
+int madsim_hip_run_seeds_campaign_diff_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_workload_t* wA, const madsim_config_t* cfgA,
+                                             const madsim_limits_t* limA, const madsim_workload_t* wB, const madsim_config_t* cfgB,
+                                             const madsim_limits_t* limB, const uint64_t* seeds, uint64_t n, uint64_t batch, uint32_t in_flight,
+                                             uint32_t flags, madsim_campaign_t* outA, madsim_campaign_t* outB, madsim_diff_t* diff) {
+    if (int rc = check_seed_list(seeds, n)) return rc;
+    if (int rc = check_diff_args(outA, outB, diff, in_flight, flags)) return rc;
+    std::vector<std::unique_lock<std::mutex>> locks;
+    if (int rc = lock_contexts(ctxs, n_ctx, "run_seeds_campaign_diff_multi", locks)) return rc;
+    const DiffSide side[2] = {{wA, cfgA, limA, outA}, {wB, cfgB, limB, outB}};
+    return run_campaign_diff_impl(ctxs, n_ctx, side, 0, n, batch, in_flight, flags, diff, n ? seeds : nullptr);
+}
+
 // ---- v1 entry points: wrappers on the process-default context ------------------------------------------------------------
 // The default context is reference-counted by its users: a wrapper pins it under g_default_mu for the duration of its call,
 // and madsim_hip_shutdown waits until no call is inside before destroying it — a concurrent run_batch and shutdown is a
@@ -1922,6 +2056,20 @@ int madsim_hip_run_campaign_diff(const madsim_workload_t* wA, const madsim_confi
                                  uint32_t in_flight, uint32_t flags, madsim_campaign_t* outA, madsim_campaign_t* outB, madsim_diff_t* diff) {
     DefaultPin p;
     return madsim_hip_ctx_run_campaign_diff(p.c, wA, cfgA, limA, wB, cfgB, limB, seed0, total, batch, in_flight, flags, outA, outB, diff);
+}
+
+int madsim_hip_run_seeds_campaign(const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n, uint64_t batch,
+                                  uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim, madsim_campaign_t* out, madsim_collect_t* col,
+                                  madsim_stats_t* st, madsim_groups_t* grp) {
+    DefaultPin p;
+    return madsim_hip_ctx_run_seeds_campaign(p.c, w, cfg, seeds, n, batch, in_flight, flags, lim, out, col, st, grp);
+}
+
+int madsim_hip_run_seeds_campaign_diff(const madsim_workload_t* wA, const madsim_config_t* cfgA, const madsim_limits_t* limA, const madsim_workload_t* wB,
+                                       const madsim_config_t* cfgB, const madsim_limits_t* limB, const uint64_t* seeds, uint64_t n, uint64_t batch,
+                                       uint32_t in_flight, uint32_t flags, madsim_campaign_t* outA, madsim_campaign_t* outB, madsim_diff_t* diff) {
+    DefaultPin p;
+    return madsim_hip_ctx_run_seeds_campaign_diff(p.c, wA, cfgA, limA, wB, cfgB, limB, seeds, n, batch, in_flight, flags, outA, outB, diff);
 }
 
 int madsim_hip_geometry(const madsim_workload_t* w, const madsim_limits_t* lim, madsim_geometry_t* out) {

@@ -383,6 +383,22 @@ int  madsim_k_launch_resolve_list(const madsim_result_t* out, uint64_t count, ui
 // out[idx[j]] = rerun[j] for j < m, 48 bytes each as three 16-byte chunks (thread t: chunk t % 3 of record t / 3); idx: distinct indices into
 // `out`, nothing else of which is touched.  m == 0 launches nothing.  Returns 0, or -1 without launching anything for 3 * m >= 2^32.
 int  madsim_k_launch_resolve_scatter(madsim_result_t* out, const madsim_result_t* rerun, const uint32_t* idx, uint64_t m, void* stream);
+// The list forms of the six report launchers above (the list campaigns, madsim_hip_run_seeds_campaign): result i belongs to seed d_seeds[i]
+// where the range form says seed0 + i — `d_seeds` a device pointer to the batch's slice of a strictly ascending seed list, `count` entries,
+// read only for a result whose seed is reported (a failing, listed, extreme, first-of-its-group, differing or re-runnable one).  Everything
+// else — buffers, preparation, cut, return values — is the range form's; for a slice seed0, seed0 + 1, ... every byte written is too.
+// The resolve form reads the slice and writes `seeds`: two buffers, never the same one.
+void madsim_k_launch_summary6_list(const madsim_result_t* out, uint64_t count, const uint64_t* d_seeds, unsigned long long* acc6, void* stream);
+void madsim_k_launch_collect_list(const madsim_result_t* out, uint64_t count, const uint64_t* d_seeds, uint32_t list_runner, unsigned long long* rep,
+                                  uint32_t* wave_cnt, madsim_failure_t* recs, uint64_t cap, void* stream);
+void madsim_k_launch_stats_list(const madsim_result_t* out, uint64_t count, const uint64_t* d_seeds, uint32_t include, uint32_t top_k,
+                                unsigned long long* srep, unsigned long long* cand, void* stream);
+int  madsim_k_launch_groups_list(const madsim_result_t* out, uint64_t count, const uint64_t* d_seeds, uint32_t include, uint32_t key_field,
+                                 uint32_t* table, uint64_t slots, uint32_t* list, unsigned long long* grep, madsim_group_t* entries, void* stream);
+int  madsim_k_launch_diff_list(const madsim_result_t* a, const madsim_result_t* b, uint64_t count, const uint64_t* d_seeds, uint32_t fields,
+                               unsigned long long* words, uint32_t* wave_cnt, madsim_diff_record_t* recs, uint64_t cap, void* stream);
+int  madsim_k_launch_resolve_list_list(const madsim_result_t* out, uint64_t count, const uint64_t* d_seeds, uint32_t steps_maxed, uint32_t* wave_cnt,
+                                       uint32_t* total, uint64_t* seeds, uint32_t* idx, void* stream);
 int  madsim_k_set_max_lds(uint32_t lds_bytes);
 int  madsim_k_variant_vgprs(const madsim_k::VariantSel* v);
 void madsim_k_launch_keyflip(unsigned long long* acc, void* stream);

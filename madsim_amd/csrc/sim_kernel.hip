@@ -64,15 +64,25 @@ __global__ __launch_bounds__(256) void summary_kernel(const madsim_result_t* __r
     }
 }
 
+// Where a report kernel takes the seed of result i from: the range forms' seed0 + i, or entry i of the batch's slice of a seed list (the list
+// campaigns, madsim_hip_run_seeds_campaign: the list ascends strictly, so every "ascending position" below is still "ascending seed").
+// A compile-time switch — the RangeSeeds instantiation is the kernel as it was, the 8 bytes of seed0 in the same kernel-argument slot —
+// and a list entry is loaded only inside the branch that uses the seed (a failing, listed, extreme or re-runnable result): the lanes
+// outside it are masked off and issue no load, and a wave none of whose lanes takes the branch skips it, so a batch of passing seeds
+// reads nothing of its list here.
+struct RangeSeeds { uint64_t seed0; __device__ __forceinline__ unsigned long long operator()(uint64_t i) const { return seed0 + i; } };
+struct ListSeeds  { const uint64_t* __restrict__ d; __device__ __forceinline__ unsigned long long operator()(uint64_t i) const { return d[i]; } };
+
 // the campaign form: also tells the RUNNER verdicts (device capacity, step cap: not reference verdicts) from genuine failures —
 // acc6 = {first failing seed, n_failed, steps, clock, first seed with a GENUINE verdict (panic / deadlock / time limit), n runner verdicts}
+template <class Seeds>
 __global__ __launch_bounds__(256) void summary6_kernel(const madsim_result_t* __restrict__ out, uint64_t count,
-                                                       uint64_t seed0, unsigned long long* __restrict__ acc) {
+                                                       const Seeds seed_of, unsigned long long* __restrict__ acc) {
     unsigned long long first = ~0ull, nfail = 0, steps = 0, clk = 0, gfirst = ~0ull, nrun = 0;
     for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < count; i += (uint64_t)gridDim.x * blockDim.x) {
         const uint4 r = reinterpret_cast<const uint4*>(out + i)[0];
         if (r.x != MADSIM_PASS) {
-            const unsigned long long s = seed0 + i;
+            const unsigned long long s = seed_of(i);
             nfail++; first = s < first ? s : first;
             if (MADSIM_IS_RUNNER_VERDICT(r.x)) nrun++; else gfirst = s < gfirst ? s : gfirst;
         }
@@ -109,7 +119,8 @@ __device__ __forceinline__ bool collect_listed(uint32_t verdict, uint32_t list_r
     return verdict != MADSIM_PASS && (list_runner || !MADSIM_IS_RUNNER_VERDICT(verdict));
 }
 
-__global__ __launch_bounds__(256) void collect_count_kernel(const madsim_result_t* __restrict__ out, uint64_t count, uint64_t seed0,
+template <class Seeds>
+__global__ __launch_bounds__(256) void collect_count_kernel(const madsim_result_t* __restrict__ out, uint64_t count, const Seeds seed_of,
                                                             uint64_t piece, uint32_t list_runner,
                                                             unsigned long long* __restrict__ rep, uint32_t* __restrict__ wave_cnt) {
     const uint32_t W = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -123,7 +134,7 @@ __global__ __launch_bounds__(256) void collect_count_kernel(const madsim_result_
             const uint4 r = reinterpret_cast<const uint4*>(out + i)[0];
             v = r.x;
             if (v != MADSIM_PASS) {
-                const unsigned long long s = seed0 + i;
+                const unsigned long long s = seed_of(i);
                 nfail++; first = s < first ? s : first;
                 if (MADSIM_IS_RUNNER_VERDICT(v)) nrun++; else gfirst = s < gfirst ? s : gfirst;
             }
@@ -153,7 +164,8 @@ __global__ __launch_bounds__(256) void collect_count_kernel(const madsim_result_
     }
 }
 
-__global__ __launch_bounds__(256) void collect_write_kernel(const madsim_result_t* __restrict__ out, uint64_t count, uint64_t seed0,
+template <class Seeds>
+__global__ __launch_bounds__(256) void collect_write_kernel(const madsim_result_t* __restrict__ out, uint64_t count, const Seeds seed_of,
                                                             uint64_t piece, uint32_t list_runner, unsigned long long* __restrict__ rep,
                                                             const uint32_t* __restrict__ wave_cnt, madsim_failure_t* __restrict__ recs,
                                                             uint64_t cap) {
@@ -178,7 +190,7 @@ __global__ __launch_bounds__(256) void collect_write_kernel(const madsim_result_
         if (mine && rank < cap) {                                                  // the other 32 bytes only of a seed that is listed
             const uint4 r1 = reinterpret_cast<const uint4*>(out + i)[1], r2 = reinterpret_cast<const uint4*>(out + i)[2];
             unsigned long long* p = reinterpret_cast<unsigned long long*>(recs + rank);          // 56 B records: 8-byte stores
-            p[0] = seed0 + i;
+            p[0] = seed_of(i);
             p[1] = ((unsigned long long)r.y << 32) | r.x;   p[2] = ((unsigned long long)r.w << 32) | r.z;
             p[3] = ((unsigned long long)r1.y << 32) | r1.x; p[4] = ((unsigned long long)r1.w << 32) | r1.z;
             p[5] = ((unsigned long long)r2.y << 32) | r2.x; p[6] = ((unsigned long long)r2.w << 32) | r2.z;
@@ -335,7 +347,8 @@ __global__ __launch_bounds__(256) void stats_fold_kernel(const madsim_result_t* 
 
 // grid = MADSIM_STAT_METRICS workgroups: workgroup m merges cand[m][0 .. n_wg)[0 .. 16) ({value, index in the batch or ~0}), a quarter per
 // wave, then wave 0 the four lists; top[m][r] = {value, seed}, r < min(K, counted seeds of the batch).
-__global__ __launch_bounds__(256) void stats_top_kernel(const unsigned long long* __restrict__ cand, uint32_t n_wg, uint32_t K, uint64_t seed0,
+template <class Seeds>
+__global__ __launch_bounds__(256) void stats_top_kernel(const unsigned long long* __restrict__ cand, uint32_t n_wg, uint32_t K, const Seeds seed_of,
                                                         unsigned long long* __restrict__ top) {
     __shared__ unsigned long long lv[4 * STAT_TOP];
     __shared__ uint32_t lk[4 * STAT_TOP];
@@ -360,7 +373,7 @@ __global__ __launch_bounds__(256) void stats_top_kernel(const unsigned long long
         topk_merge<1>(l1, n1, K, lane);
         if (lane < K && l1[0].k) {
             unsigned long long* p = top + (uint64_t)(m * STAT_TOP + lane) * 2;
-            p[0] = l1[0].v; p[1] = seed0 + (uint32_t)~l1[0].k;
+            p[0] = l1[0].v; p[1] = seed_of((uint32_t)~l1[0].k);
         }
     }
 }
@@ -442,7 +455,8 @@ __global__ __launch_bounds__(256) void group_fold_kernel(const madsim_result_t* 
     }
 }
 
-__global__ __launch_bounds__(256) void group_extract_kernel(const madsim_result_t* __restrict__ out, uint32_t count, uint64_t seed0, uint32_t key_word,
+template <class Seeds>
+__global__ __launch_bounds__(256) void group_extract_kernel(const madsim_result_t* __restrict__ out, uint32_t count, const Seeds seed_of, uint32_t key_word,
                                                             uint4* __restrict__ table, uint32_t mask, const uint32_t* __restrict__ list,
                                                             unsigned long long* __restrict__ grep, madsim_group_t* __restrict__ entries) {
     const unsigned long long claimed = grep[0];                                    // (nobody adds to it in this kernel)
@@ -461,7 +475,7 @@ __global__ __launch_bounds__(256) void group_extract_kernel(const madsim_result_
         p[0] = group_key(out + rep, key_word);
         p[1] = reinterpret_cast<const uint32_t*>(out + rep)[0];                    // verdict, reserved = 0
         p[2] = e.y;
-        p[3] = seed0 + first;
+        p[3] = seed_of(first);
     }
 }
 
@@ -534,8 +548,9 @@ __global__ __launch_bounds__(256) void diff_count_kernel(const madsim_result_t* 
     if (threadIdx.x > 0 && threadIdx.x < 64 && cells[threadIdx.x]) atomicAdd(&words[10 + threadIdx.x], (unsigned long long)cells[threadIdx.x]);
 }
 
+template <class Seeds>
 __global__ __launch_bounds__(256) void diff_write_kernel(const madsim_result_t* __restrict__ a, const madsim_result_t* __restrict__ b, uint64_t count,
-                                                         uint64_t seed0, uint64_t piece, uint32_t fields, unsigned long long* __restrict__ words,
+                                                         const Seeds seed_of, uint64_t piece, uint32_t fields, unsigned long long* __restrict__ words,
                                                          const uint32_t* __restrict__ wave_cnt, madsim_diff_record_t* __restrict__ recs, uint64_t cap) {
     const uint32_t W = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (W == 0 && lane == 0) {                                                     // PASS -> PASS is what the other 63 cells leave
@@ -559,7 +574,7 @@ __global__ __launch_bounds__(256) void diff_write_kernel(const madsim_result_t* 
             const uint4* qa = reinterpret_cast<const uint4*>(a + i);
             const uint4* qb = reinterpret_cast<const uint4*>(b + i);
             unsigned long long* p = reinterpret_cast<unsigned long long*>(recs) + rank * 13u;      // 104 B records: 8-byte stores
-            p[0] = seed0 + i;
+            p[0] = seed_of(i);
 #pragma unroll
             for (int j = 0; j < 3; j++) {
                 const uint4 x = qa[j], y = qb[j];
@@ -599,7 +614,8 @@ __global__ __launch_bounds__(256) void resolve_count_kernel(const madsim_result_
     if (lane == 0) wave_cnt[W] = n;
 }
 
-__global__ __launch_bounds__(256) void resolve_write_kernel(const madsim_result_t* __restrict__ out, uint64_t count, uint64_t seed0,
+template <class Seeds>
+__global__ __launch_bounds__(256) void resolve_write_kernel(const madsim_result_t* __restrict__ out, uint64_t count, const Seeds seed_of,
                                                             uint64_t piece, uint32_t steps_maxed, const uint32_t* __restrict__ wave_cnt,
                                                             uint32_t n_waves, uint32_t* __restrict__ total, uint64_t* __restrict__ seeds,
                                                             uint32_t* __restrict__ idx) {
@@ -623,7 +639,7 @@ __global__ __launch_bounds__(256) void resolve_write_kernel(const madsim_result_
         const unsigned long long m = __ballot(mine);
         if (mine) {
             const uint32_t rank = at + lanes_below(m);
-            seeds[rank] = seed0 + i;
+            seeds[rank] = seed_of(i);
             idx[rank] = (uint32_t)i;
         }
         at += (uint32_t)__popcll(m);
@@ -665,32 +681,56 @@ extern "C" void madsim_k_launch_summary(const madsim_result_t* out, uint64_t cou
     hipLaunchKernelGGL(madsim_k::summary_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, out, count, seed0, acc);
 }
 
-extern "C" void madsim_k_launch_summary6(const madsim_result_t* out, uint64_t count, uint64_t seed0, unsigned long long* acc6, void* stream) {
+// Every launcher of a report family below exists twice: the range form (result i is seed seed0 + i) and the _list form (result i is seed
+// d_seeds[i], a device pointer to the batch's slice of the list).  One template each, so that the two cannot drift apart.
+namespace madsim_k {
+template <class Seeds>
+static void launch_summary6(const madsim_result_t* out, uint64_t count, Seeds src, unsigned long long* acc6, void* stream) {
     uint32_t grid = (uint32_t)((count + 1023) / 1024);
     if (grid > 256) grid = 256;
     if (grid == 0) grid = 1;
-    hipLaunchKernelGGL(madsim_k::summary6_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, out, count, seed0, acc6);
+    hipLaunchKernelGGL((summary6_kernel<Seeds>), dim3(grid), dim3(256), 0, (hipStream_t)stream, out, count, src, acc6);
+}
+}  // namespace madsim_k
+extern "C" void madsim_k_launch_summary6(const madsim_result_t* out, uint64_t count, uint64_t seed0, unsigned long long* acc6, void* stream) {
+    madsim_k::launch_summary6(out, count, madsim_k::RangeSeeds{seed0}, acc6, stream);
+}
+extern "C" void madsim_k_launch_summary6_list(const madsim_result_t* out, uint64_t count, const uint64_t* d_seeds, unsigned long long* acc6, void* stream) {
+    madsim_k::launch_summary6(out, count, madsim_k::ListSeeds{d_seeds}, acc6, stream);
 }
 
 // rep: COLLECT_REP_WORDS words, wave_cnt: MADSIM_K_COLLECT_WAVES words, recs: `cap` records (may be null when cap == 0); all prepared by the
 // caller on `stream` (rep words 0 and 4 all-ones, the rest zero)
-extern "C" void madsim_k_launch_collect(const madsim_result_t* out, uint64_t count, uint64_t seed0, uint32_t list_runner,
-                                        unsigned long long* rep, uint32_t* wave_cnt, madsim_failure_t* recs, uint64_t cap, void* stream) {
+namespace madsim_k {
+template <class Seeds>
+static void launch_collect(const madsim_result_t* out, uint64_t count, Seeds src, uint32_t list_runner,
+                           unsigned long long* rep, uint32_t* wave_cnt, madsim_failure_t* recs, uint64_t cap, void* stream) {
     static_assert(madsim_k::COLLECT_MAX_WAVES == MADSIM_K_COLLECT_WAVES && madsim_k::COLLECT_REP_WORDS == MADSIM_K_COLLECT_WORDS, "sim_kernel.h");
     static_assert(sizeof(madsim_failure_t) == 56 && sizeof(madsim_result_t) == 48, "record layout");
     uint32_t grid = (uint32_t)((count + 1023) / 1024);     // summary6's grid; every wave a contiguous piece, a multiple of 64 results
     if (grid > 256) grid = 256;
     if (grid == 0) grid = 1;
     const uint64_t waves = 4ull * grid, piece = ((count + waves - 1) / waves + 63) / 64 * 64;
-    hipLaunchKernelGGL(madsim_k::collect_count_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, out, count, seed0, piece, list_runner, rep, wave_cnt);
-    hipLaunchKernelGGL(madsim_k::collect_write_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, out, count, seed0, piece, list_runner, rep,
+    hipLaunchKernelGGL((collect_count_kernel<Seeds>), dim3(grid), dim3(256), 0, (hipStream_t)stream, out, count, src, piece, list_runner, rep, wave_cnt);
+    hipLaunchKernelGGL((collect_write_kernel<Seeds>), dim3(grid), dim3(256), 0, (hipStream_t)stream, out, count, src, piece, list_runner, rep,
                        (const uint32_t*)wave_cnt, recs, cap);
+}
+}  // namespace madsim_k
+extern "C" void madsim_k_launch_collect(const madsim_result_t* out, uint64_t count, uint64_t seed0, uint32_t list_runner,
+                                        unsigned long long* rep, uint32_t* wave_cnt, madsim_failure_t* recs, uint64_t cap, void* stream) {
+    madsim_k::launch_collect(out, count, madsim_k::RangeSeeds{seed0}, list_runner, rep, wave_cnt, recs, cap, stream);
+}
+extern "C" void madsim_k_launch_collect_list(const madsim_result_t* out, uint64_t count, const uint64_t* d_seeds, uint32_t list_runner,
+                                             unsigned long long* rep, uint32_t* wave_cnt, madsim_failure_t* recs, uint64_t cap, void* stream) {
+    madsim_k::launch_collect(out, count, madsim_k::ListSeeds{d_seeds}, list_runner, rep, wave_cnt, recs, cap, stream);
 }
 
 // srep: MADSIM_K_STATS_WORDS words, all zero (prepared by the caller on `stream`); cand: MADSIM_K_STATS_CAND_WORDS words of scratch, untouched
 // when top_k == 0; count < 2^32 - 1
-extern "C" void madsim_k_launch_stats(const madsim_result_t* out, uint64_t count, uint64_t seed0, uint32_t include, uint32_t top_k,
-                                      unsigned long long* srep, unsigned long long* cand, void* stream) {
+namespace madsim_k {
+template <class Seeds>
+static void launch_stats(const madsim_result_t* out, uint64_t count, Seeds src, uint32_t include, uint32_t top_k,
+                         unsigned long long* srep, unsigned long long* cand, void* stream) {
     static_assert(MADSIM_K_STATS_WORDS == 17 + MADSIM_STAT_METRICS * MADSIM_STAT_BUCKETS / 2 + MADSIM_STAT_METRICS * MADSIM_STAT_MAX_TOP * 2, "sim_kernel.h");
     static_assert(MADSIM_K_STATS_CAND_WORDS == MADSIM_STAT_METRICS * madsim_k::STAT_WGS * madsim_k::STAT_TOP * 2, "sim_kernel.h");
     static_assert(MADSIM_STAT_BUCKETS == 256 && MADSIM_STAT_METRICS == 4 && MADSIM_STAT_MAX_TOP == 16, "one bucket per thread, one metric per wave");
@@ -701,14 +741,25 @@ extern "C" void madsim_k_launch_stats(const madsim_result_t* out, uint64_t count
     uint32_t* const ghist = reinterpret_cast<uint32_t*>(srep + 17);
     hipLaunchKernelGGL(madsim_k::stats_fold_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, out, count, piece, include, top_k, srep, ghist, cand);
     if (top_k)
-        hipLaunchKernelGGL(madsim_k::stats_top_kernel, dim3(MADSIM_STAT_METRICS), dim3(256), 0, (hipStream_t)stream, (const unsigned long long*)cand, grid,
-                           top_k, seed0, srep + 17 + MADSIM_STAT_METRICS * MADSIM_STAT_BUCKETS / 2);
+        hipLaunchKernelGGL((stats_top_kernel<Seeds>), dim3(MADSIM_STAT_METRICS), dim3(256), 0, (hipStream_t)stream, (const unsigned long long*)cand, grid,
+                           top_k, src, srep + 17 + MADSIM_STAT_METRICS * MADSIM_STAT_BUCKETS / 2);
+}
+}  // namespace madsim_k
+extern "C" void madsim_k_launch_stats(const madsim_result_t* out, uint64_t count, uint64_t seed0, uint32_t include, uint32_t top_k,
+                                      unsigned long long* srep, unsigned long long* cand, void* stream) {
+    madsim_k::launch_stats(out, count, madsim_k::RangeSeeds{seed0}, include, top_k, srep, cand, stream);
+}
+extern "C" void madsim_k_launch_stats_list(const madsim_result_t* out, uint64_t count, const uint64_t* d_seeds, uint32_t include, uint32_t top_k,
+                                           unsigned long long* srep, unsigned long long* cand, void* stream) {
+    madsim_k::launch_stats(out, count, madsim_k::ListSeeds{d_seeds}, include, top_k, srep, cand, stream);
 }
 
 // table: `slots` zeroed slots; list: `count` words of scratch; grep: MADSIM_K_GROUP_WORDS zeroed words; entries: room for `count` (sim_kernel.h).
 // Returns 0, or -1 (nothing launched) for sizes the kernels are not written for.
-extern "C" int madsim_k_launch_groups(const madsim_result_t* out, uint64_t count, uint64_t seed0, uint32_t include, uint32_t key_field, uint32_t* table,
-                                      uint64_t slots, uint32_t* list, unsigned long long* grep, madsim_group_t* entries, void* stream) {
+namespace madsim_k {
+template <class Seeds>
+static int launch_groups(const madsim_result_t* out, uint64_t count, Seeds src, uint32_t include, uint32_t key_field, uint32_t* table,
+                         uint64_t slots, uint32_t* list, unsigned long long* grep, madsim_group_t* entries, void* stream) {
     static_assert(sizeof(madsim_group_t) == 32 && sizeof(uint4) == MADSIM_K_GROUP_SLOT_BYTES && sizeof(madsim_result_t) == 48, "record layout");
     static_assert(MADSIM_K_GROUP_MAX_COUNT == MADSIM_GROUP_MAX_BATCH && MADSIM_GROUP_KEYS == 6, "sim_kernel.h");
     static const uint32_t key_words[MADSIM_GROUP_KEYS] = {5, 4, 2, 1, 3, 0};      // obs_hash, trace_hash, msg_count, clock_ns, rng_calls; steps
@@ -721,15 +772,28 @@ extern "C" int madsim_k_launch_groups(const madsim_result_t* out, uint64_t count
                        key_words[key_field], reinterpret_cast<uint4*>(table), (uint32_t)(slots - 1), list, grep);
     uint32_t xgrid = (uint32_t)((count + 255) / 256);      // the extraction pass: as many threads as there can be groups, 64 workgroups at most
     if (xgrid > 64) xgrid = 64;
-    hipLaunchKernelGGL(madsim_k::group_extract_kernel, dim3(xgrid), dim3(256), 0, (hipStream_t)stream, out, (uint32_t)count, seed0, key_words[key_field],
+    hipLaunchKernelGGL((group_extract_kernel<Seeds>), dim3(xgrid), dim3(256), 0, (hipStream_t)stream, out, (uint32_t)count, src, key_words[key_field],
                        reinterpret_cast<uint4*>(table), (uint32_t)(slots - 1), (const uint32_t*)list, grep, entries);
     return 0;
+}
+}  // namespace madsim_k
+extern "C" int madsim_k_launch_groups(const madsim_result_t* out, uint64_t count, uint64_t seed0, uint32_t include, uint32_t key_field, uint32_t* table,
+                                      uint64_t slots, uint32_t* list, unsigned long long* grep, madsim_group_t* entries, void* stream) {
+    return madsim_k::launch_groups(out, count, madsim_k::RangeSeeds{seed0}, include, key_field, table, slots, list, grep, entries, stream);
+}
+extern "C" int madsim_k_launch_groups_list(const madsim_result_t* out, uint64_t count, const uint64_t* d_seeds, uint32_t include, uint32_t key_field,
+                                           uint32_t* table, uint64_t slots, uint32_t* list, unsigned long long* grep, madsim_group_t* entries,
+                                           void* stream) {
+    if (!d_seeds) return -1;
+    return madsim_k::launch_groups(out, count, madsim_k::ListSeeds{d_seeds}, include, key_field, table, slots, list, grep, entries, stream);
 }
 
 // words: MADSIM_K_DIFF_WORDS zeroed words; wave_cnt: MADSIM_K_COLLECT_WAVES words; recs: `cap` records (may be null when cap == 0); all prepared by
 // the caller on `stream` (sim_kernel.h).  Returns 0, or -1 (nothing launched) for arguments the kernels are not written for.
-extern "C" int madsim_k_launch_diff(const madsim_result_t* a, const madsim_result_t* b, uint64_t count, uint64_t seed0, uint32_t fields,
-                                    unsigned long long* words, uint32_t* wave_cnt, madsim_diff_record_t* recs, uint64_t cap, void* stream) {
+namespace madsim_k {
+template <class Seeds>
+static int launch_diff(const madsim_result_t* a, const madsim_result_t* b, uint64_t count, Seeds src, uint32_t fields,
+                       unsigned long long* words, uint32_t* wave_cnt, madsim_diff_record_t* recs, uint64_t cap, void* stream) {
     static_assert(sizeof(madsim_diff_record_t) == 104 && sizeof(madsim_result_t) == 48, "record layout");
     static_assert(MADSIM_K_DIFF_WORDS == 2 + 8 + 64 && MADSIM_DIFF_FIELDS == 7 && MADSIM_DIFF_ALL == (1u << MADSIM_DIFF_FIELDS) - 1, "sim_kernel.h");
     if (count == 0 || count >= (1ull << 32) || fields == 0 || (fields & ~MADSIM_DIFF_ALL) || (cap && !recs)) return -1;
@@ -737,24 +801,47 @@ extern "C" int madsim_k_launch_diff(const madsim_result_t* a, const madsim_resul
     if (grid > 256) grid = 256;
     const uint64_t waves = 4ull * grid, piece = ((count + waves - 1) / waves + 63) / 64 * 64;
     hipLaunchKernelGGL(madsim_k::diff_count_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, a, b, count, piece, fields, words, wave_cnt);
-    hipLaunchKernelGGL(madsim_k::diff_write_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, a, b, count, seed0, piece, fields, words,
+    hipLaunchKernelGGL((diff_write_kernel<Seeds>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a, b, count, src, piece, fields, words,
                        (const uint32_t*)wave_cnt, recs, cap);
     return 0;
+}
+}  // namespace madsim_k
+extern "C" int madsim_k_launch_diff(const madsim_result_t* a, const madsim_result_t* b, uint64_t count, uint64_t seed0, uint32_t fields,
+                                    unsigned long long* words, uint32_t* wave_cnt, madsim_diff_record_t* recs, uint64_t cap, void* stream) {
+    return madsim_k::launch_diff(a, b, count, madsim_k::RangeSeeds{seed0}, fields, words, wave_cnt, recs, cap, stream);
+}
+extern "C" int madsim_k_launch_diff_list(const madsim_result_t* a, const madsim_result_t* b, uint64_t count, const uint64_t* d_seeds, uint32_t fields,
+                                         unsigned long long* words, uint32_t* wave_cnt, madsim_diff_record_t* recs, uint64_t cap, void* stream) {
+    if (!d_seeds) return -1;
+    return madsim_k::launch_diff(a, b, count, madsim_k::ListSeeds{d_seeds}, fields, words, wave_cnt, recs, cap, stream);
 }
 
 // wave_cnt: MADSIM_K_RESOLVE_WAVES words of scratch; total: one word; seeds / idx: room for `count` entries each, the first *total written
 // (sim_kernel.h).  Returns 0, or -1 (nothing launched) for count == 0 or count >= 2^32.
-extern "C" int madsim_k_launch_resolve_list(const madsim_result_t* out, uint64_t count, uint64_t seed0, uint32_t steps_maxed, uint32_t* wave_cnt,
-                                            uint32_t* total, uint64_t* seeds, uint32_t* idx, void* stream) {
+namespace madsim_k {
+template <class Seeds>
+static int launch_resolve_list(const madsim_result_t* out, uint64_t count, Seeds src, uint32_t steps_maxed, uint32_t* wave_cnt,
+                               uint32_t* total, uint64_t* seeds, uint32_t* idx, void* stream) {
     static_assert(madsim_k::COLLECT_MAX_WAVES == MADSIM_K_RESOLVE_WAVES && sizeof(madsim_result_t) == 48, "sim_kernel.h");
     if (count == 0 || count >= (1ull << 32)) return -1;
     uint32_t grid = (uint32_t)((count + 1023) / 1024);     // collect's cut
     if (grid > 256) grid = 256;
     const uint64_t waves = 4ull * grid, piece = ((count + waves - 1) / waves + 63) / 64 * 64;
     hipLaunchKernelGGL(madsim_k::resolve_count_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, out, count, piece, steps_maxed ? 1u : 0u, wave_cnt);
-    hipLaunchKernelGGL(madsim_k::resolve_write_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, out, count, seed0, piece, steps_maxed ? 1u : 0u,
+    hipLaunchKernelGGL((resolve_write_kernel<Seeds>), dim3(grid), dim3(256), 0, (hipStream_t)stream, out, count, src, piece, steps_maxed ? 1u : 0u,
                        (const uint32_t*)wave_cnt, (uint32_t)waves, total, seeds, idx);
     return 0;
+}
+}  // namespace madsim_k
+extern "C" int madsim_k_launch_resolve_list(const madsim_result_t* out, uint64_t count, uint64_t seed0, uint32_t steps_maxed, uint32_t* wave_cnt,
+                                            uint32_t* total, uint64_t* seeds, uint32_t* idx, void* stream) {
+    return madsim_k::launch_resolve_list(out, count, madsim_k::RangeSeeds{seed0}, steps_maxed, wave_cnt, total, seeds, idx, stream);
+}
+// d_seeds: the batch's slice of a seed list, `count` entries; it must not overlap `seeds`, which receives d_seeds[i] of the re-runnable results
+extern "C" int madsim_k_launch_resolve_list_list(const madsim_result_t* out, uint64_t count, const uint64_t* d_seeds, uint32_t steps_maxed,
+                                                 uint32_t* wave_cnt, uint32_t* total, uint64_t* seeds, uint32_t* idx, void* stream) {
+    if (!d_seeds) return -1;
+    return madsim_k::launch_resolve_list(out, count, madsim_k::ListSeeds{d_seeds}, steps_maxed, wave_cnt, total, seeds, idx, stream);
 }
 
 // out: the batch's results; rerun: m results; idx: m distinct indices into `out`.  m == 0 launches nothing.  Returns 0, or -1 (nothing

@@ -13,6 +13,7 @@ module raises, loudly.
 """
 import ctypes as C
 import math
+import operator
 import os
 import sys
 import time
@@ -138,6 +139,16 @@ def lib():
         L.madsim_hip_trace_seeds.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), u64p, C.c_uint64, C.POINTER(A.Limits), C.c_void_p,
                                              C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.madsim_hip_ctx_trace_seeds.argtypes = [ctxp] + L.madsim_hip_trace_seeds.argtypes
+        # the list campaigns: (seeds, n) where the range forms take (seed0, total); collect, stats and groups in one entry point, each optional
+        L.madsim_hip_run_seeds_campaign.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), u64p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32,
+                                                    C.POINTER(A.Limits), C.POINTER(A.Campaign), C.POINTER(A.Collect), C.POINTER(A.Stats),
+                                                    C.POINTER(A.Groups)]
+        L.madsim_hip_ctx_run_seeds_campaign.argtypes = [ctxp] + L.madsim_hip_run_seeds_campaign.argtypes
+        L.madsim_hip_run_seeds_campaign_multi.argtypes = [C.POINTER(ctxp), C.c_int] + L.madsim_hip_run_seeds_campaign.argtypes
+        L.madsim_hip_run_seeds_campaign_diff.argtypes = side + side + [u64p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(A.Campaign),
+                                                                       C.POINTER(A.Campaign), C.POINTER(A.Diff)]
+        L.madsim_hip_ctx_run_seeds_campaign_diff.argtypes = [ctxp] + L.madsim_hip_run_seeds_campaign_diff.argtypes
+        L.madsim_hip_run_seeds_campaign_diff_multi.argtypes = [C.POINTER(ctxp), C.c_int] + L.madsim_hip_run_seeds_campaign_diff.argtypes
         L.madsim_hip_observe_seed.restype = C.c_int64
         L.madsim_hip_observe_seed.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), C.c_uint64, C.POINTER(A.Limits), C.c_void_p, C.c_uint64,
                                               C.POINTER(A.Result)]
@@ -648,6 +659,86 @@ def run_campaign_diff_resolved(workload, seed0, total, resolve=True, other=None,
         workload, other, config, other_config, limits, other_limits, fields, max_listed, stop_at_diffs, resolve, observe)
 
 
+def seed_list(seeds):
+    """`seeds=` of the list campaigns as the contiguous uint64 array the library reads: any integer sequence or ndarray, which must ascend
+    strictly.  A list that is unsorted or holds a duplicate is MadsimHipError — it is never sorted silently: pass numpy.unique(seeds)."""
+    if isinstance(seeds, np.ndarray):
+        a = seeds
+        if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
+            raise MadsimHipError(f"seeds: a one-dimensional array of integers, got shape {a.shape}, dtype {a.dtype}")
+        if a.size and a.dtype.kind == "i" and int(a.min()) < 0:
+            raise MadsimHipError("seeds: a seed is an unsigned 64-bit integer, got a negative one")
+    else:
+        try:
+            a = np.array([operator.index(x) for x in seeds], dtype=np.uint64)
+        except (OverflowError, TypeError, ValueError) as e:
+            raise MadsimHipError(f"seeds: integers in [0, 2^64): {e}") from None
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    bad = np.flatnonzero(a[:-1] >= a[1:]) if a.size > 1 else ()
+    if len(bad):
+        i = int(bad[0])
+        raise MadsimHipError(f"seeds must ascend strictly: seeds[{i}] = {int(a[i])} is not below seeds[{i + 1}] = {int(a[i + 1])}; "
+                             "a list campaign never sorts silently — pass numpy.unique(seeds) (sorted, duplicates dropped)")
+    return a
+
+
+def _seeds_ptr(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint64)) if a.size else None
+
+
+def _campaign_seeds(call, tracer, workload, cfg, lim, rep, collect, stats, groups, resolve, observe):
+    """Run `call(col, st, grp)` — one of the madsim_hip_*run_campaign_seeds* entry points with everything but its last three arguments bound —
+    with the parts asked for; the return shape is run_campaign_groups': (campaign[, failures, by_verdict][, CampaignStats][, CampaignGroups])."""
+    if observe and collect is None and groups is None:
+        raise MadsimHipError("run_campaign_seeds: observe= explains listed seeds or groups: it needs collect=K or groups=")
+    if groups is not None:
+        out = _campaign_groups(call, groups[0], groups[1], groups[2], collect, stats, rep)
+        return _observe_groups(tracer, workload, out, cfg, lim, observe, resolve) if observe else out
+    if stats is not None:
+        out = _campaign_stats(lambda col, st: call(col, st, None), stats[0], stats[1], collect, rep)
+    elif collect is not None:
+        out = (rep,) + _collecting(lambda col: call(col, None, None), collect)
+    else:
+        _check(call(None, None, None))
+        return rep
+    return out + (_observe_failures(tracer, workload, out[1], cfg, lim, observe, resolve),) if observe else out
+
+
+def run_campaign_seeds(workload, seeds, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None, collect=None, list_runner=False,
+                       stop_at_cap=False, stats=None, groups=None, stop_at_groups=False, resolve=None, observe=0):
+    """madsim_hip_run_seeds_campaign: every non-differential campaign form over the seeds you name instead of a range — the failing seeds
+    an earlier campaign listed, a regression corpus, the members of one failure mode.  `seeds`: any integer sequence or ndarray, STRICTLY
+    ASCENDING (seed_list: an unsorted list or a duplicate is MadsimHipError, never sorted silently); position i of the list takes the role of
+    seed0 + i, so seeds_run counts positions and every ordering rule of the range forms holds as worded.
+
+    collect=K, list_runner, stop_at_cap: as run_campaign; stats=(include, top_k): as run_campaign_stats' include= and top_k=;
+    groups=(include, key, max_groups), stop_at_groups: as run_campaign_groups; resolve: as everywhere.  Returns
+    (campaign[, failures, by_verdict][, CampaignStats][, CampaignGroups]) in run_campaign_groups' order — the bare Campaign when none is asked
+    for.  observe=cap: with groups=, CampaignGroups.observations as run_campaign_groups fills it; otherwise it needs collect=K and appends the
+    listed seeds' observation lists as the last element, as run_campaign does."""
+    arr = seed_list(seeds)                                       # (a list that does not ascend is refused before a device is looked for)
+    if _inited_device is None:
+        init(0)
+    cfg, lim, rep = config or A.Config.default(), limits or A.Limits(), A.Campaign()
+    flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap, stop_at_groups, resolve)
+    return _campaign_seeds(lambda col, st, grp: lib().madsim_hip_run_seeds_campaign(
+        workload.ref(), C.byref(cfg), _seeds_ptr(arr), len(arr), batch, in_flight, flags, C.byref(lim), C.byref(rep), col, st, grp),
+        _default_tracer, workload, cfg, lim, rep, collect, stats, groups, resolve, observe)
+
+
+def run_campaign_diff_seeds(workload, seeds, other=None, config=None, other_config=None, limits=None, other_limits=None, fields=A.DIFF_ALL,
+                            max_listed=0, stop_at_diffs=False, batch=0, in_flight=0, resolve=None, observe=0):
+    """madsim_hip_run_seeds_campaign_diff: run_campaign_diff over the seeds you name (`seeds` as run_campaign_seeds') — "did the fix fix all
+    of them?" over exactly the seeds that failed.  Returns (campaign A, campaign B, CampaignDiff); resolve / observe as
+    run_campaign_diff_resolved's."""
+    arr = seed_list(seeds)                                       # (a list that does not ascend is refused before a device is looked for)
+    if _inited_device is None:
+        init(0)
+    return _campaign_diff(lambda wa, ca, la, wb, cb, lb, flags, ra, rb, d: lib().madsim_hip_run_seeds_campaign_diff(
+        wa, ca, la, wb, cb, lb, _seeds_ptr(arr), len(arr), batch, in_flight, flags, ra, rb, d),
+        workload, other, config, other_config, limits, other_limits, fields, max_listed, stop_at_diffs, resolve, observe)
+
+
 def run_batch_device(workload, seed0, count, d_out_ptr, stream_ptr=0, config=None, limits=None, want_summary=True):
     """Device-resident entry point: results stay in HBM at `d_out_ptr` (48 B/seed)."""
     if _inited_device is None:
@@ -770,6 +861,25 @@ class Context:
             workload, other, config, other_config, limits, other_limits, fields, max_listed, stop_at_diffs, resolve, observe, self.trace_seeds)
 
 
+    def run_campaign_seeds(self, workload, seeds, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None, collect=None,
+                           list_runner=False, stop_at_cap=False, stats=None, groups=None, stop_at_groups=False, resolve=None, observe=0):
+        """runtime.run_campaign_seeds on this context (madsim_hip_ctx_run_seeds_campaign)."""
+        arr = seed_list(seeds)
+        cfg, lim, rep = config or A.Config.default(), limits or A.Limits(), A.Campaign()
+        flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap, stop_at_groups, resolve)
+        return _campaign_seeds(lambda col, st, grp: lib().madsim_hip_ctx_run_seeds_campaign(
+            self._h, workload.ref(), C.byref(cfg), _seeds_ptr(arr), len(arr), batch, in_flight, flags, C.byref(lim), C.byref(rep), col, st, grp),
+            self.trace_seeds, workload, cfg, lim, rep, collect, stats, groups, resolve, observe)
+
+    def run_campaign_diff_seeds(self, workload, seeds, other=None, config=None, other_config=None, limits=None, other_limits=None,
+                                fields=A.DIFF_ALL, max_listed=0, stop_at_diffs=False, batch=0, in_flight=0, resolve=None, observe=0):
+        """runtime.run_campaign_diff_seeds on this context (madsim_hip_ctx_run_seeds_campaign_diff)."""
+        arr = seed_list(seeds)
+        return _campaign_diff(lambda wa, ca, la, wb, cb, lb, flags, ra, rb, d: lib().madsim_hip_ctx_run_seeds_campaign_diff(
+            self._h, wa, ca, la, wb, cb, lb, _seeds_ptr(arr), len(arr), batch, in_flight, flags, ra, rb, d),
+            workload, other, config, other_config, limits, other_limits, fields, max_listed, stop_at_diffs, resolve, observe, self.trace_seeds)
+
+
 def run_batch_multi(contexts, workload, seed0, count, config=None, limits=None, max_rounds=5):
     """madsim_hip_run_batch_multi: one process, one host thread, the seed range sharded contiguously over `contexts`
     (all devices' kernels in flight together), runner verdicts re-run compacted, reports folded on the host."""
@@ -832,6 +942,29 @@ def run_campaign_diff_multi(contexts, workload, seed0, total, other=None, config
     arr = (C.c_void_p * len(contexts))(*[c._h for c in contexts])
     return _campaign_diff(lambda wa, ca, la, wb, cb, lb, flags, ra, rb, d: lib().madsim_hip_run_campaign_diff_multi(
         arr, len(contexts), wa, ca, la, wb, cb, lb, seed0, total, batch, in_flight, flags, ra, rb, d),
+        workload, other, config, other_config, limits, other_limits, fields, max_listed, stop_at_diffs, resolve)
+
+
+def run_campaign_seeds_multi(contexts, workload, seeds, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None, collect=None,
+                             list_runner=False, stop_at_cap=False, stats=None, groups=None, stop_at_groups=False, resolve=None):
+    """madsim_hip_run_seeds_campaign_multi: run_campaign_seeds over several contexts (batch k of the list on context k % n); the reports are
+    the ones a single context gives."""
+    seeds_arr = seed_list(seeds)
+    cfg, lim, rep = config or A.Config.default(), limits or A.Limits(), A.Campaign()
+    arr = (C.c_void_p * len(contexts))(*[c._h for c in contexts])
+    flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap, stop_at_groups, resolve)
+    return _campaign_seeds(lambda col, st, grp: lib().madsim_hip_run_seeds_campaign_multi(
+        arr, len(contexts), workload.ref(), C.byref(cfg), _seeds_ptr(seeds_arr), len(seeds_arr), batch, in_flight, flags, C.byref(lim),
+        C.byref(rep), col, st, grp), None, workload, cfg, lim, rep, collect, stats, groups, resolve, 0)
+
+
+def run_campaign_diff_seeds_multi(contexts, workload, seeds, other=None, config=None, other_config=None, limits=None, other_limits=None,
+                                  fields=A.DIFF_ALL, max_listed=0, stop_at_diffs=False, batch=0, in_flight=0, resolve=None):
+    """madsim_hip_run_seeds_campaign_diff_multi: run_campaign_diff_seeds over several contexts; the report is the one a single context gives."""
+    seeds_arr = seed_list(seeds)
+    arr = (C.c_void_p * len(contexts))(*[c._h for c in contexts])
+    return _campaign_diff(lambda wa, ca, la, wb, cb, lb, flags, ra, rb, d: lib().madsim_hip_run_seeds_campaign_diff_multi(
+        arr, len(contexts), wa, ca, la, wb, cb, lb, _seeds_ptr(seeds_arr), len(seeds_arr), batch, in_flight, flags, ra, rb, d),
         workload, other, config, other_config, limits, other_limits, fields, max_listed, stop_at_diffs, resolve)
 
 
