@@ -210,6 +210,18 @@ pub struct SeedTrace {
     pub log_len: u64,
 }
 
+/// Where the two runs of one seed part (`Builder::diverge_seeds`): `rec`, the record as the library gives it — per channel (determinism log,
+/// observations) a `MADSIM_DIVERGE_*` status, the length of the common prefix that was established, the true lengths, each side's entry
+/// there, and both results —; `shared`, the observations both runs made just before `rec.obs_at`; `next_a` / `next_b`, what each side
+/// observed from there on (each at most `window` values).
+#[derive(Clone, Debug)]
+pub struct Divergence {
+    pub rec: sys::madsim_divergence_t,
+    pub shared: Vec<u64>,
+    pub next_a: Vec<u64>,
+    pub next_b: Vec<u64>,
+}
+
 /// The `obs_hash` of a run that traced `values`, in that order: 64-bit FNV-1a over whole values (the offset basis for none).
 pub fn fold_observations(values: &[u64]) -> u64 {
     values.iter().fold(0xCBF2_9CE4_8422_2325u64, |h, v| (h ^ v).wrapping_mul(0x100_0000_01B3))
@@ -361,6 +373,82 @@ impl Builder {
             idx = again;
         }
         Ok(traces)
+    }
+
+    /// Where the two runs of each of `seeds` part (`madsim_hip_ctx_diverge_seeds`): this builder's run of `workload` (side A) against
+    /// `other`'s run of `other_workload` (side B), compared on the device on the determinism log and on the observations — per seed the
+    /// record, the up to `window` observations both runs made just before they part and the up to `window` each side made from there on.
+    /// No row travels to the host.  With `resolve_runner` set, seeds that come back incomparable with a re-runnable runner verdict on
+    /// either side are replayed in one further call per round, each side under its own `madsim_hip_grow_limits(.., r)`.
+    pub fn diverge_seeds(&self, workload: &Workload, other: &Builder, other_workload: &Workload, seeds: &[u64], log_cap: usize, obs_cap: usize,
+                         window: u32) -> Result<Vec<Divergence>, RunError> {
+        let (wa, wb) = (workload.raw(), other_workload.raw());
+        let (ca, cb) = (self.config.raw(), other.config.raw());
+        let (la0, lb0) = (self.raw_limits(true), other.raw_limits(true));
+        let ctx = contexts()?.0[0];
+        let win = window as usize;
+        let mut out: Vec<Divergence> =
+            seeds.iter().map(|_| Divergence { rec: unsafe { std::mem::zeroed() }, shared: Vec::new(), next_a: Vec::new(), next_b: Vec::new() }).collect();
+        let mut idx: Vec<usize> = (0..seeds.len()).collect();
+        let rounds = if self.resolve_flags & sys::MADSIM_CAMPAIGN_RESOLVE == 0 {
+            0
+        } else {
+            match (self.resolve_flags & sys::MADSIM_CAMPAIGN_RESOLVE_ROUNDS_MASK) >> sys::MADSIM_CAMPAIGN_RESOLVE_ROUNDS_SHIFT {
+                0 => sys::MADSIM_RESOLVE_DEFAULT_ROUNDS,
+                r => r,
+            }
+        };
+        let rerunnable = |x: &sys::madsim_result_t, lim: &sys::madsim_limits_t| {
+            let cap = if lim.max_steps != 0 { lim.max_steps } else { 1 << 24 };
+            let ceiling = if lim.max_steps_ceiling != 0 { lim.max_steps_ceiling } else { 1 << 28 };
+            x.verdict == sys::MADSIM_OVERFLOW || (x.verdict == sys::MADSIM_STEP_LIMIT && cap < ceiling)
+        };
+        for r in 0..=rounds {
+            if idx.is_empty() {
+                break;
+            }
+            let (mut la, mut lb) = (la0, lb0);
+            if r > 0 {
+                for rc in [unsafe { sys::madsim_hip_grow_limits(&wa, &la0, r, &mut la) }, unsafe { sys::madsim_hip_grow_limits(&wb, &lb0, r, &mut lb) }] {
+                    if rc != 0 {
+                        return Err(last_error(rc));
+                    }
+                }
+            }
+            let m = idx.len();
+            let s: Vec<u64> = idx.iter().map(|&i| seeds[i]).collect();
+            let mut recs: Vec<sys::madsim_divergence_t> = vec![unsafe { std::mem::zeroed() }; m];
+            let mut rows = vec![0u64; m * 3 * win];
+            let rc = unsafe {
+                sys::madsim_hip_ctx_diverge_seeds(ctx, &wa, &ca, &la, &wb, &cb, &lb, s.as_ptr(), m as u64, log_cap as u64, obs_cap as u64, window,
+                                                  recs.as_mut_ptr(), if win > 0 { rows.as_mut_ptr() } else { std::ptr::null_mut() })
+            };
+            if rc != 0 {
+                return Err(last_error(rc));
+            }
+            let mut again = Vec::new();
+            for (j, &i) in idx.iter().enumerate() {
+                let rec = recs[j];
+                let d = &mut out[i];
+                d.rec = rec;
+                d.shared.clear();
+                d.next_a.clear();
+                d.next_b.clear();
+                if rec.obs_status != sys::MADSIM_DIVERGE_INCOMPARABLE {
+                    let row = &rows[j * 3 * win..(j + 1) * 3 * win];
+                    let at = rec.obs_at as usize;
+                    let (ka, kb) = ((rec.obs_len_a as usize).min(obs_cap), (rec.obs_len_b as usize).min(obs_cap));
+                    d.shared = row[win - at.min(win)..win].to_vec();
+                    d.next_a = row[win..win + ka.saturating_sub(at).min(win)].to_vec();
+                    d.next_b = row[2 * win..2 * win + kb.saturating_sub(at).min(win)].to_vec();
+                }
+                if rerunnable(&rec.a, &la) || rerunnable(&rec.b, &lb) {
+                    again.push(i);
+                }
+            }
+            idx = again;
+        }
+        Ok(out)
     }
 
     /// What one seed traced, and its result: the values in execution order (at most 65 536 of them).  A failing `run_workload` names

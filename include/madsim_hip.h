@@ -604,6 +604,50 @@ int madsim_hip_trace_seeds(const madsim_workload_t* w, const madsim_config_t* cf
 int64_t madsim_hip_observe_seed(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed,
                                 const madsim_limits_t* lim, uint64_t* obs, uint64_t cap, madsim_result_t* out);
 
+/* Divergence reports: where two variants of a seed's run first part.  A differential campaign says WHICH seeds a change affected;
+ * madsim_hip_diverge_seeds says UP TO WHERE the two runs of each listed seed are the same run, on two rulers: the determinism log (one
+ * byte per GlobalRng::with, "channel log") and the observation log (one 64-bit word per traced value, "channel obs").  Side A is
+ * (wA, cfgA, limA), side B (wB, cfgB, limB); any of B's pointers may equal A's.  Seeds in any order, duplicates allowed; recs[i] belongs
+ * to seeds[i].  One call = side A's trace launch, side B's, one compare kernel over the rows where they lie on the device, one copy of the
+ * records and one of the context rows, one synchronisation: no log or observation row travels to the host.
+ *
+ * Per channel, with L = min(len_a, len_b) and m = min(L, cap), `at` is the length of the common prefix that was established:
+ *   MADSIM_DIVERGE_INCOMPARABLE  either side's verdict is a runner verdict (MADSIM_IS_RUNNER_VERDICT): rows not meaningful, not read   at = 0
+ *   MADSIM_DIVERGE_DIFFER        there is a smallest i < m with a[i] != b[i]                                                           at = i
+ *   MADSIM_DIVERGE_SAME          no such i, L <= cap, len_a == len_b                                                                   at = len
+ *   MADSIM_DIVERGE_PREFIX        no such i, L <= cap, len_a != len_b: one run ended where the other went on                            at = L
+ *   MADSIM_DIVERGE_BEYOND_CAP    no such i, L > cap: nothing differs in what was kept                                                  at = cap
+ * log_a / log_b / obs_a / obs_b: side X's entry at index `at` when at < min(len_x, cap), else 0 (always 0 under SAME and INCOMPARABLE).
+ * obs_ctx row i, 3 * win words: the shared observations [obs_at - win, obs_at), right-aligned and zero-filled on the left; then A's
+ * [obs_at, obs_at + win) and B's, each cut at min(obs_len_x, obs_cap) and zero-filled; all zeros under INCOMPARABLE.
+ * The call does not re-run seeds: replay INCOMPARABLE ones under madsim_hip_grow_limits.  a / b: the 48 bytes madsim_hip_trace_seeds gives
+ * (trace_hash = 0 under that side's no_trace_hash).  n == 0 returns 0 and touches nothing.
+ * MADSIM_E_ARG: seeds or recs NULL with n > 0; win > MADSIM_DIVERGE_MAX_WIN; obs_ctx given with win == 0, or missing with win > 0; win > 0
+ * with obs_cap == 0; a workload or configuration either side's validation refuses ("side A: ..." / "side B: ...").
+ * MADSIM_E_LIMITS: n * (2 * (log_cap + 8 * obs_cap + 72) + 184 + 24 * win) exceeds MADSIM_TRACE_MAX_BYTES; never split. */
+#define MADSIM_DIVERGE_SAME         0u
+#define MADSIM_DIVERGE_DIFFER       1u
+#define MADSIM_DIVERGE_PREFIX       2u
+#define MADSIM_DIVERGE_BEYOND_CAP   3u
+#define MADSIM_DIVERGE_INCOMPARABLE 4u
+#define MADSIM_DIVERGE_MAX_WIN      8u
+/* (two statements, as madsim_diff_record below: the record holds madsim_result_t by value) */
+struct madsim_divergence {
+    uint64_t seed;
+    uint32_t log_status, obs_status;   /* MADSIM_DIVERGE_*                                                                        */
+    uint64_t log_at, obs_at;           /* entries of common prefix established                                                    */
+    uint64_t log_len_a, log_len_b, obs_len_a, obs_len_b;      /* the true lengths, which may exceed the caps                     */
+    uint64_t obs_a, obs_b;             /* each side's observation at obs_at, or 0                                                 */
+    uint8_t  log_a, log_b;             /* each side's log byte at log_at, or 0                                                    */
+    uint8_t  pad[6];                   /* 0                                                                                       */
+    madsim_result_t a, b;
+};                                     /* 184 bytes */
+typedef struct madsim_divergence madsim_divergence_t;
+int madsim_hip_diverge_seeds(const madsim_workload_t* wA, const madsim_config_t* cfgA, const madsim_limits_t* limA,
+                             const madsim_workload_t* wB, const madsim_config_t* cfgB, const madsim_limits_t* limB,
+                             const uint64_t* seeds, uint64_t n, uint64_t log_cap, uint64_t obs_cap, uint32_t win,
+                             madsim_divergence_t* recs, uint64_t* obs_ctx);
+
 /* The same entry points on an explicit context (see "Per-device contexts" above). */
 int madsim_hip_ctx_run_batch(madsim_hip_ctx_t* ctx, const madsim_workload_t* w, const madsim_config_t* cfg,
                              uint64_t seed0, uint64_t count, const madsim_limits_t* lim,
@@ -627,6 +671,10 @@ int madsim_hip_ctx_trace_seeds(madsim_hip_ctx_t* ctx, const madsim_workload_t* w
 int64_t madsim_hip_ctx_observe_seed(madsim_hip_ctx_t* ctx, const madsim_workload_t* w, const madsim_config_t* cfg,
                                     uint64_t seed, const madsim_limits_t* lim, uint64_t* obs, uint64_t cap,
                                     madsim_result_t* out);
+int madsim_hip_ctx_diverge_seeds(madsim_hip_ctx_t* ctx, const madsim_workload_t* wA, const madsim_config_t* cfgA,
+                                 const madsim_limits_t* limA, const madsim_workload_t* wB, const madsim_config_t* cfgB,
+                                 const madsim_limits_t* limB, const uint64_t* seeds, uint64_t n, uint64_t log_cap,
+                                 uint64_t obs_cap, uint32_t win, madsim_divergence_t* recs, uint64_t* obs_ctx);
 
 /* One process, several GPUs: the whole seed loop of Builder::run (builder.rs:129-150, every seed driven from one
  * process) over `n_ctx` contexts, each on its own GPU (or, for tests on a 1-GPU box, several on the same one).

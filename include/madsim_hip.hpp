@@ -780,6 +780,63 @@ struct Builder {
         return diff_against(other, wl, wl, fields, max_listed);           // one test body under two configurations
     }
 
+    // Where the two runs part: this builder's run of `wl` (side A) against `other`'s run of `other_wl` (side B) over `seeds` (any order,
+    // duplicates allowed), compared on the device on the determinism log and on the observations (madsim_hip_diverge_seeds): per seed the
+    // record, the up to `window` observations both runs made just before they part, and the up to `window` each side made from there on.
+    // No row travels to the host.  This builder's resolve_runner() rounds apply: seeds that come back incomparable with a re-runnable
+    // runner verdict on either side are replayed in one further call per round, each side under its own madsim_hip_grow_limits(.., r).
+    struct Divergence {
+        madsim_divergence_t rec{};
+        std::vector<uint64_t> shared, next_a, next_b;
+    };
+    std::vector<Divergence> diverge_against(const Builder& other, const std::vector<uint64_t>& seeds, const Workload& wl, const Workload& other_wl,
+                                            size_t log_cap = 65536, size_t obs_cap = 256, uint32_t window = 4) const {
+        madsim::check(madsim_hip_init(device));
+        madsim_workload_t wa = wl.raw(), wb = other_wl.raw();
+        madsim_config_t ca = config.raw(), cb = other.config.raw();
+        madsim_limits_t la0 = capacities, lb0 = other.capacities;
+        if (time_limit) { la0.time_limit_ns = (uint64_t)(*time_limit * 1e9 + 0.5); if (!la0.time_limit_ns) la0.time_limit_ns = 1; }
+        if (other.time_limit) { lb0.time_limit_ns = (uint64_t)(*other.time_limit * 1e9 + 0.5); if (!lb0.time_limit_ns) lb0.time_limit_ns = 1; }
+        std::vector<Divergence> out(seeds.size());
+        std::vector<size_t> idx(seeds.size());
+        for (size_t i = 0; i < idx.size(); i++) idx[i] = i;
+        uint32_t rounds = 0;
+        if (resolve_flags & MADSIM_CAMPAIGN_RESOLVE) {
+            rounds = (resolve_flags & MADSIM_CAMPAIGN_RESOLVE_ROUNDS_MASK) >> MADSIM_CAMPAIGN_RESOLVE_ROUNDS_SHIFT;
+            if (!rounds) rounds = MADSIM_RESOLVE_DEFAULT_ROUNDS;
+        }
+        for (uint32_t r = 0; r <= rounds && !idx.empty(); r++) {
+            madsim_limits_t la = la0, lb = lb0;
+            if (r) { madsim::check(madsim_hip_grow_limits(&wa, &la0, r, &la)); madsim::check(madsim_hip_grow_limits(&wb, &lb0, r, &lb)); }
+            const size_t m = idx.size();
+            std::vector<uint64_t> s(m), ctx(m * 3 * window);
+            std::vector<madsim_divergence_t> recs(m);
+            for (size_t j = 0; j < m; j++) s[j] = seeds[idx[j]];
+            madsim::check(madsim_hip_diverge_seeds(&wa, &ca, &la, &wb, &cb, &lb, s.data(), m, log_cap, obs_cap, window, recs.data(), window ? ctx.data() : nullptr));
+            std::vector<size_t> again;
+            auto rerunnable = [](const madsim_result_t& x, const madsim_limits_t& lim) {
+                const uint32_t cap = lim.max_steps ? lim.max_steps : 1u << 24, ceiling = lim.max_steps_ceiling ? lim.max_steps_ceiling : 1u << 28;
+                return x.verdict == MADSIM_OVERFLOW || (x.verdict == MADSIM_STEP_LIMIT && cap < ceiling);
+            };
+            for (size_t j = 0; j < m; j++) {
+                Divergence& d = out[idx[j]];
+                d.rec = recs[j];
+                d.shared.clear(); d.next_a.clear(); d.next_b.clear();
+                if (d.rec.obs_status != MADSIM_DIVERGE_INCOMPARABLE) {
+                    const uint64_t at = d.rec.obs_at, w = window;
+                    const uint64_t ka = std::min<uint64_t>(d.rec.obs_len_a, obs_cap), kb = std::min<uint64_t>(d.rec.obs_len_b, obs_cap);
+                    const uint64_t* row = ctx.data() + j * 3 * w;
+                    d.shared.assign(row + (w - std::min(at, w)), row + w);
+                    d.next_a.assign(row + w, row + w + (ka > at ? std::min(w, ka - at) : 0));
+                    d.next_b.assign(row + 2 * w, row + 2 * w + (kb > at ? std::min(w, kb - at) : 0));
+                }
+                if (rerunnable(recs[j].a, la) || rerunnable(recs[j].b, lb)) again.push_back(idx[j]);
+            }
+            idx.swap(again);
+        }
+        return out;
+    }
+
     // builder.rs:121-162: run seeds seed..seed+count; return on success, "panic" on the first failing seed.
     // Reports the numerically smallest failing seed (the reference reports the first to complete).
     std::vector<madsim_result_t> run(const Workload& wl) const {

@@ -239,6 +239,23 @@ HEADER_STRUCTS["madsim_resolve_t"] = Resolve
 TRACE_MAX_BYTES = 1 << 30     # madsim_hip_trace_seeds: device memory one call may ask for, n * (log_cap + 8 * obs_cap + 72)
 FNV_OFFSET, FNV_PRIME = 0xCBF29CE484222325, 0x100000001B3      # obs_hash / trace_hash: 64-bit FNV-1a over whole values
 
+# madsim_hip_diverge_seeds: the status of a channel (determinism log / observations) of one seed's two runs
+DIVERGE_SAME, DIVERGE_DIFFER, DIVERGE_PREFIX, DIVERGE_BEYOND_CAP, DIVERGE_INCOMPARABLE = range(5)
+DIVERGE_NAMES = ("same", "differ", "prefix", "beyond-cap", "incomparable")
+DIVERGE_MAX_WIN = 8
+
+
+class Divergence(C.Structure):
+    """madsim_divergence_t: where the two runs of one seed part, on both channels (declared in two statements in the header, as
+    madsim_diff_record_t: tests/test_diverge.py holds it against the header)."""
+    _fields_ = [("seed", C.c_uint64), ("log_status", C.c_uint32), ("obs_status", C.c_uint32), ("log_at", C.c_uint64), ("obs_at", C.c_uint64),
+                ("log_len_a", C.c_uint64), ("log_len_b", C.c_uint64), ("obs_len_a", C.c_uint64), ("obs_len_b", C.c_uint64),
+                ("obs_a", C.c_uint64), ("obs_b", C.c_uint64), ("log_a", C.c_uint8), ("log_b", C.c_uint8), ("pad", C.c_uint8 * 6),
+                ("a", Result), ("b", Result)]
+
+
+assert C.sizeof(Divergence) == 184
+
 
 class Geometry(C.Structure):
     _fields_ = [
@@ -271,6 +288,10 @@ FAILURE_DTYPE = [("seed", "<u8")] + RESULT_DTYPE
 assert C.sizeof(Failure) == 56 and C.sizeof(Collect) == 88
 # numpy view of a differential campaign's list: madsim_diff_record_t, the seed, then side A's result and side B's
 DIFF_RECORD_DTYPE = [("seed", "<u8"), ("a", RESULT_DTYPE), ("b", RESULT_DTYPE)]
+# numpy view of madsim_hip_diverge_seeds' records: madsim_divergence_t
+DIVERGENCE_DTYPE = [("seed", "<u8"), ("log_status", "<u4"), ("obs_status", "<u4"), ("log_at", "<u8"), ("obs_at", "<u8"), ("log_len_a", "<u8"),
+                    ("log_len_b", "<u8"), ("obs_len_a", "<u8"), ("obs_len_b", "<u8"), ("obs_a", "<u8"), ("obs_b", "<u8"), ("log_a", "u1"),
+                    ("log_b", "u1"), ("pad", "u1", (6,)), ("a", RESULT_DTYPE), ("b", RESULT_DTYPE)]
 # numpy view of a statistics campaign's extreme seeds: madsim_extreme_t
 EXTREME_DTYPE = [("value", "<u8"), ("seed", "<u8")]
 assert C.sizeof(Extreme) == 16 and C.sizeof(Metric) == 2080 and C.sizeof(Stats) == 32 + 4 * 2080

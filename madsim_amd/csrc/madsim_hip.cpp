@@ -127,6 +127,16 @@ struct madsim_hip_ctx {
     uint64_t* d_seeds = nullptr; size_t seeds_cap = 0;        // seed list of a compacted re-run
     // trace launches: the rows of the determinism log (bytes) and of the observation log (words), the length words (tlen_cap of them)
     uint8_t* d_tlog = nullptr; size_t tlog_cap = 0; uint64_t* d_olog = nullptr; size_t olog_cap = 0; uint64_t* d_tlen = nullptr; size_t tlen_cap = 0;
+    // divergence reports: side B's rows, length words and results, the records and the context rows
+    uint8_t* d_tlog_b = nullptr; size_t tlog_b_cap = 0; uint64_t* d_olog_b = nullptr; size_t olog_b_cap = 0; uint64_t* d_tlen_b = nullptr; size_t tlen_b_cap = 0;
+    madsim_result_t* d_out_b = nullptr; size_t out_b_cap = 0;
+    madsim_divergence_t* d_drec = nullptr; size_t drec_cap = 0; uint64_t* d_dctx = nullptr; size_t dctx_cap = 0;
+    // one side's buffers of a trace call, by reference: set 0 is what every trace call uses, set 1 side B of a divergence report
+    struct TraceSet { uint8_t*& log; size_t& log_have; uint64_t*& obs; size_t& obs_have; uint64_t*& len; size_t& len_have; madsim_result_t*& out; size_t& out_have; };
+    TraceSet trace_set(int side) {
+        return side ? TraceSet{d_tlog_b, tlog_b_cap, d_olog_b, olog_b_cap, d_tlen_b, tlen_b_cap, d_out_b, out_b_cap}
+                    : TraceSet{d_tlog, tlog_cap, d_olog, olog_cap, d_tlen, tlen_cap, d_out, out_cap};
+    }
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipEvent_t pipe_begin = nullptr;          // run_pipelined: before the first sub-batch of a call
     hipEvent_t tev[2 * 64] = {};              // timing slots of madsim_hip_run_batch_async
@@ -225,6 +235,12 @@ void madsim_hip_ctx::close() {
     if (d_tlog) (void)hipFree(d_tlog);
     if (d_olog) (void)hipFree(d_olog);
     if (d_tlen) (void)hipFree(d_tlen);
+    if (d_tlog_b) (void)hipFree(d_tlog_b);
+    if (d_olog_b) (void)hipFree(d_olog_b);
+    if (d_tlen_b) (void)hipFree(d_tlen_b);
+    if (d_out_b) (void)hipFree(d_out_b);
+    if (d_drec) (void)hipFree(d_drec);
+    if (d_dctx) (void)hipFree(d_dctx);
     if (d_prof) (void)hipFree(d_prof);
     if (ev0) (void)hipEventDestroy(ev0);
     if (ev1) (void)hipEventDestroy(ev1);
@@ -270,6 +286,8 @@ void madsim_hip_ctx::close() {
     }
     for (auto& e : tev) if (e) (void)hipEventDestroy(e);
     d_acc = nullptr; d_out = nullptr; d_seeds = nullptr; d_tlog = nullptr; d_olog = nullptr; d_tlen = nullptr; d_prof = nullptr;
+    d_tlog_b = nullptr; d_olog_b = nullptr; d_tlen_b = nullptr; d_out_b = nullptr; d_drec = nullptr; d_dctx = nullptr;
+    tlog_b_cap = olog_b_cap = tlen_b_cap = out_b_cap = drec_cap = dctx_cap = 0;
     ev0 = ev1 = nullptr; pipe_begin = nullptr; out_cap = seeds_cap = tlog_cap = olog_cap = tlen_cap = 0;
     for (auto& e : tev) e = nullptr;
     device = -1;
@@ -825,6 +843,17 @@ int run_pipelined_fwd(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workl
 }
 namespace {
 
+// a context buffer grown to `want` elements (never shrunk; the old contents are not kept)
+template <class T>
+hipError_t room(T*& d, size_t& have, size_t want) {
+    if (want <= have) return hipSuccess;
+    if (d) (void)hipFree(d);
+    d = nullptr; have = 0;
+    hipError_t e = hipMalloc((void**)&d, want * sizeof *d);
+    if (e == hipSuccess) have = want;
+    return e;
+}
+
 #define CTX_ENTER(c)                                                                              \
     if (!(c) || (c)->device < 0) return fail(MADSIM_E_NOINIT, "no context (madsim_hip_init / madsim_hip_ctx_create has not been called)"); \
     std::lock_guard<std::mutex> lk((c)->mu);                                                      \
@@ -980,6 +1009,52 @@ int madsim_hip_ctx_run_batch_auto(madsim_hip_ctx_t* c, const madsim_workload_t* 
     return 0;
 }
 
+// One side of a trace call.  trace_prepare: geometry, tables, scratch, the side's buffer set (madsim_hip_ctx::trace_set) grown to the call's
+// sizes and the parameter block filled — nothing is queued.  trace_queue: the set zeroed and the trace launch, behind whatever the stream
+// holds; TraceSteps keeps the first error and queues nothing behind it.  Shared by madsim_hip_trace_seeds, madsim_hip_trace_seed (side A's
+// set alone) and both sides of madsim_hip_diverge_seeds.
+struct TraceSteps {
+    hipError_t err = hipSuccess;
+    const char* at = nullptr;
+    bool no_build = false;
+    bool operator()(hipError_t e, const char* what) { if (e != hipSuccess && err == hipSuccess) { err = e; at = what; } return err == hipSuccess && !no_build; }
+};
+
+static int trace_prepare(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, const madsim_limits_t* lim, uint64_t n,
+                         uint64_t log_cap, uint64_t obs_cap, madsim_hip_ctx::TraceSet S, Geo& G, hipStream_t st) {
+    int rc;
+    if ((rc = madsim_geo::make_geometry(c->dev(), w, cfg, lim, n, &G, &g_err, true))) return rc;
+    G.P.count = n;
+    if ((rc = c->upload_workload(w, G.P))) return rc;
+    if ((rc = c->ensure_scratch(G.P, st, false))) return rc;
+    HIP_TRY(room(S.log, S.log_have, (size_t)(n * log_cap)));
+    HIP_TRY(room(S.obs, S.obs_have, (size_t)(n * obs_cap)));
+    HIP_TRY(room(S.len, S.len_have, (size_t)(2 * n)));                       // [n] log lengths, then [n] observation counts
+    HIP_TRY(room(c->d_seeds, c->seeds_cap, (size_t)n));
+    HIP_TRY(room(S.out, S.out_have, (size_t)n));
+    if (G.lds_bytes > c->lds_attr) {
+        if (madsim_k_set_max_lds((uint32_t)c->lds_per_cu)) return fail(MADSIM_E_HIP, "hipFuncSetAttribute failed");
+        c->lds_attr = (uint32_t)c->lds_per_cu;
+    }
+    G.P.seed0 = 0; G.P.count = n; G.P.seed_list = c->d_seeds; G.P.out = S.out;
+    G.P.trace_log = log_cap ? S.log : nullptr; G.P.trace_cap = log_cap; G.P.trace_len = S.len;
+    G.P.obs_log = obs_cap ? S.obs : nullptr; G.P.obs_cap = obs_cap; G.P.obs_len = S.len + n;
+    return 0;
+}
+
+static bool trace_queue(const Geo& G, madsim_hip_ctx::TraceSet S, uint64_t n, uint64_t log_cap, uint64_t obs_cap, bool zero_log, hipStream_t st,
+                        TraceSteps& step, bool ok) {
+    if (ok && log_cap && zero_log) ok = step(hipMemsetAsync(S.log, 0, n * log_cap, st), "hipMemsetAsync(log rows)");
+    if (ok && obs_cap) ok = step(hipMemsetAsync(S.obs, 0, n * obs_cap * sizeof(uint64_t), st), "hipMemsetAsync(observation rows)");
+    if (ok) ok = step(hipMemsetAsync(S.len, 0, 2 * n * sizeof(uint64_t), st), "hipMemsetAsync(lengths)");
+    if (ok) ok = step(hipMemsetAsync(S.out, 0, n * sizeof(madsim_result_t), st), "hipMemsetAsync(results)");
+    if (ok) {
+        step.no_build = madsim_k_launch_sim(&G.P, G.grid, G.lds_bytes, st, 1) != 0;
+        ok = step(step.no_build ? hipSuccess : hipGetLastError(), "trace kernel launch");
+    }
+    return ok;
+}
+
 // Replay a list of seeds on the trace build: one launch, unit i = seeds[i], each unit with its own row of the determinism log and of the
 // observation log and its own pair of length words (k_main.h).  The device buffers are zero before the launch, so a row comes back as its
 // first min(len, cap) entries and zeros; every output is one copy, and the call ends with one synchronisation of the stream it ran on.
@@ -1007,63 +1082,90 @@ static int trace_list(madsim_hip_ctx_t* c, const madsim_workload_t* w, const mad
     int rc = madsim_geo::validate(w, cfg, &g_err);
     if (rc) return rc;
     Geo G;
-    if ((rc = madsim_geo::make_geometry(c->dev(), w, cfg, lim, n, &G, &g_err, true))) return rc;
-    G.P.count = n;
-    if ((rc = c->upload_workload(w, G.P))) return rc;
     hipStream_t st = nullptr;
-    if ((rc = c->ensure_scratch(G.P, st, false))) return rc;
-    auto room = [](auto*& d, size_t& have, size_t want) -> hipError_t {       // (`want` in elements of *d)
-        if (want <= have) return hipSuccess;
-        if (d) (void)hipFree(d);
-        d = nullptr; have = 0;
-        hipError_t e = hipMalloc((void**)&d, want * sizeof *d);
-        if (e == hipSuccess) have = want;
-        return e;
-    };
-    HIP_TRY(room(c->d_tlog, c->tlog_cap, (size_t)(n * log_cap)));
-    HIP_TRY(room(c->d_olog, c->olog_cap, (size_t)(n * obs_cap)));
-    HIP_TRY(room(c->d_tlen, c->tlen_cap, (size_t)(2 * n)));                  // [n] log lengths, then [n] observation counts
-    HIP_TRY(room(c->d_seeds, c->seeds_cap, (size_t)n));
-    if ((rc = c->ensure_out((size_t)n))) return rc;
-    if (G.lds_bytes > c->lds_attr) {
-        if (madsim_k_set_max_lds((uint32_t)c->lds_per_cu)) return fail(MADSIM_E_HIP, "hipFuncSetAttribute failed");
-        c->lds_attr = (uint32_t)c->lds_per_cu;
-    }
-    uint64_t* d_olen = c->d_tlen + n;
-    G.P.seed0 = 0; G.P.count = n; G.P.seed_list = c->d_seeds; G.P.out = c->d_out;
-    G.P.trace_log = log_cap ? c->d_tlog : nullptr; G.P.trace_cap = log_cap; G.P.trace_len = c->d_tlen;
-    G.P.obs_log = obs_cap ? c->d_olog : nullptr; G.P.obs_cap = obs_cap; G.P.obs_len = d_olen;
+    const madsim_hip_ctx::TraceSet S = c->trace_set(0);
+    if ((rc = trace_prepare(c, w, cfg, lim, n, log_cap, obs_cap, S, G, st))) return rc;
+    uint64_t* d_olen = S.len + n;
     // from here on the stream may hold work on the caller's memory: every step is tried only while all before it succeeded, and the
     // synchronisation is reached whatever happened
-    hipError_t err = hipSuccess;
-    const char* at = nullptr;
-    bool no_build = false;
-    auto step = [&](hipError_t e, const char* what) { if (e != hipSuccess && err == hipSuccess) { err = e; at = what; } return err == hipSuccess && !no_build; };
+    TraceSteps step;
     uint64_t one_len = 0;                                                     // (`single`: the length is needed here, before the log is copied)
     bool ok = step(hipMemcpyAsync(c->d_seeds, seeds, n * sizeof(uint64_t), hipMemcpyHostToDevice, st), "hipMemcpyAsync(seeds)");
-    if (ok && log_cap && !single) ok = step(hipMemsetAsync(c->d_tlog, 0, n * log_cap, st), "hipMemsetAsync(log rows)");
-    if (ok && obs_cap) ok = step(hipMemsetAsync(c->d_olog, 0, n * obs_cap * sizeof(uint64_t), st), "hipMemsetAsync(observation rows)");
-    if (ok) ok = step(hipMemsetAsync(c->d_tlen, 0, 2 * n * sizeof(uint64_t), st), "hipMemsetAsync(lengths)");
-    if (ok) ok = step(hipMemsetAsync(c->d_out, 0, n * sizeof(madsim_result_t), st), "hipMemsetAsync(results)");
-    if (ok) {
-        no_build = madsim_k_launch_sim(&G.P, G.grid, G.lds_bytes, st, 1) != 0;
-        ok = step(no_build ? hipSuccess : hipGetLastError(), "trace kernel launch");
-    }
-    if (ok && logs && !single) ok = step(hipMemcpyAsync(logs, c->d_tlog, n * log_cap, hipMemcpyDeviceToHost, st), "hipMemcpyAsync(log rows)");
-    if (ok && obs) ok = step(hipMemcpyAsync(obs, c->d_olog, n * obs_cap * sizeof(uint64_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync(observation rows)");
-    if (ok && single) ok = step(hipMemcpyAsync(&one_len, c->d_tlen, sizeof one_len, hipMemcpyDeviceToHost, st), "hipMemcpyAsync(length)");
-    if (ok && log_len && !single) ok = step(hipMemcpyAsync(log_len, c->d_tlen, n * sizeof(uint64_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync(log lengths)");
+    ok = trace_queue(G, S, n, log_cap, obs_cap, !single, st, step, ok);
+    if (ok && logs && !single) ok = step(hipMemcpyAsync(logs, S.log, n * log_cap, hipMemcpyDeviceToHost, st), "hipMemcpyAsync(log rows)");
+    if (ok && obs) ok = step(hipMemcpyAsync(obs, S.obs, n * obs_cap * sizeof(uint64_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync(observation rows)");
+    if (ok && single) ok = step(hipMemcpyAsync(&one_len, S.len, sizeof one_len, hipMemcpyDeviceToHost, st), "hipMemcpyAsync(length)");
+    if (ok && log_len && !single) ok = step(hipMemcpyAsync(log_len, S.len, n * sizeof(uint64_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync(log lengths)");
     if (ok && obs_len) ok = step(hipMemcpyAsync(obs_len, d_olen, n * sizeof(uint64_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync(observation counts)");
-    if (ok && out) ok = step(hipMemcpyAsync(out, c->d_out, n * sizeof(madsim_result_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync(results)");
+    if (ok && out) ok = step(hipMemcpyAsync(out, S.out, n * sizeof(madsim_result_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync(results)");
     ok = step(hipStreamSynchronize(st), "hipStreamSynchronize");
-    if (err != hipSuccess) return fail(MADSIM_E_HIP, std::string(at) + ": " + hipGetErrorString(err));
-    if (no_build) return fail(MADSIM_E_LIMITS, "no trace kernel build");
+    if (step.err != hipSuccess) return fail(MADSIM_E_HIP, std::string(step.at) + ": " + hipGetErrorString(step.err));
+    if (step.no_build) return fail(MADSIM_E_LIMITS, "no trace kernel build");
     if (single) {
         if (log_len) *log_len = one_len;
-        if (logs && one_len) HIP_TRY(hipMemcpy(logs, c->d_tlog, (size_t)std::min(one_len, log_cap), hipMemcpyDeviceToHost));      // (synchronous)
+        if (logs && one_len) HIP_TRY(hipMemcpy(logs, S.log, (size_t)std::min(one_len, log_cap), hipMemcpyDeviceToHost));      // (synchronous)
     } else if (out && lim && lim->no_trace_hash) {
         for (uint64_t i = 0; i < n; i++) out[i].trace_hash = 0;
     }
+    return 0;
+}
+
+// Where two variants of a seed's run first part (include/madsim_hip.h): both sides' trace launches into the context's two buffer sets, the
+// compare kernel over them, one copy of the records and one of the context rows, one synchronisation — all on one stream; no row is copied.
+// Side B is prepared behind side A's queued launch, as a differential campaign's second side is: the tables of both workloads stay
+// uploaded (upload_workload's cache), and scratch that side B outgrows is only replaced once the stream has drained.  Until the final
+// copies nothing queued touches the caller's memory but the seed list, so an error of side B's preparation drains the stream and returns.
+int madsim_hip_ctx_diverge_seeds(madsim_hip_ctx_t* c, const madsim_workload_t* wA, const madsim_config_t* cfgA, const madsim_limits_t* limA,
+                                 const madsim_workload_t* wB, const madsim_config_t* cfgB, const madsim_limits_t* limB, const uint64_t* seeds,
+                                 uint64_t n, uint64_t log_cap, uint64_t obs_cap, uint32_t win, madsim_divergence_t* recs, uint64_t* obs_ctx) {
+    static_assert(sizeof(madsim_divergence_t) == 184, "record layout");
+    if (n == 0) return 0;
+    if (!seeds || !recs) return fail(MADSIM_E_ARG, "diverge_seeds: null seed list or record array");
+    if (win > MADSIM_DIVERGE_MAX_WIN) return fail(MADSIM_E_ARG, "diverge_seeds: win exceeds MADSIM_DIVERGE_MAX_WIN");
+    if ((obs_ctx != nullptr) != (win != 0)) return fail(MADSIM_E_ARG, "diverge_seeds: `obs_ctx` and win are given together or not at all");
+    if (win && !obs_cap) return fail(MADSIM_E_ARG, "diverge_seeds: a context window needs observation rows (obs_cap > 0)");
+    {
+        // what the call asks of the device, per seed: both sides' rows, length words, seed and result, the record and the context row
+        const uint64_t M = MADSIM_TRACE_MAX_BYTES;
+        const char* const msg = "diverge_seeds: n x (2 (log_cap + 8 obs_cap + 72) + 184 + 24 win) exceeds MADSIM_TRACE_MAX_BYTES: fewer seeds per call, or smaller caps";
+        if (log_cap > M || obs_cap > M / 8 || n > M) return fail(MADSIM_E_LIMITS, msg);
+        const uint64_t per_seed = 2 * (log_cap + 8 * obs_cap + 3 * sizeof(uint64_t) + sizeof(madsim_result_t)) + sizeof(madsim_divergence_t) + 24ull * win;
+        if (per_seed > M / n) return fail(MADSIM_E_LIMITS, msg);
+    }
+    if (madsim_geo::validate(wA, cfgA, &g_err)) return fail(MADSIM_E_ARG, "side A: " + g_err);      // (an argument error of this call, whatever validate calls it)
+    if (madsim_geo::validate(wB, cfgB, &g_err)) return fail(MADSIM_E_ARG, "side B: " + g_err);
+    CTX_ENTER(c);
+    int rc;
+    hipStream_t st = nullptr;
+    const madsim_hip_ctx::TraceSet SA = c->trace_set(0), SB = c->trace_set(1);
+    Geo GA, GB;
+    if ((rc = trace_prepare(c, wA, cfgA, limA, n, log_cap, obs_cap, SA, GA, st))) return fail(rc, "side A: " + g_err);
+    HIP_TRY(room(c->d_drec, c->drec_cap, (size_t)n));
+    HIP_TRY(room(c->d_dctx, c->dctx_cap, (size_t)(3ull * win * n)));
+    TraceSteps step;
+    bool ok = step(hipMemcpyAsync(c->d_seeds, seeds, n * sizeof(uint64_t), hipMemcpyHostToDevice, st), "hipMemcpyAsync(seeds)");
+    ok = trace_queue(GA, SA, n, log_cap, obs_cap, true, st, step, ok);
+    if (ok && (rc = trace_prepare(c, wB, cfgB, limB, n, log_cap, obs_cap, SB, GB, st))) {
+        const std::string why = "side B: " + g_err;
+        (void)hipStreamSynchronize(st);
+        return fail(rc, why);
+    }
+    ok = trace_queue(GB, SB, n, log_cap, obs_cap, true, st, step, ok);
+    if (ok) {
+        const int refused = madsim_k_launch_diverge(log_cap ? SA.log : nullptr, log_cap ? SB.log : nullptr, log_cap, obs_cap ? SA.obs : nullptr,
+                                                    obs_cap ? SB.obs : nullptr, obs_cap, SA.len, SB.len, SA.len + n, SB.len + n, SA.out, SB.out, c->d_seeds, n,
+                                                    win, c->d_drec, win ? c->d_dctx : nullptr, st);
+        if (refused) step.no_build = true;
+        ok = step(refused ? hipSuccess : hipGetLastError(), "diverge kernel launch");
+    }
+    if (ok) ok = step(hipMemcpyAsync(recs, c->d_drec, n * sizeof(madsim_divergence_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync(records)");
+    if (ok && win) ok = step(hipMemcpyAsync(obs_ctx, c->d_dctx, 3ull * win * n * sizeof(uint64_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync(context rows)");
+    ok = step(hipStreamSynchronize(st), "hipStreamSynchronize");
+    if (step.err != hipSuccess) return fail(MADSIM_E_HIP, std::string(step.at) + ": " + hipGetErrorString(step.err));
+    if (step.no_build) return fail(MADSIM_E_LIMITS, "no trace kernel build, or sizes the diverge kernel refuses");
+    const bool za = limA && limA->no_trace_hash, zb = limB && limB->no_trace_hash;
+    if (za || zb)
+        for (uint64_t i = 0; i < n; i++) { if (za) recs[i].a.trace_hash = 0; if (zb) recs[i].b.trace_hash = 0; }
     return 0;
 }
 
@@ -2023,6 +2125,13 @@ int64_t madsim_hip_observe_seed(const madsim_workload_t* w, const madsim_config_
                                 uint64_t* obs, uint64_t cap, madsim_result_t* out) {
     DefaultPin p;
     return madsim_hip_ctx_observe_seed(p.c, w, cfg, seed, lim, obs, cap, out);
+}
+
+int madsim_hip_diverge_seeds(const madsim_workload_t* wA, const madsim_config_t* cfgA, const madsim_limits_t* limA, const madsim_workload_t* wB,
+                             const madsim_config_t* cfgB, const madsim_limits_t* limB, const uint64_t* seeds, uint64_t n, uint64_t log_cap,
+                             uint64_t obs_cap, uint32_t win, madsim_divergence_t* recs, uint64_t* obs_ctx) {
+    DefaultPin p;
+    return madsim_hip_ctx_diverge_seeds(p.c, wA, cfgA, limA, wB, cfgB, limB, seeds, n, log_cap, obs_cap, win, recs, obs_ctx);
 }
 
 int madsim_hip_run_campaign(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total, uint64_t batch,

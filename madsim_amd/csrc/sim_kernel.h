@@ -399,6 +399,17 @@ int  madsim_k_launch_diff_list(const madsim_result_t* a, const madsim_result_t* 
                                unsigned long long* words, uint32_t* wave_cnt, madsim_diff_record_t* recs, uint64_t cap, void* stream);
 int  madsim_k_launch_resolve_list_list(const madsim_result_t* out, uint64_t count, const uint64_t* d_seeds, uint32_t steps_maxed, uint32_t* wave_cnt,
                                        uint32_t* total, uint64_t* seeds, uint32_t* idx, void* stream);
+// divergence reports (madsim_hip_diverge_seeds), behind the two sides' trace launches on the same stream: two sets of trace rows of the same
+// `n` seeds — log rows of `log_cap` bytes, observation rows of `obs_cap` words, 16-byte aligned arrays (null with a cap of 0), the TRUE
+// lengths (which may exceed the caps), the results and the seeds — compared where they lie.  recs[i]: the record of seed d_seeds[i], by the
+// status table in include/madsim_hip.h; ctx: n rows of 3 * win words (null iff win == 0).  A pure function of its inputs: nothing needs
+// preparing, every word of `recs` and `ctx` is written, nothing else is.  One wave per row pair, MADSIM_K_DIVERGE_WAVES waves at most.
+// Returns 0, or -1 without launching anything for n == 0, n >= 2^32, win > MADSIM_DIVERGE_MAX_WIN, a missing or misaligned array.
+#define MADSIM_K_DIVERGE_WAVES 1024u    /* = MADSIM_K_COLLECT_WAVES: 256 workgroups of four waves */
+int  madsim_k_launch_diverge(const uint8_t* log_a, const uint8_t* log_b, uint64_t log_cap, const uint64_t* obs_a, const uint64_t* obs_b,
+                             uint64_t obs_cap, const uint64_t* log_len_a, const uint64_t* log_len_b, const uint64_t* obs_len_a,
+                             const uint64_t* obs_len_b, const madsim_result_t* res_a, const madsim_result_t* res_b, const uint64_t* d_seeds,
+                             uint64_t n, uint32_t win, madsim_divergence_t* recs, uint64_t* ctx, void* stream);
 int  madsim_k_set_max_lds(uint32_t lds_bytes);
 int  madsim_k_variant_vgprs(const madsim_k::VariantSel* v);
 void madsim_k_launch_keyflip(unsigned long long* acc, void* stream);

@@ -657,6 +657,113 @@ __global__ __launch_bounds__(256) void resolve_scatter_kernel(madsim_result_t* _
     reinterpret_cast<uint4*>(out + idx[j])[chunk] = reinterpret_cast<const uint4*>(rerun)[t];
 }
 
+// ---- divergence reports: where two variants of a seed's run first part --------------------------------------------------------------
+// Two sets of trace rows of the same n seeds (the determinism log: 1-byte entries; the observation log: 8-byte entries), compared where
+// they lie.  One wave per row pair, waves striding over the rows; a pure function of its inputs: no atomics, no LDS.  Both channels walk
+// BYTES — an 8-byte entry's index is the byte index >> 3 — and only the first m = min(len_a, len_b, cap) entries: what lies behind
+// min(len_x, cap) in a row is never compared (in real rows it is zeros, and a compare that ran into it would turn "one run ended where
+// the other went on" into a later difference, or into none).
+// diverge_walk: the index of the first byte < n_bytes at which a and b differ, or n_bytes; wave-uniform.  Row i starts at i * cap entries,
+// so a and b are 16-byte aligned only when the pitch is; the launcher demands 16-byte aligned row arrays, so the two sides share the
+// misalignment: up to 15 head bytes one per lane, then 16 bytes per lane and side per trip (1 KiB per side), the wave leaving at the first
+// trip with a hit — a ballot of "my 16 bytes differ", then the lowest set lane's first differing byte —, then up to 15 tail bytes.
+__device__ __forceinline__ uint64_t diverge_walk(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b, uint64_t n_bytes, uint32_t lane) {
+    const uint64_t mis = (uint64_t)(reinterpret_cast<uintptr_t>(a) & 15u);
+    uint64_t head = mis ? 16u - mis : 0u;
+    if (head > n_bytes) head = n_bytes;
+    if (head) {                                                                    // (wave-uniform)
+        const unsigned long long hit = __ballot(lane < head && a[lane] != b[lane]);
+        if (hit) return (uint64_t)(__ffsll((long long)hit) - 1);
+    }
+    const uint4* __restrict__ qa = reinterpret_cast<const uint4*>(a + head);
+    const uint4* __restrict__ qb = reinterpret_cast<const uint4*>(b + head);
+    const uint64_t chunks = (n_bytes - head) >> 4;
+    for (uint64_t base = 0; base < chunks; base += 64) {
+        const uint64_t j = base + lane;
+        uint32_t off = 16;                                                         // my first differing byte of the 16
+        if (j < chunks) {
+            const uint4 x = qa[j], y = qb[j];
+            const uint32_t d[4] = {x.x ^ y.x, x.y ^ y.y, x.z ^ y.z, x.w ^ y.w};
+#pragma unroll
+            for (int k = 3; k >= 0; k--) if (d[k]) off = 4u * k + ((uint32_t)__ffs((int)d[k]) - 1u) / 8u;
+        }
+        const unsigned long long hit = __ballot(off < 16u);
+        if (hit) {
+            const int l = __ffsll((long long)hit) - 1;
+            return head + ((base + (uint64_t)l) << 4) + (uint64_t)__shfl(off, l);
+        }
+    }
+    const uint64_t done = head + (chunks << 4), tail = n_bytes - done;             // < 16
+    if (tail) {
+        const unsigned long long hit = __ballot(lane < tail && a[done + lane] != b[done + lane]);
+        if (hit) return done + (uint64_t)(__ffsll((long long)hit) - 1);
+    }
+    return n_bytes;
+}
+
+// One channel of one row pair: status and `at` (entries of common prefix established), by the table in include/madsim_hip.h.  `shift`: 0 for
+// 1-byte entries, 3 for 8-byte ones.  Wave-uniform; reads nothing of the rows when there is nothing to compare.
+struct DivergeAt { uint32_t status; uint64_t at; };
+__device__ __forceinline__ DivergeAt diverge_channel(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b, uint64_t len_a, uint64_t len_b,
+                                                     uint64_t cap, uint32_t shift, bool runner, uint32_t lane) {
+    if (runner) return DivergeAt{MADSIM_DIVERGE_INCOMPARABLE, 0};
+    const uint64_t L = len_a < len_b ? len_a : len_b, m = L < cap ? L : cap;
+    const uint64_t d = m ? diverge_walk(a, b, m << shift, lane) : 0;
+    if (d < m << shift) return DivergeAt{MADSIM_DIVERGE_DIFFER, d >> shift};
+    if (L > cap) return DivergeAt{MADSIM_DIVERGE_BEYOND_CAP, cap};
+    return DivergeAt{len_a == len_b ? MADSIM_DIVERGE_SAME : MADSIM_DIVERGE_PREFIX, L};
+}
+
+// Record i (23 words, madsim_divergence_t) and context row i (3 * win words: the shared values [at - win, at) right-aligned, then A's and
+// B's [at, at + win), each cut at min(len_x, cap); zeros wherever there is no entry, and everywhere under INCOMPARABLE).
+__global__ __launch_bounds__(256) void diverge_kernel(const uint8_t* __restrict__ log_a, const uint8_t* __restrict__ log_b, uint64_t log_cap,
+                                                      const unsigned long long* __restrict__ obs_a, const unsigned long long* __restrict__ obs_b,
+                                                      uint64_t obs_cap, const unsigned long long* __restrict__ log_len_a,
+                                                      const unsigned long long* __restrict__ log_len_b, const unsigned long long* __restrict__ obs_len_a,
+                                                      const unsigned long long* __restrict__ obs_len_b, const madsim_result_t* __restrict__ res_a,
+                                                      const madsim_result_t* __restrict__ res_b, const unsigned long long* __restrict__ seeds, uint64_t n,
+                                                      uint32_t win, unsigned long long* __restrict__ recs, unsigned long long* __restrict__ ctx) {
+    const uint32_t lane = threadIdx.x & 63;
+    for (uint64_t i = blockIdx.x * 4u + (threadIdx.x >> 6); i < n; i += (uint64_t)gridDim.x * 4u) {      // (wave-uniform)
+        const unsigned long long* ra = reinterpret_cast<const unsigned long long*>(res_a + i);
+        const unsigned long long* rb = reinterpret_cast<const unsigned long long*>(res_b + i);
+        const bool runner = MADSIM_IS_RUNNER_VERDICT((uint32_t)ra[0]) || MADSIM_IS_RUNNER_VERDICT((uint32_t)rb[0]);
+        const uint64_t lla = log_len_a[i], llb = log_len_b[i], ola = obs_len_a[i], olb = obs_len_b[i];
+        const uint8_t* la = log_a + i * log_cap;
+        const uint8_t* lb = log_b + i * log_cap;
+        const unsigned long long* oa = obs_a + i * obs_cap;
+        const unsigned long long* ob = obs_b + i * obs_cap;
+        const DivergeAt dl = diverge_channel(la, lb, lla, llb, log_cap, 0, runner, lane);
+        const DivergeAt dob = diverge_channel(reinterpret_cast<const uint8_t*>(oa), reinterpret_cast<const uint8_t*>(ob), ola, olb, obs_cap, 3, runner, lane);
+        const uint64_t ka_l = lla < log_cap ? lla : log_cap, kb_l = llb < log_cap ? llb : log_cap;      // entries kept of each row
+        const uint64_t ka_o = ola < obs_cap ? ola : obs_cap, kb_o = olb < obs_cap ? olb : obs_cap;
+        unsigned long long* const p = recs + i * 23u;
+        if (lane == 0) {
+            const bool cmp = !runner;
+            p[0] = seeds[i];
+            p[1] = (unsigned long long)dl.status | (unsigned long long)dob.status << 32;
+            p[2] = dl.at; p[3] = dob.at;
+            p[4] = lla; p[5] = llb; p[6] = ola; p[7] = olb;
+            p[8] = cmp && dob.at < ka_o ? oa[dob.at] : 0ull;
+            p[9] = cmp && dob.at < kb_o ? ob[dob.at] : 0ull;
+            p[10] = (cmp && dl.at < ka_l ? (unsigned long long)la[dl.at] : 0ull) | (cmp && dl.at < kb_l ? (unsigned long long)lb[dl.at] << 8 : 0ull);
+        }
+        if (lane < 6) { p[11 + lane] = ra[lane]; p[17 + lane] = rb[lane]; }
+        if (lane < 3 * win) {                                                      // (win <= 8: one word per lane)
+            const uint32_t part = lane / win, j = lane - part * win;
+            unsigned long long v = 0;
+            if (!runner) {
+                if (part == 0) { if (dob.at + j >= win) v = oa[dob.at + j - win]; }
+                else {
+                    const uint64_t k = dob.at + j;
+                    if (part == 1) { if (k < ka_o) v = oa[k]; } else if (k < kb_o) v = ob[k];
+                }
+            }
+            ctx[i * 3u * win + lane] = v;
+        }
+    }
+}
+
 // one kernel per row of variant_table (sim_kernel.h), same macro, same order
 #define MADSIM_VARIANT_KERNEL(T_, S_, L_, F_, R_, G_) (const void*)sim_kernel<Variant<T_, S_, L_, F_, R_, G_>>,
 static const void* const variant_kernels[] = {MADSIM_FOR_EACH_VARIANT(MADSIM_VARIANT_KERNEL)};
@@ -852,6 +959,28 @@ extern "C" int madsim_k_launch_resolve_scatter(madsim_result_t* out, const madsi
     if (m == 0) return 0;
     const uint32_t grid = (uint32_t)((MADSIM_K_RESOLVE_CHUNKS * m + 255) / 256);
     hipLaunchKernelGGL(madsim_k::resolve_scatter_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, out, rerun, idx, (uint32_t)m);
+    return 0;
+}
+
+// Rows, lengths, results and seeds of the same n seeds on both sides (sim_kernel.h); recs: n records; ctx: n rows of 3 * win words (null
+// when win == 0).  Nothing needs preparing: every record and context word is written.  Returns 0, or -1 (nothing launched) for n == 0,
+// n >= 2^32, win > MADSIM_DIVERGE_MAX_WIN, a missing array, a row array that is not 16-byte aligned or rows beyond 2^62 bytes.
+extern "C" int madsim_k_launch_diverge(const uint8_t* log_a, const uint8_t* log_b, uint64_t log_cap, const uint64_t* obs_a, const uint64_t* obs_b,
+                                       uint64_t obs_cap, const uint64_t* log_len_a, const uint64_t* log_len_b, const uint64_t* obs_len_a,
+                                       const uint64_t* obs_len_b, const madsim_result_t* res_a, const madsim_result_t* res_b, const uint64_t* d_seeds,
+                                       uint64_t n, uint32_t win, madsim_divergence_t* recs, uint64_t* ctx, void* stream) {
+    static_assert(sizeof(madsim_divergence_t) == 184 && sizeof(madsim_result_t) == 48 && MADSIM_K_DIVERGE_WAVES == 1024, "record layout");
+    static_assert(MADSIM_DIVERGE_MAX_WIN == 8, "one context word per lane");
+    if (n == 0 || n >= (1ull << 32) || win > MADSIM_DIVERGE_MAX_WIN || (win != 0) != (ctx != nullptr)) return -1;
+    if (!log_len_a || !log_len_b || !obs_len_a || !obs_len_b || !res_a || !res_b || !d_seeds || !recs) return -1;
+    if ((log_cap && (!log_a || !log_b)) || (obs_cap && (!obs_a || !obs_b))) return -1;
+    if (((uintptr_t)log_a | (uintptr_t)log_b | (uintptr_t)obs_a | (uintptr_t)obs_b) & 15u) return -1;
+    if (log_cap > (1ull << 62) / n || obs_cap > (1ull << 59) / n) return -1;
+    const uint64_t waves = n < MADSIM_K_DIVERGE_WAVES ? n : MADSIM_K_DIVERGE_WAVES;      // one wave per row pair, 256 workgroups at most
+    hipLaunchKernelGGL(madsim_k::diverge_kernel, dim3((uint32_t)((waves + 3) / 4)), dim3(256), 0, (hipStream_t)stream, log_a, log_b, log_cap,
+                       (const unsigned long long*)obs_a, (const unsigned long long*)obs_b, obs_cap, (const unsigned long long*)log_len_a,
+                       (const unsigned long long*)log_len_b, (const unsigned long long*)obs_len_a, (const unsigned long long*)obs_len_b, res_a, res_b,
+                       (const unsigned long long*)d_seeds, n, win, reinterpret_cast<unsigned long long*>(recs), (unsigned long long*)ctx);
     return 0;
 }
 

@@ -149,6 +149,8 @@ def lib():
                                                                        C.POINTER(A.Campaign), C.POINTER(A.Diff)]
         L.madsim_hip_ctx_run_seeds_campaign_diff.argtypes = [ctxp] + L.madsim_hip_run_seeds_campaign_diff.argtypes
         L.madsim_hip_run_seeds_campaign_diff_multi.argtypes = [C.POINTER(ctxp), C.c_int] + L.madsim_hip_run_seeds_campaign_diff.argtypes
+        L.madsim_hip_diverge_seeds.argtypes = side + side + [u64p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.madsim_hip_ctx_diverge_seeds.argtypes = [ctxp] + L.madsim_hip_diverge_seeds.argtypes
         L.madsim_hip_observe_seed.restype = C.c_int64
         L.madsim_hip_observe_seed.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), C.c_uint64, C.POINTER(A.Limits), C.c_void_p, C.c_uint64,
                                               C.POINTER(A.Result)]
@@ -348,6 +350,81 @@ def trace_seeds(workload, seeds, config=None, limits=None, obs_cap=256, log_cap=
     if _inited_device is None:
         init(0)
     return _trace_seeds(lambda *a: lib().madsim_hip_trace_seeds(workload.ref(), *a), workload, seeds, config, limits, obs_cap, log_cap, resolve)
+
+
+class Divergence:
+    """Where the two runs of one seed part (runtime.diverge_seeds): the fields of madsim_divergence_t — `seed`; per channel (`log`: the
+    determinism log, one byte per draw; `obs`: the observations) a status (A.DIVERGE_*), `*_at`, the length of the common prefix that was
+    established, the true lengths `*_len_a` / `*_len_b` and each side's entry at `*_at` (`log_a`, `log_b`, `obs_a`, `obs_b`; 0 where a
+    side has none); `a`, `b`: the two A.Result — and the observation context: `shared`, the up to `window` observations both runs made
+    just before `obs_at`, `next_a` / `next_b`, the up to `window` each side made from there on."""
+    __slots__ = ("seed", "log_status", "obs_status", "log_at", "obs_at", "log_len_a", "log_len_b", "obs_len_a", "obs_len_b", "obs_a", "obs_b",
+                 "log_a", "log_b", "a", "b", "shared", "next_a", "next_b")
+
+    def __repr__(self):
+        return (f"Divergence(seed={self.seed}, log={A.DIVERGE_NAMES[self.log_status]}@{self.log_at}, obs={A.DIVERGE_NAMES[self.obs_status]}@{self.obs_at}, "
+                f"shared={self.shared}, next_a={self.next_a}, next_b={self.next_b})")
+
+
+def _diverge_seeds(call, workload, seeds, other, config, other_config, limits, other_limits, log_cap, obs_cap, window, resolve):
+    """Run `call(wA*, cfgA*, limA*, wB*, cfgB*, limB*, seeds*, n, log_cap, obs_cap, win, recs, ctx)` — a madsim_hip_*diverge_seeds entry point
+    with its context bound — over `seeds`, then over the seeds a round leaves incomparable with a re-runnable verdict on either side, each
+    round one further call with each side under its own grown limits."""
+    seeds = [int(s) for s in seeds]
+    if any(not 0 <= s <= A.U64_MAX for s in seeds) or obs_cap < 0 or log_cap < 0 or window < 0:
+        raise MadsimHipError("diverge_seeds: seeds must fit u64, caps and window be >= 0")
+    wl_b = workload if other is None else other
+    cfg_a = config or A.Config.default()
+    cfg_b = cfg_a if other_config is None else other_config
+    lim_a0 = limits or A.Limits()
+    lim_b0 = lim_a0 if other_limits is None else other_limits
+    rounds = 0 if resolve is None or resolve is False else A.RESOLVE_DEFAULT_ROUNDS if resolve is True else int(resolve)
+    if not 0 <= rounds <= A.RESOLVE_MAX_ROUNDS:
+        raise MadsimHipError(f"resolve: None, True or a number of rounds 1..{A.RESOLVE_MAX_ROUNDS}, got {resolve!r}")
+    n = len(seeds)
+    recs, ctx = np.zeros(n, dtype=A.DIVERGENCE_DTYPE), np.zeros((n, 3 * window), dtype=np.uint64)
+    idx = np.arange(n)
+    for r in range(rounds + 1):
+        if not len(idx):
+            break
+        lim_a = lim_a0 if r == 0 else grown_limits(workload, lim_a0, r)
+        lim_b = lim_b0 if r == 0 else grown_limits(wl_b, lim_b0, r)
+        m = len(idx)
+        s = np.array([seeds[i] for i in idx], dtype=np.uint64)
+        rec, cx = np.zeros(m, dtype=A.DIVERGENCE_DTYPE), np.zeros((m, 3 * window), dtype=np.uint64)
+        _check(call(workload.ref(), C.byref(cfg_a), C.byref(lim_a), wl_b.ref(), C.byref(cfg_b), C.byref(lim_b), s.ctypes.data_as(C.POINTER(C.c_uint64)), m,
+                    log_cap, obs_cap, window, rec.ctypes.data_as(C.c_void_p), cx.ctypes.data_as(C.c_void_p) if window else None))
+        recs[idx], ctx[idx] = rec, cx
+        idx = idx[_rerunnable(rec["a"], lim_a) | _rerunnable(rec["b"], lim_b)]
+    out = []
+    for i in range(n):
+        x, d = recs[i], Divergence()
+        for name in Divergence.__slots__[:13]:
+            setattr(d, name, int(x[name]))
+        d.a, d.b = A.Result(*[int(v) for v in x["a"]]), A.Result(*[int(v) for v in x["b"]])
+        at, w = d.obs_at, window
+        keep_a, keep_b = min(d.obs_len_a, obs_cap), min(d.obs_len_b, obs_cap)
+        if d.obs_status == A.DIVERGE_INCOMPARABLE:
+            d.shared, d.next_a, d.next_b = [], [], []
+        else:
+            d.shared = [int(v) for v in ctx[i, w - min(at, w):w]]
+            d.next_a = [int(v) for v in ctx[i, w:w + max(0, min(w, keep_a - at))]]
+            d.next_b = [int(v) for v in ctx[i, 2 * w:2 * w + max(0, min(w, keep_b - at))]]
+        out.append(d)
+    return out
+
+
+def diverge_seeds(workload, seeds, other=None, config=None, other_config=None, limits=None, other_limits=None, log_cap=1 << 16, obs_cap=256,
+                  window=4, resolve=True):
+    """madsim_hip_diverge_seeds: where the runs of `seeds` under (workload, config, limits) and under (other, other_config, other_limits) — a
+    None means side A's — first part, on the determinism log and on the observations, compared on the device: returns one Divergence per
+    seed, in the order given.  No row is copied to the host.  resolve=True | rounds: seeds that come back incomparable with a re-runnable
+    runner verdict on either side are replayed in one further call per round, each side under its own grown_limits(.., r), as trace_seeds
+    does; resolve=None / False: the one call, runner verdicts as they come."""
+    if _inited_device is None:
+        init(0)
+    return _diverge_seeds(lib().madsim_hip_diverge_seeds, workload, seeds, other, config, other_config, limits, other_limits, log_cap, obs_cap,
+                          window, resolve)
 
 
 def observe_seed(workload, seed, config=None, limits=None, cap=1 << 16, resolve=True):
@@ -806,6 +883,12 @@ class Context:
         """runtime.trace_seeds on this context (madsim_hip_ctx_trace_seeds)."""
         return _trace_seeds(lambda *a: lib().madsim_hip_ctx_trace_seeds(self._h, workload.ref(), *a), workload, seeds, config, limits, obs_cap,
                             log_cap, resolve)
+
+    def diverge_seeds(self, workload, seeds, other=None, config=None, other_config=None, limits=None, other_limits=None, log_cap=1 << 16,
+                      obs_cap=256, window=4, resolve=True):
+        """runtime.diverge_seeds on this context (madsim_hip_ctx_diverge_seeds)."""
+        return _diverge_seeds(lambda *a: lib().madsim_hip_ctx_diverge_seeds(self._h, *a), workload, seeds, other, config, other_config, limits,
+                              other_limits, log_cap, obs_cap, window, resolve)
 
     def observe_seed(self, workload, seed, config=None, limits=None, cap=1 << 16, resolve=True):
         """runtime.observe_seed on this context."""
