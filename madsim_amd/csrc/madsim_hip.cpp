@@ -25,6 +25,7 @@
 
 #include "sim_kernel.h"
 #include "geometry.h"
+#include "device_mem.h"
 
 using madsim_k::KParams;
 using madsim_geo::Geo;
@@ -66,82 +67,164 @@ double since(std::chrono::steady_clock::time_point t0) {
 
 }  // namespace
 
-// One GPU's worth of runner state.  Re-entrant per handle: distinct contexts never share mutable state; one context
-// serialises its callers on `mu`.
-struct madsim_hip_ctx {
-    std::mutex mu;
-    int device = -1;
-    int num_cus = 0;
-    size_t lds_per_cu = 160 * 1024;
+using madsim_mem::DevBuf;
+using madsim_mem::PinnedBuf;
+using madsim_mem::Event;
+using madsim_mem::Stream;
+typedef unsigned long long report_word_t;
+
+// Everything a context owns on its device, each member an owning type of device_mem.h: madsim_hip_ctx::close() releases all of it by
+// assigning a fresh one, with the device bound.
+struct madsim_hip_resources {
     // Device copies of workload tables.  Looked up by content hash, confirmed by comparing the host bytes kept beside
     // them; entries are immutable once uploaded, so launches still in flight on other streams keep valid pointers when a
     // different workload comes along.
     struct Tables {
         uint64_t hash = 0;
         std::vector<uint32_t> host;      // insns | progs | socks | durs (as 32-bit words) | n_insns
-        uint4* insns = nullptr; uint32_t* progs = nullptr; uint32_t* socks = nullptr; uint32_t* nodes = nullptr; uint64_t* durs = nullptr;
-        uint32_t* iter_est = nullptr;    // ITER_KEYS words: how many passes a wave of this workload runs, one per launch shape (limits, seeds per lane:
+        DevBuf<uint32_t> insns, progs, socks, nodes; DevBuf<uint64_t> durs;      // (insns: four words an instruction, read as uint4)
+        DevBuf<uint32_t> iter_est;       // ITER_KEYS words: how many passes a wave of this workload runs, one per launch shape (limits, seeds per lane:
                                          // upload_workload picks the word; written by finishing waves, k_main.h)
     };
     static constexpr uint32_t ITER_KEYS = 16;
     std::vector<Tables> tables;
     // per-stream scratch: launches on one stream run in order, launches on different streams may overlap and must
     // not share the timer-heap spill region or the work-queue counter
-    struct Scratch { uint4* spill = nullptr; size_t spill_bytes = 0; unsigned long long* work_ctr = nullptr; uint8_t* gstate = nullptr; size_t gstate_bytes = 0; };
+    struct Scratch { DevBuf<uint8_t> spill, gstate; DevBuf<unsigned long long> work_ctr; };
     std::unordered_map<hipStream_t, Scratch> scratch;
     // madsim_hip_ctx_run_campaign: batches in flight on the context's own streams
     static constexpr int CAMPAIGN_MAX = 8;
     static constexpr size_t STATS_REP_WORDS = 16 + MADSIM_K_STATS_WORDS;      // a statistics campaign's report: the plain / collecting report's words in front
-    struct Flight { hipStream_t stream = nullptr; madsim_result_t* d_out = nullptr; size_t cap = 0; unsigned long long* d_acc6 = nullptr;
-                    unsigned long long* h_acc6 = nullptr; hipEvent_t e0 = nullptr, e1 = nullptr, done = nullptr;
-                    madsim_result_t* h_out = nullptr; size_t h_cap = 0;         // h_out: page-locked staging of run_pipelined
-                    // collecting campaigns only: report words (device, page-locked host), per-wave counts, the batch's failure records
-                    unsigned long long* d_rep = nullptr; unsigned long long* h_rep = nullptr; uint32_t* d_wcnt = nullptr;
-                    madsim_failure_t* d_rec = nullptr; size_t rec_cap = 0;
-                    // statistics campaigns only: 16 report words (summary6's or collect's) + MADSIM_K_STATS_WORDS (device, page-locked host), candidates
-                    unsigned long long* d_srep = nullptr; unsigned long long* h_srep = nullptr; unsigned long long* d_cand = nullptr;
-                    // grouping campaigns only: the 16 report words + the statistics words (used when asked for) + MADSIM_K_GROUP_WORDS (device,
-                    // page-locked host); the keyed table (zero between batches: grp_dirty = a batch was queued and never harvested), the list
-                    // of claimed slots and the batch's entries, sized for batches of grp_cap seeds
-                    unsigned long long* d_grep = nullptr; unsigned long long* h_grep = nullptr; uint32_t* d_gtab = nullptr; uint32_t* d_glist = nullptr;
-                    madsim_group_t* d_gent = nullptr; size_t grp_cap = 0; bool grp_dirty = false;
-                    // differential campaigns only: side B's results, its event pair, the report words — DIFF_REP_WORDS live ones (device, page-locked
-                    // host) and behind the device's a copy of their state before a batch, from which one device copy prepares them —, per-wave
-                    // counts and the batch's records
-                    madsim_result_t* d_out_b = nullptr; size_t cap_b = 0; hipEvent_t b0 = nullptr, b1 = nullptr;
-                    unsigned long long* d_drep = nullptr; unsigned long long* h_drep = nullptr; uint32_t* d_dwcnt = nullptr;
-                    madsim_diff_record_t* d_drec = nullptr; size_t drec_cap = 0;
-                    // resolving campaigns only, allocated when a batch first needs a round: the seed list, the index list and the re-run results of
-                    // up to rr_cap seeds (60 B per seed), the list kernels' wave counts with the count word behind them (device) and that word's
-                    // page-locked host copy, the re-run kernel's event pair
-                    uint64_t* d_seeds = nullptr; uint32_t* d_idx = nullptr; madsim_result_t* d_rerun = nullptr; size_t rr_cap = 0;
-                    uint32_t* d_rcnt = nullptr; uint32_t* h_rcnt = nullptr; hipEvent_t r0 = nullptr, r1 = nullptr;
-                    // list campaigns only: the batch's slice of the caller's seed list (device) and its page-locked staging copy, list_cap words
-                    // each.  Not d_seeds: a resolving list campaign reads this one while it writes that one.
-                    uint64_t* d_list = nullptr; uint64_t* h_list = nullptr; size_t list_cap = 0; };
     static constexpr size_t GROUP_REP_WORDS = STATS_REP_WORDS + MADSIM_K_GROUP_WORDS;
     static constexpr size_t DIFF_REP_WORDS = 16 + MADSIM_K_DIFF_WORDS;      // summary6's six words of side A at 0, of side B at 8, the diff words at 16
+    // One batch in flight: what every form uses, then one group per campaign form, made when a call of that form first comes (ensure)
+    // and kept with the flight.  Every resource is ensured on its own — none stands for another —, so a call that ran out of memory
+    // half-way leaves nothing that a later call would take for complete.
+    struct Flight {
+        Stream stream; Event e0, e1, done;
+        // the batch's report words (device, page-locked host): 16 report words (summary6's or collect's), then the statistics words, then the
+        // grouping words — sized once for all of them; run_pipelined and the plain campaign use the first six
+        DevBuf<report_word_t> d_rep; PinnedBuf<report_word_t> h_rep;
+        DevBuf<madsim_result_t> d_out; PinnedBuf<madsim_result_t> h_out;      // h_out: page-locked staging of run_pipelined
+        int ensure(uint64_t batch, bool staging) {
+            HIP_TRY(stream.ensure());
+            HIP_TRY(d_rep.room(GROUP_REP_WORDS));
+            HIP_TRY(h_rep.room(GROUP_REP_WORDS));
+            HIP_TRY(e0.ensure()); HIP_TRY(e1.ensure()); HIP_TRY(done.ensure());
+            HIP_TRY(d_out.room(batch, stream));
+            if (staging) HIP_TRY(h_out.room(batch, stream));
+            return 0;
+        }
+        // collecting campaigns: per-wave counts, the batch's failure records
+        struct Collect {
+            DevBuf<uint32_t> wcnt; DevBuf<madsim_failure_t> rec;
+            int ensure(uint64_t records, hipStream_t s) {
+                HIP_TRY(wcnt.room(MADSIM_K_COLLECT_WAVES));
+                HIP_TRY(rec.room(records, s));
+                return 0;
+            }
+        } collect;
+        // statistics campaigns: the candidate words
+        struct Stats {
+            DevBuf<unsigned long long> cand;
+            int ensure() { HIP_TRY(cand.room(MADSIM_K_STATS_CAND_WORDS)); return 0; }
+        } stats;
+        // grouping campaigns: the keyed table (zero between batches: dirty = a batch was queued and never harvested), the list of claimed
+        // slots and the batch's entries, sized for batches of `cap` seeds
+        struct Groups {
+            DevBuf<uint32_t> tab, list; DevBuf<madsim_group_t> ent; size_t cap = 0; bool dirty = false;
+            int ensure(uint64_t batch, hipStream_t s) {
+                if (batch > cap) {
+                    dirty = true; cap = 0;           // (cap counts only once all three have room)
+                    HIP_TRY(tab.room(madsim_k_group_slots(batch) * MADSIM_K_GROUP_SLOT_BYTES / sizeof(uint32_t), s));
+                    HIP_TRY(list.room(batch, s));
+                    HIP_TRY(ent.room(batch, s));
+                    cap = batch;
+                }
+                if (dirty) {                         // a new table, or one that an error left between a batch's two passes: the only time it is cleared whole
+                    HIP_TRY(hipMemsetAsync(tab, 0, madsim_k_group_slots(cap) * MADSIM_K_GROUP_SLOT_BYTES, s));
+                    HIP_TRY(hipStreamSynchronize(s));
+                    dirty = false;
+                }
+                return 0;
+            }
+        } groups;
+        // differential campaigns: side B's results, its event pair, the report words — DIFF_REP_WORDS live ones (device, page-locked
+        // host) and behind the device's a copy of their state before a batch, from which one device copy prepares them —, per-wave
+        // counts and the batch's records
+        struct Diff {
+            DevBuf<madsim_result_t> out_b; Event b0, b1;
+            DevBuf<report_word_t> d_rep; PinnedBuf<report_word_t> h_rep; DevBuf<uint32_t> wcnt; DevBuf<madsim_diff_record_t> rec;
+            int ensure(uint64_t batch, uint64_t records, hipStream_t s) {
+                if (!d_rep) {
+                    report_word_t init[DIFF_REP_WORDS] = {};                        // the words before a batch: summary6's two minima all-ones, the rest zero
+                    init[0] = init[4] = init[8] = init[12] = ~0ull;
+                    HIP_TRY(d_rep.room(2 * DIFF_REP_WORDS));
+                    const hipError_t e = hipMemcpy(d_rep + DIFF_REP_WORDS, init, sizeof init, hipMemcpyHostToDevice);
+                    if (e != hipSuccess) {                                          // (words without their initial state are no words)
+                        d_rep.reset();
+                        return fail(MADSIM_E_HIP, std::string("hipMemcpy(initial report words): ") + hipGetErrorString(e));
+                    }
+                }
+                HIP_TRY(h_rep.room(DIFF_REP_WORDS));
+                HIP_TRY(wcnt.room(MADSIM_K_COLLECT_WAVES));
+                HIP_TRY(b0.ensure()); HIP_TRY(b1.ensure());
+                HIP_TRY(out_b.room(batch, s));
+                HIP_TRY(rec.room(records, s));
+                return 0;
+            }
+        } diff;
+        // resolving campaigns, made when a batch first needs a round (most campaigns never do), enlarged — with the flight's stream drained —
+        // when a later call brings larger batches: the seed list, the index list and the re-run results of `want` seeds (60 B per seed), the
+        // list kernels' wave counts with the count word behind them (device) and that word's page-locked host copy, the re-run kernel's event pair
+        struct Resolve {
+            DevBuf<uint64_t> seeds; DevBuf<uint32_t> idx; DevBuf<madsim_result_t> rerun;
+            DevBuf<uint32_t> cnt; PinnedBuf<uint32_t> h_cnt; Event r0, r1;
+            int ensure(size_t want, hipStream_t s) {
+                HIP_TRY(cnt.room(MADSIM_K_RESOLVE_WAVES + 1));
+                HIP_TRY(h_cnt.room(1));
+                HIP_TRY(r0.ensure()); HIP_TRY(r1.ensure());
+                HIP_TRY(seeds.room(want, s));
+                HIP_TRY(idx.room(want, s));
+                HIP_TRY(rerun.room(want, s));
+                return 0;
+            }
+        } resolve;
+        // list campaigns: the batch's slice of the caller's seed list (device) and its page-locked staging copy — 8 bytes per seed of a batch
+        // each, proportional to batch x flights, never to the length of the list.  Not resolve.seeds: a resolving list campaign reads this
+        // one while it writes that one.
+        struct List {
+            DevBuf<uint64_t> d; PinnedBuf<uint64_t> h;
+            int ensure(uint64_t batch, hipStream_t s) {
+                HIP_TRY(d.room(batch, s));
+                HIP_TRY(h.room(batch, s));
+                return 0;
+            }
+        } list;
+    };
     Flight flights[CAMPAIGN_MAX];
-    unsigned long long* d_acc = nullptr;      // 4 x u64 summary accumulators
-    madsim_result_t* d_out = nullptr; size_t out_cap = 0;
-    uint64_t* d_seeds = nullptr; size_t seeds_cap = 0;        // seed list of a compacted re-run
-    // trace launches: the rows of the determinism log (bytes) and of the observation log (words), the length words (tlen_cap of them)
-    uint8_t* d_tlog = nullptr; size_t tlog_cap = 0; uint64_t* d_olog = nullptr; size_t olog_cap = 0; uint64_t* d_tlen = nullptr; size_t tlen_cap = 0;
-    // divergence reports: side B's rows, length words and results, the records and the context rows
-    uint8_t* d_tlog_b = nullptr; size_t tlog_b_cap = 0; uint64_t* d_olog_b = nullptr; size_t olog_b_cap = 0; uint64_t* d_tlen_b = nullptr; size_t tlen_b_cap = 0;
-    madsim_result_t* d_out_b = nullptr; size_t out_b_cap = 0;
-    madsim_divergence_t* d_drec = nullptr; size_t drec_cap = 0; uint64_t* d_dctx = nullptr; size_t dctx_cap = 0;
-    // one side's buffers of a trace call, by reference: set 0 is what every trace call uses, set 1 side B of a divergence report
-    struct TraceSet { uint8_t*& log; size_t& log_have; uint64_t*& obs; size_t& obs_have; uint64_t*& len; size_t& len_have; madsim_result_t*& out; size_t& out_have; };
-    TraceSet trace_set(int side) {
-        return side ? TraceSet{d_tlog_b, tlog_b_cap, d_olog_b, olog_b_cap, d_tlen_b, tlen_b_cap, d_out_b, out_b_cap}
-                    : TraceSet{d_tlog, tlog_cap, d_olog, olog_cap, d_tlen, tlen_cap, d_out, out_cap};
-    }
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipEvent_t pipe_begin = nullptr;          // run_pipelined: before the first sub-batch of a call
-    hipEvent_t tev[2 * 64] = {};              // timing slots of madsim_hip_run_batch_async
+    DevBuf<unsigned long long> d_acc;         // 4 x u64 summary accumulators
+    DevBuf<uint64_t> d_seeds;                 // seed list of a compacted re-run
+    // One side's buffers of a trace launch: the rows of the determinism log (bytes) and of the observation log (words), the length words
+    // and the results.  Set 0 is what every trace call uses, set 1 side B of a divergence report; set 0's `out` is also the result
+    // buffer of run_host and run_list.
+    struct TraceSet { DevBuf<uint8_t> log; DevBuf<uint64_t> obs, len; DevBuf<madsim_result_t> out; };
+    TraceSet trace[2];
+    DevBuf<madsim_divergence_t> d_drec; DevBuf<uint64_t> d_dctx;      // divergence reports: the records and the context rows
+    Event ev0, ev1;
+    Event pipe_begin;                         // run_pipelined: before the first sub-batch of a call
+    Event tev[2 * 64];                        // timing slots of madsim_hip_run_batch_async
+    DevBuf<uint64_t> d_prof;                  // debug counters (profiling kernel builds)
+};
+
+// One GPU's worth of runner state.  Re-entrant per handle: distinct contexts never share mutable state; one context
+// serialises its callers on `mu`.
+struct madsim_hip_ctx : madsim_hip_resources {
+    std::mutex mu;
+    int device = -1;
+    int num_cus = 0;
+    size_t lds_per_cu = 160 * 1024;
     uint32_t lds_attr = 0;
-    uint64_t* d_prof = nullptr;               // debug counters (profiling kernel builds)
     madsim_resolve_t resolved{};              // the resolve account of the most recent campaign call (madsim_hip_ctx_campaign_resolved)
 
     madsim_geo::Device dev() const {
@@ -151,20 +234,10 @@ struct madsim_hip_ctx {
         return d;
     }
     int bind() { HIP_TRY(hipSetDevice(device)); return 0; }
-    static void free_tables(Tables& t) {
-        if (t.insns) (void)hipFree(t.insns);
-        if (t.progs) (void)hipFree(t.progs);
-        if (t.socks) (void)hipFree(t.socks);
-        if (t.nodes) (void)hipFree(t.nodes);
-        if (t.durs) (void)hipFree(t.durs);
-        if (t.iter_est) (void)hipFree(t.iter_est);
-        t = Tables();
-    }
     int open(int dev_index);
     void close();
     int upload_workload(const madsim_workload_t* w, KParams& P);
     int ensure_scratch(KParams& P, hipStream_t stream, bool work_queue);
-    int ensure_out(size_t count);
     int launch(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t count, const uint64_t* d_seed_list,
                const madsim_limits_t* lim, madsim_result_t* d_out, hipStream_t stream);
     int reduce(const madsim_result_t* d_out, uint64_t count, uint64_t seed0, unsigned long long* d_acc4, hipStream_t stream);
@@ -174,11 +247,8 @@ struct madsim_hip_ctx {
                  const madsim_limits_t* lim, madsim_result_t* out, madsim_summary_t* summary);
     int run_list(const madsim_workload_t* w, const madsim_config_t* cfg, const std::vector<uint64_t>& seeds,
                  const madsim_limits_t* lim, std::vector<madsim_result_t>& res, double* kernel_ms);
-    int ensure_flights(uint32_t n, uint64_t batch, bool staging, bool collect = false, uint64_t records = 0, bool stats = false, uint64_t groups = 0,
-                       bool diff = false, uint64_t diff_records = 0);
+    int ensure_flights(uint32_t n, uint64_t batch, bool staging);
     uint32_t flights_for(const madsim_workload_t* w, const madsim_config_t* cfg, const madsim_limits_t* lim, uint64_t batch);
-    int ensure_resolve(Flight& f, uint64_t n);
-    int ensure_list(uint32_t n, uint64_t batch);
 };
 
 // The library keeps up to five sub-batches of a call in flight, each on its own HIP stream (run_pipelined, campaigns).  ROCclr maps
@@ -212,84 +282,22 @@ int madsim_hip_ctx::open(int dev_index) {
     num_cus = prop.multiProcessorCount;
     lds_per_cu = prop.maxSharedMemoryPerMultiProcessor ? prop.maxSharedMemoryPerMultiProcessor : 160 * 1024;
     if (lds_per_cu > 160 * 1024) lds_per_cu = 160 * 1024;
-    HIP_TRY(hipMalloc(&d_acc, 4 * sizeof(unsigned long long)));
-    HIP_TRY(hipMalloc(&d_prof, 16 * sizeof(uint64_t)));
+    HIP_TRY(d_acc.room(4));
+    HIP_TRY(d_prof.room(16));
     HIP_TRY(hipMemset(d_prof, 0, 16 * sizeof(uint64_t)));
-    HIP_TRY(hipEventCreate(&ev0));
-    HIP_TRY(hipEventCreate(&ev1));
-    HIP_TRY(hipEventCreate(&pipe_begin));
+    HIP_TRY(ev0.ensure());
+    HIP_TRY(ev1.ensure());
+    HIP_TRY(pipe_begin.ensure());
     return 0;
 }
 
+// Everything is released here, with the device bound and idle (also what an open() that failed half-way left): the members' destructors
+// then find nothing left.
 void madsim_hip_ctx::close() {
     if (device < 0) return;
     (void)hipSetDevice(device);
     (void)hipDeviceSynchronize();
-    for (auto& t : tables) free_tables(t);
-    tables.clear();
-    for (auto& kv : scratch) { if (kv.second.spill) (void)hipFree(kv.second.spill); if (kv.second.work_ctr) (void)hipFree(kv.second.work_ctr); if (kv.second.gstate) (void)hipFree(kv.second.gstate); }
-    scratch.clear();
-    if (d_acc) (void)hipFree(d_acc);
-    if (d_out) (void)hipFree(d_out);
-    if (d_seeds) (void)hipFree(d_seeds);
-    if (d_tlog) (void)hipFree(d_tlog);
-    if (d_olog) (void)hipFree(d_olog);
-    if (d_tlen) (void)hipFree(d_tlen);
-    if (d_tlog_b) (void)hipFree(d_tlog_b);
-    if (d_olog_b) (void)hipFree(d_olog_b);
-    if (d_tlen_b) (void)hipFree(d_tlen_b);
-    if (d_out_b) (void)hipFree(d_out_b);
-    if (d_drec) (void)hipFree(d_drec);
-    if (d_dctx) (void)hipFree(d_dctx);
-    if (d_prof) (void)hipFree(d_prof);
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    if (pipe_begin) (void)hipEventDestroy(pipe_begin);
-    for (auto& f : flights) {
-        if (f.stream) (void)hipStreamDestroy(f.stream);
-        if (f.d_out) (void)hipFree(f.d_out);
-        if (f.d_acc6) (void)hipFree(f.d_acc6);
-        if (f.h_acc6) (void)hipHostFree(f.h_acc6);
-        if (f.h_out) (void)hipHostFree(f.h_out);
-        if (f.d_rep) (void)hipFree(f.d_rep);
-        if (f.h_rep) (void)hipHostFree(f.h_rep);
-        if (f.d_wcnt) (void)hipFree(f.d_wcnt);
-        if (f.d_rec) (void)hipFree(f.d_rec);
-        if (f.d_srep) (void)hipFree(f.d_srep);
-        if (f.h_srep) (void)hipHostFree(f.h_srep);
-        if (f.d_cand) (void)hipFree(f.d_cand);
-        if (f.d_grep) (void)hipFree(f.d_grep);
-        if (f.h_grep) (void)hipHostFree(f.h_grep);
-        if (f.d_gtab) (void)hipFree(f.d_gtab);
-        if (f.d_glist) (void)hipFree(f.d_glist);
-        if (f.d_gent) (void)hipFree(f.d_gent);
-        if (f.d_out_b) (void)hipFree(f.d_out_b);
-        if (f.d_drep) (void)hipFree(f.d_drep);
-        if (f.h_drep) (void)hipHostFree(f.h_drep);
-        if (f.d_dwcnt) (void)hipFree(f.d_dwcnt);
-        if (f.d_drec) (void)hipFree(f.d_drec);
-        if (f.d_seeds) (void)hipFree(f.d_seeds);
-        if (f.d_idx) (void)hipFree(f.d_idx);
-        if (f.d_rerun) (void)hipFree(f.d_rerun);
-        if (f.d_rcnt) (void)hipFree(f.d_rcnt);
-        if (f.h_rcnt) (void)hipHostFree(f.h_rcnt);
-        if (f.d_list) (void)hipFree(f.d_list);
-        if (f.h_list) (void)hipHostFree(f.h_list);
-        if (f.r0) (void)hipEventDestroy(f.r0);
-        if (f.r1) (void)hipEventDestroy(f.r1);
-        if (f.b0) (void)hipEventDestroy(f.b0);
-        if (f.b1) (void)hipEventDestroy(f.b1);
-        if (f.e0) (void)hipEventDestroy(f.e0);
-        if (f.e1) (void)hipEventDestroy(f.e1);
-        if (f.done) (void)hipEventDestroy(f.done);
-        f = Flight();
-    }
-    for (auto& e : tev) if (e) (void)hipEventDestroy(e);
-    d_acc = nullptr; d_out = nullptr; d_seeds = nullptr; d_tlog = nullptr; d_olog = nullptr; d_tlen = nullptr; d_prof = nullptr;
-    d_tlog_b = nullptr; d_olog_b = nullptr; d_tlen_b = nullptr; d_out_b = nullptr; d_drec = nullptr; d_dctx = nullptr;
-    tlog_b_cap = olog_b_cap = tlen_b_cap = out_b_cap = drec_cap = dctx_cap = 0;
-    ev0 = ev1 = nullptr; pipe_begin = nullptr; out_cap = seeds_cap = tlog_cap = olog_cap = tlen_cap = 0;
-    for (auto& e : tev) e = nullptr;
+    static_cast<madsim_hip_resources&>(*this) = madsim_hip_resources();
     device = -1;
 }
 
@@ -311,18 +319,17 @@ int madsim_hip_ctx::upload_workload(const madsim_workload_t* w, KParams& P) {
     if (!hit) {
         if (tables.size() >= 16) {                       // bounded cache: drop everything once nothing is in flight
             HIP_TRY(hipDeviceSynchronize());
-            for (auto& t : tables) free_tables(t);
             tables.clear();
         }
         Tables t;
         t.hash = h;
-        auto up = [&]() -> int {
-            HIP_TRY(hipMalloc(&t.insns, T.insns.size() * 4 + 16));
-            HIP_TRY(hipMalloc(&t.progs, T.progs.size() * 4 + 16));
-            HIP_TRY(hipMalloc(&t.socks, T.socks.size() * 4 + 16));
-            HIP_TRY(hipMalloc(&t.durs, T.durs.size() * 8 + 16));
-            HIP_TRY(hipMalloc(&t.nodes, T.nodes.size() * 4 + 16));
-            HIP_TRY(hipMalloc(&t.iter_est, ITER_KEYS * sizeof(uint32_t)));
+        auto up = [&]() -> int {                         // (16 bytes of slack behind each table)
+            HIP_TRY(t.insns.room(T.insns.size() + 4));
+            HIP_TRY(t.progs.room(T.progs.size() + 4));
+            HIP_TRY(t.socks.room(T.socks.size() + 4));
+            HIP_TRY(t.durs.room(T.durs.size() + 2));
+            HIP_TRY(t.nodes.room(T.nodes.size() + 4));
+            HIP_TRY(t.iter_est.room(ITER_KEYS));
             HIP_TRY(hipMemset(t.iter_est, 0, ITER_KEYS * sizeof(uint32_t)));
             HIP_TRY(hipMemcpy(t.nodes, T.nodes.data(), T.nodes.size() * 4, hipMemcpyHostToDevice));
             HIP_TRY(hipMemcpy(t.insns, T.insns.data(), T.insns.size() * 4, hipMemcpyHostToDevice));
@@ -331,12 +338,12 @@ int madsim_hip_ctx::upload_workload(const madsim_workload_t* w, KParams& P) {
             HIP_TRY(hipMemcpy(t.durs, T.durs.data(), T.durs.size() * 8, hipMemcpyHostToDevice));
             return 0;
         };
-        if ((rc = up())) { free_tables(t); return rc; }  // no partial allocation survives an error
+        if ((rc = up())) return rc;                      // (no partial allocation survives an error: `t` frees what it holds)
         t.host = std::move(host);
         tables.push_back(std::move(t));
         hit = &tables.back();
     }
-    P.insns = hit->insns; P.progs = hit->progs; P.socks = hit->socks; P.nodes = hit->nodes; P.dur_table = hit->durs;
+    P.insns = (const uint4*)hit->insns.p; P.progs = hit->progs; P.socks = hit->socks; P.nodes = hit->nodes; P.dur_table = hit->durs;
     // (MADSIM_HIP_NO_PRIO=1 in the environment: launches without the progress-based wave priorities of k_main.h — a diagnostic / A-B switch,
     //  results are the same either way)
     // The pass estimate is a property of the launch SHAPE, not of the workload alone: the capacities change the kernel build and the spilled
@@ -359,39 +366,19 @@ int madsim_hip_ctx::ensure_scratch(KParams& P, hipStream_t stream, bool work_que
     if (P.gstate_mode || P.compact) {    // per-lane state blocks of the global-state builds / main-task records of the compact ones (seed_init writes what it reads)
         size_t need = (size_t)P.gs_stride * P.total_lanes;
         if (need >= (1ull << 32)) return fail(MADSIM_E_LIMITS, "global state region exceeds 4 GiB: lower the capacities");
-        if (need > sc.gstate_bytes) {
-            if (sc.gstate) { HIP_TRY(hipStreamSynchronize(stream)); (void)hipFree(sc.gstate); }
-            sc.gstate = nullptr; sc.gstate_bytes = 0;
-            HIP_TRY(hipMalloc(&sc.gstate, need));
-            sc.gstate_bytes = need;
-        }
+        HIP_TRY(sc.gstate.room(need, stream));
         P.gstate = sc.gstate;
     }
     if (P.heap_spill) {
         size_t need = (size_t)P.heap_spill * P.total_lanes * (P.narrow ? 8 : sizeof(uint4));
         if (need >= (1ull << 32)) return fail(MADSIM_E_LIMITS, "heap spill region exceeds 4 GiB: lower heap_spill_slots");
-        if (need > sc.spill_bytes) {
-            if (sc.spill) { HIP_TRY(hipStreamSynchronize(stream)); (void)hipFree(sc.spill); }
-            sc.spill = nullptr; sc.spill_bytes = 0;
-            HIP_TRY(hipMalloc(&sc.spill, need));
-            sc.spill_bytes = need;
-        }
-        P.spill = sc.spill;
+        HIP_TRY(sc.spill.room(need, stream));
+        P.spill = (uint4*)sc.spill.p;
     }
     if (work_queue) {
-        if (!sc.work_ctr) HIP_TRY(hipMalloc(&sc.work_ctr, sizeof(unsigned long long)));
+        HIP_TRY(sc.work_ctr.room(1));
         HIP_TRY(hipMemsetAsync(sc.work_ctr, 0, sizeof(unsigned long long), stream));
         P.work_ctr = sc.work_ctr;
-    }
-    return 0;
-}
-
-int madsim_hip_ctx::ensure_out(size_t count) {
-    if (count > out_cap) {
-        if (d_out) (void)hipFree(d_out);
-        d_out = nullptr; out_cap = 0;
-        HIP_TRY(hipMalloc(&d_out, count * sizeof(madsim_result_t)));
-        out_cap = count;
     }
     return 0;
 }
@@ -457,32 +444,6 @@ int madsim_hip_ctx::run_device(const madsim_workload_t* w, const madsim_config_t
     return 0;
 }
 
-constexpr uint64_t PIPE_BATCH_HOST = 65536 + 32768;     // up to one and a half batches stay one launch
-int run_pipelined_fwd(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t count,
-                      const madsim_limits_t* lim, madsim_result_t* out, unsigned long long* acc6, double* kernel_ms);
-int madsim_hip_ctx::run_host(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t count,
-                             const madsim_limits_t* lim, madsim_result_t* out, madsim_summary_t* summary) {
-    auto t0 = std::chrono::steady_clock::now();
-    int rc;
-    if (count > PIPE_BATCH_HOST) {             // more than one batch: sub-launches kept in flight, copies overlapped (run_pipelined)
-        if ((rc = madsim_geo::validate(w, cfg, &g_err))) return rc;
-        unsigned long long a[6];                     // (`out` may be NULL: summary only — no staging buffers, no copies)
-        double ms = 0.0;
-        madsim_hip_ctx* one[1] = {this};
-        if ((rc = run_pipelined_fwd(one, 1, w, cfg, seed0, count, lim, out, a, &ms))) return rc;
-        if (summary) {
-            summary->first_failing_seed = a[0]; summary->n_failed = a[1]; summary->total_steps = a[2]; summary->total_clock_ns = a[3];
-            summary->kernel_ms = ms; summary->wall_s = since(t0);
-        }
-        return 0;
-    }
-    if ((rc = ensure_out(count))) return rc;
-    madsim_summary_t tmp;
-    if ((rc = run_device(w, cfg, seed0, count, lim, d_out, nullptr, &tmp))) return rc;
-    if (out && count) HIP_TRY(hipMemcpy(out, d_out, count * sizeof(madsim_result_t), hipMemcpyDeviceToHost));
-    if (summary) { *summary = tmp; summary->wall_s = since(t0); }
-    return 0;
-}
 
 // One compacted launch over an arbitrary list of seeds (the re-run of seeds that outgrew a capacity).
 int madsim_hip_ctx::run_list(const madsim_workload_t* w, const madsim_config_t* cfg, const std::vector<uint64_t>& seeds,
@@ -491,13 +452,9 @@ int madsim_hip_ctx::run_list(const madsim_workload_t* w, const madsim_config_t* 
     res.resize(n);
     if (!n) return 0;
     int rc;
-    if ((rc = ensure_out(n))) return rc;
-    if (n > seeds_cap) {
-        if (d_seeds) (void)hipFree(d_seeds);
-        d_seeds = nullptr; seeds_cap = 0;
-        HIP_TRY(hipMalloc(&d_seeds, n * sizeof(uint64_t)));
-        seeds_cap = n;
-    }
+    DevBuf<madsim_result_t>& d_out = trace[0].out;
+    HIP_TRY(d_out.room(n));
+    HIP_TRY(d_seeds.room(n));
     HIP_TRY(hipMemcpy(d_seeds, seeds.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice));
     HIP_TRY(hipEventRecord(ev0, nullptr));
     if ((rc = launch(w, cfg, 0, n, d_seeds, lim, d_out, nullptr))) return rc;
@@ -510,136 +467,27 @@ int madsim_hip_ctx::run_list(const madsim_workload_t* w, const madsim_config_t* 
 }
 
 // Streams, report words, events and result buffers of the first n flights (campaigns and run_pipelined share them; the
-// context's mutex serialises the two).  `staging`: also a page-locked host buffer of `batch` results per flight.  `collect`: also
-// the report words and wave counts of a collecting campaign and room for `records` failure records per flight.  `stats`: also the
-// report and candidate words of a statistics campaign.  `groups` (seeds per batch, 0 = none): also the report words, the keyed table, the
-// slot list and the entry buffer of a grouping campaign — nothing of it exists for the other campaigns.  `diff`: also side B's result buffer and
-// event pair, the report words, the wave counts and room for `diff_records` records of a differential campaign — for that form only.
-int madsim_hip_ctx::ensure_flights(uint32_t n, uint64_t batch, bool staging, bool collect, uint64_t records, bool stats, uint64_t groups, bool diff,
-                                   uint64_t diff_records) {
+// context's mutex serialises the two).  `staging`: also a page-locked host buffer of `batch` results per flight.  What one campaign
+// form needs beyond that its implementation asks of the flight's group for that form (Flight::Collect ... Flight::List).
+int madsim_hip_ctx::ensure_flights(uint32_t n, uint64_t batch, bool staging) {
     if (n > (uint32_t)CAMPAIGN_MAX) return fail(MADSIM_E_ARG, "at most 8 batches in flight");
     hint_hw_queues(n);
-    for (uint32_t i = 0; i < n; i++) {
-        Flight& f = flights[i];
-        if (!f.stream) {
-            HIP_TRY(hipStreamCreateWithFlags(&f.stream, hipStreamNonBlocking));
-            HIP_TRY(hipMalloc(&f.d_acc6, 6 * sizeof(unsigned long long)));
-            HIP_TRY(hipHostMalloc((void**)&f.h_acc6, 6 * sizeof(unsigned long long), hipHostMallocDefault));
-            HIP_TRY(hipEventCreate(&f.e0)); HIP_TRY(hipEventCreate(&f.e1)); HIP_TRY(hipEventCreate(&f.done));
-        }
-        if (batch > f.cap) {
-            if (f.d_out) { HIP_TRY(hipStreamSynchronize(f.stream)); (void)hipFree(f.d_out); }
-            f.d_out = nullptr; f.cap = 0;
-            HIP_TRY(hipMalloc(&f.d_out, batch * sizeof(madsim_result_t)));
-            f.cap = batch;
-        }
-        if (staging && batch > f.h_cap) {
-            if (f.h_out) { HIP_TRY(hipStreamSynchronize(f.stream)); (void)hipHostFree(f.h_out); }
-            f.h_out = nullptr; f.h_cap = 0;
-            HIP_TRY(hipHostMalloc((void**)&f.h_out, batch * sizeof(madsim_result_t), hipHostMallocDefault));
-            f.h_cap = batch;
-        }
-        if (collect && !f.d_rep) {
-            HIP_TRY(hipMalloc(&f.d_rep, 16 * sizeof(unsigned long long)));
-            HIP_TRY(hipHostMalloc((void**)&f.h_rep, 16 * sizeof(unsigned long long), hipHostMallocDefault));
-            HIP_TRY(hipMalloc(&f.d_wcnt, MADSIM_K_COLLECT_WAVES * sizeof(uint32_t)));
-        }
-        if (collect && records > f.rec_cap) {
-            if (f.d_rec) { HIP_TRY(hipStreamSynchronize(f.stream)); (void)hipFree(f.d_rec); }
-            f.d_rec = nullptr; f.rec_cap = 0;
-            HIP_TRY(hipMalloc(&f.d_rec, records * sizeof(madsim_failure_t)));
-            f.rec_cap = records;
-        }
-        if (stats && !f.d_srep) {
-            HIP_TRY(hipMalloc(&f.d_srep, STATS_REP_WORDS * sizeof(unsigned long long)));
-            HIP_TRY(hipHostMalloc((void**)&f.h_srep, STATS_REP_WORDS * sizeof(unsigned long long), hipHostMallocDefault));
-            HIP_TRY(hipMalloc(&f.d_cand, MADSIM_K_STATS_CAND_WORDS * sizeof(unsigned long long)));
-        }
-        if (groups && !f.d_grep) {
-            HIP_TRY(hipMalloc(&f.d_grep, GROUP_REP_WORDS * sizeof(unsigned long long)));
-            HIP_TRY(hipHostMalloc((void**)&f.h_grep, GROUP_REP_WORDS * sizeof(unsigned long long), hipHostMallocDefault));
-        }
-        if (groups > f.grp_cap) {
-            if (f.d_gtab) { HIP_TRY(hipStreamSynchronize(f.stream)); (void)hipFree(f.d_gtab); (void)hipFree(f.d_glist); (void)hipFree(f.d_gent); }
-            f.d_gtab = nullptr; f.d_glist = nullptr; f.d_gent = nullptr; f.grp_cap = 0;
-            HIP_TRY(hipMalloc(&f.d_gtab, madsim_k_group_slots(groups) * MADSIM_K_GROUP_SLOT_BYTES));
-            HIP_TRY(hipMalloc(&f.d_glist, groups * sizeof(uint32_t)));
-            HIP_TRY(hipMalloc(&f.d_gent, groups * sizeof(madsim_group_t)));
-            f.grp_cap = groups; f.grp_dirty = true;
-        }
-        if (groups && f.grp_dirty) {             // a new table, or one that an error left between a batch's two passes: the only time it is cleared whole
-            HIP_TRY(hipMemsetAsync(f.d_gtab, 0, madsim_k_group_slots(f.grp_cap) * MADSIM_K_GROUP_SLOT_BYTES, f.stream));
-            HIP_TRY(hipStreamSynchronize(f.stream));
-            f.grp_dirty = false;
-        }
-        if (diff && !f.d_drep) {
-            unsigned long long init[DIFF_REP_WORDS] = {};                          // the words before a batch: summary6's two minima all-ones, the rest zero
-            init[0] = init[4] = init[8] = init[12] = ~0ull;
-            HIP_TRY(hipMalloc(&f.d_drep, 2 * DIFF_REP_WORDS * sizeof(unsigned long long)));
-            HIP_TRY(hipMemcpy(f.d_drep + DIFF_REP_WORDS, init, sizeof init, hipMemcpyHostToDevice));
-            HIP_TRY(hipHostMalloc((void**)&f.h_drep, DIFF_REP_WORDS * sizeof(unsigned long long), hipHostMallocDefault));
-            HIP_TRY(hipMalloc(&f.d_dwcnt, MADSIM_K_COLLECT_WAVES * sizeof(uint32_t)));
-            HIP_TRY(hipEventCreate(&f.b0)); HIP_TRY(hipEventCreate(&f.b1));
-        }
-        if (diff && batch > f.cap_b) {
-            if (f.d_out_b) { HIP_TRY(hipStreamSynchronize(f.stream)); (void)hipFree(f.d_out_b); }
-            f.d_out_b = nullptr; f.cap_b = 0;
-            HIP_TRY(hipMalloc(&f.d_out_b, batch * sizeof(madsim_result_t)));
-            f.cap_b = batch;
-        }
-        if (diff && diff_records > f.drec_cap) {
-            if (f.d_drec) { HIP_TRY(hipStreamSynchronize(f.stream)); (void)hipFree(f.d_drec); }
-            f.d_drec = nullptr; f.drec_cap = 0;
-            HIP_TRY(hipMalloc(&f.d_drec, diff_records * sizeof(madsim_diff_record_t)));
-            f.drec_cap = diff_records;
-        }
-    }
+    for (uint32_t i = 0; i < n; i++)
+        if (int rc = flights[i].ensure(batch, staging)) return rc;
     return 0;
 }
 
-// The re-run scratch of a resolving campaign's flight, for a batch of n seeds: made when a batch of the flight first needs a round (most
-// campaigns never do), kept with the flight, enlarged — with the flight's stream drained — when a later call brings larger batches.
-int madsim_hip_ctx::ensure_resolve(Flight& f, uint64_t n) {
-    if (!f.d_rcnt) {
-        HIP_TRY(hipMalloc(&f.d_rcnt, (MADSIM_K_RESOLVE_WAVES + 1) * sizeof(uint32_t)));
-        HIP_TRY(hipHostMalloc((void**)&f.h_rcnt, sizeof(uint32_t), hipHostMallocDefault));
-        HIP_TRY(hipEventCreate(&f.r0)); HIP_TRY(hipEventCreate(&f.r1));
-    }
-    const size_t want = std::max<size_t>(n, f.cap);         // the flight's batch size: one allocation per campaign
-    if (want > f.rr_cap) {
-        if (f.rr_cap) HIP_TRY(hipStreamSynchronize(f.stream));
-        if (f.d_seeds) (void)hipFree(f.d_seeds);                // (each on its own: an allocation error may have left some of the three)
-        if (f.d_idx) (void)hipFree(f.d_idx);
-        if (f.d_rerun) (void)hipFree(f.d_rerun);
-        f.d_seeds = nullptr; f.d_idx = nullptr; f.d_rerun = nullptr; f.rr_cap = 0;
-        HIP_TRY(hipMalloc(&f.d_seeds, want * sizeof(uint64_t)));
-        HIP_TRY(hipMalloc(&f.d_idx, want * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc(&f.d_rerun, want * sizeof(madsim_result_t)));
-        f.rr_cap = want;
-    }
-    return 0;
-}
-
-// The list buffers of the first n flights (after ensure_flights), for list campaigns with batches of `batch` seeds: 8 bytes per seed of a
-// batch on the device and as many page-locked on the host, per flight — proportional to batch x flights, never to the length of the list.
-int madsim_hip_ctx::ensure_list(uint32_t n, uint64_t batch) {
-    for (uint32_t i = 0; i < n; i++) {
-        Flight& f = flights[i];
-        if (batch <= f.list_cap) continue;
-        if (f.list_cap) HIP_TRY(hipStreamSynchronize(f.stream));
-        if (f.d_list) (void)hipFree(f.d_list);
-        if (f.h_list) (void)hipHostFree(f.h_list);
-        f.d_list = nullptr; f.h_list = nullptr; f.list_cap = 0;
-        HIP_TRY(hipMalloc(&f.d_list, batch * sizeof(uint64_t)));
-        HIP_TRY(hipHostMalloc((void**)&f.h_list, batch * sizeof(uint64_t), hipHostMallocDefault));
-        f.list_cap = batch;
-    }
-    return 0;
-}
-
-namespace { uint32_t flights_of(madsim_hip_ctx* c, const madsim_workload_t* w, const madsim_config_t* cfg, const madsim_limits_t* lim, uint64_t batch); }
+// Batches in flight by the workload's occupancy: a batch of 65 536 seeds is one wave per SIMD, so as many batches as the
+// workload's LDS admits waves per SIMD, and — when that is four (the compact base-op layout) — a fifth, whose launch queues behind
+// them and fills the gaps their tails leave.
 uint32_t madsim_hip_ctx::flights_for(const madsim_workload_t* w, const madsim_config_t* cfg, const madsim_limits_t* lim, uint64_t batch) {
-    return flights_of(this, w, cfg, lim, batch);
+    madsim_geo::Geo G;
+    uint32_t n = 3;
+    if (!madsim_geo::make_geometry(dev(), w, cfg, lim, batch, &G, &g_err)) {
+        if (G.blocks_per_cu * G.waves_per_block >= 16) n = 5;
+        else if (G.P.gstate_mode && G.P.heap_spill) n = 4;      // long launches that end with their slowest wave: one more behind them
+    }
+    return n;
 }
 
 namespace {
@@ -719,18 +567,6 @@ void host_summary(const madsim_result_t* out, uint64_t seed0, uint64_t count, ma
     }
 }
 
-// Batches in flight by the workload's occupancy: a batch of 65 536 seeds is one wave per SIMD, so as many batches as the
-// workload's LDS admits waves per SIMD, and — when that is four (the compact base-op layout) — a fifth, whose launch queues behind
-// them and fills the gaps their tails leave.
-uint32_t flights_of(madsim_hip_ctx* c, const madsim_workload_t* w, const madsim_config_t* cfg, const madsim_limits_t* lim, uint64_t batch) {
-    madsim_geo::Geo G;
-    uint32_t n = 3;
-    if (!madsim_geo::make_geometry(c->dev(), w, cfg, lim, batch, &G, &g_err)) {
-        if (G.blocks_per_cu * G.waves_per_block >= 16) n = 5;
-        else if (G.P.gstate_mode && G.P.heap_spill) n = 4;      // long launches that end with their slowest wave: one more behind them
-    }
-    return n;
-}
 
 // Per-seed results at the overlapped rate (one launch of 65 536 seeds is one wave per SIMD and leaves two
 // thirds of the issue slots idle).  Builder::run hands over ALL its seeds in one call (runtime/builder.rs:121-162), so the call
@@ -769,16 +605,17 @@ int run_pipelined(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workload_
         int e;
         if ((e = p.c->bind())) return e;
         if (k < p.F) {                                           // the flight's first sub-batch of this call: a fresh report
-            HIP_TRY(hipMemsetAsync(f.d_acc6, 0xff, 8, f.stream));
-            HIP_TRY(hipMemsetAsync((char*)f.d_acc6 + 8, 0, 24, f.stream));
-            HIP_TRY(hipMemsetAsync((char*)f.d_acc6 + 32, 0xff, 8, f.stream));
-            HIP_TRY(hipMemsetAsync((char*)f.d_acc6 + 40, 0, 8, f.stream));
+            char* const d_words = (char*)f.d_rep.p;
+            HIP_TRY(hipMemsetAsync(d_words, 0xff, 8, f.stream));
+            HIP_TRY(hipMemsetAsync(d_words + 8, 0, 24, f.stream));
+            HIP_TRY(hipMemsetAsync(d_words + 32, 0xff, 8, f.stream));
+            HIP_TRY(hipMemsetAsync(d_words + 40, 0, 8, f.stream));
         }
         if (k == 0) HIP_TRY(hipEventRecord(p.c->pipe_begin, f.stream));
         p.launched++;                                            // from here on the flight must be drained before returning
         if ((e = p.c->launch(w, cfg, seed0 + lo, n, nullptr, lim, f.d_out, f.stream))) return e;
         HIP_TRY(hipEventRecord(f.e1, f.stream));
-        madsim_k_launch_summary6(f.d_out, n, seed0 + lo, f.d_acc6, f.stream);
+        madsim_k_launch_summary6(f.d_out, n, seed0 + lo, f.d_rep, f.stream);
         HIP_TRY(hipGetLastError());
         if (out) HIP_TRY(hipMemcpyAsync(f.h_out, f.d_out, n * sizeof(madsim_result_t), hipMemcpyDeviceToHost, f.stream));
         HIP_TRY(hipEventRecord(f.done, f.stream));
@@ -824,10 +661,10 @@ int run_pipelined(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workload_
         if ((e = p.c->bind())) return e;
         for (uint32_t i = 0; i < p.F; i++) {
             madsim_hip_ctx::Flight& f = p.c->flights[i];
-            HIP_TRY(hipMemcpyAsync(f.h_acc6, f.d_acc6, 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost, f.stream));
+            HIP_TRY(hipMemcpyAsync(f.h_rep, f.d_rep, 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost, f.stream));
             HIP_TRY(hipStreamSynchronize(f.stream));
-            a[0] = std::min(a[0], f.h_acc6[0]); a[4] = std::min(a[4], f.h_acc6[4]);
-            a[1] += f.h_acc6[1]; a[2] += f.h_acc6[2]; a[3] += f.h_acc6[3]; a[5] += f.h_acc6[5];
+            a[0] = std::min(a[0], f.h_rep[0]); a[4] = std::min(a[4], f.h_rep[4]);
+            a[1] += f.h_rep[1]; a[2] += f.h_rep[2]; a[3] += f.h_rep[3]; a[5] += f.h_rep[5];
         }
         ms = std::max(ms, p.ms);                                 // devices ran concurrently
     }
@@ -837,27 +674,54 @@ int run_pipelined(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workload_
 }
 
 }  // namespace
-int run_pipelined_fwd(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t count,
-                      const madsim_limits_t* lim, madsim_result_t* out, unsigned long long* acc6, double* kernel_ms) {
-    return run_pipelined(ctxs, n_ctx, w, cfg, seed0, count, lim, out, acc6, kernel_ms);
-}
-namespace {
 
-// a context buffer grown to `want` elements (never shrunk; the old contents are not kept)
-template <class T>
-hipError_t room(T*& d, size_t& have, size_t want) {
-    if (want <= have) return hipSuccess;
-    if (d) (void)hipFree(d);
-    d = nullptr; have = 0;
-    hipError_t e = hipMalloc((void**)&d, want * sizeof *d);
-    if (e == hipSuccess) have = want;
-    return e;
+constexpr uint64_t PIPE_BATCH_HOST = 65536 + 32768;     // up to one and a half batches stay one launch
+int madsim_hip_ctx::run_host(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t count,
+                             const madsim_limits_t* lim, madsim_result_t* out, madsim_summary_t* summary) {
+    auto t0 = std::chrono::steady_clock::now();
+    int rc;
+    if (count > PIPE_BATCH_HOST) {             // more than one batch: sub-launches kept in flight, copies overlapped (run_pipelined)
+        if ((rc = madsim_geo::validate(w, cfg, &g_err))) return rc;
+        unsigned long long a[6];                     // (`out` may be NULL: summary only — no staging buffers, no copies)
+        double ms = 0.0;
+        madsim_hip_ctx* one[1] = {this};
+        if ((rc = run_pipelined(one, 1, w, cfg, seed0, count, lim, out, a, &ms))) return rc;
+        if (summary) {
+            summary->first_failing_seed = a[0]; summary->n_failed = a[1]; summary->total_steps = a[2]; summary->total_clock_ns = a[3];
+            summary->kernel_ms = ms; summary->wall_s = since(t0);
+        }
+        return 0;
+    }
+    DevBuf<madsim_result_t>& d_out = trace[0].out;
+    HIP_TRY(d_out.room(count));
+    madsim_summary_t tmp;
+    if ((rc = run_device(w, cfg, seed0, count, lim, d_out, nullptr, &tmp))) return rc;
+    if (out && count) HIP_TRY(hipMemcpy(out, d_out, count * sizeof(madsim_result_t), hipMemcpyDeviceToHost));
+    if (summary) { *summary = tmp; summary->wall_s = since(t0); }
+    return 0;
 }
+
+namespace {
 
 #define CTX_ENTER(c)                                                                              \
     if (!(c) || (c)->device < 0) return fail(MADSIM_E_NOINIT, "no context (madsim_hip_init / madsim_hip_ctx_create has not been called)"); \
     std::lock_guard<std::mutex> lk((c)->mu);                                                      \
     { int brc_ = (c)->bind(); if (brc_) return brc_; }
+
+// The contexts of a _multi call, checked and locked in address order (two threads passing the same contexts in different orders cannot
+// deadlock).  `who` names the entry point in "needs at least one context".
+int lock_contexts(madsim_hip_ctx* const* ctxs, int n_ctx, const char* who, std::vector<std::unique_lock<std::mutex>>& locks) {
+    if (!ctxs || n_ctx < 1) return fail(MADSIM_E_ARG, std::string(who) + " needs at least one context");
+    for (int g = 0; g < n_ctx; g++) {
+        if (!ctxs[g]) return fail(MADSIM_E_NOINIT, "null context");
+        for (int h = 0; h < g; h++) if (ctxs[h] == ctxs[g]) return fail(MADSIM_E_ARG, "the same context appears twice");
+    }
+    std::vector<madsim_hip_ctx*> order(ctxs, ctxs + n_ctx);
+    std::sort(order.begin(), order.end(), [](madsim_hip_ctx* a, madsim_hip_ctx* b) { return std::less<madsim_hip_ctx*>()(a, b); });
+    for (madsim_hip_ctx* c : order) locks.emplace_back(c->mu);
+    for (int g = 0; g < n_ctx; g++) if (ctxs[g]->device < 0) return fail(MADSIM_E_NOINIT, "closed context");
+    return 0;
+}
 
 }  // namespace
 
@@ -940,10 +804,10 @@ int madsim_hip_ctx_run_batch_async(madsim_hip_ctx_t* c, const madsim_workload_t*
     CTX_ENTER(c);
     if (timing_slot >= 64) return fail(MADSIM_E_ARG, "timing_slot must be < 64");
     hipStream_t st = (hipStream_t)stream;
-    hipEvent_t* ev = nullptr;
+    Event* ev = nullptr;
     if (timing_slot >= 0) {
         ev = &c->tev[2 * timing_slot];
-        if (!ev[0]) { HIP_TRY(hipEventCreate(&ev[0])); HIP_TRY(hipEventCreate(&ev[1])); }
+        HIP_TRY(ev[0].ensure()); HIP_TRY(ev[1].ensure());
         HIP_TRY(hipEventRecord(ev[0], st));
     }
     int rc = c->run_device(w, cfg, seed0, count, lim, (madsim_result_t*)d_out, st, nullptr);
@@ -964,7 +828,7 @@ int madsim_hip_ctx_run_batch_async(madsim_hip_ctx_t* c, const madsim_workload_t*
 
 int madsim_hip_ctx_timing_ms(madsim_hip_ctx_t* c, int timing_slot, double* ms) {
     CTX_ENTER(c);
-    if (timing_slot < 0 || timing_slot >= 64 || !c->tev[2 * timing_slot] || !ms) return fail(MADSIM_E_ARG, "bad timing slot");
+    if (timing_slot < 0 || timing_slot >= 64 || !c->tev[2 * timing_slot + 1] || !ms) return fail(MADSIM_E_ARG, "bad timing slot");
     float f = 0.f;
     HIP_TRY(hipEventSynchronize(c->tev[2 * timing_slot + 1]));
     HIP_TRY(hipEventElapsedTime(&f, c->tev[2 * timing_slot], c->tev[2 * timing_slot + 1]));
@@ -1009,7 +873,7 @@ int madsim_hip_ctx_run_batch_auto(madsim_hip_ctx_t* c, const madsim_workload_t* 
     return 0;
 }
 
-// One side of a trace call.  trace_prepare: geometry, tables, scratch, the side's buffer set (madsim_hip_ctx::trace_set) grown to the call's
+// One side of a trace call.  trace_prepare: geometry, tables, scratch, the side's buffer set (madsim_hip_ctx::trace) grown to the call's
 // sizes and the parameter block filled — nothing is queued.  trace_queue: the set zeroed and the trace launch, behind whatever the stream
 // holds; TraceSteps keeps the first error and queues nothing behind it.  Shared by madsim_hip_trace_seeds, madsim_hip_trace_seed (side A's
 // set alone) and both sides of madsim_hip_diverge_seeds.
@@ -1021,17 +885,17 @@ struct TraceSteps {
 };
 
 static int trace_prepare(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, const madsim_limits_t* lim, uint64_t n,
-                         uint64_t log_cap, uint64_t obs_cap, madsim_hip_ctx::TraceSet S, Geo& G, hipStream_t st) {
+                         uint64_t log_cap, uint64_t obs_cap, madsim_hip_ctx::TraceSet& S, Geo& G, hipStream_t st) {
     int rc;
     if ((rc = madsim_geo::make_geometry(c->dev(), w, cfg, lim, n, &G, &g_err, true))) return rc;
     G.P.count = n;
     if ((rc = c->upload_workload(w, G.P))) return rc;
     if ((rc = c->ensure_scratch(G.P, st, false))) return rc;
-    HIP_TRY(room(S.log, S.log_have, (size_t)(n * log_cap)));
-    HIP_TRY(room(S.obs, S.obs_have, (size_t)(n * obs_cap)));
-    HIP_TRY(room(S.len, S.len_have, (size_t)(2 * n)));                       // [n] log lengths, then [n] observation counts
-    HIP_TRY(room(c->d_seeds, c->seeds_cap, (size_t)n));
-    HIP_TRY(room(S.out, S.out_have, (size_t)n));
+    HIP_TRY(S.log.room((size_t)(n * log_cap)));
+    HIP_TRY(S.obs.room((size_t)(n * obs_cap)));
+    HIP_TRY(S.len.room((size_t)(2 * n)));                                    // [n] log lengths, then [n] observation counts
+    HIP_TRY(c->d_seeds.room((size_t)n));
+    HIP_TRY(S.out.room((size_t)n));
     if (G.lds_bytes > c->lds_attr) {
         if (madsim_k_set_max_lds((uint32_t)c->lds_per_cu)) return fail(MADSIM_E_HIP, "hipFuncSetAttribute failed");
         c->lds_attr = (uint32_t)c->lds_per_cu;
@@ -1042,7 +906,7 @@ static int trace_prepare(madsim_hip_ctx_t* c, const madsim_workload_t* w, const 
     return 0;
 }
 
-static bool trace_queue(const Geo& G, madsim_hip_ctx::TraceSet S, uint64_t n, uint64_t log_cap, uint64_t obs_cap, bool zero_log, hipStream_t st,
+static bool trace_queue(const Geo& G, const madsim_hip_ctx::TraceSet& S,uint64_t n, uint64_t log_cap, uint64_t obs_cap, bool zero_log, hipStream_t st,
                         TraceSteps& step, bool ok) {
     if (ok && log_cap && zero_log) ok = step(hipMemsetAsync(S.log, 0, n * log_cap, st), "hipMemsetAsync(log rows)");
     if (ok && obs_cap) ok = step(hipMemsetAsync(S.obs, 0, n * obs_cap * sizeof(uint64_t), st), "hipMemsetAsync(observation rows)");
@@ -1083,7 +947,7 @@ static int trace_list(madsim_hip_ctx_t* c, const madsim_workload_t* w, const mad
     if (rc) return rc;
     Geo G;
     hipStream_t st = nullptr;
-    const madsim_hip_ctx::TraceSet S = c->trace_set(0);
+    madsim_hip_ctx::TraceSet& S = c->trace[0];
     if ((rc = trace_prepare(c, w, cfg, lim, n, log_cap, obs_cap, S, G, st))) return rc;
     uint64_t* d_olen = S.len + n;
     // from here on the stream may hold work on the caller's memory: every step is tried only while all before it succeeded, and the
@@ -1137,11 +1001,11 @@ int madsim_hip_ctx_diverge_seeds(madsim_hip_ctx_t* c, const madsim_workload_t* w
     CTX_ENTER(c);
     int rc;
     hipStream_t st = nullptr;
-    const madsim_hip_ctx::TraceSet SA = c->trace_set(0), SB = c->trace_set(1);
+    madsim_hip_ctx::TraceSet &SA = c->trace[0], &SB = c->trace[1];
     Geo GA, GB;
     if ((rc = trace_prepare(c, wA, cfgA, limA, n, log_cap, obs_cap, SA, GA, st))) return fail(rc, "side A: " + g_err);
-    HIP_TRY(room(c->d_drec, c->drec_cap, (size_t)n));
-    HIP_TRY(room(c->d_dctx, c->dctx_cap, (size_t)(3ull * win * n)));
+    HIP_TRY(c->d_drec.room((size_t)n));
+    HIP_TRY(c->d_dctx.room((size_t)(3ull * win * n)));
     TraceSteps step;
     bool ok = step(hipMemcpyAsync(c->d_seeds, seeds, n * sizeof(uint64_t), hipMemcpyHostToDevice, st), "hipMemcpyAsync(seeds)");
     ok = trace_queue(GA, SA, n, log_cap, obs_cap, true, st, step, ok);
@@ -1209,19 +1073,11 @@ int madsim_hip_run_batch_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const m
                                uint64_t seed0, uint64_t count, const madsim_limits_t* lim, madsim_result_t* out,
                                madsim_summary_t* summary, int max_rounds) {
     auto t0 = std::chrono::steady_clock::now();
-    if (!ctxs || n_ctx < 1) return fail(MADSIM_E_ARG, "run_batch_multi needs at least one context");
     if (!out && count) return fail(MADSIM_E_ARG, "run_batch_multi needs the result array");
-    for (int g = 0; g < n_ctx; g++) {
-        if (!ctxs[g]) return fail(MADSIM_E_NOINIT, "null context");
-        for (int h = 0; h < g; h++) if (ctxs[h] == ctxs[g]) return fail(MADSIM_E_ARG, "the same context appears twice");
-    }
-    int rc = madsim_geo::validate(w, cfg, &g_err);
+    int rc = madsim_geo::validate(w, cfg, &g_err);             // (before any lock is taken)
     if (rc) return rc;
-    std::vector<madsim_hip_ctx*> order(ctxs, ctxs + n_ctx);
-    std::sort(order.begin(), order.end(), [](madsim_hip_ctx* a, madsim_hip_ctx* b) { return std::less<madsim_hip_ctx*>()(a, b); });
     std::vector<std::unique_lock<std::mutex>> locks;
-    for (madsim_hip_ctx* c : order) locks.emplace_back(c->mu);
-    for (int g = 0; g < n_ctx; g++) if (ctxs[g]->device < 0) return fail(MADSIM_E_NOINIT, "closed context");
+    if ((rc = lock_contexts(ctxs, n_ctx, "run_batch_multi", locks))) return rc;
     // 1 + 2. every device's sub-batches and their device-to-host copies are queued from this thread, each device keeping as many
     //        in flight as the workload's occupancy rewards; finished sub-batches move into the caller's array while the rest run
     double kernel_ms = 0.0;
@@ -1367,7 +1223,61 @@ uint64_t pump_batches(madsim_hip_ctx* const* ctxs, int n_ctx, uint64_t n_batches
     }
     return launched;
 }
+
+// The flights of a campaign call.  F[g]: how many context g keeps in flight — the caller's number, else what the workload's occupancy
+// rewards (`occupancy(context)`), no more than the context has batches.  setup() makes them ready: what every flight has
+// (ensure_flights), what the campaign's form adds (`ensure_form(flight)`) and, for a list campaign, the list buffers.
+struct CampaignFlights {
+    madsim_hip_ctx* const* ctxs; uint64_t N; std::vector<uint32_t> F;
+    CampaignFlights(madsim_hip_ctx* const* c, int n) : ctxs(c), N((uint64_t)n), F(n) {}
+    madsim_hip_ctx::Flight& of(uint64_t k) const { const uint64_t g = k % N; return ctxs[g]->flights[(k / N) % F[g]]; }
+    template <class Occupancy, class EnsureForm>
+    int setup(uint64_t n_batches, uint64_t batch, uint64_t width, uint32_t in_flight, bool list, Occupancy occupancy, EnsureForm ensure_form) {
+        for (uint64_t g = 0; g < N; g++) {
+            madsim_hip_ctx* c = ctxs[g];
+            int rc;
+            if ((rc = c->bind())) return rc;
+            const uint64_t mine = (n_batches + N - 1 - g) / N;      // batches g, g + n, g + 2n, ...
+            uint32_t f = in_flight ? in_flight : occupancy(c);
+            if ((uint64_t)f > mine) f = (uint32_t)mine;
+            F[g] = f;
+            if (f && (rc = c->ensure_flights(f, batch, false))) return rc;
+            for (uint32_t i = 0; i < f; i++) {
+                madsim_hip_ctx::Flight& fl = c->flights[i];
+                if ((rc = ensure_form(fl))) return rc;
+                if (list && (rc = fl.list.ensure(width, fl.stream))) return rc;
+            }
+        }
+        return 0;
+    }
+};
 }  // extern "C++"
+
+// What every campaign form checks of its range first (batch 0 = the default).
+int check_campaign_range(uint64_t& batch, uint32_t in_flight, bool list, uint64_t seed0, uint64_t total) {
+    if (batch == 0) batch = 65536;
+    if (in_flight > (uint32_t)madsim_hip_ctx::CAMPAIGN_MAX) return fail(MADSIM_E_ARG, "at most 8 batches in flight per context");
+    if (!list && seed0 + total < seed0) return fail(MADSIM_E_ARG, "seed0 + total wraps");
+    return 0;
+}
+
+// A list campaign's batch: its slice list[lo .. lo + n) into the flight, ahead of the launch that reads it (the flight's previous batch
+// has been harvested: both buffers are free).
+int queue_list_slice(madsim_hip_ctx::Flight& f, const uint64_t* list, uint64_t lo, uint64_t n) {
+    memcpy(f.list.h, list + lo, n * sizeof(uint64_t));
+    HIP_TRY(hipMemcpyAsync(f.list.d, f.list.h, n * sizeof(uint64_t), hipMemcpyHostToDevice, f.stream));
+    return 0;
+}
+
+// A harvested batch into its campaign report: a = summary6's six words over the batch's n results, ms = its simulation kernel's time.
+void fold_summary(madsim_campaign_t* out, const unsigned long long* a, uint64_t n, double ms) {
+    out->kernel_ms += ms;
+    out->batches_run++; out->seeds_run += n;
+    out->n_runner += a[5];
+    out->n_failed += a[1] - a[5];
+    out->total_steps += a[2]; out->total_clock_ns += a[3];
+    if (a[4] < out->first_failing_seed) out->first_failing_seed = a[4];
+}
 
 // ---- resolving campaigns (MADSIM_CAMPAIGN_RESOLVE) ---------------------------------------------------------------------------------
 // The rounds a call's flags ask for (0: the call does not resolve), and the one argument error they can hold — told, like the other
@@ -1402,36 +1312,37 @@ int resolve_results(madsim_hip_ctx* c, madsim_hip_ctx::Flight& f, const madsim_w
     madsim_limits_t L{};
     if (lim) L = *lim;
     int e;
-    if ((e = c->ensure_resolve(f, n))) return e;
-    uint32_t* const d_total = f.d_rcnt + MADSIM_K_RESOLVE_WAVES;
+    madsim_hip_ctx::Flight::Resolve& rr = f.resolve;
+    if ((e = rr.ensure(std::max<size_t>(n, f.d_out.cap), f.stream))) return e;      // the flight's batch size: one allocation per campaign
+    uint32_t* const d_total = rr.cnt + MADSIM_K_RESOLVE_WAVES;
     bool timed = false;                                          // an event pair recorded and not yet read
     auto take_ms = [&]() -> int {
         if (!timed) return 0;
         float t = 0.f;
-        HIP_TRY(hipEventElapsedTime(&t, f.r0, f.r1));
+        HIP_TRY(hipEventElapsedTime(&t, rr.r0, rr.r1));
         *rerun_ms += t; timed = false;
         return 0;
     };
     for (uint32_t r = 1; r <= rounds; r++) {
         const uint32_t steps_maxed = (L.max_steps ? L.max_steps : (1u << 24)) >= step_ceiling(L) ? 1u : 0u;
-        if (d_list ? madsim_k_launch_resolve_list_list(d_res, n, d_list, steps_maxed, f.d_rcnt, d_total, f.d_seeds, f.d_idx, f.stream)
-                   : madsim_k_launch_resolve_list(d_res, n, seed_lo, steps_maxed, f.d_rcnt, d_total, f.d_seeds, f.d_idx, f.stream))
+        if (d_list ? madsim_k_launch_resolve_list_list(d_res, n, d_list, steps_maxed, rr.cnt, d_total, rr.seeds, rr.idx, f.stream)
+                   : madsim_k_launch_resolve_list(d_res, n, seed_lo, steps_maxed, rr.cnt, d_total, rr.seeds, rr.idx, f.stream))
             return fail(MADSIM_E_ARG, "madsim_k_launch_resolve_list refused the batch's size");
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(f.h_rcnt, d_total, sizeof(uint32_t), hipMemcpyDeviceToHost, f.stream));
+        HIP_TRY(hipMemcpyAsync(rr.h_cnt, d_total, sizeof(uint32_t), hipMemcpyDeviceToHost, f.stream));
         HIP_TRY(hipStreamSynchronize(f.stream));
         if ((e = take_ms())) return e;
-        const uint64_t m = *f.h_rcnt;
+        const uint64_t m = *rr.h_cnt;
         if (m == 0) break;
-        if (m > n || m > f.rr_cap) return fail(MADSIM_E_HIP, "resolve: a batch lists more re-runnable seeds than it holds");
+        if (m > n || m > rr.rerun.cap) return fail(MADSIM_E_HIP, "resolve: a batch lists more re-runnable seeds than it holds");
         if (r == 1) { acct.n_first_pass += m; acct.batches_resolved++; }
         acct.n_by_round[r - 1] += m;
         grow(L, w, true, true);
-        HIP_TRY(hipEventRecord(f.r0, f.stream));
-        if ((e = c->launch(w, cfg, 0, m, f.d_seeds, &L, f.d_rerun, f.stream))) return e;
-        HIP_TRY(hipEventRecord(f.r1, f.stream));
+        HIP_TRY(hipEventRecord(rr.r0, f.stream));
+        if ((e = c->launch(w, cfg, 0, m, rr.seeds, &L, rr.rerun, f.stream))) return e;
+        HIP_TRY(hipEventRecord(rr.r1, f.stream));
         timed = true;
-        if (madsim_k_launch_resolve_scatter(d_res, f.d_rerun, f.d_idx, m, f.stream))
+        if (madsim_k_launch_resolve_scatter(d_res, rr.rerun, rr.idx, m, f.stream))
             return fail(MADSIM_E_ARG, "madsim_k_launch_resolve_scatter refused the list's size");
         HIP_TRY(hipGetLastError());
         *ran = true;
@@ -1464,40 +1375,38 @@ int run_campaign_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workl
     std::vector<madsim_group_t> gbatch;                          // a batch's entries, as the device left them
     int rc = madsim_geo::validate(w, cfg, &g_err);
     if (rc) return rc;
-    if (batch == 0) batch = 65536;
-    if (in_flight > (uint32_t)madsim_hip_ctx::CAMPAIGN_MAX) return fail(MADSIM_E_ARG, "at most 8 batches in flight per context");
-    if (!list && seed0 + total < seed0) return fail(MADSIM_E_ARG, "seed0 + total wraps");
+    if ((rc = check_campaign_range(batch, in_flight, list != nullptr, seed0, total))) return rc;
     if (total == 0) return 0;
-    if (st && std::min(batch, total) >= 0xffffffffull) return fail(MADSIM_E_ARG, "a statistics campaign's batch holds fewer than 2^32 - 1 seeds");
-    if (R && std::min(batch, total) >= (1ull << 30)) return fail(MADSIM_E_ARG, "a resolving campaign's batch holds fewer than 2^30 seeds");
+    const uint64_t width = std::min(batch, total);              // seeds in the largest batch
+    if (st && width >= 0xffffffffull) return fail(MADSIM_E_ARG, "a statistics campaign's batch holds fewer than 2^32 - 1 seeds");
+    if (R && width >= (1ull << 30)) return fail(MADSIM_E_ARG, "a resolving campaign's batch holds fewer than 2^30 seeds");
     const uint64_t n_batches = (total + batch - 1) / batch, N = (uint64_t)n_ctx;
-    const uint64_t rec_batch = col ? std::min(col->cap, std::min(batch, total)) : 0;      // records a flight holds: no batch lists more
+    const uint64_t rec_batch = col ? std::min(col->cap, width) : 0;      // records a flight holds: no batch lists more
     // a grouping campaign's report: the sixteen words, the statistics words when asked for, then the grouping words; its table is sized to the batch
     const size_t goff = 16 + (st ? MADSIM_K_STATS_WORDS : 0);
-    const uint64_t gslots = grp ? madsim_k_group_slots(std::min(batch, total)) : 0;
+    const uint64_t gslots = grp ? madsim_k_group_slots(width) : 0;
     uint64_t listed_seen = 0;                                   // listed seeds of the batches folded so far (not cut at cap)
-    std::vector<uint32_t> F(n_ctx);                             // flights per context: what its occupancy rewards, no more than it has batches
-    for (int g = 0; g < n_ctx; g++) {
-        if ((rc = ctxs[g]->bind())) return rc;
-        const uint64_t mine = (n_batches + N - 1 - (uint64_t)g) / N;      // batches g, g + n, g + 2n, ...
-        uint32_t f = in_flight ? in_flight : ctxs[g]->flights_for(w, cfg, lim, batch);
-        if ((uint64_t)f > mine) f = (uint32_t)mine;
-        F[g] = f;
-        if (f && (rc = ctxs[g]->ensure_flights(f, batch, false, col != nullptr, rec_batch, st != nullptr, grp ? std::min(batch, total) : 0))) return rc;
-        if (f && list && (rc = ctxs[g]->ensure_list(f, std::min(batch, total)))) return rc;
-    }
+    CampaignFlights flights(ctxs, n_ctx);
+    if ((rc = flights.setup(n_batches, batch, width, in_flight, list != nullptr,
+                            [&](madsim_hip_ctx* c) { return c->flights_for(w, cfg, lim, batch); },
+                            [&](madsim_hip_ctx::Flight& f) -> int {
+                                int e = 0;
+                                if (col) e = f.collect.ensure(rec_batch, f.stream);
+                                if (!e && st) e = f.stats.ensure();
+                                if (!e && grp) e = f.groups.ensure(width, f.stream);
+                                return e;
+                            })))
+        return rc;
     int first_err = 0;
     std::string first_msg;
-    auto flight_of = [&](uint64_t k) -> madsim_hip_ctx::Flight& { const int g = (int)(k % N); return ctxs[g]->flights[(k / N) % F[g]]; };
     // A batch's report chain, in two parts that `queue` puts around the simulation launch and a resolving `harvest` queues again back to
     // back: the report words made ready, then the report kernels over f.d_out, the copy of the words and the `done` event.
     const size_t n_words = grp ? goff + MADSIM_K_GROUP_WORDS
                                : st ? madsim_hip_ctx::STATS_REP_WORDS - (st->top_k ? 0 : 2 * MADSIM_STAT_METRICS * MADSIM_STAT_MAX_TOP)
                                : col ? MADSIM_K_COLLECT_WORDS : 6;
-    auto words_of = [&](madsim_hip_ctx::Flight& f) -> unsigned long long* { return grp ? f.d_grep : st ? f.d_srep : col ? f.d_rep : f.d_acc6; };
     auto prepare_report = [&](madsim_hip_ctx::Flight& f) -> int {
         // the same four memsets, the last one longer when collecting, and longer still with statistics (whose words all start as zero)
-        unsigned long long* const d_words = words_of(f);
+        unsigned long long* const d_words = f.d_rep;
         HIP_TRY(hipMemsetAsync(d_words, 0xff, 8, f.stream));
         HIP_TRY(hipMemsetAsync((char*)d_words + 8, 0, 24, f.stream));
         HIP_TRY(hipMemsetAsync((char*)d_words + 32, 0xff, 8, f.stream));
@@ -1505,78 +1414,70 @@ int run_campaign_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workl
         return 0;
     };
     auto queue_report = [&](madsim_hip_ctx::Flight& f, uint64_t lo, uint64_t n) -> int {
-        unsigned long long* const d_words = words_of(f);
+        unsigned long long* const d_words = f.d_rep;
         const uint32_t list_runner = (flags & MADSIM_CAMPAIGN_LIST_RUNNER) ? 1u : 0u;
-        if (col && list) madsim_k_launch_collect_list(f.d_out, n, f.d_list, list_runner, d_words, f.d_wcnt, f.d_rec, std::min(rec_batch, n), f.stream);
-        else if (col) madsim_k_launch_collect(f.d_out, n, seed0 + lo, list_runner, d_words, f.d_wcnt, f.d_rec, std::min(rec_batch, n), f.stream);
-        else if (list) madsim_k_launch_summary6_list(f.d_out, n, f.d_list, d_words, f.stream);
+        if (col && list) madsim_k_launch_collect_list(f.d_out, n, f.list.d, list_runner, d_words, f.collect.wcnt, f.collect.rec, std::min(rec_batch, n), f.stream);
+        else if (col) madsim_k_launch_collect(f.d_out, n, seed0 + lo, list_runner, d_words, f.collect.wcnt, f.collect.rec, std::min(rec_batch, n), f.stream);
+        else if (list) madsim_k_launch_summary6_list(f.d_out, n, f.list.d, d_words, f.stream);
         else madsim_k_launch_summary6(f.d_out, n, seed0 + lo, d_words, f.stream);
         HIP_TRY(hipGetLastError());
         if (st) {                                                // behind the report kernel, into the words after its sixteen
-            if (list) madsim_k_launch_stats_list(f.d_out, n, f.d_list, st->include, st->top_k, d_words + 16, f.d_cand, f.stream);
-            else madsim_k_launch_stats(f.d_out, n, seed0 + lo, st->include, st->top_k, d_words + 16, f.d_cand, f.stream);
+            if (list) madsim_k_launch_stats_list(f.d_out, n, f.list.d, st->include, st->top_k, d_words + 16, f.stats.cand, f.stream);
+            else madsim_k_launch_stats(f.d_out, n, seed0 + lo, st->include, st->top_k, d_words + 16, f.stats.cand, f.stream);
             HIP_TRY(hipGetLastError());
         }
         if (grp) {                                               // behind them: the batch's groups; their number rides with the report words
-            f.grp_dirty = true;                                  // (until the batch is harvested: its extraction pass has then left the table zero)
-            if (list ? madsim_k_launch_groups_list(f.d_out, n, f.d_list, grp->include, grp->key_field, f.d_gtab, gslots, f.d_glist, d_words + goff, f.d_gent, f.stream)
-                     : madsim_k_launch_groups(f.d_out, n, seed0 + lo, grp->include, grp->key_field, f.d_gtab, gslots, f.d_glist, d_words + goff, f.d_gent, f.stream))
+            f.groups.dirty = true;                               // (until the batch is harvested: its extraction pass has then left the table zero)
+            if (list ? madsim_k_launch_groups_list(f.d_out, n, f.list.d, grp->include, grp->key_field, f.groups.tab, gslots, f.groups.list, d_words + goff, f.groups.ent, f.stream)
+                     : madsim_k_launch_groups(f.d_out, n, seed0 + lo, grp->include, grp->key_field, f.groups.tab, gslots, f.groups.list, d_words + goff, f.groups.ent, f.stream))
                 return fail(MADSIM_E_ARG, "madsim_k_launch_groups refused the batch's sizes");
             HIP_TRY(hipGetLastError());
         }
-        HIP_TRY(hipMemcpyAsync(grp ? f.h_grep : st ? f.h_srep : col ? f.h_rep : f.h_acc6, d_words, n_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, f.stream));
+        HIP_TRY(hipMemcpyAsync(f.h_rep, d_words, n_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, f.stream));
         HIP_TRY(hipEventRecord(f.done, f.stream));
         return 0;
     };
     auto queue = [&](uint64_t k) -> int {
         madsim_hip_ctx* c = ctxs[k % N];
-        madsim_hip_ctx::Flight& f = flight_of(k);
+        madsim_hip_ctx::Flight& f = flights.of(k);
         const uint64_t lo = k * batch, n = std::min(batch, total - lo);
         int e;
         if ((e = c->bind())) return e;
         if ((e = prepare_report(f))) return e;
-        if (list) {                                              // the batch's slice, ahead of the launch that reads it (the flight's previous batch
-            memcpy(f.h_list, list + lo, n * sizeof(uint64_t));   // has been harvested: both buffers are free)
-            HIP_TRY(hipMemcpyAsync(f.d_list, f.h_list, n * sizeof(uint64_t), hipMemcpyHostToDevice, f.stream));
-        }
+        if (list && (e = queue_list_slice(f, list, lo, n))) return e;
         HIP_TRY(hipEventRecord(f.e0, f.stream));
-        if ((e = c->launch(w, cfg, seed0 + lo, n, list ? f.d_list : nullptr, lim, f.d_out, f.stream))) return e;
+        if ((e = c->launch(w, cfg, seed0 + lo, n, list ? f.list.d : nullptr, lim, f.d_out, f.stream))) return e;
         HIP_TRY(hipEventRecord(f.e1, f.stream));
         return queue_report(f, lo, n);
     };
     bool stop = false;
     auto harvest = [&](uint64_t k) -> int {                     // wait for batch k, fold its report (batches are read in order)
         madsim_hip_ctx* c = ctxs[k % N];
-        madsim_hip_ctx::Flight& f = flight_of(k);
+        madsim_hip_ctx::Flight& f = flights.of(k);
         int e;
         if ((e = c->bind())) return e;
         HIP_TRY(hipEventSynchronize(f.done));
-        f.grp_dirty = false;                                    // (both grouping passes of the batch, if any, have run)
+        f.groups.dirty = false;                                 // (both grouping passes of the batch, if any, have run)
         if (first_err) return 0;                                // (draining after an error: nothing is folded any more)
         const uint64_t lo = k * batch, n = std::min(batch, total - lo);
         float ms = 0.f;
         HIP_TRY(hipEventElapsedTime(&ms, f.e0, f.e1));
         if (!stop) {                                            // batches launched beyond the failing one are not part of the answer
-            const unsigned long long* a = grp ? f.h_grep : st ? f.h_srep : col ? f.h_rep : f.h_acc6;
+            const unsigned long long* a = f.h_rep;
             if (R && a[5] > 0) {                                // runner verdicts in a batch that is part of the answer: settle them, report again
                 const unsigned long long runner_before = a[5];
                 double rerun_ms = 0.0;
                 bool ran = false;
-                if ((e = resolve_results(c, f, w, cfg, lim, f.d_out, seed0 + lo, list ? f.d_list : nullptr, n, R, acct, &rerun_ms, &ran))) return e;
+                if ((e = resolve_results(c, f, w, cfg, lim, f.d_out, seed0 + lo, list ? f.list.d : nullptr, n, R, acct, &rerun_ms, &ran))) return e;
                 acct.rerun_kernel_ms += rerun_ms; out->kernel_ms += rerun_ms;
                 if (ran) {                                      // (the grouping table is clean: the first chain's extraction pass left it so)
                     if ((e = prepare_report(f)) || (e = queue_report(f, lo, n))) return e;
                     HIP_TRY(hipEventSynchronize(f.done));
-                    f.grp_dirty = false;
+                    f.groups.dirty = false;
                     acct.n_resolved += runner_before - a[5];
                 }
             }
-            out->kernel_ms += ms;
-            out->batches_run++; out->seeds_run += n;
-            out->n_runner += a[5];
-            out->n_failed += a[1] - a[5];
-            out->total_steps += a[2]; out->total_clock_ns += a[3];
-            if (a[4] < out->first_failing_seed) out->first_failing_seed = a[4];
+            fold_summary(out, a, n, ms);
             if ((flags & MADSIM_CAMPAIGN_STOP_AT_FAILURE) && a[4] != UINT64_MAX) stop = true;
             if (col) {
                 for (int v = 0; v < 8; v++) col->n_by_verdict[v] += a[6 + v];
@@ -1584,7 +1485,7 @@ int run_campaign_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workl
                 // The stream is idle (its `done` has passed) and takes no launch before this returns.
                 const uint64_t take = std::min<uint64_t>(std::min<uint64_t>(a[14], std::min(rec_batch, n)), col->cap - col->n_listed);
                 if (take) {
-                    HIP_TRY(hipMemcpyAsync(col->failures + col->n_listed, f.d_rec, take * sizeof(madsim_failure_t), hipMemcpyDeviceToHost, f.stream));
+                    HIP_TRY(hipMemcpyAsync(col->failures + col->n_listed, f.collect.rec, take * sizeof(madsim_failure_t), hipMemcpyDeviceToHost, f.stream));
                     HIP_TRY(hipStreamSynchronize(f.stream));
                     col->n_listed += take;
                 }
@@ -1599,7 +1500,7 @@ int run_campaign_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workl
                                                   std::to_string(a[goff + 1]) + ", " + std::to_string(ng) + " groups)");
                 if (ng) {                                       // the batch's entries, only when there are some and only that many (the stream is idle)
                     gbatch.resize(ng);
-                    HIP_TRY(hipMemcpyAsync(gbatch.data(), f.d_gent, ng * sizeof(madsim_group_t), hipMemcpyDeviceToHost, f.stream));
+                    HIP_TRY(hipMemcpyAsync(gbatch.data(), f.groups.ent, ng * sizeof(madsim_group_t), hipMemcpyDeviceToHost, f.stream));
                     HIP_TRY(hipStreamSynchronize(f.stream));
                     madsim_k_fold_groups(grp, gstate.p, gbatch.data(), ng, list ? list[lo] : seed0 + lo);
                 }
@@ -1608,7 +1509,7 @@ int run_campaign_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workl
         }
         return 0;
     };
-    out->batches_launched = pump_batches(ctxs, n_ctx, n_batches, F, stop, first_err, first_msg, queue, harvest);
+    out->batches_launched = pump_batches(ctxs, n_ctx, n_batches, flights.F, stop, first_err, first_msg, queue, harvest);
     out->wall_s = since(t0);
     return first_err ? fail(first_err, first_msg) : 0;
 }
@@ -1631,77 +1532,68 @@ int run_campaign_diff_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const DiffSid
     madsim_resolve_t& acct = account.a;
     for (int s = 0; s < 2; s++)
         if (int rc = madsim_geo::validate(side[s].w, side[s].cfg, &g_err)) return fail(rc, std::string(s ? "side B: " : "side A: ") + g_err);
-    if (batch == 0) batch = 65536;
-    if (in_flight > (uint32_t)madsim_hip_ctx::CAMPAIGN_MAX) return fail(MADSIM_E_ARG, "at most 8 batches in flight per context");
-    if (!list && seed0 + total < seed0) return fail(MADSIM_E_ARG, "seed0 + total wraps");
-    if (total == 0) return 0;
-    if (std::min(batch, total) >= (1ull << 32)) return fail(MADSIM_E_ARG, "a differential campaign's batch holds fewer than 2^32 seeds");
-    if (R && std::min(batch, total) >= (1ull << 30)) return fail(MADSIM_E_ARG, "a resolving campaign's batch holds fewer than 2^30 seeds");
-    const uint64_t n_batches = (total + batch - 1) / batch, N = (uint64_t)n_ctx;
-    const uint64_t rec_batch = std::min(d->cap, std::min(batch, total));      // records a flight holds: no batch lists more
     int rc;
-    std::vector<uint32_t> F(n_ctx);
-    for (int g = 0; g < n_ctx; g++) {
-        if ((rc = ctxs[g]->bind())) return rc;
-        const uint64_t mine = (n_batches + N - 1 - (uint64_t)g) / N;
-        uint32_t f = in_flight ? in_flight
-                               : std::min(ctxs[g]->flights_for(side[0].w, side[0].cfg, side[0].lim, batch), ctxs[g]->flights_for(side[1].w, side[1].cfg, side[1].lim, batch));
-        if ((uint64_t)f > mine) f = (uint32_t)mine;
-        F[g] = f;
-        if (f && (rc = ctxs[g]->ensure_flights(f, batch, false, false, 0, false, 0, true, rec_batch))) return rc;
-        if (f && list && (rc = ctxs[g]->ensure_list(f, std::min(batch, total)))) return rc;
-    }
+    if ((rc = check_campaign_range(batch, in_flight, list != nullptr, seed0, total))) return rc;
+    if (total == 0) return 0;
+    const uint64_t width = std::min(batch, total);
+    if (width >= (1ull << 32)) return fail(MADSIM_E_ARG, "a differential campaign's batch holds fewer than 2^32 seeds");
+    if (R && width >= (1ull << 30)) return fail(MADSIM_E_ARG, "a resolving campaign's batch holds fewer than 2^30 seeds");
+    const uint64_t n_batches = (total + batch - 1) / batch, N = (uint64_t)n_ctx;
+    const uint64_t rec_batch = std::min(d->cap, width);      // records a flight holds: no batch lists more
+    CampaignFlights flights(ctxs, n_ctx);
+    if ((rc = flights.setup(n_batches, batch, width, in_flight, list != nullptr,
+                            [&](madsim_hip_ctx* c) {
+                                return std::min(c->flights_for(side[0].w, side[0].cfg, side[0].lim, batch), c->flights_for(side[1].w, side[1].cfg, side[1].lim, batch));
+                            },
+                            [&](madsim_hip_ctx::Flight& f) { return f.diff.ensure(batch, rec_batch, f.stream); })))
+        return rc;
     constexpr size_t n_words = madsim_hip_ctx::DIFF_REP_WORDS;
     int first_err = 0;
     std::string first_msg;
     bool stop = false;
-    auto flight_of = [&](uint64_t k) -> madsim_hip_ctx::Flight& { const int g = (int)(k % N); return ctxs[g]->flights[(k / N) % F[g]]; };
     // A batch's report chain in the parts that `queue` puts around the two simulation launches and a resolving `harvest` queues again back
     // to back: the words reset by one device copy, a side's summary6 over its results, then the diff kernels, the copy and the `done` event.
     auto prepare_report = [&](madsim_hip_ctx::Flight& f) -> int {
-        HIP_TRY(hipMemcpyAsync(f.d_drep, f.d_drep + n_words, n_words * sizeof(unsigned long long), hipMemcpyDeviceToDevice, f.stream));
+        HIP_TRY(hipMemcpyAsync(f.diff.d_rep, f.diff.d_rep + n_words, n_words * sizeof(unsigned long long), hipMemcpyDeviceToDevice, f.stream));
         return 0;
     };
     auto queue_summary = [&](madsim_hip_ctx::Flight& f, int s, uint64_t lo, uint64_t n) -> int {
-        if (list) madsim_k_launch_summary6_list(s ? f.d_out_b : f.d_out, n, f.d_list, f.d_drep + 8 * s, f.stream);
-        else madsim_k_launch_summary6(s ? f.d_out_b : f.d_out, n, seed0 + lo, f.d_drep + 8 * s, f.stream);
+        if (list) madsim_k_launch_summary6_list(s ? f.diff.out_b : f.d_out, n, f.list.d, f.diff.d_rep + 8 * s, f.stream);
+        else madsim_k_launch_summary6(s ? f.diff.out_b : f.d_out, n, seed0 + lo, f.diff.d_rep + 8 * s, f.stream);
         HIP_TRY(hipGetLastError());
         return 0;
     };
     auto queue_diff = [&](madsim_hip_ctx::Flight& f, uint64_t lo, uint64_t n) -> int {
-        if (list ? madsim_k_launch_diff_list(f.d_out, f.d_out_b, n, f.d_list, d->fields, f.d_drep + 16, f.d_dwcnt, f.d_drec, std::min(rec_batch, n), f.stream)
-                 : madsim_k_launch_diff(f.d_out, f.d_out_b, n, seed0 + lo, d->fields, f.d_drep + 16, f.d_dwcnt, f.d_drec, std::min(rec_batch, n), f.stream))
+        if (list ? madsim_k_launch_diff_list(f.d_out, f.diff.out_b, n, f.list.d, d->fields, f.diff.d_rep + 16, f.diff.wcnt, f.diff.rec, std::min(rec_batch, n), f.stream)
+                 : madsim_k_launch_diff(f.d_out, f.diff.out_b, n, seed0 + lo, d->fields, f.diff.d_rep + 16, f.diff.wcnt, f.diff.rec, std::min(rec_batch, n), f.stream))
             return fail(MADSIM_E_ARG, "madsim_k_launch_diff refused the batch's arguments");
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(f.h_drep, f.d_drep, n_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, f.stream));
+        HIP_TRY(hipMemcpyAsync(f.diff.h_rep, f.diff.d_rep, n_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, f.stream));
         HIP_TRY(hipEventRecord(f.done, f.stream));
         return 0;
     };
     auto queue = [&](uint64_t k) -> int {
         madsim_hip_ctx* c = ctxs[k % N];
-        madsim_hip_ctx::Flight& f = flight_of(k);
+        madsim_hip_ctx::Flight& f = flights.of(k);
         const uint64_t lo = k * batch, n = std::min(batch, total - lo);
         int e;
         if ((e = c->bind())) return e;
         if ((e = prepare_report(f))) return e;
-        if (list) {                                              // one slice for both sides (the flight's previous batch has been harvested)
-            memcpy(f.h_list, list + lo, n * sizeof(uint64_t));
-            HIP_TRY(hipMemcpyAsync(f.d_list, f.h_list, n * sizeof(uint64_t), hipMemcpyHostToDevice, f.stream));
-        }
-        const uint64_t* const d_list = list ? f.d_list : nullptr;
+        if (list && (e = queue_list_slice(f, list, lo, n))) return e;      // (one slice for both sides)
+        const uint64_t* const d_list = list ? f.list.d : nullptr;
         HIP_TRY(hipEventRecord(f.e0, f.stream));
         if ((e = c->launch(side[0].w, side[0].cfg, seed0 + lo, n, d_list, side[0].lim, f.d_out, f.stream))) return fail(e, "side A: " + g_err);
         HIP_TRY(hipEventRecord(f.e1, f.stream));
         if ((e = queue_summary(f, 0, lo, n))) return e;
-        HIP_TRY(hipEventRecord(f.b0, f.stream));
-        if ((e = c->launch(side[1].w, side[1].cfg, seed0 + lo, n, d_list, side[1].lim, f.d_out_b, f.stream))) return fail(e, "side B: " + g_err);
-        HIP_TRY(hipEventRecord(f.b1, f.stream));
+        HIP_TRY(hipEventRecord(f.diff.b0, f.stream));
+        if ((e = c->launch(side[1].w, side[1].cfg, seed0 + lo, n, d_list, side[1].lim, f.diff.out_b, f.stream))) return fail(e, "side B: " + g_err);
+        HIP_TRY(hipEventRecord(f.diff.b1, f.stream));
         if ((e = queue_summary(f, 1, lo, n))) return e;
         return queue_diff(f, lo, n);
     };
     auto harvest = [&](uint64_t k) -> int {
         madsim_hip_ctx* c = ctxs[k % N];
-        madsim_hip_ctx::Flight& f = flight_of(k);
+        madsim_hip_ctx::Flight& f = flights.of(k);
         int e;
         if ((e = c->bind())) return e;
         HIP_TRY(hipEventSynchronize(f.done));
@@ -1709,14 +1601,14 @@ int run_campaign_diff_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const DiffSid
         const uint64_t lo = k * batch, n = std::min(batch, total - lo);
         float ms[2] = {0.f, 0.f};
         HIP_TRY(hipEventElapsedTime(&ms[0], f.e0, f.e1));
-        HIP_TRY(hipEventElapsedTime(&ms[1], f.b0, f.b1));
-        if (R && (f.h_drep[5] > 0 || f.h_drep[8 + 5] > 0)) {    // runner verdicts on a side: settle them under that side's own limits, diff again
-            const unsigned long long runner_before[2] = {f.h_drep[5], f.h_drep[8 + 5]};
+        HIP_TRY(hipEventElapsedTime(&ms[1], f.diff.b0, f.diff.b1));
+        if (R && (f.diff.h_rep[5] > 0 || f.diff.h_rep[8 + 5] > 0)) {    // runner verdicts on a side: settle them under that side's own limits, diff again
+            const unsigned long long runner_before[2] = {f.diff.h_rep[5], f.diff.h_rep[8 + 5]};
             bool ran = false;
             for (int s = 0; s < 2; s++) {                       // (one after the other on the flight's stream: they share its re-run scratch)
                 if (!runner_before[s]) continue;
                 double rerun_ms = 0.0;
-                if ((e = resolve_results(c, f, side[s].w, side[s].cfg, side[s].lim, s ? f.d_out_b : f.d_out, seed0 + lo, list ? f.d_list : nullptr, n, R, acct,
+                if ((e = resolve_results(c, f, side[s].w, side[s].cfg, side[s].lim, s ? f.diff.out_b : f.d_out, seed0 + lo, list ? f.list.d : nullptr, n, R, acct,
                                          &rerun_ms, &ran)))
                     return fail(e, std::string(s ? "side B: " : "side A: ") + g_err);
                 acct.rerun_kernel_ms += rerun_ms; side[s].out->kernel_ms += rerun_ms;
@@ -1724,30 +1616,21 @@ int run_campaign_diff_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const DiffSid
             if (ran) {
                 if ((e = prepare_report(f)) || (e = queue_summary(f, 0, lo, n)) || (e = queue_summary(f, 1, lo, n)) || (e = queue_diff(f, lo, n))) return e;
                 HIP_TRY(hipEventSynchronize(f.done));
-                acct.n_resolved += (runner_before[0] - f.h_drep[5]) + (runner_before[1] - f.h_drep[8 + 5]);
+                acct.n_resolved += (runner_before[0] - f.diff.h_rep[5]) + (runner_before[1] - f.diff.h_rep[8 + 5]);
             }
         }
-        for (int s = 0; s < 2; s++) {
-            const unsigned long long* a = f.h_drep + 8 * s;
-            madsim_campaign_t* out = side[s].out;
-            out->kernel_ms += ms[s];
-            out->batches_run++; out->seeds_run += n;
-            out->n_runner += a[5];
-            out->n_failed += a[1] - a[5];
-            out->total_steps += a[2]; out->total_clock_ns += a[3];
-            if (a[4] < out->first_failing_seed) out->first_failing_seed = a[4];
-        }
-        if (f.h_drep[16] > n) return fail(MADSIM_E_HIP, "differential campaign: a batch reports more differing seeds than it holds");
+        for (int s = 0; s < 2; s++) fold_summary(side[s].out, f.diff.h_rep + 8 * s, n, ms[s]);
+        if (f.diff.h_rep[16] > n) return fail(MADSIM_E_HIP, "differential campaign: a batch reports more differing seeds than it holds");
         // the batch's records, as many as the list still takes (the stream is idle: its `done` has passed, and it takes no launch before this returns)
-        const uint64_t at = d->n_listed, take = madsim_k_fold_diff(d, f.h_drep + 16, n, nullptr);
+        const uint64_t at = d->n_listed, take = madsim_k_fold_diff(d, f.diff.h_rep + 16, n, nullptr);
         if (take) {
-            HIP_TRY(hipMemcpyAsync(d->records + at, f.d_drec, take * sizeof(madsim_diff_record_t), hipMemcpyDeviceToHost, f.stream));
+            HIP_TRY(hipMemcpyAsync(d->records + at, f.diff.rec, take * sizeof(madsim_diff_record_t), hipMemcpyDeviceToHost, f.stream));
             HIP_TRY(hipStreamSynchronize(f.stream));
         }
         if ((flags & MADSIM_CAMPAIGN_STOP_AT_DIFFS) && d->n_differ >= d->cap) stop = true;
         return 0;
     };
-    const uint64_t launched = pump_batches(ctxs, n_ctx, n_batches, F, stop, first_err, first_msg, queue, harvest);
+    const uint64_t launched = pump_batches(ctxs, n_ctx, n_batches, flights.F, stop, first_err, first_msg, queue, harvest);
     for (const DiffSide& s : side) { s.out->batches_launched = launched; s.out->wall_s = since(t0); }
     return first_err ? fail(first_err, first_msg) : 0;
 }
@@ -1767,27 +1650,47 @@ int madsim_hip_run_campaign_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, cons
                                   const madsim_limits_t* lim, madsim_campaign_t* out) {
     if (!out) return fail(MADSIM_E_ARG, "null campaign report");
     if (int rc = check_resolve_flags(flags)) return rc;
-    if (!ctxs || n_ctx < 1) return fail(MADSIM_E_ARG, "run_campaign_multi needs at least one context");
-    for (int g = 0; g < n_ctx; g++) {
-        if (!ctxs[g]) return fail(MADSIM_E_NOINIT, "null context");
-        for (int h = 0; h < g; h++) if (ctxs[h] == ctxs[g]) return fail(MADSIM_E_ARG, "the same context appears twice");
-    }
-    std::vector<madsim_hip_ctx*> order(ctxs, ctxs + n_ctx);      // locks in address order (see madsim_hip_run_batch_multi)
-    std::sort(order.begin(), order.end(), [](madsim_hip_ctx* a, madsim_hip_ctx* b) { return std::less<madsim_hip_ctx*>()(a, b); });
     std::vector<std::unique_lock<std::mutex>> locks;
-    for (madsim_hip_ctx* c : order) locks.emplace_back(c->mu);
-    for (int g = 0; g < n_ctx; g++) if (ctxs[g]->device < 0) return fail(MADSIM_E_NOINIT, "closed context");
+    if (int rc = lock_contexts(ctxs, n_ctx, "run_campaign_multi", locks)) return rc;
     return run_campaign_impl(ctxs, n_ctx, w, cfg, seed0, total, batch, in_flight, flags, lim, out);
 }
 
-// The collecting forms: the argument errors that need no device are told first, so that a host without a GPU hears about them too.
+// The collecting, statistics and grouping forms and the list campaigns: the argument errors that need no device are told first, so that a
+// host without a GPU hears about them too.  `form` is the part the entry point cannot do without; the other parts are checked when given.
+// The errors come in the order they always came in: the report, the form's own part, the first part given (grouping before statistics
+// before collecting), the resolve flags, a grouping batch's size, the remaining parts, the batches in flight.
 namespace {
-int check_collect_args(const madsim_campaign_t* out, const madsim_collect_t* col, uint32_t in_flight, uint32_t flags) {
-    if (!out) return fail(MADSIM_E_ARG, "null campaign report");
-    if (!col) return fail(MADSIM_E_ARG, "null madsim_collect_t (madsim_hip_run_campaign is the form without a failure list)");
+enum CampaignForm { FORM_ANY, FORM_COLLECT, FORM_STATS, FORM_GROUPS };
+int check_collect_part(const madsim_collect_t* col, uint32_t flags) {
     if (col->cap && !col->failures) return fail(MADSIM_E_ARG, "madsim_collect_t.cap > 0 without a failures array");
     if ((flags & MADSIM_CAMPAIGN_STOP_AT_CAP) && !col->cap) return fail(MADSIM_E_ARG, "MADSIM_CAMPAIGN_STOP_AT_CAP with cap == 0");
-    if (int rc = check_resolve_flags(flags)) return rc;
+    return 0;
+}
+int check_stats_part(const madsim_stats_t* st) {
+    if (st->include == 0 || (st->include & ~0xfu)) return fail(MADSIM_E_ARG, "madsim_stats_t.include: at least one of bits 0-3 (PASS, PANIC, DEADLOCK, TIME_LIMIT), no other");
+    if (st->top_k > MADSIM_STAT_MAX_TOP) return fail(MADSIM_E_ARG, "madsim_stats_t.top_k > MADSIM_STAT_MAX_TOP");
+    if (st->top_k && !st->top) return fail(MADSIM_E_ARG, "madsim_stats_t.top_k > 0 without a top array");
+    return 0;
+}
+int check_groups_part(const madsim_groups_t* grp, uint32_t flags) {
+    if (grp->include == 0 || (grp->include & ~0xfu)) return fail(MADSIM_E_ARG, "madsim_groups_t.include: at least one of bits 0-3 (PASS, PANIC, DEADLOCK, TIME_LIMIT), no other");
+    if (grp->key_field >= MADSIM_GROUP_KEYS) return fail(MADSIM_E_ARG, "madsim_groups_t.key_field: one of MADSIM_GROUP_KEY_*");
+    if (grp->cap && !grp->groups) return fail(MADSIM_E_ARG, "madsim_groups_t.cap > 0 without a groups array");
+    if ((flags & MADSIM_CAMPAIGN_STOP_AT_GROUPS) && !grp->cap) return fail(MADSIM_E_ARG, "MADSIM_CAMPAIGN_STOP_AT_GROUPS with cap == 0");
+    return 0;
+}
+int check_campaign_args(CampaignForm form, const madsim_campaign_t* out, const madsim_collect_t* col, const madsim_stats_t* st, const madsim_groups_t* grp,
+                        uint64_t total, uint64_t batch, uint32_t in_flight, uint32_t flags) {
+    if (!out) return fail(MADSIM_E_ARG, "null campaign report");
+    if (form == FORM_COLLECT && !col) return fail(MADSIM_E_ARG, "null madsim_collect_t (madsim_hip_run_campaign is the form without a failure list)");
+    if (form == FORM_STATS && !st) return fail(MADSIM_E_ARG, "null madsim_stats_t");
+    if (form == FORM_GROUPS && !grp) return fail(MADSIM_E_ARG, "null madsim_groups_t");
+    int rc = grp ? check_groups_part(grp, flags) : st ? check_stats_part(st) : col ? check_collect_part(col, flags) : 0;
+    if (rc || (rc = check_resolve_flags(flags))) return rc;
+    if (grp && std::min(batch ? batch : 65536, total) > MADSIM_GROUP_MAX_BATCH)
+        return fail(MADSIM_E_ARG, "a grouping campaign's batch holds at most MADSIM_GROUP_MAX_BATCH (2^20) seeds: the device table is sized to the batch");
+    if (grp && st && (rc = check_stats_part(st))) return rc;
+    if ((grp || st) && col && (rc = check_collect_part(col, flags))) return rc;
     if (in_flight > (uint32_t)madsim_hip_ctx::CAMPAIGN_MAX) return fail(MADSIM_E_ARG, "at most 8 batches in flight per context");
     return 0;
 }
@@ -1796,7 +1699,7 @@ int check_collect_args(const madsim_campaign_t* out, const madsim_collect_t* col
 int madsim_hip_ctx_run_campaign_collect(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total,
                                         uint64_t batch, uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim, madsim_campaign_t* out,
                                         madsim_collect_t* col) {
-    if (int rc = check_collect_args(out, col, in_flight, flags)) return rc;
+    if (int rc = check_campaign_args(FORM_COLLECT, out, col, nullptr, nullptr, total, batch, in_flight, flags)) return rc;
     CTX_ENTER(c);
     madsim_hip_ctx* one[1] = {c};
     return run_campaign_impl(one, 1, w, cfg, seed0, total, batch, in_flight, flags, lim, out, col);
@@ -1805,39 +1708,16 @@ int madsim_hip_ctx_run_campaign_collect(madsim_hip_ctx_t* c, const madsim_worklo
 int madsim_hip_run_campaign_collect_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_workload_t* w, const madsim_config_t* cfg,
                                           uint64_t seed0, uint64_t total, uint64_t batch, uint32_t in_flight, uint32_t flags,
                                           const madsim_limits_t* lim, madsim_campaign_t* out, madsim_collect_t* col) {
-    if (int rc = check_collect_args(out, col, in_flight, flags)) return rc;
-    if (!ctxs || n_ctx < 1) return fail(MADSIM_E_ARG, "run_campaign_collect_multi needs at least one context");
-    for (int g = 0; g < n_ctx; g++) {
-        if (!ctxs[g]) return fail(MADSIM_E_NOINIT, "null context");
-        for (int h = 0; h < g; h++) if (ctxs[h] == ctxs[g]) return fail(MADSIM_E_ARG, "the same context appears twice");
-    }
-    std::vector<madsim_hip_ctx*> order(ctxs, ctxs + n_ctx);      // locks in address order (see madsim_hip_run_batch_multi)
-    std::sort(order.begin(), order.end(), [](madsim_hip_ctx* a, madsim_hip_ctx* b) { return std::less<madsim_hip_ctx*>()(a, b); });
+    if (int rc = check_campaign_args(FORM_COLLECT, out, col, nullptr, nullptr, total, batch, in_flight, flags)) return rc;
     std::vector<std::unique_lock<std::mutex>> locks;
-    for (madsim_hip_ctx* c : order) locks.emplace_back(c->mu);
-    for (int g = 0; g < n_ctx; g++) if (ctxs[g]->device < 0) return fail(MADSIM_E_NOINIT, "closed context");
+    if (int rc = lock_contexts(ctxs, n_ctx, "run_campaign_collect_multi", locks)) return rc;
     return run_campaign_impl(ctxs, n_ctx, w, cfg, seed0, total, batch, in_flight, flags, lim, out, col);
 }
-
-// The statistics forms: argument errors first, as the collecting forms.
-namespace {
-int check_stats_args(const madsim_campaign_t* out, const madsim_collect_t* col, const madsim_stats_t* st, uint32_t in_flight, uint32_t flags) {
-    if (!out) return fail(MADSIM_E_ARG, "null campaign report");
-    if (!st) return fail(MADSIM_E_ARG, "null madsim_stats_t");
-    if (st->include == 0 || (st->include & ~0xfu)) return fail(MADSIM_E_ARG, "madsim_stats_t.include: at least one of bits 0-3 (PASS, PANIC, DEADLOCK, TIME_LIMIT), no other");
-    if (st->top_k > MADSIM_STAT_MAX_TOP) return fail(MADSIM_E_ARG, "madsim_stats_t.top_k > MADSIM_STAT_MAX_TOP");
-    if (st->top_k && !st->top) return fail(MADSIM_E_ARG, "madsim_stats_t.top_k > 0 without a top array");
-    if (int rc = check_resolve_flags(flags)) return rc;
-    if (col) return check_collect_args(out, col, in_flight, flags);
-    if (in_flight > (uint32_t)madsim_hip_ctx::CAMPAIGN_MAX) return fail(MADSIM_E_ARG, "at most 8 batches in flight per context");
-    return 0;
-}
-}  // namespace
 
 int madsim_hip_ctx_run_campaign_stats(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total,
                                       uint64_t batch, uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim, madsim_campaign_t* out,
                                       madsim_collect_t* col, madsim_stats_t* st) {
-    if (int rc = check_stats_args(out, col, st, in_flight, flags)) return rc;
+    if (int rc = check_campaign_args(FORM_STATS, out, col, st, nullptr, total, batch, in_flight, flags)) return rc;
     CTX_ENTER(c);
     madsim_hip_ctx* one[1] = {c};
     return run_campaign_impl(one, 1, w, cfg, seed0, total, batch, in_flight, flags, lim, out, col, st);
@@ -1846,44 +1726,16 @@ int madsim_hip_ctx_run_campaign_stats(madsim_hip_ctx_t* c, const madsim_workload
 int madsim_hip_run_campaign_stats_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_workload_t* w, const madsim_config_t* cfg,
                                         uint64_t seed0, uint64_t total, uint64_t batch, uint32_t in_flight, uint32_t flags,
                                         const madsim_limits_t* lim, madsim_campaign_t* out, madsim_collect_t* col, madsim_stats_t* st) {
-    if (int rc = check_stats_args(out, col, st, in_flight, flags)) return rc;
-    if (!ctxs || n_ctx < 1) return fail(MADSIM_E_ARG, "run_campaign_stats_multi needs at least one context");
-    for (int g = 0; g < n_ctx; g++) {
-        if (!ctxs[g]) return fail(MADSIM_E_NOINIT, "null context");
-        for (int h = 0; h < g; h++) if (ctxs[h] == ctxs[g]) return fail(MADSIM_E_ARG, "the same context appears twice");
-    }
-    std::vector<madsim_hip_ctx*> order(ctxs, ctxs + n_ctx);      // locks in address order (see madsim_hip_run_batch_multi)
-    std::sort(order.begin(), order.end(), [](madsim_hip_ctx* a, madsim_hip_ctx* b) { return std::less<madsim_hip_ctx*>()(a, b); });
+    if (int rc = check_campaign_args(FORM_STATS, out, col, st, nullptr, total, batch, in_flight, flags)) return rc;
     std::vector<std::unique_lock<std::mutex>> locks;
-    for (madsim_hip_ctx* c : order) locks.emplace_back(c->mu);
-    for (int g = 0; g < n_ctx; g++) if (ctxs[g]->device < 0) return fail(MADSIM_E_NOINIT, "closed context");
+    if (int rc = lock_contexts(ctxs, n_ctx, "run_campaign_stats_multi", locks)) return rc;
     return run_campaign_impl(ctxs, n_ctx, w, cfg, seed0, total, batch, in_flight, flags, lim, out, col, st);
 }
-
-// The grouping forms: argument errors first, as the collecting and statistics forms.
-namespace {
-int check_groups_args(const madsim_campaign_t* out, const madsim_collect_t* col, const madsim_stats_t* st, const madsim_groups_t* grp, uint64_t total,
-                      uint64_t batch, uint32_t in_flight, uint32_t flags) {
-    if (!out) return fail(MADSIM_E_ARG, "null campaign report");
-    if (!grp) return fail(MADSIM_E_ARG, "null madsim_groups_t");
-    if (grp->include == 0 || (grp->include & ~0xfu)) return fail(MADSIM_E_ARG, "madsim_groups_t.include: at least one of bits 0-3 (PASS, PANIC, DEADLOCK, TIME_LIMIT), no other");
-    if (grp->key_field >= MADSIM_GROUP_KEYS) return fail(MADSIM_E_ARG, "madsim_groups_t.key_field: one of MADSIM_GROUP_KEY_*");
-    if (grp->cap && !grp->groups) return fail(MADSIM_E_ARG, "madsim_groups_t.cap > 0 without a groups array");
-    if ((flags & MADSIM_CAMPAIGN_STOP_AT_GROUPS) && !grp->cap) return fail(MADSIM_E_ARG, "MADSIM_CAMPAIGN_STOP_AT_GROUPS with cap == 0");
-    if (int rc = check_resolve_flags(flags)) return rc;
-    if (std::min(batch ? batch : 65536, total) > MADSIM_GROUP_MAX_BATCH)
-        return fail(MADSIM_E_ARG, "a grouping campaign's batch holds at most MADSIM_GROUP_MAX_BATCH (2^20) seeds: the device table is sized to the batch");
-    if (st) return check_stats_args(out, col, st, in_flight, flags);
-    if (col) return check_collect_args(out, col, in_flight, flags);
-    if (in_flight > (uint32_t)madsim_hip_ctx::CAMPAIGN_MAX) return fail(MADSIM_E_ARG, "at most 8 batches in flight per context");
-    return 0;
-}
-}  // namespace
 
 int madsim_hip_ctx_run_campaign_groups(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total,
                                        uint64_t batch, uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim, madsim_campaign_t* out,
                                        madsim_collect_t* col, madsim_stats_t* st, madsim_groups_t* grp) {
-    if (int rc = check_groups_args(out, col, st, grp, total, batch, in_flight, flags)) return rc;
+    if (int rc = check_campaign_args(FORM_GROUPS, out, col, st, grp, total, batch, in_flight, flags)) return rc;
     CTX_ENTER(c);
     madsim_hip_ctx* one[1] = {c};
     return run_campaign_impl(one, 1, w, cfg, seed0, total, batch, in_flight, flags, lim, out, col, st, grp);
@@ -1893,17 +1745,9 @@ int madsim_hip_run_campaign_groups_multi(madsim_hip_ctx_t* const* ctxs, int n_ct
                                          uint64_t seed0, uint64_t total, uint64_t batch, uint32_t in_flight, uint32_t flags,
                                          const madsim_limits_t* lim, madsim_campaign_t* out, madsim_collect_t* col, madsim_stats_t* st,
                                          madsim_groups_t* grp) {
-    if (int rc = check_groups_args(out, col, st, grp, total, batch, in_flight, flags)) return rc;
-    if (!ctxs || n_ctx < 1) return fail(MADSIM_E_ARG, "run_campaign_groups_multi needs at least one context");
-    for (int g = 0; g < n_ctx; g++) {
-        if (!ctxs[g]) return fail(MADSIM_E_NOINIT, "null context");
-        for (int h = 0; h < g; h++) if (ctxs[h] == ctxs[g]) return fail(MADSIM_E_ARG, "the same context appears twice");
-    }
-    std::vector<madsim_hip_ctx*> order(ctxs, ctxs + n_ctx);      // locks in address order (see madsim_hip_run_batch_multi)
-    std::sort(order.begin(), order.end(), [](madsim_hip_ctx* a, madsim_hip_ctx* b) { return std::less<madsim_hip_ctx*>()(a, b); });
+    if (int rc = check_campaign_args(FORM_GROUPS, out, col, st, grp, total, batch, in_flight, flags)) return rc;
     std::vector<std::unique_lock<std::mutex>> locks;
-    for (madsim_hip_ctx* c : order) locks.emplace_back(c->mu);
-    for (int g = 0; g < n_ctx; g++) if (ctxs[g]->device < 0) return fail(MADSIM_E_NOINIT, "closed context");
+    if (int rc = lock_contexts(ctxs, n_ctx, "run_campaign_groups_multi", locks)) return rc;
     return run_campaign_impl(ctxs, n_ctx, w, cfg, seed0, total, batch, in_flight, flags, lim, out, col, st, grp);
 }
 
@@ -1938,16 +1782,8 @@ int madsim_hip_run_campaign_diff_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx,
                                        const madsim_limits_t* limB, uint64_t seed0, uint64_t total, uint64_t batch, uint32_t in_flight,
                                        uint32_t flags, madsim_campaign_t* outA, madsim_campaign_t* outB, madsim_diff_t* diff) {
     if (int rc = check_diff_args(outA, outB, diff, in_flight, flags)) return rc;
-    if (!ctxs || n_ctx < 1) return fail(MADSIM_E_ARG, "run_campaign_diff_multi needs at least one context");
-    for (int g = 0; g < n_ctx; g++) {
-        if (!ctxs[g]) return fail(MADSIM_E_NOINIT, "null context");
-        for (int h = 0; h < g; h++) if (ctxs[h] == ctxs[g]) return fail(MADSIM_E_ARG, "the same context appears twice");
-    }
-    std::vector<madsim_hip_ctx*> order(ctxs, ctxs + n_ctx);      // locks in address order (see madsim_hip_run_batch_multi)
-    std::sort(order.begin(), order.end(), [](madsim_hip_ctx* a, madsim_hip_ctx* b) { return std::less<madsim_hip_ctx*>()(a, b); });
     std::vector<std::unique_lock<std::mutex>> locks;
-    for (madsim_hip_ctx* c : order) locks.emplace_back(c->mu);
-    for (int g = 0; g < n_ctx; g++) if (ctxs[g]->device < 0) return fail(MADSIM_E_NOINIT, "closed context");
+    if (int rc = lock_contexts(ctxs, n_ctx, "run_campaign_diff_multi", locks)) return rc;
     const DiffSide side[2] = {{wA, cfgA, limA, outA}, {wB, cfgB, limB, outB}};
     return run_campaign_diff_impl(ctxs, n_ctx, side, seed0, total, batch, in_flight, flags, diff);
 }
@@ -1969,26 +1805,7 @@ int check_seeds_args(const uint64_t* seeds, uint64_t n, uint64_t batch, uint32_t
     if (int rc = check_seed_list(seeds, n)) return rc;
     if (!col) flags &= ~(MADSIM_CAMPAIGN_LIST_RUNNER | MADSIM_CAMPAIGN_STOP_AT_CAP);      // (flags of an absent part are ignored)
     if (!grp) flags &= ~MADSIM_CAMPAIGN_STOP_AT_GROUPS;
-    if (grp) return check_groups_args(out, col, st, grp, n, batch, in_flight, flags);
-    if (st) return check_stats_args(out, col, st, in_flight, flags);
-    if (col) return check_collect_args(out, col, in_flight, flags);
-    if (!out) return fail(MADSIM_E_ARG, "null campaign report");
-    if (int rc = check_resolve_flags(flags)) return rc;
-    if (in_flight > (uint32_t)madsim_hip_ctx::CAMPAIGN_MAX) return fail(MADSIM_E_ARG, "at most 8 batches in flight per context");
-    return 0;
-}
-// the contexts of a _multi call, checked and locked in address order (see madsim_hip_run_batch_multi)
-int lock_contexts(madsim_hip_ctx_t* const* ctxs, int n_ctx, const char* who, std::vector<std::unique_lock<std::mutex>>& locks) {
-    if (!ctxs || n_ctx < 1) return fail(MADSIM_E_ARG, std::string(who) + " needs at least one context");
-    for (int g = 0; g < n_ctx; g++) {
-        if (!ctxs[g]) return fail(MADSIM_E_NOINIT, "null context");
-        for (int h = 0; h < g; h++) if (ctxs[h] == ctxs[g]) return fail(MADSIM_E_ARG, "the same context appears twice");
-    }
-    std::vector<madsim_hip_ctx*> order(ctxs, ctxs + n_ctx);
-    std::sort(order.begin(), order.end(), [](madsim_hip_ctx* a, madsim_hip_ctx* b) { return std::less<madsim_hip_ctx*>()(a, b); });
-    for (madsim_hip_ctx* c : order) locks.emplace_back(c->mu);
-    for (int g = 0; g < n_ctx; g++) if (ctxs[g]->device < 0) return fail(MADSIM_E_NOINIT, "closed context");
-    return 0;
+    return check_campaign_args(FORM_ANY, out, col, st, grp, n, batch, in_flight, flags);
 }
 }  // namespace
 
