@@ -269,6 +269,40 @@ pub struct madsim_resolve_t {
 
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
+pub struct madsim_sweep_variant_t {
+    pub w: *const madsim_workload_t,
+    pub cfg: *const madsim_config_t,
+    pub lim: *const madsim_limits_t,
+    pub out: *const madsim_campaign_t,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct madsim_sweep_record_t {
+    pub seed: u64,
+    pub fail_mask: u32,
+    pub differ_mask: u32,
+    pub verdict: [u8; 8],
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct madsim_sweep_t {
+    pub fields: u32,
+    pub list_rule: u32,
+    pub records: *const madsim_sweep_record_t,
+    pub cap: u64,
+    pub n_listed: u64,
+    pub n_selected: u64,
+    pub n_settled: u64,
+    pub n_incomparable: u64,
+    pub n_runner_by_variant: [u64; 8],
+    pub n_differ_from_first: [u64; 8],
+    pub n_by_mask: [u64; 256],
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
 pub struct madsim_geometry_t {
     pub lds_bytes_per_seed: u32,
     pub lds_bytes_per_block: u32,
@@ -445,6 +479,11 @@ pub const MADSIM_CAMPAIGN_RESOLVE_ROUNDS_SHIFT: u32 = 8;
 pub const MADSIM_CAMPAIGN_RESOLVE_ROUNDS_MASK: u32 = 3840;
 pub const MADSIM_RESOLVE_DEFAULT_ROUNDS: u32 = 4;
 pub const MADSIM_RESOLVE_MAX_ROUNDS: u32 = 8;
+pub const MADSIM_SWEEP_MAX_VARIANTS: u32 = 8;
+pub const MADSIM_SWEEP_LIST_MIXED: u32 = 0;
+pub const MADSIM_SWEEP_LIST_FAILING: u32 = 1;
+pub const MADSIM_SWEEP_LIST_DIFFERING: u32 = 2;
+pub const MADSIM_CAMPAIGN_STOP_AT_SWEEP: u32 = 64;
 
 #[link(name = "madsim_hip")]
 extern "C" {
@@ -504,6 +543,9 @@ extern "C" {
     pub fn madsim_hip_ctx_run_seeds_campaign_diff(ctx: *mut madsim_hip_ctx_t, wA: *const madsim_workload_t, cfgA: *const madsim_config_t, limA: *const madsim_limits_t, wB: *const madsim_workload_t, cfgB: *const madsim_config_t, limB: *const madsim_limits_t, seeds: *const u64, n: u64, batch: u64, in_flight: u32, flags: u32, outA: *mut madsim_campaign_t, outB: *mut madsim_campaign_t, diff: *mut madsim_diff_t) -> c_int;
     pub fn madsim_hip_run_seeds_campaign_diff(wA: *const madsim_workload_t, cfgA: *const madsim_config_t, limA: *const madsim_limits_t, wB: *const madsim_workload_t, cfgB: *const madsim_config_t, limB: *const madsim_limits_t, seeds: *const u64, n: u64, batch: u64, in_flight: u32, flags: u32, outA: *mut madsim_campaign_t, outB: *mut madsim_campaign_t, diff: *mut madsim_diff_t) -> c_int;
     pub fn madsim_hip_run_seeds_campaign_diff_multi(ctxs: *const *mut madsim_hip_ctx_t, n_ctx: c_int, wA: *const madsim_workload_t, cfgA: *const madsim_config_t, limA: *const madsim_limits_t, wB: *const madsim_workload_t, cfgB: *const madsim_config_t, limB: *const madsim_limits_t, seeds: *const u64, n: u64, batch: u64, in_flight: u32, flags: u32, outA: *mut madsim_campaign_t, outB: *mut madsim_campaign_t, diff: *mut madsim_diff_t) -> c_int;
+    pub fn madsim_hip_ctx_run_sweep_campaign(ctx: *mut madsim_hip_ctx_t, variants: *const madsim_sweep_variant_t, n_variants: u32, seed0: u64, total: u64, seeds: *const u64, batch: u64, in_flight: u32, flags: u32, sweep: *mut madsim_sweep_t) -> c_int;
+    pub fn madsim_hip_run_sweep_campaign(variants: *const madsim_sweep_variant_t, n_variants: u32, seed0: u64, total: u64, seeds: *const u64, batch: u64, in_flight: u32, flags: u32, sweep: *mut madsim_sweep_t) -> c_int;
+    pub fn madsim_hip_run_sweep_campaign_multi(ctxs: *const *mut madsim_hip_ctx_t, n_ctx: c_int, variants: *const madsim_sweep_variant_t, n_variants: u32, seed0: u64, total: u64, seeds: *const u64, batch: u64, in_flight: u32, flags: u32, sweep: *mut madsim_sweep_t) -> c_int;
     pub fn madsim_hip_geometry(w: *const madsim_workload_t, lim: *const madsim_limits_t, g: *mut madsim_geometry_t) -> c_int;
     pub fn madsim_hip_debug_counters(out16: *mut u64) -> c_int;
     pub fn madsim_workload_pingpong(n_nodes: u32, rounds: u32, nodes: *mut madsim_node_t, progs: *mut madsim_prog_t, socks: *mut madsim_sock_t, insns: *mut madsim_insn_t, cap_insns: u32, w: *mut madsim_workload_t) -> c_int;

@@ -187,6 +187,36 @@ pub struct Diff {
     pub b: sys::madsim_campaign_t,
 }
 
+/// What `Builder::sweep_campaign` found: per variant its plain campaign report; the report — `n_by_mask[m]` = settled seeds that fail in
+/// exactly the variants whose bits `m` has, the per-variant counts — and the smallest seeds the list rule selects (ascending), each
+/// with its masks and every variant's verdict.
+#[derive(Clone, Debug)]
+pub struct Sweep {
+    pub records: Vec<sys::madsim_sweep_record_t>,
+    pub report: sys::madsim_sweep_t,
+    pub campaigns: Vec<sys::madsim_campaign_t>,
+}
+
+impl Sweep {
+    /// Settled seeds that fail in variant `v`.
+    pub fn fails(&self, v: usize) -> u64 {
+        (0..256usize).filter(|m| m >> v & 1 == 1).map(|m| self.report.n_by_mask[m]).sum()
+    }
+    /// True when every non-empty mask that occurs is a suffix set: the failing sets grow with the variant index.
+    pub fn nested(&self) -> bool {
+        let full = (1usize << self.campaigns.len()) - 1;
+        (1..=full).all(|m| self.report.n_by_mask[m] == 0 || m == full & !((m & m.wrapping_neg()) - 1))
+    }
+    /// `[v]` = settled seeds whose lowest failing variant is `v`: the bisect reading.
+    pub fn first_failing(&self) -> Vec<u64> {
+        let mut h = vec![0u64; self.campaigns.len()];
+        for m in 1..(1usize << self.campaigns.len()) {
+            h[m.trailing_zeros() as usize] += self.report.n_by_mask[m];
+        }
+        h
+    }
+}
+
 /// What `Builder::campaign_over_seeds` found over the listed seeds: the campaign report, and each part that was asked for.
 #[derive(Clone, Debug)]
 pub struct ListCampaign {
@@ -680,6 +710,43 @@ impl Builder {
         records.truncate(report.n_listed as usize);
         report.records = std::ptr::null();
         Ok(Diff { records, report, a, b })
+    }
+
+    /// Across several variants: up to eight `(builder, workload)` pairs over `self.seed .. self.seed + self.count` — or, with
+    /// `seeds: Some(list)`, over a strictly ascending list — in one campaign (`madsim_hip_run_sweep_campaign`): a parameter sweep, a stack
+    /// of versions of a test body.  Config and limits are each variant's own; the seeds and the resolve rounds are `self`'s.  Every seed is
+    /// classified across all variants on the device; `fields`: the `MADSIM_DIFF_*` fields compared against variant 0 (0 = none);
+    /// `list_rule`: `MADSIM_SWEEP_LIST_*`; the `max_listed` smallest selected seeds come back.
+    pub fn sweep_campaign(&self, variants: &[(&Builder, &Workload)], seeds: Option<&[u64]>, fields: u32, list_rule: u32, max_listed: usize)
+                          -> Result<Sweep, RunError> {
+        let n = variants.len();
+        let ws: Vec<sys::madsim_workload_t> = variants.iter().map(|(_, w)| w.raw()).collect();
+        let cs: Vec<sys::madsim_config_t> = variants.iter().map(|(b, _)| b.config.raw()).collect();
+        let ls: Vec<sys::madsim_limits_t> = variants.iter().map(|(b, _)| b.raw_limits(true)).collect();
+        let mut campaigns: Vec<sys::madsim_campaign_t> = vec![unsafe { std::mem::zeroed() }; n];
+        let outs = campaigns.as_mut_ptr();
+        let var: Vec<sys::madsim_sweep_variant_t> = (0..n)
+            .map(|v| sys::madsim_sweep_variant_t { w: &ws[v], cfg: &cs[v], lim: &ls[v], out: unsafe { outs.add(v) } as *const _ })   // (the library writes through it)
+            .collect();
+        let ctx = contexts()?.0[0];
+        let mut records: Vec<sys::madsim_sweep_record_t> = vec![unsafe { std::mem::zeroed() }; max_listed];
+        let mut report: sys::madsim_sweep_t = unsafe { std::mem::zeroed() };
+        report.fields = fields;
+        report.list_rule = list_rule;
+        report.records = if max_listed > 0 { records.as_mut_ptr() as *const _ } else { std::ptr::null() };   // (the library writes through it)
+        report.cap = max_listed as u64;
+        let none = [0u64];                                                // (an empty list is still the list form: a non-null pointer)
+        let (seed0, total, list) = match seeds {
+            Some(s) => (0, s.len() as u64, if s.is_empty() { none.as_ptr() } else { s.as_ptr() }),
+            None => (self.seed, self.count, std::ptr::null()),
+        };
+        let rc = unsafe { sys::madsim_hip_ctx_run_sweep_campaign(ctx, var.as_ptr(), n as u32, seed0, total, list, 0, 0, self.resolve_flags, &mut report) };
+        if rc != 0 {
+            return Err(last_error(rc));
+        }
+        records.truncate(report.n_listed as usize);
+        report.records = std::ptr::null();
+        Ok(Sweep { records, report, campaigns })
     }
 
     /// Same contract as `Builder::run` (builder.rs:121-162) for a test body registered as a workload: returns the per-seed

@@ -1074,6 +1074,72 @@ int madsim_hip_run_seeds_campaign_diff_multi(madsim_hip_ctx_t* const* ctxs, int 
                                              uint32_t in_flight, uint32_t flags, madsim_campaign_t* outA,
                                              madsim_campaign_t* outB, madsim_diff_t* diff);
 
+/* ---- Sweep campaigns: UP TO EIGHT variants over one seed set, classified across all of them on the device -------------------
+ * A differential campaign compares two sides.  The questions behind it are often N-way: one test body under four loss rates
+ * ("which settings does this seed fail in: are the failing sets nested?"), a stack of K versions of a test body ("which
+ * version first breaks this seed?"), one workload under every state layout ("the same 48 bytes everywhere?").  A sweep campaign
+ * runs all n_variants variants (workload, config, limits — any pointer may repeat) of a batch on the flight's one stream, a
+ * summary6 kernel after each, then two sweep kernels read all the result arrays; nothing is copied back but the report words
+ * and the listed records.  variants[v].out receives the plain campaign's report of variant v over the same prefix.
+ * Per seed: variant v's result is PASS (verdict 0), FAIL (1 .. 3) or RUNNER (MADSIM_IS_RUNNER_VERDICT).  fail_mask has bit v set
+ * when variant v is FAIL, runner_mask when it is RUNNER.  A seed is SETTLED when runner_mask == 0, otherwise INCOMPARABLE: an
+ * incomparable seed counts in n_incomparable and in n_runner_by_variant[v] for every v with runner_mask bit v set, appears
+ * nowhere else and is never listed.  n_settled + n_incomparable = seeds_run.  For a settled seed, differ_mask has bit v (v >= 1)
+ * set when any field named in `fields` (MADSIM_DIFF_*; 0 = compare nothing) differs between variant v and variant 0 — the field
+ * comparison of a differential campaign; n_differ_from_first[v] counts those seeds, n_by_mask[m] the settled seeds with
+ * fail_mask == m (entries at or above 2^n_variants stay 0; their sum is n_settled).
+ * list_rule names the SELECTED seeds: MADSIM_SWEEP_LIST_MIXED (settled, fail_mask neither 0 nor all n_variants bits: the variants
+ * disagree on pass / fail), _FAILING (settled, fail_mask != 0), _DIFFERING (settled, differ_mask != 0).  records[0 .. n_listed) are
+ * the `cap` smallest selected seeds of the prefix, ascending by seed, each with its two masks and every variant's verdict; no
+ * atomic decides a position.  Every integer is a function of the per-seed results of the prefix: the same bytes whatever `batch`,
+ * `in_flight` and the number of contexts; batches launched beyond a stopping one contribute nothing.
+ * One signature carries the range and the list form: seeds == NULL runs [seed0, seed0 + total); otherwise seeds[0 .. total) is a
+ * strictly ascending list, seed0 must be 0, and every rule of the list section above applies (positions, total == 0 without a
+ * device — here for the range too —, the message naming the first offending position).  The entry points are spelled
+ * run_sweep_campaign as the list forms are run_seeds_campaign.  Every variant of batch k runs on context k % n_ctx;
+ * automatic `in_flight` is the smallest of the variants'.  A batch holds fewer than 2^32 seeds.
+ * MADSIM_CAMPAIGN_STOP_AT_SWEEP: stop launching once the batches read so far hold `cap` selected seeds; seeds_run / batches_run /
+ * batches_launched (set on every variant's report, as wall_s is) follow the rules of MADSIM_CAMPAIGN_STOP_AT_FAILURE.  The other
+ * stop flags are ignored by this form, and the other entry points ignore this one.  With MADSIM_CAMPAIGN_RESOLVE each variant's
+ * runner verdicts are first re-run under that variant's own grown limits; madsim_hip_campaign_resolved sums the variants.
+ * MADSIM_E_ARG, all told before any context is looked at: n_variants outside 2 .. MADSIM_SWEEP_MAX_VARIANTS; variants, sweep or
+ * any w / out NULL; a `fields` bit above MADSIM_DIFF_ALL; list_rule > 2; MADSIM_SWEEP_LIST_DIFFERING with fields == 0; cap > 0
+ * without `records`; STOP_AT_SWEEP with cap == 0; seeds != NULL with seed0 != 0 or a list that does not ascend; the usual
+ * seed0 + total, in_flight and resolve-flag errors; a validate error of any variant (the message starts "variant 3: "). */
+#define MADSIM_SWEEP_MAX_VARIANTS 8u
+#define MADSIM_SWEEP_LIST_MIXED     0u  /* settled seeds whose variants disagree on pass/fail: fail_mask not 0 and not all V bits */
+#define MADSIM_SWEEP_LIST_FAILING   1u  /* settled seeds that fail in at least one variant: fail_mask != 0                        */
+#define MADSIM_SWEEP_LIST_DIFFERING 2u  /* settled seeds with differ_mask != 0                                                    */
+#define MADSIM_CAMPAIGN_STOP_AT_SWEEP 64u /* stop launching once `cap` selected seeds have been read                              */
+typedef struct madsim_sweep_variant {   /* in: one variant; any pointer may repeat across variants                                */
+    const madsim_workload_t* w; const madsim_config_t* cfg; const madsim_limits_t* lim;  /* cfg / lim NULL = defaults, as elsewhere */
+    madsim_campaign_t* out;             /* out: the plain campaign's report for this variant over the same prefix                 */
+} madsim_sweep_variant_t;
+typedef struct madsim_sweep_record {    /* 24 bytes                                                                               */
+    uint64_t seed;
+    uint32_t fail_mask, differ_mask;
+    uint8_t  verdict[8];                /* [v] = variant v's verdict (0..3: listed seeds are settled); 0 for v >= n_variants      */
+} madsim_sweep_record_t;
+typedef struct madsim_sweep {
+    uint32_t fields, list_rule;         /* in: MADSIM_DIFF_* mask compared against variant 0 (0 = compare nothing); MADSIM_SWEEP_LIST_* */
+    madsim_sweep_record_t* records;     /* in: caller's host array [cap]; may be NULL when cap == 0                               */
+    uint64_t cap;
+    uint64_t n_listed;                  /* out: min(cap, n_selected)                                                              */
+    uint64_t n_selected;                /* out: seeds of the prefix the list rule selects                                         */
+    uint64_t n_settled, n_incomparable; /* out: sum = seeds_run                                                                   */
+    uint64_t n_runner_by_variant[8];    /* out: [v] = seeds whose variant v came back with a runner verdict                       */
+    uint64_t n_differ_from_first[8];    /* out: [v] = settled seeds whose masked fields differ between variant v and variant 0; [0] = 0 */
+    uint64_t n_by_mask[256];            /* out: settled seeds per fail_mask; entries at or above 2^n_variants are 0; sum = n_settled */
+} madsim_sweep_t;                       /* 2232 bytes                                                                             */
+int madsim_hip_ctx_run_sweep_campaign(madsim_hip_ctx_t* ctx, const madsim_sweep_variant_t* variants, uint32_t n_variants,
+                                      uint64_t seed0, uint64_t total, const uint64_t* seeds, uint64_t batch, uint32_t in_flight,
+                                      uint32_t flags, madsim_sweep_t* sweep);
+int madsim_hip_run_sweep_campaign(const madsim_sweep_variant_t* variants, uint32_t n_variants, uint64_t seed0, uint64_t total,
+                                  const uint64_t* seeds, uint64_t batch, uint32_t in_flight, uint32_t flags, madsim_sweep_t* sweep);
+int madsim_hip_run_sweep_campaign_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_sweep_variant_t* variants,
+                                        uint32_t n_variants, uint64_t seed0, uint64_t total, const uint64_t* seeds, uint64_t batch,
+                                        uint32_t in_flight, uint32_t flags, madsim_sweep_t* sweep);
+
 /* Geometry the library picked for a workload (for DESIGN/bench reporting). */
 typedef struct madsim_geometry {
     uint32_t lds_bytes_per_seed;

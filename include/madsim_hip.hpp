@@ -780,6 +780,70 @@ struct Builder {
         return diff_against(other, wl, wl, fields, max_listed);           // one test body under two configurations
     }
 
+    // Across several variants: up to eight (builder, workload) pairs over THIS builder's seed .. seed + count — or THIS builder's
+    // over_seeds() list — in one campaign (madsim_hip_run_sweep_campaign): a parameter sweep, a stack of versions of a test body, one body
+    // under every state layout.  Config, capacities and time limit are each variant's own; seed range, device and resolve_runner() rounds
+    // are this builder's.  Every seed is classified across all variants on the device: report.n_by_mask[m] counts the settled seeds that
+    // fail in exactly the variants whose bits m has, and the `max_listed` smallest seeds `list_rule` (MADSIM_SWEEP_LIST_*) selects come
+    // back with their masks and every variant's verdict.  `fields`: the MADSIM_DIFF_* fields compared against variant 0 (0 = none).
+    struct Sweep {
+        std::vector<madsim_sweep_record_t> records;                       // ascending by seed
+        madsim_sweep_t report{};                                          // (records / cap: of the call; read `records` above)
+        std::vector<madsim_campaign_t> campaigns;                         // each variant's plain campaign report
+        size_t n_variants() const { return campaigns.size(); }
+        uint64_t fails(unsigned v) const {                                // settled seeds that fail in variant v
+            uint64_t n = 0;
+            for (unsigned m = 0; m < 256; m++) if (m >> v & 1) n += report.n_by_mask[m];
+            return n;
+        }
+        uint64_t only(unsigned v) const { return report.n_by_mask[1u << v]; }      // ... in variant v and in no other
+        uint64_t fails_not(unsigned i, unsigned j) const {                // ... in variant i and not in variant j
+            uint64_t n = 0;
+            for (unsigned m = 0; m < 256; m++) if ((m >> i & 1) && !(m >> j & 1)) n += report.n_by_mask[m];
+            return n;
+        }
+        bool nested() const {                                             // every non-empty mask is a suffix set: the failing sets grow with the variant index
+            const unsigned full = (1u << n_variants()) - 1u;
+            for (unsigned m = 1; m <= full; m++) if (report.n_by_mask[m] && m != (full & ~((m & (0u - m)) - 1u))) return false;
+            return true;
+        }
+        std::vector<uint64_t> first_failing() const {                     // [v] = settled seeds whose lowest failing variant is v: the bisect reading
+            std::vector<uint64_t> h(n_variants(), 0);
+            for (unsigned m = 1; m < (1u << n_variants()); m++) h[(unsigned)__builtin_ctz(m)] += report.n_by_mask[m];
+            return h;
+        }
+    };
+    Sweep sweep(const std::vector<std::pair<const Builder*, const Workload*>>& variants, uint32_t fields = MADSIM_DIFF_VERDICT,
+                unsigned list_rule = MADSIM_SWEEP_LIST_MIXED, size_t max_listed = 0) const {
+        const size_t V = variants.size();
+        if (V < 2 || V > MADSIM_SWEEP_MAX_VARIANTS) throw std::invalid_argument("sweep: 2 .. MADSIM_SWEEP_MAX_VARIANTS variants");
+        std::vector<madsim_workload_t> w(V);
+        std::vector<madsim_config_t> c(V);
+        std::vector<madsim_limits_t> l(V);
+        std::vector<madsim_sweep_variant_t> var(V);
+        Sweep s;
+        s.campaigns.resize(V);
+        for (size_t v = 0; v < V; v++) {
+            if (!variants[v].first || !variants[v].second) throw std::invalid_argument("sweep: a variant is a builder and a workload");
+            const Builder& b = *variants[v].first;
+            w[v] = variants[v].second->raw(); c[v] = b.config.raw(); l[v] = b.capacities;
+            if (b.time_limit) { l[v].time_limit_ns = (uint64_t)(*b.time_limit * 1e9 + 0.5); if (!l[v].time_limit_ns) l[v].time_limit_ns = 1; }
+            var[v] = madsim_sweep_variant_t{&w[v], &c[v], &l[v], &s.campaigns[v]};
+        }
+        s.records.resize(max_listed);
+        s.report.fields = fields; s.report.list_rule = list_rule;
+        s.report.records = max_listed ? s.records.data() : nullptr;
+        s.report.cap = max_listed;
+        if (!listed_seeds || !seed_list.empty()) madsim::check(madsim_hip_init(device));      // (an empty list runs nothing: no device needed)
+        static const uint64_t none = 0;                                   // (an empty list is still the list form: a non-null pointer)
+        madsim::check(listed_seeds ? madsim_hip_run_sweep_campaign(var.data(), (uint32_t)V, 0, seed_list.size(), seed_list.empty() ? &none : seed_list.data(), 0, 0,
+                                                                   resolve_flags, &s.report)
+                                   : madsim_hip_run_sweep_campaign(var.data(), (uint32_t)V, seed, count, nullptr, 0, 0, resolve_flags, &s.report));
+        s.records.resize((size_t)s.report.n_listed);
+        s.report.records = nullptr;                                       // (the vector may move with the struct)
+        return s;
+    }
+
     // Where the two runs part: this builder's run of `wl` (side A) against `other`'s run of `other_wl` (side B) over `seeds` (any order,
     // duplicates allowed), compared on the device on the determinism log and on the observations (madsim_hip_diverge_seeds): per seed the
     // record, the up to `window` observations both runs made just before they part, and the up to `window` each side made from there on.

@@ -222,6 +222,39 @@ class Diff(C.Structure):
 assert C.sizeof(DiffRecord) == 104 and C.sizeof(Diff) == 632
 
 
+CAMPAIGN_STOP_AT_SWEEP = 64   # sweep campaigns: stop launching once `cap` selected seeds have been read
+SWEEP_MAX_VARIANTS = 8
+SWEEP_LIST_MIXED, SWEEP_LIST_FAILING, SWEEP_LIST_DIFFERING = range(3)      # madsim_sweep_t.list_rule
+SWEEP_LIST_NAMES = ("mixed", "failing", "differing")      # the `list_rule=` names of runtime.run_campaign_sweep, by list_rule
+
+
+class SweepVariant(C.Structure):
+    """madsim_sweep_variant_t: one variant of a sweep campaign going in — workload, config, limits (NULL = defaults) — and where its plain
+    campaign report goes."""
+    _fields_ = [("w", C.POINTER(Workload)), ("cfg", C.POINTER(Config)), ("lim", C.POINTER(Limits)), ("out", C.POINTER(Campaign))]
+
+
+class SweepRecord(C.Structure):
+    """madsim_sweep_record_t: one listed seed of a sweep campaign — the seed, the variants it fails in, the variants whose masked fields differ
+    from variant 0's, and every variant's verdict."""
+    _fields_ = [("seed", C.c_uint64), ("fail_mask", C.c_uint32), ("differ_mask", C.c_uint32), ("verdict", C.c_uint8 * 8)]
+
+
+class Sweep(C.Structure):
+    """madsim_sweep_t: the compared fields, the list rule and the caller's record array going in; the list length and the counts coming out."""
+    _fields_ = [("fields", C.c_uint32), ("list_rule", C.c_uint32), ("records", C.POINTER(SweepRecord)), ("cap", C.c_uint64), ("n_listed", C.c_uint64),
+                ("n_selected", C.c_uint64), ("n_settled", C.c_uint64), ("n_incomparable", C.c_uint64), ("n_runner_by_variant", C.c_uint64 * 8),
+                ("n_differ_from_first", C.c_uint64 * 8), ("n_by_mask", C.c_uint64 * 256)]
+
+
+# numpy view of a sweep campaign's list: madsim_sweep_record_t
+SWEEP_RECORD_DTYPE = [("seed", "<u8"), ("fail_mask", "<u4"), ("differ_mask", "<u4"), ("verdict", "u1", (8,))]
+assert C.sizeof(SweepVariant) == 32 and C.sizeof(SweepRecord) == 24 and C.sizeof(Sweep) == 2232
+HEADER_STRUCTS["madsim_sweep_variant_t"] = SweepVariant
+HEADER_STRUCTS["madsim_sweep_record_t"] = SweepRecord
+HEADER_STRUCTS["madsim_sweep_t"] = Sweep
+
+
 CAMPAIGN_RESOLVE = 32         # every campaign form: re-run runner verdicts on the device before a batch is reported
 CAMPAIGN_RESOLVE_ROUNDS_SHIFT, CAMPAIGN_RESOLVE_ROUNDS_MASK = 8, 0xF00      # flag bits 8-11: the number of rounds, 0 = the default
 RESOLVE_DEFAULT_ROUNDS, RESOLVE_MAX_ROUNDS = 4, 8

@@ -97,6 +97,7 @@ struct madsim_hip_resources {
     static constexpr size_t STATS_REP_WORDS = 16 + MADSIM_K_STATS_WORDS;      // a statistics campaign's report: the plain / collecting report's words in front
     static constexpr size_t GROUP_REP_WORDS = STATS_REP_WORDS + MADSIM_K_GROUP_WORDS;
     static constexpr size_t DIFF_REP_WORDS = 16 + MADSIM_K_DIFF_WORDS;      // summary6's six words of side A at 0, of side B at 8, the diff words at 16
+    static constexpr size_t SWEEP_REP_WORDS = 8 * MADSIM_SWEEP_MAX_VARIANTS + MADSIM_K_SWEEP_WORDS;      // summary6's six words of variant v at 8 v, the sweep words at 64
     // One batch in flight: what every form uses, then one group per campaign form, made when a call of that form first comes (ensure)
     // and kept with the flight.  Every resource is ensured on its own — none stands for another —, so a call that ran out of memory
     // half-way leaves nothing that a later call would take for complete.
@@ -174,6 +175,33 @@ struct madsim_hip_resources {
                 return 0;
             }
         } diff;
+        // sweep campaigns: the results of variants 1 .. 7 (variant 0 uses d_out), made only up to the number of variants a call needs, an
+        // event pair per variant, the report words — SWEEP_REP_WORDS live ones (device, page-locked host) and behind the device's a copy of
+        // their state before a batch —, per-wave counts and the batch's records
+        struct Sweep {
+            DevBuf<madsim_result_t> out[MADSIM_SWEEP_MAX_VARIANTS - 1]; Event v0[MADSIM_SWEEP_MAX_VARIANTS], v1[MADSIM_SWEEP_MAX_VARIANTS];
+            DevBuf<report_word_t> d_rep; PinnedBuf<report_word_t> h_rep; DevBuf<uint32_t> wcnt; DevBuf<madsim_sweep_record_t> rec;
+            int ensure(uint32_t n_variants, uint64_t batch, uint64_t records, hipStream_t s) {
+                if (!d_rep) {
+                    report_word_t init[SWEEP_REP_WORDS] = {};                       // the words before a batch: every summary6's two minima all-ones, the rest zero
+                    for (uint32_t v = 0; v < MADSIM_SWEEP_MAX_VARIANTS; v++) init[8 * v] = init[8 * v + 4] = ~0ull;
+                    HIP_TRY(d_rep.room(2 * SWEEP_REP_WORDS));
+                    const hipError_t e = hipMemcpy(d_rep + SWEEP_REP_WORDS, init, sizeof init, hipMemcpyHostToDevice);
+                    if (e != hipSuccess) {                                          // (words without their initial state are no words)
+                        d_rep.reset();
+                        return fail(MADSIM_E_HIP, std::string("hipMemcpy(initial report words): ") + hipGetErrorString(e));
+                    }
+                }
+                HIP_TRY(h_rep.room(SWEEP_REP_WORDS));
+                HIP_TRY(wcnt.room(MADSIM_K_COLLECT_WAVES));
+                for (uint32_t v = 0; v < n_variants; v++) {
+                    HIP_TRY(v0[v].ensure()); HIP_TRY(v1[v].ensure());
+                    if (v) HIP_TRY(out[v - 1].room(batch, s));
+                }
+                HIP_TRY(rec.room(records, s));
+                return 0;
+            }
+        } sweep;
         // resolving campaigns, made when a batch first needs a round (most campaigns never do), enlarged — with the flight's stream drained —
         // when a later call brings larger batches: the seed list, the index list and the re-run results of `want` seeds (60 B per seed), the
         // list kernels' wave counts with the count word behind them (device) and that word's page-locked host copy, the re-run kernel's event pair
@@ -1191,6 +1219,21 @@ extern "C" uint64_t madsim_k_fold_diff(madsim_diff_t* diff, const unsigned long 
     return take;
 }
 
+// ---- sweep campaigns: the host fold of a batch's words -----------------------------------------------------------------------------
+// w = a batch's MADSIM_K_SWEEP_WORDS (sim_kernel.hip): {n_selected, n_incomparable, n_runner_by_variant[8], n_differ_from_first[8],
+// n_by_mask[256]}.  The counts commute; the list is appended in batch order, which is seed order, and never beyond `cap`.
+extern "C" uint64_t madsim_k_fold_sweep(madsim_sweep_t* sweep, const unsigned long long* w, uint64_t count, const madsim_sweep_record_t* batch_recs) {
+    sweep->n_selected += w[0];
+    sweep->n_incomparable += w[1];
+    sweep->n_settled += count - w[1];
+    for (int v = 0; v < 8; v++) { sweep->n_runner_by_variant[v] += w[2 + v]; sweep->n_differ_from_first[v] += w[10 + v]; }
+    for (int k = 0; k < 256; k++) sweep->n_by_mask[k] += w[18 + k];
+    const uint64_t take = std::min<uint64_t>(w[0], sweep->cap - sweep->n_listed);
+    if (take && batch_recs) memcpy(sweep->records + sweep->n_listed, batch_recs, take * sizeof(madsim_sweep_record_t));
+    sweep->n_listed += take;
+    return take;
+}
+
 // ---- campaigns -------------------------------------------------------------------------------------------------------------
 // One implementation for one context and for several (madsim_hip_run_campaign_multi): batch k of the range runs on context k % n,
 // on that context's flight (k / n) % in_flight — the devices advance through the seed space TOGETHER, so with
@@ -1634,6 +1677,132 @@ int run_campaign_diff_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const DiffSid
     for (const DiffSide& s : side) { s.out->batches_launched = launched; s.out->wall_s = since(t0); }
     return first_err ? fail(first_err, first_msg) : 0;
 }
+
+// The sweep form: the same flights, the same loop; per batch every variant's simulation and summary6 launches, then the two sweep kernels,
+// all on the flight's one stream, and one copy of the words.  Every variant of batch k runs on context k % n.  `var`: the caller's
+// variants with a NULL config replaced by the default one (check_sweep_args has validated them).
+int run_campaign_sweep_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_sweep_variant_t* var, uint32_t V, uint64_t seed0, uint64_t total,
+                            uint64_t batch, uint32_t in_flight, uint32_t flags, madsim_sweep_t* sw, const uint64_t* list) {
+    // `list`: as in run_campaign_impl — position i of list[0 .. total) for seed0 + i, seed0 = 0; every variant of a batch reads the same slice.
+    auto t0 = std::chrono::steady_clock::now();
+    for (uint32_t v = 0; v < V; v++) { memset(var[v].out, 0, sizeof *var[v].out); var[v].out->first_failing_seed = UINT64_MAX; }
+    sw->n_listed = sw->n_selected = sw->n_settled = sw->n_incomparable = 0;
+    memset(sw->n_runner_by_variant, 0, sizeof sw->n_runner_by_variant);
+    memset(sw->n_differ_from_first, 0, sizeof sw->n_differ_from_first);
+    memset(sw->n_by_mask, 0, sizeof sw->n_by_mask);
+    flags &= MADSIM_CAMPAIGN_STOP_AT_SWEEP | MADSIM_CAMPAIGN_RESOLVE | MADSIM_CAMPAIGN_RESOLVE_ROUNDS_MASK;      // (the other stop flags belong to the other forms)
+    const uint32_t R = resolve_rounds(flags);
+    ResolveAccount account(ctxs, n_ctx, R);
+    madsim_resolve_t& acct = account.a;
+    int rc;
+    if ((rc = check_campaign_range(batch, in_flight, list != nullptr, seed0, total))) return rc;
+    if (total == 0) return 0;
+    const uint64_t width = std::min(batch, total);
+    if (width >= (1ull << 32)) return fail(MADSIM_E_ARG, "a sweep campaign's batch holds fewer than 2^32 seeds");
+    if (R && width >= (1ull << 30)) return fail(MADSIM_E_ARG, "a resolving campaign's batch holds fewer than 2^30 seeds");
+    const uint64_t n_batches = (total + batch - 1) / batch, N = (uint64_t)n_ctx;
+    const uint64_t rec_batch = std::min(sw->cap, width);     // records a flight holds: no batch lists more
+    CampaignFlights flights(ctxs, n_ctx);
+    if ((rc = flights.setup(n_batches, batch, width, in_flight, list != nullptr,
+                            [&](madsim_hip_ctx* c) {
+                                uint32_t f = c->flights_for(var[0].w, var[0].cfg, var[0].lim, batch);
+                                for (uint32_t v = 1; v < V; v++) f = std::min(f, c->flights_for(var[v].w, var[v].cfg, var[v].lim, batch));
+                                return f;
+                            },
+                            [&](madsim_hip_ctx::Flight& f) { return f.sweep.ensure(V, batch, rec_batch, f.stream); })))
+        return rc;
+    constexpr size_t n_words = madsim_hip_ctx::SWEEP_REP_WORDS, at_sweep = 8 * MADSIM_SWEEP_MAX_VARIANTS;
+    int first_err = 0;
+    std::string first_msg;
+    bool stop = false;
+    auto results_of = [](madsim_hip_ctx::Flight& f, uint32_t v) -> madsim_result_t* { return v ? f.sweep.out[v - 1] : f.d_out; };
+    auto who = [](uint32_t v) { return "variant " + std::to_string(v) + ": "; };
+    // A batch's report chain in the parts that `queue` puts around the simulation launches and a resolving `harvest` queues again back to
+    // back: the words reset by one device copy, a variant's summary6 over its results, then the sweep kernels, the copy and the `done` event.
+    auto prepare_report = [&](madsim_hip_ctx::Flight& f) -> int {
+        HIP_TRY(hipMemcpyAsync(f.sweep.d_rep, f.sweep.d_rep + n_words, n_words * sizeof(unsigned long long), hipMemcpyDeviceToDevice, f.stream));
+        return 0;
+    };
+    auto queue_summary = [&](madsim_hip_ctx::Flight& f, uint32_t v, uint64_t lo, uint64_t n) -> int {
+        if (list) madsim_k_launch_summary6_list(results_of(f, v), n, f.list.d, f.sweep.d_rep + 8 * v, f.stream);
+        else madsim_k_launch_summary6(results_of(f, v), n, seed0 + lo, f.sweep.d_rep + 8 * v, f.stream);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    };
+    auto queue_sweep = [&](madsim_hip_ctx::Flight& f, uint64_t lo, uint64_t n) -> int {
+        const madsim_result_t* sides[MADSIM_SWEEP_MAX_VARIANTS] = {};
+        for (uint32_t v = 0; v < V; v++) sides[v] = results_of(f, v);
+        if (list ? madsim_k_launch_sweep_list(sides, V, n, f.list.d, sw->fields, sw->list_rule, f.sweep.d_rep + at_sweep, f.sweep.wcnt, f.sweep.rec, std::min(rec_batch, n), f.stream)
+                 : madsim_k_launch_sweep(sides, V, n, seed0 + lo, sw->fields, sw->list_rule, f.sweep.d_rep + at_sweep, f.sweep.wcnt, f.sweep.rec, std::min(rec_batch, n), f.stream))
+            return fail(MADSIM_E_ARG, "madsim_k_launch_sweep refused the batch's arguments");
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(f.sweep.h_rep, f.sweep.d_rep, n_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, f.stream));
+        HIP_TRY(hipEventRecord(f.done, f.stream));
+        return 0;
+    };
+    auto queue = [&](uint64_t k) -> int {
+        madsim_hip_ctx* c = ctxs[k % N];
+        madsim_hip_ctx::Flight& f = flights.of(k);
+        const uint64_t lo = k * batch, n = std::min(batch, total - lo);
+        int e;
+        if ((e = c->bind())) return e;
+        if ((e = prepare_report(f))) return e;
+        if (list && (e = queue_list_slice(f, list, lo, n))) return e;      // (one slice for every variant)
+        const uint64_t* const d_list = list ? f.list.d : nullptr;
+        for (uint32_t v = 0; v < V; v++) {
+            HIP_TRY(hipEventRecord(f.sweep.v0[v], f.stream));
+            if ((e = c->launch(var[v].w, var[v].cfg, seed0 + lo, n, d_list, var[v].lim, results_of(f, v), f.stream))) return fail(e, who(v) + g_err);
+            HIP_TRY(hipEventRecord(f.sweep.v1[v], f.stream));
+            if ((e = queue_summary(f, v, lo, n))) return e;
+        }
+        return queue_sweep(f, lo, n);
+    };
+    auto harvest = [&](uint64_t k) -> int {
+        madsim_hip_ctx* c = ctxs[k % N];
+        madsim_hip_ctx::Flight& f = flights.of(k);
+        int e;
+        if ((e = c->bind())) return e;
+        HIP_TRY(hipEventSynchronize(f.done));
+        if (first_err || stop) return 0;                        // (draining after an error, or a batch launched beyond the stopping one)
+        const uint64_t lo = k * batch, n = std::min(batch, total - lo);
+        const unsigned long long* const h = f.sweep.h_rep;
+        float ms[MADSIM_SWEEP_MAX_VARIANTS] = {};
+        for (uint32_t v = 0; v < V; v++) HIP_TRY(hipEventElapsedTime(&ms[v], f.sweep.v0[v], f.sweep.v1[v]));
+        unsigned long long runner_before[MADSIM_SWEEP_MAX_VARIANTS] = {}, any_runner = 0;
+        for (uint32_t v = 0; v < V; v++) any_runner += runner_before[v] = h[8 * v + 5];
+        if (R && any_runner) {                                  // runner verdicts in a variant: settle them under that variant's own limits, sweep again
+            bool ran = false;
+            for (uint32_t v = 0; v < V; v++) {                  // (one after the other on the flight's stream: they share its re-run scratch)
+                if (!runner_before[v]) continue;
+                double rerun_ms = 0.0;
+                if ((e = resolve_results(c, f, var[v].w, var[v].cfg, var[v].lim, results_of(f, v), seed0 + lo, list ? f.list.d : nullptr, n, R, acct, &rerun_ms,
+                                         &ran)))
+                    return fail(e, who(v) + g_err);
+                acct.rerun_kernel_ms += rerun_ms; var[v].out->kernel_ms += rerun_ms;
+            }
+            if (ran) {
+                if ((e = prepare_report(f))) return e;
+                for (uint32_t v = 0; v < V; v++) if ((e = queue_summary(f, v, lo, n))) return e;
+                if ((e = queue_sweep(f, lo, n))) return e;
+                HIP_TRY(hipEventSynchronize(f.done));
+                for (uint32_t v = 0; v < V; v++) acct.n_resolved += runner_before[v] - h[8 * v + 5];
+            }
+        }
+        for (uint32_t v = 0; v < V; v++) fold_summary(var[v].out, h + 8 * v, n, ms[v]);
+        if (h[at_sweep] > n) return fail(MADSIM_E_HIP, "sweep campaign: a batch reports more selected seeds than it holds");
+        // the batch's records, as many as the list still takes (the stream is idle: its `done` has passed, and it takes no launch before this returns)
+        const uint64_t at = sw->n_listed, take = madsim_k_fold_sweep(sw, h + at_sweep, n, nullptr);
+        if (take) {
+            HIP_TRY(hipMemcpyAsync(sw->records + at, f.sweep.rec, take * sizeof(madsim_sweep_record_t), hipMemcpyDeviceToHost, f.stream));
+            HIP_TRY(hipStreamSynchronize(f.stream));
+        }
+        if ((flags & MADSIM_CAMPAIGN_STOP_AT_SWEEP) && sw->n_selected >= sw->cap) stop = true;
+        return 0;
+    };
+    const uint64_t launched = pump_batches(ctxs, n_ctx, n_batches, flights.F, stop, first_err, first_msg, queue, harvest);
+    for (uint32_t v = 0; v < V; v++) { var[v].out->batches_launched = launched; var[v].out->wall_s = since(t0); }
+    return first_err ? fail(first_err, first_msg) : 0;
+}
 }  // namespace
 
 int madsim_hip_ctx_run_campaign(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total,
@@ -1855,6 +2024,60 @@ int madsim_hip_run_seeds_campaign_diff_multi(madsim_hip_ctx_t* const* ctxs, int 
     return run_campaign_diff_impl(ctxs, n_ctx, side, 0, n, batch, in_flight, flags, diff, n ? seeds : nullptr);
 }
 
+// ---- sweep campaigns: up to eight variants over one seed set ------------------------------------------------------------------------
+// Argument errors first, as the other forms — here the variants' validate() errors too, all told before any context is looked at.  `var`
+// receives the variants with a NULL config replaced by the default one (loss 0, latency 1 .. 10 ms, no tables).
+namespace {
+const madsim_config_t g_default_config = [] { madsim_config_t c{}; c.lat_lo_ns = 1000000; c.lat_hi_ns = 10000000; return c; }();
+int check_sweep_args(const madsim_sweep_variant_t* variants, uint32_t n_variants, uint64_t seed0, uint64_t total, const uint64_t* seeds, uint32_t in_flight,
+                     uint32_t flags, const madsim_sweep_t* sw, std::vector<madsim_sweep_variant_t>& var) {
+    if (n_variants < 2 || n_variants > MADSIM_SWEEP_MAX_VARIANTS) return fail(MADSIM_E_ARG, "a sweep campaign runs 2 .. MADSIM_SWEEP_MAX_VARIANTS (8) variants");
+    if (!variants) return fail(MADSIM_E_ARG, "null variants array");
+    if (!sw) return fail(MADSIM_E_ARG, "null madsim_sweep_t");
+    for (uint32_t v = 0; v < n_variants; v++) {
+        if (!variants[v].w) return fail(MADSIM_E_ARG, "variant " + std::to_string(v) + ": null workload");
+        if (!variants[v].out) return fail(MADSIM_E_ARG, "variant " + std::to_string(v) + ": null campaign report (a sweep campaign fills one per variant)");
+    }
+    if (sw->fields & ~MADSIM_DIFF_ALL) return fail(MADSIM_E_ARG, "madsim_sweep_t.fields: no bit above MADSIM_DIFF_ALL");
+    if (sw->list_rule > MADSIM_SWEEP_LIST_DIFFERING) return fail(MADSIM_E_ARG, "madsim_sweep_t.list_rule: one of MADSIM_SWEEP_LIST_*");
+    if (sw->list_rule == MADSIM_SWEEP_LIST_DIFFERING && !sw->fields) return fail(MADSIM_E_ARG, "MADSIM_SWEEP_LIST_DIFFERING with fields == 0: nothing is compared");
+    if (sw->cap && !sw->records) return fail(MADSIM_E_ARG, "madsim_sweep_t.cap > 0 without a records array");
+    if ((flags & MADSIM_CAMPAIGN_STOP_AT_SWEEP) && !sw->cap) return fail(MADSIM_E_ARG, "MADSIM_CAMPAIGN_STOP_AT_SWEEP with cap == 0");
+    if (seeds && seed0) return fail(MADSIM_E_ARG, "a sweep campaign over a seed list takes seed0 == 0");
+    if (seeds) { if (int rc = check_seed_list(seeds, total)) return rc; }
+    else if (seed0 + total < seed0) return fail(MADSIM_E_ARG, "seed0 + total wraps");
+    if (int rc = check_resolve_flags(flags)) return rc;
+    if (in_flight > (uint32_t)madsim_hip_ctx::CAMPAIGN_MAX) return fail(MADSIM_E_ARG, "at most 8 batches in flight per context");
+    var.assign(variants, variants + n_variants);
+    for (uint32_t v = 0; v < n_variants; v++) {
+        if (!var[v].cfg) var[v].cfg = &g_default_config;
+        if (int rc = madsim_geo::validate(var[v].w, var[v].cfg, &g_err)) return fail(rc, "variant " + std::to_string(v) + ": " + g_err);
+    }
+    return 0;
+}
+}  // namespace
+
+int madsim_hip_ctx_run_sweep_campaign(madsim_hip_ctx_t* c, const madsim_sweep_variant_t* variants, uint32_t n_variants, uint64_t seed0, uint64_t total,
+                                      const uint64_t* seeds, uint64_t batch, uint32_t in_flight, uint32_t flags, madsim_sweep_t* sweep) {
+    std::vector<madsim_sweep_variant_t> var;
+    if (int rc = check_sweep_args(variants, n_variants, seed0, total, seeds, in_flight, flags, sweep, var)) return rc;
+    if (total == 0 && (!c || c->device < 0))                     // nothing to run needs no device: the reports of an empty range, and 0
+        return run_campaign_sweep_impl(nullptr, 0, var.data(), n_variants, 0, 0, batch, in_flight, flags, sweep, nullptr);
+    CTX_ENTER(c);
+    madsim_hip_ctx* one[1] = {c};
+    return run_campaign_sweep_impl(one, 1, var.data(), n_variants, seed0, total, batch, in_flight, flags, sweep, total ? seeds : nullptr);
+}
+
+int madsim_hip_run_sweep_campaign_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_sweep_variant_t* variants, uint32_t n_variants,
+                                        uint64_t seed0, uint64_t total, const uint64_t* seeds, uint64_t batch, uint32_t in_flight, uint32_t flags,
+                                        madsim_sweep_t* sweep) {
+    std::vector<madsim_sweep_variant_t> var;
+    if (int rc = check_sweep_args(variants, n_variants, seed0, total, seeds, in_flight, flags, sweep, var)) return rc;
+    std::vector<std::unique_lock<std::mutex>> locks;
+    if (int rc = lock_contexts(ctxs, n_ctx, "run_sweep_campaign_multi", locks)) return rc;
+    return run_campaign_sweep_impl(ctxs, n_ctx, var.data(), n_variants, seed0, total, batch, in_flight, flags, sweep, total ? seeds : nullptr);
+}
+
 // ---- v1 entry points: wrappers on the process-default context ------------------------------------------------------------
 // The default context is reference-counted by its users: a wrapper pins it under g_default_mu for the duration of its call,
 // and madsim_hip_shutdown waits until no call is inside before destroying it — a concurrent run_batch and shutdown is a
@@ -1996,6 +2219,12 @@ int madsim_hip_run_seeds_campaign_diff(const madsim_workload_t* wA, const madsim
                                        uint32_t in_flight, uint32_t flags, madsim_campaign_t* outA, madsim_campaign_t* outB, madsim_diff_t* diff) {
     DefaultPin p;
     return madsim_hip_ctx_run_seeds_campaign_diff(p.c, wA, cfgA, limA, wB, cfgB, limB, seeds, n, batch, in_flight, flags, outA, outB, diff);
+}
+
+int madsim_hip_run_sweep_campaign(const madsim_sweep_variant_t* variants, uint32_t n_variants, uint64_t seed0, uint64_t total, const uint64_t* seeds,
+                                  uint64_t batch, uint32_t in_flight, uint32_t flags, madsim_sweep_t* sweep) {
+    DefaultPin p;
+    return madsim_hip_ctx_run_sweep_campaign(p.c, variants, n_variants, seed0, total, seeds, batch, in_flight, flags, sweep);
 }
 
 int madsim_hip_geometry(const madsim_workload_t* w, const madsim_limits_t* lim, madsim_geometry_t* out) {

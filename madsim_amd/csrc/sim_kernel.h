@@ -371,6 +371,23 @@ int  madsim_k_launch_diff(const madsim_result_t* a, const madsim_result_t* b, ui
 // Returns how many of the batch's records the list still takes — min(the batch's n_differ, cap - n_listed) — and advances n_listed by it;
 // when `batch_recs` (host memory, at least that many) is given they are appended to diff->records, otherwise the caller copies them there.
 uint64_t madsim_k_fold_diff(madsim_diff_t* diff, const unsigned long long* words, uint64_t count, const madsim_diff_record_t* batch_recs);
+// the sweep campaign's report kernels, behind the variants' simulation and summary6 launches on the same stream: sides[0 .. n_variants) (a HOST
+// array of device pointers, 2 .. MADSIM_SWEEP_MAX_VARIANTS of them) are the variants' results of the same `count` seeds.  `words`:
+// MADSIM_K_SWEEP_WORDS words, ALL ZERO before the launch: {n_selected, n_incomparable, n_runner_by_variant[8], n_differ_from_first[8],
+// n_by_mask[256]} of the batch; `wave_cnt`: MADSIM_K_COLLECT_WAVES words of scratch (every wave's number of selected seeds); `recs`: the `cap`
+// selected seeds of the batch with the smallest seeds, ascending (may be null when cap == 0; nothing behind min(cap, n_selected) is written).
+// `fields`: a MADSIM_DIFF_* mask (0 = compare nothing), `rule`: MADSIM_SWEEP_LIST_*.  Returns 0, or -1 without launching anything for
+// n_variants outside 2 .. 8, a NULL side, count == 0 or count >= 2^32, a bit above MADSIM_DIFF_ALL, rule > 2, LIST_DIFFERING with
+// fields == 0, or cap > 0 without records.
+#define MADSIM_K_SWEEP_WORDS 274u       /* 64-bit words of a batch's sweep report: 2 + 8 + 8 + 256 */
+int  madsim_k_launch_sweep(const madsim_result_t* const* sides, uint32_t n_variants, uint64_t count, uint64_t seed0, uint32_t fields, uint32_t rule,
+                           unsigned long long* words, uint32_t* wave_cnt, madsim_sweep_record_t* recs, uint64_t cap, void* stream);
+int  madsim_k_launch_sweep_list(const madsim_result_t* const* sides, uint32_t n_variants, uint64_t count, const uint64_t* d_seeds, uint32_t fields,
+                                uint32_t rule, unsigned long long* words, uint32_t* wave_cnt, madsim_sweep_record_t* recs, uint64_t cap, void* stream);
+// the host fold of one batch's MADSIM_K_SWEEP_WORDS into the caller's report (madsim_hip.cpp; no device involved): batches in seed order.
+// Returns how many of the batch's records the list still takes — min(the batch's n_selected, cap - n_listed) — and advances n_listed by it;
+// when `batch_recs` (host memory, at least that many) is given they are appended to sweep->records, otherwise the caller copies them there.
+uint64_t madsim_k_fold_sweep(madsim_sweep_t* sweep, const unsigned long long* words, uint64_t count, const madsim_sweep_record_t* batch_recs);
 // resolving campaigns (MADSIM_CAMPAIGN_RESOLVE).  The list pair, over collect's cut of the batch: a result is re-runnable when its verdict is
 // MADSIM_OVERFLOW, or MADSIM_STEP_LIMIT with `steps_maxed` == 0.  *total = m, the re-runnable seeds of out[0 .. count); seeds[0 .. m) =
 // seed0 + i and idx[0 .. m) = i of those results, ascending, the same on every run; nothing behind m is written.  `wave_cnt`:

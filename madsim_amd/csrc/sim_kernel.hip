@@ -586,6 +586,151 @@ __global__ __launch_bounds__(256) void diff_write_kernel(const madsim_result_t* 
     }
 }
 
+// ---- the sweep campaign form: up to eight result arrays of the same seeds, classified across all of them ----
+// Two kernels behind the variants' simulation and summary6 launches, over collect's cut of the batch.  Variant v of a seed is PASS
+// (verdict 0), FAIL (1 .. 3) or RUNNER; fail / runner: the masks of the variants that are; a seed is SETTLED when runner == 0, and only
+// then has a differ mask: bit v (v >= 1) set when a field named in `fields` differs between variant v and variant 0 (diff_mask's
+// comparison).  The V array pointers travel by value in SweepSides; every loop over variants is unrolled to 8 with a wave-uniform v < V
+// guard, so the table is indexed by constants only and stays in scalar registers.  All V 16-byte heads of a round are loaded before the
+// first compare (V independent requests per lane); the second and third 16 bytes only when `fields` names one of theirs.
+// words = {n_selected, n_incomparable, n_runner_by_variant[8], n_differ_from_first[8], n_by_mask[256]}, all zero before the launch.
+// Cell n_by_mask[0] is not counted: sweep_write_kernel sets it to count - n_incomparable - the other 255, so a round of 64 seeds that
+// passed in every variant with no masked difference ends at one ballot.  Any other round adds its settled seeds' cells to 256 LDS
+// counters of the workgroup (one global atomic per non-zero cell per workgroup) and its ballots' popcounts to the wave's registers
+// (one set of global atomics per wave, none when zero).  wave_cnt[W] = the wave's number of SELECTED seeds (the list rule's).
+// sweep_write_kernel is diff_write_kernel with V sources: only a wave with selected seeds and an offset below `cap` reads its piece
+// again, rank = offset + lanes_below(ballot).  A record is {seed, fail | differ << 32, the eight verdict bytes}: three 8-byte stores.
+struct SweepSides { const madsim_result_t* r[MADSIM_SWEEP_MAX_VARIANTS]; };
+struct SweepSeed { uint32_t fail, runner, differ; unsigned long long verdicts; };
+
+// seed i of the batch across the V variants (live: i is inside the wave's piece; a dead lane is PASS everywhere, nothing differing)
+__device__ __forceinline__ SweepSeed sweep_classify(const SweepSides& S, uint32_t V, uint64_t i, bool live, uint32_t fields, DiffLoads L) {
+    uint4 h[MADSIM_SWEEP_MAX_VARIANTS];
+#pragma unroll
+    for (uint32_t v = 0; v < MADSIM_SWEEP_MAX_VARIANTS; v++) {
+        h[v] = uint4{0, 0, 0, 0};
+        if (v < V && live) h[v] = reinterpret_cast<const uint4*>(S.r[v] + i)[0];
+    }
+    SweepSeed s{0, 0, 0, 0};
+#pragma unroll
+    for (uint32_t v = 0; v < MADSIM_SWEEP_MAX_VARIANTS; v++) {
+        if (v >= V) continue;
+        const uint32_t x = h[v].x;
+        s.fail |= (x - 1u < 3u ? 1u : 0u) << v;
+        s.runner |= (MADSIM_IS_RUNNER_VERDICT(x) ? 1u : 0u) << v;
+        s.verdicts |= (unsigned long long)(x & 0xffu) << (8u * v);
+        if (v == 0) continue;
+        const uint32_t d = (x != h[0].x ? MADSIM_DIFF_VERDICT : 0u) | (h[v].y != h[0].y ? MADSIM_DIFF_STEPS : 0u) |
+                           ((h[v].z != h[0].z || h[v].w != h[0].w) ? MADSIM_DIFF_CLOCK : 0u);
+        s.differ |= ((d & fields) ? 1u : 0u) << v;
+    }
+    if (L.b1 && live) {                                                            // (L: wave-uniform)
+        uint4 p[MADSIM_SWEEP_MAX_VARIANTS];
+#pragma unroll
+        for (uint32_t v = 0; v < MADSIM_SWEEP_MAX_VARIANTS; v++) if (v < V) p[v] = reinterpret_cast<const uint4*>(S.r[v] + i)[1];
+#pragma unroll
+        for (uint32_t v = 1; v < MADSIM_SWEEP_MAX_VARIANTS; v++) {
+            if (v >= V) continue;
+            const uint32_t d = ((p[v].x != p[0].x || p[v].y != p[0].y) ? MADSIM_DIFF_MSGS : 0u) | ((p[v].z != p[0].z || p[v].w != p[0].w) ? MADSIM_DIFF_RNG : 0u);
+            s.differ |= ((d & fields) ? 1u : 0u) << v;
+        }
+    }
+    if (L.b2 && live) {
+        uint4 p[MADSIM_SWEEP_MAX_VARIANTS];
+#pragma unroll
+        for (uint32_t v = 0; v < MADSIM_SWEEP_MAX_VARIANTS; v++) if (v < V) p[v] = reinterpret_cast<const uint4*>(S.r[v] + i)[2];
+#pragma unroll
+        for (uint32_t v = 1; v < MADSIM_SWEEP_MAX_VARIANTS; v++) {
+            if (v >= V) continue;
+            const uint32_t d = ((p[v].x != p[0].x || p[v].y != p[0].y) ? MADSIM_DIFF_TRACE : 0u) | ((p[v].z != p[0].z || p[v].w != p[0].w) ? MADSIM_DIFF_OBS : 0u);
+            s.differ |= ((d & fields) ? 1u : 0u) << v;
+        }
+    }
+    if (s.runner) s.differ = 0;                                                    // an incomparable seed differs nowhere
+    return s;
+}
+// the list rule; full = the fail mask of a seed that fails in every variant
+__device__ __forceinline__ bool sweep_selected(const SweepSeed& s, uint32_t rule, uint32_t full) {
+    if (s.runner) return false;
+    return rule == MADSIM_SWEEP_LIST_DIFFERING ? s.differ != 0 : rule == MADSIM_SWEEP_LIST_FAILING ? s.fail != 0 : (s.fail != 0 && s.fail != full);
+}
+
+__global__ __launch_bounds__(256) void sweep_count_kernel(const SweepSides S, uint32_t V, uint64_t count, uint64_t piece, uint32_t fields, uint32_t rule,
+                                                          unsigned long long* __restrict__ words, uint32_t* __restrict__ wave_cnt) {
+    __shared__ uint32_t cells[256];
+    const uint32_t W = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    cells[threadIdx.x] = 0;
+    __syncthreads();
+    const uint64_t lo = (uint64_t)W * piece, hi = lo + piece < count ? lo + piece : count;
+    const DiffLoads L = diff_loads(fields);
+    const uint32_t full = (1u << V) - 1u;
+    uint32_t n_sel = 0, n_inc = 0, by_runner[MADSIM_SWEEP_MAX_VARIANTS] = {0, 0, 0, 0, 0, 0, 0, 0}, by_differ[MADSIM_SWEEP_MAX_VARIANTS] = {0, 0, 0, 0, 0, 0, 0, 0};      // wave-uniform
+    for (uint64_t base = lo; base < hi; base += 64) {
+        const uint64_t i = base + lane;
+        const SweepSeed s = sweep_classify(S, V, i, i < hi, fields, L);
+        if (!__ballot((s.fail | s.runner | s.differ) != 0)) continue;              // (wave-uniform) every variant passed, nothing masked differs
+        if (!s.runner && s.fail) atomicAdd(&cells[s.fail], 1u);
+        n_sel += (uint32_t)__popcll(__ballot(sweep_selected(s, rule, full)));
+        const unsigned long long inc = __ballot(s.runner != 0);
+        if (inc) {                                                                 // (wave-uniform)
+            n_inc += (uint32_t)__popcll(inc);
+#pragma unroll
+            for (uint32_t v = 0; v < MADSIM_SWEEP_MAX_VARIANTS; v++) by_runner[v] += (uint32_t)__popcll(__ballot((s.runner >> v) & 1u));
+        }
+        if (__ballot(s.differ != 0)) {
+#pragma unroll
+            for (uint32_t v = 1; v < MADSIM_SWEEP_MAX_VARIANTS; v++) by_differ[v] += (uint32_t)__popcll(__ballot((s.differ >> v) & 1u));
+        }
+    }
+    if (lane == 0) {                                                               // one set of atomics per wave: none when zero
+        wave_cnt[W] = n_sel;
+        if (n_sel) atomicAdd(&words[0], (unsigned long long)n_sel);
+        if (n_inc) atomicAdd(&words[1], (unsigned long long)n_inc);
+#pragma unroll
+        for (uint32_t v = 0; v < MADSIM_SWEEP_MAX_VARIANTS; v++) {
+            if (by_runner[v]) atomicAdd(&words[2 + v], (unsigned long long)by_runner[v]);
+            if (by_differ[v]) atomicAdd(&words[10 + v], (unsigned long long)by_differ[v]);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x > 0 && cells[threadIdx.x]) atomicAdd(&words[18 + threadIdx.x], (unsigned long long)cells[threadIdx.x]);
+}
+
+template <class Seeds>
+__global__ __launch_bounds__(256) void sweep_write_kernel(const SweepSides S, uint32_t V, uint64_t count, const Seeds seed_of, uint64_t piece, uint32_t fields,
+                                                          uint32_t rule, unsigned long long* __restrict__ words, const uint32_t* __restrict__ wave_cnt,
+                                                          madsim_sweep_record_t* __restrict__ recs, uint64_t cap) {
+    const uint32_t W = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (W == 0) {                                                                  // mask 0 is what the incomparable seeds and the other 255 cells leave
+        unsigned long long other = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++) if (lane + 64u * k) other += words[18 + lane + 64u * k];
+        for (int o = 32; o > 0; o >>= 1) other += __shfl_xor(other, o);
+        if (lane == 0) words[18] = count - words[1] - other;
+    }
+    if (cap == 0 || wave_cnt[W] == 0) return;                                      // (wave-uniform)
+    uint64_t at = 0;                                                               // selected seeds of the waves before this one
+    for (uint32_t j = lane; j < W; j += 64) at += wave_cnt[j];
+    for (int o = 32; o > 0; o >>= 1) at += __shfl_xor(at, o);
+    const uint64_t lo = (uint64_t)W * piece, hi = lo + piece < count ? lo + piece : count;
+    const DiffLoads L = diff_loads(fields);
+    const uint32_t full = (1u << V) - 1u;
+    for (uint64_t base = lo; base < hi && at < cap; base += 64) {
+        const uint64_t i = base + lane;
+        const SweepSeed s = sweep_classify(S, V, i, i < hi, fields, L);
+        const bool mine = sweep_selected(s, rule, full);
+        const unsigned long long m = __ballot(mine);
+        const uint64_t rank = at + lanes_below(m);
+        if (mine && rank < cap) {                                                  // a list entry only of a seed that is listed
+            unsigned long long* p = reinterpret_cast<unsigned long long*>(recs) + rank * 3u;      // 24 B records: 8-byte stores
+            p[0] = seed_of(i);
+            p[1] = (unsigned long long)s.fail | (unsigned long long)s.differ << 32;
+            p[2] = s.verdicts;
+        }
+        at += (uint64_t)__popcll(m);
+    }
+}
+
 __global__ void keyflip_kernel(unsigned long long* acc) { acc[0] ^= 0x8000000000000000ull; }
 
 // ---- resolving campaigns: which seeds of a batch are run again, and their new results back in place ----------------------------
@@ -921,6 +1066,42 @@ extern "C" int madsim_k_launch_diff_list(const madsim_result_t* a, const madsim_
                                          unsigned long long* words, uint32_t* wave_cnt, madsim_diff_record_t* recs, uint64_t cap, void* stream) {
     if (!d_seeds) return -1;
     return madsim_k::launch_diff(a, b, count, madsim_k::ListSeeds{d_seeds}, fields, words, wave_cnt, recs, cap, stream);
+}
+
+// sides: the n_variants result arrays of the same `count` seeds; words: MADSIM_K_SWEEP_WORDS zeroed words; wave_cnt: MADSIM_K_COLLECT_WAVES
+// words; recs: `cap` records (may be null when cap == 0); all prepared by the caller on `stream` (sim_kernel.h).  Returns 0, or -1 (nothing
+// launched) for arguments the kernels are not written for.
+namespace madsim_k {
+template <class Seeds>
+static int launch_sweep(const madsim_result_t* const* sides, uint32_t n_variants, uint64_t count, Seeds src, uint32_t fields, uint32_t rule,
+                        unsigned long long* words, uint32_t* wave_cnt, madsim_sweep_record_t* recs, uint64_t cap, void* stream) {
+    static_assert(sizeof(madsim_sweep_record_t) == 24 && sizeof(madsim_result_t) == 48 && MADSIM_SWEEP_MAX_VARIANTS == 8, "record layout");
+    static_assert(MADSIM_K_SWEEP_WORDS == 2 + 8 + 8 + 256, "sim_kernel.h");
+    if (!sides || n_variants < 2 || n_variants > MADSIM_SWEEP_MAX_VARIANTS || count == 0 || count >= (1ull << 32)) return -1;
+    if ((fields & ~MADSIM_DIFF_ALL) || rule > MADSIM_SWEEP_LIST_DIFFERING || (rule == MADSIM_SWEEP_LIST_DIFFERING && !fields) || (cap && !recs)) return -1;
+    SweepSides S{};
+    for (uint32_t v = 0; v < n_variants; v++) {
+        if (!sides[v]) return -1;
+        S.r[v] = sides[v];
+    }
+    uint32_t grid = (uint32_t)((count + 1023) / 1024);     // collect's cut
+    if (grid > 256) grid = 256;
+    const uint64_t waves = 4ull * grid, piece = ((count + waves - 1) / waves + 63) / 64 * 64;
+    hipLaunchKernelGGL(madsim_k::sweep_count_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, S, n_variants, count, piece, fields, rule, words, wave_cnt);
+    hipLaunchKernelGGL((sweep_write_kernel<Seeds>), dim3(grid), dim3(256), 0, (hipStream_t)stream, S, n_variants, count, src, piece, fields, rule, words,
+                       (const uint32_t*)wave_cnt, recs, cap);
+    return 0;
+}
+}  // namespace madsim_k
+extern "C" int madsim_k_launch_sweep(const madsim_result_t* const* sides, uint32_t n_variants, uint64_t count, uint64_t seed0, uint32_t fields,
+                                     uint32_t rule, unsigned long long* words, uint32_t* wave_cnt, madsim_sweep_record_t* recs, uint64_t cap, void* stream) {
+    return madsim_k::launch_sweep(sides, n_variants, count, madsim_k::RangeSeeds{seed0}, fields, rule, words, wave_cnt, recs, cap, stream);
+}
+extern "C" int madsim_k_launch_sweep_list(const madsim_result_t* const* sides, uint32_t n_variants, uint64_t count, const uint64_t* d_seeds, uint32_t fields,
+                                          uint32_t rule, unsigned long long* words, uint32_t* wave_cnt, madsim_sweep_record_t* recs, uint64_t cap,
+                                          void* stream) {
+    if (!d_seeds) return -1;
+    return madsim_k::launch_sweep(sides, n_variants, count, madsim_k::ListSeeds{d_seeds}, fields, rule, words, wave_cnt, recs, cap, stream);
 }
 
 // wave_cnt: MADSIM_K_RESOLVE_WAVES words of scratch; total: one word; seeds / idx: room for `count` entries each, the first *total written

@@ -151,6 +151,11 @@ def lib():
         L.madsim_hip_run_seeds_campaign_diff_multi.argtypes = [C.POINTER(ctxp), C.c_int] + L.madsim_hip_run_seeds_campaign_diff.argtypes
         L.madsim_hip_diverge_seeds.argtypes = side + side + [u64p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
         L.madsim_hip_ctx_diverge_seeds.argtypes = [ctxp] + L.madsim_hip_diverge_seeds.argtypes
+        # the sweep campaigns: one signature for the range (seeds NULL) and the list (seed0 0)
+        L.madsim_hip_run_sweep_campaign.argtypes = [C.POINTER(A.SweepVariant), C.c_uint32, C.c_uint64, C.c_uint64, u64p, C.c_uint64, C.c_uint32,
+                                                    C.c_uint32, C.POINTER(A.Sweep)]
+        L.madsim_hip_ctx_run_sweep_campaign.argtypes = [ctxp] + L.madsim_hip_run_sweep_campaign.argtypes
+        L.madsim_hip_run_sweep_campaign_multi.argtypes = [C.POINTER(ctxp), C.c_int] + L.madsim_hip_run_sweep_campaign.argtypes
         L.madsim_hip_observe_seed.restype = C.c_int64
         L.madsim_hip_observe_seed.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), C.c_uint64, C.POINTER(A.Limits), C.c_void_p, C.c_uint64,
                                               C.POINTER(A.Result)]
@@ -816,6 +821,126 @@ def run_campaign_diff_seeds(workload, seeds, other=None, config=None, other_conf
         workload, other, config, other_config, limits, other_limits, fields, max_listed, stop_at_diffs, resolve, observe)
 
 
+class CampaignSweep:
+    """What a sweep campaign (madsim_hip_run_sweep_campaign) says about the prefix that ran: `n_by_mask`, a uint64 array of length 2^V — the
+    settled seeds by the set of variants they fail in (bit v = variant v) —; `n_settled`, `n_incomparable` (a runner verdict in some variant),
+    `n_selected` (the seeds the list rule selects); `n_runner_by_variant` and `n_differ_from_first`, V counts each; and `records`, an
+    ndarray[SWEEP_RECORD_DTYPE] of the max_listed smallest selected seeds, ascending.  The helpers read n_by_mask alone."""
+
+    def __init__(self, s, records, n_variants):
+        self.n_variants, self.fields, self.list_rule, self.max_listed = n_variants, int(s.fields), int(s.list_rule), int(s.cap)
+        self.records = records[:s.n_listed].copy()
+        self.n_selected, self.n_settled, self.n_incomparable = int(s.n_selected), int(s.n_settled), int(s.n_incomparable)
+        self.n_runner_by_variant = np.array(s.n_runner_by_variant[:n_variants], dtype=np.uint64)
+        self.n_differ_from_first = np.array(s.n_differ_from_first[:n_variants], dtype=np.uint64)
+        self.n_by_mask = np.array(s.n_by_mask[:1 << n_variants], dtype=np.uint64)
+
+    def __len__(self):
+        return len(self.records)
+
+    def _sum(self, keep):
+        return int(sum(int(c) for m, c in enumerate(self.n_by_mask) if keep(m)))
+
+    def fails(self, v):
+        """Settled seeds that fail in variant v."""
+        return self._sum(lambda m: m >> v & 1)
+
+    def only(self, v):
+        """Settled seeds that fail in variant v and in no other."""
+        return int(self.n_by_mask[1 << v])
+
+    def fails_not(self, i, j):
+        """Settled seeds that fail in variant i and not in variant j."""
+        return self._sum(lambda m: m >> i & 1 and not m >> j & 1)
+
+    def nested(self):
+        """True when every non-empty mask that occurs is a suffix set {k, .., V - 1}: the failing sets grow with the variant index."""
+        full = (1 << self.n_variants) - 1
+        return all(c == 0 or m == 0 or m == full & ~((m & -m) - 1) for m, c in enumerate(self.n_by_mask))
+
+    def first_failing(self):
+        """Histogram of the lowest failing variant: [v] = settled seeds whose first failing variant is v — the bisect reading."""
+        h = np.zeros(self.n_variants, dtype=np.uint64)
+        for m, c in enumerate(self.n_by_mask):
+            if m:
+                h[(m & -m).bit_length() - 1] += c
+        return h
+
+
+def _sweep_variants(variants):
+    """`variants=` of the sweep wrappers — a sequence of (workload[, config[, limits]]) tuples or bare workloads, None meaning the default —
+    as (the A.SweepVariant array, the reports, everything that must stay alive during the call)."""
+    vs = []
+    for t in variants:
+        t = tuple(t) if isinstance(t, (tuple, list)) else (t,)
+        if not 1 <= len(t) <= 3 or t[0] is None:
+            raise MadsimHipError("run_campaign_sweep: a variant is (workload[, config[, limits]])")
+        w, cfg, lim = (t + (None, None))[:3]
+        vs.append((w, cfg or A.Config.default(), lim or A.Limits()))
+    if not 2 <= len(vs) <= A.SWEEP_MAX_VARIANTS:
+        raise MadsimHipError(f"run_campaign_sweep: 2..{A.SWEEP_MAX_VARIANTS} variants, got {len(vs)}")
+    arr, reps = (A.SweepVariant * len(vs))(), [A.Campaign() for _ in vs]
+    for i, (w, cfg, lim) in enumerate(vs):
+        arr[i].w, arr[i].cfg, arr[i].lim, arr[i].out = C.pointer(w.struct), C.pointer(cfg), C.pointer(lim), C.pointer(reps[i])
+    return arr, reps, vs
+
+
+def _campaign_sweep(call, variants, seeds, fields, list_rule, max_listed, stop_at_listed, resolve):
+    """Run `call(variants, n_variants, seeds pointer or None, total of a list or None, flags, sweep)` — one of the madsim_hip_*run_campaign_sweep
+    entry points with its contexts, batch and in_flight bound."""
+    rule = A.SWEEP_LIST_NAMES.index(list_rule) if list_rule in A.SWEEP_LIST_NAMES else list_rule
+    if not isinstance(fields, int) or fields < 0 or fields & ~A.DIFF_ALL or rule not in (0, 1, 2) or (rule == A.SWEEP_LIST_DIFFERING and not fields) \
+            or max_listed < 0 or (stop_at_listed and not max_listed):
+        raise MadsimHipError("run_campaign_sweep: fields is a mask of A.DIFF_* bits (non-empty for list_rule='differing'), list_rule one of "
+                             f"{A.SWEEP_LIST_NAMES}, max_listed >= 0, and stop_at_listed needs max_listed > 0")
+    arr, reps, keep = _sweep_variants(variants)
+    seeds_arr = seed_list(seeds) if seeds is not None else None      # (a list that does not ascend is refused before a device is looked for)
+    recs = np.zeros(max_listed, dtype=A.SWEEP_RECORD_DTYPE)
+    s = A.Sweep()
+    s.fields, s.list_rule, s.cap = fields, rule, max_listed
+    s.records = recs.ctypes.data_as(C.POINTER(A.SweepRecord)) if max_listed else None
+    flags = (A.CAMPAIGN_STOP_AT_SWEEP if stop_at_listed else 0) | _resolve_flags(resolve)
+    _check(call(arr, len(reps), seeds_arr, flags, C.byref(s)))
+    del keep
+    return reps, CampaignSweep(s, recs, len(reps))
+
+
+def _sweep_range(seed0, total, seeds_arr):
+    """(seed0, total, seeds pointer) of a sweep call: the range, or — seeds given — the list with seed0 = 0."""
+    if seeds_arr is None:
+        return seed0, total, None
+    if seed0 or total:
+        raise MadsimHipError("run_campaign_sweep: either seed0 / total or seeds=, not both")
+    # (an empty list still passes a non-NULL pointer: the list form, which needs no device)
+    return 0, len(seeds_arr), seeds_arr.ctypes.data_as(C.POINTER(C.c_uint64)) if seeds_arr.size else C.cast(C.pointer(C.c_uint64(0)), C.POINTER(C.c_uint64))
+
+
+def run_campaign_sweep(variants, seed0=0, total=0, seeds=None, fields=A.DIFF_VERDICT, list_rule="mixed", max_listed=0, stop_at_listed=False, batch=0,
+                       in_flight=0, resolve=None):
+    """madsim_hip_run_sweep_campaign: up to eight variants — `variants`, a sequence of (workload, config, limits) tuples, shorter tuples or
+    None meaning defaults — over the range [seed0, seed0 + total) or the strictly ascending list `seeds`, every seed classified across all
+    of them on the device.  Returns (reports, CampaignSweep): one plain campaign report per variant, and the counts by failing set with
+    the max_listed smallest seeds `list_rule` selects ("mixed": the variants disagree on pass / fail; "failing": some variant fails;
+    "differing": a field of `fields` differs from variant 0's).  stop_at_listed: stop launching once max_listed selected seeds have been
+    read; resolve: as everywhere, each variant under its own limits."""
+    def call(v, n, sa, flags, s):
+        s0, n_seeds, ptr = _sweep_range(seed0, total, sa)
+        if _inited_device is None and n_seeds:                  # (the mirror's argument errors come first; nothing to run needs no device)
+            init(0)
+        return lib().madsim_hip_run_sweep_campaign(v, n, s0, n_seeds, ptr, batch, in_flight, flags, s)
+    return _campaign_sweep(call, variants, seeds, fields, list_rule, max_listed, stop_at_listed, resolve)
+
+
+def run_campaign_sweep_multi(contexts, variants, seed0=0, total=0, seeds=None, fields=A.DIFF_VERDICT, list_rule="mixed", max_listed=0,
+                             stop_at_listed=False, batch=0, in_flight=0, resolve=None):
+    """madsim_hip_run_sweep_campaign_multi: run_campaign_sweep over several contexts (every variant of batch k on context k % n); the report is
+    the one a single context gives."""
+    arr = (C.c_void_p * len(contexts))(*[c._h for c in contexts])
+    return _campaign_sweep(lambda v, n, sa, flags, s: lib().madsim_hip_run_sweep_campaign_multi(
+        arr, len(contexts), v, n, *_sweep_range(seed0, total, sa), batch, in_flight, flags, s),
+        variants, seeds, fields, list_rule, max_listed, stop_at_listed, resolve)
+
+
 def run_batch_device(workload, seed0, count, d_out_ptr, stream_ptr=0, config=None, limits=None, want_summary=True):
     """Device-resident entry point: results stay in HBM at `d_out_ptr` (48 B/seed)."""
     if _inited_device is None:
@@ -961,6 +1086,13 @@ class Context:
         return _campaign_diff(lambda wa, ca, la, wb, cb, lb, flags, ra, rb, d: lib().madsim_hip_ctx_run_seeds_campaign_diff(
             self._h, wa, ca, la, wb, cb, lb, _seeds_ptr(arr), len(arr), batch, in_flight, flags, ra, rb, d),
             workload, other, config, other_config, limits, other_limits, fields, max_listed, stop_at_diffs, resolve, observe, self.trace_seeds)
+
+    def run_campaign_sweep(self, variants, seed0=0, total=0, seeds=None, fields=A.DIFF_VERDICT, list_rule="mixed", max_listed=0,
+                           stop_at_listed=False, batch=0, in_flight=0, resolve=None):
+        """runtime.run_campaign_sweep on this context (madsim_hip_ctx_run_sweep_campaign)."""
+        return _campaign_sweep(lambda v, n, sa, flags, s: lib().madsim_hip_ctx_run_sweep_campaign(
+            self._h, v, n, *_sweep_range(seed0, total, sa), batch, in_flight, flags, s),
+            variants, seeds, fields, list_rule, max_listed, stop_at_listed, resolve)
 
 
 def run_batch_multi(contexts, workload, seed0, count, config=None, limits=None, max_rounds=5):
