@@ -303,6 +303,35 @@ pub struct madsim_sweep_t {
 
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
+pub struct madsim_paired_extreme_t {
+    pub seed: u64,
+    pub a: u64,
+    pub b: u64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct madsim_paired_t {
+    pub include_a: u32,
+    pub include_b: u32,
+    pub top_k: u32,
+    pub reserved: u32,
+    pub top: *const madsim_paired_extreme_t,
+    pub n_paired: u64,
+    pub n_unpaired: u64,
+    pub n_incomparable: u64,
+    pub n_top: [u64; 8],
+    pub n: [u64; 8],
+    pub n_equal: [u64; 4],
+    pub sum_a_lo: [u64; 4],
+    pub sum_a_hi: [u64; 4],
+    pub sum_b_lo: [u64; 4],
+    pub sum_b_hi: [u64; 4],
+    pub delta: [madsim_metric_t; 8],
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
 pub struct madsim_geometry_t {
     pub lds_bytes_per_seed: u32,
     pub lds_bytes_per_block: u32,
@@ -484,6 +513,8 @@ pub const MADSIM_SWEEP_LIST_MIXED: u32 = 0;
 pub const MADSIM_SWEEP_LIST_FAILING: u32 = 1;
 pub const MADSIM_SWEEP_LIST_DIFFERING: u32 = 2;
 pub const MADSIM_CAMPAIGN_STOP_AT_SWEEP: u32 = 64;
+pub const MADSIM_PAIRED_UP: u32 = 0;
+pub const MADSIM_PAIRED_DOWN: u32 = 1;
 
 #[link(name = "madsim_hip")]
 extern "C" {
@@ -546,6 +577,12 @@ extern "C" {
     pub fn madsim_hip_ctx_run_sweep_campaign(ctx: *mut madsim_hip_ctx_t, variants: *const madsim_sweep_variant_t, n_variants: u32, seed0: u64, total: u64, seeds: *const u64, batch: u64, in_flight: u32, flags: u32, sweep: *mut madsim_sweep_t) -> c_int;
     pub fn madsim_hip_run_sweep_campaign(variants: *const madsim_sweep_variant_t, n_variants: u32, seed0: u64, total: u64, seeds: *const u64, batch: u64, in_flight: u32, flags: u32, sweep: *mut madsim_sweep_t) -> c_int;
     pub fn madsim_hip_run_sweep_campaign_multi(ctxs: *const *mut madsim_hip_ctx_t, n_ctx: c_int, variants: *const madsim_sweep_variant_t, n_variants: u32, seed0: u64, total: u64, seeds: *const u64, batch: u64, in_flight: u32, flags: u32, sweep: *mut madsim_sweep_t) -> c_int;
+    pub fn madsim_hip_ctx_run_paired_campaign(ctx: *mut madsim_hip_ctx_t, wA: *const madsim_workload_t, cfgA: *const madsim_config_t, limA: *const madsim_limits_t, wB: *const madsim_workload_t, cfgB: *const madsim_config_t, limB: *const madsim_limits_t, seed0: u64, total: u64, batch: u64, in_flight: u32, flags: u32, outA: *mut madsim_campaign_t, outB: *mut madsim_campaign_t, diff: *mut madsim_diff_t, pr: *mut madsim_paired_t) -> c_int;
+    pub fn madsim_hip_run_paired_campaign(wA: *const madsim_workload_t, cfgA: *const madsim_config_t, limA: *const madsim_limits_t, wB: *const madsim_workload_t, cfgB: *const madsim_config_t, limB: *const madsim_limits_t, seed0: u64, total: u64, batch: u64, in_flight: u32, flags: u32, outA: *mut madsim_campaign_t, outB: *mut madsim_campaign_t, diff: *mut madsim_diff_t, pr: *mut madsim_paired_t) -> c_int;
+    pub fn madsim_hip_run_paired_campaign_multi(ctxs: *const *mut madsim_hip_ctx_t, n_ctx: c_int, wA: *const madsim_workload_t, cfgA: *const madsim_config_t, limA: *const madsim_limits_t, wB: *const madsim_workload_t, cfgB: *const madsim_config_t, limB: *const madsim_limits_t, seed0: u64, total: u64, batch: u64, in_flight: u32, flags: u32, outA: *mut madsim_campaign_t, outB: *mut madsim_campaign_t, diff: *mut madsim_diff_t, pr: *mut madsim_paired_t) -> c_int;
+    pub fn madsim_hip_ctx_run_seeds_campaign_paired(ctx: *mut madsim_hip_ctx_t, wA: *const madsim_workload_t, cfgA: *const madsim_config_t, limA: *const madsim_limits_t, wB: *const madsim_workload_t, cfgB: *const madsim_config_t, limB: *const madsim_limits_t, seeds: *const u64, n: u64, batch: u64, in_flight: u32, flags: u32, outA: *mut madsim_campaign_t, outB: *mut madsim_campaign_t, diff: *mut madsim_diff_t, pr: *mut madsim_paired_t) -> c_int;
+    pub fn madsim_hip_run_seeds_campaign_paired(wA: *const madsim_workload_t, cfgA: *const madsim_config_t, limA: *const madsim_limits_t, wB: *const madsim_workload_t, cfgB: *const madsim_config_t, limB: *const madsim_limits_t, seeds: *const u64, n: u64, batch: u64, in_flight: u32, flags: u32, outA: *mut madsim_campaign_t, outB: *mut madsim_campaign_t, diff: *mut madsim_diff_t, pr: *mut madsim_paired_t) -> c_int;
+    pub fn madsim_hip_run_seeds_campaign_paired_multi(ctxs: *const *mut madsim_hip_ctx_t, n_ctx: c_int, wA: *const madsim_workload_t, cfgA: *const madsim_config_t, limA: *const madsim_limits_t, wB: *const madsim_workload_t, cfgB: *const madsim_config_t, limB: *const madsim_limits_t, seeds: *const u64, n: u64, batch: u64, in_flight: u32, flags: u32, outA: *mut madsim_campaign_t, outB: *mut madsim_campaign_t, diff: *mut madsim_diff_t, pr: *mut madsim_paired_t) -> c_int;
     pub fn madsim_hip_geometry(w: *const madsim_workload_t, lim: *const madsim_limits_t, g: *mut madsim_geometry_t) -> c_int;
     pub fn madsim_hip_debug_counters(out16: *mut u64) -> c_int;
     pub fn madsim_workload_pingpong(n_nodes: u32, rounds: u32, nodes: *mut madsim_node_t, progs: *mut madsim_prog_t, socks: *mut madsim_sock_t, insns: *mut madsim_insn_t, cap_insns: u32, w: *mut madsim_workload_t) -> c_int;

@@ -187,6 +187,34 @@ pub struct Diff {
     pub b: sys::madsim_campaign_t,
 }
 
+/// What `Builder::paired_campaign` found over the paired seeds (both verdicts named by their side's include mask): the report — at index
+/// `2 * metric + direction` (`MADSIM_STAT_*`, `MADSIM_PAIRED_UP` / `_DOWN`) the seeds that moved that way with the minimum, maximum,
+/// 128-bit sum and bucket counts of the magnitudes —, `top[2 * metric + direction]`: the extreme seeds with both sides' values, magnitude
+/// descending, then seed ascending, and each side's plain campaign report.
+#[derive(Clone, Debug)]
+pub struct Paired {
+    pub report: sys::madsim_paired_t,
+    pub top: [Vec<sys::madsim_paired_extreme_t>; 8],
+    pub a: sys::madsim_campaign_t,
+    pub b: sys::madsim_campaign_t,
+}
+
+impl Paired {
+    /// Sum over the paired seeds of `b - a` for `metric`: the UP magnitudes minus the DOWN magnitudes.
+    pub fn net_sum(&self, metric: usize) -> i128 {
+        let sum = |j: usize| ((self.report.delta[j].sum_hi as u128) << 64 | self.report.delta[j].sum_lo as u128) as i128;
+        sum(2 * metric + sys::MADSIM_PAIRED_UP as usize) - sum(2 * metric + sys::MADSIM_PAIRED_DOWN as usize)
+    }
+    /// The seeds whose `metric` grew most from side A to side B.
+    pub fn regressions(&self, metric: usize) -> &[sys::madsim_paired_extreme_t] {
+        &self.top[2 * metric + sys::MADSIM_PAIRED_UP as usize]
+    }
+    /// The seeds whose `metric` shrank most.
+    pub fn improvements(&self, metric: usize) -> &[sys::madsim_paired_extreme_t] {
+        &self.top[2 * metric + sys::MADSIM_PAIRED_DOWN as usize]
+    }
+}
+
 /// What `Builder::sweep_campaign` found: per variant its plain campaign report; the report — `n_by_mask[m]` = settled seeds that fail in
 /// exactly the variants whose bits `m` has, the per-variant counts — and the smallest seeds the list rule selects (ascending), each
 /// with its masks and every variant's verdict.
@@ -710,6 +738,54 @@ impl Builder {
         records.truncate(report.n_listed as usize);
         report.records = std::ptr::null();
         Ok(Diff { records, report, a, b })
+    }
+
+    /// What a change did to each seed's numbers: `self` running `workload` (side A) against `other` running `other_workload` (side B) over
+    /// `self.seed .. self.seed + self.count` (`madsim_hip_run_paired_campaign`).  A seed is paired when its verdict on side A is named in
+    /// `include` and on side B in `other_include` (bits 0-3); per metric and direction the device reduces count, min, max, the exact sum,
+    /// a histogram and the `top_k` (<= 16) extreme seeds of the unsigned magnitude `|b - a|`.  Config and limits are each side's own; the
+    /// seeds and the resolve rounds are `self`'s.
+    pub fn paired_campaign(&self, workload: &Workload, other: &Builder, other_workload: &Workload, include: u32, other_include: u32, top_k: u32)
+                           -> Result<Paired, RunError> {
+        self.paired_impl(workload, other, other_workload, None, include, other_include, top_k)
+    }
+
+    /// `paired_campaign` over the seeds you name (`madsim_hip_run_seeds_campaign_paired`).  `seeds` as `campaign_over_seeds`': strictly
+    /// ascending.
+    pub fn paired_campaign_seeds(&self, workload: &Workload, other: &Builder, other_workload: &Workload, seeds: &[u64], include: u32,
+                                 other_include: u32, top_k: u32) -> Result<Paired, RunError> {
+        self.paired_impl(workload, other, other_workload, Some(seeds), include, other_include, top_k)
+    }
+
+    fn paired_impl(&self, workload: &Workload, other: &Builder, other_workload: &Workload, seeds: Option<&[u64]>, include: u32, other_include: u32,
+                   top_k: u32) -> Result<Paired, RunError> {
+        let (wa, wb) = (workload.raw(), other_workload.raw());
+        let (ca, cb) = (self.config.raw(), other.config.raw());
+        let (la, lb) = (self.raw_limits(true), other.raw_limits(true));
+        let ctx = contexts()?.0[0];
+        let k = top_k as usize;
+        let mut top: Vec<sys::madsim_paired_extreme_t> = vec![unsafe { std::mem::zeroed() }; 8 * k];
+        let mut a: sys::madsim_campaign_t = unsafe { std::mem::zeroed() };
+        let mut b: sys::madsim_campaign_t = unsafe { std::mem::zeroed() };
+        let mut report: sys::madsim_paired_t = unsafe { std::mem::zeroed() };
+        report.include_a = include;
+        report.include_b = other_include;
+        report.top_k = top_k;
+        report.top = if k > 0 { top.as_mut_ptr() as *const _ } else { std::ptr::null() };   // (the library writes through it)
+        let rc = unsafe {
+            match seeds {
+                None => sys::madsim_hip_ctx_run_paired_campaign(ctx, &wa, &ca, &la, &wb, &cb, &lb, self.seed, self.count, 0, 0, self.resolve_flags, &mut a,
+                                                                &mut b, std::ptr::null_mut(), &mut report),
+                Some(s) => sys::madsim_hip_ctx_run_seeds_campaign_paired(ctx, &wa, &ca, &la, &wb, &cb, &lb, s.as_ptr(), s.len() as u64, 0, 0,
+                                                                         self.resolve_flags, &mut a, &mut b, std::ptr::null_mut(), &mut report),
+            }
+        };
+        if rc != 0 {
+            return Err(last_error(rc));
+        }
+        report.top = std::ptr::null();
+        let rows: [Vec<sys::madsim_paired_extreme_t>; 8] = std::array::from_fn(|j| top[j * k..j * k + report.n_top[j] as usize].to_vec());
+        Ok(Paired { report, top: rows, a, b })
     }
 
     /// Across several variants: up to eight `(builder, workload)` pairs over `self.seed .. self.seed + self.count` — or, with

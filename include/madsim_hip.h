@@ -1140,6 +1140,89 @@ int madsim_hip_run_sweep_campaign_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx
                                         uint32_t n_variants, uint64_t seed0, uint64_t total, const uint64_t* seeds, uint64_t batch,
                                         uint32_t in_flight, uint32_t flags, madsim_sweep_t* sweep);
 
+/* ---- Paired campaigns: WHAT A CHANGE DID TO EACH SEED'S NUMBERS ---------------------------------------------------------------
+ * A differential campaign says which seeds a change affected; two statistics campaigns give two marginal distributions.  Neither
+ * says what a same-seed simulator gives for free: the per-seed DELTA — did the new election timeout make convergence slower in
+ * virtual time, by how much, for how many seeds, and which seeds regressed most.  A paired campaign runs side A (wA, cfgA, limA) and
+ * side B (wB, cfgB, limB) over the same seeds exactly as a differential campaign does (one stream per flight, a summary6 kernel
+ * behind each side), then two paired kernels read both result arrays; nothing is copied back but the report words.
+ * Classification, per seed: INCOMPARABLE when either side's verdict is a runner verdict (MADSIM_IS_RUNNER_VERDICT: the differential
+ * campaign's rule); PAIRED when both verdicts are below 4, bit `verdict A` is set in include_a and bit `verdict B` in include_b (only
+ * bits 0-3 exist, as in madsim_stats_t.include); UNPAIRED otherwise.  n_paired + n_unpaired + n_incomparable = seeds_run.
+ * Magnitude rule, per paired seed and metric m (MADSIM_STAT_*: clock_ns, steps, msg_count, rng_calls), a and b the two sides' values
+ * compared as unsigned 64-bit numbers: b > a is direction MADSIM_PAIRED_UP with magnitude b - a; a > b is MADSIM_PAIRED_DOWN with
+ * magnitude a - b; a == b counts in n_equal[m].  A magnitude is at least 1 and always fits 64 bits: no signed 65-bit quantity
+ * appears anywhere.  n[2 m] + n[2 m + 1] + n_equal[m] = n_paired.
+ * Index j = 2 * metric + direction: n[j] seeds; delta[j] holds the minimum and maximum magnitude (UINT64_MAX and 0 when there is
+ * none, as madsim_metric_t says), the exact 128-bit sum of the magnitudes and hist[madsim_hip_stat_bucket(magnitude)] (bucket 0
+ * stays empty).  sum_a / sum_b[m] are the 128-bit sums of the two sides' values over the PAIRED seeds, so both means over the same
+ * population come from one call.
+ * Order: top[j * top_k + r], r < n_top[j] = min(top_k, n[j]), are the seeds of (metric, direction) j that come first when ordered by
+ * magnitude descending, then seed ascending; each entry carries both sides' values of that metric.  No atomic and no arrival order
+ * decides a position.
+ * Invariants: all integer, all exact; every output is a function of the per-seed results of the prefix that was run — the same bytes
+ * whatever `batch`, `in_flight` and the number of contexts, on every run; batches launched beyond a stopping one contribute nothing.
+ * A batch holds fewer than 2^32 seeds.  The per-batch words (about 8.5 KB, 11.5 KB with top_k > 0) ride back in one copy and are
+ * folded on the host in batch order.
+ * `diff` may be NULL.  When given it is filled exactly as madsim_hip_run_campaign_diff fills it (the diff kernels run between side
+ * B's summary and the paired kernels), and MADSIM_CAMPAIGN_STOP_AT_DIFFS applies; without it the flag is ignored.  outA / outB are
+ * the plain campaign's reports of the two sides.  With MADSIM_CAMPAIGN_RESOLVE each side's runner verdicts are first re-run under
+ * that side's own grown limits, the paired kernels run again over the resolved results, and n_incomparable is what no round settled.
+ * The run_seeds_campaign_paired forms take a strictly ascending list in place of (seed0, total), under every rule of the list section
+ * above.  (The range entry points are spelled run_paired_campaign, as the sweep forms are run_sweep_campaign.)
+ * MADSIM_E_ARG: pr == NULL; include_a or include_b 0 or with a bit at or above 4; reserved != 0; top_k > MADSIM_STAT_MAX_TOP;
+ * top_k > 0 without `top`; NULL outA or outB; and, when `diff` is given, the differential form's own argument errors. */
+#define MADSIM_PAIRED_UP   0u     /* b > a: the metric grew from side A to side B   */
+#define MADSIM_PAIRED_DOWN 1u     /* a > b: it shrank                               */
+typedef struct madsim_paired_extreme {
+    uint64_t seed, a, b;          /* both sides' values of the row's metric         */
+} madsim_paired_extreme_t;        /* 24 bytes */
+/* (two statements, as madsim_stats above: it holds madsim_metric_t by value) */
+struct madsim_paired {
+    uint32_t include_a, include_b;     /* in: bit v set = side A's / side B's verdict v qualifies (bits 0-3 only)                 */
+    uint32_t top_k, reserved;          /* in: 0 .. MADSIM_STAT_MAX_TOP; reserved = 0                                              */
+    madsim_paired_extreme_t* top;      /* in: caller's host array [MADSIM_STAT_METRICS][2][top_k]; may be NULL when top_k == 0    */
+    uint64_t n_paired, n_unpaired, n_incomparable;      /* out: sum = seeds_run                                                  */
+    uint64_t n_top[8];                 /* out: [2 * metric + direction] = min(top_k, n[..]): entries valid in that row of `top`   */
+    uint64_t n[8];                     /* out: [2 * metric + direction] = paired seeds that moved in that direction               */
+    uint64_t n_equal[4];               /* out: [metric] = paired seeds with a == b                                                */
+    uint64_t sum_a_lo[4];              /* out: [metric] = the 128-bit sum of side A's values over the paired seeds, low word ...  */
+    uint64_t sum_a_hi[4];              /*      ... and high word                                                                  */
+    uint64_t sum_b_lo[4];              /* out: the same of side B's                                                               */
+    uint64_t sum_b_hi[4];
+    madsim_metric_t delta[8];          /* out: [2 * metric + direction] = min, max, 128-bit sum and histogram of the magnitudes   */
+};                                     /* 16976 bytes */
+typedef struct madsim_paired madsim_paired_t;
+int madsim_hip_ctx_run_paired_campaign(madsim_hip_ctx_t* ctx, const madsim_workload_t* wA, const madsim_config_t* cfgA,
+                                       const madsim_limits_t* limA, const madsim_workload_t* wB, const madsim_config_t* cfgB,
+                                       const madsim_limits_t* limB, uint64_t seed0, uint64_t total, uint64_t batch,
+                                       uint32_t in_flight, uint32_t flags, madsim_campaign_t* outA, madsim_campaign_t* outB,
+                                       madsim_diff_t* diff, madsim_paired_t* pr);
+int madsim_hip_run_paired_campaign(const madsim_workload_t* wA, const madsim_config_t* cfgA, const madsim_limits_t* limA,
+                                   const madsim_workload_t* wB, const madsim_config_t* cfgB, const madsim_limits_t* limB,
+                                   uint64_t seed0, uint64_t total, uint64_t batch, uint32_t in_flight, uint32_t flags,
+                                   madsim_campaign_t* outA, madsim_campaign_t* outB, madsim_diff_t* diff, madsim_paired_t* pr);
+int madsim_hip_run_paired_campaign_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_workload_t* wA,
+                                         const madsim_config_t* cfgA, const madsim_limits_t* limA, const madsim_workload_t* wB,
+                                         const madsim_config_t* cfgB, const madsim_limits_t* limB, uint64_t seed0, uint64_t total,
+                                         uint64_t batch, uint32_t in_flight, uint32_t flags, madsim_campaign_t* outA,
+                                         madsim_campaign_t* outB, madsim_diff_t* diff, madsim_paired_t* pr);
+int madsim_hip_ctx_run_seeds_campaign_paired(madsim_hip_ctx_t* ctx, const madsim_workload_t* wA, const madsim_config_t* cfgA,
+                                             const madsim_limits_t* limA, const madsim_workload_t* wB, const madsim_config_t* cfgB,
+                                             const madsim_limits_t* limB, const uint64_t* seeds, uint64_t n, uint64_t batch,
+                                             uint32_t in_flight, uint32_t flags, madsim_campaign_t* outA, madsim_campaign_t* outB,
+                                             madsim_diff_t* diff, madsim_paired_t* pr);
+int madsim_hip_run_seeds_campaign_paired(const madsim_workload_t* wA, const madsim_config_t* cfgA, const madsim_limits_t* limA,
+                                         const madsim_workload_t* wB, const madsim_config_t* cfgB, const madsim_limits_t* limB,
+                                         const uint64_t* seeds, uint64_t n, uint64_t batch, uint32_t in_flight, uint32_t flags,
+                                         madsim_campaign_t* outA, madsim_campaign_t* outB, madsim_diff_t* diff, madsim_paired_t* pr);
+int madsim_hip_run_seeds_campaign_paired_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_workload_t* wA,
+                                               const madsim_config_t* cfgA, const madsim_limits_t* limA,
+                                               const madsim_workload_t* wB, const madsim_config_t* cfgB,
+                                               const madsim_limits_t* limB, const uint64_t* seeds, uint64_t n, uint64_t batch,
+                                               uint32_t in_flight, uint32_t flags, madsim_campaign_t* outA,
+                                               madsim_campaign_t* outB, madsim_diff_t* diff, madsim_paired_t* pr);
+
 /* Geometry the library picked for a workload (for DESIGN/bench reporting). */
 typedef struct madsim_geometry {
     uint32_t lds_bytes_per_seed;

@@ -780,6 +780,52 @@ struct Builder {
         return diff_against(other, wl, wl, fields, max_listed);           // one test body under two configurations
     }
 
+    // What a change did to each seed's numbers: this builder's run of `wl` (side A) against `other`'s run of `other_wl` (side B) over THIS
+    // builder's seed .. seed + count — or THIS builder's over_seeds() list — (madsim_hip_run_paired_campaign).  A seed is paired when its
+    // verdict on side A is named in `include` and on side B in `other_include` (bits 0-3, 1u << MADSIM_PASS ..); for every paired seed and
+    // each of clock_ns, steps, msg_count and rng_calls the device takes b - a as a direction and an unsigned magnitude and reduces, per
+    // metric and direction, count, min, max, the exact sum, a histogram and the `top_k` (<= MADSIM_STAT_MAX_TOP) extreme seeds.  Config,
+    // capacities and time limit are each side's own; seeds, device and resolve_runner() rounds are this builder's.
+    struct Paired {
+        madsim_paired_t report{};                                         // (top: of the call; read `top` below)
+        std::vector<madsim_paired_extreme_t> top[2 * MADSIM_STAT_METRICS]; // [2 * metric + direction]: magnitude descending, then seed ascending
+        madsim_campaign_t a{}, b{};                                       // each side's plain campaign report
+        static unsigned __int128 wide(uint64_t lo, uint64_t hi) { return (unsigned __int128)hi << 64 | lo; }
+        const std::vector<madsim_paired_extreme_t>& regressions(uint32_t metric) const { return top[2 * metric + MADSIM_PAIRED_UP]; }
+        const std::vector<madsim_paired_extreme_t>& improvements(uint32_t metric) const { return top[2 * metric + MADSIM_PAIRED_DOWN]; }
+        // the mean of b - a over the paired seeds (the sums are exact; the quotient is a double), 0 when nothing is paired
+        double mean_delta(uint32_t metric) const {
+            if (!report.n_paired) return 0.0;
+            const madsim_metric_t &up = report.delta[2 * metric + MADSIM_PAIRED_UP], &down = report.delta[2 * metric + MADSIM_PAIRED_DOWN];
+            const unsigned __int128 u = wide(up.sum_lo, up.sum_hi), d = wide(down.sum_lo, down.sum_hi);
+            return (u >= d ? (double)(u - d) : -(double)(d - u)) / (double)report.n_paired;
+        }
+    };
+    Paired paired_against(const Builder& other, const Workload& wl, const Workload& other_wl, uint32_t include = 1u << MADSIM_PASS,
+                          uint32_t other_include = 0, uint32_t top_k = 0) const {      // other_include 0: the same as `include`
+        madsim::check(madsim_hip_init(device));
+        madsim_workload_t wa = wl.raw(), wb = other_wl.raw();
+        madsim_config_t ca = config.raw(), cb = other.config.raw();
+        madsim_limits_t la = capacities, lb = other.capacities;
+        if (time_limit) { la.time_limit_ns = (uint64_t)(*time_limit * 1e9 + 0.5); if (!la.time_limit_ns) la.time_limit_ns = 1; }
+        if (other.time_limit) { lb.time_limit_ns = (uint64_t)(*other.time_limit * 1e9 + 0.5); if (!lb.time_limit_ns) lb.time_limit_ns = 1; }
+        Paired p;
+        std::vector<madsim_paired_extreme_t> rows((size_t)2 * MADSIM_STAT_METRICS * top_k);
+        p.report.include_a = include;
+        p.report.include_b = other_include ? other_include : include;
+        p.report.top_k = top_k;
+        p.report.top = top_k ? rows.data() : nullptr;
+        madsim::check(listed_seeds ? madsim_hip_run_seeds_campaign_paired(&wa, &ca, &la, &wb, &cb, &lb, seed_list.data(), seed_list.size(), 0, 0, resolve_flags, &p.a,
+                                                                          &p.b, nullptr, &p.report)
+                                   : madsim_hip_run_paired_campaign(&wa, &ca, &la, &wb, &cb, &lb, seed, count, 0, 0, resolve_flags, &p.a, &p.b, nullptr, &p.report));
+        p.report.top = nullptr;                                           // (the rows are in `top`)
+        for (size_t j = 0; j < 2 * MADSIM_STAT_METRICS; j++) p.top[j].assign(rows.begin() + j * top_k, rows.begin() + j * top_k + (size_t)p.report.n_top[j]);
+        return p;
+    }
+    Paired paired_against(const Builder& other, const Workload& wl, uint32_t include = 1u << MADSIM_PASS, uint32_t other_include = 0, uint32_t top_k = 0) const {
+        return paired_against(other, wl, wl, include, other_include, top_k);      // one test body under two configurations
+    }
+
     // Across several variants: up to eight (builder, workload) pairs over THIS builder's seed .. seed + count — or THIS builder's
     // over_seeds() list — in one campaign (madsim_hip_run_sweep_campaign): a parameter sweep, a stack of versions of a test body, one body
     // under every state layout.  Config, capacities and time limit are each variant's own; seed range, device and resolve_runner() rounds

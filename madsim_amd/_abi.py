@@ -329,6 +329,30 @@ DIVERGENCE_DTYPE = [("seed", "<u8"), ("log_status", "<u4"), ("obs_status", "<u4"
 EXTREME_DTYPE = [("value", "<u8"), ("seed", "<u8")]
 assert C.sizeof(Extreme) == 16 and C.sizeof(Metric) == 2080 and C.sizeof(Stats) == 32 + 4 * 2080
 
+PAIRED_UP, PAIRED_DOWN = 0, 1      # the direction of a paired campaign's delta: side B's value above / below side A's
+PAIRED_DIRECTION_NAMES = ("up", "down")
+
+
+class PairedExtreme(C.Structure):
+    """madsim_paired_extreme_t: one of the extreme seeds of a (metric, direction) — the seed and both sides' values of that metric."""
+    _fields_ = [("seed", C.c_uint64), ("a", C.c_uint64), ("b", C.c_uint64)]
+
+
+class Paired(C.Structure):
+    """madsim_paired_t: which verdicts pair on each side and the caller's top array going in; the classification counts and, at index
+    2 * metric + direction, the seeds that moved that way with the minimum, maximum, 128-bit sum and bucket counts of the magnitudes coming
+    out.  (Declared in two statements in the header, as madsim_stats_t: tests/test_campaign_paired.py holds it against the header.)"""
+    _fields_ = [("include_a", C.c_uint32), ("include_b", C.c_uint32), ("top_k", C.c_uint32), ("reserved", C.c_uint32), ("top", C.POINTER(PairedExtreme)),
+                ("n_paired", C.c_uint64), ("n_unpaired", C.c_uint64), ("n_incomparable", C.c_uint64), ("n_top", C.c_uint64 * 8), ("n", C.c_uint64 * 8),
+                ("n_equal", C.c_uint64 * 4), ("sum_a_lo", C.c_uint64 * 4), ("sum_a_hi", C.c_uint64 * 4), ("sum_b_lo", C.c_uint64 * 4),
+                ("sum_b_hi", C.c_uint64 * 4), ("delta", Metric * 8)]
+
+
+# numpy view of a paired campaign's extreme seeds: madsim_paired_extreme_t
+PAIRED_EXTREME_DTYPE = [("seed", "<u8"), ("a", "<u8"), ("b", "<u8")]
+assert C.sizeof(PairedExtreme) == 24 and C.sizeof(Paired) == 336 + 8 * 2080
+HEADER_STRUCTS["madsim_paired_extreme_t"] = PairedExtreme
+
 PASS, PANIC, DEADLOCK, TIME_LIMIT, OVERFLOW, STEP_LIMIT, UNSUPPORTED, INTERNAL = range(8)
 VERDICT_NAMES = ["pass", "panic", "deadlock", "time-limit", "resource-overflow", "step-limit", "outside-the-workload-model", "internal-invariant"]
 

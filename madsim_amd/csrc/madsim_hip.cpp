@@ -97,7 +97,8 @@ struct madsim_hip_resources {
     static constexpr size_t STATS_REP_WORDS = 16 + MADSIM_K_STATS_WORDS;      // a statistics campaign's report: the plain / collecting report's words in front
     static constexpr size_t GROUP_REP_WORDS = STATS_REP_WORDS + MADSIM_K_GROUP_WORDS;
     static constexpr size_t DIFF_REP_WORDS = 16 + MADSIM_K_DIFF_WORDS;      // summary6's six words of side A at 0, of side B at 8, the diff words at 16
-    static constexpr size_t SWEEP_REP_WORDS = 8 * MADSIM_SWEEP_MAX_VARIANTS + MADSIM_K_SWEEP_WORDS;      // summary6's six words of variant v at 8 v, the sweep words at 64
+    static constexpr size_t PAIRED_REP_WORDS = DIFF_REP_WORDS + MADSIM_K_PAIRED_WORDS;      // a paired campaign's report: the differential report's words in front
+    static constexpr size_t SWEEP_REP_WORDS =8 * MADSIM_SWEEP_MAX_VARIANTS + MADSIM_K_SWEEP_WORDS;      // summary6's six words of variant v at 8 v, the sweep words at 64
     // One batch in flight: what every form uses, then one group per campaign form, made when a call of that form first comes (ensure)
     // and kept with the flight.  Every resource is ensured on its own — none stands for another —, so a call that ran out of memory
     // half-way leaves nothing that a later call would take for complete.
@@ -175,6 +176,28 @@ struct madsim_hip_resources {
                 return 0;
             }
         } diff;
+        // paired campaigns (which also use the differential group: side B's results and event pair, and its counts and records when a
+        // diff report is asked for): the report words of the whole batch — PAIRED_REP_WORDS live ones (device, page-locked host): the
+        // differential campaign's DIFF_REP_WORDS in front, then the paired words with the top records at their end — and behind the
+        // device's a copy of their state before a batch; the candidate words of the top-K
+        struct Paired {
+            DevBuf<report_word_t> d_rep; PinnedBuf<report_word_t> h_rep; DevBuf<unsigned long long> cand;
+            int ensure() {
+                if (!d_rep) {
+                    std::vector<report_word_t> init(PAIRED_REP_WORDS, 0);           // the words before a batch: summary6's two minima all-ones, the rest zero
+                    init[0] = init[4] = init[8] = init[12] = ~0ull;
+                    HIP_TRY(d_rep.room(2 * PAIRED_REP_WORDS));
+                    const hipError_t e = hipMemcpy(d_rep + PAIRED_REP_WORDS, init.data(), PAIRED_REP_WORDS * sizeof(report_word_t), hipMemcpyHostToDevice);
+                    if (e != hipSuccess) {                                          // (words without their initial state are no words)
+                        d_rep.reset();
+                        return fail(MADSIM_E_HIP, std::string("hipMemcpy(initial report words): ") + hipGetErrorString(e));
+                    }
+                }
+                HIP_TRY(h_rep.room(PAIRED_REP_WORDS));
+                HIP_TRY(cand.room(MADSIM_K_PAIRED_CAND_WORDS));
+                return 0;
+            }
+        } paired;
         // sweep campaigns: the results of variants 1 .. 7 (variant 0 uses d_out), made only up to the number of variants a call needs, an
         // event pair per variant, the report words — SWEEP_REP_WORDS live ones (device, page-locked host) and behind the device's a copy of
         // their state before a batch —, per-wave counts and the batch's records
@@ -1219,6 +1242,51 @@ extern "C" uint64_t madsim_k_fold_diff(madsim_diff_t* diff, const unsigned long 
     return take;
 }
 
+// ---- paired campaigns: the host fold of a batch's words ----------------------------------------------------------------------------
+// w = a batch's MADSIM_K_PAIRED_WORDS over `count` seeds (sim_kernel.hip).  Batches are folded in seed order, but nothing here relies on it:
+// the counts, minima, maxima and sums commute, and the extreme seeds are merged under the total order (magnitude descending, seed
+// ascending) — a row of the batch holds min(top_k, the batch's n[j]) entries, in that order.
+extern "C" void madsim_k_fold_paired(madsim_paired_t* pr, const unsigned long long* w, uint64_t count) {
+    pr->n_paired += w[0];
+    pr->n_incomparable += w[1];
+    pr->n_unpaired += count - w[0] - w[1];
+    const uint32_t* hist = reinterpret_cast<const uint32_t*>(w + MADSIM_K_PAIRED_HEAD_WORDS);
+    const madsim_paired_extreme_t* top = reinterpret_cast<const madsim_paired_extreme_t*>(w + MADSIM_K_PAIRED_HEAD_WORDS + 8 * MADSIM_STAT_BUCKETS / 2);
+    auto add128 = [](uint64_t& lo, uint64_t& hi, unsigned long long low_halves, unsigned long long high_halves) {
+        const unsigned __int128 sum = ((unsigned __int128)hi << 64 | lo) + low_halves + ((unsigned __int128)high_halves << 32);
+        lo = (uint64_t)sum; hi = (uint64_t)(sum >> 64);
+    };
+    for (uint32_t m = 0; m < MADSIM_STAT_METRICS; m++) {
+        pr->n_equal[m] += w[0] - w[2 + 2 * m] - w[3 + 2 * m];
+        add128(pr->sum_a_lo[m], pr->sum_a_hi[m], w[42 + m], w[46 + m]);
+        add128(pr->sum_b_lo[m], pr->sum_b_hi[m], w[50 + m], w[54 + m]);
+    }
+    const uint64_t K = pr->top_k;
+    for (uint32_t j = 0; j < 8; j++) {
+        const uint64_t n = w[2 + j];
+        if (!n) continue;
+        madsim_metric_t& M = pr->delta[j];
+        pr->n[j] += n;
+        M.min = std::min<uint64_t>(M.min, ~w[10 + j]);
+        M.max = std::max<uint64_t>(M.max, w[18 + j]);
+        add128(M.sum_lo, M.sum_hi, w[26 + j], w[34 + j]);
+        for (uint32_t b = 0; b < MADSIM_STAT_BUCKETS; b++) M.hist[b] += hist[j * MADSIM_STAT_BUCKETS + b];
+        if (!K) continue;
+        const bool up = (j & 1u) == MADSIM_PAIRED_UP;
+        auto mag = [up](const madsim_paired_extreme_t& e) { return up ? e.b - e.a : e.a - e.b; };
+        madsim_paired_extreme_t* row = pr->top + j * K;
+        const madsim_paired_extreme_t* add = top + j * MADSIM_STAT_MAX_TOP;
+        const uint64_t have = pr->n_top[j], got = std::min(K, n), keep = std::min(K, have + got);
+        madsim_paired_extreme_t merged[MADSIM_STAT_MAX_TOP];
+        for (uint64_t i = 0, a = 0, b = 0; i < keep; i++) {
+            const bool from_row = b >= got || (a < have && (mag(row[a]) > mag(add[b]) || (mag(row[a]) == mag(add[b]) && row[a].seed < add[b].seed)));
+            merged[i] = from_row ? row[a++] : add[b++];
+        }
+        memcpy(row, merged, keep * sizeof *row);
+        pr->n_top[j] = keep;
+    }
+}
+
 // ---- sweep campaigns: the host fold of a batch's words -----------------------------------------------------------------------------
 // w = a batch's MADSIM_K_SWEEP_WORDS (sim_kernel.hip): {n_selected, n_incomparable, n_runner_by_variant[8], n_differ_from_first[8],
 // n_by_mask[256]}.  The counts commute; the list is appended in batch order, which is seed order, and never beyond `cap`.
@@ -1562,14 +1630,24 @@ int run_campaign_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workl
 struct DiffSide { const madsim_workload_t* w; const madsim_config_t* cfg; const madsim_limits_t* lim; madsim_campaign_t* out; };
 
 int run_campaign_diff_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const DiffSide (&side)[2], uint64_t seed0, uint64_t total, uint64_t batch,
-                           uint32_t in_flight, uint32_t flags, madsim_diff_t* d, const uint64_t* list = nullptr) {
+                           uint32_t in_flight, uint32_t flags, madsim_diff_t* d, const uint64_t* list = nullptr, madsim_paired_t* pr = nullptr) {
     // `list`: as in run_campaign_impl — position i of list[0 .. total) for seed0 + i, seed0 = 0; both sides of a batch read the same slice.
+    // `pr` (the paired campaigns): the paired kernels behind the diff kernels, and `d` may then be NULL (no diff kernels).  The batch's words
+    // — the two summaries, the diff words, the paired words — then live in the flight's paired group and come back in one copy; without
+    // `pr` everything below queues what the differential campaign always queued.
     auto t0 = std::chrono::steady_clock::now();
     for (const DiffSide& s : side) { memset(s.out, 0, sizeof *s.out); s.out->first_failing_seed = UINT64_MAX; }
-    d->n_listed = d->n_compared = d->n_incomparable = d->n_differ = 0;
-    memset(d->n_by_field, 0, sizeof d->n_by_field);
-    memset(d->transitions, 0, sizeof d->transitions);
+    if (d) {
+        d->n_listed = d->n_compared = d->n_incomparable = d->n_differ = 0;
+        memset(d->n_by_field, 0, sizeof d->n_by_field);
+        memset(d->transitions, 0, sizeof d->transitions);
+    }
+    if (pr) {                                                    // (everything behind the caller's inputs)
+        memset(&pr->n_paired, 0, sizeof *pr - offsetof(madsim_paired_t, n_paired));
+        for (madsim_metric_t& M : pr->delta) M.min = UINT64_MAX;
+    }
     flags &= MADSIM_CAMPAIGN_STOP_AT_DIFFS | MADSIM_CAMPAIGN_RESOLVE | MADSIM_CAMPAIGN_RESOLVE_ROUNDS_MASK;      // (the other stop flags belong to the other forms)
+    if (!d) flags &= ~MADSIM_CAMPAIGN_STOP_AT_DIFFS;
     const uint32_t R = resolve_rounds(flags);
     ResolveAccount account(ctxs, n_ctx, R);
     madsim_resolve_t& acct = account.a;
@@ -1582,36 +1660,50 @@ int run_campaign_diff_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const DiffSid
     if (width >= (1ull << 32)) return fail(MADSIM_E_ARG, "a differential campaign's batch holds fewer than 2^32 seeds");
     if (R && width >= (1ull << 30)) return fail(MADSIM_E_ARG, "a resolving campaign's batch holds fewer than 2^30 seeds");
     const uint64_t n_batches = (total + batch - 1) / batch, N = (uint64_t)n_ctx;
-    const uint64_t rec_batch = std::min(d->cap, width);      // records a flight holds: no batch lists more
+    const uint64_t rec_batch = d ? std::min(d->cap, width) : 0;      // records a flight holds: no batch lists more
     CampaignFlights flights(ctxs, n_ctx);
     if ((rc = flights.setup(n_batches, batch, width, in_flight, list != nullptr,
                             [&](madsim_hip_ctx* c) {
                                 return std::min(c->flights_for(side[0].w, side[0].cfg, side[0].lim, batch), c->flights_for(side[1].w, side[1].cfg, side[1].lim, batch));
                             },
-                            [&](madsim_hip_ctx::Flight& f) { return f.diff.ensure(batch, rec_batch, f.stream); })))
+                            [&](madsim_hip_ctx::Flight& f) {
+                                if (int e = f.diff.ensure(batch, rec_batch, f.stream)) return e;
+                                return pr ? f.paired.ensure() : 0;
+                            })))
         return rc;
-    constexpr size_t n_words = madsim_hip_ctx::DIFF_REP_WORDS;
+    // the words of a batch: the differential group's, or — in a paired campaign — the paired group's, whose copy ends before the top
+    // records when there are none
+    const size_t n_words = pr ? madsim_hip_ctx::PAIRED_REP_WORDS : madsim_hip_ctx::DIFF_REP_WORDS;
+    const size_t n_copied = pr && !pr->top_k ? n_words - 8 * MADSIM_STAT_MAX_TOP * 3 : n_words;
+    constexpr size_t at_paired = madsim_hip_ctx::DIFF_REP_WORDS;
+    auto d_rep = [&](madsim_hip_ctx::Flight& f) -> report_word_t* { return pr ? f.paired.d_rep : f.diff.d_rep; };
+    auto h_rep = [&](madsim_hip_ctx::Flight& f) -> report_word_t* { return pr ? f.paired.h_rep : f.diff.h_rep; };
     int first_err = 0;
     std::string first_msg;
     bool stop = false;
     // A batch's report chain in the parts that `queue` puts around the two simulation launches and a resolving `harvest` queues again back
     // to back: the words reset by one device copy, a side's summary6 over its results, then the diff kernels, the copy and the `done` event.
     auto prepare_report = [&](madsim_hip_ctx::Flight& f) -> int {
-        HIP_TRY(hipMemcpyAsync(f.diff.d_rep, f.diff.d_rep + n_words, n_words * sizeof(unsigned long long), hipMemcpyDeviceToDevice, f.stream));
+        HIP_TRY(hipMemcpyAsync(d_rep(f), d_rep(f) + n_words, n_copied * sizeof(unsigned long long), hipMemcpyDeviceToDevice, f.stream));
         return 0;
     };
     auto queue_summary = [&](madsim_hip_ctx::Flight& f, int s, uint64_t lo, uint64_t n) -> int {
-        if (list) madsim_k_launch_summary6_list(s ? f.diff.out_b : f.d_out, n, f.list.d, f.diff.d_rep + 8 * s, f.stream);
-        else madsim_k_launch_summary6(s ? f.diff.out_b : f.d_out, n, seed0 + lo, f.diff.d_rep + 8 * s, f.stream);
+        if (list) madsim_k_launch_summary6_list(s ? f.diff.out_b : f.d_out, n, f.list.d, d_rep(f) + 8 * s, f.stream);
+        else madsim_k_launch_summary6(s ? f.diff.out_b : f.d_out, n, seed0 + lo, d_rep(f) + 8 * s, f.stream);
         HIP_TRY(hipGetLastError());
         return 0;
     };
     auto queue_diff = [&](madsim_hip_ctx::Flight& f, uint64_t lo, uint64_t n) -> int {
-        if (list ? madsim_k_launch_diff_list(f.d_out, f.diff.out_b, n, f.list.d, d->fields, f.diff.d_rep + 16, f.diff.wcnt, f.diff.rec, std::min(rec_batch, n), f.stream)
-                 : madsim_k_launch_diff(f.d_out, f.diff.out_b, n, seed0 + lo, d->fields, f.diff.d_rep + 16, f.diff.wcnt, f.diff.rec, std::min(rec_batch, n), f.stream))
+        if (d && (list ? madsim_k_launch_diff_list(f.d_out, f.diff.out_b, n, f.list.d, d->fields, d_rep(f) + 16, f.diff.wcnt, f.diff.rec, std::min(rec_batch, n), f.stream)
+                       : madsim_k_launch_diff(f.d_out, f.diff.out_b, n, seed0 + lo, d->fields, d_rep(f) + 16, f.diff.wcnt, f.diff.rec, std::min(rec_batch, n), f.stream)))
             return fail(MADSIM_E_ARG, "madsim_k_launch_diff refused the batch's arguments");
+        if (pr && (list ? madsim_k_launch_paired_list(f.d_out, f.diff.out_b, n, f.list.d, pr->include_a, pr->include_b, pr->top_k, d_rep(f) + at_paired,
+                                                      f.paired.cand, f.stream)
+                        : madsim_k_launch_paired(f.d_out, f.diff.out_b, n, seed0 + lo, pr->include_a, pr->include_b, pr->top_k, d_rep(f) + at_paired,
+                                                 f.paired.cand, f.stream)))
+            return fail(MADSIM_E_ARG, "madsim_k_launch_paired refused the batch's arguments");
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(f.diff.h_rep, f.diff.d_rep, n_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, f.stream));
+        HIP_TRY(hipMemcpyAsync(h_rep(f), d_rep(f), n_copied * sizeof(unsigned long long), hipMemcpyDeviceToHost, f.stream));
         HIP_TRY(hipEventRecord(f.done, f.stream));
         return 0;
     };
@@ -1645,8 +1737,9 @@ int run_campaign_diff_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const DiffSid
         float ms[2] = {0.f, 0.f};
         HIP_TRY(hipEventElapsedTime(&ms[0], f.e0, f.e1));
         HIP_TRY(hipEventElapsedTime(&ms[1], f.diff.b0, f.diff.b1));
-        if (R && (f.diff.h_rep[5] > 0 || f.diff.h_rep[8 + 5] > 0)) {    // runner verdicts on a side: settle them under that side's own limits, diff again
-            const unsigned long long runner_before[2] = {f.diff.h_rep[5], f.diff.h_rep[8 + 5]};
+        const report_word_t* const h = h_rep(f);
+        if (R && (h[5] > 0 || h[8 + 5] > 0)) {    // runner verdicts on a side: settle them under that side's own limits, diff again
+            const unsigned long long runner_before[2] = {h[5], h[8 + 5]};
             bool ran = false;
             for (int s = 0; s < 2; s++) {                       // (one after the other on the flight's stream: they share its re-run scratch)
                 if (!runner_before[s]) continue;
@@ -1659,13 +1752,18 @@ int run_campaign_diff_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const DiffSid
             if (ran) {
                 if ((e = prepare_report(f)) || (e = queue_summary(f, 0, lo, n)) || (e = queue_summary(f, 1, lo, n)) || (e = queue_diff(f, lo, n))) return e;
                 HIP_TRY(hipEventSynchronize(f.done));
-                acct.n_resolved += (runner_before[0] - f.diff.h_rep[5]) + (runner_before[1] - f.diff.h_rep[8 + 5]);
+                acct.n_resolved += (runner_before[0] - h[5]) + (runner_before[1] - h[8 + 5]);
             }
         }
-        for (int s = 0; s < 2; s++) fold_summary(side[s].out, f.diff.h_rep + 8 * s, n, ms[s]);
-        if (f.diff.h_rep[16] > n) return fail(MADSIM_E_HIP, "differential campaign: a batch reports more differing seeds than it holds");
+        for (int s = 0; s < 2; s++) fold_summary(side[s].out, h + 8 * s, n, ms[s]);
+        if (pr) {
+            if (h[at_paired] + h[at_paired + 1] > n) return fail(MADSIM_E_HIP, "paired campaign: a batch reports more paired and incomparable seeds than it holds");
+            madsim_k_fold_paired(pr, h + at_paired, n);
+        }
+        if (!d) return 0;
+        if (h[16] > n) return fail(MADSIM_E_HIP, "differential campaign: a batch reports more differing seeds than it holds");
         // the batch's records, as many as the list still takes (the stream is idle: its `done` has passed, and it takes no launch before this returns)
-        const uint64_t at = d->n_listed, take = madsim_k_fold_diff(d, f.diff.h_rep + 16, n, nullptr);
+        const uint64_t at = d->n_listed, take = madsim_k_fold_diff(d, h + 16, n, nullptr);
         if (take) {
             HIP_TRY(hipMemcpyAsync(d->records + at, f.diff.rec, take * sizeof(madsim_diff_record_t), hipMemcpyDeviceToHost, f.stream));
             HIP_TRY(hipStreamSynchronize(f.stream));
@@ -2024,6 +2122,73 @@ int madsim_hip_run_seeds_campaign_diff_multi(madsim_hip_ctx_t* const* ctxs, int 
     return run_campaign_diff_impl(ctxs, n_ctx, side, 0, n, batch, in_flight, flags, diff, n ? seeds : nullptr);
 }
 
+// ---- paired campaigns: per-seed metric deltas between two variants ------------------------------------------------------------------
+// The differential entry points with a trailing madsim_paired_t and an optional diff report.  Argument errors first, as the other forms.
+namespace {
+int check_paired_args(const madsim_campaign_t* outA, const madsim_campaign_t* outB, const madsim_diff_t* d, const madsim_paired_t* pr, uint32_t in_flight,
+                      uint32_t flags) {
+    if (!pr) return fail(MADSIM_E_ARG, "null madsim_paired_t");
+    if (pr->include_a == 0 || (pr->include_a & ~0xfu) || pr->include_b == 0 || (pr->include_b & ~0xfu))
+        return fail(MADSIM_E_ARG, "madsim_paired_t.include_a / include_b: at least one of bits 0-3 (PASS, PANIC, DEADLOCK, TIME_LIMIT), none above");
+    if (pr->reserved) return fail(MADSIM_E_ARG, "madsim_paired_t.reserved must be 0");
+    if (pr->top_k > MADSIM_STAT_MAX_TOP) return fail(MADSIM_E_ARG, "madsim_paired_t.top_k: at most MADSIM_STAT_MAX_TOP (16)");
+    if (pr->top_k && !pr->top) return fail(MADSIM_E_ARG, "madsim_paired_t.top_k > 0 without a top array");
+    if (d) return check_diff_args(outA, outB, d, in_flight, flags);
+    if (!outA || !outB) return fail(MADSIM_E_ARG, "null campaign report (a paired campaign fills one per side)");
+    if (int rc = check_resolve_flags(flags)) return rc;
+    if (in_flight > (uint32_t)madsim_hip_ctx::CAMPAIGN_MAX) return fail(MADSIM_E_ARG, "at most 8 batches in flight per context");
+    return 0;
+}
+}  // namespace
+
+int madsim_hip_ctx_run_paired_campaign(madsim_hip_ctx_t* c, const madsim_workload_t* wA, const madsim_config_t* cfgA, const madsim_limits_t* limA,
+                                       const madsim_workload_t* wB, const madsim_config_t* cfgB, const madsim_limits_t* limB, uint64_t seed0,
+                                       uint64_t total, uint64_t batch, uint32_t in_flight, uint32_t flags, madsim_campaign_t* outA,
+                                       madsim_campaign_t* outB, madsim_diff_t* diff, madsim_paired_t* pr) {
+    if (int rc = check_paired_args(outA, outB, diff, pr, in_flight, flags)) return rc;
+    CTX_ENTER(c);
+    madsim_hip_ctx* one[1] = {c};
+    const DiffSide side[2] = {{wA, cfgA, limA, outA}, {wB, cfgB, limB, outB}};
+    return run_campaign_diff_impl(one, 1, side, seed0, total, batch, in_flight, flags, diff, nullptr, pr);
+}
+
+int madsim_hip_run_paired_campaign_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_workload_t* wA, const madsim_config_t* cfgA,
+                                         const madsim_limits_t* limA, const madsim_workload_t* wB, const madsim_config_t* cfgB,
+                                         const madsim_limits_t* limB, uint64_t seed0, uint64_t total, uint64_t batch, uint32_t in_flight,
+                                         uint32_t flags, madsim_campaign_t* outA, madsim_campaign_t* outB, madsim_diff_t* diff, madsim_paired_t* pr) {
+    if (int rc = check_paired_args(outA, outB, diff, pr, in_flight, flags)) return rc;
+    std::vector<std::unique_lock<std::mutex>> locks;
+    if (int rc = lock_contexts(ctxs, n_ctx, "run_paired_campaign_multi", locks)) return rc;
+    const DiffSide side[2] = {{wA, cfgA, limA, outA}, {wB, cfgB, limB, outB}};
+    return run_campaign_diff_impl(ctxs, n_ctx, side, seed0, total, batch, in_flight, flags, diff, nullptr, pr);
+}
+
+int madsim_hip_ctx_run_seeds_campaign_paired(madsim_hip_ctx_t* c, const madsim_workload_t* wA, const madsim_config_t* cfgA, const madsim_limits_t* limA,
+                                             const madsim_workload_t* wB, const madsim_config_t* cfgB, const madsim_limits_t* limB,
+                                             const uint64_t* seeds, uint64_t n, uint64_t batch, uint32_t in_flight, uint32_t flags,
+                                             madsim_campaign_t* outA, madsim_campaign_t* outB, madsim_diff_t* diff, madsim_paired_t* pr) {
+    if (int rc = check_seed_list(seeds, n)) return rc;
+    if (int rc = check_paired_args(outA, outB, diff, pr, in_flight, flags)) return rc;
+    const DiffSide side[2] = {{wA, cfgA, limA, outA}, {wB, cfgB, limB, outB}};
+    if (n == 0 && (!c || c->device < 0)) return run_campaign_diff_impl(nullptr, 0, side, 0, 0, batch, in_flight, flags, diff, nullptr, pr);      // (no device needed)
+    CTX_ENTER(c);
+    madsim_hip_ctx* one[1] = {c};
+    return run_campaign_diff_impl(one, 1, side, 0, n, batch, in_flight, flags, diff, n ? seeds : nullptr, pr);
+}
+
+int madsim_hip_run_seeds_campaign_paired_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_workload_t* wA, const madsim_config_t* cfgA,
+                                               const madsim_limits_t* limA, const madsim_workload_t* wB, const madsim_config_t* cfgB,
+                                               const madsim_limits_t* limB, const uint64_t* seeds, uint64_t n, uint64_t batch, uint32_t in_flight,
+                                               uint32_t flags, madsim_campaign_t* outA, madsim_campaign_t* outB, madsim_diff_t* diff,
+                                               madsim_paired_t* pr) {
+    if (int rc = check_seed_list(seeds, n)) return rc;
+    if (int rc = check_paired_args(outA, outB, diff, pr, in_flight, flags)) return rc;
+    std::vector<std::unique_lock<std::mutex>> locks;
+    if (int rc = lock_contexts(ctxs, n_ctx, "run_seeds_campaign_paired_multi", locks)) return rc;
+    const DiffSide side[2] = {{wA, cfgA, limA, outA}, {wB, cfgB, limB, outB}};
+    return run_campaign_diff_impl(ctxs, n_ctx, side, 0, n, batch, in_flight, flags, diff, n ? seeds : nullptr, pr);
+}
+
 // ---- sweep campaigns: up to eight variants over one seed set ------------------------------------------------------------------------
 // Argument errors first, as the other forms — here the variants' validate() errors too, all told before any context is looked at.  `var`
 // receives the variants with a NULL config replaced by the default one (loss 0, latency 1 .. 10 ms, no tables).
@@ -2219,6 +2384,22 @@ int madsim_hip_run_seeds_campaign_diff(const madsim_workload_t* wA, const madsim
                                        uint32_t in_flight, uint32_t flags, madsim_campaign_t* outA, madsim_campaign_t* outB, madsim_diff_t* diff) {
     DefaultPin p;
     return madsim_hip_ctx_run_seeds_campaign_diff(p.c, wA, cfgA, limA, wB, cfgB, limB, seeds, n, batch, in_flight, flags, outA, outB, diff);
+}
+
+int madsim_hip_run_paired_campaign(const madsim_workload_t* wA, const madsim_config_t* cfgA, const madsim_limits_t* limA, const madsim_workload_t* wB,
+                                   const madsim_config_t* cfgB, const madsim_limits_t* limB, uint64_t seed0, uint64_t total, uint64_t batch,
+                                   uint32_t in_flight, uint32_t flags, madsim_campaign_t* outA, madsim_campaign_t* outB, madsim_diff_t* diff,
+                                   madsim_paired_t* pr) {
+    DefaultPin p;
+    return madsim_hip_ctx_run_paired_campaign(p.c, wA, cfgA, limA, wB, cfgB, limB, seed0, total, batch, in_flight, flags, outA, outB, diff, pr);
+}
+
+int madsim_hip_run_seeds_campaign_paired(const madsim_workload_t* wA, const madsim_config_t* cfgA, const madsim_limits_t* limA, const madsim_workload_t* wB,
+                                         const madsim_config_t* cfgB, const madsim_limits_t* limB, const uint64_t* seeds, uint64_t n, uint64_t batch,
+                                         uint32_t in_flight, uint32_t flags, madsim_campaign_t* outA, madsim_campaign_t* outB, madsim_diff_t* diff,
+                                         madsim_paired_t* pr) {
+    DefaultPin p;
+    return madsim_hip_ctx_run_seeds_campaign_paired(p.c, wA, cfgA, limA, wB, cfgB, limB, seeds, n, batch, in_flight, flags, outA, outB, diff, pr);
 }
 
 int madsim_hip_run_sweep_campaign(const madsim_sweep_variant_t* variants, uint32_t n_variants, uint64_t seed0, uint64_t total, const uint64_t* seeds,

@@ -388,6 +388,24 @@ int  madsim_k_launch_sweep_list(const madsim_result_t* const* sides, uint32_t n_
 // Returns how many of the batch's records the list still takes — min(the batch's n_selected, cap - n_listed) — and advances n_listed by it;
 // when `batch_recs` (host memory, at least that many) is given they are appended to sweep->records, otherwise the caller copies them there.
 uint64_t madsim_k_fold_sweep(madsim_sweep_t* sweep, const unsigned long long* words, uint64_t count, const madsim_sweep_record_t* batch_recs);
+// the paired campaign's report kernels, behind the two sides' simulation and summary6 launches (and the diff kernels) on the same stream: `a`
+// and `b` are the two sides' results of the same `count` seeds.  `words`: MADSIM_K_PAIRED_WORDS words, ALL ZERO before the launch (the minima
+// are kept inverted, so one memset or device copy prepares them): {n_paired, n_incomparable, n[8], ~min[8], max[8], low half-sums of the
+// magnitudes[8], high[8], low half-sums of a[4], high[4], low half-sums of b[4], high[4]} (MADSIM_K_PAIRED_HEAD_WORDS), then hist[8][256] as
+// 32-bit counters (1 024 words), then top[8][16] {seed, a, b} (384 words); index 8 = 2 * metric + direction.  `cand`:
+// MADSIM_K_PAIRED_CAND_WORDS words of scratch, per-workgroup candidate lists; untouched, and may be null, when top_k == 0 — and then nothing
+// behind the histograms is written.  Returns 0, or -1 without launching anything for count == 0 or count >= 2^32, an include mask that is 0
+// or has a bit at or above 4, top_k > MADSIM_STAT_MAX_TOP, or a missing array.
+#define MADSIM_K_PAIRED_HEAD_WORDS 58u    /* 2 + 8 + 4 x 8 + 4 x 4: the words in front of the histograms */
+#define MADSIM_K_PAIRED_WORDS 1466u       /* 58 + 8 * 256 / 2 + 8 * 16 * 3 */
+#define MADSIM_K_PAIRED_CAND_WORDS 65536u /* 8 sets x 256 workgroups x 16 x {magnitude, index} */
+int  madsim_k_launch_paired(const madsim_result_t* a, const madsim_result_t* b, uint64_t count, uint64_t seed0, uint32_t include_a, uint32_t include_b,
+                            uint32_t top_k, unsigned long long* words, unsigned long long* cand, void* stream);
+int  madsim_k_launch_paired_list(const madsim_result_t* a, const madsim_result_t* b, uint64_t count, const uint64_t* d_seeds, uint32_t include_a,
+                                 uint32_t include_b, uint32_t top_k, unsigned long long* words, unsigned long long* cand, void* stream);
+// the host fold of one batch's MADSIM_K_PAIRED_WORDS over `count` seeds into the caller's report (madsim_hip.cpp; no device involved): the
+// counts, minima, maxima and sums commute, and the extreme seeds are merged under the total order (magnitude descending, seed ascending).
+void madsim_k_fold_paired(madsim_paired_t* pr, const unsigned long long* words, uint64_t count);
 // resolving campaigns (MADSIM_CAMPAIGN_RESOLVE).  The list pair, over collect's cut of the batch: a result is re-runnable when its verdict is
 // MADSIM_OVERFLOW, or MADSIM_STEP_LIMIT with `steps_maxed` == 0.  *total = m, the re-runnable seeds of out[0 .. count); seeds[0 .. m) =
 // seed0 + i and idx[0 .. m) = i of those results, ascending, the same on every run; nothing behind m is written.  `wave_cnt`:

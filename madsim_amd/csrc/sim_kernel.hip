@@ -731,6 +731,175 @@ __global__ __launch_bounds__(256) void sweep_write_kernel(const SweepSides S, ui
     }
 }
 
+// ---- the paired campaign form: per-seed metric deltas between two result arrays of the same seeds ----
+// Two kernels behind the two sides' simulation and summary6 launches (and the diff kernels, when asked for), over collect's cut of the batch
+// (wave W owns a contiguous piece).  A seed is INCOMPARABLE when either verdict is a runner verdict (diff's rule), PAIRED when both verdicts
+// are below 4 with bit `verdict A` set in include_a and bit `verdict B` in include_b, and unpaired otherwise (the host: count - the two).
+// paired_fold_kernel reads the 16-byte head of both sides of every seed and the second 16 bytes of a paired one (the 32 bytes
+// stats_fold_kernel decodes).  Per paired seed and metric m the two values compare as unsigned 64-bit numbers: b > a is UP with magnitude
+// b - a, a > b is DOWN with magnitude a - b — never 0 and always 64 bits —, a == b is neither (the host: n_paired - n_up - n_down).  SET
+// j = 2 m + direction holds what madsim_metric_t holds of the magnitudes: count (popcounts of ballots: wave-uniform), minimum (kept inverted:
+// zero is neutral), maximum and the two half-sums, folded in registers, per wave, then per workgroup through LDS — one set of atomics per
+// workgroup that paired a seed —, and a histogram of 256 LDS counters per set (8 KB), flushed with one atomic per non-zero bucket.  The
+// half-sums of a and of b over the paired seeds ride along.  A round of 64 seeds none of which is paired ends at two ballots.
+// The K extreme seeds of a set are the K first under "magnitude descending, seed ascending": stats_fold_kernel's scheme with the key
+// {magnitude, ~index in the batch}, as ONE instantiation of eight lists (topk_merge<8>: the kernel takes 250 of the 512 VGPRs a wave of a
+// 256-thread workgroup may have and has no private segment, so a second pass over the batch with two M = 4 instantiations would buy
+// nothing; the counts are in profiles/paired_ab.md).  Wave w of a workgroup merges the
+// four waves' lists of sets w and w + 4 into cand[set][workgroup][0..16); paired_top_kernel (one workgroup per set) merges the workgroups'
+// lists and, for each winner, loads that metric of both sides at the winner's index and writes {seed, a, b}.
+// words = {n_paired, n_incomparable, n[8], ~min[8], max[8], low half-sums of the magnitudes[8], high[8], low half-sums of a[4], high[4], of
+// b[4], high[4]} (58 words), then hist[8][256] as 32-bit counters, then top[8][16] {seed, a, b}; all zero before the launch.
+constexpr uint32_t PAIRED_SETS = 2 * MADSIM_STAT_METRICS, PAIRED_HEAD = 58;
+
+// metric m (MADSIM_STAT_*) of a result: steps is the 32-bit word 1, clock_ns / msg_count / rng_calls the 64-bit words 1 / 2 / 3
+__device__ __forceinline__ unsigned long long paired_metric(const madsim_result_t* __restrict__ r, uint32_t m) {
+    if (m == MADSIM_STAT_STEPS) return reinterpret_cast<const uint32_t*>(r)[1];
+    return reinterpret_cast<const unsigned long long*>(r)[m == MADSIM_STAT_CLOCK ? 1 : m];
+}
+
+__global__ __launch_bounds__(256) void paired_fold_kernel(const madsim_result_t* __restrict__ ra, const madsim_result_t* __restrict__ rb, uint64_t count,
+                                                          uint64_t piece, uint32_t include_a, uint32_t include_b, uint32_t K,
+                                                          unsigned long long* __restrict__ words, uint32_t* __restrict__ ghist,
+                                                          unsigned long long* __restrict__ cand) {
+    __shared__ uint32_t hist[PAIRED_SETS][MADSIM_STAT_BUCKETS];
+    __shared__ unsigned long long part[4][PAIRED_HEAD];
+    __shared__ unsigned long long lv[PAIRED_SETS][4 * STAT_TOP];
+    __shared__ uint32_t lk[PAIRED_SETS][4 * STAT_TOP];
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63, W = blockIdx.x * 4 + wave;
+    for (uint32_t i = threadIdx.x; i < PAIRED_SETS * MADSIM_STAT_BUCKETS; i += 256) (&hist[0][0])[i] = 0;
+    __syncthreads();
+    const uint64_t lo = (uint64_t)W * piece, hi = lo + piece < count ? lo + piece : count;
+    uint32_t n_pair = 0, n_inc = 0, n_dir[PAIRED_SETS] = {0, 0, 0, 0, 0, 0, 0, 0};       // wave-uniform (popcounts of ballots)
+    unsigned long long acc[PAIRED_HEAD - 10];                                      // ~min[8], max[8], low[8], high[8], a low / high[4], b low / high[4]
+#pragma unroll
+    for (int j = 0; j < (int)PAIRED_HEAD - 10; j++) acc[j] = 0;
+    TopKey list[PAIRED_SETS];
+#pragma unroll
+    for (int j = 0; j < (int)PAIRED_SETS; j++) list[j] = TopKey{0, 0};
+    for (uint64_t base = lo; base < hi; base += 64) {
+        const uint64_t i = base + lane;
+        uint4 a0 = {MADSIM_PASS, 0, 0, 0}, b0 = a0;
+        bool paired = false, inc = false;
+        if (i < hi) {
+            a0 = reinterpret_cast<const uint4*>(ra + i)[0]; b0 = reinterpret_cast<const uint4*>(rb + i)[0];
+            inc = MADSIM_IS_RUNNER_VERDICT(a0.x) || MADSIM_IS_RUNNER_VERDICT(b0.x);
+            paired = a0.x < 4u && b0.x < 4u && ((include_a >> a0.x) & 1u) && ((include_b >> b0.x) & 1u);
+        }
+        n_inc += (uint32_t)__popcll(__ballot(inc));
+        const unsigned long long pm = __ballot(paired);
+        if (!pm) continue;                                                         // (wave-uniform) nothing paired in this round
+        n_pair += (uint32_t)__popcll(pm);
+        TopKey nw[PAIRED_SETS];
+#pragma unroll
+        for (int j = 0; j < (int)PAIRED_SETS; j++) nw[j] = TopKey{0, 0};
+        if (paired) {
+            const uint4 a1 = reinterpret_cast<const uint4*>(ra + i)[1], b1 = reinterpret_cast<const uint4*>(rb + i)[1];
+            const unsigned long long va[4] = {((unsigned long long)a0.w << 32) | a0.z, a0.y, ((unsigned long long)a1.y << 32) | a1.x,
+                                              ((unsigned long long)a1.w << 32) | a1.z};
+            const unsigned long long vb[4] = {((unsigned long long)b0.w << 32) | b0.z, b0.y, ((unsigned long long)b1.y << 32) | b1.x,
+                                              ((unsigned long long)b1.w << 32) | b1.z};
+#pragma unroll
+            for (int m = 0; m < 4; m++) {
+                acc[32 + m] += va[m] & 0xffffffffull; acc[36 + m] += va[m] >> 32;
+                acc[40 + m] += vb[m] & 0xffffffffull; acc[44 + m] += vb[m] >> 32;
+                const bool up = vb[m] > va[m];
+                const unsigned long long mag = up ? vb[m] - va[m] : va[m] - vb[m];
+                const uint32_t bucket = stat_bucket(mag);
+#pragma unroll
+                for (int d = 0; d < 2; d++) {                                      // (constant indices only: everything stays in registers)
+                    const int j = 2 * m + d;
+                    const bool on = mag != 0 && up == (d == (int)MADSIM_PAIRED_UP);
+                    const unsigned long long g = on ? mag : 0ull, inv = on ? ~mag : 0ull;
+                    acc[j] = inv > acc[j] ? inv : acc[j];
+                    acc[8 + j] = g > acc[8 + j] ? g : acc[8 + j];
+                    acc[16 + j] += g & 0xffffffffull; acc[24 + j] += g >> 32;
+                    if (on) { atomicAdd(&hist[j][bucket], 1u); nw[j] = TopKey{mag, ~(uint32_t)i}; }      // (a batch holds fewer than 2^32 seeds: i < 2^32 - 1, never 0)
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < (int)PAIRED_SETS; j++) n_dir[j] += (uint32_t)__popcll(__ballot(nw[j].k != 0));
+        if (K && topk_enters<(int)PAIRED_SETS>(list, nw, K)) topk_merge<(int)PAIRED_SETS>(list, nw, K, lane);
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+        for (int j = 0; j < (int)PAIRED_HEAD - 10; j++) {
+            const unsigned long long t = __shfl_xor(acc[j], o);
+            if (j < 16) acc[j] = t > acc[j] ? t : acc[j]; else acc[j] += t;
+        }
+    }
+    if (lane == 0) {
+        part[wave][0] = n_pair; part[wave][1] = n_inc;
+#pragma unroll
+        for (int j = 0; j < (int)PAIRED_SETS; j++) part[wave][2 + j] = n_dir[j];
+#pragma unroll
+        for (int j = 0; j < (int)PAIRED_HEAD - 10; j++) part[wave][10 + j] = acc[j];
+    }
+    if (K && lane < STAT_TOP) {
+#pragma unroll
+        for (int j = 0; j < (int)PAIRED_SETS; j++) { lv[j][wave * STAT_TOP + lane] = list[j].v; lk[j][wave * STAT_TOP + lane] = list[j].k; }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < (int)PAIRED_SETS; j++) {                                   // thread t: bucket t of every set
+        const uint32_t c = hist[j][threadIdx.x];
+        if (c) atomicAdd(&ghist[j * MADSIM_STAT_BUCKETS + threadIdx.x], c);
+    }
+    if (threadIdx.x < PAIRED_HEAD) {                                               // one set of atomics per workgroup that paired a seed (word 1: that met a runner verdict)
+        const uint32_t j = threadIdx.x;
+        const bool is_max = j >= 10 && j < 26;
+        unsigned long long a = part[0][j];
+        for (int w = 1; w < 4; w++) { const unsigned long long t = part[w][j]; if (is_max) a = t > a ? t : a; else a += t; }
+        if (a) { if (is_max) atomicMax(&words[j], a); else atomicAdd(&words[j], a); }
+    }
+    if (K) {                                                                       // wave w: the workgroup's lists of sets w and w + 4
+        for (uint32_t j = wave; j < PAIRED_SETS; j += 4) {
+            TopKey l1[1] = {TopKey{0, 0}}, n1[1] = {TopKey{lv[j][lane], lk[j][lane]}};
+            topk_merge<1>(l1, n1, K, lane);
+            if (lane < STAT_TOP) {
+                unsigned long long* p = cand + ((uint64_t)(j * STAT_WGS + blockIdx.x) * STAT_TOP + lane) * 2;
+                p[0] = l1[0].v; p[1] = l1[0].k ? (unsigned long long)(uint32_t)~l1[0].k : ~0ull;
+            }
+        }
+    }
+}
+
+// grid = PAIRED_SETS workgroups: workgroup j merges cand[j][0 .. n_wg)[0 .. 16) ({magnitude, index in the batch or ~0}) as stats_top_kernel
+// does; top[j][r] = {seed, a, b} of metric j / 2, r < min(K, seeds of the batch in set j).  The list is read only for winners.
+template <class Seeds>
+__global__ __launch_bounds__(256) void paired_top_kernel(const madsim_result_t* __restrict__ ra, const madsim_result_t* __restrict__ rb,
+                                                         const unsigned long long* __restrict__ cand, uint32_t n_wg, uint32_t K, const Seeds seed_of,
+                                                         unsigned long long* __restrict__ top) {
+    __shared__ unsigned long long lv[4 * STAT_TOP];
+    __shared__ uint32_t lk[4 * STAT_TOP];
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63, j = blockIdx.x;
+    const uint32_t total = n_wg * STAT_TOP, quarter = (total / 4 + 63) / 64 * 64;      // (total is a multiple of 16, at most 4 096)
+    const uint32_t lo = wave * quarter, hi = lo + quarter < total ? lo + quarter : total;
+    const unsigned long long* src = cand + (uint64_t)j * STAT_WGS * STAT_TOP * 2;
+    TopKey list[1] = {TopKey{0, 0}};
+    for (uint32_t base = lo; base < hi; base += 64) {
+        const uint32_t c = base + lane;
+        TopKey nw[1] = {TopKey{0, 0}};
+        if (c < hi) {
+            const unsigned long long v = src[2 * c], x = src[2 * c + 1];
+            if (x != ~0ull) nw[0] = TopKey{v, ~(uint32_t)x};
+        }
+        if (topk_enters<1>(list, nw, K)) topk_merge<1>(list, nw, K, lane);
+    }
+    if (lane < STAT_TOP) { lv[wave * STAT_TOP + lane] = list[0].v; lk[wave * STAT_TOP + lane] = list[0].k; }
+    __syncthreads();
+    if (wave == 0) {
+        TopKey l1[1] = {TopKey{0, 0}}, n1[1] = {TopKey{lv[lane], lk[lane]}};
+        topk_merge<1>(l1, n1, K, lane);
+        if (lane < K && l1[0].k) {
+            const uint32_t idx = ~l1[0].k;
+            unsigned long long* p = top + (uint64_t)(j * STAT_TOP + lane) * 3;         // 24 B records: 8-byte stores
+            p[0] = seed_of(idx); p[1] = paired_metric(ra + idx, j >> 1); p[2] = paired_metric(rb + idx, j >> 1);
+        }
+    }
+}
+
 __global__ void keyflip_kernel(unsigned long long* acc) { acc[0] ^= 0x8000000000000000ull; }
 
 // ---- resolving campaigns: which seeds of a batch are run again, and their new results back in place ----------------------------
@@ -1066,6 +1235,42 @@ extern "C" int madsim_k_launch_diff_list(const madsim_result_t* a, const madsim_
                                          unsigned long long* words, uint32_t* wave_cnt, madsim_diff_record_t* recs, uint64_t cap, void* stream) {
     if (!d_seeds) return -1;
     return madsim_k::launch_diff(a, b, count, madsim_k::ListSeeds{d_seeds}, fields, words, wave_cnt, recs, cap, stream);
+}
+
+// words: MADSIM_K_PAIRED_WORDS zeroed words; cand: MADSIM_K_PAIRED_CAND_WORDS words of scratch, untouched (and may be null) when top_k == 0;
+// all prepared by the caller on `stream` (sim_kernel.h).  Returns 0, or -1 (nothing launched) for arguments the kernels are not written for.
+namespace madsim_k {
+template <class Seeds>
+static int launch_paired(const madsim_result_t* a, const madsim_result_t* b, uint64_t count, Seeds src, uint32_t include_a, uint32_t include_b,
+                         uint32_t top_k, unsigned long long* words, unsigned long long* cand, void* stream) {
+    static_assert(sizeof(madsim_paired_extreme_t) == 24 && sizeof(madsim_result_t) == 48, "record layout");
+    static_assert(MADSIM_K_PAIRED_HEAD_WORDS == madsim_k::PAIRED_HEAD && madsim_k::PAIRED_SETS == 8, "sim_kernel.h");
+    static_assert(MADSIM_K_PAIRED_WORDS == madsim_k::PAIRED_HEAD + madsim_k::PAIRED_SETS * MADSIM_STAT_BUCKETS / 2 + madsim_k::PAIRED_SETS * MADSIM_STAT_MAX_TOP * 3,
+                  "sim_kernel.h");
+    static_assert(MADSIM_K_PAIRED_CAND_WORDS == madsim_k::PAIRED_SETS * madsim_k::STAT_WGS * madsim_k::STAT_TOP * 2, "sim_kernel.h");
+    static_assert(MADSIM_PAIRED_UP == 0 && MADSIM_PAIRED_DOWN == 1 && MADSIM_STAT_BUCKETS == 256 && MADSIM_STAT_MAX_TOP == 16, "one bucket per thread, set = 2 * metric + direction");
+    if (!a || !b || !words || count == 0 || count >= (1ull << 32)) return -1;
+    if (include_a == 0 || (include_a & ~0xfu) || include_b == 0 || (include_b & ~0xfu) || top_k > MADSIM_STAT_MAX_TOP || (top_k && !cand)) return -1;
+    uint32_t grid = (uint32_t)((count + 1023) / 1024);     // collect's cut
+    if (grid > madsim_k::STAT_WGS) grid = madsim_k::STAT_WGS;
+    const uint64_t waves = 4ull * grid, piece = ((count + waves - 1) / waves + 63) / 64 * 64;
+    uint32_t* const ghist = reinterpret_cast<uint32_t*>(words + madsim_k::PAIRED_HEAD);
+    hipLaunchKernelGGL(madsim_k::paired_fold_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, a, b, count, piece, include_a, include_b, top_k, words,
+                       ghist, cand);
+    if (top_k)
+        hipLaunchKernelGGL((paired_top_kernel<Seeds>), dim3(madsim_k::PAIRED_SETS), dim3(256), 0, (hipStream_t)stream, a, b, (const unsigned long long*)cand, grid,
+                           top_k, src, words + madsim_k::PAIRED_HEAD + madsim_k::PAIRED_SETS * MADSIM_STAT_BUCKETS / 2);
+    return 0;
+}
+}  // namespace madsim_k
+extern "C" int madsim_k_launch_paired(const madsim_result_t* a, const madsim_result_t* b, uint64_t count, uint64_t seed0, uint32_t include_a,
+                                      uint32_t include_b, uint32_t top_k, unsigned long long* words, unsigned long long* cand, void* stream) {
+    return madsim_k::launch_paired(a, b, count, madsim_k::RangeSeeds{seed0}, include_a, include_b, top_k, words, cand, stream);
+}
+extern "C" int madsim_k_launch_paired_list(const madsim_result_t* a, const madsim_result_t* b, uint64_t count, const uint64_t* d_seeds, uint32_t include_a,
+                                           uint32_t include_b, uint32_t top_k, unsigned long long* words, unsigned long long* cand, void* stream) {
+    if (!d_seeds) return -1;
+    return madsim_k::launch_paired(a, b, count, madsim_k::ListSeeds{d_seeds}, include_a, include_b, top_k, words, cand, stream);
 }
 
 // sides: the n_variants result arrays of the same `count` seeds; words: MADSIM_K_SWEEP_WORDS zeroed words; wave_cnt: MADSIM_K_COLLECT_WAVES

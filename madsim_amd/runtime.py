@@ -13,6 +13,7 @@ module raises, loudly.
 """
 import ctypes as C
 import math
+from fractions import Fraction
 import operator
 import os
 import sys
@@ -149,6 +150,13 @@ def lib():
                                                                        C.POINTER(A.Campaign), C.POINTER(A.Diff)]
         L.madsim_hip_ctx_run_seeds_campaign_diff.argtypes = [ctxp] + L.madsim_hip_run_seeds_campaign_diff.argtypes
         L.madsim_hip_run_seeds_campaign_diff_multi.argtypes = [C.POINTER(ctxp), C.c_int] + L.madsim_hip_run_seeds_campaign_diff.argtypes
+        # the paired campaigns: the differential forms' arguments, the diff report optional, and a trailing madsim_paired_t
+        # (the range forms are spelled run_paired_campaign, as the sweep forms are run_sweep_campaign)
+        for twin, form in (("run_campaign_diff", "run_paired_campaign"), ("run_seeds_campaign_diff", "run_seeds_campaign_paired")):
+            base = getattr(L, f"madsim_hip_{twin}").argtypes + [C.POINTER(A.Paired)]
+            getattr(L, f"madsim_hip_{form}").argtypes = base
+            getattr(L, f"madsim_hip_ctx_{form}").argtypes = [ctxp] + base
+            getattr(L, f"madsim_hip_{form}_multi").argtypes = [C.POINTER(ctxp), C.c_int] + base
         L.madsim_hip_diverge_seeds.argtypes = side + side + [u64p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
         L.madsim_hip_ctx_diverge_seeds.argtypes = [ctxp] + L.madsim_hip_diverge_seeds.argtypes
         # the sweep campaigns: one signature for the range (seeds NULL) and the list (seed0 0)
@@ -821,6 +829,123 @@ def run_campaign_diff_seeds(workload, seeds, other=None, config=None, other_conf
         workload, other, config, other_config, limits, other_limits, fields, max_listed, stop_at_diffs, resolve, observe)
 
 
+class CampaignPaired:
+    """What a paired campaign (madsim_hip_run_paired_campaign) says about the prefix that ran: `n_paired`, `n_unpaired`, `n_incomparable`
+    (their sum is seeds_run), and per metric name of A.STAT_NAMES the dicts `n_equal`, `sum_a`, `sum_b` (Python ints: the exact 128-bit sums
+    of each side's values over the paired seeds) and — each a pair indexed by direction, A.PAIRED_UP / A.PAIRED_DOWN — `n`, `min`, `max`,
+    `sum` (Python ints) and `hist` (uint64[256] bucket counts) of the magnitudes |b - a|.  All exact integers; the helpers return ints
+    and fractions.Fraction, never floats."""
+
+    def __init__(self, pr, top):
+        self.include_a, self.include_b, self.top_k = int(pr.include_a), int(pr.include_b), int(pr.top_k)
+        self.n_paired, self.n_unpaired, self.n_incomparable = int(pr.n_paired), int(pr.n_unpaired), int(pr.n_incomparable)
+        self.n_equal, self.sum_a, self.sum_b = {}, {}, {}
+        self.n, self.min, self.max, self.sum, self.hist, self._top = {}, {}, {}, {}, {}, {}
+        for m, name in enumerate(A.STAT_NAMES):
+            self.n_equal[name] = int(pr.n_equal[m])
+            self.sum_a[name] = (int(pr.sum_a_hi[m]) << 64) | int(pr.sum_a_lo[m])
+            self.sum_b[name] = (int(pr.sum_b_hi[m]) << 64) | int(pr.sum_b_lo[m])
+            D = [pr.delta[2 * m + d] for d in (A.PAIRED_UP, A.PAIRED_DOWN)]
+            self.n[name] = tuple(int(pr.n[2 * m + d]) for d in (A.PAIRED_UP, A.PAIRED_DOWN))
+            self.min[name], self.max[name] = tuple(int(M.min) for M in D), tuple(int(M.max) for M in D)
+            self.sum[name] = tuple((int(M.sum_hi) << 64) | int(M.sum_lo) for M in D)
+            self.hist[name] = tuple(np.ctypeslib.as_array(M.hist).astype(np.uint64) for M in D)
+            self._top[name] = tuple(top[m, d, :int(pr.n_top[2 * m + d])].copy() for d in (A.PAIRED_UP, A.PAIRED_DOWN))
+
+    def net_sum(self, metric):
+        """Sum over the paired seeds of b - a as a Python int: the UP magnitudes minus the DOWN magnitudes."""
+        return self.sum[metric][A.PAIRED_UP] - self.sum[metric][A.PAIRED_DOWN]
+
+    def mean_delta(self, metric):
+        """The mean of b - a over the paired seeds, a fractions.Fraction."""
+        if not self.n_paired:
+            raise ValueError("mean_delta of no paired seeds")
+        return Fraction(self.net_sum(metric), self.n_paired)
+
+    def means(self, metric):
+        """(mean of side A, mean of side B) of `metric` over the paired seeds — the same population on both sides — as Fractions."""
+        if not self.n_paired:
+            raise ValueError("means of no paired seeds")
+        return Fraction(self.sum_a[metric], self.n_paired), Fraction(self.sum_b[metric], self.n_paired)
+
+    def quantile_bounds(self, metric, direction, q):
+        """(lo, hi): inclusive bounds of the magnitude of rank ceil(q * n) (1-based, ascending, q in (0, 1]) among the seeds that moved in
+        `direction` — those of its bucket (madsim_hip_stat_bucket_floor), clipped to [min, max]."""
+        if not 0 < q <= 1:
+            raise ValueError("quantile_bounds: q in (0, 1]")
+        n = self.n[metric][direction]
+        if not n:
+            raise ValueError("quantile_bounds of no seeds")
+        rank = min(max(math.ceil(Fraction(q) * n), 1), n)
+        b = int(np.searchsorted(np.cumsum(self.hist[metric][direction]), rank))
+        return (max(A.stat_bucket_floor(b), self.min[metric][direction]),
+                min(A.stat_bucket_floor(b + 1) - (1 if b < 251 else 0), self.max[metric][direction]))
+
+    def regressions(self, metric):
+        """The min(top_k, n up) seeds whose `metric` grew most from side A to side B, by magnitude descending, then seed ascending:
+        ndarray[PAIRED_EXTREME_DTYPE] of (seed, a, b)."""
+        return self._top[metric][A.PAIRED_UP]
+
+    def improvements(self, metric):
+        """The same of the seeds whose `metric` shrank most."""
+        return self._top[metric][A.PAIRED_DOWN]
+
+
+def _campaign_paired(call, workload, other, config, other_config, limits, other_limits, include, other_include, top_k, fields, max_listed, resolve):
+    """Run `call(wA, cfgA, limA, wB, cfgB, limB, flags, repA, repB, diff, paired)` — one of the madsim_hip_*run_campaign_paired* entry points with
+    its contexts and its range bound.  A None on the B side means "the same as A's"; fields=None: no diff report."""
+    mask_a = _include_mask(include)
+    mask_b = mask_a if other_include is None else _include_mask(other_include)
+    if not mask_a or not mask_b or not 0 <= top_k <= A.STAT_MAX_TOP:
+        raise MadsimHipError(f"run_campaign_paired: include and other_include must name a verdict and top_k be 0..{A.STAT_MAX_TOP}")
+    if fields is not None and (not isinstance(fields, int) or fields <= 0 or fields & ~A.DIFF_ALL or max_listed < 0):
+        raise MadsimHipError("run_campaign_paired: fields is None or a non-empty mask of A.DIFF_* bits, and max_listed >= 0")
+    cfg_a, lim_a = config or A.Config.default(), limits or A.Limits()
+    w_b, cfg_b, lim_b = other or workload, other_config or cfg_a, other_limits or lim_a
+    pr = A.Paired()
+    pr.include_a, pr.include_b, pr.top_k = mask_a, mask_b, top_k
+    top = np.zeros((A.STAT_METRICS, 2, top_k), dtype=A.PAIRED_EXTREME_DTYPE)
+    pr.top = top.ctypes.data_as(C.POINTER(A.PairedExtreme)) if top_k else None
+    d, arr = None, None
+    if fields is not None:
+        arr = np.zeros(max_listed, dtype=A.DIFF_RECORD_DTYPE)
+        d = A.Diff()
+        d.fields, d.cap = fields, max_listed
+        d.records = arr.ctypes.data_as(C.POINTER(A.DiffRecord)) if max_listed else None
+    rep_a, rep_b = A.Campaign(), A.Campaign()
+    _check(call(workload.ref(), C.byref(cfg_a), C.byref(lim_a), w_b.ref(), C.byref(cfg_b), C.byref(lim_b), _resolve_flags(resolve),
+                C.byref(rep_a), C.byref(rep_b), C.byref(d) if d is not None else None, C.byref(pr)))
+    out = rep_a, rep_b, CampaignPaired(pr, top)
+    return out + (CampaignDiff(d, arr),) if d is not None else out
+
+
+def run_campaign_paired(workload, seed0, total, other=None, config=None, other_config=None, limits=None, other_limits=None, include=(A.PASS,),
+                        other_include=None, top_k=0, fields=None, max_listed=0, resolve=None, batch=0, in_flight=0):
+    """madsim_hip_run_paired_campaign: what a change did to each seed's numbers.  Side A = (workload, config, limits) and side B = (other,
+    other_config, other_limits) over the same seeds — a None on the B side means "the same as A's".  A seed is PAIRED when its verdict on
+    side A is in `include` and on side B in `other_include` (None: the same as `include`); for every paired seed and each of clock_ns,
+    steps, msg_count and rng_calls the device takes b - a as a direction (up / down / equal) and an unsigned magnitude and reduces, per
+    metric and direction, count, min, max, the exact sum, a histogram and the `top_k` (<= 16) extreme seeds with both values.  Returns
+    (campaign A, campaign B, CampaignPaired); with fields= (A.DIFF_* bits) the differential report of the same run comes last, as
+    run_campaign_diff's, with the max_listed smallest differing seeds.  resolve: as run_campaign_diff_resolved's."""
+    if _inited_device is None:
+        init(0)
+    return _campaign_paired(lambda wa, ca, la, wb, cb, lb, flags, ra, rb, d, pr: lib().madsim_hip_run_paired_campaign(
+        wa, ca, la, wb, cb, lb, seed0, total, batch, in_flight, flags, ra, rb, d, pr),
+        workload, other, config, other_config, limits, other_limits, include, other_include, top_k, fields, max_listed, resolve)
+
+
+def run_campaign_paired_seeds(workload, seeds, other=None, config=None, other_config=None, limits=None, other_limits=None, include=(A.PASS,),
+                              other_include=None, top_k=0, fields=None, max_listed=0, resolve=None, batch=0, in_flight=0):
+    """madsim_hip_run_seeds_campaign_paired: run_campaign_paired over the seeds you name (`seeds` as run_campaign_seeds')."""
+    arr = seed_list(seeds)                                       # (a list that does not ascend is refused before a device is looked for)
+    if _inited_device is None:
+        init(0)
+    return _campaign_paired(lambda wa, ca, la, wb, cb, lb, flags, ra, rb, d, pr: lib().madsim_hip_run_seeds_campaign_paired(
+        wa, ca, la, wb, cb, lb, _seeds_ptr(arr), len(arr), batch, in_flight, flags, ra, rb, d, pr),
+        workload, other, config, other_config, limits, other_limits, include, other_include, top_k, fields, max_listed, resolve)
+
+
 class CampaignSweep:
     """What a sweep campaign (madsim_hip_run_sweep_campaign) says about the prefix that ran: `n_by_mask`, a uint64 array of length 2^V — the
     settled seeds by the set of variants they fail in (bit v = variant v) —; `n_settled`, `n_incomparable` (a runner verdict in some variant),
@@ -1087,6 +1212,21 @@ class Context:
             self._h, wa, ca, la, wb, cb, lb, _seeds_ptr(arr), len(arr), batch, in_flight, flags, ra, rb, d),
             workload, other, config, other_config, limits, other_limits, fields, max_listed, stop_at_diffs, resolve, observe, self.trace_seeds)
 
+    def run_campaign_paired(self, workload, seed0, total, other=None, config=None, other_config=None, limits=None, other_limits=None,
+                            include=(A.PASS,), other_include=None, top_k=0, fields=None, max_listed=0, resolve=None, batch=0, in_flight=0):
+        """runtime.run_campaign_paired on this context (madsim_hip_ctx_run_paired_campaign)."""
+        return _campaign_paired(lambda wa, ca, la, wb, cb, lb, flags, ra, rb, d, pr: lib().madsim_hip_ctx_run_paired_campaign(
+            self._h, wa, ca, la, wb, cb, lb, seed0, total, batch, in_flight, flags, ra, rb, d, pr),
+            workload, other, config, other_config, limits, other_limits, include, other_include, top_k, fields, max_listed, resolve)
+
+    def run_campaign_paired_seeds(self, workload, seeds, other=None, config=None, other_config=None, limits=None, other_limits=None,
+                                  include=(A.PASS,), other_include=None, top_k=0, fields=None, max_listed=0, resolve=None, batch=0, in_flight=0):
+        """runtime.run_campaign_paired_seeds on this context (madsim_hip_ctx_run_seeds_campaign_paired)."""
+        arr = seed_list(seeds)
+        return _campaign_paired(lambda wa, ca, la, wb, cb, lb, flags, ra, rb, d, pr: lib().madsim_hip_ctx_run_seeds_campaign_paired(
+            self._h, wa, ca, la, wb, cb, lb, _seeds_ptr(arr), len(arr), batch, in_flight, flags, ra, rb, d, pr),
+            workload, other, config, other_config, limits, other_limits, include, other_include, top_k, fields, max_listed, resolve)
+
     def run_campaign_sweep(self, variants, seed0=0, total=0, seeds=None, fields=A.DIFF_VERDICT, list_rule="mixed", max_listed=0,
                            stop_at_listed=False, batch=0, in_flight=0, resolve=None):
         """runtime.run_campaign_sweep on this context (madsim_hip_ctx_run_sweep_campaign)."""
@@ -1181,6 +1321,26 @@ def run_campaign_diff_seeds_multi(contexts, workload, seeds, other=None, config=
     return _campaign_diff(lambda wa, ca, la, wb, cb, lb, flags, ra, rb, d: lib().madsim_hip_run_seeds_campaign_diff_multi(
         arr, len(contexts), wa, ca, la, wb, cb, lb, _seeds_ptr(seeds_arr), len(seeds_arr), batch, in_flight, flags, ra, rb, d),
         workload, other, config, other_config, limits, other_limits, fields, max_listed, stop_at_diffs, resolve)
+
+
+def run_campaign_paired_multi(contexts, workload, seed0, total, other=None, config=None, other_config=None, limits=None, other_limits=None,
+                              include=(A.PASS,), other_include=None, top_k=0, fields=None, max_listed=0, resolve=None, batch=0, in_flight=0):
+    """madsim_hip_run_paired_campaign_multi: run_campaign_paired over several contexts (both sides of batch k on context k % n); the report is
+    the one a single context gives."""
+    arr = (C.c_void_p * len(contexts))(*[c._h for c in contexts])
+    return _campaign_paired(lambda wa, ca, la, wb, cb, lb, flags, ra, rb, d, pr: lib().madsim_hip_run_paired_campaign_multi(
+        arr, len(contexts), wa, ca, la, wb, cb, lb, seed0, total, batch, in_flight, flags, ra, rb, d, pr),
+        workload, other, config, other_config, limits, other_limits, include, other_include, top_k, fields, max_listed, resolve)
+
+
+def run_campaign_paired_seeds_multi(contexts, workload, seeds, other=None, config=None, other_config=None, limits=None, other_limits=None,
+                                    include=(A.PASS,), other_include=None, top_k=0, fields=None, max_listed=0, resolve=None, batch=0, in_flight=0):
+    """madsim_hip_run_seeds_campaign_paired_multi: run_campaign_paired_seeds over several contexts; the report is the one a single context gives."""
+    seeds_arr = seed_list(seeds)
+    arr = (C.c_void_p * len(contexts))(*[c._h for c in contexts])
+    return _campaign_paired(lambda wa, ca, la, wb, cb, lb, flags, ra, rb, d, pr: lib().madsim_hip_run_seeds_campaign_paired_multi(
+        arr, len(contexts), wa, ca, la, wb, cb, lb, _seeds_ptr(seeds_arr), len(seeds_arr), batch, in_flight, flags, ra, rb, d, pr),
+        workload, other, config, other_config, limits, other_limits, include, other_include, top_k, fields, max_listed, resolve)
 
 
 def run_campaign_over_ranks(workload, seed0, total, batch=65536, stop_at_failure=True, config=None, limits=None, device_tensors=None, group=None,
