@@ -96,9 +96,13 @@ struct madsim_hip_resources {
     static constexpr int CAMPAIGN_MAX = 8;
     static constexpr size_t STATS_REP_WORDS = 16 + MADSIM_K_STATS_WORDS;      // a statistics campaign's report: the plain / collecting report's words in front
     static constexpr size_t GROUP_REP_WORDS = STATS_REP_WORDS + MADSIM_K_GROUP_WORDS;
-    static constexpr size_t DIFF_REP_WORDS = 16 + MADSIM_K_DIFF_WORDS;      // summary6's six words of side A at 0, of side B at 8, the diff words at 16
-    static constexpr size_t PAIRED_REP_WORDS = DIFF_REP_WORDS + MADSIM_K_PAIRED_WORDS;      // a paired campaign's report: the differential report's words in front
-    static constexpr size_t SWEEP_REP_WORDS =8 * MADSIM_SWEEP_MAX_VARIANTS + MADSIM_K_SWEEP_WORDS;      // summary6's six words of variant v at 8 v, the sweep words at 64
+    // The multi-variant forms (differential, paired, sweep) share one word layout: summary6's six words of variant v at 8 v, the form's words at
+    // VARIANT_FORM_AT — the diff words, then the paired words with the top records at their end; or the sweep words.
+    static constexpr size_t VARIANT_FORM_AT = 8 * MADSIM_SWEEP_MAX_VARIANTS;
+    static constexpr size_t DIFF_REP_WORDS = VARIANT_FORM_AT + MADSIM_K_DIFF_WORDS;
+    static constexpr size_t PAIRED_REP_WORDS = DIFF_REP_WORDS + MADSIM_K_PAIRED_WORDS;
+    static constexpr size_t SWEEP_REP_WORDS = VARIANT_FORM_AT + MADSIM_K_SWEEP_WORDS;
+    static constexpr size_t VARIANT_REP_WORDS = PAIRED_REP_WORDS > SWEEP_REP_WORDS ? PAIRED_REP_WORDS : SWEEP_REP_WORDS;
     // One batch in flight: what every form uses, then one group per campaign form, made when a call of that form first comes (ensure)
     // and kept with the flight.  Every resource is ensured on its own — none stands for another —, so a call that ran out of memory
     // half-way leaves nothing that a later call would take for complete.
@@ -151,79 +155,43 @@ struct madsim_hip_resources {
                 return 0;
             }
         } groups;
-        // differential campaigns: side B's results, its event pair, the report words — DIFF_REP_WORDS live ones (device, page-locked
-        // host) and behind the device's a copy of their state before a batch, from which one device copy prepares them —, per-wave
-        // counts and the batch's records
-        struct Diff {
-            DevBuf<madsim_result_t> out_b; Event b0, b1;
-            DevBuf<report_word_t> d_rep; PinnedBuf<report_word_t> h_rep; DevBuf<uint32_t> wcnt; DevBuf<madsim_diff_record_t> rec;
-            int ensure(uint64_t batch, uint64_t records, hipStream_t s) {
-                if (!d_rep) {
-                    report_word_t init[DIFF_REP_WORDS] = {};                        // the words before a batch: summary6's two minima all-ones, the rest zero
-                    init[0] = init[4] = init[8] = init[12] = ~0ull;
-                    HIP_TRY(d_rep.room(2 * DIFF_REP_WORDS));
-                    const hipError_t e = hipMemcpy(d_rep + DIFF_REP_WORDS, init, sizeof init, hipMemcpyHostToDevice);
-                    if (e != hipSuccess) {                                          // (words without their initial state are no words)
-                        d_rep.reset();
-                        return fail(MADSIM_E_HIP, std::string("hipMemcpy(initial report words): ") + hipGetErrorString(e));
-                    }
-                }
-                HIP_TRY(h_rep.room(DIFF_REP_WORDS));
-                HIP_TRY(wcnt.room(MADSIM_K_COLLECT_WAVES));
-                HIP_TRY(b0.ensure()); HIP_TRY(b1.ensure());
-                HIP_TRY(out_b.room(batch, s));
-                HIP_TRY(rec.room(records, s));
-                return 0;
-            }
-        } diff;
-        // paired campaigns (which also use the differential group: side B's results and event pair, and its counts and records when a
-        // diff report is asked for): the report words of the whole batch — PAIRED_REP_WORDS live ones (device, page-locked host): the
-        // differential campaign's DIFF_REP_WORDS in front, then the paired words with the top records at their end — and behind the
-        // device's a copy of their state before a batch; the candidate words of the top-K
-        struct Paired {
-            DevBuf<report_word_t> d_rep; PinnedBuf<report_word_t> h_rep; DevBuf<unsigned long long> cand;
-            int ensure() {
-                if (!d_rep) {
-                    std::vector<report_word_t> init(PAIRED_REP_WORDS, 0);           // the words before a batch: summary6's two minima all-ones, the rest zero
-                    init[0] = init[4] = init[8] = init[12] = ~0ull;
-                    HIP_TRY(d_rep.room(2 * PAIRED_REP_WORDS));
-                    const hipError_t e = hipMemcpy(d_rep + PAIRED_REP_WORDS, init.data(), PAIRED_REP_WORDS * sizeof(report_word_t), hipMemcpyHostToDevice);
-                    if (e != hipSuccess) {                                          // (words without their initial state are no words)
-                        d_rep.reset();
-                        return fail(MADSIM_E_HIP, std::string("hipMemcpy(initial report words): ") + hipGetErrorString(e));
-                    }
-                }
-                HIP_TRY(h_rep.room(PAIRED_REP_WORDS));
-                HIP_TRY(cand.room(MADSIM_K_PAIRED_CAND_WORDS));
-                return 0;
-            }
-        } paired;
-        // sweep campaigns: the results of variants 1 .. 7 (variant 0 uses d_out), made only up to the number of variants a call needs, an
-        // event pair per variant, the report words — SWEEP_REP_WORDS live ones (device, page-locked host) and behind the device's a copy of
-        // their state before a batch —, per-wave counts and the batch's records
-        struct Sweep {
+        // the multi-variant forms: the results of variants 1 .. 7 (variant 0 uses d_out), made only up to the number of variants a call
+        // needs, an event pair per variant, the report words — VARIANT_REP_WORDS live ones (device, page-locked host) and behind the
+        // device's their state before a batch, the same for every form, from which one device copy prepares them
+        struct Variants {
             DevBuf<madsim_result_t> out[MADSIM_SWEEP_MAX_VARIANTS - 1]; Event v0[MADSIM_SWEEP_MAX_VARIANTS], v1[MADSIM_SWEEP_MAX_VARIANTS];
-            DevBuf<report_word_t> d_rep; PinnedBuf<report_word_t> h_rep; DevBuf<uint32_t> wcnt; DevBuf<madsim_sweep_record_t> rec;
-            int ensure(uint32_t n_variants, uint64_t batch, uint64_t records, hipStream_t s) {
+            DevBuf<report_word_t> d_rep; PinnedBuf<report_word_t> h_rep;
+            int ensure(uint32_t n_variants, uint64_t batch, hipStream_t s) {
                 if (!d_rep) {
-                    report_word_t init[SWEEP_REP_WORDS] = {};                       // the words before a batch: every summary6's two minima all-ones, the rest zero
+                    std::vector<report_word_t> init(VARIANT_REP_WORDS, 0);          // the words before a batch: every summary6's two minima all-ones, the rest zero
                     for (uint32_t v = 0; v < MADSIM_SWEEP_MAX_VARIANTS; v++) init[8 * v] = init[8 * v + 4] = ~0ull;
-                    HIP_TRY(d_rep.room(2 * SWEEP_REP_WORDS));
-                    const hipError_t e = hipMemcpy(d_rep + SWEEP_REP_WORDS, init, sizeof init, hipMemcpyHostToDevice);
+                    HIP_TRY(d_rep.room(2 * VARIANT_REP_WORDS));
+                    const hipError_t e = hipMemcpy(d_rep + VARIANT_REP_WORDS, init.data(), VARIANT_REP_WORDS * sizeof(report_word_t), hipMemcpyHostToDevice);
                     if (e != hipSuccess) {                                          // (words without their initial state are no words)
                         d_rep.reset();
                         return fail(MADSIM_E_HIP, std::string("hipMemcpy(initial report words): ") + hipGetErrorString(e));
                     }
                 }
-                HIP_TRY(h_rep.room(SWEEP_REP_WORDS));
-                HIP_TRY(wcnt.room(MADSIM_K_COLLECT_WAVES));
+                HIP_TRY(h_rep.room(VARIANT_REP_WORDS));
                 for (uint32_t v = 0; v < n_variants; v++) {
                     HIP_TRY(v0[v].ensure()); HIP_TRY(v1[v].ensure());
                     if (v) HIP_TRY(out[v - 1].room(batch, s));
                 }
-                HIP_TRY(rec.room(records, s));
                 return 0;
             }
+        } variants;
+        // what each of them adds: per-wave counts and the batch's records (differential, sweep), the candidate words of the top-K (paired)
+        struct Diff {
+            DevBuf<uint32_t> wcnt; DevBuf<madsim_diff_record_t> rec;
+            int ensure(uint64_t records, hipStream_t s) { HIP_TRY(wcnt.room(MADSIM_K_COLLECT_WAVES)); HIP_TRY(rec.room(records, s)); return 0; }
+        } diff;
+        struct Paired {
+            DevBuf<unsigned long long> cand;
+            int ensure() { HIP_TRY(cand.room(MADSIM_K_PAIRED_CAND_WORDS)); return 0; }
+        } paired;
+        struct Sweep {
+            DevBuf<uint32_t> wcnt; DevBuf<madsim_sweep_record_t> rec;
+            int ensure(uint64_t records, hipStream_t s) { HIP_TRY(wcnt.room(MADSIM_K_COLLECT_WAVES)); HIP_TRY(rec.room(records, s)); return 0; }
         } sweep;
         // resolving campaigns, made when a batch first needs a round (most campaigns never do), enlarged — with the flight's stream drained —
         // when a later call brings larger batches: the seed list, the index list and the re-run results of `want` seeds (60 B per seed), the
@@ -1625,181 +1593,124 @@ int run_campaign_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_workl
     return first_err ? fail(first_err, first_msg) : 0;
 }
 
-// The differential form: the same flights, the same loop; per batch both sides' simulation and summary6 launches, then the two diff kernels,
-// all on the flight's one stream, and one copy of the words.  Both sides of batch k run on context k % n.
-struct DiffSide { const madsim_workload_t* w; const madsim_config_t* cfg; const madsim_limits_t* lim; madsim_campaign_t* out; };
-
-int run_campaign_diff_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const DiffSide (&side)[2], uint64_t seed0, uint64_t total, uint64_t batch,
-                           uint32_t in_flight, uint32_t flags, madsim_diff_t* d, const uint64_t* list = nullptr, madsim_paired_t* pr = nullptr) {
-    // `list`: as in run_campaign_impl — position i of list[0 .. total) for seed0 + i, seed0 = 0; both sides of a batch read the same slice.
-    // `pr` (the paired campaigns): the paired kernels behind the diff kernels, and `d` may then be NULL (no diff kernels).  The batch's words
-    // — the two summaries, the diff words, the paired words — then live in the flight's paired group and come back in one copy; without
-    // `pr` everything below queues what the differential campaign always queued.
-    auto t0 = std::chrono::steady_clock::now();
-    for (const DiffSide& s : side) { memset(s.out, 0, sizeof *s.out); s.out->first_failing_seed = UINT64_MAX; }
-    if (d) {
-        d->n_listed = d->n_compared = d->n_incomparable = d->n_differ = 0;
-        memset(d->n_by_field, 0, sizeof d->n_by_field);
-        memset(d->transitions, 0, sizeof d->transitions);
-    }
-    if (pr) {                                                    // (everything behind the caller's inputs)
-        memset(&pr->n_paired, 0, sizeof *pr - offsetof(madsim_paired_t, n_paired));
-        for (madsim_metric_t& M : pr->delta) M.min = UINT64_MAX;
-    }
-    flags &= MADSIM_CAMPAIGN_STOP_AT_DIFFS | MADSIM_CAMPAIGN_RESOLVE | MADSIM_CAMPAIGN_RESOLVE_ROUNDS_MASK;      // (the other stop flags belong to the other forms)
-    if (!d) flags &= ~MADSIM_CAMPAIGN_STOP_AT_DIFFS;
-    const uint32_t R = resolve_rounds(flags);
-    ResolveAccount account(ctxs, n_ctx, R);
-    madsim_resolve_t& acct = account.a;
-    for (int s = 0; s < 2; s++)
-        if (int rc = madsim_geo::validate(side[s].w, side[s].cfg, &g_err)) return fail(rc, std::string(s ? "side B: " : "side A: ") + g_err);
-    int rc;
-    if ((rc = check_campaign_range(batch, in_flight, list != nullptr, seed0, total))) return rc;
-    if (total == 0) return 0;
-    const uint64_t width = std::min(batch, total);
-    if (width >= (1ull << 32)) return fail(MADSIM_E_ARG, "a differential campaign's batch holds fewer than 2^32 seeds");
-    if (R && width >= (1ull << 30)) return fail(MADSIM_E_ARG, "a resolving campaign's batch holds fewer than 2^30 seeds");
-    const uint64_t n_batches = (total + batch - 1) / batch, N = (uint64_t)n_ctx;
-    const uint64_t rec_batch = d ? std::min(d->cap, width) : 0;      // records a flight holds: no batch lists more
-    CampaignFlights flights(ctxs, n_ctx);
-    if ((rc = flights.setup(n_batches, batch, width, in_flight, list != nullptr,
-                            [&](madsim_hip_ctx* c) {
-                                return std::min(c->flights_for(side[0].w, side[0].cfg, side[0].lim, batch), c->flights_for(side[1].w, side[1].cfg, side[1].lim, batch));
-                            },
-                            [&](madsim_hip_ctx::Flight& f) {
-                                if (int e = f.diff.ensure(batch, rec_batch, f.stream)) return e;
-                                return pr ? f.paired.ensure() : 0;
-                            })))
-        return rc;
-    // the words of a batch: the differential group's, or — in a paired campaign — the paired group's, whose copy ends before the top
-    // records when there are none
-    const size_t n_words = pr ? madsim_hip_ctx::PAIRED_REP_WORDS : madsim_hip_ctx::DIFF_REP_WORDS;
-    const size_t n_copied = pr && !pr->top_k ? n_words - 8 * MADSIM_STAT_MAX_TOP * 3 : n_words;
-    constexpr size_t at_paired = madsim_hip_ctx::DIFF_REP_WORDS;
-    auto d_rep = [&](madsim_hip_ctx::Flight& f) -> report_word_t* { return pr ? f.paired.d_rep : f.diff.d_rep; };
-    auto h_rep = [&](madsim_hip_ctx::Flight& f) -> report_word_t* { return pr ? f.paired.h_rep : f.diff.h_rep; };
-    int first_err = 0;
-    std::string first_msg;
-    bool stop = false;
-    // A batch's report chain in the parts that `queue` puts around the two simulation launches and a resolving `harvest` queues again back
-    // to back: the words reset by one device copy, a side's summary6 over its results, then the diff kernels, the copy and the `done` event.
-    auto prepare_report = [&](madsim_hip_ctx::Flight& f) -> int {
-        HIP_TRY(hipMemcpyAsync(d_rep(f), d_rep(f) + n_words, n_copied * sizeof(unsigned long long), hipMemcpyDeviceToDevice, f.stream));
-        return 0;
-    };
-    auto queue_summary = [&](madsim_hip_ctx::Flight& f, int s, uint64_t lo, uint64_t n) -> int {
-        if (list) madsim_k_launch_summary6_list(s ? f.diff.out_b : f.d_out, n, f.list.d, d_rep(f) + 8 * s, f.stream);
-        else madsim_k_launch_summary6(s ? f.diff.out_b : f.d_out, n, seed0 + lo, d_rep(f) + 8 * s, f.stream);
-        HIP_TRY(hipGetLastError());
-        return 0;
-    };
-    auto queue_diff = [&](madsim_hip_ctx::Flight& f, uint64_t lo, uint64_t n) -> int {
-        if (d && (list ? madsim_k_launch_diff_list(f.d_out, f.diff.out_b, n, f.list.d, d->fields, d_rep(f) + 16, f.diff.wcnt, f.diff.rec, std::min(rec_batch, n), f.stream)
-                       : madsim_k_launch_diff(f.d_out, f.diff.out_b, n, seed0 + lo, d->fields, d_rep(f) + 16, f.diff.wcnt, f.diff.rec, std::min(rec_batch, n), f.stream)))
-            return fail(MADSIM_E_ARG, "madsim_k_launch_diff refused the batch's arguments");
-        if (pr && (list ? madsim_k_launch_paired_list(f.d_out, f.diff.out_b, n, f.list.d, pr->include_a, pr->include_b, pr->top_k, d_rep(f) + at_paired,
-                                                      f.paired.cand, f.stream)
-                        : madsim_k_launch_paired(f.d_out, f.diff.out_b, n, seed0 + lo, pr->include_a, pr->include_b, pr->top_k, d_rep(f) + at_paired,
-                                                 f.paired.cand, f.stream)))
-            return fail(MADSIM_E_ARG, "madsim_k_launch_paired refused the batch's arguments");
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(h_rep(f), d_rep(f), n_copied * sizeof(unsigned long long), hipMemcpyDeviceToHost, f.stream));
-        HIP_TRY(hipEventRecord(f.done, f.stream));
-        return 0;
-    };
-    auto queue = [&](uint64_t k) -> int {
-        madsim_hip_ctx* c = ctxs[k % N];
-        madsim_hip_ctx::Flight& f = flights.of(k);
-        const uint64_t lo = k * batch, n = std::min(batch, total - lo);
-        int e;
-        if ((e = c->bind())) return e;
-        if ((e = prepare_report(f))) return e;
-        if (list && (e = queue_list_slice(f, list, lo, n))) return e;      // (one slice for both sides)
-        const uint64_t* const d_list = list ? f.list.d : nullptr;
-        HIP_TRY(hipEventRecord(f.e0, f.stream));
-        if ((e = c->launch(side[0].w, side[0].cfg, seed0 + lo, n, d_list, side[0].lim, f.d_out, f.stream))) return fail(e, "side A: " + g_err);
-        HIP_TRY(hipEventRecord(f.e1, f.stream));
-        if ((e = queue_summary(f, 0, lo, n))) return e;
-        HIP_TRY(hipEventRecord(f.diff.b0, f.stream));
-        if ((e = c->launch(side[1].w, side[1].cfg, seed0 + lo, n, d_list, side[1].lim, f.diff.out_b, f.stream))) return fail(e, "side B: " + g_err);
-        HIP_TRY(hipEventRecord(f.diff.b1, f.stream));
-        if ((e = queue_summary(f, 1, lo, n))) return e;
-        return queue_diff(f, lo, n);
-    };
-    auto harvest = [&](uint64_t k) -> int {
-        madsim_hip_ctx* c = ctxs[k % N];
-        madsim_hip_ctx::Flight& f = flights.of(k);
-        int e;
-        if ((e = c->bind())) return e;
-        HIP_TRY(hipEventSynchronize(f.done));
-        if (first_err || stop) return 0;                        // (draining after an error, or a batch launched beyond the stopping one)
-        const uint64_t lo = k * batch, n = std::min(batch, total - lo);
-        float ms[2] = {0.f, 0.f};
-        HIP_TRY(hipEventElapsedTime(&ms[0], f.e0, f.e1));
-        HIP_TRY(hipEventElapsedTime(&ms[1], f.diff.b0, f.diff.b1));
-        const report_word_t* const h = h_rep(f);
-        if (R && (h[5] > 0 || h[8 + 5] > 0)) {    // runner verdicts on a side: settle them under that side's own limits, diff again
-            const unsigned long long runner_before[2] = {h[5], h[8 + 5]};
-            bool ran = false;
-            for (int s = 0; s < 2; s++) {                       // (one after the other on the flight's stream: they share its re-run scratch)
-                if (!runner_before[s]) continue;
-                double rerun_ms = 0.0;
-                if ((e = resolve_results(c, f, side[s].w, side[s].cfg, side[s].lim, s ? f.diff.out_b : f.d_out, seed0 + lo, list ? f.list.d : nullptr, n, R, acct,
-                                         &rerun_ms, &ran)))
-                    return fail(e, std::string(s ? "side B: " : "side A: ") + g_err);
-                acct.rerun_kernel_ms += rerun_ms; side[s].out->kernel_ms += rerun_ms;
-            }
-            if (ran) {
-                if ((e = prepare_report(f)) || (e = queue_summary(f, 0, lo, n)) || (e = queue_summary(f, 1, lo, n)) || (e = queue_diff(f, lo, n))) return e;
-                HIP_TRY(hipEventSynchronize(f.done));
-                acct.n_resolved += (runner_before[0] - h[5]) + (runner_before[1] - h[8 + 5]);
-            }
-        }
-        for (int s = 0; s < 2; s++) fold_summary(side[s].out, h + 8 * s, n, ms[s]);
-        if (pr) {
-            if (h[at_paired] + h[at_paired + 1] > n) return fail(MADSIM_E_HIP, "paired campaign: a batch reports more paired and incomparable seeds than it holds");
-            madsim_k_fold_paired(pr, h + at_paired, n);
-        }
-        if (!d) return 0;
-        if (h[16] > n) return fail(MADSIM_E_HIP, "differential campaign: a batch reports more differing seeds than it holds");
-        // the batch's records, as many as the list still takes (the stream is idle: its `done` has passed, and it takes no launch before this returns)
-        const uint64_t at = d->n_listed, take = madsim_k_fold_diff(d, h + 16, n, nullptr);
-        if (take) {
-            HIP_TRY(hipMemcpyAsync(d->records + at, f.diff.rec, take * sizeof(madsim_diff_record_t), hipMemcpyDeviceToHost, f.stream));
-            HIP_TRY(hipStreamSynchronize(f.stream));
-        }
-        if ((flags & MADSIM_CAMPAIGN_STOP_AT_DIFFS) && d->n_differ >= d->cap) stop = true;
-        return 0;
-    };
-    const uint64_t launched = pump_batches(ctxs, n_ctx, n_batches, flights.F, stop, first_err, first_msg, queue, harvest);
-    for (const DiffSide& s : side) { s.out->batches_launched = launched; s.out->wall_s = since(t0); }
-    return first_err ? fail(first_err, first_msg) : 0;
+// ---- the multi-variant forms: differential, paired, sweep ---------------------------------------------------------------------------
+// The same flights, the same loop; per batch every variant's simulation and summary6 launches, then the form's report kernels, all on the
+// flight's one stream, and one copy of the words.  Every variant of batch k runs on context k % n.  A form says what is its own: how an error
+// names variant v (who), the stop flag it honours, how wide a batch it takes, how many of the words a batch uses (n_copied: both copies stop
+// there), what it keeps on a flight (ensure), its report kernels over the variants' results (queue: `words` are the form's, all zero), and
+// its host fold with the records the list still takes and its stop rule (fold: the stream is idle — its `done` has passed — and takes no
+// launch before fold returns).
+extern "C++" {
+template <class Rec>
+int copy_records(Rec* to, const Rec* d_from, uint64_t take, hipStream_t s) {
+    if (!take) return 0;
+    HIP_TRY(hipMemcpyAsync(to, d_from, take * sizeof(Rec), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return 0;
 }
 
-// The sweep form: the same flights, the same loop; per batch every variant's simulation and summary6 launches, then the two sweep kernels,
-// all on the flight's one stream, and one copy of the words.  Every variant of batch k runs on context k % n.  `var`: the caller's
-// variants with a NULL config replaced by the default one (check_sweep_args has validated them).
-int run_campaign_sweep_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_sweep_variant_t* var, uint32_t V, uint64_t seed0, uint64_t total,
-                            uint64_t batch, uint32_t in_flight, uint32_t flags, madsim_sweep_t* sw, const uint64_t* list) {
-    // `list`: as in run_campaign_impl — position i of list[0 .. total) for seed0 + i, seed0 = 0; every variant of a batch reads the same slice.
+// Differential and paired campaigns: the diff kernels when a diff report is asked for, the paired kernels behind them when a paired one is;
+// the diff words first, then the paired words, whose copies end before the top records when there are none.
+struct PairForm {
+    madsim_diff_t* d; madsim_paired_t* pr;
+    static constexpr uint64_t max_width = 1ull << 32;
+    static constexpr const char* too_wide = "a differential campaign's batch holds fewer than 2^32 seeds";
+    static std::string who(uint32_t v) { return v ? "side B: " : "side A: "; }
+    uint32_t stop_flag() const { return d ? MADSIM_CAMPAIGN_STOP_AT_DIFFS : 0u; }
+    size_t n_copied() const {
+        return !pr ? madsim_hip_ctx::DIFF_REP_WORDS : madsim_hip_ctx::PAIRED_REP_WORDS - (pr->top_k ? 0 : 8 * MADSIM_STAT_MAX_TOP * 3);
+    }
+    void reset() const {
+        if (d) {
+            d->n_listed = d->n_compared = d->n_incomparable = d->n_differ = 0;
+            memset(d->n_by_field, 0, sizeof d->n_by_field);
+            memset(d->transitions, 0, sizeof d->transitions);
+        }
+        if (pr) {                                                // (everything behind the caller's inputs)
+            memset(&pr->n_paired, 0, sizeof *pr - offsetof(madsim_paired_t, n_paired));
+            for (madsim_metric_t& M : pr->delta) M.min = UINT64_MAX;
+        }
+    }
+    int ensure(madsim_hip_ctx::Flight& f, uint64_t width) const {
+        if (d) if (int e = f.diff.ensure(std::min(d->cap, width), f.stream)) return e;      // (records a flight holds: no batch lists more)
+        return pr ? f.paired.ensure() : 0;
+    }
+    int queue(madsim_hip_ctx::Flight& f, const madsim_result_t* const* res, uint64_t seed_lo, const uint64_t* d_list, uint64_t n, report_word_t* words) const {
+        if (d && (d_list ? madsim_k_launch_diff_list(res[0], res[1], n, d_list, d->fields, words, f.diff.wcnt, f.diff.rec, std::min(d->cap, n), f.stream)
+                         : madsim_k_launch_diff(res[0], res[1], n, seed_lo, d->fields, words, f.diff.wcnt, f.diff.rec, std::min(d->cap, n), f.stream)))
+            return fail(MADSIM_E_ARG, "madsim_k_launch_diff refused the batch's arguments");
+        report_word_t* const pw = words + MADSIM_K_DIFF_WORDS;
+        if (pr && (d_list ? madsim_k_launch_paired_list(res[0], res[1], n, d_list, pr->include_a, pr->include_b, pr->top_k, pw, f.paired.cand, f.stream)
+                          : madsim_k_launch_paired(res[0], res[1], n, seed_lo, pr->include_a, pr->include_b, pr->top_k, pw, f.paired.cand, f.stream)))
+            return fail(MADSIM_E_ARG, "madsim_k_launch_paired refused the batch's arguments");
+        return 0;
+    }
+    int fold(madsim_hip_ctx::Flight& f, const report_word_t* words, uint64_t n, uint32_t flags, bool& stop) const {
+        if (pr) {
+            const report_word_t* const pw = words + MADSIM_K_DIFF_WORDS;
+            if (pw[0] + pw[1] > n) return fail(MADSIM_E_HIP, "paired campaign: a batch reports more paired and incomparable seeds than it holds");
+            madsim_k_fold_paired(pr, pw, n);
+        }
+        if (!d) return 0;
+        if (words[0] > n) return fail(MADSIM_E_HIP, "differential campaign: a batch reports more differing seeds than it holds");
+        const uint64_t at = d->n_listed, take = madsim_k_fold_diff(d, words, n, nullptr);
+        if (int e = copy_records(d->records + at, f.diff.rec.p, take, f.stream)) return e;
+        if ((flags & MADSIM_CAMPAIGN_STOP_AT_DIFFS) && d->n_differ >= d->cap) stop = true;
+        return 0;
+    }
+};
+
+// Sweep campaigns: the two sweep kernels over all V results.
+struct SweepForm {
+    madsim_sweep_t* sw; uint32_t V;
+    static constexpr uint64_t max_width = 1ull << 32;
+    static constexpr const char* too_wide = "a sweep campaign's batch holds fewer than 2^32 seeds";
+    static std::string who(uint32_t v) { return "variant " + std::to_string(v) + ": "; }
+    static uint32_t stop_flag() { return MADSIM_CAMPAIGN_STOP_AT_SWEEP; }
+    static size_t n_copied() { return madsim_hip_ctx::SWEEP_REP_WORDS; }
+    void reset() const {
+        sw->n_listed = sw->n_selected = sw->n_settled = sw->n_incomparable = 0;
+        memset(sw->n_runner_by_variant, 0, sizeof sw->n_runner_by_variant);
+        memset(sw->n_differ_from_first, 0, sizeof sw->n_differ_from_first);
+        memset(sw->n_by_mask, 0, sizeof sw->n_by_mask);
+    }
+    int ensure(madsim_hip_ctx::Flight& f, uint64_t width) const { return f.sweep.ensure(std::min(sw->cap, width), f.stream); }      // (no batch lists more)
+    int queue(madsim_hip_ctx::Flight& f, const madsim_result_t* const* res, uint64_t seed_lo, const uint64_t* d_list, uint64_t n, report_word_t* words) const {
+        if (d_list ? madsim_k_launch_sweep_list(res, V, n, d_list, sw->fields, sw->list_rule, words, f.sweep.wcnt, f.sweep.rec, std::min(sw->cap, n), f.stream)
+                   : madsim_k_launch_sweep(res, V, n, seed_lo, sw->fields, sw->list_rule, words, f.sweep.wcnt, f.sweep.rec, std::min(sw->cap, n), f.stream))
+            return fail(MADSIM_E_ARG, "madsim_k_launch_sweep refused the batch's arguments");
+        return 0;
+    }
+    int fold(madsim_hip_ctx::Flight& f, const report_word_t* words, uint64_t n, uint32_t flags, bool& stop) const {
+        if (words[0] > n) return fail(MADSIM_E_HIP, "sweep campaign: a batch reports more selected seeds than it holds");
+        const uint64_t at = sw->n_listed, take = madsim_k_fold_sweep(sw, words, n, nullptr);
+        if (int e = copy_records(sw->records + at, f.sweep.rec.p, take, f.stream)) return e;
+        if ((flags & MADSIM_CAMPAIGN_STOP_AT_SWEEP) && sw->n_selected >= sw->cap) stop = true;
+        return 0;
+    }
+};
+
+// `var`: the V variants (a differential call's two sides; a sweep's, with a NULL config replaced by the default one).  `list`: as in
+// run_campaign_impl — position i of list[0 .. total) for seed0 + i, seed0 = 0; every variant of a batch reads the same slice.
+template <class Form>
+int run_variants_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_sweep_variant_t* var, uint32_t V, uint64_t seed0, uint64_t total, uint64_t batch,
+                      uint32_t in_flight, uint32_t flags, const uint64_t* list, const Form& form) {
     auto t0 = std::chrono::steady_clock::now();
     for (uint32_t v = 0; v < V; v++) { memset(var[v].out, 0, sizeof *var[v].out); var[v].out->first_failing_seed = UINT64_MAX; }
-    sw->n_listed = sw->n_selected = sw->n_settled = sw->n_incomparable = 0;
-    memset(sw->n_runner_by_variant, 0, sizeof sw->n_runner_by_variant);
-    memset(sw->n_differ_from_first, 0, sizeof sw->n_differ_from_first);
-    memset(sw->n_by_mask, 0, sizeof sw->n_by_mask);
-    flags &= MADSIM_CAMPAIGN_STOP_AT_SWEEP | MADSIM_CAMPAIGN_RESOLVE | MADSIM_CAMPAIGN_RESOLVE_ROUNDS_MASK;      // (the other stop flags belong to the other forms)
+    form.reset();
+    flags &= form.stop_flag() | MADSIM_CAMPAIGN_RESOLVE | MADSIM_CAMPAIGN_RESOLVE_ROUNDS_MASK;      // (the other stop flags belong to the other forms)
     const uint32_t R = resolve_rounds(flags);
     ResolveAccount account(ctxs, n_ctx, R);
     madsim_resolve_t& acct = account.a;
+    for (uint32_t v = 0; v < V; v++)                             // (a sweep's variants have passed this before: check_sweep_args)
+        if (int rc = madsim_geo::validate(var[v].w, var[v].cfg, &g_err)) return fail(rc, form.who(v) + g_err);
     int rc;
     if ((rc = check_campaign_range(batch, in_flight, list != nullptr, seed0, total))) return rc;
     if (total == 0) return 0;
     const uint64_t width = std::min(batch, total);
-    if (width >= (1ull << 32)) return fail(MADSIM_E_ARG, "a sweep campaign's batch holds fewer than 2^32 seeds");
+    if (width >= form.max_width) return fail(MADSIM_E_ARG, form.too_wide);
     if (R && width >= (1ull << 30)) return fail(MADSIM_E_ARG, "a resolving campaign's batch holds fewer than 2^30 seeds");
     const uint64_t n_batches = (total + batch - 1) / batch, N = (uint64_t)n_ctx;
-    const uint64_t rec_batch = std::min(sw->cap, width);     // records a flight holds: no batch lists more
     CampaignFlights flights(ctxs, n_ctx);
     if ((rc = flights.setup(n_batches, batch, width, in_flight, list != nullptr,
                             [&](madsim_hip_ctx* c) {
@@ -1807,34 +1718,36 @@ int run_campaign_sweep_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim
                                 for (uint32_t v = 1; v < V; v++) f = std::min(f, c->flights_for(var[v].w, var[v].cfg, var[v].lim, batch));
                                 return f;
                             },
-                            [&](madsim_hip_ctx::Flight& f) { return f.sweep.ensure(V, batch, rec_batch, f.stream); })))
+                            [&](madsim_hip_ctx::Flight& f) {
+                                if (int e = f.variants.ensure(V, batch, f.stream)) return e;
+                                return form.ensure(f, width);
+                            })))
         return rc;
-    constexpr size_t n_words = madsim_hip_ctx::SWEEP_REP_WORDS, at_sweep = 8 * MADSIM_SWEEP_MAX_VARIANTS;
+    constexpr size_t at_init = madsim_hip_ctx::VARIANT_REP_WORDS, at_form = madsim_hip_ctx::VARIANT_FORM_AT;
+    const size_t n_copied = form.n_copied();
     int first_err = 0;
     std::string first_msg;
     bool stop = false;
-    auto results_of = [](madsim_hip_ctx::Flight& f, uint32_t v) -> madsim_result_t* { return v ? f.sweep.out[v - 1] : f.d_out; };
-    auto who = [](uint32_t v) { return "variant " + std::to_string(v) + ": "; };
+    auto results_of = [](madsim_hip_ctx::Flight& f, uint32_t v) -> madsim_result_t* { return v ? f.variants.out[v - 1] : f.d_out; };
     // A batch's report chain in the parts that `queue` puts around the simulation launches and a resolving `harvest` queues again back to
-    // back: the words reset by one device copy, a variant's summary6 over its results, then the sweep kernels, the copy and the `done` event.
+    // back: the words reset by one device copy, a variant's summary6 over its results, then the form's kernels, the copy and the `done` event.
     auto prepare_report = [&](madsim_hip_ctx::Flight& f) -> int {
-        HIP_TRY(hipMemcpyAsync(f.sweep.d_rep, f.sweep.d_rep + n_words, n_words * sizeof(unsigned long long), hipMemcpyDeviceToDevice, f.stream));
+        report_word_t* const d_rep = f.variants.d_rep;
+        HIP_TRY(hipMemcpyAsync(d_rep, d_rep + at_init, n_copied * sizeof(report_word_t), hipMemcpyDeviceToDevice, f.stream));
         return 0;
     };
     auto queue_summary = [&](madsim_hip_ctx::Flight& f, uint32_t v, uint64_t lo, uint64_t n) -> int {
-        if (list) madsim_k_launch_summary6_list(results_of(f, v), n, f.list.d, f.sweep.d_rep + 8 * v, f.stream);
-        else madsim_k_launch_summary6(results_of(f, v), n, seed0 + lo, f.sweep.d_rep + 8 * v, f.stream);
+        if (list) madsim_k_launch_summary6_list(results_of(f, v), n, f.list.d, f.variants.d_rep + 8 * v, f.stream);
+        else madsim_k_launch_summary6(results_of(f, v), n, seed0 + lo, f.variants.d_rep + 8 * v, f.stream);
         HIP_TRY(hipGetLastError());
         return 0;
     };
-    auto queue_sweep = [&](madsim_hip_ctx::Flight& f, uint64_t lo, uint64_t n) -> int {
-        const madsim_result_t* sides[MADSIM_SWEEP_MAX_VARIANTS] = {};
-        for (uint32_t v = 0; v < V; v++) sides[v] = results_of(f, v);
-        if (list ? madsim_k_launch_sweep_list(sides, V, n, f.list.d, sw->fields, sw->list_rule, f.sweep.d_rep + at_sweep, f.sweep.wcnt, f.sweep.rec, std::min(rec_batch, n), f.stream)
-                 : madsim_k_launch_sweep(sides, V, n, seed0 + lo, sw->fields, sw->list_rule, f.sweep.d_rep + at_sweep, f.sweep.wcnt, f.sweep.rec, std::min(rec_batch, n), f.stream))
-            return fail(MADSIM_E_ARG, "madsim_k_launch_sweep refused the batch's arguments");
+    auto queue_form = [&](madsim_hip_ctx::Flight& f, uint64_t lo, uint64_t n) -> int {
+        const madsim_result_t* res[MADSIM_SWEEP_MAX_VARIANTS] = {};
+        for (uint32_t v = 0; v < V; v++) res[v] = results_of(f, v);
+        if (int e = form.queue(f, res, seed0 + lo, list ? f.list.d : nullptr, n, f.variants.d_rep + at_form)) return e;
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(f.sweep.h_rep, f.sweep.d_rep, n_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, f.stream));
+        HIP_TRY(hipMemcpyAsync(f.variants.h_rep, f.variants.d_rep, n_copied * sizeof(report_word_t), hipMemcpyDeviceToHost, f.stream));
         HIP_TRY(hipEventRecord(f.done, f.stream));
         return 0;
     };
@@ -1848,12 +1761,12 @@ int run_campaign_sweep_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim
         if (list && (e = queue_list_slice(f, list, lo, n))) return e;      // (one slice for every variant)
         const uint64_t* const d_list = list ? f.list.d : nullptr;
         for (uint32_t v = 0; v < V; v++) {
-            HIP_TRY(hipEventRecord(f.sweep.v0[v], f.stream));
-            if ((e = c->launch(var[v].w, var[v].cfg, seed0 + lo, n, d_list, var[v].lim, results_of(f, v), f.stream))) return fail(e, who(v) + g_err);
-            HIP_TRY(hipEventRecord(f.sweep.v1[v], f.stream));
+            HIP_TRY(hipEventRecord(f.variants.v0[v], f.stream));
+            if ((e = c->launch(var[v].w, var[v].cfg, seed0 + lo, n, d_list, var[v].lim, results_of(f, v), f.stream))) return fail(e, form.who(v) + g_err);
+            HIP_TRY(hipEventRecord(f.variants.v1[v], f.stream));
             if ((e = queue_summary(f, v, lo, n))) return e;
         }
-        return queue_sweep(f, lo, n);
+        return queue_form(f, lo, n);
     };
     auto harvest = [&](uint64_t k) -> int {
         madsim_hip_ctx* c = ctxs[k % N];
@@ -1863,44 +1776,37 @@ int run_campaign_sweep_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim
         HIP_TRY(hipEventSynchronize(f.done));
         if (first_err || stop) return 0;                        // (draining after an error, or a batch launched beyond the stopping one)
         const uint64_t lo = k * batch, n = std::min(batch, total - lo);
-        const unsigned long long* const h = f.sweep.h_rep;
+        const report_word_t* const h = f.variants.h_rep;
         float ms[MADSIM_SWEEP_MAX_VARIANTS] = {};
-        for (uint32_t v = 0; v < V; v++) HIP_TRY(hipEventElapsedTime(&ms[v], f.sweep.v0[v], f.sweep.v1[v]));
+        for (uint32_t v = 0; v < V; v++) HIP_TRY(hipEventElapsedTime(&ms[v], f.variants.v0[v], f.variants.v1[v]));
         unsigned long long runner_before[MADSIM_SWEEP_MAX_VARIANTS] = {}, any_runner = 0;
         for (uint32_t v = 0; v < V; v++) any_runner += runner_before[v] = h[8 * v + 5];
-        if (R && any_runner) {                                  // runner verdicts in a variant: settle them under that variant's own limits, sweep again
+        if (R && any_runner) {                                  // runner verdicts in a variant: settle them under that variant's own limits, report again
             bool ran = false;
             for (uint32_t v = 0; v < V; v++) {                  // (one after the other on the flight's stream: they share its re-run scratch)
                 if (!runner_before[v]) continue;
                 double rerun_ms = 0.0;
                 if ((e = resolve_results(c, f, var[v].w, var[v].cfg, var[v].lim, results_of(f, v), seed0 + lo, list ? f.list.d : nullptr, n, R, acct, &rerun_ms,
                                          &ran)))
-                    return fail(e, who(v) + g_err);
+                    return fail(e, form.who(v) + g_err);
                 acct.rerun_kernel_ms += rerun_ms; var[v].out->kernel_ms += rerun_ms;
             }
             if (ran) {
                 if ((e = prepare_report(f))) return e;
                 for (uint32_t v = 0; v < V; v++) if ((e = queue_summary(f, v, lo, n))) return e;
-                if ((e = queue_sweep(f, lo, n))) return e;
+                if ((e = queue_form(f, lo, n))) return e;
                 HIP_TRY(hipEventSynchronize(f.done));
                 for (uint32_t v = 0; v < V; v++) acct.n_resolved += runner_before[v] - h[8 * v + 5];
             }
         }
         for (uint32_t v = 0; v < V; v++) fold_summary(var[v].out, h + 8 * v, n, ms[v]);
-        if (h[at_sweep] > n) return fail(MADSIM_E_HIP, "sweep campaign: a batch reports more selected seeds than it holds");
-        // the batch's records, as many as the list still takes (the stream is idle: its `done` has passed, and it takes no launch before this returns)
-        const uint64_t at = sw->n_listed, take = madsim_k_fold_sweep(sw, h + at_sweep, n, nullptr);
-        if (take) {
-            HIP_TRY(hipMemcpyAsync(sw->records + at, f.sweep.rec, take * sizeof(madsim_sweep_record_t), hipMemcpyDeviceToHost, f.stream));
-            HIP_TRY(hipStreamSynchronize(f.stream));
-        }
-        if ((flags & MADSIM_CAMPAIGN_STOP_AT_SWEEP) && sw->n_selected >= sw->cap) stop = true;
-        return 0;
+        return form.fold(f, h + at_form, n, flags, stop);
     };
     const uint64_t launched = pump_batches(ctxs, n_ctx, n_batches, flights.F, stop, first_err, first_msg, queue, harvest);
     for (uint32_t v = 0; v < V; v++) { var[v].out->batches_launched = launched; var[v].out->wall_s = since(t0); }
     return first_err ? fail(first_err, first_msg) : 0;
 }
+}  // extern "C++"
 }  // namespace
 
 int madsim_hip_ctx_run_campaign(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total,
@@ -2040,8 +1946,8 @@ int madsim_hip_ctx_run_campaign_diff(madsim_hip_ctx_t* c, const madsim_workload_
     if (int rc = check_diff_args(outA, outB, diff, in_flight, flags)) return rc;
     CTX_ENTER(c);
     madsim_hip_ctx* one[1] = {c};
-    const DiffSide side[2] = {{wA, cfgA, limA, outA}, {wB, cfgB, limB, outB}};
-    return run_campaign_diff_impl(one, 1, side, seed0, total, batch, in_flight, flags, diff);
+    const madsim_sweep_variant_t side[2] = {{wA, cfgA, limA, outA}, {wB, cfgB, limB, outB}};
+    return run_variants_impl(one, 1, side, 2, seed0, total, batch, in_flight, flags, nullptr, PairForm{diff, nullptr});
 }
 
 int madsim_hip_run_campaign_diff_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_workload_t* wA, const madsim_config_t* cfgA,
@@ -2051,8 +1957,8 @@ int madsim_hip_run_campaign_diff_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx,
     if (int rc = check_diff_args(outA, outB, diff, in_flight, flags)) return rc;
     std::vector<std::unique_lock<std::mutex>> locks;
     if (int rc = lock_contexts(ctxs, n_ctx, "run_campaign_diff_multi", locks)) return rc;
-    const DiffSide side[2] = {{wA, cfgA, limA, outA}, {wB, cfgB, limB, outB}};
-    return run_campaign_diff_impl(ctxs, n_ctx, side, seed0, total, batch, in_flight, flags, diff);
+    const madsim_sweep_variant_t side[2] = {{wA, cfgA, limA, outA}, {wB, cfgB, limB, outB}};
+    return run_variants_impl(ctxs, n_ctx, side, 2, seed0, total, batch, in_flight, flags, nullptr, PairForm{diff, nullptr});
 }
 
 // ---- list campaigns: every campaign form over an explicit seed list ----------------------------------------------------------------
@@ -2103,11 +2009,11 @@ int madsim_hip_ctx_run_seeds_campaign_diff(madsim_hip_ctx_t* c, const madsim_wor
                                            madsim_campaign_t* outA, madsim_campaign_t* outB, madsim_diff_t* diff) {
     if (int rc = check_seed_list(seeds, n)) return rc;
     if (int rc = check_diff_args(outA, outB, diff, in_flight, flags)) return rc;
-    const DiffSide side[2] = {{wA, cfgA, limA, outA}, {wB, cfgB, limB, outB}};
-    if (n == 0 && (!c || c->device < 0)) return run_campaign_diff_impl(nullptr, 0, side, 0, 0, batch, in_flight, flags, diff);      // (no device needed)
+    const madsim_sweep_variant_t side[2] = {{wA, cfgA, limA, outA}, {wB, cfgB, limB, outB}};
+    if (n == 0 && (!c || c->device < 0)) return run_variants_impl(nullptr, 0, side, 2, 0, 0, batch, in_flight, flags, nullptr, PairForm{diff, nullptr});      // (no device needed)
     CTX_ENTER(c);
     madsim_hip_ctx* one[1] = {c};
-    return run_campaign_diff_impl(one, 1, side, 0, n, batch, in_flight, flags, diff, n ? seeds : nullptr);
+    return run_variants_impl(one, 1, side, 2, 0, n, batch, in_flight, flags, n ? seeds : nullptr, PairForm{diff, nullptr});
 }
 
 int madsim_hip_run_seeds_campaign_diff_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_workload_t* wA, const madsim_config_t* cfgA,
@@ -2118,8 +2024,8 @@ int madsim_hip_run_seeds_campaign_diff_multi(madsim_hip_ctx_t* const* ctxs, int 
     if (int rc = check_diff_args(outA, outB, diff, in_flight, flags)) return rc;
     std::vector<std::unique_lock<std::mutex>> locks;
     if (int rc = lock_contexts(ctxs, n_ctx, "run_seeds_campaign_diff_multi", locks)) return rc;
-    const DiffSide side[2] = {{wA, cfgA, limA, outA}, {wB, cfgB, limB, outB}};
-    return run_campaign_diff_impl(ctxs, n_ctx, side, 0, n, batch, in_flight, flags, diff, n ? seeds : nullptr);
+    const madsim_sweep_variant_t side[2] = {{wA, cfgA, limA, outA}, {wB, cfgB, limB, outB}};
+    return run_variants_impl(ctxs, n_ctx, side, 2, 0, n, batch, in_flight, flags, n ? seeds : nullptr, PairForm{diff, nullptr});
 }
 
 // ---- paired campaigns: per-seed metric deltas between two variants ------------------------------------------------------------------
@@ -2148,8 +2054,8 @@ int madsim_hip_ctx_run_paired_campaign(madsim_hip_ctx_t* c, const madsim_workloa
     if (int rc = check_paired_args(outA, outB, diff, pr, in_flight, flags)) return rc;
     CTX_ENTER(c);
     madsim_hip_ctx* one[1] = {c};
-    const DiffSide side[2] = {{wA, cfgA, limA, outA}, {wB, cfgB, limB, outB}};
-    return run_campaign_diff_impl(one, 1, side, seed0, total, batch, in_flight, flags, diff, nullptr, pr);
+    const madsim_sweep_variant_t side[2] = {{wA, cfgA, limA, outA}, {wB, cfgB, limB, outB}};
+    return run_variants_impl(one, 1, side, 2, seed0, total, batch, in_flight, flags, nullptr, PairForm{diff, pr});
 }
 
 int madsim_hip_run_paired_campaign_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_workload_t* wA, const madsim_config_t* cfgA,
@@ -2159,8 +2065,8 @@ int madsim_hip_run_paired_campaign_multi(madsim_hip_ctx_t* const* ctxs, int n_ct
     if (int rc = check_paired_args(outA, outB, diff, pr, in_flight, flags)) return rc;
     std::vector<std::unique_lock<std::mutex>> locks;
     if (int rc = lock_contexts(ctxs, n_ctx, "run_paired_campaign_multi", locks)) return rc;
-    const DiffSide side[2] = {{wA, cfgA, limA, outA}, {wB, cfgB, limB, outB}};
-    return run_campaign_diff_impl(ctxs, n_ctx, side, seed0, total, batch, in_flight, flags, diff, nullptr, pr);
+    const madsim_sweep_variant_t side[2] = {{wA, cfgA, limA, outA}, {wB, cfgB, limB, outB}};
+    return run_variants_impl(ctxs, n_ctx, side, 2, seed0, total, batch, in_flight, flags, nullptr, PairForm{diff, pr});
 }
 
 int madsim_hip_ctx_run_seeds_campaign_paired(madsim_hip_ctx_t* c, const madsim_workload_t* wA, const madsim_config_t* cfgA, const madsim_limits_t* limA,
@@ -2169,11 +2075,11 @@ int madsim_hip_ctx_run_seeds_campaign_paired(madsim_hip_ctx_t* c, const madsim_w
                                              madsim_campaign_t* outA, madsim_campaign_t* outB, madsim_diff_t* diff, madsim_paired_t* pr) {
     if (int rc = check_seed_list(seeds, n)) return rc;
     if (int rc = check_paired_args(outA, outB, diff, pr, in_flight, flags)) return rc;
-    const DiffSide side[2] = {{wA, cfgA, limA, outA}, {wB, cfgB, limB, outB}};
-    if (n == 0 && (!c || c->device < 0)) return run_campaign_diff_impl(nullptr, 0, side, 0, 0, batch, in_flight, flags, diff, nullptr, pr);      // (no device needed)
+    const madsim_sweep_variant_t side[2] = {{wA, cfgA, limA, outA}, {wB, cfgB, limB, outB}};
+    if (n == 0 && (!c || c->device < 0)) return run_variants_impl(nullptr, 0, side, 2, 0, 0, batch, in_flight, flags, nullptr, PairForm{diff, pr});      // (no device needed)
     CTX_ENTER(c);
     madsim_hip_ctx* one[1] = {c};
-    return run_campaign_diff_impl(one, 1, side, 0, n, batch, in_flight, flags, diff, n ? seeds : nullptr, pr);
+    return run_variants_impl(one, 1, side, 2, 0, n, batch, in_flight, flags, n ? seeds : nullptr, PairForm{diff, pr});
 }
 
 int madsim_hip_run_seeds_campaign_paired_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_workload_t* wA, const madsim_config_t* cfgA,
@@ -2185,8 +2091,8 @@ int madsim_hip_run_seeds_campaign_paired_multi(madsim_hip_ctx_t* const* ctxs, in
     if (int rc = check_paired_args(outA, outB, diff, pr, in_flight, flags)) return rc;
     std::vector<std::unique_lock<std::mutex>> locks;
     if (int rc = lock_contexts(ctxs, n_ctx, "run_seeds_campaign_paired_multi", locks)) return rc;
-    const DiffSide side[2] = {{wA, cfgA, limA, outA}, {wB, cfgB, limB, outB}};
-    return run_campaign_diff_impl(ctxs, n_ctx, side, 0, n, batch, in_flight, flags, diff, n ? seeds : nullptr, pr);
+    const madsim_sweep_variant_t side[2] = {{wA, cfgA, limA, outA}, {wB, cfgB, limB, outB}};
+    return run_variants_impl(ctxs, n_ctx, side, 2, 0, n, batch, in_flight, flags, n ? seeds : nullptr, PairForm{diff, pr});
 }
 
 // ---- sweep campaigns: up to eight variants over one seed set ------------------------------------------------------------------------
@@ -2227,10 +2133,10 @@ int madsim_hip_ctx_run_sweep_campaign(madsim_hip_ctx_t* c, const madsim_sweep_va
     std::vector<madsim_sweep_variant_t> var;
     if (int rc = check_sweep_args(variants, n_variants, seed0, total, seeds, in_flight, flags, sweep, var)) return rc;
     if (total == 0 && (!c || c->device < 0))                     // nothing to run needs no device: the reports of an empty range, and 0
-        return run_campaign_sweep_impl(nullptr, 0, var.data(), n_variants, 0, 0, batch, in_flight, flags, sweep, nullptr);
+        return run_variants_impl(nullptr, 0, var.data(), n_variants, 0, 0, batch, in_flight, flags, nullptr, SweepForm{sweep, n_variants});
     CTX_ENTER(c);
     madsim_hip_ctx* one[1] = {c};
-    return run_campaign_sweep_impl(one, 1, var.data(), n_variants, seed0, total, batch, in_flight, flags, sweep, total ? seeds : nullptr);
+    return run_variants_impl(one, 1, var.data(), n_variants, seed0, total, batch, in_flight, flags, total ? seeds : nullptr, SweepForm{sweep, n_variants});
 }
 
 int madsim_hip_run_sweep_campaign_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_sweep_variant_t* variants, uint32_t n_variants,
@@ -2240,7 +2146,7 @@ int madsim_hip_run_sweep_campaign_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx
     if (int rc = check_sweep_args(variants, n_variants, seed0, total, seeds, in_flight, flags, sweep, var)) return rc;
     std::vector<std::unique_lock<std::mutex>> locks;
     if (int rc = lock_contexts(ctxs, n_ctx, "run_sweep_campaign_multi", locks)) return rc;
-    return run_campaign_sweep_impl(ctxs, n_ctx, var.data(), n_variants, seed0, total, batch, in_flight, flags, sweep, total ? seeds : nullptr);
+    return run_variants_impl(ctxs, n_ctx, var.data(), n_variants, seed0, total, batch, in_flight, flags, total ? seeds : nullptr, SweepForm{sweep, n_variants});
 }
 
 // ---- v1 entry points: wrappers on the process-default context ------------------------------------------------------------

@@ -1,5 +1,5 @@
 """A direct driver for the differential campaign's report kernels: the launcher libmadsim_hip.so exports (madsim_k_launch_diff;
-csrc/sim_kernel.h) over two madsim_result_t arrays of the caller's making, with the buffers prepared as run_campaign_diff_impl prepares them.
+csrc/sim_kernel.h) over two madsim_result_t arrays of the caller's making, with the buffers prepared as run_variants_impl prepares them.
 Test-only: tests/test_diff_kernels.py feeds it synthetic arrays and holds every word, record and wave count against tests/diff_ref.py.
 
 Every buffer is checked on the host against the size the launcher demands before anything is launched; every buffer a launch writes is

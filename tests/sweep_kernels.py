@@ -1,5 +1,5 @@
 """A direct driver for the sweep campaign's report kernels: the launchers libmadsim_hip.so exports (madsim_k_launch_sweep and its _list
-form; csrc/sim_kernel.h) over V madsim_result_t arrays of the caller's making, with the buffers prepared as run_campaign_sweep_impl prepares
+form; csrc/sim_kernel.h) over V madsim_result_t arrays of the caller's making, with the buffers prepared as run_variants_impl prepares
 them.  Test-only: tests/test_sweep_kernels.py feeds it synthetic arrays and holds every word, record and wave count against tests/sweep_ref.py.
 
 Every buffer is checked on the host against the size the launcher demands before anything is launched; every buffer a launch writes is

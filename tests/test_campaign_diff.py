@@ -178,7 +178,7 @@ def cut(a, b, seed0, fields, batch):
 
 def fold(a, b, seed0, fields, cap, batch, copy_here=False, batches=None):
     """madsim_k_fold_diff over the device-format words (and records) of `a`, `b` cut into batches of `batch` (or over `batches`, a cut() made
-    earlier), from the state run_campaign_diff_impl starts with; (answer, the `take` of every batch).  copy_here: the fold is given no
+    earlier), from the state run_variants_impl starts with; (answer, the `take` of every batch).  copy_here: the fold is given no
     records and the caller copies them, as the library does from device memory."""
     L = _fold_lib()
     arr = np.full(cap + 1, 0xA5, dtype=np.uint8).repeat(104).view(A.DIFF_RECORD_DTYPE)             # one record of guard behind the caller's array

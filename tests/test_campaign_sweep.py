@@ -182,7 +182,7 @@ def _fold_lib():
 
 
 def fold(res, seeds, fields, rule, cap, edges, copy_here=False):
-    """madsim_k_fold_sweep over the device-format words (and records) of `res` cut at `edges`, from the state run_campaign_sweep_impl starts
+    """madsim_k_fold_sweep over the device-format words (and records) of `res` cut at `edges`, from the state run_variants_impl starts
     with; (answer, the `take` of every batch).  copy_here: the fold is given no records and the caller copies them, as the library does
     from device memory."""
     L = _fold_lib()

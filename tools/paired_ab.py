@@ -30,7 +30,7 @@ from madsim_amd import _abi as A  # noqa: E402
 from madsim_amd import workload as W  # noqa: E402
 
 BATCH, SEED0, LISTED = 65536, 1, 64
-DIFF_REP_WORDS, PAIRED_WORDS, PAIRED_TOP_WORDS = 16 + 74, 1466, 8 * 16 * 3      # csrc/madsim_hip.cpp, csrc/sim_kernel.h
+DIFF_REP_WORDS, PAIRED_WORDS, PAIRED_TOP_WORDS = 64 + 74, 1466, 8 * 16 * 3      # csrc/madsim_hip.cpp, csrc/sim_kernel.h
 
 
 def main():
