@@ -1010,7 +1010,8 @@ int madsim_hip_ctx_campaign_resolved(madsim_hip_ctx_t* ctx, madsim_resolve_t* ou
  * campaign runs under — which limits a resolved seed needed, and what to hand madsim_hip_run_batch to reproduce r_j(s).  One round:
  * lanes_per_wave = 0; MADSIM_STATE_COMPACT becomes MADSIM_STATE_AUTO and MADSIM_STATE_NARROW_HEAP is cleared; heap_lds_slots keeps
  * its value (0 becomes 8); heap_spill_slots, max_tasks, mbox_regs, mbox_msgs, max_conns and chan_queue double from their value or,
- * from 0, from 32, n_progs + 8, 2, 2, 4 and 2, up to 2^20, 254, 255, 255, 127 and 15; max_steps (0 = 2^24) grows 16-fold up to
+ * from 0, from 32, n_progs + 8, 2, 2, 4 and 2, up to 2^20, 254, 255, 255 (mbox_msgs of a workload without extended ops: 127, the most its
+ * builds take), 127 and 15; max_steps (0 = 2^24) grows 16-fold up to
  * max_steps_ceiling (0 = 2^28, and never below the first pass's cap).  MADSIM_E_ARG: w or out NULL, rounds above 64. */
 int madsim_hip_grow_limits(const madsim_workload_t* w, const madsim_limits_t* lim, uint32_t rounds, madsim_limits_t* out);
 

@@ -524,6 +524,16 @@ uint64_t step_ceiling(const madsim_limits_t& L) {
     const uint64_t first = L.max_steps ? L.max_steps : (1u << 24);
     return c < first ? first : c;
 }
+// The ceiling of mbox_msgs for this workload: 127 without extended ops (the base-op mailbox header keeps 7 bits, and make_geometry refuses
+// more), MADSIM_MAX_MBOX_MSGS with them.  Which ops a workload uses is read off the parameter block of its geometry under the default
+// limits — the op classes do not depend on the limits, and they are set before anything a limit could make fail.
+uint32_t mbox_msgs_ceiling(const madsim_workload_t* w) {
+    Geo G;
+    std::string ignored;
+    const madsim_config_t cfg = madsim_geo::probe_config();
+    madsim_geo::make_geometry(madsim_geo::Device(), w, &cfg, nullptr, 64, &G, &ignored);
+    return G.P.lifecycle ? MADSIM_MAX_MBOX_MSGS : 127u;
+}
 void grow(madsim_limits_t& L, const madsim_workload_t* w, bool any_ovf, bool any_steps) {
     auto dbl = [](uint32_t v, uint32_t dflt, uint32_t cap) { uint32_t x = (v == 0 || v == MADSIM_LIMIT_NONE) ? dflt : v; x *= 2; return x > cap ? cap : x; };
     L.lanes_per_wave = 0;
@@ -537,7 +547,7 @@ void grow(madsim_limits_t& L, const madsim_workload_t* w, bool any_ovf, bool any
         L.heap_spill_slots = dbl(L.heap_spill_slots, 32, 1u << 20);
         L.max_tasks = dbl(L.max_tasks, w->n_progs + 8, 254);
         L.mbox_regs = dbl(L.mbox_regs, 2, 255);
-        L.mbox_msgs = dbl(L.mbox_msgs, 2, 255);
+        L.mbox_msgs = dbl(L.mbox_msgs, 2, mbox_msgs_ceiling(w));      // (255 for a base-op workload fits no build: MADSIM_E_LIMITS would take the whole call)
         L.max_conns = dbl(L.max_conns, 4, 127);
         L.chan_queue = dbl(L.chan_queue, 2, 15);
     }

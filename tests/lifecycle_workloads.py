@@ -956,81 +956,259 @@ def narrow_heap_forty_datagrams_in_flight():
     return wl.build(), cfg, lim
 
 
-def model_ceiling_workloads():
-    """One workload per ceiling of the device runner's workload MODEL (include/madsim_hip.h MADSIM_UNSUPPORTED): (name, workload, limits,
-    the oracle's event bit — oracle/madsim_oracle.h MADSIM_ORACLE_ME_*).  The reference itself has none of these ceilings."""
-    from madsim_amd import _abi as A
-    ws = []
+# ---- the ceilings of the device runner's workload MODEL (include/madsim_hip.h MADSIM_UNSUPPORTED) ---------------------------------------
+# One builder per ceiling, taking the COUNT: the same construction gives the workload that stands AT the ceiling (the device must answer with
+# the oracle's bytes) and the one that goes ONE OVER it (MADSIM_UNSUPPORTED on both sides).  -> (workload, limits): the capacities the
+# at-ceiling run needs (None = the defaults); the oracle has no capacities, so they never change its answer.
+
+def _limits(**kw):
+    lim = A.Limits()
+    for k, v in kw.items():
+        setattr(lim, k, v)
+    return lim
+
+
+def _ipvs_servers(n_servers):
+    """A service of `n_servers` servers (the first six from the table, the rest added at run time), then called through: seven datagrams to the
+    virtual address go round the six servers and wrap to the first."""
     wl = W.WorkloadBuilder()
-    n = wl.create_node()
-    v = wl.virtual_addr(1, 80); a = wl.addr(n, 1)
-    svc = wl.ipvs_service(v, [a] * 6)
-    t = wl.task(n); t.sleep(ms=1); t.ipvs_add_server(svc, a)
-    m = wl.main(); m.spawn(t); m.join(t)
-    ws.append(("ipvs_seventh_server", wl.build(), None, 32))
-    wl = W.WorkloadBuilder()                               # nine clients dial one listener that never accepts
+    n1, n2 = wl.create_node(), wl.create_node()
+    srv = [wl.addr(n1, 1 + k) for k in range(6)]
+    vip, me = wl.virtual_addr(1, 80), wl.addr(n2, 1)
+    svc = wl.ipvs_service(vip, srv[:min(n_servers, 6)])
+    rx = wl.task(n1)
+    for a in srv: rx.bind(a)
+    for a in srv + srv[:1]: rx.recv_from(a, 1); rx.trace_val()
+    op = wl.task(n2); op.bind(me); op.sleep(ms=1)
+    for _ in range(n_servers - 6): op.ipvs_add_server(svc, srv[0])
+    for k in range(7): op.send_to(me, vip, 1, 10 + k); op.sleep(ms=15)
+    m = wl.main(); m.spawn(rx); m.spawn(op); m.join(rx); m.join(op)
+    return wl.build(), _limits(mbox_regs=4, mbox_msgs=4)
+
+
+def _dialling_clients(n_clients):
+    """`n_clients` clients dial one listener that never accepts: they wait in its accept1 queue."""
+    wl = W.WorkloadBuilder()
     ns, nc = wl.create_node(), wl.create_node()
     asv = wl.addr(ns, 1)
     srv = wl.task(ns); srv.bind(asv); srv.sleep(secs=5); srv.done()
     cls = []
-    for i in range(9):
+    for i in range(n_clients):
         ac = wl.addr(nc, 2 + i)
         c = wl.task(nc); c.bind(ac); c.sleep(ms=10); c.connect1(ac, asv); c.sleep(secs=1); c.done(); cls.append(c)
     m = wl.main(); m.spawn(srv)
     for c in cls: m.spawn(c)
     for c in cls: m.join(c)
-    lim = A.Limits(); lim.max_conns, lim.max_tasks = 16, 16
-    ws.append(("ninth_queued_connection", wl.build(), lim, 16))
-    wl = W.WorkloadBuilder()                               # panic!("{}", flag + 7) with flag = 300 > panic_dyn_max
-    n = wl.create_node(restart_on_panic_matching=("1",))
-    t = wl.task(n); t.flag_add(0, 300); t.panic_with_flag(0, 7)
-    m = wl.main(); m.spawn(t); m.join(t, expect_err=True)
-    ws.append(("panic_dyn_beyond_max", wl.build(), None, 64))
-    wl = W.WorkloadBuilder()                               # a spawn storm: 300 sleepers alive at once (the layout's 8-bit task slot holds 254)
+    return wl.build(), _limits(max_conns=16, max_tasks=16)
+
+
+def _spawn_storm(n_sleepers):
+    """A spawn storm: `n_sleepers` sleepers alive at once beside the main task (the layout's 8-bit task slot holds 254 live tasks)."""
+    wl = W.WorkloadBuilder()
     n = wl.create_node()
     sl = wl.task(n); sl.sleep(secs=1); sl.done()
-    m = wl.main(); m.set(0, 300); top = m.label(); m.spawn(sl); m.djnz(0, top); m.sleep(secs=2); m.done()
-    lim = A.Limits(); lim.max_tasks = 254
-    ws.append(("spawn_storm_255_tasks", wl.build(), lim, 1))
-    wl = W.WorkloadBuilder()                               # 3 x 86 timed-out receives on one socket: 255 dead registrations stay, the 256th has no room
+    m = wl.main(); m.set(0, n_sleepers); top = m.label(); m.spawn(sl); m.djnz(0, top); m.sleep(secs=2); m.done()
+    return wl.build(), _limits(max_tasks=254, heap_lds_slots=8, heap_spill_slots=1024)      # (every sleeper holds a timer)
+
+
+def _dead_registrations(n_receives):
+    """`n_receives` timed-out receives on one socket, dealt to three tasks: every one leaves a dead registration (endpoint.rs:353-362: the Vec
+    keeps them)."""
+    wl = W.WorkloadBuilder()
     n = wl.create_node()
     a = wl.addr(n, 1)
     ts = []
     for i in range(3):
         t = wl.task(n)
         if i == 0: t.bind(a)
-        else: t.sleep(us=300 * i)
-        t.set(0, 86); top = t.label(); t.recv_from_timeout(a, 1, ms=1); t.djnz(0, top); t.sleep(secs=1); t.done(); ts.append(t)
+        else: t.sleep(ms=20, us=300 * i)                     # (20 ms: the bind's random delay is over — a bind clears the registrations made before it)
+        t.set(0, (n_receives + 2 - i) // 3); top = t.label(); t.recv_from_timeout(a, 1, ms=1); t.djnz(0, top); t.sleep(secs=1); t.done(); ts.append(t)
     m = wl.main()
     for t in ts: m.spawn(t)
     for t in ts: m.join(t)
-    lim = A.Limits(); lim.mbox_regs = 255
-    ws.append(("registrations_256", wl.build(), lim, 2))
-    wl = W.WorkloadBuilder()                               # ONE task, 129 timed-out receives: its 8-bit receive sequence number wraps onto a dead registration
+    return wl.build(), _limits(mbox_regs=255)
+
+
+def _receives_of_one_task(n_receives):
+    """ONE task, `n_receives` timed-out receives.  Its receive sequence number goes up by two per timed-out receive (once when it registers,
+    once when the timeout drops the receive), so the 129th registers with 257: the 8 bits the registration word keeps are the first one's,
+    whose dead registration is still in the list."""
+    wl = W.WorkloadBuilder()
     n = wl.create_node()
     a = wl.addr(n, 1)
-    t = wl.task(n); t.bind(a); t.set(0, 129); top = t.label(); t.recv_from_timeout(a, 1, ms=1); t.djnz(0, top); t.done()
+    t = wl.task(n); t.bind(a); t.set(0, n_receives); top = t.label(); t.recv_from_timeout(a, 1, ms=1); t.djnz(0, top); t.done()
     m = wl.main(); m.spawn(t); m.join(t)
-    lim = A.Limits(); lim.mbox_regs = 255
-    ws.append(("rxseq_wraps_onto_dead_registration", wl.build(), lim, 4))
-    wl = W.WorkloadBuilder()                               # 16 payloads queued in one channel direction (the receiver never receives)
+    return wl.build(), _limits(mbox_regs=255)
+
+
+def _queued_payloads(n_payloads):
+    """`n_payloads` payloads queued in one channel direction (the receiver never receives)."""
+    wl = W.WorkloadBuilder()
     ns, nc = wl.create_node(), wl.create_node()
     asv, acl = wl.addr(ns, 1), wl.addr(nc, 1)
     srv = wl.task(ns); srv.bind(asv); srv.accept1(asv); srv.sleep(secs=30); srv.done()
-    cl = wl.task(nc); cl.bind(acl); cl.sleep(ms=10); cl.connect1(acl, asv); cl.set(0, 16); top = cl.label(); cl.chan_send(7); cl.djnz(0, top); cl.done()
+    cl = wl.task(nc); cl.bind(acl); cl.sleep(ms=10); cl.connect1(acl, asv); cl.set(0, n_payloads); top = cl.label(); cl.chan_send(7); cl.djnz(0, top); cl.done()
     m = wl.main(); m.spawn(srv); m.spawn(cl); m.join(cl)
-    lim = A.Limits(); lim.chan_queue = 15
-    ws.append(("sixteenth_queued_payload", wl.build(), lim, 8))
+    return wl.build(), _limits(chan_queue=15)
 
-    wl = W.WorkloadBuilder()                               # 256 datagrams for a bound socket nobody receives from: the 256th has no room in the model's mailbox
+
+def _queued_messages(n_datagrams, extended_op=True):
+    """`n_datagrams` datagrams for a bound socket nobody receives from.  extended_op: the owner begins with a timed-out receive of another tag —
+    an extended op, so the mailbox header counts to 255; without it the program is base ops only and the header keeps 7 bits (127)."""
+    wl = W.WorkloadBuilder()
     n1, n2 = wl.create_node(), wl.create_node()
     a1, a2 = wl.addr(n1, 1), wl.addr(n2, 1)
-    rx = wl.task(n2); rx.bind(a2); rx.recv_from_timeout(a2, 9, ms=1); rx.sleep(secs=30); rx.done()      # (an extended op: mailboxes of 255)
-    tx = wl.task(n1); tx.bind(a1); tx.sleep(ms=5); tx.set(0, 256); top = tx.label(); tx.send_to(a1, a2, 1, 9); tx.djnz(0, top); tx.sleep(ms=50); tx.done()
+    rx = wl.task(n2); rx.bind(a2)
+    if extended_op: rx.recv_from_timeout(a2, 9, ms=1)
+    rx.sleep(secs=30); rx.done()
+    tx = wl.task(n1); tx.bind(a1); tx.sleep(ms=5); tx.set(0, n_datagrams); top = tx.label(); tx.send_to(a1, a2, 1, 9); tx.djnz(0, top); tx.sleep(ms=50); tx.done()
     m = wl.main(); m.spawn(rx); m.spawn(tx); m.join(tx)
-    lim = A.Limits(); lim.mbox_msgs = 255
-    ws.append(("queued_messages_256", wl.build(), lim, 4096))
+    return wl.build(), _limits(mbox_msgs=255 if extended_op else 127)
+
+
+def _live_connections(n_conns):
+    """`n_conns` connections alive at once: two clients with an Endpoint each dial one listener in turn and park every connection in a task of
+    its own (`spawn(async move { tx, rx })`); the listener accepts each — dropping the pair it accepted before, which leaves the connection alive
+    through the client's end.  Two Endpoints, so neither holds more than 64 connection ends (the guard ceiling is another workload's)."""
+    wl = W.WorkloadBuilder()
+    ns, nc = wl.create_node(), wl.create_node()
+    asv = wl.addr(ns, 1)
+    srv = wl.task(ns); srv.bind(asv); top = srv.label(); srv.accept1(asv); srv.jmp(top)
+    hold = wl.task(nc); hold.sleep(secs=2); hold.done()
+    cls = []
+    for i, cnt in enumerate(((n_conns + 1) // 2, n_conns // 2)):
+        ac = wl.addr(nc, 1 + i)
+        c = wl.task(nc); c.bind(ac); c.sleep(ms=10, us=500 * i); c.set(0, cnt); top = c.label()
+        c.connect1(ac, asv); c.assert_val(0); c.spawn(hold, move_conn=True); c.sleep(ms=1); c.djnz(0, top); c.done(); cls.append(c)
+    m = wl.main(); m.spawn(srv)
+    for c in cls: m.spawn(c)
+    for c in cls: m.join(c)
+    m.sleep(secs=3); m.done()
+    return wl.build(), _limits(max_conns=127, max_tasks=160, heap_lds_slots=8, heap_spill_slots=512)
+
+
+def _guards_of_one_endpoint(n_ends):
+    """`n_ends` connection ends holding ONE Endpoint's BindGuard: the Endpoint dials itself and accepts (both ends clone its guard,
+    endpoint.rs:181-190, 203-210), each end parked in a task of its own — n_ends / 2 connections, far below the connection ceiling."""
+    wl = W.WorkloadBuilder()
+    n = wl.create_node()
+    a = wl.addr(n, 1)
+    hold = wl.task(n); hold.sleep(secs=2); hold.done()
+    t = wl.task(n); t.bind(a); t.set(0, n_ends // 2); top = t.label()
+    t.connect1(a, a); t.assert_val(0); t.spawn(hold, move_conn=True); t.accept1(a); t.spawn(hold, move_conn=True); t.djnz(0, top)
+    if n_ends & 1: t.connect1(a, a); t.assert_val(0); t.spawn(hold, move_conn=True)
+    t.sleep(secs=3); t.done()
+    m = wl.main(); m.spawn(t); m.join(t)
+    return wl.build(), _limits(max_conns=127, max_tasks=160, heap_lds_slots=8, heap_spill_slots=512)
+
+
+def _instances_of_one_slot(n_instances):
+    """`n_instances` instances of one task slot, one after the other (spawn, join: the lowest free slot is the same one every time), around a
+    socket with a lingering timed-out registration: the first and the last instance each make one receive (receive count 1) that times out,
+    the ones between only finish.  With 257 the slot's generation byte has come round and the last receive's registration word equals the
+    dead one's."""
+    wl = W.WorkloadBuilder()
+    n = wl.create_node()
+    a = wl.addr(n, 1)
+    own = wl.task(n); own.bind(a); own.sleep(secs=30); own.done()
+    rcv = wl.task(n); rcv.recv_from_timeout(a, 1, ms=1); rcv.done()
+    idle = wl.task(n); idle.done()
+    m = wl.main(); m.spawn(own); m.sleep(ms=20); m.spawn(rcv); m.join(rcv)        # (20 ms: the bind's random delay is over)
+    m.set(0, n_instances - 2); top = m.label(); m.spawn(idle); m.join(idle); m.djnz(0, top)
+    m.spawn(rcv); m.join(rcv); m.done()
+    return wl.build(), _limits(mbox_regs=4)
+
+
+def model_ceiling_workloads():
+    """One workload per ceiling of the device runner's workload MODEL, ONE OVER it: (name, workload, limits, the oracle's event bit —
+    oracle/madsim_oracle.h MADSIM_ORACLE_ME_*).  The reference itself has none of these ceilings."""
+    ws = [("ipvs_seventh_server", *_ipvs_servers(7), 32),
+          ("ninth_queued_connection", *_dialling_clients(9), 16)]
+    wl = W.WorkloadBuilder()                               # panic!("{}", flag + 7) with flag = 300 > panic_dyn_max
+    n = wl.create_node(restart_on_panic_matching=("1",))
+    t = wl.task(n); t.flag_add(0, 300); t.panic_with_flag(0, 7)
+    m = wl.main(); m.spawn(t); m.join(t, expect_err=True)
+    ws.append(("panic_dyn_beyond_max", wl.build(), None, 64))
+    ws += [("spawn_storm_255_tasks", *_spawn_storm(300), 1),
+           ("registrations_256", *_dead_registrations(258), 2),
+           ("rxseq_wraps_onto_dead_registration", *_receives_of_one_task(129), 4),
+           ("sixteenth_queued_payload", *_queued_payloads(16), 8),
+           ("queued_messages_256", *_queued_messages(256), 4096)]
     return ws
+
+
+def model_exactly_one_over_workloads():
+    """Two of the workloads above go well past their ceiling (300 sleepers, 258 registrations): a kernel that admitted a 255th task or a 256th
+    registration and refused a later one would give the same all-zero answer.  These stand exactly one over: 254 sleepers beside the main
+    task, 256 receives."""
+    return [("spawn_storm_exactly_255_tasks", *_spawn_storm(254), 1),
+            ("registrations_exactly_256", *_dead_registrations(256), 2)]
+
+
+def model_at_ceiling_workloads():
+    """The same constructions standing AT their ceilings — 254 live tasks, 255 registrations, the 128th receive of one task, 15 queued
+    payloads, 255 queued messages, 8 queued connections, six servers called through: no event of the workload model on any seed (bit 0),
+    so the device owes the oracle's 48 bytes."""
+    return [("ipvs_six_servers", *_ipvs_servers(6), 0),
+            ("eight_queued_connections", *_dialling_clients(8), 0),
+            ("spawn_storm_254_tasks", *_spawn_storm(253), 0),
+            ("registrations_255", *_dead_registrations(255), 0),
+            ("rxseq_128_receives", *_receives_of_one_task(128), 0),
+            ("fifteen_queued_payloads", *_queued_payloads(15), 0),
+            ("queued_messages_255", *_queued_messages(255), 0)]
+
+
+def model_edge_pairs():
+    """The ceilings that had no directed workload: (name, at-ceiling workload, over-ceiling workload, limits, the event bit of the second).
+
+    Left out, with the arithmetic — MADSIM_ORACLE_ME_EPH_PORTS (an ephemeral bind beyond the table's candidate ports) cannot be the ONLY event of
+    a seed of this oracle.  Its table keeps one address per entry, so with n entries for a (node, IP) it sees at most n ports taken and the
+    first free port is at most n + 1.  The model holds n candidates, 2 n when the program has a connect1.  With a connect1: n + 1 <= 2 n, no
+    event.  Without one nothing keeps an address past its Endpoint, so the entry being bound is itself free (or its Endpoint is alive, which
+    is MADSIM_ORACLE_ME_EPH_REBIND first): at most n - 1 ports taken, port <= n, no event.  The event is reachable only behind a port-0
+    rebind (tests/test_oracle_model_limits.py test_port0_entry_events: bits 128 | 1024) or, on the device alone, through the older address
+    the oracle's table forgets (the known gap) — neither is a workload the two sides can be compared on bit for bit."""
+    ps = []
+    for name, build, at, over, bit in (("live_connections", _live_connections, 127, 128, 2048),
+                                       ("guards_of_one_endpoint", _guards_of_one_endpoint, 127, 128, 512),
+                                       ("instances_of_one_slot", _instances_of_one_slot, 256, 257, 4)):
+        (w_at, lim), (w_over, _) = build(at), build(over)
+        ps.append((name, w_at, w_over, lim, bit))
+    return ps
+
+
+def base_op_mailbox_pair():
+    """-> (at, over, limits): 127 / 128 datagrams for a bound socket whose owner only sleeps, no extended op in the program.  The reference and
+    the oracle pass both; the device passes the first and answers the second with MADSIM_OVERFLOW at every capacity (its base-op mailbox
+    header keeps 7 bits: include/madsim_hip.h, the capacity verdict that stays one)."""
+    (w_at, lim), (w_over, _) = _queued_messages(127, extended_op=False), _queued_messages(128, extended_op=False)
+    return w_at, w_over, lim
+
+
+def model_mix_workload():
+    """-> (workload, config, limits): 256 datagrams for a mailbox of 255 under a loss rate of 0.003 — a seed that loses one stays inside the
+    model and passes, a seed that loses none is MADSIM_UNSUPPORTED: about every second lane of every wave leaves the model."""
+    w, lim = _queued_messages(256)
+    return w, A.Config.default(packet_loss_rate=0.003), lim
+
+
+def top_of_state_region():
+    """-> (workload, limits): the largest per-seed block of the global-state layout — 60 socket addresses on two nodes, every capacity at its
+    ceiling — used at its two ends: one datagram exchange through the first two addresses of the table, one through the LAST two, whose
+    planes are the highest words of a lane's block.  A chan_close selects the every-class build."""
+    wl = W.WorkloadBuilder()
+    n1, n2 = wl.create_node(), wl.create_node()
+    addrs = [wl.addr(n1 if k % 2 == 0 else n2, 1 + k // 2) for k in range(60)]
+    tasks = []
+    for (a_tx, a_rx), val in ((addrs[:2], 0x1111), (addrs[-2:], 0x2222)):
+        rx = wl.task(n2); rx.bind(a_rx); rx.recv_from_timeout(a_rx, 1, ms=50); rx.trace_val(); rx.done()
+        tx = wl.task(n1); tx.bind(a_tx); tx.sleep(ms=5); tx.send_to(a_tx, a_rx, 1, val); tx.done()
+        tasks += [rx, tx]
+    m = wl.main()
+    for t in tasks: m.spawn(t)
+    for t in tasks: m.join(t)
+    m.chan_close(); m.done()
+    return wl.build(), _limits(max_tasks=254, mbox_regs=255, mbox_msgs=255, max_conns=127, chan_queue=15, state_mem=A.STATE_GLOBAL)
 
 
 def config(name):

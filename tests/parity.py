@@ -19,8 +19,16 @@ from madsim_amd import _abi as A
 LIMIT_NONE = 0xFFFFFFFF
 
 
-def grow(lim, n_progs):
-    """One round of madsim_hip.cpp `grow()` for capacity verdicts: every device capacity doubled."""
+def msgs_ceiling(w):
+    """The ceiling of mbox_msgs for this workload (madsim_hip.cpp mbox_msgs_ceiling): 127 without extended ops — the base-op mailbox header keeps
+    7 bits and no build takes more —, 255 with them.  Read off the build the geometry selects under the default limits."""
+    from madsim_amd import runtime
+    v = runtime.geometry(w).variant
+    return 255 if (v >> 8 & 0xff) | (v >> 20 & 0xf) else 127
+
+
+def grow(lim, n_progs, msgs_cap=255):
+    """One round of madsim_hip.cpp `grow()` for capacity verdicts: every device capacity doubled (msgs_cap: msgs_ceiling(w) of the workload)."""
     def dbl(v, dflt, cap):
         x = dflt if v in (0, LIMIT_NONE) else v
         return min(2 * x, cap)
@@ -35,7 +43,7 @@ def grow(lim, n_progs):
     g.heap_spill_slots = dbl(g.heap_spill_slots, 32, 1 << 20)
     g.max_tasks = dbl(g.max_tasks, n_progs + 8, 254)
     g.mbox_regs = dbl(g.mbox_regs, 2, 255)
-    g.mbox_msgs = dbl(g.mbox_msgs, 2, 255)
+    g.mbox_msgs = dbl(g.mbox_msgs, 2, msgs_cap)
     g.max_conns = dbl(g.max_conns, 4, 127)
     g.chan_queue = dbl(g.chan_queue, 2, 15)
     return g
@@ -95,7 +103,7 @@ def resolve_seed_by_seed(run, w, seed0, got, cfg, lim, max_rounds=8):
         idx = np.nonzero(out["verdict"] == A.OVERFLOW)[0]
         if not len(idx):
             break
-        cur = grow(cur, w.struct.n_progs)
+        cur = grow(cur, w.struct.n_progs, msgs_ceiling(w))
         for i in idx:
             out[i] = run(w, seed0 + int(i), 1, cfg, cur)[0]
     return out

@@ -251,17 +251,19 @@ def test_stop_at_failure_finds_the_failure_an_overflow_was_hiding(hip):
 
 
 def test_grown_limits_that_fit_no_build_fail_the_call(hip):
-    """Mailboxes of 64 messages: the first pass runs (and overflows its two heap slots), the first round's limits ask for 128, which a
-    base-op workload's builds do not have.  The call fails as madsim_hip_run_batch fails under those limits, with every stream drained: the
-    context runs the next campaigns as if nothing had happened."""
-    w, total = W.pingpong(4, 16), 8192
+    """Sixteen sockets with mailboxes of 64 in the LDS layout: the first pass runs (and overflows its two heap slots), the first round's limits
+    ask for mailboxes of 128 / 127, and sixteen of those are more per-seed LDS than any build of the layout has.  (A base-op workload's
+    mbox_msgs alone no longer does it: its ladder ends at 127, the most its builds take.)  The call fails as madsim_hip_run_batch fails under
+    those limits, with every stream drained: the context runs the next campaigns as if nothing had happened."""
+    w, total = W.pingpong(16, 2), 8192
     lim = A.Limits()
     lim.state_mem, lim.heap_lds_slots, lim.heap_spill_slots, lim.mbox_regs, lim.mbox_msgs = A.STATE_LDS, 2, 0, 64, 64
     first, _ = hip.run_batch(w, 0, 256, None, lim)
-    assert (first["verdict"] == A.OVERFLOW).all() and hip.grown_limits(w, lim, 1).mbox_msgs == 128
-    with pytest.raises(hip.MadsimHipError, match="mbox_msgs"):
-        hip.run_batch(w, 0, 256, None, hip.grown_limits(w, lim, 1))
-    with pytest.raises(hip.MadsimHipError, match="mbox_msgs"):
+    grown = hip.grown_limits(w, lim, 1)
+    assert (first["verdict"] == A.OVERFLOW).all() and (grown.mbox_regs, grown.mbox_msgs) == (128, 127)
+    with pytest.raises(hip.MadsimHipError, match="per-seed LDS state too large"):
+        hip.run_batch(w, 0, 256, None, grown)
+    with pytest.raises(hip.MadsimHipError, match="per-seed LDS state too large"):
         hip.run_campaign(w, 0, total, 2048, 3, False, None, lim, resolve=True)
     rep = hip.run_campaign(w, 0, total, 2048, 3, False, None, lim)                               # without the flag: the first pass, whole
     assert (rep.seeds_run, rep.n_runner, rep.batches_run) == (total, total, 4) and bytes(hip.campaign_resolved()) == bytes(112)

@@ -92,10 +92,16 @@ def test_grow_limits_against_the_table():
              3: (8, 256, 104, 16, 16, 32, 15, 1 << 28, 0),
              4: (8, 512, 208, 32, 32, 64, 15, 1 << 28, 0),
              5: (8, 1024, 254, 64, 64, 127, 15, 1 << 28, 0),
-             8: (8, 8192, 254, 255, 255, 127, 15, 1 << 28, 0)}
+             8: (8, 8192, 254, 255, 127, 127, 15, 1 << 28, 0)}                            # (mbox_msgs: the ping-pong has no extended op, its builds take 127)
     for rounds, want in table.items():
         assert caps(runtime.grown_limits(w, zero, rounds)) == want, rounds
     assert caps(runtime.grown_limits(w, None, 1)) == table[1]                             # no limits = the defaults
+    ext = workload.WorkloadBuilder()                                                      # one extended op: mbox_msgs goes on to 255
+    n = ext.create_node(); a = ext.addr(n, 1)
+    t = ext.task(n); t.bind(a); t.recv_from_timeout(a, 1, ms=1); t.done()
+    m = ext.main(); m.spawn(t); m.join(t); m.done()
+    assert [runtime.grown_limits(ext.build(), zero, r).mbox_msgs for r in (5, 6, 7, 8)] == [64, 128, 255, 255]
+    assert [runtime.grown_limits(w, zero, r).mbox_msgs for r in (5, 6, 7)] == [64, 127, 127]
     # MADSIM_LIMIT_NONE counts as unset; an explicit LDS quota is kept, lanes_per_wave is dropped
     lim = A.Limits()
     lim.mbox_regs, lim.heap_lds_slots, lim.lanes_per_wave, lim.heap_spill_slots = A.LIMIT_NONE, 2, 16, 1
@@ -112,7 +118,7 @@ def test_grow_limits_against_the_table():
     lim = A.Limits()
     lim.heap_spill_slots = 4096
     g = runtime.grown_limits(w, lim, 8)
-    assert (g.max_tasks, g.mbox_regs, g.mbox_msgs, g.max_conns, g.chan_queue, g.heap_spill_slots) == (254, 255, 255, 127, 15, 1 << 20)
+    assert (g.max_tasks, g.mbox_regs, g.mbox_msgs, g.max_conns, g.chan_queue, g.heap_spill_slots) == (254, 255, 127, 127, 15, 1 << 20)      # (mbox_msgs: a base-op workload's ceiling)
     assert caps(runtime.grown_limits(w, lim, 9)) == caps(g)                               # ... and stays there
     # max_steps: 16-fold per round, never above max_steps_ceiling (0 = 2^28), which is never below the first pass's cap
     for first, ceiling, want in ((64, 1024, [1024, 1024]), (64, 128, [128, 128]), (64, 0, [1024, 16384]), (0, 0, [1 << 28, 1 << 28]),
