@@ -280,6 +280,34 @@ pub struct Divergence {
     pub next_b: Vec<u64>,
 }
 
+/// Which traced values the seeds of a census reached, by verdict (`Builder::census` / `census_seeds`): `values`, ascending by value — per
+/// distinct value the counted seeds of each verdict that observed it at least once, its occurrences, the smallest such seed and the most
+/// occurrences inside one seed —; `totals`, the counts of `madsim_census_t` (its pointers are null here); `runner_seeds`, the seeds
+/// left with a runner verdict, ascending: they are counted nowhere.
+#[derive(Clone, Debug)]
+pub struct Census {
+    pub values: Vec<sys::madsim_census_value_t>,
+    pub totals: sys::madsim_census_t,
+    pub runner_seeds: Vec<u64>,
+}
+
+impl Census {
+    /// The record of value `v`, or `None` when no counted seed observed it.
+    pub fn row(&self, v: u64) -> Option<&sys::madsim_census_value_t> {
+        self.values.binary_search_by_key(&v, |e| e.value).ok().map(|i| &self.values[i])
+    }
+
+    /// How many counted seeds observed `v` at least once.
+    pub fn reached(&self, v: u64) -> u64 {
+        self.row(v).map_or(0, |e| e.n_seeds.iter().sum())
+    }
+
+    /// The sometimes-assertion: those of `expected` that no counted seed observed, in the order given.
+    pub fn never(&self, expected: &[u64]) -> Vec<u64> {
+        expected.iter().copied().filter(|&v| self.row(v).is_none()).collect()
+    }
+}
+
 /// The `obs_hash` of a run that traced `values`, in that order: 64-bit FNV-1a over whole values (the offset basis for none).
 pub fn fold_observations(values: &[u64]) -> u64 {
     values.iter().fold(0xCBF2_9CE4_8422_2325u64, |h, v| (h ^ v).wrapping_mul(0x100_0000_01B3))
@@ -507,6 +535,110 @@ impl Builder {
             idx = again;
         }
         Ok(out)
+    }
+
+    /// Which traced values the seeds `self.seed .. self.seed + self.count` reach, by verdict (`madsim_hip_ctx_census_range`): the range run
+    /// on the trace build and reduced on the device, nothing but the table coming back.  A seed is counted when its verdict bit is set
+    /// in `include` (bits 0-3); its first `obs_cap` observations are visible; more than `max_values` distinct values is an error
+    /// (`MADSIM_E_LIMITS`: a traced time or random value is not a probe vocabulary).  With `resolve_runner` set, the seeds a call leaves
+    /// with a runner verdict are run again in one list call per round under `madsim_hip_grow_limits(.., r)` and merged in.
+    pub fn census(&self, workload: &Workload, include: u32, obs_cap: u32, max_values: usize) -> Result<Census, RunError> {
+        self.census_over(workload, None, include, obs_cap, max_values)
+    }
+
+    /// `census` over an explicit, strictly ascending seed list (`madsim_hip_ctx_census_seeds`).
+    pub fn census_seeds(&self, workload: &Workload, seeds: &[u64], include: u32, obs_cap: u32, max_values: usize) -> Result<Census, RunError> {
+        self.census_over(workload, Some(seeds), include, obs_cap, max_values)
+    }
+
+    fn census_over(&self, workload: &Workload, seeds: Option<&[u64]>, include: u32, obs_cap: u32, max_values: usize) -> Result<Census, RunError> {
+        let w = workload.raw();
+        let cfg = self.config.raw();
+        let lim0 = self.raw_limits(true);
+        let ctx = contexts()?.0[0];
+        let rounds = if self.resolve_flags & sys::MADSIM_CAMPAIGN_RESOLVE == 0 {
+            0
+        } else {
+            match (self.resolve_flags & sys::MADSIM_CAMPAIGN_RESOLVE_ROUNDS_MASK) >> sys::MADSIM_CAMPAIGN_RESOLVE_ROUNDS_SHIFT {
+                0 => sys::MADSIM_RESOLVE_DEFAULT_ROUNDS,
+                r => r,
+            }
+        };
+        let one = |lim: &sys::madsim_limits_t, list: Option<&[u64]>| -> Result<Census, RunError> {
+            let n = list.map_or(self.count, |l| l.len() as u64);
+            let mut values: Vec<sys::madsim_census_value_t> = vec![unsafe { std::mem::zeroed() }; max_values.max(1)];
+            let mut runner = vec![0u64; (n as usize).max(1)];
+            let mut cen: sys::madsim_census_t = unsafe { std::mem::zeroed() };
+            cen.include = include;
+            cen.obs_cap = obs_cap;
+            cen.values = values.as_mut_ptr() as *const _;                // (the library writes through both)
+            cen.cap = max_values as u64;
+            cen.runner_seeds = runner.as_mut_ptr() as *const _;
+            cen.runner_cap = n;
+            let rc = unsafe {
+                match list {
+                    Some(l) => sys::madsim_hip_ctx_census_seeds(ctx, &w, &cfg, l.as_ptr(), n, 0, lim, &mut cen),
+                    None => sys::madsim_hip_ctx_census_range(ctx, &w, &cfg, self.seed, n, 0, lim, &mut cen),
+                }
+            };
+            if rc != 0 {
+                return Err(last_error(rc));
+            }
+            values.truncate(cen.n_values as usize);
+            runner.truncate(cen.n_runner_listed as usize);
+            cen.values = std::ptr::null();
+            cen.runner_seeds = std::ptr::null();
+            Ok(Census { values, totals: cen, runner_seeds: runner })
+        };
+        let mut c = one(&lim0, seeds)?;
+        for r in 1..=rounds {
+            if c.runner_seeds.is_empty() {
+                break;
+            }
+            let mut lim = lim0;
+            let rc = unsafe { sys::madsim_hip_grow_limits(&w, &lim0, r, &mut lim) };
+            if rc != 0 {
+                return Err(last_error(rc));
+            }
+            let more = one(&lim, Some(&c.runner_seeds))?;
+            let mut merged = Vec::with_capacity(c.values.len() + more.values.len());
+            let (mut i, mut j) = (0, 0);
+            while i < c.values.len() || j < more.values.len() {
+                if j >= more.values.len() || (i < c.values.len() && c.values[i].value < more.values[j].value) {
+                    merged.push(c.values[i]);
+                    i += 1;
+                } else if i >= c.values.len() || more.values[j].value < c.values[i].value {
+                    merged.push(more.values[j]);
+                    j += 1;
+                } else {
+                    let (mut e, o) = (c.values[i], more.values[j]);
+                    for k in 0..4 {
+                        e.n_seeds[k] += o.n_seeds[k];
+                    }
+                    e.n_total += o.n_total;
+                    e.first_seed = e.first_seed.min(o.first_seed);
+                    e.max_per_seed = e.max_per_seed.max(o.max_per_seed);
+                    merged.push(e);
+                    i += 1;
+                    j += 1;
+                }
+            }
+            if merged.len() > max_values {
+                return Err(RunError { code: sys::MADSIM_E_LIMITS, message: "census: more than max_values distinct observed values once the runner seeds are settled".into() });
+            }
+            for k in 0..4 {
+                c.totals.n_counted[k] += more.totals.n_counted[k];
+                c.totals.n_silent[k] += more.totals.n_silent[k];
+            }
+            c.totals.n_truncated += more.totals.n_truncated;
+            c.totals.n_observations += more.totals.n_observations;
+            c.totals.n_runner = more.totals.n_runner;
+            c.totals.n_runner_listed = more.totals.n_runner_listed;
+            c.totals.n_values = merged.len() as u64;
+            c.values = merged;
+            c.runner_seeds = more.runner_seeds;
+        }
+        Ok(c)
     }
 
     /// What one seed traced, and its result: the values in execution order (at most 65 536 of them).  A failing `run_workload` names

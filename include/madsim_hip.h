@@ -648,6 +648,65 @@ int madsim_hip_diverge_seeds(const madsim_workload_t* wA, const madsim_config_t*
                              const uint64_t* seeds, uint64_t n, uint64_t log_cap, uint64_t obs_cap, uint32_t win,
                              madsim_divergence_t* recs, uint64_t* obs_ctx);
 
+/* Observation census: WHICH traced values the seeds of a range reach, by verdict — "did the interesting thing ever happen?".  The result
+ * bytes hold a seed's observations only as a fold (obs_hash); the census runs the seeds on the trace build, as madsim_hip_trace_seeds does
+ * (log_cap 0, the caller's obs_cap), and reduces the observation rows where they lie on the device: per chunk the trace launch, a fold
+ * kernel, an extract kernel, and the chunk's words and entries (64 bytes per distinct value) coming back — no row travels to the host.
+ * madsim_hip_census_range takes [seed0, seed0 + total), madsim_hip_census_seeds a STRICTLY ASCENDING list (the campaign list rule).
+ *
+ * Everything is exact and all-integer, a function of the per-seed (result, observation list) alone: the same bytes whatever `chunk`, the
+ * context and the run.  Of seed s with result r and `len` observations the census sees the first min(len, obs_cap) — what
+ * madsim_hip_trace_seeds writes to its row.  A seed is COUNTED when r.verdict < 4 and bit `verdict` of `include` is set, as in
+ * madsim_stats_t.include.  A seed with a runner verdict (MADSIM_IS_RUNNER_VERDICT) is never counted — its list is cut where the runner gave
+ * up —; such seeds are tallied in n_runner and the runner_cap smallest of them written, ascending, to runner_seeds, to be settled under
+ * madsim_hip_grow_limits.  Per distinct value v among the counted seeds' visible observations, values[0 .. n_values) ascending by `value`:
+ *   n_seeds[k]    counted seeds of verdict k that observed v at least once (a seed counts once however often it traced v)
+ *   n_total       occurrences of v over those seeds
+ *   max_per_seed  the most occurrences inside one seed
+ *   first_seed    the smallest seed that observed v
+ * Every 64-bit value is a legal value: 0, 2^64 - 1 and the FNV offset basis included.
+ * n_counted[k] / n_silent[k]: counted seeds of verdict k / those of them without a visible observation; n_truncated: counted seeds with
+ * len > obs_cap, whose later values are not in the table; n_observations: the sum of min(len, obs_cap) over the counted seeds, which is
+ * the sum of every n_total.
+ * More than `cap` distinct values: MADSIM_E_LIMITS, and nothing is reported (every output word 0) — a property of the data alone: no
+ * arrival order ever picks which values survive.  The likely cause is a traced time or random value, which is no probe vocabulary: raise
+ * `cap` or trace less.
+ * The library cuts the seeds into chunks of `chunk` (0 = a default, 65 536 or what fits) itself; a census is a reduction, so the cut is
+ * invisible in the result.  One chunk asks the device for chunk * (8 * obs_cap + 72) bytes — the rows, two length words, the seed and the
+ * result of every seed — plus 32 * slots + 68 * cap + 128 for the table (slots: the power of two >= 2 * cap, at least 128), the claim list,
+ * the entries and the words: MADSIM_E_LIMITS when that exceeds MADSIM_TRACE_MAX_BYTES or chunk * obs_cap >= 2^32 - 1.
+ * total == 0 / n == 0 reports the empty census.  MADSIM_E_ARG: cen == NULL; include == 0 or a bit at or above 4; cap == 0 or above
+ * MADSIM_CENSUS_MAX_VALUES; values == NULL; obs_cap == 0 or above MADSIM_CENSUS_MAX_OBS_CAP; runner_cap > 0 without runner_seeds; seeds ==
+ * NULL with n > 0; a list that is not strictly ascending (sort and deduplicate first). */
+#define MADSIM_CENSUS_MAX_VALUES  1048576u /* 2^20 distinct values */
+#define MADSIM_CENSUS_MAX_OBS_CAP 1024u    /* observations of a seed the census can see */
+typedef struct madsim_census_value {   /* 64 bytes */
+    uint64_t value;
+    uint64_t n_seeds[4];               /* counted seeds of each verdict that observed it at least once                            */
+    uint64_t n_total;                  /* occurrences over those seeds                                                            */
+    uint64_t first_seed;               /* the smallest seed that observed it                                                      */
+    uint64_t max_per_seed;             /* the most occurrences inside one seed                                                    */
+} madsim_census_value_t;
+typedef struct madsim_census {
+    uint32_t include;                  /* in: bit v set = count the seeds whose verdict is v (bits 0-3 only, as madsim_stats_t.include) */
+    uint32_t obs_cap;                  /* in: observations of a seed that are visible, 1 .. MADSIM_CENSUS_MAX_OBS_CAP             */
+    madsim_census_value_t* values;     /* in: caller's host array [cap]                                                           */
+    uint64_t cap;                      /* in: 1 .. MADSIM_CENSUS_MAX_VALUES                                                       */
+    uint64_t* runner_seeds;            /* in: caller's host array [runner_cap]; may be NULL when runner_cap == 0                  */
+    uint64_t runner_cap;
+    uint64_t n_values;                 /* out: entries written, ascending by value                                                */
+    uint64_t n_counted[4];             /* out: counted seeds per verdict                                                          */
+    uint64_t n_silent[4];              /* out: ... of them without a visible observation                                          */
+    uint64_t n_truncated;              /* out: counted seeds with more than obs_cap observations                                  */
+    uint64_t n_observations;           /* out: visible observations of the counted seeds = the sum of n_total                     */
+    uint64_t n_runner;                 /* out: seeds with a runner verdict                                                        */
+    uint64_t n_runner_listed;          /* out: min(n_runner, runner_cap), the entries of runner_seeds written                     */
+} madsim_census_t;
+int madsim_hip_census_range(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total, uint64_t chunk,
+                            const madsim_limits_t* lim, madsim_census_t* cen);
+int madsim_hip_census_seeds(const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n, uint64_t chunk,
+                            const madsim_limits_t* lim, madsim_census_t* cen);
+
 /* The same entry points on an explicit context (see "Per-device contexts" above). */
 int madsim_hip_ctx_run_batch(madsim_hip_ctx_t* ctx, const madsim_workload_t* w, const madsim_config_t* cfg,
                              uint64_t seed0, uint64_t count, const madsim_limits_t* lim,
@@ -675,6 +734,10 @@ int madsim_hip_ctx_diverge_seeds(madsim_hip_ctx_t* ctx, const madsim_workload_t*
                                  const madsim_limits_t* limA, const madsim_workload_t* wB, const madsim_config_t* cfgB,
                                  const madsim_limits_t* limB, const uint64_t* seeds, uint64_t n, uint64_t log_cap,
                                  uint64_t obs_cap, uint32_t win, madsim_divergence_t* recs, uint64_t* obs_ctx);
+int madsim_hip_ctx_census_range(madsim_hip_ctx_t* ctx, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0,
+                                uint64_t total, uint64_t chunk, const madsim_limits_t* lim, madsim_census_t* cen);
+int madsim_hip_ctx_census_seeds(madsim_hip_ctx_t* ctx, const madsim_workload_t* w, const madsim_config_t* cfg,
+                                const uint64_t* seeds, uint64_t n, uint64_t chunk, const madsim_limits_t* lim, madsim_census_t* cen);
 
 /* One process, several GPUs: the whole seed loop of Builder::run (builder.rs:129-150, every seed driven from one
  * process) over `n_ctx` contexts, each on its own GPU (or, for tests on a 1-GPU box, several on the same one).

@@ -890,6 +890,83 @@ struct Builder {
         return s;
     }
 
+    // Which traced values the builder's seeds reach, by verdict (madsim_hip_census_range / madsim_hip_census_seeds): `seed .. seed + count`,
+    // or the seed list when one was given, run on the trace build and reduced on the device.  values: ascending by value, one record per
+    // distinct value among the first `obs_cap` observations of the counted seeds (verdict in `include`, a bit mask over PASS, PANIC,
+    // DEADLOCK, TIME_LIMIT); more than `max_values` of them throws (MADSIM_E_LIMITS: a traced time or random value is no probe vocabulary).
+    // This builder's resolve_runner() rounds apply: the seeds a call leaves with a runner verdict are run again in one list call per round
+    // under madsim_hip_grow_limits(.., r) and merged in; what stays is counted in totals.n_runner and listed in runner_seeds.
+    struct Census {
+        std::vector<madsim_census_value_t> values;
+        madsim_census_t totals{};                  // the counts (the pointers and caps are the call's own: not meaningful here)
+        std::vector<uint64_t> runner_seeds;
+        const madsim_census_value_t* row(uint64_t v) const {
+            auto it = std::lower_bound(values.begin(), values.end(), v, [](const madsim_census_value_t& e, uint64_t x) { return e.value < x; });
+            return it != values.end() && it->value == v ? &*it : nullptr;
+        }
+        uint64_t reached(uint64_t v) const {       // counted seeds that observed v at least once
+            const madsim_census_value_t* e = row(v);
+            return e ? e->n_seeds[0] + e->n_seeds[1] + e->n_seeds[2] + e->n_seeds[3] : 0;
+        }
+        std::vector<uint64_t> never(const std::vector<uint64_t>& expected) const {      // the sometimes-assertion: expected values nobody observed
+            std::vector<uint64_t> out;
+            for (uint64_t v : expected) if (!row(v)) out.push_back(v);
+            return out;
+        }
+    };
+    Census census(const Workload& wl, uint32_t obs_cap = 256, uint64_t max_values = 4096, uint32_t include = 0xf, uint64_t chunk = 0) const {
+        madsim::check(madsim_hip_init(device));
+        madsim_workload_t w = wl.raw();
+        madsim_config_t cfg = config.raw();
+        madsim_limits_t lim0 = capacities;
+        if (time_limit) { lim0.time_limit_ns = (uint64_t)(*time_limit * 1e9 + 0.5); if (!lim0.time_limit_ns) lim0.time_limit_ns = 1; }
+        uint32_t rounds = 0;
+        if (resolve_flags & MADSIM_CAMPAIGN_RESOLVE) {
+            rounds = (resolve_flags & MADSIM_CAMPAIGN_RESOLVE_ROUNDS_MASK) >> MADSIM_CAMPAIGN_RESOLVE_ROUNDS_SHIFT;
+            if (!rounds) rounds = MADSIM_RESOLVE_DEFAULT_ROUNDS;
+        }
+        auto one = [&](const madsim_limits_t& lim, const std::vector<uint64_t>* list) {
+            Census c;
+            const uint64_t n = list ? list->size() : count;
+            c.values.resize(max_values ? max_values : 1);
+            c.runner_seeds.resize(n ? n : 1);
+            madsim_census_t& t = c.totals;
+            t.include = include; t.obs_cap = obs_cap; t.values = c.values.data(); t.cap = max_values;
+            t.runner_seeds = c.runner_seeds.data(); t.runner_cap = n;
+            madsim::check(list ? madsim_hip_census_seeds(&w, &cfg, list->data(), n, chunk, &lim, &t) : madsim_hip_census_range(&w, &cfg, seed, n, chunk, &lim, &t));
+            c.values.resize(t.n_values);
+            c.runner_seeds.resize(t.n_runner_listed);
+            t.values = nullptr; t.runner_seeds = nullptr;
+            return c;
+        };
+        Census c = one(lim0, listed_seeds ? &seed_list : nullptr);
+        for (uint32_t r = 1; r <= rounds && !c.runner_seeds.empty(); r++) {
+            madsim_limits_t lim = lim0;
+            madsim::check(madsim_hip_grow_limits(&w, &lim0, r, &lim));
+            const Census more = one(lim, &c.runner_seeds);
+            std::vector<madsim_census_value_t> merged;
+            for (size_t i = 0, j = 0; i < c.values.size() || j < more.values.size();) {
+                if (j >= more.values.size() || (i < c.values.size() && c.values[i].value < more.values[j].value)) merged.push_back(c.values[i++]);
+                else if (i >= c.values.size() || more.values[j].value < c.values[i].value) merged.push_back(more.values[j++]);
+                else {
+                    madsim_census_value_t e = c.values[i++];
+                    const madsim_census_value_t& o = more.values[j++];
+                    for (int k = 0; k < 4; k++) e.n_seeds[k] += o.n_seeds[k];
+                    e.n_total += o.n_total; e.first_seed = std::min(e.first_seed, o.first_seed); e.max_per_seed = std::max(e.max_per_seed, o.max_per_seed);
+                    merged.push_back(e);
+                }
+            }
+            if (merged.size() > max_values) throw Error(MADSIM_E_LIMITS, "census: more than max_values distinct observed values once the runner seeds are settled");
+            c.values.swap(merged);
+            for (int k = 0; k < 4; k++) { c.totals.n_counted[k] += more.totals.n_counted[k]; c.totals.n_silent[k] += more.totals.n_silent[k]; }
+            c.totals.n_truncated += more.totals.n_truncated; c.totals.n_observations += more.totals.n_observations;
+            c.totals.n_runner = more.totals.n_runner; c.totals.n_runner_listed = more.totals.n_runner_listed;
+            c.totals.n_values = c.values.size();
+            c.runner_seeds = more.runner_seeds;
+        }
+        return c;
+    }
+
     // Where the two runs part: this builder's run of `wl` (side A) against `other`'s run of `other_wl` (side B) over `seeds` (any order,
     // duplicates allowed), compared on the device on the determinism log and on the observations (madsim_hip_diverge_seeds): per seed the
     // record, the up to `window` observations both runs made just before they part, and the up to `window` each side made from there on.

@@ -289,6 +289,30 @@ class Divergence(C.Structure):
 
 assert C.sizeof(Divergence) == 184
 
+CENSUS_MAX_VALUES, CENSUS_MAX_OBS_CAP = 1 << 20, 1024      # madsim_hip_census_range / _seeds: the most distinct values, the most visible observations
+
+
+class CensusValue(C.Structure):
+    """madsim_census_value_t: one observed value — the counted seeds of each verdict that observed it at least once, its occurrences over
+    them, the smallest such seed and the most occurrences inside one seed."""
+    _fields_ = [("value", C.c_uint64), ("n_seeds", C.c_uint64 * 4), ("n_total", C.c_uint64), ("first_seed", C.c_uint64), ("max_per_seed", C.c_uint64)]
+
+
+class Census(C.Structure):
+    """madsim_census_t: which verdicts count, how many observations of a seed are visible and the caller's two arrays going in; the table's
+    length and the totals coming out."""
+    _fields_ = [("include", C.c_uint32), ("obs_cap", C.c_uint32), ("values", C.POINTER(CensusValue)), ("cap", C.c_uint64),
+                ("runner_seeds", C.POINTER(C.c_uint64)), ("runner_cap", C.c_uint64), ("n_values", C.c_uint64), ("n_counted", C.c_uint64 * 4),
+                ("n_silent", C.c_uint64 * 4), ("n_truncated", C.c_uint64), ("n_observations", C.c_uint64), ("n_runner", C.c_uint64),
+                ("n_runner_listed", C.c_uint64)]
+
+
+# numpy view of a census table: madsim_census_value_t
+CENSUS_VALUE_DTYPE = [("value", "<u8"), ("n_seeds", "<u8", (4,)), ("n_total", "<u8"), ("first_seed", "<u8"), ("max_per_seed", "<u8")]
+assert C.sizeof(CensusValue) == 64 and C.sizeof(Census) == 144
+HEADER_STRUCTS["madsim_census_value_t"] = CensusValue
+HEADER_STRUCTS["madsim_census_t"] = Census
+
 
 class Geometry(C.Structure):
     _fields_ = [

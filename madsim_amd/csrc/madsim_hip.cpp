@@ -230,6 +230,31 @@ struct madsim_hip_resources {
     struct TraceSet { DevBuf<uint8_t> log; DevBuf<uint64_t> obs, len; DevBuf<madsim_result_t> out; };
     TraceSet trace[2];
     DevBuf<madsim_divergence_t> d_drec; DevBuf<uint64_t> d_dctx;      // divergence reports: the records and the context rows
+    // the observation census: the table (all zero between chunks; `dirty` when it is new or an error may have left it otherwise), the claim
+    // list, the words and the chunk's entries (device); page-locked: the words, the entries, the range form's seed slice and — only for a
+    // chunk with runner verdicts whose seeds the caller still wants — the chunk's results
+    struct Census {
+        DevBuf<uint32_t> tab, list; DevBuf<unsigned long long> words; DevBuf<madsim_census_value_t> ent;
+        PinnedBuf<unsigned long long> h_words; PinnedBuf<madsim_census_value_t> h_ent; PinnedBuf<uint64_t> h_seeds; PinnedBuf<madsim_result_t> h_res;
+        bool dirty = true;
+        int ensure(uint64_t cap, uint64_t chunk, bool range, hipStream_t s) {
+            const size_t tab_words = (size_t)(madsim_k_census_slots(cap) * MADSIM_K_CENSUS_SLOT_BYTES / sizeof(uint32_t));
+            if (tab_words > tab.cap) dirty = true;
+            HIP_TRY(tab.room(tab_words, s));
+            HIP_TRY(list.room((size_t)cap, s));
+            HIP_TRY(ent.room((size_t)cap, s));
+            HIP_TRY(h_ent.room((size_t)cap, s));
+            HIP_TRY(words.room(MADSIM_K_CENSUS_WORDS));
+            HIP_TRY(h_words.room(MADSIM_K_CENSUS_WORDS));
+            if (range) HIP_TRY(h_seeds.room((size_t)chunk, s));
+            if (dirty) {
+                HIP_TRY(hipMemsetAsync(tab, 0, tab.cap * sizeof(uint32_t), s));
+                HIP_TRY(hipStreamSynchronize(s));
+                dirty = false;
+            }
+            return 0;
+        }
+    } census;
     Event ev0, ev1;
     Event pipe_begin;                         // run_pipelined: before the first sub-batch of a call
     Event tev[2 * 64];                        // timing slots of madsim_hip_run_batch_async
@@ -1060,6 +1085,146 @@ int madsim_hip_ctx_diverge_seeds(madsim_hip_ctx_t* c, const madsim_workload_t* w
     if (za || zb)
         for (uint64_t i = 0; i < n; i++) { if (za) recs[i].a.trace_hash = 0; if (zb) recs[i].b.trace_hash = 0; }
     return 0;
+}
+
+// ---- the observation census: table size, probe start, the host fold of a chunk, and the chunk loop ---------------------------------
+extern "C" uint64_t madsim_k_census_slots(uint64_t cap) {
+    uint64_t slots = MADSIM_K_CENSUS_MIN_SLOTS;
+    while (slots < 2 * cap) slots <<= 1;
+    return slots;
+}
+
+extern "C" uint64_t madsim_k_census_slot(uint64_t value, uint64_t slots) { return madsim_k::census_slot(value, slots); }
+
+// Declared in sim_kernel.h beside the launcher (not part of the public ABI): the tests feed it entries without a device.  Everything it
+// does commutes, so the order of the chunks and of a chunk's entries never shows; equal values inside one chunk's entries are combined too.
+extern "C" int madsim_k_fold_census(madsim_census_t* cen, const unsigned long long* words, const madsim_census_value_t* entries, uint64_t n) {
+    auto combine = [](madsim_census_value_t& a, const madsim_census_value_t& b) {
+        for (int k = 0; k < 4; k++) a.n_seeds[k] += b.n_seeds[k];
+        a.n_total += b.n_total;
+        a.first_seed = std::min(a.first_seed, b.first_seed);
+        a.max_per_seed = std::max(a.max_per_seed, b.max_per_seed);
+    };
+    std::vector<madsim_census_value_t> add(entries, entries + n);
+    std::sort(add.begin(), add.end(), [](const madsim_census_value_t& a, const madsim_census_value_t& b) { return a.value < b.value; });
+    size_t m = 0;
+    for (size_t j = 0; j < add.size(); j++) {
+        if (m && add[m - 1].value == add[j].value) combine(add[m - 1], add[j]); else add[m++] = add[j];
+    }
+    madsim_census_value_t* const v = cen->values;
+    const uint64_t have = cen->n_values;
+    uint64_t fresh = 0;
+    for (size_t i = 0, j = 0; j < m; j++) {
+        while (i < have && v[i].value < add[j].value) i++;
+        if (i >= have || v[i].value != add[j].value) fresh++;
+    }
+    if (have + fresh > cen->cap) return -1;
+    for (int64_t i = (int64_t)have - 1, j = (int64_t)m - 1, k = (int64_t)(have + fresh) - 1; j >= 0; k--) {      // merged from the back, in place
+        if (i >= 0 && v[i].value > add[j].value) v[k] = v[i--];
+        else if (i >= 0 && v[i].value == add[j].value) { madsim_census_value_t e = v[i--]; combine(e, add[j--]); v[k] = e; }
+        else v[k] = add[j--];
+    }
+    cen->n_values = have + fresh;
+    if (words) {
+        for (int k = 0; k < 4; k++) { cen->n_counted[k] += words[2 + k]; cen->n_silent[k] += words[6 + k]; }
+        cen->n_truncated += words[10]; cen->n_observations += words[11]; cen->n_runner += words[12];
+    }
+    return 0;
+}
+
+// The census of [seed0, seed0 + total) (seeds == nullptr) or of seeds[0 .. total): chunk after chunk on one stream, each the trace launch
+// into the context's trace set 0, the two census kernels and the copies of the words and of the first CENSUS_EAGER_ENTRIES entries, then
+// one synchronisation: the chunk of a probe vocabulary is done there.  Entries beyond those — and, where the caller still wants runner
+// seeds and the chunk has some, its results — follow by copies of their own.  Once a chunk is queued no
+// error returns before its synchronisation (TraceSteps); an error that may have left the table otherwise than zero marks it dirty.
+constexpr uint64_t CENSUS_EAGER_ENTRIES = 64;      // entries copied behind a chunk's words, before their number is known
+
+static int census_run(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, const uint64_t* seeds,
+                      uint64_t total, uint64_t chunk, const madsim_limits_t* lim, madsim_census_t* cen, bool list) {
+    static_assert(sizeof(madsim_census_value_t) == 64 && sizeof(madsim_census_t) == 144, "record layout");
+    if (!cen) return fail(MADSIM_E_ARG, "census: null census");
+    if (cen->include == 0 || (cen->include & ~0xfu)) return fail(MADSIM_E_ARG, "census: include is 0 or names a verdict at or above 4 (only PASS, PANIC, DEADLOCK, TIME_LIMIT are counted)");
+    if (cen->cap == 0 || cen->cap > MADSIM_CENSUS_MAX_VALUES || !cen->values) return fail(MADSIM_E_ARG, "census: cap outside 1 .. MADSIM_CENSUS_MAX_VALUES, or no value array");
+    if (cen->obs_cap == 0 || cen->obs_cap > MADSIM_CENSUS_MAX_OBS_CAP) return fail(MADSIM_E_ARG, "census: obs_cap outside 1 .. MADSIM_CENSUS_MAX_OBS_CAP");
+    if (cen->runner_cap && !cen->runner_seeds) return fail(MADSIM_E_ARG, "census: runner_cap without runner_seeds");
+    if (list && total && !seeds) return fail(MADSIM_E_ARG, "census_seeds: null seed list");
+    if (list)
+        for (uint64_t i = 1; i < total; i++)
+            if (seeds[i] <= seeds[i - 1]) return fail(MADSIM_E_ARG, "census_seeds: the seed list is not strictly ascending (sort and deduplicate it first)");
+    auto nothing = [cen] {
+        cen->n_values = cen->n_truncated = cen->n_observations = cen->n_runner = cen->n_runner_listed = 0;
+        for (int k = 0; k < 4; k++) cen->n_counted[k] = cen->n_silent[k] = 0;
+    };
+    nothing();
+    if (total == 0) return 0;
+    // what a chunk asks of the device: per seed the row, two length words, the seed and the result; once the table, the list, the entries, the words
+    const uint64_t M = MADSIM_TRACE_MAX_BYTES, obs_cap = cen->obs_cap, cap = cen->cap;
+    const uint64_t fixed = madsim_k_census_slots(cap) * MADSIM_K_CENSUS_SLOT_BYTES + cap * (sizeof(uint32_t) + sizeof(madsim_census_value_t)) + MADSIM_K_CENSUS_WORDS * 8;
+    const uint64_t per_seed = 8 * obs_cap + 3 * sizeof(uint64_t) + sizeof(madsim_result_t);
+    const uint64_t fits = fixed < M ? std::min<uint64_t>((M - fixed) / per_seed, 0xffffffffull / obs_cap - 1) : 0;
+    if (chunk == 0) chunk = std::min<uint64_t>(65536, fits);
+    if (chunk == 0 || chunk > fits)
+        return fail(MADSIM_E_LIMITS, "census: chunk x (8 obs_cap + 72) + 32 slots + 68 cap + 128 exceeds MADSIM_TRACE_MAX_BYTES, or chunk x obs_cap reaches 2^32 - 1: a smaller chunk or smaller caps");
+    chunk = std::min(chunk, total);
+    int rc = madsim_geo::validate(w, cfg, &g_err);
+    if (rc) return rc;
+    CTX_ENTER(c);
+    hipStream_t st = nullptr;
+    madsim_hip_ctx::TraceSet& S = c->trace[0];
+    madsim_hip_ctx::Census& C = c->census;
+    for (uint64_t done = 0; done < total; done += chunk) {
+        const uint64_t n = std::min(chunk, total - done);
+        Geo G;
+        if ((rc = trace_prepare(c, w, cfg, lim, n, 0, obs_cap, S, G, st))) { nothing(); return rc; }
+        if ((rc = C.ensure(cap, chunk, !list, st))) { nothing(); return rc; }
+        const uint64_t* src = list ? seeds + done : C.h_seeds.p;
+        if (!list) for (uint64_t i = 0; i < n; i++) C.h_seeds.p[i] = seed0 + done + i;
+        TraceSteps step;
+        bool ok = step(hipMemcpyAsync(c->d_seeds, src, n * sizeof(uint64_t), hipMemcpyHostToDevice, st), "hipMemcpyAsync(seeds)");
+        if (ok) ok = step(hipMemsetAsync(C.words, 0, MADSIM_K_CENSUS_WORDS * sizeof(unsigned long long), st), "hipMemsetAsync(census words)");
+        ok = trace_queue(G, S, n, 0, obs_cap, true, st, step, ok);
+        if (ok) {
+            const int refused = madsim_k_launch_census(S.obs, obs_cap, S.len + n, S.out, c->d_seeds, n, cen->include, C.tab, madsim_k_census_slots(cap),
+                                                       C.list, cap, C.words, C.ent, st);
+            if (refused) step.no_build = true;
+            ok = step(refused ? hipSuccess : hipGetLastError(), "census kernel launch");
+        }
+        if (ok) ok = step(hipMemcpyAsync(C.h_words, C.words, MADSIM_K_CENSUS_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st), "hipMemcpyAsync(census words)");
+        // the first entries ride behind the words (a probe vocabulary is small: 4 KB); a chunk with more gets the rest in a copy of its own
+        const uint64_t eager = std::min<uint64_t>(cap, CENSUS_EAGER_ENTRIES);
+        if (ok) ok = step(hipMemcpyAsync(C.h_ent, C.ent, eager * sizeof(madsim_census_value_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync(census entries)");
+        ok = step(hipStreamSynchronize(st), "hipStreamSynchronize");
+        if (step.err != hipSuccess) { C.dirty = true; nothing(); return fail(MADSIM_E_HIP, std::string(step.at) + ": " + hipGetErrorString(step.err)); }
+        if (step.no_build) { nothing(); return fail(MADSIM_E_LIMITS, "no trace kernel build, or sizes the census kernels refuse"); }
+        const unsigned long long* W = C.h_words;
+        const char* const too_many = "census: more than `cap` distinct observed values (a traced time or random value is not a probe vocabulary): raise cap (max_values), or trace less";
+        if (W[1] & MADSIM_K_CENSUS_ERR_CAP) { nothing(); return fail(MADSIM_E_LIMITS, too_many); }      // (the extract pass has cleared the table)
+        if (W[1]) { C.dirty = true; nothing(); return fail(MADSIM_E_HIP, "census: the device table was not clean (internal)"); }
+        const uint64_t nv = W[0];
+        if (nv > eager) {
+            const hipError_t e = hipMemcpy(C.h_ent + eager, C.ent + eager, (nv - eager) * sizeof(madsim_census_value_t), hipMemcpyDeviceToHost);
+            if (e != hipSuccess) { nothing(); return fail(MADSIM_E_HIP, std::string("hipMemcpy(census entries): ") + hipGetErrorString(e)); }
+        }
+        if (madsim_k_fold_census(cen, W, C.h_ent, nv)) { nothing(); return fail(MADSIM_E_LIMITS, too_many); }
+        if (W[12] && cen->n_runner_listed < cen->runner_cap) {                   // chunks and seeds ascend: the first runner_cap met are the smallest
+            hipError_t e = C.h_res.room((size_t)chunk);
+            if (e == hipSuccess) e = hipMemcpy(C.h_res, S.out, n * sizeof(madsim_result_t), hipMemcpyDeviceToHost);
+            if (e != hipSuccess) { nothing(); return fail(MADSIM_E_HIP, std::string("hipMemcpy(census results): ") + hipGetErrorString(e)); }
+            for (uint64_t i = 0; i < n && cen->n_runner_listed < cen->runner_cap; i++)
+                if (MADSIM_IS_RUNNER_VERDICT(C.h_res.p[i].verdict)) cen->runner_seeds[cen->n_runner_listed++] = list ? seeds[done + i] : seed0 + done + i;
+        }
+    }
+    return 0;
+}
+
+int madsim_hip_ctx_census_range(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total,
+                                uint64_t chunk, const madsim_limits_t* lim, madsim_census_t* cen) {
+    return census_run(c, w, cfg, seed0, nullptr, total, chunk, lim, cen, false);
+}
+
+int madsim_hip_ctx_census_seeds(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n,
+                                uint64_t chunk, const madsim_limits_t* lim, madsim_census_t* cen) {
+    return census_run(c, w, cfg, 0, seeds, n, chunk, lim, cen, true);
 }
 
 int madsim_hip_ctx_trace_seeds(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n,
@@ -2253,6 +2418,18 @@ int madsim_hip_diverge_seeds(const madsim_workload_t* wA, const madsim_config_t*
                              uint64_t obs_cap, uint32_t win, madsim_divergence_t* recs, uint64_t* obs_ctx) {
     DefaultPin p;
     return madsim_hip_ctx_diverge_seeds(p.c, wA, cfgA, limA, wB, cfgB, limB, seeds, n, log_cap, obs_cap, win, recs, obs_ctx);
+}
+
+int madsim_hip_census_range(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total, uint64_t chunk,
+                            const madsim_limits_t* lim, madsim_census_t* cen) {
+    DefaultPin p;
+    return madsim_hip_ctx_census_range(p.c, w, cfg, seed0, total, chunk, lim, cen);
+}
+
+int madsim_hip_census_seeds(const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n, uint64_t chunk,
+                            const madsim_limits_t* lim, madsim_census_t* cen) {
+    DefaultPin p;
+    return madsim_hip_ctx_census_seeds(p.c, w, cfg, seeds, n, chunk, lim, cen);
 }
 
 int madsim_hip_run_campaign(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total, uint64_t batch,

@@ -316,6 +316,10 @@ inline constexpr uint64_t group_slot(uint64_t key, uint32_t verdict, uint64_t sl
     return (h ^ (h >> 31)) & (slots - 1);
 }
 
+// The observation census: where a value starts probing in a table of `slots` (a power of two) slots — the same finalizer over the value
+// alone.  One definition for the device (census_fold_kernel) and the host (madsim_k_census_slot, for the tests' colliding values).
+inline constexpr uint64_t census_slot(uint64_t value, uint64_t slots) { return group_slot(value, 0, slots); }
+
 }  // namespace madsim_k
 
 extern "C" {
@@ -445,6 +449,41 @@ int  madsim_k_launch_diverge(const uint8_t* log_a, const uint8_t* log_b, uint64_
                              uint64_t obs_cap, const uint64_t* log_len_a, const uint64_t* log_len_b, const uint64_t* obs_len_a,
                              const uint64_t* obs_len_b, const madsim_result_t* res_a, const madsim_result_t* res_b, const uint64_t* d_seeds,
                              uint64_t n, uint32_t win, madsim_divergence_t* recs, uint64_t* ctx, void* stream);
+// the observation census (madsim_hip_census_range / _seeds), behind the chunk's trace launch on the same stream: the observation rows of `n`
+// seeds (`obs_cap` words each), their TRUE lengths (which may exceed obs_cap; whatever a row holds behind min(len, obs_cap) is ignored), the
+// results and the seeds, reduced where they lie.  `table`: `slots` (a power of two, >= 2 * cap and >= MADSIM_K_CENSUS_MIN_SLOTS) slots of
+// MADSIM_K_CENSUS_SLOT_BYTES, ALL ZERO before the launch and all zero again after it, whatever happened; `list`: cap 32-bit words of scratch
+// (the claimed slots, in arrival order); `words`: MADSIM_K_CENSUS_WORDS words, zero before the launch: {distinct values of the chunk, error
+// word, n_counted[4], n_silent[4], n_truncated, n_observations, n_runner}; `entries`: room for `cap` madsim_census_value_t, the first
+// words[0] written, in arrival order — the host sorts them.  d_seeds ASCEND with the row (the range form's seed0 + i, a strictly ascending
+// list's slice): an entry's first_seed is the seed of the smallest row that held the value.  A value that would be distinct value
+// number cap + 1 sets MADSIM_K_CENSUS_ERR_CAP in the error word and is not inserted; with a non-zero error word no entry is written (words[0] is then not a
+// count of anything).  One wave per row, MADSIM_K_CENSUS_WAVES waves at most.  Returns 0, or -1 without launching anything for n == 0,
+// n > 2^31, n * obs_cap >= 2^32 - 1 (a slot's tag is 1 + the flat index of an observation), obs_cap outside 1 .. MADSIM_CENSUS_MAX_OBS_CAP, an include
+// mask that is 0 or has a bit at or above 4, cap outside 1 .. MADSIM_CENSUS_MAX_VALUES, a table of the wrong size or a missing array.
+#define MADSIM_K_CENSUS_WORDS 16u       /* 64-bit words of a chunk's census report: 13 used  */
+#define MADSIM_K_CENSUS_SLOT_BYTES 32u  /* {tag, n_seeds[4], n_total, max_per_seed, ~smallest row} */
+#define MADSIM_K_CENSUS_MIN_SLOTS 128u  /* a table is never smaller                          */
+#define MADSIM_K_CENSUS_WAVES 1024u     /* = MADSIM_K_DIVERGE_WAVES: 256 workgroups of four waves */
+#define MADSIM_K_CENSUS_ERR_PROBE 1u    /* a probe ran out                                   */
+#define MADSIM_K_CENSUS_ERR_TAG 2u      /* a slot no observation of the chunk can have claimed: the table was not clean */
+#define MADSIM_K_CENSUS_ERR_CAP 4u      /* more than `cap` distinct values                   */
+int  madsim_k_launch_census(const uint64_t* obs, uint64_t obs_cap, const uint64_t* obs_len, const madsim_result_t* res, const uint64_t* d_seeds,
+                            uint64_t n, uint32_t include, uint32_t* table, uint64_t slots, uint32_t* list, uint64_t cap, unsigned long long* words,
+                            madsim_census_value_t* entries, void* stream);
+// ... with the fold kernel's form named: direct != 0 = one table update per row and distinct value, no wave accumulator in LDS (what
+// MADSIM_HIP_CENSUS_DIRECT=1 makes madsim_k_launch_census choose): the correctness baseline and the other side of the A/B
+int  madsim_k_launch_census_form(const uint64_t* obs, uint64_t obs_cap, const uint64_t* obs_len, const madsim_result_t* res, const uint64_t* d_seeds,
+                                 uint64_t n, uint32_t include, uint32_t* table, uint64_t slots, uint32_t* list, uint64_t cap, unsigned long long* words,
+                                 madsim_census_value_t* entries, void* stream, int direct);
+// the smallest table madsim_k_launch_census accepts for `cap` values (madsim_hip.cpp; no device involved)
+uint64_t madsim_k_census_slots(uint64_t cap);
+// the slot at which a value starts probing in a table of `slots` slots (a power of two); probing goes on at slot + 1, wrapping
+uint64_t madsim_k_census_slot(uint64_t value, uint64_t slots);
+// the host fold of one chunk into the caller's census (madsim_hip.cpp; no device involved): `words` (may be null: no totals) are added to the
+// totals, and the chunk's `n` entries (any order, distinct values) merged into cen->values[0 .. n_values), which stay ascending by value —
+// counts added, the max of max_per_seed, the min of first_seed.  Returns 0, or -1 with `cen` untouched when the table would pass cen->cap.
+int  madsim_k_fold_census(madsim_census_t* cen, const unsigned long long* words, const madsim_census_value_t* entries, uint64_t n);
 int  madsim_k_set_max_lds(uint32_t lds_bytes);
 int  madsim_k_variant_vgprs(const madsim_k::VariantSel* v);
 void madsim_k_launch_keyflip(unsigned long long* acc, void* stream);

@@ -24,6 +24,8 @@
 //
 // Integer/indexing work only: no MFMA.  No inter-lane communication: lanes only share the
 // instruction stream, so there is no barrier anywhere in the kernel.
+#include <cstdlib>
+
 #include "kernel/k_mem.h"
 #include "sim_kernel.h"
 
@@ -1078,6 +1080,250 @@ __global__ __launch_bounds__(256) void diverge_kernel(const uint8_t* __restrict_
     }
 }
 
+// ---- the observation census: the distinct traced values of a chunk's counted seeds, each with its per-verdict seed counts ----
+// Two kernels behind the chunk's trace launch.  census_fold_kernel: one wave per row, striding as diverge_kernel does.  A row is COUNTED as in
+// stats_fold_kernel (bit `verdict` of `include`, bits 0-3 only); its visible observations are the first min(len, obs_cap), walked in
+// rounds of 64.  Equal values of a round are combined by group_fold_kernel's ballot loop: one leader per distinct value, holding the
+// popcount.  What a (row, value) adds to the table is {n_seeds[verdict] += 1, n_total += count, max_per_seed = max(count), smallest row =
+// min}; the direct form (census_row_direct) adds it at once, the wave accumulator (census_row_acc) gathers a wave's rows in LDS first.
+// The table is the grouping campaign's (group_insert), keyed by the value alone: a slot's TAG is 1 + the flat index (row * obs_cap + i) of
+// one visible occurrence, the slot's value is read from the rows — which nobody writes while these kernels run —, one 32-bit
+// compare-and-swap claims, every 64-bit value is legal.  Two leaders of one round that meet at one empty slot are two lanes of one
+// atomicCAS: one claims, the other reads the winner's tag, finds another value behind it and probes on.  Every claim takes a number
+// (one atomicAdd on words[0]): below `cap` it appends its slot to `list`, the claim that would be number cap + 1 sets
+// MADSIM_K_CENSUS_ERR_CAP and writes nothing more.  The claims of a chunk are its distinct values, so that bit is a property of the data;
+// once the error word is set, inserts return at once.  The count words ride in lanes 0 .. 10 of each wave and are added once, at its end.
+// census_extract_kernel walks the list: entry j of slot list[j], the slot zeroed again — work proportional to the values.  With the
+// error word set it writes no entry and clears the WHOLE table instead, claims beyond the list included.
+constexpr uint32_t CENSUS_CLAIMS = 0, CENSUS_ERR = 1, CENSUS_COUNTS = 2, CENSUS_SLOT_WORDS = MADSIM_K_CENSUS_SLOT_BYTES / 4;
+
+// the calling lane adds to `value`'s slot: ns[k] seeds of verdict k, `total` occurrences, `maxp` the most inside one seed, `row` the
+// smallest row; one visible occurrence of the value lies at flat index `flat`
+__device__ __forceinline__ void census_insert(const unsigned long long* __restrict__ obs, uint32_t total_obs, uint32_t* __restrict__ table, uint32_t mask,
+                                              uint32_t* __restrict__ list, uint32_t cap, unsigned long long* __restrict__ words,
+                                              unsigned long long value, uint4 ns, uint32_t total, uint32_t maxp, uint32_t row, uint32_t flat) {
+    if (__hip_atomic_load(&words[CENSUS_ERR], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;      // (the chunk has failed already)
+    uint32_t s = (uint32_t)census_slot(value, (uint64_t)mask + 1u);
+    for (uint32_t probe = 0; probe <= mask; probe++, s = (s + 1u) & mask) {
+        uint32_t* const slot = table + (size_t)s * CENSUS_SLOT_WORDS;
+        uint32_t tag = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // (a tag only ever goes from 0 to its value)
+        if (tag == 0) {
+            tag = atomicCAS(slot, 0u, flat + 1u);
+            if (tag == 0) {                                                        // claimed: the slot's value is this observation's
+                const unsigned long long pos = atomicAdd(&words[CENSUS_CLAIMS], 1ull);
+                if (pos >= cap) { atomicOr(&words[CENSUS_ERR], (unsigned long long)MADSIM_K_CENSUS_ERR_CAP); return; }
+                list[pos] = s;
+                tag = flat + 1u;
+            }
+        }
+        bool match = tag == flat + 1u;
+        if (!match) {
+            const uint32_t rep = tag - 1u;
+            if (rep >= total_obs) { atomicOr(&words[CENSUS_ERR], (unsigned long long)MADSIM_K_CENSUS_ERR_TAG); return; }      // (a table that was not clean)
+            match = obs[rep] == value;
+        }
+        if (match) {
+            if (ns.x) atomicAdd(slot + 1, ns.x);
+            if (ns.y) atomicAdd(slot + 2, ns.y);
+            if (ns.z) atomicAdd(slot + 3, ns.z);
+            if (ns.w) atomicAdd(slot + 4, ns.w);
+            atomicAdd(slot + 5, total); atomicMax(slot + 6, maxp); atomicMax(slot + 7, ~row);
+            return;
+        }
+    }
+    atomicOr(&words[CENSUS_ERR], (unsigned long long)MADSIM_K_CENSUS_ERR_PROBE);   // (a full table: only ever behind claim number cap + 1)
+}
+
+// The DIRECT form of a row: one table update per distinct value of the row.  A value that an earlier round of the row held is skipped (the
+// seed counts once), and the leader of a value's FIRST round adds the later rounds' occurrences to its popcount, so it holds the row's
+// full count.  Everything that steers the loops comes from ballots: the wave stays converged up to the insert.
+__device__ __forceinline__ void census_row_direct(const unsigned long long* __restrict__ obs, uint32_t total_obs, uint32_t obs_cap, uint32_t i, uint32_t vis,
+                                                  uint32_t v, uint32_t lane, uint32_t* __restrict__ table, uint32_t mask, uint32_t* __restrict__ list,
+                                                  uint32_t cap, unsigned long long* __restrict__ words) {
+    const unsigned long long* const row = obs + (size_t)i * obs_cap;
+    for (uint32_t k = 0; k * 64u < vis; k++) {
+        const uint32_t idx = k * 64u + lane;
+        const bool have = idx < vis;
+        const unsigned long long val = have ? row[idx] : 0ull;
+        unsigned long long m = __ballot(have);
+        uint32_t cnt = 0;                                                          // non-zero in the leaders
+        while (m) {                                                                // (wave-uniform) one trip per distinct value of the round
+            const int l = __ffsll((long long)m) - 1;
+            const unsigned long long lk = __shfl(val, l);
+            const unsigned long long sm = __ballot(have && val == lk);
+            m &= ~sm;
+            bool earlier = false;                                                  // rounds below k are full: every lane's index is visible
+            for (uint32_t j = 0; j < k && !earlier; j++) earlier = __ballot(row[j * 64u + lane] == lk) != 0;
+            if (earlier) continue;
+            uint32_t c = (uint32_t)__popcll(sm);
+            for (uint32_t j = k + 1u; j * 64u < vis; j++) {
+                const uint32_t x = j * 64u + lane;
+                c += (uint32_t)__popcll(__ballot(x < vis && row[x] == lk));
+            }
+            if ((int)lane == l) cnt = c;
+        }
+        if (cnt) census_insert(obs, total_obs, table, mask, list, cap, words, val, make_uint4(v == 0u, v == 1u, v == 2u, v == 3u), cnt, cnt, i, i * obs_cap + idx);
+    }
+}
+
+// The WAVE ACCUMULATOR: CENSUS_ACC_SLOTS entries per wave in LDS, keyed by value, written by that wave alone — a wave walks its rows one
+// after another.  An entry is CENSUS_ACC_WORDS planes wide: {tag = 1 + flat index of one occurrence (0 = free), value low, value high,
+// stamp = 1 + the last row that held the value, that row's count so far, n_seeds[4], n_total, max_per_seed, smallest row}.  The stamp gives
+// both the once-per-seed rule and the per-row count: a round's leader that finds another row's stamp starts the row (n_seeds[verdict] += 1,
+// count = its popcount), one that finds its own row's adds to the count.  Leaders of one round hold different values, so they update
+// different entries; two of them that meet at one free entry are two lanes of one LDS compare-and-swap — the loser sees, behind the wave
+// fence, the winner's value and probes on.  An entry is only ever claimed while fewer than CENSUS_ACC_FILL are in use, so a probe ends.
+// The accumulator is flushed to the table between rows, when CENSUS_ACC_FILL minus the entries in use is less than the next row's
+// visible length (it could not be sure to hold the row), and once more at the wave's end; a row longer than CENSUS_ACC_FILL takes the
+// direct form.  A flush is one census_insert per entry in use — with a ten-value vocabulary ten per wave, whatever the number of rows.
+constexpr uint32_t CENSUS_ACC_SLOTS = 256, CENSUS_ACC_FILL = 192, CENSUS_ACC_WORDS = 12;
+enum { ACC_TAG, ACC_LO, ACC_HI, ACC_STAMP, ACC_ROWCNT, ACC_NS, ACC_TOTAL = ACC_NS + 4, ACC_MAXP, ACC_FIRST };
+static_assert(ACC_FIRST + 1 == CENSUS_ACC_WORDS && 4 * CENSUS_ACC_WORDS * CENSUS_ACC_SLOTS * sizeof(uint32_t) <= 49152, "the accumulators of a workgroup's four waves");
+
+__device__ __forceinline__ void census_wave_fence() {      // LDS words one lane wrote, read by another lane of the same wave
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// returns the number of entries the row claimed (wave-uniform)
+__device__ __forceinline__ uint32_t census_row_acc(uint32_t* __restrict__ A, const unsigned long long* __restrict__ obs, uint32_t obs_cap, uint32_t i,
+                                                   uint32_t vis, uint32_t v, uint32_t lane, unsigned long long* __restrict__ words) {
+    const unsigned long long* const row = obs + (size_t)i * obs_cap;
+    uint32_t claimed = 0;
+    for (uint32_t k = 0; k * 64u < vis; k++) {
+        const uint32_t idx = k * 64u + lane;
+        const bool have = idx < vis;
+        const unsigned long long val = have ? row[idx] : 0ull;
+        unsigned long long m = __ballot(have);
+        uint32_t cnt = 0;                                                          // non-zero in the leaders
+        while (m) {                                                                // (wave-uniform) one trip per distinct value of the round
+            const int l = __ffsll((long long)m) - 1;
+            const unsigned long long lk = __shfl(val, l);
+            const unsigned long long sm = __ballot(have && val == lk);
+            if ((int)lane == l) cnt = (uint32_t)__popcll(sm);
+            m &= ~sm;
+        }
+        bool pending = cnt != 0;
+        uint32_t s = (uint32_t)census_slot(val, CENSUS_ACC_SLOTS);
+        for (uint32_t probe = 0; __ballot(pending); probe++) {                     // (wave-uniform) the leaders, all at once
+            bool won = false;
+            if (pending && A[ACC_TAG * CENSUS_ACC_SLOTS + s] == 0u) {
+                won = atomicCAS(&A[ACC_TAG * CENSUS_ACC_SLOTS + s], 0u, i * obs_cap + idx + 1u) == 0u;
+                if (won) {                                                         // (every other plane of a free entry is zero)
+                    A[ACC_LO * CENSUS_ACC_SLOTS + s] = (uint32_t)val;
+                    A[ACC_HI * CENSUS_ACC_SLOTS + s] = (uint32_t)(val >> 32);
+                    A[ACC_FIRST * CENSUS_ACC_SLOTS + s] = i;
+                }
+            }
+            claimed += (uint32_t)__popcll(__ballot(won));
+            census_wave_fence();
+            if (pending) {
+                const unsigned long long held = (unsigned long long)A[ACC_LO * CENSUS_ACC_SLOTS + s] | (unsigned long long)A[ACC_HI * CENSUS_ACC_SLOTS + s] << 32;
+                if (held == val) {                                                 // (the entry is in use: this lane's claim, or an earlier one)
+                    uint32_t rc = cnt;
+                    if (A[ACC_STAMP * CENSUS_ACC_SLOTS + s] != i + 1u) {
+                        A[ACC_STAMP * CENSUS_ACC_SLOTS + s] = i + 1u;
+                        A[(ACC_NS + v) * CENSUS_ACC_SLOTS + s] += 1u;
+                    } else {
+                        rc += A[ACC_ROWCNT * CENSUS_ACC_SLOTS + s];
+                    }
+                    A[ACC_ROWCNT * CENSUS_ACC_SLOTS + s] = rc;
+                    A[ACC_TOTAL * CENSUS_ACC_SLOTS + s] += cnt;
+                    if (rc > A[ACC_MAXP * CENSUS_ACC_SLOTS + s]) A[ACC_MAXP * CENSUS_ACC_SLOTS + s] = rc;
+                    pending = false;
+                } else if (probe >= CENSUS_ACC_SLOTS) {                            // (cannot happen below CENSUS_ACC_FILL entries in use)
+                    atomicOr(&words[CENSUS_ERR], (unsigned long long)MADSIM_K_CENSUS_ERR_PROBE);
+                    pending = false;
+                } else {
+                    s = (s + 1u) & (CENSUS_ACC_SLOTS - 1u);
+                }
+            }
+            census_wave_fence();
+        }
+    }
+    return claimed;
+}
+
+__device__ __forceinline__ void census_acc_flush(uint32_t* __restrict__ A, uint32_t lane, const unsigned long long* __restrict__ obs, uint32_t total_obs,
+                                                 uint32_t* __restrict__ table, uint32_t mask, uint32_t* __restrict__ list, uint32_t cap,
+                                                 unsigned long long* __restrict__ words) {
+    census_wave_fence();
+    for (uint32_t s = lane; s < CENSUS_ACC_SLOTS; s += 64u) {
+        const uint32_t tag = A[ACC_TAG * CENSUS_ACC_SLOTS + s];
+        if (tag == 0u) continue;
+        const unsigned long long value = (unsigned long long)A[ACC_LO * CENSUS_ACC_SLOTS + s] | (unsigned long long)A[ACC_HI * CENSUS_ACC_SLOTS + s] << 32;
+        const uint4 ns = make_uint4(A[(ACC_NS + 0) * CENSUS_ACC_SLOTS + s], A[(ACC_NS + 1) * CENSUS_ACC_SLOTS + s], A[(ACC_NS + 2) * CENSUS_ACC_SLOTS + s],
+                                    A[(ACC_NS + 3) * CENSUS_ACC_SLOTS + s]);
+        census_insert(obs, total_obs, table, mask, list, cap, words, value, ns, A[ACC_TOTAL * CENSUS_ACC_SLOTS + s], A[ACC_MAXP * CENSUS_ACC_SLOTS + s],
+                      A[ACC_FIRST * CENSUS_ACC_SLOTS + s], tag - 1u);
+        for (uint32_t q = 0; q < CENSUS_ACC_WORDS; q++) A[q * CENSUS_ACC_SLOTS + s] = 0u;
+    }
+    census_wave_fence();
+}
+
+// ACC = false: every row in the direct form — the correctness baseline and the other side of the A/B (MADSIM_HIP_CENSUS_DIRECT=1)
+template <bool ACC>
+__global__ __launch_bounds__(256) void census_fold_kernel(const unsigned long long* __restrict__ obs, uint32_t obs_cap,
+                                                          const unsigned long long* __restrict__ obs_len, const madsim_result_t* __restrict__ res,
+                                                          uint32_t n, uint32_t include, uint32_t* __restrict__ table, uint32_t mask,
+                                                          uint32_t* __restrict__ list, uint32_t cap, unsigned long long* __restrict__ words) {
+    __shared__ uint32_t lds[ACC ? 4 * CENSUS_ACC_WORDS * CENSUS_ACC_SLOTS : 1];
+    const uint32_t lane = threadIdx.x & 63, total_obs = n * obs_cap;
+    uint32_t* const A = lds + (ACC ? (threadIdx.x >> 6) * CENSUS_ACC_WORDS * CENSUS_ACC_SLOTS : 0u);
+    uint32_t in_use = 0;                                                           // entries of A in use (wave-uniform)
+    if (ACC) {
+        for (uint32_t q = lane; q < CENSUS_ACC_WORDS * CENSUS_ACC_SLOTS; q += 64u) A[q] = 0u;
+        census_wave_fence();
+    }
+    uint32_t acc = 0;                                                              // lane k < 11: what this wave adds to words[2 + k]
+    for (uint32_t i = blockIdx.x * 4u + (threadIdx.x >> 6); i < n; i += gridDim.x * 4u) {      // (wave-uniform)
+        const uint32_t v = reinterpret_cast<const uint32_t*>(res + i)[0];
+        if (v >= 4u) { acc += lane == 10u; continue; }                             // a runner verdict: the row is not read
+        if (!((include >> v) & 1u)) continue;
+        const unsigned long long len = obs_len[i];
+        const uint32_t vis = len < obs_cap ? (uint32_t)len : obs_cap;
+        acc += (lane == v) + (lane == 4u + v && vis == 0u) + (lane == 8u && len > obs_cap) + (lane == 9u ? vis : 0u);
+        if (!ACC || vis > CENSUS_ACC_FILL) {
+            census_row_direct(obs, total_obs, obs_cap, i, vis, v, lane, table, mask, list, cap, words);
+        } else {
+            if (in_use + vis > CENSUS_ACC_FILL) { census_acc_flush(A, lane, obs, total_obs, table, mask, list, cap, words); in_use = 0; }
+            in_use += census_row_acc(A, obs, obs_cap, i, vis, v, lane, words);
+        }
+    }
+    if (ACC && in_use) census_acc_flush(A, lane, obs, total_obs, table, mask, list, cap, words);
+    if (lane < 11u && acc) atomicAdd(&words[CENSUS_COUNTS + lane], (unsigned long long)acc);
+}
+
+__global__ __launch_bounds__(256) void census_extract_kernel(const unsigned long long* __restrict__ obs, uint32_t total_obs,
+                                                             const unsigned long long* __restrict__ seeds, uint32_t n, uint32_t* __restrict__ table,
+                                                             uint32_t mask, const uint32_t* __restrict__ list, uint32_t cap,
+                                                             unsigned long long* __restrict__ words, unsigned long long* __restrict__ entries) {
+    uint4* const t = reinterpret_cast<uint4*>(table);                              // a slot is two of them
+    if (words[CENSUS_ERR]) {                                                       // (nobody sets it in this branch: uniform over the grid)
+        for (uint64_t j = blockIdx.x * 256u + threadIdx.x; j < 2ull * ((uint64_t)mask + 1u); j += gridDim.x * 256u) t[j] = uint4{0, 0, 0, 0};
+        return;
+    }
+    const unsigned long long claimed = words[CENSUS_CLAIMS];                       // (nobody adds to it in this kernel)
+    const uint32_t nv = claimed < cap ? (uint32_t)claimed : cap;
+    for (uint32_t j = blockIdx.x * 256u + threadIdx.x; j < nv; j += gridDim.x * 256u) {
+        const uint32_t s = list[j] & mask;
+        const uint4 e0 = t[2 * (size_t)s], e1 = t[2 * (size_t)s + 1];
+        t[2 * (size_t)s] = uint4{0, 0, 0, 0}; t[2 * (size_t)s + 1] = uint4{0, 0, 0, 0};
+        const uint32_t rep = e0.x - 1u, first = ~e1.w;
+        unsigned long long* const p = entries + 8 * (size_t)j;
+        if (e0.x == 0 || rep >= total_obs || first >= n) {                         // (a table that was not clean)
+            atomicOr(&words[CENSUS_ERR], (unsigned long long)MADSIM_K_CENSUS_ERR_TAG);
+            for (int q = 0; q < 8; q++) p[q] = 0;
+            continue;
+        }
+        p[0] = obs[rep];
+        p[1] = e0.y; p[2] = e0.z; p[3] = e0.w; p[4] = e1.x;
+        p[5] = e1.y;
+        p[6] = seeds[first];
+        p[7] = e1.z;
+    }
+}
+
 // one kernel per row of variant_table (sim_kernel.h), same macro, same order
 #define MADSIM_VARIANT_KERNEL(T_, S_, L_, F_, R_, G_) (const void*)sim_kernel<Variant<T_, S_, L_, F_, R_, G_>>,
 static const void* const variant_kernels[] = {MADSIM_FOR_EACH_VARIANT(MADSIM_VARIANT_KERNEL)};
@@ -1368,6 +1614,39 @@ extern "C" int madsim_k_launch_diverge(const uint8_t* log_a, const uint8_t* log_
                        (const unsigned long long*)log_len_b, (const unsigned long long*)obs_len_a, (const unsigned long long*)obs_len_b, res_a, res_b,
                        (const unsigned long long*)d_seeds, n, win, reinterpret_cast<unsigned long long*>(recs), (unsigned long long*)ctx);
     return 0;
+}
+
+// Rows, lengths, results and seeds of the chunk's n seeds; table: `slots` zeroed slots; list: `cap` words of scratch; words:
+// MADSIM_K_CENSUS_WORDS zeroed words; entries: room for `cap` (sim_kernel.h).  Returns 0, or -1 (nothing launched) for sizes the kernels
+// are not written for.
+// `direct` != 0: every row in the direct form, no wave accumulator — the same bytes either way.
+extern "C" int madsim_k_launch_census_form(const uint64_t* obs, uint64_t obs_cap, const uint64_t* obs_len, const madsim_result_t* res,
+                                           const uint64_t* d_seeds, uint64_t n, uint32_t include, uint32_t* table, uint64_t slots, uint32_t* list,
+                                           uint64_t cap, unsigned long long* words, madsim_census_value_t* entries, void* stream, int direct) {
+    static_assert(sizeof(madsim_census_value_t) == 64 && 2 * sizeof(uint4) == MADSIM_K_CENSUS_SLOT_BYTES && sizeof(madsim_result_t) == 48, "record layout");
+    if (n == 0 || obs_cap == 0 || obs_cap > MADSIM_CENSUS_MAX_OBS_CAP || n >= 0xffffffffull / obs_cap || n > (1ull << 31)) return -1;      // n * obs_cap < 2^32 - 1; the row index plus a grid stride stays 32-bit
+    if (include == 0 || (include & ~0xfu) || cap == 0 || cap > MADSIM_CENSUS_MAX_VALUES) return -1;
+    if ((slots & (slots - 1)) || slots < 2 * cap || slots < MADSIM_K_CENSUS_MIN_SLOTS || slots > (1ull << 26)) return -1;
+    if (!obs || !obs_len || !res || !d_seeds || !table || !list || !words || !entries || ((uintptr_t)table & 15u)) return -1;
+    const uint64_t waves = n < MADSIM_K_CENSUS_WAVES ? n : MADSIM_K_CENSUS_WAVES;        // one wave per row, 256 workgroups at most
+    const auto fold = direct ? madsim_k::census_fold_kernel<false> : madsim_k::census_fold_kernel<true>;
+    hipLaunchKernelGGL(fold, dim3((uint32_t)((waves + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+                       (const unsigned long long*)obs, (uint32_t)obs_cap, (const unsigned long long*)obs_len, res, (uint32_t)n, include, table,
+                       (uint32_t)(slots - 1), list, (uint32_t)cap, words);
+    uint32_t xgrid = (uint32_t)((cap + 255) / 256);        // the extraction pass: as many threads as there can be values, 64 workgroups at most
+    if (xgrid > 64) xgrid = 64;
+    hipLaunchKernelGGL(madsim_k::census_extract_kernel, dim3(xgrid), dim3(256), 0, (hipStream_t)stream, (const unsigned long long*)obs,
+                       (uint32_t)(n * obs_cap), (const unsigned long long*)d_seeds, (uint32_t)n, table, (uint32_t)(slots - 1), (const uint32_t*)list,
+                       (uint32_t)cap, words, reinterpret_cast<unsigned long long*>(entries));
+    return 0;
+}
+
+// (MADSIM_HIP_CENSUS_DIRECT=1 in the environment: the direct form — a diagnostic / A-B switch, results are the same either way)
+extern "C" int madsim_k_launch_census(const uint64_t* obs, uint64_t obs_cap, const uint64_t* obs_len, const madsim_result_t* res, const uint64_t* d_seeds,
+                                      uint64_t n, uint32_t include, uint32_t* table, uint64_t slots, uint32_t* list, uint64_t cap,
+                                      unsigned long long* words, madsim_census_value_t* entries, void* stream) {
+    static const bool direct = [] { const char* e = getenv("MADSIM_HIP_CENSUS_DIRECT"); return e && atoi(e) != 0; }();      // (unset, empty or 0: the accumulator)
+    return madsim_k_launch_census_form(obs, obs_cap, obs_len, res, d_seeds, n, include, table, slots, list, cap, words, entries, stream, direct);
 }
 
 extern "C" void madsim_k_launch_keyflip(unsigned long long* acc, void* stream) {

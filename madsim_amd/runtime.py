@@ -159,6 +159,14 @@ def lib():
             getattr(L, f"madsim_hip_{form}_multi").argtypes = [C.POINTER(ctxp), C.c_int] + base
         L.madsim_hip_diverge_seeds.argtypes = side + side + [u64p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
         L.madsim_hip_ctx_diverge_seeds.argtypes = [ctxp] + L.madsim_hip_diverge_seeds.argtypes
+        # the observation census: (seed0, total) or (seeds, n), then chunk, limits and the madsim_census_t
+        L.madsim_hip_census_range.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(A.Limits),
+                                              C.POINTER(A.Census)]
+        L.madsim_hip_census_seeds.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), u64p, C.c_uint64, C.c_uint64, C.POINTER(A.Limits),
+                                              C.POINTER(A.Census)]
+        L.madsim_hip_ctx_census_range.argtypes = [ctxp] + L.madsim_hip_census_range.argtypes
+        L.madsim_hip_ctx_census_seeds.argtypes = [ctxp] + L.madsim_hip_census_seeds.argtypes
+        L.madsim_k_fold_census.argtypes = [C.POINTER(A.Census), C.c_void_p, C.c_void_p, C.c_uint64]
         # the sweep campaigns: one signature for the range (seeds NULL) and the list (seed0 0)
         L.madsim_hip_run_sweep_campaign.argtypes = [C.POINTER(A.SweepVariant), C.c_uint32, C.c_uint64, C.c_uint64, u64p, C.c_uint64, C.c_uint32,
                                                     C.c_uint32, C.POINTER(A.Sweep)]
@@ -438,6 +446,123 @@ def diverge_seeds(workload, seeds, other=None, config=None, other_config=None, l
         init(0)
     return _diverge_seeds(lib().madsim_hip_diverge_seeds, workload, seeds, other, config, other_config, limits, other_limits, log_cap, obs_cap,
                           window, resolve)
+
+
+class Census:
+    """Which traced values the seeds of a census reached, by verdict (runtime.census).  `values`: ndarray[A.CENSUS_VALUE_DTYPE], ascending by
+    `value` — per distinct value the counted seeds of each verdict that observed it at least once (`n_seeds[4]`), its occurrences over them
+    (`n_total`), the smallest such seed (`first_seed`) and the most occurrences inside one seed (`max_per_seed`).  `n_counted[4]` /
+    `n_silent[4]`: counted seeds per verdict / those of them without a visible observation; `n_truncated`: counted seeds with more than
+    `obs_cap` observations, whose later values are not in the table; `n_observations`: the sum of every n_total; `n_runner` seeds were left
+    with a runner verdict and are counted nowhere, `runner_seeds` (ndarray[uint64], ascending) the ones that were listed.  Everything is an
+    exact integer."""
+
+    def __init__(self, values, n_counted, n_silent, n_truncated, n_observations, n_runner, runner_seeds, include, obs_cap):
+        self.values = values
+        self.n_counted, self.n_silent = tuple(int(x) for x in n_counted), tuple(int(x) for x in n_silent)
+        self.n_truncated, self.n_observations, self.n_runner = int(n_truncated), int(n_observations), int(n_runner)
+        self.runner_seeds, self.include, self.obs_cap = runner_seeds, include, obs_cap
+
+    def __len__(self):
+        return len(self.values)
+
+    def __repr__(self):
+        return (f"Census({len(self.values)} values over {sum(self.n_counted)} counted seeds, n_counted={self.n_counted}, n_silent={self.n_silent}, "
+                f"n_truncated={self.n_truncated}, n_runner={self.n_runner})")
+
+    def tobytes(self):
+        """The whole report as bytes: two censuses are the same census exactly when these are equal."""
+        totals = np.array(self.n_counted + self.n_silent + (self.n_truncated, self.n_observations, self.n_runner), dtype=np.uint64)
+        return self.values.tobytes() + totals.tobytes() + np.asarray(self.runner_seeds, dtype=np.uint64).tobytes()
+
+    def row(self, v):
+        """The table's record of value `v` (a numpy record of A.CENSUS_VALUE_DTYPE), or None when no counted seed observed it."""
+        i = int(np.searchsorted(self.values["value"], np.uint64(v)))
+        return self.values[i] if i < len(self.values) and int(self.values["value"][i]) == int(v) else None
+
+    def reached(self, v):
+        """How many counted seeds observed `v` at least once (0: never)."""
+        r = self.row(v)
+        return 0 if r is None else int(r["n_seeds"].sum())
+
+    def never(self, expected_values):
+        """The sometimes-assertion: those of `expected_values` that no counted seed observed, in the order given."""
+        return [int(v) for v in expected_values if self.row(v) is None]
+
+    def failing_share(self, v):
+        """(share of the seeds that observed `v` which fail, share of all counted seeds which fail), each a fractions.Fraction — a failing seed
+        is a counted one whose verdict is not PASS.  None in place of a share over no seeds."""
+        r = self.row(v)
+        ns = [0, 0, 0, 0] if r is None else [int(x) for x in r["n_seeds"]]
+        share = lambda n: Fraction(sum(n[1:]), sum(n)) if sum(n) else None         # noqa: E731
+        return share(ns), share(self.n_counted)
+
+    def merge(self, other):
+        """The census of the union of two DISJOINT seed sets taken under the same include mask and obs_cap: exact, in either order."""
+        if (self.include, self.obs_cap) != (other.include, other.obs_cap):
+            raise MadsimHipError("Census.merge: the two censuses differ in include or obs_cap")
+        out = np.zeros(len(self.values) + len(other.values), dtype=A.CENSUS_VALUE_DTYPE)
+        out[:len(self.values)] = self.values
+        cen = A.Census(include=self.include, obs_cap=self.obs_cap, cap=max(len(out), 1), n_values=len(self.values))
+        cen.values = out.ctypes.data_as(C.POINTER(A.CensusValue))
+        add = np.ascontiguousarray(other.values)
+        if lib().madsim_k_fold_census(C.byref(cen), None, add.ctypes.data_as(C.c_void_p), len(add)):
+            raise MadsimHipError("Census.merge: madsim_k_fold_census failed")
+        add4 = lambda a, b: tuple(x + y for x, y in zip(a, b))                      # noqa: E731
+        runner = np.sort(np.concatenate([np.asarray(self.runner_seeds, dtype=np.uint64), np.asarray(other.runner_seeds, dtype=np.uint64)]))
+        return Census(out[:cen.n_values].copy(), add4(self.n_counted, other.n_counted), add4(self.n_silent, other.n_silent),
+                      self.n_truncated + other.n_truncated, self.n_observations + other.n_observations, self.n_runner + other.n_runner, runner,
+                      self.include, self.obs_cap)
+
+
+def _census(call_range, call_seeds, workload, seed0, total, seeds, include, obs_cap, max_values, chunk, config, limits, resolve):
+    """One census call — `call_range(cfg, seed0, total, chunk, lim, cen)` or `call_seeds(cfg, seeds*, n, chunk, lim, cen)`, a madsim_hip_*census_*
+    entry point with its context and workload bound — and then, round by round, one list call over the seeds the last one left with a
+    runner verdict, under grown_limits(workload, limits, r), merged in: what _trace_seeds does for a list of seeds."""
+    cfg, lim0 = config or A.Config.default(), limits or A.Limits()
+    mask = _include_mask(include)
+    rounds = 0 if resolve is None or resolve is False else A.RESOLVE_DEFAULT_ROUNDS if resolve is True else int(resolve)
+    if not 0 <= rounds <= A.RESOLVE_MAX_ROUNDS:
+        raise MadsimHipError(f"resolve: None, True or a number of rounds 1..{A.RESOLVE_MAX_ROUNDS}, got {resolve!r}")
+
+    def one(lim, sa, s0, n):
+        values, runner = np.zeros(max(int(max_values), 1), dtype=A.CENSUS_VALUE_DTYPE), np.zeros(max(n, 1), dtype=np.uint64)
+        cen = A.Census(include=mask, obs_cap=obs_cap, cap=max_values, runner_cap=n)
+        cen.values, cen.runner_seeds = values.ctypes.data_as(C.POINTER(A.CensusValue)), runner.ctypes.data_as(C.POINTER(C.c_uint64))
+        if sa is None:
+            _check(call_range(C.byref(cfg), s0, n, chunk, C.byref(lim), C.byref(cen)))
+        else:
+            _check(call_seeds(C.byref(cfg), _seeds_ptr(sa), n, chunk, C.byref(lim), C.byref(cen)))
+        return Census(values[:cen.n_values].copy(), cen.n_counted, cen.n_silent, cen.n_truncated, cen.n_observations, cen.n_runner,
+                      runner[:cen.n_runner_listed].copy(), mask, obs_cap)
+
+    sa = None if seeds is None else seed_list(seeds)
+    cen = one(lim0, sa, int(seed0), int(total) if sa is None else len(sa))
+    for r in range(1, rounds + 1):
+        if not len(cen.runner_seeds):
+            break
+        more = one(grown_limits(workload, lim0, r), cen.runner_seeds, 0, len(cen.runner_seeds))
+        cen.n_runner, cen.runner_seeds = 0, np.zeros(0, dtype=np.uint64)
+        cen = cen.merge(more)
+        if len(cen.values) > max_values:
+            raise MadsimHipError(f"census: more than max_values = {max_values} distinct observed values once the runner seeds are settled")
+    return cen
+
+
+def census(workload, seed0=0, total=0, seeds=None, include=(A.PASS, A.PANIC, A.DEADLOCK, A.TIME_LIMIT), obs_cap=256, max_values=4096, chunk=0,
+           config=None, limits=None, resolve=True):
+    """madsim_hip_census_range / madsim_hip_census_seeds: which traced values the seeds [seed0, seed0 + total) — or the strictly ascending
+    `seeds` (never sorted silently: pass numpy.unique(seeds)) — reach, by verdict, reduced on the device: returns a Census.  A seed is
+    counted when its verdict is in `include`; the first `obs_cap` observations of a seed are visible; more than `max_values` distinct
+    values is MadsimHipError (a traced time or random value is not a probe vocabulary); `chunk` = seeds per trace launch, 0 = the
+    library's default — it never shows in the result.  resolve=True | rounds: the seeds a call leaves with a runner verdict are run again
+    in one further list call per round under grown_limits(workload, limits, r) and merged in, as trace_seeds settles its seeds;
+    resolve=None / False: the one call, runner seeds counted in n_runner and listed in runner_seeds."""
+    if _inited_device is None:
+        init(0)
+    L = lib()
+    return _census(lambda *a: L.madsim_hip_census_range(workload.ref(), *a), lambda *a: L.madsim_hip_census_seeds(workload.ref(), *a), workload,
+                   seed0, total, seeds, include, obs_cap, max_values, chunk, config, limits, resolve)
 
 
 def observe_seed(workload, seed, config=None, limits=None, cap=1 << 16, resolve=True):
@@ -1139,6 +1264,14 @@ class Context:
         """runtime.diverge_seeds on this context (madsim_hip_ctx_diverge_seeds)."""
         return _diverge_seeds(lambda *a: lib().madsim_hip_ctx_diverge_seeds(self._h, *a), workload, seeds, other, config, other_config, limits,
                               other_limits, log_cap, obs_cap, window, resolve)
+
+    def census(self, workload, seed0=0, total=0, seeds=None, include=(A.PASS, A.PANIC, A.DEADLOCK, A.TIME_LIMIT), obs_cap=256, max_values=4096,
+               chunk=0, config=None, limits=None, resolve=True):
+        """runtime.census on this context (madsim_hip_ctx_census_range / madsim_hip_ctx_census_seeds)."""
+        L = lib()
+        return _census(lambda *a: L.madsim_hip_ctx_census_range(self._h, workload.ref(), *a),
+                       lambda *a: L.madsim_hip_ctx_census_seeds(self._h, workload.ref(), *a), workload, seed0, total, seeds, include, obs_cap,
+                       max_values, chunk, config, limits, resolve)
 
     def observe_seed(self, workload, seed, config=None, limits=None, cap=1 << 16, resolve=True):
         """runtime.observe_seed on this context."""
