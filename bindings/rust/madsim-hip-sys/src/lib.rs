@@ -180,6 +180,31 @@ pub struct madsim_census_t {
 
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
+pub struct madsim_probe_set_t {
+    pub set: u64,
+    pub n_seeds: [u64; 4],
+    pub first_seed: [u64; 4],
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct madsim_probe_sets_t {
+    pub include: u32,
+    pub obs_cap: u32,
+    pub vocab: *const u64,
+    pub n_vocab: u64,
+    pub sets: *const madsim_probe_set_t,
+    pub cap: u64,
+    pub runner_seeds: *const u64,
+    pub runner_cap: u64,
+    pub n_sets: u64,
+    pub n_counted: [u64; 4],
+    pub n_runner: u64,
+    pub n_runner_listed: u64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
 pub struct madsim_campaign_t {
     pub seeds_run: u64,
     pub batches_run: u64,
@@ -504,6 +529,10 @@ pub const MADSIM_DIVERGE_INCOMPARABLE: u32 = 4;
 pub const MADSIM_DIVERGE_MAX_WIN: u32 = 8;
 pub const MADSIM_CENSUS_MAX_VALUES: u32 = 1048576;
 pub const MADSIM_CENSUS_MAX_OBS_CAP: u32 = 1024;
+pub const MADSIM_PROBE_SETS_MAX_VOCAB: u32 = 62;
+pub const MADSIM_PROBE_SETS_MAX: u32 = 1048576;
+pub const MADSIM_PROBE_SET_OTHER: u64 = 0x4000000000000000;
+pub const MADSIM_PROBE_SET_TRUNCATED: u64 = 0x8000000000000000;
 pub const MADSIM_CAMPAIGN_STOP_AT_FAILURE: u32 = 1;
 pub const MADSIM_CAMPAIGN_LIST_RUNNER: u32 = 2;
 pub const MADSIM_CAMPAIGN_STOP_AT_CAP: u32 = 4;
@@ -570,6 +599,8 @@ extern "C" {
     pub fn madsim_hip_diverge_seeds(wA: *const madsim_workload_t, cfgA: *const madsim_config_t, limA: *const madsim_limits_t, wB: *const madsim_workload_t, cfgB: *const madsim_config_t, limB: *const madsim_limits_t, seeds: *const u64, n: u64, log_cap: u64, obs_cap: u64, win: u32, recs: *mut madsim_divergence_t, obs_ctx: *mut u64) -> c_int;
     pub fn madsim_hip_census_range(w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, chunk: u64, lim: *const madsim_limits_t, cen: *mut madsim_census_t) -> c_int;
     pub fn madsim_hip_census_seeds(w: *const madsim_workload_t, cfg: *const madsim_config_t, seeds: *const u64, n: u64, chunk: u64, lim: *const madsim_limits_t, cen: *mut madsim_census_t) -> c_int;
+    pub fn madsim_hip_probe_sets_range(w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, chunk: u64, lim: *const madsim_limits_t, ps: *mut madsim_probe_sets_t) -> c_int;
+    pub fn madsim_hip_probe_sets_seeds(w: *const madsim_workload_t, cfg: *const madsim_config_t, seeds: *const u64, n: u64, chunk: u64, lim: *const madsim_limits_t, ps: *mut madsim_probe_sets_t) -> c_int;
     pub fn madsim_hip_ctx_run_batch(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, count: u64, lim: *const madsim_limits_t, out: *mut madsim_result_t, summary: *mut madsim_summary_t) -> c_int;
     pub fn madsim_hip_ctx_run_batch_auto(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, count: u64, lim: *const madsim_limits_t, out: *mut madsim_result_t, summary: *mut madsim_summary_t, max_rounds: c_int) -> c_int;
     pub fn madsim_hip_ctx_run_batch_device(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, count: u64, lim: *const madsim_limits_t, d_out: *mut c_void, stream: *mut c_void, summary: *mut madsim_summary_t) -> c_int;
@@ -581,6 +612,8 @@ extern "C" {
     pub fn madsim_hip_ctx_diverge_seeds(ctx: *mut madsim_hip_ctx_t, wA: *const madsim_workload_t, cfgA: *const madsim_config_t, limA: *const madsim_limits_t, wB: *const madsim_workload_t, cfgB: *const madsim_config_t, limB: *const madsim_limits_t, seeds: *const u64, n: u64, log_cap: u64, obs_cap: u64, win: u32, recs: *mut madsim_divergence_t, obs_ctx: *mut u64) -> c_int;
     pub fn madsim_hip_ctx_census_range(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, chunk: u64, lim: *const madsim_limits_t, cen: *mut madsim_census_t) -> c_int;
     pub fn madsim_hip_ctx_census_seeds(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seeds: *const u64, n: u64, chunk: u64, lim: *const madsim_limits_t, cen: *mut madsim_census_t) -> c_int;
+    pub fn madsim_hip_ctx_probe_sets_range(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, chunk: u64, lim: *const madsim_limits_t, ps: *mut madsim_probe_sets_t) -> c_int;
+    pub fn madsim_hip_ctx_probe_sets_seeds(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seeds: *const u64, n: u64, chunk: u64, lim: *const madsim_limits_t, ps: *mut madsim_probe_sets_t) -> c_int;
     pub fn madsim_hip_run_batch_multi(ctxs: *const *mut madsim_hip_ctx_t, n_ctx: c_int, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, count: u64, lim: *const madsim_limits_t, out: *mut madsim_result_t, summary: *mut madsim_summary_t, max_rounds: c_int) -> c_int;
     pub fn madsim_hip_ctx_run_campaign(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, batch: u64, in_flight: u32, flags: u32, lim: *const madsim_limits_t, out: *mut madsim_campaign_t) -> c_int;
     pub fn madsim_hip_run_campaign(w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, batch: u64, in_flight: u32, flags: u32, lim: *const madsim_limits_t, out: *mut madsim_campaign_t) -> c_int;

@@ -308,6 +308,62 @@ impl Census {
     }
 }
 
+/// Which combinations of the vocabulary's values the seeds reached, by verdict (`Builder::probe_sets` / `probe_sets_seeds`): `vocabulary`,
+/// value `i` owning bit `i` of a set word; `sets`, ascending by set word — per distinct set the counted seeds of each verdict with exactly
+/// this set and the smallest of them —; `totals`, the counts of `madsim_probe_sets_t` (its pointers are null here); `runner_seeds`, the
+/// seeds left with a runner verdict, ascending: they are counted nowhere.
+#[derive(Clone, Debug)]
+pub struct ProbeSets {
+    pub vocabulary: Vec<u64>,
+    pub sets: Vec<sys::madsim_probe_set_t>,
+    pub totals: sys::madsim_probe_sets_t,
+    pub runner_seeds: Vec<u64>,
+}
+
+impl ProbeSets {
+    /// The set-word bits of the vocabulary values `values` (a value outside the vocabulary owns no bit).
+    pub fn mask(&self, values: &[u64]) -> u64 {
+        values.iter().filter_map(|v| self.vocabulary.iter().position(|x| x == v)).fold(0, |m, i| m | 1u64 << i)
+    }
+
+    /// Counted seeds of the verdicts in `verdicts` (a bit mask, 0xf = all) that reached every value of `all_of` and none of `none_of`.
+    pub fn count(&self, all_of: &[u64], none_of: &[u64], verdicts: u32) -> u64 {
+        let (want, avoid) = (self.mask(all_of), self.mask(none_of));
+        self.sets.iter().filter(|e| e.set & want == want && e.set & avoid == 0)
+            .map(|e| (0..4).filter(|k| verdicts >> k & 1 == 1).map(|k| e.n_seeds[k]).sum::<u64>()).sum()
+    }
+
+    /// The sets that occur under PASS and under a failing verdict: (set word, the smallest passing seed, the smallest failing seed).
+    pub fn mixed(&self) -> Vec<(u64, u64, u64)> {
+        self.sets.iter().filter_map(|e| {
+            let fail = (1..4).filter(|&k| e.n_seeds[k] > 0).map(|k| e.first_seed[k]).min();
+            match fail { Some(f) if e.n_seeds[0] > 0 => Some((e.set, e.first_seed[0], f)), _ => None }
+        }).collect()
+    }
+
+    /// A greedy set cover of every reached vocabulary value: each round the entry that adds the most new values, ties to the smaller set
+    /// word; one seed (its smallest) per chosen entry, ascending and unique — a corpus for `Builder::over_seeds`.
+    pub fn cover(&self) -> Vec<u64> {
+        let vmask = if self.vocabulary.len() >= 64 { u64::MAX } else { (1u64 << self.vocabulary.len()) - 1 };
+        let mut missing = self.sets.iter().fold(0u64, |m, e| m | (e.set & vmask));
+        let mut chosen = Vec::new();
+        while missing != 0 {
+            let mut best: Option<&sys::madsim_probe_set_t> = None;
+            for e in &self.sets {                                        // ascending by set word: the first of the best wins
+                if best.map_or(true, |b| (e.set & missing).count_ones() > (b.set & missing).count_ones()) {
+                    best = Some(e);
+                }
+            }
+            let e = best.unwrap();
+            chosen.push((0..4).filter(|&k| e.n_seeds[k] > 0).map(|k| e.first_seed[k]).min().unwrap_or(0));
+            missing &= !e.set;
+        }
+        chosen.sort_unstable();
+        chosen.dedup();
+        chosen
+    }
+}
+
 /// The `obs_hash` of a run that traced `values`, in that order: 64-bit FNV-1a over whole values (the offset basis for none).
 pub fn fold_observations(values: &[u64]) -> u64 {
     values.iter().fold(0xCBF2_9CE4_8422_2325u64, |h, v| (h ^ v).wrapping_mul(0x100_0000_01B3))
@@ -636,6 +692,109 @@ impl Builder {
             c.totals.n_runner_listed = more.totals.n_runner_listed;
             c.totals.n_values = merged.len() as u64;
             c.values = merged;
+            c.runner_seeds = more.runner_seeds;
+        }
+        Ok(c)
+    }
+
+    /// Which combinations of the values of `vocabulary` (1 .. 62 distinct values) the seeds `self.seed .. self.seed + self.count` reach, by
+    /// verdict (`madsim_hip_ctx_probe_sets_range`): the range run on the trace build and reduced on the device to one entry per distinct
+    /// set.  `include`, `obs_cap`: as `census`; more than `max_sets` distinct sets is an error (`MADSIM_E_LIMITS`).  With `resolve_runner`
+    /// set, the seeds a call leaves with a runner verdict are run again in one list call per round and merged in.
+    pub fn probe_sets(&self, workload: &Workload, vocabulary: &[u64], include: u32, obs_cap: u32, max_sets: usize) -> Result<ProbeSets, RunError> {
+        self.probe_sets_over(workload, vocabulary, None, include, obs_cap, max_sets)
+    }
+
+    /// `probe_sets` over an explicit, strictly ascending seed list (`madsim_hip_ctx_probe_sets_seeds`).
+    pub fn probe_sets_seeds(&self, workload: &Workload, vocabulary: &[u64], seeds: &[u64], include: u32, obs_cap: u32, max_sets: usize) -> Result<ProbeSets, RunError> {
+        self.probe_sets_over(workload, vocabulary, Some(seeds), include, obs_cap, max_sets)
+    }
+
+    fn probe_sets_over(&self, workload: &Workload, vocabulary: &[u64], seeds: Option<&[u64]>, include: u32, obs_cap: u32, max_sets: usize) -> Result<ProbeSets, RunError> {
+        let w = workload.raw();
+        let cfg = self.config.raw();
+        let lim0 = self.raw_limits(true);
+        let ctx = contexts()?.0[0];
+        let rounds = if self.resolve_flags & sys::MADSIM_CAMPAIGN_RESOLVE == 0 {
+            0
+        } else {
+            match (self.resolve_flags & sys::MADSIM_CAMPAIGN_RESOLVE_ROUNDS_MASK) >> sys::MADSIM_CAMPAIGN_RESOLVE_ROUNDS_SHIFT {
+                0 => sys::MADSIM_RESOLVE_DEFAULT_ROUNDS,
+                r => r,
+            }
+        };
+        let one = |lim: &sys::madsim_limits_t, list: Option<&[u64]>| -> Result<ProbeSets, RunError> {
+            let n = list.map_or(self.count, |l| l.len() as u64);
+            let mut sets: Vec<sys::madsim_probe_set_t> = vec![unsafe { std::mem::zeroed() }; max_sets.max(1)];
+            let mut runner = vec![0u64; (n as usize).max(1)];
+            let mut ps: sys::madsim_probe_sets_t = unsafe { std::mem::zeroed() };
+            ps.include = include;
+            ps.obs_cap = obs_cap;
+            ps.vocab = vocabulary.as_ptr();
+            ps.n_vocab = vocabulary.len() as u64;
+            ps.sets = sets.as_mut_ptr() as *const _;                     // (the library writes through both)
+            ps.cap = max_sets as u64;
+            ps.runner_seeds = runner.as_mut_ptr() as *const _;
+            ps.runner_cap = n;
+            let rc = unsafe {
+                match list {
+                    Some(l) => sys::madsim_hip_ctx_probe_sets_seeds(ctx, &w, &cfg, l.as_ptr(), n, 0, lim, &mut ps),
+                    None => sys::madsim_hip_ctx_probe_sets_range(ctx, &w, &cfg, self.seed, n, 0, lim, &mut ps),
+                }
+            };
+            if rc != 0 {
+                return Err(last_error(rc));
+            }
+            sets.truncate(ps.n_sets as usize);
+            runner.truncate(ps.n_runner_listed as usize);
+            ps.vocab = std::ptr::null();
+            ps.sets = std::ptr::null();
+            ps.runner_seeds = std::ptr::null();
+            Ok(ProbeSets { vocabulary: vocabulary.to_vec(), sets, totals: ps, runner_seeds: runner })
+        };
+        let mut c = one(&lim0, seeds)?;
+        for r in 1..=rounds {
+            if c.runner_seeds.is_empty() {
+                break;
+            }
+            let mut lim = lim0;
+            let rc = unsafe { sys::madsim_hip_grow_limits(&w, &lim0, r, &mut lim) };
+            if rc != 0 {
+                return Err(last_error(rc));
+            }
+            let more = one(&lim, Some(&c.runner_seeds))?;
+            let mut merged = Vec::with_capacity(c.sets.len() + more.sets.len());
+            let (mut i, mut j) = (0, 0);
+            while i < c.sets.len() || j < more.sets.len() {
+                if j >= more.sets.len() || (i < c.sets.len() && c.sets[i].set < more.sets[j].set) {
+                    merged.push(c.sets[i]);
+                    i += 1;
+                } else if i >= c.sets.len() || more.sets[j].set < c.sets[i].set {
+                    merged.push(more.sets[j]);
+                    j += 1;
+                } else {
+                    let (mut e, o) = (c.sets[i], more.sets[j]);
+                    for k in 0..4 {
+                        if o.n_seeds[k] > 0 {
+                            e.first_seed[k] = if e.n_seeds[k] > 0 { e.first_seed[k].min(o.first_seed[k]) } else { o.first_seed[k] };
+                        }
+                        e.n_seeds[k] += o.n_seeds[k];
+                    }
+                    merged.push(e);
+                    i += 1;
+                    j += 1;
+                }
+            }
+            if merged.len() > max_sets {
+                return Err(RunError { code: sys::MADSIM_E_LIMITS, message: "probe_sets: more than max_sets distinct probe sets once the runner seeds are settled".into() });
+            }
+            for k in 0..4 {
+                c.totals.n_counted[k] += more.totals.n_counted[k];
+            }
+            c.totals.n_runner = more.totals.n_runner;
+            c.totals.n_runner_listed = more.totals.n_runner_listed;
+            c.totals.n_sets = merged.len() as u64;
+            c.sets = merged;
             c.runner_seeds = more.runner_seeds;
         }
         Ok(c)

@@ -707,6 +707,62 @@ int madsim_hip_census_range(const madsim_workload_t* w, const madsim_config_t* c
 int madsim_hip_census_seeds(const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n, uint64_t chunk,
                             const madsim_limits_t* lim, madsim_census_t* cen);
 
+/* Probe-set census: WHICH COMBINATIONS of traced values the seeds reach, by verdict — the conjunctions ("0x20 and 0x21 both reached") that the
+ * census, a table of marginal counts over one value each, cannot answer.  The seeds run on the trace build exactly as for the census
+ * (log_cap 0, the caller's obs_cap); per chunk three kernels behind the trace launch reduce the rows where they lie: one 64-bit SET WORD per
+ * seed, equal set words folded into a keyed table, one 72-byte entry per distinct set coming back.  No row and no per-seed word travels to
+ * the host.  madsim_hip_probe_sets_range takes [seed0, seed0 + total), madsim_hip_probe_sets_seeds a STRICTLY ASCENDING list.
+ *
+ * Everything is exact and all-integer, a function of each seed's (result, observation list) alone: the same bytes whatever `chunk`, the
+ * context and the run, and for a dense list the bytes of the range form.  The caller gives a VOCABULARY vocab[0 .. n_vocab) of distinct
+ * 64-bit values, 1 <= n_vocab <= MADSIM_PROBE_SETS_MAX_VOCAB (every value is legal: 0, 2^64 - 1 and the FNV offset basis included), and
+ * `include` and `obs_cap` with madsim_census_t's meaning and limits.  A seed is COUNTED exactly as in the census (verdict < 4 and its bit
+ * set in `include`).  Of a counted seed with `len` observations the first vis = min(len, obs_cap) are visible; its set word has
+ *   bit i (0 <= i < n_vocab)        set when vocab[i] occurs at least once among the visible observations
+ *   MADSIM_PROBE_SET_OTHER (62)     set when a visible observation is not in the vocabulary
+ *   MADSIM_PROBE_SET_TRUNCATED (63) set when len > obs_cap
+ * and bits n_vocab .. 61 zero.  A counted seed without a visible observation has the set word 0, an entry like any other.
+ * Per distinct set word, sets[0 .. n_sets) ascending by `set` (unsigned): n_seeds[k], the counted seeds of verdict k with exactly this
+ * set, and first_seed[k], the smallest of them (0 when n_seeds[k] == 0).  n_counted[k] is the column sum of n_seeds[k].  Seeds with a
+ * runner verdict are never counted; they are tallied in n_runner and listed in runner_seeds exactly as the census does it.
+ * More than `cap` distinct sets: MADSIM_E_LIMITS, and nothing is reported (every output word 0) — a property of the data alone, never of
+ * an arrival order.
+ * The library cuts the seeds into chunks of `chunk` (0 = a default, 65 536 or what fits); the cut is invisible in the result.  One chunk
+ * asks the device for chunk * (8 * obs_cap + 80) bytes — the rows, two length words, the seed, the set word and the result of every seed —
+ * plus 48 * slots + 76 * cap + 64 for the table (slots: the power of two >= 2 * cap, at least 128), the claim list, the entries and the
+ * words: MADSIM_E_LIMITS when that exceeds MADSIM_TRACE_MAX_BYTES or chunk * obs_cap >= 2^32 - 1 — never split silently.
+ * total == 0 / n == 0 reports the empty result.  MADSIM_E_ARG: ps == NULL; include == 0 or a bit at or above 4; cap == 0 or above
+ * MADSIM_PROBE_SETS_MAX; sets == NULL; obs_cap == 0 or above MADSIM_CENSUS_MAX_OBS_CAP; n_vocab == 0 or above
+ * MADSIM_PROBE_SETS_MAX_VOCAB; vocab == NULL; a value that occurs twice in vocab; runner_cap > 0 without runner_seeds; seeds == NULL with
+ * n > 0; a list that is not strictly ascending (sort and deduplicate first). */
+#define MADSIM_PROBE_SETS_MAX_VOCAB 62u
+#define MADSIM_PROBE_SETS_MAX       1048576u /* 2^20 distinct sets */
+#define MADSIM_PROBE_SET_OTHER      0x4000000000000000ull /* bit 62: a visible observation outside the vocabulary */
+#define MADSIM_PROBE_SET_TRUNCATED  0x8000000000000000ull /* bit 63: more than obs_cap observations               */
+typedef struct madsim_probe_set {      /* 72 bytes */
+    uint64_t set;
+    uint64_t n_seeds[4];               /* counted seeds of each verdict with exactly this set                                     */
+    uint64_t first_seed[4];            /* the smallest such seed of each verdict; 0 where n_seeds is 0                            */
+} madsim_probe_set_t;
+typedef struct madsim_probe_sets {
+    uint32_t include;                  /* in: as madsim_census_t.include                                                          */
+    uint32_t obs_cap;                  /* in: as madsim_census_t.obs_cap                                                          */
+    const uint64_t* vocab;             /* in: caller's host array [n_vocab], distinct values                                      */
+    uint64_t n_vocab;                  /* in: 1 .. MADSIM_PROBE_SETS_MAX_VOCAB                                                    */
+    madsim_probe_set_t* sets;          /* in: caller's host array [cap]                                                           */
+    uint64_t cap;                      /* in: 1 .. MADSIM_PROBE_SETS_MAX                                                          */
+    uint64_t* runner_seeds;            /* in: caller's host array [runner_cap]; may be NULL when runner_cap == 0                  */
+    uint64_t runner_cap;
+    uint64_t n_sets;                   /* out: entries written, ascending by set                                                  */
+    uint64_t n_counted[4];             /* out: counted seeds per verdict = the column sums of n_seeds                             */
+    uint64_t n_runner;                 /* out: seeds with a runner verdict                                                        */
+    uint64_t n_runner_listed;          /* out: min(n_runner, runner_cap), the entries of runner_seeds written                     */
+} madsim_probe_sets_t;
+int madsim_hip_probe_sets_range(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total, uint64_t chunk,
+                                const madsim_limits_t* lim, madsim_probe_sets_t* ps);
+int madsim_hip_probe_sets_seeds(const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n, uint64_t chunk,
+                                const madsim_limits_t* lim, madsim_probe_sets_t* ps);
+
 /* The same entry points on an explicit context (see "Per-device contexts" above). */
 int madsim_hip_ctx_run_batch(madsim_hip_ctx_t* ctx, const madsim_workload_t* w, const madsim_config_t* cfg,
                              uint64_t seed0, uint64_t count, const madsim_limits_t* lim,
@@ -738,6 +794,10 @@ int madsim_hip_ctx_census_range(madsim_hip_ctx_t* ctx, const madsim_workload_t* 
                                 uint64_t total, uint64_t chunk, const madsim_limits_t* lim, madsim_census_t* cen);
 int madsim_hip_ctx_census_seeds(madsim_hip_ctx_t* ctx, const madsim_workload_t* w, const madsim_config_t* cfg,
                                 const uint64_t* seeds, uint64_t n, uint64_t chunk, const madsim_limits_t* lim, madsim_census_t* cen);
+int madsim_hip_ctx_probe_sets_range(madsim_hip_ctx_t* ctx, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0,
+                                    uint64_t total, uint64_t chunk, const madsim_limits_t* lim, madsim_probe_sets_t* ps);
+int madsim_hip_ctx_probe_sets_seeds(madsim_hip_ctx_t* ctx, const madsim_workload_t* w, const madsim_config_t* cfg,
+                                    const uint64_t* seeds, uint64_t n, uint64_t chunk, const madsim_limits_t* lim, madsim_probe_sets_t* ps);
 
 /* One process, several GPUs: the whole seed loop of Builder::run (builder.rs:129-150, every seed driven from one
  * process) over `n_ctx` contexts, each on its own GPU (or, for tests on a 1-GPU box, several on the same one).

@@ -967,6 +967,122 @@ struct Builder {
         return c;
     }
 
+    // Which COMBINATIONS of the values of `vocabulary` (1 .. 62 distinct values; value i owns bit i of a set word) the builder's seeds reach,
+    // by verdict (madsim_hip_probe_sets_range / madsim_hip_probe_sets_seeds): `seed .. seed + count`, or the over_seeds() list, run on the
+    // trace build and reduced on the device to one record per distinct set.  sets: ascending by set word; MADSIM_PROBE_SET_OTHER = the seed
+    // traced a visible value outside the vocabulary, MADSIM_PROBE_SET_TRUNCATED = more than `obs_cap` values.  More than `max_sets` distinct
+    // sets throws (MADSIM_E_LIMITS).  This builder's resolve_runner() rounds apply as in census().
+    struct ProbeSets {
+        std::vector<uint64_t> vocabulary;
+        std::vector<madsim_probe_set_t> sets;
+        madsim_probe_sets_t totals{};              // the counts (the pointers and caps are the call's own: not meaningful here)
+        std::vector<uint64_t> runner_seeds;
+        struct Mixed { uint64_t set, pass_seed, fail_seed; };
+        uint64_t mask(const std::vector<uint64_t>& values) const {     // the set-word bits of vocabulary values; throws on any other value
+            uint64_t m = 0;
+            for (uint64_t v : values) {
+                auto it = std::find(vocabulary.begin(), vocabulary.end(), v);
+                if (it == vocabulary.end()) throw Error(MADSIM_E_ARG, "probe_sets: a value that is not in the vocabulary");
+                m |= 1ull << (it - vocabulary.begin());
+            }
+            return m;
+        }
+        // counted seeds of the verdicts in `verdicts` (a bit mask) that reached every value of all_of and none of none_of
+        uint64_t count(const std::vector<uint64_t>& all_of = {}, const std::vector<uint64_t>& none_of = {}, uint32_t verdicts = 0xf) const {
+            const uint64_t want = mask(all_of), avoid = mask(none_of);
+            uint64_t n = 0;
+            for (const madsim_probe_set_t& e : sets)
+                if ((e.set & want) == want && !(e.set & avoid))
+                    for (int k = 0; k < 4; k++) if ((verdicts >> k) & 1u) n += e.n_seeds[k];
+            return n;
+        }
+        // the sets that occur under PASS and under a failing verdict, each with its smallest passing and its smallest failing seed
+        std::vector<Mixed> mixed() const {
+            std::vector<Mixed> out;
+            for (const madsim_probe_set_t& e : sets) {
+                uint64_t fail = UINT64_MAX; bool any = false;
+                for (int k = 1; k < 4; k++) if (e.n_seeds[k]) { fail = std::min(fail, e.first_seed[k]); any = true; }
+                if (e.n_seeds[0] && any) out.push_back(Mixed{e.set, e.first_seed[0], fail});
+            }
+            return out;
+        }
+        // a greedy set cover of every reached vocabulary value — each round the entry that adds the most new values, ties to the smaller
+        // set word —: one seed (its smallest) per chosen entry, ascending and unique, ready for over_seeds()
+        std::vector<uint64_t> cover() const {
+            const uint64_t vmask = (1ull << vocabulary.size()) - 1;      // (at most 62 values)
+            uint64_t missing = 0;
+            for (const madsim_probe_set_t& e : sets) missing |= e.set & vmask;
+            std::vector<uint64_t> chosen;
+            while (missing) {
+                const madsim_probe_set_t* best = nullptr;
+                for (const madsim_probe_set_t& e : sets)                   // ascending by set word: the first of the best wins
+                    if (!best || __builtin_popcountll(e.set & missing) > __builtin_popcountll(best->set & missing)) best = &e;
+                uint64_t s = UINT64_MAX;
+                for (int k = 0; k < 4; k++) if (best->n_seeds[k]) s = std::min(s, best->first_seed[k]);
+                chosen.push_back(s);
+                missing &= ~best->set;
+            }
+            std::sort(chosen.begin(), chosen.end());
+            chosen.erase(std::unique(chosen.begin(), chosen.end()), chosen.end());
+            return chosen;
+        }
+    };
+    ProbeSets probe_sets(const Workload& wl, const std::vector<uint64_t>& vocabulary, uint32_t obs_cap = 256, uint64_t max_sets = 4096, uint32_t include = 0xf,
+                         uint64_t chunk = 0) const {
+        madsim::check(madsim_hip_init(device));
+        madsim_workload_t w = wl.raw();
+        madsim_config_t cfg = config.raw();
+        madsim_limits_t lim0 = capacities;
+        if (time_limit) { lim0.time_limit_ns = (uint64_t)(*time_limit * 1e9 + 0.5); if (!lim0.time_limit_ns) lim0.time_limit_ns = 1; }
+        uint32_t rounds = 0;
+        if (resolve_flags & MADSIM_CAMPAIGN_RESOLVE) {
+            rounds = (resolve_flags & MADSIM_CAMPAIGN_RESOLVE_ROUNDS_MASK) >> MADSIM_CAMPAIGN_RESOLVE_ROUNDS_SHIFT;
+            if (!rounds) rounds = MADSIM_RESOLVE_DEFAULT_ROUNDS;
+        }
+        auto one = [&](const madsim_limits_t& lim, const std::vector<uint64_t>* list) {
+            ProbeSets c;
+            const uint64_t n = list ? list->size() : count;
+            c.vocabulary = vocabulary;
+            c.sets.resize(max_sets ? max_sets : 1);
+            c.runner_seeds.resize(n ? n : 1);
+            madsim_probe_sets_t& t = c.totals;
+            t.include = include; t.obs_cap = obs_cap; t.vocab = vocabulary.data(); t.n_vocab = vocabulary.size(); t.sets = c.sets.data(); t.cap = max_sets;
+            t.runner_seeds = c.runner_seeds.data(); t.runner_cap = n;
+            madsim::check(list ? madsim_hip_probe_sets_seeds(&w, &cfg, list->data(), n, chunk, &lim, &t) : madsim_hip_probe_sets_range(&w, &cfg, seed, n, chunk, &lim, &t));
+            c.sets.resize(t.n_sets);
+            c.runner_seeds.resize(t.n_runner_listed);
+            t.vocab = nullptr; t.sets = nullptr; t.runner_seeds = nullptr;
+            return c;
+        };
+        ProbeSets c = one(lim0, listed_seeds ? &seed_list : nullptr);
+        for (uint32_t r = 1; r <= rounds && !c.runner_seeds.empty(); r++) {
+            madsim_limits_t lim = lim0;
+            madsim::check(madsim_hip_grow_limits(&w, &lim0, r, &lim));
+            const ProbeSets more = one(lim, &c.runner_seeds);
+            std::vector<madsim_probe_set_t> merged;
+            for (size_t i = 0, j = 0; i < c.sets.size() || j < more.sets.size();) {
+                if (j >= more.sets.size() || (i < c.sets.size() && c.sets[i].set < more.sets[j].set)) merged.push_back(c.sets[i++]);
+                else if (i >= c.sets.size() || more.sets[j].set < c.sets[i].set) merged.push_back(more.sets[j++]);
+                else {
+                    madsim_probe_set_t e = c.sets[i++];
+                    const madsim_probe_set_t& o = more.sets[j++];
+                    for (int k = 0; k < 4; k++) {
+                        if (o.n_seeds[k]) e.first_seed[k] = e.n_seeds[k] ? std::min(e.first_seed[k], o.first_seed[k]) : o.first_seed[k];
+                        e.n_seeds[k] += o.n_seeds[k];
+                    }
+                    merged.push_back(e);
+                }
+            }
+            if (merged.size() > max_sets) throw Error(MADSIM_E_LIMITS, "probe_sets: more than max_sets distinct probe sets once the runner seeds are settled");
+            c.sets.swap(merged);
+            for (int k = 0; k < 4; k++) c.totals.n_counted[k] += more.totals.n_counted[k];
+            c.totals.n_runner = more.totals.n_runner; c.totals.n_runner_listed = more.totals.n_runner_listed;
+            c.totals.n_sets = c.sets.size();
+            c.runner_seeds = more.runner_seeds;
+        }
+        return c;
+    }
+
     // Where the two runs part: this builder's run of `wl` (side A) against `other`'s run of `other_wl` (side B) over `seeds` (any order,
     // duplicates allowed), compared on the device on the determinism log and on the observations (madsim_hip_diverge_seeds): per seed the
     // record, the up to `window` observations both runs made just before they part, and the up to `window` each side made from there on.

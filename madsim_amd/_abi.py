@@ -313,6 +313,30 @@ assert C.sizeof(CensusValue) == 64 and C.sizeof(Census) == 144
 HEADER_STRUCTS["madsim_census_value_t"] = CensusValue
 HEADER_STRUCTS["madsim_census_t"] = Census
 
+# madsim_hip_probe_sets_range / _seeds: the most vocabulary values, the most distinct sets, and the two set-word bits beside the vocabulary's
+PROBE_SETS_MAX_VOCAB, PROBE_SETS_MAX = 62, 1 << 20
+PROBE_SET_OTHER, PROBE_SET_TRUNCATED = 1 << 62, 1 << 63
+
+
+class ProbeSet(C.Structure):
+    """madsim_probe_set_t: one distinct set word — the counted seeds of each verdict with exactly this set and the smallest of them."""
+    _fields_ = [("set", C.c_uint64), ("n_seeds", C.c_uint64 * 4), ("first_seed", C.c_uint64 * 4)]
+
+
+class ProbeSets(C.Structure):
+    """madsim_probe_sets_t: which verdicts count, how many observations of a seed are visible, the vocabulary and the caller's two arrays
+    going in; the table's length and the totals coming out."""
+    _fields_ = [("include", C.c_uint32), ("obs_cap", C.c_uint32), ("vocab", C.POINTER(C.c_uint64)), ("n_vocab", C.c_uint64),
+                ("sets", C.POINTER(ProbeSet)), ("cap", C.c_uint64), ("runner_seeds", C.POINTER(C.c_uint64)), ("runner_cap", C.c_uint64),
+                ("n_sets", C.c_uint64), ("n_counted", C.c_uint64 * 4), ("n_runner", C.c_uint64), ("n_runner_listed", C.c_uint64)]
+
+
+# numpy view of a probe-set table: madsim_probe_set_t
+PROBE_SET_DTYPE = [("set", "<u8"), ("n_seeds", "<u8", (4,)), ("first_seed", "<u8", (4,))]
+assert C.sizeof(ProbeSet) == 72 and C.sizeof(ProbeSets) == 112
+HEADER_STRUCTS["madsim_probe_set_t"] = ProbeSet
+HEADER_STRUCTS["madsim_probe_sets_t"] = ProbeSets
+
 
 class Geometry(C.Structure):
     _fields_ = [

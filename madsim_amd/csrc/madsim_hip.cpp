@@ -255,6 +255,32 @@ struct madsim_hip_resources {
             return 0;
         }
     } census;
+    // the probe-set census: the set word of every seed of a chunk (device only), the table (all zero between chunks; `dirty` as above), the
+    // claim list, the words and the chunk's entries; page-locked: the words, the entries, the range form's seed slice and — only for a chunk
+    // with runner verdicts whose seeds the caller still wants — the chunk's results
+    struct ProbeSets {
+        DevBuf<uint64_t> sig; DevBuf<uint32_t> tab, list; DevBuf<unsigned long long> words; DevBuf<madsim_probe_set_t> ent;
+        PinnedBuf<unsigned long long> h_words; PinnedBuf<madsim_probe_set_t> h_ent; PinnedBuf<uint64_t> h_seeds; PinnedBuf<madsim_result_t> h_res;
+        bool dirty = true;
+        int ensure(uint64_t cap, uint64_t chunk, bool range, hipStream_t s) {
+            const size_t tab_words = (size_t)(madsim_k_probe_sets_slots(cap) * MADSIM_K_PROBE_SETS_SLOT_BYTES / sizeof(uint32_t));
+            if (tab_words > tab.cap) dirty = true;
+            HIP_TRY(tab.room(tab_words, s));
+            HIP_TRY(sig.room((size_t)chunk, s));
+            HIP_TRY(list.room((size_t)cap, s));
+            HIP_TRY(ent.room((size_t)cap, s));
+            HIP_TRY(h_ent.room((size_t)cap, s));
+            HIP_TRY(words.room(MADSIM_K_PROBE_SETS_WORDS));
+            HIP_TRY(h_words.room(MADSIM_K_PROBE_SETS_WORDS));
+            if (range) HIP_TRY(h_seeds.room((size_t)chunk, s));
+            if (dirty) {
+                HIP_TRY(hipMemsetAsync(tab, 0, tab.cap * sizeof(uint32_t), s));
+                HIP_TRY(hipStreamSynchronize(s));
+                dirty = false;
+            }
+            return 0;
+        }
+    } probe_sets;
     Event ev0, ev1;
     Event pipe_begin;                         // run_pipelined: before the first sub-batch of a call
     Event tev[2 * 64];                        // timing slots of madsim_hip_run_batch_async
@@ -1225,6 +1251,148 @@ int madsim_hip_ctx_census_range(madsim_hip_ctx_t* c, const madsim_workload_t* w,
 int madsim_hip_ctx_census_seeds(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n,
                                 uint64_t chunk, const madsim_limits_t* lim, madsim_census_t* cen) {
     return census_run(c, w, cfg, 0, seeds, n, chunk, lim, cen, true);
+}
+
+// ---- the probe-set census: table size, the host fold of a chunk, and the chunk loop (census_run's sibling) ---------------------------
+extern "C" uint64_t madsim_k_probe_sets_slots(uint64_t cap) {
+    uint64_t slots = MADSIM_K_PROBE_SETS_MIN_SLOTS;
+    while (slots < 2 * cap) slots <<= 1;
+    return slots;
+}
+
+// Declared in sim_kernel.h beside the launcher (not part of the public ABI): the tests feed it entries without a device.  Everything it
+// does commutes, so the order of the chunks and of a chunk's entries never shows; equal sets inside one chunk's entries are combined too.
+extern "C" int madsim_k_fold_probe_sets(madsim_probe_sets_t* ps, const unsigned long long* words, const madsim_probe_set_t* entries, uint64_t n) {
+    auto combine = [](madsim_probe_set_t& a, const madsim_probe_set_t& b) {
+        for (int k = 0; k < 4; k++) {
+            if (b.n_seeds[k]) a.first_seed[k] = a.n_seeds[k] ? std::min(a.first_seed[k], b.first_seed[k]) : b.first_seed[k];
+            a.n_seeds[k] += b.n_seeds[k];
+        }
+    };
+    std::vector<madsim_probe_set_t> add(entries, entries + n);
+    std::sort(add.begin(), add.end(), [](const madsim_probe_set_t& a, const madsim_probe_set_t& b) { return a.set < b.set; });
+    size_t m = 0;
+    for (size_t j = 0; j < add.size(); j++) {
+        if (m && add[m - 1].set == add[j].set) combine(add[m - 1], add[j]); else add[m++] = add[j];
+    }
+    madsim_probe_set_t* const v = ps->sets;
+    const uint64_t have = ps->n_sets;
+    uint64_t fresh = 0;
+    for (size_t i = 0, j = 0; j < m; j++) {
+        while (i < have && v[i].set < add[j].set) i++;
+        if (i >= have || v[i].set != add[j].set) fresh++;
+    }
+    if (have + fresh > ps->cap) return -1;
+    for (int64_t i = (int64_t)have - 1, j = (int64_t)m - 1, k = (int64_t)(have + fresh) - 1; j >= 0; k--) {      // merged from the back, in place
+        if (i >= 0 && v[i].set > add[j].set) v[k] = v[i--];
+        else if (i >= 0 && v[i].set == add[j].set) { madsim_probe_set_t e = v[i--]; combine(e, add[j--]); v[k] = e; }
+        else v[k] = add[j--];
+    }
+    ps->n_sets = have + fresh;
+    if (words) {
+        for (int k = 0; k < 4; k++) ps->n_counted[k] += words[2 + k];
+        ps->n_runner += words[6];
+    }
+    return 0;
+}
+
+// The probe sets of [seed0, seed0 + total) (seeds == nullptr) or of seeds[0 .. total): chunk after chunk on one stream, each the trace launch
+// into the context's trace set 0, the three kernels and the copies of the words and of the first PROBE_SETS_EAGER_ENTRIES entries, then one
+// synchronisation; entries beyond those — and, where the caller still wants runner seeds and the chunk has some, its results — follow by
+// copies of their own.  Once a chunk is queued no error returns before its synchronisation (TraceSteps); an error that may have left the
+// table otherwise than zero marks it dirty.
+constexpr uint64_t PROBE_SETS_EAGER_ENTRIES = 56;      // entries copied behind a chunk's words, before their number is known: 4 KB
+
+static int probe_sets_run(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, const uint64_t* seeds,
+                          uint64_t total, uint64_t chunk, const madsim_limits_t* lim, madsim_probe_sets_t* ps, bool list) {
+    static_assert(sizeof(madsim_probe_set_t) == 72 && sizeof(madsim_probe_sets_t) == 112, "record layout");
+    if (!ps) return fail(MADSIM_E_ARG, "probe_sets: null report");
+    if (ps->include == 0 || (ps->include & ~0xfu)) return fail(MADSIM_E_ARG, "probe_sets: include is 0 or names a verdict at or above 4 (only PASS, PANIC, DEADLOCK, TIME_LIMIT are counted)");
+    if (ps->cap == 0 || ps->cap > MADSIM_PROBE_SETS_MAX || !ps->sets) return fail(MADSIM_E_ARG, "probe_sets: cap outside 1 .. MADSIM_PROBE_SETS_MAX, or no set array");
+    if (ps->obs_cap == 0 || ps->obs_cap > MADSIM_CENSUS_MAX_OBS_CAP) return fail(MADSIM_E_ARG, "probe_sets: obs_cap outside 1 .. MADSIM_CENSUS_MAX_OBS_CAP");
+    if (ps->n_vocab == 0 || ps->n_vocab > MADSIM_PROBE_SETS_MAX_VOCAB || !ps->vocab) return fail(MADSIM_E_ARG, "probe_sets: n_vocab outside 1 .. MADSIM_PROBE_SETS_MAX_VOCAB, or no vocabulary");
+    for (uint64_t i = 1; i < ps->n_vocab; i++)
+        for (uint64_t j = 0; j < i; j++)
+            if (ps->vocab[i] == ps->vocab[j]) return fail(MADSIM_E_ARG, "probe_sets: a value occurs twice in the vocabulary");
+    if (ps->runner_cap && !ps->runner_seeds) return fail(MADSIM_E_ARG, "probe_sets: runner_cap without runner_seeds");
+    if (list && total && !seeds) return fail(MADSIM_E_ARG, "probe_sets_seeds: null seed list");
+    if (list)
+        for (uint64_t i = 1; i < total; i++)
+            if (seeds[i] <= seeds[i - 1]) return fail(MADSIM_E_ARG, "probe_sets_seeds: the seed list is not strictly ascending (sort and deduplicate it first)");
+    auto nothing = [ps] {
+        ps->n_sets = ps->n_runner = ps->n_runner_listed = 0;
+        for (int k = 0; k < 4; k++) ps->n_counted[k] = 0;
+    };
+    nothing();
+    if (total == 0) return 0;
+    // what a chunk asks of the device: per seed the row, two length words, the seed, the set word and the result; once the table, the list, the entries, the words
+    const uint64_t M = MADSIM_TRACE_MAX_BYTES, obs_cap = ps->obs_cap, cap = ps->cap;
+    const uint64_t fixed = madsim_k_probe_sets_slots(cap) * MADSIM_K_PROBE_SETS_SLOT_BYTES + cap * (sizeof(uint32_t) + sizeof(madsim_probe_set_t)) + MADSIM_K_PROBE_SETS_WORDS * 8;
+    const uint64_t per_seed = 8 * obs_cap + 4 * sizeof(uint64_t) + sizeof(madsim_result_t);
+    const uint64_t fits = fixed < M ? std::min<uint64_t>((M - fixed) / per_seed, 0xffffffffull / obs_cap - 1) : 0;
+    if (chunk == 0) chunk = std::min<uint64_t>(65536, fits);
+    if (chunk == 0 || chunk > fits)
+        return fail(MADSIM_E_LIMITS, "probe_sets: chunk x (8 obs_cap + 80) + 48 slots + 76 cap + 64 exceeds MADSIM_TRACE_MAX_BYTES, or chunk x obs_cap reaches 2^32 - 1: a smaller chunk or smaller caps");
+    chunk = std::min(chunk, total);
+    int rc = madsim_geo::validate(w, cfg, &g_err);
+    if (rc) return rc;
+    CTX_ENTER(c);
+    hipStream_t st = nullptr;
+    madsim_hip_ctx::TraceSet& S = c->trace[0];
+    madsim_hip_ctx::ProbeSets& P = c->probe_sets;
+    for (uint64_t done = 0; done < total; done += chunk) {
+        const uint64_t n = std::min(chunk, total - done);
+        Geo G;
+        if ((rc = trace_prepare(c, w, cfg, lim, n, 0, obs_cap, S, G, st))) { nothing(); return rc; }
+        if ((rc = P.ensure(cap, chunk, !list, st))) { nothing(); return rc; }
+        const uint64_t* src = list ? seeds + done : P.h_seeds.p;
+        if (!list) for (uint64_t i = 0; i < n; i++) P.h_seeds.p[i] = seed0 + done + i;
+        TraceSteps step;
+        bool ok = step(hipMemcpyAsync(c->d_seeds, src, n * sizeof(uint64_t), hipMemcpyHostToDevice, st), "hipMemcpyAsync(seeds)");
+        if (ok) ok = step(hipMemsetAsync(P.words, 0, MADSIM_K_PROBE_SETS_WORDS * sizeof(unsigned long long), st), "hipMemsetAsync(probe-set words)");
+        ok = trace_queue(G, S, n, 0, obs_cap, true, st, step, ok);
+        if (ok) {
+            const int refused = madsim_k_launch_probe_sets(S.obs, obs_cap, S.len + n, S.out, c->d_seeds, n, ps->include, ps->vocab, ps->n_vocab, P.sig,
+                                                           P.tab, madsim_k_probe_sets_slots(cap), P.list, cap, P.words, P.ent, st);
+            if (refused) step.no_build = true;
+            ok = step(refused ? hipSuccess : hipGetLastError(), "probe-set kernel launch");
+        }
+        if (ok) ok = step(hipMemcpyAsync(P.h_words, P.words, MADSIM_K_PROBE_SETS_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st), "hipMemcpyAsync(probe-set words)");
+        // the first entries ride behind the words (a handful of sets is the usual report); a chunk with more gets the rest in a copy of its own
+        const uint64_t eager = std::min<uint64_t>(cap, PROBE_SETS_EAGER_ENTRIES);
+        if (ok) ok = step(hipMemcpyAsync(P.h_ent, P.ent, eager * sizeof(madsim_probe_set_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync(probe-set entries)");
+        ok = step(hipStreamSynchronize(st), "hipStreamSynchronize");
+        if (step.err != hipSuccess) { P.dirty = true; nothing(); return fail(MADSIM_E_HIP, std::string(step.at) + ": " + hipGetErrorString(step.err)); }
+        if (step.no_build) { nothing(); return fail(MADSIM_E_LIMITS, "no trace kernel build, or sizes the probe-set kernels refuse"); }
+        const unsigned long long* W = P.h_words;
+        const char* const too_many = "probe_sets: more than `cap` distinct probe sets: raise cap (max_sets), or name fewer values in the vocabulary";
+        if (W[1] & MADSIM_K_PROBE_SETS_ERR_CAP) { nothing(); return fail(MADSIM_E_LIMITS, too_many); }      // (the extract pass has cleared the table)
+        if (W[1]) { P.dirty = true; nothing(); return fail(MADSIM_E_HIP, "probe_sets: the device table was not clean (internal)"); }
+        const uint64_t ne = W[0];
+        if (ne > eager) {
+            const hipError_t e = hipMemcpy(P.h_ent + eager, P.ent + eager, (ne - eager) * sizeof(madsim_probe_set_t), hipMemcpyDeviceToHost);
+            if (e != hipSuccess) { nothing(); return fail(MADSIM_E_HIP, std::string("hipMemcpy(probe-set entries): ") + hipGetErrorString(e)); }
+        }
+        if (madsim_k_fold_probe_sets(ps, W, P.h_ent, ne)) { nothing(); return fail(MADSIM_E_LIMITS, too_many); }
+        if (W[6] && ps->n_runner_listed < ps->runner_cap) {                      // chunks and seeds ascend: the first runner_cap met are the smallest
+            hipError_t e = P.h_res.room((size_t)chunk);
+            if (e == hipSuccess) e = hipMemcpy(P.h_res, S.out, n * sizeof(madsim_result_t), hipMemcpyDeviceToHost);
+            if (e != hipSuccess) { nothing(); return fail(MADSIM_E_HIP, std::string("hipMemcpy(probe-set results): ") + hipGetErrorString(e)); }
+            for (uint64_t i = 0; i < n && ps->n_runner_listed < ps->runner_cap; i++)
+                if (MADSIM_IS_RUNNER_VERDICT(P.h_res.p[i].verdict)) ps->runner_seeds[ps->n_runner_listed++] = list ? seeds[done + i] : seed0 + done + i;
+        }
+    }
+    return 0;
+}
+
+int madsim_hip_ctx_probe_sets_range(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total,
+                                    uint64_t chunk, const madsim_limits_t* lim, madsim_probe_sets_t* ps) {
+    return probe_sets_run(c, w, cfg, seed0, nullptr, total, chunk, lim, ps, false);
+}
+
+int madsim_hip_ctx_probe_sets_seeds(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n,
+                                    uint64_t chunk, const madsim_limits_t* lim, madsim_probe_sets_t* ps) {
+    return probe_sets_run(c, w, cfg, 0, seeds, n, chunk, lim, ps, true);
 }
 
 int madsim_hip_ctx_trace_seeds(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n,
@@ -2430,6 +2598,18 @@ int madsim_hip_census_seeds(const madsim_workload_t* w, const madsim_config_t* c
                             const madsim_limits_t* lim, madsim_census_t* cen) {
     DefaultPin p;
     return madsim_hip_ctx_census_seeds(p.c, w, cfg, seeds, n, chunk, lim, cen);
+}
+
+int madsim_hip_probe_sets_range(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total, uint64_t chunk,
+                                const madsim_limits_t* lim, madsim_probe_sets_t* ps) {
+    DefaultPin p;
+    return madsim_hip_ctx_probe_sets_range(p.c, w, cfg, seed0, total, chunk, lim, ps);
+}
+
+int madsim_hip_probe_sets_seeds(const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n, uint64_t chunk,
+                                const madsim_limits_t* lim, madsim_probe_sets_t* ps) {
+    DefaultPin p;
+    return madsim_hip_ctx_probe_sets_seeds(p.c, w, cfg, seeds, n, chunk, lim, ps);
 }
 
 int madsim_hip_run_campaign(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total, uint64_t batch,

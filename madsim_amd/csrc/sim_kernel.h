@@ -484,6 +484,42 @@ uint64_t madsim_k_census_slot(uint64_t value, uint64_t slots);
 // totals, and the chunk's `n` entries (any order, distinct values) merged into cen->values[0 .. n_values), which stay ascending by value —
 // counts added, the max of max_per_seed, the min of first_seed.  Returns 0, or -1 with `cen` untouched when the table would pass cen->cap.
 int  madsim_k_fold_census(madsim_census_t* cen, const unsigned long long* words, const madsim_census_value_t* entries, uint64_t n);
+// the probe-set census (madsim_hip_probe_sets_range / _seeds), behind the chunk's trace launch on the same stream: three kernels over the
+// observation rows of `n` seeds (`obs_cap` words each), their TRUE lengths, the results and the seeds.  sets_mask_kernel writes the set
+// word (include/madsim_hip.h) of every COUNTED row i to sig[i] — `sig`: n 64-bit words of scratch; the words of other rows are neither
+// written nor read, and neither are those rows —, against vocab[0 .. n_vocab), HOST memory here: the values travel in the kernel arguments.
+// sets_fold_kernel folds equal set words into `table`: `slots` (a power of two, >= 2 * cap and >= MADSIM_K_PROBE_SETS_MIN_SLOTS) slots of
+// MADSIM_K_PROBE_SETS_SLOT_BYTES, ALL ZERO before the launch and all zero again after it, whatever happened; a set word starts probing at
+// madsim_k_census_slot(set, slots).  `list`: cap 32-bit words of scratch (the claimed slots, in arrival order); `words`:
+// MADSIM_K_PROBE_SETS_WORDS words, zero before the launch: {distinct sets of the chunk, error word, n_counted[4], n_runner}; `entries`: room
+// for `cap` madsim_probe_set_t, the first words[0] written by sets_extract_kernel, in arrival order — the host sorts them.  d_seeds
+// ASCEND with the row.  The set that would be distinct set number cap + 1 sets MADSIM_K_PROBE_SETS_ERR_CAP in the error word and is not
+// inserted; with a non-zero error word no entry is written (words[0] is then not a count of anything).  Returns 0, or -1 without launching
+// anything for n == 0, n > 2^31, n * obs_cap >= 2^32 - 1, obs_cap outside 1 .. MADSIM_CENSUS_MAX_OBS_CAP, n_vocab outside
+// 1 .. MADSIM_PROBE_SETS_MAX_VOCAB, an include mask that is 0 or has a bit at or above 4, cap outside 1 .. MADSIM_PROBE_SETS_MAX, a table
+// of the wrong size or a missing array.
+#define MADSIM_K_PROBE_SETS_WORDS 8u        /* 64-bit words of a chunk's report: 7 used              */
+#define MADSIM_K_PROBE_SETS_SLOT_BYTES 48u  /* {tag, n_seeds[4], ~smallest row[4], 0, 0, 0}          */
+#define MADSIM_K_PROBE_SETS_MIN_SLOTS 128u  /* a table is never smaller                              */
+#define MADSIM_K_PROBE_SETS_WAVES 1024u     /* = MADSIM_K_CENSUS_WAVES: 256 workgroups of four waves */
+#define MADSIM_K_PROBE_SETS_ERR_PROBE 1u    /* a probe ran out                                       */
+#define MADSIM_K_PROBE_SETS_ERR_TAG 2u      /* a slot no seed of the chunk can have claimed: the table was not clean */
+#define MADSIM_K_PROBE_SETS_ERR_CAP 4u      /* more than `cap` distinct sets                         */
+int  madsim_k_launch_probe_sets(const uint64_t* obs, uint64_t obs_cap, const uint64_t* obs_len, const madsim_result_t* res, const uint64_t* d_seeds,
+                                uint64_t n, uint32_t include, const uint64_t* vocab, uint64_t n_vocab, uint64_t* sig, uint32_t* table,
+                                uint64_t slots, uint32_t* list, uint64_t cap, unsigned long long* words, madsim_probe_set_t* entries, void* stream);
+// ... with the fold kernel's form named: per_seed != 0 = one table update per counted seed, no in-wave combine of equal set words: the
+// correctness baseline and the other side of the A/B (tools/sets_ab.py); the same bytes either way
+int  madsim_k_launch_probe_sets_form(const uint64_t* obs, uint64_t obs_cap, const uint64_t* obs_len, const madsim_result_t* res,
+                                     const uint64_t* d_seeds, uint64_t n, uint32_t include, const uint64_t* vocab, uint64_t n_vocab, uint64_t* sig,
+                                     uint32_t* table, uint64_t slots, uint32_t* list, uint64_t cap, unsigned long long* words,
+                                     madsim_probe_set_t* entries, void* stream, int per_seed);
+// the smallest table madsim_k_launch_probe_sets accepts for `cap` sets (madsim_hip.cpp; no device involved)
+uint64_t madsim_k_probe_sets_slots(uint64_t cap);
+// the host fold of one chunk into the caller's report (madsim_hip.cpp; no device involved): `words` (may be null: no totals) are added to
+// the totals, and the chunk's `n` entries (any order) merged into ps->sets[0 .. n_sets), which stay ascending by set — counts added,
+// per verdict the smaller first_seed of the sides that have one.  Returns 0, or -1 with `ps` untouched when the table would pass ps->cap.
+int  madsim_k_fold_probe_sets(madsim_probe_sets_t* ps, const unsigned long long* words, const madsim_probe_set_t* entries, uint64_t n);
 int  madsim_k_set_max_lds(uint32_t lds_bytes);
 int  madsim_k_variant_vgprs(const madsim_k::VariantSel* v);
 void madsim_k_launch_keyflip(unsigned long long* acc, void* stream);

@@ -1324,6 +1324,166 @@ __global__ __launch_bounds__(256) void census_extract_kernel(const unsigned long
     }
 }
 
+// ---- the probe-set census: which COMBINATIONS of vocabulary values a chunk's counted seeds reach, each with its per-verdict seed counts ----
+// Three kernels behind the chunk's trace launch.  sets_mask_kernel: one wave per row, striding as census_fold_kernel does; rows of uncounted
+// and runner seeds are not read.  The row index is made scalar (readfirstlane), so the verdict, the length and the loop bounds live in
+// scalar registers and the wave stays converged.  The visible observations are walked in rounds of 64, one coalesced 8-byte load per lane;
+// per vocabulary entry one wave-wide 64-bit compare against a scalar operand — the vocabulary travels by value in the kernel arguments
+// (496 bytes, as sweep_count_kernel's pointer table does), so entry j is one scalar load from the argument segment —, whose mask says "any
+// lane matched" and joins the round's hit mask; valid lanes outside the hit mask give OTHER.  No LDS, no atomics.  The walk ends early
+// once every vocabulary bit and OTHER are set.  Lane 0 writes the row's set word to sig[i].
+// sets_fold_kernel: one lane per seed over sig[] and the results.  Equal set words of a wave's 64 seeds are combined by group_fold_kernel's
+// ballot loop, the verdict NOT part of the key: a leader holds the four per-verdict popcounts and the four per-verdict smallest indices
+// (lanes hold ascending seeds: the lowest lane of a verdict's ballot).  One insert per leader into the census's table (census_insert's
+// claim rule): the TAG is 1 + the index of the leader's seed, the key is read from sig[] — which nobody writes while this kernel runs —,
+// one 32-bit compare-and-swap claims, nobody waits for a "ready" word, every claim takes a number and appends its slot to `list`, the
+// claim that would be number cap + 1 sets MADSIM_K_PROBE_SETS_ERR_CAP.  A slot is {tag, n_seeds[4], ~smallest index[4]} (inverted, so that
+// zero is neutral).  A range with four sets puts 65 536 seeds onto four slots: the in-wave combine makes that at most four inserts per
+// wave (COMBINE = false, one insert per seed, is the baseline of the A/B).  The count words ride in lanes 0 .. 4 and are added once per wave.
+// sets_extract_kernel walks the list: entry j of slot list[j], the slot zeroed again; with the error word set it writes no entry and
+// clears the WHOLE table instead.
+struct SetsVocab { unsigned long long v[MADSIM_PROBE_SETS_MAX_VOCAB]; };
+constexpr uint32_t SETS_CLAIMS = 0, SETS_ERR = 1, SETS_COUNTS = 2, SETS_SLOT_WORDS = MADSIM_K_PROBE_SETS_SLOT_BYTES / 4;
+
+__global__ __launch_bounds__(256) void sets_mask_kernel(const unsigned long long* __restrict__ obs, uint32_t obs_cap,
+                                                        const unsigned long long* __restrict__ obs_len, const madsim_result_t* __restrict__ res,
+                                                        uint32_t n, uint32_t include, const SetsVocab vocab, uint32_t m,
+                                                        unsigned long long* __restrict__ sig) {
+    const uint32_t lane = threadIdx.x & 63, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const unsigned long long full = (~0ull >> (64u - m)) | MADSIM_PROBE_SET_OTHER;      // (1 <= m <= 62)
+    for (uint32_t i = blockIdx.x * 4u + wave; i < n; i += gridDim.x * 4u) {        // (scalar)
+        const uint32_t v = reinterpret_cast<const uint32_t*>(res + i)[0];
+        if (v >= 4u || !((include >> v) & 1u)) continue;                           // a runner or left-out verdict: the row is not read
+        const unsigned long long len = obs_len[i];
+        const uint32_t vis = len < obs_cap ? (uint32_t)len : obs_cap;
+        const unsigned long long* const row = obs + (size_t)i * obs_cap;
+        unsigned long long set = 0;
+        for (uint32_t k = 0; k * 64u < vis && (set & full) != full; k++) {
+            const uint32_t idx = k * 64u + lane;
+            const bool have = idx < vis;
+            const unsigned long long val = have ? row[idx] : 0ull;
+            const unsigned long long valid = __ballot(have);
+            unsigned long long hit = 0;
+            for (uint32_t j = 0; j < m; j++) {
+                const unsigned long long b = __ballot(val == vocab.v[j]) & valid;
+                hit |= b;
+                set |= (unsigned long long)(b != 0ull) << j;
+            }
+            if (valid & ~hit) set |= MADSIM_PROBE_SET_OTHER;
+        }
+        if (len > obs_cap) set |= MADSIM_PROBE_SET_TRUNCATED;
+        if (lane == 0u) sig[i] = set;
+    }
+}
+
+// the calling lane adds to set word `key`'s slot: ns[k] seeds of verdict k, the smallest of them index ~nf[k] (nf[k] = 0: none); seed i has the set
+__device__ __forceinline__ void sets_insert(const unsigned long long* __restrict__ sig, uint32_t n, uint32_t* __restrict__ table, uint32_t mask,
+                                            uint32_t* __restrict__ list, uint32_t cap, unsigned long long* __restrict__ words,
+                                            unsigned long long key, uint4 ns, uint4 nf, uint32_t i) {
+    if (__hip_atomic_load(&words[SETS_ERR], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;        // (the chunk has failed already)
+    uint32_t s = (uint32_t)census_slot(key, (uint64_t)mask + 1u);
+    for (uint32_t probe = 0; probe <= mask; probe++, s = (s + 1u) & mask) {
+        uint32_t* const slot = table + (size_t)s * SETS_SLOT_WORDS;
+        uint32_t tag = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // (a tag only ever goes from 0 to its value)
+        if (tag == 0) {
+            tag = atomicCAS(slot, 0u, i + 1u);
+            if (tag == 0) {                                                        // claimed: the slot's set is this seed's
+                const unsigned long long pos = atomicAdd(&words[SETS_CLAIMS], 1ull);
+                if (pos >= cap) { atomicOr(&words[SETS_ERR], (unsigned long long)MADSIM_K_PROBE_SETS_ERR_CAP); return; }
+                list[pos] = s;
+                tag = i + 1u;
+            }
+        }
+        bool match = tag == i + 1u;
+        if (!match) {
+            const uint32_t rep = tag - 1u;
+            if (rep >= n) { atomicOr(&words[SETS_ERR], (unsigned long long)MADSIM_K_PROBE_SETS_ERR_TAG); return; }      // (a table that was not clean)
+            match = sig[rep] == key;
+        }
+        if (match) {
+            if (ns.x) { atomicAdd(slot + 1, ns.x); atomicMax(slot + 5, nf.x); }
+            if (ns.y) { atomicAdd(slot + 2, ns.y); atomicMax(slot + 6, nf.y); }
+            if (ns.z) { atomicAdd(slot + 3, ns.z); atomicMax(slot + 7, nf.z); }
+            if (ns.w) { atomicAdd(slot + 4, ns.w); atomicMax(slot + 8, nf.w); }
+            return;
+        }
+    }
+    atomicOr(&words[SETS_ERR], (unsigned long long)MADSIM_K_PROBE_SETS_ERR_PROBE);  // (a full table: only ever behind claim number cap + 1)
+}
+
+// COMBINE = false: one insert per counted seed — the correctness baseline and the other side of the A/B
+template <bool COMBINE>
+__global__ __launch_bounds__(256) void sets_fold_kernel(const unsigned long long* __restrict__ sig, const madsim_result_t* __restrict__ res, uint32_t n,
+                                                        uint32_t include, uint32_t* __restrict__ table, uint32_t mask, uint32_t* __restrict__ list,
+                                                        uint32_t cap, unsigned long long* __restrict__ words) {
+    const uint32_t lane = threadIdx.x & 63;
+    uint32_t acc = 0;                                                              // lane k < 4: counted seeds of verdict k; lane 4: runner verdicts
+    for (uint64_t base = (uint64_t)(blockIdx.x * 4u + (threadIdx.x >> 6)) * 64u; base < n; base += (uint64_t)gridDim.x * 256u) {      // (wave-uniform)
+        const uint64_t i = base + lane;
+        uint32_t v = 0u;
+        const bool in = i < n;
+        if (in) v = reinterpret_cast<const uint32_t*>(res + i)[0];
+        const bool counted = in && v < 4u && ((include >> v) & 1u);
+        const unsigned long long b0 = __ballot(counted && v == 0u), b1 = __ballot(counted && v == 1u), b2 = __ballot(counted && v == 2u),
+                                 b3 = __ballot(counted && v == 3u), br = __ballot(in && v >= 4u);
+        acc += (uint32_t)__popcll(lane == 0u ? b0 : lane == 1u ? b1 : lane == 2u ? b2 : lane == 3u ? b3 : lane == 4u ? br : 0ull);
+        unsigned long long m = b0 | b1 | b2 | b3;
+        if (!m) continue;                                                          // (wave-uniform: a round with nothing counted ends here)
+        const unsigned long long key = counted ? sig[i] : 0ull;
+        if (COMBINE) {
+            uint4 ns = {0, 0, 0, 0}, nf = {0, 0, 0, 0};                            // non-zero in the leaders
+            while (m) {                                                            // (wave-uniform) one trip per distinct set word of the round
+                const int l = __ffsll((long long)m) - 1;
+                const unsigned long long lk = __shfl(key, l);
+                const unsigned long long sm = __ballot(counted && key == lk);     // a subset of m: lane l's set is none of the earlier leaders'
+                if ((int)lane == l) {
+                    const unsigned long long s0 = sm & b0, s1 = sm & b1, s2 = sm & b2, s3 = sm & b3;
+                    const uint32_t lo = (uint32_t)base;
+                    ns = make_uint4((uint32_t)__popcll(s0), (uint32_t)__popcll(s1), (uint32_t)__popcll(s2), (uint32_t)__popcll(s3));
+                    nf = make_uint4(s0 ? ~(lo + (uint32_t)__ffsll((long long)s0) - 1u) : 0u, s1 ? ~(lo + (uint32_t)__ffsll((long long)s1) - 1u) : 0u,
+                                    s2 ? ~(lo + (uint32_t)__ffsll((long long)s2) - 1u) : 0u, s3 ? ~(lo + (uint32_t)__ffsll((long long)s3) - 1u) : 0u);
+                }
+                m &= ~sm;
+            }
+            if (ns.x | ns.y | ns.z | ns.w) sets_insert(sig, n, table, mask, list, cap, words, key, ns, nf, (uint32_t)i);
+        } else if (counted) {
+            const uint32_t inv = ~(uint32_t)i;
+            sets_insert(sig, n, table, mask, list, cap, words, key, make_uint4(v == 0u, v == 1u, v == 2u, v == 3u),
+                        make_uint4(v == 0u ? inv : 0u, v == 1u ? inv : 0u, v == 2u ? inv : 0u, v == 3u ? inv : 0u), (uint32_t)i);
+        }
+    }
+    if (lane < 5u && acc) atomicAdd(&words[SETS_COUNTS + lane], (unsigned long long)acc);
+}
+
+__global__ __launch_bounds__(256) void sets_extract_kernel(const unsigned long long* __restrict__ sig, const unsigned long long* __restrict__ seeds,
+                                                           uint32_t n, uint32_t* __restrict__ table, uint32_t mask, const uint32_t* __restrict__ list,
+                                                           uint32_t cap, unsigned long long* __restrict__ words, unsigned long long* __restrict__ entries) {
+    uint4* const t = reinterpret_cast<uint4*>(table);                              // a slot is three of them
+    if (words[SETS_ERR]) {                                                         // (nobody sets it in this branch: uniform over the grid)
+        for (uint64_t j = blockIdx.x * 256u + threadIdx.x; j < 3ull * ((uint64_t)mask + 1u); j += gridDim.x * 256u) t[j] = uint4{0, 0, 0, 0};
+        return;
+    }
+    const unsigned long long claimed = words[SETS_CLAIMS];                         // (nobody adds to it in this kernel)
+    const uint32_t ne = claimed < cap ? (uint32_t)claimed : cap;
+    for (uint32_t j = blockIdx.x * 256u + threadIdx.x; j < ne; j += gridDim.x * 256u) {
+        const uint32_t s = list[j] & mask;
+        const uint4 e0 = t[3 * (size_t)s], e1 = t[3 * (size_t)s + 1], e2 = t[3 * (size_t)s + 2];
+        t[3 * (size_t)s] = uint4{0, 0, 0, 0}; t[3 * (size_t)s + 1] = uint4{0, 0, 0, 0}; t[3 * (size_t)s + 2] = uint4{0, 0, 0, 0};
+        const uint32_t rep = e0.x - 1u;
+        const uint32_t cnt[4] = {e0.y, e0.z, e0.w, e1.x}, first[4] = {~e1.y, ~e1.z, ~e1.w, ~e2.x};
+        unsigned long long* const p = entries + 9 * (size_t)j;
+        bool bad = e0.x == 0 || rep >= n;
+        for (int k = 0; k < 4; k++) bad |= cnt[k] != 0u && first[k] >= n;
+        if (bad) {                                                                 // (a table that was not clean)
+            atomicOr(&words[SETS_ERR], (unsigned long long)MADSIM_K_PROBE_SETS_ERR_TAG);
+            for (int q = 0; q < 9; q++) p[q] = 0;
+            continue;
+        }
+        p[0] = sig[rep];
+        for (int k = 0; k < 4; k++) { p[1 + k] = cnt[k]; p[5 + k] = cnt[k] ? seeds[first[k]] : 0ull; }
+    }
+}
+
 // one kernel per row of variant_table (sim_kernel.h), same macro, same order
 #define MADSIM_VARIANT_KERNEL(T_, S_, L_, F_, R_, G_) (const void*)sim_kernel<Variant<T_, S_, L_, F_, R_, G_>>,
 static const void* const variant_kernels[] = {MADSIM_FOR_EACH_VARIANT(MADSIM_VARIANT_KERNEL)};
@@ -1647,6 +1807,45 @@ extern "C" int madsim_k_launch_census(const uint64_t* obs, uint64_t obs_cap, con
                                       unsigned long long* words, madsim_census_value_t* entries, void* stream) {
     static const bool direct = [] { const char* e = getenv("MADSIM_HIP_CENSUS_DIRECT"); return e && atoi(e) != 0; }();      // (unset, empty or 0: the accumulator)
     return madsim_k_launch_census_form(obs, obs_cap, obs_len, res, d_seeds, n, include, table, slots, list, cap, words, entries, stream, direct);
+}
+
+// Rows, lengths, results and seeds of the chunk's n seeds; vocab: n_vocab values in HOST memory (they travel in the kernel arguments); sig:
+// n words of scratch; table: `slots` zeroed slots; list: `cap` words of scratch; words: MADSIM_K_PROBE_SETS_WORDS zeroed words; entries:
+// room for `cap` (sim_kernel.h).  Returns 0, or -1 (nothing launched) for sizes the kernels are not written for.
+// `per_seed` != 0: one table update per counted seed, no in-wave combine — the same bytes either way.
+extern "C" int madsim_k_launch_probe_sets_form(const uint64_t* obs, uint64_t obs_cap, const uint64_t* obs_len, const madsim_result_t* res,
+                                               const uint64_t* d_seeds, uint64_t n, uint32_t include, const uint64_t* vocab, uint64_t n_vocab,
+                                               uint64_t* sig, uint32_t* table, uint64_t slots, uint32_t* list, uint64_t cap, unsigned long long* words,
+                                               madsim_probe_set_t* entries, void* stream, int per_seed) {
+    static_assert(sizeof(madsim_probe_set_t) == 72 && 3 * sizeof(uint4) == MADSIM_K_PROBE_SETS_SLOT_BYTES && sizeof(madsim_result_t) == 48, "record layout");
+    static_assert(sizeof(madsim_k::SetsVocab) == 496, "the vocabulary in the kernel arguments");
+    if (n == 0 || obs_cap == 0 || obs_cap > MADSIM_CENSUS_MAX_OBS_CAP || n >= 0xffffffffull / obs_cap || n > (1ull << 31)) return -1;      // n * obs_cap < 2^32 - 1; the row index plus a grid stride stays 32-bit
+    if (include == 0 || (include & ~0xfu) || cap == 0 || cap > MADSIM_PROBE_SETS_MAX || n_vocab == 0 || n_vocab > MADSIM_PROBE_SETS_MAX_VOCAB) return -1;
+    if ((slots & (slots - 1)) || slots < 2 * cap || slots < MADSIM_K_PROBE_SETS_MIN_SLOTS || slots > (1ull << 26)) return -1;
+    if (!obs || !obs_len || !res || !d_seeds || !vocab || !sig || !table || !list || !words || !entries || ((uintptr_t)table & 15u)) return -1;
+    madsim_k::SetsVocab V{};
+    for (uint64_t j = 0; j < n_vocab; j++) V.v[j] = vocab[j];
+    const uint64_t waves = n < MADSIM_K_PROBE_SETS_WAVES ? n : MADSIM_K_PROBE_SETS_WAVES;      // one wave per row, 256 workgroups at most
+    hipLaunchKernelGGL(madsim_k::sets_mask_kernel, dim3((uint32_t)((waves + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const unsigned long long*)obs,
+                       (uint32_t)obs_cap, (const unsigned long long*)obs_len, res, (uint32_t)n, include, V, (uint32_t)n_vocab, (unsigned long long*)sig);
+    const uint64_t rounds = (n + 63) / 64, fwaves = rounds < MADSIM_K_PROBE_SETS_WAVES ? rounds : MADSIM_K_PROBE_SETS_WAVES;      // one lane per seed
+    const auto fold = per_seed ? madsim_k::sets_fold_kernel<false> : madsim_k::sets_fold_kernel<true>;
+    hipLaunchKernelGGL(fold, dim3((uint32_t)((fwaves + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const unsigned long long*)sig, res, (uint32_t)n,
+                       include, table, (uint32_t)(slots - 1), list, (uint32_t)cap, words);
+    uint32_t xgrid = (uint32_t)((cap + 255) / 256);        // the extraction pass: as many threads as there can be sets, 64 workgroups at most
+    if (xgrid > 64) xgrid = 64;
+    hipLaunchKernelGGL(madsim_k::sets_extract_kernel, dim3(xgrid), dim3(256), 0, (hipStream_t)stream, (const unsigned long long*)sig,
+                       (const unsigned long long*)d_seeds, (uint32_t)n, table, (uint32_t)(slots - 1), (const uint32_t*)list, (uint32_t)cap, words,
+                       reinterpret_cast<unsigned long long*>(entries));
+    return 0;
+}
+
+extern "C" int madsim_k_launch_probe_sets(const uint64_t* obs, uint64_t obs_cap, const uint64_t* obs_len, const madsim_result_t* res,
+                                          const uint64_t* d_seeds, uint64_t n, uint32_t include, const uint64_t* vocab, uint64_t n_vocab, uint64_t* sig,
+                                          uint32_t* table, uint64_t slots, uint32_t* list, uint64_t cap, unsigned long long* words,
+                                          madsim_probe_set_t* entries, void* stream) {
+    return madsim_k_launch_probe_sets_form(obs, obs_cap, obs_len, res, d_seeds, n, include, vocab, n_vocab, sig, table, slots, list, cap, words, entries,
+                                           stream, 0);
 }
 
 extern "C" void madsim_k_launch_keyflip(unsigned long long* acc, void* stream) {

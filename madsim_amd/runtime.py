@@ -167,6 +167,14 @@ def lib():
         L.madsim_hip_ctx_census_range.argtypes = [ctxp] + L.madsim_hip_census_range.argtypes
         L.madsim_hip_ctx_census_seeds.argtypes = [ctxp] + L.madsim_hip_census_seeds.argtypes
         L.madsim_k_fold_census.argtypes = [C.POINTER(A.Census), C.c_void_p, C.c_void_p, C.c_uint64]
+        # the probe-set census: the census's signatures with a madsim_probe_sets_t
+        L.madsim_hip_probe_sets_range.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(A.Limits),
+                                                  C.POINTER(A.ProbeSets)]
+        L.madsim_hip_probe_sets_seeds.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), u64p, C.c_uint64, C.c_uint64, C.POINTER(A.Limits),
+                                                  C.POINTER(A.ProbeSets)]
+        L.madsim_hip_ctx_probe_sets_range.argtypes = [ctxp] + L.madsim_hip_probe_sets_range.argtypes
+        L.madsim_hip_ctx_probe_sets_seeds.argtypes = [ctxp] + L.madsim_hip_probe_sets_seeds.argtypes
+        L.madsim_k_fold_probe_sets.argtypes = [C.POINTER(A.ProbeSets), C.c_void_p, C.c_void_p, C.c_uint64]
         # the sweep campaigns: one signature for the range (seeds NULL) and the list (seed0 0)
         L.madsim_hip_run_sweep_campaign.argtypes = [C.POINTER(A.SweepVariant), C.c_uint32, C.c_uint64, C.c_uint64, u64p, C.c_uint64, C.c_uint32,
                                                     C.c_uint32, C.POINTER(A.Sweep)]
@@ -563,6 +571,201 @@ def census(workload, seed0=0, total=0, seeds=None, include=(A.PASS, A.PANIC, A.D
     L = lib()
     return _census(lambda *a: L.madsim_hip_census_range(workload.ref(), *a), lambda *a: L.madsim_hip_census_seeds(workload.ref(), *a), workload,
                    seed0, total, seeds, include, obs_cap, max_values, chunk, config, limits, resolve)
+
+
+class ProbeSets:
+    """Which COMBINATIONS of the vocabulary's values the seeds reached, by verdict (runtime.probe_sets).  `vocabulary`: the tuple of distinct
+    values, value i owning bit i of a set word; `sets`: ndarray[A.PROBE_SET_DTYPE], ascending by `set` — per distinct set word the counted
+    seeds of each verdict with exactly this set (`n_seeds[4]`) and the smallest of them (`first_seed[4]`, 0 where there is none).  Bit 62
+    (A.PROBE_SET_OTHER): the seed traced a visible value outside the vocabulary; bit 63 (A.PROBE_SET_TRUNCATED): it traced more than
+    `obs_cap` values.  `n_counted[4]` are the column sums of n_seeds; `n_runner` seeds were left with a runner verdict and are counted
+    nowhere, `runner_seeds` (ndarray[uint64], ascending) the ones that were listed.  The readers take vocabulary VALUES and give Python
+    ints and Fractions."""
+
+    def __init__(self, vocabulary, sets, n_counted, n_runner, runner_seeds, include, obs_cap):
+        self.vocabulary = tuple(int(v) for v in vocabulary)
+        self.sets = sets
+        self.n_counted, self.n_runner = tuple(int(x) for x in n_counted), int(n_runner)
+        self.runner_seeds, self.include, self.obs_cap = runner_seeds, include, obs_cap
+        self._bit = {v: i for i, v in enumerate(self.vocabulary)}
+
+    def __len__(self):
+        return len(self.sets)
+
+    def __repr__(self):
+        return (f"ProbeSets({len(self.sets)} sets of {len(self.vocabulary)} values over {sum(self.n_counted)} counted seeds, "
+                f"n_counted={self.n_counted}, n_runner={self.n_runner})")
+
+    def tobytes(self):
+        """The whole report as bytes: two reports under one vocabulary are the same exactly when these are equal."""
+        totals = np.array(self.n_counted + (self.n_runner,), dtype=np.uint64)
+        return self.sets.tobytes() + totals.tobytes() + np.asarray(self.runner_seeds, dtype=np.uint64).tobytes()
+
+    def mask(self, values):
+        """The set-word bits of the vocabulary values `values`."""
+        m = 0
+        for v in values:
+            if int(v) not in self._bit:
+                raise MadsimHipError(f"probe_sets: {int(v):#x} is not in the vocabulary")
+            m |= 1 << self._bit[int(v)]
+        return m
+
+    def values_of(self, set_word):
+        """The vocabulary values whose bits `set_word` holds, in vocabulary order."""
+        return tuple(v for i, v in enumerate(self.vocabulary) if (int(set_word) >> i) & 1)
+
+    @staticmethod
+    def _verdicts(verdicts):
+        vs = (0, 1, 2, 3) if verdicts is None else (verdicts,) if isinstance(verdicts, int) else tuple(verdicts)
+        for v in vs:
+            if not 0 <= int(v) < 4:
+                raise MadsimHipError(f"verdicts: 0-3 (PASS, PANIC, DEADLOCK, TIME_LIMIT), got {v}")
+        return tuple(sorted(set(int(v) for v in vs)))
+
+    def _match(self, all_of=(), none_of=(), other=None, truncated=None):
+        """The indices of the entries whose set holds every value of `all_of` and none of `none_of`; other / truncated: None = either, else
+        the OTHER / TRUNCATED bit must be as given."""
+        want, avoid = self.mask(all_of), self.mask(none_of)
+        for flag, bit in ((other, A.PROBE_SET_OTHER), (truncated, A.PROBE_SET_TRUNCATED)):
+            if flag is not None:
+                want, avoid = (want | bit, avoid) if flag else (want, avoid | bit)
+        return [i for i, s in enumerate(int(x) for x in self.sets["set"]) if s & want == want and not s & avoid]
+
+    def count(self, all_of=(), none_of=(), verdicts=None, other=None, truncated=None):
+        """Counted seeds of `verdicts` (None: all four) that reached every value of `all_of` and none of `none_of`."""
+        vs = self._verdicts(verdicts)
+        return sum(int(self.sets["n_seeds"][i][k]) for i in self._match(all_of, none_of, other, truncated) for k in vs)
+
+    def failing_share(self, all_of=(), none_of=()):
+        """(share of the matching seeds which fail, share of all counted seeds which fail), each a fractions.Fraction — a failing seed is a
+        counted one whose verdict is not PASS.  None in place of a share over no seeds."""
+        n, f = self.count(all_of, none_of), self.count(all_of, none_of, verdicts=(1, 2, 3))
+        return (Fraction(f, n) if n else None), (Fraction(sum(self.n_counted[1:]), sum(self.n_counted)) if sum(self.n_counted) else None)
+
+    def first_seeds(self, all_of=(), none_of=(), verdicts=None):
+        """{verdict: the smallest counted seed of that verdict that matches}, for the verdicts of `verdicts` that have one: the seeds to replay."""
+        out = {}
+        for i in self._match(all_of, none_of):
+            for k in self._verdicts(verdicts):
+                if int(self.sets["n_seeds"][i][k]):
+                    out[k] = min(out.get(k, A.U64_MAX), int(self.sets["first_seed"][i][k]))
+        return out
+
+    def cooccurrence(self, verdicts=None):
+        """m x m lists of ints: [i][j] = counted seeds of `verdicts` that reached both vocabulary[i] and vocabulary[j] ([i][i]: reached value i)."""
+        vs, m = self._verdicts(verdicts), len(self.vocabulary)
+        out = [[0] * m for _ in range(m)]
+        for e in self.sets:
+            s, n = int(e["set"]), sum(int(e["n_seeds"][k]) for k in vs)
+            bits = [i for i in range(m) if (s >> i) & 1]
+            for i in bits:
+                for j in bits:
+                    out[i][j] += n
+        return out
+
+    def mixed(self):
+        """The sets that occur under PASS and under a failing verdict — the probes do not tell those seeds apart —, ascending: a list of
+        (set word, a passing seed, a failing seed), each the smallest of its kind."""
+        out = []
+        for e in self.sets:
+            fails = [int(e["first_seed"][k]) for k in (1, 2, 3) if int(e["n_seeds"][k])]
+            if int(e["n_seeds"][0]) and fails:
+                out.append((int(e["set"]), int(e["first_seed"][0]), min(fails)))
+        return out
+
+    def cover(self, verdicts=None):
+        """A small corpus that between its seeds reaches every vocabulary value some counted seed of `verdicts` reached: a greedy set cover
+        over the entries — each round the entry that adds the most new values, ties to the smaller set word — giving one seed per chosen
+        entry (its smallest of `verdicts`), ascending and unique: ready for run_campaign_seeds."""
+        vs, vmask = self._verdicts(verdicts), (1 << len(self.vocabulary)) - 1
+        cand = []
+        for e in self.sets:
+            seeds = [int(e["first_seed"][k]) for k in vs if int(e["n_seeds"][k])]
+            if seeds:
+                cand.append((int(e["set"]) & vmask, int(e["set"]), min(seeds)))
+        missing, chosen = 0, set()
+        for bits, _, _ in cand:
+            missing |= bits
+        while missing:
+            bits, _, seed = max(cand, key=lambda c: (bin(c[0] & missing).count("1"), -c[1]))
+            chosen.add(seed)
+            missing &= ~bits
+        return sorted(chosen)
+
+    def merge(self, other):
+        """The report of the union of two DISJOINT seed sets taken under the same vocabulary, include mask and obs_cap: exact, in either order."""
+        if (self.vocabulary, self.include, self.obs_cap) != (other.vocabulary, other.include, other.obs_cap):
+            raise MadsimHipError("ProbeSets.merge: the two reports differ in vocabulary, include or obs_cap")
+        out = np.zeros(len(self.sets) + len(other.sets), dtype=A.PROBE_SET_DTYPE)
+        out[:len(self.sets)] = self.sets
+        ps = A.ProbeSets(include=self.include, obs_cap=self.obs_cap, cap=max(len(out), 1), n_sets=len(self.sets))
+        ps.sets = out.ctypes.data_as(C.POINTER(A.ProbeSet))
+        add = np.ascontiguousarray(other.sets)
+        if lib().madsim_k_fold_probe_sets(C.byref(ps), None, add.ctypes.data_as(C.c_void_p), len(add)):
+            raise MadsimHipError("ProbeSets.merge: madsim_k_fold_probe_sets failed")
+        runner = np.sort(np.concatenate([np.asarray(self.runner_seeds, dtype=np.uint64), np.asarray(other.runner_seeds, dtype=np.uint64)]))
+        return ProbeSets(self.vocabulary, out[:ps.n_sets].copy(), tuple(x + y for x, y in zip(self.n_counted, other.n_counted)),
+                         self.n_runner + other.n_runner, runner, self.include, self.obs_cap)
+
+
+def _probe_sets(call_range, call_seeds, census_call, workload, vocabulary, seed0, total, seeds, include, obs_cap, max_sets, chunk, config, limits,
+                resolve):
+    """One probe-set call — `call_range(cfg, seed0, total, chunk, lim, ps)` or `call_seeds(cfg, seeds*, n, chunk, lim, ps)`, a
+    madsim_hip_*probe_sets_* entry point with its context and workload bound — and then, round by round, one list call over the seeds the
+    last one left with a runner verdict, under grown_limits(workload, limits, r), merged in: what _census does.  vocabulary=None: one
+    `census_call` (the same seeds, masks and limits) first, whose values are the vocabulary."""
+    cfg, lim0 = config or A.Config.default(), limits or A.Limits()
+    mask = _include_mask(include)
+    rounds = 0 if resolve is None or resolve is False else A.RESOLVE_DEFAULT_ROUNDS if resolve is True else int(resolve)
+    if not 0 <= rounds <= A.RESOLVE_MAX_ROUNDS:
+        raise MadsimHipError(f"resolve: None, True or a number of rounds 1..{A.RESOLVE_MAX_ROUNDS}, got {resolve!r}")
+    if vocabulary is None:
+        cen = census_call(workload, seed0, total, seeds, include, obs_cap, 4096, chunk, config, limits, resolve)
+        vocabulary = [int(v) for v in cen.values["value"]]
+        if not vocabulary:
+            raise MadsimHipError("probe_sets: vocabulary=None and no counted seed traced a value: there is no vocabulary to take")
+    vocab = np.array([int(v) for v in vocabulary], dtype=np.uint64)
+    if not 1 <= len(vocab) <= A.PROBE_SETS_MAX_VOCAB:
+        raise MadsimHipError(f"probe_sets: a vocabulary of 1..{A.PROBE_SETS_MAX_VOCAB} values, got {len(vocab)} (a set word has one bit per value)")
+    if len(set(int(v) for v in vocab)) != len(vocab):
+        raise MadsimHipError("probe_sets: a value occurs twice in the vocabulary")
+
+    def one(lim, sa, s0, n):
+        sets, runner = np.zeros(max(int(max_sets), 1), dtype=A.PROBE_SET_DTYPE), np.zeros(max(n, 1), dtype=np.uint64)
+        ps = A.ProbeSets(include=mask, obs_cap=obs_cap, n_vocab=len(vocab), cap=max_sets, runner_cap=n)
+        ps.vocab, ps.sets = vocab.ctypes.data_as(C.POINTER(C.c_uint64)), sets.ctypes.data_as(C.POINTER(A.ProbeSet))
+        ps.runner_seeds = runner.ctypes.data_as(C.POINTER(C.c_uint64))
+        if sa is None:
+            _check(call_range(C.byref(cfg), s0, n, chunk, C.byref(lim), C.byref(ps)))
+        else:
+            _check(call_seeds(C.byref(cfg), _seeds_ptr(sa), n, chunk, C.byref(lim), C.byref(ps)))
+        return ProbeSets(vocab, sets[:ps.n_sets].copy(), ps.n_counted, ps.n_runner, runner[:ps.n_runner_listed].copy(), mask, obs_cap)
+
+    sa = None if seeds is None else seed_list(seeds)
+    rep = one(lim0, sa, int(seed0), int(total) if sa is None else len(sa))
+    for r in range(1, rounds + 1):
+        if not len(rep.runner_seeds):
+            break
+        more = one(grown_limits(workload, lim0, r), rep.runner_seeds, 0, len(rep.runner_seeds))
+        rep.n_runner, rep.runner_seeds = 0, np.zeros(0, dtype=np.uint64)
+        rep = rep.merge(more)
+        if len(rep.sets) > max_sets:
+            raise MadsimHipError(f"probe_sets: more than max_sets = {max_sets} distinct probe sets once the runner seeds are settled")
+    return rep
+
+
+def probe_sets(workload, vocabulary=None, seed0=0, total=0, seeds=None, include=(A.PASS, A.PANIC, A.DEADLOCK, A.TIME_LIMIT), obs_cap=256,
+               max_sets=4096, chunk=0, config=None, limits=None, resolve=True):
+    """madsim_hip_probe_sets_range / madsim_hip_probe_sets_seeds: which COMBINATIONS of the values of `vocabulary` (1 .. 62 distinct 64-bit
+    values; None: the values a census of the same seeds finds) the seeds [seed0, seed0 + total) — or the strictly ascending `seeds` —
+    reach, by verdict, reduced on the device: returns a ProbeSets.  A seed is counted when its verdict is in `include`; the first `obs_cap`
+    observations of a seed are visible; more than `max_sets` distinct sets is MadsimHipError; `chunk` = seeds per trace launch, 0 = the
+    library's default — it never shows in the result.  resolve: as runtime.census."""
+    if _inited_device is None:
+        init(0)
+    L = lib()
+    return _probe_sets(lambda *a: L.madsim_hip_probe_sets_range(workload.ref(), *a), lambda *a: L.madsim_hip_probe_sets_seeds(workload.ref(), *a),
+                       census, workload, vocabulary, seed0, total, seeds, include, obs_cap, max_sets, chunk, config, limits, resolve)
 
 
 def observe_seed(workload, seed, config=None, limits=None, cap=1 << 16, resolve=True):
@@ -1272,6 +1475,14 @@ class Context:
         return _census(lambda *a: L.madsim_hip_ctx_census_range(self._h, workload.ref(), *a),
                        lambda *a: L.madsim_hip_ctx_census_seeds(self._h, workload.ref(), *a), workload, seed0, total, seeds, include, obs_cap,
                        max_values, chunk, config, limits, resolve)
+
+    def probe_sets(self, workload, vocabulary=None, seed0=0, total=0, seeds=None, include=(A.PASS, A.PANIC, A.DEADLOCK, A.TIME_LIMIT), obs_cap=256,
+                   max_sets=4096, chunk=0, config=None, limits=None, resolve=True):
+        """runtime.probe_sets on this context (madsim_hip_ctx_probe_sets_range / madsim_hip_ctx_probe_sets_seeds)."""
+        L = lib()
+        return _probe_sets(lambda *a: L.madsim_hip_ctx_probe_sets_range(self._h, workload.ref(), *a),
+                           lambda *a: L.madsim_hip_ctx_probe_sets_seeds(self._h, workload.ref(), *a), self.census, workload, vocabulary, seed0,
+                           total, seeds, include, obs_cap, max_sets, chunk, config, limits, resolve)
 
     def observe_seed(self, workload, seed, config=None, limits=None, cap=1 << 16, resolve=True):
         """runtime.observe_seed on this context."""

@@ -80,7 +80,7 @@ def main():
         name, val = m.group(1), m.group(2)
         if name == "MADSIM_HIP_H":
             continue
-        ty = "c_int" if name.startswith("MADSIM_E_") else "u32"
+        ty = "c_int" if name.startswith("MADSIM_E_") else "u32" if int(val, 0) <= 0xffffffff else "u64"
         w(f"pub const {name}: {ty} = {val};")
     w("")
     w('#[link(name = "madsim_hip")]')
