@@ -230,22 +230,24 @@ struct madsim_hip_resources {
     struct TraceSet { DevBuf<uint8_t> log; DevBuf<uint64_t> obs, len; DevBuf<madsim_result_t> out; };
     TraceSet trace[2];
     DevBuf<madsim_divergence_t> d_drec; DevBuf<uint64_t> d_dctx;      // divergence reports: the records and the context rows
-    // the observation census: the table (all zero between chunks; `dirty` when it is new or an error may have left it otherwise), the claim
-    // list, the words and the chunk's entries (device); page-locked: the words, the entries, the range form's seed slice and — only for a
-    // chunk with runner verdicts whose seeds the caller still wants — the chunk's results
-    struct Census {
-        DevBuf<uint32_t> tab, list; DevBuf<unsigned long long> words; DevBuf<madsim_census_value_t> ent;
-        PinnedBuf<unsigned long long> h_words; PinnedBuf<madsim_census_value_t> h_ent; PinnedBuf<uint64_t> h_seeds; PinnedBuf<madsim_result_t> h_res;
+    // One census form's buffers (the observation census, the probe-set census: each its own, the slots differ in size): the table (all zero
+    // between chunks; `dirty` when it is new or an error may have left it otherwise), the claim list, the words and the chunk's entries
+    // (device); page-locked: the words, the entries, the range form's seed slice and — only for a chunk with runner verdicts whose seeds the
+    // caller still wants — the chunk's results.
+    template <class Entry, size_t SlotBytes, size_t Words>
+    struct ObsReport {
+        DevBuf<uint32_t> tab, list; DevBuf<unsigned long long> words; DevBuf<Entry> ent;
+        PinnedBuf<unsigned long long> h_words; PinnedBuf<Entry> h_ent; PinnedBuf<uint64_t> h_seeds; PinnedBuf<madsim_result_t> h_res;
         bool dirty = true;
-        int ensure(uint64_t cap, uint64_t chunk, bool range, hipStream_t s) {
-            const size_t tab_words = (size_t)(madsim_k_census_slots(cap) * MADSIM_K_CENSUS_SLOT_BYTES / sizeof(uint32_t));
+        int ensure(uint64_t slots, uint64_t cap, uint64_t chunk, bool range, hipStream_t s) {
+            const size_t tab_words = (size_t)(slots * SlotBytes / sizeof(uint32_t));
             if (tab_words > tab.cap) dirty = true;
             HIP_TRY(tab.room(tab_words, s));
             HIP_TRY(list.room((size_t)cap, s));
             HIP_TRY(ent.room((size_t)cap, s));
             HIP_TRY(h_ent.room((size_t)cap, s));
-            HIP_TRY(words.room(MADSIM_K_CENSUS_WORDS));
-            HIP_TRY(h_words.room(MADSIM_K_CENSUS_WORDS));
+            HIP_TRY(words.room(Words));
+            HIP_TRY(h_words.room(Words));
             if (range) HIP_TRY(h_seeds.room((size_t)chunk, s));
             if (dirty) {
                 HIP_TRY(hipMemsetAsync(tab, 0, tab.cap * sizeof(uint32_t), s));
@@ -254,31 +256,13 @@ struct madsim_hip_resources {
             }
             return 0;
         }
-    } census;
-    // the probe-set census: the set word of every seed of a chunk (device only), the table (all zero between chunks; `dirty` as above), the
-    // claim list, the words and the chunk's entries; page-locked: the words, the entries, the range form's seed slice and — only for a chunk
-    // with runner verdicts whose seeds the caller still wants — the chunk's results
-    struct ProbeSets {
-        DevBuf<uint64_t> sig; DevBuf<uint32_t> tab, list; DevBuf<unsigned long long> words; DevBuf<madsim_probe_set_t> ent;
-        PinnedBuf<unsigned long long> h_words; PinnedBuf<madsim_probe_set_t> h_ent; PinnedBuf<uint64_t> h_seeds; PinnedBuf<madsim_result_t> h_res;
-        bool dirty = true;
-        int ensure(uint64_t cap, uint64_t chunk, bool range, hipStream_t s) {
-            const size_t tab_words = (size_t)(madsim_k_probe_sets_slots(cap) * MADSIM_K_PROBE_SETS_SLOT_BYTES / sizeof(uint32_t));
-            if (tab_words > tab.cap) dirty = true;
-            HIP_TRY(tab.room(tab_words, s));
+    };
+    ObsReport<madsim_census_value_t, MADSIM_K_CENSUS_SLOT_BYTES, MADSIM_K_CENSUS_WORDS> census;
+    struct ProbeSets : ObsReport<madsim_probe_set_t, MADSIM_K_PROBE_SETS_SLOT_BYTES, MADSIM_K_PROBE_SETS_WORDS> {
+        DevBuf<uint64_t> sig;                 // its own: the set word of every seed of a chunk (device only)
+        int ensure(uint64_t slots, uint64_t cap, uint64_t chunk, bool range, hipStream_t s) {
             HIP_TRY(sig.room((size_t)chunk, s));
-            HIP_TRY(list.room((size_t)cap, s));
-            HIP_TRY(ent.room((size_t)cap, s));
-            HIP_TRY(h_ent.room((size_t)cap, s));
-            HIP_TRY(words.room(MADSIM_K_PROBE_SETS_WORDS));
-            HIP_TRY(h_words.room(MADSIM_K_PROBE_SETS_WORDS));
-            if (range) HIP_TRY(h_seeds.room((size_t)chunk, s));
-            if (dirty) {
-                HIP_TRY(hipMemsetAsync(tab, 0, tab.cap * sizeof(uint32_t), s));
-                HIP_TRY(hipStreamSynchronize(s));
-                dirty = false;
-            }
-            return 0;
+            return ObsReport::ensure(slots, cap, chunk, range, s);
         }
     } probe_sets;
     Event ev0, ev1;
@@ -1113,286 +1097,256 @@ int madsim_hip_ctx_diverge_seeds(madsim_hip_ctx_t* c, const madsim_workload_t* w
     return 0;
 }
 
-// ---- the observation census: table size, probe start, the host fold of a chunk, and the chunk loop ---------------------------------
-extern "C" uint64_t madsim_k_census_slots(uint64_t cap) {
-    uint64_t slots = MADSIM_K_CENSUS_MIN_SLOTS;
-    while (slots < 2 * cap) slots <<= 1;
-    return slots;
-}
-
-extern "C" uint64_t madsim_k_census_slot(uint64_t value, uint64_t slots) { return madsim_k::census_slot(value, slots); }
-
-// Declared in sim_kernel.h beside the launcher (not part of the public ABI): the tests feed it entries without a device.  Everything it
-// does commutes, so the order of the chunks and of a chunk's entries never shows; equal values inside one chunk's entries are combined too.
-extern "C" int madsim_k_fold_census(madsim_census_t* cen, const unsigned long long* words, const madsim_census_value_t* entries, uint64_t n) {
-    auto combine = [](madsim_census_value_t& a, const madsim_census_value_t& b) {
+// ---- the observation census and the probe-set census: table size, probe start, the host fold of a chunk, and the chunk loop ----------
+// One of each for both.  A form says what is its own: the report and its entries (key, combine, the totals a chunk's words add), its
+// argument checks and what an empty report is, the sizes, its kernels' launch, the word that counts runner verdicts and its messages.
+namespace {
+extern "C++" {
+// Which traced values the seeds reach: entries keyed by the value.
+struct CensusForm {
+    typedef madsim_census_t Report;
+    typedef madsim_census_value_t Entry;
+    static_assert(sizeof(Entry) == 64 && sizeof(Report) == 144, "record layout");
+    Report* r;
+    static constexpr uint64_t slot_bytes = MADSIM_K_CENSUS_SLOT_BYTES, min_slots = MADSIM_K_CENSUS_MIN_SLOTS, n_words = MADSIM_K_CENSUS_WORDS;
+    static constexpr uint64_t per_seed_bytes = 3 * sizeof(uint64_t) + sizeof(madsim_result_t);      // beside the row: two length words, the seed, the result
+    static constexpr uint64_t eager = 64;              // entries copied behind a chunk's words, before their number is known (a probe vocabulary is small: 4 KB)
+    static constexpr uint32_t runner_word = 12, err_cap = MADSIM_K_CENSUS_ERR_CAP;
+    static constexpr const char *name = "census", *noun = "census";
+    static constexpr const char *at_zero = "hipMemsetAsync(census words)", *at_launch = "census kernel launch", *at_words = "hipMemcpyAsync(census words)",
+                                *at_entries = "hipMemcpyAsync(census entries)";
+    static constexpr const char* too_big = "census: chunk x (8 obs_cap + 72) + 32 slots + 68 cap + 128 exceeds MADSIM_TRACE_MAX_BYTES, or chunk x obs_cap reaches 2^32 - 1: a smaller chunk or smaller caps";
+    static constexpr const char* too_many = "census: more than `cap` distinct observed values (a traced time or random value is not a probe vocabulary): raise cap (max_values), or trace less";
+    static auto& bufs(madsim_hip_ctx_t* c) { return c->census; }
+    Entry* entries() const { return r->values; }
+    uint64_t& count() const { return r->n_values; }
+    static uint64_t key(const Entry& e) { return e.value; }
+    static void combine(Entry& a, const Entry& b) {
         for (int k = 0; k < 4; k++) a.n_seeds[k] += b.n_seeds[k];
         a.n_total += b.n_total;
         a.first_seed = std::min(a.first_seed, b.first_seed);
         a.max_per_seed = std::max(a.max_per_seed, b.max_per_seed);
-    };
-    std::vector<madsim_census_value_t> add(entries, entries + n);
-    std::sort(add.begin(), add.end(), [](const madsim_census_value_t& a, const madsim_census_value_t& b) { return a.value < b.value; });
-    size_t m = 0;
-    for (size_t j = 0; j < add.size(); j++) {
-        if (m && add[m - 1].value == add[j].value) combine(add[m - 1], add[j]); else add[m++] = add[j];
     }
-    madsim_census_value_t* const v = cen->values;
-    const uint64_t have = cen->n_values;
-    uint64_t fresh = 0;
-    for (size_t i = 0, j = 0; j < m; j++) {
-        while (i < have && v[i].value < add[j].value) i++;
-        if (i >= have || v[i].value != add[j].value) fresh++;
+    void totals(const unsigned long long* words) const {
+        for (int k = 0; k < 4; k++) { r->n_counted[k] += words[2 + k]; r->n_silent[k] += words[6 + k]; }
+        r->n_truncated += words[10]; r->n_observations += words[11]; r->n_runner += words[12];
     }
-    if (have + fresh > cen->cap) return -1;
-    for (int64_t i = (int64_t)have - 1, j = (int64_t)m - 1, k = (int64_t)(have + fresh) - 1; j >= 0; k--) {      // merged from the back, in place
-        if (i >= 0 && v[i].value > add[j].value) v[k] = v[i--];
-        else if (i >= 0 && v[i].value == add[j].value) { madsim_census_value_t e = v[i--]; combine(e, add[j--]); v[k] = e; }
-        else v[k] = add[j--];
+    int check() const {
+        if (!r) return fail(MADSIM_E_ARG, "census: null census");
+        if (r->include == 0 || (r->include & ~0xfu)) return fail(MADSIM_E_ARG, "census: include is 0 or names a verdict at or above 4 (only PASS, PANIC, DEADLOCK, TIME_LIMIT are counted)");
+        if (r->cap == 0 || r->cap > MADSIM_CENSUS_MAX_VALUES || !r->values) return fail(MADSIM_E_ARG, "census: cap outside 1 .. MADSIM_CENSUS_MAX_VALUES, or no value array");
+        if (r->obs_cap == 0 || r->obs_cap > MADSIM_CENSUS_MAX_OBS_CAP) return fail(MADSIM_E_ARG, "census: obs_cap outside 1 .. MADSIM_CENSUS_MAX_OBS_CAP");
+        if (r->runner_cap && !r->runner_seeds) return fail(MADSIM_E_ARG, "census: runner_cap without runner_seeds");
+        return 0;
     }
-    cen->n_values = have + fresh;
-    if (words) {
-        for (int k = 0; k < 4; k++) { cen->n_counted[k] += words[2 + k]; cen->n_silent[k] += words[6 + k]; }
-        cen->n_truncated += words[10]; cen->n_observations += words[11]; cen->n_runner += words[12];
+    void nothing() const {
+        r->n_values = r->n_truncated = r->n_observations = r->n_runner = r->n_runner_listed = 0;
+        for (int k = 0; k < 4; k++) r->n_counted[k] = r->n_silent[k] = 0;
     }
-    return 0;
-}
-
-// The census of [seed0, seed0 + total) (seeds == nullptr) or of seeds[0 .. total): chunk after chunk on one stream, each the trace launch
-// into the context's trace set 0, the two census kernels and the copies of the words and of the first CENSUS_EAGER_ENTRIES entries, then
-// one synchronisation: the chunk of a probe vocabulary is done there.  Entries beyond those — and, where the caller still wants runner
-// seeds and the chunk has some, its results — follow by copies of their own.  Once a chunk is queued no
-// error returns before its synchronisation (TraceSteps); an error that may have left the table otherwise than zero marks it dirty.
-constexpr uint64_t CENSUS_EAGER_ENTRIES = 64;      // entries copied behind a chunk's words, before their number is known
-
-static int census_run(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, const uint64_t* seeds,
-                      uint64_t total, uint64_t chunk, const madsim_limits_t* lim, madsim_census_t* cen, bool list) {
-    static_assert(sizeof(madsim_census_value_t) == 64 && sizeof(madsim_census_t) == 144, "record layout");
-    if (!cen) return fail(MADSIM_E_ARG, "census: null census");
-    if (cen->include == 0 || (cen->include & ~0xfu)) return fail(MADSIM_E_ARG, "census: include is 0 or names a verdict at or above 4 (only PASS, PANIC, DEADLOCK, TIME_LIMIT are counted)");
-    if (cen->cap == 0 || cen->cap > MADSIM_CENSUS_MAX_VALUES || !cen->values) return fail(MADSIM_E_ARG, "census: cap outside 1 .. MADSIM_CENSUS_MAX_VALUES, or no value array");
-    if (cen->obs_cap == 0 || cen->obs_cap > MADSIM_CENSUS_MAX_OBS_CAP) return fail(MADSIM_E_ARG, "census: obs_cap outside 1 .. MADSIM_CENSUS_MAX_OBS_CAP");
-    if (cen->runner_cap && !cen->runner_seeds) return fail(MADSIM_E_ARG, "census: runner_cap without runner_seeds");
-    if (list && total && !seeds) return fail(MADSIM_E_ARG, "census_seeds: null seed list");
-    if (list)
-        for (uint64_t i = 1; i < total; i++)
-            if (seeds[i] <= seeds[i - 1]) return fail(MADSIM_E_ARG, "census_seeds: the seed list is not strictly ascending (sort and deduplicate it first)");
-    auto nothing = [cen] {
-        cen->n_values = cen->n_truncated = cen->n_observations = cen->n_runner = cen->n_runner_listed = 0;
-        for (int k = 0; k < 4; k++) cen->n_counted[k] = cen->n_silent[k] = 0;
-    };
-    nothing();
-    if (total == 0) return 0;
-    // what a chunk asks of the device: per seed the row, two length words, the seed and the result; once the table, the list, the entries, the words
-    const uint64_t M = MADSIM_TRACE_MAX_BYTES, obs_cap = cen->obs_cap, cap = cen->cap;
-    const uint64_t fixed = madsim_k_census_slots(cap) * MADSIM_K_CENSUS_SLOT_BYTES + cap * (sizeof(uint32_t) + sizeof(madsim_census_value_t)) + MADSIM_K_CENSUS_WORDS * 8;
-    const uint64_t per_seed = 8 * obs_cap + 3 * sizeof(uint64_t) + sizeof(madsim_result_t);
-    const uint64_t fits = fixed < M ? std::min<uint64_t>((M - fixed) / per_seed, 0xffffffffull / obs_cap - 1) : 0;
-    if (chunk == 0) chunk = std::min<uint64_t>(65536, fits);
-    if (chunk == 0 || chunk > fits)
-        return fail(MADSIM_E_LIMITS, "census: chunk x (8 obs_cap + 72) + 32 slots + 68 cap + 128 exceeds MADSIM_TRACE_MAX_BYTES, or chunk x obs_cap reaches 2^32 - 1: a smaller chunk or smaller caps");
-    chunk = std::min(chunk, total);
-    int rc = madsim_geo::validate(w, cfg, &g_err);
-    if (rc) return rc;
-    CTX_ENTER(c);
-    hipStream_t st = nullptr;
-    madsim_hip_ctx::TraceSet& S = c->trace[0];
-    madsim_hip_ctx::Census& C = c->census;
-    for (uint64_t done = 0; done < total; done += chunk) {
-        const uint64_t n = std::min(chunk, total - done);
-        Geo G;
-        if ((rc = trace_prepare(c, w, cfg, lim, n, 0, obs_cap, S, G, st))) { nothing(); return rc; }
-        if ((rc = C.ensure(cap, chunk, !list, st))) { nothing(); return rc; }
-        const uint64_t* src = list ? seeds + done : C.h_seeds.p;
-        if (!list) for (uint64_t i = 0; i < n; i++) C.h_seeds.p[i] = seed0 + done + i;
-        TraceSteps step;
-        bool ok = step(hipMemcpyAsync(c->d_seeds, src, n * sizeof(uint64_t), hipMemcpyHostToDevice, st), "hipMemcpyAsync(seeds)");
-        if (ok) ok = step(hipMemsetAsync(C.words, 0, MADSIM_K_CENSUS_WORDS * sizeof(unsigned long long), st), "hipMemsetAsync(census words)");
-        ok = trace_queue(G, S, n, 0, obs_cap, true, st, step, ok);
-        if (ok) {
-            const int refused = madsim_k_launch_census(S.obs, obs_cap, S.len + n, S.out, c->d_seeds, n, cen->include, C.tab, madsim_k_census_slots(cap),
-                                                       C.list, cap, C.words, C.ent, st);
-            if (refused) step.no_build = true;
-            ok = step(refused ? hipSuccess : hipGetLastError(), "census kernel launch");
-        }
-        if (ok) ok = step(hipMemcpyAsync(C.h_words, C.words, MADSIM_K_CENSUS_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st), "hipMemcpyAsync(census words)");
-        // the first entries ride behind the words (a probe vocabulary is small: 4 KB); a chunk with more gets the rest in a copy of its own
-        const uint64_t eager = std::min<uint64_t>(cap, CENSUS_EAGER_ENTRIES);
-        if (ok) ok = step(hipMemcpyAsync(C.h_ent, C.ent, eager * sizeof(madsim_census_value_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync(census entries)");
-        ok = step(hipStreamSynchronize(st), "hipStreamSynchronize");
-        if (step.err != hipSuccess) { C.dirty = true; nothing(); return fail(MADSIM_E_HIP, std::string(step.at) + ": " + hipGetErrorString(step.err)); }
-        if (step.no_build) { nothing(); return fail(MADSIM_E_LIMITS, "no trace kernel build, or sizes the census kernels refuse"); }
-        const unsigned long long* W = C.h_words;
-        const char* const too_many = "census: more than `cap` distinct observed values (a traced time or random value is not a probe vocabulary): raise cap (max_values), or trace less";
-        if (W[1] & MADSIM_K_CENSUS_ERR_CAP) { nothing(); return fail(MADSIM_E_LIMITS, too_many); }      // (the extract pass has cleared the table)
-        if (W[1]) { C.dirty = true; nothing(); return fail(MADSIM_E_HIP, "census: the device table was not clean (internal)"); }
-        const uint64_t nv = W[0];
-        if (nv > eager) {
-            const hipError_t e = hipMemcpy(C.h_ent + eager, C.ent + eager, (nv - eager) * sizeof(madsim_census_value_t), hipMemcpyDeviceToHost);
-            if (e != hipSuccess) { nothing(); return fail(MADSIM_E_HIP, std::string("hipMemcpy(census entries): ") + hipGetErrorString(e)); }
-        }
-        if (madsim_k_fold_census(cen, W, C.h_ent, nv)) { nothing(); return fail(MADSIM_E_LIMITS, too_many); }
-        if (W[12] && cen->n_runner_listed < cen->runner_cap) {                   // chunks and seeds ascend: the first runner_cap met are the smallest
-            hipError_t e = C.h_res.room((size_t)chunk);
-            if (e == hipSuccess) e = hipMemcpy(C.h_res, S.out, n * sizeof(madsim_result_t), hipMemcpyDeviceToHost);
-            if (e != hipSuccess) { nothing(); return fail(MADSIM_E_HIP, std::string("hipMemcpy(census results): ") + hipGetErrorString(e)); }
-            for (uint64_t i = 0; i < n && cen->n_runner_listed < cen->runner_cap; i++)
-                if (MADSIM_IS_RUNNER_VERDICT(C.h_res.p[i].verdict)) cen->runner_seeds[cen->n_runner_listed++] = list ? seeds[done + i] : seed0 + done + i;
-        }
+    int launch(madsim_hip_ctx_t* c, uint64_t n, uint64_t slots, hipStream_t st) const {
+        const madsim_hip_ctx::TraceSet& S = c->trace[0];
+        auto& C = c->census;
+        return madsim_k_launch_census(S.obs, r->obs_cap, S.len + n, S.out, c->d_seeds, n, r->include, C.tab, slots, C.list, r->cap, C.words, C.ent, st);
     }
-    return 0;
-}
+};
 
-int madsim_hip_ctx_census_range(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total,
-                                uint64_t chunk, const madsim_limits_t* lim, madsim_census_t* cen) {
-    return census_run(c, w, cfg, seed0, nullptr, total, chunk, lim, cen, false);
-}
-
-int madsim_hip_ctx_census_seeds(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n,
-                                uint64_t chunk, const madsim_limits_t* lim, madsim_census_t* cen) {
-    return census_run(c, w, cfg, 0, seeds, n, chunk, lim, cen, true);
-}
-
-// ---- the probe-set census: table size, the host fold of a chunk, and the chunk loop (census_run's sibling) ---------------------------
-extern "C" uint64_t madsim_k_probe_sets_slots(uint64_t cap) {
-    uint64_t slots = MADSIM_K_PROBE_SETS_MIN_SLOTS;
-    while (slots < 2 * cap) slots <<= 1;
-    return slots;
-}
-
-// Declared in sim_kernel.h beside the launcher (not part of the public ABI): the tests feed it entries without a device.  Everything it
-// does commutes, so the order of the chunks and of a chunk's entries never shows; equal sets inside one chunk's entries are combined too.
-extern "C" int madsim_k_fold_probe_sets(madsim_probe_sets_t* ps, const unsigned long long* words, const madsim_probe_set_t* entries, uint64_t n) {
-    auto combine = [](madsim_probe_set_t& a, const madsim_probe_set_t& b) {
+// Which combinations of a vocabulary's values the seeds reach: entries keyed by the set word, one more word per seed on the device.
+struct ProbeSetsForm {
+    typedef madsim_probe_sets_t Report;
+    typedef madsim_probe_set_t Entry;
+    static_assert(sizeof(Entry) == 72 && sizeof(Report) == 112, "record layout");
+    Report* r;
+    static constexpr uint64_t slot_bytes = MADSIM_K_PROBE_SETS_SLOT_BYTES, min_slots = MADSIM_K_PROBE_SETS_MIN_SLOTS, n_words = MADSIM_K_PROBE_SETS_WORDS;
+    static constexpr uint64_t per_seed_bytes = 4 * sizeof(uint64_t) + sizeof(madsim_result_t);      // beside the row: two length words, the seed, the set word, the result
+    static constexpr uint64_t eager = 56;              // entries copied behind a chunk's words, before their number is known (a handful of sets is the usual report): 4 KB
+    static constexpr uint32_t runner_word = 6, err_cap = MADSIM_K_PROBE_SETS_ERR_CAP;
+    static constexpr const char *name = "probe_sets", *noun = "probe-set";
+    static constexpr const char *at_zero = "hipMemsetAsync(probe-set words)", *at_launch = "probe-set kernel launch", *at_words = "hipMemcpyAsync(probe-set words)",
+                                *at_entries = "hipMemcpyAsync(probe-set entries)";
+    static constexpr const char* too_big = "probe_sets: chunk x (8 obs_cap + 80) + 48 slots + 76 cap + 64 exceeds MADSIM_TRACE_MAX_BYTES, or chunk x obs_cap reaches 2^32 - 1: a smaller chunk or smaller caps";
+    static constexpr const char* too_many = "probe_sets: more than `cap` distinct probe sets: raise cap (max_sets), or name fewer values in the vocabulary";
+    static auto& bufs(madsim_hip_ctx_t* c) { return c->probe_sets; }
+    Entry* entries() const { return r->sets; }
+    uint64_t& count() const { return r->n_sets; }
+    static uint64_t key(const Entry& e) { return e.set; }
+    static void combine(Entry& a, const Entry& b) {
         for (int k = 0; k < 4; k++) {
             if (b.n_seeds[k]) a.first_seed[k] = a.n_seeds[k] ? std::min(a.first_seed[k], b.first_seed[k]) : b.first_seed[k];
             a.n_seeds[k] += b.n_seeds[k];
         }
-    };
-    std::vector<madsim_probe_set_t> add(entries, entries + n);
-    std::sort(add.begin(), add.end(), [](const madsim_probe_set_t& a, const madsim_probe_set_t& b) { return a.set < b.set; });
+    }
+    void totals(const unsigned long long* words) const {
+        for (int k = 0; k < 4; k++) r->n_counted[k] += words[2 + k];
+        r->n_runner += words[6];
+    }
+    int check() const {
+        if (!r) return fail(MADSIM_E_ARG, "probe_sets: null report");
+        if (r->include == 0 || (r->include & ~0xfu)) return fail(MADSIM_E_ARG, "probe_sets: include is 0 or names a verdict at or above 4 (only PASS, PANIC, DEADLOCK, TIME_LIMIT are counted)");
+        if (r->cap == 0 || r->cap > MADSIM_PROBE_SETS_MAX || !r->sets) return fail(MADSIM_E_ARG, "probe_sets: cap outside 1 .. MADSIM_PROBE_SETS_MAX, or no set array");
+        if (r->obs_cap == 0 || r->obs_cap > MADSIM_CENSUS_MAX_OBS_CAP) return fail(MADSIM_E_ARG, "probe_sets: obs_cap outside 1 .. MADSIM_CENSUS_MAX_OBS_CAP");
+        if (r->n_vocab == 0 || r->n_vocab > MADSIM_PROBE_SETS_MAX_VOCAB || !r->vocab) return fail(MADSIM_E_ARG, "probe_sets: n_vocab outside 1 .. MADSIM_PROBE_SETS_MAX_VOCAB, or no vocabulary");
+        for (uint64_t i = 1; i < r->n_vocab; i++)
+            for (uint64_t j = 0; j < i; j++)
+                if (r->vocab[i] == r->vocab[j]) return fail(MADSIM_E_ARG, "probe_sets: a value occurs twice in the vocabulary");
+        if (r->runner_cap && !r->runner_seeds) return fail(MADSIM_E_ARG, "probe_sets: runner_cap without runner_seeds");
+        return 0;
+    }
+    void nothing() const {
+        r->n_sets = r->n_runner = r->n_runner_listed = 0;
+        for (int k = 0; k < 4; k++) r->n_counted[k] = 0;
+    }
+    int launch(madsim_hip_ctx_t* c, uint64_t n, uint64_t slots, hipStream_t st) const {
+        const madsim_hip_ctx::TraceSet& S = c->trace[0];
+        auto& P = c->probe_sets;
+        return madsim_k_launch_probe_sets(S.obs, r->obs_cap, S.len + n, S.out, c->d_seeds, n, r->include, r->vocab, r->n_vocab, P.sig, P.tab, slots, P.list,
+                                          r->cap, P.words, P.ent, st);
+    }
+};
+
+uint64_t obs_report_slots(uint64_t cap, uint64_t min_slots) {
+    uint64_t slots = min_slots;
+    while (slots < 2 * cap) slots <<= 1;
+    return slots;
+}
+
+// The host fold of one chunk into the caller's report: the chunk's entries sorted and equal keys combined, then merged into the ascending
+// array — or -1 with the report untouched when that would pass `cap` —, then the totals of `words` (may be null: none) added.  Everything
+// it does commutes, so the order of the chunks and of a chunk's entries never shows.
+template <class Form>
+int fold_chunk(const Form& f, const unsigned long long* words, const typename Form::Entry* entries, uint64_t n) {
+    typedef typename Form::Entry Entry;
+    std::vector<Entry> add(entries, entries + n);
+    std::sort(add.begin(), add.end(), [](const Entry& a, const Entry& b) { return Form::key(a) < Form::key(b); });
     size_t m = 0;
     for (size_t j = 0; j < add.size(); j++) {
-        if (m && add[m - 1].set == add[j].set) combine(add[m - 1], add[j]); else add[m++] = add[j];
+        if (m && Form::key(add[m - 1]) == Form::key(add[j])) Form::combine(add[m - 1], add[j]); else add[m++] = add[j];
     }
-    madsim_probe_set_t* const v = ps->sets;
-    const uint64_t have = ps->n_sets;
+    Entry* const v = f.entries();
+    const uint64_t have = f.count();
     uint64_t fresh = 0;
     for (size_t i = 0, j = 0; j < m; j++) {
-        while (i < have && v[i].set < add[j].set) i++;
-        if (i >= have || v[i].set != add[j].set) fresh++;
+        while (i < have && Form::key(v[i]) < Form::key(add[j])) i++;
+        if (i >= have || Form::key(v[i]) != Form::key(add[j])) fresh++;
     }
-    if (have + fresh > ps->cap) return -1;
+    if (have + fresh > f.r->cap) return -1;
     for (int64_t i = (int64_t)have - 1, j = (int64_t)m - 1, k = (int64_t)(have + fresh) - 1; j >= 0; k--) {      // merged from the back, in place
-        if (i >= 0 && v[i].set > add[j].set) v[k] = v[i--];
-        else if (i >= 0 && v[i].set == add[j].set) { madsim_probe_set_t e = v[i--]; combine(e, add[j--]); v[k] = e; }
+        if (i >= 0 && Form::key(v[i]) > Form::key(add[j])) v[k] = v[i--];
+        else if (i >= 0 && Form::key(v[i]) == Form::key(add[j])) { Entry e = v[i--]; Form::combine(e, add[j--]); v[k] = e; }
         else v[k] = add[j--];
     }
-    ps->n_sets = have + fresh;
-    if (words) {
-        for (int k = 0; k < 4; k++) ps->n_counted[k] += words[2 + k];
-        ps->n_runner += words[6];
-    }
+    f.count() = have + fresh;
+    if (words) f.totals(words);
     return 0;
 }
 
-// The probe sets of [seed0, seed0 + total) (seeds == nullptr) or of seeds[0 .. total): chunk after chunk on one stream, each the trace launch
-// into the context's trace set 0, the three kernels and the copies of the words and of the first PROBE_SETS_EAGER_ENTRIES entries, then one
-// synchronisation; entries beyond those — and, where the caller still wants runner seeds and the chunk has some, its results — follow by
-// copies of their own.  Once a chunk is queued no error returns before its synchronisation (TraceSteps); an error that may have left the
-// table otherwise than zero marks it dirty.
-constexpr uint64_t PROBE_SETS_EAGER_ENTRIES = 56;      // entries copied behind a chunk's words, before their number is known: 4 KB
-
-static int probe_sets_run(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, const uint64_t* seeds,
-                          uint64_t total, uint64_t chunk, const madsim_limits_t* lim, madsim_probe_sets_t* ps, bool list) {
-    static_assert(sizeof(madsim_probe_set_t) == 72 && sizeof(madsim_probe_sets_t) == 112, "record layout");
-    if (!ps) return fail(MADSIM_E_ARG, "probe_sets: null report");
-    if (ps->include == 0 || (ps->include & ~0xfu)) return fail(MADSIM_E_ARG, "probe_sets: include is 0 or names a verdict at or above 4 (only PASS, PANIC, DEADLOCK, TIME_LIMIT are counted)");
-    if (ps->cap == 0 || ps->cap > MADSIM_PROBE_SETS_MAX || !ps->sets) return fail(MADSIM_E_ARG, "probe_sets: cap outside 1 .. MADSIM_PROBE_SETS_MAX, or no set array");
-    if (ps->obs_cap == 0 || ps->obs_cap > MADSIM_CENSUS_MAX_OBS_CAP) return fail(MADSIM_E_ARG, "probe_sets: obs_cap outside 1 .. MADSIM_CENSUS_MAX_OBS_CAP");
-    if (ps->n_vocab == 0 || ps->n_vocab > MADSIM_PROBE_SETS_MAX_VOCAB || !ps->vocab) return fail(MADSIM_E_ARG, "probe_sets: n_vocab outside 1 .. MADSIM_PROBE_SETS_MAX_VOCAB, or no vocabulary");
-    for (uint64_t i = 1; i < ps->n_vocab; i++)
-        for (uint64_t j = 0; j < i; j++)
-            if (ps->vocab[i] == ps->vocab[j]) return fail(MADSIM_E_ARG, "probe_sets: a value occurs twice in the vocabulary");
-    if (ps->runner_cap && !ps->runner_seeds) return fail(MADSIM_E_ARG, "probe_sets: runner_cap without runner_seeds");
-    if (list && total && !seeds) return fail(MADSIM_E_ARG, "probe_sets_seeds: null seed list");
+// The report over [seed0, seed0 + total) (seeds == nullptr) or over seeds[0 .. total): chunk after chunk on one stream, each the trace launch
+// into the context's trace set 0, the form's kernels and the copies of the words and of the first Form::eager entries, then one
+// synchronisation: the chunk of a probe vocabulary is done there.  Entries beyond those — and, where the caller still wants runner seeds and
+// the chunk has some, its results — follow by copies of their own.  Once a chunk is queued no error returns before its synchronisation
+// (TraceSteps); an error that may have left the table otherwise than zero marks it dirty; every failure leaves an empty report.
+template <class Form>
+int obs_report_run(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, const uint64_t* seeds, uint64_t total,
+                   uint64_t chunk, const madsim_limits_t* lim, typename Form::Report* rep, bool list) {
+    typedef typename Form::Entry Entry;
+    const Form f{rep};
+    const std::string name = Form::name, noun = Form::noun;
+    if (int rc = f.check()) return rc;
+    if (list && total && !seeds) return fail(MADSIM_E_ARG, name + "_seeds: null seed list");
     if (list)
         for (uint64_t i = 1; i < total; i++)
-            if (seeds[i] <= seeds[i - 1]) return fail(MADSIM_E_ARG, "probe_sets_seeds: the seed list is not strictly ascending (sort and deduplicate it first)");
-    auto nothing = [ps] {
-        ps->n_sets = ps->n_runner = ps->n_runner_listed = 0;
-        for (int k = 0; k < 4; k++) ps->n_counted[k] = 0;
-    };
-    nothing();
+            if (seeds[i] <= seeds[i - 1]) return fail(MADSIM_E_ARG, name + "_seeds: the seed list is not strictly ascending (sort and deduplicate it first)");
+    f.nothing();
     if (total == 0) return 0;
-    // what a chunk asks of the device: per seed the row, two length words, the seed, the set word and the result; once the table, the list, the entries, the words
-    const uint64_t M = MADSIM_TRACE_MAX_BYTES, obs_cap = ps->obs_cap, cap = ps->cap;
-    const uint64_t fixed = madsim_k_probe_sets_slots(cap) * MADSIM_K_PROBE_SETS_SLOT_BYTES + cap * (sizeof(uint32_t) + sizeof(madsim_probe_set_t)) + MADSIM_K_PROBE_SETS_WORDS * 8;
-    const uint64_t per_seed = 8 * obs_cap + 4 * sizeof(uint64_t) + sizeof(madsim_result_t);
+    // what a chunk asks of the device: per seed the row and the form's words beside it; once the table, the list, the entries, the words
+    const uint64_t M = MADSIM_TRACE_MAX_BYTES, obs_cap = rep->obs_cap, cap = rep->cap, slots = obs_report_slots(cap, Form::min_slots);
+    const uint64_t fixed = slots * Form::slot_bytes + cap * (sizeof(uint32_t) + sizeof(Entry)) + Form::n_words * 8;
+    const uint64_t per_seed = 8 * obs_cap + Form::per_seed_bytes;
     const uint64_t fits = fixed < M ? std::min<uint64_t>((M - fixed) / per_seed, 0xffffffffull / obs_cap - 1) : 0;
     if (chunk == 0) chunk = std::min<uint64_t>(65536, fits);
-    if (chunk == 0 || chunk > fits)
-        return fail(MADSIM_E_LIMITS, "probe_sets: chunk x (8 obs_cap + 80) + 48 slots + 76 cap + 64 exceeds MADSIM_TRACE_MAX_BYTES, or chunk x obs_cap reaches 2^32 - 1: a smaller chunk or smaller caps");
+    if (chunk == 0 || chunk > fits) return fail(MADSIM_E_LIMITS, Form::too_big);
     chunk = std::min(chunk, total);
     int rc = madsim_geo::validate(w, cfg, &g_err);
     if (rc) return rc;
     CTX_ENTER(c);
     hipStream_t st = nullptr;
     madsim_hip_ctx::TraceSet& S = c->trace[0];
-    madsim_hip_ctx::ProbeSets& P = c->probe_sets;
+    auto& B = Form::bufs(c);
+    const auto failed = [&f](int code, const std::string& msg) { f.nothing(); return fail(code, msg); };
     for (uint64_t done = 0; done < total; done += chunk) {
         const uint64_t n = std::min(chunk, total - done);
         Geo G;
-        if ((rc = trace_prepare(c, w, cfg, lim, n, 0, obs_cap, S, G, st))) { nothing(); return rc; }
-        if ((rc = P.ensure(cap, chunk, !list, st))) { nothing(); return rc; }
-        const uint64_t* src = list ? seeds + done : P.h_seeds.p;
-        if (!list) for (uint64_t i = 0; i < n; i++) P.h_seeds.p[i] = seed0 + done + i;
+        if ((rc = trace_prepare(c, w, cfg, lim, n, 0, obs_cap, S, G, st))) { f.nothing(); return rc; }
+        if ((rc = B.ensure(slots, cap, chunk, !list, st))) { f.nothing(); return rc; }
+        const uint64_t* src = list ? seeds + done : B.h_seeds.p;
+        if (!list) for (uint64_t i = 0; i < n; i++) B.h_seeds.p[i] = seed0 + done + i;
         TraceSteps step;
         bool ok = step(hipMemcpyAsync(c->d_seeds, src, n * sizeof(uint64_t), hipMemcpyHostToDevice, st), "hipMemcpyAsync(seeds)");
-        if (ok) ok = step(hipMemsetAsync(P.words, 0, MADSIM_K_PROBE_SETS_WORDS * sizeof(unsigned long long), st), "hipMemsetAsync(probe-set words)");
+        if (ok) ok = step(hipMemsetAsync(B.words, 0, Form::n_words * sizeof(unsigned long long), st), Form::at_zero);
         ok = trace_queue(G, S, n, 0, obs_cap, true, st, step, ok);
         if (ok) {
-            const int refused = madsim_k_launch_probe_sets(S.obs, obs_cap, S.len + n, S.out, c->d_seeds, n, ps->include, ps->vocab, ps->n_vocab, P.sig,
-                                                           P.tab, madsim_k_probe_sets_slots(cap), P.list, cap, P.words, P.ent, st);
+            const int refused = f.launch(c, n, slots, st);
             if (refused) step.no_build = true;
-            ok = step(refused ? hipSuccess : hipGetLastError(), "probe-set kernel launch");
+            ok = step(refused ? hipSuccess : hipGetLastError(), Form::at_launch);
         }
-        if (ok) ok = step(hipMemcpyAsync(P.h_words, P.words, MADSIM_K_PROBE_SETS_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st), "hipMemcpyAsync(probe-set words)");
-        // the first entries ride behind the words (a handful of sets is the usual report); a chunk with more gets the rest in a copy of its own
-        const uint64_t eager = std::min<uint64_t>(cap, PROBE_SETS_EAGER_ENTRIES);
-        if (ok) ok = step(hipMemcpyAsync(P.h_ent, P.ent, eager * sizeof(madsim_probe_set_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync(probe-set entries)");
+        if (ok) ok = step(hipMemcpyAsync(B.h_words, B.words, Form::n_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, st), Form::at_words);
+        // the first entries ride behind the words; a chunk with more gets the rest in a copy of its own
+        const uint64_t eager = std::min<uint64_t>(cap, Form::eager);
+        if (ok) ok = step(hipMemcpyAsync(B.h_ent, B.ent, eager * sizeof(Entry), hipMemcpyDeviceToHost, st), Form::at_entries);
         ok = step(hipStreamSynchronize(st), "hipStreamSynchronize");
-        if (step.err != hipSuccess) { P.dirty = true; nothing(); return fail(MADSIM_E_HIP, std::string(step.at) + ": " + hipGetErrorString(step.err)); }
-        if (step.no_build) { nothing(); return fail(MADSIM_E_LIMITS, "no trace kernel build, or sizes the probe-set kernels refuse"); }
-        const unsigned long long* W = P.h_words;
-        const char* const too_many = "probe_sets: more than `cap` distinct probe sets: raise cap (max_sets), or name fewer values in the vocabulary";
-        if (W[1] & MADSIM_K_PROBE_SETS_ERR_CAP) { nothing(); return fail(MADSIM_E_LIMITS, too_many); }      // (the extract pass has cleared the table)
-        if (W[1]) { P.dirty = true; nothing(); return fail(MADSIM_E_HIP, "probe_sets: the device table was not clean (internal)"); }
+        if (step.err != hipSuccess) { B.dirty = true; return failed(MADSIM_E_HIP, std::string(step.at) + ": " + hipGetErrorString(step.err)); }
+        if (step.no_build) return failed(MADSIM_E_LIMITS, "no trace kernel build, or sizes the " + noun + " kernels refuse");
+        const unsigned long long* W = B.h_words;
+        if (W[1] & Form::err_cap) return failed(MADSIM_E_LIMITS, Form::too_many);      // (the extract pass has cleared the table)
+        if (W[1]) { B.dirty = true; return failed(MADSIM_E_HIP, name + ": the device table was not clean (internal)"); }
         const uint64_t ne = W[0];
         if (ne > eager) {
-            const hipError_t e = hipMemcpy(P.h_ent + eager, P.ent + eager, (ne - eager) * sizeof(madsim_probe_set_t), hipMemcpyDeviceToHost);
-            if (e != hipSuccess) { nothing(); return fail(MADSIM_E_HIP, std::string("hipMemcpy(probe-set entries): ") + hipGetErrorString(e)); }
+            const hipError_t e = hipMemcpy(B.h_ent + eager, B.ent + eager, (ne - eager) * sizeof(Entry), hipMemcpyDeviceToHost);
+            if (e != hipSuccess) return failed(MADSIM_E_HIP, "hipMemcpy(" + noun + " entries): " + hipGetErrorString(e));
         }
-        if (madsim_k_fold_probe_sets(ps, W, P.h_ent, ne)) { nothing(); return fail(MADSIM_E_LIMITS, too_many); }
-        if (W[6] && ps->n_runner_listed < ps->runner_cap) {                      // chunks and seeds ascend: the first runner_cap met are the smallest
-            hipError_t e = P.h_res.room((size_t)chunk);
-            if (e == hipSuccess) e = hipMemcpy(P.h_res, S.out, n * sizeof(madsim_result_t), hipMemcpyDeviceToHost);
-            if (e != hipSuccess) { nothing(); return fail(MADSIM_E_HIP, std::string("hipMemcpy(probe-set results): ") + hipGetErrorString(e)); }
-            for (uint64_t i = 0; i < n && ps->n_runner_listed < ps->runner_cap; i++)
-                if (MADSIM_IS_RUNNER_VERDICT(P.h_res.p[i].verdict)) ps->runner_seeds[ps->n_runner_listed++] = list ? seeds[done + i] : seed0 + done + i;
+        if (fold_chunk(f, W, B.h_ent.p, ne)) return failed(MADSIM_E_LIMITS, Form::too_many);
+        if (W[Form::runner_word] && rep->n_runner_listed < rep->runner_cap) {      // chunks and seeds ascend: the first runner_cap met are the smallest
+            hipError_t e = B.h_res.room((size_t)chunk);
+            if (e == hipSuccess) e = hipMemcpy(B.h_res, S.out, n * sizeof(madsim_result_t), hipMemcpyDeviceToHost);
+            if (e != hipSuccess) return failed(MADSIM_E_HIP, "hipMemcpy(" + noun + " results): " + hipGetErrorString(e));
+            for (uint64_t i = 0; i < n && rep->n_runner_listed < rep->runner_cap; i++)
+                if (MADSIM_IS_RUNNER_VERDICT(B.h_res.p[i].verdict)) rep->runner_seeds[rep->n_runner_listed++] = list ? seeds[done + i] : seed0 + done + i;
         }
     }
     return 0;
 }
+}  // extern "C++"
+}  // namespace
+
+extern "C" uint64_t madsim_k_census_slots(uint64_t cap) { return obs_report_slots(cap, MADSIM_K_CENSUS_MIN_SLOTS); }
+extern "C" uint64_t madsim_k_probe_sets_slots(uint64_t cap) { return obs_report_slots(cap, MADSIM_K_PROBE_SETS_MIN_SLOTS); }
+extern "C" uint64_t madsim_k_census_slot(uint64_t value, uint64_t slots) { return madsim_k::census_slot(value, slots); }
+
+// Declared in sim_kernel.h beside the launchers (not part of the public ABI): the tests feed them entries without a device.
+extern "C" int madsim_k_fold_census(madsim_census_t* cen, const unsigned long long* words, const madsim_census_value_t* entries, uint64_t n) {
+    return fold_chunk(CensusForm{cen}, words, entries, n);
+}
+extern "C" int madsim_k_fold_probe_sets(madsim_probe_sets_t* ps, const unsigned long long* words, const madsim_probe_set_t* entries, uint64_t n) {
+    return fold_chunk(ProbeSetsForm{ps}, words, entries, n);
+}
+
+int madsim_hip_ctx_census_range(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total,
+                                uint64_t chunk, const madsim_limits_t* lim, madsim_census_t* cen) {
+    return obs_report_run<CensusForm>(c, w, cfg, seed0, nullptr, total, chunk, lim, cen, false);
+}
+
+int madsim_hip_ctx_census_seeds(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n,
+                                uint64_t chunk, const madsim_limits_t* lim, madsim_census_t* cen) {
+    return obs_report_run<CensusForm>(c, w, cfg, 0, seeds, n, chunk, lim, cen, true);
+}
 
 int madsim_hip_ctx_probe_sets_range(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total,
                                     uint64_t chunk, const madsim_limits_t* lim, madsim_probe_sets_t* ps) {
-    return probe_sets_run(c, w, cfg, seed0, nullptr, total, chunk, lim, ps, false);
+    return obs_report_run<ProbeSetsForm>(c, w, cfg, seed0, nullptr, total, chunk, lim, ps, false);
 }
 
 int madsim_hip_ctx_probe_sets_seeds(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n,
                                     uint64_t chunk, const madsim_limits_t* lim, madsim_probe_sets_t* ps) {
-    return probe_sets_run(c, w, cfg, 0, seeds, n, chunk, lim, ps, true);
+    return obs_report_run<ProbeSetsForm>(c, w, cfg, 0, seeds, n, chunk, lim, ps, true);
 }
 
 int madsim_hip_ctx_trace_seeds(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n,

@@ -299,6 +299,14 @@ def _resolve_flags(resolve):
     return A.CAMPAIGN_RESOLVE | rounds << A.CAMPAIGN_RESOLVE_ROUNDS_SHIFT
 
 
+def _resolve_rounds(resolve):
+    """`resolve=` of trace_seeds, diverge_seeds, census and probe_sets as a number of rounds: None / False = 0, True = the default, an int = that many."""
+    rounds = 0 if resolve is None or resolve is False else A.RESOLVE_DEFAULT_ROUNDS if resolve is True else int(resolve)
+    if not 0 <= rounds <= A.RESOLVE_MAX_ROUNDS:
+        raise MadsimHipError(f"resolve: None, True or a number of rounds 1..{A.RESOLVE_MAX_ROUNDS}, got {resolve!r}")
+    return rounds
+
+
 def _campaign_flags(stop_at_failure, list_runner=False, stop_at_cap=False, stop_at_groups=False, resolve=None):
     return (A.CAMPAIGN_STOP_AT_FAILURE if stop_at_failure else 0) | (A.CAMPAIGN_LIST_RUNNER if list_runner else 0) \
         | (A.CAMPAIGN_STOP_AT_CAP if stop_at_cap else 0) | (A.CAMPAIGN_STOP_AT_GROUPS if stop_at_groups else 0) | _resolve_flags(resolve)
@@ -347,9 +355,7 @@ def _trace_seeds(call, workload, seeds, config, limits, obs_cap, log_cap, resolv
     res = np.zeros(n, dtype=A.RESULT_DTYPE)
     obs, logs = np.zeros((n, obs_cap), dtype=np.uint64), np.zeros((n, log_cap), dtype=np.uint8)
     obs_len, log_len = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
-    rounds = 0 if resolve is None or resolve is False else A.RESOLVE_DEFAULT_ROUNDS if resolve is True else int(resolve)
-    if not 0 <= rounds <= A.RESOLVE_MAX_ROUNDS:
-        raise MadsimHipError(f"resolve: None, True or a number of rounds 1..{A.RESOLVE_MAX_ROUNDS}, got {resolve!r}")
+    rounds = _resolve_rounds(resolve)
     idx = np.arange(n)
     for r in range(rounds + 1):
         if not len(idx):
@@ -407,9 +413,7 @@ def _diverge_seeds(call, workload, seeds, other, config, other_config, limits, o
     cfg_b = cfg_a if other_config is None else other_config
     lim_a0 = limits or A.Limits()
     lim_b0 = lim_a0 if other_limits is None else other_limits
-    rounds = 0 if resolve is None or resolve is False else A.RESOLVE_DEFAULT_ROUNDS if resolve is True else int(resolve)
-    if not 0 <= rounds <= A.RESOLVE_MAX_ROUNDS:
-        raise MadsimHipError(f"resolve: None, True or a number of rounds 1..{A.RESOLVE_MAX_ROUNDS}, got {resolve!r}")
+    rounds = _resolve_rounds(resolve)
     n = len(seeds)
     recs, ctx = np.zeros(n, dtype=A.DIVERGENCE_DTYPE), np.zeros((n, 3 * window), dtype=np.uint64)
     idx = np.arange(n)
@@ -456,7 +460,44 @@ def diverge_seeds(workload, seeds, other=None, config=None, other_config=None, l
                           window, resolve)
 
 
-class Census:
+class _ObsReport:
+    """What Census and ProbeSets share.  A form names its entry array (`_array`: the attribute here and the field of its C struct `_struct`, of
+    `_entry` records), that struct's count field and the library's host fold of the form."""
+
+    def __len__(self):
+        return len(getattr(self, self._array))
+
+    def _merged(self, other):
+        """(the entries of both reports as one ascending array, equal keys combined by the form's fold; the runner seeds of both, ascending)."""
+        mine, theirs = getattr(self, self._array), getattr(other, self._array)
+        out = np.concatenate([mine, np.zeros(len(theirs), dtype=mine.dtype)])          # room for every entry of both
+        rep = self._struct(include=self.include, obs_cap=self.obs_cap, cap=max(len(out), 1))
+        setattr(rep, self._count, len(mine))
+        setattr(rep, self._array, out.ctypes.data_as(C.POINTER(self._entry)))
+        add = np.ascontiguousarray(theirs)
+        if getattr(lib(), self._fold)(C.byref(rep), None, add.ctypes.data_as(C.c_void_p), len(add)):
+            raise MadsimHipError(f"{type(self).__name__}.merge: {self._fold} failed")
+        runner = np.sort(np.concatenate([np.asarray(self.runner_seeds, dtype=np.uint64), np.asarray(other.runner_seeds, dtype=np.uint64)]))
+        return out[:getattr(rep, self._count)].copy(), runner
+
+
+def _settle(one, workload, lim0, rounds, seed0, total, seeds, cap, over_cap):
+    """One call of a census form — `one(lim, seeds or None, seed0, n)` gives its report — and then, round by round, one list call over the seeds the
+    last one left with a runner verdict, under grown_limits(workload, limits, r), merged in (`over_cap`: the form's error past `cap` entries)."""
+    sa = None if seeds is None else seed_list(seeds)
+    rep = one(lim0, sa, int(seed0), int(total) if sa is None else len(sa))
+    for r in range(1, rounds + 1):
+        if not len(rep.runner_seeds):
+            break
+        more = one(grown_limits(workload, lim0, r), rep.runner_seeds, 0, len(rep.runner_seeds))
+        rep.n_runner, rep.runner_seeds = 0, np.zeros(0, dtype=np.uint64)
+        rep = rep.merge(more)
+        if len(rep) > cap:
+            raise MadsimHipError(over_cap)
+    return rep
+
+
+class Census(_ObsReport):
     """Which traced values the seeds of a census reached, by verdict (runtime.census).  `values`: ndarray[A.CENSUS_VALUE_DTYPE], ascending by
     `value` — per distinct value the counted seeds of each verdict that observed it at least once (`n_seeds[4]`), its occurrences over them
     (`n_total`), the smallest such seed (`first_seed`) and the most occurrences inside one seed (`max_per_seed`).  `n_counted[4]` /
@@ -464,15 +505,13 @@ class Census:
     `obs_cap` observations, whose later values are not in the table; `n_observations`: the sum of every n_total; `n_runner` seeds were left
     with a runner verdict and are counted nowhere, `runner_seeds` (ndarray[uint64], ascending) the ones that were listed.  Everything is an
     exact integer."""
+    _array, _count, _struct, _entry, _fold = "values", "n_values", A.Census, A.CensusValue, "madsim_k_fold_census"
 
     def __init__(self, values, n_counted, n_silent, n_truncated, n_observations, n_runner, runner_seeds, include, obs_cap):
         self.values = values
         self.n_counted, self.n_silent = tuple(int(x) for x in n_counted), tuple(int(x) for x in n_silent)
         self.n_truncated, self.n_observations, self.n_runner = int(n_truncated), int(n_observations), int(n_runner)
         self.runner_seeds, self.include, self.obs_cap = runner_seeds, include, obs_cap
-
-    def __len__(self):
-        return len(self.values)
 
     def __repr__(self):
         return (f"Census({len(self.values)} values over {sum(self.n_counted)} counted seeds, n_counted={self.n_counted}, n_silent={self.n_silent}, "
@@ -509,29 +548,19 @@ class Census:
         """The census of the union of two DISJOINT seed sets taken under the same include mask and obs_cap: exact, in either order."""
         if (self.include, self.obs_cap) != (other.include, other.obs_cap):
             raise MadsimHipError("Census.merge: the two censuses differ in include or obs_cap")
-        out = np.zeros(len(self.values) + len(other.values), dtype=A.CENSUS_VALUE_DTYPE)
-        out[:len(self.values)] = self.values
-        cen = A.Census(include=self.include, obs_cap=self.obs_cap, cap=max(len(out), 1), n_values=len(self.values))
-        cen.values = out.ctypes.data_as(C.POINTER(A.CensusValue))
-        add = np.ascontiguousarray(other.values)
-        if lib().madsim_k_fold_census(C.byref(cen), None, add.ctypes.data_as(C.c_void_p), len(add)):
-            raise MadsimHipError("Census.merge: madsim_k_fold_census failed")
+        values, runner = self._merged(other)
         add4 = lambda a, b: tuple(x + y for x, y in zip(a, b))                      # noqa: E731
-        runner = np.sort(np.concatenate([np.asarray(self.runner_seeds, dtype=np.uint64), np.asarray(other.runner_seeds, dtype=np.uint64)]))
-        return Census(out[:cen.n_values].copy(), add4(self.n_counted, other.n_counted), add4(self.n_silent, other.n_silent),
+        return Census(values, add4(self.n_counted, other.n_counted), add4(self.n_silent, other.n_silent),
                       self.n_truncated + other.n_truncated, self.n_observations + other.n_observations, self.n_runner + other.n_runner, runner,
                       self.include, self.obs_cap)
 
 
 def _census(call_range, call_seeds, workload, seed0, total, seeds, include, obs_cap, max_values, chunk, config, limits, resolve):
     """One census call — `call_range(cfg, seed0, total, chunk, lim, cen)` or `call_seeds(cfg, seeds*, n, chunk, lim, cen)`, a madsim_hip_*census_*
-    entry point with its context and workload bound — and then, round by round, one list call over the seeds the last one left with a
-    runner verdict, under grown_limits(workload, limits, r), merged in: what _trace_seeds does for a list of seeds."""
+    entry point with its context and workload bound — and its runner seeds settled round by round (_settle)."""
     cfg, lim0 = config or A.Config.default(), limits or A.Limits()
     mask = _include_mask(include)
-    rounds = 0 if resolve is None or resolve is False else A.RESOLVE_DEFAULT_ROUNDS if resolve is True else int(resolve)
-    if not 0 <= rounds <= A.RESOLVE_MAX_ROUNDS:
-        raise MadsimHipError(f"resolve: None, True or a number of rounds 1..{A.RESOLVE_MAX_ROUNDS}, got {resolve!r}")
+    rounds = _resolve_rounds(resolve)
 
     def one(lim, sa, s0, n):
         values, runner = np.zeros(max(int(max_values), 1), dtype=A.CENSUS_VALUE_DTYPE), np.zeros(max(n, 1), dtype=np.uint64)
@@ -544,17 +573,8 @@ def _census(call_range, call_seeds, workload, seed0, total, seeds, include, obs_
         return Census(values[:cen.n_values].copy(), cen.n_counted, cen.n_silent, cen.n_truncated, cen.n_observations, cen.n_runner,
                       runner[:cen.n_runner_listed].copy(), mask, obs_cap)
 
-    sa = None if seeds is None else seed_list(seeds)
-    cen = one(lim0, sa, int(seed0), int(total) if sa is None else len(sa))
-    for r in range(1, rounds + 1):
-        if not len(cen.runner_seeds):
-            break
-        more = one(grown_limits(workload, lim0, r), cen.runner_seeds, 0, len(cen.runner_seeds))
-        cen.n_runner, cen.runner_seeds = 0, np.zeros(0, dtype=np.uint64)
-        cen = cen.merge(more)
-        if len(cen.values) > max_values:
-            raise MadsimHipError(f"census: more than max_values = {max_values} distinct observed values once the runner seeds are settled")
-    return cen
+    return _settle(one, workload, lim0, rounds, seed0, total, seeds, max_values,
+                   f"census: more than max_values = {max_values} distinct observed values once the runner seeds are settled")
 
 
 def census(workload, seed0=0, total=0, seeds=None, include=(A.PASS, A.PANIC, A.DEADLOCK, A.TIME_LIMIT), obs_cap=256, max_values=4096, chunk=0,
@@ -573,7 +593,7 @@ def census(workload, seed0=0, total=0, seeds=None, include=(A.PASS, A.PANIC, A.D
                    seed0, total, seeds, include, obs_cap, max_values, chunk, config, limits, resolve)
 
 
-class ProbeSets:
+class ProbeSets(_ObsReport):
     """Which COMBINATIONS of the vocabulary's values the seeds reached, by verdict (runtime.probe_sets).  `vocabulary`: the tuple of distinct
     values, value i owning bit i of a set word; `sets`: ndarray[A.PROBE_SET_DTYPE], ascending by `set` — per distinct set word the counted
     seeds of each verdict with exactly this set (`n_seeds[4]`) and the smallest of them (`first_seed[4]`, 0 where there is none).  Bit 62
@@ -581,6 +601,7 @@ class ProbeSets:
     `obs_cap` values.  `n_counted[4]` are the column sums of n_seeds; `n_runner` seeds were left with a runner verdict and are counted
     nowhere, `runner_seeds` (ndarray[uint64], ascending) the ones that were listed.  The readers take vocabulary VALUES and give Python
     ints and Fractions."""
+    _array, _count, _struct, _entry, _fold = "sets", "n_sets", A.ProbeSets, A.ProbeSet, "madsim_k_fold_probe_sets"
 
     def __init__(self, vocabulary, sets, n_counted, n_runner, runner_seeds, include, obs_cap):
         self.vocabulary = tuple(int(v) for v in vocabulary)
@@ -588,9 +609,6 @@ class ProbeSets:
         self.n_counted, self.n_runner = tuple(int(x) for x in n_counted), int(n_runner)
         self.runner_seeds, self.include, self.obs_cap = runner_seeds, include, obs_cap
         self._bit = {v: i for i, v in enumerate(self.vocabulary)}
-
-    def __len__(self):
-        return len(self.sets)
 
     def __repr__(self):
         return (f"ProbeSets({len(self.sets)} sets of {len(self.vocabulary)} values over {sum(self.n_counted)} counted seeds, "
@@ -696,29 +714,19 @@ class ProbeSets:
         """The report of the union of two DISJOINT seed sets taken under the same vocabulary, include mask and obs_cap: exact, in either order."""
         if (self.vocabulary, self.include, self.obs_cap) != (other.vocabulary, other.include, other.obs_cap):
             raise MadsimHipError("ProbeSets.merge: the two reports differ in vocabulary, include or obs_cap")
-        out = np.zeros(len(self.sets) + len(other.sets), dtype=A.PROBE_SET_DTYPE)
-        out[:len(self.sets)] = self.sets
-        ps = A.ProbeSets(include=self.include, obs_cap=self.obs_cap, cap=max(len(out), 1), n_sets=len(self.sets))
-        ps.sets = out.ctypes.data_as(C.POINTER(A.ProbeSet))
-        add = np.ascontiguousarray(other.sets)
-        if lib().madsim_k_fold_probe_sets(C.byref(ps), None, add.ctypes.data_as(C.c_void_p), len(add)):
-            raise MadsimHipError("ProbeSets.merge: madsim_k_fold_probe_sets failed")
-        runner = np.sort(np.concatenate([np.asarray(self.runner_seeds, dtype=np.uint64), np.asarray(other.runner_seeds, dtype=np.uint64)]))
-        return ProbeSets(self.vocabulary, out[:ps.n_sets].copy(), tuple(x + y for x, y in zip(self.n_counted, other.n_counted)),
-                         self.n_runner + other.n_runner, runner, self.include, self.obs_cap)
+        sets, runner = self._merged(other)
+        return ProbeSets(self.vocabulary, sets, tuple(x + y for x, y in zip(self.n_counted, other.n_counted)), self.n_runner + other.n_runner, runner,
+                         self.include, self.obs_cap)
 
 
 def _probe_sets(call_range, call_seeds, census_call, workload, vocabulary, seed0, total, seeds, include, obs_cap, max_sets, chunk, config, limits,
                 resolve):
     """One probe-set call — `call_range(cfg, seed0, total, chunk, lim, ps)` or `call_seeds(cfg, seeds*, n, chunk, lim, ps)`, a
-    madsim_hip_*probe_sets_* entry point with its context and workload bound — and then, round by round, one list call over the seeds the
-    last one left with a runner verdict, under grown_limits(workload, limits, r), merged in: what _census does.  vocabulary=None: one
-    `census_call` (the same seeds, masks and limits) first, whose values are the vocabulary."""
+    madsim_hip_*probe_sets_* entry point with its context and workload bound — and its runner seeds settled round by round (_settle), as
+    _census does.  vocabulary=None: one `census_call` (the same seeds, masks and limits) first, whose values are the vocabulary."""
     cfg, lim0 = config or A.Config.default(), limits or A.Limits()
     mask = _include_mask(include)
-    rounds = 0 if resolve is None or resolve is False else A.RESOLVE_DEFAULT_ROUNDS if resolve is True else int(resolve)
-    if not 0 <= rounds <= A.RESOLVE_MAX_ROUNDS:
-        raise MadsimHipError(f"resolve: None, True or a number of rounds 1..{A.RESOLVE_MAX_ROUNDS}, got {resolve!r}")
+    rounds = _resolve_rounds(resolve)
     if vocabulary is None:
         cen = census_call(workload, seed0, total, seeds, include, obs_cap, 4096, chunk, config, limits, resolve)
         vocabulary = [int(v) for v in cen.values["value"]]
@@ -741,17 +749,8 @@ def _probe_sets(call_range, call_seeds, census_call, workload, vocabulary, seed0
             _check(call_seeds(C.byref(cfg), _seeds_ptr(sa), n, chunk, C.byref(lim), C.byref(ps)))
         return ProbeSets(vocab, sets[:ps.n_sets].copy(), ps.n_counted, ps.n_runner, runner[:ps.n_runner_listed].copy(), mask, obs_cap)
 
-    sa = None if seeds is None else seed_list(seeds)
-    rep = one(lim0, sa, int(seed0), int(total) if sa is None else len(sa))
-    for r in range(1, rounds + 1):
-        if not len(rep.runner_seeds):
-            break
-        more = one(grown_limits(workload, lim0, r), rep.runner_seeds, 0, len(rep.runner_seeds))
-        rep.n_runner, rep.runner_seeds = 0, np.zeros(0, dtype=np.uint64)
-        rep = rep.merge(more)
-        if len(rep.sets) > max_sets:
-            raise MadsimHipError(f"probe_sets: more than max_sets = {max_sets} distinct probe sets once the runner seeds are settled")
-    return rep
+    return _settle(one, workload, lim0, rounds, seed0, total, seeds, max_sets,
+                   f"probe_sets: more than max_sets = {max_sets} distinct probe sets once the runner seeds are settled")
 
 
 def probe_sets(workload, vocabulary=None, seed0=0, total=0, seeds=None, include=(A.PASS, A.PANIC, A.DEADLOCK, A.TIME_LIMIT), obs_cap=256,
