@@ -205,6 +205,34 @@ pub struct madsim_probe_sets_t {
 
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
+pub struct madsim_probe_order_pair_t {
+    pub a: u32,
+    pub b: u32,
+    pub n_seeds: [u64; 4],
+    pub first_seed: [u64; 4],
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct madsim_probe_order_t {
+    pub include: u32,
+    pub obs_cap: u32,
+    pub vocab: *const u64,
+    pub n_vocab: u64,
+    pub pairs: *const madsim_probe_order_pair_t,
+    pub cap: u64,
+    pub runner_seeds: *const u64,
+    pub runner_cap: u64,
+    pub n_pairs: u64,
+    pub n_counted: [u64; 4],
+    pub n_none: [u64; 4],
+    pub n_truncated: u64,
+    pub n_runner: u64,
+    pub n_runner_listed: u64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
 pub struct madsim_campaign_t {
     pub seeds_run: u64,
     pub batches_run: u64,
@@ -533,6 +561,7 @@ pub const MADSIM_PROBE_SETS_MAX_VOCAB: u32 = 62;
 pub const MADSIM_PROBE_SETS_MAX: u32 = 1048576;
 pub const MADSIM_PROBE_SET_OTHER: u64 = 0x4000000000000000;
 pub const MADSIM_PROBE_SET_TRUNCATED: u64 = 0x8000000000000000;
+pub const MADSIM_PROBE_ORDER_MAX_VOCAB: u32 = 32;
 pub const MADSIM_CAMPAIGN_STOP_AT_FAILURE: u32 = 1;
 pub const MADSIM_CAMPAIGN_LIST_RUNNER: u32 = 2;
 pub const MADSIM_CAMPAIGN_STOP_AT_CAP: u32 = 4;
@@ -601,6 +630,8 @@ extern "C" {
     pub fn madsim_hip_census_seeds(w: *const madsim_workload_t, cfg: *const madsim_config_t, seeds: *const u64, n: u64, chunk: u64, lim: *const madsim_limits_t, cen: *mut madsim_census_t) -> c_int;
     pub fn madsim_hip_probe_sets_range(w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, chunk: u64, lim: *const madsim_limits_t, ps: *mut madsim_probe_sets_t) -> c_int;
     pub fn madsim_hip_probe_sets_seeds(w: *const madsim_workload_t, cfg: *const madsim_config_t, seeds: *const u64, n: u64, chunk: u64, lim: *const madsim_limits_t, ps: *mut madsim_probe_sets_t) -> c_int;
+    pub fn madsim_hip_probe_order_range(w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, chunk: u64, lim: *const madsim_limits_t, po: *mut madsim_probe_order_t) -> c_int;
+    pub fn madsim_hip_probe_order_seeds(w: *const madsim_workload_t, cfg: *const madsim_config_t, seeds: *const u64, n: u64, chunk: u64, lim: *const madsim_limits_t, po: *mut madsim_probe_order_t) -> c_int;
     pub fn madsim_hip_ctx_run_batch(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, count: u64, lim: *const madsim_limits_t, out: *mut madsim_result_t, summary: *mut madsim_summary_t) -> c_int;
     pub fn madsim_hip_ctx_run_batch_auto(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, count: u64, lim: *const madsim_limits_t, out: *mut madsim_result_t, summary: *mut madsim_summary_t, max_rounds: c_int) -> c_int;
     pub fn madsim_hip_ctx_run_batch_device(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, count: u64, lim: *const madsim_limits_t, d_out: *mut c_void, stream: *mut c_void, summary: *mut madsim_summary_t) -> c_int;
@@ -614,6 +645,8 @@ extern "C" {
     pub fn madsim_hip_ctx_census_seeds(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seeds: *const u64, n: u64, chunk: u64, lim: *const madsim_limits_t, cen: *mut madsim_census_t) -> c_int;
     pub fn madsim_hip_ctx_probe_sets_range(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, chunk: u64, lim: *const madsim_limits_t, ps: *mut madsim_probe_sets_t) -> c_int;
     pub fn madsim_hip_ctx_probe_sets_seeds(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seeds: *const u64, n: u64, chunk: u64, lim: *const madsim_limits_t, ps: *mut madsim_probe_sets_t) -> c_int;
+    pub fn madsim_hip_ctx_probe_order_range(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, chunk: u64, lim: *const madsim_limits_t, po: *mut madsim_probe_order_t) -> c_int;
+    pub fn madsim_hip_ctx_probe_order_seeds(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seeds: *const u64, n: u64, chunk: u64, lim: *const madsim_limits_t, po: *mut madsim_probe_order_t) -> c_int;
     pub fn madsim_hip_run_batch_multi(ctxs: *const *mut madsim_hip_ctx_t, n_ctx: c_int, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, count: u64, lim: *const madsim_limits_t, out: *mut madsim_result_t, summary: *mut madsim_summary_t, max_rounds: c_int) -> c_int;
     pub fn madsim_hip_ctx_run_campaign(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, batch: u64, in_flight: u32, flags: u32, lim: *const madsim_limits_t, out: *mut madsim_campaign_t) -> c_int;
     pub fn madsim_hip_run_campaign(w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, batch: u64, in_flight: u32, flags: u32, lim: *const madsim_limits_t, out: *mut madsim_campaign_t) -> c_int;

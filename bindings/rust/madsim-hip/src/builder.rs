@@ -364,6 +364,46 @@ impl ProbeSets {
     }
 }
 
+/// Which vocabulary value the seeds reached first, by verdict (`Builder::probe_order` / `probe_order_seeds`): `vocabulary`; `pairs`, ascending
+/// by (a, b), a and b indices into the vocabulary — a == b: the counted seeds of each verdict that reached the value; a != b: those that
+/// reached both and saw a first — each with the smallest such seed; `totals`, the counts of `madsim_probe_order_t` (its pointers are null
+/// here); `runner_seeds`, the seeds left with a runner verdict, ascending: they are counted nowhere.
+#[derive(Clone, Debug)]
+pub struct ProbeOrder {
+    pub vocabulary: Vec<u64>,
+    pub pairs: Vec<sys::madsim_probe_order_pair_t>,
+    pub totals: sys::madsim_probe_order_t,
+    pub runner_seeds: Vec<u64>,
+}
+
+impl ProbeOrder {
+    /// Counted seeds of the verdicts in `verdicts` (a bit mask, 0xf = all) that reached both values and saw `a` first (a == b: that reached
+    /// `a`); 0 for a value outside the vocabulary.
+    pub fn before(&self, a: u64, b: u64, verdicts: u32) -> u64 {
+        let at = |v: u64| self.vocabulary.iter().position(|x| *x == v);
+        match (at(a), at(b)) {
+            (Some(ia), Some(ib)) => self.pairs.iter().filter(|e| e.a as usize == ia && e.b as usize == ib)
+                .map(|e| (0..4).filter(|k| verdicts >> k & 1 == 1).map(|k| e.n_seeds[k]).sum::<u64>()).sum(),
+            _ => 0,
+        }
+    }
+
+    /// Counted seeds of `verdicts` that reached `a`.
+    pub fn reached(&self, a: u64, verdicts: u32) -> u64 {
+        self.before(a, a, verdicts)
+    }
+
+    /// Counted seeds of `verdicts` that reached both `a` and `b`: two values never share an index, so one of them came first.
+    pub fn both(&self, a: u64, b: u64, verdicts: u32) -> u64 {
+        if a == b { self.reached(a, verdicts) } else { self.before(a, b, verdicts) + self.before(b, a, verdicts) }
+    }
+
+    /// Some counted seed of `verdicts` reached both, and none of them saw `b` first.
+    pub fn always_before(&self, a: u64, b: u64, verdicts: u32) -> bool {
+        a != b && self.both(a, b, verdicts) > 0 && self.before(b, a, verdicts) == 0
+    }
+}
+
 /// The `obs_hash` of a run that traced `values`, in that order: 64-bit FNV-1a over whole values (the offset basis for none).
 pub fn fold_observations(values: &[u64]) -> u64 {
     values.iter().fold(0xCBF2_9CE4_8422_2325u64, |h, v| (h ^ v).wrapping_mul(0x100_0000_01B3))
@@ -795,6 +835,110 @@ impl Builder {
             c.totals.n_runner_listed = more.totals.n_runner_listed;
             c.totals.n_sets = merged.len() as u64;
             c.sets = merged;
+            c.runner_seeds = more.runner_seeds;
+        }
+        Ok(c)
+    }
+
+    /// Which of the values of `vocabulary` (1 .. 32 distinct values) the seeds `self.seed .. self.seed + self.count` reach first, by verdict
+    /// (`madsim_hip_ctx_probe_order_range`): the range run on the trace build and reduced on the device to one entry per non-empty cell.
+    /// `include`, `obs_cap`: as `census`.  With `resolve_runner` set, the seeds a call leaves with a runner verdict are run again in one list
+    /// call per round and merged in.
+    pub fn probe_order(&self, workload: &Workload, vocabulary: &[u64], include: u32, obs_cap: u32) -> Result<ProbeOrder, RunError> {
+        self.probe_order_over(workload, vocabulary, None, include, obs_cap)
+    }
+
+    /// `probe_order` over an explicit, strictly ascending seed list (`madsim_hip_ctx_probe_order_seeds`).
+    pub fn probe_order_seeds(&self, workload: &Workload, vocabulary: &[u64], seeds: &[u64], include: u32, obs_cap: u32) -> Result<ProbeOrder, RunError> {
+        self.probe_order_over(workload, vocabulary, Some(seeds), include, obs_cap)
+    }
+
+    fn probe_order_over(&self, workload: &Workload, vocabulary: &[u64], seeds: Option<&[u64]>, include: u32, obs_cap: u32) -> Result<ProbeOrder, RunError> {
+        let w = workload.raw();
+        let cfg = self.config.raw();
+        let lim0 = self.raw_limits(true);
+        let ctx = contexts()?.0[0];
+        let rounds = if self.resolve_flags & sys::MADSIM_CAMPAIGN_RESOLVE == 0 {
+            0
+        } else {
+            match (self.resolve_flags & sys::MADSIM_CAMPAIGN_RESOLVE_ROUNDS_MASK) >> sys::MADSIM_CAMPAIGN_RESOLVE_ROUNDS_SHIFT {
+                0 => sys::MADSIM_RESOLVE_DEFAULT_ROUNDS,
+                r => r,
+            }
+        };
+        let cap = vocabulary.len() * vocabulary.len();
+        let one = |lim: &sys::madsim_limits_t, list: Option<&[u64]>| -> Result<ProbeOrder, RunError> {
+            let n = list.map_or(self.count, |l| l.len() as u64);
+            let mut pairs: Vec<sys::madsim_probe_order_pair_t> = vec![unsafe { std::mem::zeroed() }; cap.max(1)];
+            let mut runner = vec![0u64; (n as usize).max(1)];
+            let mut po: sys::madsim_probe_order_t = unsafe { std::mem::zeroed() };
+            po.include = include;
+            po.obs_cap = obs_cap;
+            po.vocab = vocabulary.as_ptr();
+            po.n_vocab = vocabulary.len() as u64;
+            po.pairs = pairs.as_mut_ptr() as *const _;                   // (the library writes through both)
+            po.cap = cap as u64;
+            po.runner_seeds = runner.as_mut_ptr() as *const _;
+            po.runner_cap = n;
+            let rc = unsafe {
+                match list {
+                    Some(l) => sys::madsim_hip_ctx_probe_order_seeds(ctx, &w, &cfg, l.as_ptr(), n, 0, lim, &mut po),
+                    None => sys::madsim_hip_ctx_probe_order_range(ctx, &w, &cfg, self.seed, n, 0, lim, &mut po),
+                }
+            };
+            if rc != 0 {
+                return Err(last_error(rc));
+            }
+            pairs.truncate(po.n_pairs as usize);
+            runner.truncate(po.n_runner_listed as usize);
+            po.vocab = std::ptr::null();
+            po.pairs = std::ptr::null();
+            po.runner_seeds = std::ptr::null();
+            Ok(ProbeOrder { vocabulary: vocabulary.to_vec(), pairs, totals: po, runner_seeds: runner })
+        };
+        let key = |e: &sys::madsim_probe_order_pair_t| (e.a as u64) << 32 | e.b as u64;
+        let mut c = one(&lim0, seeds)?;
+        for r in 1..=rounds {
+            if c.runner_seeds.is_empty() {
+                break;
+            }
+            let mut lim = lim0;
+            let rc = unsafe { sys::madsim_hip_grow_limits(&w, &lim0, r, &mut lim) };
+            if rc != 0 {
+                return Err(last_error(rc));
+            }
+            let more = one(&lim, Some(&c.runner_seeds))?;
+            let mut merged = Vec::with_capacity(c.pairs.len() + more.pairs.len());
+            let (mut i, mut j) = (0, 0);
+            while i < c.pairs.len() || j < more.pairs.len() {
+                if j >= more.pairs.len() || (i < c.pairs.len() && key(&c.pairs[i]) < key(&more.pairs[j])) {
+                    merged.push(c.pairs[i]);
+                    i += 1;
+                } else if i >= c.pairs.len() || key(&more.pairs[j]) < key(&c.pairs[i]) {
+                    merged.push(more.pairs[j]);
+                    j += 1;
+                } else {
+                    let (mut e, o) = (c.pairs[i], more.pairs[j]);
+                    for k in 0..4 {
+                        if o.n_seeds[k] > 0 {
+                            e.first_seed[k] = if e.n_seeds[k] > 0 { e.first_seed[k].min(o.first_seed[k]) } else { o.first_seed[k] };
+                        }
+                        e.n_seeds[k] += o.n_seeds[k];
+                    }
+                    merged.push(e);
+                    i += 1;
+                    j += 1;
+                }
+            }
+            for k in 0..4 {
+                c.totals.n_counted[k] += more.totals.n_counted[k];
+                c.totals.n_none[k] += more.totals.n_none[k];
+            }
+            c.totals.n_truncated += more.totals.n_truncated;
+            c.totals.n_runner = more.totals.n_runner;
+            c.totals.n_runner_listed = more.totals.n_runner_listed;
+            c.totals.n_pairs = merged.len() as u64;
+            c.pairs = merged;
             c.runner_seeds = more.runner_seeds;
         }
         Ok(c)

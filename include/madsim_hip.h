@@ -763,6 +763,66 @@ int madsim_hip_probe_sets_range(const madsim_workload_t* w, const madsim_config_
 int madsim_hip_probe_sets_seeds(const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n, uint64_t chunk,
                                 const madsim_limits_t* lim, madsim_probe_sets_t* ps);
 
+/* Probe-order census: WHICH TRACED VALUE COMES FIRST, by verdict — the orders ("the timeout fired before the ack", "pair 1 finished before
+ * pair 0 had started") that neither the census, a table of marginal counts, nor the probe sets, whose set words are symmetric in what they
+ * hold, can answer.  The seeds run on the trace build exactly as for the census (log_cap 0, the caller's obs_cap); per chunk two kernels
+ * behind the trace launch reduce the rows where they lie into a dense matrix of cells, one 72-byte entry per non-empty cell coming back.
+ * No row and no per-seed word travels to the host.  madsim_hip_probe_order_range takes [seed0, seed0 + total),
+ * madsim_hip_probe_order_seeds a STRICTLY ASCENDING list.
+ *
+ * Everything is exact and all-integer, a function of each seed's (result, observation list) alone: the same bytes whatever `chunk`, the
+ * context and the run, and for a dense list the bytes of the range form.  The caller gives a VOCABULARY vocab[0 .. n_vocab) of distinct
+ * 64-bit values, 1 <= n_vocab <= MADSIM_PROBE_ORDER_MAX_VOCAB (every value is legal: 0, 2^64 - 1 and the FNV offset basis included), and
+ * `include` and `obs_cap` with madsim_census_t's meaning and limits.  A seed is COUNTED exactly as in the census (verdict < 4 and its bit
+ * set in `include`).  Of a counted seed with `len` observations the first vis = min(len, obs_cap) are visible; first(i) is the index of
+ * the first occurrence of vocab[i] among them, undefined when vocab[i] does not occur there.  A cell is a pair (a, b) of vocabulary
+ * INDICES:
+ *   the diagonal (a, a):            n_seeds[k] = the counted seeds of verdict k in which first(a) is defined
+ *   off the diagonal (a, b), a != b: n_seeds[k] = the counted seeds of verdict k in which first(a) and first(b) are both defined and
+ *                                   first(a) < first(b)
+ * and first_seed[k] the smallest such seed (0 when n_seeds[k] == 0): the witness to replay.  Only cells with a non-zero count in some
+ * verdict become entries, pairs[0 .. n_pairs) ascending by (a, b).  Two values never share an index, so for a != b the cells (a, b) and
+ * (b, a) add up to the seeds that reached both, and "a without b" is (a, a) - (a, b) - (b, a).
+ * n_counted[k]: the counted seeds of verdict k; n_none[k]: those of them with no vocabulary value visible; n_truncated: counted seeds with
+ * len > obs_cap — they are counted on their visible prefix like every other seed: a first occurrence inside a prefix is the true one.
+ * Seeds with a runner verdict are never counted; they are tallied in n_runner and listed in runner_seeds exactly as the census does it.
+ * `cap`, the room of `pairs`, must be at least n_vocab * n_vocab: there is no "too many" outcome.
+ * The library cuts the seeds into chunks of `chunk` (0 = a default, 65 536 or what fits); the cut is invisible in the result.  One chunk
+ * asks the device for chunk * (8 * obs_cap + 72) bytes — the rows, two length words, the seed and the result of every seed — plus
+ * 32 768 + 76 * n_vocab^2 + 96 for the matrix, the entries and the words: MADSIM_E_LIMITS when that exceeds MADSIM_TRACE_MAX_BYTES or
+ * chunk * obs_cap >= 2^32 - 1 — never split silently.
+ * total == 0 / n == 0 reports the empty result.  MADSIM_E_ARG: po == NULL; include == 0 or a bit at or above 4; obs_cap == 0 or above
+ * MADSIM_CENSUS_MAX_OBS_CAP; n_vocab == 0 or above MADSIM_PROBE_ORDER_MAX_VOCAB; vocab == NULL; a value that occurs twice in vocab;
+ * cap < n_vocab * n_vocab; pairs == NULL; runner_cap > 0 without runner_seeds; seeds == NULL with n > 0; a list that is not strictly
+ * ascending (sort and deduplicate first). */
+#define MADSIM_PROBE_ORDER_MAX_VOCAB 32u
+typedef struct madsim_probe_order_pair { /* 72 bytes */
+    uint32_t a;                        /* vocabulary index of the value that comes first (or, on the diagonal, of the value reached) */
+    uint32_t b;                        /* vocabulary index of the value that comes later; a == b: the diagonal                      */
+    uint64_t n_seeds[4];               /* counted seeds of each verdict in this cell                                              */
+    uint64_t first_seed[4];            /* the smallest such seed of each verdict; 0 where n_seeds is 0                            */
+} madsim_probe_order_pair_t;
+typedef struct madsim_probe_order {
+    uint32_t include;                  /* in: as madsim_census_t.include                                                          */
+    uint32_t obs_cap;                  /* in: as madsim_census_t.obs_cap                                                          */
+    const uint64_t* vocab;             /* in: caller's host array [n_vocab], distinct values                                      */
+    uint64_t n_vocab;                  /* in: 1 .. MADSIM_PROBE_ORDER_MAX_VOCAB                                                   */
+    madsim_probe_order_pair_t* pairs;  /* in: caller's host array [cap]                                                           */
+    uint64_t cap;                      /* in: at least n_vocab * n_vocab                                                          */
+    uint64_t* runner_seeds;            /* in: caller's host array [runner_cap]; may be NULL when runner_cap == 0                  */
+    uint64_t runner_cap;
+    uint64_t n_pairs;                  /* out: entries written, ascending by (a, b)                                               */
+    uint64_t n_counted[4];             /* out: counted seeds per verdict                                                          */
+    uint64_t n_none[4];                /* out: counted seeds per verdict with no vocabulary value visible                         */
+    uint64_t n_truncated;              /* out: counted seeds with more than obs_cap observations                                  */
+    uint64_t n_runner;                 /* out: seeds with a runner verdict                                                        */
+    uint64_t n_runner_listed;          /* out: min(n_runner, runner_cap), the entries of runner_seeds written                     */
+} madsim_probe_order_t;
+int madsim_hip_probe_order_range(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total, uint64_t chunk,
+                                 const madsim_limits_t* lim, madsim_probe_order_t* po);
+int madsim_hip_probe_order_seeds(const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n, uint64_t chunk,
+                                 const madsim_limits_t* lim, madsim_probe_order_t* po);
+
 /* The same entry points on an explicit context (see "Per-device contexts" above). */
 int madsim_hip_ctx_run_batch(madsim_hip_ctx_t* ctx, const madsim_workload_t* w, const madsim_config_t* cfg,
                              uint64_t seed0, uint64_t count, const madsim_limits_t* lim,
@@ -798,6 +858,10 @@ int madsim_hip_ctx_probe_sets_range(madsim_hip_ctx_t* ctx, const madsim_workload
                                     uint64_t total, uint64_t chunk, const madsim_limits_t* lim, madsim_probe_sets_t* ps);
 int madsim_hip_ctx_probe_sets_seeds(madsim_hip_ctx_t* ctx, const madsim_workload_t* w, const madsim_config_t* cfg,
                                     const uint64_t* seeds, uint64_t n, uint64_t chunk, const madsim_limits_t* lim, madsim_probe_sets_t* ps);
+int madsim_hip_ctx_probe_order_range(madsim_hip_ctx_t* ctx, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0,
+                                     uint64_t total, uint64_t chunk, const madsim_limits_t* lim, madsim_probe_order_t* po);
+int madsim_hip_ctx_probe_order_seeds(madsim_hip_ctx_t* ctx, const madsim_workload_t* w, const madsim_config_t* cfg,
+                                     const uint64_t* seeds, uint64_t n, uint64_t chunk, const madsim_limits_t* lim, madsim_probe_order_t* po);
 
 /* One process, several GPUs: the whole seed loop of Builder::run (builder.rs:129-150, every seed driven from one
  * process) over `n_ctx` contexts, each on its own GPU (or, for tests on a 1-GPU box, several on the same one).

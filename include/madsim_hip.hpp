@@ -1083,6 +1083,94 @@ struct Builder {
         return c;
     }
 
+    // Which of the values of `vocabulary` (1 .. 32 distinct values) the builder's seeds reach FIRST, by verdict (madsim_hip_probe_order_range
+    // / madsim_hip_probe_order_seeds): `seed .. seed + count`, or the over_seeds() list, run on the trace build and reduced on the device to
+    // one record per non-empty cell (a, b) of vocabulary indices — a == b: the seeds that reached the value; a != b: those that reached both
+    // and saw a first.  pairs: ascending by (a, b).  This builder's resolve_runner() rounds apply as in census().
+    struct ProbeOrder {
+        std::vector<uint64_t> vocabulary;
+        std::vector<madsim_probe_order_pair_t> pairs;
+        madsim_probe_order_t totals{};             // the counts (the pointers and caps are the call's own: not meaningful here)
+        std::vector<uint64_t> runner_seeds;
+        size_t index(uint64_t value) const {                            // the vocabulary index of a value; throws on any other value
+            auto it = std::find(vocabulary.begin(), vocabulary.end(), value);
+            if (it == vocabulary.end()) throw Error(MADSIM_E_ARG, "probe_order: a value that is not in the vocabulary");
+            return (size_t)(it - vocabulary.begin());
+        }
+        const madsim_probe_order_pair_t* cell(uint64_t a, uint64_t b) const {      // the record of cell (a, b) of VALUES, or nullptr: no seed in it
+            const size_t ia = index(a), ib = index(b);
+            for (const madsim_probe_order_pair_t& e : pairs) if (e.a == ia && e.b == ib) return &e;
+            return nullptr;
+        }
+        // counted seeds of the verdicts in `verdicts` (a bit mask) that reached both and saw `a` first (a == b: that reached a)
+        uint64_t before(uint64_t a, uint64_t b, uint32_t verdicts = 0xf) const {
+            const madsim_probe_order_pair_t* e = cell(a, b);
+            uint64_t n = 0;
+            for (int k = 0; e && k < 4; k++) if ((verdicts >> k) & 1u) n += e->n_seeds[k];
+            return n;
+        }
+        uint64_t reached(uint64_t a, uint32_t verdicts = 0xf) const { return before(a, a, verdicts); }
+        uint64_t both(uint64_t a, uint64_t b, uint32_t verdicts = 0xf) const { return a == b ? reached(a, verdicts) : before(a, b, verdicts) + before(b, a, verdicts); }
+        uint64_t without(uint64_t a, uint64_t b, uint32_t verdicts = 0xf) const { return reached(a, verdicts) - both(a, b, verdicts); }
+        bool always_before(uint64_t a, uint64_t b, uint32_t verdicts = 0xf) const { return a != b && both(a, b, verdicts) > 0 && before(b, a, verdicts) == 0; }
+    };
+    ProbeOrder probe_order(const Workload& wl, const std::vector<uint64_t>& vocabulary, uint32_t obs_cap = 256, uint32_t include = 0xf, uint64_t chunk = 0) const {
+        madsim::check(madsim_hip_init(device));
+        madsim_workload_t w = wl.raw();
+        madsim_config_t cfg = config.raw();
+        madsim_limits_t lim0 = capacities;
+        if (time_limit) { lim0.time_limit_ns = (uint64_t)(*time_limit * 1e9 + 0.5); if (!lim0.time_limit_ns) lim0.time_limit_ns = 1; }
+        uint32_t rounds = 0;
+        if (resolve_flags & MADSIM_CAMPAIGN_RESOLVE) {
+            rounds = (resolve_flags & MADSIM_CAMPAIGN_RESOLVE_ROUNDS_MASK) >> MADSIM_CAMPAIGN_RESOLVE_ROUNDS_SHIFT;
+            if (!rounds) rounds = MADSIM_RESOLVE_DEFAULT_ROUNDS;
+        }
+        const uint64_t cap = vocabulary.size() * vocabulary.size();
+        auto one = [&](const madsim_limits_t& lim, const std::vector<uint64_t>* list) {
+            ProbeOrder c;
+            const uint64_t n = list ? list->size() : count;
+            c.vocabulary = vocabulary;
+            c.pairs.resize(cap ? cap : 1);
+            c.runner_seeds.resize(n ? n : 1);
+            madsim_probe_order_t& t = c.totals;
+            t.include = include; t.obs_cap = obs_cap; t.vocab = vocabulary.data(); t.n_vocab = vocabulary.size(); t.pairs = c.pairs.data(); t.cap = cap;
+            t.runner_seeds = c.runner_seeds.data(); t.runner_cap = n;
+            madsim::check(list ? madsim_hip_probe_order_seeds(&w, &cfg, list->data(), n, chunk, &lim, &t) : madsim_hip_probe_order_range(&w, &cfg, seed, n, chunk, &lim, &t));
+            c.pairs.resize(t.n_pairs);
+            c.runner_seeds.resize(t.n_runner_listed);
+            t.vocab = nullptr; t.pairs = nullptr; t.runner_seeds = nullptr;
+            return c;
+        };
+        ProbeOrder c = one(lim0, listed_seeds ? &seed_list : nullptr);
+        const auto key = [](const madsim_probe_order_pair_t& e) { return (uint64_t)e.a << 32 | e.b; };
+        for (uint32_t r = 1; r <= rounds && !c.runner_seeds.empty(); r++) {
+            madsim_limits_t lim = lim0;
+            madsim::check(madsim_hip_grow_limits(&w, &lim0, r, &lim));
+            const ProbeOrder more = one(lim, &c.runner_seeds);
+            std::vector<madsim_probe_order_pair_t> merged;
+            for (size_t i = 0, j = 0; i < c.pairs.size() || j < more.pairs.size();) {
+                if (j >= more.pairs.size() || (i < c.pairs.size() && key(c.pairs[i]) < key(more.pairs[j]))) merged.push_back(c.pairs[i++]);
+                else if (i >= c.pairs.size() || key(more.pairs[j]) < key(c.pairs[i])) merged.push_back(more.pairs[j++]);
+                else {
+                    madsim_probe_order_pair_t e = c.pairs[i++];
+                    const madsim_probe_order_pair_t& o = more.pairs[j++];
+                    for (int k = 0; k < 4; k++) {
+                        if (o.n_seeds[k]) e.first_seed[k] = e.n_seeds[k] ? std::min(e.first_seed[k], o.first_seed[k]) : o.first_seed[k];
+                        e.n_seeds[k] += o.n_seeds[k];
+                    }
+                    merged.push_back(e);
+                }
+            }
+            c.pairs.swap(merged);
+            for (int k = 0; k < 4; k++) { c.totals.n_counted[k] += more.totals.n_counted[k]; c.totals.n_none[k] += more.totals.n_none[k]; }
+            c.totals.n_truncated += more.totals.n_truncated;
+            c.totals.n_runner = more.totals.n_runner; c.totals.n_runner_listed = more.totals.n_runner_listed;
+            c.totals.n_pairs = c.pairs.size();
+            c.runner_seeds = more.runner_seeds;
+        }
+        return c;
+    }
+
     // Where the two runs part: this builder's run of `wl` (side A) against `other`'s run of `other_wl` (side B) over `seeds` (any order,
     // duplicates allowed), compared on the device on the determinism log and on the observations (madsim_hip_diverge_seeds): per seed the
     // record, the up to `window` observations both runs made just before they part, and the up to `window` each side made from there on.

@@ -337,6 +337,31 @@ assert C.sizeof(ProbeSet) == 72 and C.sizeof(ProbeSets) == 112
 HEADER_STRUCTS["madsim_probe_set_t"] = ProbeSet
 HEADER_STRUCTS["madsim_probe_sets_t"] = ProbeSets
 
+# madsim_hip_probe_order_range / _seeds: the most vocabulary values (the device's matrix is 32 x 32 cells per verdict)
+PROBE_ORDER_MAX_VOCAB = 32
+
+
+class ProbeOrderPair(C.Structure):
+    """madsim_probe_order_pair_t: one cell (a, b) of vocabulary indices — a == b: the counted seeds of each verdict that reached value a;
+    a != b: those in which a's first occurrence comes before b's — and the smallest such seed of each verdict."""
+    _fields_ = [("a", C.c_uint32), ("b", C.c_uint32), ("n_seeds", C.c_uint64 * 4), ("first_seed", C.c_uint64 * 4)]
+
+
+class ProbeOrder(C.Structure):
+    """madsim_probe_order_t: which verdicts count, how many observations of a seed are visible, the vocabulary and the caller's two arrays
+    going in; the number of entries and the totals coming out."""
+    _fields_ = [("include", C.c_uint32), ("obs_cap", C.c_uint32), ("vocab", C.POINTER(C.c_uint64)), ("n_vocab", C.c_uint64),
+                ("pairs", C.POINTER(ProbeOrderPair)), ("cap", C.c_uint64), ("runner_seeds", C.POINTER(C.c_uint64)), ("runner_cap", C.c_uint64),
+                ("n_pairs", C.c_uint64), ("n_counted", C.c_uint64 * 4), ("n_none", C.c_uint64 * 4), ("n_truncated", C.c_uint64),
+                ("n_runner", C.c_uint64), ("n_runner_listed", C.c_uint64)]
+
+
+# numpy view of a probe-order table: madsim_probe_order_pair_t
+PROBE_ORDER_PAIR_DTYPE = [("a", "<u4"), ("b", "<u4"), ("n_seeds", "<u8", (4,)), ("first_seed", "<u8", (4,))]
+assert C.sizeof(ProbeOrderPair) == 72 and C.sizeof(ProbeOrder) == 152
+HEADER_STRUCTS["madsim_probe_order_pair_t"] = ProbeOrderPair
+HEADER_STRUCTS["madsim_probe_order_t"] = ProbeOrder
+
 
 class Geometry(C.Structure):
     _fields_ = [

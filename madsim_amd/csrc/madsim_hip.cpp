@@ -230,7 +230,7 @@ struct madsim_hip_resources {
     struct TraceSet { DevBuf<uint8_t> log; DevBuf<uint64_t> obs, len; DevBuf<madsim_result_t> out; };
     TraceSet trace[2];
     DevBuf<madsim_divergence_t> d_drec; DevBuf<uint64_t> d_dctx;      // divergence reports: the records and the context rows
-    // One census form's buffers (the observation census, the probe-set census: each its own, the slots differ in size): the table (all zero
+    // One census form's buffers (the observation census, the probe-set census, the probe-order census: each its own, the slots differ in size): the table (all zero
     // between chunks; `dirty` when it is new or an error may have left it otherwise), the claim list, the words and the chunk's entries
     // (device); page-locked: the words, the entries, the range form's seed slice and — only for a chunk with runner verdicts whose seeds the
     // caller still wants — the chunk's results.
@@ -265,6 +265,8 @@ struct madsim_hip_resources {
             return ObsReport::ensure(slots, cap, chunk, range, s);
         }
     } probe_sets;
+    // the probe-order census: the dense matrix of cells takes the table's place (1024 cells of 32 bytes); the claim list is not used
+    ObsReport<madsim_probe_order_pair_t, 32, MADSIM_K_PROBE_ORDER_WORDS> probe_order;
     Event ev0, ev1;
     Event pipe_begin;                         // run_pipelined: before the first sub-batch of a call
     Event tev[2 * 64];                        // timing slots of madsim_hip_run_batch_async
@@ -1097,8 +1099,8 @@ int madsim_hip_ctx_diverge_seeds(madsim_hip_ctx_t* c, const madsim_workload_t* w
     return 0;
 }
 
-// ---- the observation census and the probe-set census: table size, probe start, the host fold of a chunk, and the chunk loop ----------
-// One of each for both.  A form says what is its own: the report and its entries (key, combine, the totals a chunk's words add), its
+// ---- the observation census, the probe-set census and the probe-order census: table size, probe start, the host fold of a chunk, and the chunk loop ----
+// One of each for all three.  A form says what is its own: the report and its entries (key, combine, the totals a chunk's words add), its
 // argument checks and what an empty report is, the sizes, its kernels' launch, the word that counts runner verdicts and its messages.
 namespace {
 extern "C++" {
@@ -1112,6 +1114,8 @@ struct CensusForm {
     static constexpr uint64_t per_seed_bytes = 3 * sizeof(uint64_t) + sizeof(madsim_result_t);      // beside the row: two length words, the seed, the result
     static constexpr uint64_t eager = 64;              // entries copied behind a chunk's words, before their number is known (a probe vocabulary is small: 4 KB)
     static constexpr uint32_t runner_word = 12, err_cap = MADSIM_K_CENSUS_ERR_CAP;
+    static constexpr uint64_t fixed_slots = 0;         // the table grows with the caller's cap
+    uint64_t dev_cap() const { return r->cap; }        // entries a chunk may write on the device
     static constexpr const char *name = "census", *noun = "census";
     static constexpr const char *at_zero = "hipMemsetAsync(census words)", *at_launch = "census kernel launch", *at_words = "hipMemcpyAsync(census words)",
                                 *at_entries = "hipMemcpyAsync(census entries)";
@@ -1160,6 +1164,8 @@ struct ProbeSetsForm {
     static constexpr uint64_t per_seed_bytes = 4 * sizeof(uint64_t) + sizeof(madsim_result_t);      // beside the row: two length words, the seed, the set word, the result
     static constexpr uint64_t eager = 56;              // entries copied behind a chunk's words, before their number is known (a handful of sets is the usual report): 4 KB
     static constexpr uint32_t runner_word = 6, err_cap = MADSIM_K_PROBE_SETS_ERR_CAP;
+    static constexpr uint64_t fixed_slots = 0;
+    uint64_t dev_cap() const { return r->cap; }
     static constexpr const char *name = "probe_sets", *noun = "probe-set";
     static constexpr const char *at_zero = "hipMemsetAsync(probe-set words)", *at_launch = "probe-set kernel launch", *at_words = "hipMemcpyAsync(probe-set words)",
                                 *at_entries = "hipMemcpyAsync(probe-set entries)";
@@ -1169,12 +1175,14 @@ struct ProbeSetsForm {
     Entry* entries() const { return r->sets; }
     uint64_t& count() const { return r->n_sets; }
     static uint64_t key(const Entry& e) { return e.set; }
-    static void combine(Entry& a, const Entry& b) {
+    template <class E>
+    static void combine_seeds(E& a, const E& b) {      // per verdict: counts added, the smaller first_seed of the sides that have one
         for (int k = 0; k < 4; k++) {
             if (b.n_seeds[k]) a.first_seed[k] = a.n_seeds[k] ? std::min(a.first_seed[k], b.first_seed[k]) : b.first_seed[k];
             a.n_seeds[k] += b.n_seeds[k];
         }
     }
+    static void combine(Entry& a, const Entry& b) { combine_seeds(a, b); }
     void totals(const unsigned long long* words) const {
         for (int k = 0; k < 4; k++) r->n_counted[k] += words[2 + k];
         r->n_runner += words[6];
@@ -1200,6 +1208,56 @@ struct ProbeSetsForm {
         auto& P = c->probe_sets;
         return madsim_k_launch_probe_sets(S.obs, r->obs_cap, S.len + n, S.out, c->d_seeds, n, r->include, r->vocab, r->n_vocab, P.sig, P.tab, slots, P.list,
                                           r->cap, P.words, P.ent, st);
+    }
+};
+
+// Which vocabulary value comes first: entries keyed by the cell (a, b); a dense matrix of 32 x 32 cells in the table's place, so the
+// device's entries number n_vocab^2 at most whatever the caller's cap, and there is no "too many".
+struct ProbeOrderForm {
+    typedef madsim_probe_order_t Report;
+    typedef madsim_probe_order_pair_t Entry;
+    static_assert(sizeof(Entry) == 72 && sizeof(Report) == 152, "record layout");
+    Report* r;
+    static constexpr uint64_t slot_bytes = 32, min_slots = 1024, fixed_slots = 1024, n_words = MADSIM_K_PROBE_ORDER_WORDS;      // a cell: four counts, four witnesses
+    static_assert(slot_bytes * fixed_slots == 4 * MADSIM_K_PROBE_ORDER_MATRIX_WORDS, "the matrix");
+    static constexpr uint64_t per_seed_bytes = 3 * sizeof(uint64_t) + sizeof(madsim_result_t);      // beside the row: two length words, the seed, the result
+    static constexpr uint64_t eager = 56;              // entries copied behind a chunk's words, before their number is known (seven values' full matrix): 4 KB
+    static constexpr uint32_t runner_word = 11, err_cap = 0;       // (no cap outcome on the device)
+    static constexpr const char *name = "probe_order", *noun = "probe-order";
+    static constexpr const char *at_zero = "hipMemsetAsync(probe-order words)", *at_launch = "probe-order kernel launch", *at_words = "hipMemcpyAsync(probe-order words)",
+                                *at_entries = "hipMemcpyAsync(probe-order entries)";
+    static constexpr const char* too_big = "probe_order: chunk x (8 obs_cap + 72) + 32768 + 76 n_vocab^2 + 96 exceeds MADSIM_TRACE_MAX_BYTES, or chunk x obs_cap reaches 2^32 - 1: a smaller chunk or a smaller obs_cap";
+    static constexpr const char* too_many = "probe_order: more cells than n_vocab^2 (internal)";
+    static auto& bufs(madsim_hip_ctx_t* c) { return c->probe_order; }
+    Entry* entries() const { return r->pairs; }
+    uint64_t& count() const { return r->n_pairs; }
+    uint64_t dev_cap() const { return r->n_vocab * r->n_vocab; }
+    static uint64_t key(const Entry& e) { return (uint64_t)e.a << 32 | e.b; }
+    static void combine(Entry& a, const Entry& b) { ProbeSetsForm::combine_seeds(a, b); }
+    void totals(const unsigned long long* words) const {
+        for (int k = 0; k < 4; k++) { r->n_counted[k] += words[2 + k]; r->n_none[k] += words[6 + k]; }
+        r->n_truncated += words[10]; r->n_runner += words[11];
+    }
+    int check() const {
+        if (!r) return fail(MADSIM_E_ARG, "probe_order: null report");
+        if (r->include == 0 || (r->include & ~0xfu)) return fail(MADSIM_E_ARG, "probe_order: include is 0 or names a verdict at or above 4 (only PASS, PANIC, DEADLOCK, TIME_LIMIT are counted)");
+        if (r->obs_cap == 0 || r->obs_cap > MADSIM_CENSUS_MAX_OBS_CAP) return fail(MADSIM_E_ARG, "probe_order: obs_cap outside 1 .. MADSIM_CENSUS_MAX_OBS_CAP");
+        if (r->n_vocab == 0 || r->n_vocab > MADSIM_PROBE_ORDER_MAX_VOCAB || !r->vocab) return fail(MADSIM_E_ARG, "probe_order: n_vocab outside 1 .. MADSIM_PROBE_ORDER_MAX_VOCAB, or no vocabulary");
+        for (uint64_t i = 1; i < r->n_vocab; i++)
+            for (uint64_t j = 0; j < i; j++)
+                if (r->vocab[i] == r->vocab[j]) return fail(MADSIM_E_ARG, "probe_order: a value occurs twice in the vocabulary");
+        if (r->cap < r->n_vocab * r->n_vocab || !r->pairs) return fail(MADSIM_E_ARG, "probe_order: cap below n_vocab x n_vocab, or no pair array");
+        if (r->runner_cap && !r->runner_seeds) return fail(MADSIM_E_ARG, "probe_order: runner_cap without runner_seeds");
+        return 0;
+    }
+    void nothing() const {
+        r->n_pairs = r->n_truncated = r->n_runner = r->n_runner_listed = 0;
+        for (int k = 0; k < 4; k++) r->n_counted[k] = r->n_none[k] = 0;
+    }
+    int launch(madsim_hip_ctx_t* c, uint64_t n, uint64_t, hipStream_t st) const {
+        const madsim_hip_ctx::TraceSet& S = c->trace[0];
+        auto& P = c->probe_order;
+        return madsim_k_launch_probe_order(S.obs, r->obs_cap, S.len + n, S.out, c->d_seeds, n, r->include, r->vocab, r->n_vocab, P.tab, P.words, P.ent, st);
     }
 };
 
@@ -1258,7 +1316,9 @@ int obs_report_run(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim
     f.nothing();
     if (total == 0) return 0;
     // what a chunk asks of the device: per seed the row and the form's words beside it; once the table, the list, the entries, the words
-    const uint64_t M = MADSIM_TRACE_MAX_BYTES, obs_cap = rep->obs_cap, cap = rep->cap, slots = obs_report_slots(cap, Form::min_slots);
+    // (cap: the entries a chunk may write on the device — the caller's cap, or for the dense matrix its cells)
+    const uint64_t M = MADSIM_TRACE_MAX_BYTES, obs_cap = rep->obs_cap, cap = f.dev_cap();
+    const uint64_t slots = Form::fixed_slots ? Form::fixed_slots : obs_report_slots(cap, Form::min_slots);
     const uint64_t fixed = slots * Form::slot_bytes + cap * (sizeof(uint32_t) + sizeof(Entry)) + Form::n_words * 8;
     const uint64_t per_seed = 8 * obs_cap + Form::per_seed_bytes;
     const uint64_t fits = fixed < M ? std::min<uint64_t>((M - fixed) / per_seed, 0xffffffffull / obs_cap - 1) : 0;
@@ -1328,6 +1388,9 @@ extern "C" int madsim_k_fold_census(madsim_census_t* cen, const unsigned long lo
 extern "C" int madsim_k_fold_probe_sets(madsim_probe_sets_t* ps, const unsigned long long* words, const madsim_probe_set_t* entries, uint64_t n) {
     return fold_chunk(ProbeSetsForm{ps}, words, entries, n);
 }
+extern "C" int madsim_k_fold_probe_order(madsim_probe_order_t* po, const unsigned long long* words, const madsim_probe_order_pair_t* entries, uint64_t n) {
+    return fold_chunk(ProbeOrderForm{po}, words, entries, n);
+}
 
 int madsim_hip_ctx_census_range(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total,
                                 uint64_t chunk, const madsim_limits_t* lim, madsim_census_t* cen) {
@@ -1347,6 +1410,16 @@ int madsim_hip_ctx_probe_sets_range(madsim_hip_ctx_t* c, const madsim_workload_t
 int madsim_hip_ctx_probe_sets_seeds(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n,
                                     uint64_t chunk, const madsim_limits_t* lim, madsim_probe_sets_t* ps) {
     return obs_report_run<ProbeSetsForm>(c, w, cfg, 0, seeds, n, chunk, lim, ps, true);
+}
+
+int madsim_hip_ctx_probe_order_range(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total,
+                                     uint64_t chunk, const madsim_limits_t* lim, madsim_probe_order_t* po) {
+    return obs_report_run<ProbeOrderForm>(c, w, cfg, seed0, nullptr, total, chunk, lim, po, false);
+}
+
+int madsim_hip_ctx_probe_order_seeds(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n,
+                                     uint64_t chunk, const madsim_limits_t* lim, madsim_probe_order_t* po) {
+    return obs_report_run<ProbeOrderForm>(c, w, cfg, 0, seeds, n, chunk, lim, po, true);
 }
 
 int madsim_hip_ctx_trace_seeds(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n,
@@ -2564,6 +2637,18 @@ int madsim_hip_probe_sets_seeds(const madsim_workload_t* w, const madsim_config_
                                 const madsim_limits_t* lim, madsim_probe_sets_t* ps) {
     DefaultPin p;
     return madsim_hip_ctx_probe_sets_seeds(p.c, w, cfg, seeds, n, chunk, lim, ps);
+}
+
+int madsim_hip_probe_order_range(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total, uint64_t chunk,
+                                 const madsim_limits_t* lim, madsim_probe_order_t* po) {
+    DefaultPin p;
+    return madsim_hip_ctx_probe_order_range(p.c, w, cfg, seed0, total, chunk, lim, po);
+}
+
+int madsim_hip_probe_order_seeds(const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n, uint64_t chunk,
+                                 const madsim_limits_t* lim, madsim_probe_order_t* po) {
+    DefaultPin p;
+    return madsim_hip_ctx_probe_order_seeds(p.c, w, cfg, seeds, n, chunk, lim, po);
 }
 
 int madsim_hip_run_campaign(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total, uint64_t batch,

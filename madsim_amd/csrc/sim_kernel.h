@@ -520,6 +520,34 @@ uint64_t madsim_k_probe_sets_slots(uint64_t cap);
 // the totals, and the chunk's `n` entries (any order) merged into ps->sets[0 .. n_sets), which stay ascending by set — counts added,
 // per verdict the smaller first_seed of the sides that have one.  Returns 0, or -1 with `ps` untouched when the table would pass ps->cap.
 int  madsim_k_fold_probe_sets(madsim_probe_sets_t* ps, const unsigned long long* words, const madsim_probe_set_t* entries, uint64_t n);
+// the probe-order census (madsim_hip_probe_order_range / _seeds), behind the chunk's trace launch on the same stream: two kernels over the
+// observation rows of `n` seeds (`obs_cap` words each), their TRUE lengths, the results and the seeds.  order_fold_kernel finds first(j)
+// (include/madsim_hip.h) of every COUNTED row against vocab[0 .. n_vocab), HOST memory here: the values travel in the kernel arguments —
+// other rows are not read — and adds the row's relation to `matrix`: MADSIM_K_PROBE_ORDER_MATRIX_WORDS 32-bit words, ALL ZERO before the
+// launch and all zero again after it, whatever happened — counts [verdict][a][b] (4 x 32 x 32), then as many witnesses, the largest
+// inverted row index of the cell.  `words`: MADSIM_K_PROBE_ORDER_WORDS words, zero before the launch: {entries written, error word,
+// n_counted[4], n_none[4], n_truncated, n_runner}; `entries`: room for n_vocab * n_vocab madsim_probe_order_pair_t, the first words[0]
+// written by order_extract_kernel, ascending by (a, b), with first_seed read from d_seeds.  A witness that is no row of the chunk, or a
+// non-zero cell outside the vocabulary, sets MADSIM_K_PROBE_ORDER_ERR_TAG in the error word (a matrix that was not clean); the entry is
+// then all zero.  Returns 0, or -1 without launching anything for n == 0, n > 2^31, n * obs_cap >= 2^32 - 1, obs_cap outside
+// 1 .. MADSIM_CENSUS_MAX_OBS_CAP, n_vocab outside 1 .. MADSIM_PROBE_ORDER_MAX_VOCAB, an include mask that is 0 or has a bit at or above
+// 4, or a missing or misaligned array.
+#define MADSIM_K_PROBE_ORDER_WORDS 12u          /* 64-bit words of a chunk's report                                */
+#define MADSIM_K_PROBE_ORDER_MATRIX_WORDS 8192u /* 32-bit words: 4 x 32 x 32 counts, 4 x 32 x 32 witnesses: 32 KB   */
+#define MADSIM_K_PROBE_ORDER_WAVES 1024u        /* = MADSIM_K_CENSUS_WAVES: 256 workgroups of four waves            */
+#define MADSIM_K_PROBE_ORDER_ERR_TAG 2u         /* a cell no seed of the chunk can have written: the matrix was not clean */
+int  madsim_k_launch_probe_order(const uint64_t* obs, uint64_t obs_cap, const uint64_t* obs_len, const madsim_result_t* res, const uint64_t* d_seeds,
+                                 uint64_t n, uint32_t include, const uint64_t* vocab, uint64_t n_vocab, uint32_t* matrix, unsigned long long* words,
+                                 madsim_probe_order_pair_t* entries, void* stream);
+// ... with the fold kernel's form named: direct != 0 = every update goes straight to the global matrix, no workgroup accumulator in LDS:
+// the correctness baseline and the other side of the A/B (tools/order_ab.py); the same bytes either way
+int  madsim_k_launch_probe_order_form(const uint64_t* obs, uint64_t obs_cap, const uint64_t* obs_len, const madsim_result_t* res,
+                                      const uint64_t* d_seeds, uint64_t n, uint32_t include, const uint64_t* vocab, uint64_t n_vocab, uint32_t* matrix,
+                                      unsigned long long* words, madsim_probe_order_pair_t* entries, void* stream, int direct);
+// the host fold of one chunk into the caller's report (madsim_hip.cpp; no device involved): `words` (may be null: no totals) are added to
+// the totals, and the chunk's `n` entries (any order) merged into po->pairs[0 .. n_pairs), which stay ascending by (a, b) — counts added,
+// per verdict the smaller first_seed of the sides that have one.  Returns 0, or -1 with `po` untouched when the table would pass po->cap.
+int  madsim_k_fold_probe_order(madsim_probe_order_t* po, const unsigned long long* words, const madsim_probe_order_pair_t* entries, uint64_t n);
 int  madsim_k_set_max_lds(uint32_t lds_bytes);
 int  madsim_k_variant_vgprs(const madsim_k::VariantSel* v);
 void madsim_k_launch_keyflip(unsigned long long* acc, void* stream);

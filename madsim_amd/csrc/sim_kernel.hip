@@ -1484,6 +1484,116 @@ __global__ __launch_bounds__(256) void sets_extract_kernel(const unsigned long l
     }
 }
 
+// ---- the probe-order census: which vocabulary value a chunk's counted seeds reach FIRST, cell (a, b) = "a before b", per verdict -----------
+// Two kernels behind the chunk's trace launch.  order_fold_kernel: one wave per row, striding as sets_mask_kernel does, the row index,
+// the verdict, the length and the loop bounds in scalar registers; rows of uncounted and runner seeds are not read.  The visible
+// observations are walked in rounds of 64, one coalesced 8-byte load per lane; per vocabulary entry j not yet placed one wave-wide compare
+// against a scalar operand from the kernel-argument struct (256 bytes) and a ballot; lane j keeps first(j), set ONCE from the lowest bit of
+// the first non-empty ballot (64 * round + ctz) and never moved by a later occurrence: a placed entry is not compared again.  The walk
+// ends once every entry is placed.  Then the row's relation: for each placed i (a scalar walk over the placed mask, first(i) read from
+// lane i into a scalar register) the lanes j with j == i, or first(j) defined and first(i) < first(j), add 1 to cell [verdict][i][j] and
+// max the inverted row index into its witness (inverted, so that zero is neutral, as sets_insert does): consecutive lanes, consecutive
+// words — one conflict-free add and one max per present i.  LDS_ACC: the cells are a workgroup accumulator in LDS (32 KB: four waves'
+// rows meet there, and every row the workgroup strides over), updated with LDS atomics and flushed once, the non-zero cells only, into
+// the global matrix with atomicAdd / atomicMax: integer add and max commute, so no arrival order shows.  LDS_ACC = false sends the same
+// updates straight to the global matrix: the correctness baseline and the other side of the A/B.  The count words ride in lanes 0 .. 9
+// and are added once per wave, as in sets_fold_kernel.
+// order_extract_kernel: one workgroup of 1024 threads, thread t owning cell (t >> 5, t & 31).  The non-zero cells are placed by a ballot
+// per wave and a prefix sum over the sixteen wave counts — no atomic decides a position —, so the entries leave ascending by (a, b);
+// first_seed[k] = seeds[~witness]; every cell is written back to zero.
+struct OrderVocab { unsigned long long v[MADSIM_PROBE_ORDER_MAX_VOCAB]; };
+constexpr uint32_t ORDER_ENTRIES = 0, ORDER_ERR = 1, ORDER_COUNTS = 2, ORDER_CELLS = 4u * 32u * 32u, ORDER_UNDEF = 0xffffffffu;
+static_assert(2 * ORDER_CELLS == MADSIM_K_PROBE_ORDER_MATRIX_WORDS && MADSIM_PROBE_ORDER_MAX_VOCAB == 32, "the matrix");
+
+template <bool LDS_ACC>
+__global__ __launch_bounds__(256) void order_fold_kernel(const unsigned long long* __restrict__ obs, uint32_t obs_cap,
+                                                         const unsigned long long* __restrict__ obs_len, const madsim_result_t* __restrict__ res,
+                                                         uint32_t n, uint32_t include, const OrderVocab vocab, uint32_t m,
+                                                         uint32_t* __restrict__ matrix, unsigned long long* __restrict__ words) {
+    __shared__ uint32_t acc_lds[LDS_ACC ? 2 * ORDER_CELLS : 1];
+    const uint32_t lane = threadIdx.x & 63, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (LDS_ACC) {
+        for (uint32_t c = threadIdx.x; c < 2 * ORDER_CELLS; c += 256u) acc_lds[c] = 0u;
+        __syncthreads();
+    }
+    uint32_t* const cells = LDS_ACC ? acc_lds : matrix;
+    const uint32_t full = 0xffffffffu >> (32u - m);                                // (1 <= m <= 32)
+    uint32_t acc = 0;                                                              // lane k < 4: counted seeds of verdict k; 4 + k: of them none visible; 8: truncated; 9: runner
+    for (uint32_t i = blockIdx.x * 4u + wave; i < n; i += gridDim.x * 4u) {        // (scalar)
+        const uint32_t v = reinterpret_cast<const uint32_t*>(res + i)[0];
+        if (v >= 4u) { acc += lane == 9u; continue; }
+        if (!((include >> v) & 1u)) continue;                                      // a left-out verdict: the row is not read
+        const unsigned long long len = obs_len[i];
+        const uint32_t vis = len < obs_cap ? (uint32_t)len : obs_cap;
+        const unsigned long long* const row = obs + (size_t)i * obs_cap;
+        uint32_t first = ORDER_UNDEF, placed = 0;                                  // lane j: first(j); (scalar) the entries placed so far
+        for (uint32_t k = 0; k * 64u < vis && placed != full; k++) {
+            const uint32_t idx = k * 64u + lane;
+            const bool have = idx < vis;
+            const unsigned long long val = have ? row[idx] : 0ull;
+            const unsigned long long valid = __ballot(have);
+            for (uint32_t j = 0; j < m; j++) {
+                if ((placed >> j) & 1u) continue;                                  // (scalar) placed once, never moved
+                const unsigned long long b = __ballot(val == vocab.v[j]) & valid;
+                if (b) {
+                    if (lane == j) first = k * 64u + (uint32_t)__ffsll((long long)b) - 1u;
+                    placed |= 1u << j;
+                }
+            }
+        }
+        acc += (lane == v) + (lane == 4u + v && !placed) + (lane == 8u && len > obs_cap);
+        const uint32_t inv = ~i;
+        uint32_t* const cnt = cells + v * 1024u;
+        for (uint32_t p = placed; p; p &= p - 1u) {                                // (scalar) one trip per value the row reached
+            const uint32_t a = (uint32_t)__ffs((int)p) - 1u;
+            const uint32_t fa = (uint32_t)__builtin_amdgcn_readlane((int)first, (int)a);
+            if (lane == a || (first != ORDER_UNDEF && fa < first)) {               // (lanes at or above m never hold a first)
+                atomicAdd(cnt + a * 32u + lane, 1u);
+                atomicMax(cnt + ORDER_CELLS + a * 32u + lane, inv);
+            }
+        }
+    }
+    if (lane < 10u && acc) atomicAdd(&words[ORDER_COUNTS + lane], (unsigned long long)acc);
+    if (LDS_ACC) {
+        __syncthreads();
+        for (uint32_t c = threadIdx.x; c < ORDER_CELLS; c += 256u) {
+            const uint32_t cn = acc_lds[c];
+            if (cn) { atomicAdd(matrix + c, cn); atomicMax(matrix + ORDER_CELLS + c, acc_lds[ORDER_CELLS + c]); }
+        }
+    }
+}
+
+__global__ __launch_bounds__(1024) void order_extract_kernel(const unsigned long long* __restrict__ seeds, uint32_t n, uint32_t m,
+                                                             uint32_t* __restrict__ matrix, unsigned long long* __restrict__ words,
+                                                             unsigned long long* __restrict__ entries) {
+    __shared__ uint32_t wave_n[16];
+    const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6, a = t >> 5, b = t & 31;
+    uint32_t cnt[4], wit[4];
+    bool some = false, stale = false;
+    for (uint32_t k = 0; k < 4; k++) {
+        cnt[k] = matrix[k * 1024u + t]; wit[k] = matrix[ORDER_CELLS + k * 1024u + t];
+        matrix[k * 1024u + t] = 0u; matrix[ORDER_CELLS + k * 1024u + t] = 0u;      // clean for the next chunk
+        some |= cnt[k] != 0u;
+        stale |= cnt[k] ? ~wit[k] >= n : wit[k] != 0u;
+    }
+    stale |= some && (a >= m || b >= m);
+    const unsigned long long mine = __ballot(some);
+    if (lane == 0u) wave_n[wave] = (uint32_t)__popcll(mine);
+    __syncthreads();
+    uint32_t pos = (uint32_t)__popcll(mine & ((1ull << lane) - 1ull)), total = 0;
+    for (uint32_t wv = 0; wv < 16u; wv++) { pos += wv < wave ? wave_n[wv] : 0u; total += wave_n[wv]; }
+    if (stale) atomicOr(&words[ORDER_ERR], (unsigned long long)MADSIM_K_PROBE_ORDER_ERR_TAG);
+    if (t == 0u) words[ORDER_ENTRIES] = total;
+    if (some && pos < m * m) {                                                     // (a clean matrix has no more)
+        unsigned long long* const p = entries + 9 * (size_t)pos;
+        p[0] = stale ? 0ull : (unsigned long long)a | (unsigned long long)b << 32; // {uint32_t a, b}, little-endian
+        for (uint32_t k = 0; k < 4; k++) {
+            p[1 + k] = stale ? 0ull : cnt[k];
+            p[5 + k] = !stale && cnt[k] ? seeds[~wit[k]] : 0ull;
+        }
+    }
+}
+
 // one kernel per row of variant_table (sim_kernel.h), same macro, same order
 #define MADSIM_VARIANT_KERNEL(T_, S_, L_, F_, R_, G_) (const void*)sim_kernel<Variant<T_, S_, L_, F_, R_, G_>>,
 static const void* const variant_kernels[] = {MADSIM_FOR_EACH_VARIANT(MADSIM_VARIANT_KERNEL)};
@@ -1846,6 +1956,36 @@ extern "C" int madsim_k_launch_probe_sets(const uint64_t* obs, uint64_t obs_cap,
                                           madsim_probe_set_t* entries, void* stream) {
     return madsim_k_launch_probe_sets_form(obs, obs_cap, obs_len, res, d_seeds, n, include, vocab, n_vocab, sig, table, slots, list, cap, words, entries,
                                            stream, 0);
+}
+
+// Rows, lengths, results and seeds of the chunk's n seeds; vocab: n_vocab values in HOST memory (they travel in the kernel arguments);
+// matrix: MADSIM_K_PROBE_ORDER_MATRIX_WORDS zeroed words; words: MADSIM_K_PROBE_ORDER_WORDS zeroed words; entries: room for
+// n_vocab * n_vocab (sim_kernel.h).  Returns 0, or -1 (nothing launched) for sizes the kernels are not written for.
+// `direct` != 0: every update straight to the global matrix, no workgroup accumulator — the same bytes either way.
+extern "C" int madsim_k_launch_probe_order_form(const uint64_t* obs, uint64_t obs_cap, const uint64_t* obs_len, const madsim_result_t* res,
+                                                const uint64_t* d_seeds, uint64_t n, uint32_t include, const uint64_t* vocab, uint64_t n_vocab,
+                                                uint32_t* matrix, unsigned long long* words, madsim_probe_order_pair_t* entries, void* stream,
+                                                int direct) {
+    static_assert(sizeof(madsim_probe_order_pair_t) == 72 && sizeof(madsim_result_t) == 48, "record layout");
+    static_assert(sizeof(madsim_k::OrderVocab) == 256, "the vocabulary in the kernel arguments");
+    if (n == 0 || obs_cap == 0 || obs_cap > MADSIM_CENSUS_MAX_OBS_CAP || n >= 0xffffffffull / obs_cap || n > (1ull << 31)) return -1;      // n * obs_cap < 2^32 - 1; the row index plus a grid stride stays 32-bit
+    if (include == 0 || (include & ~0xfu) || n_vocab == 0 || n_vocab > MADSIM_PROBE_ORDER_MAX_VOCAB) return -1;
+    if (!obs || !obs_len || !res || !d_seeds || !vocab || !matrix || !words || !entries || ((uintptr_t)matrix & 3u) || ((uintptr_t)entries & 7u)) return -1;
+    madsim_k::OrderVocab V{};
+    for (uint64_t j = 0; j < n_vocab; j++) V.v[j] = vocab[j];
+    const uint64_t waves = n < MADSIM_K_PROBE_ORDER_WAVES ? n : MADSIM_K_PROBE_ORDER_WAVES;      // one wave per row, 256 workgroups at most
+    const auto fold = direct ? madsim_k::order_fold_kernel<false> : madsim_k::order_fold_kernel<true>;
+    hipLaunchKernelGGL(fold, dim3((uint32_t)((waves + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const unsigned long long*)obs, (uint32_t)obs_cap,
+                       (const unsigned long long*)obs_len, res, (uint32_t)n, include, V, (uint32_t)n_vocab, matrix, words);
+    hipLaunchKernelGGL(madsim_k::order_extract_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, (const unsigned long long*)d_seeds, (uint32_t)n,
+                       (uint32_t)n_vocab, matrix, words, reinterpret_cast<unsigned long long*>(entries));
+    return 0;
+}
+
+extern "C" int madsim_k_launch_probe_order(const uint64_t* obs, uint64_t obs_cap, const uint64_t* obs_len, const madsim_result_t* res,
+                                           const uint64_t* d_seeds, uint64_t n, uint32_t include, const uint64_t* vocab, uint64_t n_vocab,
+                                           uint32_t* matrix, unsigned long long* words, madsim_probe_order_pair_t* entries, void* stream) {
+    return madsim_k_launch_probe_order_form(obs, obs_cap, obs_len, res, d_seeds, n, include, vocab, n_vocab, matrix, words, entries, stream, 0);
 }
 
 extern "C" void madsim_k_launch_keyflip(unsigned long long* acc, void* stream) {

@@ -175,6 +175,14 @@ def lib():
         L.madsim_hip_ctx_probe_sets_range.argtypes = [ctxp] + L.madsim_hip_probe_sets_range.argtypes
         L.madsim_hip_ctx_probe_sets_seeds.argtypes = [ctxp] + L.madsim_hip_probe_sets_seeds.argtypes
         L.madsim_k_fold_probe_sets.argtypes = [C.POINTER(A.ProbeSets), C.c_void_p, C.c_void_p, C.c_uint64]
+        # the probe-order census: the census's signatures with a madsim_probe_order_t
+        L.madsim_hip_probe_order_range.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(A.Limits),
+                                                   C.POINTER(A.ProbeOrder)]
+        L.madsim_hip_probe_order_seeds.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), u64p, C.c_uint64, C.c_uint64, C.POINTER(A.Limits),
+                                                   C.POINTER(A.ProbeOrder)]
+        L.madsim_hip_ctx_probe_order_range.argtypes = [ctxp] + L.madsim_hip_probe_order_range.argtypes
+        L.madsim_hip_ctx_probe_order_seeds.argtypes = [ctxp] + L.madsim_hip_probe_order_seeds.argtypes
+        L.madsim_k_fold_probe_order.argtypes = [C.POINTER(A.ProbeOrder), C.c_void_p, C.c_void_p, C.c_uint64]
         # the sweep campaigns: one signature for the range (seeds NULL) and the list (seed0 0)
         L.madsim_hip_run_sweep_campaign.argtypes = [C.POINTER(A.SweepVariant), C.c_uint32, C.c_uint64, C.c_uint64, u64p, C.c_uint64, C.c_uint32,
                                                     C.c_uint32, C.POINTER(A.Sweep)]
@@ -300,7 +308,7 @@ def _resolve_flags(resolve):
 
 
 def _resolve_rounds(resolve):
-    """`resolve=` of trace_seeds, diverge_seeds, census and probe_sets as a number of rounds: None / False = 0, True = the default, an int = that many."""
+    """`resolve=` of trace_seeds, diverge_seeds, census, probe_sets and probe_order as a number of rounds: None / False = 0, True = the default, an int = that many."""
     rounds = 0 if resolve is None or resolve is False else A.RESOLVE_DEFAULT_ROUNDS if resolve is True else int(resolve)
     if not 0 <= rounds <= A.RESOLVE_MAX_ROUNDS:
         raise MadsimHipError(f"resolve: None, True or a number of rounds 1..{A.RESOLVE_MAX_ROUNDS}, got {resolve!r}")
@@ -461,7 +469,7 @@ def diverge_seeds(workload, seeds, other=None, config=None, other_config=None, l
 
 
 class _ObsReport:
-    """What Census and ProbeSets share.  A form names its entry array (`_array`: the attribute here and the field of its C struct `_struct`, of
+    """What Census, ProbeSets and ProbeOrder share.  A form names its entry array (`_array`: the attribute here and the field of its C struct `_struct`, of
     `_entry` records), that struct's count field and the library's host fold of the form."""
 
     def __len__(self):
@@ -765,6 +773,158 @@ def probe_sets(workload, vocabulary=None, seed0=0, total=0, seeds=None, include=
     L = lib()
     return _probe_sets(lambda *a: L.madsim_hip_probe_sets_range(workload.ref(), *a), lambda *a: L.madsim_hip_probe_sets_seeds(workload.ref(), *a),
                        census, workload, vocabulary, seed0, total, seeds, include, obs_cap, max_sets, chunk, config, limits, resolve)
+
+
+class ProbeOrder(_ObsReport):
+    """Which vocabulary value the seeds reached FIRST, by verdict (runtime.probe_order).  `vocabulary`: the tuple of distinct values;
+    `pairs`: ndarray[A.PROBE_ORDER_PAIR_DTYPE], ascending by (a, b), a and b INDICES into the vocabulary, only the cells with a seed in some
+    verdict — the diagonal (a, a): the counted seeds of each verdict that reached vocabulary[a] (`n_seeds[4]`); off it: those that reached
+    both and saw vocabulary[a] first before they first saw vocabulary[b]; `first_seed[4]` the smallest such seed, 0 where there is none.
+    `n_counted[4]` / `n_none[4]`: counted seeds per verdict / those of them that reached no vocabulary value; `n_truncated`: counted seeds
+    with more than `obs_cap` observations, counted on their visible prefix; `n_runner` seeds were left with a runner verdict and are counted
+    nowhere, `runner_seeds` (ndarray[uint64], ascending) the ones that were listed.  The readers take vocabulary VALUES and give Python ints."""
+    _array, _count, _struct, _entry, _fold = "pairs", "n_pairs", A.ProbeOrder, A.ProbeOrderPair, "madsim_k_fold_probe_order"
+    _verdicts = staticmethod(ProbeSets._verdicts)
+
+    def __init__(self, vocabulary, pairs, n_counted, n_none, n_truncated, n_runner, runner_seeds, include, obs_cap):
+        self.vocabulary = tuple(int(v) for v in vocabulary)
+        self.pairs = pairs
+        self.n_counted, self.n_none = tuple(int(x) for x in n_counted), tuple(int(x) for x in n_none)
+        self.n_truncated, self.n_runner = int(n_truncated), int(n_runner)
+        self.runner_seeds, self.include, self.obs_cap = runner_seeds, include, obs_cap
+        self._index = {v: i for i, v in enumerate(self.vocabulary)}
+        self._at = {(int(e["a"]), int(e["b"])): i for i, e in enumerate(pairs)}
+
+    def __repr__(self):
+        return (f"ProbeOrder({len(self.pairs)} cells of {len(self.vocabulary)} values over {sum(self.n_counted)} counted seeds, "
+                f"n_counted={self.n_counted}, n_none={self.n_none}, n_truncated={self.n_truncated}, n_runner={self.n_runner})")
+
+    def tobytes(self):
+        """The whole report as bytes: two reports under one vocabulary are the same exactly when these are equal."""
+        totals = np.array(self.n_counted + self.n_none + (self.n_truncated, self.n_runner), dtype=np.uint64)
+        return self.pairs.tobytes() + totals.tobytes() + np.asarray(self.runner_seeds, dtype=np.uint64).tobytes()
+
+    def cell(self, a, b):
+        """The record of the cell (a, b) of vocabulary values (a numpy record of A.PROBE_ORDER_PAIR_DTYPE), or None when no counted seed is in it."""
+        for v in (a, b):
+            if int(v) not in self._index:
+                raise MadsimHipError(f"probe_order: {int(v):#x} is not in the vocabulary")
+        i = self._at.get((self._index[int(a)], self._index[int(b)]))
+        return None if i is None else self.pairs[i]
+
+    def _n(self, a, b, verdicts):
+        e, vs = self.cell(a, b), self._verdicts(verdicts)
+        return 0 if e is None else sum(int(e["n_seeds"][k]) for k in vs)
+
+    def reached(self, a, verdicts=None):
+        """Counted seeds of `verdicts` (None: all four) that reached `a`."""
+        return self._n(a, a, verdicts)
+
+    def before(self, a, b, verdicts=None):
+        """Counted seeds of `verdicts` that reached both and first saw `a` before they first saw `b` (a == b: reached(a))."""
+        return self._n(a, b, verdicts)
+
+    def both(self, a, b, verdicts=None):
+        """Counted seeds of `verdicts` that reached both `a` and `b`: two values never share an index, so one of them came first."""
+        return self.reached(a, verdicts) if int(a) == int(b) else self._n(a, b, verdicts) + self._n(b, a, verdicts)
+
+    def without(self, a, b, verdicts=None):
+        """Counted seeds of `verdicts` that reached `a` and not `b`."""
+        return self.reached(a, verdicts) - self.both(a, b, verdicts)
+
+    def always_before(self, a, b, verdicts=None):
+        """Some counted seed of `verdicts` reached both, and none of them saw `b` first."""
+        return int(a) != int(b) and self.both(a, b, verdicts) > 0 and self._n(b, a, verdicts) == 0
+
+    def witness(self, a, b, verdict):
+        """The smallest counted seed of `verdict` in the cell (a, b) — the seed to replay —, or None when there is none."""
+        e = self.cell(a, b)
+        (k,) = self._verdicts(int(verdict))
+        return int(e["first_seed"][k]) if e is not None and int(e["n_seeds"][k]) else None
+
+    def precedence(self, verdicts=None):
+        """The always-before pairs of `verdicts`, transitively reduced: (a, b) is dropped when a chain of other always-before pairs
+        leads from a to b.  A list of (a, b) in vocabulary order."""
+        edges = {a: [b for b in self.vocabulary if self.always_before(a, b, verdicts)] for a in self.vocabulary}
+
+        def chained(a, b):                                                         # a path from a to b that does not use the pair (a, b) itself
+            seen, todo = set(), [a]
+            while todo:
+                x = todo.pop()
+                for y in edges[x]:
+                    if (x, y) != (a, b) and y not in seen:
+                        seen.add(y)
+                        todo.append(y)
+            return b in seen
+
+        return [(a, b) for a in self.vocabulary for b in edges[a] if not chained(a, b)]
+
+    def discriminating(self):
+        """The order-violation candidates: (a, b, seed) where every PASSING seed that reached both saw `a` first (there is one), and at
+        least one failing seed saw `b` first: `seed` is the smallest of those, over the failing verdicts — the witness to replay."""
+        out = []
+        for a in self.vocabulary:
+            for b in self.vocabulary:
+                if self.always_before(a, b, A.PASS) and self._n(b, a, (1, 2, 3)):
+                    out.append((a, b, min(s for s in (self.witness(b, a, k) for k in (1, 2, 3)) if s is not None)))
+        return out
+
+    def merge(self, other):
+        """The report of the union of two DISJOINT seed sets taken under the same vocabulary, include mask and obs_cap: exact, in either order."""
+        if (self.vocabulary, self.include, self.obs_cap) != (other.vocabulary, other.include, other.obs_cap):
+            raise MadsimHipError("ProbeOrder.merge: the two reports differ in vocabulary, include or obs_cap")
+        pairs, runner = self._merged(other)
+        add4 = lambda a, b: tuple(x + y for x, y in zip(a, b))                      # noqa: E731
+        return ProbeOrder(self.vocabulary, pairs, add4(self.n_counted, other.n_counted), add4(self.n_none, other.n_none),
+                          self.n_truncated + other.n_truncated, self.n_runner + other.n_runner, runner, self.include, self.obs_cap)
+
+
+def _probe_order(call_range, call_seeds, census_call, workload, vocabulary, seed0, total, seeds, include, obs_cap, chunk, config, limits, resolve):
+    """One probe-order call — `call_range(cfg, seed0, total, chunk, lim, po)` or `call_seeds(cfg, seeds*, n, chunk, lim, po)`, a
+    madsim_hip_*probe_order_* entry point with its context and workload bound — and its runner seeds settled round by round (_settle), as
+    _census does.  vocabulary=None: one `census_call` (the same seeds, masks and limits) first, whose values are the vocabulary."""
+    cfg, lim0 = config or A.Config.default(), limits or A.Limits()
+    mask = _include_mask(include)
+    rounds = _resolve_rounds(resolve)
+    if vocabulary is None:
+        cen = census_call(workload, seed0, total, seeds, include, obs_cap, 4096, chunk, config, limits, resolve)
+        vocabulary = [int(v) for v in cen.values["value"]]
+        if not vocabulary:
+            raise MadsimHipError("probe_order: vocabulary=None and no counted seed traced a value: there is no vocabulary to take")
+    vocab = np.array([int(v) for v in vocabulary], dtype=np.uint64)
+    if not 1 <= len(vocab) <= A.PROBE_ORDER_MAX_VOCAB:
+        raise MadsimHipError(f"probe_order: a vocabulary of 1..{A.PROBE_ORDER_MAX_VOCAB} values, got {len(vocab)} (name the values whose order matters)")
+    if len(set(int(v) for v in vocab)) != len(vocab):
+        raise MadsimHipError("probe_order: a value occurs twice in the vocabulary")
+    cap = len(vocab) ** 2
+
+    def one(lim, sa, s0, n):
+        pairs, runner = np.zeros(cap, dtype=A.PROBE_ORDER_PAIR_DTYPE), np.zeros(max(n, 1), dtype=np.uint64)
+        po = A.ProbeOrder(include=mask, obs_cap=obs_cap, n_vocab=len(vocab), cap=cap, runner_cap=n)
+        po.vocab, po.pairs = vocab.ctypes.data_as(C.POINTER(C.c_uint64)), pairs.ctypes.data_as(C.POINTER(A.ProbeOrderPair))
+        po.runner_seeds = runner.ctypes.data_as(C.POINTER(C.c_uint64))
+        if sa is None:
+            _check(call_range(C.byref(cfg), s0, n, chunk, C.byref(lim), C.byref(po)))
+        else:
+            _check(call_seeds(C.byref(cfg), _seeds_ptr(sa), n, chunk, C.byref(lim), C.byref(po)))
+        return ProbeOrder(vocab, pairs[:po.n_pairs].copy(), po.n_counted, po.n_none, po.n_truncated, po.n_runner, runner[:po.n_runner_listed].copy(),
+                          mask, obs_cap)
+
+    return _settle(one, workload, lim0, rounds, seed0, total, seeds, cap, "probe_order: more cells than the vocabulary has pairs (internal)")
+
+
+def probe_order(workload, vocabulary=None, seed0=0, total=0, seeds=None, include=(A.PASS, A.PANIC, A.DEADLOCK, A.TIME_LIMIT), obs_cap=256,
+                chunk=0, config=None, limits=None, resolve=True):
+    """madsim_hip_probe_order_range / madsim_hip_probe_order_seeds: which of the values of `vocabulary` (1 .. 32 distinct 64-bit values; None:
+    the values a census of the same seeds finds, MadsimHipError when they are more than 32) the seeds [seed0, seed0 + total) — or the
+    strictly ascending `seeds` — reach FIRST, by verdict, reduced on the device: returns a ProbeOrder.  A seed is counted when its verdict
+    is in `include`; the first `obs_cap` observations of a seed are visible; `chunk` = seeds per trace launch, 0 = the library's default
+    — it never shows in the result.  resolve: as runtime.census."""
+    if _inited_device is None:
+        init(0)
+    L = lib()
+    return _probe_order(lambda *a: L.madsim_hip_probe_order_range(workload.ref(), *a), lambda *a: L.madsim_hip_probe_order_seeds(workload.ref(), *a),
+                        census, workload, vocabulary, seed0, total, seeds, include, obs_cap, chunk, config, limits, resolve)
 
 
 def observe_seed(workload, seed, config=None, limits=None, cap=1 << 16, resolve=True):
@@ -1482,6 +1642,14 @@ class Context:
         return _probe_sets(lambda *a: L.madsim_hip_ctx_probe_sets_range(self._h, workload.ref(), *a),
                            lambda *a: L.madsim_hip_ctx_probe_sets_seeds(self._h, workload.ref(), *a), self.census, workload, vocabulary, seed0,
                            total, seeds, include, obs_cap, max_sets, chunk, config, limits, resolve)
+
+    def probe_order(self, workload, vocabulary=None, seed0=0, total=0, seeds=None, include=(A.PASS, A.PANIC, A.DEADLOCK, A.TIME_LIMIT), obs_cap=256,
+                    chunk=0, config=None, limits=None, resolve=True):
+        """runtime.probe_order on this context (madsim_hip_ctx_probe_order_range / madsim_hip_ctx_probe_order_seeds)."""
+        L = lib()
+        return _probe_order(lambda *a: L.madsim_hip_ctx_probe_order_range(self._h, workload.ref(), *a),
+                            lambda *a: L.madsim_hip_ctx_probe_order_seeds(self._h, workload.ref(), *a), self.census, workload, vocabulary, seed0,
+                            total, seeds, include, obs_cap, chunk, config, limits, resolve)
 
     def observe_seed(self, workload, seed, config=None, limits=None, cap=1 << 16, resolve=True):
         """runtime.observe_seed on this context."""

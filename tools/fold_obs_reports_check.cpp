@@ -1,5 +1,5 @@
-// tools/fold_obs_reports_check.cpp — madsim_k_fold_census and madsim_k_fold_probe_sets (the host folds of the observation census and of the
-// probe-set census: one merge routine in madsim_hip.cpp under two forms) in a stand-alone program, meant to be built with AddressSanitizer
+// tools/fold_obs_reports_check.cpp — madsim_k_fold_census, madsim_k_fold_probe_sets and madsim_k_fold_probe_order (the host folds of the
+// observation census, the probe-set census and the probe-order census: one merge routine in madsim_hip.cpp under three forms) in a stand-alone program, meant to be built with AddressSanitizer
 // and UndefinedBehaviorSanitizer on the host side.  No device is touched: the folds are plain host code.  For each fold, random chunks of
 // entries (equal keys inside a chunk, keys shared between chunks, the keys 0 and 2^64 - 1) are folded into a table sized EXACTLY to the
 // number of distinct keys — every write at the table's last element is inside it — and held against a std::map; then once more into a
@@ -24,6 +24,7 @@
 // (csrc/sim_kernel.h, which needs the HIP headers, declares these)
 extern "C" int madsim_k_fold_census(madsim_census_t* cen, const unsigned long long* words, const madsim_census_value_t* entries, uint64_t n);
 extern "C" int madsim_k_fold_probe_sets(madsim_probe_sets_t* ps, const unsigned long long* words, const madsim_probe_set_t* entries, uint64_t n);
+extern "C" int madsim_k_fold_probe_order(madsim_probe_order_t* po, const unsigned long long* words, const madsim_probe_order_pair_t* entries, uint64_t n);
 
 static uint64_t state = 0x9E3779B97F4A7C15ull;
 static uint64_t rnd() { state ^= state << 13; state ^= state >> 7; state ^= state << 17; return state; }
@@ -77,16 +78,45 @@ struct ProbeSetsFold {
         }
         return x;
     }
-    static void combine(Entry& a, const Entry& b) {                // per verdict the smallest seed of the sides that have seeds; 0 where neither has
+    template <class E>
+    static void combine_seeds(E& a, const E& b) {                  // per verdict the smallest seed of the sides that have seeds; 0 where neither has
         for (int k = 0; k < 4; k++) {
             if (b.n_seeds[k]) a.first_seed[k] = a.n_seeds[k] ? std::min(a.first_seed[k], b.first_seed[k]) : b.first_seed[k];
             a.n_seeds[k] += b.n_seeds[k];
         }
     }
+    static void combine(Entry& a, const Entry& b) { combine_seeds(a, b); }
     static void totals(unsigned long long* w) { for (int i = 2; i <= 6; i++) w[i] = rnd() % 1000; }
     static void add(Report& r, const unsigned long long* w) {
         for (int k = 0; k < 4; k++) r.n_counted[k] += w[2 + k];
         r.n_runner += w[6];
+    }
+};
+
+struct ProbeOrderFold {
+    typedef madsim_probe_order_t Report;
+    typedef madsim_probe_order_pair_t Entry;
+    static constexpr const char* name = "madsim_k_fold_probe_order";
+    static constexpr size_t words = 12;
+    static int fold(Report* r, const unsigned long long* w, const Entry* e, uint64_t n) { return madsim_k_fold_probe_order(r, w, e, n); }
+    static void table(Report& r, Entry* t) { r.pairs = t; }
+    static uint64_t& count(Report& r) { return r.n_pairs; }
+    static uint64_t key(const Entry& e) { return (uint64_t)e.a << 32 | e.b; }      // ascending by (a, b)
+    static Entry entry(uint64_t key) {
+        Entry x{};
+        x.a = (uint32_t)(key >> 32); x.b = (uint32_t)key;
+        for (int k = 0; k < 4; k++) {
+            if (rnd() % 3 == 0) continue;
+            x.n_seeds[k] = 1 + rnd() % 1000;
+            x.first_seed[k] = rnd() % 5 ? rnd() : 0;                               // (seed 0 is a seed like any other)
+        }
+        return x;
+    }
+    static void combine(Entry& a, const Entry& b) { ProbeSetsFold::combine_seeds(a, b); }
+    static void totals(unsigned long long* w) { for (int i = 2; i <= 11; i++) w[i] = rnd() % 1000; }
+    static void add(Report& r, const unsigned long long* w) {
+        for (int k = 0; k < 4; k++) { r.n_counted[k] += w[2 + k]; r.n_none[k] += w[6 + k]; }
+        r.n_truncated += w[10]; r.n_runner += w[11];
     }
 };
 
@@ -150,6 +180,6 @@ static int check() {
 }
 
 int main() {
-    const int failures = check<CensusFold>() + check<ProbeSetsFold>();
+    const int failures = check<CensusFold>() + check<ProbeSetsFold>() + check<ProbeOrderFold>();
     return failures ? 1 : 0;
 }
