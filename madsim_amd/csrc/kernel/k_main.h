@@ -34,6 +34,7 @@ __device__ __forceinline__ void seed_init(const Ctx& c, Lane& L, uint64_t seed) 
     L.pq_n = 0; L.ready_len = 0; L.rq = 0; L.heap_len = 0; L.top_dl = ~0ull; L.top_meta = 0; L.verdict = MADSIM_RUNNING; L.ovf = 0; L.main_done = 0;
     L.loss_pint = P.loss_pint; L.loss_always = P.loss_always;
     // TimeRuntime::new (time/mod.rs:26-38): base_time draw, before logging is enabled
+    L.clock_fold = 0;                                      // (the fold of clock 0: the draw's log entry is discarded, the first pass folds again — k_rng.h ClockFold)
     { uint64_t h = L.trace_hash, n = L.log_len; uint32_t bt = gen_range_small<Variant<false, false, K::LWS, 0, K::RQ>, 31536000u>(c, L); L.trace_hash = h; L.log_len = n;
       if (K::LIFE) NODEW(4 + ((P.n_nodes + 4) >> 2)) = bt; }      // seconds into 2022: SystemTime::now() of MS_OP_TRACE_TIME
     L.trace_hash = FNV_OFFSET; L.obs_hash = FNV_OFFSET; L.log_len = 0;
@@ -65,6 +66,9 @@ __device__ __forceinline__ uint32_t progress_priority(uint32_t pass, uint32_t es
     const uint32_t q = (pass < (1u << 30) ? pass : (1u << 30) - 1u) * 4u / est;      // (saturating: pass * 4 wrapped once a wave had run 2^30 passes; one s_min_u32)
     return q >= 3 ? 0u : 3u - q;
 }
+
+// Register-ready-queue builds pop a queue of one under gen_index's wave vote (sim_kernel.h MADSIM_POP_ONE; the pop in sim_kernel below).
+template <class K> struct PopOne { static constexpr bool ON = MADSIM_POP_ONE && K::RQ; };
 
 template <class K>
 __global__ __launch_bounds__(256, K::CMP ? 4 : !K::G ? 1 : (K::FEAT & (MADSIM_FEAT_ALL & ~MADSIM_FEAT_ADDR)) == (MADSIM_FEAT_ALL & ~MADSIM_FEAT_ADDR) ? MADSIM_ALLG_WAVES_PER_EU : MADSIM_G_WAVES_PER_EU) void sim_kernel(const KParams P) {
@@ -181,12 +185,26 @@ __global__ __launch_bounds__(256, K::CMP ? 4 : !K::G ? 1 : (K::FEAT & (MADSIM_FE
             const uint32_t slot0 = K::RQ ? (uint32_t)(L.rq & 0xff) : rq_get<K>(c, 0);
             const uint4 pu0 = TU(c, slot0, 0), pu1 = load_u1<K>(c, slot0);
             PollPrefetch pp = poll_prefetch<K>(c, slot0);     // (global-state builds: more of the slot's granule, same cache line)
+            // the first with() of the pass, behind every clock write of the previous one: the fold its log entries share (k_rng.h ClockFold)
+            if (ClockFold<K>::ON) L.clock_fold = clock_fold_byte(L.clock);
             // try_recv_random (utils/mpsc.rs:73-83): idx drawn even when len == 1
-            uint32_t idx = gen_index<K>(c, L, L.ready_len);
+            const bool all_one = wave_all(L.ready_len == 1);  // every lane of the wave holds one queued task (wave-uniform: gen_index's short accept test)
+            uint32_t idx = gen_index<K>(c, L, L.ready_len, all_one);
             L.ready_len--;
             uint32_t slot = slot0;
             uint4 u0 = pu0, u1 = pu1;
-            if (K::RQ) {
+            if (PopOne<K>::ON && all_one) {
+                // ... and the pop under the same vote: index 0 of a queue of one leaves the queue empty — none of swap_remove's shifts
+#ifdef MADSIM_EMU
+                {
+                    const uint64_t last = (L.rq >> (8 * L.ready_len)) & 0xff;
+                    uint64_t q = (L.rq & ~(0xffull << (8 * idx))) | (last << (8 * idx));
+                    q &= ~(0xffull << (8 * L.ready_len));
+                    if (idx != 0 || L.ready_len != 0 || q != 0) OVF_SET(L, OVF_BUG);     // what the general form below would have left
+                }
+#endif
+                L.rq = 0; L.ready_len = 0;
+            } else if (K::RQ) {
                 if (idx != 0) { slot = (uint32_t)(L.rq >> (8 * idx)) & 0xff; u0 = TU(c, slot, 0); u1 = load_u1<K>(c, slot); pp = poll_prefetch<K>(c, slot); }
                 uint64_t last = (L.rq >> (8 * L.ready_len)) & 0xff;      // swap_remove on bytes
                 L.rq = (L.rq & ~(0xffull << (8 * idx))) | (last << (8 * idx));

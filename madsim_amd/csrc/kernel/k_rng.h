@@ -59,6 +59,16 @@ __device__ __forceinline__ bool reject_const(uint64_t v, uint32_t zone_hi) {
     return reject32(v, RANGE, zone_hi);
 }
 
+// The log entry's xor-fold of the elapsed time, down to the byte that is kept.  In the base-op builds the clock moves in three places — the add behind the
+// pass's advance draw (after that draw's own entry), the idle jump, seed_init — and none of them lies between two with()s of one poll (MS_OP_ADVANCE
+// is an extended-build op): those builds fold once per pass, where the ready-queue draw begins (k_main.h), and every entry of the pass reads Lane::clock_fold.
+template <class K> struct ClockFold { static constexpr bool ON = MADSIM_CLOCK_FOLD && MADSIM_K_LOG_ENABLED && !K::NOLOG && !K::LIFE; };
+__device__ __forceinline__ uint32_t clock_fold_byte(uint64_t clock) {
+    uint32_t f = (uint32_t)clock ^ (uint32_t)(clock >> 32);
+    f ^= f >> 16; f ^= f >> 8;
+    return f & 0xff;
+}
+
 // One determinism-log byte per GlobalRng::with (rand.rs:64-88): clone.gen::<u8>() ^ xor-fold(elapsed).
 template <class K>
 __device__ __forceinline__ void rng_log(const Ctx& c, Lane& L, bool have = false) {     // have: Lane::peek is current (gen_index)
@@ -67,8 +77,16 @@ __device__ __forceinline__ void rng_log(const Ctx& c, Lane& L, bool have = false
     if (K::LOGSW && c.P.no_log) return;                    // (wave-uniform)
     const uint64_t r = Peek<K>::ON ? L.peek : rng_out(L);
     uint32_t v = (uint32_t)(r >> 32);
-    uint32_t f = (uint32_t)L.clock ^ (uint32_t)(L.clock >> 32);
-    f ^= f >> 16; f ^= f >> 8;
+    uint32_t f;
+    if (ClockFold<K>::ON) {
+        f = L.clock_fold;
+#ifdef MADSIM_EMU
+        if (f != clock_fold_byte(L.clock)) OVF_SET(L, OVF_BUG);     // a clock write between the pass's fold and this with()
+#endif
+    } else {
+        f = (uint32_t)L.clock ^ (uint32_t)(L.clock >> 32);
+        f ^= f >> 16; f ^= f >> 8;
+    }
     v = (v ^ f) & 0xff;
     L.trace_hash = (L.trace_hash ^ v) * FNV_PRIME;
     if (K::TRACE) { if (L.log_len < c.P.trace_cap) c.tlog[L.log_len] = (uint8_t)v; }
@@ -100,13 +118,14 @@ __device__ __forceinline__ uint64_t gen_range_u64(const Ctx& c, Lane& L, uint64_
 
 // ready-queue index draw: range = len <= 255, so the 128-bit product splits into two 32x32 pieces.
 template <class K>
-__device__ __forceinline__ uint32_t gen_index(const Ctx& c, Lane& L, uint32_t len) {
+__device__ __forceinline__ uint32_t gen_index(const Ctx& c, Lane& L, uint32_t len, bool all_one) {
     uint64_t v;
     uint32_t trips = 0;
     // The queue usually holds ONE task: range 1, zone 2^63 - 1 — the draw is rejected while the output's top bit is set and the
-    // index is 0.  When that is so for every lane of the wave (k_mem.h wave_all) the accept test is one signed compare instead of
-    // the two multiplies of reject32: ~7 wave trips an executor pass end here.  (Same outputs consumed, same results.)
-    if (wave_all(len == 1)) {
+    // index is 0.  When that is so for every lane of the wave (all_one: the caller's wave_all(len == 1), k_mem.h — k_main.h pops under the
+    // same vote) the accept test is one signed compare instead of the two multiplies of reject32: ~7 wave trips an executor pass end here.
+    // (Same outputs consumed, same results.)
+    if (all_one) {
         if (Peek<K>::ON) {
             // the accepted output itself is not needed (the index is 0): each trip tests the output in hand, advances and computes the next one —
             // the do-while it always was, and the output left in hand at the exit is the log entry's number (rng_log_with)

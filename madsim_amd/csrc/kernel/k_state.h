@@ -160,6 +160,8 @@ struct Lane {
     uint32_t exact, hazard;
     uint64_t dd_occ;         // which buckets of the re-registration table hold a count (k_timer.h dedup_note)
     uint64_t obs_len;        // trace builds: values folded into obs_hash so far (k_rng.h obs_fold)
+    // (last: the builds that do not keep it compile to what they were)
+    uint32_t clock_fold;     // the determinism log's xor-fold byte of `clock` as of the pass's ready-queue draw (k_rng.h ClockFold: base-op builds that keep the log)
 };
 
 #define LDS128(i) (reinterpret_cast<uint4*>(SMEM)[(i)])

@@ -62,6 +62,16 @@
 #ifndef MADSIM_RNG_PEEK_LIFE
 #define MADSIM_RNG_PEEK_LIFE 0   /* ... in the extended builds too */
 #endif
+/* Base-op builds that keep the determinism log: the xor-fold of the clock that every log entry carries is held in a lane register,
+   computed once per pass where the ready-queue draw begins (k_rng.h ClockFold) — the clock does not move between the with()s of one poll there. */
+#ifndef MADSIM_CLOCK_FOLD
+#define MADSIM_CLOCK_FOLD 1
+#endif
+/* Register-ready-queue builds: a wave whose lanes all hold ONE queued task pops it without swap_remove's shifts (k_main.h; the vote is the one
+   gen_index needs anyway). */
+#ifndef MADSIM_POP_ONE
+#define MADSIM_POP_ONE 1
+#endif
 /* MADSIM_STATE_DEDUP_TIMERS builds: the occupancy of the re-registration table mirrored in a register (k_timer.h dedup_note). */
 #ifndef MADSIM_DEDUP_OCC
 #define MADSIM_DEDUP_OCC 1

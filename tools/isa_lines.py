@@ -5,7 +5,7 @@ Compiles sim_kernel.hip for ONE variant with line tables, reads the `.loc` direc
 the VALU / SALU / LDS / VMEM / branch instructions the compiler made of it.  A wave executes every line some lane of it reaches, so for
 the straight-line part of a pass (everything but the rejection loops) the static count IS the per-pass cost; loops count once here.
 
-    python tools/isa_lines.py ['X(false,false,6,MADSIM_FEAT_COMPACT,true,false)'] [top=45]
+    python tools/isa_lines.py ['X(false,false,6,MADSIM_FEAT_COMPACT,true,false)'] [top=45] [extra hipcc flags, e.g. -DMADSIM_POP_ONE=0 ...]
 """
 import collections, os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -13,7 +13,7 @@ var = sys.argv[1] if len(sys.argv) > 1 else "X(false,false,6,MADSIM_FEAT_COMPACT
 top = int(sys.argv[2]) if len(sys.argv) > 2 else 45
 out = "/tmp/isa_lines.s"
 subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-Os", "-std=c++17", "-fPIC", "-Wno-unused-function", "-gline-tables-only",
-                       f"-DMADSIM_FOR_EACH_VARIANT(X)={var}", "--cuda-device-only", "-S", "sim_kernel.hip", "-o", out],
+                       f"-DMADSIM_FOR_EACH_VARIANT(X)={var}", *sys.argv[3:], "--cuda-device-only", "-S", "sim_kernel.hip", "-o", out],
                       cwd=os.path.join(ROOT, "madsim_amd", "csrc"), stderr=subprocess.DEVNULL)
 files, cur, in_kernel = {}, None, False
 cnt = collections.defaultdict(lambda: collections.Counter())
