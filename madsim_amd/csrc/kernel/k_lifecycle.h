@@ -20,6 +20,7 @@ template <class K>
 __device__ __forceinline__ uint32_t spawn_task(const Ctx& c, Lane& L, uint32_t prog, bool record, bool via_handle = false, int parent = -1,
                                                const SpawnInit init = SpawnInit{false, 0, 0, false, 0, 0, 0, false, 0, 0, 0, 0, 0}) {
     uint32_t slot = 0;
+    const KParams& P = c.P;
     if (K::G) {                                              // first free slot = first zero bit of the alive mask (LDS)
         slot = c.P.max_tasks;
         if (init.words_known) slot = init.slot;              // (found by the caller, nothing spawned since)
@@ -31,12 +32,13 @@ __device__ __forceinline__ uint32_t spawn_task(const Ctx& c, Lane& L, uint32_t p
         if (init.words_known && ((AMASK(slot >> 5) >> (slot & 31)) & 1)) OVF_SET(L, OVF_BUG);
 #endif
     } else {
-        while (slot < c.P.max_tasks && (TWORD(c, slot, 0, 0) & TF_ALIVE)) slot++;
+        const uint32_t n = ColdParams<K>::ON ? PCOLD(max_tasks) : 0u;
+        while (slot < (ColdParams<K>::ON ? n : c.P.max_tasks) && (TWORD(c, slot, 0, 0) & TF_ALIVE)) slot++;
     }
     // (the task table holds max_tasks <= 254 live tasks — an 8-bit slot.  Short of that a larger limit lifts it: a capacity verdict, the seed is
     //  run again.  AT 254 nothing does: the 255th live task leaves the workload model, MADSIM_UNSUPPORTED — and since the oracle fills its
     //  unbounded Vec lowest free slot first, as this does, it says so at the same spawn)
-    if (slot >= c.P.max_tasks) { OVF_SET(L, c.P.max_tasks >= MADSIM_MAX_LIVE_TASKS ? OVF_MODEL : OVF_CAP); return 0xffffffffu; }
+    if (slot >= PCOLD(max_tasks)) { OVF_SET(L, PCOLD(max_tasks) >= MADSIM_MAX_LIVE_TASKS ? OVF_MODEL : OVF_CAP); return 0xffffffffu; }
     if (K::G) AMASK(slot >> 5) |= 1u << (slot & 31);
     uint32_t pw, node, gen, killed = 0, info_gen = 0, seq = 0;
     if constexpr (K::G) {
@@ -146,7 +148,8 @@ __device__ __forceinline__ void task_drop_locals(const Ctx& c, Lane& L, uint32_t
             }
         }
     } else if (f & TF_OWNER) {                                // LDS-resident builds: every table entry, in order
-        for (uint32_t i = 0; i < c.P.n_socks; i++) {
+        const KParams& P = c.P;
+        PCOLD_FOR(i, 0, n_socks) {
             const uint32_t hdr = SW(c, i, 0);
             if (!sock_owned_by<K>(c, i, hdr, slot, gen)) continue;
             endpoint_drop<K>(c, L, i, (f & TF_KILLED) != 0);

@@ -15,9 +15,9 @@ __device__ __forceinline__ void seed_init(const Ctx& c, Lane& L, uint64_t seed) 
         OMASK(0) = 0; OMASK(1) = 0;
         if (K::NH) for (uint32_t w = 0; w < P.pool_n / 32; w++) PMASK(w) = 0;
     }
-    else for (uint32_t w = 0; w < P.lane_words; w++) RW(w) = 0;     // plane 0 is the ready queue: RW spans all planes
+    else PCOLD_FOR(w, 0, lane_words) RW(w) = 0;     // plane 0 is the ready queue: RW spans all planes
     if (K::DEDUP) { for (uint32_t b = 0; b < P.dedup_n; b++) gs_store32(c.gs, gs_addr_uword(c, P.dedup_off + b * 16u + 12u), 0); L.hazard = 0; L.dd_occ = 0; }   // empty buckets
-    for (uint32_t t = 0; t < P.max_tasks; t++) { TWORD(c, t, 0, 0) = 0; if (!K::LIFE) TWORD(c, t, 1, 1) = 0; }
+    PCOLD_FOR(t, 0, max_tasks) { TWORD(c, t, 0, 0) = 0; if (!K::LIFE) TWORD(c, t, 1, 1) = 0; }
     if (K::FA && P.ipvs_dyn)                               // the services as the table declares them: the ipvs calls made before the first task runs
         for (uint32_t k = 0; k < P.n_services; k++) {
             const uint32_t w0 = SMEM[c.nodet0 + P.svc_off + 2 * k], w1 = SMEM[c.nodet0 + P.svc_off + 2 * k + 1];
@@ -32,7 +32,7 @@ __device__ __forceinline__ void seed_init(const Ctx& c, Lane& L, uint64_t seed) 
     L.peek = rng_out(L);                                   // (k_rng.h Peek: the first with() has no log entry before it)
     L.rng_calls = 0; L.clock = 0; L.msg_count = 0; L.steps = 0;
     L.pq_n = 0; L.ready_len = 0; L.rq = 0; L.heap_len = 0; L.top_dl = ~0ull; L.top_meta = 0; L.verdict = MADSIM_RUNNING; L.ovf = 0; L.main_done = 0;
-    L.loss_pint = P.loss_pint; L.loss_always = P.loss_always;
+    L.loss_pint = PCOLD(loss_pint); L.loss_always = PCOLD(loss_always);
     // TimeRuntime::new (time/mod.rs:26-38): base_time draw, before logging is enabled
     L.clock_fold = 0;                                      // (the fold of clock 0: the draw's log entry is discarded, the first pass folds again — k_rng.h ClockFold)
     { uint64_t h = L.trace_hash, n = L.log_len; uint32_t bt = gen_range_small<Variant<false, false, K::LWS, 0, K::RQ>, 31536000u>(c, L); L.trace_hash = h; L.log_len = n;
@@ -40,7 +40,7 @@ __device__ __forceinline__ void seed_init(const Ctx& c, Lane& L, uint64_t seed) 
     L.trace_hash = FNV_OFFSET; L.obs_hash = FNV_OFFSET; L.log_len = 0;
     if (K::TRACE) L.obs_len = 0;
     // tasks spawned before block_on, then the main task (task/mod.rs:222-235)
-    for (uint32_t p = 1; p < P.n_progs; p++) {
+    PCOLD_FOR(p, 1, n_progs) {
         uint32_t fl = (PROGW(c, p) >> 8) & 0xff;
         if (fl & MADSIM_PROG_PRE) spawn_task<K>(c, L, p, !(fl & MADSIM_PROG_INIT));
     }
@@ -72,6 +72,8 @@ template <class K> struct PopOne { static constexpr bool ON = MADSIM_POP_ONE && 
 
 template <class K>
 __global__ __launch_bounds__(256, K::CMP ? 4 : !K::G ? 1 : (K::FEAT & (MADSIM_FEAT_ALL & ~MADSIM_FEAT_ADDR)) == (MADSIM_FEAT_ALL & ~MADSIM_FEAT_ADDR) ? MADSIM_ALLG_WAVES_PER_EU : MADSIM_G_WAVES_PER_EU) void sim_kernel(const KParams P) {
+    // PCOLD (k_state.h) reads fields of P at their offsets in the kernel-argument segment: P is the only explicit argument, so it begins the segment
+    static_assert(std::is_same<decltype(&sim_kernel<K>), void (*)(KParams)>::value && std::is_trivially_copyable<KParams>::value, "PCOLD: KParams by value, alone");
     const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     // workgroup-shared tables
     uint32_t* sh = SMEM;
@@ -93,6 +95,7 @@ __global__ __launch_bounds__(256, K::CMP ? 4 : !K::G ? 1 : (K::FEAT & (MADSIM_FE
     else if (K::CMP) { c.heap0 = (P.sh_heap + wbase) / 2 + lane; c.heapm0 = 0; }        // 8-byte entries 1 .. heap_lds - 1 (entry 0: registers)
     else { c.heap0 = (P.sh_heap + wbase) / 2 + lane; c.heapm0 = P.sh_heap + wbase + ((P.heap_lds * 2) << P.lw_shift) + lane; }
     c.lws = P.lw_shift;
+    c.uflags = ColdParams<K>::ON ? uflags_word(P) : 0u;
     const uint32_t pl = P.sh_planes + wbase + lane;
     c.ready0 = pl + (P.off_ready << P.lw_shift);
     c.amask0 = pl + (P.off_amask << P.lw_shift);
@@ -148,23 +151,24 @@ __global__ __launch_bounds__(256, K::CMP ? 4 : !K::G ? 1 : (K::FEAT & (MADSIM_FE
     uint32_t pass_est = (K::TRACE || !P.iter_est) ? 0u : wave_uniform(*P.iter_est);
     uint32_t pass = 0;
     for (;;) {
-        if (!K::TRACE && P.iter_est) {
+        // (base-op builds: the pass counter first, the pointer from the kernel-argument segment on every 16th pass — k_state.h PCOLD)
+        if (!K::TRACE && (ColdParams<K>::ON || P.iter_est)) {
             const uint32_t pu = wave_uniform(pass);
-            if ((pu & MADSIM_PRIO_EVERY_MASK) == 0) {
+            if ((pu & MADSIM_PRIO_EVERY_MASK) == 0 && (!ColdParams<K>::ON || PCOLD(iter_est))) {
                 // (the first launches of a workload start without an estimate: they look again until a wave has finished — the drain, where
                 //  the priorities matter, comes after that)
-                if (!pass_est && (pu & 63u) == 0) pass_est = wave_uniform(__atomic_load_n(P.iter_est, __ATOMIC_RELAXED));
+                if (!pass_est && (pu & 63u) == 0) pass_est = wave_uniform(__atomic_load_n(PCOLD(iter_est), __ATOMIC_RELAXED));
                 if (pass_est) wave_set_priority(progress_priority(pu, pass_est));
             }
         }
         pass++;
         if (!have) {
-            if (next >= P.count) break;
+            if (next >= PCOLD(count)) break;
             if (K::TRACE) {                               // this unit's rows of the two logs (next < count: inside what the host sized)
                 c.tlog = P.trace_log + next * P.trace_cap;
                 c.olog = (P.obs_log && P.obs_cap) ? P.obs_log + next * P.obs_cap : nullptr;
             }
-            seed_init<K>(c, L, P.seed_list ? P.seed_list[next] : P.seed0 + next);
+            { const uint64_t* const sl = PCOLD(seed_list); seed_init<K>(c, L, sl ? sl[next] : PCOLD(seed0) + next); }
             have = true;
         }
         // One iteration = one pass of the block_on loop body (task/mod.rs:239-259):
@@ -298,25 +302,25 @@ __global__ __launch_bounds__(256, K::CMP ? 4 : !K::G ? 1 : (K::FEAT & (MADSIM_FE
             r.verdict = L.verdict; r.steps = L.steps; r.clock_ns = L.clock; r.msg_count = L.msg_count;
             r.rng_calls = L.rng_calls; r.trace_hash = (K::NOLOG || (K::LOGSW && P.no_log)) ? 0 : L.trace_hash; r.obs_hash = L.obs_hash;
             if (r.verdict >= MADSIM_UNSUPPORTED) { r.steps = 0; r.clock_ns = 0; r.msg_count = 0; r.rng_calls = 0; r.trace_hash = 0; r.obs_hash = 0; }   // the verdict is the whole answer
-            P.out[next] = r;
+            PCOLD(out)[next] = r;
             if (K::TRACE) { P.trace_len[next] = L.log_len; if (P.obs_len) P.obs_len[next] = L.obs_len; }
             have = false;
             if (K::DEDUP) L.exact = 0;
             // next unit: static striding, or the per-launch work queue (a lane whose seeds end early — deadlocks under
             // packet loss — then keeps pulling work instead of idling behind the slowest lane of its stride)
-            if (P.work_ctr) next = P.total_lanes + atomicAdd(P.work_ctr, 1ull);
-            else next += P.total_lanes / EXP_LANE_DIV;
+            if (unsigned long long* const wc = PCOLD(work_ctr)) next = PCOLD(total_lanes) + atomicAdd(wc, 1ull);
+            else next += PCOLD(total_lanes) / EXP_LANE_DIV;
         }
     }
     // the estimate = the longest wave of this (workload, launch shape) so far: the maximum over the wave's lanes (lane 0 may have left long
     // before the others when seeds differ in length or come from the work queue), one atomic per wave into the word the host keyed by
     // workload, limits and seeds per lane (madsim_hip.cpp upload_workload)
     // (the base-op builds — every seed of theirs runs the same program at nearly the same pace — keep round 5's form: lane 0's own count)
-    if (!K::TRACE && P.iter_est) {
+    if (!K::TRACE && PCOLD(iter_est)) {
         if (K::LIFE) {
             const uint32_t wmax = wave_max_u32(pass);
             if (wave_first_lane() && wmax > 16) atomic_max_u32(P.iter_est, wmax);
-        } else if (lane == 0 && pass > 16) *P.iter_est = pass;
+        } else if (lane == 0 && pass > 16) *PCOLD(iter_est) = pass;
     }
 #ifdef MADSIM_K_PROF
     PROBE2(0);

@@ -15,7 +15,7 @@ __device__ __forceinline__ uint64_t sleep_deadline(const Lane& L, uint64_t deadl
 template <class K>
 __device__ __forceinline__ uint64_t rand_delay_deadline(const Ctx& c, Lane& L) {
     uint64_t delay = (uint64_t)gen_range_small<K, 5>(c, L) * 1000ull;
-    if (c.P.buggify) {
+    if (uflag<K>(c, c.P.buggify, UF_BUGGIFY)) {
         if (gen_bool_pint<K>(c, L, c.P.bug_pint, 0)) delay = (uint64_t)(1 + gen_range_small<K, 4>(c, L)) * NS_PER_S;
     }
     return sleep_deadline(L, L.clock + delay);
@@ -126,7 +126,9 @@ __device__ __forceinline__ bool poll_task(const Ctx& c, Lane& L, const uint32_t 
     const KParams& P = c.P;
     // a full registration list: short of the ceiling of 255 a larger mbox_regs lifts it (a capacity verdict, the seed is run again); AT the ceiling the
     // 256th registration leaves the workload model — the oracle's Vec holds the same registrations, it says MADSIM_UNSUPPORTED at the same receive
-    const uint32_t REGS_FULL = P.mbox_regs >= MADSIM_MAX_MBOX_REGS ? (uint32_t)OVF_MODEL : (uint32_t)OVF_CAP;
+    // (base-op builds read the limit again on that side — k_state.h PCOLD — instead of carrying the code through every pass)
+    const uint32_t regs_full_hot = P.mbox_regs >= MADSIM_MAX_MBOX_REGS ? (uint32_t)OVF_MODEL : (uint32_t)OVF_CAP;
+#define REGS_FULL (ColdParams<K>::ON ? (PCOLD(mbox_regs) >= MADSIM_MAX_MBOX_REGS ? (uint32_t)OVF_MODEL : (uint32_t)OVF_CAP) : regs_full_hot)
     bool u1_dirty = false;
     uint32_t pc = u0.y & 0xffff, sub = (u0.y >> 16) & 0xff, from = u0.y >> 24;
     const uint32_t gen = (u0.x >> 8) & 0xffff;
@@ -894,7 +896,7 @@ __device__ __forceinline__ bool poll_task(const Ctx& c, Lane& L, const uint32_t 
                 pc++;
                 break;
             case MS_OP_BUILD:
-                for (uint32_t p = 1; p < P.n_progs; p++) {
+                PCOLD_FOR(p, 1, n_progs) {
                     uint32_t pw = PROGW(c, p);
                     if ((pw & 0xff) == a && ((pw >> 8) & MADSIM_PROG_INIT) && !((pw >> 8) & MADSIM_PROG_PRE)) spawn_task<K>(c, L, p, false);
                 }
@@ -1230,6 +1232,7 @@ __device__ __forceinline__ bool poll_task(const Ctx& c, Lane& L, const uint32_t 
     return st == ST_PANIC;
 }
 #undef RX_DROP
+#undef REGS_FULL
 #undef SCOPE_DROP_CONN
 
 }  // namespace madsim_k

@@ -98,6 +98,41 @@ template <bool TRACE_, bool SPILL_, int LWS_, int FEAT_, bool RQ_ = false, bool 
     static constexpr bool FSIG = (FEAT_ & MADSIM_FEAT_SIGNAL) != 0;
 };
 
+// Cold launch parameters (sim_kernel.h MADSIM_COLD_PARAMS): PCOLD(f) is KParams field f, read where it is used.  KParams is passed by value, so every
+// field the kernel mentions is pulled into scalar registers at entry and held there; the base-op builds then need more than a wave has, and
+// the allocator parks what the pass loop reads in the lanes of a vector register.  The kernel-argument segment is memory the wave can read at any time:
+// a cold field becomes one s_load at its use.  The block is sim_kernel's only explicit argument, so it begins at offset 0 of the segment
+// (k_main.h asserts the signature), and every launch reads its own.  The pointer is made opaque per use: the load stays where the use is
+// instead of being hoisted back out of the pass loop.  (`P` must be in scope at the use; the host-compiled kernel reads P.f.)
+#ifdef MADSIM_EMU
+template <class K> struct ColdParams { static constexpr bool ON = false; };
+#define PCOLD(f) (P.f)
+#else
+template <class K> struct ColdParams { static constexpr bool ON = MADSIM_COLD_PARAMS && !K::LIFE; };
+template <bool ON, class T> __device__ __forceinline__ T cold_read(const T& hot, uint32_t off) {
+    if constexpr (ON) {
+        typedef const char __attribute__((address_space(4)))* seg_t;      // (constant address space: a scalar load; a generic pointer would be a flat_load through VGPRs)
+        seg_t p = (seg_t)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(p));
+        return *(const T __attribute__((address_space(4)))*)(p + off);
+    } else return hot;
+}
+#define PCOLD(f) cold_read<ColdParams<K>::ON>(P.f, (uint32_t)offsetof(KParams, f))
+#endif
+// for (i = start; i < P.f; i++) with a cold bound: read once where the loop begins in the builds with cold parameters, the loop as it was written in the others
+#define PCOLD_FOR(i_, start_, f_) for (uint32_t i_ = (start_), i_##_n = ColdParams<K>::ON ? PCOLD(f_) : 0u; i_ < (ColdParams<K>::ON ? i_##_n : P.f_); i_++)
+// Wave-uniform yes/no parameters tested on the send path (has_clog, has_clog_link, buggify): held by value each is a 64-bit lane mask; the builds with
+// cold parameters keep the three as bits of ONE scalar word (Ctx::uflags, made opaque where the kernel begins so that it stays one word) and test a bit.
+enum : uint32_t { UF_CLOG = 1, UF_CLOG_LINK = 2, UF_BUGGIFY = 4 };
+__device__ __forceinline__ uint32_t uflags_word(const KParams& P) {
+    uint32_t f = (P.has_clog ? (uint32_t)UF_CLOG : 0u) | (P.has_clog_link ? (uint32_t)UF_CLOG_LINK : 0u) | (P.buggify ? (uint32_t)UF_BUGGIFY : 0u);
+#ifndef MADSIM_EMU
+    f = wave_uniform(f);
+    asm volatile("" : "+s"(f));
+#endif
+    return f;
+}
+
 // REG(id): divergence-model markers, compiled in only by tools/divergence_model.py's host emulation build
 #ifndef REG
 #define REG(id) do { } while (0)
@@ -193,9 +228,20 @@ struct Ctx {
     uint32_t pmask0;     // Variant::NH: word index of the delivery-record pool's used mask (bit r of word r / 32 = record r holds a message in flight)
     uint8_t* tlog;       // trace mode only: the current unit's row of the determinism log
     uint64_t* olog;      // trace mode only: the current unit's row of the observation log (null: none kept)
+    uint32_t uflags;     // builds with cold parameters: UF_* (uflags_word), wave-uniform; 0 and unread in the others (set where the kernel begins)
     __device__ Ctx(const KParams& p) : P(p) {}
 };
 
+template <class K> __device__ __forceinline__ bool uflag(const Ctx& c, uint32_t hot, uint32_t bit) {
+#ifndef MADSIM_EMU
+    if constexpr (ColdParams<K>::ON) {
+        uint32_t f = c.uflags;
+        asm volatile("" : "+s"(f));           // (opaque per use: the test stays a bit test of one word here instead of a lane mask made where the kernel begins)
+        return (f & bit) != 0;
+    } else
+#endif
+    return hot != 0;
+}
 template <class K> __device__ __forceinline__ uint32_t LWSH(const Ctx& c) { return K::LWS >= 0 ? (uint32_t)K::LWS : c.lws; }
 #define RW(i) SMEM[c.ready0 + ((i) << LWSH<K>(c))]
 // Entry i of the ready Vec (a task slot).  LDS-resident builds: one plane word per entry.  Global-state builds, where the
@@ -262,24 +308,35 @@ template <> struct URef<true> {
 };
 // Compact base-op builds: task slot 0 (the main task) lives in global memory, the other slots in LDS.  `glob` is rarely true
 // (the main task is polled a handful of times per run), so the global side sits behind a branch that whole waves skip.
-struct HWRef {
-    BufRef gs; uint32_t at; bool glob;   // at: LDS word index, or byte offset in the main-task buffer
-    __device__ __forceinline__ operator uint32_t() const { uint32_t v; if (glob) v = gs_load32(gs, at); else v = SMEM[at]; return v; }
-    __device__ __forceinline__ uint32_t operator=(uint32_t v) const { if (glob) gs_store32(gs, at, v); else SMEM[at] = v; return v; }
+// COLD (k_state.h ColdParams): the reference carries no buffer descriptor; the global side builds it from the kernel-argument segment where
+// it is used (main_task_buf), so its four scalars are not held through the pass loop for a task that is polled a handful of times per seed.
+struct NoBuf { };
+template <bool COLD> struct MainBuf { typedef BufRef T; static __device__ __forceinline__ const BufRef& get(const BufRef& b) { return b; } };
+#ifndef MADSIM_EMU
+__device__ __forceinline__ BufRef main_task_buf() {
+    return buf_make(cold_read<true, uint8_t*>(nullptr, (uint32_t)offsetof(KParams, gstate)),
+                    (uint64_t)cold_read<true, uint32_t>(0u, (uint32_t)offsetof(KParams, gs_stride)) * cold_read<true, uint32_t>(0u, (uint32_t)offsetof(KParams, total_lanes)));
+}
+template <> struct MainBuf<true> { typedef NoBuf T; static __device__ __forceinline__ BufRef get(const NoBuf&) { return main_task_buf(); } };
+#endif
+template <bool COLD> struct HWRef {
+    typename MainBuf<COLD>::T gs; uint32_t at; bool glob;   // at: LDS word index, or byte offset in the main-task buffer
+    __device__ __forceinline__ operator uint32_t() const { uint32_t v; if (glob) v = gs_load32(MainBuf<COLD>::get(gs), at); else v = SMEM[at]; return v; }
+    __device__ __forceinline__ uint32_t operator=(uint32_t v) const { if (glob) gs_store32(MainBuf<COLD>::get(gs), at, v); else SMEM[at] = v; return v; }
     __device__ __forceinline__ uint32_t operator=(const HWRef& o) const { return *this = (uint32_t)o; }
     __device__ __forceinline__ uint32_t operator|=(uint32_t v) const { return *this = (uint32_t)*this | v; }
     __device__ __forceinline__ uint32_t operator&=(uint32_t v) const { return *this = (uint32_t)*this & v; }
     __device__ __forceinline__ uint32_t operator+=(uint32_t v) const { return *this = (uint32_t)*this + v; }
 };
-struct HURef {
-    BufRef gs; uint32_t at; bool glob;   // at: LDS uint4 index, or byte offset in the main-task buffer
-    __device__ __forceinline__ operator uint4() const { uint4 v; if (glob) v = gs_load128(gs, at); else v = LDS128(at); return v; }
-    __device__ __forceinline__ void operator=(const uint4& v) const { if (glob) gs_store128(gs, at, v); else LDS128(at) = v; }
+template <bool COLD> struct HURef {
+    typename MainBuf<COLD>::T gs; uint32_t at; bool glob;   // at: LDS uint4 index, or byte offset in the main-task buffer
+    __device__ __forceinline__ operator uint4() const { uint4 v; if (glob) v = gs_load128(MainBuf<COLD>::get(gs), at); else v = LDS128(at); return v; }
+    __device__ __forceinline__ void operator=(const uint4& v) const { if (glob) gs_store128(MainBuf<COLD>::get(gs), at, v); else LDS128(at) = v; }
     __device__ __forceinline__ void operator=(const HURef& o) const { *this = (uint4)o; }
 };
 template <class K> struct TaskRef {      // what TU / TWORD / HW hand out
-    typedef typename std::conditional<K::CMP, HURef, URef<K::G>>::type U;
-    typedef typename std::conditional<K::CMP, HWRef, WRef<K::G>>::type W;
+    typedef typename std::conditional<K::CMP, HURef<ColdParams<K>::ON>, URef<K::G>>::type U;
+    typedef typename std::conditional<K::CMP, HWRef<ColdParams<K>::ON>, WRef<K::G>>::type W;
 };
 template <bool G> __device__ __forceinline__ WRef<G> make_wref(const Ctx& c, uint32_t lds_at, uint32_t gs_at);
 template <> __device__ __forceinline__ WRef<false> make_wref<false>(const Ctx&, uint32_t lds_at, uint32_t) { return WRef<false>{lds_at}; }
@@ -364,24 +421,27 @@ template <class K> __device__ __forceinline__ WRef<K::G> tword_ref_plain(const C
     if (K::G) return tword_gs2<K::G>(c, slot, u, k);
     return make_wref<K::G>(c, (c.task0 + ((slot * c.P.task_units + u) << LWSH<K>(c))) * 4u + k, 0);
 }
+template <class K> __device__ __forceinline__ typename MainBuf<ColdParams<K>::ON>::T main_buf_of(const Ctx& c) {
+    if constexpr (ColdParams<K>::ON) return NoBuf{}; else return c.gs;
+}
 // Compact builds: the main task's record in the global buffer is unit0 at [lane * 16], then unit1 {x, y} at
 // [total_lanes * 16 + lane * 8]; c.task0 / c.task1 are biased so that slot s >= 1 indexes LDS entry s - 1.
 template <class K> __device__ __forceinline__ typename TaskRef<K>::U tu_ref(const Ctx& c, uint32_t slot, uint32_t u) {
-    if constexpr (K::CMP) return HURef{c.gs, slot == 0 ? c.gs_lane * 16u : c.task0 + (slot << LWSH<K>(c)), slot == 0};
+    if constexpr (K::CMP) return HURef<ColdParams<K>::ON>{main_buf_of<K>(c), slot == 0 ? c.gs_lane * 16u : c.task0 + (slot << LWSH<K>(c)), slot == 0};
     else return tu_ref_plain<K>(c, slot, u);
 }
 template <class K> __device__ __forceinline__ typename TaskRef<K>::W tword_ref(const Ctx& c, uint32_t slot, uint32_t u, uint32_t k) {
     if constexpr (K::CMP) {
         const uint32_t lds = u == 0 ? (c.task0 + (slot << LWSH<K>(c))) * 4u + k : (c.task1 + (slot << LWSH<K>(c))) * 2u + k;
         const uint32_t glb = u == 0 ? c.gs_lane * 16u + k * 4u : c.P.total_lanes * 16u + c.gs_lane * 8u + k * 4u;
-        return HWRef{c.gs, slot == 0 ? glb : lds, slot == 0};
+        return HWRef<ColdParams<K>::ON>{main_buf_of<K>(c), slot == 0 ? glb : lds, slot == 0};
     } else return tword_ref_plain<K>(c, slot, u, k);
 }
 // unit1 as a uint4 in registers; base-op builds hold {x, y} only
 template <class K> __device__ __forceinline__ uint4 load_u1(const Ctx& c, uint32_t slot) {
     if (K::LIFE) return tu_ref<K>(c, slot, 1);
     uint2 t;
-    if (K::CMP && slot == 0) t = buf_load64(c.gs, c.P.total_lanes * 16u + c.gs_lane * 8u);
+    if (K::CMP && slot == 0) { const KParams& P = c.P; t = buf_load64(MainBuf<ColdParams<K>::ON>::get(main_buf_of<K>(c)), PCOLD(total_lanes) * 16u + c.gs_lane * 8u); }
     else t = LDS64(c.task1 + (slot << LWSH<K>(c)));
     return make_uint4(t.x, t.y, 0, 0);
 }

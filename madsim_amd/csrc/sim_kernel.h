@@ -72,6 +72,12 @@
 #ifndef MADSIM_POP_ONE
 #define MADSIM_POP_ONE 1
 #endif
+/* Base-op builds: launch parameters that are read once per seed, once per many passes or on rare sides only are loaded from the kernel-argument
+   segment where they are used (k_state.h ColdParams / PCOLD) instead of being held in scalar registers for the wave's whole life, where they pushed
+   values the pass loop reads through spill lanes (v_readlane_b32 inside the loop). */
+#ifndef MADSIM_COLD_PARAMS
+#define MADSIM_COLD_PARAMS 1
+#endif
 /* MADSIM_STATE_DEDUP_TIMERS builds: the occupancy of the re-registration table mirrored in a register (k_timer.h dedup_note). */
 #ifndef MADSIM_DEDUP_OCC
 #define MADSIM_DEDUP_OCC 1

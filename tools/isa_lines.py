@@ -2,7 +2,8 @@
 """Static instruction budget of one sim_kernel build by SOURCE LINE (no GPU needed).
 
 Compiles sim_kernel.hip for ONE variant with line tables, reads the `.loc` directives of the assembly and counts, per source line,
-the VALU / SALU / LDS / VMEM / branch instructions the compiler made of it.  A wave executes every line some lane of it reaches, so for
+the VALU / SALU / LDS / VMEM / branch instructions the compiler made of it — and, as a class of their own beside their VALU count, the lane
+reads and writes of scalars the register allocator spilled to a vector register (lane_rd / lane_wr), by source line and by site.  A wave executes every line some lane of it reaches, so for
 the straight-line part of a pass (everything but the rejection loops) the static count IS the per-pass cost; loops count once here.
 
     python tools/isa_lines.py ['X(false,false,6,MADSIM_FEAT_COMPACT,true,false)'] [top=45] [extra hipcc flags, e.g. -DMADSIM_POP_ONE=0 ...]
@@ -19,6 +20,9 @@ files, cur, in_kernel = {}, None, False
 cnt = collections.defaultdict(lambda: collections.Counter())
 tot = collections.Counter()
 site_cnt = collections.defaultdict(lambda: collections.Counter()); cur_site = None
+# the vector registers that hold spilled scalars: written with v_writelane_b32 from an SGPR at a constant lane (a wave reduction reads lanes it
+# never wrote this way, and is not counted)
+lane_vgprs = set(re.findall(r"^\s*v_writelane_b32 (v\d+), s\d+, \d+\s*(?:;.*)?$", open(out).read(), re.M))
 for ln in open(out):
     s = ln.strip()
     m = re.match(r'\.file\s+(\d+)\s+"([^"]*)"\s+"([^"]*)"', s)
@@ -43,11 +47,19 @@ for ln in open(out):
     if not in_kernel or not s or s.startswith((".", ";", "//")) or s.endswith(":"):
         continue
     op = s.split()[0]
+    if op in ("v_readlane_b32", "v_writelane_b32"):
+        # a class of its own beside its VALU count: reloads / parks of scalars the allocator spilled to the lanes of a vector register
+        m = re.match(r"v_(read|write)lane_b32 (\w+), (\w+), (\d+)$", s.split(";")[0].strip())
+        if m and (m.group(3) if m.group(1) == "read" else m.group(2)) in lane_vgprs:
+            lk = "lane_rd" if m.group(1) == "read" else "lane_wr"
+            cnt[cur][lk] += 1; tot[lk] += 1
+            if cur_site: site_cnt[cur_site][lk] += 1
     k = "branch" if op.startswith(("s_cbranch", "s_branch")) else "valu" if op.startswith("v_") else "lds" if op.startswith("ds_") else \
         "vmem" if op.startswith(("buffer_", "global_", "flat_", "scratch_")) else "wait" if op.startswith(("s_waitcnt", "s_nop")) else "salu" if op.startswith("s_") else "other"
     cnt[cur][k] += 1; tot[k] += 1
     if cur_site: site_cnt[cur_site][k] += 1
 print(f"variant {var}: {dict(tot)}")
+print(f"spilled scalars: {tot['lane_wr']} lane writes, {tot['lane_rd']} lane reads (v_writelane_b32 / v_readlane_b32 of {sorted(lane_vgprs) or 'no register'})")
 src = {}
 def text(f, l):
     p = files.get(f, "?")
@@ -68,6 +80,15 @@ for (f, l), c in sorted(cnt.items(), key=lambda kv: -(kv[1]["valu"] + kv[1]["sal
     w, t = text(f, l)
     print(f"  {w:18s} valu {c['valu']:4d} salu {c['salu']:4d} br {c['branch']:3d} lds {c['lds']:3d} | {t}")
 
+if tot["lane_rd"]:
+    print("lane reads of spilled scalars by source line:")
+    for (f, l), c in sorted(cnt.items(), key=lambda kv: -kv[1]["lane_rd"]):
+        if c["lane_rd"]:
+            w, t = text(f, l)
+            print(f"  {w:18s} lane_rd {c['lane_rd']:3d} lane_wr {c['lane_wr']:3d} | {t}")
+    print("lane reads of spilled scalars by site:")
+    for (b, l), c in sorted(site_cnt.items(), key=lambda kv: -kv[1]["lane_rd"]):
+        if c["lane_rd"]: print(f"  {b + ':' + str(l):16s} lane_rd {c['lane_rd']:3d} lane_wr {c['lane_wr']:3d}")
 print(f"top {top} sites (the line of k_poll.h / k_main.h whose inlined callees the instructions belong to):")
 def stext(b, l):
     p2 = os.path.join(ROOT, "madsim_amd", "csrc", "kernel", b)
