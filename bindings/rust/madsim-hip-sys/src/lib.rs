@@ -233,6 +233,27 @@ pub struct madsim_probe_order_t {
 
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
+pub struct madsim_stall_census_t {
+    pub include: u32,
+    pub task_cap: u32,
+    pub sites: *const madsim_census_value_t,
+    pub site_cap: u64,
+    pub shapes: *const madsim_census_value_t,
+    pub shape_cap: u64,
+    pub runner_seeds: *const u64,
+    pub runner_cap: u64,
+    pub n_sites: u64,
+    pub n_shapes: u64,
+    pub n_counted: [u64; 4],
+    pub n_idle: [u64; 4],
+    pub n_truncated: u64,
+    pub n_tasks: u64,
+    pub n_runner: u64,
+    pub n_runner_listed: u64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
 pub struct madsim_campaign_t {
     pub seeds_run: u64,
     pub batches_run: u64,
@@ -549,6 +570,10 @@ pub const MADSIM_E_NOINIT: c_int = -3;
 pub const MADSIM_E_WORKLOAD: c_int = -4;
 pub const MADSIM_E_LIMITS: c_int = -5;
 pub const MADSIM_TRACE_MAX_BYTES: u32 = 1073741824;
+pub const MADSIM_TASK_PARKED: u32 = 1;
+pub const MADSIM_TASK_QUEUED: u32 = 2;
+pub const MADSIM_TASK_PANICKED: u32 = 3;
+pub const MADSIM_TASK_CANCELLED: u32 = 4;
 pub const MADSIM_DIVERGE_SAME: u32 = 0;
 pub const MADSIM_DIVERGE_DIFFER: u32 = 1;
 pub const MADSIM_DIVERGE_PREFIX: u32 = 2;
@@ -625,6 +650,8 @@ extern "C" {
     pub fn madsim_hip_trace_seed(w: *const madsim_workload_t, cfg: *const madsim_config_t, seed: u64, lim: *const madsim_limits_t, log: *mut u8, cap: u64, out: *mut madsim_result_t) -> i64;
     pub fn madsim_hip_trace_seeds(w: *const madsim_workload_t, cfg: *const madsim_config_t, seeds: *const u64, n: u64, lim: *const madsim_limits_t, logs: *mut u8, log_cap: u64, obs: *mut u64, obs_cap: u64, log_len: *mut u64, obs_len: *mut u64, out: *mut madsim_result_t) -> c_int;
     pub fn madsim_hip_observe_seed(w: *const madsim_workload_t, cfg: *const madsim_config_t, seed: u64, lim: *const madsim_limits_t, obs: *mut u64, cap: u64, out: *mut madsim_result_t) -> i64;
+    pub fn madsim_hip_task_states(w: *const madsim_workload_t, cfg: *const madsim_config_t, seeds: *const u64, n: u64, lim: *const madsim_limits_t, tasks: *mut u64, task_cap: u64, task_len: *mut u64, out: *mut madsim_result_t) -> c_int;
+    pub fn madsim_hip_stall_shape(tasks: *const u64, n: u64) -> u64;
     pub fn madsim_hip_diverge_seeds(wA: *const madsim_workload_t, cfgA: *const madsim_config_t, limA: *const madsim_limits_t, wB: *const madsim_workload_t, cfgB: *const madsim_config_t, limB: *const madsim_limits_t, seeds: *const u64, n: u64, log_cap: u64, obs_cap: u64, win: u32, recs: *mut madsim_divergence_t, obs_ctx: *mut u64) -> c_int;
     pub fn madsim_hip_census_range(w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, chunk: u64, lim: *const madsim_limits_t, cen: *mut madsim_census_t) -> c_int;
     pub fn madsim_hip_census_seeds(w: *const madsim_workload_t, cfg: *const madsim_config_t, seeds: *const u64, n: u64, chunk: u64, lim: *const madsim_limits_t, cen: *mut madsim_census_t) -> c_int;
@@ -632,6 +659,8 @@ extern "C" {
     pub fn madsim_hip_probe_sets_seeds(w: *const madsim_workload_t, cfg: *const madsim_config_t, seeds: *const u64, n: u64, chunk: u64, lim: *const madsim_limits_t, ps: *mut madsim_probe_sets_t) -> c_int;
     pub fn madsim_hip_probe_order_range(w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, chunk: u64, lim: *const madsim_limits_t, po: *mut madsim_probe_order_t) -> c_int;
     pub fn madsim_hip_probe_order_seeds(w: *const madsim_workload_t, cfg: *const madsim_config_t, seeds: *const u64, n: u64, chunk: u64, lim: *const madsim_limits_t, po: *mut madsim_probe_order_t) -> c_int;
+    pub fn madsim_hip_stall_census_range(w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, chunk: u64, lim: *const madsim_limits_t, sc: *mut madsim_stall_census_t) -> c_int;
+    pub fn madsim_hip_stall_census_seeds(w: *const madsim_workload_t, cfg: *const madsim_config_t, seeds: *const u64, n: u64, chunk: u64, lim: *const madsim_limits_t, sc: *mut madsim_stall_census_t) -> c_int;
     pub fn madsim_hip_ctx_run_batch(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, count: u64, lim: *const madsim_limits_t, out: *mut madsim_result_t, summary: *mut madsim_summary_t) -> c_int;
     pub fn madsim_hip_ctx_run_batch_auto(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, count: u64, lim: *const madsim_limits_t, out: *mut madsim_result_t, summary: *mut madsim_summary_t, max_rounds: c_int) -> c_int;
     pub fn madsim_hip_ctx_run_batch_device(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, count: u64, lim: *const madsim_limits_t, d_out: *mut c_void, stream: *mut c_void, summary: *mut madsim_summary_t) -> c_int;
@@ -640,6 +669,7 @@ extern "C" {
     pub fn madsim_hip_ctx_trace_seed(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed: u64, lim: *const madsim_limits_t, log: *mut u8, cap: u64, out: *mut madsim_result_t) -> i64;
     pub fn madsim_hip_ctx_trace_seeds(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seeds: *const u64, n: u64, lim: *const madsim_limits_t, logs: *mut u8, log_cap: u64, obs: *mut u64, obs_cap: u64, log_len: *mut u64, obs_len: *mut u64, out: *mut madsim_result_t) -> c_int;
     pub fn madsim_hip_ctx_observe_seed(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed: u64, lim: *const madsim_limits_t, obs: *mut u64, cap: u64, out: *mut madsim_result_t) -> i64;
+    pub fn madsim_hip_ctx_task_states(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seeds: *const u64, n: u64, lim: *const madsim_limits_t, tasks: *mut u64, task_cap: u64, task_len: *mut u64, out: *mut madsim_result_t) -> c_int;
     pub fn madsim_hip_ctx_diverge_seeds(ctx: *mut madsim_hip_ctx_t, wA: *const madsim_workload_t, cfgA: *const madsim_config_t, limA: *const madsim_limits_t, wB: *const madsim_workload_t, cfgB: *const madsim_config_t, limB: *const madsim_limits_t, seeds: *const u64, n: u64, log_cap: u64, obs_cap: u64, win: u32, recs: *mut madsim_divergence_t, obs_ctx: *mut u64) -> c_int;
     pub fn madsim_hip_ctx_census_range(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, chunk: u64, lim: *const madsim_limits_t, cen: *mut madsim_census_t) -> c_int;
     pub fn madsim_hip_ctx_census_seeds(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seeds: *const u64, n: u64, chunk: u64, lim: *const madsim_limits_t, cen: *mut madsim_census_t) -> c_int;
@@ -647,6 +677,8 @@ extern "C" {
     pub fn madsim_hip_ctx_probe_sets_seeds(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seeds: *const u64, n: u64, chunk: u64, lim: *const madsim_limits_t, ps: *mut madsim_probe_sets_t) -> c_int;
     pub fn madsim_hip_ctx_probe_order_range(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, chunk: u64, lim: *const madsim_limits_t, po: *mut madsim_probe_order_t) -> c_int;
     pub fn madsim_hip_ctx_probe_order_seeds(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seeds: *const u64, n: u64, chunk: u64, lim: *const madsim_limits_t, po: *mut madsim_probe_order_t) -> c_int;
+    pub fn madsim_hip_ctx_stall_census_range(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, chunk: u64, lim: *const madsim_limits_t, sc: *mut madsim_stall_census_t) -> c_int;
+    pub fn madsim_hip_ctx_stall_census_seeds(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seeds: *const u64, n: u64, chunk: u64, lim: *const madsim_limits_t, sc: *mut madsim_stall_census_t) -> c_int;
     pub fn madsim_hip_run_batch_multi(ctxs: *const *mut madsim_hip_ctx_t, n_ctx: c_int, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, count: u64, lim: *const madsim_limits_t, out: *mut madsim_result_t, summary: *mut madsim_summary_t, max_rounds: c_int) -> c_int;
     pub fn madsim_hip_ctx_run_campaign(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, batch: u64, in_flight: u32, flags: u32, lim: *const madsim_limits_t, out: *mut madsim_campaign_t) -> c_int;
     pub fn madsim_hip_run_campaign(w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, batch: u64, in_flight: u32, flags: u32, lim: *const madsim_limits_t, out: *mut madsim_campaign_t) -> c_int;

@@ -308,6 +308,57 @@ impl Census {
     }
 }
 
+/// Where one seed's tasks stand when its run ends (`Builder::post_mortem`): `result`, its 48 bytes; `tasks`, the first `task_cap` records
+/// of the tasks still alive, in task-slot order — bits 63-56 the state (`sys::MADSIM_TASK_PARKED` / `_QUEUED` / `_PANICKED` /
+/// `_CANCELLED`), 55-48 the program, 47-32 the instruction, 31-16 and 15-0 the loop registers —; `n_tasks`, how many there were.  A seed
+/// with a runner verdict has none.
+#[derive(Clone, Debug)]
+pub struct PostMortem {
+    pub seed: u64,
+    pub result: sys::madsim_result_t,
+    pub tasks: Vec<u64>,
+    pub n_tasks: u64,
+}
+
+impl PostMortem {
+    /// (state, program, instruction, loop register 0, loop register 1) of a task record: the header's `MADSIM_TASK_*` accessors.
+    pub fn fields(record: u64) -> (u32, u32, u32, u32, u32) {
+        ((record >> 56) as u32, ((record >> 48) & 0xff) as u32, ((record >> 32) & 0xffff) as u32, ((record >> 16) & 0xffff) as u32, (record & 0xffff) as u32)
+    }
+
+    /// `MADSIM_TASK_SITE`: state | program | instruction, the loop registers dropped — the key of a stall census.
+    pub fn site(record: u64) -> u64 {
+        record >> 32
+    }
+
+    /// The shape word of this table (`madsim_hip_stall_shape`): what matches it against `StallCensus::shapes`.
+    pub fn shape(&self) -> u64 {
+        unsafe { sys::madsim_hip_stall_shape(self.tasks.as_ptr(), self.tasks.len() as u64) }
+    }
+}
+
+/// Where the tasks of a range's seeds stand when their runs end, by verdict (`Builder::stall_census` / `stall_census_seeds`): `sites`,
+/// ascending by site (`PostMortem::site` of a record) — per site the counted seeds of each verdict with at least one task there, the
+/// tasks there, the most inside one seed and the smallest such seed —; `shapes`, ascending by shape word — per distinct multiset of sites
+/// the counted seeds of each verdict and, in `first_seed`, the one to replay —; `totals`, the counts of `madsim_stall_census_t` (its
+/// pointers are null here); `runner_seeds`, the seeds left with a runner verdict, ascending: they are counted nowhere.
+#[derive(Clone, Debug)]
+pub struct StallCensus {
+    pub sites: Vec<sys::madsim_census_value_t>,
+    pub shapes: Vec<sys::madsim_census_value_t>,
+    pub totals: sys::madsim_stall_census_t,
+    pub runner_seeds: Vec<u64>,
+}
+
+impl StallCensus {
+    /// The shapes that counted seeds of `verdict` ended in, the most frequent first.
+    pub fn shapes_of(&self, verdict: usize) -> Vec<sys::madsim_census_value_t> {
+        let mut out: Vec<_> = self.shapes.iter().copied().filter(|e| e.n_seeds[verdict] != 0).collect();
+        out.sort_by(|a, b| b.n_seeds[verdict].cmp(&a.n_seeds[verdict]).then(a.value.cmp(&b.value)));
+        out
+    }
+}
+
 /// Which combinations of the vocabulary's values the seeds reached, by verdict (`Builder::probe_sets` / `probe_sets_seeds`): `vocabulary`,
 /// value `i` owning bit `i` of a set word; `sets`, ascending by set word — per distinct set the counted seeds of each verdict with exactly
 /// this set and the smallest of them —; `totals`, the counts of `madsim_probe_sets_t` (its pointers are null here); `runner_seeds`, the
@@ -732,6 +783,175 @@ impl Builder {
             c.totals.n_runner_listed = more.totals.n_runner_listed;
             c.totals.n_values = merged.len() as u64;
             c.values = merged;
+            c.runner_seeds = more.runner_seeds;
+        }
+        Ok(c)
+    }
+
+    /// Where the tasks of `seeds` stand when their runs end (`madsim_hip_ctx_task_states`): any order, duplicates allowed, the whole list
+    /// in ONE launch of the trace build, one `PostMortem` per seed in the order given.  With `resolve_runner` set, seeds that come back
+    /// with a re-runnable runner verdict are replayed as one further call per round under `madsim_hip_grow_limits(.., r)`.
+    pub fn post_mortem(&self, workload: &Workload, seeds: &[u64], task_cap: usize) -> Result<Vec<PostMortem>, RunError> {
+        let w = workload.raw();
+        let cfg = self.config.raw();
+        let lim0 = self.raw_limits(true);
+        let ctx = contexts()?.0[0];
+        let zero: sys::madsim_result_t = unsafe { std::mem::zeroed() };
+        let mut out: Vec<PostMortem> = seeds.iter().map(|&seed| PostMortem { seed, result: zero, tasks: Vec::new(), n_tasks: 0 }).collect();
+        let mut idx: Vec<usize> = (0..seeds.len()).collect();
+        for r in 0..=self.resolve_rounds() {
+            if idx.is_empty() {
+                break;
+            }
+            let mut lim = lim0;
+            if r > 0 {
+                let rc = unsafe { sys::madsim_hip_grow_limits(&w, &lim0, r, &mut lim) };
+                if rc != 0 {
+                    return Err(last_error(rc));
+                }
+            }
+            let m = idx.len();
+            let s: Vec<u64> = idx.iter().map(|&i| seeds[i]).collect();
+            let (mut rows, mut lens) = (vec![0u64; m * task_cap], vec![0u64; m]);
+            let mut res = vec![zero; m];
+            let rc = unsafe {
+                sys::madsim_hip_ctx_task_states(ctx, &w, &cfg, s.as_ptr(), m as u64, &lim,
+                                                if task_cap > 0 { rows.as_mut_ptr() } else { std::ptr::null_mut() }, task_cap as u64,
+                                                lens.as_mut_ptr(), res.as_mut_ptr())
+            };
+            if rc != 0 {
+                return Err(last_error(rc));
+            }
+            let cap = if lim.max_steps != 0 { lim.max_steps } else { 1 << 24 };
+            let ceiling = if lim.max_steps_ceiling != 0 { lim.max_steps_ceiling } else { 1 << 28 };
+            let mut again = Vec::new();
+            for (j, &i) in idx.iter().enumerate() {
+                let p = &mut out[i];
+                p.result = res[j];
+                p.n_tasks = lens[j];
+                p.tasks = rows[j * task_cap..j * task_cap + (lens[j] as usize).min(task_cap)].to_vec();
+                if res[j].verdict == sys::MADSIM_OVERFLOW || (res[j].verdict == sys::MADSIM_STEP_LIMIT && cap < ceiling) {
+                    again.push(i);
+                }
+            }
+            idx = again;
+        }
+        Ok(out)
+    }
+
+    fn resolve_rounds(&self) -> u32 {
+        if self.resolve_flags & sys::MADSIM_CAMPAIGN_RESOLVE == 0 {
+            return 0;
+        }
+        match (self.resolve_flags & sys::MADSIM_CAMPAIGN_RESOLVE_ROUNDS_MASK) >> sys::MADSIM_CAMPAIGN_RESOLVE_ROUNDS_SHIFT {
+            0 => sys::MADSIM_RESOLVE_DEFAULT_ROUNDS,
+            r => r,
+        }
+    }
+
+    /// Where the tasks of the seeds `self.seed .. self.seed + self.count` stand when their runs end, by verdict
+    /// (`madsim_hip_ctx_stall_census_range`): the range run on the trace build with the task log and reduced on the device to one entry
+    /// per distinct site and one per distinct shape.  A seed is counted when its verdict bit is set in `include` (bits 0-3); its first
+    /// `task_cap` live tasks are visible; more than `max_sites` distinct sites or `max_shapes` distinct shapes is an error
+    /// (`MADSIM_E_LIMITS`; `max_shapes` 0: no shapes pass).  With `resolve_runner` set, the seeds a call leaves with a runner verdict are
+    /// run again in one list call per round and merged in.
+    pub fn stall_census(&self, workload: &Workload, include: u32, task_cap: u32, max_sites: usize, max_shapes: usize) -> Result<StallCensus, RunError> {
+        self.stall_census_over(workload, None, include, task_cap, max_sites, max_shapes)
+    }
+
+    /// `stall_census` over an explicit, strictly ascending seed list (`madsim_hip_ctx_stall_census_seeds`).
+    pub fn stall_census_seeds(&self, workload: &Workload, seeds: &[u64], include: u32, task_cap: u32, max_sites: usize, max_shapes: usize) -> Result<StallCensus, RunError> {
+        self.stall_census_over(workload, Some(seeds), include, task_cap, max_sites, max_shapes)
+    }
+
+    fn stall_census_over(&self, workload: &Workload, seeds: Option<&[u64]>, include: u32, task_cap: u32, max_sites: usize, max_shapes: usize) -> Result<StallCensus, RunError> {
+        let w = workload.raw();
+        let cfg = self.config.raw();
+        let lim0 = self.raw_limits(true);
+        let ctx = contexts()?.0[0];
+        let one = |lim: &sys::madsim_limits_t, list: Option<&[u64]>| -> Result<StallCensus, RunError> {
+            let n = list.map_or(self.count, |l| l.len() as u64);
+            let mut sites: Vec<sys::madsim_census_value_t> = vec![unsafe { std::mem::zeroed() }; max_sites.max(1)];
+            let mut shapes: Vec<sys::madsim_census_value_t> = vec![unsafe { std::mem::zeroed() }; max_shapes.max(1)];
+            let mut runner = vec![0u64; (n as usize).max(1)];
+            let mut sc: sys::madsim_stall_census_t = unsafe { std::mem::zeroed() };
+            sc.include = include;
+            sc.task_cap = task_cap;
+            sc.sites = sites.as_mut_ptr() as *const _;                   // (the library writes through all three)
+            sc.site_cap = max_sites as u64;
+            sc.shapes = if max_shapes > 0 { shapes.as_mut_ptr() as *const _ } else { std::ptr::null() };
+            sc.shape_cap = max_shapes as u64;
+            sc.runner_seeds = runner.as_mut_ptr() as *const _;
+            sc.runner_cap = n;
+            let rc = unsafe {
+                match list {
+                    Some(l) => sys::madsim_hip_ctx_stall_census_seeds(ctx, &w, &cfg, l.as_ptr(), n, 0, lim, &mut sc),
+                    None => sys::madsim_hip_ctx_stall_census_range(ctx, &w, &cfg, self.seed, n, 0, lim, &mut sc),
+                }
+            };
+            if rc != 0 {
+                return Err(last_error(rc));
+            }
+            sites.truncate(sc.n_sites as usize);
+            shapes.truncate(sc.n_shapes as usize);
+            runner.truncate(sc.n_runner_listed as usize);
+            sc.sites = std::ptr::null();
+            sc.shapes = std::ptr::null();
+            sc.runner_seeds = std::ptr::null();
+            Ok(StallCensus { sites, shapes, totals: sc, runner_seeds: runner })
+        };
+        let merge = |into: &[sys::madsim_census_value_t], more: &[sys::madsim_census_value_t]| {
+            let mut merged = Vec::with_capacity(into.len() + more.len());
+            let (mut i, mut j) = (0, 0);
+            while i < into.len() || j < more.len() {
+                if j >= more.len() || (i < into.len() && into[i].value < more[j].value) {
+                    merged.push(into[i]);
+                    i += 1;
+                } else if i >= into.len() || more[j].value < into[i].value {
+                    merged.push(more[j]);
+                    j += 1;
+                } else {
+                    let (mut e, o) = (into[i], more[j]);
+                    for k in 0..4 {
+                        e.n_seeds[k] += o.n_seeds[k];
+                    }
+                    e.n_total += o.n_total;
+                    e.first_seed = e.first_seed.min(o.first_seed);
+                    e.max_per_seed = e.max_per_seed.max(o.max_per_seed);
+                    merged.push(e);
+                    i += 1;
+                    j += 1;
+                }
+            }
+            merged
+        };
+        let mut c = one(&lim0, seeds)?;
+        for r in 1..=self.resolve_rounds() {
+            if c.runner_seeds.is_empty() {
+                break;
+            }
+            let mut lim = lim0;
+            let rc = unsafe { sys::madsim_hip_grow_limits(&w, &lim0, r, &mut lim) };
+            if rc != 0 {
+                return Err(last_error(rc));
+            }
+            let more = one(&lim, Some(&c.runner_seeds))?;
+            let (sites, shapes) = (merge(&c.sites, &more.sites), merge(&c.shapes, &more.shapes));
+            if sites.len() > max_sites || shapes.len() > max_shapes {
+                return Err(RunError { code: sys::MADSIM_E_LIMITS, message: "stall_census: more than max_sites distinct sites or max_shapes distinct shapes once the runner seeds are settled".into() });
+            }
+            for k in 0..4 {
+                c.totals.n_counted[k] += more.totals.n_counted[k];
+                c.totals.n_idle[k] += more.totals.n_idle[k];
+            }
+            c.totals.n_truncated += more.totals.n_truncated;
+            c.totals.n_tasks += more.totals.n_tasks;
+            c.totals.n_runner = more.totals.n_runner;
+            c.totals.n_runner_listed = more.totals.n_runner_listed;
+            c.totals.n_sites = sites.len() as u64;
+            c.totals.n_shapes = shapes.len() as u64;
+            c.sites = sites;
+            c.shapes = shapes;
             c.runner_seeds = more.runner_seeds;
         }
         Ok(c)

@@ -604,6 +604,63 @@ int madsim_hip_trace_seeds(const madsim_workload_t* w, const madsim_config_t* cf
 int64_t madsim_hip_observe_seed(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed,
                                 const madsim_limits_t* lim, uint64_t* obs, uint64_t cap, madsim_result_t* out);
 
+/* Task post-mortems: where the tasks stand when a seed's run ends.  The 48 result bytes say THAT a seed deadlocked, panicked, ran into its
+ * time limit or passed; these calls say which tasks were still alive at that moment and what each was doing — the reference's
+ * RuntimeMetrics::num_tasks_by_node_by_spawn (runtime/metrics.rs, task/mod.rs:497-541), per instruction instead of per spawn site, with no
+ * probe placed in the test body beforehand.  The trace builds keep unit 0 of every live task slot when the result is written: one 64-bit
+ * word per task, never 0 (state >= 1):
+ *   bits 63-56 state   MADSIM_TASK_PARKED     awaiting, not woken
+ *                      MADSIM_TASK_QUEUED     woken and not yet polled: in the ready queue, or held back by a paused node
+ *                      MADSIM_TASK_PANICKED   the task whose poll raised the verdict MADSIM_PANIC
+ *                      MADSIM_TASK_CANCELLED  aborted, or its node killed, and the executor had not yet dropped the runnable (task/mod.rs:269-273
+ *                                             happens at the pop)
+ *   bits 55-48 prog    index into madsim_workload_t's program table
+ *   bits 47-32 pc      index into the workload's instruction array as the caller wrote it: the instruction whose await has not completed;
+ *                      for QUEUED the await that will be polled again, or the program's entry for a task never polled; for PANICKED the
+ *                      panicking instruction
+ *   bits 31-16 cnt0, bits 15-0 cnt1: the loop registers (MS_OP_SET / MS_OP_DJNZ)
+ * Settled from the kernel's code:
+ *   pc.     The device runs the caller's instruction array index for index (the fused post-chain words are additions to an instruction, no
+ *           instruction moves), and no awaiting op advances pc before its await completes, whatever its stage: a sleep, a rand_delay, a
+ *           receive's registration, oneshot and delay, every stage of an rpc call, accept1's delay and queue wait, a channel receive's wait,
+ *           backoff and arrival, a join, a yield, a tick, ctrl_c and the selects all leave pc on their own instruction until they are Ready.
+ *           A task inside a timeout scope stands at the await inside the block, not at MS_OP_TIMEOUT_BEGIN.  One case is normalised: an
+ *           assert_eq!(val, ..) fused into the awaiting op in front of it fails while pc is still that op's; the record names the
+ *           MS_OP_ASSERT_VAL, as it does for an assert reached on its own.
+ *   panic.  The task whose poll panicked is recorded from the registers of that poll (pc of the panicking instruction, the loop registers
+ *           as they stood).  A panic that restart_on_panic absorbs is no verdict and leaves no PANICKED record: the task is gone.
+ *   order.  Ascending task slot, the runner's task-table order.  A spawn takes the lowest free slot, so a seed's slots are the same under
+ *           every madsim_limits_t whose max_tasks it does not exhaust — and a seed that exhausts it has a runner verdict and no records.
+ *           The rows are therefore a function of (workload, configuration, seed) alone and are not sorted.
+ *   states. In precedence: PANICKED; CANCELLED (the abort or kill flag is set: every such task has also been woken); QUEUED; PARKED.
+ * A seed with a runner verdict (MADSIM_IS_RUNNER_VERDICT) has task_len 0 and an all-zero row: the verdict is the whole answer.
+ *
+ * madsim_hip_task_states follows madsim_hip_trace_seeds to the letter: ONE launch of the trace build over `n` seeds (any order, duplicates
+ * allowed), row i belongs to seeds[i].
+ *   tasks:    n rows of task_cap words (NULL with task_cap 0: the counts alone); a row holds the first min(len, task_cap) records and
+ *             zeros behind them.  task_cap <= MADSIM_MAX_LIVE_TASKS
+ *   task_len: n TRUE counts of live tasks (may be NULL), which may exceed task_cap
+ *   out:      n results (may be NULL): the 48 bytes madsim_hip_run_batch gives under the same limits.  No silent re-run
+ * n == 0 returns 0 and touches nothing.  MADSIM_E_ARG: seeds == NULL with n > 0; a buffer without a cap or a cap without a buffer;
+ * task_cap above MADSIM_MAX_LIVE_TASKS.  MADSIM_E_LIMITS: n * (8 * task_cap + 72) exceeds MADSIM_TRACE_MAX_BYTES; the list is never split. */
+#define MADSIM_TASK_PARKED 1
+#define MADSIM_TASK_QUEUED 2
+#define MADSIM_TASK_PANICKED 3
+#define MADSIM_TASK_CANCELLED 4
+#define MADSIM_TASK_STATE(w) ((uint32_t)((uint64_t)(w) >> 56))
+#define MADSIM_TASK_PROG(w) ((uint32_t)(((uint64_t)(w) >> 48) & 0xffu))
+#define MADSIM_TASK_PC(w) ((uint32_t)(((uint64_t)(w) >> 32) & 0xffffu))
+#define MADSIM_TASK_CNT0(w) ((uint32_t)(((uint64_t)(w) >> 16) & 0xffffu))
+#define MADSIM_TASK_CNT1(w) ((uint32_t)((uint64_t)(w) & 0xffffu))
+#define MADSIM_TASK_SITE(w) ((uint64_t)(w) >> 32) /* state | prog | pc: where the task stands, the loop registers dropped */
+int madsim_hip_task_states(const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n,
+                           const madsim_limits_t* lim, uint64_t* tasks, uint64_t task_cap, uint64_t* task_len, madsim_result_t* out);
+/* The shape of a task table: the sum over its records of mix(MADSIM_TASK_SITE(record)) mod 2^64, mix the splitmix64 finaliser
+ *   z = site; z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9; z = (z ^ (z >> 27)) * 0x94d049bb133111eb; mix = z ^ (z >> 31)
+ * — commutative, so it names the multiset of sites whatever the order of the records, and two seeds stuck the same way have the same shape
+ * whatever their loop registers say.  The empty table's shape is 0.  No device involved. */
+uint64_t madsim_hip_stall_shape(const uint64_t* tasks, uint64_t n);
+
 /* Divergence reports: where two variants of a seed's run first part.  A differential campaign says WHICH seeds a change affected;
  * madsim_hip_diverge_seeds says UP TO WHERE the two runs of each listed seed are the same run, on two rulers: the determinism log (one
  * byte per GlobalRng::with, "channel log") and the observation log (one 64-bit word per traced value, "channel obs").  Side A is
@@ -823,6 +880,55 @@ int madsim_hip_probe_order_range(const madsim_workload_t* w, const madsim_config
 int madsim_hip_probe_order_seeds(const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n, uint64_t chunk,
                                  const madsim_limits_t* lim, madsim_probe_order_t* po);
 
+/* Stall-site census: WHERE the tasks of a range's seeds stand when their runs end, by verdict — "409 of the 412 deadlocking seeds have a
+ * task of program 2 parked in the recv_from at pc 7", with no probe placed in advance.  The seeds run on the trace build with the task log
+ * alone (madsim_hip_task_states' launch: log_cap 0, obs_cap 0, the caller's task_cap); per chunk the work runs behind the trace launch on
+ * the rows where they lie — no row and no per-seed word travels to the host.  stall_sites_kernel turns every row's visible records, the
+ * first min(len, task_cap), into a SITE ROW (each word MADSIM_TASK_SITE(record): state | prog | pc, the loop registers dropped) and one
+ * SHAPE word (madsim_hip_stall_shape of the visible records: the multiset of sites, whatever the slot order).  Then the observation
+ * census's own kernels, host fold and table run twice, unchanged, on those materialised rows: once over the site rows, once over the shape
+ * words as rows of cap 1 and length 1 — so every rule of the census holds as worded there: a seed is COUNTED when r.verdict < 4 and bit
+ * `verdict` of `include` is set; runner verdicts are tallied in n_runner and the runner_cap smallest listed in runner_seeds, never counted;
+ * the bytes are the same whatever `chunk`, the form (range or list), the context and the run.
+ *   sites[0 .. n_sites), ascending by `value` = the site:  n_seeds[k] counted seeds of verdict k with at least one task there; n_total
+ *        tasks there over those seeds; max_per_seed the most inside one seed; first_seed the smallest such seed
+ *   shapes[0 .. n_shapes), ascending by `value` = the shape word:  n_seeds[k] counted seeds of verdict k with exactly that multiset of
+ *        sites; first_seed the one to replay (madsim_hip_task_states, then madsim_hip_stall_shape of its row gives the word back);
+ *        n_total = the seeds, max_per_seed = 1.  shapes == NULL with shape_cap 0: no shapes pass, n_shapes = 0
+ *   n_counted[k] / n_idle[k]: counted seeds of verdict k / those of them with no live task (the empty table, shape 0); n_truncated: counted
+ *        seeds with more than task_cap live tasks, whose later tasks are in neither table; n_tasks: the visible records of the counted
+ *        seeds = the sum of every site's n_total
+ * More than site_cap distinct sites, or more than shape_cap distinct shapes: MADSIM_E_LIMITS, and nothing is reported (every output word 0).
+ * One chunk (0 = a default, 65 536 or what fits) asks the device for chunk * (16 * task_cap + 96) bytes — the task row and the site row, the
+ * count, the shape word, its length word, two unused length words, the seed and the result of every seed — plus, per pass, 32 * slots +
+ * 68 * cap + 128: MADSIM_E_LIMITS when that exceeds MADSIM_TRACE_MAX_BYTES.
+ * total == 0 / n == 0 reports the empty result.  MADSIM_E_ARG: sc == NULL; include == 0 or a bit at or above 4; task_cap == 0 or above
+ * MADSIM_MAX_LIVE_TASKS; site_cap == 0 or above MADSIM_CENSUS_MAX_VALUES or sites == NULL; shapes without shape_cap or the reverse, or
+ * shape_cap above MADSIM_CENSUS_MAX_VALUES; runner_cap > 0 without runner_seeds; seeds == NULL with n > 0; a list that is not strictly
+ * ascending (sort and deduplicate first). */
+typedef struct madsim_stall_census {
+    uint32_t include;                  /* in: as madsim_census_t.include                                                          */
+    uint32_t task_cap;                 /* in: live tasks of a seed that are visible, 1 .. MADSIM_MAX_LIVE_TASKS                   */
+    madsim_census_value_t* sites;      /* in: caller's host array [site_cap]                                                      */
+    uint64_t site_cap;                 /* in: 1 .. MADSIM_CENSUS_MAX_VALUES                                                       */
+    madsim_census_value_t* shapes;     /* in: caller's host array [shape_cap]; NULL with shape_cap 0: no shapes pass             */
+    uint64_t shape_cap;
+    uint64_t* runner_seeds;            /* in: caller's host array [runner_cap]; may be NULL when runner_cap == 0                  */
+    uint64_t runner_cap;
+    uint64_t n_sites;                  /* out: entries of `sites` written, ascending by value                                     */
+    uint64_t n_shapes;                 /* out: entries of `shapes` written, ascending by value                                    */
+    uint64_t n_counted[4];             /* out: counted seeds per verdict                                                          */
+    uint64_t n_idle[4];                /* out: ... of them with no live task                                                      */
+    uint64_t n_truncated;              /* out: counted seeds with more than task_cap live tasks                                   */
+    uint64_t n_tasks;                  /* out: visible records of the counted seeds = the sum of every site's n_total            */
+    uint64_t n_runner;                 /* out: seeds with a runner verdict                                                        */
+    uint64_t n_runner_listed;          /* out: min(n_runner, runner_cap), the entries of runner_seeds written                     */
+} madsim_stall_census_t;
+int madsim_hip_stall_census_range(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total, uint64_t chunk,
+                                  const madsim_limits_t* lim, madsim_stall_census_t* sc);
+int madsim_hip_stall_census_seeds(const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n, uint64_t chunk,
+                                  const madsim_limits_t* lim, madsim_stall_census_t* sc);
+
 /* The same entry points on an explicit context (see "Per-device contexts" above). */
 int madsim_hip_ctx_run_batch(madsim_hip_ctx_t* ctx, const madsim_workload_t* w, const madsim_config_t* cfg,
                              uint64_t seed0, uint64_t count, const madsim_limits_t* lim,
@@ -846,6 +952,9 @@ int madsim_hip_ctx_trace_seeds(madsim_hip_ctx_t* ctx, const madsim_workload_t* w
 int64_t madsim_hip_ctx_observe_seed(madsim_hip_ctx_t* ctx, const madsim_workload_t* w, const madsim_config_t* cfg,
                                     uint64_t seed, const madsim_limits_t* lim, uint64_t* obs, uint64_t cap,
                                     madsim_result_t* out);
+int madsim_hip_ctx_task_states(madsim_hip_ctx_t* ctx, const madsim_workload_t* w, const madsim_config_t* cfg,
+                               const uint64_t* seeds, uint64_t n, const madsim_limits_t* lim, uint64_t* tasks, uint64_t task_cap,
+                               uint64_t* task_len, madsim_result_t* out);
 int madsim_hip_ctx_diverge_seeds(madsim_hip_ctx_t* ctx, const madsim_workload_t* wA, const madsim_config_t* cfgA,
                                  const madsim_limits_t* limA, const madsim_workload_t* wB, const madsim_config_t* cfgB,
                                  const madsim_limits_t* limB, const uint64_t* seeds, uint64_t n, uint64_t log_cap,
@@ -862,6 +971,10 @@ int madsim_hip_ctx_probe_order_range(madsim_hip_ctx_t* ctx, const madsim_workloa
                                      uint64_t total, uint64_t chunk, const madsim_limits_t* lim, madsim_probe_order_t* po);
 int madsim_hip_ctx_probe_order_seeds(madsim_hip_ctx_t* ctx, const madsim_workload_t* w, const madsim_config_t* cfg,
                                      const uint64_t* seeds, uint64_t n, uint64_t chunk, const madsim_limits_t* lim, madsim_probe_order_t* po);
+int madsim_hip_ctx_stall_census_range(madsim_hip_ctx_t* ctx, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0,
+                                      uint64_t total, uint64_t chunk, const madsim_limits_t* lim, madsim_stall_census_t* sc);
+int madsim_hip_ctx_stall_census_seeds(madsim_hip_ctx_t* ctx, const madsim_workload_t* w, const madsim_config_t* cfg,
+                                      const uint64_t* seeds, uint64_t n, uint64_t chunk, const madsim_limits_t* lim, madsim_stall_census_t* sc);
 
 /* One process, several GPUs: the whole seed loop of Builder::run (builder.rs:129-150, every seed driven from one
  * process) over `n_ctx` contexts, each on its own GPU (or, for tests on a 1-GPU box, several on the same one).

@@ -548,6 +548,11 @@ struct Builder {
     }
 
   private:
+    uint32_t resolve_rounds() const {            // the rounds resolve_runner() asked for (0: none)
+        if (!(resolve_flags & MADSIM_CAMPAIGN_RESOLVE)) return 0;
+        const uint32_t rounds = (resolve_flags & MADSIM_CAMPAIGN_RESOLVE_ROUNDS_MASK) >> MADSIM_CAMPAIGN_RESOLVE_ROUNDS_SHIFT;
+        return rounds ? rounds : MADSIM_RESOLVE_DEFAULT_ROUNDS;
+    }
     std::vector<SeedTrace> trace_seeds_under(const madsim_workload_t& w, const madsim_config_t& cfg, const madsim_limits_t& lim0,
                                              const std::vector<uint64_t>& seeds, size_t obs_cap, size_t log_cap) const {
         std::vector<SeedTrace> traces(seeds.size());
@@ -962,6 +967,157 @@ struct Builder {
             c.totals.n_truncated += more.totals.n_truncated; c.totals.n_observations += more.totals.n_observations;
             c.totals.n_runner = more.totals.n_runner; c.totals.n_runner_listed = more.totals.n_runner_listed;
             c.totals.n_values = c.values.size();
+            c.runner_seeds = more.runner_seeds;
+        }
+        return c;
+    }
+
+    // Where the tasks of the listed seeds stand when their runs end (madsim_hip_task_states): one record per task still alive, in task-slot
+    // order — MADSIM_TASK_STATE / _PROG / _PC / _CNT0 / _CNT1 decode one, describe() spells it out against the workload table.  `tasks` holds
+    // the first task_cap records, n_tasks says how many there were.  A seed with a runner verdict has none; the builder's resolve_runner()
+    // rounds replay such seeds under madsim_hip_grow_limits(.., r), as trace_seeds does.
+    struct PostMortem {
+        uint64_t seed = 0;
+        madsim_result_t result{};
+        std::vector<uint64_t> tasks;
+        uint64_t n_tasks = 0;
+        uint64_t shape() const { return madsim_hip_stall_shape(tasks.data(), tasks.size()); }
+    };
+    std::vector<PostMortem> post_mortem(const Workload& wl, const std::vector<uint64_t>& seeds, size_t task_cap = 32) const {
+        madsim::check(madsim_hip_init(device));
+        madsim_workload_t w = wl.raw();
+        madsim_config_t cfg = config.raw();
+        madsim_limits_t lim0 = capacities;
+        if (time_limit) { lim0.time_limit_ns = (uint64_t)(*time_limit * 1e9 + 0.5); if (!lim0.time_limit_ns) lim0.time_limit_ns = 1; }
+        std::vector<PostMortem> out(seeds.size());
+        std::vector<size_t> idx(seeds.size());
+        for (size_t i = 0; i < idx.size(); i++) idx[i] = i;
+        const uint32_t rounds = resolve_rounds();
+        for (uint32_t r = 0; r <= rounds && !idx.empty(); r++) {
+            madsim_limits_t lim = lim0;
+            if (r) madsim::check(madsim_hip_grow_limits(&w, &lim0, r, &lim));
+            const size_t m = idx.size();
+            std::vector<uint64_t> s(m), rows(m * task_cap), lens(m);
+            std::vector<madsim_result_t> res(m);
+            for (size_t j = 0; j < m; j++) s[j] = seeds[idx[j]];
+            madsim::check(madsim_hip_task_states(&w, &cfg, s.data(), m, &lim, task_cap ? rows.data() : nullptr, task_cap, lens.data(), res.data()));
+            std::vector<size_t> again;
+            const uint32_t cap = lim.max_steps ? lim.max_steps : 1u << 24, ceiling = lim.max_steps_ceiling ? lim.max_steps_ceiling : 1u << 28;
+            for (size_t j = 0; j < m; j++) {
+                PostMortem& p = out[idx[j]];
+                p.seed = s[j]; p.result = res[j]; p.n_tasks = lens[j];
+                p.tasks.assign(rows.begin() + j * task_cap, rows.begin() + j * task_cap + (size_t)std::min<uint64_t>(lens[j], task_cap));
+                if (res[j].verdict == MADSIM_OVERFLOW || (res[j].verdict == MADSIM_STEP_LIMIT && cap < ceiling)) again.push_back(idx[j]);
+            }
+            idx.swap(again);
+        }
+        return out;
+    }
+    // A site (state << 24 | prog << 16 | pc) or a whole task record as text, decoded from the workload table on the host:
+    // "prog 2 (node 2) pc 20 RECV sock 1 tag 1 PARKED" — the op's name and its operands as that op reads them (a socket-table entry, a tag, a
+    // program; raw a / b / imm for the rest).
+    static const char* op_name(uint32_t op) {       // enum madsim_op, by value
+        static const char* const names[] = {"DONE", "SPAWN", "JOIN", "ABORT", "YIELD", "PANIC", "SET", "DJNZ", "JMP", "TRACE", "SLEEP", "MARK", "SLEEP_UNTIL", "ASSERT_ELAPSED", "ADVANCE", "BUILD", "?", "?", "?", "?", "BIND", "SEND", "REPLY", "RECV", "ASSERT_VAL", "RECV_TIMEOUT", "CLOSE", "?", "?", "?", "KILL", "RESTART", "PAUSE", "RESUME", "CLOG_NODE", "UNCLOG_NODE", "CLOG_LINK", "UNCLOG_LINK", "ASSERT_EXIT", "SET_LOSS", "SLEEP_RAND", "GSET", "GADD", "ASSERT_G", "PANIC_IF_G_LT", "JEQ", "CONNECT", "ACCEPT", "CSEND", "CRECV", "CCLOSE", "RPC_CALL", "RPC_REPLY", "RAND_BOOL", "RANDOM", "TRACE_TIME", "HOOK_REQ", "HOOK_RSP", "IPVS", "SET_LATENCY", "TIMEOUT_BEGIN", "TIMEOUT_END", "INTERVAL", "TICK", "INTERVAL_RESET", "RECV_OR_TICK", "RECV_TIMEOUT_AT", "CTRL_C", "SEND_CTRL_C", "RECV_OR_CTRL_C"};
+        return op < sizeof names / sizeof *names ? names[op] : "?";
+    }
+    static std::string describe(const Workload& wl, uint64_t site) {
+        if (site >> 32) site >>= 32;
+        const uint32_t state = (uint32_t)(site >> 24), prog = (uint32_t)(site >> 16) & 0xff, pc = (uint32_t)site & 0xffff;
+        static const char* const states[] = {"?", "PARKED", "QUEUED", "PANICKED", "CANCELLED"};
+        const madsim_workload_t w = wl.raw();
+        std::string s = "prog " + std::to_string(prog);
+        if (prog < w.n_progs && pc < w.n_insns) {
+            const madsim_insn_t& in = w.insns[pc];
+            const auto n = [](uint32_t v) { return std::to_string(v); };
+            s += " (node " + n(w.progs[prog].node) + ") pc " + n(pc) + " " + op_name(in.op);
+            switch (in.op) {
+            case MS_OP_RECV: case MS_OP_RECV_TIMEOUT: case MS_OP_RECV_TIMEOUT_AT: case MS_OP_RECV_OR_TICK: case MS_OP_RECV_OR_CTRL_C: case MS_OP_REPLY:
+                s += " sock " + n(in.a) + " tag " + n(in.b >> 8); break;
+            case MS_OP_SEND: s += " sock " + n(in.a) + " to sock " + n(in.b & 0xff) + " tag " + n(in.b >> 8); break;
+            case MS_OP_RPC_CALL: s += " sock " + n(in.a) + " to sock " + n(in.b & 0xff) + " request " + n((in.b >> 8) - 0x80); break;
+            case MS_OP_CONNECT: s += " sock " + n(in.a) + " to sock " + n(in.b & 0xff); break;
+            case MS_OP_BIND: case MS_OP_ACCEPT: case MS_OP_RPC_REPLY: case MS_OP_CLOSE: s += " sock " + n(in.a); break;
+            case MS_OP_JOIN: case MS_OP_SPAWN: case MS_OP_ABORT: s += " prog " + n(in.a); break;
+            case MS_OP_SLEEP: case MS_OP_SLEEP_UNTIL: s += " " + n(in.b) + " s + " + n(in.imm) + " ns"; break;
+            case MS_OP_CRECV: case MS_OP_CTRL_C: case MS_OP_YIELD: case MS_OP_TICK: case MS_OP_DONE: break;
+            default: s += " a=" + n(in.a) + " b=" + n(in.b) + " imm=" + n(in.imm);
+            }
+        } else s += " pc " + std::to_string(pc) + " (outside the workload)";
+        return s + " " + (state <= 4 ? states[state] : "?");
+    }
+
+    // Where the tasks of the builder's seeds stand when their runs end, by verdict (madsim_hip_stall_census_range / _seeds): `seed .. seed +
+    // count`, or the over_seeds() list, run on the trace build with the task log and reduced on the device.  sites: ascending by site
+    // (MADSIM_TASK_SITE of a record), per site the counted seeds of each verdict with a task there; shapes: ascending by shape word
+    // (madsim_hip_stall_shape), per distinct multiset of sites the counted seeds of each verdict and, in first_seed, the one to replay
+    // (max_shapes 0: no shapes pass).  More than max_sites / max_shapes distinct entries throws (MADSIM_E_LIMITS).  The default mask counts
+    // the failing verdicts.  This builder's resolve_runner() rounds apply as in census().
+    struct StallCensus {
+        std::vector<madsim_census_value_t> sites, shapes;
+        madsim_stall_census_t totals{};            // the counts (the pointers and caps are the call's own: not meaningful here)
+        std::vector<uint64_t> runner_seeds;
+        std::vector<madsim_census_value_t> shapes_of(uint32_t verdict) const {       // the shapes seeds of `verdict` ended in, the most frequent first
+            std::vector<madsim_census_value_t> out;
+            for (const madsim_census_value_t& e : shapes) if (e.n_seeds[verdict]) out.push_back(e);
+            std::sort(out.begin(), out.end(), [verdict](const madsim_census_value_t& a, const madsim_census_value_t& b) {
+                return a.n_seeds[verdict] != b.n_seeds[verdict] ? a.n_seeds[verdict] > b.n_seeds[verdict] : a.value < b.value; });
+            return out;
+        }
+    };
+    StallCensus stall_census(const Workload& wl, uint32_t task_cap = 32, uint64_t max_sites = 4096, uint64_t max_shapes = 4096, uint32_t include = 0xe,
+                             uint64_t chunk = 0) const {
+        madsim::check(madsim_hip_init(device));
+        madsim_workload_t w = wl.raw();
+        madsim_config_t cfg = config.raw();
+        madsim_limits_t lim0 = capacities;
+        if (time_limit) { lim0.time_limit_ns = (uint64_t)(*time_limit * 1e9 + 0.5); if (!lim0.time_limit_ns) lim0.time_limit_ns = 1; }
+        auto one = [&](const madsim_limits_t& lim, const std::vector<uint64_t>* list) {
+            StallCensus c;
+            const uint64_t n = list ? list->size() : count;
+            c.sites.resize(max_sites ? max_sites : 1);
+            c.shapes.resize(max_shapes ? max_shapes : 1);
+            c.runner_seeds.resize(n ? n : 1);
+            madsim_stall_census_t& t = c.totals;
+            t.include = include; t.task_cap = task_cap; t.sites = c.sites.data(); t.site_cap = max_sites;
+            t.shapes = max_shapes ? c.shapes.data() : nullptr; t.shape_cap = max_shapes;
+            t.runner_seeds = c.runner_seeds.data(); t.runner_cap = n;
+            madsim::check(list ? madsim_hip_stall_census_seeds(&w, &cfg, list->data(), n, chunk, &lim, &t)
+                               : madsim_hip_stall_census_range(&w, &cfg, seed, n, chunk, &lim, &t));
+            c.sites.resize(t.n_sites);
+            c.shapes.resize(t.n_shapes);
+            c.runner_seeds.resize(t.n_runner_listed);
+            t.sites = t.shapes = nullptr; t.runner_seeds = nullptr;
+            return c;
+        };
+        auto merge = [](std::vector<madsim_census_value_t>& into, const std::vector<madsim_census_value_t>& more) {
+            std::vector<madsim_census_value_t> merged;
+            for (size_t i = 0, j = 0; i < into.size() || j < more.size();) {
+                if (j >= more.size() || (i < into.size() && into[i].value < more[j].value)) merged.push_back(into[i++]);
+                else if (i >= into.size() || more[j].value < into[i].value) merged.push_back(more[j++]);
+                else {
+                    madsim_census_value_t e = into[i++];
+                    const madsim_census_value_t& o = more[j++];
+                    for (int k = 0; k < 4; k++) e.n_seeds[k] += o.n_seeds[k];
+                    e.n_total += o.n_total; e.first_seed = std::min(e.first_seed, o.first_seed); e.max_per_seed = std::max(e.max_per_seed, o.max_per_seed);
+                    merged.push_back(e);
+                }
+            }
+            into.swap(merged);
+        };
+        StallCensus c = one(lim0, listed_seeds ? &seed_list : nullptr);
+        const uint32_t rounds = resolve_rounds();
+        for (uint32_t r = 1; r <= rounds && !c.runner_seeds.empty(); r++) {
+            madsim_limits_t lim = lim0;
+            madsim::check(madsim_hip_grow_limits(&w, &lim0, r, &lim));
+            const StallCensus more = one(lim, &c.runner_seeds);
+            merge(c.sites, more.sites);
+            merge(c.shapes, more.shapes);
+            if (c.sites.size() > max_sites || c.shapes.size() > max_shapes)
+                throw Error(MADSIM_E_LIMITS, "stall_census: more than max_sites distinct sites or max_shapes distinct shapes once the runner seeds are settled");
+            for (int k = 0; k < 4; k++) { c.totals.n_counted[k] += more.totals.n_counted[k]; c.totals.n_idle[k] += more.totals.n_idle[k]; }
+            c.totals.n_truncated += more.totals.n_truncated; c.totals.n_tasks += more.totals.n_tasks;
+            c.totals.n_runner = more.totals.n_runner; c.totals.n_runner_listed = more.totals.n_runner_listed;
+            c.totals.n_sites = c.sites.size(); c.totals.n_shapes = c.shapes.size();
             c.runner_seeds = more.runner_seeds;
         }
         return c;

@@ -362,6 +362,24 @@ assert C.sizeof(ProbeOrderPair) == 72 and C.sizeof(ProbeOrder) == 152
 HEADER_STRUCTS["madsim_probe_order_pair_t"] = ProbeOrderPair
 HEADER_STRUCTS["madsim_probe_order_t"] = ProbeOrder
 
+# madsim_hip_task_states: the state byte of a task record (bits 63-56; prog 55-48, pc 47-32, cnt0 31-16, cnt1 15-0)
+TASK_PARKED, TASK_QUEUED, TASK_PANICKED, TASK_CANCELLED = 1, 2, 3, 4
+TASK_STATE_NAMES = {TASK_PARKED: "PARKED", TASK_QUEUED: "QUEUED", TASK_PANICKED: "PANICKED", TASK_CANCELLED: "CANCELLED"}
+MAX_LIVE_TASKS = 254          # the most task records a row can hold (madsim_limits_t.max_tasks' ceiling)
+
+
+class StallCensus(C.Structure):
+    """madsim_stall_census_t: which verdicts count, how many live tasks of a seed are visible and the caller's three arrays going in (the
+    site table, the shape table — NULL with 0: no shapes pass —, the runner seeds); the tables' lengths and the totals coming out."""
+    _fields_ = [("include", C.c_uint32), ("task_cap", C.c_uint32), ("sites", C.POINTER(CensusValue)), ("site_cap", C.c_uint64),
+                ("shapes", C.POINTER(CensusValue)), ("shape_cap", C.c_uint64), ("runner_seeds", C.POINTER(C.c_uint64)), ("runner_cap", C.c_uint64),
+                ("n_sites", C.c_uint64), ("n_shapes", C.c_uint64), ("n_counted", C.c_uint64 * 4), ("n_idle", C.c_uint64 * 4),
+                ("n_truncated", C.c_uint64), ("n_tasks", C.c_uint64), ("n_runner", C.c_uint64), ("n_runner_listed", C.c_uint64)]
+
+
+assert C.sizeof(StallCensus) == 168
+HEADER_STRUCTS["madsim_stall_census_t"] = StallCensus
+
 
 class Geometry(C.Structure):
     _fields_ = [

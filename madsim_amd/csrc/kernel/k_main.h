@@ -67,6 +67,38 @@ __device__ __forceinline__ uint32_t progress_priority(uint32_t pass, uint32_t es
     return q >= 3 ? 0u : 3u - q;
 }
 
+// Trace builds: the unit's row of the task log (sim_kernel.h KParams::task_log; the record: include/madsim_hip.h "Task post-mortems") —
+// unit 0 of every slot that is still alive, in slot order, as the run left it.  Only the task whose poll raised MADSIM_PANIC still
+// carries TF_RUN in memory: the executor loop stores its registers back for this walk (below) and nothing clears the flag afterwards.
+// An aborted or killed task has been woken by whoever flagged it and is dropped at its pop, so the flag alone says CANCELLED.  The row
+// is cap-guarded and the host zero-fills it; the count is the true one.  A runner verdict writes no record.
+// The three parameters are read once per finished seed: from the kernel-argument segment where they are used (PTASK: k_state.h cold_read), never
+// held in scalar registers through the pass loop, where the trace builds have none to spare (what the log costs them: profiles/stall_ab.md).
+#ifdef MADSIM_EMU
+#define PTASK(f) (P.f)
+#else
+#define PTASK(f) cold_read<true>(P.f, (uint32_t)offsetof(KParams, f))
+#endif
+template <class K>
+__device__ __forceinline__ void task_log_write(const Ctx& c, uint32_t verdict, uint64_t unit) {
+    const KParams& P = c.P;
+    uint64_t* const log = PTASK(task_log);
+    const uint64_t cap = PTASK(task_cap);
+    uint64_t n = 0;
+    if (!MADSIM_IS_RUNNER_VERDICT(verdict))
+        for (uint32_t t = 0; t < P.max_tasks; t++) {
+            const uint4 u = TU(c, t, 0);
+            if (!(u.x & TF_ALIVE)) continue;
+            const uint64_t state = (u.x & TF_RUN) ? MADSIM_TASK_PANICKED : (u.x & (TF_CANCEL | TF_KILLED)) ? MADSIM_TASK_CANCELLED
+                                 : (u.x & TF_SCHED) ? MADSIM_TASK_QUEUED : MADSIM_TASK_PARKED;
+            if (n < cap)
+                log[unit * cap + n] = (state << 56) | ((uint64_t)(u.x >> 24) << 48) | ((uint64_t)(u.y & 0xffffu) << 32) |
+                                                    ((uint64_t)(u.z & 0xffffu) << 16) | (u.z >> 16);
+            n++;
+        }
+    PTASK(task_len)[unit] = n;
+}
+
 // Register-ready-queue builds pop a queue of one under gen_index's wave vote (sim_kernel.h MADSIM_POP_ONE; the pop in sim_kernel below).
 template <class K> struct PopOne { static constexpr bool ON = MADSIM_POP_ONE && K::RQ; };
 
@@ -262,6 +294,7 @@ __global__ __launch_bounds__(256, K::CMP ? 4 : !K::G ? 1 : (K::FEAT & (MADSIM_FE
                     panicked = false;
                 }
             }
+            if (K::TRACE && panicked) TU(c, slot, 0) = u0;  // (the task log's PANICKED record: task_log_write above; nothing runs after this poll)
             if (panicked) L.verdict = MADSIM_PANIC;          // resume_unwind (:315): no advance, no expire
             else if (!parked) L.clock += 50 + gen_range_small<K, 50>(c, L);   // :319-321, then Timer::expire (time/mod.rs:103-106)
             now = L.clock;
@@ -303,7 +336,7 @@ __global__ __launch_bounds__(256, K::CMP ? 4 : !K::G ? 1 : (K::FEAT & (MADSIM_FE
             r.rng_calls = L.rng_calls; r.trace_hash = (K::NOLOG || (K::LOGSW && P.no_log)) ? 0 : L.trace_hash; r.obs_hash = L.obs_hash;
             if (r.verdict >= MADSIM_UNSUPPORTED) { r.steps = 0; r.clock_ns = 0; r.msg_count = 0; r.rng_calls = 0; r.trace_hash = 0; r.obs_hash = 0; }   // the verdict is the whole answer
             PCOLD(out)[next] = r;
-            if (K::TRACE) { P.trace_len[next] = L.log_len; if (P.obs_len) P.obs_len[next] = L.obs_len; }
+            if (K::TRACE) { P.trace_len[next] = L.log_len; if (P.obs_len) P.obs_len[next] = L.obs_len; if (PTASK(task_log)) task_log_write<K>(c, r.verdict, next); }
             have = false;
             if (K::DEDUP) L.exact = 0;
             // next unit: static striding, or the per-launch work queue (a lane whose seeds end early — deadlocks under

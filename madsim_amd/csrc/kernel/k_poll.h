@@ -607,7 +607,8 @@ __device__ __forceinline__ bool poll_task(const Ctx& c, Lane& L, const uint32_t 
                 sub = 0;
                 // fused post-chain of this op (geometry.h build_tables): assert_eq!(val, ..), then djnz / jmp
                 const uint32_t pf = in.w;
-                if ((pf & 1) && u0.w != in.z) st = ST_PANIC;   // (no `break`: `op` stays this awaiting op, so [B] is skipped too)
+                if ((pf & 1) && u0.w != in.z) { st = ST_PANIC; if (K::TRACE) pc++; }   // (no `break`: `op` stays this awaiting op, so [B] is skipped too;
+                                                                                       //  trace builds: the task log names the MS_OP_ASSERT_VAL, the next instruction)
                 else {
                     pc = (pf >> 4) & 0x3fff;
                     if (pf & 2) {

@@ -227,7 +227,7 @@ struct madsim_hip_resources {
     // One side's buffers of a trace launch: the rows of the determinism log (bytes) and of the observation log (words), the length words
     // and the results.  Set 0 is what every trace call uses, set 1 side B of a divergence report; set 0's `out` is also the result
     // buffer of run_host and run_list.
-    struct TraceSet { DevBuf<uint8_t> log; DevBuf<uint64_t> obs, len; DevBuf<madsim_result_t> out; };
+    struct TraceSet { DevBuf<uint8_t> log; DevBuf<uint64_t> obs, len; DevBuf<madsim_result_t> out; DevBuf<uint64_t> task, task_len; };      // (task, task_len: the task log, only where a call asks for it)
     TraceSet trace[2];
     DevBuf<madsim_divergence_t> d_drec; DevBuf<uint64_t> d_dctx;      // divergence reports: the records and the context rows
     // One census form's buffers (the observation census, the probe-set census, the probe-order census: each its own, the slots differ in size): the table (all zero
@@ -267,6 +267,12 @@ struct madsim_hip_resources {
     } probe_sets;
     // the probe-order census: the dense matrix of cells takes the table's place (1024 cells of 32 bytes); the claim list is not used
     ObsReport<madsim_probe_order_pair_t, 32, MADSIM_K_PROBE_ORDER_WORDS> probe_order;
+    // the stall-site census: the observation census's buffer group twice — the site pass and the shape pass — and what stall_sites_kernel
+    // writes for them (device only): the chunk's site rows, shape words and the length array of ones
+    struct Stall {
+        ObsReport<madsim_census_value_t, MADSIM_K_CENSUS_SLOT_BYTES, MADSIM_K_CENSUS_WORDS> sites, shapes;
+        DevBuf<uint64_t> rows, shape, ones;
+    } stall;
     Event ev0, ev1;
     Event pipe_begin;                         // run_pipelined: before the first sub-batch of a call
     Event tev[2 * 64];                        // timing slots of madsim_hip_run_batch_async
@@ -951,7 +957,7 @@ struct TraceSteps {
 };
 
 static int trace_prepare(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, const madsim_limits_t* lim, uint64_t n,
-                         uint64_t log_cap, uint64_t obs_cap, madsim_hip_ctx::TraceSet& S, Geo& G, hipStream_t st) {
+                         uint64_t log_cap, uint64_t obs_cap, madsim_hip_ctx::TraceSet& S, Geo& G, hipStream_t st, const uint64_t* task_cap = nullptr) {
     int rc;
     if ((rc = madsim_geo::make_geometry(c->dev(), w, cfg, lim, n, &G, &g_err, true))) return rc;
     G.P.count = n;
@@ -962,6 +968,10 @@ static int trace_prepare(madsim_hip_ctx_t* c, const madsim_workload_t* w, const 
     HIP_TRY(S.len.room((size_t)(2 * n)));                                    // [n] log lengths, then [n] observation counts
     HIP_TRY(c->d_seeds.room((size_t)n));
     HIP_TRY(S.out.room((size_t)n));
+    if (task_cap) {                                                          // (at least one word: a non-null task_log is what asks the kernel for the counts)
+        HIP_TRY(S.task.room((size_t)std::max<uint64_t>(n * *task_cap, 1)));
+        HIP_TRY(S.task_len.room((size_t)n));
+    }
     if (G.lds_bytes > c->lds_attr) {
         if (madsim_k_set_max_lds((uint32_t)c->lds_per_cu)) return fail(MADSIM_E_HIP, "hipFuncSetAttribute failed");
         c->lds_attr = (uint32_t)c->lds_per_cu;
@@ -969,6 +979,7 @@ static int trace_prepare(madsim_hip_ctx_t* c, const madsim_workload_t* w, const 
     G.P.seed0 = 0; G.P.count = n; G.P.seed_list = c->d_seeds; G.P.out = S.out;
     G.P.trace_log = log_cap ? S.log : nullptr; G.P.trace_cap = log_cap; G.P.trace_len = S.len;
     G.P.obs_log = obs_cap ? S.obs : nullptr; G.P.obs_cap = obs_cap; G.P.obs_len = S.len + n;
+    if (task_cap) { G.P.task_log = S.task; G.P.task_cap = *task_cap; G.P.task_len = S.task_len; }
     return 0;
 }
 
@@ -977,6 +988,8 @@ static bool trace_queue(const Geo& G, const madsim_hip_ctx::TraceSet& S,uint64_t
     if (ok && log_cap && zero_log) ok = step(hipMemsetAsync(S.log, 0, n * log_cap, st), "hipMemsetAsync(log rows)");
     if (ok && obs_cap) ok = step(hipMemsetAsync(S.obs, 0, n * obs_cap * sizeof(uint64_t), st), "hipMemsetAsync(observation rows)");
     if (ok) ok = step(hipMemsetAsync(S.len, 0, 2 * n * sizeof(uint64_t), st), "hipMemsetAsync(lengths)");
+    if (ok && G.P.task_log && G.P.task_cap) ok = step(hipMemsetAsync(S.task, 0, n * G.P.task_cap * sizeof(uint64_t), st), "hipMemsetAsync(task rows)");
+    if (ok && G.P.task_log) ok = step(hipMemsetAsync(S.task_len, 0, n * sizeof(uint64_t), st), "hipMemsetAsync(task counts)");
     if (ok) ok = step(hipMemsetAsync(S.out, 0, n * sizeof(madsim_result_t), st), "hipMemsetAsync(results)");
     if (ok) {
         step.no_build = madsim_k_launch_sim(&G.P, G.grid, G.lds_bytes, st, 1) != 0;
@@ -994,19 +1007,26 @@ static bool trace_queue(const Geo& G, const madsim_hip_ctx::TraceSet& S,uint64_t
 // bytes and nothing behind them, so the device row needs no zeroes —, no bound on `log_cap` but the device's memory, and results that
 // carry the fingerprint whatever the limits say.  The list form answers with the bytes madsim_hip_run_batch gives: the trace builds always
 // fold the determinism log, so under madsim_limits_t.no_trace_hash its results' trace_hash is zeroed here.
+// (`tr`: madsim_hip_task_states — one more optional buffer, the task log's rows and counts; madsim_hip_trace_seeds passes none and queues what it queued)
+struct TaskRows { uint64_t* tasks; uint64_t cap; uint64_t* len; };
 static int trace_list(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n,
                       const madsim_limits_t* lim, uint8_t* logs, uint64_t log_cap, uint64_t* obs, uint64_t obs_cap,
-                      uint64_t* log_len, uint64_t* obs_len, madsim_result_t* out, bool single) {
+                      uint64_t* log_len, uint64_t* obs_len, madsim_result_t* out, bool single, const TaskRows* tr = nullptr) {
     if (n == 0) return 0;
-    if (!seeds) return fail(MADSIM_E_ARG, "trace_seeds: null seed list");
+    if (!seeds) return fail(MADSIM_E_ARG, tr ? "task_states: null seed list" : "trace_seeds: null seed list");
+    if (tr) {
+        if ((tr->tasks != nullptr) != (tr->cap != 0)) return fail(MADSIM_E_ARG, "task_states: `tasks` and task_cap are given together or not at all");
+        if (tr->cap > MADSIM_MAX_LIVE_TASKS) return fail(MADSIM_E_ARG, "task_states: task_cap exceeds MADSIM_MAX_LIVE_TASKS");
+    }
     if ((logs != nullptr) != (log_cap != 0)) return fail(MADSIM_E_ARG, "trace_seeds: `logs` and log_cap are given together or not at all");
     if ((obs != nullptr) != (obs_cap != 0)) return fail(MADSIM_E_ARG, "trace_seeds: `obs` and obs_cap are given together or not at all");
     if (!single) {
         // what the call asks of the device, per seed: the two rows, the two lengths, the seed and the result
         const uint64_t M = MADSIM_TRACE_MAX_BYTES;
         if (log_cap > M || obs_cap > M / 8 || n > M) return fail(MADSIM_E_LIMITS, "trace_seeds: more than MADSIM_TRACE_MAX_BYTES of device memory");
-        const uint64_t per_seed = log_cap + 8 * obs_cap + 3 * sizeof(uint64_t) + sizeof(madsim_result_t);
-        if (per_seed > M / n) return fail(MADSIM_E_LIMITS, "trace_seeds: n x (log_cap + 8 obs_cap + 72) exceeds MADSIM_TRACE_MAX_BYTES: fewer seeds per call, or smaller caps");
+        const uint64_t per_seed = log_cap + 8 * obs_cap + 3 * sizeof(uint64_t) + sizeof(madsim_result_t) + (tr ? 8 * tr->cap : 0);
+        if (per_seed > M / n) return fail(MADSIM_E_LIMITS, tr ? "task_states: n x (8 task_cap + 72) exceeds MADSIM_TRACE_MAX_BYTES: fewer seeds per call, or a smaller task_cap"
+                                                              : "trace_seeds: n x (log_cap + 8 obs_cap + 72) exceeds MADSIM_TRACE_MAX_BYTES: fewer seeds per call, or smaller caps");
     }
     CTX_ENTER(c);
     int rc = madsim_geo::validate(w, cfg, &g_err);
@@ -1014,7 +1034,7 @@ static int trace_list(madsim_hip_ctx_t* c, const madsim_workload_t* w, const mad
     Geo G;
     hipStream_t st = nullptr;
     madsim_hip_ctx::TraceSet& S = c->trace[0];
-    if ((rc = trace_prepare(c, w, cfg, lim, n, log_cap, obs_cap, S, G, st))) return rc;
+    if ((rc = trace_prepare(c, w, cfg, lim, n, log_cap, obs_cap, S, G, st, tr ? &tr->cap : nullptr))) return rc;
     uint64_t* d_olen = S.len + n;
     // from here on the stream may hold work on the caller's memory: every step is tried only while all before it succeeded, and the
     // synchronisation is reached whatever happened
@@ -1027,6 +1047,8 @@ static int trace_list(madsim_hip_ctx_t* c, const madsim_workload_t* w, const mad
     if (ok && single) ok = step(hipMemcpyAsync(&one_len, S.len, sizeof one_len, hipMemcpyDeviceToHost, st), "hipMemcpyAsync(length)");
     if (ok && log_len && !single) ok = step(hipMemcpyAsync(log_len, S.len, n * sizeof(uint64_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync(log lengths)");
     if (ok && obs_len) ok = step(hipMemcpyAsync(obs_len, d_olen, n * sizeof(uint64_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync(observation counts)");
+    if (ok && tr && tr->tasks) ok = step(hipMemcpyAsync(tr->tasks, S.task, n * tr->cap * sizeof(uint64_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync(task rows)");
+    if (ok && tr && tr->len) ok = step(hipMemcpyAsync(tr->len, S.task_len, n * sizeof(uint64_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync(task counts)");
     if (ok && out) ok = step(hipMemcpyAsync(out, S.out, n * sizeof(madsim_result_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync(results)");
     ok = step(hipStreamSynchronize(st), "hipStreamSynchronize");
     if (step.err != hipSuccess) return fail(MADSIM_E_HIP, std::string(step.at) + ": " + hipGetErrorString(step.err));
@@ -1297,15 +1319,109 @@ int fold_chunk(const Form& f, const unsigned long long* words, const typename Fo
     return 0;
 }
 
+// The stall-site census (include/madsim_hip.h): the fourth form of obs_report_run, and the one with TWO passes.  The trace launch keeps the task log in
+// the observation log's place; stall_sites_kernel turns the task rows into site rows and shape words; the observation census's launch and host fold
+// (CensusForm) run over each — the site pass in buffer group 0, the shape pass (none when the caller gave no shape array) in group 1.
+int fold_stall(madsim_stall_census_t* sc, const unsigned long long* words, const madsim_census_value_t* sites, uint64_t n_sites,
+               const madsim_census_value_t* shapes, uint64_t n_shapes) {
+    madsim_census_t a{}, b{};
+    a.values = sc->sites; a.cap = sc->site_cap; a.n_values = sc->n_sites;
+    b.values = sc->shapes; b.cap = sc->shape_cap; b.n_values = sc->n_shapes;
+    if (fold_chunk(CensusForm{&a}, words, sites, n_sites)) return -1;
+    if (n_shapes && fold_chunk(CensusForm{&b}, nullptr, shapes, n_shapes)) return -1;
+    sc->n_sites = a.n_values; sc->n_shapes = b.n_values;
+    for (int k = 0; k < 4; k++) { sc->n_counted[k] += a.n_counted[k]; sc->n_idle[k] += a.n_silent[k]; }
+    sc->n_truncated += a.n_truncated; sc->n_tasks += a.n_observations; sc->n_runner += a.n_runner;
+    return 0;
+}
+
+struct StallForm {
+    typedef madsim_stall_census_t Report;
+    typedef madsim_census_value_t Entry;
+    static_assert(sizeof(Report) == 168, "record layout");
+    Report* r;
+    static constexpr uint64_t slot_bytes = MADSIM_K_CENSUS_SLOT_BYTES, min_slots = MADSIM_K_CENSUS_MIN_SLOTS, n_words = MADSIM_K_CENSUS_WORDS;
+    // beside the task row and the site row: the count, the shape word and its length word, the trace set's two length words, the seed, the result
+    static constexpr uint64_t per_seed_bytes = 6 * sizeof(uint64_t) + sizeof(madsim_result_t);
+    static constexpr uint64_t eager = CensusForm::eager;
+    static constexpr uint32_t runner_word = CensusForm::runner_word, err_cap = MADSIM_K_CENSUS_ERR_CAP;
+    static constexpr uint64_t fixed_slots = 0;
+    static constexpr const char *name = "stall_census", *noun = "stall census";
+    static constexpr const char *at_zero = "hipMemsetAsync(stall census words)", *at_launch = "stall census kernel launch", *at_words = "hipMemcpyAsync(stall census words)",
+                                *at_entries = "hipMemcpyAsync(stall census entries)";
+    static constexpr const char* too_big = "stall_census: chunk x (16 task_cap + 96) + per pass 32 slots + 68 cap + 128 exceeds MADSIM_TRACE_MAX_BYTES: a smaller chunk or smaller caps";
+    static constexpr const char* too_many = "stall_census: more than site_cap distinct sites or more than shape_cap distinct shapes: raise max_sites / max_shapes";
+    int check() const {
+        if (!r) return fail(MADSIM_E_ARG, "stall_census: null report");
+        if (r->include == 0 || (r->include & ~0xfu)) return fail(MADSIM_E_ARG, "stall_census: include is 0 or names a verdict at or above 4 (only PASS, PANIC, DEADLOCK, TIME_LIMIT are counted)");
+        if (r->task_cap == 0 || r->task_cap > MADSIM_MAX_LIVE_TASKS) return fail(MADSIM_E_ARG, "stall_census: task_cap outside 1 .. MADSIM_MAX_LIVE_TASKS");
+        if (r->site_cap == 0 || r->site_cap > MADSIM_CENSUS_MAX_VALUES || !r->sites) return fail(MADSIM_E_ARG, "stall_census: site_cap outside 1 .. MADSIM_CENSUS_MAX_VALUES, or no site array");
+        if ((r->shapes != nullptr) != (r->shape_cap != 0) || r->shape_cap > MADSIM_CENSUS_MAX_VALUES)
+            return fail(MADSIM_E_ARG, "stall_census: `shapes` and shape_cap are given together or not at all, shape_cap at most MADSIM_CENSUS_MAX_VALUES");
+        if (r->runner_cap && !r->runner_seeds) return fail(MADSIM_E_ARG, "stall_census: runner_cap without runner_seeds");
+        return 0;
+    }
+    void nothing() const {
+        r->n_sites = r->n_shapes = r->n_truncated = r->n_tasks = r->n_runner = r->n_runner_listed = 0;
+        for (int k = 0; k < 4; k++) r->n_counted[k] = r->n_idle[k] = 0;
+    }
+};
+
+// What obs_report_run asks of a form beyond its own members: how many passes it makes (each with a buffer group, a cap, a table, words and entries of
+// its own), what a seed's rows weigh, which log the trace launch keeps, its kernels' launch and its host fold.  One pass over the observation rows for
+// the three observation forms; the stall census specialises it.
+template <class Form> struct Passes {
+    static constexpr int max = 1;
+    static constexpr bool task_log = false;
+    static int count(const Form&) { return 1; }
+    static uint64_t row_cap(const Form& f) { return f.r->obs_cap; }
+    static uint64_t row_bytes(uint64_t row_cap) { return 8 * row_cap; }
+    static uint64_t cap(const Form& f, int) { return f.dev_cap(); }
+    static auto& bufs(madsim_hip_ctx_t* c, int) { return Form::bufs(c); }
+    static int ensure_rows(madsim_hip_ctx_t*, uint64_t, uint64_t, hipStream_t) { return 0; }
+    static int launch(const Form& f, madsim_hip_ctx_t* c, uint64_t n, const uint64_t* slots, hipStream_t st) { return f.launch(c, n, slots[0], st); }
+    static int fold(const Form& f, const unsigned long long* const* W, typename Form::Entry* const* E, const uint64_t* ne) { return fold_chunk(f, W[0], E[0], ne[0]); }
+};
+template <> struct Passes<StallForm> {
+    static constexpr int max = 2;
+    static constexpr bool task_log = true;
+    static int count(const StallForm& f) { return f.r->shape_cap ? 2 : 1; }
+    static uint64_t row_cap(const StallForm& f) { return f.r->task_cap; }
+    static uint64_t row_bytes(uint64_t row_cap) { return 16 * row_cap; }      // the task row and the site row
+    static uint64_t cap(const StallForm& f, int p) { return p ? f.r->shape_cap : f.r->site_cap; }
+    static auto& bufs(madsim_hip_ctx_t* c, int p) { return p ? c->stall.shapes : c->stall.sites; }
+    static int ensure_rows(madsim_hip_ctx_t* c, uint64_t chunk, uint64_t task_cap, hipStream_t st) {
+        HIP_TRY(c->stall.rows.room((size_t)(chunk * task_cap), st));
+        HIP_TRY(c->stall.shape.room((size_t)chunk, st));
+        HIP_TRY(c->stall.ones.room((size_t)chunk, st));
+        return 0;
+    }
+    static int launch(const StallForm& f, madsim_hip_ctx_t* c, uint64_t n, const uint64_t* slots, hipStream_t st) {
+        const madsim_hip_ctx::TraceSet& S = c->trace[0];
+        auto& B = c->stall;
+        const madsim_stall_census_t* r = f.r;
+        if (int rc = madsim_k_launch_stall_sites(S.task, r->task_cap, S.task_len, S.out, n, B.rows, B.shape, B.ones, st)) return rc;
+        if (int rc = madsim_k_launch_census(B.rows, r->task_cap, S.task_len, S.out, c->d_seeds, n, r->include, B.sites.tab, slots[0], B.sites.list, r->site_cap,
+                                            B.sites.words, B.sites.ent, st)) return rc;
+        if (!r->shape_cap) return 0;
+        return madsim_k_launch_census(B.shape, 1, B.ones, S.out, c->d_seeds, n, r->include, B.shapes.tab, slots[1], B.shapes.list, r->shape_cap, B.shapes.words,
+                                      B.shapes.ent, st);
+    }
+    static int fold(const StallForm& f, const unsigned long long* const* W, madsim_census_value_t* const* E, const uint64_t* ne) {
+        return fold_stall(f.r, W[0], E[0], ne[0], E[1], ne[1]);
+    }
+};
+
 // The report over [seed0, seed0 + total) (seeds == nullptr) or over seeds[0 .. total): chunk after chunk on one stream, each the trace launch
-// into the context's trace set 0, the form's kernels and the copies of the words and of the first Form::eager entries, then one
+// into the context's trace set 0, the form's kernels and, per pass, the copies of the words and of the first Form::eager entries, then one
 // synchronisation: the chunk of a probe vocabulary is done there.  Entries beyond those — and, where the caller still wants runner seeds and
 // the chunk has some, its results — follow by copies of their own.  Once a chunk is queued no error returns before its synchronisation
-// (TraceSteps); an error that may have left the table otherwise than zero marks it dirty; every failure leaves an empty report.
+// (TraceSteps); an error that may have left a table otherwise than zero marks the tables dirty; every failure leaves an empty report.
 template <class Form>
 int obs_report_run(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, const uint64_t* seeds, uint64_t total,
                    uint64_t chunk, const madsim_limits_t* lim, typename Form::Report* rep, bool list) {
     typedef typename Form::Entry Entry;
+    typedef Passes<Form> P;
     const Form f{rep};
     const std::string name = Form::name, noun = Form::noun;
     if (int rc = f.check()) return rc;
@@ -1315,13 +1431,18 @@ int obs_report_run(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim
             if (seeds[i] <= seeds[i - 1]) return fail(MADSIM_E_ARG, name + "_seeds: the seed list is not strictly ascending (sort and deduplicate it first)");
     f.nothing();
     if (total == 0) return 0;
-    // what a chunk asks of the device: per seed the row and the form's words beside it; once the table, the list, the entries, the words
+    // what a chunk asks of the device: per seed the rows and the form's words beside them; once per pass the table, the list, the entries, the words
     // (cap: the entries a chunk may write on the device — the caller's cap, or for the dense matrix its cells)
-    const uint64_t M = MADSIM_TRACE_MAX_BYTES, obs_cap = rep->obs_cap, cap = f.dev_cap();
-    const uint64_t slots = Form::fixed_slots ? Form::fixed_slots : obs_report_slots(cap, Form::min_slots);
-    const uint64_t fixed = slots * Form::slot_bytes + cap * (sizeof(uint32_t) + sizeof(Entry)) + Form::n_words * 8;
-    const uint64_t per_seed = 8 * obs_cap + Form::per_seed_bytes;
-    const uint64_t fits = fixed < M ? std::min<uint64_t>((M - fixed) / per_seed, 0xffffffffull / obs_cap - 1) : 0;
+    const int np = P::count(f);
+    const uint64_t M = MADSIM_TRACE_MAX_BYTES, row_cap = P::row_cap(f);
+    uint64_t cap[P::max] = {}, slots[P::max] = {}, fixed = 0;
+    for (int p = 0; p < np; p++) {
+        cap[p] = P::cap(f, p);
+        slots[p] = Form::fixed_slots ? Form::fixed_slots : obs_report_slots(cap[p], Form::min_slots);
+        fixed += slots[p] * Form::slot_bytes + cap[p] * (sizeof(uint32_t) + sizeof(Entry)) + Form::n_words * 8;
+    }
+    const uint64_t per_seed = P::row_bytes(row_cap) + Form::per_seed_bytes;
+    const uint64_t fits = fixed < M ? std::min<uint64_t>((M - fixed) / per_seed, 0xffffffffull / row_cap - 1) : 0;
     if (chunk == 0) chunk = std::min<uint64_t>(65536, fits);
     if (chunk == 0 || chunk > fits) return fail(MADSIM_E_LIMITS, Form::too_big);
     chunk = std::min(chunk, total);
@@ -1330,46 +1451,62 @@ int obs_report_run(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim
     CTX_ENTER(c);
     hipStream_t st = nullptr;
     madsim_hip_ctx::TraceSet& S = c->trace[0];
-    auto& B = Form::bufs(c);
+    auto& B0 = P::bufs(c, 0);                      // (the range form's seed slice and a chunk's results are staged in the first group)
     const auto failed = [&f](int code, const std::string& msg) { f.nothing(); return fail(code, msg); };
+    const auto dirty = [&] { for (int p = 0; p < np; p++) P::bufs(c, p).dirty = true; };
+    const uint64_t obs_cap = P::task_log ? 0 : row_cap;
     for (uint64_t done = 0; done < total; done += chunk) {
         const uint64_t n = std::min(chunk, total - done);
         Geo G;
-        if ((rc = trace_prepare(c, w, cfg, lim, n, 0, obs_cap, S, G, st))) { f.nothing(); return rc; }
-        if ((rc = B.ensure(slots, cap, chunk, !list, st))) { f.nothing(); return rc; }
-        const uint64_t* src = list ? seeds + done : B.h_seeds.p;
-        if (!list) for (uint64_t i = 0; i < n; i++) B.h_seeds.p[i] = seed0 + done + i;
+        if ((rc = trace_prepare(c, w, cfg, lim, n, 0, obs_cap, S, G, st, P::task_log ? &row_cap : nullptr))) { f.nothing(); return rc; }
+        for (int p = 0; p < np; p++)
+            if ((rc = P::bufs(c, p).ensure(slots[p], cap[p], chunk, !list && p == 0, st))) { f.nothing(); return rc; }
+        if ((rc = P::ensure_rows(c, chunk, row_cap, st))) { f.nothing(); return rc; }
+        const uint64_t* src = list ? seeds + done : B0.h_seeds.p;
+        if (!list) for (uint64_t i = 0; i < n; i++) B0.h_seeds.p[i] = seed0 + done + i;
         TraceSteps step;
         bool ok = step(hipMemcpyAsync(c->d_seeds, src, n * sizeof(uint64_t), hipMemcpyHostToDevice, st), "hipMemcpyAsync(seeds)");
-        if (ok) ok = step(hipMemsetAsync(B.words, 0, Form::n_words * sizeof(unsigned long long), st), Form::at_zero);
+        for (int p = 0; p < np; p++)
+            if (ok) ok = step(hipMemsetAsync(P::bufs(c, p).words, 0, Form::n_words * sizeof(unsigned long long), st), Form::at_zero);
         ok = trace_queue(G, S, n, 0, obs_cap, true, st, step, ok);
         if (ok) {
-            const int refused = f.launch(c, n, slots, st);
+            const int refused = P::launch(f, c, n, slots, st);
             if (refused) step.no_build = true;
             ok = step(refused ? hipSuccess : hipGetLastError(), Form::at_launch);
         }
-        if (ok) ok = step(hipMemcpyAsync(B.h_words, B.words, Form::n_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, st), Form::at_words);
         // the first entries ride behind the words; a chunk with more gets the rest in a copy of its own
-        const uint64_t eager = std::min<uint64_t>(cap, Form::eager);
-        if (ok) ok = step(hipMemcpyAsync(B.h_ent, B.ent, eager * sizeof(Entry), hipMemcpyDeviceToHost, st), Form::at_entries);
-        ok = step(hipStreamSynchronize(st), "hipStreamSynchronize");
-        if (step.err != hipSuccess) { B.dirty = true; return failed(MADSIM_E_HIP, std::string(step.at) + ": " + hipGetErrorString(step.err)); }
-        if (step.no_build) return failed(MADSIM_E_LIMITS, "no trace kernel build, or sizes the " + noun + " kernels refuse");
-        const unsigned long long* W = B.h_words;
-        if (W[1] & Form::err_cap) return failed(MADSIM_E_LIMITS, Form::too_many);      // (the extract pass has cleared the table)
-        if (W[1]) { B.dirty = true; return failed(MADSIM_E_HIP, name + ": the device table was not clean (internal)"); }
-        const uint64_t ne = W[0];
-        if (ne > eager) {
-            const hipError_t e = hipMemcpy(B.h_ent + eager, B.ent + eager, (ne - eager) * sizeof(Entry), hipMemcpyDeviceToHost);
-            if (e != hipSuccess) return failed(MADSIM_E_HIP, "hipMemcpy(" + noun + " entries): " + hipGetErrorString(e));
+        uint64_t eager[P::max] = {};
+        for (int p = 0; p < np; p++) {
+            auto& B = P::bufs(c, p);
+            eager[p] = std::min<uint64_t>(cap[p], Form::eager);
+            if (ok) ok = step(hipMemcpyAsync(B.h_words, B.words, Form::n_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, st), Form::at_words);
+            if (ok) ok = step(hipMemcpyAsync(B.h_ent, B.ent, eager[p] * sizeof(Entry), hipMemcpyDeviceToHost, st), Form::at_entries);
         }
-        if (fold_chunk(f, W, B.h_ent.p, ne)) return failed(MADSIM_E_LIMITS, Form::too_many);
-        if (W[Form::runner_word] && rep->n_runner_listed < rep->runner_cap) {      // chunks and seeds ascend: the first runner_cap met are the smallest
-            hipError_t e = B.h_res.room((size_t)chunk);
-            if (e == hipSuccess) e = hipMemcpy(B.h_res, S.out, n * sizeof(madsim_result_t), hipMemcpyDeviceToHost);
+        ok = step(hipStreamSynchronize(st), "hipStreamSynchronize");
+        if (step.err != hipSuccess) { dirty(); return failed(MADSIM_E_HIP, std::string(step.at) + ": " + hipGetErrorString(step.err)); }
+        if (step.no_build) return failed(MADSIM_E_LIMITS, "no trace kernel build, or sizes the " + noun + " kernels refuse");
+        const unsigned long long* W[P::max] = {};
+        Entry* E[P::max] = {};
+        uint64_t ne[P::max] = {};
+        unsigned long long err = 0;
+        for (int p = 0; p < np; p++) { W[p] = P::bufs(c, p).h_words; E[p] = P::bufs(c, p).h_ent.p; err |= W[p][1]; }
+        if (err & Form::err_cap) return failed(MADSIM_E_LIMITS, Form::too_many);      // (the extract pass has cleared the table)
+        if (err) { dirty(); return failed(MADSIM_E_HIP, name + ": the device table was not clean (internal)"); }
+        for (int p = 0; p < np; p++) {
+            auto& B = P::bufs(c, p);
+            ne[p] = W[p][0];
+            if (ne[p] > eager[p]) {
+                const hipError_t e = hipMemcpy(B.h_ent + eager[p], B.ent + eager[p], (ne[p] - eager[p]) * sizeof(Entry), hipMemcpyDeviceToHost);
+                if (e != hipSuccess) return failed(MADSIM_E_HIP, "hipMemcpy(" + noun + " entries): " + hipGetErrorString(e));
+            }
+        }
+        if (P::fold(f, W, E, ne)) return failed(MADSIM_E_LIMITS, Form::too_many);
+        if (W[0][Form::runner_word] && rep->n_runner_listed < rep->runner_cap) {      // chunks and seeds ascend: the first runner_cap met are the smallest
+            hipError_t e = B0.h_res.room((size_t)chunk);
+            if (e == hipSuccess) e = hipMemcpy(B0.h_res, S.out, n * sizeof(madsim_result_t), hipMemcpyDeviceToHost);
             if (e != hipSuccess) return failed(MADSIM_E_HIP, "hipMemcpy(" + noun + " results): " + hipGetErrorString(e));
             for (uint64_t i = 0; i < n && rep->n_runner_listed < rep->runner_cap; i++)
-                if (MADSIM_IS_RUNNER_VERDICT(B.h_res.p[i].verdict)) rep->runner_seeds[rep->n_runner_listed++] = list ? seeds[done + i] : seed0 + done + i;
+                if (MADSIM_IS_RUNNER_VERDICT(B0.h_res.p[i].verdict)) rep->runner_seeds[rep->n_runner_listed++] = list ? seeds[done + i] : seed0 + done + i;
         }
     }
     return 0;
@@ -1390,6 +1527,21 @@ extern "C" int madsim_k_fold_probe_sets(madsim_probe_sets_t* ps, const unsigned 
 }
 extern "C" int madsim_k_fold_probe_order(madsim_probe_order_t* po, const unsigned long long* words, const madsim_probe_order_pair_t* entries, uint64_t n) {
     return fold_chunk(ProbeOrderForm{po}, words, entries, n);
+}
+
+extern "C" int madsim_k_fold_stall_census(madsim_stall_census_t* sc, const unsigned long long* words, const madsim_census_value_t* sites, uint64_t n_sites,
+                                          const madsim_census_value_t* shapes, uint64_t n_shapes) {
+    return fold_stall(sc, words, sites, n_sites, shapes, n_shapes);
+}
+
+int madsim_hip_ctx_stall_census_range(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total,
+                                      uint64_t chunk, const madsim_limits_t* lim, madsim_stall_census_t* sc) {
+    return obs_report_run<StallForm>(c, w, cfg, seed0, nullptr, total, chunk, lim, sc, false);
+}
+
+int madsim_hip_ctx_stall_census_seeds(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n,
+                                      uint64_t chunk, const madsim_limits_t* lim, madsim_stall_census_t* sc) {
+    return obs_report_run<StallForm>(c, w, cfg, 0, seeds, n, chunk, lim, sc, true);
 }
 
 int madsim_hip_ctx_census_range(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total,
@@ -1426,6 +1578,26 @@ int madsim_hip_ctx_trace_seeds(madsim_hip_ctx_t* c, const madsim_workload_t* w, 
                                const madsim_limits_t* lim, uint8_t* logs, uint64_t log_cap, uint64_t* obs, uint64_t obs_cap,
                                uint64_t* log_len, uint64_t* obs_len, madsim_result_t* out) {
     return trace_list(c, w, cfg, seeds, n, lim, logs, log_cap, obs, obs_cap, log_len, obs_len, out, false);
+}
+
+// Where the listed seeds' tasks stand when their runs end (include/madsim_hip.h "Task post-mortems"): the trace launch of trace_list with the task log
+// and neither of the other two.
+int madsim_hip_ctx_task_states(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n,
+                               const madsim_limits_t* lim, uint64_t* tasks, uint64_t task_cap, uint64_t* task_len, madsim_result_t* out) {
+    const TaskRows tr{tasks, task_cap, task_len};
+    return trace_list(c, w, cfg, seeds, n, lim, nullptr, 0, nullptr, 0, nullptr, nullptr, out, false, &tr);
+}
+
+// The shape of a task table: the sum of mix(site) over its records, mix = splitmix64's finaliser (include/madsim_hip.h).  No device involved.
+uint64_t madsim_hip_stall_shape(const uint64_t* tasks, uint64_t n) {
+    uint64_t s = 0;
+    for (uint64_t i = 0; tasks && i < n; i++) {
+        uint64_t z = MADSIM_TASK_SITE(tasks[i]);
+        z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+        z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+        s += z ^ (z >> 31);
+    }
+    return s;
 }
 
 // One seed of the list form.  (What it always did: at most min(length, cap) bytes of `log` are written, and a null `log` or a zero cap asks
@@ -2595,6 +2767,12 @@ int64_t madsim_hip_trace_seed(const madsim_workload_t* w, const madsim_config_t*
     return madsim_hip_ctx_trace_seed(p.c, w, cfg, seed, lim, log, cap, out);
 }
 
+int madsim_hip_task_states(const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n, const madsim_limits_t* lim,
+                           uint64_t* tasks, uint64_t task_cap, uint64_t* task_len, madsim_result_t* out) {
+    DefaultPin p;
+    return madsim_hip_ctx_task_states(p.c, w, cfg, seeds, n, lim, tasks, task_cap, task_len, out);
+}
+
 int madsim_hip_trace_seeds(const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n, const madsim_limits_t* lim,
                            uint8_t* logs, uint64_t log_cap, uint64_t* obs, uint64_t obs_cap, uint64_t* log_len, uint64_t* obs_len,
                            madsim_result_t* out) {
@@ -2625,6 +2803,18 @@ int madsim_hip_census_seeds(const madsim_workload_t* w, const madsim_config_t* c
                             const madsim_limits_t* lim, madsim_census_t* cen) {
     DefaultPin p;
     return madsim_hip_ctx_census_seeds(p.c, w, cfg, seeds, n, chunk, lim, cen);
+}
+
+int madsim_hip_stall_census_range(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total, uint64_t chunk,
+                                  const madsim_limits_t* lim, madsim_stall_census_t* sc) {
+    DefaultPin p;
+    return madsim_hip_ctx_stall_census_range(p.c, w, cfg, seed0, total, chunk, lim, sc);
+}
+
+int madsim_hip_stall_census_seeds(const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n, uint64_t chunk,
+                                  const madsim_limits_t* lim, madsim_stall_census_t* sc) {
+    DefaultPin p;
+    return madsim_hip_ctx_stall_census_seeds(p.c, w, cfg, seeds, n, chunk, lim, sc);
 }
 
 int madsim_hip_probe_sets_range(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total, uint64_t chunk,

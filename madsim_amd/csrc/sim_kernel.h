@@ -181,6 +181,10 @@ struct KParams {
     // launch writes its determinism log to trace_log + i * trace_cap, its observations to obs_log + i * obs_cap (64-bit words) and its
     // true lengths to trace_len[i] / obs_len[i]; a null obs_log or obs_cap == 0 stores no observation, a null obs_len no length
     uint64_t* obs_log; uint64_t obs_cap; uint64_t* obs_len;
+    // trace builds (after obs_len, same reason): the task log — one word per task still alive when the unit's result is written
+    // (include/madsim_hip.h "Task post-mortems"), in ascending slot order, to task_log + i * task_cap, the true count to task_len[i]; a null
+    // task_log keeps nothing and walks nothing, a unit with a runner verdict writes no record and a count of 0
+    uint64_t* task_log; uint64_t task_cap; uint64_t* task_len;
 };
 
 // The compiled builds, X(TRACE, SPILL, LWS, FEAT, RQ, G) = sim_kernel<Variant<...>>: the trace build; for base-op workloads on
@@ -500,6 +504,20 @@ uint64_t madsim_k_census_slot(uint64_t value, uint64_t slots);
 // totals, and the chunk's `n` entries (any order, distinct values) merged into cen->values[0 .. n_values), which stay ascending by value —
 // counts added, the max of max_per_seed, the min of first_seed.  Returns 0, or -1 with `cen` untouched when the table would pass cen->cap.
 int  madsim_k_fold_census(madsim_census_t* cen, const unsigned long long* words, const madsim_census_value_t* entries, uint64_t n);
+// the stall-site census (madsim_hip_stall_census_range / _seeds), behind the chunk's trace launch on the same stream: stall_sites_kernel over the
+// task rows of `n` seeds (`task_cap` words each, include/madsim_hip.h "Task post-mortems"), their TRUE counts and the results.  sites: n rows of
+// task_cap words — MADSIM_TASK_SITE of each of row i's visible records (the first min(len, task_cap); of a runner verdict's row none: the
+// row and its count are not read), zeros behind; shape: n words, madsim_hip_stall_shape of the visible records; ones: n words, each 1 — the
+// length array under which madsim_k_launch_census folds `shape` as rows of cap 1.  A pure function of its inputs: nothing needs preparing,
+// every word of the three outputs is written, nothing else is.  One wave per row, MADSIM_K_CENSUS_WAVES waves at most.  Returns 0, or -1
+// without launching anything for n == 0, n > 2^31, task_cap outside 1 .. MADSIM_MAX_LIVE_TASKS, n * task_cap >= 2^32 - 1 or a missing array.
+int  madsim_k_launch_stall_sites(const uint64_t* tasks, uint64_t task_cap, const uint64_t* task_len, const madsim_result_t* res, uint64_t n,
+                                 uint64_t* sites, uint64_t* shape, uint64_t* ones, void* stream);
+// the host fold of one chunk into the caller's report (madsim_hip.cpp; no device involved): the site pass's words and entries and the shape
+// pass's entries (null with 0: none), each through madsim_k_fold_census's merge.  Returns 0, or -1 when either table would pass its cap:
+// the report is then to be discarded.
+int  madsim_k_fold_stall_census(madsim_stall_census_t* sc, const unsigned long long* words, const madsim_census_value_t* sites, uint64_t n_sites,
+                                const madsim_census_value_t* shapes, uint64_t n_shapes);
 // the probe-set census (madsim_hip_probe_sets_range / _seeds), behind the chunk's trace launch on the same stream: three kernels over the
 // observation rows of `n` seeds (`obs_cap` words each), their TRUE lengths, the results and the seeds.  sets_mask_kernel writes the set
 // word (include/madsim_hip.h) of every COUNTED row i to sig[i] — `sig`: n 64-bit words of scratch; the words of other rows are neither

@@ -1324,6 +1324,43 @@ __global__ __launch_bounds__(256) void census_extract_kernel(const unsigned long
     }
 }
 
+// ---- the stall-site census: a chunk's task rows made into site rows and shape words, which the observation census's kernels then fold ----
+// stall_sites_kernel, behind the chunk's trace launch: one wave per row, striding as census_fold_kernel does, a row in rounds of 64 records.
+// The visible records of row i are the first min(len, task_cap) — of a row whose verdict is a runner verdict none: neither that row nor
+// its count is read.  Site row i: MADSIM_TASK_SITE of each visible record, zeros behind them (every word of the row is written).  Shape
+// word i: the sum over the visible records of splitmix64's finaliser of the site — a lane's share added up, then a butterfly over the
+// wave: commutative, so the word names the multiset of sites whatever the slot order; 0 for the empty table.  ones[i] = 1: the shape words
+// are folded as rows of cap 1 and length 1.  A pure function of its inputs; the inputs are not written.
+__device__ __forceinline__ unsigned long long stall_mix(unsigned long long z) {
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    return z ^ (z >> 31);
+}
+__global__ __launch_bounds__(256) void stall_sites_kernel(const unsigned long long* __restrict__ tasks, uint32_t task_cap,
+                                                          const unsigned long long* __restrict__ task_len, const madsim_result_t* __restrict__ res,
+                                                          uint32_t n, unsigned long long* __restrict__ sites, unsigned long long* __restrict__ shape,
+                                                          unsigned long long* __restrict__ ones) {
+    const uint32_t lane = threadIdx.x & 63;
+    for (uint32_t i = blockIdx.x * 4u + (threadIdx.x >> 6); i < n; i += gridDim.x * 4u) {      // (wave-uniform)
+        const uint32_t v = reinterpret_cast<const uint32_t*>(res + i)[0];
+        uint32_t vis = 0;
+        if (v < 4u) { const unsigned long long len = task_len[i]; vis = len < task_cap ? (uint32_t)len : task_cap; }
+        const unsigned long long* const row = tasks + (size_t)i * task_cap;
+        unsigned long long* const out = sites + (size_t)i * task_cap;
+        unsigned long long sum = 0;
+        for (uint32_t k = 0; k * 64u < task_cap; k++) {
+            const uint32_t idx = k * 64u + lane;
+            if (idx < task_cap) {
+                unsigned long long site = 0;
+                if (idx < vis) { site = row[idx] >> 32; sum += stall_mix(site); }
+                out[idx] = site;
+            }
+        }
+        for (int o = 32; o; o >>= 1) sum += __shfl_xor(sum, o);
+        if (lane == 0) { shape[i] = sum; ones[i] = 1ull; }
+    }
+}
+
 // ---- the probe-set census: which COMBINATIONS of vocabulary values a chunk's counted seeds reach, each with its per-verdict seed counts ----
 // Three kernels behind the chunk's trace launch.  sets_mask_kernel: one wave per row, striding as census_fold_kernel does; rows of uncounted
 // and runner seeds are not read.  The row index is made scalar (readfirstlane), so the verdict, the length and the loop bounds live in
@@ -1908,6 +1945,19 @@ extern "C" int madsim_k_launch_census_form(const uint64_t* obs, uint64_t obs_cap
     hipLaunchKernelGGL(madsim_k::census_extract_kernel, dim3(xgrid), dim3(256), 0, (hipStream_t)stream, (const unsigned long long*)obs,
                        (uint32_t)(n * obs_cap), (const unsigned long long*)d_seeds, (uint32_t)n, table, (uint32_t)(slots - 1), (const uint32_t*)list,
                        (uint32_t)cap, words, reinterpret_cast<unsigned long long*>(entries));
+    return 0;
+}
+
+// The task rows (`task_cap` words each), their true counts and the results of the chunk's n seeds; sites: n rows of task_cap words, shape and
+// ones: n words each (sim_kernel.h).  Returns 0, or -1 (nothing launched) for sizes the kernel is not written for.
+extern "C" int madsim_k_launch_stall_sites(const uint64_t* tasks, uint64_t task_cap, const uint64_t* task_len, const madsim_result_t* res, uint64_t n,
+                                           uint64_t* sites, uint64_t* shape, uint64_t* ones, void* stream) {
+    if (n == 0 || task_cap == 0 || task_cap > MADSIM_MAX_LIVE_TASKS || n >= 0xffffffffull / task_cap || n > (1ull << 31)) return -1;
+    if (!tasks || !task_len || !res || !sites || !shape || !ones) return -1;
+    const uint64_t waves = n < MADSIM_K_CENSUS_WAVES ? n : MADSIM_K_CENSUS_WAVES;        // one wave per row, 256 workgroups at most
+    hipLaunchKernelGGL(madsim_k::stall_sites_kernel, dim3((uint32_t)((waves + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+                       (const unsigned long long*)tasks, (uint32_t)task_cap, (const unsigned long long*)task_len, res, (uint32_t)n,
+                       (unsigned long long*)sites, (unsigned long long*)shape, (unsigned long long*)ones);
     return 0;
 }
 

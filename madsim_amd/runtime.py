@@ -140,6 +140,20 @@ def lib():
         L.madsim_hip_trace_seeds.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), u64p, C.c_uint64, C.POINTER(A.Limits), C.c_void_p,
                                              C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.madsim_hip_ctx_trace_seeds.argtypes = [ctxp] + L.madsim_hip_trace_seeds.argtypes
+        # task post-mortems: trace_seeds' conventions with one buffer, the task rows, and the host twin of the shape word
+        L.madsim_hip_task_states.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), u64p, C.c_uint64, C.POINTER(A.Limits), C.c_void_p,
+                                             C.c_uint64, C.c_void_p, C.c_void_p]
+        L.madsim_hip_ctx_task_states.argtypes = [ctxp] + L.madsim_hip_task_states.argtypes
+        L.madsim_hip_stall_shape.restype = C.c_uint64
+        L.madsim_hip_stall_shape.argtypes = [C.c_void_p, C.c_uint64]
+        # the stall-site census: the census's signatures with a madsim_stall_census_t
+        L.madsim_hip_stall_census_range.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(A.Limits),
+                                                    C.POINTER(A.StallCensus)]
+        L.madsim_hip_stall_census_seeds.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), u64p, C.c_uint64, C.c_uint64, C.POINTER(A.Limits),
+                                                    C.POINTER(A.StallCensus)]
+        L.madsim_hip_ctx_stall_census_range.argtypes = [ctxp] + L.madsim_hip_stall_census_range.argtypes
+        L.madsim_hip_ctx_stall_census_seeds.argtypes = [ctxp] + L.madsim_hip_stall_census_seeds.argtypes
+        L.madsim_k_fold_stall_census.argtypes = [C.POINTER(A.StallCensus), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]
         # the list campaigns: (seeds, n) where the range forms take (seed0, total); collect, stats and groups in one entry point, each optional
         L.madsim_hip_run_seeds_campaign.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), u64p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32,
                                                     C.POINTER(A.Limits), C.POINTER(A.Campaign), C.POINTER(A.Collect), C.POINTER(A.Stats),
@@ -395,6 +409,113 @@ def trace_seeds(workload, seeds, config=None, limits=None, obs_cap=256, log_cap=
     return _trace_seeds(lambda *a: lib().madsim_hip_trace_seeds(workload.ref(), *a), workload, seeds, config, limits, obs_cap, log_cap, resolve)
 
 
+def task_word(state, prog, pc, cnt0=0, cnt1=0):
+    """A task record as madsim_hip_task_states writes it (include/madsim_hip.h "Task post-mortems"): state | prog | pc | cnt0 | cnt1."""
+    return (int(state) << 56) | (int(prog) << 48) | (int(pc) << 32) | (int(cnt0) << 16) | int(cnt1)
+
+
+def task_fields(word):
+    """(state, prog, pc, cnt0, cnt1) of a task record: the header's MADSIM_TASK_* accessors."""
+    w = int(word)
+    return w >> 56, (w >> 48) & 0xFF, (w >> 32) & 0xFFFF, (w >> 16) & 0xFFFF, w & 0xFFFF
+
+
+def task_site(word):
+    """MADSIM_TASK_SITE: state | prog | pc, the loop registers dropped — the key of a stall census."""
+    return int(word) >> 32
+
+
+def stall_shape(tasks):
+    """madsim_hip_stall_shape: the shape word of a task table (the sum of the mixed sites of its records), computed by the library on the
+    host — what matches a post-mortem against a shape of a stall census.  No device involved."""
+    a = np.ascontiguousarray(np.asarray(tasks, dtype=np.uint64))
+    return int(lib().madsim_hip_stall_shape(a.ctypes.data_as(C.c_void_p) if len(a) else None, len(a)))
+
+
+_RECV_FAMILY = ("RECV", "RECV_TIMEOUT", "RECV_TIMEOUT_AT", "RECV_OR_TICK", "RECV_OR_CTRL_C", "REPLY")
+
+
+def _operands(name, i):
+    """The operands of instruction `i` as its op reads them (include/madsim_hip.h documents each op's a / b / imm)."""
+    if name in _RECV_FAMILY:
+        return f"sock {i.a} tag {i.b >> 8}"
+    if name == "SEND":
+        return f"sock {i.a} to sock {i.b & 0xFF} tag {i.b >> 8}"
+    if name == "RPC_CALL":
+        return f"sock {i.a} to sock {i.b & 0xFF} request {(i.b >> 8) - 0x80}"
+    if name == "CONNECT":
+        return f"sock {i.a} to sock {i.b & 0xFF}"
+    if name in ("BIND", "ACCEPT", "RPC_REPLY", "CLOSE"):
+        return f"sock {i.a}"
+    if name in ("JOIN", "SPAWN", "ABORT"):
+        return f"prog {i.a}"
+    if name in ("SLEEP", "SLEEP_UNTIL"):
+        return f"{i.b} s + {i.imm} ns"
+    if name in ("CRECV", "CTRL_C", "YIELD", "TICK", "DONE"):
+        return ""
+    return f"a={i.a} b={i.b} imm={i.imm}"
+
+
+def describe(workload, site):
+    """A site (or a whole task record) as text, decoded from the workload table on the host: "prog 2 (node 2) pc 20 RECV sock 1 tag 1
+    PARKED" — the op's name and its operands as that op reads them (a socket-table entry, a tag, a program; raw a / b / imm for the rest)."""
+    site = int(site)
+    if site >> 32:
+        site >>= 32
+    state, prog, pc = site >> 24, (site >> 16) & 0xFF, site & 0xFFFF
+    names = {v: k for k, v in A.OP.items()}
+    st = A.TASK_STATE_NAMES.get(state, f"state {state}")
+    if prog >= workload.struct.n_progs or pc >= workload.struct.n_insns:
+        return f"prog {prog} pc {pc} (outside the workload) {st}"
+    i = workload.insns[pc]
+    name = names.get(i.op, f"op {i.op}")
+    return " ".join(x for x in (f"prog {prog} (node {workload.progs[prog].node}) pc {pc} {name}", _operands(name, i), st) if x)
+
+
+def _task_states(call, workload, seeds, config, limits, task_cap, resolve):
+    """Run `call(cfg, seeds*, n, lim, tasks, task_cap, task_len, out)` — a madsim_hip_*task_states entry point with its context and workload
+    bound — over `seeds`, then over the seeds a round leaves re-runnable, each round one further call (as _trace_seeds)."""
+    seeds = [int(s) for s in seeds]
+    if any(not 0 <= s <= A.U64_MAX for s in seeds) or task_cap < 0:
+        raise MadsimHipError("post_mortem: seeds must fit u64, task_cap be >= 0")
+    cfg, lim0 = config or A.Config.default(), limits or A.Limits()
+    n = len(seeds)
+    res, rows, lens = np.zeros(n, dtype=A.RESULT_DTYPE), np.zeros((n, task_cap), dtype=np.uint64), np.zeros(n, dtype=np.uint64)
+    idx = np.arange(n)
+    for r in range(_resolve_rounds(resolve) + 1):
+        if not len(idx):
+            break
+        lim = lim0 if r == 0 else grown_limits(workload, lim0, r)
+        m = len(idx)
+        s = np.array([seeds[i] for i in idx], dtype=np.uint64)
+        t, tl, out = np.zeros((m, task_cap), dtype=np.uint64), np.zeros(m, dtype=np.uint64), np.zeros(m, dtype=A.RESULT_DTYPE)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)                                 # noqa: E731
+        _check(call(C.byref(cfg), s.ctypes.data_as(C.POINTER(C.c_uint64)), m, C.byref(lim), ptr(t) if task_cap else None, task_cap, ptr(tl), ptr(out)))
+        res[idx], rows[idx], lens[idx] = out, t, tl
+        idx = idx[_rerunnable(out, lim)]
+    return res, rows, lens
+
+
+def post_mortem(workload, seeds, task_cap=32, config=None, limits=None, resolve=True, lengths=False):
+    """madsim_hip_task_states: where the tasks of `seeds` (any order, duplicates allowed) stand when their runs end, the whole list in one
+    launch of the trace build.  Returns per seed (result, ndarray[uint64]): its A.Result and the records of the tasks still alive, in task
+    slot order, at most `task_cap` of them (runtime.task_fields / describe decode a record) — with lengths=True (result, records, true
+    count), the count being what task_cap may have cut.  A seed with a runner verdict has no records; resolve=True | rounds replays such
+    seeds under grown_limits(workload, limits, r), as trace_seeds does; resolve=None / False: the one call."""
+    if _inited_device is None:
+        init(0)
+    return _post_mortem(lambda *a: lib().madsim_hip_task_states(workload.ref(), *a), workload, seeds, task_cap, config, limits, resolve, lengths)
+
+
+def _post_mortem(call, workload, seeds, task_cap, config, limits, resolve, lengths):
+    res, rows, lens = _task_states(call, workload, seeds, config, limits, task_cap, resolve)
+    out = []
+    for i in range(len(res)):
+        r, t = A.Result(*[int(x) for x in res[i]]), rows[i, :min(int(lens[i]), task_cap)].copy()
+        out.append((r, t, int(lens[i])) if lengths else (r, t))
+    return out
+
+
 class Divergence:
     """Where the two runs of one seed part (runtime.diverge_seeds): the fields of madsim_divergence_t — `seed`; per channel (`log`: the
     determinism log, one byte per draw; `obs`: the observations) a status (A.DIVERGE_*), `*_at`, the length of the common prefix that was
@@ -599,6 +720,126 @@ def census(workload, seed0=0, total=0, seeds=None, include=(A.PASS, A.PANIC, A.D
     L = lib()
     return _census(lambda *a: L.madsim_hip_census_range(workload.ref(), *a), lambda *a: L.madsim_hip_census_seeds(workload.ref(), *a), workload,
                    seed0, total, seeds, include, obs_cap, max_values, chunk, config, limits, resolve)
+
+
+class StallCensus:
+    """Where the tasks of a census's seeds stand when their runs end, by verdict (runtime.stall_census).  `sites`: ndarray[A.CENSUS_VALUE_DTYPE],
+    ascending by `value` = the site (state << 24 | prog << 16 | pc, runtime.task_site of a record) — per site the counted seeds of each
+    verdict with at least one task there (`n_seeds[4]`), the tasks there (`n_total`), the most inside one seed (`max_per_seed`) and the
+    smallest such seed (`first_seed`).  `shapes`: the same records keyed by the shape word (runtime.stall_shape of a seed's records) — the
+    counted seeds of each verdict with exactly that multiset of sites, `first_seed` the one to replay with runtime.post_mortem.
+    `n_counted[4]` / `n_idle[4]`: counted seeds per verdict / those of them with no live task; `n_truncated`: counted seeds with more than
+    `task_cap` live tasks; `n_tasks`: the sum of every site's n_total; `n_runner` seeds were left with a runner verdict and are counted
+    nowhere, `runner_seeds` the ones listed.  Everything is an exact integer."""
+
+    def __init__(self, sites, shapes, n_counted, n_idle, n_truncated, n_tasks, n_runner, runner_seeds, include, task_cap, want_shapes=True):
+        self.sites, self.shapes = sites, shapes
+        self.n_counted, self.n_idle = tuple(int(x) for x in n_counted), tuple(int(x) for x in n_idle)
+        self.n_truncated, self.n_tasks, self.n_runner = int(n_truncated), int(n_tasks), int(n_runner)
+        self.runner_seeds, self.include, self.task_cap, self.want_shapes = runner_seeds, include, task_cap, want_shapes
+
+    def __len__(self):
+        return len(self.sites)
+
+    def __repr__(self):
+        return (f"StallCensus({len(self.sites)} sites, {len(self.shapes)} shapes over {sum(self.n_counted)} counted seeds, n_counted={self.n_counted}, "
+                f"n_idle={self.n_idle}, n_truncated={self.n_truncated}, n_runner={self.n_runner})")
+
+    def tobytes(self):
+        """The whole report as bytes: two stall censuses are the same exactly when these are equal."""
+        totals = np.array(self.n_counted + self.n_idle + (self.n_truncated, self.n_tasks, self.n_runner), dtype=np.uint64)
+        return self.sites.tobytes() + self.shapes.tobytes() + totals.tobytes() + np.asarray(self.runner_seeds, dtype=np.uint64).tobytes()
+
+    @staticmethod
+    def _row(table, key):
+        i = int(np.searchsorted(table["value"], np.uint64(key)))
+        return table[i] if i < len(table) and int(table["value"][i]) == int(key) else None
+
+    def at(self, prog, pc, state=None):
+        """The site records of tasks of program `prog` standing at instruction `pc` — in every state, or in `state` (A.TASK_*) alone."""
+        v = self.sites["value"]
+        keep = (((v >> np.uint64(16)) & np.uint64(0xFF)) == np.uint64(prog)) & ((v & np.uint64(0xFFFF)) == np.uint64(pc))
+        if state is not None:
+            keep &= (v >> np.uint64(24)) == np.uint64(state)
+        return self.sites[keep]
+
+    def share(self, site, verdict):
+        """Of the counted seeds of `verdict`, the share with at least one task at `site`: a fractions.Fraction, None over no seeds."""
+        r = self._row(self.sites, site)
+        n = self.n_counted[verdict]
+        return Fraction(0 if r is None else int(r["n_seeds"][verdict]), n) if n else None
+
+    def shapes_of(self, verdict):
+        """The shapes that counted seeds of `verdict` ended in, the most frequent first: [(shape word, seeds of that verdict, first seed)] —
+        the first seed being the smallest counted seed with that shape, of whichever counted verdict."""
+        rows = [(int(r["value"]), int(r["n_seeds"][verdict]), int(r["first_seed"])) for r in self.shapes if int(r["n_seeds"][verdict])]
+        return sorted(rows, key=lambda t: (-t[1], t[0]))
+
+    def describe(self, workload):
+        """{site: text} for every site of the table (runtime.describe)."""
+        return {int(v): describe(workload, int(v)) for v in self.sites["value"]}
+
+    def merge(self, other):
+        """The stall census of the union of two DISJOINT seed sets taken under the same include mask and task_cap: exact, in either order.
+        (first_seed of a shape is the smallest seed of the union with that shape.)"""
+        if (self.include, self.task_cap, self.want_shapes) != (other.include, other.task_cap, other.want_shapes):
+            raise MadsimHipError("StallCensus.merge: the two censuses differ in include, task_cap or whether shapes were taken")
+        sites = np.concatenate([self.sites, np.zeros(len(other.sites), dtype=self.sites.dtype)])
+        shapes = np.concatenate([self.shapes, np.zeros(len(other.shapes), dtype=self.shapes.dtype)])
+        rep = A.StallCensus(include=self.include, task_cap=self.task_cap, site_cap=max(len(sites), 1), shape_cap=max(len(shapes), 1),
+                            n_sites=len(self.sites), n_shapes=len(self.shapes))
+        rep.sites, rep.shapes = sites.ctypes.data_as(C.POINTER(A.CensusValue)), shapes.ctypes.data_as(C.POINTER(A.CensusValue))
+        add_a, add_b = np.ascontiguousarray(other.sites), np.ascontiguousarray(other.shapes)
+        if lib().madsim_k_fold_stall_census(C.byref(rep), None, add_a.ctypes.data_as(C.c_void_p), len(add_a), add_b.ctypes.data_as(C.c_void_p), len(add_b)):
+            raise MadsimHipError("StallCensus.merge: madsim_k_fold_stall_census failed")
+        runner = np.sort(np.concatenate([np.asarray(self.runner_seeds, dtype=np.uint64), np.asarray(other.runner_seeds, dtype=np.uint64)]))
+        add4 = lambda a, b: tuple(x + y for x, y in zip(a, b))                      # noqa: E731
+        return StallCensus(sites[:rep.n_sites].copy(), shapes[:rep.n_shapes].copy(), add4(self.n_counted, other.n_counted), add4(self.n_idle, other.n_idle),
+                           self.n_truncated + other.n_truncated, self.n_tasks + other.n_tasks, self.n_runner + other.n_runner, runner, self.include,
+                           self.task_cap, self.want_shapes)
+
+
+def _stall_census(call_range, call_seeds, workload, seed0, total, seeds, include, task_cap, max_sites, max_shapes, chunk, config, limits, resolve):
+    """One stall census call — `call_range(cfg, seed0, total, chunk, lim, sc)` or `call_seeds(cfg, seeds*, n, chunk, lim, sc)`, a
+    madsim_hip_*stall_census_* entry point with its context and workload bound — and its runner seeds settled round by round (_settle)."""
+    cfg, lim0 = config or A.Config.default(), limits or A.Limits()
+    mask = _include_mask(include)
+    rounds = _resolve_rounds(resolve)
+    max_sites, max_shapes = int(max_sites), int(max_shapes)
+
+    def one(lim, sa, s0, n):
+        sites, shapes = np.zeros(max(max_sites, 1), dtype=A.CENSUS_VALUE_DTYPE), np.zeros(max(max_shapes, 1), dtype=A.CENSUS_VALUE_DTYPE)
+        runner = np.zeros(max(n, 1), dtype=np.uint64)
+        sc = A.StallCensus(include=mask, task_cap=task_cap, site_cap=max_sites, shape_cap=max_shapes, runner_cap=n)
+        sc.sites, sc.runner_seeds = sites.ctypes.data_as(C.POINTER(A.CensusValue)), runner.ctypes.data_as(C.POINTER(C.c_uint64))
+        if max_shapes:
+            sc.shapes = shapes.ctypes.data_as(C.POINTER(A.CensusValue))
+        if sa is None:
+            _check(call_range(C.byref(cfg), s0, n, chunk, C.byref(lim), C.byref(sc)))
+        else:
+            _check(call_seeds(C.byref(cfg), _seeds_ptr(sa), n, chunk, C.byref(lim), C.byref(sc)))
+        return StallCensus(sites[:sc.n_sites].copy(), shapes[:sc.n_shapes].copy(), sc.n_counted, sc.n_idle, sc.n_truncated, sc.n_tasks, sc.n_runner,
+                           runner[:sc.n_runner_listed].copy(), mask, task_cap, max_shapes != 0)
+
+    rep = _settle(one, workload, lim0, rounds, seed0, total, seeds, max_sites,
+                  f"stall_census: more than max_sites = {max_sites} distinct sites once the runner seeds are settled")
+    if len(rep.shapes) > max_shapes:
+        raise MadsimHipError(f"stall_census: more than max_shapes = {max_shapes} distinct shapes once the runner seeds are settled")
+    return rep
+
+
+def stall_census(workload, seed0=0, total=0, seeds=None, include=(A.PANIC, A.DEADLOCK, A.TIME_LIMIT), task_cap=32, max_sites=4096, max_shapes=4096,
+                 chunk=0, config=None, limits=None, resolve=True):
+    """madsim_hip_stall_census_range / madsim_hip_stall_census_seeds: where the tasks of the seeds [seed0, seed0 + total) — or of the strictly
+    ascending `seeds` — stand when their runs end, by verdict, reduced on the device: returns a StallCensus.  A seed is counted when its
+    verdict is in `include`; the first `task_cap` live tasks of a seed (slot order) are visible; more than `max_sites` distinct sites or
+    `max_shapes` distinct shapes is MadsimHipError (max_shapes=0: no shapes pass); `chunk` = seeds per trace launch, 0 = the library's
+    default — it never shows in the result.  resolve: as runtime.census."""
+    if _inited_device is None:
+        init(0)
+    L = lib()
+    return _stall_census(lambda *a: L.madsim_hip_stall_census_range(workload.ref(), *a), lambda *a: L.madsim_hip_stall_census_seeds(workload.ref(), *a),
+                         workload, seed0, total, seeds, include, task_cap, max_sites, max_shapes, chunk, config, limits, resolve)
 
 
 class ProbeSets(_ObsReport):
@@ -1621,6 +1862,11 @@ class Context:
         return _trace_seeds(lambda *a: lib().madsim_hip_ctx_trace_seeds(self._h, workload.ref(), *a), workload, seeds, config, limits, obs_cap,
                             log_cap, resolve)
 
+    def post_mortem(self, workload, seeds, task_cap=32, config=None, limits=None, resolve=True, lengths=False):
+        """runtime.post_mortem on this context (madsim_hip_ctx_task_states)."""
+        return _post_mortem(lambda *a: lib().madsim_hip_ctx_task_states(self._h, workload.ref(), *a), workload, seeds, task_cap, config, limits,
+                            resolve, lengths)
+
     def diverge_seeds(self, workload, seeds, other=None, config=None, other_config=None, limits=None, other_limits=None, log_cap=1 << 16,
                       obs_cap=256, window=4, resolve=True):
         """runtime.diverge_seeds on this context (madsim_hip_ctx_diverge_seeds)."""
@@ -1634,6 +1880,14 @@ class Context:
         return _census(lambda *a: L.madsim_hip_ctx_census_range(self._h, workload.ref(), *a),
                        lambda *a: L.madsim_hip_ctx_census_seeds(self._h, workload.ref(), *a), workload, seed0, total, seeds, include, obs_cap,
                        max_values, chunk, config, limits, resolve)
+
+    def stall_census(self, workload, seed0=0, total=0, seeds=None, include=(A.PANIC, A.DEADLOCK, A.TIME_LIMIT), task_cap=32, max_sites=4096,
+                     max_shapes=4096, chunk=0, config=None, limits=None, resolve=True):
+        """runtime.stall_census on this context (madsim_hip_ctx_stall_census_range / madsim_hip_ctx_stall_census_seeds)."""
+        L = lib()
+        return _stall_census(lambda *a: L.madsim_hip_ctx_stall_census_range(self._h, workload.ref(), *a),
+                             lambda *a: L.madsim_hip_ctx_stall_census_seeds(self._h, workload.ref(), *a), workload, seed0, total, seeds, include,
+                             task_cap, max_sites, max_shapes, chunk, config, limits, resolve)
 
     def probe_sets(self, workload, vocabulary=None, seed0=0, total=0, seeds=None, include=(A.PASS, A.PANIC, A.DEADLOCK, A.TIME_LIMIT), obs_cap=256,
                    max_sets=4096, chunk=0, config=None, limits=None, resolve=True):
