@@ -233,6 +233,46 @@ pub struct madsim_probe_order_t {
 
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
+pub struct madsim_span_def_t {
+    pub from: u64,
+    pub to: u64,
+    pub flags: u32,
+    pub reserved: u32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct madsim_span_t {
+    pub n_state: [u64; 16],
+    pub n: u64,
+    pub min: u64,
+    pub max: u64,
+    pub sum_lo: u64,
+    pub sum_hi: u64,
+    pub min_seed: u64,
+    pub max_seed: u64,
+    pub first_open_seed: u64,
+    pub hist: [u64; 256],
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct madsim_probe_spans_t {
+    pub include: u32,
+    pub obs_cap: u32,
+    pub defs: *const madsim_span_def_t,
+    pub n_spans: u64,
+    pub spans: *const madsim_span_t,
+    pub runner_seeds: *const u64,
+    pub runner_cap: u64,
+    pub n_counted: [u64; 4],
+    pub n_truncated: u64,
+    pub n_runner: u64,
+    pub n_runner_listed: u64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
 pub struct madsim_stall_census_t {
     pub include: u32,
     pub task_cap: u32,
@@ -587,6 +627,12 @@ pub const MADSIM_PROBE_SETS_MAX: u32 = 1048576;
 pub const MADSIM_PROBE_SET_OTHER: u64 = 0x4000000000000000;
 pub const MADSIM_PROBE_SET_TRUNCATED: u64 = 0x8000000000000000;
 pub const MADSIM_PROBE_ORDER_MAX_VOCAB: u32 = 32;
+pub const MADSIM_PROBE_SPANS_MAX: u32 = 16;
+pub const MADSIM_SPAN_FROM_START: u32 = 1;
+pub const MADSIM_SPAN_ABSENT: u32 = 0;
+pub const MADSIM_SPAN_CLOSED: u32 = 1;
+pub const MADSIM_SPAN_OPEN: u32 = 2;
+pub const MADSIM_SPAN_CUT: u32 = 3;
 pub const MADSIM_CAMPAIGN_STOP_AT_FAILURE: u32 = 1;
 pub const MADSIM_CAMPAIGN_LIST_RUNNER: u32 = 2;
 pub const MADSIM_CAMPAIGN_STOP_AT_CAP: u32 = 4;
@@ -652,6 +698,7 @@ extern "C" {
     pub fn madsim_hip_observe_seed(w: *const madsim_workload_t, cfg: *const madsim_config_t, seed: u64, lim: *const madsim_limits_t, obs: *mut u64, cap: u64, out: *mut madsim_result_t) -> i64;
     pub fn madsim_hip_task_states(w: *const madsim_workload_t, cfg: *const madsim_config_t, seeds: *const u64, n: u64, lim: *const madsim_limits_t, tasks: *mut u64, task_cap: u64, task_len: *mut u64, out: *mut madsim_result_t) -> c_int;
     pub fn madsim_hip_stall_shape(tasks: *const u64, n: u64) -> u64;
+    pub fn madsim_hip_timeline_seeds(w: *const madsim_workload_t, cfg: *const madsim_config_t, seeds: *const u64, n: u64, lim: *const madsim_limits_t, obs: *mut u64, times: *mut u64, obs_cap: u64, obs_len: *mut u64, out: *mut madsim_result_t) -> c_int;
     pub fn madsim_hip_diverge_seeds(wA: *const madsim_workload_t, cfgA: *const madsim_config_t, limA: *const madsim_limits_t, wB: *const madsim_workload_t, cfgB: *const madsim_config_t, limB: *const madsim_limits_t, seeds: *const u64, n: u64, log_cap: u64, obs_cap: u64, win: u32, recs: *mut madsim_divergence_t, obs_ctx: *mut u64) -> c_int;
     pub fn madsim_hip_census_range(w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, chunk: u64, lim: *const madsim_limits_t, cen: *mut madsim_census_t) -> c_int;
     pub fn madsim_hip_census_seeds(w: *const madsim_workload_t, cfg: *const madsim_config_t, seeds: *const u64, n: u64, chunk: u64, lim: *const madsim_limits_t, cen: *mut madsim_census_t) -> c_int;
@@ -659,6 +706,9 @@ extern "C" {
     pub fn madsim_hip_probe_sets_seeds(w: *const madsim_workload_t, cfg: *const madsim_config_t, seeds: *const u64, n: u64, chunk: u64, lim: *const madsim_limits_t, ps: *mut madsim_probe_sets_t) -> c_int;
     pub fn madsim_hip_probe_order_range(w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, chunk: u64, lim: *const madsim_limits_t, po: *mut madsim_probe_order_t) -> c_int;
     pub fn madsim_hip_probe_order_seeds(w: *const madsim_workload_t, cfg: *const madsim_config_t, seeds: *const u64, n: u64, chunk: u64, lim: *const madsim_limits_t, po: *mut madsim_probe_order_t) -> c_int;
+    pub fn madsim_hip_probe_spans_range(w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, chunk: u64, lim: *const madsim_limits_t, ps: *mut madsim_probe_spans_t) -> c_int;
+    pub fn madsim_hip_probe_spans_seeds(w: *const madsim_workload_t, cfg: *const madsim_config_t, seeds: *const u64, n: u64, chunk: u64, lim: *const madsim_limits_t, ps: *mut madsim_probe_spans_t) -> c_int;
+    pub fn madsim_hip_span_merge(into: *mut madsim_span_t, from: *const madsim_span_t);
     pub fn madsim_hip_stall_census_range(w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, chunk: u64, lim: *const madsim_limits_t, sc: *mut madsim_stall_census_t) -> c_int;
     pub fn madsim_hip_stall_census_seeds(w: *const madsim_workload_t, cfg: *const madsim_config_t, seeds: *const u64, n: u64, chunk: u64, lim: *const madsim_limits_t, sc: *mut madsim_stall_census_t) -> c_int;
     pub fn madsim_hip_ctx_run_batch(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, count: u64, lim: *const madsim_limits_t, out: *mut madsim_result_t, summary: *mut madsim_summary_t) -> c_int;
@@ -670,6 +720,7 @@ extern "C" {
     pub fn madsim_hip_ctx_trace_seeds(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seeds: *const u64, n: u64, lim: *const madsim_limits_t, logs: *mut u8, log_cap: u64, obs: *mut u64, obs_cap: u64, log_len: *mut u64, obs_len: *mut u64, out: *mut madsim_result_t) -> c_int;
     pub fn madsim_hip_ctx_observe_seed(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed: u64, lim: *const madsim_limits_t, obs: *mut u64, cap: u64, out: *mut madsim_result_t) -> i64;
     pub fn madsim_hip_ctx_task_states(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seeds: *const u64, n: u64, lim: *const madsim_limits_t, tasks: *mut u64, task_cap: u64, task_len: *mut u64, out: *mut madsim_result_t) -> c_int;
+    pub fn madsim_hip_ctx_timeline_seeds(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seeds: *const u64, n: u64, lim: *const madsim_limits_t, obs: *mut u64, times: *mut u64, obs_cap: u64, obs_len: *mut u64, out: *mut madsim_result_t) -> c_int;
     pub fn madsim_hip_ctx_diverge_seeds(ctx: *mut madsim_hip_ctx_t, wA: *const madsim_workload_t, cfgA: *const madsim_config_t, limA: *const madsim_limits_t, wB: *const madsim_workload_t, cfgB: *const madsim_config_t, limB: *const madsim_limits_t, seeds: *const u64, n: u64, log_cap: u64, obs_cap: u64, win: u32, recs: *mut madsim_divergence_t, obs_ctx: *mut u64) -> c_int;
     pub fn madsim_hip_ctx_census_range(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, chunk: u64, lim: *const madsim_limits_t, cen: *mut madsim_census_t) -> c_int;
     pub fn madsim_hip_ctx_census_seeds(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seeds: *const u64, n: u64, chunk: u64, lim: *const madsim_limits_t, cen: *mut madsim_census_t) -> c_int;
@@ -677,6 +728,8 @@ extern "C" {
     pub fn madsim_hip_ctx_probe_sets_seeds(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seeds: *const u64, n: u64, chunk: u64, lim: *const madsim_limits_t, ps: *mut madsim_probe_sets_t) -> c_int;
     pub fn madsim_hip_ctx_probe_order_range(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, chunk: u64, lim: *const madsim_limits_t, po: *mut madsim_probe_order_t) -> c_int;
     pub fn madsim_hip_ctx_probe_order_seeds(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seeds: *const u64, n: u64, chunk: u64, lim: *const madsim_limits_t, po: *mut madsim_probe_order_t) -> c_int;
+    pub fn madsim_hip_ctx_probe_spans_range(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, chunk: u64, lim: *const madsim_limits_t, ps: *mut madsim_probe_spans_t) -> c_int;
+    pub fn madsim_hip_ctx_probe_spans_seeds(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seeds: *const u64, n: u64, chunk: u64, lim: *const madsim_limits_t, ps: *mut madsim_probe_spans_t) -> c_int;
     pub fn madsim_hip_ctx_stall_census_range(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, total: u64, chunk: u64, lim: *const madsim_limits_t, sc: *mut madsim_stall_census_t) -> c_int;
     pub fn madsim_hip_ctx_stall_census_seeds(ctx: *mut madsim_hip_ctx_t, w: *const madsim_workload_t, cfg: *const madsim_config_t, seeds: *const u64, n: u64, chunk: u64, lim: *const madsim_limits_t, sc: *mut madsim_stall_census_t) -> c_int;
     pub fn madsim_hip_run_batch_multi(ctxs: *const *mut madsim_hip_ctx_t, n_ctx: c_int, w: *const madsim_workload_t, cfg: *const madsim_config_t, seed0: u64, count: u64, lim: *const madsim_limits_t, out: *mut madsim_result_t, summary: *mut madsim_summary_t, max_rounds: c_int) -> c_int;

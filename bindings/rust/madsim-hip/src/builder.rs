@@ -308,6 +308,71 @@ impl Census {
     }
 }
 
+/// When one seed traced what it traced (`Builder::timeline`): `result`, its 48 bytes; `observations`, the first `obs_cap` values its test
+/// body handed to trace / trace_time / a traced tick, and `times`, the runtime's elapsed nanoseconds at each of them (what trace_instant
+/// would have folded there) — two vectors of one length, the times never decreasing; `n_observations`, how many values there were.
+#[derive(Clone, Debug)]
+pub struct SeedTimeline {
+    pub seed: u64,
+    pub result: sys::madsim_result_t,
+    pub observations: Vec<u64>,
+    pub times: Vec<u64>,
+    pub n_observations: u64,
+}
+
+/// How long, in virtual nanoseconds, from one traced value to another over a range of seeds (`Builder::probe_spans`): `definitions`, the
+/// spans asked for (`ProbeSpans::between` / `ProbeSpans::start`); `spans`, one `madsim_span_t` per definition in that order — counted seeds
+/// per verdict and `sys::MADSIM_SPAN_*` state, and over the CLOSED ones n, min, max, the 128-bit sum, the histogram under
+/// `madsim_hip_stat_bucket`, the smallest seeds attaining the extremes and the smallest OPEN seed; `totals`, the counts (its pointers are
+/// null); `runner_seeds`, the seeds left with a runner verdict.
+#[derive(Clone, Debug)]
+pub struct ProbeSpans {
+    pub definitions: Vec<sys::madsim_span_def_t>,
+    pub spans: Vec<sys::madsim_span_t>,
+    pub totals: sys::madsim_probe_spans_t,
+    pub runner_seeds: Vec<u64>,
+}
+
+impl ProbeSpans {
+    /// From the first `from` to the first `to` behind it (`from == to`: the time between the first two occurrences).
+    pub fn between(from: u64, to: u64) -> sys::madsim_span_def_t {
+        sys::madsim_span_def_t { from, to, flags: 0, reserved: 0 }
+    }
+
+    /// From the start of the run to the first `to`.
+    pub fn start(to: u64) -> sys::madsim_span_def_t {
+        sys::madsim_span_def_t { from: 0, to, flags: sys::MADSIM_SPAN_FROM_START, reserved: 0 }
+    }
+
+    /// How many counted seeds closed span `i`.
+    pub fn closed(&self, i: usize) -> u64 {
+        self.spans[i].n
+    }
+
+    /// Counted seeds of span `i` in `sys::MADSIM_SPAN_*` state `state`, over the verdicts of the bit mask `verdicts`.
+    pub fn state(&self, i: usize, state: u32, verdicts: u32) -> u64 {
+        (0..4).filter(|k| (verdicts >> k) & 1 != 0).map(|k| self.spans[i].n_state[4 * k + state as usize]).sum()
+    }
+
+    /// The exact sum of span `i`'s durations.
+    pub fn total(&self, i: usize) -> u128 {
+        (self.spans[i].sum_hi as u128) << 64 | self.spans[i].sum_lo as u128
+    }
+
+    /// The smallest seed whose span `i` took the longest / the shortest; the smallest counted seed that never closed it.
+    pub fn slowest(&self, i: usize) -> Option<u64> {
+        if self.spans[i].n > 0 { Some(self.spans[i].max_seed) } else { None }
+    }
+
+    pub fn fastest(&self, i: usize) -> Option<u64> {
+        if self.spans[i].n > 0 { Some(self.spans[i].min_seed) } else { None }
+    }
+
+    pub fn never_closed(&self, i: usize) -> Option<u64> {
+        if self.state(i, sys::MADSIM_SPAN_OPEN, 0xf) > 0 { Some(self.spans[i].first_open_seed) } else { None }
+    }
+}
+
 /// Where one seed's tasks stand when its run ends (`Builder::post_mortem`): `result`, its 48 bytes; `tasks`, the first `task_cap` records
 /// of the tasks still alive, in task-slot order — bits 63-56 the state (`sys::MADSIM_TASK_PARKED` / `_QUEUED` / `_PANICKED` /
 /// `_CANCELLED`), 55-48 the program, 47-32 the instruction, 31-16 and 15-0 the loop registers —; `n_tasks`, how many there were.  A seed
@@ -837,6 +902,129 @@ impl Builder {
             idx = again;
         }
         Ok(out)
+    }
+
+    /// When `seeds` traced what they traced (`madsim_hip_ctx_timeline_seeds`): any order, duplicates allowed, the whole list in ONE launch
+    /// of the trace build, one `SeedTimeline` per seed in the order given.  `resolve_runner` rounds apply as in `post_mortem`.
+    pub fn timeline(&self, workload: &Workload, seeds: &[u64], obs_cap: usize) -> Result<Vec<SeedTimeline>, RunError> {
+        let w = workload.raw();
+        let cfg = self.config.raw();
+        let lim0 = self.raw_limits(true);
+        let ctx = contexts()?.0[0];
+        let zero: sys::madsim_result_t = unsafe { std::mem::zeroed() };
+        let mut out: Vec<SeedTimeline> =
+            seeds.iter().map(|&seed| SeedTimeline { seed, result: zero, observations: Vec::new(), times: Vec::new(), n_observations: 0 }).collect();
+        let mut idx: Vec<usize> = (0..seeds.len()).collect();
+        for r in 0..=self.resolve_rounds() {
+            if idx.is_empty() {
+                break;
+            }
+            let mut lim = lim0;
+            if r > 0 {
+                let rc = unsafe { sys::madsim_hip_grow_limits(&w, &lim0, r, &mut lim) };
+                if rc != 0 {
+                    return Err(last_error(rc));
+                }
+            }
+            let m = idx.len();
+            let s: Vec<u64> = idx.iter().map(|&i| seeds[i]).collect();
+            let (mut obs, mut tim, mut lens) = (vec![0u64; m * obs_cap], vec![0u64; m * obs_cap], vec![0u64; m]);
+            let mut res = vec![zero; m];
+            let rc = unsafe {
+                sys::madsim_hip_ctx_timeline_seeds(ctx, &w, &cfg, s.as_ptr(), m as u64, &lim, obs.as_mut_ptr(), tim.as_mut_ptr(), obs_cap as u64,
+                                                   lens.as_mut_ptr(), res.as_mut_ptr())
+            };
+            if rc != 0 {
+                return Err(last_error(rc));
+            }
+            let cap = if lim.max_steps != 0 { lim.max_steps } else { 1 << 24 };
+            let ceiling = if lim.max_steps_ceiling != 0 { lim.max_steps_ceiling } else { 1 << 28 };
+            let mut again = Vec::new();
+            for (j, &i) in idx.iter().enumerate() {
+                let t = &mut out[i];
+                let k = (lens[j] as usize).min(obs_cap);
+                t.result = res[j];
+                t.n_observations = lens[j];
+                t.observations = obs[j * obs_cap..j * obs_cap + k].to_vec();
+                t.times = tim[j * obs_cap..j * obs_cap + k].to_vec();
+                if res[j].verdict == sys::MADSIM_OVERFLOW || (res[j].verdict == sys::MADSIM_STEP_LIMIT && cap < ceiling) {
+                    again.push(i);
+                }
+            }
+            idx = again;
+        }
+        Ok(out)
+    }
+
+    /// How long from the first traced `from` to the first `to` behind it, for 1 .. 16 `definitions`, over the seeds
+    /// `self.seed .. self.seed + self.count` (`madsim_hip_ctx_probe_spans_range`): the range run on the trace build with the time log and
+    /// reduced on the device to one record per definition.  `include`, `obs_cap`: as `census`.  With `resolve_runner` set, the seeds a call
+    /// leaves with a runner verdict are run again in one list call per round and merged in (`madsim_hip_span_merge`).
+    pub fn probe_spans(&self, workload: &Workload, definitions: &[sys::madsim_span_def_t], include: u32, obs_cap: u32) -> Result<ProbeSpans, RunError> {
+        self.probe_spans_over(workload, definitions, None, include, obs_cap)
+    }
+
+    /// `probe_spans` over an explicit, strictly ascending seed list (`madsim_hip_ctx_probe_spans_seeds`).
+    pub fn probe_spans_seeds(&self, workload: &Workload, definitions: &[sys::madsim_span_def_t], seeds: &[u64], include: u32, obs_cap: u32) -> Result<ProbeSpans, RunError> {
+        self.probe_spans_over(workload, definitions, Some(seeds), include, obs_cap)
+    }
+
+    fn probe_spans_over(&self, workload: &Workload, definitions: &[sys::madsim_span_def_t], seeds: Option<&[u64]>, include: u32, obs_cap: u32) -> Result<ProbeSpans, RunError> {
+        let w = workload.raw();
+        let cfg = self.config.raw();
+        let lim0 = self.raw_limits(true);
+        let ctx = contexts()?.0[0];
+        let one = |lim: &sys::madsim_limits_t, list: Option<&[u64]>| -> Result<ProbeSpans, RunError> {
+            let n = list.map_or(self.count, |l| l.len() as u64);
+            let mut spans: Vec<sys::madsim_span_t> = vec![unsafe { std::mem::zeroed() }; definitions.len().max(1)];
+            let mut runner = vec![0u64; (n as usize).max(1)];
+            let mut ps: sys::madsim_probe_spans_t = unsafe { std::mem::zeroed() };
+            ps.include = include;
+            ps.obs_cap = obs_cap;
+            ps.defs = definitions.as_ptr();
+            ps.n_spans = definitions.len() as u64;
+            ps.spans = spans.as_mut_ptr() as *const _;                   // (the library writes through both)
+            ps.runner_seeds = runner.as_mut_ptr() as *const _;
+            ps.runner_cap = n;
+            let rc = unsafe {
+                match list {
+                    Some(l) => sys::madsim_hip_ctx_probe_spans_seeds(ctx, &w, &cfg, l.as_ptr(), n, 0, lim, &mut ps),
+                    None => sys::madsim_hip_ctx_probe_spans_range(ctx, &w, &cfg, self.seed, n, 0, lim, &mut ps),
+                }
+            };
+            if rc != 0 {
+                return Err(last_error(rc));
+            }
+            spans.truncate(definitions.len());
+            runner.truncate(ps.n_runner_listed as usize);
+            ps.defs = std::ptr::null();
+            ps.spans = std::ptr::null();
+            ps.runner_seeds = std::ptr::null();
+            Ok(ProbeSpans { definitions: definitions.to_vec(), spans, totals: ps, runner_seeds: runner })
+        };
+        let mut c = one(&lim0, seeds)?;
+        for r in 1..=self.resolve_rounds() {
+            if c.runner_seeds.is_empty() {
+                break;
+            }
+            let mut lim = lim0;
+            let rc = unsafe { sys::madsim_hip_grow_limits(&w, &lim0, r, &mut lim) };
+            if rc != 0 {
+                return Err(last_error(rc));
+            }
+            let more = one(&lim, Some(&c.runner_seeds))?;
+            for (a, b) in c.spans.iter_mut().zip(more.spans.iter()) {
+                unsafe { sys::madsim_hip_span_merge(a, b) };
+            }
+            for k in 0..4 {
+                c.totals.n_counted[k] += more.totals.n_counted[k];
+            }
+            c.totals.n_truncated += more.totals.n_truncated;
+            c.totals.n_runner = more.totals.n_runner;
+            c.totals.n_runner_listed = more.totals.n_runner_listed;
+            c.runner_seeds = more.runner_seeds;
+        }
+        Ok(c)
     }
 
     fn resolve_rounds(&self) -> u32 {

@@ -13,6 +13,6 @@ pub mod workload;
 #[cfg(all(feature = "madsim", madsim))]
 pub mod interp;
 
-pub use builder::{fold_observations, Builder, Census, Diff, Divergence, Failures, Groups, ListCampaign, NetConfig, PostMortem, ProbeOrder, ProbeSets, RunError, SeedTrace, StallCensus, Stats, Sweep};
+pub use builder::{fold_observations, Builder, Census, Diff, Divergence, Failures, Groups, ListCampaign, NetConfig, PostMortem, ProbeOrder, ProbeSets, ProbeSpans, RunError, SeedTimeline, SeedTrace, StallCensus, Stats, Sweep};
 pub use madsim_hip_sys as sys;
 pub use workload::{pingpong, pingpong_twin, Addr, TaskBuilder, TaskId, Workload, WorkloadBuilder};

@@ -661,6 +661,26 @@ int madsim_hip_task_states(const madsim_workload_t* w, const madsim_config_t* cf
  * whatever their loop registers say.  The empty table's shape is 0.  No device involved. */
 uint64_t madsim_hip_stall_shape(const uint64_t* tasks, uint64_t n);
 
+/* Timelines: WHEN the listed seeds traced what they traced.  The observation log holds the values; the trace builds keep beside each value
+ * the virtual time of the observation — the runtime's elapsed nanoseconds at that instruction, the number MS_OP_TRACE_TIME a=1
+ * (trace_instant) would fold there.  It is the time of the observation, not the value: a traced tick folds the deadline it was scheduled
+ * for, which may lie before the clock, and its time entry is the clock.  Within a row the times never decrease.  Stamping every traced
+ * value of a test body with a trace_instant behind it leaves the run's result unchanged, so the oracle's observation list of that stamped
+ * twin is the reference: its odd entries are this call's time row.
+ *
+ * madsim_hip_timeline_seeds is madsim_hip_trace_seeds with the time rows beside the observation rows and no determinism log: ONE launch of
+ * the trace build over `n` seeds (any order, duplicates allowed), one synchronisation, row i belongs to seeds[i].
+ *   obs, times: n rows of obs_cap 64-bit words each (both required, obs_cap > 0): times[i * obs_cap + k] is when obs[i * obs_cap + k] was
+ *               traced; both rows hold their first min(len, obs_cap) entries and zeros behind them
+ *   obs_len:    n TRUE lengths (may be NULL), the one length of both rows
+ *   out:        n results (may be NULL), as madsim_hip_trace_seeds gives them.  No silent re-run: a seed with a runner verdict
+ *               (MADSIM_IS_RUNNER_VERDICT) has rows that are not meaningful; replay it under madsim_hip_grow_limits
+ * n == 0 returns 0 and touches nothing.  MADSIM_E_ARG: seeds == NULL with n > 0; a missing row array or obs_cap == 0.  MADSIM_E_LIMITS:
+ * n * (16 * obs_cap + 72) exceeds MADSIM_TRACE_MAX_BYTES; the list is never split. */
+int madsim_hip_timeline_seeds(const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n,
+                              const madsim_limits_t* lim, uint64_t* obs, uint64_t* times, uint64_t obs_cap, uint64_t* obs_len,
+                              madsim_result_t* out);
+
 /* Divergence reports: where two variants of a seed's run first part.  A differential campaign says WHICH seeds a change affected;
  * madsim_hip_diverge_seeds says UP TO WHERE the two runs of each listed seed are the same run, on two rulers: the determinism log (one
  * byte per GlobalRng::with, "channel log") and the observation log (one 64-bit word per traced value, "channel obs").  Side A is
@@ -880,6 +900,77 @@ int madsim_hip_probe_order_range(const madsim_workload_t* w, const madsim_config
 int madsim_hip_probe_order_seeds(const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n, uint64_t chunk,
                                  const madsim_limits_t* lim, madsim_probe_order_t* po);
 
+/* Probe spans: HOW LONG, in virtual time, from one traced value to another — "after the kill, how long until a leader is elected again?",
+ * "which seed has the slowest recovery, and which seeds never recover?" — as a distribution over a range of seeds.  The seeds run on the
+ * trace build as for the census, with the time log beside the observation log (madsim_hip_timeline_seeds' launch: "Timelines" above); per
+ * chunk two kernels behind the trace launch reduce the rows where they lie.  No row and no per-seed word travels to the host.
+ * madsim_hip_probe_spans_range takes [seed0, seed0 + total), madsim_hip_probe_spans_seeds a STRICTLY ASCENDING list.
+ *
+ * The caller gives 1 .. MADSIM_PROBE_SPANS_MAX span definitions {from, to, flags} (every value is legal; from == to is the time between the
+ * first two occurrences, a period; equal definitions are allowed and give equal records) and `include` and `obs_cap` with
+ * madsim_census_t's meaning and limits.  A seed is COUNTED exactly as in the census.  Per counted seed and span, over the visible
+ * observations (the first min(len, obs_cap)):
+ *   i = the first index whose value is `from` — or, with MADSIM_SPAN_FROM_START, -1: the start of the run, time 0; `from` is then ignored
+ *   j = the first index greater than i whose value is `to`
+ *   MADSIM_SPAN_ABSENT  there is no i
+ *   MADSIM_SPAN_CLOSED  i and j exist: the duration is time[j] - time[i] (time[-1] = 0), unsigned; the clock never goes back.  A span closed
+ *                       inside a cut prefix is the true one
+ *   MADSIM_SPAN_OPEN    an i but no j, and len <= obs_cap: the run ended first
+ *   MADSIM_SPAN_CUT     an i but no j, and len > obs_cap: unknown, counted apart
+ * spans[s], one record per definition, in definition order: n_state[4 * verdict + state] the counted seeds; over the CLOSED seeds of all counted
+ * verdicts n, min, max, the exact 128-bit sum of the durations, hist[madsim_hip_stat_bucket(duration)], and min_seed / max_seed, the
+ * smallest seed that attains each extreme; first_open_seed, the smallest counted seed that is OPEN: the one to replay.  Where there is no
+ * such seed: the seed is UINT64_MAX, min is UINT64_MAX and max 0, as madsim_metric_t has it.  n_counted, n_truncated (counted seeds with
+ * len > obs_cap), n_runner, runner_seeds / runner_cap / n_runner_listed: as the probe-order census has them.
+ * Everything is exact and all-integer, a function of each seed's (result, observation list, time list) alone: the same bytes whatever
+ * `chunk`, the form, the context and the run.  No atomic decides a seed: every witness is a minimum.  There is no "too many".
+ * One chunk (0 = a default, 65 536 or what fits) asks the device for chunk * (16 * obs_cap + 72 + 12 * n_spans) + 2240 * n_spans + 64
+ * bytes: MADSIM_E_LIMITS when that exceeds MADSIM_TRACE_MAX_BYTES or chunk * obs_cap >= 2^32 - 1 — never split silently.
+ * total == 0 / n == 0 reports the empty result.  MADSIM_E_ARG: ps == NULL; include == 0 or a bit at or above 4; obs_cap == 0 or above
+ * MADSIM_CENSUS_MAX_OBS_CAP; n_spans == 0 or above MADSIM_PROBE_SPANS_MAX; defs == NULL or spans == NULL; a flag other than
+ * MADSIM_SPAN_FROM_START; runner_cap > 0 without runner_seeds; seeds == NULL with n > 0; a list that is not strictly ascending. */
+#define MADSIM_PROBE_SPANS_MAX 16u
+#define MADSIM_SPAN_FROM_START 1u
+#define MADSIM_SPAN_ABSENT 0u
+#define MADSIM_SPAN_CLOSED 1u
+#define MADSIM_SPAN_OPEN 2u
+#define MADSIM_SPAN_CUT 3u
+typedef struct madsim_span_def {       /* 24 bytes */
+    uint64_t from, to;
+    uint32_t flags;                    /* 0 or MADSIM_SPAN_FROM_START */
+    uint32_t reserved;                 /* ignored */
+} madsim_span_def_t;
+typedef struct madsim_span {           /* 2240 bytes */
+    uint64_t n_state[16];              /* [4 * verdict + MADSIM_SPAN_*]: counted seeds                                            */
+    uint64_t n;                        /* CLOSED seeds over the counted verdicts                                                  */
+    uint64_t min, max;                 /* of their durations; UINT64_MAX and 0 when n == 0                                        */
+    uint64_t sum_lo, sum_hi;           /* the 128-bit sum of their durations                                                      */
+    uint64_t min_seed, max_seed;       /* the smallest seed whose duration is min / max; UINT64_MAX when n == 0                   */
+    uint64_t first_open_seed;          /* the smallest counted seed that is OPEN; UINT64_MAX when there is none                   */
+    uint64_t hist[256];                /* [MADSIM_STAT_BUCKETS]: CLOSED seeds per bucket of madsim_hip_stat_bucket(duration)      */
+} madsim_span_t;
+typedef struct madsim_probe_spans {    /* 104 bytes */
+    uint32_t include;                  /* in: as madsim_census_t.include                                                          */
+    uint32_t obs_cap;                  /* in: as madsim_census_t.obs_cap                                                          */
+    const madsim_span_def_t* defs;     /* in: caller's host array [n_spans]                                                       */
+    uint64_t n_spans;                  /* in: 1 .. MADSIM_PROBE_SPANS_MAX                                                         */
+    madsim_span_t* spans;              /* in: caller's host array [n_spans]; out: one record per definition                       */
+    uint64_t* runner_seeds;            /* in: caller's host array [runner_cap]; may be NULL when runner_cap == 0                  */
+    uint64_t runner_cap;
+    uint64_t n_counted[4];             /* out: counted seeds per verdict                                                          */
+    uint64_t n_truncated;              /* out: counted seeds with more than obs_cap observations                                  */
+    uint64_t n_runner;                 /* out: seeds with a runner verdict                                                        */
+    uint64_t n_runner_listed;          /* out: min(n_runner, runner_cap), the entries of runner_seeds written                     */
+} madsim_probe_spans_t;
+int madsim_hip_probe_spans_range(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total, uint64_t chunk,
+                                 const madsim_limits_t* lim, madsim_probe_spans_t* ps);
+int madsim_hip_probe_spans_seeds(const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n, uint64_t chunk,
+                                 const madsim_limits_t* lim, madsim_probe_spans_t* ps);
+/* The record of one definition over the union of two DISJOINT seed sets: `from` merged into `into` — counts, the sum and the histogram add,
+ * of two equal extremes the smaller seed wins, first_open_seed is the minimum.  What settles runner seeds under grown limits and merges
+ * reports of several ranges; exact, in either order.  No device involved. */
+void madsim_hip_span_merge(madsim_span_t* into, const madsim_span_t* from);
+
 /* Stall-site census: WHERE the tasks of a range's seeds stand when their runs end, by verdict — "409 of the 412 deadlocking seeds have a
  * task of program 2 parked in the recv_from at pc 7", with no probe placed in advance.  The seeds run on the trace build with the task log
  * alone (madsim_hip_task_states' launch: log_cap 0, obs_cap 0, the caller's task_cap); per chunk the work runs behind the trace launch on
@@ -955,6 +1046,9 @@ int64_t madsim_hip_ctx_observe_seed(madsim_hip_ctx_t* ctx, const madsim_workload
 int madsim_hip_ctx_task_states(madsim_hip_ctx_t* ctx, const madsim_workload_t* w, const madsim_config_t* cfg,
                                const uint64_t* seeds, uint64_t n, const madsim_limits_t* lim, uint64_t* tasks, uint64_t task_cap,
                                uint64_t* task_len, madsim_result_t* out);
+int madsim_hip_ctx_timeline_seeds(madsim_hip_ctx_t* ctx, const madsim_workload_t* w, const madsim_config_t* cfg,
+                                  const uint64_t* seeds, uint64_t n, const madsim_limits_t* lim, uint64_t* obs, uint64_t* times,
+                                  uint64_t obs_cap, uint64_t* obs_len, madsim_result_t* out);
 int madsim_hip_ctx_diverge_seeds(madsim_hip_ctx_t* ctx, const madsim_workload_t* wA, const madsim_config_t* cfgA,
                                  const madsim_limits_t* limA, const madsim_workload_t* wB, const madsim_config_t* cfgB,
                                  const madsim_limits_t* limB, const uint64_t* seeds, uint64_t n, uint64_t log_cap,
@@ -971,6 +1065,11 @@ int madsim_hip_ctx_probe_order_range(madsim_hip_ctx_t* ctx, const madsim_workloa
                                      uint64_t total, uint64_t chunk, const madsim_limits_t* lim, madsim_probe_order_t* po);
 int madsim_hip_ctx_probe_order_seeds(madsim_hip_ctx_t* ctx, const madsim_workload_t* w, const madsim_config_t* cfg,
                                      const uint64_t* seeds, uint64_t n, uint64_t chunk, const madsim_limits_t* lim, madsim_probe_order_t* po);
+int madsim_hip_ctx_probe_spans_range(madsim_hip_ctx_t* ctx, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0,
+                                     uint64_t total, uint64_t chunk, const madsim_limits_t* lim, madsim_probe_spans_t* ps);
+int madsim_hip_ctx_probe_spans_seeds(madsim_hip_ctx_t* ctx, const madsim_workload_t* w, const madsim_config_t* cfg,
+                                     const uint64_t* seeds, uint64_t n, uint64_t chunk, const madsim_limits_t* lim,
+                                     madsim_probe_spans_t* ps);
 int madsim_hip_ctx_stall_census_range(madsim_hip_ctx_t* ctx, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0,
                                       uint64_t total, uint64_t chunk, const madsim_limits_t* lim, madsim_stall_census_t* sc);
 int madsim_hip_ctx_stall_census_seeds(madsim_hip_ctx_t* ctx, const madsim_workload_t* w, const madsim_config_t* cfg,

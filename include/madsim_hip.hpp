@@ -18,6 +18,7 @@
 #include <array>
 #include <cctype>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -1322,6 +1323,124 @@ struct Builder {
             c.totals.n_truncated += more.totals.n_truncated;
             c.totals.n_runner = more.totals.n_runner; c.totals.n_runner_listed = more.totals.n_runner_listed;
             c.totals.n_pairs = c.pairs.size();
+            c.runner_seeds = more.runner_seeds;
+        }
+        return c;
+    }
+
+    // When the listed seeds traced what they traced (madsim_hip_timeline_seeds): the values trace_seeds returns and, beside each, the runtime's
+    // elapsed nanoseconds at that observation — what trace_instant would have folded there.  `observations` and `times` hold the first obs_cap
+    // entries, n_observations says how many there were.  The builder's resolve_runner() rounds replay seeds with a runner verdict, as trace_seeds does.
+    struct SeedTimeline {
+        uint64_t seed = 0;
+        madsim_result_t result{};
+        std::vector<uint64_t> observations, times;
+        uint64_t n_observations = 0;
+    };
+    std::vector<SeedTimeline> timeline(const Workload& wl, const std::vector<uint64_t>& seeds, size_t obs_cap = 256) const {
+        madsim::check(madsim_hip_init(device));
+        madsim_workload_t w = wl.raw();
+        madsim_config_t cfg = config.raw();
+        madsim_limits_t lim0 = capacities;
+        if (time_limit) { lim0.time_limit_ns = (uint64_t)(*time_limit * 1e9 + 0.5); if (!lim0.time_limit_ns) lim0.time_limit_ns = 1; }
+        std::vector<SeedTimeline> out(seeds.size());
+        std::vector<size_t> idx(seeds.size());
+        for (size_t i = 0; i < idx.size(); i++) idx[i] = i;
+        const uint32_t rounds = resolve_rounds();
+        for (uint32_t r = 0; r <= rounds && !idx.empty(); r++) {
+            madsim_limits_t lim = lim0;
+            if (r) madsim::check(madsim_hip_grow_limits(&w, &lim0, r, &lim));
+            const size_t m = idx.size();
+            std::vector<uint64_t> s(m), obs(m * obs_cap), tim(m * obs_cap), lens(m);
+            std::vector<madsim_result_t> res(m);
+            for (size_t j = 0; j < m; j++) s[j] = seeds[idx[j]];
+            madsim::check(madsim_hip_timeline_seeds(&w, &cfg, s.data(), m, &lim, obs.data(), tim.data(), obs_cap, lens.data(), res.data()));
+            std::vector<size_t> again;
+            const uint32_t cap = lim.max_steps ? lim.max_steps : 1u << 24, ceiling = lim.max_steps_ceiling ? lim.max_steps_ceiling : 1u << 28;
+            for (size_t j = 0; j < m; j++) {
+                SeedTimeline& t = out[idx[j]];
+                const size_t k = (size_t)std::min<uint64_t>(lens[j], obs_cap);
+                t.seed = s[j]; t.result = res[j]; t.n_observations = lens[j];
+                t.observations.assign(obs.begin() + j * obs_cap, obs.begin() + j * obs_cap + k);
+                t.times.assign(tim.begin() + j * obs_cap, tim.begin() + j * obs_cap + k);
+                if (res[j].verdict == MADSIM_OVERFLOW || (res[j].verdict == MADSIM_STEP_LIMIT && cap < ceiling)) again.push_back(idx[j]);
+            }
+            idx.swap(again);
+        }
+        return out;
+    }
+
+    // How long, in virtual nanoseconds, from the first traced `from` to the first `to` behind it over the builder's seeds
+    // (madsim_hip_probe_spans_range / madsim_hip_probe_spans_seeds): `seed .. seed + count`, or the over_seeds() list, run on the trace build
+    // with the time log and reduced on the device to one record per definition.  Span::start(to) begins at the start of the run.  This
+    // builder's resolve_runner() rounds apply as in census().
+    struct Span {
+        static madsim_span_def_t between(uint64_t from, uint64_t to) { return madsim_span_def_t{from, to, 0, 0}; }
+        static madsim_span_def_t start(uint64_t to) { return madsim_span_def_t{0, to, MADSIM_SPAN_FROM_START, 0}; }
+    };
+    struct ProbeSpans {
+        std::vector<madsim_span_def_t> definitions;
+        std::vector<madsim_span_t> spans;          // one per definition, in that order
+        madsim_probe_spans_t totals{};             // the counts (the pointers and caps are the call's own: not meaningful here)
+        std::vector<uint64_t> runner_seeds;
+        uint64_t closed(size_t i) const { return spans[i].n; }
+        uint64_t state(size_t i, uint32_t st, uint32_t verdicts = 0xf) const {      // counted seeds of span i in MADSIM_SPAN_* state st
+            uint64_t n = 0;
+            for (int k = 0; k < 4; k++) if ((verdicts >> k) & 1u) n += spans[i].n_state[4 * k + st];
+            return n;
+        }
+        long double mean(size_t i) const { return spans[i].n ? ((long double)spans[i].sum_hi * 18446744073709551616.0L + (long double)spans[i].sum_lo) / (long double)spans[i].n : 0.0L; }
+        // lo <= the q-quantile (nearest rank) of span i's durations <= hi: its bucket of the histogram, narrowed by the exact min and max
+        std::pair<uint64_t, uint64_t> quantile_bounds(size_t i, double q) const {
+            const madsim_span_t& s = spans[i];
+            if (!s.n) throw Error(MADSIM_E_ARG, "quantile_bounds: no seed closed this span");
+            uint64_t rank = (uint64_t)std::ceil(q * (double)s.n), acc = 0;
+            if (rank < 1) rank = 1;
+            if (rank > s.n) rank = s.n;
+            for (uint32_t b = 0; b < MADSIM_STAT_BUCKETS; b++) {
+                acc += s.hist[b];
+                if (acc >= rank) {
+                    const uint64_t lo = madsim_hip_stat_bucket_floor(b), next = madsim_hip_stat_bucket_floor(b + 1);
+                    return {std::max(lo, s.min), std::min(next == UINT64_MAX ? next : next - 1, s.max)};
+                }
+            }
+            return {s.min, s.max};
+        }
+        std::optional<uint64_t> slowest(size_t i) const { return spans[i].n ? std::optional<uint64_t>(spans[i].max_seed) : std::nullopt; }
+        std::optional<uint64_t> fastest(size_t i) const { return spans[i].n ? std::optional<uint64_t>(spans[i].min_seed) : std::nullopt; }
+        std::optional<uint64_t> never_closed(size_t i) const { return state(i, MADSIM_SPAN_OPEN) ? std::optional<uint64_t>(spans[i].first_open_seed) : std::nullopt; }
+    };
+    ProbeSpans probe_spans(const Workload& wl, const std::vector<madsim_span_def_t>& definitions, uint32_t obs_cap = 256, uint32_t include = 0xf, uint64_t chunk = 0) const {
+        madsim::check(madsim_hip_init(device));
+        madsim_workload_t w = wl.raw();
+        madsim_config_t cfg = config.raw();
+        madsim_limits_t lim0 = capacities;
+        if (time_limit) { lim0.time_limit_ns = (uint64_t)(*time_limit * 1e9 + 0.5); if (!lim0.time_limit_ns) lim0.time_limit_ns = 1; }
+        const uint32_t rounds = resolve_rounds();
+        auto one = [&](const madsim_limits_t& lim, const std::vector<uint64_t>* list) {
+            ProbeSpans c;
+            const uint64_t n = list ? list->size() : count;
+            c.definitions = definitions;
+            c.spans.resize(definitions.size() ? definitions.size() : 1);
+            c.runner_seeds.resize(n ? n : 1);
+            madsim_probe_spans_t& t = c.totals;
+            t.include = include; t.obs_cap = obs_cap; t.defs = definitions.data(); t.n_spans = definitions.size(); t.spans = c.spans.data();
+            t.runner_seeds = c.runner_seeds.data(); t.runner_cap = n;
+            madsim::check(list ? madsim_hip_probe_spans_seeds(&w, &cfg, list->data(), n, chunk, &lim, &t) : madsim_hip_probe_spans_range(&w, &cfg, seed, n, chunk, &lim, &t));
+            c.spans.resize(definitions.size());
+            c.runner_seeds.resize(t.n_runner_listed);
+            t.defs = nullptr; t.spans = nullptr; t.runner_seeds = nullptr;
+            return c;
+        };
+        ProbeSpans c = one(lim0, listed_seeds ? &seed_list : nullptr);
+        for (uint32_t r = 1; r <= rounds && !c.runner_seeds.empty(); r++) {
+            madsim_limits_t lim = lim0;
+            madsim::check(madsim_hip_grow_limits(&w, &lim0, r, &lim));
+            const ProbeSpans more = one(lim, &c.runner_seeds);
+            for (size_t i = 0; i < c.spans.size(); i++) madsim_hip_span_merge(&c.spans[i], &more.spans[i]);
+            for (int k = 0; k < 4; k++) c.totals.n_counted[k] += more.totals.n_counted[k];
+            c.totals.n_truncated += more.totals.n_truncated;
+            c.totals.n_runner = more.totals.n_runner; c.totals.n_runner_listed = more.totals.n_runner_listed;
             c.runner_seeds = more.runner_seeds;
         }
         return c;

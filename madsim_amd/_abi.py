@@ -362,6 +362,45 @@ assert C.sizeof(ProbeOrderPair) == 72 and C.sizeof(ProbeOrder) == 152
 HEADER_STRUCTS["madsim_probe_order_pair_t"] = ProbeOrderPair
 HEADER_STRUCTS["madsim_probe_order_t"] = ProbeOrder
 
+# madsim_hip_probe_spans_range / _seeds: the most span definitions of one call, the one flag, the states of a (seed, span)
+PROBE_SPANS_MAX = 16
+SPAN_FROM_START = 1
+SPAN_ABSENT, SPAN_CLOSED, SPAN_OPEN, SPAN_CUT = 0, 1, 2, 3
+SPAN_STATE_NAMES = {SPAN_ABSENT: "ABSENT", SPAN_CLOSED: "CLOSED", SPAN_OPEN: "OPEN", SPAN_CUT: "CUT"}
+
+
+class SpanDef(C.Structure):
+    """madsim_span_def_t: from the first `from` (flags = SPAN_FROM_START: from the start of the run) to the first `to` behind it.  (`from` is
+    a Python keyword: getattr(d, "from"), or the numpy view SPAN_DEF_DTYPE.)"""
+    _fields_ = [("from", C.c_uint64), ("to", C.c_uint64), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class Span(C.Structure):
+    """madsim_span_t: the counted seeds per verdict and state, and over the CLOSED ones the distribution of the durations with the seeds
+    that attain its extremes; the smallest OPEN seed."""
+    _fields_ = [("n_state", C.c_uint64 * 16), ("n", C.c_uint64), ("min", C.c_uint64), ("max", C.c_uint64), ("sum_lo", C.c_uint64),
+                ("sum_hi", C.c_uint64), ("min_seed", C.c_uint64), ("max_seed", C.c_uint64), ("first_open_seed", C.c_uint64),
+                ("hist", C.c_uint64 * STAT_BUCKETS)]
+
+
+class ProbeSpans(C.Structure):
+    """madsim_probe_spans_t: which verdicts count, how many observations of a seed are visible, the definitions and the caller's two arrays
+    going in; the totals coming out."""
+    _fields_ = [("include", C.c_uint32), ("obs_cap", C.c_uint32), ("defs", C.POINTER(SpanDef)), ("n_spans", C.c_uint64), ("spans", C.POINTER(Span)),
+                ("runner_seeds", C.POINTER(C.c_uint64)), ("runner_cap", C.c_uint64), ("n_counted", C.c_uint64 * 4), ("n_truncated", C.c_uint64),
+                ("n_runner", C.c_uint64), ("n_runner_listed", C.c_uint64)]
+
+
+# numpy views: madsim_span_def_t, madsim_span_t (n_state[4 * verdict + state] seen as [verdict][state]); SPAN_REC_WORDS: the 64-bit words of a record, on the device and on the host
+SPAN_DEF_DTYPE = [("from", "<u8"), ("to", "<u8"), ("flags", "<u4"), ("reserved", "<u4")]
+SPAN_DTYPE = [("n_state", "<u8", (4, 4)), ("n", "<u8"), ("min", "<u8"), ("max", "<u8"), ("sum_lo", "<u8"), ("sum_hi", "<u8"), ("min_seed", "<u8"),
+              ("max_seed", "<u8"), ("first_open_seed", "<u8"), ("hist", "<u8", (STAT_BUCKETS,))]
+SPAN_REC_WORDS = 280
+assert C.sizeof(SpanDef) == 24 and C.sizeof(Span) == 2240 == 8 * SPAN_REC_WORDS and C.sizeof(ProbeSpans) == 104
+HEADER_STRUCTS["madsim_span_def_t"] = SpanDef
+HEADER_STRUCTS["madsim_span_t"] = Span
+HEADER_STRUCTS["madsim_probe_spans_t"] = ProbeSpans
+
 # madsim_hip_task_states: the state byte of a task record (bits 63-56; prog 55-48, pc 47-32, cnt0 31-16, cnt1 15-0)
 TASK_PARKED, TASK_QUEUED, TASK_PANICKED, TASK_CANCELLED = 1, 2, 3, 4
 TASK_STATE_NAMES = {TASK_PARKED: "PARKED", TASK_QUEUED: "QUEUED", TASK_PANICKED: "PANICKED", TASK_CANCELLED: "CANCELLED"}

@@ -74,11 +74,6 @@ __device__ __forceinline__ uint32_t progress_priority(uint32_t pass, uint32_t es
 // is cap-guarded and the host zero-fills it; the count is the true one.  A runner verdict writes no record.
 // The three parameters are read once per finished seed: from the kernel-argument segment where they are used (PTASK: k_state.h cold_read), never
 // held in scalar registers through the pass loop, where the trace builds have none to spare (what the log costs them: profiles/stall_ab.md).
-#ifdef MADSIM_EMU
-#define PTASK(f) (P.f)
-#else
-#define PTASK(f) cold_read<true>(P.f, (uint32_t)offsetof(KParams, f))
-#endif
 template <class K>
 __device__ __forceinline__ void task_log_write(const Ctx& c, uint32_t verdict, uint64_t unit) {
     const KParams& P = c.P;

@@ -95,11 +95,20 @@ __device__ __forceinline__ void rng_log(const Ctx& c, Lane& L, bool have = false
 
 // One observed value (MS_OP_TRACE, MS_OP_TRACE_TIME, a traced tick): folded into obs_hash; the trace builds also keep the value itself,
 // the first obs_cap of a seed (rng_log's rule: the length counts on past the cap).
+// The time log (sim_kernel.h KParams::obs_time_words) keeps, at the same index of the unit's time row, the clock AT the observation — what
+// MS_OP_TRACE_TIME a=1 would fold here —, not the value: a traced tick folds the deadline it was scheduled for, and its time entry is the
+// clock.  The time row's address is the observation row's plus the wave-uniform distance between the two logs, read from the
+// kernel-argument segment at the store (PTASK: k_state.h): no lane or context state of its own; a distance of 0 stores nothing.
 template <class K>
 __device__ __forceinline__ void obs_fold(const Ctx& c, Lane& L, uint64_t v) {
     L.obs_hash = (L.obs_hash ^ v) * FNV_PRIME;
     if (K::TRACE) {
-        if (c.olog && L.obs_len < c.P.obs_cap) c.olog[L.obs_len] = v;
+        if (c.olog && L.obs_len < c.P.obs_cap) {
+            uint64_t* const at = c.olog + L.obs_len;
+            *at = v;
+            const KParams& P = c.P;
+            if (const uint32_t behind = PTASK(obs_time_words)) at[behind] = L.clock;
+        }
         L.obs_len++;
     }
 }

@@ -119,6 +119,13 @@ template <bool ON, class T> __device__ __forceinline__ T cold_read(const T& hot,
 }
 #define PCOLD(f) cold_read<ColdParams<K>::ON>(P.f, (uint32_t)offsetof(KParams, f))
 #endif
+// The trace builds' own cold parameters (the task log: k_main.h task_log_write; the time log: k_rng.h obs_fold): read from the kernel-argument
+// segment where they are used whatever ColdParams says, never held in scalar registers through the pass loop, where the trace builds have none to spare.
+#ifdef MADSIM_EMU
+#define PTASK(f) (P.f)
+#else
+#define PTASK(f) cold_read<true>(P.f, (uint32_t)offsetof(KParams, f))
+#endif
 // for (i = start; i < P.f; i++) with a cold bound: read once where the loop begins in the builds with cold parameters, the loop as it was written in the others
 #define PCOLD_FOR(i_, start_, f_) for (uint32_t i_ = (start_), i_##_n = ColdParams<K>::ON ? PCOLD(f_) : 0u; i_ < (ColdParams<K>::ON ? i_##_n : P.f_); i_++)
 // Wave-uniform yes/no parameters tested on the send path (has_clog, has_clog_link, buggify): held by value each is a 64-bit lane mask; the builds with

@@ -227,7 +227,7 @@ struct madsim_hip_resources {
     // One side's buffers of a trace launch: the rows of the determinism log (bytes) and of the observation log (words), the length words
     // and the results.  Set 0 is what every trace call uses, set 1 side B of a divergence report; set 0's `out` is also the result
     // buffer of run_host and run_list.
-    struct TraceSet { DevBuf<uint8_t> log; DevBuf<uint64_t> obs, len; DevBuf<madsim_result_t> out; DevBuf<uint64_t> task, task_len; };      // (task, task_len: the task log, only where a call asks for it)
+    struct TraceSet { DevBuf<uint8_t> log; DevBuf<uint64_t> obs, len; DevBuf<madsim_result_t> out; DevBuf<uint64_t> task, task_len; };      // (task, task_len: the task log, only where a call asks for it; obs: with the time log its rows too, n * obs_cap words behind the observation rows)
     TraceSet trace[2];
     DevBuf<madsim_divergence_t> d_drec; DevBuf<uint64_t> d_dctx;      // divergence reports: the records and the context rows
     // One census form's buffers (the observation census, the probe-set census, the probe-order census: each its own, the slots differ in size): the table (all zero
@@ -273,6 +273,11 @@ struct madsim_hip_resources {
         ObsReport<madsim_census_value_t, MADSIM_K_CENSUS_SLOT_BYTES, MADSIM_K_CENSUS_WORDS> sites, shapes;
         DevBuf<uint64_t> rows, shape, ones;
     } stall;
+    // probe spans: the chunk's records take the entries' place (one per definition; the table and the claim list are not used) and what
+    // span_fold_kernel writes for span_witness_kernel (device only): state and duration per (seed, span)
+    struct Spans : ObsReport<madsim_k_span_rec_t, 4, MADSIM_K_PROBE_SPANS_WORDS> {
+        DevBuf<uint32_t> st; DevBuf<unsigned long long> dur;
+    } probe_spans;
     Event ev0, ev1;
     Event pipe_begin;                         // run_pipelined: before the first sub-batch of a call
     Event tev[2 * 64];                        // timing slots of madsim_hip_run_batch_async
@@ -957,14 +962,16 @@ struct TraceSteps {
 };
 
 static int trace_prepare(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, const madsim_limits_t* lim, uint64_t n,
-                         uint64_t log_cap, uint64_t obs_cap, madsim_hip_ctx::TraceSet& S, Geo& G, hipStream_t st, const uint64_t* task_cap = nullptr) {
+                         uint64_t log_cap, uint64_t obs_cap, madsim_hip_ctx::TraceSet& S, Geo& G, hipStream_t st, const uint64_t* task_cap = nullptr, bool times = false) {
     int rc;
     if ((rc = madsim_geo::make_geometry(c->dev(), w, cfg, lim, n, &G, &g_err, true))) return rc;
     G.P.count = n;
     if ((rc = c->upload_workload(w, G.P))) return rc;
     if ((rc = c->ensure_scratch(G.P, st, false))) return rc;
     HIP_TRY(S.log.room((size_t)(n * log_cap)));
-    HIP_TRY(S.obs.room((size_t)(n * obs_cap)));
+    times = times && obs_cap;                                                // (never without the observation log: the kernel addresses the time row from it)
+    if (times && n * obs_cap > 0xffffffffull) return fail(MADSIM_E_LIMITS, "the time log: n x obs_cap exceeds 2^32 - 1 words");
+    HIP_TRY(S.obs.room((size_t)(n * obs_cap * (times ? 2 : 1))));           // (the time rows: the second half, only where a call asks for them)
     HIP_TRY(S.len.room((size_t)(2 * n)));                                    // [n] log lengths, then [n] observation counts
     HIP_TRY(c->d_seeds.room((size_t)n));
     HIP_TRY(S.out.room((size_t)n));
@@ -980,6 +987,7 @@ static int trace_prepare(madsim_hip_ctx_t* c, const madsim_workload_t* w, const 
     G.P.trace_log = log_cap ? S.log : nullptr; G.P.trace_cap = log_cap; G.P.trace_len = S.len;
     G.P.obs_log = obs_cap ? S.obs : nullptr; G.P.obs_cap = obs_cap; G.P.obs_len = S.len + n;
     if (task_cap) { G.P.task_log = S.task; G.P.task_cap = *task_cap; G.P.task_len = S.task_len; }
+    if (times) G.P.obs_time_words = (uint32_t)(n * obs_cap);
     return 0;
 }
 
@@ -987,6 +995,7 @@ static bool trace_queue(const Geo& G, const madsim_hip_ctx::TraceSet& S,uint64_t
                         TraceSteps& step, bool ok) {
     if (ok && log_cap && zero_log) ok = step(hipMemsetAsync(S.log, 0, n * log_cap, st), "hipMemsetAsync(log rows)");
     if (ok && obs_cap) ok = step(hipMemsetAsync(S.obs, 0, n * obs_cap * sizeof(uint64_t), st), "hipMemsetAsync(observation rows)");
+    if (ok && obs_cap && G.P.obs_time_words) ok = step(hipMemsetAsync(S.obs + n * obs_cap, 0, n * obs_cap * sizeof(uint64_t), st), "hipMemsetAsync(time rows)");
     if (ok) ok = step(hipMemsetAsync(S.len, 0, 2 * n * sizeof(uint64_t), st), "hipMemsetAsync(lengths)");
     if (ok && G.P.task_log && G.P.task_cap) ok = step(hipMemsetAsync(S.task, 0, n * G.P.task_cap * sizeof(uint64_t), st), "hipMemsetAsync(task rows)");
     if (ok && G.P.task_log) ok = step(hipMemsetAsync(S.task_len, 0, n * sizeof(uint64_t), st), "hipMemsetAsync(task counts)");
@@ -1007,13 +1016,15 @@ static bool trace_queue(const Geo& G, const madsim_hip_ctx::TraceSet& S,uint64_t
 // bytes and nothing behind them, so the device row needs no zeroes —, no bound on `log_cap` but the device's memory, and results that
 // carry the fingerprint whatever the limits say.  The list form answers with the bytes madsim_hip_run_batch gives: the trace builds always
 // fold the determinism log, so under madsim_limits_t.no_trace_hash its results' trace_hash is zeroed here.
-// (`tr`: madsim_hip_task_states — one more optional buffer, the task log's rows and counts; madsim_hip_trace_seeds passes none and queues what it queued)
+// (`tr`: madsim_hip_task_states — one more optional buffer, the task log's rows and counts; `times`: madsim_hip_timeline_seeds — the time
+// log's rows beside the observation rows; madsim_hip_trace_seeds passes neither and queues what it queued)
 struct TaskRows { uint64_t* tasks; uint64_t cap; uint64_t* len; };
 static int trace_list(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n,
                       const madsim_limits_t* lim, uint8_t* logs, uint64_t log_cap, uint64_t* obs, uint64_t obs_cap,
-                      uint64_t* log_len, uint64_t* obs_len, madsim_result_t* out, bool single, const TaskRows* tr = nullptr) {
+                      uint64_t* log_len, uint64_t* obs_len, madsim_result_t* out, bool single, const TaskRows* tr = nullptr, uint64_t* times = nullptr) {
     if (n == 0) return 0;
-    if (!seeds) return fail(MADSIM_E_ARG, tr ? "task_states: null seed list" : "trace_seeds: null seed list");
+    if (!seeds) return fail(MADSIM_E_ARG, tr ? "task_states: null seed list" : times ? "timeline_seeds: null seed list" : "trace_seeds: null seed list");
+    if (times && !obs) return fail(MADSIM_E_ARG, "timeline_seeds: time rows without observation rows");
     if (tr) {
         if ((tr->tasks != nullptr) != (tr->cap != 0)) return fail(MADSIM_E_ARG, "task_states: `tasks` and task_cap are given together or not at all");
         if (tr->cap > MADSIM_MAX_LIVE_TASKS) return fail(MADSIM_E_ARG, "task_states: task_cap exceeds MADSIM_MAX_LIVE_TASKS");
@@ -1024,8 +1035,9 @@ static int trace_list(madsim_hip_ctx_t* c, const madsim_workload_t* w, const mad
         // what the call asks of the device, per seed: the two rows, the two lengths, the seed and the result
         const uint64_t M = MADSIM_TRACE_MAX_BYTES;
         if (log_cap > M || obs_cap > M / 8 || n > M) return fail(MADSIM_E_LIMITS, "trace_seeds: more than MADSIM_TRACE_MAX_BYTES of device memory");
-        const uint64_t per_seed = log_cap + 8 * obs_cap + 3 * sizeof(uint64_t) + sizeof(madsim_result_t) + (tr ? 8 * tr->cap : 0);
-        if (per_seed > M / n) return fail(MADSIM_E_LIMITS, tr ? "task_states: n x (8 task_cap + 72) exceeds MADSIM_TRACE_MAX_BYTES: fewer seeds per call, or a smaller task_cap"
+        const uint64_t per_seed = log_cap + (times ? 16 : 8) * obs_cap + 3 * sizeof(uint64_t) + sizeof(madsim_result_t) + (tr ? 8 * tr->cap : 0);
+        if (per_seed > M / n) return fail(MADSIM_E_LIMITS, times ? "timeline_seeds: n x (16 obs_cap + 72) exceeds MADSIM_TRACE_MAX_BYTES: fewer seeds per call, or a smaller obs_cap" :
+                                                              tr ? "task_states: n x (8 task_cap + 72) exceeds MADSIM_TRACE_MAX_BYTES: fewer seeds per call, or a smaller task_cap"
                                                               : "trace_seeds: n x (log_cap + 8 obs_cap + 72) exceeds MADSIM_TRACE_MAX_BYTES: fewer seeds per call, or smaller caps");
     }
     CTX_ENTER(c);
@@ -1034,7 +1046,7 @@ static int trace_list(madsim_hip_ctx_t* c, const madsim_workload_t* w, const mad
     Geo G;
     hipStream_t st = nullptr;
     madsim_hip_ctx::TraceSet& S = c->trace[0];
-    if ((rc = trace_prepare(c, w, cfg, lim, n, log_cap, obs_cap, S, G, st, tr ? &tr->cap : nullptr))) return rc;
+    if ((rc = trace_prepare(c, w, cfg, lim, n, log_cap, obs_cap, S, G, st, tr ? &tr->cap : nullptr, times != nullptr))) return rc;
     uint64_t* d_olen = S.len + n;
     // from here on the stream may hold work on the caller's memory: every step is tried only while all before it succeeded, and the
     // synchronisation is reached whatever happened
@@ -1044,6 +1056,7 @@ static int trace_list(madsim_hip_ctx_t* c, const madsim_workload_t* w, const mad
     ok = trace_queue(G, S, n, log_cap, obs_cap, !single, st, step, ok);
     if (ok && logs && !single) ok = step(hipMemcpyAsync(logs, S.log, n * log_cap, hipMemcpyDeviceToHost, st), "hipMemcpyAsync(log rows)");
     if (ok && obs) ok = step(hipMemcpyAsync(obs, S.obs, n * obs_cap * sizeof(uint64_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync(observation rows)");
+    if (ok && times) ok = step(hipMemcpyAsync(times, S.obs + n * obs_cap, n * obs_cap * sizeof(uint64_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync(time rows)");
     if (ok && single) ok = step(hipMemcpyAsync(&one_len, S.len, sizeof one_len, hipMemcpyDeviceToHost, st), "hipMemcpyAsync(length)");
     if (ok && log_len && !single) ok = step(hipMemcpyAsync(log_len, S.len, n * sizeof(uint64_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync(log lengths)");
     if (ok && obs_len) ok = step(hipMemcpyAsync(obs_len, d_olen, n * sizeof(uint64_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync(observation counts)");
@@ -1367,12 +1380,83 @@ struct StallForm {
     }
 };
 
+// Probe spans (include/madsim_hip.h): the fifth form of obs_report_run.  The trace launch keeps the time log beside the observation log; the
+// chunk's "entries" are its n_spans device records (sim_kernel.h), always all of them, decoded and merged by fold_spans: there is no table, no
+// cap outcome and no "too many".
+void span_init(madsim_span_t* sp) {
+    memset(sp, 0, sizeof *sp);
+    sp->min = sp->min_seed = sp->max_seed = sp->first_open_seed = UINT64_MAX;
+}
+
+int fold_spans(madsim_probe_spans_t* ps, const unsigned long long* words, const madsim_k_span_rec_t* recs, uint64_t n) {
+    if (n != ps->n_spans) return -1;
+    for (uint64_t s = 0; s < n; s++) {
+        const unsigned long long* const w = recs[s].w;
+        madsim_span_t& sp = ps->spans[s];
+        uint64_t open = 0;
+        for (int v = 0; v < 4; v++) {
+            for (int q = 0; q < 4; q++) sp.n_state[v * 4 + q] += w[v * 4 + q];
+            open += w[v * 4 + MADSIM_SPAN_OPEN];
+        }
+        if (w[16]) {                                                                 // closed seeds: the chunk's extremes against the report's, the smaller seed on a tie
+            const uint64_t mn = ~w[17], mx = w[18], mn_seed = ~w[21], mx_seed = ~w[22];
+            if (mn < sp.min || (mn == sp.min && mn_seed < sp.min_seed)) { sp.min = mn; sp.min_seed = mn_seed; }
+            if (mx > sp.max || (mx == sp.max && mx_seed < sp.max_seed)) { sp.max = mx; sp.max_seed = mx_seed; }
+            sp.n += w[16];
+            unsigned __int128 sum = ((unsigned __int128)sp.sum_hi << 64) | sp.sum_lo;
+            sum += (unsigned __int128)w[19] + ((unsigned __int128)w[20] << 32);
+            sp.sum_lo = (uint64_t)sum; sp.sum_hi = (uint64_t)(sum >> 64);
+            for (int b = 0; b < 256; b++) sp.hist[b] += w[24 + b];
+        }
+        if (open) sp.first_open_seed = std::min<uint64_t>(sp.first_open_seed, ~w[23]);
+    }
+    if (words) {
+        for (int k = 0; k < 4; k++) ps->n_counted[k] += words[2 + k];
+        ps->n_truncated += words[6]; ps->n_runner += words[7];
+    }
+    return 0;
+}
+
+struct SpansForm {
+    typedef madsim_probe_spans_t Report;
+    typedef madsim_k_span_rec_t Entry;
+    static_assert(sizeof(Entry) == 2240 && sizeof(madsim_span_t) == 2240 && sizeof(Report) == 104 && sizeof(madsim_span_def_t) == 24, "record layout");
+    Report* r;
+    static constexpr uint64_t slot_bytes = 4, min_slots = 1, fixed_slots = 1, n_words = MADSIM_K_PROBE_SPANS_WORDS;      // (no table: one word of it)
+    // beside the two rows: two length words, the seed, the result, and per span a state word and a duration
+    static constexpr uint64_t per_seed_bytes = 3 * sizeof(uint64_t) + sizeof(madsim_result_t) + 12 * MADSIM_PROBE_SPANS_MAX;
+    static constexpr uint64_t eager = MADSIM_PROBE_SPANS_MAX;         // every record rides behind the words
+    static constexpr uint32_t runner_word = 7, err_cap = 0;
+    static constexpr const char *name = "probe_spans", *noun = "probe-span";
+    static constexpr const char *at_zero = "hipMemsetAsync(probe-span words)", *at_launch = "probe-span kernel launch", *at_words = "hipMemcpyAsync(probe-span words)",
+                                *at_entries = "hipMemcpyAsync(probe-span records)";
+    static constexpr const char* too_big = "probe_spans: chunk x (16 obs_cap + 72 + 12 n_spans) + 2240 n_spans + 64 exceeds MADSIM_TRACE_MAX_BYTES, or chunk x obs_cap reaches 2^32 - 1: a smaller chunk or a smaller obs_cap";
+    static constexpr const char* too_many = "probe_spans: a chunk came back without its records (internal)";
+    static auto& bufs(madsim_hip_ctx_t* c) { return c->probe_spans; }
+    uint64_t dev_cap() const { return r->n_spans; }
+    int check() const {
+        if (!r) return fail(MADSIM_E_ARG, "probe_spans: null report");
+        if (r->include == 0 || (r->include & ~0xfu)) return fail(MADSIM_E_ARG, "probe_spans: include is 0 or names a verdict at or above 4 (only PASS, PANIC, DEADLOCK, TIME_LIMIT are counted)");
+        if (r->obs_cap == 0 || r->obs_cap > MADSIM_CENSUS_MAX_OBS_CAP) return fail(MADSIM_E_ARG, "probe_spans: obs_cap outside 1 .. MADSIM_CENSUS_MAX_OBS_CAP");
+        if (r->n_spans == 0 || r->n_spans > MADSIM_PROBE_SPANS_MAX || !r->defs || !r->spans) return fail(MADSIM_E_ARG, "probe_spans: n_spans outside 1 .. MADSIM_PROBE_SPANS_MAX, or no definition or record array");
+        for (uint64_t s = 0; s < r->n_spans; s++)
+            if (r->defs[s].flags & ~MADSIM_SPAN_FROM_START) return fail(MADSIM_E_ARG, "probe_spans: a definition carries a flag other than MADSIM_SPAN_FROM_START");
+        if (r->runner_cap && !r->runner_seeds) return fail(MADSIM_E_ARG, "probe_spans: runner_cap without runner_seeds");
+        return 0;
+    }
+    void nothing() const {
+        r->n_truncated = r->n_runner = r->n_runner_listed = 0;
+        for (int k = 0; k < 4; k++) r->n_counted[k] = 0;
+        for (uint64_t s = 0; s < r->n_spans; s++) span_init(&r->spans[s]);
+    }
+};
+
 // What obs_report_run asks of a form beyond its own members: how many passes it makes (each with a buffer group, a cap, a table, words and entries of
 // its own), what a seed's rows weigh, which log the trace launch keeps, its kernels' launch and its host fold.  One pass over the observation rows for
 // the three observation forms; the stall census specialises it.
 template <class Form> struct Passes {
     static constexpr int max = 1;
-    static constexpr bool task_log = false;
+    static constexpr bool task_log = false, time_log = false;
     static int count(const Form&) { return 1; }
     static uint64_t row_cap(const Form& f) { return f.r->obs_cap; }
     static uint64_t row_bytes(uint64_t row_cap) { return 8 * row_cap; }
@@ -1384,7 +1468,7 @@ template <class Form> struct Passes {
 };
 template <> struct Passes<StallForm> {
     static constexpr int max = 2;
-    static constexpr bool task_log = true;
+    static constexpr bool task_log = true, time_log = false;
     static int count(const StallForm& f) { return f.r->shape_cap ? 2 : 1; }
     static uint64_t row_cap(const StallForm& f) { return f.r->task_cap; }
     static uint64_t row_bytes(uint64_t row_cap) { return 16 * row_cap; }      // the task row and the site row
@@ -1410,6 +1494,28 @@ template <> struct Passes<StallForm> {
     static int fold(const StallForm& f, const unsigned long long* const* W, madsim_census_value_t* const* E, const uint64_t* ne) {
         return fold_stall(f.r, W[0], E[0], ne[0], E[1], ne[1]);
     }
+};
+
+template <> struct Passes<SpansForm> {
+    static constexpr int max = 1;
+    static constexpr bool task_log = false, time_log = true;
+    static int count(const SpansForm&) { return 1; }
+    static uint64_t row_cap(const SpansForm& f) { return f.r->obs_cap; }
+    static uint64_t row_bytes(uint64_t row_cap) { return 16 * row_cap; }      // the observation row and the time row
+    static uint64_t cap(const SpansForm& f, int) { return f.dev_cap(); }
+    static auto& bufs(madsim_hip_ctx_t* c, int) { return c->probe_spans; }
+    static int ensure_rows(madsim_hip_ctx_t* c, uint64_t chunk, uint64_t, hipStream_t st) {
+        HIP_TRY(c->probe_spans.st.room((size_t)(chunk * MADSIM_PROBE_SPANS_MAX), st));
+        HIP_TRY(c->probe_spans.dur.room((size_t)(chunk * MADSIM_PROBE_SPANS_MAX), st));
+        return 0;
+    }
+    static int launch(const SpansForm& f, madsim_hip_ctx_t* c, uint64_t n, const uint64_t*, hipStream_t st) {
+        const madsim_hip_ctx::TraceSet& S = c->trace[0];
+        auto& B = c->probe_spans;
+        return madsim_k_launch_probe_spans(S.obs, S.obs + n * f.r->obs_cap, f.r->obs_cap, S.len + n, S.out, c->d_seeds, n, f.r->include, f.r->defs, f.r->n_spans, B.st, B.dur, B.ent,
+                                           B.words, st);
+    }
+    static int fold(const SpansForm& f, const unsigned long long* const* W, madsim_k_span_rec_t* const* E, const uint64_t* ne) { return fold_spans(f.r, W[0], E[0], ne[0]); }
 };
 
 // The report over [seed0, seed0 + total) (seeds == nullptr) or over seeds[0 .. total): chunk after chunk on one stream, each the trace launch
@@ -1458,7 +1564,7 @@ int obs_report_run(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim
     for (uint64_t done = 0; done < total; done += chunk) {
         const uint64_t n = std::min(chunk, total - done);
         Geo G;
-        if ((rc = trace_prepare(c, w, cfg, lim, n, 0, obs_cap, S, G, st, P::task_log ? &row_cap : nullptr))) { f.nothing(); return rc; }
+        if ((rc = trace_prepare(c, w, cfg, lim, n, 0, obs_cap, S, G, st, P::task_log ? &row_cap : nullptr, P::time_log))) { f.nothing(); return rc; }
         for (int p = 0; p < np; p++)
             if ((rc = P::bufs(c, p).ensure(slots[p], cap[p], chunk, !list && p == 0, st))) { f.nothing(); return rc; }
         if ((rc = P::ensure_rows(c, chunk, row_cap, st))) { f.nothing(); return rc; }
@@ -1529,9 +1635,24 @@ extern "C" int madsim_k_fold_probe_order(madsim_probe_order_t* po, const unsigne
     return fold_chunk(ProbeOrderForm{po}, words, entries, n);
 }
 
+extern "C" int madsim_k_fold_probe_spans(madsim_probe_spans_t* ps, const unsigned long long* words, const madsim_k_span_rec_t* recs, uint64_t n) {
+    return fold_spans(ps, words, recs, n);
+}
+extern "C" void madsim_k_span_init(madsim_span_t* span) { span_init(span); }
+
 extern "C" int madsim_k_fold_stall_census(madsim_stall_census_t* sc, const unsigned long long* words, const madsim_census_value_t* sites, uint64_t n_sites,
                                           const madsim_census_value_t* shapes, uint64_t n_shapes) {
     return fold_stall(sc, words, sites, n_sites, shapes, n_shapes);
+}
+
+int madsim_hip_ctx_probe_spans_range(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total,
+                                     uint64_t chunk, const madsim_limits_t* lim, madsim_probe_spans_t* ps) {
+    return obs_report_run<SpansForm>(c, w, cfg, seed0, nullptr, total, chunk, lim, ps, false);
+}
+
+int madsim_hip_ctx_probe_spans_seeds(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n,
+                                     uint64_t chunk, const madsim_limits_t* lim, madsim_probe_spans_t* ps) {
+    return obs_report_run<SpansForm>(c, w, cfg, 0, seeds, n, chunk, lim, ps, true);
 }
 
 int madsim_hip_ctx_stall_census_range(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total,
@@ -1586,6 +1707,30 @@ int madsim_hip_ctx_task_states(madsim_hip_ctx_t* c, const madsim_workload_t* w, 
                                const madsim_limits_t* lim, uint64_t* tasks, uint64_t task_cap, uint64_t* task_len, madsim_result_t* out) {
     const TaskRows tr{tasks, task_cap, task_len};
     return trace_list(c, w, cfg, seeds, n, lim, nullptr, 0, nullptr, 0, nullptr, nullptr, out, false, &tr);
+}
+
+// When the listed seeds traced what they traced (include/madsim_hip.h "Timelines"): trace_list's launch with the time log beside the observation log.
+int madsim_hip_ctx_timeline_seeds(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n,
+                                  const madsim_limits_t* lim, uint64_t* obs, uint64_t* times, uint64_t obs_cap, uint64_t* obs_len, madsim_result_t* out) {
+    if (n && (!obs || !times || !obs_cap)) return fail(MADSIM_E_ARG, "timeline_seeds: needs the observation rows, the time rows and obs_cap > 0");
+    return trace_list(c, w, cfg, seeds, n, lim, nullptr, 0, obs, obs_cap, nullptr, obs_len, out, false, nullptr, times);
+}
+
+// Two span records over disjoint seed sets as one (include/madsim_hip.h).  No device involved.
+void madsim_hip_span_merge(madsim_span_t* into, const madsim_span_t* from) {
+    if (!into || !from) return;
+    madsim_span_t& a = *into;
+    const madsim_span_t& b = *from;
+    for (int q = 0; q < 16; q++) a.n_state[q] += b.n_state[q];
+    if (b.n) {
+        if (b.min < a.min || (b.min == a.min && b.min_seed < a.min_seed)) { a.min = b.min; a.min_seed = b.min_seed; }
+        if (b.max > a.max || (b.max == a.max && b.max_seed < a.max_seed)) { a.max = b.max; a.max_seed = b.max_seed; }
+        a.n += b.n;
+        const unsigned __int128 sum = (((unsigned __int128)a.sum_hi << 64) | a.sum_lo) + (((unsigned __int128)b.sum_hi << 64) | b.sum_lo);
+        a.sum_lo = (uint64_t)sum; a.sum_hi = (uint64_t)(sum >> 64);
+        for (int k = 0; k < 256; k++) a.hist[k] += b.hist[k];
+    }
+    a.first_open_seed = std::min(a.first_open_seed, b.first_open_seed);
 }
 
 // The shape of a task table: the sum of mix(site) over its records, mix = splitmix64's finaliser (include/madsim_hip.h).  No device involved.
@@ -2773,6 +2918,12 @@ int madsim_hip_task_states(const madsim_workload_t* w, const madsim_config_t* cf
     return madsim_hip_ctx_task_states(p.c, w, cfg, seeds, n, lim, tasks, task_cap, task_len, out);
 }
 
+int madsim_hip_timeline_seeds(const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n, const madsim_limits_t* lim,
+                              uint64_t* obs, uint64_t* times, uint64_t obs_cap, uint64_t* obs_len, madsim_result_t* out) {
+    DefaultPin p;
+    return madsim_hip_ctx_timeline_seeds(p.c, w, cfg, seeds, n, lim, obs, times, obs_cap, obs_len, out);
+}
+
 int madsim_hip_trace_seeds(const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n, const madsim_limits_t* lim,
                            uint8_t* logs, uint64_t log_cap, uint64_t* obs, uint64_t obs_cap, uint64_t* log_len, uint64_t* obs_len,
                            madsim_result_t* out) {
@@ -2827,6 +2978,18 @@ int madsim_hip_probe_sets_seeds(const madsim_workload_t* w, const madsim_config_
                                 const madsim_limits_t* lim, madsim_probe_sets_t* ps) {
     DefaultPin p;
     return madsim_hip_ctx_probe_sets_seeds(p.c, w, cfg, seeds, n, chunk, lim, ps);
+}
+
+int madsim_hip_probe_spans_range(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total, uint64_t chunk,
+                                 const madsim_limits_t* lim, madsim_probe_spans_t* ps) {
+    DefaultPin p;
+    return madsim_hip_ctx_probe_spans_range(p.c, w, cfg, seed0, total, chunk, lim, ps);
+}
+
+int madsim_hip_probe_spans_seeds(const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n, uint64_t chunk,
+                                 const madsim_limits_t* lim, madsim_probe_spans_t* ps) {
+    DefaultPin p;
+    return madsim_hip_ctx_probe_spans_seeds(p.c, w, cfg, seeds, n, chunk, lim, ps);
 }
 
 int madsim_hip_probe_order_range(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total, uint64_t chunk,

@@ -113,7 +113,12 @@ struct KParams {
     uint32_t n_insns, n_progs, n_socks, n_nodes;
     // net config (Bernoulli p_int, UniformDuration parameters precomputed on the host)
     uint64_t loss_pint; uint32_t loss_always; uint32_t buggify; uint64_t bug_pint;
-    uint32_t lat_mode; uint32_t has_clog_link; uint32_t has_clog; uint32_t pad0; uint64_t lat_low, lat_range, lat_zone;
+    // (obs_time_words: the trace builds' time log, in the word that was padding here, so every field keeps its kernel-argument offset and the
+    // block its size — beside every value kept in the observation log, at the same index of the unit's time row, the runtime's elapsed
+    // nanoseconds at that observation (k_rng.h obs_fold).  The time rows lie in the observation log's own allocation: row i at obs_log +
+    // obs_time_words + i * obs_cap, obs_time_words 64-bit words behind the observation row.  The observation log's rule: cap-guarded, the rows
+    // zero-filled by the host, obs_len the one true length.  0 keeps nothing; never non-zero without obs_log)
+    uint32_t lat_mode; uint32_t has_clog_link; uint32_t has_clog; uint32_t obs_time_words; uint64_t lat_low, lat_range, lat_zone;
     uint64_t loss_table_pint[4]; uint32_t loss_table_always[4];
     // MS_OP_SET_LATENCY (extended builds): madsim_config_t.lat_table as UniformDuration parameters; a lane keeps the index of its
     // current entry (Lane::loss_always bits 4-6: 0 = lat_* above) and sample_latency selects
@@ -582,6 +587,37 @@ int  madsim_k_launch_probe_order_form(const uint64_t* obs, uint64_t obs_cap, con
 // the totals, and the chunk's `n` entries (any order) merged into po->pairs[0 .. n_pairs), which stay ascending by (a, b) — counts added,
 // per verdict the smaller first_seed of the sides that have one.  Returns 0, or -1 with `po` untouched when the table would pass po->cap.
 int  madsim_k_fold_probe_order(madsim_probe_order_t* po, const unsigned long long* words, const madsim_probe_order_pair_t* entries, uint64_t n);
+// probe spans (madsim_hip_probe_spans_range / _seeds), behind the chunk's trace launch on the same stream: two kernels over the observation rows
+// and the time rows of `n` seeds (`obs_cap` words each), their TRUE lengths, the results and the seeds; defs[0 .. n_spans) in HOST memory (they
+// travel in the kernel arguments).  span_fold_kernel places i and j (include/madsim_hip.h) of every COUNTED row — other rows are not read —,
+// writes state (32-bit; MADSIM_K_SPAN_UNCOUNTED for a row that is not counted) and duration per (row, span) to `st` / `dur` (n * n_spans each,
+// need not be zero) and adds to `recs`: n_spans records of MADSIM_K_SPAN_REC_WORDS 64-bit words, which the launcher zeroes first —
+//   [v * 4 + state] counts, [16] n, [17] max of ~duration, [18] max of duration, [19] / [20] the sums of the durations' low / high 32-bit
+//   halves, [21] / [22] / [23] max of ~seed over the rows whose duration is the minimum / the maximum / that are OPEN, [24 ..] hist
+// — every word is a sum or a maximum from zero, so no arrival order shows, and madsim_k_fold_probe_spans decodes them.  span_witness_kernel,
+// behind it, reads the chunk's final [17] / [18] and writes [21 .. 23].  `words`: MADSIM_K_PROBE_SPANS_WORDS words, zero before the launch:
+// {n_spans, error word (always 0), n_counted[4], n_truncated, n_runner}.  Returns 0, or -1 without launching anything for n == 0, n > 2^31,
+// n * obs_cap >= 2^32 - 1, obs_cap outside 1 .. MADSIM_CENSUS_MAX_OBS_CAP, n_spans outside 1 .. MADSIM_PROBE_SPANS_MAX, an unknown flag, an
+// include mask that is 0 or has a bit at or above 4, or a missing or misaligned array.
+#define MADSIM_K_PROBE_SPANS_WORDS 8u           /* 64-bit words of a chunk's report                                */
+#define MADSIM_K_SPAN_REC_WORDS 280u            /* = sizeof(madsim_span_t) / 8                                     */
+#define MADSIM_K_SPAN_UNCOUNTED 4u              /* the state word of a row that is not counted                     */
+typedef struct madsim_k_span_rec { unsigned long long w[MADSIM_K_SPAN_REC_WORDS]; } madsim_k_span_rec_t;
+int  madsim_k_launch_probe_spans(const uint64_t* obs, const uint64_t* times, uint64_t obs_cap, const uint64_t* obs_len, const madsim_result_t* res,
+                                 const uint64_t* d_seeds, uint64_t n, uint32_t include, const madsim_span_def_t* defs, uint64_t n_spans, uint32_t* st,
+                                 unsigned long long* dur, madsim_k_span_rec_t* recs, unsigned long long* words, void* stream);
+// ... with the fold kernel's form named: direct != 0 = every update goes straight to the global records, no workgroup accumulator in LDS: the
+// correctness baseline and the other side of the A/B (tools/spans_ab.py); the same bytes either way
+int  madsim_k_launch_probe_spans_form(const uint64_t* obs, const uint64_t* times, uint64_t obs_cap, const uint64_t* obs_len, const madsim_result_t* res,
+                                      const uint64_t* d_seeds, uint64_t n, uint32_t include, const madsim_span_def_t* defs, uint64_t n_spans,
+                                      uint32_t* st, unsigned long long* dur, madsim_k_span_rec_t* recs, unsigned long long* words, void* stream,
+                                      int direct);
+// the host fold of one chunk into the caller's report (madsim_hip.cpp; no device involved): `words` (may be null: no totals) are added to the
+// totals, and the chunk's `n` == ps->n_spans device records decoded and merged into ps->spans — counts, sums and histograms add, of two equal
+// extremes the smaller seed wins, first_open_seed is the minimum.  ps->spans must hold records (madsim_k_span_init gives the empty one).
+// Returns 0, or -1 with `ps` untouched when n != ps->n_spans.
+int  madsim_k_fold_probe_spans(madsim_probe_spans_t* ps, const unsigned long long* words, const madsim_k_span_rec_t* recs, uint64_t n);
+void madsim_k_span_init(madsim_span_t* span);
 int  madsim_k_set_max_lds(uint32_t lds_bytes);
 int  madsim_k_variant_vgprs(const madsim_k::VariantSel* v);
 void madsim_k_launch_keyflip(unsigned long long* acc, void* stream);

@@ -1631,6 +1631,159 @@ __global__ __launch_bounds__(1024) void order_extract_kernel(const unsigned long
     }
 }
 
+// ---- probe spans: the virtual time from a chunk's counted seeds' first `from` to the first `to` behind it, as a distribution ------------------
+// Two kernels behind the chunk's trace launch (sim_kernel.h: the records' words).  span_fold_kernel follows order_fold_kernel: one wave per
+// row, striding, the row index, the verdict, the length and the loop bounds in scalar registers; rows of uncounted and runner seeds are not
+// read.  The visible observations are walked in rounds of 64, one coalesced 8-byte load per lane; the definitions travel by value in the kernel
+// arguments (384 bytes).  Per span not yet closed: while i is not placed one wave-wide compare against `from` and a ballot, and in the round
+// that places it the compare against `to` is masked to the lanes behind i; from then on every lane.  `placed` and `closed` are scalar masks;
+// lane s keeps i and j of span s.  The walk ends once every span is closed or the row ends.  Lane s then loads the two times of span s and has
+// its state and duration, written to st / dur for span_witness_kernel.  LDS_ACC: histogram, state counts, n, ~min, max and the two half-sums
+// (the statistics kernels' way to an exact sum) are a workgroup accumulator in LDS (about 18 KB) under LDS atomics — lane s touches span s's
+// words only, so a wave never collides with itself — flushed once, the non-zero words only, into the chunk's records with atomicAdd /
+// atomicMax: sums and maxima from zero commute, so no arrival order shows.  LDS_ACC = false sends the same updates straight to the records:
+// the correctness baseline and the other side of the A/B.
+// span_witness_kernel: one thread per row, striding; reads the chunk's final min and max and takes, per workgroup in LDS and then globally,
+// the maximum of ~seed over the rows whose duration equals them and over the OPEN rows: the smallest seed, whatever the order of arrival.
+struct SpanDefs { madsim_span_def_t d[MADSIM_PROBE_SPANS_MAX]; };
+constexpr uint32_t SPAN_N = 16, SPAN_MIN = 17, SPAN_MAX = 18, SPAN_LO = 19, SPAN_HI = 20, SPAN_WIT = 21, SPAN_HIST = 24, SPAN_REC = MADSIM_K_SPAN_REC_WORDS;
+constexpr uint32_t SPANS_ENTRIES = 0, SPANS_COUNTS = 2, SPAN_UNDEF = 0xffffffffu;
+static_assert(SPAN_HIST + MADSIM_STAT_BUCKETS == SPAN_REC && MADSIM_PROBE_SPANS_MAX == 16, "the record");
+struct SpanAcc {
+    uint32_t hist[MADSIM_PROBE_SPANS_MAX][MADSIM_STAT_BUCKETS];
+    uint32_t n_state[MADSIM_PROBE_SPANS_MAX][16];
+    uint32_t n[MADSIM_PROBE_SPANS_MAX];
+    unsigned long long mn[MADSIM_PROBE_SPANS_MAX], mx[MADSIM_PROBE_SPANS_MAX], lo[MADSIM_PROBE_SPANS_MAX], hi[MADSIM_PROBE_SPANS_MAX];      // mn: the largest ~duration
+};
+
+template <bool LDS_ACC>
+__global__ __launch_bounds__(256) void span_fold_kernel(const unsigned long long* __restrict__ obs, const unsigned long long* __restrict__ times,
+                                                        uint32_t obs_cap, const unsigned long long* __restrict__ obs_len,
+                                                        const madsim_result_t* __restrict__ res, uint32_t n, uint32_t include, const SpanDefs defs,
+                                                        uint32_t m, uint32_t* __restrict__ st, unsigned long long* __restrict__ dur,
+                                                        unsigned long long* __restrict__ recs, unsigned long long* __restrict__ words) {
+    __shared__ unsigned long long acc_lds[LDS_ACC ? sizeof(SpanAcc) / 8 : 1];
+    SpanAcc& A = *reinterpret_cast<SpanAcc*>(acc_lds);
+    const uint32_t lane = threadIdx.x & 63, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (LDS_ACC) {
+        for (uint32_t c = threadIdx.x; c < sizeof(SpanAcc) / 8; c += 256u) acc_lds[c] = 0ull;
+        __syncthreads();
+    }
+    const uint32_t full = 0xffffu >> (16u - m);                                    // (1 <= m <= 16)
+    uint32_t start = 0;                                                            // (scalar) the spans that begin at the start of the run
+    for (uint32_t s = 0; s < m; s++) start |= (defs.d[s].flags & MADSIM_SPAN_FROM_START) << s;
+    uint32_t acc = 0;                                                              // lane k < 4: counted seeds of verdict k; 4: truncated; 5: runner
+    for (uint32_t i = blockIdx.x * 4u + wave; i < n; i += gridDim.x * 4u) {        // (scalar)
+        const uint32_t v = reinterpret_cast<const uint32_t*>(res + i)[0];
+        if (v >= 4u || !((include >> v) & 1u)) {                                   // a runner verdict or a left-out one: the row is not read
+            acc += lane == 5u && v >= 4u;
+            if (lane < m) st[(size_t)i * m + lane] = MADSIM_K_SPAN_UNCOUNTED;
+            continue;
+        }
+        const unsigned long long len = obs_len[i];
+        const uint32_t vis = len < obs_cap ? (uint32_t)len : obs_cap;
+        const unsigned long long* const row = obs + (size_t)i * obs_cap;
+        uint32_t fi = SPAN_UNDEF, fj = SPAN_UNDEF;                                 // lane s: i and j of span s
+        uint32_t placed = start, closed = 0;                                       // (scalar) the spans whose i / whose j is known
+        for (uint32_t k = 0; k * 64u < vis && closed != full; k++) {
+            const uint32_t idx = k * 64u + lane;
+            const bool have = idx < vis;
+            const unsigned long long val = have ? row[idx] : 0ull;
+            const unsigned long long valid = __ballot(have);
+            for (uint32_t s = 0; s < m; s++) {
+                if ((closed >> s) & 1u) continue;                                  // (scalar)
+                unsigned long long behind = ~0ull;
+                if (!((placed >> s) & 1u)) {
+                    const unsigned long long b = __ballot(val == defs.d[s].from) & valid;
+                    if (!b) continue;
+                    const uint32_t p = (uint32_t)__ffsll((long long)b) - 1u;
+                    if (lane == s) fi = k * 64u + p;
+                    placed |= 1u << s;
+                    behind = p == 63u ? 0ull : ~0ull << (p + 1u);                  // in this round the higher lanes only
+                }
+                const unsigned long long b2 = __ballot(val == defs.d[s].to) & valid & behind;
+                if (b2) {
+                    if (lane == s) fj = k * 64u + (uint32_t)__ffsll((long long)b2) - 1u;
+                    closed |= 1u << s;
+                }
+            }
+        }
+        acc += (lane == v) + (lane == 4u && len > obs_cap);
+        if (lane < m) {
+            const bool cl = (closed >> lane) & 1u;
+            const uint32_t state = !((placed >> lane) & 1u) ? MADSIM_SPAN_ABSENT : cl ? MADSIM_SPAN_CLOSED : len > obs_cap ? MADSIM_SPAN_CUT : MADSIM_SPAN_OPEN;
+            unsigned long long d = 0ull;
+            if (cl) {
+                const unsigned long long* const trow = times + (size_t)i * obs_cap;
+                d = trow[fj] - (fi == SPAN_UNDEF ? 0ull : trow[fi]);               // (the start of the run: time 0)
+            }
+            st[(size_t)i * m + lane] = state;
+            dur[(size_t)i * m + lane] = d;
+            if (LDS_ACC) {
+                atomicAdd(&A.n_state[lane][v * 4u + state], 1u);
+                if (cl) {
+                    atomicAdd(&A.hist[lane][stat_bucket(d)], 1u);
+                    atomicAdd(&A.n[lane], 1u);
+                    atomicMax(&A.mn[lane], ~d); atomicMax(&A.mx[lane], d);
+                    atomicAdd(&A.lo[lane], d & 0xffffffffull); atomicAdd(&A.hi[lane], d >> 32);
+                }
+            } else {
+                unsigned long long* const r = recs + (size_t)lane * SPAN_REC;
+                atomicAdd(r + v * 4u + state, 1ull);
+                if (cl) {
+                    atomicAdd(r + SPAN_HIST + stat_bucket(d), 1ull);
+                    atomicAdd(r + SPAN_N, 1ull);
+                    atomicMax(r + SPAN_MIN, ~d); atomicMax(r + SPAN_MAX, d);
+                    atomicAdd(r + SPAN_LO, d & 0xffffffffull); atomicAdd(r + SPAN_HI, d >> 32);
+                }
+            }
+        }
+    }
+    if (lane < 6u && acc) atomicAdd(&words[SPANS_COUNTS + lane], (unsigned long long)acc);
+    if (LDS_ACC) {
+        __syncthreads();
+        for (uint32_t c = threadIdx.x; c < m * MADSIM_STAT_BUCKETS; c += 256u) {
+            const uint32_t cn = A.hist[c >> 8][c & 255u];
+            if (cn) atomicAdd(recs + (size_t)(c >> 8) * SPAN_REC + SPAN_HIST + (c & 255u), (unsigned long long)cn);
+        }
+        if (threadIdx.x < m * 16u) {
+            const uint32_t cn = A.n_state[threadIdx.x >> 4][threadIdx.x & 15u];
+            if (cn) atomicAdd(recs + (size_t)(threadIdx.x >> 4) * SPAN_REC + (threadIdx.x & 15u), (unsigned long long)cn);
+        }
+        if (threadIdx.x < m && A.n[threadIdx.x]) {
+            unsigned long long* const r = recs + (size_t)threadIdx.x * SPAN_REC;
+            atomicAdd(r + SPAN_N, (unsigned long long)A.n[threadIdx.x]);
+            atomicMax(r + SPAN_MIN, A.mn[threadIdx.x]); atomicMax(r + SPAN_MAX, A.mx[threadIdx.x]);
+            atomicAdd(r + SPAN_LO, A.lo[threadIdx.x]); atomicAdd(r + SPAN_HI, A.hi[threadIdx.x]);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void span_witness_kernel(const uint32_t* __restrict__ st, const unsigned long long* __restrict__ dur,
+                                                           const unsigned long long* __restrict__ seeds, uint32_t n, uint32_t m,
+                                                           unsigned long long* __restrict__ recs, unsigned long long* __restrict__ words) {
+    __shared__ unsigned long long wit[MADSIM_PROBE_SPANS_MAX][3], ext[MADSIM_PROBE_SPANS_MAX][2];
+    if (threadIdx.x < 3u * MADSIM_PROBE_SPANS_MAX) (&wit[0][0])[threadIdx.x] = 0ull;
+    if (threadIdx.x < m) { ext[threadIdx.x][0] = ~recs[(size_t)threadIdx.x * SPAN_REC + SPAN_MIN]; ext[threadIdx.x][1] = recs[(size_t)threadIdx.x * SPAN_REC + SPAN_MAX]; }
+    __syncthreads();
+    for (uint32_t row = blockIdx.x * 256u + threadIdx.x; row < n; row += gridDim.x * 256u) {
+        for (uint32_t s = 0; s < m; s++) {
+            const uint32_t state = st[(size_t)row * m + s];
+            if (state == MADSIM_SPAN_CLOSED) {
+                const unsigned long long d = dur[(size_t)row * m + s];
+                if (d == ext[s][0]) atomicMax(&wit[s][0], ~seeds[row]);
+                if (d == ext[s][1]) atomicMax(&wit[s][1], ~seeds[row]);
+            } else if (state == MADSIM_SPAN_OPEN) atomicMax(&wit[s][2], ~seeds[row]);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 3u * m) {
+        const unsigned long long w = (&wit[0][0])[threadIdx.x];
+        if (w) atomicMax(recs + (size_t)(threadIdx.x / 3u) * SPAN_REC + SPAN_WIT + threadIdx.x % 3u, w);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) words[SPANS_ENTRIES] = m;
+}
+
 // one kernel per row of variant_table (sim_kernel.h), same macro, same order
 #define MADSIM_VARIANT_KERNEL(T_, S_, L_, F_, R_, G_) (const void*)sim_kernel<Variant<T_, S_, L_, F_, R_, G_>>,
 static const void* const variant_kernels[] = {MADSIM_FOR_EACH_VARIANT(MADSIM_VARIANT_KERNEL)};
@@ -2036,6 +2189,43 @@ extern "C" int madsim_k_launch_probe_order(const uint64_t* obs, uint64_t obs_cap
                                            const uint64_t* d_seeds, uint64_t n, uint32_t include, const uint64_t* vocab, uint64_t n_vocab,
                                            uint32_t* matrix, unsigned long long* words, madsim_probe_order_pair_t* entries, void* stream) {
     return madsim_k_launch_probe_order_form(obs, obs_cap, obs_len, res, d_seeds, n, include, vocab, n_vocab, matrix, words, entries, stream, 0);
+}
+
+// Rows, time rows, lengths, results and seeds of the chunk's n seeds; defs: n_spans definitions in HOST memory (they travel in the kernel
+// arguments); st / dur: n * n_spans words each; recs: n_spans records, zeroed here; words: MADSIM_K_PROBE_SPANS_WORDS zeroed words
+// (sim_kernel.h).  Returns 0, or -1 (nothing launched) for sizes the kernels are not written for.
+extern "C" int madsim_k_launch_probe_spans_form(const uint64_t* obs, const uint64_t* times, uint64_t obs_cap, const uint64_t* obs_len,
+                                                const madsim_result_t* res, const uint64_t* d_seeds, uint64_t n, uint32_t include,
+                                                const madsim_span_def_t* defs, uint64_t n_spans, uint32_t* st, unsigned long long* dur,
+                                                madsim_k_span_rec_t* recs, unsigned long long* words, void* stream, int direct) {
+    static_assert(sizeof(madsim_span_t) == 8 * MADSIM_K_SPAN_REC_WORDS && sizeof(madsim_k_span_rec_t) == sizeof(madsim_span_t) && sizeof(madsim_result_t) == 48, "record layout");
+    static_assert(sizeof(madsim_k::SpanDefs) == 384 && sizeof(madsim_k::SpanAcc) % 8 == 0 && sizeof(madsim_k::SpanAcc) < 20480, "the definitions in the kernel arguments; the accumulator");
+    if (n == 0 || obs_cap == 0 || obs_cap > MADSIM_CENSUS_MAX_OBS_CAP || n >= 0xffffffffull / obs_cap || n > (1ull << 31)) return -1;      // n * obs_cap < 2^32 - 1; the row index plus a grid stride stays 32-bit
+    if (include == 0 || (include & ~0xfu) || n_spans == 0 || n_spans > MADSIM_PROBE_SPANS_MAX) return -1;
+    if (!obs || !times || !obs_len || !res || !d_seeds || !defs || !st || !dur || !recs || !words || ((uintptr_t)st & 3u) || ((uintptr_t)dur & 7u) || ((uintptr_t)recs & 7u)) return -1;
+    madsim_k::SpanDefs D{};
+    for (uint64_t s = 0; s < n_spans; s++) {
+        if (defs[s].flags & ~MADSIM_SPAN_FROM_START) return -1;
+        D.d[s].from = defs[s].from; D.d[s].to = defs[s].to; D.d[s].flags = defs[s].flags;
+    }
+    if (hipMemsetAsync(recs, 0, n_spans * sizeof(madsim_k_span_rec_t), (hipStream_t)stream) != hipSuccess) return -1;
+    const uint64_t waves = n < MADSIM_K_PROBE_ORDER_WAVES ? n : MADSIM_K_PROBE_ORDER_WAVES;      // one wave per row, 256 workgroups at most
+    const auto fold = direct ? madsim_k::span_fold_kernel<false> : madsim_k::span_fold_kernel<true>;
+    hipLaunchKernelGGL(fold, dim3((uint32_t)((waves + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const unsigned long long*)obs,
+                       (const unsigned long long*)times, (uint32_t)obs_cap, (const unsigned long long*)obs_len, res, (uint32_t)n, include, D,
+                       (uint32_t)n_spans, st, dur, reinterpret_cast<unsigned long long*>(recs), words);
+    const uint64_t wgs = (n + 255) / 256 < 256 ? (n + 255) / 256 : 256;
+    hipLaunchKernelGGL(madsim_k::span_witness_kernel, dim3((uint32_t)wgs), dim3(256), 0, (hipStream_t)stream, (const uint32_t*)st,
+                       (const unsigned long long*)dur, (const unsigned long long*)d_seeds, (uint32_t)n, (uint32_t)n_spans,
+                       reinterpret_cast<unsigned long long*>(recs), words);
+    return 0;
+}
+
+extern "C" int madsim_k_launch_probe_spans(const uint64_t* obs, const uint64_t* times, uint64_t obs_cap, const uint64_t* obs_len,
+                                           const madsim_result_t* res, const uint64_t* d_seeds, uint64_t n, uint32_t include,
+                                           const madsim_span_def_t* defs, uint64_t n_spans, uint32_t* st, unsigned long long* dur,
+                                           madsim_k_span_rec_t* recs, unsigned long long* words, void* stream) {
+    return madsim_k_launch_probe_spans_form(obs, times, obs_cap, obs_len, res, d_seeds, n, include, defs, n_spans, st, dur, recs, words, stream, 0);
 }
 
 extern "C" void madsim_k_launch_keyflip(unsigned long long* acc, void* stream) {

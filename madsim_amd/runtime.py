@@ -144,6 +144,10 @@ def lib():
         L.madsim_hip_task_states.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), u64p, C.c_uint64, C.POINTER(A.Limits), C.c_void_p,
                                              C.c_uint64, C.c_void_p, C.c_void_p]
         L.madsim_hip_ctx_task_states.argtypes = [ctxp] + L.madsim_hip_task_states.argtypes
+        # timelines: trace_seeds' conventions, the time rows beside the observation rows
+        L.madsim_hip_timeline_seeds.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), u64p, C.c_uint64, C.POINTER(A.Limits), C.c_void_p,
+                                                C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.madsim_hip_ctx_timeline_seeds.argtypes = [ctxp] + L.madsim_hip_timeline_seeds.argtypes
         L.madsim_hip_stall_shape.restype = C.c_uint64
         L.madsim_hip_stall_shape.argtypes = [C.c_void_p, C.c_uint64]
         # the stall-site census: the census's signatures with a madsim_stall_census_t
@@ -197,6 +201,18 @@ def lib():
         L.madsim_hip_ctx_probe_order_range.argtypes = [ctxp] + L.madsim_hip_probe_order_range.argtypes
         L.madsim_hip_ctx_probe_order_seeds.argtypes = [ctxp] + L.madsim_hip_probe_order_seeds.argtypes
         L.madsim_k_fold_probe_order.argtypes = [C.POINTER(A.ProbeOrder), C.c_void_p, C.c_void_p, C.c_uint64]
+        # probe spans: the census's signatures with a madsim_probe_spans_t
+        L.madsim_hip_probe_spans_range.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(A.Limits),
+                                                   C.POINTER(A.ProbeSpans)]
+        L.madsim_hip_probe_spans_seeds.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), u64p, C.c_uint64, C.c_uint64, C.POINTER(A.Limits),
+                                                   C.POINTER(A.ProbeSpans)]
+        L.madsim_hip_ctx_probe_spans_range.argtypes = [ctxp] + L.madsim_hip_probe_spans_range.argtypes
+        L.madsim_hip_ctx_probe_spans_seeds.argtypes = [ctxp] + L.madsim_hip_probe_spans_seeds.argtypes
+        L.madsim_k_fold_probe_spans.argtypes = [C.POINTER(A.ProbeSpans), C.c_void_p, C.c_void_p, C.c_uint64]
+        L.madsim_k_span_init.argtypes = [C.c_void_p]
+        L.madsim_k_span_init.restype = None
+        L.madsim_hip_span_merge.argtypes = [C.c_void_p, C.c_void_p]
+        L.madsim_hip_span_merge.restype = None
         # the sweep campaigns: one signature for the range (seeds NULL) and the list (seed0 0)
         L.madsim_hip_run_sweep_campaign.argtypes = [C.POINTER(A.SweepVariant), C.c_uint32, C.c_uint64, C.c_uint64, u64p, C.c_uint64, C.c_uint32,
                                                     C.c_uint32, C.POINTER(A.Sweep)]
@@ -407,6 +423,77 @@ def trace_seeds(workload, seeds, config=None, limits=None, obs_cap=256, log_cap=
     if _inited_device is None:
         init(0)
     return _trace_seeds(lambda *a: lib().madsim_hip_trace_seeds(workload.ref(), *a), workload, seeds, config, limits, obs_cap, log_cap, resolve)
+
+
+class SeedTimeline:
+    """When one seed traced what it traced (runtime.timeline): `seed`; `result`, its A.Result; `observations`, the first obs_cap values it
+    handed to trace / trace_time / a traced tick, in execution order, and `times`, the runtime's elapsed nanoseconds at each of them (what
+    trace_instant would have folded there) — two lists of one length, Python ints, the times never decreasing; `n_observations`, how many
+    values there were.  Under a runner verdict the lists are what was recorded until the verdict: not meaningful."""
+    __slots__ = ("seed", "result", "observations", "times", "n_observations")
+
+    def __init__(self, seed, result, observations, times, n_observations):
+        self.seed, self.result, self.observations, self.times, self.n_observations = seed, result, observations, times, n_observations
+
+    def events(self):
+        """[(time, value)] in execution order."""
+        return list(zip(self.times, self.observations))
+
+    def first(self, value, after=-1):
+        """Index of the first occurrence of `value` behind index `after`, or None."""
+        for k in range(after + 1, len(self.observations)):
+            if self.observations[k] == value:
+                return k
+        return None
+
+    def span(self, start, end):
+        """Virtual nanoseconds from the first `start` (None: the start of the run) to the first `end` behind it; None where either is missing."""
+        i = -1 if start is None else self.first(start)
+        j = None if i is None else self.first(end, i)
+        return None if j is None else self.times[j] - (0 if i < 0 else self.times[i])
+
+    def __repr__(self):
+        return (f"SeedTimeline(seed={self.seed}, verdict={A.VERDICT_NAMES[self.result.verdict] if self.result.verdict < 8 else self.result.verdict}, "
+                f"events={self.events()}, n_observations={self.n_observations})")
+
+
+def _timeline(call, workload, seeds, config, limits, obs_cap, resolve):
+    """Run `call(cfg, seeds*, n, lim, obs, times, obs_cap, obs_len, out)` — a madsim_hip_*timeline_seeds entry point with its context and
+    workload bound — over `seeds`, then over the seeds a round leaves re-runnable, each round one further call (as _trace_seeds)."""
+    seeds = [int(s) for s in seeds]
+    if any(not 0 <= s <= A.U64_MAX for s in seeds) or obs_cap < 1:
+        raise MadsimHipError("timeline: seeds must fit u64, obs_cap be >= 1")
+    cfg, lim0 = config or A.Config.default(), limits or A.Limits()
+    n = len(seeds)
+    res, lens = np.zeros(n, dtype=A.RESULT_DTYPE), np.zeros(n, dtype=np.uint64)
+    obs, times = np.zeros((n, obs_cap), dtype=np.uint64), np.zeros((n, obs_cap), dtype=np.uint64)
+    idx = np.arange(n)
+    for r in range(_resolve_rounds(resolve) + 1):
+        if not len(idx):
+            break
+        lim = lim0 if r == 0 else grown_limits(workload, lim0, r)
+        m = len(idx)
+        s = np.array([seeds[i] for i in idx], dtype=np.uint64)
+        o, t = np.zeros((m, obs_cap), dtype=np.uint64), np.zeros((m, obs_cap), dtype=np.uint64)
+        ol, out = np.zeros(m, dtype=np.uint64), np.zeros(m, dtype=A.RESULT_DTYPE)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)                                 # noqa: E731
+        _check(call(C.byref(cfg), s.ctypes.data_as(C.POINTER(C.c_uint64)), m, C.byref(lim), ptr(o), ptr(t), obs_cap, ptr(ol), ptr(out)))
+        res[idx], obs[idx], times[idx], lens[idx] = out, o, t, ol
+        idx = idx[_rerunnable(out, lim)]
+    out = []
+    for i in range(n):
+        k = min(int(lens[i]), obs_cap)
+        out.append(SeedTimeline(seeds[i], A.Result(*[int(x) for x in res[i]]), [int(v) for v in obs[i, :k]], [int(v) for v in times[i, :k]], int(lens[i])))
+    return out
+
+
+def timeline(workload, seeds, config=None, limits=None, obs_cap=256, resolve=True):
+    """madsim_hip_timeline_seeds: replay `seeds` (any order, duplicates allowed) on the trace build, the whole list in one launch, and return
+    one SeedTimeline per seed, in the order given: the values trace_seeds returns and, beside each, the virtual time at which it was traced.
+    resolve= as trace_seeds has it."""
+    if _inited_device is None:
+        init(0)
+    return _timeline(lambda *a: lib().madsim_hip_timeline_seeds(workload.ref(), *a), workload, seeds, config, limits, obs_cap, resolve)
 
 
 def task_word(state, prog, pc, cnt0=0, cnt1=0):
@@ -1168,6 +1255,156 @@ def probe_order(workload, vocabulary=None, seed0=0, total=0, seeds=None, include
                         census, workload, vocabulary, seed0, total, seeds, include, obs_cap, chunk, config, limits, resolve)
 
 
+def span_defs(spans):
+    """ndarray[A.SPAN_DEF_DTYPE] of `spans`: (from, to) pairs, from=None for the start of the run."""
+    spans = list(spans)
+    if not 1 <= len(spans) <= A.PROBE_SPANS_MAX:
+        raise MadsimHipError(f"probe_spans: 1..{A.PROBE_SPANS_MAX} span definitions, got {len(spans)}")
+    defs = np.zeros(len(spans), dtype=A.SPAN_DEF_DTYPE)
+    for k, (a, b) in enumerate(spans):
+        if not (a is None or 0 <= int(a) <= A.U64_MAX) or not 0 <= int(b) <= A.U64_MAX:
+            raise MadsimHipError("probe_spans: span values must fit u64")
+        defs[k] = (0 if a is None else int(a), int(b), A.SPAN_FROM_START if a is None else 0, 0)
+    return defs
+
+
+def empty_spans(n):
+    """ndarray[A.SPAN_DTYPE] of n records over no seed: min and the three seeds UINT64_MAX, everything else 0 (madsim_k_span_init)."""
+    sp = np.zeros(n, dtype=A.SPAN_DTYPE)
+    for k in range(n):
+        lib().madsim_k_span_init(sp[k:k + 1].ctypes.data_as(C.c_void_p))
+    return sp
+
+
+class ProbeSpans:
+    """How long, in virtual nanoseconds, from one traced value to another over the seeds of a range (runtime.probe_spans).  `definitions`:
+    the (from, to) pairs asked for, from=None being the start of the run; `spans`: ndarray[A.SPAN_DTYPE], one record per definition in that
+    order — `n_state[verdict][A.SPAN_*]` counted seeds, and over the CLOSED ones `n`, `min`, `max`, the 128-bit sum, `hist` under
+    A.stat_bucket, `min_seed` / `max_seed` (the smallest seed attaining each extreme) and `first_open_seed`.  `n_counted[4]`, `n_truncated`,
+    `n_runner`, `runner_seeds`: as a Census has them.  Everything is an exact integer."""
+
+    def __init__(self, defs, spans, n_counted, n_truncated, n_runner, runner_seeds, include, obs_cap):
+        self.defs, self.spans = defs, spans
+        self.n_counted, self.n_truncated, self.n_runner = tuple(int(x) for x in n_counted), int(n_truncated), int(n_runner)
+        self.runner_seeds, self.include, self.obs_cap = runner_seeds, include, obs_cap
+
+    @property
+    def definitions(self):
+        return [(None if int(d["flags"]) & A.SPAN_FROM_START else int(d["from"]), int(d["to"])) for d in self.defs]
+
+    def __len__(self):
+        return len(self.spans)
+
+    def __repr__(self):
+        return (f"ProbeSpans({self.definitions}, closed={[self.closed(i) for i in range(len(self))]} of {sum(self.n_counted)} counted seeds, "
+                f"n_truncated={self.n_truncated}, n_runner={self.n_runner})")
+
+    def tobytes(self):
+        """The whole report as bytes: two reports are the same report exactly when these are equal."""
+        totals = np.array(self.n_counted + (self.n_truncated, self.n_runner), dtype=np.uint64)
+        return self.defs.tobytes() + self.spans.tobytes() + totals.tobytes() + np.asarray(self.runner_seeds, dtype=np.uint64).tobytes()
+
+    def closed(self, i):
+        """How many counted seeds closed span i."""
+        return int(self.spans["n"][i])
+
+    def states(self, i, verdict=None):
+        """{state name: counted seeds} of span i — of one verdict, or over all."""
+        ns = self.spans["n_state"][i]
+        row = ns.sum(axis=0) if verdict is None else ns[verdict]
+        return {A.SPAN_STATE_NAMES[q]: int(row[q]) for q in range(4)}
+
+    def total(self, i):
+        """The exact sum of span i's durations."""
+        return int(self.spans["sum_hi"][i]) << 64 | int(self.spans["sum_lo"][i])
+
+    def mean(self, i):
+        """The exact mean duration of span i as a fractions.Fraction; None over no closed seed."""
+        return Fraction(self.total(i), self.closed(i)) if self.closed(i) else None
+
+    def quantile_bounds(self, i, q):
+        """(lo, hi): the q-quantile (0 <= q <= 1; nearest rank) of span i's durations lies in lo <= d <= hi, the bucket of the histogram it
+        falls in, narrowed by the exact min and max.  None over no closed seed."""
+        n = self.closed(i)
+        if not n:
+            return None
+        if not 0 <= q <= 1:
+            raise MadsimHipError("quantile_bounds: q in 0..1")
+        rank = max(1, math.ceil(Fraction(q) * n))
+        acc = 0
+        for b in range(A.STAT_BUCKETS):
+            acc += int(self.spans["hist"][i][b])
+            if acc >= rank:
+                lo, hi = A.stat_bucket_floor(b), A.stat_bucket_floor(b + 1) - 1 if b + 1 < 252 else A.U64_MAX
+                return max(lo, int(self.spans["min"][i])), min(hi, int(self.spans["max"][i]))
+        raise MadsimHipError("quantile_bounds: the histogram holds fewer seeds than n (internal)")
+
+    def _seed(self, field, i):
+        s = int(self.spans[field][i])
+        return None if s == A.U64_MAX and not (self.closed(i) if field != "first_open_seed" else self.states(i)["OPEN"]) else s
+
+    def slowest(self, i):
+        """The smallest seed whose span i took the longest; None over no closed seed."""
+        return self._seed("max_seed", i)
+
+    def fastest(self, i):
+        """The smallest seed whose span i took the shortest; None over no closed seed."""
+        return self._seed("min_seed", i)
+
+    def never_closed(self, i):
+        """The smallest counted seed that reached span i's start and ended, with nothing cut, before its end: the one to replay.  None when
+        there is none."""
+        return self._seed("first_open_seed", i)
+
+    def merge(self, other):
+        """The report over the union of two DISJOINT seed sets taken under the same definitions, include mask and obs_cap: exact, in either order."""
+        if (self.defs.tobytes(), self.include, self.obs_cap) != (other.defs.tobytes(), other.include, other.obs_cap):
+            raise MadsimHipError("ProbeSpans.merge: the two reports differ in definitions, include or obs_cap")
+        out, add = self.spans.copy(), np.ascontiguousarray(other.spans)
+        for i in range(len(out)):
+            lib().madsim_hip_span_merge(out[i:i + 1].ctypes.data_as(C.c_void_p), add[i:i + 1].ctypes.data_as(C.c_void_p))
+        runner = np.sort(np.concatenate([np.asarray(self.runner_seeds, dtype=np.uint64), np.asarray(other.runner_seeds, dtype=np.uint64)]))
+        return ProbeSpans(self.defs, out, tuple(x + y for x, y in zip(self.n_counted, other.n_counted)), self.n_truncated + other.n_truncated,
+                          self.n_runner + other.n_runner, runner, self.include, self.obs_cap)
+
+
+def _probe_spans(call_range, call_seeds, workload, spans, seed0, total, seeds, include, obs_cap, chunk, config, limits, resolve):
+    """One probe-spans call — `call_range(cfg, seed0, total, chunk, lim, ps)` or `call_seeds(cfg, seeds*, n, chunk, lim, ps)`, a
+    madsim_hip_*probe_spans_* entry point with its context and workload bound — and its runner seeds settled round by round (_settle), as
+    _census does."""
+    cfg, lim0 = config or A.Config.default(), limits or A.Limits()
+    mask = _include_mask(include)
+    rounds = _resolve_rounds(resolve)
+    defs = span_defs(spans)
+
+    def one(lim, sa, s0, n):
+        recs, runner = np.zeros(len(defs), dtype=A.SPAN_DTYPE), np.zeros(max(n, 1), dtype=np.uint64)
+        ps = A.ProbeSpans(include=mask, obs_cap=obs_cap, n_spans=len(defs), runner_cap=n)
+        ps.defs, ps.spans = defs.ctypes.data_as(C.POINTER(A.SpanDef)), recs.ctypes.data_as(C.POINTER(A.Span))
+        ps.runner_seeds = runner.ctypes.data_as(C.POINTER(C.c_uint64))
+        if sa is None:
+            _check(call_range(C.byref(cfg), s0, n, chunk, C.byref(lim), C.byref(ps)))
+        else:
+            _check(call_seeds(C.byref(cfg), _seeds_ptr(sa), n, chunk, C.byref(lim), C.byref(ps)))
+        return ProbeSpans(defs, recs, ps.n_counted, ps.n_truncated, ps.n_runner, runner[:ps.n_runner_listed].copy(), mask, obs_cap)
+
+    return _settle(one, workload, lim0, rounds, seed0, total, seeds, len(defs), "probe_spans: more records than definitions (internal)")
+
+
+def probe_spans(workload, spans, seed0=0, total=0, seeds=None, include=(A.PASS, A.PANIC, A.DEADLOCK, A.TIME_LIMIT), obs_cap=256, chunk=0,
+                config=None, limits=None, resolve=True):
+    """madsim_hip_probe_spans_range / madsim_hip_probe_spans_seeds: the virtual time from the first traced `from` to the first `to` behind
+    it, for 1 .. 16 `spans` = (from, to) pairs (from=None: from the start of the run; from == to: the time between the first two
+    occurrences), over the seeds [seed0, seed0 + total) — or the strictly ascending `seeds` —, reduced on the device: returns a ProbeSpans.
+    A seed is counted when its verdict is in `include`; the first `obs_cap` observations of a seed are visible; `chunk` = seeds per trace
+    launch, 0 = the library's default — it never shows in the result.  resolve: as runtime.census."""
+    if _inited_device is None:
+        init(0)
+    L = lib()
+    return _probe_spans(lambda *a: L.madsim_hip_probe_spans_range(workload.ref(), *a), lambda *a: L.madsim_hip_probe_spans_seeds(workload.ref(), *a),
+                        workload, spans, seed0, total, seeds, include, obs_cap, chunk, config, limits, resolve)
+
+
 def observe_seed(workload, seed, config=None, limits=None, cap=1 << 16, resolve=True):
     """What one seed traced, as oracle.observe_seed gives it: (list of values, A.Result)."""
     t = trace_seeds(workload, [seed], config, limits, obs_cap=cap, log_cap=0, resolve=resolve)[0]
@@ -1862,6 +2099,11 @@ class Context:
         return _trace_seeds(lambda *a: lib().madsim_hip_ctx_trace_seeds(self._h, workload.ref(), *a), workload, seeds, config, limits, obs_cap,
                             log_cap, resolve)
 
+    def timeline(self, workload, seeds, config=None, limits=None, obs_cap=256, resolve=True):
+        """runtime.timeline on this context (madsim_hip_ctx_timeline_seeds)."""
+        return _timeline(lambda *a: lib().madsim_hip_ctx_timeline_seeds(self._h, workload.ref(), *a), workload, seeds, config, limits, obs_cap,
+                         resolve)
+
     def post_mortem(self, workload, seeds, task_cap=32, config=None, limits=None, resolve=True, lengths=False):
         """runtime.post_mortem on this context (madsim_hip_ctx_task_states)."""
         return _post_mortem(lambda *a: lib().madsim_hip_ctx_task_states(self._h, workload.ref(), *a), workload, seeds, task_cap, config, limits,
@@ -1904,6 +2146,14 @@ class Context:
         return _probe_order(lambda *a: L.madsim_hip_ctx_probe_order_range(self._h, workload.ref(), *a),
                             lambda *a: L.madsim_hip_ctx_probe_order_seeds(self._h, workload.ref(), *a), self.census, workload, vocabulary, seed0,
                             total, seeds, include, obs_cap, chunk, config, limits, resolve)
+
+    def probe_spans(self, workload, spans, seed0=0, total=0, seeds=None, include=(A.PASS, A.PANIC, A.DEADLOCK, A.TIME_LIMIT), obs_cap=256, chunk=0,
+                    config=None, limits=None, resolve=True):
+        """runtime.probe_spans on this context (madsim_hip_ctx_probe_spans_range / madsim_hip_ctx_probe_spans_seeds)."""
+        L = lib()
+        return _probe_spans(lambda *a: L.madsim_hip_ctx_probe_spans_range(self._h, workload.ref(), *a),
+                            lambda *a: L.madsim_hip_ctx_probe_spans_seeds(self._h, workload.ref(), *a), workload, spans, seed0, total, seeds,
+                            include, obs_cap, chunk, config, limits, resolve)
 
     def observe_seed(self, workload, seed, config=None, limits=None, cap=1 << 16, resolve=True):
         """runtime.observe_seed on this context."""
