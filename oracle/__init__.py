@@ -26,7 +26,9 @@ class OracleStats(C.Structure):
                 ("scopes_expired", C.c_uint32), ("scopes_completed", C.c_uint32), ("ticks_first_poll", C.c_uint32),
                 ("ticks_parked", C.c_uint32), ("sel_won_recv", C.c_uint32), ("sel_won_time", C.c_uint32),
                 ("sel_won_ctrl_c", C.c_uint32), ("msgs_lost", C.c_uint32), ("sig_lost", C.c_uint32),
-                ("sig_caught", C.c_uint32), ("sig_killed", C.c_uint32)]
+                ("sig_caught", C.c_uint32), ("sig_killed", C.c_uint32),
+                # test-only counters of the timer heap, summed likewise: pops, and pops that left a root with the popped entry's deadline
+                ("heap_pops", C.c_uint32), ("heap_tie_pops", C.c_uint32)]
 
 
 class OracleError(RuntimeError):

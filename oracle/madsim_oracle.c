@@ -356,7 +356,9 @@ static event_t timer_pop(sim_t* S) {                      /* BinaryHeap::pop */
         if (child == end - 1) { d[pos] = d[child]; pos = child; }
         d[pos] = hole;
         heap_sift_up(d, 0, pos);
+        if (d[0].deadline == item.deadline) S->st.heap_tie_pops++;   /* the order of the two was the array algorithm's tie rule */
     }
+    S->st.heap_pops++;
     return item;
 }
 
@@ -1816,6 +1818,7 @@ static int run_one(const madsim_workload_t* w, const madsim_config_t* cfg, const
         stats->sel_won_recv += S.st.sel_won_recv; stats->sel_won_time += S.st.sel_won_time; stats->sel_won_ctrl_c += S.st.sel_won_ctrl_c;
         stats->msgs_lost += S.st.msgs_lost; stats->sig_lost += S.st.sig_lost; stats->sig_caught += S.st.sig_caught;
         stats->sig_killed += S.st.sig_killed;
+        stats->heap_pops += S.st.heap_pops; stats->heap_tie_pops += S.st.heap_tie_pops;
         if (S.st.max_heap > stats->max_heap) stats->max_heap = S.st.max_heap;
         if (S.st.max_ready > stats->max_ready) stats->max_ready = S.st.max_ready;
         if (S.st.max_tasks > stats->max_tasks) stats->max_tasks = S.st.max_tasks;

@@ -33,6 +33,9 @@ typedef struct madsim_oracle_stats {
     uint32_t sig_lost;          /* ctrl-c signals nobody waited for, or dropped with a select's subscription           */
     uint32_t sig_caught;        /* ctrl_c() calls and ctrl-c arms that completed                                       */
     uint32_t sig_killed;        /* ctrl-c signals to a node without a handler: kill_id                                 */
+    /* TEST-ONLY counters of the timer heap, summed likewise: what tests/heap_cases.py holds its tie-dense workloads to */
+    uint32_t heap_pops;         /* BinaryHeap::pop calls                                                               */
+    uint32_t heap_tie_pops;     /* ... after which the new root's deadline equals the popped entry's                   */
 } madsim_oracle_stats_t;
 
 /* Events in which a seed leaves the device runner's workload MODEL (not reference concepts; madsim_oracle.c model_event). */
