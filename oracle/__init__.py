@@ -19,6 +19,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.path.join(_HERE, "libmadsim_oracle.so")
 
 
+OP_COUNT = max(A.OP.values()) + 1      # MS_OP__COUNT
+
+
 class OracleStats(C.Structure):
     _fields_ = [("max_heap", C.c_uint32), ("max_ready", C.c_uint32), ("max_tasks", C.c_uint32),
                 ("max_msgs", C.c_uint32), ("max_regs", C.c_uint32), ("max_conns", C.c_uint32), ("max_cq", C.c_uint32),
@@ -28,7 +31,9 @@ class OracleStats(C.Structure):
                 ("sel_won_ctrl_c", C.c_uint32), ("msgs_lost", C.c_uint32), ("sig_lost", C.c_uint32),
                 ("sig_caught", C.c_uint32), ("sig_killed", C.c_uint32),
                 # test-only counters of the timer heap, summed likewise: pops, and pops that left a root with the popped entry's deadline
-                ("heap_pops", C.c_uint32), ("heap_tie_pops", C.c_uint32)]
+                ("heap_pops", C.c_uint32), ("heap_tie_pops", C.c_uint32),
+                # test-only poll counters, summed likewise: op_polls[op] = polls of a task body standing at an instruction with that opcode
+                ("op_polls", C.c_uint32 * OP_COUNT)]
 
 
 class OracleError(RuntimeError):
@@ -63,6 +68,10 @@ def lib():
         L.madsim_oracle_run_batch.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), C.c_uint64, C.c_uint64,
                                               C.POINTER(A.Limits), C.c_void_p, C.POINTER(A.Summary),
                                               C.POINTER(OracleStats)]
+        L.madsim_oracle_run_batch_sized.restype = C.c_int
+        L.madsim_oracle_run_batch_sized.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), C.c_uint64, C.c_uint64,
+                                                    C.POINTER(A.Limits), C.c_void_p, C.POINTER(A.Summary),
+                                                    C.POINTER(OracleStats), C.c_uint64]
         L.madsim_oracle_run_batch_pure.restype = C.c_int
         L.madsim_oracle_run_batch_pure.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), C.c_uint64, C.c_uint64,
                                                    C.POINTER(A.Limits), C.c_void_p, C.c_void_p]
@@ -91,8 +100,9 @@ def run_batch(workload, seed0, count, config=None, limits=None, want_stats=False
     out = np.zeros(count, dtype=A.RESULT_DTYPE)
     summ = A.Summary()
     st = OracleStats()
-    rc = lib().madsim_oracle_run_batch(workload.ref(), C.byref(cfg), seed0, count, C.byref(lim),
-                                       out.ctypes.data_as(C.c_void_p), C.byref(summ), C.byref(st))
+    # (the sized entry point: the struct grows at its end, and madsim_oracle_run_batch keeps to the size earlier callers allocate)
+    rc = lib().madsim_oracle_run_batch_sized(workload.ref(), C.byref(cfg), seed0, count, C.byref(lim),
+                                             out.ctypes.data_as(C.c_void_p), C.byref(summ), C.byref(st), C.sizeof(OracleStats))
     if rc != 0:
         raise OracleError(rc)
     return (out, summ, st) if want_stats else (out, summ)

@@ -822,6 +822,7 @@ static int poll_body(sim_t* S, uint16_t slot) {
         task_t* t = &S->tasks.p[slot];
         if (t->pc >= w->n_insns) return 1;
         const madsim_insn_t* in = &w->insns[t->pc];
+        S->st.op_polls[in->op]++;                          /* (validate: every op < MS_OP__COUNT) */
         switch (in->op) {                                  /* ops whose `a` names an Endpoint, through a port-0 table entry: */
         case MS_OP_SEND: case MS_OP_CONNECT: case MS_OP_RPC_CALL: case MS_OP_REPLY: case MS_OP_RECV:
         case MS_OP_RECV_TIMEOUT: case MS_OP_ACCEPT: case MS_OP_RPC_REPLY:
@@ -1819,6 +1820,7 @@ static int run_one(const madsim_workload_t* w, const madsim_config_t* cfg, const
         stats->msgs_lost += S.st.msgs_lost; stats->sig_lost += S.st.sig_lost; stats->sig_caught += S.st.sig_caught;
         stats->sig_killed += S.st.sig_killed;
         stats->heap_pops += S.st.heap_pops; stats->heap_tie_pops += S.st.heap_tie_pops;
+        for (int op = 0; op < MS_OP__COUNT; op++) stats->op_polls[op] += S.st.op_polls[op];
         if (S.st.max_heap > stats->max_heap) stats->max_heap = S.st.max_heap;
         if (S.st.max_ready > stats->max_ready) stats->max_ready = S.st.max_ready;
         if (S.st.max_tasks > stats->max_tasks) stats->max_tasks = S.st.max_tasks;
@@ -1841,15 +1843,22 @@ static int run_one(const madsim_workload_t* w, const madsim_config_t* cfg, const
  * ---------------------------------------------------------------------------------------------- */
 static double now_s(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec + ts.tv_nsec * 1e-9; }
 
-int madsim_oracle_run_batch(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0,
-                            uint64_t count, const madsim_limits_t* lim, madsim_result_t* out,
-                            madsim_summary_t* summary, madsim_oracle_stats_t* stats) {
+_Static_assert(__builtin_offsetof(madsim_oracle_stats_t, op_polls) == MADSIM_ORACLE_STATS_V1_BYTES, "the struct grows at its end only");
+/* `stats_bytes`: how much of madsim_oracle_stats_t the caller's `stats` holds.  The struct grows at its end, and the caller allocates it: a
+ * caller built against an earlier header passes a shorter one, so nothing behind stats_bytes is read or written. */
+int madsim_oracle_run_batch_sized(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0,
+                                  uint64_t count, const madsim_limits_t* lim, madsim_result_t* out,
+                                  madsim_summary_t* summary, void* stats, uint64_t stats_bytes) {
     { const int bad = cfg ? validate(w, cfg) : MADSIM_E_ARG; if (bad) return bad; }
     double t0 = now_s();
     uint64_t first = UINT64_MAX, nfail = 0, tsteps = 0, tclock = 0;
+    madsim_oracle_stats_t full; memset(&full, 0, sizeof full);
+    if (stats_bytes > sizeof full) stats_bytes = sizeof full;
+    if (stats) memcpy(&full, stats, stats_bytes);          /* (the counters add to what the caller's struct holds, as they always did) */
     for (uint64_t i = 0; i < count; i++) {
         madsim_result_t r;
-        const int err = run_one(w, cfg, lim, seed0 + i, &r, NULL, 0, NULL, stats, 1, NULL);
+        const int err = run_one(w, cfg, lim, seed0 + i, &r, NULL, 0, NULL, stats ? &full : NULL, 1, NULL);
+        if (stats) memcpy(stats, &full, stats_bytes);
         if (err) return err;
         if (out) out[i] = r;
         if (r.verdict != MADSIM_PASS) { nfail++; if (seed0 + i < first) first = seed0 + i; }
@@ -1860,6 +1869,13 @@ int madsim_oracle_run_batch(const madsim_workload_t* w, const madsim_config_t* c
         summary->total_clock_ns = tclock; summary->kernel_ms = 0.0; summary->wall_s = now_s() - t0;
     }
     return 0;
+}
+
+/* The entry point as every caller built before op_polls knows it: its `stats` ends in front of op_polls (MADSIM_ORACLE_STATS_V1_BYTES). */
+int madsim_oracle_run_batch(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0,
+                            uint64_t count, const madsim_limits_t* lim, madsim_result_t* out,
+                            madsim_summary_t* summary, madsim_oracle_stats_t* stats) {
+    return madsim_oracle_run_batch_sized(w, cfg, seed0, count, lim, out, summary, stats, MADSIM_ORACLE_STATS_V1_BYTES);
 }
 
 int64_t madsim_oracle_trace_seed(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed,

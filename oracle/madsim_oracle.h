@@ -36,6 +36,10 @@ typedef struct madsim_oracle_stats {
     /* TEST-ONLY counters of the timer heap, summed likewise: what tests/heap_cases.py holds its tie-dense workloads to */
     uint32_t heap_pops;         /* BinaryHeap::pop calls                                                               */
     uint32_t heap_tie_pops;     /* ... after which the new root's deadline equals the popped entry's                   */
+    /* TEST-ONLY poll counters, summed likewise: op_polls[op] = how often a task body was polled while it stood at an instruction with
+     * that opcode (first polls and re-polls alike; a light op that runs through counts once).  The device equals this oracle seed for
+     * seed, so "the seeds of a case poll op X" holds for every build the case runs on: what tests/build_cases.py rests on */
+    uint32_t op_polls[MS_OP__COUNT];
 } madsim_oracle_stats_t;
 
 /* Events in which a seed leaves the device runner's workload MODEL (not reference concepts; madsim_oracle.c model_event). */
@@ -58,9 +62,17 @@ typedef struct madsim_oracle_stats {
  * becomes a verdict.  Returned by every entry point below (the trace / observe ones return it as their negative length). */
 #define MADSIM_ORACLE_E_OPCODE (-100)
 
+/* `stats` here is the struct as it was before op_polls: the caller allocates it, and callers built against the earlier header pass those
+ * MADSIM_ORACLE_STATS_V1_BYTES — this entry point writes nothing behind them.  The whole struct: madsim_oracle_run_batch_sized. */
+#define MADSIM_ORACLE_STATS_V1_BYTES 80u   /* offsetof(madsim_oracle_stats_t, op_polls) */
 int madsim_oracle_run_batch(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0,
                             uint64_t count, const madsim_limits_t* lim, madsim_result_t* out,
                             madsim_summary_t* summary, madsim_oracle_stats_t* stats);
+/* ... with `stats_bytes` = the size of the caller's struct (sizeof(madsim_oracle_stats_t) for the current one): nothing behind it is
+ * read or written, so the struct can go on growing at its end. */
+int madsim_oracle_run_batch_sized(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0,
+                                  uint64_t count, const madsim_limits_t* lim, madsim_result_t* out,
+                                  madsim_summary_t* summary, void* stats, uint64_t stats_bytes);
 
 /* The same restatement with the model's ceilings switched OFF: unbounded containers throughout, `events[i]` = MADSIM_ORACLE_ME_*
  * mask of seed i (0 = the seed never met a ceiling, and its result equals madsim_oracle_run_batch's byte for byte). */

@@ -137,6 +137,49 @@ extern "C" int madsim_emu_variants(int32_t* out6, int cap) {
     return madsim_k::n_variants;
 }
 
+#ifdef MADSIM_EMU_OPS
+#include <unistd.h>
+// tools/build_coverage.py: polls per (row of variant_table, opcode), noted by emu_shim.h's REG markers; written as text when the process ends —
+// one line per row, to $MADSIM_EMU_OPS_OUT.<pid> (a pytest run may be several processes)
+static int emu_ops_row = -1;
+static uint64_t emu_ops[128][MS_OP__COUNT];
+void emu_op_note(int id, unsigned op) { if ((id == 2 || id == 9 || id == 13) && emu_ops_row >= 0 && emu_ops_row < 128 && op < MS_OP__COUNT) emu_ops[emu_ops_row][op]++; }
+static void emu_ops_write(void) {
+    const char* base = getenv("MADSIM_EMU_OPS_OUT");
+    if (!base) return;
+    const std::string path = std::string(base) + "." + std::to_string((long)getpid());
+    FILE* f = fopen(path.c_str(), "w");
+    if (!f) return;
+    for (int i = 0; i < madsim_k::n_variants; i++) {
+        for (int op = 0; op < MS_OP__COUNT; op++) fprintf(f, "%llu ", (unsigned long long)emu_ops[i][op]);
+        fprintf(f, "\n");
+    }
+    fclose(f);
+}
+static const int emu_ops_registered = atexit(emu_ops_write);
+#endif
+
+// the row of madsim_k::variant_table the last madsim_emu_run_batch of this thread ran its lanes on (-1: none yet)
+static thread_local int emu_last_variant = -1;
+extern "C" int madsim_emu_last_variant(void) { return emu_last_variant; }
+
+// which rows of variant_table select_variant can name at all: every parameter block it reads — lane stride 8 .. 64, spill region or none,
+// every features word, state in LDS or global, narrow entries, compact layout, determinism log, register ready queue, trace launch or not —
+// reach[i] = 1 when some block selects row i (up to cap rows); returns n_variants
+extern "C" int madsim_emu_selectable(uint8_t* reach, int cap) {
+    using namespace madsim_k;
+    for (int i = 0; i < n_variants && i < cap; i++) reach[i] = 0;
+    KParams P{};
+    for (uint32_t lw = 3; lw <= 6; lw++) for (uint32_t spill = 0; spill < 2; spill++) for (uint32_t feat = 0; feat < 4096; feat++)
+        for (uint32_t bits = 0; bits < 64; bits++) {
+            P.lw_shift = lw; P.heap_spill = spill; P.features = feat;
+            P.gstate_mode = bits & 1; P.narrow = bits >> 1 & 1; P.compact = bits >> 2 & 1; P.no_log = bits >> 3 & 1; P.rq_in_reg = bits >> 4 & 1;
+            const int i = variant_index(select_variant(P, (bits >> 5 & 1) != 0));
+            if (i >= 0 && i < cap) reach[i] = 1;
+        }
+    return n_variants;
+}
+
 extern "C" int madsim_emu_run_batch(const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t count,
                                     const madsim_limits_t* lim, madsim_result_t* out, int num_cus, uint8_t* tlog,
                                     uint64_t tcap, uint64_t* tlen) {
@@ -184,6 +227,10 @@ extern "C" int madsim_emu_run_batch(const madsim_workload_t* w, const madsim_con
             using namespace madsim_k;
             const int vi = variant_index(select_variant(P, tlog != nullptr));      // the same build the GPU launcher would pick
             if (vi < 0) { emu_err = "select_variant named a build that is not compiled"; return MADSIM_E_LIMITS; }
+            emu_last_variant = vi;
+#ifdef MADSIM_EMU_OPS
+            emu_ops_row = vi;
+#endif
             emu_kernels[vi](P);
         }
 #ifdef MADSIM_EMU_SITES

@@ -68,5 +68,12 @@ static inline uint32_t table_copy_stride(uint32_t) { return 1; }          // eac
 #ifdef MADSIM_EMU_REGIONS   // tools/divergence_model.py: per-iteration code-region visit counts of each emulated lane
 void emu_region(int id);
 #define REG(id) emu_region(id)
+#elif defined(MADSIM_EMU_OPS)   // tools/build_coverage.py: which opcodes poll_task dispatches, per build.  The kernel's region markers expand
+// in scope of poll_task's `op` at three places — REG(2), the instruction a poll round starts at (a re-poll included); REG(13), every op the
+// light-op loop runs; REG(9), the op a round begins behind that loop — which together see every instruction a task executes.  The other
+// markers, where no `op` is in scope, find the constant below and note nothing: the kernel sources are not touched.
+static const unsigned op = ~0u;
+void emu_op_note(int id, unsigned op);
+#define REG(id) emu_op_note((id), (unsigned)(op))
 #endif
 #endif
