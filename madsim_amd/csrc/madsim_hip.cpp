@@ -800,6 +800,34 @@ int lock_contexts(madsim_hip_ctx* const* ctxs, int n_ctx, const char* who, std::
     return 0;
 }
 
+// The contexts a campaign call runs on: one context (what CTX_ENTER does) or the contexts of a _multi call (what lock_contexts does, `who`
+// naming the entry point).  enter() checks and locks them; the locks are held for as long as this object lives.
+class Contexts {
+    madsim_hip_ctx* one_[1];
+    madsim_hip_ctx* const* ctxs_;
+    int n_;
+    const char* who_;                                            // (null: the single-context form)
+    std::vector<std::unique_lock<std::mutex>> locks_;
+public:
+    explicit Contexts(madsim_hip_ctx* c) : one_{c}, ctxs_(one_), n_(1), who_(nullptr) {}
+    Contexts(madsim_hip_ctx* const* ctxs, int n_ctx, const char* who) : one_{nullptr}, ctxs_(ctxs), n_(n_ctx), who_(who) {}
+    Contexts(const Contexts&) = delete;
+    Contexts& operator=(const Contexts&) = delete;
+    // `nothing_to_run`: the call's seed list is empty.  An empty list needs no device — the single-context forms' rule, and theirs only:
+    // without an open context they run on no context at all (the engines then fill the reports of an empty range and return 0), while a
+    // _multi call still asks for at least one context.
+    int enter(bool nothing_to_run = false) {
+        if (who_) return lock_contexts(ctxs_, n_, who_, locks_);
+        madsim_hip_ctx* const c = one_[0];
+        if (nothing_to_run && (!c || c->device < 0)) { ctxs_ = nullptr; n_ = 0; return 0; }
+        if (!c || c->device < 0) return fail(MADSIM_E_NOINIT, "no context (madsim_hip_init / madsim_hip_ctx_create has not been called)");
+        locks_.emplace_back(c->mu);
+        return c->bind();
+    }
+    madsim_hip_ctx* const* ctxs() const { return ctxs_; }
+    int n() const { return n_; }
+};
+
 }  // namespace
 
 extern "C" {
@@ -2496,31 +2524,13 @@ int run_variants_impl(madsim_hip_ctx* const* ctxs, int n_ctx, const madsim_sweep
 }  // extern "C++"
 }  // namespace
 
-int madsim_hip_ctx_run_campaign(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total,
-                                uint64_t batch, uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim, madsim_campaign_t* out) {
-    if (!out) return fail(MADSIM_E_ARG, "null campaign report");
-    if (int rc = check_resolve_flags(flags)) return rc;
-    CTX_ENTER(c);
-    madsim_hip_ctx* one[1] = {c};
-    return run_campaign_impl(one, 1, w, cfg, seed0, total, batch, in_flight, flags, lim, out);
-}
-
-int madsim_hip_run_campaign_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_workload_t* w, const madsim_config_t* cfg,
-                                  uint64_t seed0, uint64_t total, uint64_t batch, uint32_t in_flight, uint32_t flags,
-                                  const madsim_limits_t* lim, madsim_campaign_t* out) {
-    if (!out) return fail(MADSIM_E_ARG, "null campaign report");
-    if (int rc = check_resolve_flags(flags)) return rc;
-    std::vector<std::unique_lock<std::mutex>> locks;
-    if (int rc = lock_contexts(ctxs, n_ctx, "run_campaign_multi", locks)) return rc;
-    return run_campaign_impl(ctxs, n_ctx, w, cfg, seed0, total, batch, in_flight, flags, lim, out);
-}
-
 // The collecting, statistics and grouping forms and the list campaigns: the argument errors that need no device are told first, so that a
 // host without a GPU hears about them too.  `form` is the part the entry point cannot do without; the other parts are checked when given.
 // The errors come in the order they always came in: the report, the form's own part, the first part given (grouping before statistics
-// before collecting), the resolve flags, a grouping batch's size, the remaining parts, the batches in flight.
+// before collecting), the resolve flags, a grouping batch's size, the remaining parts, the batches in flight.  (FORM_PLAIN, the form with
+// the report alone, hears about its batches in flight from the engine, behind the workload's own errors: where it always did.)
 namespace {
-enum CampaignForm { FORM_ANY, FORM_COLLECT, FORM_STATS, FORM_GROUPS };
+enum CampaignForm { FORM_ANY, FORM_PLAIN, FORM_COLLECT, FORM_STATS, FORM_GROUPS };
 int check_collect_part(const madsim_collect_t* col, uint32_t flags) {
     if (col->cap && !col->failures) return fail(MADSIM_E_ARG, "madsim_collect_t.cap > 0 without a failures array");
     if ((flags & MADSIM_CAMPAIGN_STOP_AT_CAP) && !col->cap) return fail(MADSIM_E_ARG, "MADSIM_CAMPAIGN_STOP_AT_CAP with cap == 0");
@@ -2551,65 +2561,10 @@ int check_campaign_args(CampaignForm form, const madsim_campaign_t* out, const m
         return fail(MADSIM_E_ARG, "a grouping campaign's batch holds at most MADSIM_GROUP_MAX_BATCH (2^20) seeds: the device table is sized to the batch");
     if (grp && st && (rc = check_stats_part(st))) return rc;
     if ((grp || st) && col && (rc = check_collect_part(col, flags))) return rc;
-    if (in_flight > (uint32_t)madsim_hip_ctx::CAMPAIGN_MAX) return fail(MADSIM_E_ARG, "at most 8 batches in flight per context");
+    if (form != FORM_PLAIN && in_flight > (uint32_t)madsim_hip_ctx::CAMPAIGN_MAX) return fail(MADSIM_E_ARG, "at most 8 batches in flight per context");
     return 0;
 }
 }  // namespace
-
-int madsim_hip_ctx_run_campaign_collect(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total,
-                                        uint64_t batch, uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim, madsim_campaign_t* out,
-                                        madsim_collect_t* col) {
-    if (int rc = check_campaign_args(FORM_COLLECT, out, col, nullptr, nullptr, total, batch, in_flight, flags)) return rc;
-    CTX_ENTER(c);
-    madsim_hip_ctx* one[1] = {c};
-    return run_campaign_impl(one, 1, w, cfg, seed0, total, batch, in_flight, flags, lim, out, col);
-}
-
-int madsim_hip_run_campaign_collect_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_workload_t* w, const madsim_config_t* cfg,
-                                          uint64_t seed0, uint64_t total, uint64_t batch, uint32_t in_flight, uint32_t flags,
-                                          const madsim_limits_t* lim, madsim_campaign_t* out, madsim_collect_t* col) {
-    if (int rc = check_campaign_args(FORM_COLLECT, out, col, nullptr, nullptr, total, batch, in_flight, flags)) return rc;
-    std::vector<std::unique_lock<std::mutex>> locks;
-    if (int rc = lock_contexts(ctxs, n_ctx, "run_campaign_collect_multi", locks)) return rc;
-    return run_campaign_impl(ctxs, n_ctx, w, cfg, seed0, total, batch, in_flight, flags, lim, out, col);
-}
-
-int madsim_hip_ctx_run_campaign_stats(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total,
-                                      uint64_t batch, uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim, madsim_campaign_t* out,
-                                      madsim_collect_t* col, madsim_stats_t* st) {
-    if (int rc = check_campaign_args(FORM_STATS, out, col, st, nullptr, total, batch, in_flight, flags)) return rc;
-    CTX_ENTER(c);
-    madsim_hip_ctx* one[1] = {c};
-    return run_campaign_impl(one, 1, w, cfg, seed0, total, batch, in_flight, flags, lim, out, col, st);
-}
-
-int madsim_hip_run_campaign_stats_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_workload_t* w, const madsim_config_t* cfg,
-                                        uint64_t seed0, uint64_t total, uint64_t batch, uint32_t in_flight, uint32_t flags,
-                                        const madsim_limits_t* lim, madsim_campaign_t* out, madsim_collect_t* col, madsim_stats_t* st) {
-    if (int rc = check_campaign_args(FORM_STATS, out, col, st, nullptr, total, batch, in_flight, flags)) return rc;
-    std::vector<std::unique_lock<std::mutex>> locks;
-    if (int rc = lock_contexts(ctxs, n_ctx, "run_campaign_stats_multi", locks)) return rc;
-    return run_campaign_impl(ctxs, n_ctx, w, cfg, seed0, total, batch, in_flight, flags, lim, out, col, st);
-}
-
-int madsim_hip_ctx_run_campaign_groups(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total,
-                                       uint64_t batch, uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim, madsim_campaign_t* out,
-                                       madsim_collect_t* col, madsim_stats_t* st, madsim_groups_t* grp) {
-    if (int rc = check_campaign_args(FORM_GROUPS, out, col, st, grp, total, batch, in_flight, flags)) return rc;
-    CTX_ENTER(c);
-    madsim_hip_ctx* one[1] = {c};
-    return run_campaign_impl(one, 1, w, cfg, seed0, total, batch, in_flight, flags, lim, out, col, st, grp);
-}
-
-int madsim_hip_run_campaign_groups_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_workload_t* w, const madsim_config_t* cfg,
-                                         uint64_t seed0, uint64_t total, uint64_t batch, uint32_t in_flight, uint32_t flags,
-                                         const madsim_limits_t* lim, madsim_campaign_t* out, madsim_collect_t* col, madsim_stats_t* st,
-                                         madsim_groups_t* grp) {
-    if (int rc = check_campaign_args(FORM_GROUPS, out, col, st, grp, total, batch, in_flight, flags)) return rc;
-    std::vector<std::unique_lock<std::mutex>> locks;
-    if (int rc = lock_contexts(ctxs, n_ctx, "run_campaign_groups_multi", locks)) return rc;
-    return run_campaign_impl(ctxs, n_ctx, w, cfg, seed0, total, batch, in_flight, flags, lim, out, col, st, grp);
-}
 
 // The differential forms: argument errors first, as the other forms.
 namespace {
@@ -2625,28 +2580,6 @@ int check_diff_args(const madsim_campaign_t* outA, const madsim_campaign_t* outB
     return 0;
 }
 }  // namespace
-
-int madsim_hip_ctx_run_campaign_diff(madsim_hip_ctx_t* c, const madsim_workload_t* wA, const madsim_config_t* cfgA, const madsim_limits_t* limA,
-                                     const madsim_workload_t* wB, const madsim_config_t* cfgB, const madsim_limits_t* limB, uint64_t seed0,
-                                     uint64_t total, uint64_t batch, uint32_t in_flight, uint32_t flags, madsim_campaign_t* outA,
-                                     madsim_campaign_t* outB, madsim_diff_t* diff) {
-    if (int rc = check_diff_args(outA, outB, diff, in_flight, flags)) return rc;
-    CTX_ENTER(c);
-    madsim_hip_ctx* one[1] = {c};
-    const madsim_sweep_variant_t side[2] = {{wA, cfgA, limA, outA}, {wB, cfgB, limB, outB}};
-    return run_variants_impl(one, 1, side, 2, seed0, total, batch, in_flight, flags, nullptr, PairForm{diff, nullptr});
-}
-
-int madsim_hip_run_campaign_diff_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_workload_t* wA, const madsim_config_t* cfgA,
-                                       const madsim_limits_t* limA, const madsim_workload_t* wB, const madsim_config_t* cfgB,
-                                       const madsim_limits_t* limB, uint64_t seed0, uint64_t total, uint64_t batch, uint32_t in_flight,
-                                       uint32_t flags, madsim_campaign_t* outA, madsim_campaign_t* outB, madsim_diff_t* diff) {
-    if (int rc = check_diff_args(outA, outB, diff, in_flight, flags)) return rc;
-    std::vector<std::unique_lock<std::mutex>> locks;
-    if (int rc = lock_contexts(ctxs, n_ctx, "run_campaign_diff_multi", locks)) return rc;
-    const madsim_sweep_variant_t side[2] = {{wA, cfgA, limA, outA}, {wB, cfgB, limB, outB}};
-    return run_variants_impl(ctxs, n_ctx, side, 2, seed0, total, batch, in_flight, flags, nullptr, PairForm{diff, nullptr});
-}
 
 // ---- list campaigns: every campaign form over an explicit seed list ----------------------------------------------------------------
 // Argument errors first, as the other forms: the list itself (NULL with n > 0; a pair that does not ascend strictly, named by the position
@@ -2669,52 +2602,6 @@ int check_seeds_args(const uint64_t* seeds, uint64_t n, uint64_t batch, uint32_t
 }
 }  // namespace
 
-int madsim_hip_ctx_run_seeds_campaign(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n,
-                                      uint64_t batch, uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim, madsim_campaign_t* out,
-                                      madsim_collect_t* col, madsim_stats_t* st, madsim_groups_t* grp) {
-    if (int rc = check_seeds_args(seeds, n, batch, in_flight, flags, out, col, st, grp)) return rc;
-    if (n == 0 && (!c || c->device < 0))                         // an empty list needs no device: the reports of an empty range, and 0
-        return run_campaign_impl(nullptr, 0, w, cfg, 0, 0, batch, in_flight, flags, lim, out, col, st, grp);
-    CTX_ENTER(c);
-    madsim_hip_ctx* one[1] = {c};
-    return run_campaign_impl(one, 1, w, cfg, 0, n, batch, in_flight, flags, lim, out, col, st, grp, n ? seeds : nullptr);
-}
-
-int madsim_hip_run_seeds_campaign_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_workload_t* w, const madsim_config_t* cfg,
-                                        const uint64_t* seeds, uint64_t n, uint64_t batch, uint32_t in_flight, uint32_t flags,
-                                        const madsim_limits_t* lim, madsim_campaign_t* out, madsim_collect_t* col, madsim_stats_t* st,
-                                        madsim_groups_t* grp) {
-    if (int rc = check_seeds_args(seeds, n, batch, in_flight, flags, out, col, st, grp)) return rc;
-    std::vector<std::unique_lock<std::mutex>> locks;
-    if (int rc = lock_contexts(ctxs, n_ctx, "run_seeds_campaign_multi", locks)) return rc;
-    return run_campaign_impl(ctxs, n_ctx, w, cfg, 0, n, batch, in_flight, flags, lim, out, col, st, grp, n ? seeds : nullptr);
-}
-
-int madsim_hip_ctx_run_seeds_campaign_diff(madsim_hip_ctx_t* c, const madsim_workload_t* wA, const madsim_config_t* cfgA, const madsim_limits_t* limA,
-                                           const madsim_workload_t* wB, const madsim_config_t* cfgB, const madsim_limits_t* limB,
-                                           const uint64_t* seeds, uint64_t n, uint64_t batch, uint32_t in_flight, uint32_t flags,
-                                           madsim_campaign_t* outA, madsim_campaign_t* outB, madsim_diff_t* diff) {
-    if (int rc = check_seed_list(seeds, n)) return rc;
-    if (int rc = check_diff_args(outA, outB, diff, in_flight, flags)) return rc;
-    const madsim_sweep_variant_t side[2] = {{wA, cfgA, limA, outA}, {wB, cfgB, limB, outB}};
-    if (n == 0 && (!c || c->device < 0)) return run_variants_impl(nullptr, 0, side, 2, 0, 0, batch, in_flight, flags, nullptr, PairForm{diff, nullptr});      // (no device needed)
-    CTX_ENTER(c);
-    madsim_hip_ctx* one[1] = {c};
-    return run_variants_impl(one, 1, side, 2, 0, n, batch, in_flight, flags, n ? seeds : nullptr, PairForm{diff, nullptr});
-}
-
-int madsim_hip_run_seeds_campaign_diff_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_workload_t* wA, const madsim_config_t* cfgA,
-                                             const madsim_limits_t* limA, const madsim_workload_t* wB, const madsim_config_t* cfgB,
-                                             const madsim_limits_t* limB, const uint64_t* seeds, uint64_t n, uint64_t batch, uint32_t in_flight,
-                                             uint32_t flags, madsim_campaign_t* outA, madsim_campaign_t* outB, madsim_diff_t* diff) {
-    if (int rc = check_seed_list(seeds, n)) return rc;
-    if (int rc = check_diff_args(outA, outB, diff, in_flight, flags)) return rc;
-    std::vector<std::unique_lock<std::mutex>> locks;
-    if (int rc = lock_contexts(ctxs, n_ctx, "run_seeds_campaign_diff_multi", locks)) return rc;
-    const madsim_sweep_variant_t side[2] = {{wA, cfgA, limA, outA}, {wB, cfgB, limB, outB}};
-    return run_variants_impl(ctxs, n_ctx, side, 2, 0, n, batch, in_flight, flags, n ? seeds : nullptr, PairForm{diff, nullptr});
-}
-
 // ---- paired campaigns: per-seed metric deltas between two variants ------------------------------------------------------------------
 // The differential entry points with a trailing madsim_paired_t and an optional diff report.  Argument errors first, as the other forms.
 namespace {
@@ -2733,54 +2620,6 @@ int check_paired_args(const madsim_campaign_t* outA, const madsim_campaign_t* ou
     return 0;
 }
 }  // namespace
-
-int madsim_hip_ctx_run_paired_campaign(madsim_hip_ctx_t* c, const madsim_workload_t* wA, const madsim_config_t* cfgA, const madsim_limits_t* limA,
-                                       const madsim_workload_t* wB, const madsim_config_t* cfgB, const madsim_limits_t* limB, uint64_t seed0,
-                                       uint64_t total, uint64_t batch, uint32_t in_flight, uint32_t flags, madsim_campaign_t* outA,
-                                       madsim_campaign_t* outB, madsim_diff_t* diff, madsim_paired_t* pr) {
-    if (int rc = check_paired_args(outA, outB, diff, pr, in_flight, flags)) return rc;
-    CTX_ENTER(c);
-    madsim_hip_ctx* one[1] = {c};
-    const madsim_sweep_variant_t side[2] = {{wA, cfgA, limA, outA}, {wB, cfgB, limB, outB}};
-    return run_variants_impl(one, 1, side, 2, seed0, total, batch, in_flight, flags, nullptr, PairForm{diff, pr});
-}
-
-int madsim_hip_run_paired_campaign_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_workload_t* wA, const madsim_config_t* cfgA,
-                                         const madsim_limits_t* limA, const madsim_workload_t* wB, const madsim_config_t* cfgB,
-                                         const madsim_limits_t* limB, uint64_t seed0, uint64_t total, uint64_t batch, uint32_t in_flight,
-                                         uint32_t flags, madsim_campaign_t* outA, madsim_campaign_t* outB, madsim_diff_t* diff, madsim_paired_t* pr) {
-    if (int rc = check_paired_args(outA, outB, diff, pr, in_flight, flags)) return rc;
-    std::vector<std::unique_lock<std::mutex>> locks;
-    if (int rc = lock_contexts(ctxs, n_ctx, "run_paired_campaign_multi", locks)) return rc;
-    const madsim_sweep_variant_t side[2] = {{wA, cfgA, limA, outA}, {wB, cfgB, limB, outB}};
-    return run_variants_impl(ctxs, n_ctx, side, 2, seed0, total, batch, in_flight, flags, nullptr, PairForm{diff, pr});
-}
-
-int madsim_hip_ctx_run_seeds_campaign_paired(madsim_hip_ctx_t* c, const madsim_workload_t* wA, const madsim_config_t* cfgA, const madsim_limits_t* limA,
-                                             const madsim_workload_t* wB, const madsim_config_t* cfgB, const madsim_limits_t* limB,
-                                             const uint64_t* seeds, uint64_t n, uint64_t batch, uint32_t in_flight, uint32_t flags,
-                                             madsim_campaign_t* outA, madsim_campaign_t* outB, madsim_diff_t* diff, madsim_paired_t* pr) {
-    if (int rc = check_seed_list(seeds, n)) return rc;
-    if (int rc = check_paired_args(outA, outB, diff, pr, in_flight, flags)) return rc;
-    const madsim_sweep_variant_t side[2] = {{wA, cfgA, limA, outA}, {wB, cfgB, limB, outB}};
-    if (n == 0 && (!c || c->device < 0)) return run_variants_impl(nullptr, 0, side, 2, 0, 0, batch, in_flight, flags, nullptr, PairForm{diff, pr});      // (no device needed)
-    CTX_ENTER(c);
-    madsim_hip_ctx* one[1] = {c};
-    return run_variants_impl(one, 1, side, 2, 0, n, batch, in_flight, flags, n ? seeds : nullptr, PairForm{diff, pr});
-}
-
-int madsim_hip_run_seeds_campaign_paired_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_workload_t* wA, const madsim_config_t* cfgA,
-                                               const madsim_limits_t* limA, const madsim_workload_t* wB, const madsim_config_t* cfgB,
-                                               const madsim_limits_t* limB, const uint64_t* seeds, uint64_t n, uint64_t batch, uint32_t in_flight,
-                                               uint32_t flags, madsim_campaign_t* outA, madsim_campaign_t* outB, madsim_diff_t* diff,
-                                               madsim_paired_t* pr) {
-    if (int rc = check_seed_list(seeds, n)) return rc;
-    if (int rc = check_paired_args(outA, outB, diff, pr, in_flight, flags)) return rc;
-    std::vector<std::unique_lock<std::mutex>> locks;
-    if (int rc = lock_contexts(ctxs, n_ctx, "run_seeds_campaign_paired_multi", locks)) return rc;
-    const madsim_sweep_variant_t side[2] = {{wA, cfgA, limA, outA}, {wB, cfgB, limB, outB}};
-    return run_variants_impl(ctxs, n_ctx, side, 2, 0, n, batch, in_flight, flags, n ? seeds : nullptr, PairForm{diff, pr});
-}
 
 // ---- sweep campaigns: up to eight variants over one seed set ------------------------------------------------------------------------
 // Argument errors first, as the other forms — here the variants' validate() errors too, all told before any context is looked at.  `var`
@@ -2815,25 +2654,179 @@ int check_sweep_args(const madsim_sweep_variant_t* variants, uint32_t n_variants
 }
 }  // namespace
 
-int madsim_hip_ctx_run_sweep_campaign(madsim_hip_ctx_t* c, const madsim_sweep_variant_t* variants, uint32_t n_variants, uint64_t seed0, uint64_t total,
-                                      const uint64_t* seeds, uint64_t batch, uint32_t in_flight, uint32_t flags, madsim_sweep_t* sweep) {
-    std::vector<madsim_sweep_variant_t> var;
-    if (int rc = check_sweep_args(variants, n_variants, seed0, total, seeds, in_flight, flags, sweep, var)) return rc;
-    if (total == 0 && (!c || c->device < 0))                     // nothing to run needs no device: the reports of an empty range, and 0
-        return run_variants_impl(nullptr, 0, var.data(), n_variants, 0, 0, batch, in_flight, flags, nullptr, SweepForm{sweep, n_variants});
-    CTX_ENTER(c);
-    madsim_hip_ctx* one[1] = {c};
-    return run_variants_impl(one, 1, var.data(), n_variants, seed0, total, batch, in_flight, flags, total ? seeds : nullptr, SweepForm{sweep, n_variants});
+// ---- the campaign operations, each written once against the contexts it runs on ------------------------------------------------------
+// Every body: the argument errors that need no device, then the contexts (Contexts::enter), then the engine.  The entry points below, one per
+// context form (madsim_hip_ctx_X) and one per _multi form (madsim_hip_X_multi), only say which contexts and which seeds.  (The bodies are
+// static: inside this file's extern "C" block the library would export their plain names, and its list of symbols stays what it is.)
+namespace {
+// A call's seeds: the range [seed0, seed0 + total), or the strictly ascending list seeds[0 .. total), for which seed0 is 0.
+struct Seeds {
+    bool listed; uint64_t seed0, total; const uint64_t* seeds;
+    static Seeds range(uint64_t seed0, uint64_t total) { return {false, seed0, total, nullptr}; }
+    static Seeds list(const uint64_t* seeds, uint64_t n) { return {true, 0, n, seeds}; }
+    bool empty_list() const { return listed && total == 0; }
+    const uint64_t* engine_list() const { return total ? seeds : nullptr; }      // (the engines take a list by its pointer: none when it is empty)
+};
+
+// run_campaign, _collect, _stats, _groups (`form`: the part the range form cannot do without) and run_seeds_campaign.
+static int plain_campaign(Contexts&& on, CampaignForm form, const madsim_workload_t* w, const madsim_config_t* cfg, const Seeds& s, uint64_t batch,
+                   uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim, madsim_campaign_t* out, madsim_collect_t* col, madsim_stats_t* st,
+                   madsim_groups_t* grp) {
+    if (int rc = s.listed ? check_seeds_args(s.seeds, s.total, batch, in_flight, flags, out, col, st, grp)
+                          : check_campaign_args(form, out, col, st, grp, s.total, batch, in_flight, flags))
+        return rc;
+    if (int rc = on.enter(s.empty_list())) return rc;
+    return run_campaign_impl(on.ctxs(), on.n(), w, cfg, s.seed0, s.total, batch, in_flight, flags, lim, out, col, st, grp, s.engine_list());
 }
 
+// The differential and the paired forms, over a range or a list.  `paired`: the entry point takes a madsim_paired_t, and the diff report is optional.
+static int pair_campaign(Contexts&& on, bool paired, const madsim_workload_t* wA, const madsim_config_t* cfgA, const madsim_limits_t* limA,
+                  const madsim_workload_t* wB, const madsim_config_t* cfgB, const madsim_limits_t* limB, const Seeds& s, uint64_t batch, uint32_t in_flight,
+                  uint32_t flags, madsim_campaign_t* outA, madsim_campaign_t* outB, madsim_diff_t* diff, madsim_paired_t* pr) {
+    if (s.listed) if (int rc = check_seed_list(s.seeds, s.total)) return rc;
+    if (int rc = paired ? check_paired_args(outA, outB, diff, pr, in_flight, flags) : check_diff_args(outA, outB, diff, in_flight, flags)) return rc;
+    const madsim_sweep_variant_t side[2] = {{wA, cfgA, limA, outA}, {wB, cfgB, limB, outB}};
+    if (int rc = on.enter(s.empty_list())) return rc;
+    return run_variants_impl(on.ctxs(), on.n(), side, 2, s.seed0, s.total, batch, in_flight, flags, s.engine_list(), PairForm{diff, pr});
+}
+
+// The sweep form: one entry point for the range (seeds == NULL) and the list, so nothing to run is total == 0 either way.
+static int sweep_campaign(Contexts&& on, const madsim_sweep_variant_t* variants, uint32_t n_variants, uint64_t seed0, uint64_t total, const uint64_t* seeds,
+                   uint64_t batch, uint32_t in_flight, uint32_t flags, madsim_sweep_t* sweep) {
+    std::vector<madsim_sweep_variant_t> var;
+    if (int rc = check_sweep_args(variants, n_variants, seed0, total, seeds, in_flight, flags, sweep, var)) return rc;
+    if (int rc = on.enter(total == 0)) return rc;
+    return run_variants_impl(on.ctxs(), on.n(), var.data(), n_variants, seed0, total, batch, in_flight, flags, total ? seeds : nullptr,
+                             SweepForm{sweep, n_variants});
+}
+}  // namespace
+
+int madsim_hip_ctx_run_campaign(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total,
+                                uint64_t batch, uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim, madsim_campaign_t* out) {
+    return plain_campaign(Contexts(c), FORM_PLAIN, w, cfg, Seeds::range(seed0, total), batch, in_flight, flags, lim, out, nullptr, nullptr, nullptr);
+}
+int madsim_hip_run_campaign_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_workload_t* w, const madsim_config_t* cfg,
+                                  uint64_t seed0, uint64_t total, uint64_t batch, uint32_t in_flight, uint32_t flags,
+                                  const madsim_limits_t* lim, madsim_campaign_t* out) {
+    return plain_campaign(Contexts(ctxs, n_ctx, "run_campaign_multi"), FORM_PLAIN, w, cfg, Seeds::range(seed0, total), batch, in_flight, flags, lim, out,
+                          nullptr, nullptr, nullptr);
+}
+
+int madsim_hip_ctx_run_campaign_collect(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total,
+                                        uint64_t batch, uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim, madsim_campaign_t* out,
+                                        madsim_collect_t* col) {
+    return plain_campaign(Contexts(c), FORM_COLLECT, w, cfg, Seeds::range(seed0, total), batch, in_flight, flags, lim, out, col, nullptr, nullptr);
+}
+int madsim_hip_run_campaign_collect_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_workload_t* w, const madsim_config_t* cfg,
+                                          uint64_t seed0, uint64_t total, uint64_t batch, uint32_t in_flight, uint32_t flags,
+                                          const madsim_limits_t* lim, madsim_campaign_t* out, madsim_collect_t* col) {
+    return plain_campaign(Contexts(ctxs, n_ctx, "run_campaign_collect_multi"), FORM_COLLECT, w, cfg, Seeds::range(seed0, total), batch, in_flight, flags,
+                          lim, out, col, nullptr, nullptr);
+}
+
+int madsim_hip_ctx_run_campaign_stats(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total,
+                                      uint64_t batch, uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim, madsim_campaign_t* out,
+                                      madsim_collect_t* col, madsim_stats_t* st) {
+    return plain_campaign(Contexts(c), FORM_STATS, w, cfg, Seeds::range(seed0, total), batch, in_flight, flags, lim, out, col, st, nullptr);
+}
+int madsim_hip_run_campaign_stats_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_workload_t* w, const madsim_config_t* cfg,
+                                        uint64_t seed0, uint64_t total, uint64_t batch, uint32_t in_flight, uint32_t flags,
+                                        const madsim_limits_t* lim, madsim_campaign_t* out, madsim_collect_t* col, madsim_stats_t* st) {
+    return plain_campaign(Contexts(ctxs, n_ctx, "run_campaign_stats_multi"), FORM_STATS, w, cfg, Seeds::range(seed0, total), batch, in_flight, flags, lim,
+                          out, col, st, nullptr);
+}
+
+int madsim_hip_ctx_run_campaign_groups(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, uint64_t seed0, uint64_t total,
+                                       uint64_t batch, uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim, madsim_campaign_t* out,
+                                       madsim_collect_t* col, madsim_stats_t* st, madsim_groups_t* grp) {
+    return plain_campaign(Contexts(c), FORM_GROUPS, w, cfg, Seeds::range(seed0, total), batch, in_flight, flags, lim, out, col, st, grp);
+}
+int madsim_hip_run_campaign_groups_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_workload_t* w, const madsim_config_t* cfg,
+                                         uint64_t seed0, uint64_t total, uint64_t batch, uint32_t in_flight, uint32_t flags,
+                                         const madsim_limits_t* lim, madsim_campaign_t* out, madsim_collect_t* col, madsim_stats_t* st,
+                                         madsim_groups_t* grp) {
+    return plain_campaign(Contexts(ctxs, n_ctx, "run_campaign_groups_multi"), FORM_GROUPS, w, cfg, Seeds::range(seed0, total), batch, in_flight, flags,
+                          lim, out, col, st, grp);
+}
+
+int madsim_hip_ctx_run_seeds_campaign(madsim_hip_ctx_t* c, const madsim_workload_t* w, const madsim_config_t* cfg, const uint64_t* seeds, uint64_t n,
+                                      uint64_t batch, uint32_t in_flight, uint32_t flags, const madsim_limits_t* lim, madsim_campaign_t* out,
+                                      madsim_collect_t* col, madsim_stats_t* st, madsim_groups_t* grp) {
+    return plain_campaign(Contexts(c), FORM_ANY, w, cfg, Seeds::list(seeds, n), batch, in_flight, flags, lim, out, col, st, grp);
+}
+int madsim_hip_run_seeds_campaign_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_workload_t* w, const madsim_config_t* cfg,
+                                        const uint64_t* seeds, uint64_t n, uint64_t batch, uint32_t in_flight, uint32_t flags,
+                                        const madsim_limits_t* lim, madsim_campaign_t* out, madsim_collect_t* col, madsim_stats_t* st,
+                                        madsim_groups_t* grp) {
+    return plain_campaign(Contexts(ctxs, n_ctx, "run_seeds_campaign_multi"), FORM_ANY, w, cfg, Seeds::list(seeds, n), batch, in_flight, flags, lim, out,
+                          col, st, grp);
+}
+
+int madsim_hip_ctx_run_campaign_diff(madsim_hip_ctx_t* c, const madsim_workload_t* wA, const madsim_config_t* cfgA, const madsim_limits_t* limA,
+                                     const madsim_workload_t* wB, const madsim_config_t* cfgB, const madsim_limits_t* limB, uint64_t seed0,
+                                     uint64_t total, uint64_t batch, uint32_t in_flight, uint32_t flags, madsim_campaign_t* outA,
+                                     madsim_campaign_t* outB, madsim_diff_t* diff) {
+    return pair_campaign(Contexts(c), false, wA, cfgA, limA, wB, cfgB, limB, Seeds::range(seed0, total), batch, in_flight, flags, outA, outB, diff, nullptr);
+}
+int madsim_hip_run_campaign_diff_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_workload_t* wA, const madsim_config_t* cfgA,
+                                       const madsim_limits_t* limA, const madsim_workload_t* wB, const madsim_config_t* cfgB,
+                                       const madsim_limits_t* limB, uint64_t seed0, uint64_t total, uint64_t batch, uint32_t in_flight,
+                                       uint32_t flags, madsim_campaign_t* outA, madsim_campaign_t* outB, madsim_diff_t* diff) {
+    return pair_campaign(Contexts(ctxs, n_ctx, "run_campaign_diff_multi"), false, wA, cfgA, limA, wB, cfgB, limB, Seeds::range(seed0, total), batch,
+                         in_flight, flags, outA, outB, diff, nullptr);
+}
+
+int madsim_hip_ctx_run_seeds_campaign_diff(madsim_hip_ctx_t* c, const madsim_workload_t* wA, const madsim_config_t* cfgA, const madsim_limits_t* limA,
+                                           const madsim_workload_t* wB, const madsim_config_t* cfgB, const madsim_limits_t* limB,
+                                           const uint64_t* seeds, uint64_t n, uint64_t batch, uint32_t in_flight, uint32_t flags,
+                                           madsim_campaign_t* outA, madsim_campaign_t* outB, madsim_diff_t* diff) {
+    return pair_campaign(Contexts(c), false, wA, cfgA, limA, wB, cfgB, limB, Seeds::list(seeds, n), batch, in_flight, flags, outA, outB, diff, nullptr);
+}
+int madsim_hip_run_seeds_campaign_diff_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_workload_t* wA, const madsim_config_t* cfgA,
+                                             const madsim_limits_t* limA, const madsim_workload_t* wB, const madsim_config_t* cfgB,
+                                             const madsim_limits_t* limB, const uint64_t* seeds, uint64_t n, uint64_t batch, uint32_t in_flight,
+                                             uint32_t flags, madsim_campaign_t* outA, madsim_campaign_t* outB, madsim_diff_t* diff) {
+    return pair_campaign(Contexts(ctxs, n_ctx, "run_seeds_campaign_diff_multi"), false, wA, cfgA, limA, wB, cfgB, limB, Seeds::list(seeds, n), batch,
+                         in_flight, flags, outA, outB, diff, nullptr);
+}
+
+int madsim_hip_ctx_run_paired_campaign(madsim_hip_ctx_t* c, const madsim_workload_t* wA, const madsim_config_t* cfgA, const madsim_limits_t* limA,
+                                       const madsim_workload_t* wB, const madsim_config_t* cfgB, const madsim_limits_t* limB, uint64_t seed0,
+                                       uint64_t total, uint64_t batch, uint32_t in_flight, uint32_t flags, madsim_campaign_t* outA,
+                                       madsim_campaign_t* outB, madsim_diff_t* diff, madsim_paired_t* pr) {
+    return pair_campaign(Contexts(c), true, wA, cfgA, limA, wB, cfgB, limB, Seeds::range(seed0, total), batch, in_flight, flags, outA, outB, diff, pr);
+}
+int madsim_hip_run_paired_campaign_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_workload_t* wA, const madsim_config_t* cfgA,
+                                         const madsim_limits_t* limA, const madsim_workload_t* wB, const madsim_config_t* cfgB,
+                                         const madsim_limits_t* limB, uint64_t seed0, uint64_t total, uint64_t batch, uint32_t in_flight,
+                                         uint32_t flags, madsim_campaign_t* outA, madsim_campaign_t* outB, madsim_diff_t* diff, madsim_paired_t* pr) {
+    return pair_campaign(Contexts(ctxs, n_ctx, "run_paired_campaign_multi"), true, wA, cfgA, limA, wB, cfgB, limB, Seeds::range(seed0, total), batch,
+                         in_flight, flags, outA, outB, diff, pr);
+}
+
+int madsim_hip_ctx_run_seeds_campaign_paired(madsim_hip_ctx_t* c, const madsim_workload_t* wA, const madsim_config_t* cfgA, const madsim_limits_t* limA,
+                                             const madsim_workload_t* wB, const madsim_config_t* cfgB, const madsim_limits_t* limB,
+                                             const uint64_t* seeds, uint64_t n, uint64_t batch, uint32_t in_flight, uint32_t flags,
+                                             madsim_campaign_t* outA, madsim_campaign_t* outB, madsim_diff_t* diff, madsim_paired_t* pr) {
+    return pair_campaign(Contexts(c), true, wA, cfgA, limA, wB, cfgB, limB, Seeds::list(seeds, n), batch, in_flight, flags, outA, outB, diff, pr);
+}
+int madsim_hip_run_seeds_campaign_paired_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_workload_t* wA, const madsim_config_t* cfgA,
+                                               const madsim_limits_t* limA, const madsim_workload_t* wB, const madsim_config_t* cfgB,
+                                               const madsim_limits_t* limB, const uint64_t* seeds, uint64_t n, uint64_t batch, uint32_t in_flight,
+                                               uint32_t flags, madsim_campaign_t* outA, madsim_campaign_t* outB, madsim_diff_t* diff,
+                                               madsim_paired_t* pr) {
+    return pair_campaign(Contexts(ctxs, n_ctx, "run_seeds_campaign_paired_multi"), true, wA, cfgA, limA, wB, cfgB, limB, Seeds::list(seeds, n), batch,
+                         in_flight, flags, outA, outB, diff, pr);
+}
+
+int madsim_hip_ctx_run_sweep_campaign(madsim_hip_ctx_t* c, const madsim_sweep_variant_t* variants, uint32_t n_variants, uint64_t seed0, uint64_t total,
+                                      const uint64_t* seeds, uint64_t batch, uint32_t in_flight, uint32_t flags, madsim_sweep_t* sweep) {
+    return sweep_campaign(Contexts(c), variants, n_variants, seed0, total, seeds, batch, in_flight, flags, sweep);
+}
 int madsim_hip_run_sweep_campaign_multi(madsim_hip_ctx_t* const* ctxs, int n_ctx, const madsim_sweep_variant_t* variants, uint32_t n_variants,
                                         uint64_t seed0, uint64_t total, const uint64_t* seeds, uint64_t batch, uint32_t in_flight, uint32_t flags,
                                         madsim_sweep_t* sweep) {
-    std::vector<madsim_sweep_variant_t> var;
-    if (int rc = check_sweep_args(variants, n_variants, seed0, total, seeds, in_flight, flags, sweep, var)) return rc;
-    std::vector<std::unique_lock<std::mutex>> locks;
-    if (int rc = lock_contexts(ctxs, n_ctx, "run_sweep_campaign_multi", locks)) return rc;
-    return run_variants_impl(ctxs, n_ctx, var.data(), n_variants, seed0, total, batch, in_flight, flags, total ? seeds : nullptr, SweepForm{sweep, n_variants});
+    return sweep_campaign(Contexts(ctxs, n_ctx, "run_sweep_campaign_multi"), variants, n_variants, seed0, total, seeds, batch, in_flight, flags, sweep);
 }
 
 // ---- v1 entry points: wrappers on the process-default context ------------------------------------------------------------

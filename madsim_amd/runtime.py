@@ -12,6 +12,8 @@ There is no CPU fallback: if the library is missing or no GPU is visible this
 module raises, loudly.
 """
 import ctypes as C
+import functools
+import inspect
 import math
 from fractions import Fraction
 import operator
@@ -52,6 +54,86 @@ class SimulationFailure(AssertionError):
 _lib = None
 
 
+def _declare(L):
+    """The ctypes prototypes of the library's entry points.  An operation's prototype is written once, as madsim_hip_<name> takes it: the
+    context form madsim_hip_ctx_<name> takes a context in front of it and — for the campaign operations — madsim_hip_<name>_multi the
+    contexts and their number."""
+    W, CFG, LIM, REP = C.POINTER(A.Workload), C.POINTER(A.Config), C.POINTER(A.Limits), C.POINTER(A.Campaign)
+    u32, u64, u64p, vp, ctxp = C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p
+    batch = [W, CFG, u64, u64, LIM, vp]                          # workload, config, seed0, count, limits, the results
+    side = [W, CFG, LIM]
+    how = [u64, u32, u32]                                        # batch, in_flight, flags
+    parts = [C.POINTER(A.Collect), C.POINTER(A.Stats), C.POINTER(A.Groups)]
+    campaign = [W, CFG, u64, u64] + how + [LIM, REP]             # ... over the range (seed0, total)
+    diff = side + side + [u64, u64] + how + [REP, REP, C.POINTER(A.Diff)]
+    # the list campaigns: (seeds, n) where the range forms take (seed0, total); collect, stats and groups in one entry point, each optional
+    seeds_diff = side + side + [u64p, u64] + how + [REP, REP, C.POINTER(A.Diff)]
+    with_context = {                                             # operation -> its prototype on the default context
+        "run_batch": batch + [C.POINTER(A.Summary)],
+        "run_batch_auto": batch + [C.POINTER(A.Summary), C.c_int],
+        "run_batch_device": batch + [vp, C.POINTER(A.Summary)],
+        "run_batch_async": batch + [vp, vp, C.c_int],
+        "timing_ms": [C.c_int, C.POINTER(C.c_double)],
+        "campaign_resolved": [C.POINTER(A.Resolve)],
+        "trace_seed": [W, CFG, u64, LIM, vp, u64, C.POINTER(A.Result)],
+        "observe_seed": [W, CFG, u64, LIM, vp, u64, C.POINTER(A.Result)],
+        "trace_seeds": [W, CFG, u64p, u64, LIM, vp, u64, vp, u64, vp, vp, vp],
+        # task post-mortems: trace_seeds' conventions with one buffer, the task rows; timelines: the time rows beside the observation rows
+        "task_states": [W, CFG, u64p, u64, LIM, vp, u64, vp, vp],
+        "timeline_seeds": [W, CFG, u64p, u64, LIM, vp, vp, u64, vp, vp],
+        "diverge_seeds": side + side + [u64p, u64, u64, u64, u32, vp, vp],
+    }
+    # the observation reports: (seed0, total) or (seeds, n), then chunk, limits and the form's report struct
+    for form, report in (("census", A.Census), ("stall_census", A.StallCensus), ("probe_sets", A.ProbeSets), ("probe_order", A.ProbeOrder),
+                         ("probe_spans", A.ProbeSpans)):
+        with_context[form + "_range"] = [W, CFG, u64, u64, u64, LIM, C.POINTER(report)]
+        with_context[form + "_seeds"] = [W, CFG, u64p, u64, u64, LIM, C.POINTER(report)]
+    with_multi = {                                               # the campaign operations: a context form and a _multi form
+        "run_campaign": campaign,
+        "run_campaign_collect": campaign + parts[:1],
+        "run_campaign_stats": campaign + parts[:2],
+        "run_campaign_groups": campaign + parts,
+        "run_seeds_campaign": [W, CFG, u64p, u64] + how + [LIM, REP] + parts,
+        "run_campaign_diff": diff,
+        "run_seeds_campaign_diff": seeds_diff,
+        # the paired campaigns: the differential forms' arguments, the diff report optional, and a trailing madsim_paired_t
+        # (the range forms are spelled run_paired_campaign, as the sweep forms are run_sweep_campaign)
+        "run_paired_campaign": diff + [C.POINTER(A.Paired)],
+        "run_seeds_campaign_paired": seeds_diff + [C.POINTER(A.Paired)],
+        # the sweep campaigns: one signature for the range (seeds NULL) and the list (seed0 0)
+        "run_sweep_campaign": [C.POINTER(A.SweepVariant), u32, u64, u64, u64p] + how + [C.POINTER(A.Sweep)],
+    }
+    for name, base in list(with_context.items()) + list(with_multi.items()):
+        getattr(L, "madsim_hip_" + name).argtypes = base
+        getattr(L, "madsim_hip_ctx_" + name).argtypes = [ctxp] + base
+        if name in with_multi:
+            getattr(L, f"madsim_hip_{name}_multi").argtypes = [C.POINTER(ctxp), C.c_int] + base
+    L.madsim_hip_run_batch_multi.argtypes = [C.POINTER(ctxp), C.c_int] + with_context["run_batch_auto"]      # (the last argument: max_rounds)
+    # everything else: no context in front
+    without_context = {
+        "madsim_hip_prefer_hw_queues": [C.c_int], "madsim_hip_strerror": [C.c_int], "madsim_hip_init": [C.c_int],
+        "madsim_hip_geometry": [W, LIM, C.POINTER(A.Geometry)],
+        "madsim_workload_pingpong": [u32, u32, C.POINTER(A.Node), C.POINTER(A.Prog), C.POINTER(A.Sock), C.POINTER(A.Insn), u32, W],
+        "madsim_hip_ctx_create": [C.c_int, C.POINTER(ctxp)], "madsim_hip_ctx_destroy": [ctxp], "madsim_hip_ctx_device": [ctxp],
+        "madsim_hip_stat_bucket": [u64], "madsim_hip_stat_bucket_floor": [u32],
+        "madsim_hip_grow_limits": [W, LIM, u32, LIM],
+        "madsim_hip_stall_shape": [vp, u64], "madsim_hip_span_merge": [vp, vp], "madsim_k_span_init": [vp],
+        # the host folds of the observation reports (what their merge() calls)
+        "madsim_k_fold_census": [C.POINTER(A.Census), vp, vp, u64], "madsim_k_fold_probe_sets": [C.POINTER(A.ProbeSets), vp, vp, u64],
+        "madsim_k_fold_probe_order": [C.POINTER(A.ProbeOrder), vp, vp, u64], "madsim_k_fold_probe_spans": [C.POINTER(A.ProbeSpans), vp, vp, u64],
+        "madsim_k_fold_stall_census": [C.POINTER(A.StallCensus), vp, vp, u64, vp, u64],
+    }
+    for symbol, argtypes in without_context.items():
+        getattr(L, symbol).argtypes = argtypes
+    returns = {"madsim_hip_version": u32, "madsim_hip_strerror": C.c_char_p, "madsim_hip_last_error": C.c_char_p, "madsim_hip_default_ctx": ctxp,
+               "madsim_hip_stat_bucket": u32, "madsim_hip_stat_bucket_floor": u64, "madsim_hip_stall_shape": u64, "madsim_k_span_init": None,
+               "madsim_hip_span_merge": None}
+    for name in ("trace_seed", "observe_seed"):                  # (a length, or a negative error code)
+        returns["madsim_hip_" + name] = returns["madsim_hip_ctx_" + name] = C.c_int64
+    for symbol, restype in returns.items():
+        getattr(L, symbol).restype = restype
+
+
 def lib():
     """Load the product library. Raises if it has not been built (run __graft_entry__.build())."""
     global _lib
@@ -73,156 +155,7 @@ def lib():
         # HIP — unless the application set the variable itself or initialised HIP earlier (import torch first, then its setting stands).
         os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
         L = C.CDLL(LIB_PATH)
-        L.madsim_hip_version.restype = C.c_uint32
-        L.madsim_hip_prefer_hw_queues.argtypes = [C.c_int]
-        L.madsim_hip_strerror.restype = C.c_char_p
-        L.madsim_hip_strerror.argtypes = [C.c_int]
-        L.madsim_hip_last_error.restype = C.c_char_p
-        L.madsim_hip_init.argtypes = [C.c_int]
-        L.madsim_hip_run_batch.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), C.c_uint64, C.c_uint64,
-                                           C.POINTER(A.Limits), C.c_void_p, C.POINTER(A.Summary)]
-        L.madsim_hip_run_batch_device.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), C.c_uint64,
-                                                  C.c_uint64, C.POINTER(A.Limits), C.c_void_p, C.c_void_p,
-                                                  C.POINTER(A.Summary)]
-        L.madsim_hip_run_batch_async.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), C.c_uint64, C.c_uint64,
-                                                 C.POINTER(A.Limits), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-        L.madsim_hip_timing_ms.argtypes = [C.c_int, C.POINTER(C.c_double)]
-        L.madsim_hip_trace_seed.restype = C.c_int64
-        L.madsim_hip_trace_seed.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), C.c_uint64,
-                                            C.POINTER(A.Limits), C.c_void_p, C.c_uint64, C.POINTER(A.Result)]
-        L.madsim_hip_run_batch_auto.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), C.c_uint64, C.c_uint64,
-                                                C.POINTER(A.Limits), C.c_void_p, C.POINTER(A.Summary), C.c_int]
-        L.madsim_hip_geometry.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Limits), C.POINTER(A.Geometry)]
-        L.madsim_workload_pingpong.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(A.Node), C.POINTER(A.Prog),
-                                               C.POINTER(A.Sock), C.POINTER(A.Insn), C.c_uint32,
-                                               C.POINTER(A.Workload)]
-        ctxp = C.c_void_p
-        L.madsim_hip_ctx_create.argtypes = [C.c_int, C.POINTER(ctxp)]
-        L.madsim_hip_ctx_destroy.argtypes = [ctxp]
-        L.madsim_hip_ctx_device.argtypes = [ctxp]
-        L.madsim_hip_default_ctx.restype = ctxp
-        L.madsim_hip_ctx_run_batch.argtypes = [ctxp] + L.madsim_hip_run_batch.argtypes
-        L.madsim_hip_ctx_run_batch_auto.argtypes = [ctxp] + L.madsim_hip_run_batch_auto.argtypes
-        L.madsim_hip_ctx_run_batch_device.argtypes = [ctxp] + L.madsim_hip_run_batch_device.argtypes
-        L.madsim_hip_ctx_run_batch_async.argtypes = [ctxp] + L.madsim_hip_run_batch_async.argtypes
-        L.madsim_hip_ctx_timing_ms.argtypes = [ctxp] + L.madsim_hip_timing_ms.argtypes
-        L.madsim_hip_ctx_trace_seed.restype = C.c_int64
-        L.madsim_hip_ctx_trace_seed.argtypes = [ctxp] + L.madsim_hip_trace_seed.argtypes
-        L.madsim_hip_run_batch_multi.argtypes = [C.POINTER(ctxp), C.c_int, C.POINTER(A.Workload), C.POINTER(A.Config),
-                                                 C.c_uint64, C.c_uint64, C.POINTER(A.Limits), C.c_void_p,
-                                                 C.POINTER(A.Summary), C.c_int]
-        L.madsim_hip_run_campaign.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), C.c_uint64, C.c_uint64, C.c_uint64,
-                                              C.c_uint32, C.c_uint32, C.POINTER(A.Limits), C.POINTER(A.Campaign)]
-        L.madsim_hip_ctx_run_campaign.argtypes = [ctxp] + L.madsim_hip_run_campaign.argtypes
-        L.madsim_hip_run_campaign_multi.argtypes = [C.POINTER(ctxp), C.c_int] + L.madsim_hip_run_campaign.argtypes
-        L.madsim_hip_run_campaign_collect.argtypes = L.madsim_hip_run_campaign.argtypes + [C.POINTER(A.Collect)]
-        L.madsim_hip_ctx_run_campaign_collect.argtypes = [ctxp] + L.madsim_hip_run_campaign_collect.argtypes
-        L.madsim_hip_run_campaign_collect_multi.argtypes = [C.POINTER(ctxp), C.c_int] + L.madsim_hip_run_campaign_collect.argtypes
-        L.madsim_hip_stat_bucket.restype = C.c_uint32
-        L.madsim_hip_stat_bucket.argtypes = [C.c_uint64]
-        L.madsim_hip_stat_bucket_floor.restype = C.c_uint64
-        L.madsim_hip_stat_bucket_floor.argtypes = [C.c_uint32]
-        L.madsim_hip_run_campaign_stats.argtypes = L.madsim_hip_run_campaign_collect.argtypes + [C.POINTER(A.Stats)]
-        L.madsim_hip_ctx_run_campaign_stats.argtypes = [ctxp] + L.madsim_hip_run_campaign_stats.argtypes
-        L.madsim_hip_run_campaign_stats_multi.argtypes = [C.POINTER(ctxp), C.c_int] + L.madsim_hip_run_campaign_stats.argtypes
-        L.madsim_hip_run_campaign_groups.argtypes = L.madsim_hip_run_campaign_stats.argtypes + [C.POINTER(A.Groups)]
-        L.madsim_hip_ctx_run_campaign_groups.argtypes = [ctxp] + L.madsim_hip_run_campaign_groups.argtypes
-        L.madsim_hip_run_campaign_groups_multi.argtypes = [C.POINTER(ctxp), C.c_int] + L.madsim_hip_run_campaign_groups.argtypes
-        side = [C.POINTER(A.Workload), C.POINTER(A.Config), C.POINTER(A.Limits)]
-        L.madsim_hip_run_campaign_diff.argtypes = side + side + [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(A.Campaign),
-                                                                 C.POINTER(A.Campaign), C.POINTER(A.Diff)]
-        L.madsim_hip_ctx_run_campaign_diff.argtypes = [ctxp] + L.madsim_hip_run_campaign_diff.argtypes
-        L.madsim_hip_run_campaign_diff_multi.argtypes = [C.POINTER(ctxp), C.c_int] + L.madsim_hip_run_campaign_diff.argtypes
-        L.madsim_hip_campaign_resolved.argtypes = [C.POINTER(A.Resolve)]
-        L.madsim_hip_ctx_campaign_resolved.argtypes = [ctxp, C.POINTER(A.Resolve)]
-        L.madsim_hip_grow_limits.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Limits), C.c_uint32, C.POINTER(A.Limits)]
-        u64p = C.POINTER(C.c_uint64)
-        L.madsim_hip_trace_seeds.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), u64p, C.c_uint64, C.POINTER(A.Limits), C.c_void_p,
-                                             C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.madsim_hip_ctx_trace_seeds.argtypes = [ctxp] + L.madsim_hip_trace_seeds.argtypes
-        # task post-mortems: trace_seeds' conventions with one buffer, the task rows, and the host twin of the shape word
-        L.madsim_hip_task_states.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), u64p, C.c_uint64, C.POINTER(A.Limits), C.c_void_p,
-                                             C.c_uint64, C.c_void_p, C.c_void_p]
-        L.madsim_hip_ctx_task_states.argtypes = [ctxp] + L.madsim_hip_task_states.argtypes
-        # timelines: trace_seeds' conventions, the time rows beside the observation rows
-        L.madsim_hip_timeline_seeds.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), u64p, C.c_uint64, C.POINTER(A.Limits), C.c_void_p,
-                                                C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-        L.madsim_hip_ctx_timeline_seeds.argtypes = [ctxp] + L.madsim_hip_timeline_seeds.argtypes
-        L.madsim_hip_stall_shape.restype = C.c_uint64
-        L.madsim_hip_stall_shape.argtypes = [C.c_void_p, C.c_uint64]
-        # the stall-site census: the census's signatures with a madsim_stall_census_t
-        L.madsim_hip_stall_census_range.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(A.Limits),
-                                                    C.POINTER(A.StallCensus)]
-        L.madsim_hip_stall_census_seeds.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), u64p, C.c_uint64, C.c_uint64, C.POINTER(A.Limits),
-                                                    C.POINTER(A.StallCensus)]
-        L.madsim_hip_ctx_stall_census_range.argtypes = [ctxp] + L.madsim_hip_stall_census_range.argtypes
-        L.madsim_hip_ctx_stall_census_seeds.argtypes = [ctxp] + L.madsim_hip_stall_census_seeds.argtypes
-        L.madsim_k_fold_stall_census.argtypes = [C.POINTER(A.StallCensus), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]
-        # the list campaigns: (seeds, n) where the range forms take (seed0, total); collect, stats and groups in one entry point, each optional
-        L.madsim_hip_run_seeds_campaign.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), u64p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32,
-                                                    C.POINTER(A.Limits), C.POINTER(A.Campaign), C.POINTER(A.Collect), C.POINTER(A.Stats),
-                                                    C.POINTER(A.Groups)]
-        L.madsim_hip_ctx_run_seeds_campaign.argtypes = [ctxp] + L.madsim_hip_run_seeds_campaign.argtypes
-        L.madsim_hip_run_seeds_campaign_multi.argtypes = [C.POINTER(ctxp), C.c_int] + L.madsim_hip_run_seeds_campaign.argtypes
-        L.madsim_hip_run_seeds_campaign_diff.argtypes = side + side + [u64p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(A.Campaign),
-                                                                       C.POINTER(A.Campaign), C.POINTER(A.Diff)]
-        L.madsim_hip_ctx_run_seeds_campaign_diff.argtypes = [ctxp] + L.madsim_hip_run_seeds_campaign_diff.argtypes
-        L.madsim_hip_run_seeds_campaign_diff_multi.argtypes = [C.POINTER(ctxp), C.c_int] + L.madsim_hip_run_seeds_campaign_diff.argtypes
-        # the paired campaigns: the differential forms' arguments, the diff report optional, and a trailing madsim_paired_t
-        # (the range forms are spelled run_paired_campaign, as the sweep forms are run_sweep_campaign)
-        for twin, form in (("run_campaign_diff", "run_paired_campaign"), ("run_seeds_campaign_diff", "run_seeds_campaign_paired")):
-            base = getattr(L, f"madsim_hip_{twin}").argtypes + [C.POINTER(A.Paired)]
-            getattr(L, f"madsim_hip_{form}").argtypes = base
-            getattr(L, f"madsim_hip_ctx_{form}").argtypes = [ctxp] + base
-            getattr(L, f"madsim_hip_{form}_multi").argtypes = [C.POINTER(ctxp), C.c_int] + base
-        L.madsim_hip_diverge_seeds.argtypes = side + side + [u64p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
-        L.madsim_hip_ctx_diverge_seeds.argtypes = [ctxp] + L.madsim_hip_diverge_seeds.argtypes
-        # the observation census: (seed0, total) or (seeds, n), then chunk, limits and the madsim_census_t
-        L.madsim_hip_census_range.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(A.Limits),
-                                              C.POINTER(A.Census)]
-        L.madsim_hip_census_seeds.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), u64p, C.c_uint64, C.c_uint64, C.POINTER(A.Limits),
-                                              C.POINTER(A.Census)]
-        L.madsim_hip_ctx_census_range.argtypes = [ctxp] + L.madsim_hip_census_range.argtypes
-        L.madsim_hip_ctx_census_seeds.argtypes = [ctxp] + L.madsim_hip_census_seeds.argtypes
-        L.madsim_k_fold_census.argtypes = [C.POINTER(A.Census), C.c_void_p, C.c_void_p, C.c_uint64]
-        # the probe-set census: the census's signatures with a madsim_probe_sets_t
-        L.madsim_hip_probe_sets_range.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(A.Limits),
-                                                  C.POINTER(A.ProbeSets)]
-        L.madsim_hip_probe_sets_seeds.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), u64p, C.c_uint64, C.c_uint64, C.POINTER(A.Limits),
-                                                  C.POINTER(A.ProbeSets)]
-        L.madsim_hip_ctx_probe_sets_range.argtypes = [ctxp] + L.madsim_hip_probe_sets_range.argtypes
-        L.madsim_hip_ctx_probe_sets_seeds.argtypes = [ctxp] + L.madsim_hip_probe_sets_seeds.argtypes
-        L.madsim_k_fold_probe_sets.argtypes = [C.POINTER(A.ProbeSets), C.c_void_p, C.c_void_p, C.c_uint64]
-        # the probe-order census: the census's signatures with a madsim_probe_order_t
-        L.madsim_hip_probe_order_range.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(A.Limits),
-                                                   C.POINTER(A.ProbeOrder)]
-        L.madsim_hip_probe_order_seeds.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), u64p, C.c_uint64, C.c_uint64, C.POINTER(A.Limits),
-                                                   C.POINTER(A.ProbeOrder)]
-        L.madsim_hip_ctx_probe_order_range.argtypes = [ctxp] + L.madsim_hip_probe_order_range.argtypes
-        L.madsim_hip_ctx_probe_order_seeds.argtypes = [ctxp] + L.madsim_hip_probe_order_seeds.argtypes
-        L.madsim_k_fold_probe_order.argtypes = [C.POINTER(A.ProbeOrder), C.c_void_p, C.c_void_p, C.c_uint64]
-        # probe spans: the census's signatures with a madsim_probe_spans_t
-        L.madsim_hip_probe_spans_range.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(A.Limits),
-                                                   C.POINTER(A.ProbeSpans)]
-        L.madsim_hip_probe_spans_seeds.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), u64p, C.c_uint64, C.c_uint64, C.POINTER(A.Limits),
-                                                   C.POINTER(A.ProbeSpans)]
-        L.madsim_hip_ctx_probe_spans_range.argtypes = [ctxp] + L.madsim_hip_probe_spans_range.argtypes
-        L.madsim_hip_ctx_probe_spans_seeds.argtypes = [ctxp] + L.madsim_hip_probe_spans_seeds.argtypes
-        L.madsim_k_fold_probe_spans.argtypes = [C.POINTER(A.ProbeSpans), C.c_void_p, C.c_void_p, C.c_uint64]
-        L.madsim_k_span_init.argtypes = [C.c_void_p]
-        L.madsim_k_span_init.restype = None
-        L.madsim_hip_span_merge.argtypes = [C.c_void_p, C.c_void_p]
-        L.madsim_hip_span_merge.restype = None
-        # the sweep campaigns: one signature for the range (seeds NULL) and the list (seed0 0)
-        L.madsim_hip_run_sweep_campaign.argtypes = [C.POINTER(A.SweepVariant), C.c_uint32, C.c_uint64, C.c_uint64, u64p, C.c_uint64, C.c_uint32,
-                                                    C.c_uint32, C.POINTER(A.Sweep)]
-        L.madsim_hip_ctx_run_sweep_campaign.argtypes = [ctxp] + L.madsim_hip_run_sweep_campaign.argtypes
-        L.madsim_hip_run_sweep_campaign_multi.argtypes = [C.POINTER(ctxp), C.c_int] + L.madsim_hip_run_sweep_campaign.argtypes
-        L.madsim_hip_observe_seed.restype = C.c_int64
-        L.madsim_hip_observe_seed.argtypes = [C.POINTER(A.Workload), C.POINTER(A.Config), C.c_uint64, C.POINTER(A.Limits), C.c_void_p, C.c_uint64,
-                                              C.POINTER(A.Result)]
-        L.madsim_hip_ctx_observe_seed.restype = C.c_int64
-        L.madsim_hip_ctx_observe_seed.argtypes = [ctxp] + L.madsim_hip_observe_seed.argtypes
+        _declare(L)
         if L.madsim_hip_version() != A.ABI_VERSION:
             raise MadsimHipError("libmadsim_hip.so ABI version mismatch")
         # build identity: MADSIM_HIP_LIB may name an A/B build of THIS library (tools/build_variant.sh), nothing else — an
@@ -258,10 +191,92 @@ def init(device=0):
 
 
 def shutdown():
+    """Destroy the process-default context (madsim_hip_shutdown); the next module-level call binds GPU 0 again."""
     global _inited_device
     if _lib is not None:
         _lib.madsim_hip_shutdown()
     _inited_device = None
+
+
+# ---- one definition per operation, three ways to reach the library --------------------------------------------------------------------
+# A campaign or report operation is defined once, as `_on_<name>(on, ...)`: its parameter list, its defaults and its docstring.  `on` is the
+# target, which says how the call reaches the library: entry(name) is the C entry point of the operation `name` with the target's leading
+# arguments bound; ready() is where the process-default context gets initialised (nothing for the other two); trace_seeds is what
+# `observe=` replays on (None over several contexts: those spellings have no observe=) and census what a vocabulary is taken with.
+
+class _OnDefault:
+    """The process-default context: madsim_hip_<name>, bound to GPU 0 by the first call that needs it."""
+
+    def ready(self):
+        if _inited_device is None:
+            init(0)
+
+    def entry(self, name):
+        return getattr(lib(), "madsim_hip_" + name)
+
+    trace_seeds = property(lambda self: _default_tracer)
+    census = property(lambda self: census)
+
+
+class _OnContext:
+    """A Context the caller holds: madsim_hip_ctx_<name> with its handle in front."""
+
+    def __init__(self, ctx):
+        self.ctx, self.trace_seeds, self.census = ctx, ctx.trace_seeds, ctx.census
+
+    def ready(self):
+        pass
+
+    def entry(self, name):
+        return functools.partial(getattr(lib(), "madsim_hip_ctx_" + name), self.ctx._h)
+
+
+class _OnContexts:
+    """Several contexts: madsim_hip_<name>_multi with the handle array and its length in front."""
+    trace_seeds = census = None
+
+    def __init__(self, contexts):
+        self.contexts = contexts
+
+    def ready(self):
+        pass
+
+    def entry(self, name):
+        handles = (C.c_void_p * len(self.contexts))(*[c._h for c in self.contexts])
+        return functools.partial(getattr(lib(), f"madsim_hip_{name}_multi"), handles, len(self.contexts))
+
+
+def _operation(*entries):
+    """Marks `_on_<name>(on, ...)` as the one definition of the operation <name>; `entries`: the C operations it calls, for the docstrings."""
+    def mark(op):
+        op.public_name, op.entries = op.__name__[len("_on_"):], entries
+        return op
+    return mark
+
+
+def _spelled(op, target=_OnDefault, lead=None, without=()):
+    """One public spelling of the operation `op`: the module-level function (no `lead`), the Context method (lead="self") or the _multi
+    function (lead="contexts"), which makes its target from the leading argument.  Its signature is the definition's without `on`, behind
+    `lead`, and without the parameters this target cannot serve (`without`); the derived spellings get a one-line docstring."""
+    own = [p for p in list(inspect.signature(op).parameters.values())[1:] if p.name not in without]
+    front = [inspect.Parameter(lead, inspect.Parameter.POSITIONAL_OR_KEYWORD)] if lead else []
+    sig = inspect.Signature(front + own)
+
+    def spelling(*args, **kwargs):
+        given = sig.bind(*args, **kwargs).arguments                                # (TypeError for what the signature does not take)
+        return op(target(given.pop(lead)) if lead else target(), **given)
+
+    spelling.__signature__ = sig
+    spelling.__name__ = op.public_name + ("_multi" if lead == "contexts" else "")
+    spelling.__qualname__ = ("Context." if lead == "self" else "") + spelling.__name__
+    if lead == "self":
+        spelling.__doc__ = f"runtime.{op.public_name} on this context ({' / '.join('madsim_hip_ctx_' + e for e in op.entries)})."
+    elif lead:
+        spelling.__doc__ = (f"{' / '.join(f'madsim_hip_{e}_multi' for e in op.entries)}: runtime.{op.public_name} over several contexts (batch k "
+                            "on context k % n); the reports are the ones a single context gives.")
+    else:
+        spelling.__doc__ = op.__doc__
+    return spelling
 
 
 def run_batch(workload, seed0, count, config=None, limits=None):
@@ -415,14 +430,18 @@ def _trace_seeds(call, workload, seeds, config, limits, obs_cap, log_cap, resolv
     return traces
 
 
-def trace_seeds(workload, seeds, config=None, limits=None, obs_cap=256, log_cap=0, resolve=True):
+@_operation("trace_seeds")
+def _on_trace_seeds(on, workload, seeds, config=None, limits=None, obs_cap=256, log_cap=0, resolve=True):
     """madsim_hip_trace_seeds: replay `seeds` (any order, duplicates allowed) on the trace build, the whole list in one launch; returns one
     SeedTrace per seed, in the order given.  resolve=True | rounds: the seeds a call leaves with a re-runnable runner verdict are replayed as
     one further call under grown_limits(workload, limits, r), r = 1, 2, ... — the rounds of a resolving campaign; resolve=None / False: the
     one call under `limits`, runner verdicts as they come."""
-    if _inited_device is None:
-        init(0)
-    return _trace_seeds(lambda *a: lib().madsim_hip_trace_seeds(workload.ref(), *a), workload, seeds, config, limits, obs_cap, log_cap, resolve)
+    on.ready()
+    call = on.entry("trace_seeds")
+    return _trace_seeds(lambda *a: call(workload.ref(), *a), workload, seeds, config, limits, obs_cap, log_cap, resolve)
+
+
+trace_seeds = _spelled(_on_trace_seeds)
 
 
 class SeedTimeline:
@@ -487,13 +506,17 @@ def _timeline(call, workload, seeds, config, limits, obs_cap, resolve):
     return out
 
 
-def timeline(workload, seeds, config=None, limits=None, obs_cap=256, resolve=True):
+@_operation("timeline_seeds")
+def _on_timeline(on, workload, seeds, config=None, limits=None, obs_cap=256, resolve=True):
     """madsim_hip_timeline_seeds: replay `seeds` (any order, duplicates allowed) on the trace build, the whole list in one launch, and return
     one SeedTimeline per seed, in the order given: the values trace_seeds returns and, beside each, the virtual time at which it was traced.
     resolve= as trace_seeds has it."""
-    if _inited_device is None:
-        init(0)
-    return _timeline(lambda *a: lib().madsim_hip_timeline_seeds(workload.ref(), *a), workload, seeds, config, limits, obs_cap, resolve)
+    on.ready()
+    call = on.entry("timeline_seeds")
+    return _timeline(lambda *a: call(workload.ref(), *a), workload, seeds, config, limits, obs_cap, resolve)
+
+
+timeline = _spelled(_on_timeline)
 
 
 def task_word(state, prog, pc, cnt0=0, cnt1=0):
@@ -583,24 +606,24 @@ def _task_states(call, workload, seeds, config, limits, task_cap, resolve):
     return res, rows, lens
 
 
-def post_mortem(workload, seeds, task_cap=32, config=None, limits=None, resolve=True, lengths=False):
+@_operation("task_states")
+def _on_post_mortem(on, workload, seeds, task_cap=32, config=None, limits=None, resolve=True, lengths=False):
     """madsim_hip_task_states: where the tasks of `seeds` (any order, duplicates allowed) stand when their runs end, the whole list in one
     launch of the trace build.  Returns per seed (result, ndarray[uint64]): its A.Result and the records of the tasks still alive, in task
     slot order, at most `task_cap` of them (runtime.task_fields / describe decode a record) — with lengths=True (result, records, true
     count), the count being what task_cap may have cut.  A seed with a runner verdict has no records; resolve=True | rounds replays such
     seeds under grown_limits(workload, limits, r), as trace_seeds does; resolve=None / False: the one call."""
-    if _inited_device is None:
-        init(0)
-    return _post_mortem(lambda *a: lib().madsim_hip_task_states(workload.ref(), *a), workload, seeds, task_cap, config, limits, resolve, lengths)
-
-
-def _post_mortem(call, workload, seeds, task_cap, config, limits, resolve, lengths):
-    res, rows, lens = _task_states(call, workload, seeds, config, limits, task_cap, resolve)
+    on.ready()
+    call = on.entry("task_states")
+    res, rows, lens = _task_states(lambda *a: call(workload.ref(), *a), workload, seeds, config, limits, task_cap, resolve)
     out = []
     for i in range(len(res)):
         r, t = A.Result(*[int(x) for x in res[i]]), rows[i, :min(int(lens[i]), task_cap)].copy()
         out.append((r, t, int(lens[i])) if lengths else (r, t))
     return out
+
+
+post_mortem = _spelled(_on_post_mortem)
 
 
 class Divergence:
@@ -663,17 +686,20 @@ def _diverge_seeds(call, workload, seeds, other, config, other_config, limits, o
     return out
 
 
-def diverge_seeds(workload, seeds, other=None, config=None, other_config=None, limits=None, other_limits=None, log_cap=1 << 16, obs_cap=256,
-                  window=4, resolve=True):
+@_operation("diverge_seeds")
+def _on_diverge_seeds(on, workload, seeds, other=None, config=None, other_config=None, limits=None, other_limits=None, log_cap=1 << 16, obs_cap=256,
+                      window=4, resolve=True):
     """madsim_hip_diverge_seeds: where the runs of `seeds` under (workload, config, limits) and under (other, other_config, other_limits) — a
     None means side A's — first part, on the determinism log and on the observations, compared on the device: returns one Divergence per
     seed, in the order given.  No row is copied to the host.  resolve=True | rounds: seeds that come back incomparable with a re-runnable
     runner verdict on either side are replayed in one further call per round, each side under its own grown_limits(.., r), as trace_seeds
     does; resolve=None / False: the one call, runner verdicts as they come."""
-    if _inited_device is None:
-        init(0)
-    return _diverge_seeds(lib().madsim_hip_diverge_seeds, workload, seeds, other, config, other_config, limits, other_limits, log_cap, obs_cap,
-                          window, resolve)
+    on.ready()
+    return _diverge_seeds(on.entry("diverge_seeds"), workload, seeds, other, config, other_config, limits, other_limits, log_cap, obs_cap, window,
+                          resolve)
+
+
+diverge_seeds = _spelled(_on_diverge_seeds)
 
 
 class _ObsReport:
@@ -695,6 +721,13 @@ class _ObsReport:
             raise MadsimHipError(f"{type(self).__name__}.merge: {self._fold} failed")
         runner = np.sort(np.concatenate([np.asarray(self.runner_seeds, dtype=np.uint64), np.asarray(other.runner_seeds, dtype=np.uint64)]))
         return out[:getattr(rep, self._count)].copy(), runner
+
+
+def _range_and_seeds(on, form, workload):
+    """(call_range, call_seeds) of an observation report: madsim_hip_*<form>_range and _seeds on the target, the workload bound."""
+    on.ready()
+    over_range, over_seeds = on.entry(form + "_range"), on.entry(form + "_seeds")
+    return (lambda *a: over_range(workload.ref(), *a)), (lambda *a: over_seeds(workload.ref(), *a))
 
 
 def _settle(one, workload, lim0, rounds, seed0, total, seeds, cap, over_cap):
@@ -793,8 +826,9 @@ def _census(call_range, call_seeds, workload, seed0, total, seeds, include, obs_
                    f"census: more than max_values = {max_values} distinct observed values once the runner seeds are settled")
 
 
-def census(workload, seed0=0, total=0, seeds=None, include=(A.PASS, A.PANIC, A.DEADLOCK, A.TIME_LIMIT), obs_cap=256, max_values=4096, chunk=0,
-           config=None, limits=None, resolve=True):
+@_operation("census_range", "census_seeds")
+def _on_census(on, workload, seed0=0, total=0, seeds=None, include=(A.PASS, A.PANIC, A.DEADLOCK, A.TIME_LIMIT), obs_cap=256, max_values=4096, chunk=0,
+               config=None, limits=None, resolve=True):
     """madsim_hip_census_range / madsim_hip_census_seeds: which traced values the seeds [seed0, seed0 + total) — or the strictly ascending
     `seeds` (never sorted silently: pass numpy.unique(seeds)) — reach, by verdict, reduced on the device: returns a Census.  A seed is
     counted when its verdict is in `include`; the first `obs_cap` observations of a seed are visible; more than `max_values` distinct
@@ -802,11 +836,11 @@ def census(workload, seed0=0, total=0, seeds=None, include=(A.PASS, A.PANIC, A.D
     library's default — it never shows in the result.  resolve=True | rounds: the seeds a call leaves with a runner verdict are run again
     in one further list call per round under grown_limits(workload, limits, r) and merged in, as trace_seeds settles its seeds;
     resolve=None / False: the one call, runner seeds counted in n_runner and listed in runner_seeds."""
-    if _inited_device is None:
-        init(0)
-    L = lib()
-    return _census(lambda *a: L.madsim_hip_census_range(workload.ref(), *a), lambda *a: L.madsim_hip_census_seeds(workload.ref(), *a), workload,
-                   seed0, total, seeds, include, obs_cap, max_values, chunk, config, limits, resolve)
+    return _census(*_range_and_seeds(on, "census", workload), workload, seed0, total, seeds, include, obs_cap, max_values, chunk, config, limits,
+                   resolve)
+
+
+census = _spelled(_on_census)
 
 
 class StallCensus:
@@ -915,18 +949,19 @@ def _stall_census(call_range, call_seeds, workload, seed0, total, seeds, include
     return rep
 
 
-def stall_census(workload, seed0=0, total=0, seeds=None, include=(A.PANIC, A.DEADLOCK, A.TIME_LIMIT), task_cap=32, max_sites=4096, max_shapes=4096,
-                 chunk=0, config=None, limits=None, resolve=True):
+@_operation("stall_census_range", "stall_census_seeds")
+def _on_stall_census(on, workload, seed0=0, total=0, seeds=None, include=(A.PANIC, A.DEADLOCK, A.TIME_LIMIT), task_cap=32, max_sites=4096,
+                     max_shapes=4096, chunk=0, config=None, limits=None, resolve=True):
     """madsim_hip_stall_census_range / madsim_hip_stall_census_seeds: where the tasks of the seeds [seed0, seed0 + total) — or of the strictly
     ascending `seeds` — stand when their runs end, by verdict, reduced on the device: returns a StallCensus.  A seed is counted when its
     verdict is in `include`; the first `task_cap` live tasks of a seed (slot order) are visible; more than `max_sites` distinct sites or
     `max_shapes` distinct shapes is MadsimHipError (max_shapes=0: no shapes pass); `chunk` = seeds per trace launch, 0 = the library's
     default — it never shows in the result.  resolve: as runtime.census."""
-    if _inited_device is None:
-        init(0)
-    L = lib()
-    return _stall_census(lambda *a: L.madsim_hip_stall_census_range(workload.ref(), *a), lambda *a: L.madsim_hip_stall_census_seeds(workload.ref(), *a),
-                         workload, seed0, total, seeds, include, task_cap, max_sites, max_shapes, chunk, config, limits, resolve)
+    return _stall_census(*_range_and_seeds(on, "stall_census", workload), workload, seed0, total, seeds, include, task_cap, max_sites, max_shapes,
+                         chunk, config, limits, resolve)
+
+
+stall_census = _spelled(_on_stall_census)
 
 
 class ProbeSets(_ObsReport):
@@ -1089,18 +1124,19 @@ def _probe_sets(call_range, call_seeds, census_call, workload, vocabulary, seed0
                    f"probe_sets: more than max_sets = {max_sets} distinct probe sets once the runner seeds are settled")
 
 
-def probe_sets(workload, vocabulary=None, seed0=0, total=0, seeds=None, include=(A.PASS, A.PANIC, A.DEADLOCK, A.TIME_LIMIT), obs_cap=256,
-               max_sets=4096, chunk=0, config=None, limits=None, resolve=True):
+@_operation("probe_sets_range", "probe_sets_seeds")
+def _on_probe_sets(on, workload, vocabulary=None, seed0=0, total=0, seeds=None, include=(A.PASS, A.PANIC, A.DEADLOCK, A.TIME_LIMIT), obs_cap=256,
+                   max_sets=4096, chunk=0, config=None, limits=None, resolve=True):
     """madsim_hip_probe_sets_range / madsim_hip_probe_sets_seeds: which COMBINATIONS of the values of `vocabulary` (1 .. 62 distinct 64-bit
     values; None: the values a census of the same seeds finds) the seeds [seed0, seed0 + total) — or the strictly ascending `seeds` —
     reach, by verdict, reduced on the device: returns a ProbeSets.  A seed is counted when its verdict is in `include`; the first `obs_cap`
     observations of a seed are visible; more than `max_sets` distinct sets is MadsimHipError; `chunk` = seeds per trace launch, 0 = the
     library's default — it never shows in the result.  resolve: as runtime.census."""
-    if _inited_device is None:
-        init(0)
-    L = lib()
-    return _probe_sets(lambda *a: L.madsim_hip_probe_sets_range(workload.ref(), *a), lambda *a: L.madsim_hip_probe_sets_seeds(workload.ref(), *a),
-                       census, workload, vocabulary, seed0, total, seeds, include, obs_cap, max_sets, chunk, config, limits, resolve)
+    return _probe_sets(*_range_and_seeds(on, "probe_sets", workload), on.census, workload, vocabulary, seed0, total, seeds, include, obs_cap,
+                       max_sets, chunk, config, limits, resolve)
+
+
+probe_sets = _spelled(_on_probe_sets)
 
 
 class ProbeOrder(_ObsReport):
@@ -1241,18 +1277,19 @@ def _probe_order(call_range, call_seeds, census_call, workload, vocabulary, seed
     return _settle(one, workload, lim0, rounds, seed0, total, seeds, cap, "probe_order: more cells than the vocabulary has pairs (internal)")
 
 
-def probe_order(workload, vocabulary=None, seed0=0, total=0, seeds=None, include=(A.PASS, A.PANIC, A.DEADLOCK, A.TIME_LIMIT), obs_cap=256,
-                chunk=0, config=None, limits=None, resolve=True):
+@_operation("probe_order_range", "probe_order_seeds")
+def _on_probe_order(on, workload, vocabulary=None, seed0=0, total=0, seeds=None, include=(A.PASS, A.PANIC, A.DEADLOCK, A.TIME_LIMIT), obs_cap=256,
+                    chunk=0, config=None, limits=None, resolve=True):
     """madsim_hip_probe_order_range / madsim_hip_probe_order_seeds: which of the values of `vocabulary` (1 .. 32 distinct 64-bit values; None:
     the values a census of the same seeds finds, MadsimHipError when they are more than 32) the seeds [seed0, seed0 + total) — or the
     strictly ascending `seeds` — reach FIRST, by verdict, reduced on the device: returns a ProbeOrder.  A seed is counted when its verdict
     is in `include`; the first `obs_cap` observations of a seed are visible; `chunk` = seeds per trace launch, 0 = the library's default
     — it never shows in the result.  resolve: as runtime.census."""
-    if _inited_device is None:
-        init(0)
-    L = lib()
-    return _probe_order(lambda *a: L.madsim_hip_probe_order_range(workload.ref(), *a), lambda *a: L.madsim_hip_probe_order_seeds(workload.ref(), *a),
-                        census, workload, vocabulary, seed0, total, seeds, include, obs_cap, chunk, config, limits, resolve)
+    return _probe_order(*_range_and_seeds(on, "probe_order", workload), on.census, workload, vocabulary, seed0, total, seeds, include, obs_cap,
+                        chunk, config, limits, resolve)
+
+
+probe_order = _spelled(_on_probe_order)
 
 
 def span_defs(spans):
@@ -1391,18 +1428,19 @@ def _probe_spans(call_range, call_seeds, workload, spans, seed0, total, seeds, i
     return _settle(one, workload, lim0, rounds, seed0, total, seeds, len(defs), "probe_spans: more records than definitions (internal)")
 
 
-def probe_spans(workload, spans, seed0=0, total=0, seeds=None, include=(A.PASS, A.PANIC, A.DEADLOCK, A.TIME_LIMIT), obs_cap=256, chunk=0,
-                config=None, limits=None, resolve=True):
+@_operation("probe_spans_range", "probe_spans_seeds")
+def _on_probe_spans(on, workload, spans, seed0=0, total=0, seeds=None, include=(A.PASS, A.PANIC, A.DEADLOCK, A.TIME_LIMIT), obs_cap=256, chunk=0,
+                    config=None, limits=None, resolve=True):
     """madsim_hip_probe_spans_range / madsim_hip_probe_spans_seeds: the virtual time from the first traced `from` to the first `to` behind
     it, for 1 .. 16 `spans` = (from, to) pairs (from=None: from the start of the run; from == to: the time between the first two
     occurrences), over the seeds [seed0, seed0 + total) — or the strictly ascending `seeds` —, reduced on the device: returns a ProbeSpans.
     A seed is counted when its verdict is in `include`; the first `obs_cap` observations of a seed are visible; `chunk` = seeds per trace
     launch, 0 = the library's default — it never shows in the result.  resolve: as runtime.census."""
-    if _inited_device is None:
-        init(0)
-    L = lib()
-    return _probe_spans(lambda *a: L.madsim_hip_probe_spans_range(workload.ref(), *a), lambda *a: L.madsim_hip_probe_spans_seeds(workload.ref(), *a),
-                        workload, spans, seed0, total, seeds, include, obs_cap, chunk, config, limits, resolve)
+    return _probe_spans(*_range_and_seeds(on, "probe_spans", workload), workload, spans, seed0, total, seeds, include, obs_cap, chunk, config,
+                        limits, resolve)
+
+
+probe_spans = _spelled(_on_probe_spans)
 
 
 def observe_seed(workload, seed, config=None, limits=None, cap=1 << 16, resolve=True):
@@ -1471,8 +1509,9 @@ def _collecting(call, collect):
     return rec[:col.n_listed].copy(), np.array(list(col.n_by_verdict), dtype=np.uint64)
 
 
-def run_campaign(workload, seed0, total, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None,
-                 collect=None, list_runner=False, stop_at_cap=False, resolve=None, observe=0):
+@_operation("run_campaign", "run_campaign_collect")
+def _on_run_campaign(on, workload, seed0, total, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None,
+                     collect=None, list_runner=False, stop_at_cap=False, resolve=None, observe=0):
     """madsim_hip_run_campaign: `total` seeds as batches kept in flight on the library's own streams; returns the Campaign
     report (first failing seed, counts) — no per-seed results.  stop_at_failure: stop launching once a completed batch holds a
     seed with a genuine verdict.
@@ -1494,21 +1533,24 @@ def run_campaign(workload, seed0, total, batch=0, in_flight=0, stop_at_failure=F
     observe without collect is MadsimHipError: there is no list to explain."""
     if observe and collect is None:
         raise MadsimHipError("run_campaign: observe= explains the listed seeds: it needs collect=K")
-    if _inited_device is None:
-        init(0)
+    on.ready()
     cfg = config or A.Config.default()
     lim = limits or A.Limits()
     rep = A.Campaign()
     if collect is None:
-        _check(lib().madsim_hip_run_campaign(workload.ref(), C.byref(cfg), seed0, total, batch, in_flight,
-                                             _campaign_flags(stop_at_failure, resolve=resolve), C.byref(lim), C.byref(rep)))
+        _check(on.entry("run_campaign")(workload.ref(), C.byref(cfg), seed0, total, batch, in_flight,
+                                        _campaign_flags(stop_at_failure, resolve=resolve), C.byref(lim), C.byref(rep)))
         return rep
     flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap, resolve=resolve)
-    failures, by_verdict = _collecting(lambda col: lib().madsim_hip_run_campaign_collect(
+    failures, by_verdict = _collecting(lambda col: on.entry("run_campaign_collect")(
         workload.ref(), C.byref(cfg), seed0, total, batch, in_flight, flags, C.byref(lim), C.byref(rep), col), collect)
     if observe:
-        return rep, failures, by_verdict, _observe_failures(_default_tracer, workload, failures, cfg, lim, observe, resolve)
+        return rep, failures, by_verdict, _observe_failures(on.trace_seeds, workload, failures, cfg, lim, observe, resolve)
     return rep, failures, by_verdict
+
+
+run_campaign = _spelled(_on_run_campaign)
+run_campaign_multi = _spelled(_on_run_campaign, _OnContexts, "contexts", without=("observe",))
 
 
 class CampaignStats:
@@ -1571,17 +1613,21 @@ def _campaign_stats(call, include, top_k, collect, rep):
     return rep, failures, by_verdict, CampaignStats(st, top)
 
 
-def run_campaign_stats(workload, seed0, total, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None, include=(A.PASS,),
-                       top_k=0, collect=None, list_runner=False, stop_at_cap=False, resolve=None):
+@_operation("run_campaign_stats")
+def _on_run_campaign_stats(on, workload, seed0, total, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None, include=(A.PASS,),
+                           top_k=0, collect=None, list_runner=False, stop_at_cap=False, resolve=None):
     """madsim_hip_run_campaign_stats: run_campaign, plus the statistics of clock_ns, steps, msg_count and rng_calls over the seeds whose
     verdict is in `include` (PASS / PANIC / DEADLOCK / TIME_LIMIT) and the `top_k` (<= 16) extreme seeds of each.  Returns
     (campaign, CampaignStats); with collect=K (as run_campaign) (campaign, failures, by_verdict, CampaignStats)."""
-    if _inited_device is None:
-        init(0)
+    on.ready()
     cfg, lim, rep = config or A.Config.default(), limits or A.Limits(), A.Campaign()
     flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap, resolve=resolve)
-    return _campaign_stats(lambda col, st: lib().madsim_hip_run_campaign_stats(
+    return _campaign_stats(lambda col, st: on.entry("run_campaign_stats")(
         workload.ref(), C.byref(cfg), seed0, total, batch, in_flight, flags, C.byref(lim), C.byref(rep), col, st), include, top_k, collect, rep)
+
+
+run_campaign_stats = _spelled(_on_run_campaign_stats)
+run_campaign_stats_multi = _spelled(_on_run_campaign_stats, _OnContexts, "contexts")
 
 
 class CampaignGroups:
@@ -1626,9 +1672,10 @@ def _campaign_groups(call, include, key, max_groups, collect, stats, rep):
     return out + (done(),)
 
 
-def run_campaign_groups(workload, seed0, total, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None,
-                        include=(A.PANIC, A.DEADLOCK, A.TIME_LIMIT), key="obs", max_groups=32, stop_at_groups=False, collect=None, stats=None,
-                        list_runner=False, stop_at_cap=False, resolve=None, observe=0):
+@_operation("run_campaign_groups")
+def _on_run_campaign_groups(on, workload, seed0, total, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None,
+                            include=(A.PANIC, A.DEADLOCK, A.TIME_LIMIT), key="obs", max_groups=32, stop_at_groups=False, collect=None, stats=None,
+                            list_runner=False, stop_at_cap=False, resolve=None, observe=0):
     """madsim_hip_run_campaign_groups: run_campaign, plus the failure modes of the range — the seeds whose verdict is in `include` grouped by
     (verdict, key), `key` one of "obs" (obs_hash: what the workload traced), "trace", "msgs", "clock", "rng", "steps"; the first `max_groups`
     groups in order of first appearance, each with its exact count and its smallest seed.  stop_at_groups: stop launching once max_groups
@@ -1638,14 +1685,17 @@ def run_campaign_groups(workload, seed0, total, batch=0, in_flight=0, stop_at_fa
     observe=cap (0 = nothing new): CampaignGroups.observations[i] is what the smallest seed of groups[i] traced, at most `cap` values — the
     failure mode spelled out, not only its key.  One trace_seeds call after the campaign, under the campaign's limits and resolve rounds;
     MadsimHipError if a replayed seed does not carry the verdict and key it was grouped under."""
-    if _inited_device is None:
-        init(0)
+    on.ready()
     cfg, lim, rep = config or A.Config.default(), limits or A.Limits(), A.Campaign()
     flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap, stop_at_groups, resolve)
-    out = _campaign_groups(lambda col, st, grp: lib().madsim_hip_run_campaign_groups(
+    out = _campaign_groups(lambda col, st, grp: on.entry("run_campaign_groups")(
         workload.ref(), C.byref(cfg), seed0, total, batch, in_flight, flags, C.byref(lim), C.byref(rep), col, st, grp),
         include, key, max_groups, collect, stats, rep)
-    return _observe_groups(_default_tracer, workload, out, cfg, lim, observe, resolve) if observe else out
+    return _observe_groups(on.trace_seeds, workload, out, cfg, lim, observe, resolve) if observe else out
+
+
+run_campaign_groups = _spelled(_on_run_campaign_groups)
+run_campaign_groups_multi = _spelled(_on_run_campaign_groups, _OnContexts, "contexts", without=("observe",))
 
 
 class CampaignDiff:
@@ -1759,8 +1809,9 @@ def _campaign_seeds(call, tracer, workload, cfg, lim, rep, collect, stats, group
     return out + (_observe_failures(tracer, workload, out[1], cfg, lim, observe, resolve),) if observe else out
 
 
-def run_campaign_seeds(workload, seeds, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None, collect=None, list_runner=False,
-                       stop_at_cap=False, stats=None, groups=None, stop_at_groups=False, resolve=None, observe=0):
+@_operation("run_seeds_campaign")
+def _on_run_campaign_seeds(on, workload, seeds, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None, collect=None,
+                           list_runner=False, stop_at_cap=False, stats=None, groups=None, stop_at_groups=False, resolve=None, observe=0):
     """madsim_hip_run_seeds_campaign: every non-differential campaign form over the seeds you name instead of a range — the failing seeds
     an earlier campaign listed, a regression corpus, the members of one failure mode.  `seeds`: any integer sequence or ndarray, STRICTLY
     ASCENDING (seed_list: an unsorted list or a duplicate is MadsimHipError, never sorted silently); position i of the list takes the role of
@@ -1772,26 +1823,33 @@ def run_campaign_seeds(workload, seeds, batch=0, in_flight=0, stop_at_failure=Fa
     for.  observe=cap: with groups=, CampaignGroups.observations as run_campaign_groups fills it; otherwise it needs collect=K and appends the
     listed seeds' observation lists as the last element, as run_campaign does."""
     arr = seed_list(seeds)                                       # (a list that does not ascend is refused before a device is looked for)
-    if _inited_device is None:
-        init(0)
+    on.ready()
     cfg, lim, rep = config or A.Config.default(), limits or A.Limits(), A.Campaign()
     flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap, stop_at_groups, resolve)
-    return _campaign_seeds(lambda col, st, grp: lib().madsim_hip_run_seeds_campaign(
+    return _campaign_seeds(lambda col, st, grp: on.entry("run_seeds_campaign")(
         workload.ref(), C.byref(cfg), _seeds_ptr(arr), len(arr), batch, in_flight, flags, C.byref(lim), C.byref(rep), col, st, grp),
-        _default_tracer, workload, cfg, lim, rep, collect, stats, groups, resolve, observe)
+        on.trace_seeds, workload, cfg, lim, rep, collect, stats, groups, resolve, observe)
 
 
-def run_campaign_diff_seeds(workload, seeds, other=None, config=None, other_config=None, limits=None, other_limits=None, fields=A.DIFF_ALL,
-                            max_listed=0, stop_at_diffs=False, batch=0, in_flight=0, resolve=None, observe=0):
+run_campaign_seeds = _spelled(_on_run_campaign_seeds)
+run_campaign_seeds_multi = _spelled(_on_run_campaign_seeds, _OnContexts, "contexts", without=("observe",))
+
+
+@_operation("run_seeds_campaign_diff")
+def _on_run_campaign_diff_seeds(on, workload, seeds, other=None, config=None, other_config=None, limits=None, other_limits=None, fields=A.DIFF_ALL,
+                                max_listed=0, stop_at_diffs=False, batch=0, in_flight=0, resolve=None, observe=0):
     """madsim_hip_run_seeds_campaign_diff: run_campaign_diff over the seeds you name (`seeds` as run_campaign_seeds') — "did the fix fix all
     of them?" over exactly the seeds that failed.  Returns (campaign A, campaign B, CampaignDiff); resolve / observe as
     run_campaign_diff_resolved's."""
     arr = seed_list(seeds)                                       # (a list that does not ascend is refused before a device is looked for)
-    if _inited_device is None:
-        init(0)
-    return _campaign_diff(lambda wa, ca, la, wb, cb, lb, flags, ra, rb, d: lib().madsim_hip_run_seeds_campaign_diff(
+    on.ready()
+    return _campaign_diff(lambda wa, ca, la, wb, cb, lb, flags, ra, rb, d: on.entry("run_seeds_campaign_diff")(
         wa, ca, la, wb, cb, lb, _seeds_ptr(arr), len(arr), batch, in_flight, flags, ra, rb, d),
-        workload, other, config, other_config, limits, other_limits, fields, max_listed, stop_at_diffs, resolve, observe)
+        workload, other, config, other_config, limits, other_limits, fields, max_listed, stop_at_diffs, resolve, observe, on.trace_seeds)
+
+
+run_campaign_diff_seeds = _spelled(_on_run_campaign_diff_seeds)
+run_campaign_diff_seeds_multi = _spelled(_on_run_campaign_diff_seeds, _OnContexts, "contexts", without=("observe",))
 
 
 class CampaignPaired:
@@ -1884,8 +1942,9 @@ def _campaign_paired(call, workload, other, config, other_config, limits, other_
     return out + (CampaignDiff(d, arr),) if d is not None else out
 
 
-def run_campaign_paired(workload, seed0, total, other=None, config=None, other_config=None, limits=None, other_limits=None, include=(A.PASS,),
-                        other_include=None, top_k=0, fields=None, max_listed=0, resolve=None, batch=0, in_flight=0):
+@_operation("run_paired_campaign")
+def _on_run_campaign_paired(on, workload, seed0, total, other=None, config=None, other_config=None, limits=None, other_limits=None, include=(A.PASS,),
+                            other_include=None, top_k=0, fields=None, max_listed=0, resolve=None, batch=0, in_flight=0):
     """madsim_hip_run_paired_campaign: what a change did to each seed's numbers.  Side A = (workload, config, limits) and side B = (other,
     other_config, other_limits) over the same seeds — a None on the B side means "the same as A's".  A seed is PAIRED when its verdict on
     side A is in `include` and on side B in `other_include` (None: the same as `include`); for every paired seed and each of clock_ns,
@@ -1893,22 +1952,29 @@ def run_campaign_paired(workload, seed0, total, other=None, config=None, other_c
     metric and direction, count, min, max, the exact sum, a histogram and the `top_k` (<= 16) extreme seeds with both values.  Returns
     (campaign A, campaign B, CampaignPaired); with fields= (A.DIFF_* bits) the differential report of the same run comes last, as
     run_campaign_diff's, with the max_listed smallest differing seeds.  resolve: as run_campaign_diff_resolved's."""
-    if _inited_device is None:
-        init(0)
-    return _campaign_paired(lambda wa, ca, la, wb, cb, lb, flags, ra, rb, d, pr: lib().madsim_hip_run_paired_campaign(
+    on.ready()
+    return _campaign_paired(lambda wa, ca, la, wb, cb, lb, flags, ra, rb, d, pr: on.entry("run_paired_campaign")(
         wa, ca, la, wb, cb, lb, seed0, total, batch, in_flight, flags, ra, rb, d, pr),
         workload, other, config, other_config, limits, other_limits, include, other_include, top_k, fields, max_listed, resolve)
 
 
-def run_campaign_paired_seeds(workload, seeds, other=None, config=None, other_config=None, limits=None, other_limits=None, include=(A.PASS,),
-                              other_include=None, top_k=0, fields=None, max_listed=0, resolve=None, batch=0, in_flight=0):
+run_campaign_paired = _spelled(_on_run_campaign_paired)
+run_campaign_paired_multi = _spelled(_on_run_campaign_paired, _OnContexts, "contexts")
+
+
+@_operation("run_seeds_campaign_paired")
+def _on_run_campaign_paired_seeds(on, workload, seeds, other=None, config=None, other_config=None, limits=None, other_limits=None, include=(A.PASS,),
+                                  other_include=None, top_k=0, fields=None, max_listed=0, resolve=None, batch=0, in_flight=0):
     """madsim_hip_run_seeds_campaign_paired: run_campaign_paired over the seeds you name (`seeds` as run_campaign_seeds')."""
     arr = seed_list(seeds)                                       # (a list that does not ascend is refused before a device is looked for)
-    if _inited_device is None:
-        init(0)
-    return _campaign_paired(lambda wa, ca, la, wb, cb, lb, flags, ra, rb, d, pr: lib().madsim_hip_run_seeds_campaign_paired(
+    on.ready()
+    return _campaign_paired(lambda wa, ca, la, wb, cb, lb, flags, ra, rb, d, pr: on.entry("run_seeds_campaign_paired")(
         wa, ca, la, wb, cb, lb, _seeds_ptr(arr), len(arr), batch, in_flight, flags, ra, rb, d, pr),
         workload, other, config, other_config, limits, other_limits, include, other_include, top_k, fields, max_listed, resolve)
+
+
+run_campaign_paired_seeds = _spelled(_on_run_campaign_paired_seeds)
+run_campaign_paired_seeds_multi = _spelled(_on_run_campaign_paired_seeds, _OnContexts, "contexts")
 
 
 class CampaignSweep:
@@ -2005,8 +2071,9 @@ def _sweep_range(seed0, total, seeds_arr):
     return 0, len(seeds_arr), seeds_arr.ctypes.data_as(C.POINTER(C.c_uint64)) if seeds_arr.size else C.cast(C.pointer(C.c_uint64(0)), C.POINTER(C.c_uint64))
 
 
-def run_campaign_sweep(variants, seed0=0, total=0, seeds=None, fields=A.DIFF_VERDICT, list_rule="mixed", max_listed=0, stop_at_listed=False, batch=0,
-                       in_flight=0, resolve=None):
+@_operation("run_sweep_campaign")
+def _on_run_campaign_sweep(on, variants, seed0=0, total=0, seeds=None, fields=A.DIFF_VERDICT, list_rule="mixed", max_listed=0, stop_at_listed=False,
+                           batch=0, in_flight=0, resolve=None):
     """madsim_hip_run_sweep_campaign: up to eight variants — `variants`, a sequence of (workload, config, limits) tuples, shorter tuples or
     None meaning defaults — over the range [seed0, seed0 + total) or the strictly ascending list `seeds`, every seed classified across all
     of them on the device.  Returns (reports, CampaignSweep): one plain campaign report per variant, and the counts by failing set with
@@ -2015,20 +2082,14 @@ def run_campaign_sweep(variants, seed0=0, total=0, seeds=None, fields=A.DIFF_VER
     read; resolve: as everywhere, each variant under its own limits."""
     def call(v, n, sa, flags, s):
         s0, n_seeds, ptr = _sweep_range(seed0, total, sa)
-        if _inited_device is None and n_seeds:                  # (the mirror's argument errors come first; nothing to run needs no device)
-            init(0)
-        return lib().madsim_hip_run_sweep_campaign(v, n, s0, n_seeds, ptr, batch, in_flight, flags, s)
+        if n_seeds:                                             # (the mirror's argument errors come first; nothing to run needs no device)
+            on.ready()
+        return on.entry("run_sweep_campaign")(v, n, s0, n_seeds, ptr, batch, in_flight, flags, s)
     return _campaign_sweep(call, variants, seeds, fields, list_rule, max_listed, stop_at_listed, resolve)
 
 
-def run_campaign_sweep_multi(contexts, variants, seed0=0, total=0, seeds=None, fields=A.DIFF_VERDICT, list_rule="mixed", max_listed=0,
-                             stop_at_listed=False, batch=0, in_flight=0, resolve=None):
-    """madsim_hip_run_sweep_campaign_multi: run_campaign_sweep over several contexts (every variant of batch k on context k % n); the report is
-    the one a single context gives."""
-    arr = (C.c_void_p * len(contexts))(*[c._h for c in contexts])
-    return _campaign_sweep(lambda v, n, sa, flags, s: lib().madsim_hip_run_sweep_campaign_multi(
-        arr, len(contexts), v, n, *_sweep_range(seed0, total, sa), batch, in_flight, flags, s),
-        variants, seeds, fields, list_rule, max_listed, stop_at_listed, resolve)
+run_campaign_sweep = _spelled(_on_run_campaign_sweep)
+run_campaign_sweep_multi = _spelled(_on_run_campaign_sweep, _OnContexts, "contexts")
 
 
 def run_batch_device(workload, seed0, count, d_out_ptr, stream_ptr=0, config=None, limits=None, want_summary=True):
@@ -2066,6 +2127,7 @@ class Context:
         self.device = device
 
     def close(self):
+        """Destroy the context (madsim_hip_ctx_destroy); closing twice is harmless."""
         if self._h:
             lib().madsim_hip_ctx_destroy(self._h)
             self._h = C.c_void_p()
@@ -2083,6 +2145,8 @@ class Context:
         return out
 
     def run_batch(self, workload, seed0, count, config=None, limits=None, auto_rounds=0):
+        """runtime.run_batch on this context (madsim_hip_ctx_run_batch); auto_rounds=N: runtime.run_batch_auto with max_rounds=N
+        (madsim_hip_ctx_run_batch_auto)."""
         cfg, lim = config or A.Config.default(), limits or A.Limits()
         out = np.zeros(count, dtype=A.RESULT_DTYPE)
         summ = A.Summary()
@@ -2094,112 +2158,10 @@ class Context:
                                                   out.ctypes.data_as(C.c_void_p), C.byref(summ)))
         return out, summ
 
-    def trace_seeds(self, workload, seeds, config=None, limits=None, obs_cap=256, log_cap=0, resolve=True):
-        """runtime.trace_seeds on this context (madsim_hip_ctx_trace_seeds)."""
-        return _trace_seeds(lambda *a: lib().madsim_hip_ctx_trace_seeds(self._h, workload.ref(), *a), workload, seeds, config, limits, obs_cap,
-                            log_cap, resolve)
-
-    def timeline(self, workload, seeds, config=None, limits=None, obs_cap=256, resolve=True):
-        """runtime.timeline on this context (madsim_hip_ctx_timeline_seeds)."""
-        return _timeline(lambda *a: lib().madsim_hip_ctx_timeline_seeds(self._h, workload.ref(), *a), workload, seeds, config, limits, obs_cap,
-                         resolve)
-
-    def post_mortem(self, workload, seeds, task_cap=32, config=None, limits=None, resolve=True, lengths=False):
-        """runtime.post_mortem on this context (madsim_hip_ctx_task_states)."""
-        return _post_mortem(lambda *a: lib().madsim_hip_ctx_task_states(self._h, workload.ref(), *a), workload, seeds, task_cap, config, limits,
-                            resolve, lengths)
-
-    def diverge_seeds(self, workload, seeds, other=None, config=None, other_config=None, limits=None, other_limits=None, log_cap=1 << 16,
-                      obs_cap=256, window=4, resolve=True):
-        """runtime.diverge_seeds on this context (madsim_hip_ctx_diverge_seeds)."""
-        return _diverge_seeds(lambda *a: lib().madsim_hip_ctx_diverge_seeds(self._h, *a), workload, seeds, other, config, other_config, limits,
-                              other_limits, log_cap, obs_cap, window, resolve)
-
-    def census(self, workload, seed0=0, total=0, seeds=None, include=(A.PASS, A.PANIC, A.DEADLOCK, A.TIME_LIMIT), obs_cap=256, max_values=4096,
-               chunk=0, config=None, limits=None, resolve=True):
-        """runtime.census on this context (madsim_hip_ctx_census_range / madsim_hip_ctx_census_seeds)."""
-        L = lib()
-        return _census(lambda *a: L.madsim_hip_ctx_census_range(self._h, workload.ref(), *a),
-                       lambda *a: L.madsim_hip_ctx_census_seeds(self._h, workload.ref(), *a), workload, seed0, total, seeds, include, obs_cap,
-                       max_values, chunk, config, limits, resolve)
-
-    def stall_census(self, workload, seed0=0, total=0, seeds=None, include=(A.PANIC, A.DEADLOCK, A.TIME_LIMIT), task_cap=32, max_sites=4096,
-                     max_shapes=4096, chunk=0, config=None, limits=None, resolve=True):
-        """runtime.stall_census on this context (madsim_hip_ctx_stall_census_range / madsim_hip_ctx_stall_census_seeds)."""
-        L = lib()
-        return _stall_census(lambda *a: L.madsim_hip_ctx_stall_census_range(self._h, workload.ref(), *a),
-                             lambda *a: L.madsim_hip_ctx_stall_census_seeds(self._h, workload.ref(), *a), workload, seed0, total, seeds, include,
-                             task_cap, max_sites, max_shapes, chunk, config, limits, resolve)
-
-    def probe_sets(self, workload, vocabulary=None, seed0=0, total=0, seeds=None, include=(A.PASS, A.PANIC, A.DEADLOCK, A.TIME_LIMIT), obs_cap=256,
-                   max_sets=4096, chunk=0, config=None, limits=None, resolve=True):
-        """runtime.probe_sets on this context (madsim_hip_ctx_probe_sets_range / madsim_hip_ctx_probe_sets_seeds)."""
-        L = lib()
-        return _probe_sets(lambda *a: L.madsim_hip_ctx_probe_sets_range(self._h, workload.ref(), *a),
-                           lambda *a: L.madsim_hip_ctx_probe_sets_seeds(self._h, workload.ref(), *a), self.census, workload, vocabulary, seed0,
-                           total, seeds, include, obs_cap, max_sets, chunk, config, limits, resolve)
-
-    def probe_order(self, workload, vocabulary=None, seed0=0, total=0, seeds=None, include=(A.PASS, A.PANIC, A.DEADLOCK, A.TIME_LIMIT), obs_cap=256,
-                    chunk=0, config=None, limits=None, resolve=True):
-        """runtime.probe_order on this context (madsim_hip_ctx_probe_order_range / madsim_hip_ctx_probe_order_seeds)."""
-        L = lib()
-        return _probe_order(lambda *a: L.madsim_hip_ctx_probe_order_range(self._h, workload.ref(), *a),
-                            lambda *a: L.madsim_hip_ctx_probe_order_seeds(self._h, workload.ref(), *a), self.census, workload, vocabulary, seed0,
-                            total, seeds, include, obs_cap, chunk, config, limits, resolve)
-
-    def probe_spans(self, workload, spans, seed0=0, total=0, seeds=None, include=(A.PASS, A.PANIC, A.DEADLOCK, A.TIME_LIMIT), obs_cap=256, chunk=0,
-                    config=None, limits=None, resolve=True):
-        """runtime.probe_spans on this context (madsim_hip_ctx_probe_spans_range / madsim_hip_ctx_probe_spans_seeds)."""
-        L = lib()
-        return _probe_spans(lambda *a: L.madsim_hip_ctx_probe_spans_range(self._h, workload.ref(), *a),
-                            lambda *a: L.madsim_hip_ctx_probe_spans_seeds(self._h, workload.ref(), *a), workload, spans, seed0, total, seeds,
-                            include, obs_cap, chunk, config, limits, resolve)
-
     def observe_seed(self, workload, seed, config=None, limits=None, cap=1 << 16, resolve=True):
         """runtime.observe_seed on this context."""
         t = self.trace_seeds(workload, [seed], config, limits, obs_cap=cap, log_cap=0, resolve=resolve)[0]
         return t.observations, t.result
-
-    def run_campaign(self, workload, seed0, total, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None,
-                     collect=None, list_runner=False, stop_at_cap=False, resolve=None, observe=0):
-        """runtime.run_campaign on this context (madsim_hip_ctx_run_campaign / madsim_hip_ctx_run_campaign_collect); observe=cap needs
-        collect=K and makes the return value (campaign, failures, by_verdict, observations), as there."""
-        if observe and collect is None:
-            raise MadsimHipError("run_campaign: observe= explains the listed seeds: it needs collect=K")
-        cfg, lim = config or A.Config.default(), limits or A.Limits()
-        rep = A.Campaign()
-        if collect is None:
-            _check(lib().madsim_hip_ctx_run_campaign(self._h, workload.ref(), C.byref(cfg), seed0, total, batch, in_flight,
-                                                     _campaign_flags(stop_at_failure, resolve=resolve), C.byref(lim), C.byref(rep)))
-            return rep
-        flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap, resolve=resolve)
-        failures, by_verdict = _collecting(lambda col: lib().madsim_hip_ctx_run_campaign_collect(
-            self._h, workload.ref(), C.byref(cfg), seed0, total, batch, in_flight, flags, C.byref(lim), C.byref(rep), col), collect)
-        if observe:
-            return rep, failures, by_verdict, _observe_failures(self.trace_seeds, workload, failures, cfg, lim, observe, resolve)
-        return rep, failures, by_verdict
-
-    def run_campaign_stats(self, workload, seed0, total, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None,
-                           include=(A.PASS,), top_k=0, collect=None, list_runner=False, stop_at_cap=False, resolve=None):
-        """runtime.run_campaign_stats on this context (madsim_hip_ctx_run_campaign_stats)."""
-        cfg, lim, rep = config or A.Config.default(), limits or A.Limits(), A.Campaign()
-        flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap, resolve=resolve)
-        return _campaign_stats(lambda col, st: lib().madsim_hip_ctx_run_campaign_stats(
-            self._h, workload.ref(), C.byref(cfg), seed0, total, batch, in_flight, flags, C.byref(lim), C.byref(rep), col, st),
-            include, top_k, collect, rep)
-
-
-    def run_campaign_groups(self, workload, seed0, total, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None,
-                            include=(A.PANIC, A.DEADLOCK, A.TIME_LIMIT), key="obs", max_groups=32, stop_at_groups=False, collect=None, stats=None,
-                            list_runner=False, stop_at_cap=False, resolve=None, observe=0):
-        """runtime.run_campaign_groups on this context (madsim_hip_ctx_run_campaign_groups)."""
-        cfg, lim, rep = config or A.Config.default(), limits or A.Limits(), A.Campaign()
-        flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap, stop_at_groups, resolve)
-        out = _campaign_groups(lambda col, st, grp: lib().madsim_hip_ctx_run_campaign_groups(
-            self._h, workload.ref(), C.byref(cfg), seed0, total, batch, in_flight, flags, C.byref(lim), C.byref(rep), col, st, grp),
-            include, key, max_groups, collect, stats, rep)
-        return _observe_groups(self.trace_seeds, workload, out, cfg, lim, observe, resolve) if observe else out
-
 
     def run_campaign_diff(self, workload, seed0, total, other=None, config=None, other_config=None, limits=None, other_limits=None,
                           fields=A.DIFF_ALL, max_listed=0, stop_at_diffs=False, batch=0, in_flight=0, resolve=None, observe=0):
@@ -2209,45 +2171,11 @@ class Context:
             workload, other, config, other_config, limits, other_limits, fields, max_listed, stop_at_diffs, resolve, observe, self.trace_seeds)
 
 
-    def run_campaign_seeds(self, workload, seeds, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None, collect=None,
-                           list_runner=False, stop_at_cap=False, stats=None, groups=None, stop_at_groups=False, resolve=None, observe=0):
-        """runtime.run_campaign_seeds on this context (madsim_hip_ctx_run_seeds_campaign)."""
-        arr = seed_list(seeds)
-        cfg, lim, rep = config or A.Config.default(), limits or A.Limits(), A.Campaign()
-        flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap, stop_at_groups, resolve)
-        return _campaign_seeds(lambda col, st, grp: lib().madsim_hip_ctx_run_seeds_campaign(
-            self._h, workload.ref(), C.byref(cfg), _seeds_ptr(arr), len(arr), batch, in_flight, flags, C.byref(lim), C.byref(rep), col, st, grp),
-            self.trace_seeds, workload, cfg, lim, rep, collect, stats, groups, resolve, observe)
-
-    def run_campaign_diff_seeds(self, workload, seeds, other=None, config=None, other_config=None, limits=None, other_limits=None,
-                                fields=A.DIFF_ALL, max_listed=0, stop_at_diffs=False, batch=0, in_flight=0, resolve=None, observe=0):
-        """runtime.run_campaign_diff_seeds on this context (madsim_hip_ctx_run_seeds_campaign_diff)."""
-        arr = seed_list(seeds)
-        return _campaign_diff(lambda wa, ca, la, wb, cb, lb, flags, ra, rb, d: lib().madsim_hip_ctx_run_seeds_campaign_diff(
-            self._h, wa, ca, la, wb, cb, lb, _seeds_ptr(arr), len(arr), batch, in_flight, flags, ra, rb, d),
-            workload, other, config, other_config, limits, other_limits, fields, max_listed, stop_at_diffs, resolve, observe, self.trace_seeds)
-
-    def run_campaign_paired(self, workload, seed0, total, other=None, config=None, other_config=None, limits=None, other_limits=None,
-                            include=(A.PASS,), other_include=None, top_k=0, fields=None, max_listed=0, resolve=None, batch=0, in_flight=0):
-        """runtime.run_campaign_paired on this context (madsim_hip_ctx_run_paired_campaign)."""
-        return _campaign_paired(lambda wa, ca, la, wb, cb, lb, flags, ra, rb, d, pr: lib().madsim_hip_ctx_run_paired_campaign(
-            self._h, wa, ca, la, wb, cb, lb, seed0, total, batch, in_flight, flags, ra, rb, d, pr),
-            workload, other, config, other_config, limits, other_limits, include, other_include, top_k, fields, max_listed, resolve)
-
-    def run_campaign_paired_seeds(self, workload, seeds, other=None, config=None, other_config=None, limits=None, other_limits=None,
-                                  include=(A.PASS,), other_include=None, top_k=0, fields=None, max_listed=0, resolve=None, batch=0, in_flight=0):
-        """runtime.run_campaign_paired_seeds on this context (madsim_hip_ctx_run_seeds_campaign_paired)."""
-        arr = seed_list(seeds)
-        return _campaign_paired(lambda wa, ca, la, wb, cb, lb, flags, ra, rb, d, pr: lib().madsim_hip_ctx_run_seeds_campaign_paired(
-            self._h, wa, ca, la, wb, cb, lb, _seeds_ptr(arr), len(arr), batch, in_flight, flags, ra, rb, d, pr),
-            workload, other, config, other_config, limits, other_limits, include, other_include, top_k, fields, max_listed, resolve)
-
-    def run_campaign_sweep(self, variants, seed0=0, total=0, seeds=None, fields=A.DIFF_VERDICT, list_rule="mixed", max_listed=0,
-                           stop_at_listed=False, batch=0, in_flight=0, resolve=None):
-        """runtime.run_campaign_sweep on this context (madsim_hip_ctx_run_sweep_campaign)."""
-        return _campaign_sweep(lambda v, n, sa, flags, s: lib().madsim_hip_ctx_run_sweep_campaign(
-            self._h, v, n, *_sweep_range(seed0, total, sa), batch, in_flight, flags, s),
-            variants, seeds, fields, list_rule, max_listed, stop_at_listed, resolve)
+# Every other operation on a Context: its one definition, reaching the library through that context.
+for _op in (_on_trace_seeds, _on_timeline, _on_post_mortem, _on_diverge_seeds, _on_census, _on_stall_census, _on_probe_sets, _on_probe_order,
+            _on_probe_spans, _on_run_campaign, _on_run_campaign_stats, _on_run_campaign_groups, _on_run_campaign_seeds, _on_run_campaign_diff_seeds,
+            _on_run_campaign_paired, _on_run_campaign_paired_seeds, _on_run_campaign_sweep):
+    setattr(Context, _op.public_name, _spelled(_op, _OnContext, "self"))
 
 
 def run_batch_multi(contexts, workload, seed0, count, config=None, limits=None, max_rounds=5):
@@ -2262,49 +2190,6 @@ def run_batch_multi(contexts, workload, seed0, count, config=None, limits=None, 
     return out, summ
 
 
-def run_campaign_multi(contexts, workload, seed0, total, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None,
-                       collect=None, list_runner=False, stop_at_cap=False, resolve=None):
-    """madsim_hip_run_campaign_multi: the seed search over several contexts (one per GPU) from one host thread — batch k on context
-    k % n, reports read in batch order, every device stopped within one round of batches of the first genuine failure.
-    collect / list_runner / stop_at_cap: as run_campaign (madsim_hip_run_campaign_collect_multi); the list is the one a single
-    context gives."""
-    cfg = config or A.Config.default()
-    lim = limits or A.Limits()
-    rep = A.Campaign()
-    arr = (C.c_void_p * len(contexts))(*[c._h for c in contexts])
-    if collect is None:
-        _check(lib().madsim_hip_run_campaign_multi(arr, len(contexts), workload.ref(), C.byref(cfg), seed0, total, batch, in_flight,
-                                                   _campaign_flags(stop_at_failure, resolve=resolve), C.byref(lim), C.byref(rep)))
-        return rep
-    flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap, resolve=resolve)
-    failures, by_verdict = _collecting(lambda col: lib().madsim_hip_run_campaign_collect_multi(
-        arr, len(contexts), workload.ref(), C.byref(cfg), seed0, total, batch, in_flight, flags, C.byref(lim), C.byref(rep), col), collect)
-    return rep, failures, by_verdict
-
-
-def run_campaign_stats_multi(contexts, workload, seed0, total, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None,
-                             include=(A.PASS,), top_k=0, collect=None, list_runner=False, stop_at_cap=False, resolve=None):
-    """madsim_hip_run_campaign_stats_multi: run_campaign_stats over several contexts; the statistics are the ones a single context gives."""
-    cfg, lim, rep = config or A.Config.default(), limits or A.Limits(), A.Campaign()
-    arr = (C.c_void_p * len(contexts))(*[c._h for c in contexts])
-    flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap, resolve=resolve)
-    return _campaign_stats(lambda col, st: lib().madsim_hip_run_campaign_stats_multi(
-        arr, len(contexts), workload.ref(), C.byref(cfg), seed0, total, batch, in_flight, flags, C.byref(lim), C.byref(rep), col, st),
-        include, top_k, collect, rep)
-
-
-def run_campaign_groups_multi(contexts, workload, seed0, total, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None,
-                              include=(A.PANIC, A.DEADLOCK, A.TIME_LIMIT), key="obs", max_groups=32, stop_at_groups=False, collect=None, stats=None,
-                              list_runner=False, stop_at_cap=False, resolve=None):
-    """madsim_hip_run_campaign_groups_multi: run_campaign_groups over several contexts; the groups are the ones a single context gives."""
-    cfg, lim, rep = config or A.Config.default(), limits or A.Limits(), A.Campaign()
-    arr = (C.c_void_p * len(contexts))(*[c._h for c in contexts])
-    flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap, stop_at_groups, resolve)
-    return _campaign_groups(lambda col, st, grp: lib().madsim_hip_run_campaign_groups_multi(
-        arr, len(contexts), workload.ref(), C.byref(cfg), seed0, total, batch, in_flight, flags, C.byref(lim), C.byref(rep), col, st, grp),
-        include, key, max_groups, collect, stats, rep)
-
-
 def run_campaign_diff_multi(contexts, workload, seed0, total, other=None, config=None, other_config=None, limits=None, other_limits=None,
                             fields=A.DIFF_ALL, max_listed=0, stop_at_diffs=False, batch=0, in_flight=0, resolve=None):
     """madsim_hip_run_campaign_diff_multi: run_campaign_diff over several contexts (both sides of batch k on context k % n); the report is the
@@ -2313,49 +2198,6 @@ def run_campaign_diff_multi(contexts, workload, seed0, total, other=None, config
     return _campaign_diff(lambda wa, ca, la, wb, cb, lb, flags, ra, rb, d: lib().madsim_hip_run_campaign_diff_multi(
         arr, len(contexts), wa, ca, la, wb, cb, lb, seed0, total, batch, in_flight, flags, ra, rb, d),
         workload, other, config, other_config, limits, other_limits, fields, max_listed, stop_at_diffs, resolve)
-
-
-def run_campaign_seeds_multi(contexts, workload, seeds, batch=0, in_flight=0, stop_at_failure=False, config=None, limits=None, collect=None,
-                             list_runner=False, stop_at_cap=False, stats=None, groups=None, stop_at_groups=False, resolve=None):
-    """madsim_hip_run_seeds_campaign_multi: run_campaign_seeds over several contexts (batch k of the list on context k % n); the reports are
-    the ones a single context gives."""
-    seeds_arr = seed_list(seeds)
-    cfg, lim, rep = config or A.Config.default(), limits or A.Limits(), A.Campaign()
-    arr = (C.c_void_p * len(contexts))(*[c._h for c in contexts])
-    flags = _campaign_flags(stop_at_failure, list_runner, stop_at_cap, stop_at_groups, resolve)
-    return _campaign_seeds(lambda col, st, grp: lib().madsim_hip_run_seeds_campaign_multi(
-        arr, len(contexts), workload.ref(), C.byref(cfg), _seeds_ptr(seeds_arr), len(seeds_arr), batch, in_flight, flags, C.byref(lim),
-        C.byref(rep), col, st, grp), None, workload, cfg, lim, rep, collect, stats, groups, resolve, 0)
-
-
-def run_campaign_diff_seeds_multi(contexts, workload, seeds, other=None, config=None, other_config=None, limits=None, other_limits=None,
-                                  fields=A.DIFF_ALL, max_listed=0, stop_at_diffs=False, batch=0, in_flight=0, resolve=None):
-    """madsim_hip_run_seeds_campaign_diff_multi: run_campaign_diff_seeds over several contexts; the report is the one a single context gives."""
-    seeds_arr = seed_list(seeds)
-    arr = (C.c_void_p * len(contexts))(*[c._h for c in contexts])
-    return _campaign_diff(lambda wa, ca, la, wb, cb, lb, flags, ra, rb, d: lib().madsim_hip_run_seeds_campaign_diff_multi(
-        arr, len(contexts), wa, ca, la, wb, cb, lb, _seeds_ptr(seeds_arr), len(seeds_arr), batch, in_flight, flags, ra, rb, d),
-        workload, other, config, other_config, limits, other_limits, fields, max_listed, stop_at_diffs, resolve)
-
-
-def run_campaign_paired_multi(contexts, workload, seed0, total, other=None, config=None, other_config=None, limits=None, other_limits=None,
-                              include=(A.PASS,), other_include=None, top_k=0, fields=None, max_listed=0, resolve=None, batch=0, in_flight=0):
-    """madsim_hip_run_paired_campaign_multi: run_campaign_paired over several contexts (both sides of batch k on context k % n); the report is
-    the one a single context gives."""
-    arr = (C.c_void_p * len(contexts))(*[c._h for c in contexts])
-    return _campaign_paired(lambda wa, ca, la, wb, cb, lb, flags, ra, rb, d, pr: lib().madsim_hip_run_paired_campaign_multi(
-        arr, len(contexts), wa, ca, la, wb, cb, lb, seed0, total, batch, in_flight, flags, ra, rb, d, pr),
-        workload, other, config, other_config, limits, other_limits, include, other_include, top_k, fields, max_listed, resolve)
-
-
-def run_campaign_paired_seeds_multi(contexts, workload, seeds, other=None, config=None, other_config=None, limits=None, other_limits=None,
-                                    include=(A.PASS,), other_include=None, top_k=0, fields=None, max_listed=0, resolve=None, batch=0, in_flight=0):
-    """madsim_hip_run_seeds_campaign_paired_multi: run_campaign_paired_seeds over several contexts; the report is the one a single context gives."""
-    seeds_arr = seed_list(seeds)
-    arr = (C.c_void_p * len(contexts))(*[c._h for c in contexts])
-    return _campaign_paired(lambda wa, ca, la, wb, cb, lb, flags, ra, rb, d, pr: lib().madsim_hip_run_seeds_campaign_paired_multi(
-        arr, len(contexts), wa, ca, la, wb, cb, lb, _seeds_ptr(seeds_arr), len(seeds_arr), batch, in_flight, flags, ra, rb, d, pr),
-        workload, other, config, other_config, limits, other_limits, include, other_include, top_k, fields, max_listed, resolve)
 
 
 def run_campaign_over_ranks(workload, seed0, total, batch=65536, stop_at_failure=True, config=None, limits=None, device_tensors=None, group=None,
@@ -2398,6 +2240,7 @@ def run_campaign_over_ranks(workload, seed0, total, batch=65536, stop_at_failure
 
 
 def timing_ms(slot):
+    """madsim_hip_timing_ms: the milliseconds between the two events of timing slot `slot` of run_batch_async, on the default context."""
     ms = C.c_double(0.0)
     _check(lib().madsim_hip_timing_ms(slot, C.byref(ms)))
     return ms.value
@@ -2416,6 +2259,8 @@ def trace_seed(workload, seed, config=None, limits=None, cap=1 << 20):
 
 
 def geometry(workload, limits=None):
+    """madsim_hip_geometry: the A.Geometry the library derives for `workload` under `limits` — the kernel build it selects, its block
+    shape and its capacities.  A host computation: no device needed."""
     lim = limits or A.Limits()
     g = A.Geometry()
     _check(lib().madsim_hip_geometry(workload.ref(), C.byref(lim), C.byref(g)))
