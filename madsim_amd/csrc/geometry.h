@@ -5,6 +5,7 @@
 
 #include <cstring>
 #include <algorithm>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -26,10 +27,46 @@ struct Geo {
     uint32_t lds_bytes, lds_per_seed, blocks_per_cu, grid, lanes_per_wave, waves_per_block;
 };
 
-inline bool uses_op(const madsim_workload_t* w, int op) {
-    for (uint32_t i = 0; i < w->n_insns; i++) if (w->insns[i].op == op) return true;
-    return false;
+// A set of opcodes.  validate() and make_geometry() ask a workload once which ops it uses (ops_used) and test that, and every group of ops that
+// a rule, a task unit or a kernel build is about is named once, below: a new op joins the groups it belongs to, here.
+struct OpSet {
+    uint64_t bits[2] = {0, 0};
+    constexpr OpSet() = default;
+    constexpr OpSet(std::initializer_list<int> ops) { for (int op : ops) bits[op >> 6] |= 1ull << (op & 63); }
+    constexpr bool has(int op) const { return (unsigned)op < 128u && ((bits[op >> 6] >> (op & 63)) & 1) != 0; }
+    constexpr bool any(const OpSet& o) const { return ((bits[0] & o.bits[0]) | (bits[1] & o.bits[1])) != 0; }
+    constexpr OpSet operator|(const OpSet& o) const { OpSet r; r.bits[0] = bits[0] | o.bits[0]; r.bits[1] = bits[1] | o.bits[1]; return r; }
+};
+static_assert(MS_OP__COUNT <= 128, "OpSet holds two words");
+static inline OpSet ops_used(const madsim_workload_t* w) {          // (static, like horizon() below: the library exports no new symbol)
+    OpSet s;
+    for (uint32_t i = 0; i < w->n_insns; i++) if (w->insns[i].op < 128) s.bits[w->insns[i].op >> 6] |= 1ull << (w->insns[i].op & 63);
+    return s;
 }
+constexpr OpSet OPS_JUMP{MS_OP_DJNZ, MS_OP_JMP, MS_OP_JEQ};                               // b is a pc: range-checked, and held to the timeout scopes' borders
+constexpr OpSet OPS_MARK{MS_OP_MARK, MS_OP_SLEEP_UNTIL, MS_OP_ASSERT_ELAPSED};            // the mark family: t0 itself — its two words of unit 2 are taken
+constexpr OpSet OPS_SELECT{MS_OP_RECV_OR_TICK, MS_OP_RECV_TIMEOUT_AT};                    // the selects of ABI v7: the select builds (their receive rides RECV_TIMEOUT's path)
+constexpr OpSet OPS_SIGNAL{MS_OP_CTRL_C, MS_OP_SEND_CTRL_C, MS_OP_RECV_OR_CTRL_C};        // ctrl-c: the signal builds, which carry no timer-op tier
+constexpr OpSet OPS_TICKER_USE{MS_OP_TICK, MS_OP_INTERVAL_RESET, MS_OP_RECV_OR_TICK};     // need a ticker: an INTERVAL on every path from the program's entry
+constexpr OpSet OPS_TIER = OpSet{MS_OP_TIMEOUT_BEGIN, MS_OP_TIMEOUT_END, MS_OP_INTERVAL} | OPS_TICKER_USE | OPS_SELECT;   // the timer-op tiers: no signal build carries one
+constexpr OpSet OPS_TAGGED_RECV{MS_OP_REPLY, MS_OP_RECV, MS_OP_RECV_TIMEOUT, MS_OP_RECV_OR_TICK, MS_OP_RECV_TIMEOUT_AT, MS_OP_RECV_OR_CTRL_C};   // b >> 8 is a tag: not a reserved one
+constexpr OpSet OPS_BOUND_EP = OPS_TAGGED_RECV | OpSet{MS_OP_BIND, MS_OP_CLOSE, MS_OP_ACCEPT};     // a is an Endpoint of the task's own: a table entry, never a virtual address
+constexpr OpSet OPS_CONN_ACCEPT{MS_OP_CONNECT, MS_OP_ACCEPT};                             // make connections: servers spawn a handler per accept, so task slots to spare
+constexpr OpSet OPS_CONN = OPS_CONN_ACCEPT | OpSet{MS_OP_CSEND, MS_OP_CRECV, MS_OP_CCLOSE};       // touch the connection unit (CCLOSE alone too: a stray `drop((tx, rx))` would
+                                                                                          // read the task's flag word as a connection id without it): the CHAN class
+constexpr OpSet OPS_RPC{MS_OP_RPC_CALL, MS_OP_RPC_REPLY};                                 // typed RPC (with the hooks: the RPC unit and class, one task per request in flight)
+constexpr OpSet OPS_HOOK{MS_OP_HOOK_REQ, MS_OP_HOOK_RSP};                                 // the per-node hook plane
+constexpr OpSet OPS_T0 = OPS_MARK | OPS_SELECT | OpSet{MS_OP_RECV_TIMEOUT, MS_OP_RECV_OR_CTRL_C};    // read or write unit 2 {t0, timeout()'s deadline} (RPC does too)
+constexpr OpSet OPS_TIME_CLASS = OPS_T0 | OpSet{MS_OP_ADVANCE, MS_OP_TRACE_TIME, MS_OP_SET_LATENCY};  // MADSIM_FEAT_TIME (set_latency: any extended build; this is the leanest)
+constexpr OpSet OPS_NODE_CLASS = OPS_SIGNAL | OpSet{MS_OP_KILL, MS_OP_RESTART, MS_OP_PAUSE, MS_OP_RESUME, MS_OP_ABORT, MS_OP_ASSERT_EXIT, MS_OP_BUILD};   // MADSIM_FEAT_NODE
+                                                                                          // (a ctrl-c sent to a node without a handler is kill_id)
+constexpr OpSet OPS_GFLAG{MS_OP_GSET, MS_OP_GADD, MS_OP_ASSERT_G, MS_OP_PANIC_IF_G_LT};   // the four global flags: their plane
+constexpr OpSet OPS_RESET_NODE{MS_OP_KILL, MS_OP_RESTART, MS_OP_SEND_CTRL_C};             // can reset node a (a ctrl-c without a handler is kill_id)
+constexpr OpSet OPS_IN_SCOPE = OPS_JUMP | OPS_GFLAG | OpSet{MS_OP_SLEEP, MS_OP_SLEEP_UNTIL, MS_OP_SLEEP_RAND, MS_OP_YIELD, MS_OP_SEND, MS_OP_REPLY, MS_OP_RECV,
+    MS_OP_CONNECT, MS_OP_SET, MS_OP_ASSERT_VAL, MS_OP_TRACE, MS_OP_TRACE_TIME, MS_OP_PANIC, MS_OP_RANDOM, MS_OP_RAND_BOOL,   // a timeout scope can drop their pending state
+    MS_OP_TICK, MS_OP_INTERVAL_RESET};                                                    // (timeout(d, ticker.tick()): expiry drops the tick future, not the ticker)
+constexpr OpSet OPS_SLEEP_BASE{MS_OP_SLEEP, MS_OP_SLEEP_RAND};                            // b s + imm ns is a duration: the base ops among them (the compact layout's horizon)
+constexpr OpSet OPS_SLEEP_ANY = OPS_SLEEP_BASE | OpSet{MS_OP_SLEEP_UNTIL, MS_OP_ADVANCE}; // ... and every class's (the narrow heap's horizon)
 
 // UniformDuration::new(lo, hi) [DEP rand 0.8]: see SURVEY.md Appendix A.3
 inline void uniform_duration_params(uint64_t lo, uint64_t hi, uint32_t* mode, uint64_t* low, uint64_t* range, uint64_t* zone) {
@@ -71,7 +108,7 @@ inline std::vector<uint32_t> device_socks(const madsim_workload_t* w) {
         if (w->socks[i].port != 0 || (t[i] & 0x8000u)) continue;
         uint32_t K = 0;
         for (uint32_t j = 0; j < w->n_socks; j++) K += w->socks[j].node == w->socks[i].node && w->socks[j].kind == w->socks[i].kind;
-        if (uses_op(w, MS_OP_CONNECT)) K *= 2;
+        if (ops_used(w).has(MS_OP_CONNECT)) K *= 2;
         const uint32_t base = (uint32_t)t.size();
         if (base + K > 255) { t.resize(256); return t; }                         // far too many: validate() rejects it
         for (uint32_t p = 1; p <= K; p++) t.push_back((uint32_t)w->socks[i].node | ((uint32_t)w->socks[i].kind << 8) | (p << 16));
@@ -116,25 +153,24 @@ inline int validate(const madsim_workload_t* w, const madsim_config_t* cfg, std:
     }
     if (w->panic_dyn_max > 254) return fail(err, MADSIM_E_WORKLOAD, "panic_dyn_max must be <= 254");
     if (device_socks(w).size() > 63) return fail(err, MADSIM_E_WORKLOAD, "at most 63 socket addresses, counting the candidate ports of ephemeral endpoints");
+    const OpSet ops = ops_used(w);
+    std::vector<uint8_t> is_entry(w->n_insns, 0);           // pc -> a program starts here
+    for (uint32_t p = 0; p < w->n_progs; p++) is_entry[w->progs[p].entry] = 1;
     for (uint32_t i = 0; i < w->n_insns; i++) {
         const madsim_insn_t& in = w->insns[i];
-        switch (in.op) {
-        case MS_OP_SPAWN: case MS_OP_JOIN: case MS_OP_ABORT:
-            if (in.a >= w->n_progs) return fail(err, MADSIM_E_WORKLOAD, "prog operand out of range"); break;
-        case MS_OP_DJNZ: case MS_OP_JMP: case MS_OP_JEQ:
-            if (in.b >= w->n_insns) return fail(err, MADSIM_E_WORKLOAD, "jump target out of range"); break;
-        case MS_OP_BIND: case MS_OP_REPLY: case MS_OP_RECV: case MS_OP_CLOSE: case MS_OP_RECV_TIMEOUT: case MS_OP_ACCEPT:
-        case MS_OP_RECV_OR_TICK: case MS_OP_RECV_TIMEOUT_AT: case MS_OP_RECV_OR_CTRL_C:
+        if (OPS_JUMP.has(in.op) && in.b >= w->n_insns) return fail(err, MADSIM_E_WORKLOAD, "jump target out of range");
+        if (OPS_BOUND_EP.has(in.op)) {
             if (in.a >= w->n_socks) return fail(err, MADSIM_E_WORKLOAD, "socket operand out of range");
             // (the reference would let an IP-less node bind it and answer AddrNotAvailable to every other: not modelled, refused)
             if (w->socks[in.a].kind == MADSIM_ADDR_VIRTUAL) return fail(err, MADSIM_E_WORKLOAD, "a virtual address is a destination only: it cannot be bound or used as an Endpoint");
-            if ((in.op == MS_OP_REPLY || in.op == MS_OP_RECV || in.op == MS_OP_RECV_TIMEOUT || in.op == MS_OP_RECV_OR_TICK || in.op == MS_OP_RECV_TIMEOUT_AT ||
-                 in.op == MS_OP_RECV_OR_CTRL_C) && (in.b >> 8) > MADSIM_TAG_RPC_LAST)
-                return fail(err, MADSIM_E_WORKLOAD, "tags 0xFE and 0xFF are reserved");
+            if (OPS_TAGGED_RECV.has(in.op) && (in.b >> 8) > MADSIM_TAG_RPC_LAST) return fail(err, MADSIM_E_WORKLOAD, "tags 0xFE and 0xFF are reserved");
             if (in.op == MS_OP_RECV_OR_TICK && (in.b & 0xfc)) return fail(err, MADSIM_E_WORKLOAD, "recv_or_tick: b bits 0-1 are the flags (1 tick arm first, 2 fold the tick's instant)");
             if (in.op == MS_OP_RECV_OR_CTRL_C && (in.b & 0xfe)) return fail(err, MADSIM_E_WORKLOAD, "recv_or_ctrl_c: b bit 0 is the only flag (1 recv arm first)");
             if (in.op == MS_OP_RECV_TIMEOUT_AT && in.imm >= 1000000000u) return fail(err, MADSIM_E_WORKLOAD, "recv_from_timeout_at: imm is the nanoseconds below one second");
-            break;
+        }
+        switch (in.op) {                                    // (the groups above have no case below)
+        case MS_OP_SPAWN: case MS_OP_JOIN: case MS_OP_ABORT:
+            if (in.a >= w->n_progs) return fail(err, MADSIM_E_WORKLOAD, "prog operand out of range"); break;
         case MS_OP_SEND: case MS_OP_CONNECT:
             if (in.a >= w->n_socks || (uint32_t)(in.b & 0xff) >= w->n_socks) return fail(err, MADSIM_E_WORKLOAD, "socket operand out of range");
             if (w->socks[in.a].kind == MADSIM_ADDR_VIRTUAL) return fail(err, MADSIM_E_WORKLOAD, "a virtual address is never an Endpoint");
@@ -167,8 +203,6 @@ inline int validate(const madsim_workload_t* w, const madsim_config_t* cfg, std:
     {   // `t0` is a local of the task body (`let t0 = Instant::now()`): Rust refuses a use before its assignment, and so does this —
         // a task slot's t0 words are whatever its previous occupant left there.  Rule: in the program that owns it (the one with the
         // largest entry <= pc) a MS_OP_MARK stands at a lower pc than every MS_OP_SLEEP_UNTIL / MS_OP_ASSERT_ELAPSED.
-        std::vector<uint8_t> is_entry(w->n_insns, 0);
-        for (uint32_t p = 0; p < w->n_progs; p++) is_entry[w->progs[p].entry] = 1;
         bool marked = false;
         for (uint32_t i = 0; i < w->n_insns; i++) {
             if (is_entry[i]) marked = false;
@@ -184,8 +218,6 @@ inline int validate(const madsim_workload_t* w, const madsim_config_t* cfg, std:
         // the pcs BEGIN + 1 .. END; the device keeps ONE scope per task (no nesting), and the ops a scope may drop at any await are the ones whose
         // pending state it knows how to drop (include/madsim_hip.h).
         std::vector<int32_t> scope(w->n_insns, -1);         // pc -> BEGIN pc of the scope that covers it
-        std::vector<uint8_t> is_entry(w->n_insns, 0);
-        for (uint32_t p = 0; p < w->n_progs; p++) is_entry[w->progs[p].entry] = 1;
         for (uint32_t i = 0; i < w->n_insns; i++) {
             const madsim_insn_t& in = w->insns[i];
             if (in.op == MS_OP_TIMEOUT_END && scope[i] < 0) return fail(err, MADSIM_E_WORKLOAD, "timeout_end without its timeout_begin");
@@ -200,20 +232,10 @@ inline int validate(const madsim_workload_t* w, const madsim_config_t* cfg, std:
                 if (is_entry[k]) return fail(err, MADSIM_E_WORKLOAD, "a timeout scope must lie inside one program");
                 if (op == MS_OP_TIMEOUT_BEGIN) return fail(err, MADSIM_E_WORKLOAD, "timeout scopes do not nest");
                 if (k < end) {
-                    bool ok = false;
-                    switch (op) {
-                    case MS_OP_SLEEP: case MS_OP_SLEEP_UNTIL: case MS_OP_SLEEP_RAND: case MS_OP_YIELD:
-                    case MS_OP_SEND: case MS_OP_REPLY: case MS_OP_RECV: case MS_OP_CONNECT:
-                    case MS_OP_SET: case MS_OP_DJNZ: case MS_OP_JMP: case MS_OP_JEQ: case MS_OP_ASSERT_VAL: case MS_OP_TRACE: case MS_OP_TRACE_TIME:
-                    case MS_OP_GSET: case MS_OP_GADD: case MS_OP_ASSERT_G: case MS_OP_PANIC_IF_G_LT: case MS_OP_PANIC: case MS_OP_RANDOM: case MS_OP_RAND_BOOL:
-                    case MS_OP_TICK: case MS_OP_INTERVAL_RESET:     // timeout(d, ticker.tick()): expiry drops the tick future, not the ticker
-                        ok = true; break;
-                    case MS_OP_INTERVAL:
-                        return fail(err, MADSIM_E_WORKLOAD, "interval inside a timeout scope: the ticker would be a local of the async block");
-                    case MS_OP_RPC_CALL: ok = (w->insns[k].imm >> 8) == 0; break;          // an untimed call only
-                    case MS_OP_CSEND: case MS_OP_CRECV: ok = conn; break;                   // on the block's own connection
-                    default: break;
-                    }
+                    bool ok = OPS_IN_SCOPE.has(op);
+                    if (op == MS_OP_INTERVAL) return fail(err, MADSIM_E_WORKLOAD, "interval inside a timeout scope: the ticker would be a local of the async block");
+                    if (op == MS_OP_RPC_CALL) ok = (w->insns[k].imm >> 8) == 0;             // an untimed call only
+                    if (op == MS_OP_CSEND || op == MS_OP_CRECV) ok = conn;                  // on the block's own connection
                     if (!ok) return fail(err, MADSIM_E_WORKLOAD, (op == MS_OP_CSEND || op == MS_OP_CRECV)
                         ? "csend / crecv inside a timeout scope need a connect at a lower pc of the same scope"
                         : "op not allowed inside a timeout scope (nested timeouts, spawn / join / abort / done, bind / close / accept / cclose, node ops, hooks, ipvs, set_latency, advance)");
@@ -224,7 +246,7 @@ inline int validate(const madsim_workload_t* w, const madsim_config_t* cfg, std:
         }
         for (uint32_t i = 0; i < w->n_insns; i++) {     // no jump enters a scope; none leaves one except to its END
             const madsim_insn_t& in = w->insns[i];
-            if (in.op != MS_OP_DJNZ && in.op != MS_OP_JMP && in.op != MS_OP_JEQ) continue;
+            if (!OPS_JUMP.has(in.op)) continue;
             const int32_t from = scope[i], to = scope[in.b];
             if (from != to) return fail(err, MADSIM_E_WORKLOAD, from < 0 ? "a jump into a timeout scope" : "a jump out of a timeout scope (only its timeout_end may be the target)");
         }
@@ -232,21 +254,18 @@ inline int validate(const madsim_workload_t* w, const madsim_config_t* cfg, std:
     {   // interval tickers (MS_OP_INTERVAL / TICK / INTERVAL_RESET): `let mut i = interval(p)` is a local of the task body.  Rust refuses a use
         // before the assignment, and so does this: forward data-flow from every program entry over fall-through, jump and scope-expiry edges
         // (BEGIN -> END + 1); an INTERVAL ends a path that has no ticker.  A spawned program starts without one (it has its own entry).
-        std::vector<uint8_t> is_entry(w->n_insns, 0);
-        for (uint32_t p = 0; p < w->n_progs; p++) is_entry[w->progs[p].entry] = 1;
-        bool marked = false, ticks = false;
+        bool marked = false;
         for (uint32_t i = 0; i < w->n_insns; i++) {
             if (is_entry[i]) marked = false;
             const madsim_insn_t& in = w->insns[i];
             if (in.op == MS_OP_MARK) marked = true;
-            if (in.op == MS_OP_TICK || in.op == MS_OP_INTERVAL_RESET || in.op == MS_OP_RECV_OR_TICK) ticks = true;
             if (in.op != MS_OP_INTERVAL) continue;
             if (in.b == 0 && in.imm == 0) return fail(err, MADSIM_E_WORKLOAD, "interval: the period must be non-zero");
             if ((in.a & 3) == 3 || in.a > 7) return fail(err, MADSIM_E_WORKLOAD, "interval: a bits 0-1 are the missed-tick behaviour (0 burst, 1 delay, 2 skip), bit 2 interval_at");
             if (in.imm >= 1000000000u) return fail(err, MADSIM_E_WORKLOAD, "interval: imm is the nanoseconds below one second");
             if ((in.a & 4) && !marked) return fail(err, MADSIM_E_WORKLOAD, "interval_at before the program's first mark: t0 is not assigned yet");
         }
-        if (ticks) {
+        if (ops.any(OPS_TICKER_USE)) {
             std::vector<uint8_t> bare(w->n_insns, 0);         // pc reachable from an entry on a path without an INTERVAL
             std::vector<uint32_t> work;
             for (uint32_t p = 0; p < w->n_progs; p++) if (!bare[w->progs[p].entry]) { bare[w->progs[p].entry] = 1; work.push_back(w->progs[p].entry); }
@@ -254,11 +273,11 @@ inline int validate(const madsim_workload_t* w, const madsim_config_t* cfg, std:
             while (!work.empty()) {
                 const uint32_t i = work.back(); work.pop_back();
                 const madsim_insn_t& in = w->insns[i];
-                if (in.op == MS_OP_TICK || in.op == MS_OP_INTERVAL_RESET || in.op == MS_OP_RECV_OR_TICK)
+                if (OPS_TICKER_USE.has(in.op))
                     return fail(err, MADSIM_E_WORKLOAD, "tick / interval_reset / recv_or_tick on a path from the program's entry that passes no interval: the ticker does not exist yet");
                 if (in.op == MS_OP_INTERVAL || in.op == MS_OP_DONE || in.op == MS_OP_PANIC) continue;
-                if (in.op == MS_OP_JMP) { edge(in.b); continue; }
-                if (in.op == MS_OP_DJNZ || in.op == MS_OP_JEQ) edge(in.b);
+                if (OPS_JUMP.has(in.op)) edge(in.b);
+                if (in.op == MS_OP_JMP) continue;                       // (the one jump that never falls through)
                 if (in.op == MS_OP_TIMEOUT_BEGIN) edge((uint32_t)in.b + 1);
                 edge(i + 1);
             }
@@ -266,17 +285,14 @@ inline int validate(const madsim_workload_t* w, const madsim_config_t* cfg, std:
     }
     {   // ctrl-c signals (MS_OP_CTRL_C / SEND_CTRL_C / RECV_OR_CTRL_C) run on builds of their own, which carry no timer-op tier: a workload that
         // uses both has no build (a limit of the compiled set, not of madsim)
-        const bool signals = uses_op(w, MS_OP_CTRL_C) || uses_op(w, MS_OP_SEND_CTRL_C) || uses_op(w, MS_OP_RECV_OR_CTRL_C);
-        const bool tiers = uses_op(w, MS_OP_TIMEOUT_BEGIN) || uses_op(w, MS_OP_TIMEOUT_END) || uses_op(w, MS_OP_INTERVAL) || uses_op(w, MS_OP_TICK) ||
-                           uses_op(w, MS_OP_INTERVAL_RESET) || uses_op(w, MS_OP_RECV_OR_TICK) || uses_op(w, MS_OP_RECV_TIMEOUT_AT);
-        if (signals && tiers)
+        if (ops.any(OPS_SIGNAL) && ops.any(OPS_TIER))
             return fail(err, MADSIM_E_WORKLOAD, "ctrl-c signal ops cannot be combined with timeout scopes, interval tickers, recv_or_tick or recv_from_timeout_at: no kernel build carries both");
     }
     for (uint32_t p = 0; p < w->n_progs; p++) {
         if (!(w->progs[p].flags & MADSIM_PROG_DROP_SPAWN)) continue;
         if (p + 1 >= w->n_progs || w->progs[p + 1].node != w->progs[p].node)
             return fail(err, MADSIM_E_WORKLOAD, "MADSIM_PROG_DROP_SPAWN: the guard spawns program p + 1, which must exist and run on the same node");
-        if (uses_op(w, MS_OP_PAUSE))
+        if (ops.has(MS_OP_PAUSE))
             return fail(err, MADSIM_E_WORKLOAD, "MADSIM_PROG_DROP_SPAWN cannot be combined with MS_OP_PAUSE (a parked Runnable is dropped in the killer's context)");
     }
     {   // NetSim::reset_node (network.rs:142-147) drops a killed node's sockets in the iteration order of a HashMap hashed with
@@ -287,7 +303,7 @@ inline int validate(const madsim_workload_t* w, const madsim_config_t* cfg, std:
         uint32_t resettable = 0;
         for (uint32_t i = 0; i < w->n_insns; i++) {
             const madsim_insn_t& in = w->insns[i];
-            if (in.op == MS_OP_KILL || in.op == MS_OP_RESTART || in.op == MS_OP_SEND_CTRL_C) resettable |= 1u << in.a;   // (a ctrl-c without a handler is kill_id)
+            if (OPS_RESET_NODE.has(in.op)) resettable |= 1u << in.a;
         }
         for (uint32_t n = 0; n <= w->n_nodes && w->nodes; n++) if (w->nodes[n].flags & (MADSIM_NODE_RESTART_ON_PANIC | MADSIM_NODE_RESTART_MATCHING)) resettable |= 1u << n;
         for (uint32_t p = 0; p < w->n_progs; p++) if (w->progs[p].flags & MADSIM_PROG_INIT) resettable |= 1u << w->progs[p].node;
@@ -331,6 +347,21 @@ inline madsim_config_t probe_config() {
 #define MADSIM_DEDUP_BUCKETS 64
 #endif
 static_assert(MADSIM_DEDUP_BUCKETS <= 64 && (MADSIM_DEDUP_BUCKETS & (MADSIM_DEDUP_BUCKETS - 1)) == 0, "Lane::dd_occ mirrors the buckets in 64 bits");
+// How far ahead of the clock a deadline the workload asks for can lie: the latency range, rand_delay's 1 ms floor, the longest of the
+// `durations` ops (b s + imm ns) and — timed_ops: in workloads with extended ops — the latency table, receive timeouts and RPC call timeouts.
+// 8-byte heap entries (the narrow heap, the compact layout) hold a deadline as 32 bits from the clock: below HORIZON_8_BYTE only.
+constexpr uint64_t HORIZON_8_BYTE = (1ull << 31) - (1ull << 24);
+static inline uint64_t horizon(const madsim_workload_t* w, const madsim_config_t* cfg, OpSet durations, bool timed_ops) {
+    uint64_t h = std::max<uint64_t>(cfg->lat_hi_ns, 1000000ull);
+    for (uint32_t i = 0; timed_ops && i < cfg->n_lat_table && i < 4; i++) h = std::max<uint64_t>(h, cfg->lat_table_hi_ns[i]);
+    for (uint32_t i = 0; i < w->n_insns; i++) {
+        const madsim_insn_t& in = w->insns[i];
+        if (durations.has(in.op)) h = std::max<uint64_t>(h, (uint64_t)in.b * 1000000000ull + in.imm);
+        if (timed_ops && (in.op == MS_OP_RECV_TIMEOUT || in.op == MS_OP_RECV_TIMEOUT_AT)) h = std::max<uint64_t>(h, (uint64_t)(in.b & 0xff) * 1000000000ull + in.imm);
+        if (timed_ops && in.op == MS_OP_RPC_CALL) h = std::max<uint64_t>(h, (uint64_t)(in.imm >> 8) * 1000000ull);
+    }
+    return h;
+}
 inline int make_geometry(const Device& g, const madsim_workload_t* w, const madsim_config_t* cfg, const madsim_limits_t* lim, uint64_t count, Geo* G, std::string* err, bool trace = false) {
     KParams& P = G->P;
     memset(&P, 0, sizeof P);
@@ -344,19 +375,19 @@ inline int make_geometry(const Device& g, const madsim_workload_t* w, const mads
     uint32_t dummy; bernoulli(0.1, &P.bug_pint, &dummy);
     uniform_duration_params(cfg->lat_lo_ns, cfg->lat_hi_ns, &P.lat_mode, &P.lat_low, &P.lat_range, &P.lat_zone);
     for (int i = 0; i < 4; i++) bernoulli(i < (int)cfg->n_loss_table ? cfg->loss_table[i] : 0.0, &P.loss_table_pint[i], &P.loss_table_always[i]);
-    P.uses_set_lat = uses_op(w, MS_OP_SET_LATENCY);
+    const OpSet ops = ops_used(w);
+    P.uses_set_lat = ops.has(MS_OP_SET_LATENCY);
     for (uint32_t i = 0; i < 4 && i < cfg->n_lat_table; i++)
         uniform_duration_params(cfg->lat_table_lo_ns[i], cfg->lat_table_hi_ns[i], &P.lat_tab_mode[i], &P.lat_tab_low[i], &P.lat_tab_range[i], &P.lat_tab_zone[i]);
     P.time_limit = L.time_limit_ns;
     P.max_steps = L.max_steps ? L.max_steps : (1u << 24);
     P.no_log = L.no_trace_hash ? 1u : 0u;
-    bool restarts = uses_op(w, MS_OP_RESTART);
+    bool restarts = ops.has(MS_OP_RESTART);
     for (uint32_t i = 0; i <= w->n_nodes && w->nodes; i++) restarts |= (w->nodes[i].flags & (MADSIM_NODE_RESTART_ON_PANIC | MADSIM_NODE_RESTART_MATCHING)) != 0;
     // request-per-connection servers spawn a handler per accept: leave room for a few concurrent ones
-    bool chan = uses_op(w, MS_OP_CONNECT) || uses_op(w, MS_OP_ACCEPT);
-    P.uses_hooks = uses_op(w, MS_OP_HOOK_REQ) || uses_op(w, MS_OP_HOOK_RSP);
-    P.uses_rpc = uses_op(w, MS_OP_RPC_CALL) || uses_op(w, MS_OP_RPC_REPLY) || P.uses_hooks;   // likewise: one task per request in flight
-    P.max_tasks = L.max_tasks ? L.max_tasks : w->n_progs + (restarts ? w->n_progs : 0) + (chan || P.uses_rpc ? 8 : 0);
+    P.uses_hooks = ops.any(OPS_HOOK);
+    P.uses_rpc = ops.any(OPS_RPC) || P.uses_hooks;                                 // likewise: one task per request in flight
+    P.max_tasks = L.max_tasks ? L.max_tasks : w->n_progs + (restarts ? w->n_progs : 0) + (ops.any(OPS_CONN_ACCEPT) || P.uses_rpc ? 8 : 0);
     if (P.max_tasks > 254) P.max_tasks = 254;
     if (P.max_tasks > 254) return fail(err, MADSIM_E_LIMITS, "max_tasks must be <= 254");
     P.mbox_regs = L.mbox_regs == MADSIM_LIMIT_NONE ? 0 : L.mbox_regs ? L.mbox_regs : 2;
@@ -364,32 +395,28 @@ inline int make_geometry(const Device& g, const madsim_workload_t* w, const mads
     if (P.mbox_regs > 255 || P.mbox_msgs > 255) return fail(err, MADSIM_E_LIMITS, "mailbox capacities must be <= 255");
     P.heap_lds = L.heap_lds_slots ? L.heap_lds_slots : 8;
     P.heap_spill = (L.heap_lds_slots || L.heap_spill_slots) ? L.heap_spill_slots : 56;
-    bool t0 = uses_op(w, MS_OP_MARK) || uses_op(w, MS_OP_SLEEP_UNTIL) || uses_op(w, MS_OP_ASSERT_ELAPSED) || uses_op(w, MS_OP_RECV_TIMEOUT) || P.uses_rpc;
-    t0 |= uses_op(w, MS_OP_RECV_OR_TICK) || uses_op(w, MS_OP_RECV_TIMEOUT_AT);      // (the receive of either rides RECV_TIMEOUT's path)
-    t0 |= uses_op(w, MS_OP_RECV_OR_CTRL_C);                                          // (likewise)
-    // (MS_OP_CCLOSE alone counts too: without the connection unit a stray `drop((tx, rx))` read the task's flag word as a connection id)
-    P.uses_chan = uses_op(w, MS_OP_CONNECT) || uses_op(w, MS_OP_ACCEPT) || uses_op(w, MS_OP_CSEND) || uses_op(w, MS_OP_CRECV) || uses_op(w, MS_OP_CCLOSE);
+    P.uses_chan = ops.any(OPS_CONN);
     // task units: 0-1 always; 2 = {t0, timeout()'s deadline} when used; then the connection unit, then the RPC unit
-    P.task_units = t0 ? 3 : 2;
+    P.task_units = ops.any(OPS_T0) || P.uses_rpc ? 3 : 2;
     if (P.uses_chan) { P.chan_unit = P.task_units; P.task_units++; }
     // {rsp_tag in hand, rsp_tag staged with the oneshot value}: the two t0 words of unit 2 when no MARK-family op needs
     // them (unit 2's other half is the timeout deadline RPC calls use anyway), else a unit of their own
-    const bool mark = uses_op(w, MS_OP_MARK) || uses_op(w, MS_OP_SLEEP_UNTIL) || uses_op(w, MS_OP_ASSERT_ELAPSED);
-    if (P.uses_rpc) { if (!mark) P.rpc_unit = 2; else { P.rpc_unit = P.task_units; P.task_units++; } }
+    if (P.uses_rpc) { if (!ops.any(OPS_MARK)) P.rpc_unit = 2; else { P.rpc_unit = P.task_units; P.task_units++; } }
     // timeout scopes: {END pc | active << 16 | connection made in the scope << 17, -, the scope's deadline} (k_poll.h)
     P.scope_unit = 0;
-    if (uses_op(w, MS_OP_TIMEOUT_BEGIN)) { P.scope_unit = P.task_units; P.task_units++; }
+    const bool scopes = ops.has(MS_OP_TIMEOUT_BEGIN), selects = ops.any(OPS_SELECT), ticks = ops.has(MS_OP_INTERVAL) || selects, signals = ops.any(OPS_SIGNAL);
+    if (scopes) { P.scope_unit = P.task_units; P.task_units++; }
     // interval tickers: {TICK_ACTIVE | behaviour << 1 | period s << 16, period ns, next deadline} (k_poll.h)
     P.tick_unit = 0;
-    if (uses_op(w, MS_OP_INTERVAL)) { P.tick_unit = P.task_units; P.task_units++; }
+    if (ops.has(MS_OP_INTERVAL)) { P.tick_unit = P.task_units; P.task_units++; }
     // per socket: header, owner, registrations, queued messages (+ accept queue, parked acceptor); set once the layout
     // (base or extended) is known, below
     P.max_conns = L.max_conns ? L.max_conns : 4;
     P.chan_queue = L.chan_queue ? L.chan_queue : 2;
     if (P.max_conns > 127 || P.chan_queue > 15) return fail(err, MADSIM_E_LIMITS, "max_conns <= 127, chan_queue <= 15");
     P.conn_words = 3 + 2 * P.chan_queue * 3;
-    P.has_clog_link = uses_op(w, MS_OP_CLOG_LINK) || uses_op(w, MS_OP_UNCLOG_LINK);
-    P.has_clog = P.has_clog_link || uses_op(w, MS_OP_CLOG_NODE) || uses_op(w, MS_OP_UNCLOG_NODE);
+    P.has_clog_link = ops.any(OpSet{MS_OP_CLOG_LINK, MS_OP_UNCLOG_LINK});
+    P.has_clog = P.has_clog_link || ops.any(OpSet{MS_OP_CLOG_NODE, MS_OP_UNCLOG_NODE});
     // uniq_addr: every table entry is a distinct node-IP address and every node has its IP — then an address resolves to
     // its node and to its own table entry, and the kernel skips the general resolution of network.rs:272-313
     P.uniq_addr = 1;
@@ -420,28 +447,18 @@ inline int make_geometry(const Device& g, const madsim_workload_t* w, const mads
     // Classes of extended ops the workload needs (sim_kernel.h MADSIM_FEAT_*): the kernel build is picked by this mask
     // (select_variant), and any of them switches the per-seed LDS layout to its extended form.
     P.features = 0;
-    if (uses_op(w, MS_OP_RECV_TIMEOUT) || uses_op(w, MS_OP_MARK) || uses_op(w, MS_OP_SLEEP_UNTIL) || uses_op(w, MS_OP_ASSERT_ELAPSED) ||
-        uses_op(w, MS_OP_ADVANCE) || uses_op(w, MS_OP_TRACE_TIME) || P.uses_set_lat) P.features |= MADSIM_FEAT_TIME;   // (set_latency: any extended build; this is the leanest)
-    if (uses_op(w, MS_OP_RECV_OR_TICK) || uses_op(w, MS_OP_RECV_TIMEOUT_AT)) P.features |= MADSIM_FEAT_TIME;
-    // ctrl-c signals: a send without a handler is kill_id (the node class); the select's receive rides RECV_TIMEOUT's path (the time class)
-    const bool signals = uses_op(w, MS_OP_CTRL_C) || uses_op(w, MS_OP_SEND_CTRL_C) || uses_op(w, MS_OP_RECV_OR_CTRL_C);
-    if (signals) P.features |= MADSIM_FEAT_NODE;
-    if (uses_op(w, MS_OP_RECV_OR_CTRL_C)) P.features |= MADSIM_FEAT_TIME;
+    if (ops.any(OPS_TIME_CLASS)) P.features |= MADSIM_FEAT_TIME;
     if (P.uses_chan) P.features |= MADSIM_FEAT_CHAN;
     if (P.uses_rpc) P.features |= MADSIM_FEAT_RPC | MADSIM_FEAT_TIME;            // call_timeout rides the timeout unit
-    if (P.has_restart_on_panic || uses_op(w, MS_OP_KILL) || uses_op(w, MS_OP_RESTART) || uses_op(w, MS_OP_PAUSE) || uses_op(w, MS_OP_RESUME) ||
-        uses_op(w, MS_OP_ABORT) || uses_op(w, MS_OP_ASSERT_EXIT) || uses_op(w, MS_OP_BUILD)) P.features |= MADSIM_FEAT_NODE;
+    if (P.has_restart_on_panic || ops.any(OPS_NODE_CLASS)) P.features |= MADSIM_FEAT_NODE;
     for (uint32_t i = 0; i < w->n_progs; i++) if (w->progs[i].flags & MADSIM_PROG_INIT) P.features |= MADSIM_FEAT_NODE;
     if (!P.uniq_addr) P.features |= MADSIM_FEAT_ADDR;
     for (uint32_t i = 0; i < w->n_progs; i++)          // guards that spawn in Drop: compiled into the full builds only
         if (w->progs[i].flags & MADSIM_PROG_DROP_SPAWN) P.features |= MADSIM_FEAT_NODE | MADSIM_FEAT_ADDR;
-    const bool scopes = uses_op(w, MS_OP_TIMEOUT_BEGIN);
     if (trace) P.features = MADSIM_FEAT_ALL;          // the trace build carries every class
     if (scopes) P.features |= MADSIM_FEAT_SCOPE;      // (outside MADSIM_FEAT_ALL: only these workloads select the scope builds)
     // (likewise: only these workloads select the ticker builds; those with the selects of ABI v7, the select builds — a workload with
     //  timeout_at and no ticker runs there without the tick unit, only INTERVAL allocates it)
-    const bool selects = uses_op(w, MS_OP_RECV_OR_TICK) || uses_op(w, MS_OP_RECV_TIMEOUT_AT);
-    const bool ticks = uses_op(w, MS_OP_INTERVAL) || selects;
     if (ticks) P.features |= MADSIM_FEAT_TICK;
     if (selects) P.features |= MADSIM_FEAT_SELECT;
     if (signals) P.features |= MADSIM_FEAT_SIGNAL;    // (outside MADSIM_FEAT_ALL too: only these workloads select the signal builds)
@@ -458,18 +475,7 @@ inline int make_geometry(const Device& g, const madsim_workload_t* w, const mads
     // MADSIM_STATE_NARROW_HEAP: 8-byte heap entries hold the low deadline word — admitted when nothing the workload can ask for lies 2^31 ns
     // ahead of the clock (the device checks every push all the same: a channel back-off can grow past it at run time)
     bool narrow_ok = (L.state_mem & MADSIM_STATE_NARROW_HEAP) && !trace && !cfg->buggify && !P.has_restart_on_panic && !scopes && !ticks && !signals;   // (no narrow scope / ticker / signal build)
-    {
-        uint64_t horizon = std::max<uint64_t>(cfg->lat_hi_ns, 1000000ull);
-        for (uint32_t i = 0; i < cfg->n_lat_table && i < 4; i++) horizon = std::max<uint64_t>(horizon, cfg->lat_table_hi_ns[i]);
-        for (uint32_t i = 0; i < w->n_insns; i++) {
-            const madsim_insn_t& in = w->insns[i];
-            if (in.op == MS_OP_SLEEP || in.op == MS_OP_SLEEP_RAND || in.op == MS_OP_SLEEP_UNTIL || in.op == MS_OP_ADVANCE)
-                horizon = std::max<uint64_t>(horizon, (uint64_t)in.b * 1000000000ull + in.imm);
-            if (in.op == MS_OP_RECV_TIMEOUT || in.op == MS_OP_RECV_TIMEOUT_AT) horizon = std::max<uint64_t>(horizon, (uint64_t)(in.b & 0xff) * 1000000000ull + in.imm);
-            if (in.op == MS_OP_RPC_CALL) horizon = std::max<uint64_t>(horizon, (uint64_t)(in.imm >> 8) * 1000000ull);
-        }
-        if (horizon >= (1ull << 31) - (1ull << 24)) narrow_ok = false;
-    }
+    if (horizon(w, cfg, OPS_SLEEP_ANY, true) >= HORIZON_8_BYTE) narrow_ok = false;
     P.narrow = 0; P.pool_n = 0; P.pool_off = 0; P.off_pmask = 0;
     bool use_narrow = false;
     // delivery records of a narrow heap: a quarter of the heap's capacity (in-flight datagrams are a fifth of its entries), 32 .. 256
@@ -481,6 +487,8 @@ inline int make_geometry(const Device& g, const madsim_workload_t* w, const mads
     if (!P.lifecycle && P.mbox_msgs > 127) return fail(err, MADSIM_E_LIMITS, "mbox_msgs must be <= 127 for workloads without extended ops");
     const uint32_t task_bytes = P.lifecycle ? P.task_units * 16 : 24;
     const uint32_t heap_bytes = P.lifecycle ? 16 : 12;        // base ops: {deadline 8, meta 4}, no payload word (k_timer.h)
+    bool gregs = ops.any(OPS_GFLAG);
+    for (uint32_t i = 0; i < w->n_insns; i++) gregs |= w->insns[i].op == MS_OP_PANIC && (w->insns[i].a & 1);   // panic!("{}", flag)
     for (int pass = 0; pass < 3; pass++) {
         if (!P.lifecycle && P.max_tasks < P.n_progs) P.max_tasks = P.n_progs;   // handle words live in task slots there
         // the ready queue lives in a register in the (base ops, <= 8 tasks, full 64-lane waves) builds: lay out with it
@@ -495,14 +503,12 @@ inline int make_geometry(const Device& g, const madsim_workload_t* w, const mads
         // (signal builds' workloads only: one more mask behind the base-time word, "a ctrl-c handler is installed" — k_state.h NODE_SIGW)
         P.off_clog = P.off_nodes + (P.lifecycle ? 4 + (P.n_nodes + 4) / 4 + 1 + (signals ? 1 : 0) : 0);   // + the base-time word
         P.off_pause = P.off_clog + (P.has_clog ? 2 + (P.has_clog_link ? P.n_nodes + 1 : 0) : 0);
-        P.uses_pause = uses_op(w, MS_OP_PAUSE);
+        P.uses_pause = ops.has(MS_OP_PAUSE);
         P.off_greg = P.off_pause + (P.uses_pause ? 1 + P.max_tasks : 0);
-        bool gregs = uses_op(w, MS_OP_GSET) || uses_op(w, MS_OP_GADD) || uses_op(w, MS_OP_ASSERT_G) || uses_op(w, MS_OP_PANIC_IF_G_LT);
-        for (uint32_t i = 0; i < w->n_insns; i++) gregs |= w->insns[i].op == MS_OP_PANIC && (w->insns[i].a & 1);   // panic!("{}", flag)
         P.off_conn = P.off_greg + (gregs ? 4 : 0);
         P.off_hooks = P.off_conn + (P.uses_chan ? P.max_conns * P.conn_words : 0);
         P.off_ipvs = P.off_hooks + (P.uses_hooks ? P.n_nodes + 1 : 0);
-        P.ipvs_dyn = uses_op(w, MS_OP_IPVS);
+        P.ipvs_dyn = ops.has(MS_OP_IPVS);
         P.lane_words = P.off_ipvs + P.n_services * (P.ipvs_dyn ? 2 : 1);
         if (P.gstate_mode) {           // the planes just laid out go to the global block; LDS keeps the ready queue only
             P.gs_plane_words = P.lane_words;
@@ -605,15 +611,8 @@ inline int make_geometry(const Device& g, const madsim_workload_t* w, const mads
     P.compact = 0;
     uint32_t heap_n = P.heap_lds, heap_b = P.narrow ? 8u : heap_bytes, task_n = P.max_tasks;
     {
-        uint64_t horizon = std::max<uint64_t>(cfg->lat_hi_ns, 1000000ull);
-        if (cfg->buggify) horizon = ~0ull;
-        for (uint32_t i = 0; i < w->n_insns; i++) {
-            const madsim_insn_t& in = w->insns[i];
-            if (in.op == MS_OP_SLEEP || in.op == MS_OP_SLEEP_RAND)
-                horizon = std::max<uint64_t>(horizon, (uint64_t)in.b * 1000000000ull + in.imm);
-        }
         const bool can = !P.lifecycle && !trace && !P.gstate_mode && lw == 64 && P.rq_in_reg && P.heap_spill == 0 && P.heap_lds >= 2 &&
-                         P.max_tasks >= 2 && horizon < (1ull << 31) - (1ull << 24) && !L.lanes_per_wave;
+                         P.max_tasks >= 2 && !cfg->buggify && horizon(w, cfg, OPS_SLEEP_BASE, false) < HORIZON_8_BYTE && !L.lanes_per_wave;
         if (state_mem == MADSIM_STATE_COMPACT && !can)
             return fail(err, MADSIM_E_LIMITS, "state_mem = 3 (compact): base-op workloads on full waves with <= 8 tasks, no heap spill, no buggify and sleeps below 2.1 s only");
         if (can && state_mem != MADSIM_STATE_LDS) {

@@ -82,6 +82,41 @@ def geometry_params(workload, limits=None):
     return dict(zip(names, kp))
 
 
+class HostPlan(C.Structure):
+    """madsim_emu_host_plan_t (emu_driver.cpp)."""
+    _fields_ = [("validate_rc", C.c_int32), ("geometry_rc", C.c_int32), ("tables_rc", C.c_int32), ("kparams_bytes", C.c_int32),
+                ("validate_msg", C.c_char_p), ("geometry_msg", C.c_char_p), ("tables_msg", C.c_char_p),
+                ("lds_bytes", C.c_uint32), ("lds_per_seed", C.c_uint32), ("blocks_per_cu", C.c_uint32), ("grid", C.c_uint32),
+                ("lanes_per_wave", C.c_uint32), ("waves_per_block", C.c_uint32),
+                ("kparams", C.c_void_p), ("table", C.c_void_p * 5), ("table_bytes", C.c_uint64 * 5)]
+
+
+GEO_SCALARS = ("lds_bytes", "lds_per_seed", "blocks_per_cu", "grid", "lanes_per_wave", "waves_per_block")
+TABLES = ("insns", "progs", "socks", "nodes", "durs")
+
+
+def host_plan(wref, cfg, lim, count=65, trace=False, vgprs_hint=0, tables=True):
+    """What validate, make_geometry and build_tables (geometry.h) answer for one launch: {"validate": (rc, msg)}, and for a workload validate
+    accepts "geometry": (rc, msg), "tables": (rc, msg) — rc 0 brings "geo" (every scalar of Geo), "kparams" (the parameter block's bytes) and
+    "table" (the five device tables' bytes; tables=False leaves them out).  `wref`: a pointer to a madsim_workload_t."""
+    L = lib()
+    L.madsim_emu_host_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.POINTER(HostPlan)]
+    L.madsim_emu_host_plan.restype = None
+    p = HostPlan()
+    L.madsim_emu_host_plan(wref, C.byref(cfg), C.byref(lim) if lim is not None else None, count, int(trace), vgprs_hint, C.byref(p))
+    out = {"validate": (p.validate_rc, p.validate_msg.decode())}
+    if p.validate_rc:
+        return out
+    out["geometry"] = (p.geometry_rc, p.geometry_msg.decode())
+    out["tables"] = (p.tables_rc, p.tables_msg.decode())
+    if p.geometry_rc == 0:
+        out["geo"] = tuple(getattr(p, f) for f in GEO_SCALARS)
+        out["kparams"] = C.string_at(p.kparams, p.kparams_bytes)
+    if p.tables_rc == 0 and tables:
+        out["table"] = tuple(C.string_at(p.table[i], p.table_bytes[i]) if p.table_bytes[i] else b"" for i in range(5))
+    return out
+
+
 def trace_seed(workload, seed, config=None, limits=None, cap=1 << 20):
     cfg = config or A.Config.default()
     lim = limits or A.Limits()

@@ -289,6 +289,46 @@ extern "C" int madsim_emu_geometry(const madsim_workload_t* w, const madsim_limi
     return 0;
 }
 
+// Everything the host planner decides for one launch, for tests/test_host_plan.py: validate's verdict, then — for a workload it accepts —
+// make_geometry's verdict with every scalar of Geo and the raw bytes of its parameter block (memset first, so padding and the still-null
+// pointers are deterministic; Geo itself is zeroed here), and build_tables' verdict with its five vectors.  The pointers stay valid until
+// this thread's next call.  vgprs_hint: 0 leaves Device::vgprs null, any other value is what a stub reports for every build.
+struct madsim_emu_host_plan_t {
+    int32_t validate_rc, geometry_rc, tables_rc, kparams_bytes;
+    const char *validate_msg, *geometry_msg, *tables_msg;
+    uint32_t lds_bytes, lds_per_seed, blocks_per_cu, grid, lanes_per_wave, waves_per_block;
+    const uint8_t* kparams;
+    const void* table[5];          // insns, progs, socks, nodes, durs
+    uint64_t table_bytes[5];
+};
+static thread_local int plan_vgprs;
+extern "C" void madsim_emu_host_plan(const madsim_workload_t* w, const madsim_config_t* cfg, const madsim_limits_t* lim, uint64_t count, int trace,
+                                     int vgprs_hint, madsim_emu_host_plan_t* out) {
+    static thread_local std::string msg[3];
+    static thread_local madsim_geo::Geo G;
+    static thread_local madsim_geo::DeviceTables T;
+    memset(out, 0, sizeof *out);
+    for (auto& m : msg) m.clear();
+    memset(&G, 0, sizeof G);
+    T = madsim_geo::DeviceTables();
+    out->validate_rc = madsim_geo::validate(w, cfg, &msg[0]);
+    out->geometry_rc = out->tables_rc = 1;          // (not run)
+    if (out->validate_rc == 0) {
+        madsim_geo::Device dev;
+        plan_vgprs = vgprs_hint;
+        if (vgprs_hint) dev.vgprs = [](const madsim_k::VariantSel*) { return plan_vgprs; };
+        out->geometry_rc = madsim_geo::make_geometry(dev, w, cfg, lim, count, &G, &msg[1], trace != 0);
+        out->tables_rc = madsim_geo::build_tables(w, &T, &msg[2]);
+    }
+    out->validate_msg = msg[0].c_str(); out->geometry_msg = msg[1].c_str(); out->tables_msg = msg[2].c_str();
+    out->lds_bytes = G.lds_bytes; out->lds_per_seed = G.lds_per_seed; out->blocks_per_cu = G.blocks_per_cu; out->grid = G.grid;
+    out->lanes_per_wave = G.lanes_per_wave; out->waves_per_block = G.waves_per_block;
+    out->kparams = (const uint8_t*)&G.P; out->kparams_bytes = (int32_t)sizeof(madsim_k::KParams);
+    const void* p[5] = {T.insns.data(), T.progs.data(), T.socks.data(), T.nodes.data(), T.durs.data()};
+    const uint64_t n[5] = {T.insns.size() * 4, T.progs.size() * 4, T.socks.size() * 4, T.nodes.size() * 4, T.durs.size() * 8};
+    for (int i = 0; i < 5; i++) { out->table[i] = p[i]; out->table_bytes[i] = n[i]; }
+}
+
 // selected KParams of the geometry a workload gets (tools/gstate_access_model.py)
 extern "C" int madsim_emu_geometry_params(const madsim_workload_t* w, const madsim_limits_t* lim, uint32_t* out32) {
     madsim_config_t cfg = madsim_geo::probe_config();
