@@ -101,6 +101,67 @@ __device__ __forceinline__ void ipvs_rewrite(const Ctx& c, uint32_t& idx, uint32
 // Mailbox::deliver (endpoint.rs:331-351)
 // `pf` (global-state builds): the socket's header word and first registration, loaded by timer_expire before the pop's sift
 struct DeliverPrefetch { uint32_t hdr, reg0; };
+// Is the task a registration names still in that receive?  `f_`, `link_` = its flag word and link word; `g8_`, `rxseq_` = the registration's generation
+// and receive sequence number.  The general delivery's test, and what the host-compiled kernel holds the short delivery's own against
+// (mailbox_deliver_one).  (A macro: as a function the same four parts compile to another branch in every build.)
+#define RECEIVER_LIVE(f_, link_, g8_, rxseq_) (((f_) & TF_ALIVE) && (((f_) >> 8) & 0xff) == (g8_) && ((link_) & 0xff) == (rxseq_) && !((f_) & TF_INBOX))
+
+// Mailbox::deliver into a mailbox of one registration and no message queue (k_state.h mbox_one; `h` = the live socket's header word): the one
+// registration is the whole scan, removing it moves nothing, and a message nobody takes has no queue to wait in — with mbox_msgs = 0, below the
+// model's ceiling, that is the capacity verdict the general form raises.  Loads before stores, as there.
+template <class K>
+__device__ __forceinline__ void mailbox_deliver_one(const Ctx& c, Lane& L, uint32_t s, uint32_t h, uint32_t from, uint32_t tag, uint32_t val) {
+    const uint32_t nreg = (h >> 9) & 0xff;
+    // the receiver's liveness, the general form's four parts (RECEIVER_LIVE): alive, of the registration's generation, in that receive, its oneshot
+    // empty — written out here, so that the host-compiled kernel can hold this form against the one the general delivery runs
+    auto receives = [](uint32_t f, uint32_t link, uint32_t g8, uint32_t rxseq) {
+        return (f & TF_ALIVE) && ((f >> 8) & 0xff) == g8 && (link & 0xff) == rxseq && !(f & TF_INBOX);
+    };
+#ifdef MADSIM_EMU
+    if (HDR_NMSG(h) != 0 || nreg > 1) OVF_SET(L, OVF_BUG);         // what the two limits keep true of every header
+#endif
+    bool taken = false;
+    if (nreg == 1) {
+        const uint32_t r = SW(c, s, 2);
+        if ((r & 0xff) == tag) {
+            const uint32_t slot = (r >> 8) & 0xff, rxseq = (r >> 16) & 0xff, g8 = r >> 24;
+            uint4 u0 = TU(c, slot, 0);
+            const uint32_t link = TWORD(c, slot, 1, 0);
+#ifdef MADSIM_EMU
+            // The general arithmetic on the same inputs: the scan stops at i = 0, the decrement leaves nreg = 0 = i, so swap_remove's entry to move is
+            // the entry itself; its liveness test (RECEIVER_LIVE, the text the general delivery runs) — held against the short one here and one
+            // bit away in each of its four parts, which the base ops themselves never reach (a task with a pending receive does not end) — and,
+            // below, the words it stores.
+            {
+                const uint32_t i = 0, n = nreg - 1, moved = (uint32_t)SW(c, s, 2 + n);
+                const uint32_t fs[5] = {u0.x, u0.x ^ TF_ALIVE, u0.x ^ 0x100u, u0.x, u0.x ^ TF_INBOX}, ls[5] = {link, link, link, link ^ 1u, link};
+                bool same = i == n && moved == r;
+                for (int k = 0; k < 5; k++) same = same && receives(fs[k], ls[k], g8, rxseq) == RECEIVER_LIVE(fs[k], ls[k], g8, rxseq);
+                if (!same) OVF_SET(L, OVF_BUG);
+            }
+            const uint4 g0 = make_uint4(u0.x | TF_INBOX | TF_SCHED, (u0.y & 0x00ffffffu) | (from << 24), u0.z, val);
+            const uint32_t gh = (h & ~(0xffu << 9)) | ((nreg - 1) << 9);
+#endif
+            if (receives(u0.x, link, g8, rxseq)) {
+                // oneshot::Sender::send Ok -> value stored, receiver task woken [DEP tokio oneshot]
+                const bool sched = u0.x & TF_SCHED;
+                u0.x |= TF_INBOX | TF_SCHED;
+                u0.y = (u0.y & 0x00ffffffu) | (from << 24);
+                u0.w = val;
+                TU(c, slot, 0) = u0;
+                SW(c, s, 0) = h & ~(0xffu << 9);
+                if (!sched && !(u0.x & TF_RUN)) ready_push<K>(c, L, slot);
+                taken = true;
+#ifdef MADSIM_EMU
+                const uint4 w0 = TU(c, slot, 0);
+                if (w0.x != g0.x || w0.y != g0.y || w0.z != g0.z || w0.w != g0.w || (uint32_t)SW(c, s, 0) != gh || (uint32_t)SW(c, s, 2) != r) OVF_SET(L, OVF_BUG);
+#endif
+            }
+        }
+    }
+    if (!taken) OVF_SET(L, OVF_CAP);
+}
+
 template <class K>
 __device__ __forceinline__ void mailbox_deliver(const Ctx& c, Lane& L, uint32_t meta, uint32_t val, const DeliverPrefetch* pf = nullptr) {
     uint32_t s = meta & 0x3f, from = (meta >> 6) & 0x7f, tag = (meta >> 13) & 0xff, sgen = (meta >> 21) & 0xff;
@@ -114,7 +175,9 @@ __device__ __forceinline__ void mailbox_deliver(const Ctx& c, Lane& L, uint32_t 
     // BindGuard dropped — `if self.node.is_killed() { return }`, net/mod.rs:483-493 — and TaskHandle::restart resets no sockets): the
     // EndpointSocket stays in the table and its mailbox still takes a message for a receive that some OTHER holder of the Endpoint
     // registered; with nobody left to register one, a message is dropped instead of queued for ever.
-    if (live) {
+    if (mbox_one<K>(c)) {                                // (a scalar test: base-op builds, one registration per mailbox, no message queue)
+        if (live) mailbox_deliver_one<K>(c, L, s, h, from, tag, val);
+    } else if (live) {
         uint32_t nreg = (h >> 9) & 0xff, nmsg = HDR_NMSG(h);
         // Typed RPC (net/rpc.rs): a response (tag 0xff) is addressed to one pending receive — the word of its registration,
         // tag | slot | rxseq | gen, rides in the payload's upper 24 bits — where the reference matches a random u64 tag.
@@ -144,7 +207,7 @@ __device__ __forceinline__ void mailbox_deliver(const Ctx& c, Lane& L, uint32_t 
                 uint32_t link = TWORD(c, slot, 1, 0);
                 if (!last) SW(c, s, 2 + i) = moved;
                 if (K::G) { known = true; r_known = moved; }
-                if ((u0.x & TF_ALIVE) && ((u0.x >> 8) & 0xff) == g8 && (link & 0xff) == rxseq && !(u0.x & TF_INBOX)) {
+                if (RECEIVER_LIVE(u0.x, link, g8, rxseq)) {
                     // oneshot::Sender::send Ok -> value stored, receiver task woken [DEP tokio oneshot]
                     bool sched = u0.x & TF_SCHED;
                     u0.x |= TF_INBOX | TF_SCHED;
@@ -162,17 +225,24 @@ __device__ __forceinline__ void mailbox_deliver(const Ctx& c, Lane& L, uint32_t 
                 i++;
             }
         }
+        uint32_t msgs = 0;                                 // (builds with the short side: each capacity is ONE load from the kernel-argument segment; the others keep their text)
         if (taken) {
             SW(c, s, 0) = (h & ~(0xffu << 9)) | (nreg << 9);
         } else if (K::LIFE && SW(c, s, 1) == ~0u) {              // (the owner word is read only when nobody took the message)
             SW(c, s, 0) = (h & ~(0xffu << 9)) | (nreg << 9);      // (dead registrations swept on the way stay swept)
-        } else if (nmsg >= c.P.mbox_msgs) {
+        } else if (MboxOne<K>::ON ? nmsg >= (msgs = mbox_msgs_of<K>(c)) : nmsg >= c.P.mbox_msgs) {
             // (short of the ceiling of 255 queued messages a larger mbox_msgs lifts it; AT the ceiling the 256th leaves the model)
-            OVF_SET(L, c.P.mbox_msgs >= MADSIM_MAX_MBOX_MSGS ? OVF_MODEL : OVF_CAP);
+            OVF_SET(L, (MboxOne<K>::ON ? msgs : c.P.mbox_msgs) >= MADSIM_MAX_MBOX_MSGS ? OVF_MODEL : OVF_CAP);
         } else {
             if (rsp) tag = 0xfe;                           // nobody holds that rsp_tag any more: it can never be received
-            SW(c, s, 2 + c.P.mbox_regs + 2 * nmsg) = tag | (from << 8);
-            SW(c, s, 2 + c.P.mbox_regs + 2 * nmsg + 1) = val;
+            if constexpr (MboxOne<K>::ON) {                // (the other builds keep the text they had: a local there moves their instructions)
+                const uint32_t at = 2 + mbox_regs_of<K>(c) + 2 * nmsg;
+                SW(c, s, at) = tag | (from << 8);
+                SW(c, s, at + 1) = val;
+            } else {
+                SW(c, s, 2 + c.P.mbox_regs + 2 * nmsg) = tag | (from << 8);
+                SW(c, s, 2 + c.P.mbox_regs + 2 * nmsg + 1) = val;
+            }
             nmsg++;
             SW(c, s, 0) = (HDR_SET_NMSG(h, nmsg) & ~(0xffu << 9)) | (nreg << 9);
         }

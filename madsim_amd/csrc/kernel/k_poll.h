@@ -721,34 +721,57 @@ __device__ __forceinline__ bool poll_task(const Ctx& c, Lane& L, const uint32_t 
                 if (rxseq == 0) u0.x |= TF_RXWRAP;
                 u0.x &= ~TF_INBOX;
                 uint32_t h = RecvPrefetch<K>::ON ? c_hdr : (uint32_t)SW(c, a, 0);
-                uint32_t nreg = (h >> 9) & 0xff, nmsg = HDR_NMSG(h);
-                uint32_t idx = 0, mbase = 2 + P.mbox_regs;
-                while (idx < nmsg && ((RecvPrefetch<K>::ON && idx == 0 ? c_q0 : (uint32_t)SW(c, a, mbase + 2 * idx)) & 0xff) != tag) idx++;
-                if (idx < nmsg) {
-                    uint32_t m0, m1;
-                    if (RecvPrefetch<K>::ON && idx == 0) { m0 = c_q0; m1 = c_q1; } else { m0 = SW(c, a, mbase + 2 * idx); m1 = SW(c, a, mbase + 2 * idx + 1); }
-                    nmsg--;
-                    if (!RecvPrefetch<K>::ON || idx != nmsg) {    // swap_remove (with the requests above: the last entry onto itself moves nothing)
-                        SW(c, a, mbase + 2 * idx) = SW(c, a, mbase + 2 * nmsg);
-                        SW(c, a, mbase + 2 * idx + 1) = SW(c, a, mbase + 2 * nmsg + 1);
-                    }
-                    u0.w = m1;
-                    if (K::FR && P.uses_rpc && tag >= MADSIM_TAG_RPC_FIRST) { u0.w = m1 & 0xff; RQ_SET(0, m1 >> 8); }
-                    from = (m0 >> 8) & 0xff;
-                    sub = 2;                               // oneshot already holds the value
-                    SW(c, a, 0) = HDR_SET_NMSG(h, nmsg);
-                } else {
-                    if (nreg >= P.mbox_regs) OVF_SET(L, REGS_FULL);          // (a runner verdict: the state no longer matters)
+                const uint32_t nreg = (h >> 9) & 0xff;
+                if (mbox_one<K>(c)) {
+                    // One registration, no message queue (k_state.h mbox_one; a scalar test): nothing is ever queued, so there is no scan and nothing to
+                    // take; the list is full with one entry, and the first entry's word is word 2.
+#ifdef MADSIM_EMU
+                    // (what the general arithmetic below makes of the same header: no queued message, `nreg >= mbox_regs` is `nreg != 0`, the
+                    //  registration at word 2 + nreg = 2, the header with nreg + 1 = 1, the capacity code)
+                    if (HDR_NMSG(h) != 0 || nreg > 1 || (nreg >= P.mbox_regs) != (nreg != 0) || REGS_FULL != (uint32_t)OVF_CAP) OVF_SET(L, OVF_BUG);
+#endif
+                    if (nreg != 0) OVF_SET(L, OVF_CAP);                      // (a runner verdict: the state no longer matters)
                     else {
                         const uint32_t reg = tag | (slot << 8) | (rxseq << 16) | ((gen & 0xff) << 24);
-                        // dead registrations (timed-out / dropped receives, extended ops only) stay in the Vec like the
-                        // reference's; an 8-bit rxseq that wraps onto one of them would make it look live: overflow, never a different answer
-                        if ((K::FT || K::FN || K::FS) && may_have_twin(u0.x, gen)) for (uint32_t i = 0; i < nreg; i++) if (SW(c, a, 2 + i) == reg) OVF_SET(L, OVF_MODEL);
-                        SW(c, a, 2 + nreg) = reg;
-                        SW(c, a, 0) = (h & ~(0xffu << 9)) | ((nreg + 1) << 9);
+                        SW(c, a, 2) = reg;
+                        SW(c, a, 0) = h | (1u << 9);
                         sub = 1;
+#ifdef MADSIM_EMU
+                        if ((uint32_t)SW(c, a, 2 + nreg) != reg || (uint32_t)SW(c, a, 0) != ((h & ~(0xffu << 9)) | ((nreg + 1) << 9))) OVF_SET(L, OVF_BUG);
+#endif
                     }
                     st = ST_PENDING;
+                } else {
+                    uint32_t nmsg = HDR_NMSG(h);
+                    const uint32_t regs = mbox_regs_of<K>(c);
+                    uint32_t idx = 0, mbase = 2 + regs;
+                    while (idx < nmsg && ((RecvPrefetch<K>::ON && idx == 0 ? c_q0 : (uint32_t)SW(c, a, mbase + 2 * idx)) & 0xff) != tag) idx++;
+                    if (idx < nmsg) {
+                        uint32_t m0, m1;
+                        if (RecvPrefetch<K>::ON && idx == 0) { m0 = c_q0; m1 = c_q1; } else { m0 = SW(c, a, mbase + 2 * idx); m1 = SW(c, a, mbase + 2 * idx + 1); }
+                        nmsg--;
+                        if (!RecvPrefetch<K>::ON || idx != nmsg) {    // swap_remove (with the requests above: the last entry onto itself moves nothing)
+                            SW(c, a, mbase + 2 * idx) = SW(c, a, mbase + 2 * nmsg);
+                            SW(c, a, mbase + 2 * idx + 1) = SW(c, a, mbase + 2 * nmsg + 1);
+                        }
+                        u0.w = m1;
+                        if (K::FR && P.uses_rpc && tag >= MADSIM_TAG_RPC_FIRST) { u0.w = m1 & 0xff; RQ_SET(0, m1 >> 8); }
+                        from = (m0 >> 8) & 0xff;
+                        sub = 2;                               // oneshot already holds the value
+                        SW(c, a, 0) = HDR_SET_NMSG(h, nmsg);
+                    } else {
+                        if (nreg >= regs) OVF_SET(L, REGS_FULL);          // (a runner verdict: the state no longer matters)
+                        else {
+                            const uint32_t reg = tag | (slot << 8) | (rxseq << 16) | ((gen & 0xff) << 24);
+                            // dead registrations (timed-out / dropped receives, extended ops only) stay in the Vec like the
+                            // reference's; an 8-bit rxseq that wraps onto one of them would make it look live: overflow, never a different answer
+                            if ((K::FT || K::FN || K::FS) && may_have_twin(u0.x, gen)) for (uint32_t i = 0; i < nreg; i++) if (SW(c, a, 2 + i) == reg) OVF_SET(L, OVF_MODEL);
+                            SW(c, a, 2 + nreg) = reg;
+                            SW(c, a, 0) = (h & ~(0xffu << 9)) | ((nreg + 1) << 9);
+                            sub = 1;
+                        }
+                        st = ST_PENDING;
+                    }
                 }
             }
             want_delay = (sub == 2);                       // endpoint.rs:145 rand_delay

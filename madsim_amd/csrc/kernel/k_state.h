@@ -128,11 +128,17 @@ template <bool ON, class T> __device__ __forceinline__ T cold_read(const T& hot,
 #endif
 // for (i = start; i < P.f; i++) with a cold bound: read once where the loop begins in the builds with cold parameters, the loop as it was written in the others
 #define PCOLD_FOR(i_, start_, f_) for (uint32_t i_ = (start_), i_##_n = ColdParams<K>::ON ? PCOLD(f_) : 0u; i_ < (ColdParams<K>::ON ? i_##_n : P.f_); i_++)
+// One-slot, queue-less mailboxes (sim_kernel.h MADSIM_MBOX_ONE): mbox_one<K>(c) is the scalar test of the two launch parameters behind which the
+// base-op builds deliver (k_net.h mailbox_deliver_one) and register (k_poll.h MS_OP_RECV) in straight lines.  A mailbox then holds 0 or 1
+// registrations (the second is refused) and never a queued message (mbox_msgs = 0 refuses the first).
+template <class K> struct MboxOne { static constexpr bool ON = MADSIM_MBOX_ONE && !K::LIFE; };
 // Wave-uniform yes/no parameters tested on the send path (has_clog, has_clog_link, buggify): held by value each is a 64-bit lane mask; the builds with
 // cold parameters keep the three as bits of ONE scalar word (Ctx::uflags, made opaque where the kernel begins so that it stays one word) and test a bit.
-enum : uint32_t { UF_CLOG = 1, UF_CLOG_LINK = 2, UF_BUGGIFY = 4 };
+// (UF_MBOX_ONE: mbox_one's answer, a bit of the same word — as a test of its own it cost the headline build two scalars parked in vector lanes.)
+enum : uint32_t { UF_CLOG = 1, UF_CLOG_LINK = 2, UF_BUGGIFY = 4, UF_MBOX_ONE = 8 };
 __device__ __forceinline__ uint32_t uflags_word(const KParams& P) {
     uint32_t f = (P.has_clog ? (uint32_t)UF_CLOG : 0u) | (P.has_clog_link ? (uint32_t)UF_CLOG_LINK : 0u) | (P.buggify ? (uint32_t)UF_BUGGIFY : 0u);
+    if (MADSIM_MBOX_ONE && P.mbox_regs == 1 && P.mbox_msgs == 0) f |= UF_MBOX_ONE;
 #ifndef MADSIM_EMU
     f = wave_uniform(f);
     asm volatile("" : "+s"(f));
@@ -248,6 +254,21 @@ template <class K> __device__ __forceinline__ bool uflag(const Ctx& c, uint32_t 
     } else
 #endif
     return hot != 0;
+}
+template <class K> __device__ __forceinline__ bool mbox_one(const Ctx& c) {
+    if constexpr (!MboxOne<K>::ON) return false;
+    else return uflag<K>(c, c.P.mbox_regs == 1 && c.P.mbox_msgs == 0, UF_MBOX_ONE);
+}
+// (the two capacities in those builds: the short side reads neither, so the general side reads them where it uses them — PCOLD above.  Held by value
+//  they took the scalar registers whose want showed as launch constants parked in a vector lane: two in the headline build, one or two in the three
+//  builds with a spill region.)
+template <class K> __device__ __forceinline__ uint32_t mbox_msgs_of(const Ctx& c) {
+    const KParams& P = c.P;
+    if constexpr (MboxOne<K>::ON) return PCOLD(mbox_msgs); else return P.mbox_msgs;
+}
+template <class K> __device__ __forceinline__ uint32_t mbox_regs_of(const Ctx& c) {
+    const KParams& P = c.P;
+    if constexpr (MboxOne<K>::ON) return PCOLD(mbox_regs); else return P.mbox_regs;
 }
 template <class K> __device__ __forceinline__ uint32_t LWSH(const Ctx& c) { return K::LWS >= 0 ? (uint32_t)K::LWS : c.lws; }
 #define RW(i) SMEM[c.ready0 + ((i) << LWSH<K>(c))]

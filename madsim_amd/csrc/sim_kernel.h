@@ -78,6 +78,12 @@
 #ifndef MADSIM_COLD_PARAMS
 #define MADSIM_COLD_PARAMS 1
 #endif
+/* Base-op builds: a launch whose mailboxes hold ONE registration and queue no message (mbox_regs = 1, mbox_msgs = MADSIM_LIMIT_NONE: the benchmark's
+   limits, the compact layout's usual ones) delivers and registers in straight lines — no registration scan, no swap_remove of an entry onto itself, no
+   message queue — behind one scalar test of the two launch parameters (k_state.h MboxOne; k_net.h mailbox_deliver_one, k_poll.h MS_OP_RECV). */
+#ifndef MADSIM_MBOX_ONE
+#define MADSIM_MBOX_ONE 1
+#endif
 /* MADSIM_STATE_DEDUP_TIMERS builds: the occupancy of the re-registration table mirrored in a register (k_timer.h dedup_note). */
 #ifndef MADSIM_DEDUP_OCC
 #define MADSIM_DEDUP_OCC 1
